@@ -3,7 +3,9 @@
 2048^2 render of the 512^3-base 3-level AMR scene (config-4 of SURVEY.md 8d), translucent
 transfer function (box_transparency 0.97: full traversal, the throughput regime).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line; --full adds the
+figures that take runs or checks of their own (roofline, latency, CPU baseline, self-check).
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU over RCCL); started
 bare (no WORLD_SIZE in the environment) it launches those N ranks itself, as child processes and
 before anything in this process touches the GPU, relays rank 0's JSON line and exits with the
@@ -42,6 +44,15 @@ def parse_args():
     ap.add_argument("--ownership", default="level_pairs", choices=["morton", "morton_cost", "morton_pairs", "level_pairs", "round_robin",
                              "block"])
     ap.add_argument("--antialiasing", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the roofline of the paint stage "
+                         "(one more frame, the committed PMC traffic), the sample-count self-check, "
+                         "the `latency` figures and the CPU baseline (each of the last two can be "
+                         "left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32; a fixed seeded sample of pixels where "
+                         "the whole frame exceeds 60 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=60.0,
                     help="cap of the cpu_baseline leg's CPU time (config-4 needs ~35 s for its "
@@ -108,7 +119,10 @@ def parse_args():
     ap.add_argument("--rehearse-python-pipeline", action="store_true",
                     help="with --rehearse-on-one-gpu: the torch.distributed frame loop over gloo "
                          "through host copies instead of the C++ driver")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 CONFIG_IMAGE = {"config1": (256, 256), "config2": (1024, 1024), "config3": (2048, 2048),
@@ -269,6 +283,32 @@ def latency(ctx, spec, all_boxes, local_boxes, rparams, cameras):
             "first_frame_with_allocations_ms": round(singles[0], 3),
             "first_100_frames_mean_ms": round(mean_100, 4),
             "frames_to_settle": settled_at, "settled_on": corun}
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # (the budget of a dump is 64 MB, headers included)
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: `outputs` maps a name to a frame's array [H, W, C] (the rgb8 bytes, and the
+    depth-sort image where the path returns one) and each is written as DIR/<name>.npy in float32,
+    which holds the bytes and the f32 pixels exactly.  Where the whole frames would exceed 60 MB,
+    every array keeps the same fixed sample of pixels (seed 0, sorted) as [n, C], and
+    DIR/pixel_index.npy (float64) says which pixels of the row-major frame those are."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: value.cpu().numpy() for name, value in outputs.items()}
+    height, width = next(iter(arrays.values())).shape[:2]
+    pixels = height * width
+    per_pixel = 4 * sum(a.shape[2] for a in arrays.values())
+    index = None
+    if pixels * per_pixel > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_pixel + 8)
+        index = np.sort(np.random.default_rng(0).choice(pixels, size=keep, replace=False))
+        np.save(os.path.join(directory, "pixel_index.npy"), index.astype(np.float64))
+    for name, value in arrays.items():
+        if index is not None:
+            value = value.reshape(pixels, -1)[index]
+        np.save(os.path.join(directory, f"{name}.npy"), value.astype(np.float32))
 
 
 PMC_DIR = os.path.join("profiles", "r5_final")
@@ -538,7 +578,7 @@ def run(args, state):
     default_scene = (args.config == "config4" and args.field == "smooth" and not args.width
                      and not args.height and args.transparency == 0.97 and args.antialiasing == 1
                      and args.orbit == 0 and not args.fly_through)
-    if default_scene and not args.no_self_check:
+    if args.full and default_scene and not args.no_self_check:
         # the ranks' shares of the frame add up to the one-rank frame's samples, whatever N
         # (the count tests/test_full_size_gpu.py checks against the oracle)
         checks["samples_sum_equals_one_rank_frame"] = frame_samples[0] == 759136367
@@ -681,8 +721,9 @@ def run(args, state):
         t0 = float(start.item())
         while time.monotonic() < t0:
             pass
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(i, timed=True)
+    last_outputs = step(args.steps - 1, timed=True)   # (what --dump-outputs writes)
     renderer.synchronize()
     torch.cuda.synchronize()
     # this rank's K frames are complete (every frame is a collective, so they are complete on every
@@ -736,51 +777,58 @@ def run(args, state):
     ms_per_step = elapsed * 1e3 / args.steps
     value = samples_total / elapsed / 1e6
 
-    # ---- roofline of the paint stage (classify_kernel + render_runs_kernel, launched back to
-    # back by one avr_render_plan call), this rank's launch ----------------------------------
-    # algorithmic bytes per launch = 8 B per executed cell fetch (one amrex::Real) + 20 B per
-    # emitted layer pixel; samples of THIS rank's launch:
-    samples_dev.zero_()
-    renderer.render(rparams, cameras[0], samples=samples_dev)
-    renderer.synchronize()
-    my_samples = int(samples_dev.item())
-    if args.fly_through and world == 1:   # the timed frames' own average, not the first view's
-        my_samples = round(sum(frame_samples) / len(frame_samples))
-    n_pixels = params.width * params.height
-    send_floats = renderer.last_plan.send_floats   # (N > 1: the tightened layout by now)
-    algo_bytes = 8.0 * my_samples + 4.0 * send_floats
-    achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-    traffic, traffic_source = profiled_traffic(args, world)
-    # (a speculating driver -- one rank, a standing camera, at most 85 % of the boxes sampled:
-    # the opaque regime -- classifies only the boxes an earlier frame's rays sampled; the boxes of
-    # BASELINE's configurations are all of one size, so the fraction of boxes is that of the cells)
-    speculation = renderer.native.speculation_state() if native else None
-    classified_fraction = (speculation["sampled_fraction"]
-                           if speculation and speculation["state"] == "speculating"
-                           and speculation["sampled_fraction"] is not None else 1.0)
-    roofline = {
-        "bound": "hbm", "kernel": "classify_kernel + render_runs_kernel (the paint stage of one frame)",
-        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        # `frac` is the ALGORITHMIC fraction the task defines (8 B per sample + 20 B per stored
-        # layer pixel over the paint stage's GPU time).  The kernels move far fewer bytes -- the
-        # f64 cells are read once per frame by the classify pass and the march gathers one
-        # classified byte per sample from cache -- so the fraction of the HBM peak the MEASURED
-        # traffic amounts to is reported beside it and the two must be quoted together.
-        "frac": round(achieved / HBM_PEAK_GBS, 5), "algorithmic_frac": round(achieved / HBM_PEAK_GBS, 5),
-        "traffic": traffic, "traffic_source": traffic_source,
-        "traffic_frac": (round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                         if traffic else None),
-        "kernel_ms": round(kernel_ms, 4), "classify_ms": round(classify_ms, 4),
-        "march_ms": round(march_ms, 4), "algorithmic_bytes": int(algo_bytes),
-        "samples_this_rank": my_samples,
-        "classified_fraction": classified_fraction,
-        "compulsory_bytes": int(sum(b.values.numel() for b in local_boxes) * 8 * classified_fraction
-                                + 4 * send_floats),
-    }
-    # the third reading SURVEY.md 8(d) asks for: what the frame cannot avoid moving (every f64 cell
-    # the frame's rays can reach once + the stored layer pixels) over the same kernel time
-    roofline["compulsory_frac"] = round(
-        roofline["compulsory_bytes"] / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+    if args.dump_outputs and rank == 0:
+        image, rgb8 = last_outputs
+        dump_outputs(args.dump_outputs,
+                     {"rgb8": rgb8, **({"image": image} if image is not None else {})})
+
+    roofline = None
+    if args.full:
+        # ---- roofline of the paint stage (classify_kernel + render_runs_kernel, launched back to
+        # back by one avr_render_plan call), this rank's launch ----------------------------------
+        # algorithmic bytes per launch = 8 B per executed cell fetch (one amrex::Real) + 20 B per
+        # emitted layer pixel; samples of THIS rank's launch:
+        samples_dev.zero_()
+        renderer.render(rparams, cameras[0], samples=samples_dev)
+        renderer.synchronize()
+        my_samples = int(samples_dev.item())
+        if args.fly_through and world == 1:   # the timed frames' own average, not the first view's
+            my_samples = round(sum(frame_samples) / len(frame_samples))
+        n_pixels = params.width * params.height
+        send_floats = renderer.last_plan.send_floats   # (N > 1: the tightened layout by now)
+        algo_bytes = 8.0 * my_samples + 4.0 * send_floats
+        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+        traffic, traffic_source = profiled_traffic(args, world)
+        # (a speculating driver -- one rank, a standing camera, at most 85 % of the boxes sampled:
+        # the opaque regime -- classifies only the boxes an earlier frame's rays sampled; the boxes of
+        # BASELINE's configurations are all of one size, so the fraction of boxes is that of the cells)
+        speculation = renderer.native.speculation_state() if native else None
+        classified_fraction = (speculation["sampled_fraction"]
+                               if speculation and speculation["state"] == "speculating"
+                               and speculation["sampled_fraction"] is not None else 1.0)
+        roofline = {
+            "bound": "hbm", "kernel": "classify_kernel + render_runs_kernel (the paint stage of one frame)",
+            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            # `frac` is the ALGORITHMIC fraction the task defines (8 B per sample + 20 B per stored
+            # layer pixel over the paint stage's GPU time).  The kernels move far fewer bytes -- the
+            # f64 cells are read once per frame by the classify pass and the march gathers one
+            # classified byte per sample from cache -- so the fraction of the HBM peak the MEASURED
+            # traffic amounts to is reported beside it and the two must be quoted together.
+            "frac": round(achieved / HBM_PEAK_GBS, 5), "algorithmic_frac": round(achieved / HBM_PEAK_GBS, 5),
+            "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_frac": (round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                             if traffic else None),
+            "kernel_ms": round(kernel_ms, 4), "classify_ms": round(classify_ms, 4),
+            "march_ms": round(march_ms, 4), "algorithmic_bytes": int(algo_bytes),
+            "samples_this_rank": my_samples,
+            "classified_fraction": classified_fraction,
+            "compulsory_bytes": int(sum(b.values.numel() for b in local_boxes) * 8 * classified_fraction
+                                    + 4 * send_floats),
+        }
+        # the third reading SURVEY.md 8(d) asks for: what the frame cannot avoid moving (every f64 cell
+        # the frame's rays can reach once + the stored layer pixels) over the same kernel time
+        roofline["compulsory_frac"] = round(
+            roofline["compulsory_bytes"] / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
 
     corun_ranks = [renderer.native.corun_state() if native else None]
     if world > 1:
@@ -843,7 +891,7 @@ def run(args, state):
         },
         "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_latency and native:
+    if rank == 0 and world == 1 and args.full and not args.no_latency and native:
         # (the headline's renderer goes first: a second set of classified volumes beside it is
         # 1.1 GB for config-4, 11 GB for config-5)
         state.pop("renderer", None)
@@ -851,7 +899,7 @@ def run(args, state):
         out["latency"] = latency(ctx, spec, all_boxes, local_boxes, rparams, cameras)
         renderer = FrameRenderer(ctx, all_boxes, local_boxes, spec.transform, spec.bounds,
                                  spec.scalar_range, rank, world, group)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(spec, local_boxes, renderer, rparams, cameras[0],
                                            args.cpu_seconds, frame_samples[0])
     elif rank == 0:

@@ -1,12 +1,15 @@
 """CPU unit test of bench.py's self-launch: `python bench.py --gpus N` from a bare shell must
 start the N ranks as child processes with the driver's own torch.distributed.run command, relay
-exactly rank 0's JSON line and propagate a failure."""
+exactly rank 0's JSON line and propagate a failure; and the options of a plain run
+(--steps, --dump-outputs, --full)."""
 import importlib.util
 import json
 import os
 import subprocess
 import sys
 import types
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -116,3 +119,75 @@ def test_profiled_traffic_is_only_quoted_for_the_kernels_it_was_measured_on(tmp_
     args.orbit = 16                                                # not a profiled workload
     assert bench.profiled_traffic(args, 1) == (None, None)
     assert bench.workload_key(args, 2) is None
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    bench = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        bench.parse_args()
+    except SystemExit as stop:
+        assert stop.code == 2
+    else:
+        raise AssertionError("--steps 0 was accepted")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1"])
+    args = bench.parse_args()
+    assert args.steps == 3 and not args.full and args.dump_outputs is None
+
+
+def test_dump_outputs_keeps_whole_frames_and_samples_large_ones(tmp_path):
+    """--dump-outputs: float32 arrays that hold the frame's bytes and pixels exactly; above the
+    budget every array keeps the same fixed, seeded, sorted sample of pixels."""
+    import numpy as np
+    import torch
+    bench = load_bench()
+    rng = np.random.default_rng(5)
+    rgb8 = torch.from_numpy(rng.integers(0, 256, (64, 48, 3), dtype=np.uint8))
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), {"rgb8": rgb8})
+    assert sorted(os.listdir(small)) == ["rgb8.npy"]
+    got = np.load(small / "rgb8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgb8.numpy().astype(np.float32))
+
+    image = torch.from_numpy(rng.random((2048, 2048, 5), dtype=np.float32))
+    rgb8 = torch.from_numpy(rng.integers(0, 256, (2048, 2048, 3), dtype=np.uint8))
+    large = [tmp_path / "large_a", tmp_path / "large_b"]
+    for where in large:
+        bench.dump_outputs(str(where), {"rgb8": rgb8, "image": image})
+    assert sorted(os.listdir(large[0])) == ["image.npy", "pixel_index.npy", "rgb8.npy"]
+    assert sum(os.path.getsize(large[0] / name) for name in os.listdir(large[0])) <= 64e6
+    index = np.load(large[0] / "pixel_index.npy")
+    assert index.dtype == np.float64 and np.all(np.diff(index) > 0)
+    index = index.astype(np.int64)
+    assert np.array_equal(np.load(large[0] / "image.npy"), image.numpy().reshape(-1, 5)[index])
+    assert np.array_equal(np.load(large[0] / "rgb8.npy"),
+                          rgb8.numpy().reshape(-1, 3)[index].astype(np.float32))
+    for name in os.listdir(large[0]):   # the same sample every time
+        assert np.array_equal(np.load(large[0] / name), np.load(large[1] / name))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """`bench.py --steps K` without --full: the headline line only (no roofline, latency or CPU
+    baseline), K timed steps, and --dump-outputs writes the last timed frame's RGB8 bytes --
+    the same bytes in a second run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    lines, dumps = [], []
+    for run in range(2):
+        dump = tmp_path / f"dump{run}"
+        done = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "tiny",
+             "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert done.returncode == 0, done.stderr[-3000:]
+        found = [l for l in done.stdout.splitlines() if l.startswith('{"metric"')]
+        assert len(found) == 1, done.stdout
+        lines.append(json.loads(found[0]))
+        dumps.append(np.load(dump / "rgb8.npy"))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "latency" not in line
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (256, 256, 3)
+    assert dumps[0].any() and np.array_equal(dumps[0], dumps[1])

@@ -10,8 +10,8 @@ print('%-10s %-10s frame %.4f ms  classify %.4f  march %.4f  reserve %s' % ('$1'
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = tree ]; then unset AVR_HIP_LIBRARY; else export AVR_HIP_LIBRARY=$PWD/tools/_variants/$v.so; fi
-  python3 bench.py --no-cpu-baseline --no-latency --cache-classification --march-occupancy 0 --steps 200 2>/dev/null | line $v alone
-  python3 bench.py --no-cpu-baseline --no-latency --steps 200 --warmup 20 2>/dev/null | line $v pipelined
-  if [ -n "$AB_EXTRA" ]; then python3 bench.py --no-cpu-baseline --no-latency $AB_EXTRA 2>/dev/null | line $v extra; fi
+  python3 bench.py --full --no-cpu-baseline --no-latency --cache-classification --march-occupancy 0 --steps 200 2>/dev/null | line $v alone
+  python3 bench.py --full --no-cpu-baseline --no-latency --steps 200 --warmup 20 2>/dev/null | line $v pipelined
+  if [ -n "$AB_EXTRA" ]; then python3 bench.py --full --no-cpu-baseline --no-latency $AB_EXTRA 2>/dev/null | line $v extra; fi
 done
 done

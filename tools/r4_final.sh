@@ -12,9 +12,9 @@ if [ "$part" = kernels ] || [ "$part" = all ]; then
   timeout -k 10 1000 python3 -m pytest tests -m gpu -x -q > $out/pytest.txt 2>&1 || { tail -40 $out/pytest.txt; exit 1; }
   tail -2 $out/pytest.txt
   for i in 1 2 3; do
-    timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $out/bench_20_$i.json 2> $out/bench_20.err || { tail -20 $out/bench_20.err; exit 1; }
+    timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $out/bench_20_$i.json 2> $out/bench_20.err || { tail -20 $out/bench_20.err; exit 1; }
   done
-  timeout -k 10 400 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err || exit 1
   python3 -c "
 import json
 for f in ('bench_20_1','bench_20_2','bench_20_3','bench_200'):

@@ -16,9 +16,9 @@ if [ "$part" = kernels ]; then
   timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q > $out/pytest_gpu.txt 2>&1 || { tail -40 $out/pytest_gpu.txt; exit 1; }
   tail -2 $out/pytest_gpu.txt
   for i in 1 2 3; do
-    timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $out/bench_20_$i.json 2> $out/bench_20.err || { tail -20 $out/bench_20.err; exit 1; }
+    timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $out/bench_20_$i.json 2> $out/bench_20.err || { tail -20 $out/bench_20.err; exit 1; }
   done
-  timeout -k 10 400 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err || exit 1
   python3 -c "
 import json
 for f in ('bench_20_1','bench_20_2','bench_20_3','bench_200'):
@@ -45,7 +45,7 @@ if [ "$part" = regimes ]; then
   : > $out/regimes.txt
   run() {
     name=$1; shift
-    timeout -k 10 600 python3 bench.py --no-cpu-baseline --no-latency --steps 100 --warmup 10 "$@" > $out/regime_$name.json 2> $out/regime_$name.err || { tail -5 $out/regime_$name.err; return 1; }
+    timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --no-latency --steps 100 --warmup 10 "$@" > $out/regime_$name.json 2> $out/regime_$name.err || { tail -5 $out/regime_$name.err; return 1; }
     python3 - "$name" $out/regime_$name.json >> $out/regimes.txt <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ mkdir -p $out
 : > $out/regimes.txt
 run() {
   name=$1; shift
-  timeout -k 10 600 python3 bench.py --no-cpu-baseline --steps 100 --warmup 10 "$@" > $out/$name.json 2> $out/$name.err || { tail -5 $out/$name.err; return 1; }
+  timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --steps 100 --warmup 10 "$@" > $out/$name.json 2> $out/$name.err || { tail -5 $out/$name.err; return 1; }
   python3 - "$name" $out/$name.json >> $out/regimes.txt <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$R/gpurun_out/$1; n=$2; shift 2
 echo "== bench.py $* (x$n)" >> $out
 for i in $(seq $n); do
-  timeout -k 10 300 python3 $R/bench.py "$@" --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 $R/bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 c=d['config']['corun']; r=d['roofline']
