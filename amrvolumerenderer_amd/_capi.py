@@ -143,6 +143,8 @@ SIGNATURES = {
     "avr_piece_range": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "avr_paint_box": (C.c_int, [_vp, C.POINTER(Box), C.POINTER(ScalarTransform),
                                  C.POINTER(PaintParams), C.POINTER(Camera), _vp, _vp]),
+    "avr_paint_box_max": (C.c_int, [_vp, C.POINTER(Box), C.POINTER(ScalarTransform),
+                                     C.POINTER(PaintParams), C.POINTER(Camera), _vp, _vp]),
     "avr_scene_create": (C.c_int, [_vp, C.POINTER(Box), C.c_int, C.POINTER(ScalarTransform),
                                     C.POINTER(_vp)]),
     "avr_scene_set_classification_cache": (C.c_int, [_vp, C.c_int]),
@@ -168,6 +170,8 @@ SIGNATURES = {
     "avr_frame_plan_send_block": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_i64), _ip, _ip]),
     "avr_frame_plan_recv_block": (C.c_int, [_vp, C.c_int, C.POINTER(_i64), _ip, _ip]),
     "avr_render_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_render_plan_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_march_plan_max": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
     "avr_classify_plan": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "avr_march_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
     "avr_classify_plan_chunked": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp), C.c_int]),
@@ -180,6 +184,9 @@ SIGNATURES = {
     "avr_fold_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_fold_plan_own": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "avr_fold_plan_image": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_own_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_image_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_visibility_graph_create": (C.c_int, [C.POINTER(Box), C.POINTER(C.c_int32), C.c_int,
                                                C.c_int, C.POINTER(_vp)]),
     "avr_visibility_graph_destroy": (None, [_vp]),
@@ -244,6 +251,8 @@ SIGNATURES = {
     "avr_renderer_reference_sample_distance": (C.c_int, [_vp, _fp]),
     "avr_renderer_render": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera), _ip, _vp,
                                        _vp, C.c_int, _vp, _vp]),
+    "avr_renderer_render_max": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera), _ip,
+                                           _vp, _vp, _vp, _vp]),
     "avr_renderer_prepare": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera), _ip]),
     "avr_renderer_synchronize": (C.c_int, [_vp]),
     "avr_renderer_set_frame_chunks": (C.c_int, [_vp, C.c_int]),

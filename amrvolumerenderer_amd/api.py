@@ -39,6 +39,12 @@ class RenderOptions:
     scalar_range: Optional[Tuple[float, float]] = None
     camera: Optional[CameraParameters] = None
     color_map: Optional[List[ColorMapControlPoint]] = None
+    # "volume" (the reference's image) or "max_intensity": per pixel the colour-map entry of the
+    # largest value along the ray (FrameRenderer.render_max_intensity; antialiasing must be 1)
+    mode: str = "volume"
+
+
+RENDER_MODES = ("volume", "max_intensity")
 
 
 @dataclass
@@ -203,8 +209,18 @@ def _finite(values) -> bool:
     return all(math.isfinite(float(v)) for v in values)
 
 
+def validate_mode(options: RenderOptions) -> None:
+    """RenderOptions.mode: one of RENDER_MODES; a max_intensity frame has no antialiasing."""
+    if options.mode not in RENDER_MODES:
+        raise ValueError(f"mode must be one of {', '.join(RENDER_MODES)}, not {options.mode!r}")
+    if options.mode == "max_intensity" and options.antialiasing != 1:
+        raise ValueError("max_intensity frames have no antialiasing (antialiasing must be 1)")
+
+
 def validate_options(options: RenderOptions) -> None:
-    """The argument checks of api::Render (VolumeRendererApi.cpp:150-255, 257-274)."""
+    """The argument checks of api::Render (VolumeRendererApi.cpp:150-255, 257-274), and of the
+    render mode."""
+    validate_mode(options)
     if not options.output_filename:
         raise ValueError("output filename must not be empty")
     if options.min_level < 0:
@@ -474,10 +490,16 @@ def render_scene(ctx, scene: SceneGeometry, options: RenderOptions, rank: int = 
     renderer = FrameRenderer(ctx, scene.all_boxes, scene.local_boxes, scene.scalar_transform,
                              scene.bounds, scene.scalar_range, rank, n_ranks, process_group,
                              color_map=options.color_map, stage_through_host=stage_through_host)
-    _, rgb8 = renderer.render(
-        RenderParameters(options.width, options.height, options.box_transparency,
-                         options.antialiasing, options.visibility_graph,
-                         write_visibility_graph=options.write_visibility_graph), camera)
+    if options.mode == "max_intensity":
+        rgb8, _ = renderer.render_max_intensity(
+            RenderParameters(options.width, options.height, options.box_transparency,
+                             options.antialiasing, options.visibility_graph, draw_bounds=False,
+                             write_visibility_graph=options.write_visibility_graph), camera)
+    else:
+        _, rgb8 = renderer.render(
+            RenderParameters(options.width, options.height, options.box_transparency,
+                             options.antialiasing, options.visibility_graph,
+                             write_visibility_graph=options.write_visibility_graph), camera)
     renderer.synchronize()
     if rank == 0:
         # any other extension falls back to PPM (VolumeRenderer.cpp:1316-1327)
@@ -497,11 +519,12 @@ def render(plotfile: str, width: int = 512, height: int = 512, box_transparency:
            camera_look_at: Optional[Sequence[float]] = None,
            camera_up: Optional[Sequence[float]] = None, camera_fov_y: Optional[float] = None,
            camera_near: Optional[float] = None, camera_far: Optional[float] = None,
-           color_map: Optional[Sequence[Sequence[float]]] = None) -> int:
+           color_map: Optional[Sequence[Sequence[float]]] = None, mode: str = "volume") -> int:
     """The reference's python entry (python/amrVolumeRenderer/module.cpp:275-303), same keyword
     names and defaults: validates the arguments as the reference does, reads the plotfile
     (plotfile.py), renders on cuda:0 and writes the image.  Multi-rank use: call run() with the
-    rank, world size and process group."""
+    rank, world size and process group.  mode: "volume" (default) or "max_intensity" (a
+    maximum-intensity projection, RenderOptions.mode)."""
     camera = None
     if camera_eye is not None or camera_look_at is not None:
         if camera_eye is None or camera_look_at is None:
@@ -525,7 +548,7 @@ def render(plotfile: str, width: int = 512, height: int = 512, box_transparency:
         output_filename=output if output is not None else "volume-renderer.ppm",
         up_vector=tuple(up_vector) if up_vector is not None else None,
         scalar_range=tuple(scalar_range) if scalar_range is not None else None,
-        camera=camera, color_map=cmap)
+        camera=camera, color_map=cmap, mode=mode)
     validate_options(options)
     from .renderer import validate_render_parameters, RenderParameters
     validate_render_parameters(RenderParameters(width, height, box_transparency, antialiasing))
@@ -544,6 +567,7 @@ def run(plotfile: str, options: RenderOptions, variable_name: str = "", ctx=None
     values to normalised ones, then renderScene."""
     from . import plotfile as pf
     from . import runtime
+    validate_mode(options)
     if ctx is None:
         ctx = runtime.Context(0)
     has_override = options.scalar_range is not None

@@ -322,6 +322,8 @@ struct avr_context {
   bool classify_stream_stores = false;         // context_set_classify_stream_stores
   bool fold_whole_grid = false;                // context_set_fold_whole_grid
   uint64_t* march_counters = nullptr;          // diagnostics (avr_context_set_march_counters)
+  void* max_layers = nullptr;                  // layer of avr_paint_box_max (grow-only)
+  size_t max_layers_capacity = 0;
 };
 
 
@@ -392,6 +394,9 @@ struct FrameChunks {
   const int32_t* classify_positions = nullptr;
   int n_classify_positions = 0;
   const avr_speculation* speculation = nullptr;
+  // a maximum-intensity march (avr_render_plan_max / avr_march_plan_max / avr_paint_box_max): one
+  // launch of render_runs_max_kernel, never chunked, culled or speculative
+  bool max_intensity = false;
 };
 
 // Positions [bounds[k], bounds[k + 1]) of the global layer order for chunk k: equal shares of the
@@ -445,6 +450,8 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   require(chunks.count == 1 || phases == kClassify || phases == kMarch || chunks.visibility != nullptr,
           "a chunked frame is classified and marched by separate calls (or by avr_render_plan_culled)");
   require(slot >= 0 && slot < AVR_CLASSIFIED_SLOTS, "classified slot out of range");
+  require(!chunks.max_intensity || (chunks.count == 1 && chunks.speculation == nullptr),
+          "a maximum-intensity march is one launch: no chunks, no speculation");
   avr::FramePlan local;
   avr::FramePlan& plan = cached ? *cached : local;
   if (plan.boxes.size() != static_cast<size_t>(n_boxes) || !plan.ready) {
@@ -669,6 +676,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
     launch.items_dev = staging.add(items.data(), items.size());
     launch.n_items = static_cast<uint32_t>(items.size());
     launch.workgroups_per_cu = ctx->march_workgroups_per_cu;
+    launch.max_intensity = chunks.max_intensity ? 1 : 0;
     launch.only_mode = plan.boxes.empty() ? -1 : plan.boxes[0].index_mode;
     for (const avr::BoxDev& dev : plan.boxes) {
       if (dev.index_mode != launch.only_mode) launch.only_mode = -1;
@@ -803,6 +811,7 @@ void avr_context_destroy(avr_context* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->own_stream != nullptr) (void)hipStreamSynchronize(ctx->own_stream);
   ctx->staging.release();
+  if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -942,6 +951,61 @@ int avr_paint_box(avr_context* ctx, const avr_box* box, const avr_scalar_transfo
                   1, 1, rects, blocks, nullptr,
                   avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height),
                   &ctx->scratch_scene, 0, out_rgbad, samples_out, nullptr);
+  });
+}
+
+int avr_paint_box_max(avr_context* ctx, const avr_box* box, const avr_scalar_transform* transform,
+                      const avr_paint_params* params, const avr_camera* camera, int16_t* out_index,
+                      uint64_t* samples_out) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(box != nullptr && transform != nullptr && params != nullptr && camera != nullptr &&
+                out_index != nullptr,
+            "null argument");
+    require(params->width > 0 && params->height > 0, "image width and height must be positive");
+    const int32_t order[1] = {0};
+    const int32_t run_end[1] = {1};
+    std::vector<avr::RunRectDev> rects;
+    std::vector<avr::RunBlockDev> blocks;
+    avr::dense_run_tables(params->width, params->height, 1, 1, &rects, &blocks);
+    const int64_t n_pixels = static_cast<int64_t>(params->width) * params->height;
+    const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
+    if (bytes > ctx->max_layers_capacity) {
+      avr::wait_stream(ctx->stream, "avr_paint_box_max");
+      if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
+      ctx->max_layers = nullptr;
+      ctx->max_layers_capacity = 0;
+      avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(maximum-intensity layer)");
+      ctx->max_layers_capacity = bytes;
+    }
+    float* layer = static_cast<float*>(ctx->max_layers);
+    const avr::PieceMapDev pieces =
+        avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height);
+    FrameChunks chunks;
+    chunks.max_intensity = true;
+    int status = render(ctx, kClassify | kMarch, box, 1, *transform, *params, *camera, order, 1,
+                        run_end, 1, 1, rects, blocks, nullptr, pieces, &ctx->scratch_scene, 0, layer,
+                        samples_out, nullptr, chunks);
+    if (status != AVR_OK) return status;
+    // the layer -> index image: the max fold over the one run
+    avr::FoldLaunch launch;
+    ctx->staging.begin(rects.size() * sizeof(avr::RunRectDev) + blocks.size() * sizeof(avr::RunBlockDev), 2);
+    launch.run_rects_dev = ctx->staging.add(rects.data(), rects.size());
+    launch.run_blocks_dev = ctx->staging.add(blocks.data(), blocks.size());
+    launch.run_spans_dev = nullptr;
+    ctx->staging.commit(ctx->stream);
+    launch.pieces = pieces;
+    launch.piece = 0;
+    launch.width = params->width;
+    launch.piece_begin = 0;
+    launch.piece_end = n_pixels;
+    launch.n_runs = 1;
+    launch.recv = layer;
+    launch.out_piece = nullptr;
+    launch.out_rgb8 = nullptr;
+    launch.max_intensity = 1;
+    launch.out_index = out_index;
+    return avr::launch_fold_plan(launch, ctx->stream);
   });
 }
 
@@ -1224,6 +1288,20 @@ int avr_render_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_pl
   return plan_phase(ctx, kClassify | kMarch, scene, plan, 0, send_buffer, samples_out);
 }
 
+int avr_render_plan_max(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
+                        float* send_buffer, uint64_t* samples_out) {
+  FrameChunks chunks;
+  chunks.max_intensity = true;
+  return plan_phase(ctx, kClassify | kMarch, scene, plan, 0, send_buffer, samples_out, chunks);
+}
+
+int avr_march_plan_max(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan, int slot,
+                       float* send_buffer, uint64_t* samples_out) {
+  FrameChunks chunks;
+  chunks.max_intensity = true;
+  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+}
+
 int avr_classify_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                       int slot) {
   return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr);
@@ -1313,7 +1391,8 @@ int avr_fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* rec
 
 namespace {
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
-              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image);
+              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
+              int16_t* out_index = nullptr, bool max_intensity = false);
 }
 
 int avr_fold_plan_own(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
@@ -1326,9 +1405,25 @@ int avr_fold_plan_image(avr_context* ctx, const avr_frame_plan* plan, const floa
   return fold_plan(ctx, plan, recv_buffer, nullptr, out_piece, out_rgb8_image, true);
 }
 
+int avr_fold_plan_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
+                      int16_t* out_index, uint8_t* out_rgb8) {
+  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, out_rgb8, false, out_index, true);
+}
+
+int avr_fold_plan_own_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
+                          const float* own_send_buffer, int16_t* out_index, uint8_t* out_rgb8) {
+  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, nullptr, out_rgb8, false, out_index, true);
+}
+
+int avr_fold_plan_image_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
+                            int16_t* out_index, uint8_t* out_rgb8_image) {
+  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, out_rgb8_image, true, out_index, true);
+}
+
 namespace {
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
-              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image) {
+              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
+              int16_t* out_index, bool max_intensity) {
   return guarded([&]() -> int {
     bind_device(ctx);
     require(plan != nullptr, "null argument");
@@ -1337,7 +1432,7 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
     // (a rank whose piece is empty -- more ranks than pixels, or row bands on a short image --
     // has nothing to fold and may pass empty buffers)
     if (plan->info.piece_end <= plan->info.piece_begin) return AVR_OK;
-    require(out_piece != nullptr || out_rgb8 != nullptr, "null argument");
+    require(out_piece != nullptr || out_rgb8 != nullptr || out_index != nullptr, "null argument");
     require(plan->info.recv_floats == 0 || recv_buffer != nullptr, "null receive buffer");
     avr::FoldLaunch launch;
     const bool spans = plan->tightened && !plan->recv_spans.empty();
@@ -1359,6 +1454,8 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
     launch.recv = recv_buffer;
     launch.out_piece = out_piece;
     launch.out_rgb8 = out_rgb8;
+    launch.max_intensity = max_intensity ? 1 : 0;
+    launch.out_index = out_index;
     // One rank folds the whole image while the next frame's paint kernels start, and nothing
     // waits for it: one workgroup per CU keeps it out of their way (0.997 -> 0.980 ms per frame).
     // A rank of several folds its piece on the stream that also carries the exchange and the

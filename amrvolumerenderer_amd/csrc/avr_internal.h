@@ -290,6 +290,8 @@ struct RenderLaunch {
   // order), the classify launch of chunk k + 1 leaves out the others (indexed like its box list)
   uint8_t* visible_out = nullptr;
   const uint8_t* visible_in = nullptr;
+  // a maximum-intensity frame (render_runs_max_kernel): one launch, no speculation, no culling
+  int max_intensity = 0;
 };
 // classify pass (cells -> table indices) and march; the march reads what the classify pass of
 // the same frame wrote into `classified`
@@ -322,6 +324,10 @@ struct FoldLaunch {
   int64_t own_begin = 0, own_end = 0, own_delta = 0;
   int max_workgroups = 0;              // grid cap (0: the default, 2048)
   int flip_height = 0;                 // > 0: out_rgb8 is the whole image, rows top-down (one rank)
+  // maximum-intensity frames (fold_plan_max_kernel): the max fold; out_piece is not written, the
+  // index piece (piece order, -1 = no sample) goes to out_index (may be null)
+  int max_intensity = 0;
+  int16_t* out_index = nullptr;
 };
 int launch_fold_plan(const FoldLaunch& launch, void* stream);
 int launch_fold_runs(const float* const* slices_dev, int n_slices, float* out, int64_t n,

@@ -16,6 +16,9 @@
 //                        DirectSendBase.cpp:413-426)
 //   fold_plan_kernel    receiver side: blends the received run blocks of a pixel piece in global
 //                       order, optional RGB8 (DirectSendBase.cpp:400-446, Color.hpp:66-91)
+//   render_runs_max_kernel / fold_plan_kernel<OWN, true>
+//                       maximum-intensity frames: the same march taking every sample, one byte
+//                       gather and one integer max each; the max fold
 //   blend_*             Features::blend of the three image types (element-wise)
 //   fold_runs_kernel    left fold over dense run layers
 //   downsample / quantize / encode / decode   frame tail
@@ -25,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "avr_internal.h"
 #include "avr_device.h"
@@ -214,10 +218,16 @@ __device__ __forceinline__ uint32_t cell_offset(const BoxDev& box, uint32_t row_
 
 // The march of one ray through one box (VolumePainter.cpp:811-921 + host epilogue :939-955).
 // Returns the layer pixel the reference would store for this box.
-template <bool STATS, int MODE>
-__device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts& fc,
+// MAX (maximum-intensity projection): the same samples at the same positions, but as if the
+// accumulator never saturated -- every sample up to tmax is taken -- and per sample one byte gather
+// and one integer max; returns the largest table index sampled, -1 if none.
+// (MAX takes the ray by value: by reference its fields were loaded as overlapping float pairs
+// from a stack copy that then stayed in scratch memory)
+template <bool STATS, int MODE, bool MAX = false>
+__device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const BoxDev& box, const FrameConsts& fc,
                                             const uint8_t* __restrict__ classified,
-                                            const float4* __restrict__ table, const Ray& ray,
+                                            const float4* __restrict__ table,
+                                            std::conditional_t<MAX, const Ray, const Ray&> ray,
                                             float tmin, float tmax, unsigned& fetches,
                                             unsigned& near_hits) {
   const float min_x = box.minc[0], min_y = box.minc[1], min_z = box.minc[2];
@@ -234,6 +244,7 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
   if (distance < 0.0f) distance = box.mesh_eps;
 
   float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
+  [[maybe_unused]] int best = -1;  // (MAX)
 
 #define AVR_INSIDE(x, y, z) \
   (!((x) < min_x || (x) > max_x || (y) < min_y || (y) > max_y || (z) < min_z || (z) > max_z))
@@ -331,6 +342,13 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
         int idx[kDeep];
 #pragma unroll
         for (int i = 0; i < kDeep; ++i) idx[i] = cells[off[i]];
+        if constexpr (MAX) {
+#pragma unroll
+          for (int i = 0; i < kDeep; ++i) best = (idx[i] > best) ? idx[i] : best;
+          distance = d[kDeep - 1] + step;
+          if (STATS) fetches += static_cast<unsigned>(kDeep);
+          continue;
+        }
         float4 sample[kDeep];
 #pragma unroll
         for (int i = 0; i < kDeep; ++i) sample[i] = table[idx[i]];
@@ -453,6 +471,15 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
       const int idx2 = cells[off2];
       const int idx3 = cells[off3];
       const int idx4 = cells[off4];
+      if constexpr (MAX) {
+        const int m12 = (idx1 > idx2) ? idx1 : idx2;
+        const int m34 = (idx3 > idx4) ? idx3 : idx4;
+        const int m = (m12 > m34) ? m12 : m34;
+        best = (m > best) ? m : best;
+        distance = d4 + step;
+        if (STATS) fetches += 4u;
+        continue;
+      }
       const float4 s1 = table[idx1];
       const float4 s2 = table[idx2];
       const float4 s3 = table[idx3];
@@ -538,7 +565,7 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
   // The reference's skip loop (:830-835) and the "continue" branch of the main loop (:838-844)
   // do the same thing -- advance without sampling while the position is outside -- so one loop
   // with an inside test reproduces both.
-  while (distance < tmax && acc_a < 1.0f) {
+  while (distance < tmax && (MAX || acc_a < 1.0f)) {
     if (AVR_INSIDE(pos_x, pos_y, pos_z)) {
       const uint32_t offset = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch, pos_x - min_x,
                                                        pos_y - min_y, pos_z - min_z, near_hits);
@@ -546,8 +573,12 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
       // classify pass of this frame (same arithmetic as VolumePainter.cpp:870-883)
       const int idx = cells[offset];
       if (STATS) ++fetches;
-      const float4 sample = table[idx];
-      AVR_ACCUMULATE(sample);
+      if constexpr (MAX) {
+        best = (idx > best) ? idx : best;
+      } else {
+        const float4 sample = table[idx];
+        AVR_ACCUMULATE(sample);
+      }
     }
     distance += step;
     pos_x = ray.ox + ray.dx * distance;
@@ -557,28 +588,32 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
 #undef AVR_INSIDE
 #undef AVR_ACCUMULATE
 
-  // device-side clamp (:902-905) then the host epilogue's std::clamp to [0,1] (:944-947)
-  acc_r = (acc_r > 1.0f) ? 1.0f : acc_r;
-  acc_g = (acc_g > 1.0f) ? 1.0f : acc_g;
-  acc_b = (acc_b > 1.0f) ? 1.0f : acc_b;
-  acc_a = (acc_a > 1.0f) ? 1.0f : acc_a;
-  Layer5 out;
-  out.r = (acc_r < 0.0f) ? 0.0f : acc_r;
-  out.g = (acc_g < 0.0f) ? 0.0f : acc_g;
-  out.b = (acc_b < 0.0f) ? 0.0f : acc_b;
-  out.a = (acc_a < 0.0f) ? 0.0f : acc_a;
+  if constexpr (MAX) {
+    return best;
+  } else {
+    // device-side clamp (:902-905) then the host epilogue's std::clamp to [0,1] (:944-947)
+    acc_r = (acc_r > 1.0f) ? 1.0f : acc_r;
+    acc_g = (acc_g > 1.0f) ? 1.0f : acc_g;
+    acc_b = (acc_b > 1.0f) ? 1.0f : acc_b;
+    acc_a = (acc_a > 1.0f) ? 1.0f : acc_a;
+    Layer5 out;
+    out.r = (acc_r < 0.0f) ? 0.0f : acc_r;
+    out.g = (acc_g < 0.0f) ? 0.0f : acc_g;
+    out.b = (acc_b < 0.0f) ? 0.0f : acc_b;
+    out.a = (acc_a < 0.0f) ? 0.0f : acc_a;
 
-  float depth = AVR_INF;
-  if (acc_a > 0.0f) {  // entry depth along the view axis (:912-920)
-    const float ex = ray.ox + ray.dx * tmin;
-    const float ey = ray.oy + ray.dy * tmin;
-    const float ez = ray.oz + ray.dz * tmin;
-    depth = (ex - fc.eye[0]) * fc.fwd[0] + (ey - fc.eye[1]) * fc.fwd[1] +
-            (ez - fc.eye[2]) * fc.fwd[2];
+    float depth = AVR_INF;
+    if (acc_a > 0.0f) {  // entry depth along the view axis (:912-920)
+      const float ex = ray.ox + ray.dx * tmin;
+      const float ey = ray.oy + ray.dy * tmin;
+      const float ez = ray.oz + ray.dz * tmin;
+      depth = (ex - fc.eye[0]) * fc.fwd[0] + (ey - fc.eye[1]) * fc.fwd[1] +
+              (ez - fc.eye[2]) * fc.fwd[2];
+    }
+    if (!__builtin_isfinite(depth) || out.a <= 0.0f) depth = AVR_INF;  // (:950-952)
+    out.d = depth;
+    return out;
   }
-  if (!__builtin_isfinite(depth) || out.a <= 0.0f) depth = AVR_INF;  // (:950-952)
-  out.d = depth;
-  return out;
 }
 
 // ONLY_MODE >= 0: every box of the launch uses that IndexMode (the common case: one scene, one
@@ -587,7 +622,12 @@ __device__ __forceinline__ Layer5 march_box(const BoxDev& box, const FrameConsts
 // (MI355X_MICROARCH.md, "Residency"), i.e. 8 per CU only up to 80 SGPRs, 6 at 98+.
 // SPEC: the speculative frame's bookkeeping is compiled in (one vector register more: six waves per
 // SIMD instead of seven, so it is its own instantiation; never together with STATS).
-template <bool STATS, int ONLY_MODE, bool SPEC>
+// MAX: a maximum-intensity frame (render_runs_max_kernel; never with SPEC, chunks or culling): the
+// same work items, tiles, rays, culling and layer addressing, but every box a ray hits is marched
+// to its end (march_box<..., true>: no opacity, no skipped box) and the run's pixel is the largest
+// table index.  Layer encoding, so that plan, tightening, exchange and gather carry it unchanged:
+// a hit is (RGB of table entry `index`, 1, index), a miss the cleared pixel (0, 0, 0, 0, +inf).
+template <bool STATS, int ONLY_MODE, bool SPEC, bool MAX = false>
 __device__ __forceinline__ void
 render_runs_body(
     const FrameConsts& fc, const BoxDev* __restrict__ boxes,
@@ -714,7 +754,8 @@ render_runs_body(
     const int run_begin = (run > 0) ? run_end[run - 1] : 0;
     const int end = (run_end[run] < pos_end) ? run_end[run] : pos_end;
     Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, AVR_INF};  // cleared layer pixel: exact blend identity
-    if (resume != 0) {
+    [[maybe_unused]] int acc_index = -1;              // (MAX) the run's largest index so far
+    if (!MAX && resume != 0) {
       const float* src = layer_pixel();
       if (src != nullptr) {
         acc.r = src[0];
@@ -757,6 +798,31 @@ render_runs_body(
       slab_axis(ray.oy, ray.dy, inv_dy, box.minc[1], box.maxc[1], tmin, tmax);
       slab_axis(ray.oz, ray.dz, inv_dz, box.minc[2], box.maxc[2], tmin, tmax);
       bool hit = live && (tmax >= tmin);
+      if constexpr (MAX) {
+        // every sample counts: no box is skipped for opacity
+        if (!__builtin_amdgcn_ballot_w64(hit)) continue;
+        if (hit) {
+          int m;
+          if (ONLY_MODE == kPow2Multiply) {
+            m = march_box<STATS, kPow2Multiply, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                      fetches, near_hits);
+          } else if (ONLY_MODE == kReciprocal) {
+            m = march_box<STATS, kReciprocal, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                    fetches, near_hits);
+          } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
+            m = march_box<STATS, kPow2Multiply, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                      fetches, near_hits);
+          } else if (box.index_mode == kReciprocal) {
+            m = march_box<STATS, kReciprocal, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                    fetches, near_hits);
+          } else {
+            m = march_box<STATS, kExactDivide, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                     fetches, near_hits);
+          }
+          acc_index = (m > acc_index) ? m : acc_index;
+        }
+        continue;
+      }
       if (hit && acc.a == 1.0f) {
         // The run accumulator is opaque: if it is also in front of this box's entry point the
         // blend returns the accumulator unchanged (front + back * (1 - 1)), whatever the box
@@ -825,7 +891,7 @@ render_runs_body(
     // a + 1 * (1 - a), which need not round to 1), so every later box the pixel's ray hits counts
     // as visible.  By induction a box flagged invisible finds, at every pixel that hits it, the
     // accumulator this launch left -- and is skipped.
-    if (visible_out != nullptr) {
+    if (!MAX && visible_out != nullptr) {
       bool open = false;  // an earlier box to come is marched at this pixel
       // (the run's boxes behind this launch's; a run that only starts behind them: all of its boxes)
       for (int position = (end > run_begin) ? end : run_begin; position < run_end[run]; ++position) {
@@ -850,6 +916,12 @@ render_runs_body(
         }
         open = open || visible;
         if (__builtin_amdgcn_ballot_w64(visible) != 0 && lane == 0) visible_out[position] = 1;
+      }
+    }
+    if constexpr (MAX) {
+      if (acc_index >= 0) {  // RGB does not depend on the level (only alpha does): any table will do
+        const float4 c = lds_tables[acc_index];
+        acc = {c.x, c.y, c.z, 1.0f, static_cast<float>(acc_index)};
       }
     }
     // (a resumed launch stores every pixel again, reached or not: keeping "was it reached" per lane
@@ -917,6 +989,11 @@ __global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARC
 template <int ONLY_MODE>
 __global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_repair_kernel(AVR_MARCH_PARAMETERS) {
   render_runs_body<false, ONLY_MODE, true>(AVR_MARCH_ARGUMENTS);
+}
+// The maximum-intensity march (render_runs_body<..., MAX = true>).
+template <bool STATS, int ONLY_MODE>
+__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_max_kernel(AVR_MARCH_PARAMETERS) {
+  render_runs_body<STATS, ONLY_MODE, false, true>(AVR_MARCH_ARGUMENTS);
 }
 #undef AVR_MARCH_PARAMETERS
 #undef AVR_MARCH_ARGUMENTS
@@ -1390,7 +1467,13 @@ struct FoldEntry {
   int64_t base;  // float offset of pixel x = 0 of this row inside the run's block
 };
 
-template <bool OWN>
+//
+// MAX (maximum-intensity frames): among the covering runs with a hit
+// (a != 0, see render_runs_body) the one of the largest index (d) wins -- max is exact and
+// order-free; the bytes are its table RGB, and `out_piece` (optional) is then an int16_t index
+// piece, -1 for a miss.  (The parameter list stays that of the blend fold: its instantiations
+// compile to the instructions they had before MAX.)
+template <bool OWN, bool MAX = false>
 __global__ __launch_bounds__(256) void fold_plan_kernel(
     const int width, const int64_t piece_begin, const int64_t piece_end, const int n_runs,
     const RunRectDev* __restrict__ rects, const RunBlockDev* __restrict__ blocks,
@@ -1421,7 +1504,7 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
   const int64_t p = static_cast<int64_t>(block_row) * width + px;
   const bool live = (px < width) && (p >= piece_begin) && (p < piece_end);
 
-  Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, AVR_INF};
+  Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, MAX ? -1.0f : AVR_INF};
   for (int chunk = 0; chunk < n_runs; chunk += 256) {
     const int g = chunk + tid;
     bool touches = false;
@@ -1464,14 +1547,18 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
       if (live && px >= run.x0 && px <= run.x1) {
         const float* src = recv + run.base + static_cast<int64_t>(px) * 5;
         const Layer5 layer = {src[0], src[1], src[2], src[3], src[4]};
-        acc = blend_depthsort(acc, layer);
+        if constexpr (MAX) {
+          if (layer.a != 0.0f && layer.d > acc.d) acc = layer;
+        } else {
+          acc = blend_depthsort(acc, layer);
+        }
       }
     }
     __syncthreads();  // the list is rewritten by the next chunk
   }
   if (!live) continue;  // (after the chunk loop's closing barrier: the list is free again)
   const int64_t q = p - piece_begin;
-  if (out_piece != nullptr) {
+  if (!MAX && out_piece != nullptr) {
     float* d = out_piece + q * 5;
     d[0] = acc.r;
     d[1] = acc.g;
@@ -1489,6 +1576,12 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
     b[0] = static_cast<uint8_t>(component_as_byte(acc.r));
     b[1] = static_cast<uint8_t>(component_as_byte(acc.g));
     b[2] = static_cast<uint8_t>(component_as_byte(acc.b));
+  }
+  if constexpr (MAX) {
+    if (out_piece != nullptr) {
+      reinterpret_cast<int16_t*>(out_piece)[q] =
+          static_cast<int16_t>(acc.a != 0.0f ? static_cast<int>(acc.d) : -1);
+    }
   }
   }  // segments
 }
@@ -1704,6 +1797,10 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
                      L.out_layers, L.samples_out, L.counters, L.pos_begin,                       \
                      (L.pos_end < 0 ? L.n_order : L.pos_end), L.resume, L.visible_out, L.spec_dev)
   if (L.spec_dev != nullptr) {
+    if (L.max_intensity) {
+      set_error("render_runs_kernel: a maximum-intensity frame is not speculative");
+      return AVR_ERR_INVALID_ARGUMENT;
+    }
     if (stats) {
       set_error("render_runs_kernel: a speculative frame cannot count samples");
       return AVR_ERR_INVALID_ARGUMENT;
@@ -1729,6 +1826,29 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
     }
 #undef AVR_LAUNCH_SPEC
     return check_launch("render_runs_kernel (speculative)");
+  }
+  if (L.max_intensity) {
+    if (L.resume != 0 || L.visible_out != nullptr) {
+      set_error("render_runs_max_kernel: a maximum-intensity frame is one launch, not chunks");
+      return AVR_ERR_INVALID_ARGUMENT;
+    }
+#define AVR_LAUNCH_MAX(STATS, ONLY)                                                             \
+  hipLaunchKernelGGL((render_runs_max_kernel<STATS, ONLY>), dim3(blocks), dim3(kBlockThreads),  \
+                     lds_bytes, stream, L.consts, L.boxes_dev, L.classified, L.tables_dev,      \
+                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
+                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
+                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
+                     tiles_y, L.items_dev, L.out_layers, L.samples_out, L.counters, L.pos_begin, \
+                     (L.pos_end < 0 ? L.n_order : L.pos_end), 0, nullptr, nullptr)
+    if (L.only_mode == kPow2Multiply) {
+      if (stats) AVR_LAUNCH_MAX(true, kPow2Multiply); else AVR_LAUNCH_MAX(false, kPow2Multiply);
+    } else if (L.only_mode == kReciprocal) {
+      if (stats) AVR_LAUNCH_MAX(true, kReciprocal); else AVR_LAUNCH_MAX(false, kReciprocal);
+    } else {
+      if (stats) AVR_LAUNCH_MAX(true, -1); else AVR_LAUNCH_MAX(false, -1);
+    }
+#undef AVR_LAUNCH_MAX
+    return check_launch("render_runs_max_kernel");
   }
   if (L.only_mode == kPow2Multiply) {
     if (stats) AVR_LAUNCH(true, kPow2Multiply); else AVR_LAUNCH(false, kPow2Multiply);
@@ -1813,8 +1933,18 @@ int launch_fold_plan(const FoldLaunch& L, void* stream_v) {
     set_error("fold_plan_kernel: image too large");
     return AVR_ERR_INVALID_ARGUMENT;
   }
-  auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true> : fold_plan_kernel<false>;
   const int64_t grid = std::min<int64_t>(blocks, L.max_workgroups > 0 ? L.max_workgroups : kFoldWorkgroups);
+  if (L.max_intensity) {
+    auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true, true> : fold_plan_kernel<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
+                       L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,
+                       reinterpret_cast<float*>(L.out_index), L.out_rgb8,
+                       first_row, chunks_per_row, L.pieces, L.piece, L.own_begin, L.own_end,
+                       L.own_delta, static_cast<int>(blocks), L.flip_height);
+    return check_launch("fold_plan_kernel (maximum intensity)");
+  }
+  auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true> : fold_plan_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
                      static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
                      L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,

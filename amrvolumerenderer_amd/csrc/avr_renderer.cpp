@@ -197,6 +197,7 @@ struct avr_renderer {
   // instead of two.  The fold of frame f + 1 must not overwrite what that round still sends: two
   // piece buffers alternate.  avr_renderer_synchronize sends what is still pending (collective).
   DeviceBuffer piece_rgb8_odd;
+  DeviceBuffer piece_index, full_index;  // maximum-intensity frames of ranks of several
   int deferred_gather = -1;  // avr_renderer_set_deferred_gather: -1 = ranks of several
   struct PendingGather {
     bool valid = false;
@@ -1045,12 +1046,25 @@ int avr_renderer_prepare(avr_renderer* r, const avr_render_params* render, const
   });
 }
 
-int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
-                        const int32_t* group_order, void* input_stream, uint64_t* samples_out,
-                        int want_image, uint8_t* rgb8_out, float* image_out) {
+}  // extern "C"
+
+namespace {
+
+// One frame of avr_renderer_render (mip == false) or avr_renderer_render_max (mip == true).  A MIP
+// frame takes the same path with the MIP march and the max fold; what rests on opacity -- frame
+// chunks, occlusion culling, visibility speculation -- is left out (and speculation is not fed).
+int render_frame(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
+                 const int32_t* group_order, void* input_stream, uint64_t* samples_out,
+                 int want_image, uint8_t* rgb8_out, float* image_out, bool mip, int16_t* index_out) {
   return guarded_renderer(r, [&]() -> int {
     require(render != nullptr && camera != nullptr, "null argument");
     const int root = validate(*render);
+    if (mip) {
+      require(root == 1, "a maximum-intensity frame has no antialiasing (render->antialiasing must be 1)");
+      require(!render->draw_bounds, "a maximum-intensity frame has no wireframe (draw_bounds must be 0)");
+      require(want_image == 0, "a maximum-intensity frame has no float image");
+      require(r->rank == 0 || index_out == nullptr, "index_out is rank 0's");
+    }
     hip_ok(hipSetDevice(r->device), "hipSetDevice");
     const bool is_root = r->rank == 0;
     require(!is_root || rgb8_out != nullptr, "the root rank needs an rgb8 output buffer");
@@ -1120,7 +1134,7 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     // ---- occlusion culling (one rank): the frame in depth-ordered chunks on ONE stream, every
     // chunk's classify launch leaving out the boxes its predecessors' marches found hidden
     int cull = 0;
-    if (!many && !r->cache_classification && info.n_local_runs > 0 && info.n_local_boxes >= 8) {
+    if (!mip && !many && !r->cache_classification && info.n_local_runs > 0 && info.n_local_boxes >= 8) {
       cull = std::min(std::max(r->occlusion_chunks, 0), info.n_local_boxes);
     }
     uint8_t* visibility = nullptr;
@@ -1131,7 +1145,7 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     // ---- visibility speculation (one rank): this frame's buffers; what the frame does with them
     // is settled below, when its layout is known
     avr_renderer::Speculating& sp = r->spec;
-    const bool spec_considered = !many && r->speculation != 0 && cull < 2 && !r->cache_classification &&
+    const bool spec_considered = !mip && !many && r->speculation != 0 && cull < 2 && !r->cache_classification &&
                                  info.n_local_runs > 0 && info.n_local_boxes >= 8 && samples_out == nullptr &&
                                  plan->local_order.size() == static_cast<size_t>(info.n_local_boxes);
     const size_t spec_bytes = (static_cast<size_t>(std::max(info.n_local_boxes, 1)) + 15) / 16 * 16;
@@ -1222,7 +1236,19 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     uint8_t* piece_rgb8 =
         early_rgb8 ? static_cast<uint8_t*>(rgb8_buffer.reserve(bytes_of(piece_pixels, 3), drain))
                    : nullptr;
-    const bool defer_gather = many && r->deferred_gather != 0 && early_rgb8 && !gather_image;
+    const bool defer_gather = !mip && many && r->deferred_gather != 0 && early_rgb8 && !gather_image;
+    // (MIP, ranks of several: the int16 index piece, gathered to rank 0 in the frame itself --
+    // straight into index_out where the gathered buffer is the image)
+    int16_t* piece_index = nullptr;
+    int16_t* gathered_index = nullptr;
+    if (mip && many) {
+      piece_index = static_cast<int16_t*>(r->piece_index.reserve(bytes_of(piece_pixels, 2), drain));
+      if (is_root) {
+        gathered_index = (index_out != nullptr && !banded)
+                             ? index_out
+                             : static_cast<int16_t*>(r->full_index.reserve(bytes_of(n_pixels, 2), drain));
+      }
+    }
     uint8_t* gathered_rgb8 = nullptr;
     float* gathered_image = nullptr;
     float* assembled = nullptr;
@@ -1418,7 +1444,7 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     // classify pass to cut.
     const bool was_idle = r->pipeline_idle;
     int n_chunks = 1;
-    if (overlap && !paired && !r->cache_classification && info.n_local_runs > 0) {
+    if (!mip && overlap && !paired && !r->cache_classification && info.n_local_runs > 0) {
       n_chunks = std::min(std::max(r->frame_chunks, 1), std::max(info.n_local_boxes, 1));
     }
     r->last_chunks = n_chunks;
@@ -1603,7 +1629,7 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
         spec_mode != 0 && spec_observation != nullptr &&
         (spec_mode == 1 || plan != sp.previous_plan || sp.frame % avr_renderer::kSpecObserveEvery == 0 ||
          sp.frame - sp.last_repair < 2 * avr_renderer::kSpecObserveEvery);
-    sp.previous_plan = plan;
+    if (!mip) sp.previous_plan = plan;
     if (spec_observed) {  // (cleared while the classify pass still runs)
       hip_ok(hipMemsetAsync(spec_visited, 0, spec_bytes, stream_m), "hipMemsetAsync(speculation)");
     }
@@ -1617,7 +1643,9 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     }
     if (r->timing) hip_ok(hipEventRecord(timed.march_begin, stream_m), "hipEventRecord");
     if (probe != nullptr) hip_ok(hipEventRecord(probe->events.march_begin, stream_m), "hipEventRecord");
-    if (cull >= 2) {
+    if (mip) {
+      abi_ok(avr_march_plan_max(march_ctx, r->scene, plan, volume, send, samples_out));
+    } else if (cull >= 2) {
       abi_ok(avr_render_plan_culled(march_ctx, r->scene, plan, volume, send, samples_out, cull, visibility));
       r->last_chunks = cull;
     } else if (n_chunks > 1) {
@@ -1758,7 +1786,11 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     // (one rank without antialiasing or wireframe: the fold writes the output file's rows itself)
     const bool fold_to_image = !many && early_rgb8 && !overlay_piece && is_root;
     avr::context_set_fold_whole_grid(r->compose, was_idle);
-    if (fold_to_image) {
+    if (mip && fold_to_image) {
+      abi_ok(avr_fold_plan_image_max(r->compose, plan, received, index_out, rgb8_out));
+    } else if (mip) {
+      abi_ok(avr_fold_plan_own_max(r->compose, plan, received, own, piece_index, piece_rgb8));
+    } else if (fold_to_image) {
       abi_ok(avr_fold_plan_image(r->compose, plan, received, piece, rgb8_out));
     } else {
       abi_ok(avr_fold_plan_own(r->compose, plan, received, own, piece,
@@ -1793,6 +1825,12 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
         abi_ok(avr_gather(r->compose, plan, r->comm, piece_rgb8, 3, full, 0));
       }
       if (is_root && !fold_to_image) abi_ok(avr_assemble_rows(r->compose, plan, full, 3, 1, rgb8_out));
+      if (mip && many) {
+        abi_ok(avr_gather(r->compose, plan, r->comm, piece_index, 2, gathered_index, 0));
+        if (is_root && banded && index_out != nullptr) {
+          abi_ok(avr_assemble_rows(r->compose, plan, gathered_index, 2, 0, index_out));
+        }
+      }
       if (gather_image) {
         if (many) {
           float* gathered = is_root ? (banded ? gathered_image : image_out) : nullptr;
@@ -1829,6 +1867,24 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
     r->pipeline_idle = false;  // (a buffer that grew drained the streams in between)
     return AVR_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
+                        const int32_t* group_order, void* input_stream, uint64_t* samples_out,
+                        int want_image, uint8_t* rgb8_out, float* image_out) {
+  return render_frame(r, render, camera, group_order, input_stream, samples_out, want_image, rgb8_out,
+                      image_out, false, nullptr);
+}
+
+int avr_renderer_render_max(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
+                            const int32_t* group_order, void* input_stream, uint64_t* samples_out,
+                            uint8_t* rgb8_out, int16_t* index_out) {
+  return render_frame(r, render, camera, group_order, input_stream, samples_out, 0, rgb8_out, nullptr,
+                      true, index_out);
 }
 
 }  // extern "C"

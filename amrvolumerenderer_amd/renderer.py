@@ -400,6 +400,26 @@ class FrameRenderer:
                     rgb8 = comm.quantize_rgb8(image.reshape(-1), p.width, p.height)
         return image, rgb8
 
+    def render_max_intensity(self, p: RenderParameters, camera: CameraParameters,
+                             samples: Optional[torch.Tensor] = None,
+                             group_order: Optional[Sequence[int]] = None):
+        """One maximum-intensity projection frame: per pixel the largest transfer-function table
+        index over every sample the volume march would take with an accumulator that never
+        saturates, coloured by that entry's RGB ("Maximum-intensity projection").  On
+        rank 0 returns (rgb8 [H, W, 3] uint8, rows top-down; index [H, W] int16, -1 where no box
+        takes a sample, row 0 at the bottom like render()'s image); other ranks (None, None).
+        Results are produced on the compositing stream, as for render().  p.antialiasing must be 1
+        and p.draw_bounds False; p.box_transparency has no effect.  Needs the native frame driver."""
+        validate_render_parameters(p)
+        if p.antialiasing != 1:
+            raise ValueError("a maximum-intensity frame has no antialiasing (antialiasing must be 1)")
+        if p.draw_bounds:
+            raise ValueError("a maximum-intensity frame has no wireframe (draw_bounds must be False)")
+        if self.native is None:
+            raise RuntimeError("maximum-intensity frames need the native frame driver (native=True)")
+        return self.native.render_max(p.width, p.height, camera, p.use_visibility_graph, group_order,
+                                      samples)
+
 
 def build_scene_on_device(ctx: runtime.Context, spec: scenes.SceneSpec, rank: int = 0):
     """Materialises this rank's boxes of a synthetic scene in HBM (torch, float64) and returns

@@ -257,6 +257,27 @@ class Context:
         self.publish()
         return out
 
+    def paint_box_max(self, box: AmrBox, transform: ScalarTransform, params: _capi.PaintParams,
+                      camera: CameraParameters, out: Optional[torch.Tensor] = None,
+                      samples: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """avr_paint_box_max: one box -> [H, W] int16 maximum-intensity indices (-1: no sample),
+        rows in paint_box's order (row 0 at the bottom)."""
+        if out is None:
+            out = torch.empty((params.height, params.width), dtype=torch.int16, device=self.device)
+        self._check_tensor(out, torch.int16, "out")
+        if out.numel() != params.width * params.height:
+            raise ValueError("out has the wrong size")
+        if samples is not None:
+            self._check_tensor(samples, torch.int64, "samples")
+        cbox, ctr, ccam = box.to_c(), transform.to_c(), camera.to_c()
+        self.join()
+        _capi.check(_capi.lib().avr_paint_box_max(
+            self._handle, C.byref(cbox), C.byref(ctr), C.byref(params), C.byref(ccam),
+            C.c_void_p(out.data_ptr()),
+            C.c_void_p(samples.data_ptr()) if samples is not None else None))
+        self.publish()
+        return out
+
     def create_scene(self, boxes: Sequence[AmrBox], transform: ScalarTransform) -> "Scene":
         return Scene(self, boxes, transform)
 
@@ -1130,6 +1151,35 @@ class NativeRenderer:
         # synchronize(): the tensor must outlive the caller's interest in it until then)
         self._held_outputs = (image, rgb8)
         return image, rgb8
+
+    def render_max(self, width: int, height: int, camera: CameraParameters,
+                   use_visibility_graph: bool = True, group_order: Optional[Sequence[int]] = None,
+                   samples: Optional[torch.Tensor] = None):
+        """One maximum-intensity frame (avr_renderer_render_max, asynchronous like render()).
+        Rank 0 returns (rgb8 [H, W, 3] uint8, rows top-down; index [H, W] int16, the largest
+        transfer-function table index per pixel, -1 where no box takes a sample, row 0 at the
+        bottom like render()'s image); other ranks (None, None).  Both are complete on stream X."""
+        rp = _capi.RenderParams(int(width), int(height), 0.0, 1, int(bool(use_visibility_graph)), 0, 0)
+        ccam = camera.to_c()
+        group = None
+        if group_order is not None:
+            group = (C.c_int32 * self.n_ranks)(*[int(g) for g in group_order])
+        rgb8 = index = None
+        caller = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.streams[2]):
+            if self.rank == 0:
+                rgb8 = torch.empty((height, width, 3), dtype=torch.uint8, device=self.device)
+                index = torch.empty((height, width), dtype=torch.int16, device=self.device)
+        if samples is not None and (samples.dtype != torch.int64 or samples.device != self.device):
+            raise ValueError("samples must be an int64 tensor on the renderer's device")
+        wait = None if caller.query() else C.c_void_p(caller.cuda_stream or _capi.DEFAULT_STREAM)
+        _capi.check(_capi.lib().avr_renderer_render_max(
+            self._handle, C.byref(rp), C.byref(ccam), group, wait,
+            C.c_void_p(samples.data_ptr()) if samples is not None else None,
+            C.c_void_p(rgb8.data_ptr()) if rgb8 is not None else None,
+            C.c_void_p(index.data_ptr()) if index is not None else None))
+        self._held_outputs = (index, rgb8)
+        return rgb8, index
 
 
 class PlanAhead:

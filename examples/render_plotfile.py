@@ -49,6 +49,8 @@ def main() -> int:
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--transparency", type=float, default=0.6)
     ap.add_argument("--orbit", type=int, default=0, help="render this many views around the data")
+    ap.add_argument("--mode", choices=api.RENDER_MODES, default="volume",
+                    help="volume rendering or maximum-intensity projection")
     args = ap.parse_args()
     path = args.plotfile
     scratch = None
@@ -58,7 +60,7 @@ def main() -> int:
         synthetic_plotfile(path)
     if args.orbit <= 0:
         return api.render(path, width=args.size, height=args.size, variable=args.variable,
-                          box_transparency=args.transparency, output=args.output)
+                          box_transparency=args.transparency, output=args.output, mode=args.mode)
     ctx = runtime.Context(0)
     scene = pf.load_plotfile_geometry(ctx, path, args.variable or "")
     renderer = FrameRenderer(ctx, scene.all_boxes, scene.local_boxes, scene.scalar_transform,
@@ -69,7 +71,11 @@ def main() -> int:
         angle = 2.0 * math.pi * view / args.orbit
         eye = (centre[0] + 3.0 * math.sin(angle), centre[1] + 1.0, centre[2] + 3.0 * math.cos(angle))
         camera = CameraParameters(eye, tuple(centre), (0.0, 1.0, 0.0), 45.0, 0.1, 20.0)
-        _, rgb8 = renderer.render(RenderParameters(args.size, args.size, args.transparency), camera)
+        if args.mode == "max_intensity":
+            rgb8, _ = renderer.render_max_intensity(
+                RenderParameters(args.size, args.size, draw_bounds=False), camera)
+        else:
+            _, rgb8 = renderer.render(RenderParameters(args.size, args.size, args.transparency), camera)
         renderer.synchronize()
         writer = api.save_png if ext.lower() == ".png" else api.save_ppm
         writer(rgb8, f"{base}_{view:03d}{ext}")

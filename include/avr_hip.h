@@ -200,6 +200,18 @@ int avr_paint_box(avr_context *ctx, const avr_box *box, const avr_scalar_transfo
                   const avr_paint_params *params, const avr_camera *camera, float *out_rgbad,
                   uint64_t *samples_out);
 
+/* Maximum-intensity projection (MIP) of one box: per pixel, the largest transfer-function table
+ * index over the samples avr_paint_box's march takes in the box if its accumulator never
+ * saturated -- the same ray, slab bounds, start distance, step, inside test and index clamp, every
+ * sample up to the exit point; the index is the byte the classify pass stores for the sample's
+ * cell (VolumePainter.cpp:870-883, NaN / Inf / soft-clip rules included), -1 where no sample is
+ * taken.  width*height int16 values to out_index (device), in avr_paint_box's pixel order
+ * (p = y * width + x, row 0 at the bottom).  samples_out: every sample taken is ADDED to it.
+ * box_transparency has no effect (it only scales alpha). */
+int avr_paint_box_max(avr_context *ctx, const avr_box *box, const avr_scalar_transform *transform,
+                      const avr_paint_params *params, const avr_camera *camera, int16_t *out_index,
+                      uint64_t *samples_out);
+
 /* A scene = the rank's local boxes (geometry.localBoxes, VolumeRenderer.cpp:1201) with one
  * scalar transform (geometry.scalarTransform).  Descriptors are copied to the device; cell
  * data stays where `cells` points. */
@@ -364,6 +376,16 @@ int avr_classify_plan(avr_context *ctx, const avr_scene *scene, const avr_frame_
 int avr_march_plan(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan, int slot,
                    float *send_buffer, uint64_t *samples_out);
 
+/* Maximum-intensity frames (avr_paint_box_max per pixel and box): avr_render_plan and
+ * avr_march_plan with the MIP march.  The same plan, classified volume and send layout; a run's
+ * layer pixel is (RGB of table entry i, 1, i) for the run's largest index i and the cleared pixel
+ * (0,0,0,0,+inf) where it takes no sample, so that tightening, avr_exchange_peers and the gathers
+ * carry it unchanged.  Fold with the avr_fold_plan*_max calls below.  No chunks, no speculation. */
+int avr_render_plan_max(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan,
+                        float *send_buffer, uint64_t *samples_out);
+int avr_march_plan_max(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan, int slot,
+                       float *send_buffer, uint64_t *samples_out);
+
 /* ONE frame in n_chunks (2 .. AVR_MAX_FRAME_CHUNKS) depth-ordered chunks, for the caller who waits
  * for every frame (the reference's Render() returns after one: VolumeRenderer.cpp:1103-1339): the
  * rank's boxes are cut, in global layer order, into chunks of equal classify work; chunk k is
@@ -465,6 +487,19 @@ int avr_fold_plan_own(avr_context *ctx, const avr_frame_plan *plan, const float 
  * pixels.  out_rgb8_image: width * height * 3 bytes; out_piece as avr_fold_plan (may be NULL). */
 int avr_fold_plan_image(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
                         float *out_piece, uint8_t *out_rgb8_image);
+
+/* The max fold of a maximum-intensity frame (avr_render_plan_max): per pixel of the piece, the
+ * largest index among the covering runs that took a sample (max is exact and order-free).
+ * out_index (may be NULL): the piece's int16 indices, -1 where no run took a sample, in the order
+ * of avr_fold_plan's out_piece; out_rgb8 (may be NULL): Color::GetComponentAsByte of the RGB of
+ * that table entry, (0,0,0) for -1.  _own and _image as avr_fold_plan_own / avr_fold_plan_image
+ * (the image's bytes top-down; out_index stays in piece order). */
+int avr_fold_plan_max(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
+                      int16_t *out_index, uint8_t *out_rgb8);
+int avr_fold_plan_own_max(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
+                          const float *own_send_buffer, int16_t *out_index, uint8_t *out_rgb8);
+int avr_fold_plan_image_max(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
+                            int16_t *out_index, uint8_t *out_rgb8_image);
 
 /* ---- image algebra ----------------------------------------------------------------------- */
 
@@ -814,6 +849,19 @@ const char *avr_renderer_failure(const avr_renderer *renderer);
 int avr_renderer_render(avr_renderer *renderer, const avr_render_params *render,
                         const avr_camera *camera, const int32_t *group_order, void *input_stream,
                         uint64_t *samples_out, int want_image, uint8_t *rgb8_out, float *image_out);
+/* A maximum-intensity frame (avr_paint_box_max over the whole scene): classify pass, MIP march
+ * (avr_march_plan_max), the same exchange, the max fold (avr_fold_plan_own_max), the same gather.
+ * rgb8_out as avr_renderer_render: the colour of the pixel's largest index, (0,0,0) where no box
+ * takes a sample, rows top-down.  index_out (may be NULL; rank 0 only, NULL elsewhere):
+ * width*height int16 indices, -1 for none, in image_out's order (row 0 at the bottom); for N > 1
+ * the indices are gathered to rank 0 in every MIP frame.  Same completion rules as
+ * avr_renderer_render (a MIP frame's bytes are never deferred).  Frame chunks, occlusion culling
+ * and visibility speculation (which rest on opacity) are not used and not fed; the classified
+ * volume and its cache are shared with volume frames, which may alternate with MIP frames.
+ * render->antialiasing > 1 or draw_bounds: AVR_ERR_INVALID_ARGUMENT. */
+int avr_renderer_render_max(avr_renderer *renderer, const avr_render_params *render,
+                            const avr_camera *camera, const int32_t *group_order, void *input_stream,
+                            uint64_t *samples_out, uint8_t *rgb8_out, int16_t *index_out);
 /* Plans a frame ahead of time: makes the frame plan of (render, camera, group_order) -- visibility
  * order (VolumeRenderer.cpp:1235-1241), global layer order and exchange layout
  * (DirectSendBase.cpp:400-446), for N > 1 tightened to the runs' per-row extents -- and keeps it
