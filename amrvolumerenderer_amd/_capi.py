@@ -145,6 +145,10 @@ SIGNATURES = {
                                  C.POINTER(PaintParams), C.POINTER(Camera), _vp, _vp]),
     "avr_paint_box_max": (C.c_int, [_vp, C.POINTER(Box), C.POINTER(ScalarTransform),
                                      C.POINTER(PaintParams), C.POINTER(Camera), _vp, _vp]),
+    "avr_paint_box_projection": (C.c_int, [_vp, C.POINTER(Box), C.POINTER(PaintParams),
+                                            C.POINTER(Camera), _vp, _vp, _vp]),
+    "avr_projection_colorize": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                           C.c_int, _vp, _vp]),
     "avr_scene_create": (C.c_int, [_vp, C.POINTER(Box), C.c_int, C.POINTER(ScalarTransform),
                                     C.POINTER(_vp)]),
     "avr_scene_set_classification_cache": (C.c_int, [_vp, C.c_int]),
@@ -172,6 +176,8 @@ SIGNATURES = {
     "avr_render_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_render_plan_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_march_plan_max": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "avr_render_plan_projection": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_march_plan_projection": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
     "avr_classify_plan": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "avr_march_plan": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
     "avr_classify_plan_chunked": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp), C.c_int]),
@@ -187,6 +193,9 @@ SIGNATURES = {
     "avr_fold_plan_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_fold_plan_own_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "avr_fold_plan_image_max": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_projection": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_own_projection": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "avr_fold_plan_image_projection": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "avr_visibility_graph_create": (C.c_int, [C.POINTER(Box), C.POINTER(C.c_int32), C.c_int,
                                                C.c_int, C.POINTER(_vp)]),
     "avr_visibility_graph_destroy": (None, [_vp]),
@@ -253,6 +262,8 @@ SIGNATURES = {
                                        _vp, C.c_int, _vp, _vp]),
     "avr_renderer_render_max": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera), _ip,
                                            _vp, _vp, _vp, _vp]),
+    "avr_renderer_render_projection": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera),
+                                                  _ip, _vp, _vp, _vp, _vp]),
     "avr_renderer_prepare": (C.c_int, [_vp, C.POINTER(RenderParams), C.POINTER(Camera), _ip]),
     "avr_renderer_synchronize": (C.c_int, [_vp]),
     "avr_renderer_set_frame_chunks": (C.c_int, [_vp, C.c_int]),

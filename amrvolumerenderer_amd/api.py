@@ -56,6 +56,8 @@ class SceneGeometry:
     bounds: VolumeBounds
     scalar_range: Tuple[float, float] = (0.0, 1.0)
     processed_scalar_range: Optional[Tuple[float, float]] = None   # after log scaling, if any
+    # scene units per physical unit: plotfiles are rescaled so that their shortest edge is 1
+    world_scale: float = 1.0
 
 
 @dataclass
@@ -658,3 +660,119 @@ def _render_loaded_scene(ctx, scene: SceneGeometry, options: RenderOptions, rank
 def _replace(options: RenderOptions, **changes) -> RenderOptions:
     import dataclasses
     return dataclasses.replace(options, **changes)
+
+
+def validate_projection_arguments(width: int, height: int, quantity: str, log_scale: bool,
+                                  value_range: Optional[Sequence[float]]) -> Optional[Tuple[float, float]]:
+    """The argument checks of project(), before any GPU work: returns value_range as floats."""
+    from .renderer import validate_render_parameters, RenderParameters
+    from .runtime import PROJECTION_QUANTITIES
+    if quantity not in PROJECTION_QUANTITIES:
+        raise ValueError(f"quantity must be one of {', '.join(PROJECTION_QUANTITIES)}, not {quantity!r}")
+    validate_render_parameters(RenderParameters(width, height))
+    if value_range is None:
+        return None
+    values = tuple(value_range)
+    if len(values) != 2:
+        raise ValueError("value_range must hold two values (lo, hi)")
+    lo, hi = (float(v) for v in values)
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite")
+    if not (lo < hi):
+        raise ValueError("value_range must satisfy lo < hi")
+    if log_scale and not (lo > 0.0):
+        raise ValueError("value_range must be positive when log_scale is enabled")
+    return lo, hi
+
+
+def projection_rgb_table(color_map: Optional[Sequence[Sequence[float]]] = None):
+    """The 256 RGB8 entries of a projection picture: buildColorTable's colours of the colour map
+    over [0, 1] (entries (value, red, green, blue, alpha); alpha has no effect), each component as
+    Color::GetComponentAsByte makes it a byte -> [256, 3] uint8."""
+    import numpy as np
+    from .runtime import build_color_table
+    cmap = None
+    if color_map is not None:
+        cmap = []
+        for entry in color_map:
+            if len(tuple(entry)) != 5:
+                raise ValueError("color_map entries are (value, red, green, blue, alpha)")
+            cmap.append(ColorMapControlPoint(*[float(v) for v in entry]))
+    table = build_color_table(1.0, 1.0, (0.0, 1.0), cmap)[:, :3]
+    scaled = (table * np.float32(256.0)).astype(np.float32)
+    return np.clip(np.trunc(scaled), 0, 255).astype(np.uint8)
+
+
+def project(plotfile: str, width: int = 512, height: int = 512, variable: Optional[str] = None,
+            min_level: int = 0, max_level: int = -1,
+            camera_eye: Optional[Sequence[float]] = None,
+            camera_look_at: Optional[Sequence[float]] = None,
+            camera_up: Optional[Sequence[float]] = None, camera_fov_y: Optional[float] = None,
+            camera_near: Optional[float] = None, camera_far: Optional[float] = None,
+            quantity: str = "column", log_scale: bool = False,
+            value_range: Optional[Sequence[float]] = None,
+            color_map: Optional[Sequence[Sequence[float]]] = None, output: Optional[str] = None,
+            up_vector: Optional[Sequence[float]] = None):
+    """Line-integral projection of a plotfile's raw field (yt's ProjectionPlot; DESIGN.md, "Column
+    projection"), on cuda:0.  Per pixel, over the samples of the maximum-intensity march, column =
+    sum over boxes of step * (sum of the finite cell values) and length = sum of step * (their
+    number), with lengths in the plotfile's physical units (the geometry loader's rescale undone).
+    quantity "column" returns column (for a density, the surface density), "mean" column / length
+    (0 where length is 0).  Returns that array on rank 0 -- numpy float64 [height, width], row 0 at
+    the bottom like the image's origin -- and None on other ranks.  With output (.png, else PPM) rank
+    0 also writes the picture: q = the quantity (log10 of it with log_scale) -> colour-map entry
+    clamp(floor((q - lo) / (hi - lo) * 255), 0, 255) over value_range = (lo, hi) (log_scale: lo and
+    hi are quantities, not logarithms), or over the min and max of q when value_range is None;
+    pixels with length 0 (and, with log_scale, q <= 0) are black.  The camera arguments are
+    those of render(); without camera_eye / camera_look_at the automatic camera is used."""
+    rng = validate_projection_arguments(width, height, quantity, log_scale, value_range)
+    camera = None
+    if camera_eye is not None or camera_look_at is not None:
+        if camera_eye is None or camera_look_at is None:
+            raise ValueError("camera_eye and camera_look_at must be given together")
+        up = tuple(camera_up) if camera_up is not None else (0.0, 1.0, 0.0)
+        length = math.sqrt(sum(float(v) ** 2 for v in up))
+        up = tuple(float(v) / length for v in up) if (length > 0.0 and math.isfinite(length)) \
+            else (0.0, 0.0, -1.0)
+        camera = CameraParameters(tuple(camera_eye), tuple(camera_look_at), up,
+                                  45.0 if camera_fov_y is None else float(camera_fov_y),
+                                  0.1 if camera_near is None else float(camera_near),
+                                  1000.0 if camera_far is None else float(camera_far))
+    table = projection_rgb_table(color_map)
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    from . import plotfile as pf
+    from .renderer import FrameRenderer, RenderParameters
+    import torch
+    ctx, rank, world, group = _runtime_scope()
+    scene = pf.load_plotfile_geometry(ctx, plotfile, variable or "", min_level, max_level, False,
+                                      True, rank, world, group)
+    if camera is None:
+        camera = automatic_camera(scene.bounds,
+                                  up_vector=tuple(up_vector) if up_vector is not None else None)
+    renderer = FrameRenderer(ctx, scene.all_boxes, scene.local_boxes, scene.scalar_transform,
+                             scene.bounds, scene.scalar_range, rank, world, group)
+    column, length = renderer.render_projection(RenderParameters(width, height, draw_bounds=False),
+                                                camera)
+    renderer.synchronize()
+    if rank != 0:
+        return None
+    # scene lengths -> physical lengths
+    to_physical = 1.0 / float(scene.world_scale)
+    column = column * to_physical
+    length = length * to_physical
+    if quantity == "mean":
+        q = torch.where(length > 0.0, column / torch.where(length > 0.0, length, 1.0),
+                        torch.zeros_like(column))
+    else:
+        q = column
+    if output is not None:
+        rgb8, _ = ctx.projection_colorize(
+            column, length, torch.from_numpy(table).to(column.device), quantity, log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
+        if not writer(rgb8.cpu().numpy(), output):
+            raise RuntimeError(f"could not write '{output}'")
+    return q.cpu().numpy()

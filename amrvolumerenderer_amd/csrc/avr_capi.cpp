@@ -324,6 +324,7 @@ struct avr_context {
   uint64_t* march_counters = nullptr;          // diagnostics (avr_context_set_march_counters)
   void* max_layers = nullptr;                  // layer of avr_paint_box_max (grow-only)
   size_t max_layers_capacity = 0;
+  double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
 };
 
 
@@ -397,6 +398,10 @@ struct FrameChunks {
   // a maximum-intensity march (avr_render_plan_max / avr_march_plan_max / avr_paint_box_max): one
   // launch of render_runs_max_kernel, never chunked, culled or speculative
   bool max_intensity = false;
+  // a column-projection march (avr_render_plan_projection / avr_march_plan_projection /
+  // avr_paint_box_projection): one launch of render_runs_sum_kernel over the raw cells; no classify
+  // pass, the classified volume is neither read nor made
+  bool projection = false;
 };
 
 // Positions [bounds[k], bounds[k + 1]) of the global layer order for chunk k: equal shares of the
@@ -452,6 +457,8 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   require(slot >= 0 && slot < AVR_CLASSIFIED_SLOTS, "classified slot out of range");
   require(!chunks.max_intensity || (chunks.count == 1 && chunks.speculation == nullptr),
           "a maximum-intensity march is one launch: no chunks, no speculation");
+  require(!chunks.projection || (chunks.count == 1 && chunks.speculation == nullptr && phases == kMarch),
+          "a column-projection march is one launch: no classify pass, no chunks, no speculation");
   avr::FramePlan local;
   avr::FramePlan& plan = cached ? *cached : local;
   if (plan.boxes.size() != static_cast<size_t>(n_boxes) || !plan.ready) {
@@ -472,7 +479,8 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   // 0.378 ms per frame against 0.465 streamed; config-4's 370 MB are not, 0.967 -> 0.958)
   launch.classify_stream_stores =
       (ctx->classify_stream_stores && plan.classified_bytes > (256ull << 20)) ? 1 : 0;
-  launch.classified = scene->classified_slot(slot, plan.classified_bytes, ctx->stream);
+  launch.classified =
+      chunks.projection ? nullptr : scene->classified_slot(slot, plan.classified_bytes, ctx->stream);
 
   if ((phases & kClassify) && scene->cache_classification) {
     // everything classify_kernel reads besides the cells themselves
@@ -677,6 +685,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
     launch.n_items = static_cast<uint32_t>(items.size());
     launch.workgroups_per_cu = ctx->march_workgroups_per_cu;
     launch.max_intensity = chunks.max_intensity ? 1 : 0;
+    launch.projection = chunks.projection ? 1 : 0;
     launch.only_mode = plan.boxes.empty() ? -1 : plan.boxes[0].index_mode;
     for (const avr::BoxDev& dev : plan.boxes) {
       if (dev.index_mode != launch.only_mode) launch.only_mode = -1;
@@ -812,6 +821,7 @@ void avr_context_destroy(avr_context* ctx) {
   if (ctx->own_stream != nullptr) (void)hipStreamSynchronize(ctx->own_stream);
   ctx->staging.release();
   if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
+  if (ctx->colorize_scratch != nullptr) (void)hipFree(ctx->colorize_scratch);
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -1006,6 +1016,86 @@ int avr_paint_box_max(avr_context* ctx, const avr_box* box, const avr_scalar_tra
     launch.max_intensity = 1;
     launch.out_index = out_index;
     return avr::launch_fold_plan(launch, ctx->stream);
+  });
+}
+
+int avr_paint_box_projection(avr_context* ctx, const avr_box* box, const avr_paint_params* params,
+                             const avr_camera* camera, double* column, double* length,
+                             uint64_t* samples_out) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(box != nullptr && params != nullptr && camera != nullptr && column != nullptr &&
+                length != nullptr,
+            "null argument");
+    require(params->width > 0 && params->height > 0, "image width and height must be positive");
+    const int32_t order[1] = {0};
+    const int32_t run_end[1] = {1};
+    std::vector<avr::RunRectDev> rects;
+    std::vector<avr::RunBlockDev> blocks;
+    avr::dense_run_tables(params->width, params->height, 1, 1, &rects, &blocks);
+    const int64_t n_pixels = static_cast<int64_t>(params->width) * params->height;
+    const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
+    if (bytes > ctx->max_layers_capacity) {
+      avr::wait_stream(ctx->stream, "avr_paint_box_projection");
+      if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
+      ctx->max_layers = nullptr;
+      ctx->max_layers_capacity = 0;
+      avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(projection layer)");
+      ctx->max_layers_capacity = bytes;
+    }
+    float* layer = static_cast<float*>(ctx->max_layers);
+    const avr::PieceMapDev pieces =
+        avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height);
+    FrameChunks chunks;
+    chunks.projection = true;
+    const avr_scalar_transform transform{};  // (no classify pass: the raw values are summed)
+    int status = render(ctx, kMarch, box, 1, transform, *params, *camera, order, 1, run_end, 1, 1,
+                        rects, blocks, nullptr, pieces, &ctx->scratch_scene, 0, layer, samples_out,
+                        nullptr, chunks);
+    if (status != AVR_OK) return status;
+    // the layer -> f64 images: the sum fold over the one run (a pixel no box covers stays 0)
+    avr::FoldLaunch launch;
+    ctx->staging.begin(rects.size() * sizeof(avr::RunRectDev) + blocks.size() * sizeof(avr::RunBlockDev), 2);
+    launch.run_rects_dev = ctx->staging.add(rects.data(), rects.size());
+    launch.run_blocks_dev = ctx->staging.add(blocks.data(), blocks.size());
+    launch.run_spans_dev = nullptr;
+    ctx->staging.commit(ctx->stream);
+    launch.pieces = pieces;
+    launch.piece = 0;
+    launch.width = params->width;
+    launch.piece_begin = 0;
+    launch.piece_end = n_pixels;
+    launch.n_runs = 1;
+    launch.recv = layer;
+    launch.out_piece = nullptr;
+    launch.out_rgb8 = nullptr;
+    launch.projection = 1;
+    launch.out_column = column;
+    launch.out_length = length;
+    return avr::launch_fold_plan(launch, ctx->stream);
+  });
+}
+
+int avr_projection_colorize(avr_context* ctx, const double* column, const double* length, int width,
+                            int height, int quantity, int log_scale, double* range, int auto_range,
+                            const uint8_t* rgb_table, uint8_t* rgb8_out) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(column != nullptr && length != nullptr && range != nullptr && rgb_table != nullptr &&
+                rgb8_out != nullptr,
+            "null argument");
+    require(width > 0 && height > 0, "image width and height must be positive");
+    require(quantity == AVR_PROJECTION_COLUMN || quantity == AVR_PROJECTION_MEAN, "unknown quantity");
+    if (auto_range && ctx->colorize_scratch == nullptr) {
+      void* block = nullptr;
+      avr::hip_check(hipMalloc(&block, 2 * avr::kProjectionRangeWorkgroups * sizeof(double)),
+                     "hipMalloc(projection range)");
+      ctx->colorize_scratch = static_cast<double*>(block);
+    }
+    return avr::launch_projection_colorize(column, length, width, height,
+                                           quantity == AVR_PROJECTION_MEAN ? 1 : 0,
+                                           log_scale ? 1 : 0, range, auto_range ? 1 : 0,
+                                           ctx->colorize_scratch, rgb_table, rgb8_out, ctx->stream);
   });
 }
 
@@ -1302,6 +1392,20 @@ int avr_march_plan_max(avr_context* ctx, const avr_scene* scene, const avr_frame
   return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
 }
 
+int avr_render_plan_projection(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
+                               float* send_buffer, uint64_t* samples_out) {
+  FrameChunks chunks;
+  chunks.projection = true;
+  return plan_phase(ctx, kMarch, scene, plan, 0, send_buffer, samples_out, chunks);
+}
+
+int avr_march_plan_projection(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
+                              int slot, float* send_buffer, uint64_t* samples_out) {
+  FrameChunks chunks;
+  chunks.projection = true;
+  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+}
+
 int avr_classify_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                       int slot) {
   return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr);
@@ -1392,7 +1496,8 @@ int avr_fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* rec
 namespace {
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
               const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
-              int16_t* out_index = nullptr, bool max_intensity = false);
+              int16_t* out_index = nullptr, bool max_intensity = false,
+              double* out_column = nullptr, double* out_length = nullptr, bool projection = false);
 }
 
 int avr_fold_plan_own(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
@@ -1420,10 +1525,33 @@ int avr_fold_plan_image_max(avr_context* ctx, const avr_frame_plan* plan, const 
   return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, out_rgb8_image, true, out_index, true);
 }
 
+int avr_fold_plan_projection(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
+                             double* out_column, double* out_length) {
+  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, nullptr, false, nullptr, false,
+                   out_column, out_length, true);
+}
+
+int avr_fold_plan_own_projection(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
+                                 const float* own_send_buffer, double* out_column, double* out_length) {
+  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, nullptr, nullptr, false, nullptr, false,
+                   out_column, out_length, true);
+}
+
+int avr_fold_plan_image_projection(avr_context* ctx, const avr_frame_plan* plan,
+                                   const float* recv_buffer, double* out_column, double* out_length) {
+  if (plan != nullptr && plan->info.n_ranks != 1) {
+    avr::set_error("avr_fold_plan_image_projection is for one rank's whole image");
+    return AVR_ERR_INVALID_ARGUMENT;
+  }
+  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, nullptr, false, nullptr, false,
+                   out_column, out_length, true);
+}
+
 namespace {
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
               const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
-              int16_t* out_index, bool max_intensity) {
+              int16_t* out_index, bool max_intensity, double* out_column, double* out_length,
+              bool projection) {
   return guarded([&]() -> int {
     bind_device(ctx);
     require(plan != nullptr, "null argument");
@@ -1432,7 +1560,9 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
     // (a rank whose piece is empty -- more ranks than pixels, or row bands on a short image --
     // has nothing to fold and may pass empty buffers)
     if (plan->info.piece_end <= plan->info.piece_begin) return AVR_OK;
-    require(out_piece != nullptr || out_rgb8 != nullptr || out_index != nullptr, "null argument");
+    require(out_piece != nullptr || out_rgb8 != nullptr || out_index != nullptr ||
+                out_column != nullptr || out_length != nullptr,
+            "null argument");
     require(plan->info.recv_floats == 0 || recv_buffer != nullptr, "null receive buffer");
     avr::FoldLaunch launch;
     const bool spans = plan->tightened && !plan->recv_spans.empty();
@@ -1456,6 +1586,9 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
     launch.out_rgb8 = out_rgb8;
     launch.max_intensity = max_intensity ? 1 : 0;
     launch.out_index = out_index;
+    launch.projection = projection ? 1 : 0;
+    launch.out_column = out_column;
+    launch.out_length = out_length;
     // One rank folds the whole image while the next frame's paint kernels start, and nothing
     // waits for it: one workgroup per CU keeps it out of their way (0.997 -> 0.980 ms per frame).
     // A rank of several folds its piece on the stream that also carries the exchange and the

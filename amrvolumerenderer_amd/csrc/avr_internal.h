@@ -292,6 +292,9 @@ struct RenderLaunch {
   const uint8_t* visible_in = nullptr;
   // a maximum-intensity frame (render_runs_max_kernel): one launch, no speculation, no culling
   int max_intensity = 0;
+  // a column projection (render_runs_sum_kernel): no classify pass, the raw cells, no tables; one
+  // launch, no speculation, no culling
+  int projection = 0;
 };
 // classify pass (cells -> table indices) and march; the march reads what the classify pass of
 // the same frame wrote into `classified`
@@ -328,7 +331,24 @@ struct FoldLaunch {
   // index piece (piece order, -1 = no sample) goes to out_index (may be null)
   int max_intensity = 0;
   int16_t* out_index = nullptr;
+  // column projections (fold_plan_kernel<OWN, false, true>): the sum fold; out_piece and out_rgb8
+  // are not written, the f64 column and length pieces (piece order) go to out_column / out_length
+  // (either may be null)
+  int projection = 0;
+  double* out_column = nullptr;
+  double* out_length = nullptr;
 };
+// Picture of a column projection (width x height f64 column and length, row 0 at the bottom):
+// per pixel the quantity (column, or column / length if mean; log10 if log_scale) of pixels with
+// length > 0 (and a quantity > 0 under log) -> table entry clamp(floor((q - lo) / (hi - lo) * 255),
+// 0, 255) -> rgb_table's 3 bytes, (0, 0, 0) otherwise; rgb8 rows top-down.  range (device, 2 f64):
+// [lo, hi] -- computed there first if auto_range (min / max over the pixels that take part, (0, 1)
+// if none), with partial (device, 2 * kProjectionRangeWorkgroups f64) as scratch.
+constexpr int kProjectionRangeWorkgroups = 256;
+int launch_projection_colorize(const double* column, const double* length, int width, int height,
+                               int mean, int log_scale, double* range, int auto_range,
+                               double* partial, const uint8_t* rgb_table, uint8_t* rgb8,
+                               void* stream);
 int launch_fold_plan(const FoldLaunch& launch, void* stream);
 int launch_fold_runs(const float* const* slices_dev, int n_slices, float* out, int64_t n,
                      void* stream);

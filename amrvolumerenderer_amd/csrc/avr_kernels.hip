@@ -156,6 +156,20 @@ __device__ __forceinline__ uint32_t bricklet_offset(int i, int j, int k, uint32_
   return offset;
 }
 
+// LINEAR (the column projection, which reads the raw f64 cells): the byte offset of cell (i, j, k)
+// in the box's Array4, (i + j * jstride + k * kstride) * 8, with (y_pitch, x_pitch) = (jstride,
+// kstride); the box spans < 2^28 elements, so it fits 32 bits.  Otherwise bricklet_offset.
+template <bool LINEAR>
+__device__ __forceinline__ uint32_t cell_address(int i, int j, int k, uint32_t y_pitch,
+                                                 uint32_t x_pitch) {
+  if constexpr (LINEAR) {
+    return (static_cast<uint32_t>(i) + static_cast<uint32_t>(j) * y_pitch +
+            static_cast<uint32_t>(k) * x_pitch) << 3;
+  } else {
+    return bricklet_offset(i, j, k, y_pitch, x_pitch);
+  }
+}
+
 // Cell indices of an inside sample: the reference's clamp(int(floor((pos - min) / d)), 0, n - 1)
 // per axis (VolumePainter.cpp:846-867).  `fx` = pos - min >= 0 for an inside sample, so
 // truncation equals floor and only the upper clamp can bind on the multiply paths; the
@@ -166,7 +180,7 @@ __device__ __forceinline__ uint32_t bricklet_offset(int i, int j, int k, uint32_
 // half is an ordinary IEEE binary32 operation, so results equal the scalar expressions bit for bit).
 typedef float float_pair __attribute__((ext_vector_type(2)));
 
-template <int MODE, bool CLAMP, bool STATS>
+template <int MODE, bool CLAMP, bool STATS, bool LINEAR = false>
 __device__ __forceinline__ uint32_t offset_from_quotients(const BoxDev& box, uint32_t row_pitch,
                                                           uint32_t plane_pitch, float qx, float qy,
                                                           float qz, float fx, float fy, float fz,
@@ -195,10 +209,10 @@ __device__ __forceinline__ uint32_t offset_from_quotients(const BoxDev& box, uin
       k = (ek < 0) ? 0 : ((ek >= box.nz) ? box.nz - 1 : ek);
     }
   }
-  return bricklet_offset(i, j, k, row_pitch, plane_pitch);
+  return cell_address<LINEAR>(i, j, k, row_pitch, plane_pitch);
 }
 
-template <int MODE, bool STATS>
+template <int MODE, bool STATS, bool LINEAR = false>
 __device__ __forceinline__ uint32_t cell_offset(const BoxDev& box, uint32_t row_pitch,
                                                 uint32_t plane_pitch, float fx, float fy,
                                                 float fz, unsigned& near_hits) {
@@ -209,9 +223,9 @@ __device__ __forceinline__ uint32_t cell_offset(const BoxDev& box, uint32_t row_
     ei = (ei < 0) ? 0 : ((ei >= box.nx) ? box.nx - 1 : ei);
     ej = (ej < 0) ? 0 : ((ej >= box.ny) ? box.ny - 1 : ej);
     ek = (ek < 0) ? 0 : ((ek >= box.nz) ? box.nz - 1 : ek);
-    return bricklet_offset(ei, ej, ek, row_pitch, plane_pitch);
+    return cell_address<LINEAR>(ei, ej, ek, row_pitch, plane_pitch);
   }
-  return offset_from_quotients<MODE, true, STATS>(box, row_pitch, plane_pitch, fx * box.inv_dx,
+  return offset_from_quotients<MODE, true, STATS, LINEAR>(box, row_pitch, plane_pitch, fx * box.inv_dx,
                                                   fy * box.inv_dy, fz * box.inv_dz, fx, fy, fz,
                                                   near_hits);
 }
@@ -221,13 +235,21 @@ __device__ __forceinline__ uint32_t cell_offset(const BoxDev& box, uint32_t row_
 // MAX (maximum-intensity projection): the same samples at the same positions, but as if the
 // accumulator never saturated -- every sample up to tmax is taken -- and per sample one byte gather
 // and one integer max; returns the largest table index sampled, -1 if none.
-// (MAX takes the ray by value: by reference its fields were loaded as overlapping float pairs
-// from a stack copy that then stayed in scratch memory)
-template <bool STATS, int MODE, bool MAX = false>
-__device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const BoxDev& box, const FrameConsts& fc,
+// SUM (column projection): the samples of MAX, but per sample one f64 gather
+// of the raw cell value (box.cells, no classify pass, no table) and, if it is finite, one f64 add
+// in march order and one count; returns the sum and the count of the finite samples.
+// (MAX and SUM take the ray by value: by reference its fields were loaded as overlapping float
+// pairs from a stack copy that then stayed in scratch memory)
+struct ColumnSum {
+  double sum;
+  unsigned count;
+};
+template <bool STATS, int MODE, bool MAX = false, bool SUM = false>
+__device__ __forceinline__ std::conditional_t<SUM, ColumnSum, std::conditional_t<MAX, int, Layer5>>
+march_box(const BoxDev& box, const FrameConsts& fc,
                                             const uint8_t* __restrict__ classified,
                                             const float4* __restrict__ table,
-                                            std::conditional_t<MAX, const Ray, const Ray&> ray,
+                                            std::conditional_t<MAX || SUM, const Ray, const Ray&> ray,
                                             float tmin, float tmax, unsigned& fetches,
                                             unsigned& near_hits) {
   const float min_x = box.minc[0], min_y = box.minc[1], min_z = box.minc[2];
@@ -237,17 +259,33 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
       (const uint8_t __attribute__((address_space(1)))*)(classified + box.cls_offset);
   const uint32_t bricks_z = static_cast<uint32_t>(box.nz + kBrickZ - 1) >> 2;
   const uint32_t bricks_y = static_cast<uint32_t>(box.ny + kBrickY - 1) >> 2;
-  const uint32_t row_pitch = bricks_z * kBrickBytes - 32u;              // y_pitch of bricklet_offset
-  const uint32_t plane_pitch = bricks_y * bricks_z * kBrickBytes - 8u;  // x_pitch
+  const uint32_t row_pitch = SUM ? static_cast<uint32_t>(box.jstride)     // (cell_address<SUM>)
+                                 : bricks_z * kBrickBytes - 32u;              // y_pitch of bricklet_offset
+  const uint32_t plane_pitch = SUM ? static_cast<uint32_t>(box.kstride)
+                                   : bricks_y * bricks_z * kBrickBytes - 8u;  // x_pitch
+  // (SUM) the raw cells, addressed by byte offset
+  [[maybe_unused]] const uint8_t __attribute__((address_space(1)))* values =
+      (const uint8_t __attribute__((address_space(1)))*)(box.cells);
 
   float distance = tmin + box.mesh_eps;
   if (distance < 0.0f) distance = box.mesh_eps;
 
   float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
   [[maybe_unused]] int best = -1;  // (MAX)
+  [[maybe_unused]] double sum = 0.0;  // (SUM) finite values in march order, and their number
+  [[maybe_unused]] unsigned count = 0u;
 
 #define AVR_INSIDE(x, y, z) \
   (!((x) < min_x || (x) > max_x || (y) < min_y || (y) > max_y || (z) < min_z || (z) > max_z))
+#define AVR_VALUE(offset) \
+  (*reinterpret_cast<const double __attribute__((address_space(1)))*>(values + (offset)))
+// (adding 0.0 for a non-finite value is skipping it: the sum starts at +0 and never becomes -0)
+#define AVR_ADD(value)                                  \
+  do {                                                  \
+    const bool finite_ = __builtin_isfinite(value);     \
+    sum += finite_ ? (value) : 0.0;                     \
+    count += finite_ ? 1u : 0u;                         \
+  } while (0)
 #define AVR_ACCUMULATE(sample)                          \
   do {                                                  \
     const float alpha_ = (sample).w * (1.0f - acc_a);   \
@@ -323,9 +361,9 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
             const float_pair qx = __builtin_elementwise_fma(ray.ox + ray.dx * dd, ix2, nx2);
             const float_pair qy = __builtin_elementwise_fma(ray.oy + ray.dy * dd, iy2, ny2);
             const float_pair qz = __builtin_elementwise_fma(ray.oz + ray.dz * dd, iz2, nz2);
-            off[2 * pair] = bricklet_offset(static_cast<int>(qx.x), static_cast<int>(qy.x),
+            off[2 * pair] = cell_address<SUM>(static_cast<int>(qx.x), static_cast<int>(qy.x),
                                             static_cast<int>(qz.x), row_pitch, plane_pitch);
-            off[2 * pair + 1] = bricklet_offset(static_cast<int>(qx.y), static_cast<int>(qy.y),
+            off[2 * pair + 1] = cell_address<SUM>(static_cast<int>(qx.y), static_cast<int>(qy.y),
                                                 static_cast<int>(qz.y), row_pitch, plane_pitch);
           } else {
             // the reference's two roundings, (pos - min) then * RN(1/d), as in the loop of four
@@ -333,11 +371,21 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
             const float_pair fy = (ray.oy + ray.dy * dd) - min_y;
             const float_pair fz = (ray.oz + ray.dz * dd) - min_z;
             const float_pair qx = fx * inv_x, qy = fy * inv_y, qz = fz * inv_z;
-            off[2 * pair] = offset_from_quotients<MODE, false, STATS>(
+            off[2 * pair] = offset_from_quotients<MODE, false, STATS, SUM>(
                 box, row_pitch, plane_pitch, qx.x, qy.x, qz.x, fx.x, fy.x, fz.x, near_hits);
-            off[2 * pair + 1] = offset_from_quotients<MODE, false, STATS>(
+            off[2 * pair + 1] = offset_from_quotients<MODE, false, STATS, SUM>(
                 box, row_pitch, plane_pitch, qx.y, qy.y, qz.y, fx.y, fy.y, fz.y, near_hits);
           }
+        }
+        if constexpr (SUM) {
+          double v[kDeep];
+#pragma unroll
+          for (int i = 0; i < kDeep; ++i) v[i] = AVR_VALUE(off[i]);
+#pragma unroll
+          for (int i = 0; i < kDeep; ++i) AVR_ADD(v[i]);
+          distance = d[kDeep - 1] + step;
+          if (STATS) fetches += static_cast<unsigned>(kDeep);
+          continue;
         }
         int idx[kDeep];
 #pragma unroll
@@ -409,19 +457,19 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
       if (!(d4 < safe_end)) break;
       uint32_t off1, off2, off3, off4;
       if (MODE == kExactDivide) {
-        off1 = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch,
+        off1 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d1) - min_x,
                                         (ray.oy + ray.dy * d1) - min_y,
                                         (ray.oz + ray.dz * d1) - min_z, near_hits);
-        off2 = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch,
+        off2 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d2) - min_x,
                                         (ray.oy + ray.dy * d2) - min_y,
                                         (ray.oz + ray.dz * d2) - min_z, near_hits);
-        off3 = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch,
+        off3 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d3) - min_x,
                                         (ray.oy + ray.dy * d3) - min_y,
                                         (ray.oz + ray.dz * d3) - min_z, near_hits);
-        off4 = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch,
+        off4 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d4) - min_x,
                                         (ray.oy + ray.dy * d4) - min_y,
                                         (ray.oz + ray.dz * d4) - min_z, near_hits);
@@ -437,13 +485,13 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
         const float_pair qx34 = __builtin_elementwise_fma(ray.ox + ray.dx * d34, ix2, nx2);
         const float_pair qy34 = __builtin_elementwise_fma(ray.oy + ray.dy * d34, iy2, ny2);
         const float_pair qz34 = __builtin_elementwise_fma(ray.oz + ray.dz * d34, iz2, nz2);
-        off1 = bricklet_offset(static_cast<int>(qx12.x), static_cast<int>(qy12.x),
+        off1 = cell_address<SUM>(static_cast<int>(qx12.x), static_cast<int>(qy12.x),
                                static_cast<int>(qz12.x), row_pitch, plane_pitch);
-        off2 = bricklet_offset(static_cast<int>(qx12.y), static_cast<int>(qy12.y),
+        off2 = cell_address<SUM>(static_cast<int>(qx12.y), static_cast<int>(qy12.y),
                                static_cast<int>(qz12.y), row_pitch, plane_pitch);
-        off3 = bricklet_offset(static_cast<int>(qx34.x), static_cast<int>(qy34.x),
+        off3 = cell_address<SUM>(static_cast<int>(qx34.x), static_cast<int>(qy34.x),
                                static_cast<int>(qz34.x), row_pitch, plane_pitch);
-        off4 = bricklet_offset(static_cast<int>(qx34.y), static_cast<int>(qy34.y),
+        off4 = cell_address<SUM>(static_cast<int>(qx34.y), static_cast<int>(qy34.y),
                                static_cast<int>(qz34.y), row_pitch, plane_pitch);
       } else {
         // the reference's two roundings, (pos - min) then * RN(1/d), two samples per instruction
@@ -454,18 +502,31 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
         const float_pair qx12 = fx12 * inv_x, qx34 = fx34 * inv_x;
         const float_pair qy12 = fy12 * inv_y, qy34 = fy34 * inv_y;
         const float_pair qz12 = fz12 * inv_z, qz34 = fz34 * inv_z;
-        off1 = offset_from_quotients<MODE, false, STATS>(box, row_pitch, plane_pitch, qx12.x,
+        off1 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx12.x,
                                                          qy12.x, qz12.x, fx12.x, fy12.x, fz12.x,
                                                          near_hits);
-        off2 = offset_from_quotients<MODE, false, STATS>(box, row_pitch, plane_pitch, qx12.y,
+        off2 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx12.y,
                                                          qy12.y, qz12.y, fx12.y, fy12.y, fz12.y,
                                                          near_hits);
-        off3 = offset_from_quotients<MODE, false, STATS>(box, row_pitch, plane_pitch, qx34.x,
+        off3 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx34.x,
                                                          qy34.x, qz34.x, fx34.x, fy34.x, fz34.x,
                                                          near_hits);
-        off4 = offset_from_quotients<MODE, false, STATS>(box, row_pitch, plane_pitch, qx34.y,
+        off4 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx34.y,
                                                          qy34.y, qz34.y, fx34.y, fy34.y, fz34.y,
                                                          near_hits);
+      }
+      if constexpr (SUM) {
+        const double v1 = AVR_VALUE(off1);
+        const double v2 = AVR_VALUE(off2);
+        const double v3 = AVR_VALUE(off3);
+        const double v4 = AVR_VALUE(off4);
+        AVR_ADD(v1);
+        AVR_ADD(v2);
+        AVR_ADD(v3);
+        AVR_ADD(v4);
+        distance = d4 + step;
+        if (STATS) fetches += 4u;
+        continue;
       }
       const int idx1 = cells[off1];
       const int idx2 = cells[off2];
@@ -565,10 +626,15 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
   // The reference's skip loop (:830-835) and the "continue" branch of the main loop (:838-844)
   // do the same thing -- advance without sampling while the position is outside -- so one loop
   // with an inside test reproduces both.
-  while (distance < tmax && (MAX || acc_a < 1.0f)) {
+  while (distance < tmax && (MAX || SUM || acc_a < 1.0f)) {
     if (AVR_INSIDE(pos_x, pos_y, pos_z)) {
-      const uint32_t offset = cell_offset<MODE, STATS>(box, row_pitch, plane_pitch, pos_x - min_x,
+      const uint32_t offset = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch, pos_x - min_x,
                                                        pos_y - min_y, pos_z - min_z, near_hits);
+      if constexpr (SUM) {
+        const double v = AVR_VALUE(offset);
+        if (STATS) ++fetches;
+        AVR_ADD(v);
+      } else {
       // the cell's transfer-function table index, computed from the f64 cell value by the
       // classify pass of this frame (same arithmetic as VolumePainter.cpp:870-883)
       const int idx = cells[offset];
@@ -579,6 +645,7 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
         const float4 sample = table[idx];
         AVR_ACCUMULATE(sample);
       }
+      }
     }
     distance += step;
     pos_x = ray.ox + ray.dx * distance;
@@ -587,8 +654,12 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
   }
 #undef AVR_INSIDE
 #undef AVR_ACCUMULATE
+#undef AVR_VALUE
+#undef AVR_ADD
 
-  if constexpr (MAX) {
+  if constexpr (SUM) {
+    return ColumnSum{sum, count};
+  } else if constexpr (MAX) {
     return best;
   } else {
     // device-side clamp (:902-905) then the host epilogue's std::clamp to [0,1] (:944-947)
@@ -627,7 +698,13 @@ __device__ __forceinline__ std::conditional_t<MAX, int, Layer5> march_box(const 
 // to its end (march_box<..., true>: no opacity, no skipped box) and the run's pixel is the largest
 // table index.  Layer encoding, so that plan, tightening, exchange and gather carry it unchanged:
 // a hit is (RGB of table entry `index`, 1, index), a miss the cleared pixel (0, 0, 0, 0, +inf).
-template <bool STATS, int ONLY_MODE, bool SPEC, bool MAX = false>
+// SUM: a column-projection frame (render_runs_sum_kernel; never with SPEC, chunks or culling): as
+// MAX, but march_box<..., SUM> gathers the raw f64 cells (no classify pass, no tables in LDS) and
+// the run's pixel is column = sum of f64(step) * S_b and length = sum of f64(step) * n_b over its
+// boxes in order.  A hit (length > 0) is (column lo, column hi, length lo, 1, length hi) -- the
+// 32-bit halves of the two f64 as float bit patterns, which the plan, tightening, exchange and
+// gather copy without looking at them -- a miss the cleared pixel.
+template <bool STATS, int ONLY_MODE, bool SPEC, bool MAX = false, bool SUM = false>
 __device__ __forceinline__ void
 render_runs_body(
     const FrameConsts& fc, const BoxDev* __restrict__ boxes,
@@ -693,12 +770,14 @@ render_runs_body(
   }
 
   // ---- stage the transfer-function tables in LDS (one per AMR sampling level) -------------
+  if constexpr (!SUM) {
   {
     const float4* src = reinterpret_cast<const float4*>(tables);
     const int total = n_tables * kTableSize;
     for (int e = threadIdx.x; e < total; e += kBlockThreads) lds_tables[e] = src[e];
   }
   __syncthreads();
+  }
 
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   const int lane = static_cast<int>(threadIdx.x) & 63;
@@ -755,7 +834,8 @@ render_runs_body(
     const int end = (run_end[run] < pos_end) ? run_end[run] : pos_end;
     Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, AVR_INF};  // cleared layer pixel: exact blend identity
     [[maybe_unused]] int acc_index = -1;              // (MAX) the run's largest index so far
-    if (!MAX && resume != 0) {
+    [[maybe_unused]] double acc_column = 0.0, acc_length = 0.0;  // (SUM) the run's sums so far
+    if (!MAX && !SUM && resume != 0) {
       const float* src = layer_pixel();
       if (src != nullptr) {
         acc.r = src[0];
@@ -820,6 +900,32 @@ render_runs_body(
                                                      fetches, near_hits);
           }
           acc_index = (m > acc_index) ? m : acc_index;
+        }
+        continue;
+      }
+      if constexpr (SUM) {
+        if (!__builtin_amdgcn_ballot_w64(hit)) continue;
+        if (hit) {
+          ColumnSum c;
+          if (ONLY_MODE == kPow2Multiply) {
+            c = march_box<STATS, kPow2Multiply, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+                                                             tmax, fetches, near_hits);
+          } else if (ONLY_MODE == kReciprocal) {
+            c = march_box<STATS, kReciprocal, false, true>(box, fc, nullptr, nullptr, ray, tmin, tmax,
+                                                           fetches, near_hits);
+          } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
+            c = march_box<STATS, kPow2Multiply, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+                                                             tmax, fetches, near_hits);
+          } else if (box.index_mode == kReciprocal) {
+            c = march_box<STATS, kReciprocal, false, true>(box, fc, nullptr, nullptr, ray, tmin, tmax,
+                                                           fetches, near_hits);
+          } else {
+            c = march_box<STATS, kExactDivide, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+                                                            tmax, fetches, near_hits);
+          }
+          const double step = static_cast<double>(box.sample_dist);
+          acc_column += step * c.sum;
+          acc_length += step * static_cast<double>(c.count);
         }
         continue;
       }
@@ -891,7 +997,7 @@ render_runs_body(
     // a + 1 * (1 - a), which need not round to 1), so every later box the pixel's ray hits counts
     // as visible.  By induction a box flagged invisible finds, at every pixel that hits it, the
     // accumulator this launch left -- and is skipped.
-    if (!MAX && visible_out != nullptr) {
+    if (!MAX && !SUM && visible_out != nullptr) {
       bool open = false;  // an earlier box to come is marched at this pixel
       // (the run's boxes behind this launch's; a run that only starts behind them: all of its boxes)
       for (int position = (end > run_begin) ? end : run_begin; position < run_end[run]; ++position) {
@@ -922,6 +1028,16 @@ render_runs_body(
       if (acc_index >= 0) {  // RGB does not depend on the level (only alpha does): any table will do
         const float4 c = lds_tables[acc_index];
         acc = {c.x, c.y, c.z, 1.0f, static_cast<float>(acc_index)};
+      }
+    }
+    if constexpr (SUM) {
+      if (acc_length > 0.0) {
+        const uint64_t column = static_cast<uint64_t>(__double_as_longlong(acc_column));
+        const uint64_t length = static_cast<uint64_t>(__double_as_longlong(acc_length));
+        acc = {__uint_as_float(static_cast<uint32_t>(column)),
+               __uint_as_float(static_cast<uint32_t>(column >> 32)),
+               __uint_as_float(static_cast<uint32_t>(length)), 1.0f,
+               __uint_as_float(static_cast<uint32_t>(length >> 32))};
       }
     }
     // (a resumed launch stores every pixel again, reached or not: keeping "was it reached" per lane
@@ -994,6 +1110,11 @@ __global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARC
 template <bool STATS, int ONLY_MODE>
 __global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_max_kernel(AVR_MARCH_PARAMETERS) {
   render_runs_body<STATS, ONLY_MODE, false, true>(AVR_MARCH_ARGUMENTS);
+}
+// The column-projection march (render_runs_body<..., SUM = true>).
+template <bool STATS, int ONLY_MODE>
+__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_sum_kernel(AVR_MARCH_PARAMETERS) {
+  render_runs_body<STATS, ONLY_MODE, false, false, true>(AVR_MARCH_ARGUMENTS);
 }
 #undef AVR_MARCH_PARAMETERS
 #undef AVR_MARCH_ARGUMENTS
@@ -1473,7 +1594,11 @@ struct FoldEntry {
 // order-free; the bytes are its table RGB, and `out_piece` (optional) is then an int16_t index
 // piece, -1 for a miss.  (The parameter list stays that of the blend fold: its instantiations
 // compile to the instructions they had before MAX.)
-template <bool OWN, bool MAX = false>
+// SUM (column projections): the covering runs with a hit (a != 0) are added in fold order, column
+// and length in f64 (see render_runs_body for the encoding); `out_piece` (optional) is then the
+// f64 column piece and `out_rgb8` (optional) the f64 length piece, 0 where no run took a finite
+// sample.
+template <bool OWN, bool MAX = false, bool SUM = false>
 __global__ __launch_bounds__(256) void fold_plan_kernel(
     const int width, const int64_t piece_begin, const int64_t piece_end, const int n_runs,
     const RunRectDev* __restrict__ rects, const RunBlockDev* __restrict__ blocks,
@@ -1505,6 +1630,7 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
   const bool live = (px < width) && (p >= piece_begin) && (p < piece_end);
 
   Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, MAX ? -1.0f : AVR_INF};
+  [[maybe_unused]] double column = 0.0, length = 0.0;  // (SUM)
   for (int chunk = 0; chunk < n_runs; chunk += 256) {
     const int g = chunk + tid;
     bool touches = false;
@@ -1547,7 +1673,14 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
       if (live && px >= run.x0 && px <= run.x1) {
         const float* src = recv + run.base + static_cast<int64_t>(px) * 5;
         const Layer5 layer = {src[0], src[1], src[2], src[3], src[4]};
-        if constexpr (MAX) {
+        if constexpr (SUM) {
+          if (layer.a != 0.0f) {
+            column += __longlong_as_double(static_cast<long long>(
+                (static_cast<uint64_t>(__float_as_uint(layer.g)) << 32) | __float_as_uint(layer.r)));
+            length += __longlong_as_double(static_cast<long long>(
+                (static_cast<uint64_t>(__float_as_uint(layer.d)) << 32) | __float_as_uint(layer.b)));
+          }
+        } else if constexpr (MAX) {
           if (layer.a != 0.0f && layer.d > acc.d) acc = layer;
         } else {
           acc = blend_depthsort(acc, layer);
@@ -1558,6 +1691,11 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
   }
   if (!live) continue;  // (after the chunk loop's closing barrier: the list is free again)
   const int64_t q = p - piece_begin;
+  if constexpr (SUM) {
+    if (out_piece != nullptr) reinterpret_cast<double*>(out_piece)[q] = column;
+    if (out_rgb8 != nullptr) reinterpret_cast<double*>(out_rgb8)[q] = length;
+    continue;
+  }
   if (!MAX && out_piece != nullptr) {
     float* d = out_piece + q * 5;
     d[0] = acc.r;
@@ -1584,6 +1722,110 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
     }
   }
   }  // segments
+}
+
+// ---- column projection pictures (avr_projection_colorize) ------------------------------------
+// The displayed quantity of pixel p and whether it takes part: column, or column / length for the
+// mean, optionally log10; only pixels with length > 0 (and, under log, a quantity > 0) do.
+__device__ __forceinline__ bool projection_quantity(const double* __restrict__ column,
+                                                    const double* __restrict__ length, int64_t p,
+                                                    int mean, int log_scale, double& q) {
+  const double l = length[p];
+  if (!(l > 0.0)) return false;
+  q = mean ? column[p] / l : column[p];
+  if (log_scale) {
+    if (!(q > 0.0)) return false;
+    q = log10(q);
+  }
+  return __builtin_isfinite(q);
+}
+
+// min / max of the eligible quantities: one (min, max) pair per workgroup into partial
+__global__ __launch_bounds__(256) void projection_range_kernel(
+    const double* __restrict__ column, const double* __restrict__ length, int64_t n, int mean,
+    int log_scale, double* __restrict__ partial) {
+  __shared__ double lo_s[256], hi_s[256];
+  double lo = AVR_INF, hi = -AVR_INF;
+  for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < n;
+       p += static_cast<int64_t>(gridDim.x) * 256) {
+    double q;
+    if (projection_quantity(column, length, p, mean, log_scale, q)) {
+      lo = (q < lo) ? q : lo;
+      hi = (q > hi) ? q : hi;
+    }
+  }
+  lo_s[threadIdx.x] = lo;
+  hi_s[threadIdx.x] = hi;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if (static_cast<int>(threadIdx.x) < half) {
+      const double l2 = lo_s[threadIdx.x + half], h2 = hi_s[threadIdx.x + half];
+      lo_s[threadIdx.x] = (l2 < lo_s[threadIdx.x]) ? l2 : lo_s[threadIdx.x];
+      hi_s[threadIdx.x] = (h2 > hi_s[threadIdx.x]) ? h2 : hi_s[threadIdx.x];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = lo_s[0];
+    partial[2 * blockIdx.x + 1] = hi_s[0];
+  }
+}
+
+// the workgroups' pairs -> range[0..1]; (0, 1) when no pixel takes part
+__global__ __launch_bounds__(256) void projection_range_final_kernel(const double* __restrict__ partial,
+                                                                     int n_partial,
+                                                                     double* __restrict__ range) {
+  __shared__ double lo_s[256], hi_s[256];
+  double lo = AVR_INF, hi = -AVR_INF;
+  for (int i = static_cast<int>(threadIdx.x); i < n_partial; i += 256) {
+    lo = (partial[2 * i] < lo) ? partial[2 * i] : lo;
+    hi = (partial[2 * i + 1] > hi) ? partial[2 * i + 1] : hi;
+  }
+  lo_s[threadIdx.x] = lo;
+  hi_s[threadIdx.x] = hi;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if (static_cast<int>(threadIdx.x) < half) {
+      const double l2 = lo_s[threadIdx.x + half], h2 = hi_s[threadIdx.x + half];
+      lo_s[threadIdx.x] = (l2 < lo_s[threadIdx.x]) ? l2 : lo_s[threadIdx.x];
+      hi_s[threadIdx.x] = (h2 > hi_s[threadIdx.x]) ? h2 : hi_s[threadIdx.x];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const bool any = lo_s[0] <= hi_s[0];
+    range[0] = any ? lo_s[0] : 0.0;
+    range[1] = any ? hi_s[0] : 1.0;
+  }
+}
+
+// pixel -> table entry clamp(floor((q - lo) / (hi - lo) * 255), 0, 255) -> its RGB8 (rgb_table:
+// 256 x 3 bytes); (0, 0, 0) for a pixel that takes no part; output rows top-down.  hi <= lo: entry 0.
+__global__ __launch_bounds__(256) void projection_colorize_kernel(
+    const double* __restrict__ column, const double* __restrict__ length, int width, int height,
+    int mean, int log_scale, const double* __restrict__ range, const uint8_t* __restrict__ rgb_table,
+    uint8_t* __restrict__ rgb8) {
+  const int64_t n = static_cast<int64_t>(width) * height;
+  const double lo = range[0], hi = range[1];
+  const double span = hi - lo;
+  for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < n;
+       p += static_cast<int64_t>(gridDim.x) * 256) {
+    double q;
+    uint8_t r = 0, g = 0, b = 0;
+    if (projection_quantity(column, length, p, mean, log_scale, q)) {
+      const double t = (span > 0.0) ? floor((q - lo) / span * 255.0) : 0.0;
+      const int entry = (t >= 255.0) ? 255 : ((t > 0.0) ? static_cast<int>(t) : 0);
+      r = rgb_table[entry * 3];
+      g = rgb_table[entry * 3 + 1];
+      b = rgb_table[entry * 3 + 2];
+    }
+    const int64_t y = p / width;
+    const int64_t x = p - y * width;
+    uint8_t* d = rgb8 + ((height - 1 - y) * width + x) * 3;
+    d[0] = r;
+    d[1] = g;
+    d[2] = b;
+  }
 }
 
 // downsampleImage (VolumeRenderer.cpp:479-528): sums in dy-major, dx-minor order.
@@ -1769,7 +2011,8 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
   const int tiles_y = (L.consts.height + kTile - 1) / kTile;
   const unsigned blocks = L.n_items * kSuperTileTiles;
   if (blocks == 0) return AVR_OK;
-  size_t lds_bytes = static_cast<size_t>(L.n_tables) * kTableSize * sizeof(float4);
+  // (a column projection reads no tables)
+  size_t lds_bytes = L.projection ? 0 : static_cast<size_t>(L.n_tables) * kTableSize * sizeof(float4);
   if (L.workgroups_per_cu > 0) {
     // Occupancy cap through the LDS allocation: n workgroups of 160 KiB / n minus a share of the
     // 10 KiB left for the co-resident kernel's own LDS (classify_kernel stages 2 KiB per workgroup).
@@ -1797,7 +2040,7 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
                      L.out_layers, L.samples_out, L.counters, L.pos_begin,                       \
                      (L.pos_end < 0 ? L.n_order : L.pos_end), L.resume, L.visible_out, L.spec_dev)
   if (L.spec_dev != nullptr) {
-    if (L.max_intensity) {
+    if (L.max_intensity || L.projection) {
       set_error("render_runs_kernel: a maximum-intensity frame is not speculative");
       return AVR_ERR_INVALID_ARGUMENT;
     }
@@ -1849,6 +2092,29 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
     }
 #undef AVR_LAUNCH_MAX
     return check_launch("render_runs_max_kernel");
+  }
+  if (L.projection) {
+    if (L.resume != 0 || L.visible_out != nullptr) {
+      set_error("render_runs_sum_kernel: a column projection is one launch, not chunks");
+      return AVR_ERR_INVALID_ARGUMENT;
+    }
+#define AVR_LAUNCH_SUM(STATS, ONLY)                                                             \
+  hipLaunchKernelGGL((render_runs_sum_kernel<STATS, ONLY>), dim3(blocks), dim3(kBlockThreads),  \
+                     lds_bytes, stream, L.consts, L.boxes_dev, nullptr, nullptr,                 \
+                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
+                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
+                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
+                     tiles_y, L.items_dev, L.out_layers, L.samples_out, L.counters, L.pos_begin, \
+                     (L.pos_end < 0 ? L.n_order : L.pos_end), 0, nullptr, nullptr)
+    if (L.only_mode == kPow2Multiply) {
+      if (stats) AVR_LAUNCH_SUM(true, kPow2Multiply); else AVR_LAUNCH_SUM(false, kPow2Multiply);
+    } else if (L.only_mode == kReciprocal) {
+      if (stats) AVR_LAUNCH_SUM(true, kReciprocal); else AVR_LAUNCH_SUM(false, kReciprocal);
+    } else {
+      if (stats) AVR_LAUNCH_SUM(true, -1); else AVR_LAUNCH_SUM(false, -1);
+    }
+#undef AVR_LAUNCH_SUM
+    return check_launch("render_runs_sum_kernel");
   }
   if (L.only_mode == kPow2Multiply) {
     if (stats) AVR_LAUNCH(true, kPow2Multiply); else AVR_LAUNCH(false, kPow2Multiply);
@@ -1944,6 +2210,17 @@ int launch_fold_plan(const FoldLaunch& L, void* stream_v) {
                        L.own_delta, static_cast<int>(blocks), L.flip_height);
     return check_launch("fold_plan_kernel (maximum intensity)");
   }
+  if (L.projection) {
+    auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true, false, true>
+                                            : fold_plan_kernel<false, false, true>;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
+                       L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,
+                       reinterpret_cast<float*>(L.out_column), reinterpret_cast<uint8_t*>(L.out_length),
+                       first_row, chunks_per_row, L.pieces, L.piece, L.own_begin, L.own_end,
+                       L.own_delta, static_cast<int>(blocks), 0);
+    return check_launch("fold_plan_kernel (column projection)");
+  }
   auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true> : fold_plan_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
                      static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
@@ -2027,4 +2304,26 @@ int launch_quantize(const float* src, int w, int h, int stride, uint8_t* dst, vo
   return check_launch("quantize_kernel");
 }
 
+}  // namespace avr
+
+namespace avr {
+int launch_projection_colorize(const double* column, const double* length, int width, int height,
+                               int mean, int log_scale, double* range, int auto_range,
+                               double* partial, const uint8_t* rgb_table, uint8_t* rgb8,
+                               void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const int64_t n = static_cast<int64_t>(width) * height;
+  if (n <= 0) return AVR_OK;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, kProjectionRangeWorkgroups));
+  if (auto_range) {
+    hipLaunchKernelGGL(projection_range_kernel, dim3(grid), dim3(256), 0, stream, column, length, n,
+                       mean, log_scale, partial);
+    hipLaunchKernelGGL(projection_range_final_kernel, dim3(1), dim3(256), 0, stream, partial,
+                       static_cast<int>(grid), range);
+  }
+  hipLaunchKernelGGL(projection_colorize_kernel,
+                     dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 2048))), dim3(256),
+                     0, stream, column, length, width, height, mean, log_scale, range, rgb_table, rgb8);
+  return check_launch("projection_colorize_kernel");
+}
 }  // namespace avr

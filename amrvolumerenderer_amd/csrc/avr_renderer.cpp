@@ -198,6 +198,10 @@ struct avr_renderer {
   // piece buffers alternate.  avr_renderer_synchronize sends what is still pending (collective).
   DeviceBuffer piece_rgb8_odd;
   DeviceBuffer piece_index, full_index;  // maximum-intensity frames of ranks of several
+  // column-projection frames: their own send buffer, f64 pieces and (row bands) gathered images,
+  // and the event that frees the send buffer again
+  DeviceBuffer projection_send, projection_piece, projection_full;
+  hipEvent_t projection_done = nullptr;
   int deferred_gather = -1;  // avr_renderer_set_deferred_gather: -1 = ranks of several
   struct PendingGather {
     bool valid = false;
@@ -379,6 +383,7 @@ struct avr_renderer {
       }
     }
     if (input_event != nullptr) (void)hipEventDestroy(input_event);
+    if (projection_done != nullptr) (void)hipEventDestroy(projection_done);
     if (epoch != nullptr) (void)hipEventDestroy(epoch);
     forget_plans();
     if (visibility != nullptr) avr_visibility_graph_destroy(visibility);
@@ -1869,6 +1874,137 @@ int render_frame(avr_renderer* r, const avr_render_params* render, const avr_cam
   });
 }
 
+
+// A column-projection frame (avr_renderer_render_projection): the projection march on stream M,
+// then on stream X the same exchange (carrying a deferred RGB8 gather of the frame before, as a
+// volume frame's would), the sum fold and the f64 gathers.  It has buffers of its own and leaves
+// the frame counter, the classified volumes, the send buffers of the pipelined frames, the co-run
+// tuner and the speculation alone, so that the volume and MIP frames around it are what they
+// would be without it.
+int render_projection_frame(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
+                            const int32_t* group_order, void* input_stream, uint64_t* samples_out,
+                            double* column_out, double* length_out) {
+  return guarded_renderer(r, [&]() -> int {
+    require(render != nullptr && camera != nullptr, "null argument");
+    const int root = validate(*render);
+    require(root == 1, "a column projection has no antialiasing (render->antialiasing must be 1)");
+    require(!render->draw_bounds, "a column projection has no wireframe (draw_bounds must be 0)");
+    hip_ok(hipSetDevice(r->device), "hipSetDevice");
+    const bool is_root = r->rank == 0;
+    require(!is_root || (column_out != nullptr && length_out != nullptr),
+            "the root rank needs column and length output buffers");
+    require(is_root || (column_out == nullptr && length_out == nullptr),
+            "column_out and length_out are rank 0's");
+    r->stage = "frame plan";
+    const avr_frame_plan* plan = plan_for(r, *render, *camera, group_order, /*use=*/true);
+    const avr_frame_plan_info& info = plan->info;
+    const int64_t piece_pixels = info.piece_end - info.piece_begin;
+    const bool many = r->n_ranks > 1;
+    if (many && r->plan_check != 0 && plan->agreed_epoch != r->settings_epoch) {
+      r->stage = "plan agreement (control plane)";
+      abi_ok(avr_frame_plan_agree(plan, r->comm, r->compose, r->settings_digest()));
+      plan->agreed_epoch = r->settings_epoch;
+    }
+    const bool banded = info.piece_layout == AVR_PIECES_ROW_BANDS;
+    const int64_t n_pixels = info.n_pixels;
+    auto bytes_of = [](int64_t count, int each) {
+      return static_cast<size_t>(std::max<int64_t>(count, 1)) * static_cast<size_t>(each);
+    };
+    hipStream_t stream_m = r->stream_of(r->march);
+    hipStream_t stream_x = r->stream_of(r->compose);
+    // (a buffer that grows waits for everything queued; the co-run tuner is not told: nothing of
+    // the pipelined frames' timing is this frame's)
+    auto drain = [&] {
+      for (avr_context* ctx : {r->classify, r->march, r->compose, r->pair_b}) {
+        if (ctx != nullptr) avr::wait_stream_deadline(r->stream_of(ctx), "a stream before a column projection");
+      }
+    };
+    r->stage = "frame buffers";
+    float* send = static_cast<float*>(r->projection_send.reserve(bytes_of(info.send_floats, 4), drain));
+    float* recv = many ? static_cast<float*>(r->recv.reserve(bytes_of(info.recv_floats, 4), drain))
+                       : nullptr;
+    double* piece = nullptr;     // ranks of several: column piece, then length piece
+    double* gathered = nullptr;  // root of several: column image, then length image (piece-major)
+    if (many) {
+      piece = static_cast<double*>(r->projection_piece.reserve(bytes_of(2 * piece_pixels, 8), drain));
+      if (is_root && banded) {
+        gathered = static_cast<double*>(r->projection_full.reserve(bytes_of(2 * n_pixels, 8), drain));
+      }
+    }
+    uint8_t* gathered_rgb8 = nullptr;  // (the deferred bytes of the frame before, see below)
+    if (many && is_root && r->pending.valid) {
+      gathered_rgb8 = static_cast<uint8_t*>(r->full_rgb8.reserve(
+          bytes_of(static_cast<int64_t>(r->pending.pieces.width) * r->pending.pieces.height, 3), drain));
+    }
+    if (r->projection_done == nullptr) r->projection_done = make_event(false);
+
+    r->stage = "projection march";
+    if (input_stream != nullptr) {  // the caller's cell data is produced on that stream
+      hipStream_t producer = (input_stream == AVR_DEFAULT_STREAM)
+                                 ? nullptr
+                                 : static_cast<hipStream_t>(input_stream);
+      hip_ok(hipEventRecord(r->input_event, producer), "hipEventRecord");
+      hip_ok(hipStreamWaitEvent(stream_m, r->input_event, 0), "hipStreamWaitEvent");
+    }
+    // the send buffer of the projection before must have been exchanged and folded
+    hip_ok(hipStreamWaitEvent(stream_m, r->projection_done, 0), "hipStreamWaitEvent");
+    abi_ok(avr_march_plan_projection(r->march, r->scene, plan, 0, send, samples_out));
+    hip_ok(hipEventRecord(r->projection_done, stream_m), "hipEventRecord");
+
+    r->stage = "exchange";
+    hip_ok(hipStreamWaitEvent(stream_x, r->projection_done, 0), "hipStreamWaitEvent");
+    const float* received = send;
+    const float* own = nullptr;
+    if (many) {
+      avr_renderer::PendingGather& pending = r->pending;
+      avr_gather_op rider{};
+      if (pending.valid) {
+        rider.piece = pending.piece;
+        rider.bytes_per_pixel = 3;
+        rider.root = 0;
+        rider.full = gathered_rgb8;
+        rider.begin = pending.begin.data();
+        rider.end = pending.end.data();
+        rider.skip_own = pending.own_in_place ? 1 : 0;
+      }
+      abi_ok(avr_exchange_peers_gather(r->compose, plan, r->comm, send, recv,
+                                       pending.valid ? &rider : nullptr));
+      if (pending.valid && is_root) {
+        if (avr::launch_assemble_rows(pending.pieces, gathered_rgb8,
+                                      static_cast<int64_t>(pending.pieces.width) * 3, /*flip=*/1,
+                                      pending.out, stream_x,
+                                      pending.own_in_place ? pending.piece : nullptr,
+                                      pending.own_piece) != AVR_OK) {
+          throw std::runtime_error(avr_last_error());
+        }
+      }
+      pending.valid = false;
+      received = recv;
+      own = send;
+    }
+    r->stage = "fold";
+    if (!many) {
+      abi_ok(avr_fold_plan_projection(r->compose, plan, received, column_out, length_out));
+    } else {
+      double* piece_length = piece + std::max<int64_t>(piece_pixels, 1);
+      abi_ok(avr_fold_plan_own_projection(r->compose, plan, received, own, piece, piece_length));
+      r->stage = "gather";
+      double* full_column = is_root ? (banded ? gathered : column_out) : nullptr;
+      double* full_length = is_root ? (banded ? gathered + n_pixels : length_out) : nullptr;
+      abi_ok(avr_gather(r->compose, plan, r->comm, piece, 8, full_column, 0));
+      abi_ok(avr_gather(r->compose, plan, r->comm, piece_length, 8, full_length, 0));
+      if (is_root && banded) {
+        abi_ok(avr_assemble_rows(r->compose, plan, full_column, 8, 0, column_out));
+        abi_ok(avr_assemble_rows(r->compose, plan, full_length, 8, 0, length_out));
+      }
+    }
+    // (the next projection's march waits for this: its send buffer is free again)
+    hip_ok(hipEventRecord(r->projection_done, stream_x), "hipEventRecord");
+    r->stage = "queued";
+    return AVR_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1885,6 +2021,14 @@ int avr_renderer_render_max(avr_renderer* r, const avr_render_params* render, co
                             uint8_t* rgb8_out, int16_t* index_out) {
   return render_frame(r, render, camera, group_order, input_stream, samples_out, 0, rgb8_out, nullptr,
                       true, index_out);
+}
+
+int avr_renderer_render_projection(avr_renderer* r, const avr_render_params* render,
+                                   const avr_camera* camera, const int32_t* group_order,
+                                   void* input_stream, uint64_t* samples_out, double* column_out,
+                                   double* length_out) {
+  return render_projection_frame(r, render, camera, group_order, input_stream, samples_out,
+                                 column_out, length_out);
 }
 
 }  // extern "C"

@@ -447,8 +447,10 @@ def build_scene_from_levels(ctx, level_boxes, cell_sizes, prob_lo, ref_ratio, fe
         view = grid[lo[2] - glo[2]:hi[2] - glo[2] + 1, lo[1] - glo[1]:hi[1] - glo[1] + 1,
                     lo[0] - glo[0]:hi[0] - glo[0] + 1]
         local.append(AmrBox(b.min_corner, b.max_corner, view, b.level, owner=rank))
-    return api.build_scene_geometry(ctx, boxes, local, bounds, log_scale_input,
-                                    normalize_to_data_range, process_group, n_ranks)
+    scene = api.build_scene_geometry(ctx, boxes, local, bounds, log_scale_input,
+                                     normalize_to_data_range, process_group, n_ranks)
+    scene.world_scale = scale
+    return scene
 
 
 def clamp_levels(requested_min_level: int, requested_max_level: int, finest: int):

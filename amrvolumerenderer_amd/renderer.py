@@ -420,6 +420,26 @@ class FrameRenderer:
         return self.native.render_max(p.width, p.height, camera, p.use_visibility_graph, group_order,
                                       samples)
 
+    def render_projection(self, p: RenderParameters, camera: CameraParameters,
+                          samples: Optional[torch.Tensor] = None,
+                          group_order: Optional[Sequence[int]] = None):
+        """One column-projection frame of the raw field: per pixel column = sum over boxes of
+        f64(step) * (sum of the finite cell values sampled) and length = sum of f64(step) * (their
+        number), over the samples the maximum-intensity march takes ("Column
+        projection").  On rank 0 returns (column, length) float64 [H, W], row 0 at the bottom;
+        other ranks (None, None).  Results are produced on the compositing stream, as for
+        render().  p.antialiasing must be 1 and p.draw_bounds False; p.box_transparency, the
+        colour map and the scalar transform have no effect.  Needs the native frame driver."""
+        validate_render_parameters(p)
+        if p.antialiasing != 1:
+            raise ValueError("a column projection has no antialiasing (antialiasing must be 1)")
+        if p.draw_bounds:
+            raise ValueError("a column projection has no wireframe (draw_bounds must be False)")
+        if self.native is None:
+            raise RuntimeError("column projections need the native frame driver (native=True)")
+        return self.native.render_projection(p.width, p.height, camera, p.use_visibility_graph,
+                                             group_order, samples)
+
 
 def build_scene_on_device(ctx: runtime.Context, spec: scenes.SceneSpec, rank: int = 0):
     """Materialises this rank's boxes of a synthetic scene in HBM (torch, float64) and returns

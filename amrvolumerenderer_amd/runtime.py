@@ -16,6 +16,8 @@ from . import _capi
 from .types import AmrBox, CameraParameters, ScalarTransform
 
 INF = float("inf")
+# what a column-projection picture shows (avr_projection_colorize: AVR_PROJECTION_COLUMN, _MEAN)
+PROJECTION_QUANTITIES = ("column", "mean")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -277,6 +279,62 @@ class Context:
             C.c_void_p(samples.data_ptr()) if samples is not None else None))
         self.publish()
         return out
+
+    def paint_box_projection(self, box: AmrBox, params: _capi.PaintParams, camera: CameraParameters,
+                             column: Optional[torch.Tensor] = None,
+                             length: Optional[torch.Tensor] = None,
+                             samples: Optional[torch.Tensor] = None):
+        """avr_paint_box_projection: one box -> (column, length), [H, W] float64 each: per pixel
+        f64(step) times the sum, and times the number, of the finite raw cell values the box's
+        march samples; rows in paint_box's order (row 0 at the bottom).  samples (int64) gains
+        every sample taken."""
+        outs = []
+        for name, t in (("column", column), ("length", length)):
+            if t is None:
+                t = torch.empty((params.height, params.width), dtype=torch.float64, device=self.device)
+            self._check_tensor(t, torch.float64, name)
+            if t.numel() != params.width * params.height:
+                raise ValueError(f"{name} has the wrong size")
+            outs.append(t)
+        if samples is not None:
+            self._check_tensor(samples, torch.int64, "samples")
+        cbox, ccam = box.to_c(), camera.to_c()
+        self.join()
+        _capi.check(_capi.lib().avr_paint_box_projection(
+            self._handle, C.byref(cbox), C.byref(params), C.byref(ccam),
+            C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
+            C.c_void_p(samples.data_ptr()) if samples is not None else None))
+        self.publish()
+        return outs[0], outs[1]
+
+    def projection_colorize(self, column: torch.Tensor, length: torch.Tensor, rgb_table: torch.Tensor,
+                            quantity: str = "column", log_scale: bool = False,
+                            value_range: Optional[Sequence[float]] = None):
+        """avr_projection_colorize: (column, length) [H, W] float64 (row 0 at the bottom) ->
+        (rgb8 [H, W, 3] uint8, rows top-down; range float64 [2], the [lo, hi] used -- the min and
+        max of the displayed quantity when value_range is None).  rgb_table: [256, 3] uint8."""
+        if quantity not in PROJECTION_QUANTITIES:
+            raise ValueError(f"quantity must be one of {', '.join(PROJECTION_QUANTITIES)}, not {quantity!r}")
+        self._check_tensor(column, torch.float64, "column")
+        self._check_tensor(length, torch.float64, "length")
+        self._check_tensor(rgb_table, torch.uint8, "rgb_table")
+        if column.dim() != 2 or column.shape != length.shape or rgb_table.numel() != 256 * 3:
+            raise ValueError("column and length must be [H, W] alike; rgb_table [256, 3]")
+        height, width = column.shape
+        rgb8 = torch.empty((height, width, 3), dtype=torch.uint8, device=self.device)
+        if value_range is None:
+            rng = torch.empty(2, dtype=torch.float64, device=self.device)
+        else:
+            rng = torch.tensor([float(value_range[0]), float(value_range[1])], dtype=torch.float64,
+                               device=self.device)
+        self.join()
+        _capi.check(_capi.lib().avr_projection_colorize(
+            self._handle, C.c_void_p(column.data_ptr()), C.c_void_p(length.data_ptr()), int(width),
+            int(height), PROJECTION_QUANTITIES.index(quantity), int(bool(log_scale)),
+            C.c_void_p(rng.data_ptr()), int(value_range is None), C.c_void_p(rgb_table.data_ptr()),
+            C.c_void_p(rgb8.data_ptr())))
+        self.publish()
+        return rgb8, rng
 
     def create_scene(self, boxes: Sequence[AmrBox], transform: ScalarTransform) -> "Scene":
         return Scene(self, boxes, transform)
@@ -1180,6 +1238,38 @@ class NativeRenderer:
             C.c_void_p(index.data_ptr()) if index is not None else None))
         self._held_outputs = (index, rgb8)
         return rgb8, index
+
+    def render_projection(self, width: int, height: int, camera: CameraParameters,
+                          use_visibility_graph: bool = True,
+                          group_order: Optional[Sequence[int]] = None,
+                          samples: Optional[torch.Tensor] = None):
+        """One column-projection frame (avr_renderer_render_projection, asynchronous like
+        render()).  Rank 0 returns (column, length) as float64 [H, W], row 0 at the bottom like
+        render_max()'s index: per pixel the sums over the boxes of f64(step) times the sum, and
+        times the number, of the finite raw cell values sampled (DESIGN.md, "Column projection");
+        other ranks (None, None).  Both are complete on stream X.  samples (int64) gains every
+        sample taken, finite or not.  The cells must stay unchanged until then."""
+        rp = _capi.RenderParams(int(width), int(height), 0.0, 1, int(bool(use_visibility_graph)), 0, 0)
+        ccam = camera.to_c()
+        group = None
+        if group_order is not None:
+            group = (C.c_int32 * self.n_ranks)(*[int(g) for g in group_order])
+        column = length = None
+        caller = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.streams[2]):
+            if self.rank == 0:
+                column = torch.empty((height, width), dtype=torch.float64, device=self.device)
+                length = torch.empty((height, width), dtype=torch.float64, device=self.device)
+        if samples is not None and (samples.dtype != torch.int64 or samples.device != self.device):
+            raise ValueError("samples must be an int64 tensor on the renderer's device")
+        wait = None if caller.query() else C.c_void_p(caller.cuda_stream or _capi.DEFAULT_STREAM)
+        _capi.check(_capi.lib().avr_renderer_render_projection(
+            self._handle, C.byref(rp), C.byref(ccam), group, wait,
+            C.c_void_p(samples.data_ptr()) if samples is not None else None,
+            C.c_void_p(column.data_ptr()) if column is not None else None,
+            C.c_void_p(length.data_ptr()) if length is not None else None))
+        self._held_outputs = (column, length)
+        return column, length
 
 
 class PlanAhead:

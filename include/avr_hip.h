@@ -212,6 +212,35 @@ int avr_paint_box_max(avr_context *ctx, const avr_box *box, const avr_scalar_tra
                       const avr_paint_params *params, const avr_camera *camera, int16_t *out_index,
                       uint64_t *samples_out);
 
+/* Line-integral (column) projection of one box's raw field: per pixel, over the samples
+ * avr_paint_box_max takes in the box (the same ray, slab bounds, start distance, step, inside test
+ * and index clamp), the f64 sum S of the finite raw cell values v = cells[i + j*jstride +
+ * k*kstride] in march order (no scalar transform, no table) and their number n; then
+ * column = f64(step) * S and length = f64(step) * n, step = the box's sample distance.  Both are 0
+ * where no finite sample is taken.  width*height f64 values each to column and length (device), in
+ * avr_paint_box's pixel order (p = y * width + x, row 0 at the bottom).  samples_out: every sample
+ * taken, finite or not, is ADDED to it.  The classified volume is not used; box_transparency, the
+ * colour map and the scalar range have no effect.  The cells are read on the context's stream. */
+int avr_paint_box_projection(avr_context *ctx, const avr_box *box, const avr_paint_params *params,
+                             const avr_camera *camera, double *column, double *length,
+                             uint64_t *samples_out);
+
+/* Quantities of avr_projection_colorize */
+#define AVR_PROJECTION_COLUMN 0 /* column */
+#define AVR_PROJECTION_MEAN 1   /* column / length */
+
+/* Picture of a column projection: column, length as avr_renderer_render_projection returns them
+ * (width*height f64, device).  A pixel takes part if length > 0 and, with log_scale, its quantity
+ * q > 0 (q = column, or column / length for AVR_PROJECTION_MEAN; log10 of it with log_scale).
+ * It gets table entry clamp(floor((q - lo) / (hi - lo) * 255), 0, 255) (entry 0 if hi <= lo); its
+ * three bytes of rgb_table (256 x RGB8, device) go to rgb8_out (device, rows top-down as
+ * avr_renderer_render writes them); other pixels get (0,0,0).  range (device, 2 f64) holds
+ * [lo, hi]; with auto_range it is first set to the min and max of q over the pixels that take part
+ * ((0, 1) if none).  Asynchronous on the context's stream. */
+int avr_projection_colorize(avr_context *ctx, const double *column, const double *length, int width,
+                            int height, int quantity, int log_scale, double *range, int auto_range,
+                            const uint8_t *rgb_table, uint8_t *rgb8_out);
+
 /* A scene = the rank's local boxes (geometry.localBoxes, VolumeRenderer.cpp:1201) with one
  * scalar transform (geometry.scalarTransform).  Descriptors are copied to the device; cell
  * data stays where `cells` points. */
@@ -386,6 +415,19 @@ int avr_render_plan_max(avr_context *ctx, const avr_scene *scene, const avr_fram
 int avr_march_plan_max(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan, int slot,
                        float *send_buffer, uint64_t *samples_out);
 
+/* Column-projection frames (avr_paint_box_projection per pixel and box): the march of the plan
+ * over the scene's raw cells -- no classify pass; the classified volume (slot: as
+ * avr_march_plan_max, not read) is neither read nor written.  A run's layer pixel is
+ * (column lo, column hi, length lo, 1, length hi) -- the 32-bit halves of its f64 sums over its boxes
+ * in order, column = sum of f64(step) * S_b, length = sum of f64(step) * n_b -- where length > 0,
+ * and the cleared pixel (0,0,0,0,+inf) elsewhere, so that tightening, avr_exchange_peers and the
+ * gathers carry it unchanged.  Fold with the avr_fold_plan*_projection calls.  No chunks, no
+ * speculation.  The cells are read by the march, on the context's stream. */
+int avr_render_plan_projection(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan,
+                               float *send_buffer, uint64_t *samples_out);
+int avr_march_plan_projection(avr_context *ctx, const avr_scene *scene, const avr_frame_plan *plan,
+                              int slot, float *send_buffer, uint64_t *samples_out);
+
 /* ONE frame in n_chunks (2 .. AVR_MAX_FRAME_CHUNKS) depth-ordered chunks, for the caller who waits
  * for every frame (the reference's Render() returns after one: VolumeRenderer.cpp:1103-1339): the
  * rank's boxes are cut, in global layer order, into chunks of equal classify work; chunk k is
@@ -500,6 +542,18 @@ int avr_fold_plan_own_max(avr_context *ctx, const avr_frame_plan *plan, const fl
                           const float *own_send_buffer, int16_t *out_index, uint8_t *out_rgb8);
 int avr_fold_plan_image_max(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
                             int16_t *out_index, uint8_t *out_rgb8_image);
+
+/* The sum fold of a column-projection frame (avr_render_plan_projection): per pixel of the piece,
+ * the column and length of the covering runs that took a finite sample, added in fold (global
+ * run) order in f64.  out_column / out_length (either may be NULL): the piece's f64 values, 0
+ * where no run took a finite sample, in the order of avr_fold_plan's out_piece.  _own as
+ * avr_fold_plan_own; _image: one rank's whole image (the same order: row 0 at the bottom). */
+int avr_fold_plan_projection(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
+                             double *out_column, double *out_length);
+int avr_fold_plan_own_projection(avr_context *ctx, const avr_frame_plan *plan, const float *recv_buffer,
+                                 const float *own_send_buffer, double *out_column, double *out_length);
+int avr_fold_plan_image_projection(avr_context *ctx, const avr_frame_plan *plan,
+                                   const float *recv_buffer, double *out_column, double *out_length);
 
 /* ---- image algebra ----------------------------------------------------------------------- */
 
@@ -862,6 +916,21 @@ int avr_renderer_render(avr_renderer *renderer, const avr_render_params *render,
 int avr_renderer_render_max(avr_renderer *renderer, const avr_render_params *render,
                             const avr_camera *camera, const int32_t *group_order, void *input_stream,
                             uint64_t *samples_out, uint8_t *rgb8_out, int16_t *index_out);
+/* A column-projection frame (avr_paint_box_projection over the whole scene): the projection march
+ * (avr_march_plan_projection, no classify pass), the same exchange, the sum fold
+ * (avr_fold_plan_own_projection), and a gather of the f64 pieces to rank 0.  column_out and
+ * length_out (rank 0: required; NULL elsewhere): width*height f64 each, row 0 at the bottom.
+ * samples_out: as avr_renderer_render (every sample, finite or not).  The frame neither reads nor
+ * invalidates the classified volume or its cache, and does not feed or consult the co-run balance,
+ * speculation, frame chunks or occlusion culling; volume and MIP frames may alternate with it.
+ * It is ordered behind the frames queued before it on the renderer's streams.  The march reads
+ * the caller's cells on the march stream after input_stream's work (as avr_renderer_render): they
+ * must stay unchanged until the frame is complete on the compositing stream
+ * (avr_renderer_synchronize).  render->antialiasing > 1 or draw_bounds: AVR_ERR_INVALID_ARGUMENT. */
+int avr_renderer_render_projection(avr_renderer *renderer, const avr_render_params *render,
+                                   const avr_camera *camera, const int32_t *group_order,
+                                   void *input_stream, uint64_t *samples_out, double *column_out,
+                                   double *length_out);
 /* Plans a frame ahead of time: makes the frame plan of (render, camera, group_order) -- visibility
  * order (VolumeRenderer.cpp:1235-1241), global layer order and exchange layout
  * (DirectSendBase.cpp:400-446), for N > 1 tightened to the runs' per-row extents -- and keeps it
