@@ -2,6 +2,9 @@
 HIP path (uploaded to HBM), and results are compared bit for bit."""
 from __future__ import annotations
 
+import struct
+import zlib
+
 import numpy as np
 
 from amrvolumerenderer_amd import runtime, scenes
@@ -70,3 +73,97 @@ def spawn_ranks(worker, nprocs: int, args_for_port) -> None:
         except Exception as error:   # (mp.ProcessRaisedException carries the rank's traceback as text)
             if "EADDRINUSE" not in str(error) or attempt == 3:
                 raise
+
+
+# ---- reading sample counts out of the oracle's volume march ------------------------------------
+
+SAMPLING_BOUNDS = VolumeBounds((-0.05,) * 3, (1.05,) * 3)
+INDICATOR_MAP = [(0.0, 0.5, 0.5, 0.5, 0.0), (1.0, 0.5, 0.5, 0.5, 0.002)]
+_RECURRENCES = {}
+
+
+def count_samples(O, indicator, minc, maxc, cam, width, height, ref_dist, box):
+    """m(p): the number of samples per pixel on cells of value 1 (tests/test_projection_gpu.py, module docstring), and the
+    oracle's fetch count."""
+    params = make_params(width, height, (0.0, 1.0), 0.0, ref_dist, SAMPLING_BOUNDS, INDICATOR_MAP)
+    _, factor, alpha_scale = runtime.box_sampling(box, params)
+    table = O.build_color_table(alpha_scale, factor, (0.0, 1.0), INDICATOR_MAP).reshape(256, 4)
+    assert table[0, 3] == 0.0
+    w = np.float32(table[255, 3])
+    assert 0.0 < w < 0.01
+    ob = O.make_box(np.ascontiguousarray(indicator, dtype=np.float64), minc, maxc)
+    op = oracle_params(O, width, height, (0.0, 1.0), 0.0, ref_dist, SAMPLING_BOUNDS, INDICATOR_MAP)
+    img, fetches = O.paint_box(ob, oracle_transform(O, ScalarTransform(normalize_to_unit_range=True)), op, oracle_camera(O, cam), threads=16)
+    alpha = img[..., 3].astype(np.float32)
+    # the recurrence's values, as far as the image needs them (strictly increasing: checked)
+    a, top = np.float32(0.0), alpha.max()
+    alphas = _RECURRENCES.setdefault(w.tobytes(), ([a], {a.tobytes(): 0}))
+    values, index = alphas
+    while values[-1] < top:
+        a = values[-1]
+        b = np.float32(a + np.float32(w * np.float32(np.float32(1.0) - a)))
+        assert b > a and b < 1.0
+        index[b.tobytes()] = len(values)
+        values.append(b)
+    m = np.array([index[v.tobytes()] for v in alpha.reshape(-1)], dtype=np.int64)
+    return m.reshape(height, width), fetches
+
+
+# ---- step maps: reading maximum indices out of the oracle's volume march -----------------------
+
+def step_map(t, scalar_range=(0.0, 1.0)):
+    """Colour map (value, r, g, b, alpha) whose table alpha is 0 for entries < t, > 0 from t on."""
+    lo, hi = float(scalar_range[0]), float(scalar_range[1])
+    at = lambda i: lo + (hi - lo) * i / 255.0  # noqa: E731
+    if t <= 0:
+        return [(lo, 0.5, 0.5, 0.5, 1.0), (hi, 0.5, 0.5, 0.5, 1.0)]
+    points = [(lo, 0.5, 0.5, 0.5, 0.0), (at(t - 0.5), 0.5, 0.5, 0.5, 0.0)]
+    if t < 255:
+        points.append((at(t), 0.5, 0.5, 0.5, 1.0))
+    points.append((hi, 0.5, 0.5, 0.5, 1.0))
+    return points
+
+
+_checked_tables = set()
+
+
+def check_step_table(O, t, scalar_range):
+    """Opacity nodes interpolate: the alpha > 0 set of the step map's table must be {i >= t}."""
+    key = (t, tuple(scalar_range))
+    if key in _checked_tables:
+        return
+    for factor in (1.0, 0.5, 0.25, 2.0):
+        table = O.build_color_table(1.0, factor, scalar_range, step_map(t, scalar_range))
+        lit = np.nonzero(table.reshape(256, 4)[:, 3] > 0.0)[0]
+        assert np.array_equal(lit, np.arange(t, 256)), (t, factor, lit[:4])
+    _checked_tables.add(key)
+
+
+# ---- pictures ----------------------------------------------------------------------------------
+
+def read_png(path):
+    raw = open(path, "rb").read()
+    assert raw[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, idat, width, height = 8, b"", 0, 0
+    while pos < len(raw):
+        size, tag = struct.unpack(">I4s", raw[pos:pos + 8])
+        body = raw[pos + 8:pos + 8 + size]
+        if tag == b"IHDR":
+            width, height = struct.unpack(">II", body[:8])
+        elif tag == b"IDAT":
+            idat += body
+        pos += 12 + size
+    rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(height, 1 + 3 * width)
+    assert not rows[:, 0].any()   # filter type 0
+    return rows[:, 1:].reshape(height, width, 3)
+
+
+def colorize(q, lo, hi, table, eligible=None):
+    """numpy restatement of avr_projection_colorize (every sampled pixel here has q > 0)."""
+    if eligible is None:
+        eligible = q > 0.0
+    t = np.floor((q - lo) / (hi - lo) * 255.0)
+    entry = np.clip(np.where(eligible, t, 0), 0, 255).astype(np.int64)
+    rgb = table[entry]
+    rgb[~eligible] = 0
+    return rgb[::-1]

@@ -18,7 +18,8 @@ from amrvolumerenderer_amd.renderer import FrameRenderer, RenderParameters
 from amrvolumerenderer_amd.types import (AmrBox, CameraParameters, ColorMapControlPoint,
                                          ScalarTransform, VolumeBounds, make_params)
 
-from helpers import device_box, oracle_camera, oracle_params, oracle_transform, spawn_ranks
+from helpers import (check_step_table, device_box, oracle_camera, oracle_params, oracle_transform,
+                     spawn_ranks, step_map)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,35 +37,7 @@ def radial(nx, ny, nz):
         (x[None, None, :] ** 2 + y[None, :, None] ** 2 + z[:, None, None] ** 2) / 3.0)
 
 
-def step_map(t, scalar_range=(0.0, 1.0)):
-    """Colour map (value, r, g, b, alpha) whose table alpha is 0 for entries < t, > 0 from t on."""
-    lo, hi = float(scalar_range[0]), float(scalar_range[1])
-    at = lambda i: lo + (hi - lo) * i / 255.0  # noqa: E731
-    if t <= 0:
-        return [(lo, 0.5, 0.5, 0.5, 1.0), (hi, 0.5, 0.5, 0.5, 1.0)]
-    points = [(lo, 0.5, 0.5, 0.5, 0.0), (at(t - 0.5), 0.5, 0.5, 0.5, 0.0)]
-    if t < 255:
-        points.append((at(t), 0.5, 0.5, 0.5, 1.0))
-    points.append((hi, 0.5, 0.5, 0.5, 1.0))
-    return points
-
-
 ZERO_MAP = [(0.0, 0.5, 0.5, 0.5, 0.0), (1.0, 0.5, 0.5, 0.5, 0.0)]
-
-_checked_tables = set()
-
-
-def check_step_table(O, t, scalar_range):
-    """Opacity nodes interpolate: the alpha > 0 set of the step map's table must be {i >= t}."""
-    key = (t, tuple(scalar_range))
-    if key in _checked_tables:
-        return
-    for factor in (1.0, 0.5, 0.25, 2.0):
-        table = O.build_color_table(1.0, factor, scalar_range, step_map(t, scalar_range))
-        lit = np.nonzero(table.reshape(256, 4)[:, 3] > 0.0)[0]
-        assert np.array_equal(lit, np.arange(t, 256)), (t, factor, lit[:4])
-    _checked_tables.add(key)
-
 
 def oracle_confirms_index(O, cells, minc, maxc, cam, width, height, index, samples,
                           transform=NORM, scalar_range=(0.0, 1.0), ref_dist=0.0):
