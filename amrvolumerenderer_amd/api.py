@@ -776,3 +776,234 @@ def project(plotfile: str, width: int = 512, height: int = 512, variable: Option
         if not writer(rgb8.cpu().numpy(), output):
             raise RuntimeError(f"could not write '{output}'")
     return q.cpu().numpy()
+
+
+# ---- slices ("Slice") ---------------------------------------------------------------
+
+SLICE_QUANTITIES = ("value", "level")
+# axis -> (normal, north): (U, V) = (y, z), (z, x), (x, y), yt's convention
+SLICE_AXES = {"x": ((1.0, 0.0, 0.0), (0.0, 0.0, 1.0)),
+              "y": ((0.0, 1.0, 0.0), (1.0, 0.0, 0.0)),
+              "z": ((0.0, 0.0, 1.0), (0.0, 1.0, 0.0))}
+
+
+@dataclass
+class SlicePlane:
+    """A slice's plane in the plotfile's physical units: pixel (x, y) of a W x H image, row 0 at
+    the bottom, shows the point center + ((x + 0.5) / W - 0.5) width[0] U + ((y + 0.5) / H - 0.5)
+    width[1] V with (U, V) = slice_basis(normal, north)."""
+    center: Tuple[float, float, float]
+    normal: Tuple[float, float, float]
+    north: Tuple[float, float, float]
+    width: Tuple[float, float]
+
+
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _unit(v, what: str):
+    values = tuple(float(c) for c in v)
+    if len(values) != 3:
+        raise ValueError(f"{what} must hold three values")
+    length = math.sqrt(values[0] * values[0] + values[1] * values[1] + values[2] * values[2])
+    if not (math.isfinite(length) and length > 0.0):
+        raise ValueError(f"{what} must be a finite, non-zero vector")
+    return tuple(c / length for c in values)
+
+
+def slice_basis(normal: Sequence[float], north: Sequence[float]):
+    """(n, U, V) of a slice plane, float64: n = normal / |normal|, U = normalize(north x n),
+    V = n x U -- with n pointing at the viewer U points right and V up.  ValueError if north is
+    parallel to the normal (|north x n| <= 1e-6 for unit vectors), zero or not finite."""
+    n = _unit(normal, "normal")
+    right = _cross(_unit(north, "north"), n)
+    length = math.sqrt(right[0] * right[0] + right[1] * right[1] + right[2] * right[2])
+    if not (length > 1e-6):
+        raise ValueError("north must not be parallel to the normal")
+    u = tuple(c / length for c in right)
+    return n, u, _cross(n, u)
+
+
+def validate_slice_arguments(width: int, height: int, axis: str = "z",
+                             normal: Optional[Sequence[float]] = None,
+                             north: Optional[Sequence[float]] = None,
+                             plane_width: Optional[Sequence[float]] = None,
+                             quantity: str = "value", log_scale: bool = False,
+                             value_range: Optional[Sequence[float]] = None):
+    """The argument checks of slice(), before any GPU work.  Returns (normal, north, plane_width
+    or None, value_range or None): normal / north as given (they override axis) or the axis's."""
+    if quantity not in SLICE_QUANTITIES:
+        raise ValueError(f"quantity must be one of {', '.join(SLICE_QUANTITIES)}, not {quantity!r}")
+    if normal is None and north is None:
+        if axis not in SLICE_AXES:
+            raise ValueError(f"axis must be one of x, y, z, not {axis!r}")
+        normal, north = SLICE_AXES[axis]
+    elif normal is None:
+        if axis not in SLICE_AXES:
+            raise ValueError(f"axis must be one of x, y, z, not {axis!r}")
+        normal = SLICE_AXES[axis][0]
+    elif north is None:
+        raise ValueError("north must be given with normal")
+    slice_basis(normal, north)
+    widths = None
+    if plane_width is not None:
+        widths = tuple(float(v) for v in plane_width)
+        if len(widths) != 2:
+            raise ValueError("plane_width must hold two values (wu, wv)")
+        if not all(math.isfinite(v) and v > 0.0 for v in widths):
+            raise ValueError("plane_width must be finite and positive")
+    rng = validate_projection_arguments(width, height, "column", log_scale, value_range)
+    return tuple(float(c) for c in normal), tuple(float(c) for c in north), widths, rng
+
+
+def combine_slices(parts):
+    """The slices of several owners -> the slice of them all; parts: (value, level, box) triples
+    as slice_scene returns them (torch tensors or numpy arrays of one shape).  The owners' boxes
+    are disjoint, so at most one part hits a pixel and the others hold (0.0, -1, -1) there: the
+    combination is the SUM of value and the MAX of level and of box.  The sum runs over the
+    values' 64-bit patterns (a miss is all zero bits), which keeps the hit's bits -- -0.0 and a
+    NaN's payload included -- where a floating-point sum would not."""
+    import numpy as np
+    import torch
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_slices needs at least one part")
+    as_tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    value, level, box = (as_tensor(a) for a in parts[0])
+    if value.dtype != torch.float64 or level.dtype != torch.int8 or box.dtype != torch.int32:
+        raise ValueError("parts are (float64 value, int8 level, int32 box)")
+    bits = value.contiguous().view(torch.int64).clone()
+    level, box = level.clone(), box.clone()
+    for part in parts[1:]:
+        v, l, b = (as_tensor(a) for a in part)
+        if v.shape != value.shape or l.shape != value.shape or b.shape != value.shape or \
+                (v.dtype, l.dtype, b.dtype) != (torch.float64, torch.int8, torch.int32):
+            raise ValueError("parts must agree in shape and type")
+        bits += v.contiguous().view(torch.int64)
+        level = torch.maximum(level, l)
+        box = torch.maximum(box, b)
+    out = (bits.view(torch.float64), level, box)
+    if not isinstance(parts[0][0], torch.Tensor):
+        return tuple(t.numpy() for t in out)
+    return out
+
+
+def slice_scene(ctx, scene: SceneGeometry, plane: SlicePlane, width: int, height: int,
+                rank: int = 0, n_ranks: int = 1, process_group=None):
+    """The slice of a loaded scene: (value float64, level int8, box int32), [height, width]
+    tensors on ctx.device, row 0 at the bottom ("Slice"): the raw value of the cell
+    that contains the pixel's point, its box's AMR level and its index in scene.all_boxes;
+    (0.0, -1, -1) where no box does.  Every rank slices its local_boxes; for n_ranks > 1 the parts
+    are combined on rank 0 as combine_slices states (other ranks get (None, None, None)), through
+    the host if the group's backend is not NCCL.  Every box of scene.local_boxes must be among
+    scene.all_boxes with the same corners and level (ValueError otherwise): that is where its
+    index comes from.  Each call stages the box table anew; for many slices of one scene keep a
+    runtime.Scene and call its slice()."""
+    import torch
+    _, u, v = slice_basis(plane.normal, plane.north)
+    wu, wv = (float(w) for w in plane.width)
+    if not (math.isfinite(wu) and wu > 0.0 and math.isfinite(wv) and wv > 0.0):
+        raise ValueError("plane_width must be finite and positive")
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError("image dimensions must be positive")
+    scale = float(scene.world_scale)
+    center = tuple(float(c) for c in plane.center)
+    origin = tuple((center[a] - 0.5 * wu * u[a] - 0.5 * wv * v[a]) * scale for a in range(3))
+    du = tuple(u[a] * wu * scale / float(width) for a in range(3))
+    dv = tuple(v[a] * wv * scale / float(height) for a in range(3))
+    where = {(tuple(b.min_corner), tuple(b.max_corner), int(b.level)): i
+             for i, b in enumerate(scene.all_boxes)}
+    try:
+        index = [where[(tuple(b.min_corner), tuple(b.max_corner), int(b.level))]
+                 for b in scene.local_boxes]
+    except KeyError:
+        raise ValueError("a local box is not among the scene's all_boxes") from None
+    local = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
+    value, level, box = local.slice(origin, du, dv, width, height, index)
+    if n_ranks > 1:
+        import torch.distributed as dist
+        stage = dist.get_backend(process_group) != "nccl"
+        root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+        ctx.synchronize()
+        parts = [value.view(torch.int64), level.to(torch.int32), box]
+        if stage:
+            parts = [t.cpu() for t in parts]
+        dist.reduce(parts[0], root, op=dist.ReduceOp.SUM, group=process_group)
+        dist.reduce(parts[1], root, op=dist.ReduceOp.MAX, group=process_group)
+        dist.reduce(parts[2], root, op=dist.ReduceOp.MAX, group=process_group)
+        if rank != 0:
+            local.close()
+            return None, None, None
+        value = parts[0].to(ctx.device).view(torch.float64)
+        level = parts[1].to(ctx.device).to(torch.int8)
+        box = parts[2].to(ctx.device)
+    ctx.synchronize()
+    local.close()
+    return value, level, box
+
+
+def slice(plotfile: str, width: int = 512, height: int = 512, variable: Optional[str] = None,
+          min_level: int = 0, max_level: int = -1, axis: str = "z",
+          center: Optional[Sequence[float]] = None, normal: Optional[Sequence[float]] = None,
+          north: Optional[Sequence[float]] = None, plane_width: Optional[Sequence[float]] = None,
+          quantity: str = "value", log_scale: bool = False,
+          value_range: Optional[Sequence[float]] = None,
+          color_map: Optional[Sequence[Sequence[float]]] = None, annotate_grids: bool = False,
+          output: Optional[str] = None):
+    """Slice of a plotfile's raw field (yt's SlicePlot; DESIGN.md 7, "Slice"), on cuda:0: the plane
+    through `center` with the given normal; per pixel the value of the finest loaded cell that
+    contains the pixel's point (quantity "value", no interpolation, no transform) or that cell's
+    AMR level (quantity "level").  axis "x" | "y" | "z" puts (right, up) = (y, z), (z, x), (x, y);
+    normal with north (the direction that is up in the picture) override it.  center defaults to
+    the centre of the data's bounding box, plane_width = (wu, wv) to the data's extent along right
+    and up; all three are in the plotfile's physical units.  Returns the numpy float64 [height,
+    width] image on rank 0, row 0 at the bottom, NaN where no loaded cell contains the point
+    (outside the data, or in a hole left by min_level > 0), and None on other ranks.  With output
+    (.png, else PPM) rank 0 also writes the picture, coloured as project() colours a column: entry
+    clamp(floor((q - lo) / (hi - lo) * 255), 0, 255) of the colour map over value_range (or the
+    min and max of q), log10 of q with log_scale; misses and non-finite values are black;
+    annotate_grids draws the boxes' boundaries in white."""
+    normal, north, widths, rng = validate_slice_arguments(width, height, axis, normal, north,
+                                                          plane_width, quantity, log_scale,
+                                                          value_range)
+    if center is not None:
+        center = tuple(float(c) for c in center)
+        if len(center) != 3 or not _finite(center):
+            raise ValueError("center must hold three finite values")
+    table = projection_rgb_table(color_map)
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    from . import plotfile as pf
+    import torch
+    ctx, rank, world, group = _runtime_scope()
+    scene = pf.load_plotfile_geometry(ctx, plotfile, variable or "", min_level, max_level, False,
+                                      True, rank, world, group)
+    to_physical = 1.0 / float(scene.world_scale)
+    lo = [min(b.min_corner[a] for b in scene.all_boxes) * to_physical for a in range(3)]
+    hi = [max(b.max_corner[a] for b in scene.all_boxes) * to_physical for a in range(3)]
+    if center is None:
+        center = tuple(0.5 * (lo[a] + hi[a]) for a in range(3))
+    if widths is None:
+        _, u, v = slice_basis(normal, north)
+        widths = tuple(sum(abs(e[a]) * (hi[a] - lo[a]) for a in range(3)) for e in (u, v))
+    value, level, box = slice_scene(ctx, scene, SlicePlane(center, normal, north, widths), width,
+                                    height, rank, world, group)
+    if rank != 0:
+        return None
+    hit = level >= 0
+    shown = value if quantity == "value" else level.to(torch.float64)
+    if output is not None:
+        rgb8, _ = ctx.projection_colorize(
+            torch.where(hit, shown, torch.zeros_like(shown)), hit.to(torch.float64),
+            torch.from_numpy(table).to(value.device), "column", log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        if annotate_grids:
+            ctx.slice_outline(box, rgb8)
+        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
+        if not writer(rgb8.cpu().numpy(), output):
+            raise RuntimeError(f"could not write '{output}'")
+    nan = torch.full_like(shown, float("nan"))
+    return torch.where(hit, shown, nan).cpu().numpy()

@@ -1825,6 +1825,69 @@ int avr_scene_histogram(avr_context* ctx, const avr_scene* scene,
   });
 }
 
+int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origin[3],
+                    const double du[3], const double dv[3], int width, int height,
+                    const int32_t* global_index, double* value, int8_t* level, int32_t* box) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene != nullptr && origin != nullptr && du != nullptr && dv != nullptr &&
+                value != nullptr && level != nullptr && box != nullptr, "null argument");
+    require(width > 0 && height > 0, "image width and height must be positive");
+    require(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
+            "image has more than 2^31-1 pixels");
+    avr::SlicePlaneDev plane;
+    for (int a = 0; a < 3; ++a) {
+      require(std::isfinite(origin[a]) && std::isfinite(du[a]) && std::isfinite(dv[a]),
+              "slice plane must be finite");
+      plane.origin[a] = origin[a];
+      plane.du[a] = du[a];
+      plane.dv[a] = dv[a];
+    }
+    const size_t n_boxes = scene->boxes.size();
+    std::vector<avr::SliceBoxDev> boxes(n_boxes);
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& in = scene->boxes[b];
+      avr::SliceBoxDev& dev = boxes[b];
+      std::memset(&dev, 0, sizeof(dev));
+      dev.global_index = global_index != nullptr ? global_index[b] : static_cast<int32_t>(b);
+      require(in.level >= 0 && in.level <= 127, "box level must lie in [0, 127]");
+      dev.level = in.level;
+      if (in.dims[0] <= 0 || in.dims[1] <= 0 || in.dims[2] <= 0) continue;  // holds no point
+      require(in.cells != nullptr, "box has no cell data");
+      const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
+                           static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
+                           static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
+      require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
+              "box spans more than 2^28 cells (or has negative strides)");
+      for (int a = 0; a < 3; ++a) {
+        dev.minc[a] = in.min_corner[a];
+        dev.maxc[a] = in.max_corner[a];
+        dev.n[a] = in.dims[a];
+      }
+      dev.cells = in.cells;
+      dev.jstride = static_cast<int32_t>(in.jstride);
+      dev.kstride = static_cast<int32_t>(in.kstride);
+    }
+    ctx->staging.begin(boxes.size() * sizeof(avr::SliceBoxDev), 1);
+    const avr::SliceBoxDev* boxes_dev = ctx->staging.add(boxes.data(), boxes.size());
+    ctx->staging.commit(ctx->stream);
+    return avr::launch_slice(plane, width, height, boxes_dev, static_cast<int>(n_boxes), value,
+                             level, box, ctx->stream);
+  });
+}
+
+int avr_slice_outline(avr_context* ctx, const int32_t* box, int width, int height, int red,
+                      int green, int blue, uint8_t* rgb8) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(box != nullptr && rgb8 != nullptr, "null argument");
+    require(width > 0 && height > 0, "image width and height must be positive");
+    require(red >= 0 && red <= 255 && green >= 0 && green <= 255 && blue >= 0 && blue <= 255,
+            "colour components must lie in [0, 255]");
+    return avr::launch_slice_outline(box, width, height, red, green, blue, rgb8, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

@@ -380,6 +380,30 @@ void scene_transform_from_stats(const double stats[3], int64_t finite_count, boo
                                 double processed[2], float processed_range[2],
                                 float scalar_range[2]);
 
+// Slice images (avr_slice.hip).  A box as the slice kernel reads it: the f64 corners of avr_box
+// (the containment test is done in binary64, unlike the march's float prologue), the cell
+// addressing and what a pixel reports.  A box without cells has max = min: it contains no point.
+struct alignas(16) SliceBoxDev {
+  double minc[3];
+  double maxc[3];
+  int32_t n[3];
+  int32_t level;
+  const double* cells;
+  int32_t jstride;        // element strides (Array4); the box spans < 2^28 elements
+  int32_t kstride;
+  int32_t global_index;   // what the box image holds for this box
+  int32_t pad_[3];
+};
+static_assert(sizeof(SliceBoxDev) == 96, "SliceBoxDev: 16-byte multiple for scalar loads");
+// Pixel (x, y) samples (origin + (x + 0.5) * du) + (y + 0.5) * dv, scene coordinates.
+struct SlicePlaneDev {
+  double origin[3], du[3], dv[3];
+};
+int launch_slice(const SlicePlaneDev& plane, int width, int height, const SliceBoxDev* boxes_dev,
+                 int n_boxes, double* value, int8_t* level, int32_t* box_index, void* stream);
+int launch_slice_outline(const int32_t* box_index, int width, int height, int red, int green,
+                         int blue, uint8_t* rgb8, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

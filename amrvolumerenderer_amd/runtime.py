@@ -336,6 +336,26 @@ class Context:
         self.publish()
         return rgb8, rng
 
+    def slice_outline(self, box: torch.Tensor, rgb8: torch.Tensor,
+                      color: Sequence[int] = (255, 255, 255)) -> torch.Tensor:
+        """avr_slice_outline: box [H, W] int32 (Scene.slice's, row 0 at the bottom), rgb8 [H, W, 3]
+        uint8 (rows top-down, written in place): every pixel whose box differs from that of its
+        right or upper neighbour gets `color`."""
+        self._check_tensor(box, torch.int32, "box")
+        self._check_tensor(rgb8, torch.uint8, "rgb8")
+        if box.dim() != 2 or tuple(rgb8.shape) != (box.shape[0], box.shape[1], 3):
+            raise ValueError("box must be [H, W] and rgb8 [H, W, 3]")
+        rgb = tuple(int(c) for c in color)
+        if len(rgb) != 3 or not all(0 <= c <= 255 for c in rgb):
+            raise ValueError("color must hold three values in [0, 255]")
+        height, width = box.shape
+        self.join()
+        _capi.check(_capi.lib().avr_slice_outline(
+            self._handle, C.c_void_p(box.data_ptr()), int(width), int(height), rgb[0], rgb[1],
+            rgb[2], C.c_void_p(rgb8.data_ptr())))
+        self.publish()
+        return rgb8
+
     def create_scene(self, boxes: Sequence[AmrBox], transform: ScalarTransform) -> "Scene":
         return Scene(self, boxes, transform)
 
@@ -536,6 +556,48 @@ class Scene:
             int(bin_count), C.c_void_p(counts.data_ptr())))
         self.ctx.publish()
         return counts
+
+    def slice(self, origin: Sequence[float], du: Sequence[float], dv: Sequence[float], width: int,
+              height: int, global_index: Optional[Sequence[int]] = None,
+              value: Optional[torch.Tensor] = None, level: Optional[torch.Tensor] = None,
+              box: Optional[torch.Tensor] = None):
+        """avr_slice_scene: the plane origin + (x + 0.5) du + (y + 0.5) dv (scene coordinates)
+        through this scene's boxes -> (value float64, level int8, box int32), [height, width]
+        each, row 0 at the bottom: the raw value of the cell that contains the pixel's point, its
+        box's level and global_index[its box] (the box's position in this scene if None);
+        (0.0, -1, -1) where no box contains the point."""
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError("image width and height must be positive")
+        vectors = []
+        for name, vec in (("origin", origin), ("du", du), ("dv", dv)):
+            values = tuple(float(c) for c in vec)
+            if len(values) != 3:
+                raise ValueError(f"{name} must hold three values")
+            vectors.append((C.c_double * 3)(*values))
+        index = None
+        if global_index is not None:
+            index = np.ascontiguousarray(global_index, dtype=np.int32)
+            if index.shape != (len(self.boxes),):
+                raise ValueError("global_index must hold one entry per box of the scene")
+        ctx = self.ctx
+        outs = []
+        for name, t, dtype in (("value", value, torch.float64), ("level", level, torch.int8),
+                               ("box", box, torch.int32)):
+            if t is None:
+                t = torch.empty((height, width), dtype=dtype, device=ctx.device)
+            ctx._check_tensor(t, dtype, name)
+            if t.numel() != width * height:
+                raise ValueError(f"{name} has the wrong size")
+            outs.append(t)
+        ctx.join()
+        _capi.check(_capi.lib().avr_slice_scene(
+            ctx._handle, self._handle, vectors[0], vectors[1], vectors[2], width, height,
+            index.ctypes.data_as(C.POINTER(C.c_int32)) if index is not None else None,
+            C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
+            C.c_void_p(outs[2].data_ptr())))
+        ctx.publish()
+        return outs[0], outs[1], outs[2]
 
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the

@@ -51,6 +51,9 @@ def main() -> int:
     ap.add_argument("--orbit", type=int, default=0, help="render this many views around the data")
     ap.add_argument("--mode", choices=api.RENDER_MODES, default="volume",
                     help="volume rendering or maximum-intensity projection")
+    ap.add_argument("--slice", choices=sorted(api.SLICE_AXES), default=None, metavar="AXIS",
+                    help="write a slice of the raw field through the data's centre, normal to "
+                         "this axis, with the grids outlined, instead of a rendering")
     args = ap.parse_args()
     path = args.plotfile
     scratch = None
@@ -58,6 +61,10 @@ def main() -> int:
         scratch = tempfile.TemporaryDirectory()
         path = os.path.join(scratch.name, "plt00000")
         synthetic_plotfile(path)
+    if args.slice is not None:
+        api.slice(path, width=args.size, height=args.size, variable=args.variable,
+                  axis=args.slice, annotate_grids=True, output=args.output)
+        return 0
     if args.orbit <= 0:
         return api.render(path, width=args.size, height=args.size, variable=args.variable,
                           box_transparency=args.transparency, output=args.output, mode=args.mode)

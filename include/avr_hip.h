@@ -1055,6 +1055,30 @@ int avr_scene_histogram(avr_context *ctx, const avr_scene *scene,
                         const avr_scalar_transform *transform, float range_min, float range_max,
                         int bin_count, uint64_t *counts_dev);
 
+/* ---- slice images of the raw field ("Slice") ------------------------------------ */
+
+/* A plane through the scene: pixel (x, y), row 0 at the bottom, samples the point
+ *   P[a] = (origin[a] + (x + 0.5) * du[a]) + (y + 0.5) * dv[a]      (binary64, nothing fused)
+ * in the scene's coordinates.  A box contains P when min_corner[a] <= P[a] < max_corner[a] on all
+ * three axes; the scene's boxes must be disjoint (the first that contains P is taken).  In it the
+ * cell is i_a = min(int(floor((P[a] - min[a]) / (max[a] - min[a]) * dims[a])), dims[a] - 1), and
+ *   value[p] = cells[i + j*jstride + k*kstride] as it is (NaN and Inf included), 0.0 on a miss,
+ *   level[p] = the box's level (0..127), -1 on a miss,
+ *   box[p]   = global_index[b] of the scene's box b (host array, one per box of the scene; null:
+ *              b itself), -1 on a miss,
+ * p = y * width + x; all three on the device.  No transform, no classified volume.  Asynchronous
+ * on the context's stream. */
+int avr_slice_scene(avr_context *ctx, const avr_scene *scene, const double origin[3],
+                    const double du[3], const double dv[3], int width, int height,
+                    const int32_t *global_index, double *value, int8_t *level, int32_t *box);
+
+/* Box outlines of a slice: every pixel of `box` (avr_slice_scene's, row 0 at the bottom) whose
+ * entry differs from that of its right or its upper neighbour -- the last column has no right
+ * neighbour, the top row no upper one -- gets (red, green, blue) in rgb8 (width*height*3 bytes,
+ * device, rows top-down as avr_projection_colorize writes them); other pixels are left alone. */
+int avr_slice_outline(avr_context *ctx, const int32_t *box, int width, int height, int red,
+                      int green, int blue, uint8_t *rgb8);
+
 #ifdef __cplusplus
 }
 #endif
