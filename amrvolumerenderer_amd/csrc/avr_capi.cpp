@@ -372,6 +372,7 @@ void bind_device(avr_context* ctx) {
 }
 
 enum Phase { kClassify = 1, kMarch = 2 };
+constexpr avr::FrameKind kVolume = avr::FrameKind::kVolume;
 
 // A frame cut into depth-ordered chunks of its global layer order (avr_classify_plan_chunked /
 // avr_march_plan_chunked): chunk k is classified by launch k of the classify call, which records
@@ -395,13 +396,46 @@ struct FrameChunks {
   const int32_t* classify_positions = nullptr;
   int n_classify_positions = 0;
   const avr_speculation* speculation = nullptr;
-  // a maximum-intensity march (avr_render_plan_max / avr_march_plan_max / avr_paint_box_max): one
-  // launch of render_runs_max_kernel, never chunked, culled or speculative
-  bool max_intensity = false;
-  // a column-projection march (avr_render_plan_projection / avr_march_plan_projection /
-  // avr_paint_box_projection): one launch of render_runs_sum_kernel over the raw cells; no classify
-  // pass, the classified volume is neither read nor made
-  bool projection = false;
+};
+
+using VolumeOut = avr::FoldOutputs<avr::FrameKind::kVolume>;
+using MaxOut = avr::FoldOutputs<avr::FrameKind::kMaxIntensity>;
+using SumOut = avr::FoldOutputs<avr::FrameKind::kProjection>;
+
+// What render() is asked for -- the classify pass and/or the march of one frame -- in parts that a
+// caller fills in one expression each.
+struct FrameBoxes {  // the boxes and how they are seen
+  const avr_box* boxes;
+  int n_boxes;
+  const avr_scalar_transform& transform;
+  const avr_paint_params& params;
+  const avr_camera& camera;
+};
+struct FrameRuns {  // their global layer order cut into runs, the runs' tables, the exchange's pieces
+  const int32_t* box_order;
+  int n_order;
+  const int32_t* run_end;
+  int n_runs, n_pieces;
+  const std::vector<avr::RunRectDev>& rects;
+  const std::vector<avr::RunBlockDev>& blocks;  // n_runs x n_pieces
+  const std::vector<avr::RunSpanDev>* spans;    // a tightened plan's, or null
+  const avr::PieceMapDev& pieces;
+};
+struct FrameTarget {  // the scene whose classified slot the frame uses, and where the results go
+  avr_scene* scene;
+  int slot;
+  float* out_layers;
+  uint64_t* samples_out;  // may be null
+  avr::FramePlan* cached;  // null, or the host prologue kept from a frame's classify call to its march
+};
+struct RenderRequest {
+  int phases;  // Phase bits
+  // kMaxIntensity: one march launch, never chunked, culled or speculative.  kProjection: the same,
+  // over the raw cells: march only, the classified volume is neither read nor made.
+  avr::FrameKind kind;
+  FrameBoxes in;
+  FrameRuns runs;
+  FrameTarget to;
 };
 
 // Positions [bounds[k], bounds[k + 1]) of the global layer order for chunk k: equal shares of the
@@ -428,8 +462,6 @@ std::vector<int> chunk_bounds(const avr::FramePlan& plan, const int32_t* box_ord
   return bounds;
 }
 
-// One frame's device work for a list of boxes: the classify pass and/or the march.
-// `classified` must hold plan.classified_bytes bytes; `cached` (optional) carries the host
 // Upper bound of the march's workgroups: a work item per super-tile of the screen and run, padded
 // to whole rounds of the XCDs, four workgroups each (build_march_items, avr_host.cpp).
 int64_t march_workgroups_bound(int width, int height, int n_runs) {
@@ -439,39 +471,37 @@ int64_t march_workgroups_bound(int width, int height, int n_runs) {
   return items * avr::kSuperTileTiles;
 }
 
-// prologue from the classify call of a frame to its march call.
-int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
-           const avr_scalar_transform& transform, const avr_paint_params& params,
-           const avr_camera& camera, const int32_t* box_order, int n_order,
-           const int32_t* run_end, int n_runs, int n_pieces,
-           const std::vector<avr::RunRectDev>& run_rects,
-           const std::vector<avr::RunBlockDev>& run_blocks,
-           const std::vector<avr::RunSpanDev>* run_spans, const avr::PieceMapDev& pieces,
-           avr_scene* scene, int slot,
-           float* out_layers, uint64_t* samples_out, avr::FramePlan* cached,
-           const FrameChunks& chunks = FrameChunks{}) {
-  require(n_runs >= 0 && n_order >= 0 && n_pieces >= 1, "invalid run description");
+// One frame's device work for a list of boxes: the classify pass and/or the march, queued on the
+// context's stream.  This is where a frame's kind enters the native layer, so what the kinds other
+// than kVolume exclude is checked here and nowhere below.
+int render(avr_context* ctx, const RenderRequest& frame, const FrameChunks& chunks = FrameChunks{}) {
+  const FrameBoxes& in = frame.in;
+  const FrameRuns& runs = frame.runs;
+  const FrameTarget& to = frame.to;
+  int phases = frame.phases;
+  require(runs.n_runs >= 0 && runs.n_order >= 0 && runs.n_pieces >= 1, "invalid run description");
   require(chunks.count >= 1 && chunks.count <= AVR_MAX_FRAME_CHUNKS, "invalid chunk count");
   require(chunks.count == 1 || phases == kClassify || phases == kMarch || chunks.visibility != nullptr,
           "a chunked frame is classified and marched by separate calls (or by avr_render_plan_culled)");
-  require(slot >= 0 && slot < AVR_CLASSIFIED_SLOTS, "classified slot out of range");
-  require(!chunks.max_intensity || (chunks.count == 1 && chunks.speculation == nullptr),
-          "a maximum-intensity march is one launch: no chunks, no speculation");
-  require(!chunks.projection || (chunks.count == 1 && chunks.speculation == nullptr && phases == kMarch),
-          "a column-projection march is one launch: no classify pass, no chunks, no speculation");
+  require(to.slot >= 0 && to.slot < AVR_CLASSIFIED_SLOTS, "classified slot out of range");
+  require(frame.kind == avr::FrameKind::kVolume ||
+              (chunks.count == 1 && chunks.speculation == nullptr),
+          "a maximum-intensity or column-projection march is one launch: no chunks, no speculation");
+  require(frame.kind != avr::FrameKind::kProjection || phases == kMarch,
+          "a column-projection march has no classify pass");
   avr::FramePlan local;
-  avr::FramePlan& plan = cached ? *cached : local;
-  if (plan.boxes.size() != static_cast<size_t>(n_boxes) || !plan.ready) {
-    avr::plan_frame(boxes, n_boxes, transform, params, camera, &plan);
+  avr::FramePlan& plan = to.cached ? *to.cached : local;
+  if (plan.boxes.size() != static_cast<size_t>(in.n_boxes) || !plan.ready) {
+    avr::plan_frame(in.boxes, in.n_boxes, in.transform, in.params, in.camera, &plan);
     plan.march_items_ready = false;
   }
-  if (n_runs == 0) return AVR_OK;
+  if (runs.n_runs == 0) return AVR_OK;
   require(plan.n_tables <= avr::kMaxLdsTables,
           "too many distinct sampling levels for the LDS transfer-function cache");
 
   avr::RenderLaunch launch;
   launch.consts = plan.consts;
-  launch.n_boxes = n_boxes;
+  launch.n_boxes = in.n_boxes;
   launch.n_classify_tiles = plan.classify_tile_begin.back();
   launch.classify_lds_pad = ctx->classify_lds_pad;
   // (streamed only when the classified volume is more than the 256 MB memory-side cache holds:
@@ -480,9 +510,11 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   launch.classify_stream_stores =
       (ctx->classify_stream_stores && plan.classified_bytes > (256ull << 20)) ? 1 : 0;
   launch.classified =
-      chunks.projection ? nullptr : scene->classified_slot(slot, plan.classified_bytes, ctx->stream);
+      frame.kind == avr::FrameKind::kProjection
+          ? nullptr
+          : to.scene->classified_slot(to.slot, plan.classified_bytes, ctx->stream);
 
-  if ((phases & kClassify) && scene->cache_classification) {
+  if ((phases & kClassify) && to.scene->cache_classification) {
     // everything classify_kernel reads besides the cells themselves
     std::vector<uint64_t> key;
     auto bits = [](double v) {
@@ -507,45 +539,46 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
                     static_cast<uint64_t>(dev.nz));
       key.push_back(dev.cls_offset);
     }
-    if (key == scene->classified_key[slot]) {
+    if (key == to.scene->classified_key[to.slot]) {
       phases &= ~kClassify;  // the slot already holds exactly this classification
       if (phases == 0) return AVR_OK;
     } else {
-      scene->classified_key[slot] = std::move(key);
+      to.scene->classified_key[to.slot] = std::move(key);
     }
   }
 
   // scratch, reused across frames; a frame plan's prologue keeps its own (they depend on the
   // plan alone)
-  const bool keep_items = cached != nullptr;
+  const bool keep_items = to.cached != nullptr;
   std::vector<avr::MarchItemDev>& items = keep_items ? plan.march_items : ctx->march_items;
   size_t bytes = plan.boxes.size() * sizeof(avr::BoxDev);
   if (phases & kClassify) bytes += plan.classify_tile_begin.size() * sizeof(uint32_t);
   if (phases & kMarch) {
-    require(out_layers != nullptr, "null output image");
-    require(n_runs == 0 || (run_end != nullptr), "null run_end");
-    require(n_order == 0 || (box_order != nullptr), "null box_order");
-    require(run_rects.size() == static_cast<size_t>(n_runs) &&
-                run_blocks.size() == static_cast<size_t>(n_runs) * n_pieces,
+    require(to.out_layers != nullptr, "null output image");
+    require(runs.n_runs == 0 || (runs.run_end != nullptr), "null run_end");
+    require(runs.n_order == 0 || (runs.box_order != nullptr), "null box_order");
+    require(runs.rects.size() == static_cast<size_t>(runs.n_runs) &&
+                runs.blocks.size() == static_cast<size_t>(runs.n_runs) * runs.n_pieces,
             "run tables do not match the runs");
     if (!(keep_items && plan.march_items_ready)) {
       int previous = 0;
-      for (int r = 0; r < n_runs; ++r) {
-        require(run_end[r] >= previous && run_end[r] <= n_order, "run_end must be non-decreasing");
-        previous = run_end[r];
+      for (int r = 0; r < runs.n_runs; ++r) {
+        require(runs.run_end[r] >= previous && runs.run_end[r] <= runs.n_order,
+                "run_end must be non-decreasing");
+        previous = runs.run_end[r];
       }
-      require(run_end[n_runs - 1] == n_order, "runs must cover box_order");
-      for (int i = 0; i < n_order; ++i) {
-        require(box_order[i] >= 0 && box_order[i] < n_boxes, "box_order entry out of range");
+      require(runs.run_end[runs.n_runs - 1] == runs.n_order, "runs must cover box_order");
+      for (int i = 0; i < runs.n_order; ++i) {
+        require(runs.box_order[i] >= 0 && runs.box_order[i] < in.n_boxes, "box_order entry out of range");
       }
-      avr::build_march_items(plan, box_order, run_end, n_runs, run_rects, &items);
+      avr::build_march_items(plan, runs.box_order, runs.run_end, runs.n_runs, runs.rects, &items);
       plan.march_items_ready = keep_items;
     }
-    bytes += plan.tables.size() * sizeof(float) + static_cast<size_t>(n_order + n_runs) * 4 +
-             static_cast<size_t>(n_order) * 16 +
+    bytes += plan.tables.size() * sizeof(float) + static_cast<size_t>(runs.n_order + runs.n_runs) * 4 +
+             static_cast<size_t>(runs.n_order) * 16 +
              items.size() * sizeof(avr::MarchItemDev) +
-             run_rects.size() * sizeof(avr::RunRectDev) + run_blocks.size() * sizeof(avr::RunBlockDev) +
-             (run_spans != nullptr ? run_spans->size() * sizeof(avr::RunSpanDev) : 0);
+             runs.rects.size() * sizeof(avr::RunRectDev) + runs.blocks.size() * sizeof(avr::RunBlockDev) +
+             (runs.spans != nullptr ? runs.spans->size() * sizeof(avr::RunSpanDev) : 0);
   }
   // chunked: the positions of every chunk, and for the classify call the chunks' box lists (the
   // local boxes in global layer order ARE the lists: chunk k is box_order[bounds[k] .. bounds[k+1]))
@@ -554,23 +587,23 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   std::vector<int> bounds;
   std::vector<uint32_t> chunk_tile_begin;  // chunk k: entries bounds[k] + k .. bounds[k + 1] + k
   if (chunked) {
-    require(n_order == 0 || box_order != nullptr, "null box_order");
-    for (int i = 0; i < n_order; ++i) {
-      require(box_order[i] >= 0 && box_order[i] < n_boxes, "box_order entry out of range");
+    require(runs.n_order == 0 || runs.box_order != nullptr, "null box_order");
+    for (int i = 0; i < runs.n_order; ++i) {
+      require(runs.box_order[i] >= 0 && runs.box_order[i] < in.n_boxes, "box_order entry out of range");
     }
-    bounds = chunk_bounds(plan, box_order, n_order, chunks.count);
+    bounds = chunk_bounds(plan, runs.box_order, runs.n_order, chunks.count);
     if (phases & kClassify) {
-      chunk_tile_begin.reserve(static_cast<size_t>(n_order + chunks.count));
+      chunk_tile_begin.reserve(static_cast<size_t>(runs.n_order + chunks.count));
       for (int k = 0; k < chunks.count; ++k) {
         uint32_t sum = 0;
         chunk_tile_begin.push_back(0u);
         for (int i = bounds[static_cast<size_t>(k)]; i < bounds[static_cast<size_t>(k) + 1]; ++i) {
-          const size_t b = static_cast<size_t>(box_order[i]);
+          const size_t b = static_cast<size_t>(runs.box_order[i]);
           sum += plan.classify_tile_begin[b + 1] - plan.classify_tile_begin[b];
           chunk_tile_begin.push_back(sum);
         }
       }
-      bytes += chunk_tile_begin.size() * sizeof(uint32_t) + static_cast<size_t>(n_order) * 4;
+      bytes += chunk_tile_begin.size() * sizeof(uint32_t) + static_cast<size_t>(runs.n_order) * 4;
     }
   }
   // a flagged classify pass: the local boxes in layer order as ONE list under its own prefix sum
@@ -580,10 +613,10 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   const bool flagged = (phases & kClassify) && (chunks.classify_flags != nullptr || positioned);
   if (flagged) {
     require(chunks.count == 1, "a flagged classify pass is not cut into chunks");
-    require(n_order == 0 || box_order != nullptr, "null box_order");
+    require(runs.n_order == 0 || runs.box_order != nullptr, "null box_order");
     require(!(positioned && chunks.classify_flags != nullptr), "flags or positions, not both");
-    const int n_listed = positioned ? chunks.n_classify_positions : n_order;
-    require(n_listed >= 0 && n_listed <= n_order, "too many positions");
+    const int n_listed = positioned ? chunks.n_classify_positions : runs.n_order;
+    require(n_listed >= 0 && n_listed <= runs.n_order, "too many positions");
     listed_tile_begin.reserve(static_cast<size_t>(n_listed) + 1);
     listed_boxes.reserve(static_cast<size_t>(n_listed));
     uint32_t sum = 0;
@@ -591,18 +624,19 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
     int previous = -1;
     for (int i = 0; i < n_listed; ++i) {
       const int position = positioned ? chunks.classify_positions[i] : i;
-      require(position > previous && position < n_order, "positions must ascend within the layer order");
+      require(position > previous && position < runs.n_order, "positions must ascend within the layer order");
       previous = position;
-      require(box_order[position] >= 0 && box_order[position] < n_boxes, "box_order entry out of range");
-      const size_t b = static_cast<size_t>(box_order[position]);
+      require(runs.box_order[position] >= 0 && runs.box_order[position] < in.n_boxes,
+              "box_order entry out of range");
+      const size_t b = static_cast<size_t>(runs.box_order[position]);
       sum += plan.classify_tile_begin[b + 1] - plan.classify_tile_begin[b];
       listed_tile_begin.push_back(sum);
-      listed_boxes.push_back(box_order[position]);
+      listed_boxes.push_back(runs.box_order[position]);
     }
     bytes += listed_tile_begin.size() * sizeof(uint32_t) + listed_boxes.size() * 4;
   }
   if ((phases & kMarch) && chunks.speculation != nullptr) {
-    bytes += sizeof(avr::MarchSpecDev) + static_cast<size_t>(n_order);
+    bytes += sizeof(avr::MarchSpecDev) + static_cast<size_t>(runs.n_order);
   }
   avr::StagingRing& staging = ctx->staging;
   staging.begin(bytes, 16);
@@ -614,7 +648,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
         staging.add(plan.classify_tile_begin.data(), plan.classify_tile_begin.size());
     if (chunked) {
       chunk_tile_begin_dev = staging.add(chunk_tile_begin.data(), chunk_tile_begin.size());
-      chunk_box_list_dev = staging.add(box_order, static_cast<size_t>(n_order));
+      chunk_box_list_dev = staging.add(runs.box_order, static_cast<size_t>(runs.n_order));
     }
     if (flagged) {
       launch.tile_begin_dev = staging.add(listed_tile_begin.data(), listed_tile_begin.size());
@@ -628,32 +662,32 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
   if (phases & kMarch) {
     launch.tables_dev = staging.add(plan.tables.data(), plan.tables.size());
     launch.n_tables = plan.n_tables;
-    launch.order_dev = staging.add(box_order, static_cast<size_t>(n_order));
+    launch.order_dev = staging.add(runs.box_order, static_cast<size_t>(runs.n_order));
     {
       // the boxes' screen rectangles in that order: what the march's cull reads 64 at a time
       std::vector<int32_t>& rects = ctx->order_rects;
-      rects.resize(static_cast<size_t>(n_order) * 4);
-      for (int i = 0; i < n_order; ++i) {
-        const avr::BoxDev& dev = plan.boxes[static_cast<size_t>(box_order[i])];
+      rects.resize(static_cast<size_t>(runs.n_order) * 4);
+      for (int i = 0; i < runs.n_order; ++i) {
+        const avr::BoxDev& dev = plan.boxes[static_cast<size_t>(runs.box_order[i])];
         std::copy(dev.rect, dev.rect + 4, rects.begin() + static_cast<std::ptrdiff_t>(i) * 4);
       }
       launch.order_rects_dev = staging.add(rects.data(), rects.size());
     }
-    launch.run_end_dev = staging.add(run_end, static_cast<size_t>(n_runs));
-    launch.n_order = n_order;
-    launch.n_runs = n_runs;
-    launch.n_pieces = n_pieces;
-    launch.run_rects_dev = staging.add(run_rects.data(), run_rects.size());
-    launch.run_blocks_dev = staging.add(run_blocks.data(), run_blocks.size());
-    launch.run_spans_dev = (run_spans != nullptr && !run_spans->empty())
-                               ? staging.add(run_spans->data(), run_spans->size())
+    launch.run_end_dev = staging.add(runs.run_end, static_cast<size_t>(runs.n_runs));
+    launch.n_order = runs.n_order;
+    launch.n_runs = runs.n_runs;
+    launch.n_pieces = runs.n_pieces;
+    launch.run_rects_dev = staging.add(runs.rects.data(), runs.rects.size());
+    launch.run_blocks_dev = staging.add(runs.blocks.data(), runs.blocks.size());
+    launch.run_spans_dev = (runs.spans != nullptr && !runs.spans->empty())
+                               ? staging.add(runs.spans->data(), runs.spans->size())
                                : nullptr;
-    launch.pieces = pieces;
-    launch.out_layers = out_layers;
-    launch.samples_out = reinterpret_cast<unsigned long long*>(samples_out);
+    launch.pieces = runs.pieces;
+    launch.out_layers = to.out_layers;
+    launch.samples_out = reinterpret_cast<unsigned long long*>(to.samples_out);
     launch.counters = reinterpret_cast<unsigned long long*>(ctx->march_counters);
     if (chunks.speculation != nullptr) {
-      require(chunks.count == 1 && samples_out == nullptr,
+      require(chunks.count == 1 && to.samples_out == nullptr,
               "a speculative march is one launch and counts no samples");
       const avr_speculation& given = *chunks.speculation;
       require(given.classified == nullptr || given.classified_host == nullptr,
@@ -663,7 +697,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
               "a speculative march that checks flags needs somewhere to report misses");
       avr::MarchSpecDev spec{};
       spec.classified = given.classified_host != nullptr
-                            ? staging.add(given.classified_host, static_cast<size_t>(n_order))
+                            ? staging.add(given.classified_host, static_cast<size_t>(runs.n_order))
                             : given.classified;
       spec.visited = given.visited;
       spec.missed = given.missed;
@@ -675,7 +709,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
       spec.dirty_blocks = given.gate != nullptr ? given.dirty_workgroups : nullptr;
       if (given.dirty_workgroups != nullptr) {
         require(static_cast<int64_t>(items.size()) * avr::kSuperTileTiles <=
-                    march_workgroups_bound(params.width, params.height, n_runs),
+                    march_workgroups_bound(in.params.width, in.params.height, runs.n_runs),
                 "more march workgroups than avr_march_plan_workgroups promised");
       }
       launch.spec_dev = staging.add(&spec, 1);
@@ -684,8 +718,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
     launch.items_dev = staging.add(items.data(), items.size());
     launch.n_items = static_cast<uint32_t>(items.size());
     launch.workgroups_per_cu = ctx->march_workgroups_per_cu;
-    launch.max_intensity = chunks.max_intensity ? 1 : 0;
-    launch.projection = chunks.projection ? 1 : 0;
+    launch.kind = frame.kind;
     launch.only_mode = plan.boxes.empty() ? -1 : plan.boxes[0].index_mode;
     for (const avr::BoxDev& dev : plan.boxes) {
       if (dev.index_mode != launch.only_mode) launch.only_mode = -1;
@@ -696,7 +729,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
     const uint32_t reserve = launch.classify_lds_pad;
     if (chunks.visibility != nullptr) {
       avr::hip_check(hipMemsetAsync(chunks.visibility, 0,
-                                    static_cast<size_t>(chunks.count) * static_cast<size_t>(n_order),
+                                    static_cast<size_t>(chunks.count) * static_cast<size_t>(runs.n_order),
                                     ctx->stream), "hipMemsetAsync(visibility)");
     }
     for (int k = 0; k < chunks.count; ++k) {
@@ -704,7 +737,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
       if (phases & kClassify) {
         // (what the march launch of the chunk before found still visible of this chunk's boxes)
         launch.visible_in = (chunks.visibility != nullptr && k > 0)
-                                ? chunks.visibility + static_cast<size_t>(k - 1) * n_order + first
+                                ? chunks.visibility + static_cast<size_t>(k - 1) * runs.n_order + first
                                 : nullptr;
         if (last > first) {
           launch.box_list_dev = chunk_box_list_dev + first;
@@ -721,7 +754,7 @@ int render(avr_context* ctx, int phases, const avr_box* boxes, int n_boxes,
       }
       if (phases & kMarch) {
         launch.visible_out = (chunks.visibility != nullptr && k + 1 < chunks.count)
-                                 ? chunks.visibility + static_cast<size_t>(k) * n_order
+                                 ? chunks.visibility + static_cast<size_t>(k) * runs.n_order
                                  : nullptr;
         if (chunks.events != nullptr && !(phases & kClassify)) {
           avr::hip_check(hipStreamWaitEvent(ctx->stream, chunks.events[k], 0), "hipStreamWaitEvent(chunk)");
@@ -944,6 +977,66 @@ int avr_piece_range(int64_t image_size, int piece_index, int num_pieces, int64_t
   });
 }
 
+namespace {
+// One box as one dense run in one contiguous piece: what the avr_paint_box calls render.
+struct OneBoxRun {
+  const int32_t order[1] = {0};
+  const int32_t run_end[1] = {1};
+  std::vector<avr::RunRectDev> rects;
+  std::vector<avr::RunBlockDev> blocks;
+  avr::PieceMapDev pieces;
+};
+int paint_one_box(avr_context* ctx, int phases, avr::FrameKind kind, const avr_box* box,
+                  const avr_scalar_transform& transform, const avr_paint_params& params,
+                  const avr_camera& camera, float* out_layers, uint64_t* samples_out,
+                  OneBoxRun* run) {
+  avr::dense_run_tables(params.width, params.height, 1, 1, &run->rects, &run->blocks);
+  run->pieces = avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params.width, params.height);
+  return render(ctx, {phases, kind, {box, 1, transform, params, camera},
+                      {run->order, 1, run->run_end, 1, 1, run->rects, run->blocks, nullptr, run->pieces},
+                      {&ctx->scratch_scene, 0, out_layers, samples_out, nullptr}});
+}
+
+// The same into the context's scratch layer (grown as needed), then the fold of that one run into
+// `out`: a maximum-intensity index image or a projection's f64 images.
+int paint_and_fold_one_box(avr_context* ctx, int phases, const avr_box* box,
+                           const avr_scalar_transform& transform, const avr_paint_params& params,
+                           const avr_camera& camera, uint64_t* samples_out, const avr::FoldOut& out) {
+  require(params.width > 0 && params.height > 0, "image width and height must be positive");
+  const int64_t n_pixels = static_cast<int64_t>(params.width) * params.height;
+  const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
+  if (bytes > ctx->max_layers_capacity) {
+    avr::wait_stream(ctx->stream, "avr_paint_box (scratch layer)");
+    if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
+    ctx->max_layers = nullptr;
+    ctx->max_layers_capacity = 0;
+    avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(scratch layer)");
+    ctx->max_layers_capacity = bytes;
+  }
+  float* layer = static_cast<float*>(ctx->max_layers);
+  OneBoxRun run;
+  const int status = paint_one_box(ctx, phases, static_cast<avr::FrameKind>(out.index()), box,
+                                   transform, params, camera, layer, samples_out, &run);
+  if (status != AVR_OK) return status;
+  avr::FoldLaunch launch;
+  ctx->staging.begin(run.rects.size() * sizeof(avr::RunRectDev) +
+                         run.blocks.size() * sizeof(avr::RunBlockDev), 2);
+  launch.run_rects_dev = ctx->staging.add(run.rects.data(), run.rects.size());
+  launch.run_blocks_dev = ctx->staging.add(run.blocks.data(), run.blocks.size());
+  launch.run_spans_dev = nullptr;
+  ctx->staging.commit(ctx->stream);
+  launch.pieces = run.pieces;
+  launch.piece = 0;
+  launch.width = params.width;
+  launch.piece_begin = 0;
+  launch.piece_end = n_pixels;
+  launch.n_runs = 1;
+  launch.recv = layer;
+  launch.out = out;
+  return avr::launch_fold_plan(launch, ctx->stream);
+}
+}  // namespace
+
 int avr_paint_box(avr_context* ctx, const avr_box* box, const avr_scalar_transform* transform,
                   const avr_paint_params* params, const avr_camera* camera, float* out_rgbad,
                   uint64_t* samples_out) {
@@ -951,16 +1044,10 @@ int avr_paint_box(avr_context* ctx, const avr_box* box, const avr_scalar_transfo
     bind_device(ctx);
     require(box != nullptr && transform != nullptr && params != nullptr && camera != nullptr,
             "null argument");
-    const int32_t order[1] = {0};
-    const int32_t run_end[1] = {1};
-    std::vector<avr::RunRectDev> rects;
-    std::vector<avr::RunBlockDev> blocks;
     require(params->width > 0 && params->height > 0, "image width and height must be positive");
-    avr::dense_run_tables(params->width, params->height, 1, 1, &rects, &blocks);
-    return render(ctx, kClassify | kMarch, box, 1, *transform, *params, *camera, order, 1, run_end,
-                  1, 1, rects, blocks, nullptr,
-                  avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height),
-                  &ctx->scratch_scene, 0, out_rgbad, samples_out, nullptr);
+    OneBoxRun run;
+    return paint_one_box(ctx, kClassify | kMarch, kVolume, box, *transform, *params,
+                         *camera, out_rgbad, samples_out, &run);
   });
 }
 
@@ -972,50 +1059,9 @@ int avr_paint_box_max(avr_context* ctx, const avr_box* box, const avr_scalar_tra
     require(box != nullptr && transform != nullptr && params != nullptr && camera != nullptr &&
                 out_index != nullptr,
             "null argument");
-    require(params->width > 0 && params->height > 0, "image width and height must be positive");
-    const int32_t order[1] = {0};
-    const int32_t run_end[1] = {1};
-    std::vector<avr::RunRectDev> rects;
-    std::vector<avr::RunBlockDev> blocks;
-    avr::dense_run_tables(params->width, params->height, 1, 1, &rects, &blocks);
-    const int64_t n_pixels = static_cast<int64_t>(params->width) * params->height;
-    const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
-    if (bytes > ctx->max_layers_capacity) {
-      avr::wait_stream(ctx->stream, "avr_paint_box_max");
-      if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
-      ctx->max_layers = nullptr;
-      ctx->max_layers_capacity = 0;
-      avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(maximum-intensity layer)");
-      ctx->max_layers_capacity = bytes;
-    }
-    float* layer = static_cast<float*>(ctx->max_layers);
-    const avr::PieceMapDev pieces =
-        avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height);
-    FrameChunks chunks;
-    chunks.max_intensity = true;
-    int status = render(ctx, kClassify | kMarch, box, 1, *transform, *params, *camera, order, 1,
-                        run_end, 1, 1, rects, blocks, nullptr, pieces, &ctx->scratch_scene, 0, layer,
-                        samples_out, nullptr, chunks);
-    if (status != AVR_OK) return status;
     // the layer -> index image: the max fold over the one run
-    avr::FoldLaunch launch;
-    ctx->staging.begin(rects.size() * sizeof(avr::RunRectDev) + blocks.size() * sizeof(avr::RunBlockDev), 2);
-    launch.run_rects_dev = ctx->staging.add(rects.data(), rects.size());
-    launch.run_blocks_dev = ctx->staging.add(blocks.data(), blocks.size());
-    launch.run_spans_dev = nullptr;
-    ctx->staging.commit(ctx->stream);
-    launch.pieces = pieces;
-    launch.piece = 0;
-    launch.width = params->width;
-    launch.piece_begin = 0;
-    launch.piece_end = n_pixels;
-    launch.n_runs = 1;
-    launch.recv = layer;
-    launch.out_piece = nullptr;
-    launch.out_rgb8 = nullptr;
-    launch.max_intensity = 1;
-    launch.out_index = out_index;
-    return avr::launch_fold_plan(launch, ctx->stream);
+    return paint_and_fold_one_box(ctx, kClassify | kMarch, box, *transform, *params, *camera,
+                                  samples_out, MaxOut{out_index, nullptr});
   });
 }
 
@@ -1027,52 +1073,10 @@ int avr_paint_box_projection(avr_context* ctx, const avr_box* box, const avr_pai
     require(box != nullptr && params != nullptr && camera != nullptr && column != nullptr &&
                 length != nullptr,
             "null argument");
-    require(params->width > 0 && params->height > 0, "image width and height must be positive");
-    const int32_t order[1] = {0};
-    const int32_t run_end[1] = {1};
-    std::vector<avr::RunRectDev> rects;
-    std::vector<avr::RunBlockDev> blocks;
-    avr::dense_run_tables(params->width, params->height, 1, 1, &rects, &blocks);
-    const int64_t n_pixels = static_cast<int64_t>(params->width) * params->height;
-    const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
-    if (bytes > ctx->max_layers_capacity) {
-      avr::wait_stream(ctx->stream, "avr_paint_box_projection");
-      if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
-      ctx->max_layers = nullptr;
-      ctx->max_layers_capacity = 0;
-      avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(projection layer)");
-      ctx->max_layers_capacity = bytes;
-    }
-    float* layer = static_cast<float*>(ctx->max_layers);
-    const avr::PieceMapDev pieces =
-        avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params->width, params->height);
-    FrameChunks chunks;
-    chunks.projection = true;
     const avr_scalar_transform transform{};  // (no classify pass: the raw values are summed)
-    int status = render(ctx, kMarch, box, 1, transform, *params, *camera, order, 1, run_end, 1, 1,
-                        rects, blocks, nullptr, pieces, &ctx->scratch_scene, 0, layer, samples_out,
-                        nullptr, chunks);
-    if (status != AVR_OK) return status;
     // the layer -> f64 images: the sum fold over the one run (a pixel no box covers stays 0)
-    avr::FoldLaunch launch;
-    ctx->staging.begin(rects.size() * sizeof(avr::RunRectDev) + blocks.size() * sizeof(avr::RunBlockDev), 2);
-    launch.run_rects_dev = ctx->staging.add(rects.data(), rects.size());
-    launch.run_blocks_dev = ctx->staging.add(blocks.data(), blocks.size());
-    launch.run_spans_dev = nullptr;
-    ctx->staging.commit(ctx->stream);
-    launch.pieces = pieces;
-    launch.piece = 0;
-    launch.width = params->width;
-    launch.piece_begin = 0;
-    launch.piece_end = n_pixels;
-    launch.n_runs = 1;
-    launch.recv = layer;
-    launch.out_piece = nullptr;
-    launch.out_rgb8 = nullptr;
-    launch.projection = 1;
-    launch.out_column = column;
-    launch.out_length = length;
-    return avr::launch_fold_plan(launch, ctx->stream);
+    return paint_and_fold_one_box(ctx, kMarch, box, transform, *params, *camera, samples_out,
+                                  SumOut{column, length});
   });
 }
 
@@ -1127,12 +1131,13 @@ int avr_render_runs(avr_context* ctx, const avr_scene* scene, const avr_paint_pa
     std::vector<avr::RunRectDev> rects;
     std::vector<avr::RunBlockDev> blocks;
     avr::dense_run_tables(params->width, params->height, n_runs, n_pieces, &rects, &blocks);
-    return render(ctx, kClassify | kMarch, scene->boxes.data(),
-                  static_cast<int>(scene->boxes.size()), scene->transform, *params, *camera,
-                  box_order, n_order, run_end, n_runs, n_pieces, rects, blocks, nullptr,
-                  avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, n_pieces, params->width,
-                                      params->height),
-                  const_cast<avr_scene*>(scene), 0, out_layers, samples_out, nullptr);
+    const avr::PieceMapDev pieces =
+        avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, n_pieces, params->width, params->height);
+    return render(ctx, {kClassify | kMarch, kVolume,
+                        {scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
+                         *params, *camera},
+                        {box_order, n_order, run_end, n_runs, n_pieces, rects, blocks, nullptr, pieces},
+                        {const_cast<avr_scene*>(scene), 0, out_layers, samples_out, nullptr}});
   });
 }
 
@@ -1331,7 +1336,7 @@ int avr_frame_plan_recv_block(const avr_frame_plan* plan, int global_run, int64_
   });
 }
 
-static int plan_phase(avr_context* ctx, int phases, const avr_scene* scene,
+static int plan_phase(avr_context* ctx, int phases, avr::FrameKind kind, const avr_scene* scene,
                       const avr_frame_plan* plan, int slot, float* send_buffer,
                       uint64_t* samples_out, const FrameChunks& chunks = FrameChunks{}) {
   return guarded([&]() -> int {
@@ -1345,14 +1350,17 @@ static int plan_phase(avr_context* ctx, int phases, const avr_scene* scene,
     require(static_cast<int>(scene->boxes.size()) == plan->info.n_local_boxes,
             "the scene does not hold this rank's boxes of the plan");
     if (plan->info.n_local_runs == 0) return AVR_OK;
-    return render(ctx, phases, scene->boxes.data(), static_cast<int>(scene->boxes.size()),
-                  scene->transform, plan->params, plan->camera, plan->local_order.data(),
-                  static_cast<int>(plan->local_order.size()), plan->local_run_end.data(),
-                  plan->info.n_local_runs, plan->info.n_ranks, plan->local_rects, plan->send_blocks,
-                  ((phases & kMarch) && plan->tightened) ? &plan->send_spans : nullptr,
-                  plan->pieces,
-                  const_cast<avr_scene*>(scene), slot, send_buffer, samples_out,
-                  &const_cast<avr_frame_plan*>(plan)->prologue, chunks);
+    return render(ctx,
+                  {phases, kind,
+                   {scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
+                    plan->params, plan->camera},
+                   {plan->local_order.data(), static_cast<int>(plan->local_order.size()),
+                    plan->local_run_end.data(), plan->info.n_local_runs, plan->info.n_ranks,
+                    plan->local_rects, plan->send_blocks,
+                    ((phases & kMarch) && plan->tightened) ? &plan->send_spans : nullptr, plan->pieces},
+                   {const_cast<avr_scene*>(scene), slot, send_buffer, samples_out,
+                    &const_cast<avr_frame_plan*>(plan)->prologue}},
+                  chunks);
   });
 }
 
@@ -1375,45 +1383,41 @@ int avr_scene_invalidate(avr_scene* scene) {
 
 int avr_render_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                     float* send_buffer, uint64_t* samples_out) {
-  return plan_phase(ctx, kClassify | kMarch, scene, plan, 0, send_buffer, samples_out);
+  return plan_phase(ctx, kClassify | kMarch, kVolume, scene, plan, 0, send_buffer, samples_out);
 }
 
 int avr_render_plan_max(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                         float* send_buffer, uint64_t* samples_out) {
-  FrameChunks chunks;
-  chunks.max_intensity = true;
-  return plan_phase(ctx, kClassify | kMarch, scene, plan, 0, send_buffer, samples_out, chunks);
+  return plan_phase(ctx, kClassify | kMarch, avr::FrameKind::kMaxIntensity, scene, plan, 0,
+                    send_buffer, samples_out);
 }
 
 int avr_march_plan_max(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan, int slot,
                        float* send_buffer, uint64_t* samples_out) {
-  FrameChunks chunks;
-  chunks.max_intensity = true;
-  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+  return plan_phase(ctx, kMarch, avr::FrameKind::kMaxIntensity, scene, plan, slot, send_buffer,
+                    samples_out);
 }
 
 int avr_render_plan_projection(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                                float* send_buffer, uint64_t* samples_out) {
-  FrameChunks chunks;
-  chunks.projection = true;
-  return plan_phase(ctx, kMarch, scene, plan, 0, send_buffer, samples_out, chunks);
+  return plan_phase(ctx, kMarch, avr::FrameKind::kProjection, scene, plan, 0, send_buffer,
+                    samples_out);
 }
 
 int avr_march_plan_projection(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                               int slot, float* send_buffer, uint64_t* samples_out) {
-  FrameChunks chunks;
-  chunks.projection = true;
-  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+  return plan_phase(ctx, kMarch, avr::FrameKind::kProjection, scene, plan, slot, send_buffer,
+                    samples_out);
 }
 
 int avr_classify_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                       int slot) {
-  return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr);
+  return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr);
 }
 
 int avr_march_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan, int slot,
                    float* send_buffer, uint64_t* samples_out) {
-  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out);
+  return plan_phase(ctx, kMarch, kVolume, scene, plan, slot, send_buffer, samples_out);
 }
 
 int avr_classify_plan_chunked(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
@@ -1422,7 +1426,7 @@ int avr_classify_plan_chunked(avr_context* ctx, const avr_scene* scene, const av
   chunks.count = n_chunks;
   chunks.events = reinterpret_cast<hipEvent_t const*>(chunk_events);
   chunks.first_alone = first_alone != 0;
-  return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr, chunks);
+  return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr, chunks);
 }
 
 int avr_march_plan_chunked(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
@@ -1431,7 +1435,7 @@ int avr_march_plan_chunked(avr_context* ctx, const avr_scene* scene, const avr_f
   FrameChunks chunks;
   chunks.count = n_chunks;
   chunks.events = reinterpret_cast<hipEvent_t const*>(chunk_events);
-  return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+  return plan_phase(ctx, kMarch, kVolume, scene, plan, slot, send_buffer, samples_out, chunks);
 }
 
 int avr_classify_plan_flagged(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
@@ -1441,7 +1445,7 @@ int avr_classify_plan_flagged(avr_context* ctx, const avr_scene* scene, const av
     FrameChunks chunks;
     chunks.classify_flags = flags;
     chunks.classify_gate = gate;
-    return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr, chunks);
+    return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr, chunks);
   });
 }
 
@@ -1461,7 +1465,7 @@ int avr_classify_plan_positions(avr_context* ctx, const avr_scene* scene, const 
     FrameChunks chunks;
     chunks.classify_positions = positions;
     chunks.n_classify_positions = n_positions;
-    return plan_phase(ctx, kClassify, scene, plan, slot, nullptr, nullptr, chunks);
+    return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr, chunks);
   });
 }
 
@@ -1471,7 +1475,7 @@ int avr_march_plan_speculative(avr_context* ctx, const avr_scene* scene, const a
     require(speculation != nullptr, "null speculation");
     FrameChunks chunks;
     chunks.speculation = speculation;
-    return plan_phase(ctx, kMarch, scene, plan, slot, send_buffer, nullptr, chunks);
+    return plan_phase(ctx, kMarch, kVolume, scene, plan, slot, send_buffer, nullptr, chunks);
   });
 }
 
@@ -1484,7 +1488,8 @@ int avr_render_plan_culled(avr_context* ctx, const avr_scene* scene, const avr_f
     chunks.count = n_chunks;
     chunks.visibility = visibility;
     chunks.first_alone = true;
-    return plan_phase(ctx, kClassify | kMarch, scene, plan, slot, send_buffer, samples_out, chunks);
+    return plan_phase(ctx, kClassify | kMarch, kVolume, scene, plan, slot, send_buffer, samples_out,
+                      chunks);
   });
 }
 
@@ -1494,47 +1499,45 @@ int avr_fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* rec
 }
 
 namespace {
+// to_image (one rank, volume and maximum-intensity frames): the RGB8 output is the whole image,
+// rows top-down.
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
-              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
-              int16_t* out_index = nullptr, bool max_intensity = false,
-              double* out_column = nullptr, double* out_length = nullptr, bool projection = false);
+              const float* own_send_buffer, const avr::FoldOut& out, bool to_image = false);
 }
 
 int avr_fold_plan_own(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                       const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8) {
-  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, out_piece, out_rgb8, false);
+  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, VolumeOut{out_piece, out_rgb8});
 }
 
 int avr_fold_plan_image(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                         float* out_piece, uint8_t* out_rgb8_image) {
-  return fold_plan(ctx, plan, recv_buffer, nullptr, out_piece, out_rgb8_image, true);
+  return fold_plan(ctx, plan, recv_buffer, nullptr, VolumeOut{out_piece, out_rgb8_image}, true);
 }
 
 int avr_fold_plan_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                       int16_t* out_index, uint8_t* out_rgb8) {
-  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, out_rgb8, false, out_index, true);
+  return fold_plan(ctx, plan, recv_buffer, nullptr, MaxOut{out_index, out_rgb8});
 }
 
 int avr_fold_plan_own_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                           const float* own_send_buffer, int16_t* out_index, uint8_t* out_rgb8) {
-  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, nullptr, out_rgb8, false, out_index, true);
+  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, MaxOut{out_index, out_rgb8});
 }
 
 int avr_fold_plan_image_max(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                             int16_t* out_index, uint8_t* out_rgb8_image) {
-  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, out_rgb8_image, true, out_index, true);
+  return fold_plan(ctx, plan, recv_buffer, nullptr, MaxOut{out_index, out_rgb8_image}, true);
 }
 
 int avr_fold_plan_projection(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                              double* out_column, double* out_length) {
-  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, nullptr, false, nullptr, false,
-                   out_column, out_length, true);
+  return fold_plan(ctx, plan, recv_buffer, nullptr, SumOut{out_column, out_length});
 }
 
 int avr_fold_plan_own_projection(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
                                  const float* own_send_buffer, double* out_column, double* out_length) {
-  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, nullptr, nullptr, false, nullptr, false,
-                   out_column, out_length, true);
+  return fold_plan(ctx, plan, recv_buffer, own_send_buffer, SumOut{out_column, out_length});
 }
 
 int avr_fold_plan_image_projection(avr_context* ctx, const avr_frame_plan* plan,
@@ -1543,25 +1546,23 @@ int avr_fold_plan_image_projection(avr_context* ctx, const avr_frame_plan* plan,
     avr::set_error("avr_fold_plan_image_projection is for one rank's whole image");
     return AVR_ERR_INVALID_ARGUMENT;
   }
-  return fold_plan(ctx, plan, recv_buffer, nullptr, nullptr, nullptr, false, nullptr, false,
-                   out_column, out_length, true);
+  return fold_plan(ctx, plan, recv_buffer, nullptr, SumOut{out_column, out_length});
 }
 
 namespace {
 int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_buffer,
-              const float* own_send_buffer, float* out_piece, uint8_t* out_rgb8, bool to_image,
-              int16_t* out_index, bool max_intensity, double* out_column, double* out_length,
-              bool projection) {
+              const float* own_send_buffer, const avr::FoldOut& out, bool to_image) {
   return guarded([&]() -> int {
     bind_device(ctx);
     require(plan != nullptr, "null argument");
-    require(!to_image || (plan->info.n_ranks == 1 && out_rgb8 != nullptr),
+    const bool has_rgb8 = std::visit(
+        [](auto o) { return std::is_same_v<decltype(o.second), uint8_t*> && o.second != nullptr; }, out);
+    require(!to_image || (plan->info.n_ranks == 1 && has_rgb8),
             "avr_fold_plan_image is for one rank's whole image");
     // (a rank whose piece is empty -- more ranks than pixels, or row bands on a short image --
     // has nothing to fold and may pass empty buffers)
     if (plan->info.piece_end <= plan->info.piece_begin) return AVR_OK;
-    require(out_piece != nullptr || out_rgb8 != nullptr || out_index != nullptr ||
-                out_column != nullptr || out_length != nullptr,
+    require(std::visit([](auto o) { return o.first != nullptr || o.second != nullptr; }, out),
             "null argument");
     require(plan->info.recv_floats == 0 || recv_buffer != nullptr, "null receive buffer");
     avr::FoldLaunch launch;
@@ -1582,13 +1583,7 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
     launch.piece_end = plan->info.piece_end;
     launch.n_runs = plan->info.n_runs_total;
     launch.recv = recv_buffer;
-    launch.out_piece = out_piece;
-    launch.out_rgb8 = out_rgb8;
-    launch.max_intensity = max_intensity ? 1 : 0;
-    launch.out_index = out_index;
-    launch.projection = projection ? 1 : 0;
-    launch.out_column = out_column;
-    launch.out_length = out_length;
+    launch.out = out;
     // One rank folds the whole image while the next frame's paint kernels start, and nothing
     // waits for it: one workgroup per CU keeps it out of their way (0.997 -> 0.980 ms per frame).
     // A rank of several folds its piece on the stream that also carries the exchange and the

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "../../include/avr_hip.h"
@@ -245,6 +246,14 @@ void box_row_spans(const avr_box& box, const avr_camera& camera, int width, int 
 void plan_frame(const avr_box* boxes, int n_boxes, const avr_scalar_transform& transform,
                 const avr_paint_params& params, const avr_camera& camera, FramePlan* plan);
 
+// What a frame's pixels are.  The march, the layers' encoding and the fold depend on it; the plan,
+// the exchange and the gather carry every kind alike.
+enum class FrameKind : int {
+  kVolume,        // emission-absorption through the transfer function: Layer5 pixels, blended
+  kMaxIntensity,  // the largest table index along the ray; the fold takes the maximum
+  kProjection,    // column and length of the raw f64 cells along the ray; the fold adds
+};
+
 // ---- kernel launchers (avr_kernels.hip); all asynchronous on `stream` (hipStream_t) ---------
 struct RenderLaunch {
   FrameConsts consts;
@@ -290,11 +299,9 @@ struct RenderLaunch {
   // order), the classify launch of chunk k + 1 leaves out the others (indexed like its box list)
   uint8_t* visible_out = nullptr;
   const uint8_t* visible_in = nullptr;
-  // a maximum-intensity frame (render_runs_max_kernel): one launch, no speculation, no culling
-  int max_intensity = 0;
-  // a column projection (render_runs_sum_kernel): no classify pass, the raw cells, no tables; one
-  // launch, no speculation, no culling
-  int projection = 0;
+  // kMaxIntensity (render_runs_max_kernel) and kProjection (render_runs_sum_kernel: no classify
+  // pass, the raw cells, no tables) are one launch each: no chunks, no culling, no speculation
+  FrameKind kind = FrameKind::kVolume;
 };
 // classify pass (cells -> table indices) and march; the march reads what the classify pass of
 // the same frame wrote into `classified`
@@ -309,6 +316,23 @@ int launch_blend_regions(int kind, const void* top, int64_t tb, int64_t te, cons
                          int64_t bb, int64_t be, void* out, void* stream);
 int launch_encode_u8(const float* rgba, uint32_t* out, int64_t n, void* stream);
 int launch_decode_u8(const uint32_t* in, float* rgba, int64_t n, void* stream);
+// The two pieces a fold writes (piece order; either may be null), each kind with its own types:
+// kVolume the Layer5 piece and its RGB8 bytes, kMaxIntensity the index piece (-1 = no sample) and
+// the winner's RGB8 bytes, kProjection the f64 column and length pieces.
+template <FrameKind KIND, typename FIRST, typename SECOND>
+struct FoldPair {
+  static constexpr FrameKind kKind = KIND;
+  using First = FIRST;
+  using Second = SECOND;
+  FIRST* first = nullptr;
+  SECOND* second = nullptr;
+};
+// The outputs of one fold: one kind's pair (the alternative's index is the kind).
+using FoldOut = std::variant<FoldPair<FrameKind::kVolume, float, uint8_t>,
+                             FoldPair<FrameKind::kMaxIntensity, int16_t, uint8_t>,
+                             FoldPair<FrameKind::kProjection, double, double>>;
+template <FrameKind KIND>
+using FoldOutputs = std::variant_alternative_t<static_cast<size_t>(KIND), FoldOut>;
 struct FoldLaunch {
   int width;
   PieceMapDev pieces;
@@ -319,24 +343,13 @@ struct FoldLaunch {
   const RunBlockDev* run_blocks_dev;   // n_runs: block of this rank's piece in the recv buffer
   const RunSpanDev* run_spans_dev;     // rows of the blocks with span_base >= 0 (may be null)
   const float* recv;
-  float* out_piece;
-  uint8_t* out_rgb8;                   // may be null
+  FoldOut out;
   // Blocks whose offset in the receive layout lies in [own_begin, own_end) -- the rank's own runs
   // -- are read own_delta floats away from there: from the send buffer the march stored them in
   // (avr_fold_plan_own).  own_begin == own_end: everything from recv.
   int64_t own_begin = 0, own_end = 0, own_delta = 0;
   int max_workgroups = 0;              // grid cap (0: the default, 2048)
-  int flip_height = 0;                 // > 0: out_rgb8 is the whole image, rows top-down (one rank)
-  // maximum-intensity frames (fold_plan_max_kernel): the max fold; out_piece is not written, the
-  // index piece (piece order, -1 = no sample) goes to out_index (may be null)
-  int max_intensity = 0;
-  int16_t* out_index = nullptr;
-  // column projections (fold_plan_kernel<OWN, false, true>): the sum fold; out_piece and out_rgb8
-  // are not written, the f64 column and length pieces (piece order) go to out_column / out_length
-  // (either may be null)
-  int projection = 0;
-  double* out_column = nullptr;
-  double* out_length = nullptr;
+  int flip_height = 0;                 // > 0: the RGB8 output is the whole image, rows top-down (one rank)
 };
 // Picture of a column projection (width x height f64 column and length, row 0 at the bottom):
 // per pixel the quantity (column, or column / length if mean; log10 if log_scale) of pixels with

@@ -230,28 +230,34 @@ __device__ __forceinline__ uint32_t cell_offset(const BoxDev& box, uint32_t row_
                                                   near_hits);
 }
 
-// The march of one ray through one box (VolumePainter.cpp:811-921 + host epilogue :939-955).
-// Returns the layer pixel the reference would store for this box.
-// MAX (maximum-intensity projection): the same samples at the same positions, but as if the
-// accumulator never saturated -- every sample up to tmax is taken -- and per sample one byte gather
-// and one integer max; returns the largest table index sampled, -1 if none.
-// SUM (column projection): the samples of MAX, but per sample one f64 gather
+// The march of one ray through one box (VolumePainter.cpp:811-921 + host epilogue :939-955), by
+// the kind of frame (FrameKind, avr_internal.h):
+// kVolume: returns the layer pixel the reference would store for this box.
+// kMaxIntensity: the same samples at the same positions, but as if the accumulator never
+// saturated -- every sample up to tmax is taken -- and per sample one byte gather and one integer
+// max; returns the largest table index sampled, -1 if none.
+// kProjection: the samples of kMaxIntensity, but per sample one f64 gather
 // of the raw cell value (box.cells, no classify pass, no table) and, if it is finite, one f64 add
 // in march order and one count; returns the sum and the count of the finite samples.
-// (MAX and SUM take the ray by value: by reference its fields were loaded as overlapping float
-// pairs from a stack copy that then stayed in scratch memory)
+// (The two kinds other than kVolume take the ray by value: by reference its fields were loaded as
+// overlapping float pairs from a stack copy that then stayed in scratch memory)
 struct ColumnSum {
   double sum;
   unsigned count;
 };
-template <bool STATS, int MODE, bool MAX = false, bool SUM = false>
-__device__ __forceinline__ std::conditional_t<SUM, ColumnSum, std::conditional_t<MAX, int, Layer5>>
+template <FrameKind KIND> struct MarchOf { using Result = Layer5; using RayArg = const Ray&; };
+template <> struct MarchOf<FrameKind::kMaxIntensity> { using Result = int; using RayArg = const Ray; };
+template <> struct MarchOf<FrameKind::kProjection> { using Result = ColumnSum; using RayArg = const Ray; };
+
+template <bool STATS, int MODE, FrameKind KIND = FrameKind::kVolume>
+__device__ __forceinline__ typename MarchOf<KIND>::Result
 march_box(const BoxDev& box, const FrameConsts& fc,
                                             const uint8_t* __restrict__ classified,
                                             const float4* __restrict__ table,
-                                            std::conditional_t<MAX || SUM, const Ray, const Ray&> ray,
+                                            typename MarchOf<KIND>::RayArg ray,
                                             float tmin, float tmax, unsigned& fetches,
                                             unsigned& near_hits) {
+  constexpr bool is_max = KIND == FrameKind::kMaxIntensity, is_sum = KIND == FrameKind::kProjection;
   const float min_x = box.minc[0], min_y = box.minc[1], min_z = box.minc[2];
   const float max_x = box.maxc[0], max_y = box.maxc[1], max_z = box.maxc[2];
   const float step = box.sample_dist;
@@ -259,11 +265,11 @@ march_box(const BoxDev& box, const FrameConsts& fc,
       (const uint8_t __attribute__((address_space(1)))*)(classified + box.cls_offset);
   const uint32_t bricks_z = static_cast<uint32_t>(box.nz + kBrickZ - 1) >> 2;
   const uint32_t bricks_y = static_cast<uint32_t>(box.ny + kBrickY - 1) >> 2;
-  const uint32_t row_pitch = SUM ? static_cast<uint32_t>(box.jstride)     // (cell_address<SUM>)
+  const uint32_t row_pitch = is_sum ? static_cast<uint32_t>(box.jstride)     // (cell_address<is_sum>)
                                  : bricks_z * kBrickBytes - 32u;              // y_pitch of bricklet_offset
-  const uint32_t plane_pitch = SUM ? static_cast<uint32_t>(box.kstride)
+  const uint32_t plane_pitch = is_sum ? static_cast<uint32_t>(box.kstride)
                                    : bricks_y * bricks_z * kBrickBytes - 8u;  // x_pitch
-  // (SUM) the raw cells, addressed by byte offset
+  // (is_sum) the raw cells, addressed by byte offset
   [[maybe_unused]] const uint8_t __attribute__((address_space(1)))* values =
       (const uint8_t __attribute__((address_space(1)))*)(box.cells);
 
@@ -271,8 +277,8 @@ march_box(const BoxDev& box, const FrameConsts& fc,
   if (distance < 0.0f) distance = box.mesh_eps;
 
   float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, acc_a = 0.0f;
-  [[maybe_unused]] int best = -1;  // (MAX)
-  [[maybe_unused]] double sum = 0.0;  // (SUM) finite values in march order, and their number
+  [[maybe_unused]] int best = -1;  // (is_max)
+  [[maybe_unused]] double sum = 0.0;  // (is_sum) finite values in march order, and their number
   [[maybe_unused]] unsigned count = 0u;
 
 #define AVR_INSIDE(x, y, z) \
@@ -361,9 +367,9 @@ march_box(const BoxDev& box, const FrameConsts& fc,
             const float_pair qx = __builtin_elementwise_fma(ray.ox + ray.dx * dd, ix2, nx2);
             const float_pair qy = __builtin_elementwise_fma(ray.oy + ray.dy * dd, iy2, ny2);
             const float_pair qz = __builtin_elementwise_fma(ray.oz + ray.dz * dd, iz2, nz2);
-            off[2 * pair] = cell_address<SUM>(static_cast<int>(qx.x), static_cast<int>(qy.x),
+            off[2 * pair] = cell_address<is_sum>(static_cast<int>(qx.x), static_cast<int>(qy.x),
                                             static_cast<int>(qz.x), row_pitch, plane_pitch);
-            off[2 * pair + 1] = cell_address<SUM>(static_cast<int>(qx.y), static_cast<int>(qy.y),
+            off[2 * pair + 1] = cell_address<is_sum>(static_cast<int>(qx.y), static_cast<int>(qy.y),
                                                 static_cast<int>(qz.y), row_pitch, plane_pitch);
           } else {
             // the reference's two roundings, (pos - min) then * RN(1/d), as in the loop of four
@@ -371,13 +377,13 @@ march_box(const BoxDev& box, const FrameConsts& fc,
             const float_pair fy = (ray.oy + ray.dy * dd) - min_y;
             const float_pair fz = (ray.oz + ray.dz * dd) - min_z;
             const float_pair qx = fx * inv_x, qy = fy * inv_y, qz = fz * inv_z;
-            off[2 * pair] = offset_from_quotients<MODE, false, STATS, SUM>(
+            off[2 * pair] = offset_from_quotients<MODE, false, STATS, is_sum>(
                 box, row_pitch, plane_pitch, qx.x, qy.x, qz.x, fx.x, fy.x, fz.x, near_hits);
-            off[2 * pair + 1] = offset_from_quotients<MODE, false, STATS, SUM>(
+            off[2 * pair + 1] = offset_from_quotients<MODE, false, STATS, is_sum>(
                 box, row_pitch, plane_pitch, qx.y, qy.y, qz.y, fx.y, fy.y, fz.y, near_hits);
           }
         }
-        if constexpr (SUM) {
+        if constexpr (is_sum) {
           double v[kDeep];
 #pragma unroll
           for (int i = 0; i < kDeep; ++i) v[i] = AVR_VALUE(off[i]);
@@ -390,7 +396,7 @@ march_box(const BoxDev& box, const FrameConsts& fc,
         int idx[kDeep];
 #pragma unroll
         for (int i = 0; i < kDeep; ++i) idx[i] = cells[off[i]];
-        if constexpr (MAX) {
+        if constexpr (is_max) {
 #pragma unroll
           for (int i = 0; i < kDeep; ++i) best = (idx[i] > best) ? idx[i] : best;
           distance = d[kDeep - 1] + step;
@@ -457,19 +463,19 @@ march_box(const BoxDev& box, const FrameConsts& fc,
       if (!(d4 < safe_end)) break;
       uint32_t off1, off2, off3, off4;
       if (MODE == kExactDivide) {
-        off1 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
+        off1 = cell_offset<MODE, STATS, is_sum>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d1) - min_x,
                                         (ray.oy + ray.dy * d1) - min_y,
                                         (ray.oz + ray.dz * d1) - min_z, near_hits);
-        off2 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
+        off2 = cell_offset<MODE, STATS, is_sum>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d2) - min_x,
                                         (ray.oy + ray.dy * d2) - min_y,
                                         (ray.oz + ray.dz * d2) - min_z, near_hits);
-        off3 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
+        off3 = cell_offset<MODE, STATS, is_sum>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d3) - min_x,
                                         (ray.oy + ray.dy * d3) - min_y,
                                         (ray.oz + ray.dz * d3) - min_z, near_hits);
-        off4 = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch,
+        off4 = cell_offset<MODE, STATS, is_sum>(box, row_pitch, plane_pitch,
                                         (ray.ox + ray.dx * d4) - min_x,
                                         (ray.oy + ray.dy * d4) - min_y,
                                         (ray.oz + ray.dz * d4) - min_z, near_hits);
@@ -485,13 +491,13 @@ march_box(const BoxDev& box, const FrameConsts& fc,
         const float_pair qx34 = __builtin_elementwise_fma(ray.ox + ray.dx * d34, ix2, nx2);
         const float_pair qy34 = __builtin_elementwise_fma(ray.oy + ray.dy * d34, iy2, ny2);
         const float_pair qz34 = __builtin_elementwise_fma(ray.oz + ray.dz * d34, iz2, nz2);
-        off1 = cell_address<SUM>(static_cast<int>(qx12.x), static_cast<int>(qy12.x),
+        off1 = cell_address<is_sum>(static_cast<int>(qx12.x), static_cast<int>(qy12.x),
                                static_cast<int>(qz12.x), row_pitch, plane_pitch);
-        off2 = cell_address<SUM>(static_cast<int>(qx12.y), static_cast<int>(qy12.y),
+        off2 = cell_address<is_sum>(static_cast<int>(qx12.y), static_cast<int>(qy12.y),
                                static_cast<int>(qz12.y), row_pitch, plane_pitch);
-        off3 = cell_address<SUM>(static_cast<int>(qx34.x), static_cast<int>(qy34.x),
+        off3 = cell_address<is_sum>(static_cast<int>(qx34.x), static_cast<int>(qy34.x),
                                static_cast<int>(qz34.x), row_pitch, plane_pitch);
-        off4 = cell_address<SUM>(static_cast<int>(qx34.y), static_cast<int>(qy34.y),
+        off4 = cell_address<is_sum>(static_cast<int>(qx34.y), static_cast<int>(qy34.y),
                                static_cast<int>(qz34.y), row_pitch, plane_pitch);
       } else {
         // the reference's two roundings, (pos - min) then * RN(1/d), two samples per instruction
@@ -502,20 +508,20 @@ march_box(const BoxDev& box, const FrameConsts& fc,
         const float_pair qx12 = fx12 * inv_x, qx34 = fx34 * inv_x;
         const float_pair qy12 = fy12 * inv_y, qy34 = fy34 * inv_y;
         const float_pair qz12 = fz12 * inv_z, qz34 = fz34 * inv_z;
-        off1 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx12.x,
+        off1 = offset_from_quotients<MODE, false, STATS, is_sum>(box, row_pitch, plane_pitch, qx12.x,
                                                          qy12.x, qz12.x, fx12.x, fy12.x, fz12.x,
                                                          near_hits);
-        off2 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx12.y,
+        off2 = offset_from_quotients<MODE, false, STATS, is_sum>(box, row_pitch, plane_pitch, qx12.y,
                                                          qy12.y, qz12.y, fx12.y, fy12.y, fz12.y,
                                                          near_hits);
-        off3 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx34.x,
+        off3 = offset_from_quotients<MODE, false, STATS, is_sum>(box, row_pitch, plane_pitch, qx34.x,
                                                          qy34.x, qz34.x, fx34.x, fy34.x, fz34.x,
                                                          near_hits);
-        off4 = offset_from_quotients<MODE, false, STATS, SUM>(box, row_pitch, plane_pitch, qx34.y,
+        off4 = offset_from_quotients<MODE, false, STATS, is_sum>(box, row_pitch, plane_pitch, qx34.y,
                                                          qy34.y, qz34.y, fx34.y, fy34.y, fz34.y,
                                                          near_hits);
       }
-      if constexpr (SUM) {
+      if constexpr (is_sum) {
         const double v1 = AVR_VALUE(off1);
         const double v2 = AVR_VALUE(off2);
         const double v3 = AVR_VALUE(off3);
@@ -532,7 +538,7 @@ march_box(const BoxDev& box, const FrameConsts& fc,
       const int idx2 = cells[off2];
       const int idx3 = cells[off3];
       const int idx4 = cells[off4];
-      if constexpr (MAX) {
+      if constexpr (is_max) {
         const int m12 = (idx1 > idx2) ? idx1 : idx2;
         const int m34 = (idx3 > idx4) ? idx3 : idx4;
         const int m = (m12 > m34) ? m12 : m34;
@@ -626,11 +632,11 @@ march_box(const BoxDev& box, const FrameConsts& fc,
   // The reference's skip loop (:830-835) and the "continue" branch of the main loop (:838-844)
   // do the same thing -- advance without sampling while the position is outside -- so one loop
   // with an inside test reproduces both.
-  while (distance < tmax && (MAX || SUM || acc_a < 1.0f)) {
+  while (distance < tmax && (is_max || is_sum || acc_a < 1.0f)) {
     if (AVR_INSIDE(pos_x, pos_y, pos_z)) {
-      const uint32_t offset = cell_offset<MODE, STATS, SUM>(box, row_pitch, plane_pitch, pos_x - min_x,
-                                                       pos_y - min_y, pos_z - min_z, near_hits);
-      if constexpr (SUM) {
+      const uint32_t offset = cell_offset<MODE, STATS, is_sum>(
+          box, row_pitch, plane_pitch, pos_x - min_x, pos_y - min_y, pos_z - min_z, near_hits);
+      if constexpr (is_sum) {
         const double v = AVR_VALUE(offset);
         if (STATS) ++fetches;
         AVR_ADD(v);
@@ -639,7 +645,7 @@ march_box(const BoxDev& box, const FrameConsts& fc,
       // classify pass of this frame (same arithmetic as VolumePainter.cpp:870-883)
       const int idx = cells[offset];
       if (STATS) ++fetches;
-      if constexpr (MAX) {
+      if constexpr (is_max) {
         best = (idx > best) ? idx : best;
       } else {
         const float4 sample = table[idx];
@@ -657,9 +663,9 @@ march_box(const BoxDev& box, const FrameConsts& fc,
 #undef AVR_VALUE
 #undef AVR_ADD
 
-  if constexpr (SUM) {
+  if constexpr (is_sum) {
     return ColumnSum{sum, count};
-  } else if constexpr (MAX) {
+  } else if constexpr (is_max) {
     return best;
   } else {
     // device-side clamp (:902-905) then the host epilogue's std::clamp to [0,1] (:944-947)
@@ -689,22 +695,28 @@ march_box(const BoxDev& box, const FrameConsts& fc,
 
 // ONLY_MODE >= 0: every box of the launch uses that IndexMode (the common case: one scene, one
 // kind of spacing), so only that march variant is compiled in; -1 dispatches per box.
-// <= 80 SGPRs: 256-thread workgroups are admitted per CU up to floor(800 / (ceil(sgpr/16)*16 + 16))
-// (MI355X_MICROARCH.md, "Residency"), i.e. 8 per CU only up to 80 SGPRs, 6 at 98+.
-// SPEC: the speculative frame's bookkeeping is compiled in (one vector register more: six waves per
-// SIMD instead of seven, so it is its own instantiation; never together with STATS).
-// MAX: a maximum-intensity frame (render_runs_max_kernel; never with SPEC, chunks or culling): the
-// same work items, tiles, rays, culling and layer addressing, but every box a ray hits is marched
-// to its end (march_box<..., true>: no opacity, no skipped box) and the run's pixel is the largest
-// table index.  Layer encoding, so that plan, tightening, exchange and gather carry it unchanged:
-// a hit is (RGB of table entry `index`, 1, index), a miss the cleared pixel (0, 0, 0, 0, +inf).
-// SUM: a column-projection frame (render_runs_sum_kernel; never with SPEC, chunks or culling): as
-// MAX, but march_box<..., SUM> gathers the raw f64 cells (no classify pass, no tables in LDS) and
-// the run's pixel is column = sum of f64(step) * S_b and length = sum of f64(step) * n_b over its
-// boxes in order.  A hit (length > 0) is (column lo, column hi, length lo, 1, length hi) -- the
-// 32-bit halves of the two f64 as float bit patterns, which the plan, tightening, exchange and
-// gather copy without looking at them -- a miss the cleared pixel.
-template <bool STATS, int ONLY_MODE, bool SPEC, bool MAX = false, bool SUM = false>
+// Registers, as the compiler reports them (make asm): every march kernel takes 106 SGPRs except
+// the two ONLY_MODE = kPow2Multiply column projections (100), and spills some of them to vector
+// lanes (volume 15-44, maximum intensity 0-6, projection 0-25; no VGPR spills); 16 bytes of scratch
+// per lane in the speculative kernels, 24 in the two ONLY_MODE = -1 volume kernels, none elsewhere;
+// 85-105 VGPRs for a volume frame (5 waves per SIMD, 4 for the two non-speculative ONLY_MODE = -1
+// kernels), 46-56 for maximum intensity (7) and 58-73 for a projection (6-8).
+// SPEC: the speculative frame's bookkeeping is compiled in (its own instantiation; never together
+// with STATS).
+// KIND, the kind of frame (FrameKind, avr_internal.h; only kVolume goes with SPEC, chunks or
+// culling -- render() in avr_capi.cpp sees to that):
+// kMaxIntensity (render_runs_max_kernel): the same work items, tiles, rays, culling and layer
+// addressing, but every box a ray hits is marched to its end (no opacity, no skipped box) and the
+// run's pixel is the largest table index.  Layer encoding, so that plan, tightening, exchange and
+// gather carry it unchanged: a hit is (RGB of table entry `index`, 1, index), a miss the cleared
+// pixel (0, 0, 0, 0, +inf).
+// kProjection (render_runs_sum_kernel): as kMaxIntensity, but march_box gathers the raw f64 cells
+// (no classify pass, no tables in LDS) and the run's pixel is column = sum of f64(step) * S_b and
+// length = sum of f64(step) * n_b over its boxes in order.  A hit (length > 0) is (column lo,
+// column hi, length lo, 1, length hi) -- the 32-bit halves of the two f64 as float bit patterns,
+// which the plan, tightening, exchange and gather copy without looking at them -- a miss the
+// cleared pixel.
+template <bool STATS, int ONLY_MODE, bool SPEC, FrameKind KIND = FrameKind::kVolume>
 __device__ __forceinline__ void
 render_runs_body(
     const FrameConsts& fc, const BoxDev* __restrict__ boxes,
@@ -734,6 +746,7 @@ render_runs_body(
     // everything the true frame needs); a gated second classify + march, queued behind this launch,
     // then redo the frame with those boxes classified -- and do nothing when no flag was raised.
     const MarchSpecDev* __restrict__ spec) {
+  constexpr bool is_max = KIND == FrameKind::kMaxIntensity, is_sum = KIND == FrameKind::kProjection;
   extern __shared__ float4 lds_tables[];  // n_tables x 256 RGBA entries
   if (SPEC && spec != nullptr) {
     const uint32_t* const gate = spec->gate;
@@ -770,7 +783,7 @@ render_runs_body(
   }
 
   // ---- stage the transfer-function tables in LDS (one per AMR sampling level) -------------
-  if constexpr (!SUM) {
+  if constexpr (!is_sum) {
   {
     const float4* src = reinterpret_cast<const float4*>(tables);
     const int total = n_tables * kTableSize;
@@ -833,9 +846,9 @@ render_runs_body(
     const int run_begin = (run > 0) ? run_end[run - 1] : 0;
     const int end = (run_end[run] < pos_end) ? run_end[run] : pos_end;
     Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, AVR_INF};  // cleared layer pixel: exact blend identity
-    [[maybe_unused]] int acc_index = -1;              // (MAX) the run's largest index so far
-    [[maybe_unused]] double acc_column = 0.0, acc_length = 0.0;  // (SUM) the run's sums so far
-    if (!MAX && !SUM && resume != 0) {
+    [[maybe_unused]] int acc_index = -1;              // (is_max) the run's largest index so far
+    [[maybe_unused]] double acc_column = 0.0, acc_length = 0.0;  // (is_sum) the run's sums so far
+    if (!is_max && !is_sum && resume != 0) {
       const float* src = layer_pixel();
       if (src != nullptr) {
         acc.r = src[0];
@@ -878,49 +891,49 @@ render_runs_body(
       slab_axis(ray.oy, ray.dy, inv_dy, box.minc[1], box.maxc[1], tmin, tmax);
       slab_axis(ray.oz, ray.dz, inv_dz, box.minc[2], box.maxc[2], tmin, tmax);
       bool hit = live && (tmax >= tmin);
-      if constexpr (MAX) {
+      if constexpr (is_max) {
         // every sample counts: no box is skipped for opacity
         if (!__builtin_amdgcn_ballot_w64(hit)) continue;
         if (hit) {
           int m;
           if (ONLY_MODE == kPow2Multiply) {
-            m = march_box<STATS, kPow2Multiply, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+            m = march_box<STATS, kPow2Multiply, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                       fetches, near_hits);
           } else if (ONLY_MODE == kReciprocal) {
-            m = march_box<STATS, kReciprocal, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+            m = march_box<STATS, kReciprocal, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                     fetches, near_hits);
           } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
-            m = march_box<STATS, kPow2Multiply, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+            m = march_box<STATS, kPow2Multiply, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                       fetches, near_hits);
           } else if (box.index_mode == kReciprocal) {
-            m = march_box<STATS, kReciprocal, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+            m = march_box<STATS, kReciprocal, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                     fetches, near_hits);
           } else {
-            m = march_box<STATS, kExactDivide, true>(box, fc, classified, nullptr, ray, tmin, tmax,
+            m = march_box<STATS, kExactDivide, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                      fetches, near_hits);
           }
           acc_index = (m > acc_index) ? m : acc_index;
         }
         continue;
       }
-      if constexpr (SUM) {
+      if constexpr (is_sum) {
         if (!__builtin_amdgcn_ballot_w64(hit)) continue;
         if (hit) {
           ColumnSum c;
           if (ONLY_MODE == kPow2Multiply) {
-            c = march_box<STATS, kPow2Multiply, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+            c = march_box<STATS, kPow2Multiply, KIND>(box, fc, nullptr, nullptr, ray, tmin,
                                                              tmax, fetches, near_hits);
           } else if (ONLY_MODE == kReciprocal) {
-            c = march_box<STATS, kReciprocal, false, true>(box, fc, nullptr, nullptr, ray, tmin, tmax,
+            c = march_box<STATS, kReciprocal, KIND>(box, fc, nullptr, nullptr, ray, tmin, tmax,
                                                            fetches, near_hits);
           } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
-            c = march_box<STATS, kPow2Multiply, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+            c = march_box<STATS, kPow2Multiply, KIND>(box, fc, nullptr, nullptr, ray, tmin,
                                                              tmax, fetches, near_hits);
           } else if (box.index_mode == kReciprocal) {
-            c = march_box<STATS, kReciprocal, false, true>(box, fc, nullptr, nullptr, ray, tmin, tmax,
+            c = march_box<STATS, kReciprocal, KIND>(box, fc, nullptr, nullptr, ray, tmin, tmax,
                                                            fetches, near_hits);
           } else {
-            c = march_box<STATS, kExactDivide, false, true>(box, fc, nullptr, nullptr, ray, tmin,
+            c = march_box<STATS, kExactDivide, KIND>(box, fc, nullptr, nullptr, ray, tmin,
                                                             tmax, fetches, near_hits);
           }
           const double step = static_cast<double>(box.sample_dist);
@@ -997,7 +1010,7 @@ render_runs_body(
     // a + 1 * (1 - a), which need not round to 1), so every later box the pixel's ray hits counts
     // as visible.  By induction a box flagged invisible finds, at every pixel that hits it, the
     // accumulator this launch left -- and is skipped.
-    if (!MAX && !SUM && visible_out != nullptr) {
+    if (!is_max && !is_sum && visible_out != nullptr) {
       bool open = false;  // an earlier box to come is marched at this pixel
       // (the run's boxes behind this launch's; a run that only starts behind them: all of its boxes)
       for (int position = (end > run_begin) ? end : run_begin; position < run_end[run]; ++position) {
@@ -1024,13 +1037,13 @@ render_runs_body(
         if (__builtin_amdgcn_ballot_w64(visible) != 0 && lane == 0) visible_out[position] = 1;
       }
     }
-    if constexpr (MAX) {
+    if constexpr (is_max) {
       if (acc_index >= 0) {  // RGB does not depend on the level (only alpha does): any table will do
         const float4 c = lds_tables[acc_index];
         acc = {c.x, c.y, c.z, 1.0f, static_cast<float>(acc_index)};
       }
     }
-    if constexpr (SUM) {
+    if constexpr (is_sum) {
       if (acc_length > 0.0) {
         const uint64_t column = static_cast<uint64_t>(__double_as_longlong(acc_column));
         const uint64_t length = static_cast<uint64_t>(__double_as_longlong(acc_length));
@@ -1095,26 +1108,30 @@ render_runs_body(
     run_rects, run_blocks, run_spans, band_shift, tiles_x, tiles_y, items, out, samples_out,       \
     counters, pos_begin, pos_end, resume, visible_out, spec
 
+// workgroups per CU the compiler is to leave registers for, by the experiment build's group size
+constexpr int kMarchMinWorkgroups =
+    AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6;
+
 template <bool STATS, int ONLY_MODE, bool SPEC = false>
-__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_kernel(AVR_MARCH_PARAMETERS) {
+__global__ __launch_bounds__(kBlockThreads, kMarchMinWorkgroups) void render_runs_kernel(AVR_MARCH_PARAMETERS) {
   render_runs_body<STATS, ONLY_MODE, SPEC>(AVR_MARCH_ARGUMENTS);
 }
 
 // The gated second march of a speculative frame under a name of its own (a profile then tells the
 // marches that ran from the repair launches that found nothing to do).
 template <int ONLY_MODE>
-__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_repair_kernel(AVR_MARCH_PARAMETERS) {
+__global__ __launch_bounds__(kBlockThreads, kMarchMinWorkgroups) void render_runs_repair_kernel(AVR_MARCH_PARAMETERS) {
   render_runs_body<false, ONLY_MODE, true>(AVR_MARCH_ARGUMENTS);
 }
-// The maximum-intensity march (render_runs_body<..., MAX = true>).
+// The maximum-intensity march.
 template <bool STATS, int ONLY_MODE>
-__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_max_kernel(AVR_MARCH_PARAMETERS) {
-  render_runs_body<STATS, ONLY_MODE, false, true>(AVR_MARCH_ARGUMENTS);
+__global__ __launch_bounds__(kBlockThreads, kMarchMinWorkgroups) void render_runs_max_kernel(AVR_MARCH_PARAMETERS) {
+  render_runs_body<STATS, ONLY_MODE, false, FrameKind::kMaxIntensity>(AVR_MARCH_ARGUMENTS);
 }
-// The column-projection march (render_runs_body<..., SUM = true>).
+// The column-projection march.
 template <bool STATS, int ONLY_MODE>
-__global__ __launch_bounds__(kBlockThreads, AVR_MARCH_GROUP >= 16 ? 3 : AVR_MARCH_GROUP >= 8 ? 4 : AVR_MARCH_GROUP >= 6 ? 5 : 6) void render_runs_sum_kernel(AVR_MARCH_PARAMETERS) {
-  render_runs_body<STATS, ONLY_MODE, false, false, true>(AVR_MARCH_ARGUMENTS);
+__global__ __launch_bounds__(kBlockThreads, kMarchMinWorkgroups) void render_runs_sum_kernel(AVR_MARCH_PARAMETERS) {
+  render_runs_body<STATS, ONLY_MODE, false, FrameKind::kProjection>(AVR_MARCH_ARGUMENTS);
 }
 #undef AVR_MARCH_PARAMETERS
 #undef AVR_MARCH_ARGUMENTS
@@ -1589,24 +1606,26 @@ struct FoldEntry {
 };
 
 //
-// MAX (maximum-intensity frames): among the covering runs with a hit
-// (a != 0, see render_runs_body) the one of the largest index (d) wins -- max is exact and
-// order-free; the bytes are its table RGB, and `out_piece` (optional) is then an int16_t index
-// piece, -1 for a miss.  (The parameter list stays that of the blend fold: its instantiations
-// compile to the instructions they had before MAX.)
-// SUM (column projections): the covering runs with a hit (a != 0) are added in fold order, column
-// and length in f64 (see render_runs_body for the encoding); `out_piece` (optional) is then the
-// f64 column piece and `out_rgb8` (optional) the f64 length piece, 0 where no run took a finite
-// sample.
-template <bool OWN, bool MAX = false, bool SUM = false>
+// The two outputs (FoldOutputs<KIND>, avr_internal.h; either may be null) by the kind of frame:
+// kVolume: `first` the Layer5 piece, `second` its RGB8 bytes.
+// kMaxIntensity: among the covering runs with a hit (a != 0, see render_runs_body) the one of the
+// largest index (d) wins -- max is exact and order-free; `second` the bytes of its table RGB,
+// `first` the int16_t index piece, -1 for a miss.
+// kProjection: the covering runs with a hit (a != 0) are added in fold order, column and length in
+// f64 (see render_runs_body for the encoding); `first` the f64 column piece and `second` the f64
+// length piece, 0 where no run took a finite sample.
+// (Every kind takes two pointers at the same place in the parameter list: one argument block.)
+template <bool OWN, FrameKind KIND = FrameKind::kVolume>
 __global__ __launch_bounds__(256) void fold_plan_kernel(
     const int width, const int64_t piece_begin, const int64_t piece_end, const int n_runs,
     const RunRectDev* __restrict__ rects, const RunBlockDev* __restrict__ blocks,
     const RunSpanDev* __restrict__ spans, const float* __restrict__ recv,
-    float* __restrict__ out_piece,
-    uint8_t* __restrict__ out_rgb8, const int first_row, const int chunks_per_row,
+    typename FoldOutputs<KIND>::First* __restrict__ out_first,
+    typename FoldOutputs<KIND>::Second* __restrict__ out_second, const int first_row,
+    const int chunks_per_row,
     const PieceMapDev pieces, const int piece, const int64_t own_begin, const int64_t own_end,
     const int64_t own_delta, const int n_segments, const int flip_height) {
+  constexpr bool is_max = KIND == FrameKind::kMaxIntensity, is_sum = KIND == FrameKind::kProjection;
   __shared__ FoldEntry list[256];
   __shared__ int wave_count[4];
   const int tid = static_cast<int>(threadIdx.x);
@@ -1629,8 +1648,8 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
   const int64_t p = static_cast<int64_t>(block_row) * width + px;
   const bool live = (px < width) && (p >= piece_begin) && (p < piece_end);
 
-  Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, MAX ? -1.0f : AVR_INF};
-  [[maybe_unused]] double column = 0.0, length = 0.0;  // (SUM)
+  Layer5 acc = {0.0f, 0.0f, 0.0f, 0.0f, is_max ? -1.0f : AVR_INF};
+  [[maybe_unused]] double column = 0.0, length = 0.0;  // (is_sum)
   for (int chunk = 0; chunk < n_runs; chunk += 256) {
     const int g = chunk + tid;
     bool touches = false;
@@ -1673,14 +1692,14 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
       if (live && px >= run.x0 && px <= run.x1) {
         const float* src = recv + run.base + static_cast<int64_t>(px) * 5;
         const Layer5 layer = {src[0], src[1], src[2], src[3], src[4]};
-        if constexpr (SUM) {
+        if constexpr (is_sum) {
           if (layer.a != 0.0f) {
             column += __longlong_as_double(static_cast<long long>(
                 (static_cast<uint64_t>(__float_as_uint(layer.g)) << 32) | __float_as_uint(layer.r)));
             length += __longlong_as_double(static_cast<long long>(
                 (static_cast<uint64_t>(__float_as_uint(layer.d)) << 32) | __float_as_uint(layer.b)));
           }
-        } else if constexpr (MAX) {
+        } else if constexpr (is_max) {
           if (layer.a != 0.0f && layer.d > acc.d) acc = layer;
         } else {
           acc = blend_depthsort(acc, layer);
@@ -1691,34 +1710,35 @@ __global__ __launch_bounds__(256) void fold_plan_kernel(
   }
   if (!live) continue;  // (after the chunk loop's closing barrier: the list is free again)
   const int64_t q = p - piece_begin;
-  if constexpr (SUM) {
-    if (out_piece != nullptr) reinterpret_cast<double*>(out_piece)[q] = column;
-    if (out_rgb8 != nullptr) reinterpret_cast<double*>(out_rgb8)[q] = length;
-    continue;
-  }
-  if (!MAX && out_piece != nullptr) {
-    float* d = out_piece + q * 5;
-    d[0] = acc.r;
-    d[1] = acc.g;
-    d[2] = acc.b;
-    d[3] = acc.a;
-    d[4] = acc.d;
-  }
-  if (out_rgb8 != nullptr) {
-    // flip_height > 0 (one rank, the piece is the image): the bytes go straight to the output
-    // file's rows, top-down (SavePPM.cpp:25) -- avr_assemble_rows' flip in the same pass
-    const int64_t at = (flip_height > 0)
-                           ? static_cast<int64_t>(flip_height - 1 - row) * width + px
-                           : q;
-    uint8_t* b = out_rgb8 + at * 3;
-    b[0] = static_cast<uint8_t>(component_as_byte(acc.r));
-    b[1] = static_cast<uint8_t>(component_as_byte(acc.g));
-    b[2] = static_cast<uint8_t>(component_as_byte(acc.b));
-  }
-  if constexpr (MAX) {
-    if (out_piece != nullptr) {
-      reinterpret_cast<int16_t*>(out_piece)[q] =
-          static_cast<int16_t>(acc.a != 0.0f ? static_cast<int>(acc.d) : -1);
+  if constexpr (is_sum) {
+    if (out_first != nullptr) out_first[q] = column;
+    if (out_second != nullptr) out_second[q] = length;
+  } else {
+    if constexpr (!is_max) {
+      if (out_first != nullptr) {
+        float* d = out_first + q * 5;
+        d[0] = acc.r;
+        d[1] = acc.g;
+        d[2] = acc.b;
+        d[3] = acc.a;
+        d[4] = acc.d;
+      }
+    }
+    if (out_second != nullptr) {
+      // flip_height > 0 (one rank, the piece is the image): the bytes go straight to the output
+      // file's rows, top-down (SavePPM.cpp:25) -- avr_assemble_rows' flip in the same pass
+      const int64_t at = (flip_height > 0)
+                             ? static_cast<int64_t>(flip_height - 1 - row) * width + px
+                             : q;
+      uint8_t* b = out_second + at * 3;
+      b[0] = static_cast<uint8_t>(component_as_byte(acc.r));
+      b[1] = static_cast<uint8_t>(component_as_byte(acc.g));
+      b[2] = static_cast<uint8_t>(component_as_byte(acc.b));
+    }
+    if constexpr (is_max) {
+      if (out_first != nullptr) {
+        out_first[q] = static_cast<int16_t>(acc.a != 0.0f ? static_cast<int>(acc.d) : -1);
+      }
     }
   }
   }  // segments
@@ -2005,6 +2025,22 @@ int launch_classify(const RenderLaunch& L, void* stream_v) {
   return check_launch("classify_kernel");
 }
 
+// Calls f(STATS, ONLY_MODE) with the two template arguments of a march kernel as integral
+// constants: launch_march picks them here, once, for every kernel family.
+template <typename F>
+void with_march_variant(bool stats, int only_mode, F&& f) {
+  const auto with_mode = [&](auto stats_c) {
+    if (only_mode == kPow2Multiply) {
+      f(stats_c, std::integral_constant<int, kPow2Multiply>{});
+    } else if (only_mode == kReciprocal) {
+      f(stats_c, std::integral_constant<int, kReciprocal>{});
+    } else {
+      f(stats_c, std::integral_constant<int, -1>{});
+    }
+  };
+  if (stats) with_mode(std::true_type{}); else with_mode(std::false_type{});
+}
+
 int launch_march(const RenderLaunch& L, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const int tiles_x = (L.consts.width + kTile - 1) / kTile;
@@ -2012,7 +2048,9 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
   const unsigned blocks = L.n_items * kSuperTileTiles;
   if (blocks == 0) return AVR_OK;
   // (a column projection reads no tables)
-  size_t lds_bytes = L.projection ? 0 : static_cast<size_t>(L.n_tables) * kTableSize * sizeof(float4);
+  size_t lds_bytes = L.kind == FrameKind::kProjection
+                         ? 0
+                         : static_cast<size_t>(L.n_tables) * kTableSize * sizeof(float4);
   if (L.workgroups_per_cu > 0) {
     // Occupancy cap through the LDS allocation: n workgroups of 160 KiB / n minus a share of the
     // 10 KiB left for the co-resident kernel's own LDS (classify_kernel stages 2 KiB per workgroup).
@@ -2029,101 +2067,44 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
       return AVR_ERR_INVALID_ARGUMENT;
     }
   }
-#define AVR_LAUNCH(STATS, ONLY)                                                                 \
-  hipLaunchKernelGGL((render_runs_kernel<STATS, ONLY>), dim3(blocks), dim3(kBlockThreads),      \
-                     lds_bytes, stream, L.consts, L.boxes_dev, L.classified, L.tables_dev,      \
-                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
-                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
-                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
-                     tiles_y,                                                                    \
-                     L.items_dev,                                                                \
-                     L.out_layers, L.samples_out, L.counters, L.pos_begin,                       \
-                     (L.pos_end < 0 ? L.n_order : L.pos_end), L.resume, L.visible_out, L.spec_dev)
+  // The four kernel families take one argument list.  A maximum-intensity frame or a projection
+  // is one launch without speculation: render(), where the kind enters, leaves resume, visible_out
+  // and spec_dev unset for them, and classified null for a projection.  tables_dev is passed to
+  // the projection march too, which ignores it (no tables are staged for that kind).
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlockThreads), lds_bytes, stream, L.consts,
+                       L.boxes_dev, L.classified, L.tables_dev, L.n_tables, L.order_dev,
+                       reinterpret_cast<const int4*>(L.order_rects_dev), L.run_end_dev, L.n_runs,
+                       L.n_pieces, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift,
+                       tiles_x, tiles_y, L.items_dev, L.out_layers, L.samples_out, L.counters,
+                       L.pos_begin, (L.pos_end < 0 ? L.n_order : L.pos_end), L.resume,
+                       L.visible_out, L.spec_dev);
+  };
   if (L.spec_dev != nullptr) {
-    if (L.max_intensity || L.projection) {
-      set_error("render_runs_kernel: a maximum-intensity frame is not speculative");
-      return AVR_ERR_INVALID_ARGUMENT;
-    }
     if (stats) {
       set_error("render_runs_kernel: a speculative frame cannot count samples");
       return AVR_ERR_INVALID_ARGUMENT;
     }
-#define AVR_LAUNCH_SPEC(ONLY)                                                                    \
-  hipLaunchKernelGGL((L.spec_is_repair ? render_runs_repair_kernel<ONLY>                           \
-                                       : render_runs_kernel<false, ONLY, true>),                  \
-                     dim3(blocks), dim3(kBlockThreads),                                            \
-                     lds_bytes, stream, L.consts, L.boxes_dev, L.classified, L.tables_dev,       \
-                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
-                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
-                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
-                     tiles_y,                                                                    \
-                     L.items_dev,                                                                \
-                     L.out_layers, L.samples_out, L.counters, L.pos_begin,                       \
-                     (L.pos_end < 0 ? L.n_order : L.pos_end), L.resume, L.visible_out, L.spec_dev)
-    if (L.only_mode == kPow2Multiply) {
-      AVR_LAUNCH_SPEC(kPow2Multiply);
-    } else if (L.only_mode == kReciprocal) {
-      AVR_LAUNCH_SPEC(kReciprocal);
-    } else {
-      AVR_LAUNCH_SPEC(-1);
-    }
-#undef AVR_LAUNCH_SPEC
+    with_march_variant(false, L.only_mode, [&](auto, auto only) {
+      launch(L.spec_is_repair ? render_runs_repair_kernel<only()> : render_runs_kernel<false, only(), true>);
+    });
     return check_launch("render_runs_kernel (speculative)");
   }
-  if (L.max_intensity) {
-    if (L.resume != 0 || L.visible_out != nullptr) {
-      set_error("render_runs_max_kernel: a maximum-intensity frame is one launch, not chunks");
-      return AVR_ERR_INVALID_ARGUMENT;
-    }
-#define AVR_LAUNCH_MAX(STATS, ONLY)                                                             \
-  hipLaunchKernelGGL((render_runs_max_kernel<STATS, ONLY>), dim3(blocks), dim3(kBlockThreads),  \
-                     lds_bytes, stream, L.consts, L.boxes_dev, L.classified, L.tables_dev,      \
-                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
-                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
-                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
-                     tiles_y, L.items_dev, L.out_layers, L.samples_out, L.counters, L.pos_begin, \
-                     (L.pos_end < 0 ? L.n_order : L.pos_end), 0, nullptr, nullptr)
-    if (L.only_mode == kPow2Multiply) {
-      if (stats) AVR_LAUNCH_MAX(true, kPow2Multiply); else AVR_LAUNCH_MAX(false, kPow2Multiply);
-    } else if (L.only_mode == kReciprocal) {
-      if (stats) AVR_LAUNCH_MAX(true, kReciprocal); else AVR_LAUNCH_MAX(false, kReciprocal);
-    } else {
-      if (stats) AVR_LAUNCH_MAX(true, -1); else AVR_LAUNCH_MAX(false, -1);
-    }
-#undef AVR_LAUNCH_MAX
+  if (L.kind == FrameKind::kMaxIntensity) {
+    with_march_variant(stats, L.only_mode, [&](auto stats_c, auto only) {
+      launch(render_runs_max_kernel<stats_c(), only()>);
+    });
     return check_launch("render_runs_max_kernel");
   }
-  if (L.projection) {
-    if (L.resume != 0 || L.visible_out != nullptr) {
-      set_error("render_runs_sum_kernel: a column projection is one launch, not chunks");
-      return AVR_ERR_INVALID_ARGUMENT;
-    }
-#define AVR_LAUNCH_SUM(STATS, ONLY)                                                             \
-  hipLaunchKernelGGL((render_runs_sum_kernel<STATS, ONLY>), dim3(blocks), dim3(kBlockThreads),  \
-                     lds_bytes, stream, L.consts, L.boxes_dev, nullptr, nullptr,                 \
-                     L.n_tables, L.order_dev, reinterpret_cast<const int4*>(L.order_rects_dev),  \
-                     L.run_end_dev, L.n_runs, L.n_pieces,                                        \
-                     L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, band_shift, tiles_x,    \
-                     tiles_y, L.items_dev, L.out_layers, L.samples_out, L.counters, L.pos_begin, \
-                     (L.pos_end < 0 ? L.n_order : L.pos_end), 0, nullptr, nullptr)
-    if (L.only_mode == kPow2Multiply) {
-      if (stats) AVR_LAUNCH_SUM(true, kPow2Multiply); else AVR_LAUNCH_SUM(false, kPow2Multiply);
-    } else if (L.only_mode == kReciprocal) {
-      if (stats) AVR_LAUNCH_SUM(true, kReciprocal); else AVR_LAUNCH_SUM(false, kReciprocal);
-    } else {
-      if (stats) AVR_LAUNCH_SUM(true, -1); else AVR_LAUNCH_SUM(false, -1);
-    }
-#undef AVR_LAUNCH_SUM
+  if (L.kind == FrameKind::kProjection) {
+    with_march_variant(stats, L.only_mode, [&](auto stats_c, auto only) {
+      launch(render_runs_sum_kernel<stats_c(), only()>);
+    });
     return check_launch("render_runs_sum_kernel");
   }
-  if (L.only_mode == kPow2Multiply) {
-    if (stats) AVR_LAUNCH(true, kPow2Multiply); else AVR_LAUNCH(false, kPow2Multiply);
-  } else if (L.only_mode == kReciprocal) {
-    if (stats) AVR_LAUNCH(true, kReciprocal); else AVR_LAUNCH(false, kReciprocal);
-  } else {
-    if (stats) AVR_LAUNCH(true, -1); else AVR_LAUNCH(false, -1);
-  }
-#undef AVR_LAUNCH
+  with_march_variant(stats, L.only_mode, [&](auto stats_c, auto only) {
+    launch(render_runs_kernel<stats_c(), only()>);
+  });
   return check_launch("render_runs_kernel");
 }
 
@@ -2200,35 +2181,24 @@ int launch_fold_plan(const FoldLaunch& L, void* stream_v) {
     return AVR_ERR_INVALID_ARGUMENT;
   }
   const int64_t grid = std::min<int64_t>(blocks, L.max_workgroups > 0 ? L.max_workgroups : kFoldWorkgroups);
-  if (L.max_intensity) {
-    auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true, true> : fold_plan_kernel<false, true>;
+  const bool own = L.own_end > L.own_begin;
+  const auto launch = [&](const auto& out, const char* what) {
+    constexpr FrameKind kind = std::decay_t<decltype(out)>::kKind;
+    const auto kernel = own ? fold_plan_kernel<true, kind> : fold_plan_kernel<false, kind>;
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
                        static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
-                       L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,
-                       reinterpret_cast<float*>(L.out_index), L.out_rgb8,
-                       first_row, chunks_per_row, L.pieces, L.piece, L.own_begin, L.own_end,
-                       L.own_delta, static_cast<int>(blocks), L.flip_height);
-    return check_launch("fold_plan_kernel (maximum intensity)");
+                       L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv, out.first,
+                       out.second, first_row, chunks_per_row, L.pieces, L.piece, L.own_begin,
+                       L.own_end, L.own_delta, static_cast<int>(blocks), L.flip_height);
+    return check_launch(what);
+  };
+  if (const auto* out = std::get_if<FoldOutputs<FrameKind::kMaxIntensity>>(&L.out)) {
+    return launch(*out, "fold_plan_kernel (maximum intensity)");
   }
-  if (L.projection) {
-    auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true, false, true>
-                                            : fold_plan_kernel<false, false, true>;
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
-                       L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,
-                       reinterpret_cast<float*>(L.out_column), reinterpret_cast<uint8_t*>(L.out_length),
-                       first_row, chunks_per_row, L.pieces, L.piece, L.own_begin, L.own_end,
-                       L.own_delta, static_cast<int>(blocks), 0);
-    return check_launch("fold_plan_kernel (column projection)");
+  if (const auto* out = std::get_if<FoldOutputs<FrameKind::kProjection>>(&L.out)) {
+    return launch(*out, "fold_plan_kernel (column projection)");
   }
-  auto kernel = (L.own_end > L.own_begin) ? fold_plan_kernel<true> : fold_plan_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_v), L.width, L.piece_begin, L.piece_end,
-                     L.n_runs, L.run_rects_dev, L.run_blocks_dev, L.run_spans_dev, L.recv,
-                     L.out_piece, L.out_rgb8,
-                     first_row, chunks_per_row, L.pieces, L.piece, L.own_begin, L.own_end,
-                     L.own_delta, static_cast<int>(blocks), L.flip_height);
-  return check_launch("fold_plan_kernel");
+  return launch(std::get<FoldOutputs<FrameKind::kVolume>>(L.out), "fold_plan_kernel");
 }
 
 int launch_fold_runs(const float* const* slices_dev, int n_slices, float* out, int64_t n,

@@ -1055,14 +1055,75 @@ int avr_renderer_prepare(avr_renderer* r, const avr_render_params* render, const
 
 namespace {
 
-// One frame of avr_renderer_render (mip == false) or avr_renderer_render_max (mip == true).  A MIP
+// ---- what the two frame functions below share ------------------------------------------------
+// A NEW plan of a rank of several is agreed on before anything of its first frame is queued: a
+// grouped ncclSend / ncclRecv round whose two sides disagree on a block size never ends (the
+// reference would notice in the metadata message of every transfer, Common/Image.cpp:62-90).  Once
+// per plan (and again after a setting changed), never per frame; on disagreement EVERY rank
+// returns the error here (avr_frame_plan_agree).
+void agree_on_plan(avr_renderer* r, const avr_frame_plan* plan) {
+  if (r->n_ranks > 1 && r->plan_check != 0 && plan->agreed_epoch != r->settings_epoch) {
+    r->stage = "plan agreement (control plane)";
+    abi_ok(avr_frame_plan_agree(plan, r->comm, r->compose, r->settings_digest()));
+    plan->agreed_epoch = r->settings_epoch;
+  }
+}
+
+// The caller's cell data is produced on input_stream (null: nothing to wait for): `consumer`, the
+// first stream of the frame that reads it, waits for what is queued there now.
+void wait_for_input(avr_renderer* r, void* input_stream, hipStream_t consumer) {
+  if (input_stream == nullptr) return;
+  hipStream_t producer = (input_stream == AVR_DEFAULT_STREAM)
+                             ? nullptr  // recording on stream 0 IS recording on the null stream
+                             : static_cast<hipStream_t>(input_stream);
+  hip_ok(hipEventRecord(r->input_event, producer), "hipEventRecord");
+  hip_ok(hipStreamWaitEvent(consumer, r->input_event, 0), "hipStreamWaitEvent");
+}
+
+// A rank of several's exchange on stream X: send -> recv, and in the same grouped round the RGB8
+// pieces of the frame before (its deferred gather) travel to the root, which then puts their rows
+// into that frame's output.  gathered_rgb8: the root's buffer for them (unused if none is pending).
+void exchange_with_pending_gather(avr_renderer* r, const avr_frame_plan* plan, const float* send,
+                                  float* recv, uint8_t* gathered_rgb8, hipStream_t stream_x) {
+  avr_renderer::PendingGather& pending = r->pending;
+  avr_gather_op rider{};
+  if (pending.valid) {
+    rider.piece = pending.piece;
+    rider.bytes_per_pixel = 3;
+    rider.root = 0;
+    rider.full = gathered_rgb8;
+    rider.begin = pending.begin.data();
+    rider.end = pending.end.data();
+    // (the assemble pass reads the root's own piece where its fold wrote it -- unless the
+    // reference's contiguous pieces cut through rows)
+    rider.skip_own = pending.own_in_place ? 1 : 0;
+  }
+  abi_ok(avr_exchange_peers_gather(r->compose, plan, r->comm, send, recv,
+                                   pending.valid ? &rider : nullptr));
+  if (pending.valid && r->rank == 0) {
+    if (avr::launch_assemble_rows(pending.pieces, gathered_rgb8,
+                                  static_cast<int64_t>(pending.pieces.width) * 3, /*flip=*/1,
+                                  pending.out, stream_x,
+                                  pending.own_in_place ? pending.piece : nullptr,
+                                  pending.own_piece) != AVR_OK) {
+      throw std::runtime_error(avr_last_error());
+    }
+  }
+  pending.valid = false;
+}
+
+// One frame of avr_renderer_render (kVolume) or avr_renderer_render_max (kMaxIntensity).  A MIP
 // frame takes the same path with the MIP march and the max fold; what rests on opacity -- frame
 // chunks, occlusion culling, visibility speculation -- is left out (and speculation is not fed).
+// (A projection is render_projection_frame's.)
 int render_frame(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
                  const int32_t* group_order, void* input_stream, uint64_t* samples_out,
-                 int want_image, uint8_t* rgb8_out, float* image_out, bool mip, int16_t* index_out) {
+                 int want_image, uint8_t* rgb8_out, float* image_out, avr::FrameKind kind,
+                 int16_t* index_out) {
   return guarded_renderer(r, [&]() -> int {
     require(render != nullptr && camera != nullptr, "null argument");
+    require(kind != avr::FrameKind::kProjection, "a column projection is not a pipelined frame");
+    const bool mip = kind == avr::FrameKind::kMaxIntensity;
     const int root = validate(*render);
     if (mip) {
       require(root == 1, "a maximum-intensity frame has no antialiasing (render->antialiasing must be 1)");
@@ -1091,16 +1152,7 @@ int render_frame(avr_renderer* r, const avr_render_params* render, const avr_cam
     const avr_frame_plan_info& info = plan->info;
     const int64_t piece_pixels = info.piece_end - info.piece_begin;
     const bool many = r->n_ranks > 1;
-    // ---- a NEW plan of a rank of several is agreed on before anything of its first frame is
-    // queued: a grouped ncclSend / ncclRecv round whose two sides disagree on a block size never
-    // ends (the reference would notice in the metadata message of every transfer,
-    // Common/Image.cpp:62-90).  Once per plan (and again after a setting changed), never per frame;
-    // on disagreement EVERY rank returns the error here (avr_frame_plan_agree).
-    if (many && r->plan_check != 0 && plan->agreed_epoch != r->settings_epoch) {
-      r->stage = "plan agreement (control plane)";
-      abi_ok(avr_frame_plan_agree(plan, r->comm, r->compose, r->settings_digest()));
-      plan->agreed_epoch = r->settings_epoch;
-    }
+    agree_on_plan(r, plan);
 
     // Round 1's march (8 workgroups per CU) gained from being capped at 5 beside the classify
     // pass; the present one is admitted 6 per CU by its register budget and runs best uncapped
@@ -1571,13 +1623,7 @@ int render_frame(avr_renderer* r, const avr_render_params* render, const avr_cam
     lap(0);
     r->stage = "classify";
     // ---- stream C: classify pass of this frame into classified volume `slot` -------------------
-    if (input_stream != nullptr) {  // the caller's cell data is produced on that stream
-      hipStream_t producer = (input_stream == AVR_DEFAULT_STREAM)
-                                 ? nullptr  // recording on stream 0 IS recording on the null stream
-                                 : static_cast<hipStream_t>(input_stream);
-      hip_ok(hipEventRecord(r->input_event, producer), "hipEventRecord");
-      hip_ok(hipStreamWaitEvent(stream_c, r->input_event, 0), "hipStreamWaitEvent");
-    }
+    wait_for_input(r, input_stream, stream_c);
     // (With host-side back-pressure the re-use of the frame's classified volume and send buffer
     // was settled before anything was queued; otherwise the streams wait -- unless the event has
     // already happened.)
@@ -1757,32 +1803,7 @@ int render_frame(avr_renderer* r, const avr_render_params* render, const avr_cam
     const float* received = send;
     const float* own = nullptr;
     if (many) {
-      // ... and in the same grouped round the RGB8 pieces of the frame before travel to the root
-      avr_renderer::PendingGather& pending = r->pending;
-      avr_gather_op rider{};
-      if (pending.valid) {
-        rider.piece = pending.piece;
-        rider.bytes_per_pixel = 3;
-        rider.root = 0;
-        rider.full = gathered_rgb8;
-        rider.begin = pending.begin.data();
-        rider.end = pending.end.data();
-        // (the assemble pass reads the root's own piece where its fold wrote it -- unless the
-        // reference's contiguous pieces cut through rows)
-        rider.skip_own = pending.own_in_place ? 1 : 0;
-      }
-      abi_ok(avr_exchange_peers_gather(r->compose, plan, r->comm, send, recv,
-                                       pending.valid ? &rider : nullptr));
-      if (pending.valid && is_root) {
-        if (avr::launch_assemble_rows(pending.pieces, gathered_rgb8,
-                                      static_cast<int64_t>(pending.pieces.width) * 3, /*flip=*/1,
-                                      pending.out, stream_x,
-                                      pending.own_in_place ? pending.piece : nullptr,
-                                      pending.own_piece) != AVR_OK) {
-          throw std::runtime_error(avr_last_error());
-        }
-      }
-      pending.valid = false;
+      exchange_with_pending_gather(r, plan, send, recv, gathered_rgb8, stream_x);
       received = recv;
       own = send;
     }
@@ -1900,11 +1921,7 @@ int render_projection_frame(avr_renderer* r, const avr_render_params* render, co
     const avr_frame_plan_info& info = plan->info;
     const int64_t piece_pixels = info.piece_end - info.piece_begin;
     const bool many = r->n_ranks > 1;
-    if (many && r->plan_check != 0 && plan->agreed_epoch != r->settings_epoch) {
-      r->stage = "plan agreement (control plane)";
-      abi_ok(avr_frame_plan_agree(plan, r->comm, r->compose, r->settings_digest()));
-      plan->agreed_epoch = r->settings_epoch;
-    }
+    agree_on_plan(r, plan);
     const bool banded = info.piece_layout == AVR_PIECES_ROW_BANDS;
     const int64_t n_pixels = info.n_pixels;
     auto bytes_of = [](int64_t count, int each) {
@@ -1939,13 +1956,7 @@ int render_projection_frame(avr_renderer* r, const avr_render_params* render, co
     if (r->projection_done == nullptr) r->projection_done = make_event(false);
 
     r->stage = "projection march";
-    if (input_stream != nullptr) {  // the caller's cell data is produced on that stream
-      hipStream_t producer = (input_stream == AVR_DEFAULT_STREAM)
-                                 ? nullptr
-                                 : static_cast<hipStream_t>(input_stream);
-      hip_ok(hipEventRecord(r->input_event, producer), "hipEventRecord");
-      hip_ok(hipStreamWaitEvent(stream_m, r->input_event, 0), "hipStreamWaitEvent");
-    }
+    wait_for_input(r, input_stream, stream_m);
     // the send buffer of the projection before must have been exchanged and folded
     hip_ok(hipStreamWaitEvent(stream_m, r->projection_done, 0), "hipStreamWaitEvent");
     abi_ok(avr_march_plan_projection(r->march, r->scene, plan, 0, send, samples_out));
@@ -1956,29 +1967,7 @@ int render_projection_frame(avr_renderer* r, const avr_render_params* render, co
     const float* received = send;
     const float* own = nullptr;
     if (many) {
-      avr_renderer::PendingGather& pending = r->pending;
-      avr_gather_op rider{};
-      if (pending.valid) {
-        rider.piece = pending.piece;
-        rider.bytes_per_pixel = 3;
-        rider.root = 0;
-        rider.full = gathered_rgb8;
-        rider.begin = pending.begin.data();
-        rider.end = pending.end.data();
-        rider.skip_own = pending.own_in_place ? 1 : 0;
-      }
-      abi_ok(avr_exchange_peers_gather(r->compose, plan, r->comm, send, recv,
-                                       pending.valid ? &rider : nullptr));
-      if (pending.valid && is_root) {
-        if (avr::launch_assemble_rows(pending.pieces, gathered_rgb8,
-                                      static_cast<int64_t>(pending.pieces.width) * 3, /*flip=*/1,
-                                      pending.out, stream_x,
-                                      pending.own_in_place ? pending.piece : nullptr,
-                                      pending.own_piece) != AVR_OK) {
-          throw std::runtime_error(avr_last_error());
-        }
-      }
-      pending.valid = false;
+      exchange_with_pending_gather(r, plan, send, recv, gathered_rgb8, stream_x);
       received = recv;
       own = send;
     }
@@ -2013,14 +2002,14 @@ int avr_renderer_render(avr_renderer* r, const avr_render_params* render, const 
                         const int32_t* group_order, void* input_stream, uint64_t* samples_out,
                         int want_image, uint8_t* rgb8_out, float* image_out) {
   return render_frame(r, render, camera, group_order, input_stream, samples_out, want_image, rgb8_out,
-                      image_out, false, nullptr);
+                      image_out, avr::FrameKind::kVolume, nullptr);
 }
 
 int avr_renderer_render_max(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
                             const int32_t* group_order, void* input_stream, uint64_t* samples_out,
                             uint8_t* rgb8_out, int16_t* index_out) {
   return render_frame(r, render, camera, group_order, input_stream, samples_out, 0, rgb8_out, nullptr,
-                      true, index_out);
+                      avr::FrameKind::kMaxIntensity, index_out);
 }
 
 int avr_renderer_render_projection(avr_renderer* r, const avr_render_params* render,
