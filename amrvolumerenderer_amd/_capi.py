@@ -217,6 +217,9 @@ SIGNATURES = {
                                                   C.POINTER(C.c_double), _fp, _fp]),
     "avr_scene_histogram": (C.c_int, [_vp, _vp, C.POINTER(ScalarTransform), C.c_float, C.c_float,
                                        C.c_int, _vp]),
+    "avr_scene_joint_histogram": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_double), C.c_int,
+                                            C.POINTER(C.c_double), C.c_int, C.c_int, _vp, _vp,
+                                            _vp]),
     "avr_slice_scene": (C.c_int, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.c_int, C.c_int, _ip, _vp, _vp, _vp]),
     "avr_slice_outline": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),

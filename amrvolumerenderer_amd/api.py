@@ -1007,3 +1007,361 @@ def slice(plotfile: str, width: int = 512, height: int = 512, variable: Optional
             raise RuntimeError(f"could not write '{output}'")
     nan = torch.full_like(shown, float("nan"))
     return torch.where(hit, shown, nan).cpu().numpy()
+
+
+# ---- phase plots and profiles ("Phase plot and profile") ----------------------------
+
+JOINT_HISTOGRAM_MAX_BINS = 1024        # per axis
+JOINT_HISTOGRAM_MAX_CELLS = 1 << 20    # nx * ny
+JOINT_HISTOGRAM_MAX_LEVELS = 16
+HISTOGRAM_WEIGHTS = ("cell_volume", "cells")
+
+
+def _bin_count(n, what: str) -> int:
+    import operator
+    try:
+        n = operator.index(n)
+    except TypeError:
+        n = 0
+    if isinstance(n, bool) or not (1 <= n <= JOINT_HISTOGRAM_MAX_BINS):
+        raise ValueError(f"{what} must be an integer in [1, {JOINT_HISTOGRAM_MAX_BINS}]")
+    return n
+
+
+def _bin_range(values, log: bool, what: str) -> Tuple[float, float]:
+    values = tuple(values)
+    if len(values) != 2:
+        raise ValueError(f"{what} must hold two values (lo, hi)")
+    lo, hi = (float(v) for v in values)
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"{what} must be finite")
+    if not (lo < hi):
+        raise ValueError(f"{what} must satisfy lo < hi")
+    if log and not (lo > 0.0):
+        raise ValueError(f"{what} must be positive for logarithmic bins")
+    return lo, hi
+
+
+def _checked_edges(edges, what: str):
+    import numpy as np
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or not (2 <= e.size <= JOINT_HISTOGRAM_MAX_BINS + 1):
+        raise ValueError(f"{what} must hold between 2 and {JOINT_HISTOGRAM_MAX_BINS + 1} values")
+    if not np.isfinite(e).all():
+        raise ValueError(f"{what} must be finite")
+    if not (e[1:] > e[:-1]).all():
+        raise ValueError(f"{what} must be strictly increasing")
+    return e
+
+
+def bin_edges(lo: float, hi: float, n: int, log: bool = False):
+    """The n + 1 float64 edges of n bins over [lo, hi], numpy float64 arithmetic throughout:
+    linear e[i] = lo + (hi - lo) * (i / n); log (lo > 0) e[i] = 10 ** (log10(lo) + (log10(hi) -
+    log10(lo)) * (i / n)); e[0] = lo and e[n] = hi exactly in both.  ValueError if the result is
+    not finite and strictly increasing (a range too narrow for n bins)."""
+    import numpy as np
+    n = _bin_count(n, "the bin count")
+    lo, hi = _bin_range((lo, hi), log, "the bin range")
+    fraction = np.arange(n + 1, dtype=np.float64) / np.float64(n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        if log:
+            a, b = np.log10(np.float64(lo)), np.log10(np.float64(hi))
+            e = np.float64(10.0) ** (a + (b - a) * fraction)
+        else:
+            e = np.float64(lo) + (np.float64(hi) - np.float64(lo)) * fraction
+    e[0], e[n] = lo, hi
+    return _checked_edges(e, "the bin edges")
+
+
+def _histogram_axis(bins, rng, log: bool, edges, name: str):
+    """(n, range or None, edges or None) of one axis; explicit edges override the rest."""
+    if edges is not None:
+        e = _checked_edges(edges, f"{name}_edges")
+        return e.size - 1, None, e
+    n = _bin_count(bins, f"{name} bins")
+    return n, (None if rng is None else _bin_range(rng, bool(log), f"{name}_range")), None
+
+
+def validate_phase_arguments(z="cell_volume", bins=(128, 128), x_range=None, y_range=None,
+                             x_log: bool = False, y_log: bool = False, x_edges=None, y_edges=None,
+                             log_scale: bool = False, value_range=None):
+    """The argument checks of phase(), before any GPU work and before the plotfile is opened.
+    Returns ((nx, x_range, x_edges), (ny, y_range, y_edges), value_range): a range / edges entry
+    is None where it was not given, edges are float64 arrays."""
+    if not isinstance(z, str) or not z:
+        raise ValueError(f"z must be one of {', '.join(HISTOGRAM_WEIGHTS)} or a variable name, "
+                         f"not {z!r}")
+    try:
+        pair = tuple(bins)
+    except TypeError:
+        raise ValueError("bins must hold two values (nx, ny)") from None
+    if len(pair) != 2:
+        raise ValueError("bins must hold two values (nx, ny)")
+    x = _histogram_axis(pair[0], x_range, x_log, x_edges, "x")
+    y = _histogram_axis(pair[1], y_range, y_log, y_edges, "y")
+    if x[0] * y[0] > JOINT_HISTOGRAM_MAX_CELLS:
+        raise ValueError(f"the histogram must not have more than {JOINT_HISTOGRAM_MAX_CELLS} bins")
+    rng = validate_projection_arguments(1, 1, "column", log_scale, value_range)
+    return x, y, rng
+
+
+def validate_profile_arguments(weight="cell_volume", bins=128, x_range=None, x_log: bool = False,
+                               x_edges=None):
+    """The argument checks of profile(), before any GPU work and before the plotfile is opened.
+    Returns (nx, x_range or None, x_edges or None)."""
+    if weight not in HISTOGRAM_WEIGHTS:
+        raise ValueError(f"weight must be one of {', '.join(HISTOGRAM_WEIGHTS)}, not {weight!r}")
+    return _histogram_axis(bins, x_range, x_log, x_edges, "x")
+
+
+def joint_histogram_values(cells_by_level, sums_by_level, cell_volumes, z: str = "cell_volume"):
+    """values of a joint histogram from its per-level arrays, float64, level ascending from +0.0:
+    "cell_volume": sum_l vol[l] * f64(cells[l]); "cells": sum_l f64(cells[l]); anything else (a
+    summed variable): sum_l vol[l] * sums[l], the volume integral of that variable per bin."""
+    import numpy as np
+    cells = np.asarray(cells_by_level)
+    values = np.zeros(cells.shape[1:], dtype=np.float64)
+    if z not in HISTOGRAM_WEIGHTS and sums_by_level is None:
+        raise ValueError("a summed variable needs sums_by_level")
+    for level in range(cells.shape[0]):
+        vol = np.float64(cell_volumes[level])
+        if z == "cell_volume":
+            values = values + vol * cells[level].astype(np.float64)
+        elif z == "cells":
+            values = values + cells[level].astype(np.float64)
+        else:
+            values = values + vol * np.asarray(sums_by_level[level], dtype=np.float64)
+    return values
+
+
+def profile_mean(cells_by_level, sums_by_level, cell_volumes, weight: str = "cell_volume"):
+    """(mean, weight_sum) of a profile from its per-level arrays: mean = sum_l w[l] sums[l] /
+    sum_l w[l] f64(cells[l]) with w = vol ("cell_volume") or 1 ("cells"), level ascending from
+    +0.0; NaN where the denominator (weight_sum) is 0."""
+    import numpy as np
+    if weight not in HISTOGRAM_WEIGHTS:
+        raise ValueError(f"weight must be one of {', '.join(HISTOGRAM_WEIGHTS)}, not {weight!r}")
+    cells = np.asarray(cells_by_level)
+    numerator = np.zeros(cells.shape[1:], dtype=np.float64)
+    weight_sum = np.zeros(cells.shape[1:], dtype=np.float64)
+    for level in range(cells.shape[0]):
+        w = np.float64(cell_volumes[level]) if weight == "cell_volume" else np.float64(1.0)
+        numerator = numerator + w * np.asarray(sums_by_level[level], dtype=np.float64)
+        weight_sum = weight_sum + w * cells[level].astype(np.float64)
+    filled = weight_sum != 0.0
+    mean = np.full(weight_sum.shape, np.nan, dtype=np.float64)
+    mean[filled] = numerator[filled] / weight_sum[filled]
+    return mean, weight_sum
+
+
+def combine_joint_histograms(parts):
+    """The joint histograms of several owners -> that of them all: the plain sum, in the order
+    given.  parts: (cells, sums or None, totals) triples as Scene.joint_histogram returns them
+    (torch tensors or numpy arrays of one shape); sums is None if it is None in every part."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_joint_histograms needs at least one part")
+    cells, sums, totals = parts[0]
+    cells, totals = cells.copy() if hasattr(cells, "copy") else cells.clone(), \
+        totals.copy() if hasattr(totals, "copy") else totals.clone()
+    if sums is not None:
+        sums = sums.copy() if hasattr(sums, "copy") else sums.clone()
+    for c, s, t in parts[1:]:
+        if tuple(c.shape) != tuple(cells.shape) or (s is None) != (sums is None):
+            raise ValueError("parts must agree in shape and in having sums")
+        cells += c
+        totals += t
+        if s is not None:
+            sums += s
+    return cells, sums, totals
+
+
+def level_cell_volumes(cell_sizes) -> List[float]:
+    """vol[l] = dx * dy * dz (float64, multiplied in this order) of each level's cell_size."""
+    return [float(c[0]) * float(c[1]) * float(c[2]) for c in cell_sizes]
+
+
+def phase_scene(ctx, scene_x: SceneGeometry, scene_y: Optional[SceneGeometry], x_edges, y_edges,
+                cell_volumes: Sequence[float], z: str = "cell_volume",
+                scene_z: Optional[SceneGeometry] = None, rank: int = 0, n_ranks: int = 1,
+                process_group=None) -> dict:
+    """Joint histogram of loaded scenes ("Phase plot and profile"): scene_x, scene_y
+    and scene_z are the scenes load_plotfile_geometry returns for different variables of one
+    plotfile with the same levels, rank and world size.  scene_y None: one y bin (a profile's
+    input; y_edges is then None).  z "cell_volume" | "cells", or anything else with scene_z: that
+    field is summed per bin.  cell_volumes[l] = the physical cell volume of level l, one entry per
+    level up to the finest loaded one.  Every rank bins its local_boxes; cells, sums and totals are
+    all-reduced with SUM (through the host if the group's backend is not NCCL).  Returns, on every
+    rank, a dict of numpy arrays: values float64 [ny, nx] (joint_histogram_values), cells int64
+    [ny, nx] and sums float64 [ny, nx] (None without scene_z) summed over levels, cells_by_level
+    / sums_by_level [L, ny, nx], outside and nonfinite (int), x_edges, y_edges."""
+    import numpy as np
+    import torch
+    if (z not in HISTOGRAM_WEIGHTS) != (scene_z is not None):
+        raise ValueError("scene_z is given exactly when z names a variable")
+    ex = _checked_edges(x_edges, "x_edges")
+    ey = None
+    if scene_y is not None:
+        ey = _checked_edges(y_edges, "y_edges")
+    elif y_edges is not None:
+        raise ValueError("y_edges must be given with scene_y")
+    if (ex.size - 1) * (1 if ey is None else ey.size - 1) > JOINT_HISTOGRAM_MAX_CELLS:
+        raise ValueError(f"the histogram must not have more than {JOINT_HISTOGRAM_MAX_CELLS} bins")
+    volumes = [float(v) for v in cell_volumes]
+    n_levels = len(volumes)
+    finest = max((int(b.level) for b in scene_x.all_boxes), default=0)
+    if not (finest < n_levels <= JOINT_HISTOGRAM_MAX_LEVELS):
+        raise ValueError("cell_volumes must hold one entry per level up to the finest loaded one "
+                         f"(at most {JOINT_HISTOGRAM_MAX_LEVELS})")
+    fields = [ctx.create_scene(s.local_boxes, s.scalar_transform) if s is not None else None
+              for s in (scene_x, scene_y, scene_z)]
+    try:
+        cells, sums, totals = fields[0].joint_histogram(ex, fields[1], ey, fields[2], n_levels)
+        if n_ranks > 1:
+            import torch.distributed as dist
+            stage = dist.get_backend(process_group) != "nccl"
+            ctx.synchronize()
+            reduced = []
+            for t in (cells, sums, totals):
+                if t is None:
+                    reduced.append(None)
+                    continue
+                t = t.cpu() if stage else t
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+                reduced.append(t)
+            cells, sums, totals = reduced
+        ctx.synchronize()
+        cells_by_level = cells.cpu().numpy()
+        sums_by_level = None if sums is None else sums.cpu().numpy()
+        totals = totals.cpu().numpy()
+    finally:
+        for field in fields:
+            if field is not None:
+                field.close()
+    total_sums = None
+    if sums_by_level is not None:
+        total_sums = np.zeros(sums_by_level.shape[1:], dtype=np.float64)
+        for level in range(n_levels):
+            total_sums = total_sums + sums_by_level[level]
+    return {"values": joint_histogram_values(cells_by_level, sums_by_level, volumes, z),
+            "cells": cells_by_level.sum(axis=0), "sums": total_sums,
+            "cells_by_level": cells_by_level, "sums_by_level": sums_by_level,
+            "outside": int(totals[0]), "nonfinite": int(totals[1]),
+            "x_edges": ex, "y_edges": ey}
+
+
+def _field_range(ctx, scene: SceneGeometry, log: bool, what: str, n_ranks: int, process_group):
+    """(lo, hi) of a field's finite cells over all ranks ((min positive, max) with log), hi moved
+    off lo if they are equal."""
+    import torch
+    local = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
+    lo, hi, lo_pos, finite = local.scalar_stats()
+    local.close()
+    if n_ranks > 1:
+        import torch.distributed as dist
+        device = ctx.device if dist.get_backend(process_group) == "nccl" else "cpu"
+        mins = torch.tensor([lo, lo_pos], dtype=torch.float64, device=device)
+        maxs = torch.tensor([hi], dtype=torch.float64, device=device)
+        dist.all_reduce(mins, op=dist.ReduceOp.MIN, group=process_group)
+        dist.all_reduce(maxs, op=dist.ReduceOp.MAX, group=process_group)
+        lo, lo_pos, hi = mins[0].item(), mins[1].item(), maxs[0].item()
+    if log:
+        lo = lo_pos
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise RuntimeError(f"{what} has no {'positive ' if log else ''}finite cells to take a bin "
+                           "range from")
+    if lo == hi:
+        hi = lo * 10.0 if log else lo + 1.0
+    return lo, hi
+
+
+def _load_fields(plotfile: str, variables, min_level: int, max_level: int):
+    """(ctx, rank, world, group, scenes, cell volumes): one scene per variable name."""
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    from . import plotfile as pf
+    header = pf.PlotFileData(plotfile)
+    for name in variables:
+        if name and name not in header.var_names:
+            raise RuntimeError(f"Variable '{name}' not found in plotfile '{plotfile}'.")
+    ctx, rank, world, group = _runtime_scope()
+    scenes = [pf.load_plotfile_geometry(ctx, plotfile, name or "", min_level, max_level, False,
+                                        True, rank, world, group) for name in variables]
+    finest = max(int(b.level) for b in scenes[0].all_boxes)
+    return ctx, rank, world, group, scenes, level_cell_volumes(header.cell_size[:finest + 1])
+
+
+def _axis_edges(ctx, scene, axis, log: bool, what: str, world: int, group):
+    n, rng, edges = axis
+    if edges is not None:
+        return edges
+    if rng is None:
+        rng = _field_range(ctx, scene, bool(log), what, world, group)
+    return bin_edges(rng[0], rng[1], n, bool(log))
+
+
+def phase(plotfile: str, x_variable: str, y_variable: str, z: str = "cell_volume",
+          bins: Sequence[int] = (128, 128), x_range: Optional[Sequence[float]] = None,
+          y_range: Optional[Sequence[float]] = None, x_log: bool = False, y_log: bool = False,
+          x_edges=None, y_edges=None, min_level: int = 0, max_level: int = -1,
+          log_scale: bool = False, value_range: Optional[Sequence[float]] = None,
+          color_map: Optional[Sequence[Sequence[float]]] = None, output: Optional[str] = None):
+    """Phase plot of a plotfile (yt's PhasePlot; DESIGN.md 7, "Phase plot and profile"), on cuda:0:
+    the joint histogram of the raw cells of x_variable and y_variable over bins = (nx, ny) bins,
+    every uncovered cell of the loaded levels counted once.  z "cell_volume": the physical volume
+    per bin, "cells": the number of cells, a variable's name: the volume integral of that variable
+    over the bin's cells (mass, for a density).  A range defaults to the field's (min, max) over
+    its finite cells, (min positive, max) with x_log / y_log, which make the bins logarithmic; equal
+    ends become (lo, lo + 1) ((lo, 10 lo) with log).  x_edges / y_edges (strictly increasing) override
+    range, bins and log.  A value v lies in bin i when e[i] <= v < e[i + 1], the last bin closed at
+    the top.  Returns, on every rank, phase_scene's dict: values [ny, nx] float64 (row = y bin),
+    cells, sums, cells_by_level, sums_by_level, outside, nonfinite, x_edges, y_edges.  With output
+    (.png, else PPM) rank 0 also writes the picture, coloured as project() colours a column: x to
+    the right, the lowest y bin at the bottom, values over value_range (or their min and max),
+    log10 of them with log_scale; bins without cells are black."""
+    x, y, rng = validate_phase_arguments(z, bins, x_range, y_range, x_log, y_log, x_edges, y_edges,
+                                         log_scale, value_range)
+    table = projection_rgb_table(color_map)
+    summed = z not in HISTOGRAM_WEIGHTS
+    variables = [x_variable, y_variable] + ([z] if summed else [])
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, variables, min_level,
+                                                            max_level)
+    ex = _axis_edges(ctx, scenes[0], x, x_log, "x_variable", world, group)
+    ey = _axis_edges(ctx, scenes[1], y, y_log, "y_variable", world, group)
+    result = phase_scene(ctx, scenes[0], scenes[1], ex, ey, volumes, z,
+                         scenes[2] if summed else None, rank, world, group)
+    if output is not None and rank == 0:
+        import torch
+        column = torch.from_numpy(result["values"]).to(ctx.device)
+        length = torch.from_numpy((result["cells"] > 0).astype("float64")).to(ctx.device)
+        rgb8, _ = ctx.projection_colorize(
+            column, length, torch.from_numpy(table).to(ctx.device), "column", log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
+        if not writer(rgb8.cpu().numpy(), output):
+            raise RuntimeError(f"could not write '{output}'")
+    return result
+
+
+def profile(plotfile: str, x_variable: str, y_variable: str, weight: str = "cell_volume",
+            bins: int = 128, x_range: Optional[Sequence[float]] = None, x_log: bool = False,
+            x_edges=None, min_level: int = 0, max_level: int = -1) -> dict:
+    """Profile of a plotfile (yt's ProfilePlot; DESIGN.md 7, "Phase plot and profile"), on cuda:0:
+    the mean of y_variable over the cells whose x_variable lies in each of `bins` bins, weighted by
+    the cells' physical volume (weight "cell_volume") or equally ("cells").  Range, log and edges
+    as in phase().  Returns, on every rank, a dict: x_edges, mean float64 [nx] (NaN for a bin
+    without cells), weight_sum float64 [nx] (the mean's denominator), cells int64 [nx], outside,
+    nonfinite."""
+    x = validate_profile_arguments(weight, bins, x_range, x_log, x_edges)
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [x_variable, y_variable],
+                                                            min_level, max_level)
+    ex = _axis_edges(ctx, scenes[0], x, x_log, "x_variable", world, group)
+    result = phase_scene(ctx, scenes[0], None, ex, None, volumes, y_variable or "field",
+                         scenes[1], rank, world, group)
+    mean, weight_sum = profile_mean(result["cells_by_level"][:, 0, :],
+                                    result["sums_by_level"][:, 0, :], volumes, weight)
+    return {"x_edges": result["x_edges"], "mean": mean, "weight_sum": weight_sum,
+            "cells": result["cells"][0], "outside": result["outside"],
+            "nonfinite": result["nonfinite"]}

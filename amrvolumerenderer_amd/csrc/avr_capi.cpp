@@ -1820,6 +1820,114 @@ int avr_scene_histogram(avr_context* ctx, const avr_scene* scene,
   });
 }
 
+// n + 1 finite, strictly increasing edges; returns n / (e[n] - e[0]), or 0 if that is not finite
+static double joint_histogram_axis(const double* edges, int n, const char* axis) {
+  const std::string name(axis);
+  require(edges != nullptr, (name + "_edges is null").c_str());
+  require(n >= 1 && n <= avr::kJointHistogramMaxBins,
+          (name + " bin count must lie in [1, 1024]").c_str());
+  for (int i = 0; i <= n; ++i) {
+    require(std::isfinite(edges[i]), (name + "_edges must be finite").c_str());
+    require(i == 0 || edges[i - 1] < edges[i], (name + "_edges must be strictly increasing").c_str());
+  }
+  const double scale = static_cast<double>(n) / (edges[n] - edges[0]);
+  return std::isfinite(scale) ? scale : 0.0;
+}
+
+int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const avr_scene* scene_y,
+                              const avr_scene* scene_s, const double* x_edges, int nx,
+                              const double* y_edges, int ny, int n_levels, uint64_t* cells_dev,
+                              double* sums_dev, uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene_x != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
+    require(scene_s == nullptr || sums_dev != nullptr, "a summed field needs sums_dev");
+    avr::JointHistogramArgs args{};
+    args.x_scale = joint_histogram_axis(x_edges, nx, "x");
+    if (scene_y != nullptr) {
+      args.y_scale = joint_histogram_axis(y_edges, ny, "y");
+    } else {
+      require(ny == 1, "without scene_y there is one y bin");
+    }
+    require(static_cast<int64_t>(nx) * ny <= avr::kJointHistogramMaxCells,
+            "the histogram has more than 2^20 bins");
+    require(n_levels >= 1 && n_levels <= avr::kJointHistogramMaxLevels,
+            "n_levels must lie in [1, 16]");
+    const avr_scene* fields[3] = {scene_x, scene_y != nullptr ? scene_y : scene_x,
+                                  scene_s != nullptr ? scene_s : scene_x};
+    const size_t n_boxes = scene_x->boxes.size();
+    for (const avr_scene* field : fields) {
+      require(field->ctx == ctx && field->boxes.size() == n_boxes,
+              "the scenes must belong to the context and hold the same number of boxes");
+    }
+    std::vector<avr::JointBoxDev> boxes(n_boxes);
+    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& first = scene_x->boxes[b];
+      avr::JointBoxDev& dev = boxes[b];
+      std::memset(&dev, 0, sizeof(dev));
+      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
+      dev.level = first.level;
+      dev.paired = 1;
+      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
+      for (int f = 0; f < 3; ++f) {
+        const avr_box& in = fields[f]->boxes[b];
+        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
+                    in.dims[2] == first.dims[2] && in.level == first.level,
+                "the scenes' boxes differ in dims or level");
+        if (empty) continue;
+        require(in.cells != nullptr, "box has no cell data");
+        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
+                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
+                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
+        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
+                "box spans more than 2^28 cells (or has negative strides)");
+        dev.cells[f] = in.cells;
+        dev.jstride[f] = static_cast<int32_t>(in.jstride);
+        dev.kstride[f] = static_cast<int32_t>(in.kstride);
+        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
+            (in.kstride & 1) != 0) {
+          dev.paired = 0;
+        }
+      }
+      uint64_t tiles = 0;
+      if (!empty) {
+        dev.nx = first.dims[0];
+        dev.ny = first.dims[1];
+        dev.nz = first.dims[2];
+        tiles = avr::joint_histogram_tiles(dev.nx, dev.ny, dev.nz);
+      }
+      const uint64_t total = tile_begin[b] + tiles;
+      require(total < (uint64_t{1} << 31), "scene has too many cells");
+      tile_begin[b + 1] = static_cast<uint32_t>(total);
+    }
+    if (tile_begin.back() == 0) return AVR_OK;
+    const size_t n_x = static_cast<size_t>(nx) + 1;
+    const size_t n_y = scene_y != nullptr ? static_cast<size_t>(ny) + 1 : 0;
+    ctx->staging.begin(boxes.size() * sizeof(avr::JointBoxDev) +
+                           tile_begin.size() * sizeof(uint32_t) + (n_x + n_y) * sizeof(double), 4);
+    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
+    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    args.x_edges = ctx->staging.add(x_edges, n_x);
+    args.y_edges = n_y != 0 ? ctx->staging.add(y_edges, n_y) : nullptr;
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_tiles = tile_begin.back();
+    args.nx = nx;
+    args.ny = ny;
+    args.x_lo = x_edges[0];
+    args.x_hi = x_edges[nx];
+    if (scene_y != nullptr) {
+      args.y_lo = y_edges[0];
+      args.y_hi = y_edges[ny];
+    }
+    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
+    args.sums = scene_s != nullptr ? sums_dev : nullptr;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_joint_histogram(args, scene_y != nullptr, scene_s != nullptr, ctx->stream);
+  });
+}
+
 int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origin[3],
                     const double du[3], const double dv[3], int width, int height,
                     const int32_t* global_index, double* value, int8_t* level, int32_t* box) {

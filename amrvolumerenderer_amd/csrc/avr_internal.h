@@ -417,6 +417,45 @@ int launch_slice(const SlicePlaneDev& plane, int width, int height, const SliceB
 int launch_slice_outline(const int32_t* box_index, int width, int height, int red, int green,
                          int blue, uint8_t* rgb8, void* stream);
 
+// Joint histogram (avr_joint_histogram.hip).  A box as that kernel reads it: the cells of the x,
+// y and s fields (an absent field repeats x) with each field's own strides, the dims and the level
+// they share.
+struct alignas(16) JointBoxDev {
+  const double* cells[3];
+  int32_t jstride[3];     // element strides (Array4); every field spans < 2^28 elements
+  int32_t kstride[3];
+  int32_t nx, ny, nz;
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t paired;         // every field: cells 16-byte aligned, both strides even
+  int32_t pad_[3];
+};
+static_assert(sizeof(JointBoxDev) == 80, "JointBoxDev: 16-byte multiple for scalar loads");
+constexpr int kJointHistogramMaxBins = 1024;          // per axis
+constexpr int kJointHistogramMaxCells = 1 << 20;      // nx * ny
+constexpr int kJointHistogramMaxLevels = 16;
+// Dynamic LDS of one workgroup (edges + counts + sums) up to which the bins are kept in LDS; above
+// it every cell goes to the global arrays.  64 KiB: what a kernel gets without asking for more,
+// and at least two workgroups (8 waves) per CU at the limit.
+constexpr size_t kJointHistogramLdsBudget = 64 * 1024;
+struct JointHistogramArgs {
+  const JointBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  const double* x_edges;        // nx + 1, device
+  const double* y_edges;        // ny + 1, device (null without y)
+  int32_t nx, ny;
+  double x_lo, x_hi, x_scale;   // e[0], e[n] and nx / (e[n] - e[0]) (0 if that is not finite)
+  double y_lo, y_hi, y_scale;
+  unsigned long long* cells;    // [n_levels][ny][nx], added to
+  double* sums;                 // the same shape (null without s), added to
+  unsigned long long* totals;   // [2]: outside, nonfinite, added to
+};
+// tiles of one box (4 x 4 rows of 128 cells); UINT32_MAX if they do not fit 31 bits
+uint32_t joint_histogram_tiles(int nx, int ny, int nz);
+size_t joint_histogram_lds_bytes(int nx, int ny, bool has_y, bool has_s, bool lds);
+int launch_joint_histogram(const JointHistogramArgs& args, bool has_y, bool has_s, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

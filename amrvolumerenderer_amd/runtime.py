@@ -557,6 +557,64 @@ class Scene:
         self.ctx.publish()
         return counts
 
+    def joint_histogram(self, x_edges, y: Optional["Scene"] = None, y_edges=None,
+                        s: Optional["Scene"] = None, n_levels: Optional[int] = None,
+                        cells: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
+                        totals: Optional[torch.Tensor] = None):
+        """avr_scene_joint_histogram with this scene as the x field: adds this rank's cells to
+        (cells int64 [L, ny, nx], sums float64 [L, ny, nx] or None without s, totals int64 [2] =
+        (outside, nonfinite)) on the device.  y and s are scenes of the same context with the same
+        box list (other fields of the same cells); without y there is one y bin.  x_edges /
+        y_edges: float64, strictly increasing, n + 1 each.  L = n_levels, by default 1 + the
+        largest level among this scene's boxes."""
+        ctx = self.ctx
+        ex = np.ascontiguousarray(x_edges, dtype=np.float64)
+        if ex.ndim != 1 or ex.size < 2:
+            raise ValueError("x_edges must hold at least two values")
+        nx, ny, ey = ex.size - 1, 1, None
+        if y is not None:
+            if y_edges is None:
+                raise ValueError("y_edges must be given with y")
+            ey = np.ascontiguousarray(y_edges, dtype=np.float64)
+            if ey.ndim != 1 or ey.size < 2:
+                raise ValueError("y_edges must hold at least two values")
+            ny = ey.size - 1
+        elif y_edges is not None:
+            raise ValueError("y_edges must be given with y")
+        if n_levels is None:
+            n_levels = 1 + max((int(b.level) for b in self.boxes), default=0)
+        n_levels = int(n_levels)
+        if n_levels < 1:
+            raise ValueError("n_levels must be positive")
+        shape = (n_levels, ny, nx)
+        if cells is None:
+            cells = torch.zeros(shape, dtype=torch.int64, device=ctx.device)
+        if totals is None:
+            totals = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+        if s is not None and sums is None:
+            sums = torch.zeros(shape, dtype=torch.float64, device=ctx.device)
+        ctx._check_tensor(cells, torch.int64, "cells")
+        ctx._check_tensor(totals, torch.int64, "totals")
+        if tuple(cells.shape) != shape or totals.numel() != 2:
+            raise ValueError("cells must be [n_levels, ny, nx] and totals [2]")
+        if s is not None:
+            ctx._check_tensor(sums, torch.float64, "sums")
+            if tuple(sums.shape) != shape:
+                raise ValueError("sums must be [n_levels, ny, nx]")
+        else:
+            sums = None
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_joint_histogram(
+            ctx._handle, self._handle, y._handle if y is not None else None,
+            s._handle if s is not None else None, as_doubles(ex), int(nx),
+            as_doubles(ey) if ey is not None else None, int(ny), n_levels,
+            C.c_void_p(cells.data_ptr()),
+            C.c_void_p(sums.data_ptr()) if sums is not None else None,
+            C.c_void_p(totals.data_ptr())))
+        ctx.publish()
+        return cells, sums, totals
+
     def slice(self, origin: Sequence[float], du: Sequence[float], dv: Sequence[float], width: int,
               height: int, global_index: Optional[Sequence[int]] = None,
               value: Optional[torch.Tensor] = None, level: Optional[torch.Tensor] = None,

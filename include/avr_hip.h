@@ -1055,6 +1055,32 @@ int avr_scene_histogram(avr_context *ctx, const avr_scene *scene,
                         const avr_scalar_transform *transform, float range_min, float range_max,
                         int bin_count, uint64_t *counts_dev);
 
+/* ---- joint histogram of two raw fields ("Phase plot and profile") --------------- */
+
+/* Joint histogram of the raw f64 cells of scene_x and scene_y, per AMR level, with the cells of
+ * scene_s summed per bin.  scene_y may be NULL (one y bin: ny must be 1, y_edges is not read) and
+ * so may scene_s (sums_dev is not written).  The scenes belong to ctx and hold the same box list:
+ * the same number of boxes and, per position, the same dims and level -- the cells at one
+ * (box, i, j, k) are one cell's values of the fields; each scene keeps its own strides.
+ * x_edges[nx + 1] and y_edges[ny + 1] (host) are finite and strictly increasing, 1 <= nx, ny <=
+ * 1024, nx * ny <= 2^20.  A value v lies in bin i when e[i] <= v < e[i + 1]; the last bin is
+ * closed at the top (v == e[n] lies in bin n - 1).  The bin is decided by f64 comparisons against
+ * the edges as given, nothing else.  Per cell, in this order:
+ *   vx, vy or vs not finite            totals[1] += 1   (nonfinite)
+ *   vx or vy outside [e[0], e[n]]      totals[0] += 1   (outside)
+ *   otherwise, l = the box's level     cells[(l * ny + by) * nx + bx] += 1,
+ *                                      sums [(l * ny + by) * nx + bx] += vs
+ * with no transform and no normalisation.  0 <= level < n_levels <= 16 for every box.
+ * cells_dev (uint64 [n_levels][ny][nx]), sums_dev (f64, the same shape) and totals_dev (uint64
+ * [2]) are device arrays that are ADDED to (the caller zeroes them and sums over ranks).  Counts
+ * are exact; a sum is made of f64 additions in no fixed order.  Everything is checked on the host
+ * before any device work: AVR_ERR_INVALID_ARGUMENT leaves the outputs untouched.  Asynchronous
+ * on the context's stream. */
+int avr_scene_joint_histogram(avr_context *ctx, const avr_scene *scene_x, const avr_scene *scene_y,
+                              const avr_scene *scene_s, const double *x_edges, int nx,
+                              const double *y_edges, int ny, int n_levels, uint64_t *cells_dev,
+                              double *sums_dev, uint64_t *totals_dev);
+
 /* ---- slice images of the raw field ("Slice") ------------------------------------ */
 
 /* A plane through the scene: pixel (x, y), row 0 at the bottom, samples the point
