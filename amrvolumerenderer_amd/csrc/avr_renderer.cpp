@@ -39,6 +39,7 @@
 #include "avr_corun.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
+#include "avr_speculation.h"
 
 namespace {
 
@@ -67,6 +68,7 @@ struct DeviceBuffer {
   ~DeviceBuffer() {
     if (ptr != nullptr) (void)hipFree(ptr);
   }
+  void abandon() { ptr = nullptr; }  // leaked on purpose: hipFree waits for the device
   template <typename Drain>
   void* reserve(size_t bytes, Drain&& drain) {
     if (bytes > capacity) {
@@ -113,6 +115,10 @@ struct FrameEvents {
              march_end = nullptr;
 };
 
+size_t bytes_of(int64_t count, int each) {
+  return static_cast<size_t>(std::max<int64_t>(count, 1)) * static_cast<size_t>(each);
+}
+
 }  // namespace
 
 struct avr_renderer {
@@ -126,6 +132,7 @@ struct avr_renderer {
   avr_visibility_graph* visibility = nullptr;
   std::vector<avr_box> all_boxes;
   std::vector<int32_t> owner;
+  double local_cell_bytes = 0.0;  // the f64 cells of this rank's boxes
   avr_scalar_transform transform{};
   double bounds_min[3]{}, bounds_max[3]{};
   double tight_min[3]{}, tight_max[3]{};
@@ -191,16 +198,28 @@ struct avr_renderer {
     spec.forget();  // (what was sampled under the old settings)
   }
 
-  DeviceBuffer send[AVR_CLASSIFIED_SLOTS], recv, piece, piece_rgb8, full_rgb8, full_image, assembled_image, small_image;
+  // Every device buffer of the renderer, in one array: whatever must reach all of them (the
+  // destructor of a failed renderer) is one loop, and a buffer added here cannot be forgotten.
+  // The kinds with a slot are by frame % 3, like the classified volumes.
+  enum Buffer {
+    kSend, kRecv = kSend + AVR_CLASSIFIED_SLOTS, kPiece, kPieceRgb8, kFullRgb8, kFullImage,
+    kAssembledImage, kSmallImage,
+    kPieceRgb8Odd,                          // (see PendingGather below)
+    kPieceIndex, kFullIndex,                // maximum-intensity frames of ranks of several
+    // column-projection frames: their own send buffer, f64 pieces and (row bands) gathered images
+    kProjectionSend, kProjectionPiece, kProjectionFull,
+    kVisibleFlags,                          // occlusion culling
+    kSpecVisited = kVisibleFlags + AVR_CLASSIFIED_SLOTS,  // speculation: what that frame's march sampled
+    kSpecMissed = kSpecVisited + AVR_CLASSIFIED_SLOTS,    // ... needed and found unclassified, then a counter
+    kBufferCount = kSpecMissed + AVR_CLASSIFIED_SLOTS
+  };
+  DeviceBuffer buffers[kBufferCount];
+  DeviceBuffer& buffer(Buffer kind, int slot = 0) { return buffers[kind + slot]; }
   // Ranks of several: the RGB8 pieces of frame f travel to the root inside the grouped round of
   // frame f + 1 (avr_exchange_peers_gather) -- ONE RCCL launch per frame on the compositing stream
   // instead of two.  The fold of frame f + 1 must not overwrite what that round still sends: two
   // piece buffers alternate.  avr_renderer_synchronize sends what is still pending (collective).
-  DeviceBuffer piece_rgb8_odd;
-  DeviceBuffer piece_index, full_index;  // maximum-intensity frames of ranks of several
-  // column-projection frames: their own send buffer, f64 pieces and (row bands) gathered images,
-  // and the event that frees the send buffer again
-  DeviceBuffer projection_send, projection_piece, projection_full;
+  // (column-projection frames: the event that frees their send buffer again)
   hipEvent_t projection_done = nullptr;
   int deferred_gather = -1;  // avr_renderer_set_deferred_gather: -1 = ranks of several
   struct PendingGather {
@@ -238,73 +257,40 @@ struct avr_renderer {
   // ms), while a march in four launches costs 0.66 ms instead of 0.38 (every launch walks every
   // tile and evaluates the boxes behind it), on one stream with nothing beside it.
   int occlusion_chunks = -1;
-  DeviceBuffer visible_flags[AVR_CLASSIFIED_SLOTS];
   hipEvent_t chunk_event[AVR_CLASSIFIED_SLOTS][AVR_MAX_FRAME_CHUNKS] = {};
   int last_chunks = 1;  // what the last frame did (avr_renderer_corun_state / diagnostics)
 
   // ---- visibility speculation (avr_classify_plan_positions / avr_march_plan_speculative; one rank) --
-  // With the reference's default boxTransparency = 0 the march's skip test keeps config-4's rays out
-  // of 118 of its 176 boxes, yet every frame reads their f64 cells.  The driver remembers, per BOX
-  // of the rank, the last frame whose march sampled it (observations: a march that records the boxes
-  // it samples, the flags copied to the host and read a few frames later -- by box, so they outlive
-  // the plan: a moving camera keeps what it learnt).  While at most spec_worth_it of the boxes were
-  // sampled in the last kSpecMemory frames, a frame classifies only those (a launch of exactly
-  // their tiles), its march checks every box it is about to march against the same set, and two
-  // gated launches behind it repair the frame when the set was wrong (the cells changed, the camera
-  // turned) -- results never change.  Config-4 opaque: classify pass 0.55 -> 0.18 ms, pipelined
-  // frame 0.64 -> 0.43 ms.  A translucent frame (every box sampled) is observed once and then left
-  // alone but for one observing frame in kSpecProbeEvery.
+  // What it is and every decision of it: avr_speculation.h.  Here: what those decisions need of HIP.
   int speculation = -1;  // avr_renderer_set_visibility_speculation: -1 = auto (one rank), 0 = never
-  struct Speculating {
-    enum State { kObserving, kDeciding, kActive, kRejected, kBackoff };
-    State state = kObserving;
-    std::vector<int64_t> last_sampled;     // per local box: the last frame that sampled it (-1 never)
-    std::vector<int32_t> positions;        // this frame's set, as positions in its layer order
-    std::vector<uint8_t> flags;            // ... and as flags by position (staged with the march)
-    int64_t frame = 0;                     // frames this struct has seen
-    int64_t asleep_until = 0;              // kRejected / kBackoff: the next observing frame
-    int next_backoff = 64;                 // after the next run of repairs
-    int recent_repairs = 0, recent_frames = 0;
-    int64_t last_repair = -1000;           // the frame that learnt of the latest repair
-    const void* previous_plan = nullptr;   // of the frame before (only compared: a standing camera)
-    // observations in flight: the march's flags by POSITION, that frame's layer order, an event
+  Speculation spec;
+  struct SpeculationMemory {
+    // an observation in flight (Speculation::observations, slot by slot): the march's flags by
+    // POSITION, an event
     struct Observation {
       uint8_t* host = nullptr;             // pinned, device-visible
       uint8_t* host_dev = nullptr;
       size_t capacity = 0;
       hipEvent_t copied = nullptr;
-      std::vector<int32_t> order;          // position -> local box of that frame's plan
-      int64_t frame = 0;
-      bool pending = false;
-      bool stale = false;                  // taken under settings that are gone: ignored when it arrives
     };
-    static constexpr int kObservations = 4;
-    Observation observations[kObservations];
-    DeviceBuffer visited[AVR_CLASSIFIED_SLOTS];  // by frame % 3: what that frame's march sampled
-    DeviceBuffer missed[AVR_CLASSIFIED_SLOTS];   // ... needed and found unclassified, then a counter
+    Observation observations[Speculation::kObservations];
     uint32_t* host_miss = nullptr;         // pinned, device-visible: set by a march that missed
     uint32_t* host_miss_dev = nullptr;
-    long active_frames = 0, repaired_frames = 0;
-    float sampled_fraction = -1.0f;        // of the rank's boxes, in the last kSpecMemory frames
-    void forget() {                        // (another transfer function, other boxes)
-      last_sampled.clear();
-      state = kObserving;
-      sampled_fraction = -1.0f;
-      for (Observation& o : observations) o.stale = o.pending;  // (their flags are of the old settings)
+    void abandon() {                       // (hipHostFree waits for the device as well)
+      for (Observation& o : observations) {
+        o.host = nullptr;
+        o.copied = nullptr;
+      }
+      host_miss = nullptr;
     }
-    ~Speculating() {
+    ~SpeculationMemory() {
       for (Observation& o : observations) {
         if (o.host != nullptr) (void)hipHostFree(o.host);
         if (o.copied != nullptr) (void)hipEventDestroy(o.copied);
       }
       if (host_miss != nullptr) (void)hipHostFree(host_miss);
     }
-  } spec;
-  static constexpr int kSpecMemory = 24;       // frames a box stays in the set after it was last sampled
-  static constexpr int kSpecProbeEvery = 512;  // kRejected: one observing frame in so many
-  static constexpr int kSpecObserveEvery = 8;  // kActive without repairs: one observed frame in so many
-  float spec_worth_it = 0.85f;  // (avr_renderer_debug_set_speculation_threshold: tests)
-  double spec_min_saving_ms = 0.15;  // (... sets it to 0 with any threshold: small test scenes)
+  } spec_memory;
   bool marched_pending[AVR_CLASSIFIED_SLOTS] = {}, composed_pending[AVR_CLASSIFIED_SLOTS] = {};
   unsigned frame = 0;
 
@@ -342,17 +328,8 @@ struct avr_renderer {
       // it, or freeing device memory (which waits for the device), would hang the caller too.
       // Everything on the device is leaked; the process is expected to report the error and exit.
       forget_plans();
-      for (DeviceBuffer* buffer : {&send[0], &send[1], &send[2], &recv, &piece, &piece_rgb8, &piece_rgb8_odd,
-                                   &full_rgb8, &full_image, &assembled_image, &small_image,
-                                   &visible_flags[0], &visible_flags[1], &visible_flags[2]}) {
-        buffer->ptr = nullptr;  // (hipFree waits for the device)
-      }
-      for (int i = 0; i < AVR_CLASSIFIED_SLOTS; ++i) spec.visited[i].ptr = spec.missed[i].ptr = nullptr;
-      for (Speculating::Observation& o : spec.observations) {
-        o.host = nullptr;  // (hipHostFree waits as well)
-        o.copied = nullptr;
-      }
-      spec.host_miss = nullptr;
+      for (DeviceBuffer& each : buffers) each.abandon();
+      spec_memory.abandon();
       return;
     }
     for (avr_context* ctx : {classify, march, compose, pair_b}) {
@@ -437,6 +414,15 @@ struct avr_renderer {
     paired_previous = nullptr;  // nothing is in flight: nothing to order the next classify pass after
     probe_tail = probe_head;    // (their frames ran into the drain: not the steady state)
     tuner.drained();
+  }
+
+  // A column projection's wait for everything queued (a buffer of its own grows).  Unlike
+  // drain_all() the co-run tuner is not told and the pipeline is not marked idle: nothing of the
+  // pipelined frames' timing is that frame's.
+  void drain_quietly() {
+    for (avr_context* ctx : {classify, march, compose, pair_b}) {
+      if (ctx != nullptr) avr::wait_stream_deadline(stream_of(ctx), "a stream before a column projection");
+    }
   }
 };
 
@@ -651,6 +637,7 @@ int avr_renderer_create(int device_id, int rank, int n_ranks, avr_comm* comm,
       if (owner[b] == rank) {
         require(all_boxes[b].cells != nullptr, "a box of this rank has no cell data");
         local.push_back(all_boxes[b]);
+        r->local_cell_bytes += 8.0 * all_boxes[b].dims[0] * all_boxes[b].dims[1] * all_boxes[b].dims[2];
       }
     }
     abi_ok(avr_scene_create(r->march, local.data(), static_cast<int>(local.size()), transform,
@@ -796,7 +783,7 @@ int avr_renderer_set_visibility_speculation(avr_renderer* r, int mode) {
   return guarded_renderer(r, [&]() -> int {
     require(mode >= -1 && mode <= 1, "mode must be -1, 0 or 1");
     r->drain_all();
-    if ((r->speculation != 0) != (mode != 0) && r->spec.state == avr_renderer::Speculating::kActive) {
+    if ((r->speculation != 0) != (mode != 0) && r->spec.state == Speculation::kActive) {
       r->tuner.restart();  // (the classify pass changes its length)
     }
     r->speculation = mode;
@@ -809,8 +796,8 @@ int avr_renderer_debug_set_speculation_threshold(avr_renderer* r, float sampled_
   return guarded_renderer(r, [&]() -> int {
     require(sampled_fraction >= 0.0f && sampled_fraction <= 1.0f, "the fraction must be in [0, 1]");
     r->drain_all();
-    r->spec_worth_it = sampled_fraction;
-    r->spec_min_saving_ms = 0.0;
+    r->spec.worth_it = sampled_fraction;
+    r->spec.min_saving_ms = 0.0;
     r->spec.forget();
     return AVR_OK;
   });
@@ -819,7 +806,7 @@ int avr_renderer_debug_set_speculation_threshold(avr_renderer* r, float sampled_
 int avr_renderer_speculation_state(const avr_renderer* r, int* state, int64_t* speculative_frames,
                                    int64_t* repaired_frames, float* sampled_fraction) {
   if (r == nullptr) return AVR_ERR_INVALID_ARGUMENT;
-  const avr_renderer::Speculating& sp = r->spec;
+  const Speculation& sp = r->spec;
   if (state != nullptr) {
     *state = (r->speculation == 0 || r->n_ranks > 1) ? -1 : static_cast<int>(sp.state);
   }
@@ -925,7 +912,7 @@ int avr_renderer_synchronize(avr_renderer* r) {
       uint8_t* gathered = nullptr;
       if (r->rank == 0) {
         const size_t bytes = static_cast<size_t>(pending.pieces.width) * pending.pieces.height * 3 + 1;
-        gathered = static_cast<uint8_t*>(r->full_rgb8.reserve(bytes, [&] { r->drain_all(); }));
+        gathered = static_cast<uint8_t*>(r->buffer(avr_renderer::kFullRgb8).reserve(bytes, [&] { r->drain_all(); }));
       }
       avr_gather_op op{};
       op.piece = pending.piece;
@@ -1080,11 +1067,23 @@ void wait_for_input(avr_renderer* r, void* input_stream, hipStream_t consumer) {
   hip_ok(hipStreamWaitEvent(consumer, r->input_event, 0), "hipStreamWaitEvent");
 }
 
-// A rank of several's exchange on stream X: send -> recv, and in the same grouped round the RGB8
-// pieces of the frame before (its deferred gather) travel to the root, which then puts their rows
-// into that frame's output.  gathered_rgb8: the root's buffer for them (unused if none is pending).
-void exchange_with_pending_gather(avr_renderer* r, const avr_frame_plan* plan, const float* send,
-                                  float* recv, uint8_t* gathered_rgb8, hipStream_t stream_x) {
+// Stream X (stage "exchange") once `marched` has happened on the march's stream; returns what the
+// fold then reads, from the peers and from this rank itself.  A rank of several: send -> recv, and
+// in the same grouped round the RGB8 pieces of the frame before (its deferred gather) travel to
+// the root, which then puts their rows into that frame's output.  gathered_rgb8: the root's buffer
+// for them (unused if none is pending).
+struct Exchanged {
+  const float* received;
+  const float* own;
+};
+Exchanged exchange_after(avr_renderer* r, const avr_frame_plan* plan, hipEvent_t marched, const float* send,
+                         float* recv, uint8_t* gathered_rgb8, hipStream_t stream_x) {
+  r->stage = "exchange";
+  hip_ok(hipStreamWaitEvent(stream_x, marched, 0), "hipStreamWaitEvent");
+  // (the rank's block for itself is not copied into the receive buffer: the fold reads it
+  // where the march stored it -- the send buffer lives until composed_event -- which is one
+  // kernel and one gap less on this stream, the busiest of a rank of eight's frame)
+  if (r->n_ranks == 1) return {send, nullptr};
   avr_renderer::PendingGather& pending = r->pending;
   avr_gather_op rider{};
   if (pending.valid) {
@@ -1110,791 +1109,802 @@ void exchange_with_pending_gather(avr_renderer* r, const avr_frame_plan* plan, c
     }
   }
   pending.valid = false;
+  return {recv, send};
+}
+
+// The plan of the frame (stage "frame plan"): made or found, and agreed on by the ranks.
+const avr_frame_plan* plan_and_agree(avr_renderer* r, const avr_render_params& render,
+                                     const avr_camera& camera, const int32_t* group_order) {
+  // ---- host plan (re-used while camera and parameters repeat; avr_renderer_prepare may have
+  // made it ahead of time on another thread) ---------------------------------------------------
+  r->stage = "frame plan";
+  const avr_frame_plan* plan = plan_for(r, render, camera, group_order, /*use=*/true);
+  agree_on_plan(r, plan);
+  return plan;
+}
+
+// What a pipelined frame puts out and where its pixels become bytes: a function of the call and
+// the renderer's settings alone, the same on every rank.
+struct OutputShape {
+  // 8-bit conversion is per pixel, so without antialiasing it is done on each rank's piece
+  // before the gather (3 bytes per pixel on the wire instead of 20); the wireframe of the tight
+  // bounds is per pixel too, so each rank overlays its own piece
+  bool early_rgb8 = false, overlay_piece = false;
+  bool gather_image = false;  // the same on every rank: it adds a collective
+  bool bytes_only = false;
+  // The gathered buffer is piece-major; with contiguous pieces that IS the image, with row
+  // bands avr_assemble_rows puts the rows back (for the bytes in the same pass that turns the
+  // bottom-up image into the file's top-down rows).
+  bool banded = false;
+  bool defer_gather = false;   // the RGB8 pieces travel with the next frame's round (PendingGather)
+  bool fold_to_image = false;  // (one rank without antialiasing or wireframe: the fold writes the output file's rows itself)
+};
+
+OutputShape output_shape(const avr_render_params& render, const avr_frame_plan_info& info, int n_ranks,
+                         avr::FrameKind kind, int want_image, int deferred_gather) {
+  const bool many = n_ranks > 1;
+  OutputShape shape;
+  shape.early_rgb8 = render.antialiasing == 1;
+  shape.overlay_piece = shape.early_rgb8 && render.draw_bounds;
+  shape.gather_image = want_image != 0;
+  shape.bytes_only = shape.early_rgb8 && !shape.overlay_piece && !shape.gather_image;
+  shape.banded = info.piece_layout == AVR_PIECES_ROW_BANDS;
+  shape.defer_gather = kind != avr::FrameKind::kMaxIntensity && many && deferred_gather != 0 &&
+                       shape.early_rgb8 && !shape.gather_image;
+  shape.fold_to_image = !many && shape.early_rgb8 && !shape.overlay_piece;  // (the one rank is the root)
+  return shape;
+}
+
+struct TimedGuard {  // the frame's four timing events, destroyed unless the frame keeps them
+  FrameEvents events;
+  bool kept = false;
+  ~TimedGuard() {
+    if (kept) return;
+    for (hipEvent_t ev : {events.classify_begin, events.classify_end, events.march_begin,
+                          events.march_end}) {
+      if (ev != nullptr) (void)hipEventDestroy(ev);
+    }
+  }
+};
+
+// One call of render_frame: what its stages (below, in the order they run) share.  On the stack
+// of the call; nothing in it owns memory but the timing-event guard.
+struct Frame {
+  // the call
+  const avr_render_params* render;
+  const avr_camera* camera;
+  void* input_stream;
+  uint64_t* samples_out;
+  int want_image;
+  uint8_t* rgb8_out;
+  float* image_out;
+  int16_t* index_out;
+  avr::FrameKind kind;
+  // check_arguments, plan_frame
+  bool mip = false, is_root = false, many = false;
+  int root = 1, width = 0, height = 0;
+  const avr_frame_plan* plan = nullptr;
+  const avr_frame_plan_info& info() const { return plan->info; }
+  int64_t piece_pixels = 0;
+  OutputShape shape{};
+  int volume = 0, slot = 0;  // classified volume and send buffer of the frame
+  // reserve_buffers
+  int cull = 0;
+  uint8_t* visibility = nullptr;
+  float *send = nullptr, *recv = nullptr, *piece = nullptr;
+  uint8_t* piece_rgb8 = nullptr;
+  int16_t *piece_index = nullptr, *gathered_index = nullptr;
+  uint8_t* gathered_rgb8 = nullptr;
+  float *gathered_image = nullptr, *assembled = nullptr, *small = nullptr;
+  // reserve_speculation, choose_launch_form
+  bool spec_considered = false;
+  size_t spec_bytes = 0, spec_block = 0;
+  uint8_t *spec_visited = nullptr, *spec_missed = nullptr, *spec_dirty = nullptr;
+  uint32_t* spec_count = nullptr;
+  int spec_slot = -1;  // this frame's observation slot (-1: none free)
+  int spec_mode = 0;
+  // back_pressure, place_kernels
+  bool host_side = false, overlap = false, paired = false;
+  int reserve = 0;
+  avr_context *march_ctx = nullptr, *classify_ctx = nullptr;
+  hipStream_t stream_c = nullptr, stream_m = nullptr, stream_x = nullptr;
+  avr_renderer::Probe* probe = nullptr;
+  TimedGuard timed{};
+  // choose_launch_form, queue_classify
+  bool was_idle = false;
+  int n_chunks = 1;
+  void* chunk_events[AVR_MAX_FRAME_CHUNKS] = {};
+  hipEvent_t classified = nullptr;  // this frame's classify pass finished
+  Exchanged exchanged{nullptr, nullptr};
+  std::chrono::steady_clock::time_point mark{};  // host time, section by section (lap)
+};
+
+void lap(avr_renderer* r, Frame& f, int section) {
+  const auto now = std::chrono::steady_clock::now();
+  r->host_seconds[section] += std::chrono::duration<double>(now - f.mark).count();
+  f.mark = now;
+}
+
+void check_arguments(avr_renderer* r, Frame& f) {
+  require(f.render != nullptr && f.camera != nullptr, "null argument");
+  require(f.kind != avr::FrameKind::kProjection, "a column projection is not a pipelined frame");
+  f.mip = f.kind == avr::FrameKind::kMaxIntensity;
+  f.root = validate(*f.render);
+  if (f.mip) {
+    require(f.root == 1, "a maximum-intensity frame has no antialiasing (render->antialiasing must be 1)");
+    require(!f.render->draw_bounds, "a maximum-intensity frame has no wireframe (draw_bounds must be 0)");
+    require(f.want_image == 0, "a maximum-intensity frame has no float image");
+    require(r->rank == 0 || f.index_out == nullptr, "index_out is rank 0's");
+  }
+  hip_ok(hipSetDevice(r->device), "hipSetDevice");
+  f.is_root = r->rank == 0;
+  require(!f.is_root || f.rgb8_out != nullptr, "the root rank needs an rgb8 output buffer");
+  require(!f.is_root || !f.want_image || f.image_out != nullptr,
+          "want_image needs an image output buffer on the root rank");
+  f.width = f.render->width;
+  f.height = f.render->height;
+  f.many = r->n_ranks > 1;
+}
+
+void plan_frame(avr_renderer* r, Frame& f, const int32_t* group_order) {
+  f.plan = plan_and_agree(r, *f.render, *f.camera, group_order);
+  f.piece_pixels = f.info().piece_end - f.info().piece_begin;
+  f.shape = output_shape(*f.render, f.info(), r->n_ranks, f.kind, f.want_image, r->deferred_gather);
+  // Send buffers alternate; the classified volumes rotate through three, so that the classify
+  // stream may run a whole frame ahead of the march: with two, classify(f+1) and march(f) both
+  // had to wait for the later of classify(f) and march(f-1) and started in lockstep, a launch
+  // latency apart from the kernels before them, every frame.
+  f.volume = static_cast<int>(r->frame % static_cast<unsigned>(AVR_CLASSIFIED_SLOTS));
+  f.slot = f.volume;  // send buffers rotate with the classified volumes
+}
+
+// ---- visibility speculation (one rank): this frame's buffers, and the observations that have
+// arrived; what the frame does with them is settled in choose_launch_form, when its layout is known
+void reserve_speculation(avr_renderer* r, Frame& f) {
+  const avr_frame_plan_info& info = f.info();
+  Speculation& sp = r->spec;
+  avr_renderer::SpeculationMemory& memory = r->spec_memory;
+  auto drain = [&] { r->drain_all(); };
+  f.spec_considered = !f.mip && !f.many && r->speculation != 0 && f.cull < 2 && !r->cache_classification &&
+                      info.n_local_runs > 0 && info.n_local_boxes >= 8 && f.samples_out == nullptr &&
+                      f.plan->local_order.size() == static_cast<size_t>(info.n_local_boxes);
+  f.spec_bytes = Speculation::flag_bytes(info.n_local_boxes);
+  if (!f.spec_considered) return;
+  sp.begin_frame(info.n_local_boxes);
+  f.spec_visited = static_cast<uint8_t*>(r->buffer(avr_renderer::kSpecVisited, f.slot).reserve(f.spec_bytes, drain));
+  // (one block per slot: the missed flags, the miss counter, a byte per march workgroup)
+  int64_t workgroups = 0;
+  abi_ok(avr_march_plan_workgroups(f.plan, &workgroups));
+  f.spec_block = f.spec_bytes + 16 + (static_cast<size_t>(workgroups) + 15) / 16 * 16;
+  f.spec_missed = static_cast<uint8_t*>(r->buffer(avr_renderer::kSpecMissed, f.slot).reserve(f.spec_block, drain));
+  f.spec_count = reinterpret_cast<uint32_t*>(f.spec_missed + f.spec_bytes);
+  f.spec_dirty = f.spec_missed + f.spec_bytes + 16;
+  if (memory.host_miss == nullptr) {
+    void* block = nullptr;
+    void* mapped = nullptr;
+    hip_ok(hipHostMalloc(&block, 64, hipHostMallocMapped), "hipHostMalloc(speculation miss flag)");
+    std::memset(block, 0, 64);
+    memory.host_miss = static_cast<uint32_t*>(block);
+    hip_ok(hipHostGetDevicePointer(&mapped, block, 0), "hipHostGetDevicePointer");
+    memory.host_miss_dev = static_cast<uint32_t*>(mapped);
+  }
+  // the observations that have arrived, oldest first: which boxes those frames' rays sampled
+  for (int k = 0; k < Speculation::kObservations; ++k) {
+    const int oldest = sp.oldest_pending();
+    if (oldest < 0) break;
+    if (hipEventQuery(memory.observations[oldest].copied) != hipSuccess) {
+      (void)hipGetLastError();  // hipErrorNotReady is not an error here
+      break;
+    }
+    sp.absorb(oldest, memory.observations[oldest].host);
+  }
+  // a free observation slot for this frame (none: the host is far ahead, this frame is not observed)
+  f.spec_slot = sp.free_slot();
+  if (f.spec_slot < 0) return;
+  avr_renderer::SpeculationMemory::Observation& o = memory.observations[f.spec_slot];
+  if (o.capacity < f.spec_bytes) {
+    if (o.host != nullptr) (void)hipHostFree(o.host);
+    o.host = nullptr;
+    o.capacity = 0;
+    void* block = nullptr;
+    void* mapped = nullptr;
+    hip_ok(hipHostMalloc(&block, f.spec_bytes * 2, hipHostMallocMapped), "hipHostMalloc(speculation flags)");
+    o.host = static_cast<uint8_t*>(block);
+    hip_ok(hipHostGetDevicePointer(&mapped, block, 0), "hipHostGetDevicePointer");
+    o.host_dev = static_cast<uint8_t*>(mapped);
+    o.capacity = f.spec_bytes * 2;
+  }
+  if (o.copied == nullptr) {
+    // (WITH the system fence, unlike the ordering events: the host reads what the copy wrote)
+    hip_ok(hipEventCreateWithFlags(&o.copied, hipEventDisableTiming), "hipEventCreate");
+  }
+}
+
+// ---- everything that can fail for lack of memory happens BEFORE anything is queued and
+// before the frame counter moves (here and in place_kernels): a frame either is not started at
+// all (the renderer stays usable) or has every buffer and event it needs.  (A failure later -- a
+// launch, a collective -- leaves a frame half queued: the caller synchronises and tears the
+// renderer down, on every rank; the peers of a failed rank are otherwise left waiting in the
+// exchange.)
+void reserve_buffers(avr_renderer* r, Frame& f) {
+  r->stage = "frame buffers";
+  const avr_frame_plan_info& info = f.info();
+  const OutputShape& shape = f.shape;
+  const int64_t n_pixels = info.n_pixels;
+  auto drain = [&] { r->drain_all(); };
+  auto reserve = [&](avr_renderer::Buffer kind, int64_t count, int each) {
+    return r->buffer(kind).reserve(bytes_of(count, each), drain);
+  };
+  // ---- occlusion culling (one rank): the frame in depth-ordered chunks on ONE stream, every
+  // chunk's classify launch leaving out the boxes its predecessors' marches found hidden
+  if (!f.mip && !f.many && !r->cache_classification && info.n_local_runs > 0 && info.n_local_boxes >= 8) {
+    f.cull = std::min(std::max(r->occlusion_chunks, 0), info.n_local_boxes);
+  }
+  if (f.cull >= 2) {
+    f.visibility = static_cast<uint8_t*>(r->buffer(avr_renderer::kVisibleFlags, f.slot).reserve(
+        bytes_of(static_cast<int64_t>(f.cull) * info.n_local_boxes, 1), drain));
+  }
+  reserve_speculation(r, f);
+  f.send = static_cast<float*>(r->buffer(avr_renderer::kSend, f.slot).reserve(bytes_of(info.send_floats, 4), drain));
+  f.recv = f.many ? static_cast<float*>(reserve(avr_renderer::kRecv, info.recv_floats, 4)) : nullptr;
+  f.piece = shape.bytes_only ? nullptr : static_cast<float*>(reserve(avr_renderer::kPiece, f.piece_pixels, 20));
+  // (ranks of several: two RGB8 pieces alternate, see PendingGather)
+  const avr_renderer::Buffer rgb8_buffer =
+      (f.many && (r->frame & 1u)) ? avr_renderer::kPieceRgb8Odd : avr_renderer::kPieceRgb8;
+  f.piece_rgb8 = shape.early_rgb8 ? static_cast<uint8_t*>(reserve(rgb8_buffer, f.piece_pixels, 3)) : nullptr;
+  // (MIP, ranks of several: the int16 index piece, gathered to rank 0 in the frame itself --
+  // straight into index_out where the gathered buffer is the image)
+  if (f.mip && f.many) {
+    f.piece_index = static_cast<int16_t*>(reserve(avr_renderer::kPieceIndex, f.piece_pixels, 2));
+    if (f.is_root) {
+      f.gathered_index = (f.index_out != nullptr && !shape.banded)
+                             ? f.index_out
+                             : static_cast<int16_t*>(reserve(avr_renderer::kFullIndex, n_pixels, 2));
+    }
+  }
+  if (!f.is_root) return;
+  if (f.many && (shape.early_rgb8 || r->pending.valid)) {
+    int64_t pixels = shape.early_rgb8 ? n_pixels : 0;
+    if (r->pending.valid) {
+      pixels = std::max<int64_t>(pixels, static_cast<int64_t>(r->pending.pieces.width) *
+                                             r->pending.pieces.height);
+    }
+    f.gathered_rgb8 = static_cast<uint8_t*>(reserve(avr_renderer::kFullRgb8, pixels, 3));
+  }
+  if (f.many && ((shape.early_rgb8 && shape.gather_image && shape.banded) || !shape.early_rgb8)) {
+    f.gathered_image = static_cast<float*>(reserve(avr_renderer::kFullImage, n_pixels, 20));
+  }
+  if (!shape.early_rgb8 && f.many && shape.banded) {
+    f.assembled = static_cast<float*>(reserve(avr_renderer::kAssembledImage, n_pixels, 20));
+  }
+  if (!shape.early_rgb8 && !shape.gather_image) {
+    f.small = static_cast<float*>(
+        reserve(avr_renderer::kSmallImage, static_cast<int64_t>(f.width) * f.height, 20));
+  }
+}
+
+// ---- back-pressure.  The frame re-uses the classified volume and the send buffer of the
+// frame three before it.  Either the two streams wait for that frame's march and exchange /
+// fold (two wait packets between this frame's kernels and their predecessors, and with the
+// descriptor ring's events the host stays a few frames ahead), or -- for the short frames of
+// a rank of several -- the HOST waits here until they are through and nothing is queued: every
+// packet between two marches is microseconds of a rank's 0.17 ms frame (with the descriptor
+// copies of a repeating camera skipped as well, a rank of eight went from 0.187 to 0.164 ms);
+// at most three frames are then in flight.  One rank's 1 ms frames hide those packets and lose
+// 1-2 % to the shorter queue (measured), so there the streams wait.
+// avr_renderer_set_host_backpressure.  (The waits have the deadline of
+// avr_set_frame_timeout_ms: the exchange of the frame three back involves every peer.)
+void back_pressure(avr_renderer* r, Frame& f) {
+  f.host_side = (r->host_backpressure < 0) ? f.many : (r->host_backpressure != 0);
+  if (!f.host_side) return;
+  if (r->marched_pending[f.volume]) {
+    r->stage = "back-pressure: the march of the frame three before";
+    avr::wait_event_deadline(r->marched_event[f.volume], "the march of the frame three before this one");
+  }
+  if (r->composed_pending[f.slot]) {
+    r->stage = "back-pressure: the exchange and fold of the frame three before";
+    avr::wait_event_deadline(r->composed_event[f.slot],
+                             "the exchange / fold of the frame three before this one (compositing "
+                             "stream: a peer's blocks have not arrived)");
+  }
+}
+
+// What the caller lets the co-run tuner choose from.
+void restrict_tuner(avr_renderer* r, const Frame& f) {
+  CoRunTuner& tuner = r->tuner;
+  // overlap_classify: -1 everything, 0 back to back, 1 side by side, 2 paired
+  int first = CoRunTuner::kBackToBack, last = CoRunTuner::kLastPaired;
+  if (r->cache_classification) {  // no classify pass to place
+    first = last = (r->overlap_classify == 0) ? CoRunTuner::kBackToBack : 0;
+  } else if (r->overlap_classify == 0) {
+    last = first;
+  } else if (r->overlap_classify == 2) {
+    first = CoRunTuner::kPairedBase;
+    if (r->share_fixed >= 0) last = first;  // the caller's reserve, kept outside the scale
+  } else {
+    if (r->overlap_classify > 0) {
+      first = 0;
+      last = CoRunTuner::kLastCandidate;
+    }
+    if (r->share_fixed >= 0) {
+      // one side-by-side candidate: the caller's reserve (kept outside the candidate scale)
+      last = (first == CoRunTuner::kBackToBack) ? 0 : first;
+    }
+  }
+  if (f.cull >= 2) first = last = CoRunTuner::kBackToBack;  // (one stream: nothing to place)
+  tuner.restrict_to(first, last, r->n_ranks == 1);
+  // one rank with nothing fixed: the balance of the two kernels is read off their durations
+  tuner.set_balance(r->n_ranks == 1 && r->balance != 0);
+  // ranks of several search together (avr_corun.h): the same candidate in the same frames,
+  // every window's period the maximum over the ranks
+  tuner.set_coordinated(f.many && r->comm != nullptr && r->coordinate != 0);
+}
+
+// The window closed kReportLag frames ago (the back-pressure has seen its last march through);
+// all ranks are at this frame.  A rank whose window was void (its pipeline had drained: a buffer
+// grew) says so, and then everybody times the candidate again.
+void agree_on_window(avr_renderer* r, const Frame& f) {
+  CoRunTuner& tuner = r->tuner;
+  r->stage = "co-run window agreement (control plane)";
+  avr::wait_event_deadline(r->window_end, "the march that closes the co-run window");
+  // (the message also says which frame of which plan the rank is in: ranks that were driven
+  // apart -- same block sizes, another camera -- are found out here at the latest)
+  struct Word {
+    float period_ms;
+    uint32_t frame;
+    uint64_t plan_digest;
+  } mine{-1.0f, r->frame, f.plan->agreed_digest};
+  static_assert(sizeof(Word) == 16, "control word");
+  if (!tuner.window_void) {
+    float elapsed_ms = 0.0f;
+    hip_ok(hipEventElapsedTime(&elapsed_ms, r->window_begin, r->window_end), "hipEventElapsedTime");
+    mine.period_ms = elapsed_ms / static_cast<float>(tuner.window_length);
+  }
+  std::vector<Word> words(static_cast<size_t>(r->n_ranks));
+  abi_ok(avr_comm_control_allgather(r->comm, r->compose, &mine, words.data(), sizeof(Word)));
+  float agreed = 0.0f;
+  bool any_void = false;
+  for (size_t peer = 0; peer < words.size(); ++peer) {
+    const Word& word = words[peer];
+    if (word.frame != mine.frame || word.plan_digest != mine.plan_digest) {
+      throw std::runtime_error("rank " + std::to_string(peer) + " is in frame " +
+                               std::to_string(word.frame) + (word.plan_digest != mine.plan_digest
+                                                                 ? " of another frame plan" : "") +
+                               " while rank " + std::to_string(r->rank) + " is in frame " +
+                               std::to_string(mine.frame) + ": the ranks were not driven alike");
+    }
+    any_void = any_void || !(word.period_ms >= 0.0f);
+    agreed = std::max(agreed, word.period_ms);
+  }
+  if (any_void) {
+    tuner.retime();
+  } else {
+    tuner.report(agreed);
+  }
+}
+
+// One rank: the classify pass of the next frame runs beside the march of this one (HBM-bound
+// beside issue-bound).  A rank's share of an N-rank frame is two SHORT kernels whose time is
+// their slowest workgroups': side by side each stretched the other (N = 8, slowest rank:
+// 77 us + 151 us alone, 0.26 + 0.27 ms overlapped), so there they run back to back on the
+// march stream and only the exchange / fold / gather of the previous frame overlaps them.
+// Which of the two, and how many classify workgroups a CU admits beside the march, is measured
+// on the running pipeline (CoRunTuner) unless the caller fixed it: avr_renderer_set_overlap,
+// avr_renderer_set_classify_share.  (A cached classification leaves nothing to tune.)
+// The last stage that may fail for lack of memory: it ends with the frame counter moving.
+void place_kernels(avr_renderer* r, Frame& f) {
+  CoRunTuner& tuner = r->tuner;
+  restrict_tuner(r, f);
+  if (tuner.tuning() && tuner.report_due()) agree_on_window(r, f);
+  f.overlap = tuner.candidate != CoRunTuner::kBackToBack;
+  f.paired = CoRunTuner::is_paired(tuner.candidate);
+  f.reserve = !f.overlap ? 0
+              : (r->share_fixed >= 0)
+                  ? r->share_fixed
+                  : CoRunTuner::reserve_index(tuner.candidate) * CoRunTuner::kReserveStep;
+  // (One stream per kernel kind.  Letting the odd frames take a second march or classify stream
+  // -- the frames are independent, so march(f+1) need not queue behind march(f) and its wait /
+  // record / copy packets could be worked off early -- was measured in round 3 and is worse by
+  // half: with a FOURTH concurrently active queue everything stalls, a 5 us descriptor copy
+  // takes 40-50 us, the frame of a rank of eight goes from 0.187 to 0.26-0.33 ms and the one-rank
+  // frame from 0.98 to 1.25-1.42 ms.  profiles/r3_experiments/.)
+  // Paired layout (avr_corun.h): this frame's classify pass and march back to back on ONE
+  // stream, the even frames on stream M, the odd ones on stream B -- with stream X three active
+  // queues, the number this GPU runs side by side without penalty.
+  f.march_ctx = r->march;
+  if (f.paired && (r->frame & 1u)) {
+    if (r->pair_b == nullptr) abi_ok(avr_context_create_with_priority(r->device, 1, &r->pair_b));
+    f.march_ctx = r->pair_b;
+  }
+  f.classify_ctx = f.paired ? f.march_ctx : f.overlap ? r->classify : r->march;
+  // Round 1's march (8 workgroups per CU) gained from being capped at 5 beside the classify
+  // pass; the present one is admitted 6 per CU by its register budget and runs best uncapped
+  // (config-4 frame: uncapped 1.06-1.07 ms, cap 5 1.09-1.11 ms).
+  abi_ok(avr_context_set_march_occupancy(f.march_ctx, (r->march_cap < 0) ? 0 : r->march_cap));
+  f.stream_c = r->stream_of(f.classify_ctx);
+  f.stream_m = r->stream_of(f.march_ctx);
+  f.stream_x = r->stream_of(r->compose);
+  for (avr_context* ctx : {r->classify, r->march, r->compose, r->pair_b}) {
+    if (ctx != nullptr) avr::context_set_lean_descriptors(ctx, f.host_side);
+  }
+  if (r->history.size() < r->history_capacity) {
+    r->history.push_back(static_cast<int16_t>(tuner.candidate));
+  }
+  // kBalance: this frame's kernels are timed through a slot of the probe ring (if one is free)
+  if (tuner.balancing() && f.overlap && !f.paired && !r->pipeline_idle &&
+      r->probe_head - r->probe_tail < avr_renderer::kProbes) {
+    f.probe = &r->probes[r->probe_head % avr_renderer::kProbes];
+    for (hipEvent_t* ev : {&f.probe->events.classify_begin, &f.probe->events.classify_end,
+                           &f.probe->events.march_begin, &f.probe->events.march_end}) {
+      if (*ev == nullptr) *ev = make_event(true);
+    }
+    f.probe->candidate = tuner.candidate;
+  }
+  if (r->timing) {
+    FrameEvents& timed = f.timed.events;
+    timed.classify_begin = make_event(true);
+    timed.classify_end = make_event(true);
+    timed.march_begin = make_event(true);
+    timed.march_end = make_event(true);
+    r->timed.reserve(r->timed.size() + 1);
+  }
+  ++r->frame;
+}
+
+// ---- one launch per kernel, or depth-ordered chunks (an idle pipeline: see frame_chunks); what
+// speculation does with the frame; how the classify pass shares the CUs and stores its bricklets
+void choose_launch_form(avr_renderer* r, Frame& f) {
+  const avr_frame_plan_info& info = f.info();
+  // Chunks need the two kernels on two streams (side by side); a cached classification has no
+  // classify pass to cut.
+  f.was_idle = r->pipeline_idle;
+  if (!f.mip && f.overlap && !f.paired && !r->cache_classification && info.n_local_runs > 0) {
+    f.n_chunks = std::min(std::max(r->frame_chunks, 1), std::max(info.n_local_boxes, 1));
+  }
+  r->last_chunks = f.n_chunks;
+  // ---- visibility speculation: what this frame does (0 nothing, 1 a plain frame whose march
+  // records the boxes it samples, 2 classifies only the set, checks, repairs -- and records)
+  if (f.spec_considered && f.n_chunks == 1) {  // (any layout: one stream or two, the protocol is the same)
+    volatile uint32_t* host_miss = r->spec_memory.host_miss;
+    if (*host_miss != 0) {  // a march of an earlier frame missed (its repair redid that frame)
+      *host_miss = 0;
+      r->spec.note_repair();
+    }
+    const Speculation::Decision decision = r->spec.decide(f.plan->local_order.data(), info.n_local_boxes,
+                                                          r->local_cell_bytes, f.spec_slot >= 0);
+    f.spec_mode = decision.mode;
+    if (decision.restart_corun) {
+      // (the classify pass changes its length: the co-run balance is found again -- and the frames
+      // still in flight, timed under the old length, must not be read as its first steps: they sent
+      // the bisection the wrong way, 26 KiB held instead of 43, 0.45 ms instead of 0.42)
+      r->tuner.restart();
+      r->probe_tail = r->probe_head;
+    }
+  }
+  for (int k = 0; k < f.n_chunks && f.n_chunks > 1; ++k) {
+    hipEvent_t& event = r->chunk_event[f.volume][k];
+    if (event == nullptr) event = make_event(false);
+    f.chunk_events[k] = event;
+  }
+  // (the first frame after a drain classifies alone -- its first chunk, if it is cut: no march
+  // to leave room for)
+  abi_ok(avr_context_set_classify_lds_reserve(
+      f.classify_ctx, (f.overlap && (!f.was_idle || f.n_chunks > 1)) ? f.reserve : 0));
+  // Side by side the march that reads this frame's bricklets starts a frame later: they are
+  // streamed to memory.  Back to back and paired it follows at once: they are stored plainly
+  // (a rank of eight 0.143 against 0.149 ms).
+  {
+    static const char* forced = std::getenv("AVR_CLASSIFY_STREAM");  // A/B only
+    // (a chunk's bricklets are marched right away, and so are those of a frame that found the
+    // pipeline empty: stored plainly, like back to back)
+    const bool stream = forced != nullptr ? std::atoi(forced) != 0
+                                          : (f.overlap && !f.paired && f.n_chunks == 1 && !f.was_idle);
+    avr::context_set_classify_stream_stores(f.classify_ctx, stream);
+  }
+  r->last_overlap = f.overlap;
+  r->last_paired = f.paired;
+  r->last_reserve = f.reserve;
+  r->pipeline_idle = false;
+}
+
+// ---- stream C: classify pass of this frame into classified volume `slot` -------------------
+void queue_classify(avr_renderer* r, Frame& f) {
+  r->stage = "classify";
+  const FrameEvents& timed = f.timed.events;
+  wait_for_input(r, f.input_stream, f.stream_c);
+  // (With host-side back-pressure the re-use of the frame's classified volume and send buffer
+  // was settled before anything was queued; otherwise the streams wait -- unless the event has
+  // already happened.)
+  auto wait_unless_done = [&](hipStream_t stream, hipEvent_t event) {
+    if (hipEventQuery(event) == hipSuccess) return;
+    (void)hipGetLastError();  // hipErrorNotReady is not an error here
+    hip_ok(hipStreamWaitEvent(stream, event, 0), "hipStreamWaitEvent");
+  };
+  if (!f.host_side) {
+    if (r->marched_pending[f.volume]) wait_unless_done(f.stream_c, r->marched_event[f.volume]);
+    if (r->composed_pending[f.slot]) wait_unless_done(f.stream_m, r->composed_event[f.slot]);
+  }
+  if (f.paired && r->paired_previous != nullptr) {  // one classify pass at a time
+    wait_unless_done(f.stream_c, r->paired_previous);
+  }
+  if (r->timing) hip_ok(hipEventRecord(timed.classify_begin, f.stream_c), "hipEventRecord");
+  if (f.probe != nullptr) hip_ok(hipEventRecord(f.probe->events.classify_begin, f.stream_c), "hipEventRecord");
+  if (f.cull >= 2) {
+    // (classified chunk by chunk between the march launches, in queue_march)
+  } else if (f.n_chunks > 1) {
+    abi_ok(avr_classify_plan_chunked(f.classify_ctx, r->scene, f.plan, f.volume, f.n_chunks, f.chunk_events,
+                                     f.was_idle ? 1 : 0));
+  } else if (f.spec_mode == 2) {
+    // only the boxes of the held set: a launch of exactly their tiles
+    abi_ok(avr_classify_plan_positions(f.classify_ctx, r->scene, f.plan, f.volume, r->spec.positions.data(),
+                                       static_cast<int>(r->spec.positions.size())));
+  } else {
+    abi_ok(avr_classify_plan(f.classify_ctx, r->scene, f.plan, f.volume));
+  }
+  if (f.probe != nullptr) hip_ok(hipEventRecord(f.probe->events.classify_end, f.stream_c), "hipEventRecord");
+  f.classified = r->timing ? timed.classify_end : r->classified_event[f.volume];
+  if (f.overlap || r->timing) hip_ok(hipEventRecord(f.classified, f.stream_c), "hipEventRecord");
+  // (what the NEXT frame waits on must outlive this frame's timing events, which
+  // avr_renderer_set_timing destroys: always the volume's own ordering event)
+  if (f.paired && r->timing) {
+    hip_ok(hipEventRecord(r->classified_event[f.volume], f.stream_c), "hipEventRecord");
+  }
+  r->paired_previous = f.paired ? r->classified_event[f.volume] : nullptr;
+}
+
+// ---- stream M: march into send buffer `slot` ------------------------------------------------
+void queue_march(avr_renderer* r, Frame& f) {
+  r->stage = "march";
+  Speculation& sp = r->spec;
+  const FrameEvents& timed = f.timed.events;
+  const avr_frame_plan* plan = f.plan;
+  // (three batches of descriptors per speculating frame on the march's context: the whole ring)
+  avr::context_set_descriptor_lead(f.march_ctx, f.spec_mode == 2 ? 9 : 4);
+  const bool spec_observed = sp.observed(f.spec_mode, f.spec_slot >= 0, plan);
+  if (!f.mip) sp.previous_plan = plan;
+  if (spec_observed) {  // (cleared while the classify pass still runs)
+    hip_ok(hipMemsetAsync(f.spec_visited, 0, f.spec_bytes, f.stream_m), "hipMemsetAsync(speculation)");
+  }
+  if (f.spec_mode == 2) {
+    hip_ok(hipMemsetAsync(f.spec_missed, 0, f.spec_block, f.stream_m), "hipMemsetAsync(speculation)");
+  }
+  if (f.overlap && !f.paired && f.n_chunks == 1) {
+    // (paired: the march follows its classify pass on the same stream; chunked: every march
+    // launch waits for its own chunk's event)
+    hip_ok(hipStreamWaitEvent(f.stream_m, f.classified, 0), "hipStreamWaitEvent");
+  }
+  if (r->timing) hip_ok(hipEventRecord(timed.march_begin, f.stream_m), "hipEventRecord");
+  if (f.probe != nullptr) hip_ok(hipEventRecord(f.probe->events.march_begin, f.stream_m), "hipEventRecord");
+  if (f.mip) {
+    abi_ok(avr_march_plan_max(f.march_ctx, r->scene, plan, f.volume, f.send, f.samples_out));
+  } else if (f.cull >= 2) {
+    abi_ok(avr_render_plan_culled(f.march_ctx, r->scene, plan, f.volume, f.send, f.samples_out, f.cull,
+                                  f.visibility));
+    r->last_chunks = f.cull;
+  } else if (f.n_chunks > 1) {
+    abi_ok(avr_march_plan_chunked(f.march_ctx, r->scene, plan, f.volume, f.send, f.samples_out, f.n_chunks,
+                                  f.chunk_events));
+  } else if (f.spec_mode != 0) {
+    avr_speculation first{};
+    first.visited = spec_observed ? f.spec_visited : nullptr;
+    if (f.spec_mode == 2) {
+      first.classified_host = sp.flags.data();
+      first.missed = f.spec_missed;
+      first.miss_count = f.spec_count;
+      first.host_miss_flag = r->spec_memory.host_miss_dev;
+      first.dirty_workgroups = f.spec_dirty;
+    }
+    abi_ok(avr_march_plan_speculative(f.march_ctx, r->scene, plan, f.volume, f.send, &first));
+    if (f.spec_mode == 2) {
+      // the repair, queued unconditionally: both launches do nothing unless the march missed
+      abi_ok(avr_classify_plan_flagged(f.march_ctx, r->scene, plan, f.volume, f.spec_missed, f.spec_count));
+      avr_speculation again{};
+      again.visited = first.visited;
+      again.gate = f.spec_count;
+      again.dirty_workgroups = f.spec_dirty;  // (only the workgroups that met an unclassified box)
+      abi_ok(avr_march_plan_speculative(f.march_ctx, r->scene, plan, f.volume, f.send, &again));
+      ++sp.active_frames;
+    }
+    if (spec_observed) {
+      // the boxes this frame's rays sampled go to the host (a copy kernel into pinned memory) and
+      // are read a few frames on, by box
+      const avr_renderer::SpeculationMemory::Observation& observation = r->spec_memory.observations[f.spec_slot];
+      abi_ok(avr::launch_upload(f.spec_visited, observation.host_dev, f.spec_bytes, f.stream_m));
+      hip_ok(hipEventRecord(observation.copied, f.stream_m), "hipEventRecord");
+      sp.observe(f.spec_slot, plan->local_order);
+    }
+  } else {
+    abi_ok(avr_march_plan(f.march_ctx, r->scene, plan, f.volume, f.send, f.samples_out));
+  }
+  if (f.probe != nullptr) {
+    hip_ok(hipEventRecord(f.probe->events.march_end, f.stream_m), "hipEventRecord");
+    ++r->probe_head;
+  }
+}
+
+// What the co-run tuner learns behind the march, and the events that end the march's part of the
+// frame (the tuner's window events lie between the march and them on stream M).
+void service_tuner(avr_renderer* r, Frame& f) {
+  CoRunTuner& tuner = r->tuner;
+  // kBalance: the durations of the frames that are through by now, in frame order
+  while (r->probe_tail != r->probe_head) {
+    avr_renderer::Probe& done = r->probes[r->probe_tail % avr_renderer::kProbes];
+    if (hipEventQuery(done.events.march_end) != hipSuccess ||
+        hipEventQuery(done.events.classify_end) != hipSuccess) {
+      (void)hipGetLastError();  // hipErrorNotReady is not an error here
+      break;
+    }
+    float classify_ms = 0.0f, march_ms = 0.0f;
+    hip_ok(hipEventElapsedTime(&classify_ms, done.events.classify_begin, done.events.classify_end),
+           "hipEventElapsedTime");
+    hip_ok(hipEventElapsedTime(&march_ms, done.events.march_begin, done.events.march_end),
+           "hipEventElapsedTime");
+    ++r->probe_tail;
+    tuner.report_durations(done.candidate, classify_ms, march_ms);
+  }
+  // the tuner's window: the period of a few frames between two events after the march
+  if (tuner.tuning()) {
+    if (tuner.closing) {
+      if (tuner.coordinated) {
+        // (agreed on by all ranks kReportLag frames after the window, in place_kernels)
+      } else if (hipEventQuery(r->window_end) == hipSuccess) {
+        float elapsed_ms = 0.0f;
+        hip_ok(hipEventElapsedTime(&elapsed_ms, r->window_begin, r->window_end),
+               "hipEventElapsedTime");
+        tuner.report(elapsed_ms / static_cast<float>(tuner.window_length));
+      } else {
+        (void)hipGetLastError();  // hipErrorNotReady is not an error here
+      }
+    } else {
+      switch (tuner.frame()) {
+        case CoRunTuner::kOpenWindow:
+          if (r->window_begin == nullptr) {
+            r->window_begin = make_event(true);
+            r->window_end = make_event(true);
+          }
+          hip_ok(hipEventRecord(r->window_begin, f.stream_m), "hipEventRecord");
+          break;
+        case CoRunTuner::kCloseWindow:
+          hip_ok(hipEventRecord(r->window_end, f.stream_m), "hipEventRecord");
+          break;
+        case CoRunTuner::kNothing:
+          break;
+      }
+    }
+  }
+  if (r->timing) hip_ok(hipEventRecord(f.timed.events.march_end, f.stream_m), "hipEventRecord");
+  hip_ok(hipEventRecord(r->marched_event[f.volume], f.stream_m), "hipEventRecord");
+  r->marched_pending[f.volume] = true;
+  if (r->timing) {
+    r->timed.push_back(f.timed.events);
+    f.timed.kept = true;
+  }
+}
+
+// ---- stream X: exchange (exchange_after), fold, gather, frame tail -----------------------------
+void queue_fold(avr_renderer* r, Frame& f) {
+  r->stage = "fold";
+  const OutputShape& shape = f.shape;
+  const float *received = f.exchanged.received, *own = f.exchanged.own;
+  avr::context_set_fold_whole_grid(r->compose, f.was_idle);
+  if (f.mip && shape.fold_to_image) {
+    abi_ok(avr_fold_plan_image_max(r->compose, f.plan, received, f.index_out, f.rgb8_out));
+  } else if (f.mip) {
+    abi_ok(avr_fold_plan_own_max(r->compose, f.plan, received, own, f.piece_index, f.piece_rgb8));
+  } else if (shape.fold_to_image) {
+    abi_ok(avr_fold_plan_image(r->compose, f.plan, received, f.piece, f.rgb8_out));
+  } else {
+    abi_ok(avr_fold_plan_own(r->compose, f.plan, received, own, f.piece,
+                             shape.overlay_piece ? nullptr : f.piece_rgb8));
+  }
+  if (shape.overlay_piece && f.piece_pixels > 0) {
+    abi_ok(avr_bbox_overlay_piece(r->compose, f.plan, r->tight_min, r->tight_max, f.camera, f.piece,
+                                  f.piece_rgb8));
+  }
+  hip_ok(hipEventRecord(r->composed_event[f.slot], f.stream_x), "hipEventRecord");
+  r->composed_pending[f.slot] = true;
+}
+
+void queue_gather_and_tail(avr_renderer* r, Frame& f) {
+  r->stage = "gather and frame tail";
+  const OutputShape& shape = f.shape;
+  const avr_frame_plan* plan = f.plan;
+  if (shape.defer_gather) {
+    // the bytes travel with the next frame's round (or with avr_renderer_synchronize)
+    avr_renderer::PendingGather& pending = r->pending;
+    pending.valid = true;
+    pending.pieces = plan->pieces;
+    pending.begin.resize(static_cast<size_t>(r->n_ranks));
+    pending.end.resize(static_cast<size_t>(r->n_ranks));
+    abi_ok(avr_frame_plan_piece_ranges(plan, pending.begin.data(), pending.end.data()));
+    pending.own_piece = plan->piece_of_rank[static_cast<size_t>(r->rank)];
+    pending.own_in_place = shape.banded || (plan->pieces.width > 0 &&
+                                            plan->pieces.piece_size % plan->pieces.width == 0);
+    pending.piece = f.piece_rgb8;
+    pending.out = f.rgb8_out;
+  } else if (shape.early_rgb8) {
+    uint8_t* full = f.piece_rgb8;
+    if (f.many) {
+      full = f.gathered_rgb8;
+      abi_ok(avr_gather(r->compose, plan, r->comm, f.piece_rgb8, 3, full, 0));
+    }
+    if (f.is_root && !shape.fold_to_image) abi_ok(avr_assemble_rows(r->compose, plan, full, 3, 1, f.rgb8_out));
+    if (f.mip && f.many) {
+      abi_ok(avr_gather(r->compose, plan, r->comm, f.piece_index, 2, f.gathered_index, 0));
+      if (f.is_root && shape.banded && f.index_out != nullptr) {
+        abi_ok(avr_assemble_rows(r->compose, plan, f.gathered_index, 2, 0, f.index_out));
+      }
+    }
+    if (shape.gather_image) {
+      if (f.many) {
+        float* gathered = f.is_root ? (shape.banded ? f.gathered_image : f.image_out) : nullptr;
+        abi_ok(avr_gather(r->compose, plan, r->comm, f.piece, 20, gathered, 0));
+        if (f.is_root && shape.banded) abi_ok(avr_assemble_rows(r->compose, plan, gathered, 20, 0, f.image_out));
+      } else {
+        hip_ok(hipMemcpyAsync(f.image_out, f.piece, static_cast<size_t>(f.info().n_pixels) * 20,
+                              hipMemcpyDeviceToDevice, f.stream_x), "hipMemcpyAsync(image)");
+      }
+    }
+  } else {
+    float* full = f.piece;
+    if (f.many) {
+      full = f.gathered_image;
+      abi_ok(avr_gather(r->compose, plan, r->comm, f.piece, 20, full, 0));
+      if (f.is_root && shape.banded) {
+        abi_ok(avr_assemble_rows(r->compose, plan, full, 20, 0, f.assembled));
+        full = f.assembled;
+      }
+    }
+    if (f.is_root) {
+      float* target = shape.gather_image ? f.image_out : f.small;
+      abi_ok(avr_downsample_depthsort(r->compose, full, f.width, f.height, f.root, target));
+      if (f.render->draw_bounds) {
+        abi_ok(avr_bbox_overlay(r->compose, r->tight_min, r->tight_max, f.camera, 1, f.width, f.height, 0,
+                                static_cast<int64_t>(f.width) * f.height, target, nullptr));
+      }
+      abi_ok(avr_quantize_rgb8(r->compose, target, f.width, f.height, 5, f.rgb8_out));
+    }
+  }
 }
 
 // One frame of avr_renderer_render (kVolume) or avr_renderer_render_max (kMaxIntensity).  A MIP
 // frame takes the same path with the MIP march and the max fold; what rests on opacity -- frame
 // chunks, occlusion culling, visibility speculation -- is left out (and speculation is not fed).
 // (A projection is render_projection_frame's.)
+// Everything up to place_kernels may fail and leave the renderer as it was; from there on the
+// frame is being queued, stream by stream.  lap(0..5): avr_renderer_host_profile's six sections.
 int render_frame(avr_renderer* r, const avr_render_params* render, const avr_camera* camera,
                  const int32_t* group_order, void* input_stream, uint64_t* samples_out,
                  int want_image, uint8_t* rgb8_out, float* image_out, avr::FrameKind kind,
                  int16_t* index_out) {
   return guarded_renderer(r, [&]() -> int {
-    require(render != nullptr && camera != nullptr, "null argument");
-    require(kind != avr::FrameKind::kProjection, "a column projection is not a pipelined frame");
-    const bool mip = kind == avr::FrameKind::kMaxIntensity;
-    const int root = validate(*render);
-    if (mip) {
-      require(root == 1, "a maximum-intensity frame has no antialiasing (render->antialiasing must be 1)");
-      require(!render->draw_bounds, "a maximum-intensity frame has no wireframe (draw_bounds must be 0)");
-      require(want_image == 0, "a maximum-intensity frame has no float image");
-      require(r->rank == 0 || index_out == nullptr, "index_out is rank 0's");
-    }
-    hip_ok(hipSetDevice(r->device), "hipSetDevice");
-    const bool is_root = r->rank == 0;
-    require(!is_root || rgb8_out != nullptr, "the root rank needs an rgb8 output buffer");
-    require(!is_root || !want_image || image_out != nullptr,
-            "want_image needs an image output buffer on the root rank");
-    const int width = render->width, height = render->height;
-
-    using Clock = std::chrono::steady_clock;
-    auto mark = Clock::now();
-    auto lap = [&](int section) {
-      const auto now = Clock::now();
-      r->host_seconds[section] += std::chrono::duration<double>(now - mark).count();
-      mark = now;
-    };
-    // ---- host plan (re-used while camera and parameters repeat; avr_renderer_prepare may have
-    // made it ahead of time on another thread) ---------------------------------------------------
-    r->stage = "frame plan";
-    const avr_frame_plan* plan = plan_for(r, *render, *camera, group_order, /*use=*/true);
-    const avr_frame_plan_info& info = plan->info;
-    const int64_t piece_pixels = info.piece_end - info.piece_begin;
-    const bool many = r->n_ranks > 1;
-    agree_on_plan(r, plan);
-
-    // Round 1's march (8 workgroups per CU) gained from being capped at 5 beside the classify
-    // pass; the present one is admitted 6 per CU by its register budget and runs best uncapped
-    // (config-4 frame: uncapped 1.06-1.07 ms, cap 5 1.09-1.11 ms).
-    const int cap = (r->march_cap < 0) ? 0 : r->march_cap;
-
-    // Send buffers alternate; the classified volumes rotate through three, so that the classify
-    // stream may run a whole frame ahead of the march: with two, classify(f+1) and march(f) both
-    // had to wait for the later of classify(f) and march(f-1) and started in lockstep, a launch
-    // latency apart from the kernels before them, every frame.
-    const int volume = static_cast<int>(r->frame % static_cast<unsigned>(AVR_CLASSIFIED_SLOTS));
-    const int slot = volume;  // send buffers rotate with the classified volumes
-    auto drain = [&] { r->drain_all(); };
-
-    // ---- everything that can fail for lack of memory happens BEFORE anything is queued and
-    // before the frame counter moves: a frame either is not started at all (the renderer stays
-    // usable) or has every buffer and event it needs.  (A failure later -- a launch, a collective
-    // -- leaves a frame half queued: the caller synchronises and tears the renderer down, on
-    // every rank; the peers of a failed rank are otherwise left waiting in the exchange.)
-    // 8-bit conversion is per pixel, so without antialiasing it is done on each rank's piece
-    // before the gather (3 bytes per pixel on the wire instead of 20); the wireframe of the tight
-    // bounds is per pixel too, so each rank overlays its own piece
-    r->stage = "frame buffers";
-    const bool early_rgb8 = root == 1;
-    const bool overlay_piece = early_rgb8 && render->draw_bounds;
-    const bool gather_image = want_image != 0;  // the same on every rank: it adds a collective
-    const bool bytes_only = early_rgb8 && !overlay_piece && !gather_image;
-    // The gathered buffer is piece-major; with contiguous pieces that IS the image, with row
-    // bands avr_assemble_rows puts the rows back (for the bytes in the same pass that turns the
-    // bottom-up image into the file's top-down rows).
-    const bool banded = info.piece_layout == AVR_PIECES_ROW_BANDS;
-    const int64_t n_pixels = info.n_pixels;
-    auto bytes_of = [](int64_t count, int each) {
-      return static_cast<size_t>(std::max<int64_t>(count, 1)) * static_cast<size_t>(each);
-    };
-    // ---- occlusion culling (one rank): the frame in depth-ordered chunks on ONE stream, every
-    // chunk's classify launch leaving out the boxes its predecessors' marches found hidden
-    int cull = 0;
-    if (!mip && !many && !r->cache_classification && info.n_local_runs > 0 && info.n_local_boxes >= 8) {
-      cull = std::min(std::max(r->occlusion_chunks, 0), info.n_local_boxes);
-    }
-    uint8_t* visibility = nullptr;
-    if (cull >= 2) {
-      visibility = static_cast<uint8_t*>(r->visible_flags[slot].reserve(
-          bytes_of(static_cast<int64_t>(cull) * info.n_local_boxes, 1), drain));
-    }
-    // ---- visibility speculation (one rank): this frame's buffers; what the frame does with them
-    // is settled below, when its layout is known
-    avr_renderer::Speculating& sp = r->spec;
-    const bool spec_considered = !mip && !many && r->speculation != 0 && cull < 2 && !r->cache_classification &&
-                                 info.n_local_runs > 0 && info.n_local_boxes >= 8 && samples_out == nullptr &&
-                                 plan->local_order.size() == static_cast<size_t>(info.n_local_boxes);
-    const size_t spec_bytes = (static_cast<size_t>(std::max(info.n_local_boxes, 1)) + 15) / 16 * 16;
-    uint8_t* spec_visited = nullptr;
-    uint8_t* spec_missed = nullptr;
-    uint32_t* spec_count = nullptr;
-    uint8_t* spec_dirty = nullptr;
-    int64_t spec_workgroups = 0;
-    size_t spec_block = 0;
-    avr_renderer::Speculating::Observation* spec_observation = nullptr;
-    if (spec_considered) {
-      ++sp.frame;
-      if (sp.last_sampled.size() != static_cast<size_t>(info.n_local_boxes)) {
-        sp.last_sampled.assign(static_cast<size_t>(info.n_local_boxes), -1);
-        sp.state = avr_renderer::Speculating::kObserving;
-      }
-      spec_visited = static_cast<uint8_t*>(sp.visited[slot].reserve(spec_bytes, drain));
-      // (one block per slot: the missed flags, the miss counter, a byte per march workgroup)
-      abi_ok(avr_march_plan_workgroups(plan, &spec_workgroups));
-      spec_block = spec_bytes + 16 + (static_cast<size_t>(spec_workgroups) + 15) / 16 * 16;
-      spec_missed = static_cast<uint8_t*>(sp.missed[slot].reserve(spec_block, drain));
-      spec_count = reinterpret_cast<uint32_t*>(spec_missed + spec_bytes);
-      spec_dirty = spec_missed + spec_bytes + 16;
-      if (sp.host_miss == nullptr) {
-        void* block = nullptr;
-        void* mapped = nullptr;
-        hip_ok(hipHostMalloc(&block, 64, hipHostMallocMapped), "hipHostMalloc(speculation miss flag)");
-        std::memset(block, 0, 64);
-        sp.host_miss = static_cast<uint32_t*>(block);
-        hip_ok(hipHostGetDevicePointer(&mapped, block, 0), "hipHostGetDevicePointer");
-        sp.host_miss_dev = static_cast<uint32_t*>(mapped);
-      }
-      // the observations that have arrived, oldest first: which boxes those frames' rays sampled
-      for (int k = 0; k < avr_renderer::Speculating::kObservations; ++k) {
-        avr_renderer::Speculating::Observation* oldest = nullptr;
-        for (avr_renderer::Speculating::Observation& o : sp.observations) {
-          if (o.pending && (oldest == nullptr || o.frame < oldest->frame)) oldest = &o;
-        }
-        if (oldest == nullptr) break;
-        if (hipEventQuery(oldest->copied) != hipSuccess) {
-          (void)hipGetLastError();  // hipErrorNotReady is not an error here
-          break;
-        }
-        oldest->pending = false;
-        if (sp.state == avr_renderer::Speculating::kDeciding) sp.state = avr_renderer::Speculating::kObserving;
-        if (oldest->stale || oldest->order.size() != sp.last_sampled.size()) {
-          oldest->stale = false;
-          continue;
-        }
-        for (size_t position = 0; position < oldest->order.size(); ++position) {
-          if (oldest->host[position] != 0) {
-            int64_t& last = sp.last_sampled[static_cast<size_t>(oldest->order[position])];
-            last = std::max(last, oldest->frame);
-          }
-        }
-        sp.sampled_fraction = -2.0f;  // (to be counted below)
-      }
-      // a free observation slot for this frame (none: the host is far ahead, this frame is not observed)
-      for (avr_renderer::Speculating::Observation& o : sp.observations) {
-        if (o.pending) continue;
-        if (o.capacity < spec_bytes) {
-          if (o.host != nullptr) (void)hipHostFree(o.host);
-          o.host = nullptr;
-          o.capacity = 0;
-          void* block = nullptr;
-          void* mapped = nullptr;
-          hip_ok(hipHostMalloc(&block, spec_bytes * 2, hipHostMallocMapped), "hipHostMalloc(speculation flags)");
-          o.host = static_cast<uint8_t*>(block);
-          hip_ok(hipHostGetDevicePointer(&mapped, block, 0), "hipHostGetDevicePointer");
-          o.host_dev = static_cast<uint8_t*>(mapped);
-          o.capacity = spec_bytes * 2;
-        }
-        if (o.copied == nullptr) {
-          // (WITH the system fence, unlike the ordering events: the host reads what the copy wrote)
-          hip_ok(hipEventCreateWithFlags(&o.copied, hipEventDisableTiming), "hipEventCreate");
-        }
-        spec_observation = &o;
-        break;
-      }
-    }
-    float* send = static_cast<float*>(r->send[slot].reserve(bytes_of(info.send_floats, 4), drain));
-    float* recv = many ? static_cast<float*>(r->recv.reserve(bytes_of(info.recv_floats, 4), drain))
-                       : nullptr;
-    float* piece = bytes_only ? nullptr
-                              : static_cast<float*>(r->piece.reserve(bytes_of(piece_pixels, 20), drain));
-    // (ranks of several: two RGB8 pieces alternate, see PendingGather)
-    DeviceBuffer& rgb8_buffer = (many && (r->frame & 1u)) ? r->piece_rgb8_odd : r->piece_rgb8;
-    uint8_t* piece_rgb8 =
-        early_rgb8 ? static_cast<uint8_t*>(rgb8_buffer.reserve(bytes_of(piece_pixels, 3), drain))
-                   : nullptr;
-    const bool defer_gather = !mip && many && r->deferred_gather != 0 && early_rgb8 && !gather_image;
-    // (MIP, ranks of several: the int16 index piece, gathered to rank 0 in the frame itself --
-    // straight into index_out where the gathered buffer is the image)
-    int16_t* piece_index = nullptr;
-    int16_t* gathered_index = nullptr;
-    if (mip && many) {
-      piece_index = static_cast<int16_t*>(r->piece_index.reserve(bytes_of(piece_pixels, 2), drain));
-      if (is_root) {
-        gathered_index = (index_out != nullptr && !banded)
-                             ? index_out
-                             : static_cast<int16_t*>(r->full_index.reserve(bytes_of(n_pixels, 2), drain));
-      }
-    }
-    uint8_t* gathered_rgb8 = nullptr;
-    float* gathered_image = nullptr;
-    float* assembled = nullptr;
-    float* small = nullptr;
-    if (is_root) {
-      if (many && (early_rgb8 || r->pending.valid)) {
-        int64_t pixels = early_rgb8 ? n_pixels : 0;
-        if (r->pending.valid) {
-          pixels = std::max<int64_t>(pixels, static_cast<int64_t>(r->pending.pieces.width) *
-                                                 r->pending.pieces.height);
-        }
-        gathered_rgb8 = static_cast<uint8_t*>(r->full_rgb8.reserve(bytes_of(pixels, 3), drain));
-      }
-      if (many && ((early_rgb8 && gather_image && banded) || !early_rgb8)) {
-        gathered_image = static_cast<float*>(r->full_image.reserve(bytes_of(n_pixels, 20), drain));
-      }
-      if (!early_rgb8 && many && banded) {
-        assembled = static_cast<float*>(r->assembled_image.reserve(bytes_of(n_pixels, 20), drain));
-      }
-      if (!early_rgb8 && !gather_image) {
-        small = static_cast<float*>(
-            r->small_image.reserve(bytes_of(static_cast<int64_t>(width) * height, 20), drain));
-      }
-    }
-    // ---- back-pressure.  The frame re-uses the classified volume and the send buffer of the
-    // frame three before it.  Either the two streams wait for that frame's march and exchange /
-    // fold (two wait packets between this frame's kernels and their predecessors, and with the
-    // descriptor ring's events the host stays a few frames ahead), or -- for the short frames of
-    // a rank of several -- the HOST waits here until they are through and nothing is queued: every
-    // packet between two marches is microseconds of a rank's 0.17 ms frame (with the descriptor
-    // copies of a repeating camera skipped as well, a rank of eight went from 0.187 to 0.164 ms);
-    // at most three frames are then in flight.  One rank's 1 ms frames hide those packets and lose
-    // 1-2 % to the shorter queue (measured), so there the streams wait.
-    // avr_renderer_set_host_backpressure.  (The waits have the deadline of
-    // avr_set_frame_timeout_ms: the exchange of the frame three back involves every peer.)
-    const bool host_side = (r->host_backpressure < 0) ? many : (r->host_backpressure != 0);
-    if (host_side) {
-      if (r->marched_pending[volume]) {
-        r->stage = "back-pressure: the march of the frame three before";
-        avr::wait_event_deadline(r->marched_event[volume], "the march of the frame three before this one");
-      }
-      if (r->composed_pending[slot]) {
-        r->stage = "back-pressure: the exchange and fold of the frame three before";
-        avr::wait_event_deadline(r->composed_event[slot],
-                                 "the exchange / fold of the frame three before this one (compositing "
-                                 "stream: a peer's blocks have not arrived)");
-      }
-    }
-
-    // One rank: the classify pass of the next frame runs beside the march of this one (HBM-bound
-    // beside issue-bound).  A rank's share of an N-rank frame is two SHORT kernels whose time is
-    // their slowest workgroups': side by side each stretched the other (N = 8, slowest rank:
-    // 77 us + 151 us alone, 0.26 + 0.27 ms overlapped), so there they run back to back on the
-    // march stream and only the exchange / fold / gather of the previous frame overlaps them.
-    // Which of the two, and how many classify workgroups a CU admits beside the march, is measured
-    // on the running pipeline (CoRunTuner) unless the caller fixed it: avr_renderer_set_overlap,
-    // avr_renderer_set_classify_share.  (A cached classification leaves nothing to tune.)
-    CoRunTuner& tuner = r->tuner;
-    {
-      // overlap_classify: -1 everything, 0 back to back, 1 side by side, 2 paired
-      int first = CoRunTuner::kBackToBack, last = CoRunTuner::kLastPaired;
-      if (r->cache_classification) {  // no classify pass to place
-        first = last = (r->overlap_classify == 0) ? CoRunTuner::kBackToBack : 0;
-      } else if (r->overlap_classify == 0) {
-        last = first;
-      } else if (r->overlap_classify == 2) {
-        first = CoRunTuner::kPairedBase;
-        if (r->share_fixed >= 0) last = first;  // the caller's reserve, kept outside the scale
-      } else {
-        if (r->overlap_classify > 0) {
-          first = 0;
-          last = CoRunTuner::kLastCandidate;
-        }
-        if (r->share_fixed >= 0) {
-          // one side-by-side candidate: the caller's reserve (kept outside the candidate scale)
-          last = (first == CoRunTuner::kBackToBack) ? 0 : first;
-        }
-      }
-      if (cull >= 2) first = last = CoRunTuner::kBackToBack;  // (one stream: nothing to place)
-      tuner.restrict_to(first, last, r->n_ranks == 1);
-      // one rank with nothing fixed: the balance of the two kernels is read off their durations
-      tuner.set_balance(r->n_ranks == 1 && r->balance != 0);
-      // ranks of several search together (avr_corun.h): the same candidate in the same frames,
-      // every window's period the maximum over the ranks
-      tuner.set_coordinated(many && r->comm != nullptr && r->coordinate != 0);
-    }
-    if (tuner.tuning() && tuner.report_due()) {
-      // The window closed kReportLag frames ago (the back-pressure above has seen its last march
-      // through); all ranks are at this frame.  A rank whose window was void (its pipeline had
-      // drained: a buffer grew) says so, and then everybody times the candidate again.
-      r->stage = "co-run window agreement (control plane)";
-      avr::wait_event_deadline(r->window_end, "the march that closes the co-run window");
-      // (the message also says which frame of which plan the rank is in: ranks that were driven
-      // apart -- same block sizes, another camera -- are found out here at the latest)
-      struct Word {
-        float period_ms;
-        uint32_t frame;
-        uint64_t plan_digest;
-      } mine{-1.0f, r->frame, plan->agreed_digest};
-      static_assert(sizeof(Word) == 16, "control word");
-      if (!tuner.window_void) {
-        float elapsed_ms = 0.0f;
-        hip_ok(hipEventElapsedTime(&elapsed_ms, r->window_begin, r->window_end), "hipEventElapsedTime");
-        mine.period_ms = elapsed_ms / static_cast<float>(tuner.window_length);
-      }
-      std::vector<Word> words(static_cast<size_t>(r->n_ranks));
-      abi_ok(avr_comm_control_allgather(r->comm, r->compose, &mine, words.data(), sizeof(Word)));
-      float agreed = 0.0f;
-      bool any_void = false;
-      for (size_t peer = 0; peer < words.size(); ++peer) {
-        const Word& word = words[peer];
-        if (word.frame != mine.frame || word.plan_digest != mine.plan_digest) {
-          throw std::runtime_error("rank " + std::to_string(peer) + " is in frame " +
-                                   std::to_string(word.frame) + (word.plan_digest != mine.plan_digest
-                                                                     ? " of another frame plan" : "") +
-                                   " while rank " + std::to_string(r->rank) + " is in frame " +
-                                   std::to_string(mine.frame) + ": the ranks were not driven alike");
-        }
-        any_void = any_void || !(word.period_ms >= 0.0f);
-        agreed = std::max(agreed, word.period_ms);
-      }
-      if (any_void) {
-        tuner.retime();
-      } else {
-        tuner.report(agreed);
-      }
-    }
-    const bool overlap = tuner.candidate != CoRunTuner::kBackToBack;
-    const bool paired = CoRunTuner::is_paired(tuner.candidate);
-    const int reserve = !overlap ? 0
-                        : (r->share_fixed >= 0)
-                            ? r->share_fixed
-                            : CoRunTuner::reserve_index(tuner.candidate) * CoRunTuner::kReserveStep;
-    // (One stream per kernel kind.  Letting the odd frames take a second march or classify stream
-    // -- the frames are independent, so march(f+1) need not queue behind march(f) and its wait /
-    // record / copy packets could be worked off early -- was measured in round 3 and is worse by
-    // half: with a FOURTH concurrently active queue everything stalls, a 5 us descriptor copy
-    // takes 40-50 us, the frame of a rank of eight goes from 0.187 to 0.26-0.33 ms and the one-rank
-    // frame from 0.98 to 1.25-1.42 ms.  profiles/r3_experiments/.)
-    // Paired layout (avr_corun.h): this frame's classify pass and march back to back on ONE
-    // stream, the even frames on stream M, the odd ones on stream B -- with stream X three active
-    // queues, the number this GPU runs side by side without penalty.
-    avr_context* march_ctx = r->march;
-    if (paired && (r->frame & 1u)) {
-      if (r->pair_b == nullptr) abi_ok(avr_context_create_with_priority(r->device, 1, &r->pair_b));
-      march_ctx = r->pair_b;
-    }
-    avr_context* classify_ctx = paired ? march_ctx : overlap ? r->classify : r->march;
-    abi_ok(avr_context_set_march_occupancy(march_ctx, cap));
-    hipStream_t stream_c = r->stream_of(classify_ctx);
-    hipStream_t stream_m = r->stream_of(march_ctx);
-    hipStream_t stream_x = r->stream_of(r->compose);
-    for (avr_context* ctx : {r->classify, r->march, r->compose, r->pair_b}) {
-      if (ctx != nullptr) avr::context_set_lean_descriptors(ctx, host_side);
-    }
-    if (r->history.size() < r->history_capacity) {
-      r->history.push_back(static_cast<int16_t>(tuner.candidate));
-    }
-    struct TimedGuard {  // the frame's four timing events, destroyed unless the frame keeps them
-      FrameEvents events;
-      bool kept = false;
-      ~TimedGuard() {
-        if (kept) return;
-        for (hipEvent_t ev : {events.classify_begin, events.classify_end, events.march_begin,
-                              events.march_end}) {
-          if (ev != nullptr) (void)hipEventDestroy(ev);
-        }
-      }
-    } timed_guard;
-    FrameEvents& timed = timed_guard.events;
-    // kBalance: this frame's kernels are timed through a slot of the probe ring (if one is free)
-    avr_renderer::Probe* probe = nullptr;
-    if (tuner.balancing() && overlap && !paired && !r->pipeline_idle &&
-        r->probe_head - r->probe_tail < avr_renderer::kProbes) {
-      probe = &r->probes[r->probe_head % avr_renderer::kProbes];
-      for (hipEvent_t* ev : {&probe->events.classify_begin, &probe->events.classify_end,
-                             &probe->events.march_begin, &probe->events.march_end}) {
-        if (*ev == nullptr) *ev = make_event(true);
-      }
-      probe->candidate = tuner.candidate;
-    }
-    if (r->timing) {
-      timed.classify_begin = make_event(true);
-      timed.classify_end = make_event(true);
-      timed.march_begin = make_event(true);
-      timed.march_end = make_event(true);
-      r->timed.reserve(r->timed.size() + 1);
-    }
-    ++r->frame;
-
-    // ---- one launch per kernel, or depth-ordered chunks (an idle pipeline: see frame_chunks) ----
-    // Chunks need the two kernels on two streams (side by side); a cached classification has no
-    // classify pass to cut.
-    const bool was_idle = r->pipeline_idle;
-    int n_chunks = 1;
-    if (!mip && overlap && !paired && !r->cache_classification && info.n_local_runs > 0) {
-      n_chunks = std::min(std::max(r->frame_chunks, 1), std::max(info.n_local_boxes, 1));
-    }
-    r->last_chunks = n_chunks;
-    // ---- visibility speculation: what this frame does (0 nothing, 1 a plain frame whose march
-    // records the boxes it samples, 2 classifies only the set, checks, repairs -- and records)
-    int spec_mode = 0;
-    {
-      using S = avr_renderer::Speculating;
-      // (the classify pass changes its length: the co-run balance is found again -- and the frames
-      // still in flight, timed under the old length, must not be read as its first steps: they sent
-      // the bisection the wrong way, 26 KiB held instead of 43, 0.45 ms instead of 0.42)
-      auto restart_corun_search = [&] {
-        tuner.restart();
-        r->probe_tail = r->probe_head;
-      };
-      if (spec_considered && n_chunks == 1) {  // (any layout: one stream or two, the protocol is the same)
-        const bool missed_lately = *static_cast<volatile uint32_t*>(sp.host_miss) != 0;
-        if (missed_lately) {  // a march of an earlier frame missed (its repair redid that frame)
-          *static_cast<volatile uint32_t*>(sp.host_miss) = 0;
-          ++sp.repaired_frames;
-          ++sp.recent_repairs;
-          sp.last_repair = sp.frame;
-        }
-        if (sp.state == S::kActive && ++sp.recent_frames >= 32) {
-          // repairs in more than half of the frames: the cells change what is visible faster than
-          // the observations follow (a repair redoes the tiles that met an unclassified box)
-          if (sp.recent_repairs * 2 > sp.recent_frames) {
-            sp.state = S::kBackoff;
-            sp.asleep_until = sp.frame + sp.next_backoff;
-            sp.next_backoff = std::min(sp.next_backoff * 2, 4096);
-            restart_corun_search();  // (the classify pass is the whole pass again)
-          } else if (sp.recent_repairs == 0) {
-            sp.next_backoff = 64;
-          }
-          sp.recent_repairs = sp.recent_frames = 0;
-        }
-        if ((sp.state == S::kRejected || sp.state == S::kBackoff) && sp.frame >= sp.asleep_until) {
-          sp.state = S::kObserving;
-          std::fill(sp.last_sampled.begin(), sp.last_sampled.end(), int64_t{-1});  // (look afresh)
-        }
-        // this frame's set: the boxes sampled within the last kSpecMemory frames, in its layer order
-        if (sp.state == S::kObserving || sp.state == S::kActive) {
-          sp.positions.clear();
-          sp.flags.assign(spec_bytes, 0);
-          bool any_observation = false;
-          for (int position = 0; position < info.n_local_boxes; ++position) {
-            const int64_t last = sp.last_sampled[static_cast<size_t>(plan->local_order[static_cast<size_t>(position)])];
-            any_observation = any_observation || last >= 0;
-            if (last >= 0 && last + avr_renderer::kSpecMemory >= sp.frame) {
-              sp.positions.push_back(position);
-              sp.flags[static_cast<size_t>(position)] = 1;
-            }
-          }
-          if (any_observation) {
-            sp.sampled_fraction = static_cast<float>(sp.positions.size()) /
-                                  static_cast<float>(std::max(info.n_local_boxes, 1));
-            // Worth it when the part of the classify pass it removes outweighs what it adds (two
-            // gated launches and two memsets on the march's stream, ~20 us, and a march that holds a
-            // wave per SIMD less): the rank's cells at ~5 TB/s, the unsampled share of that -- at
-            // least kSpecMinSavingMs.  (config-4 opaque 0.39 ms saved: frame 0.63 -> 0.43; config-3
-            // opaque 0.14, config-2 0.06: 1-2 % SLOWER when tried, their frames are march-bound.)
-            double cell_bytes = 0.0;
-            for (size_t b = 0; b < r->all_boxes.size(); ++b) {
-              if (r->owner[b] != r->rank) continue;
-              const avr_box& box = r->all_boxes[b];
-              cell_bytes += 8.0 * box.dims[0] * box.dims[1] * box.dims[2];
-            }
-            const double saving_ms = (1.0 - sp.sampled_fraction) * cell_bytes / 5.0e9;
-            const bool worth_it = sp.sampled_fraction <= r->spec_worth_it && !sp.positions.empty() &&
-                                  saving_ms >= r->spec_min_saving_ms;
-            if (sp.state == S::kObserving && worth_it) {
-              sp.state = S::kActive;
-              sp.recent_repairs = sp.recent_frames = 0;
-              restart_corun_search();  // (a classify pass of a fraction of the boxes: another balance)
-            } else if (sp.state == S::kObserving) {
-              sp.state = S::kRejected;
-              sp.asleep_until = sp.frame + avr_renderer::kSpecProbeEvery;
-            } else if (!worth_it) {  // (kActive: the rays reach nearly everything now)
-              sp.state = S::kRejected;
-              sp.asleep_until = sp.frame + avr_renderer::kSpecProbeEvery;
-              restart_corun_search();
-            }
-          }
-        }
-        if (sp.state == S::kActive) {
-          spec_mode = 2;
-        } else if (sp.state == S::kObserving && spec_observation != nullptr) {
-          spec_mode = 1;
-          sp.state = S::kDeciding;  // (until this observation has arrived)
-        }
-      }
-    }
-    void* chunk_events[AVR_MAX_FRAME_CHUNKS] = {};
-    for (int k = 0; k < n_chunks && n_chunks > 1; ++k) {
-      hipEvent_t& event = r->chunk_event[volume][k];
-      if (event == nullptr) event = make_event(false);
-      chunk_events[k] = event;
-    }
-    // (the first frame after a drain classifies alone -- its first chunk, if it is cut: no march
-    // to leave room for)
-    abi_ok(avr_context_set_classify_lds_reserve(
-        classify_ctx, (overlap && (!was_idle || n_chunks > 1)) ? reserve : 0));
-    // Side by side the march that reads this frame's bricklets starts a frame later: they are
-    // streamed to memory.  Back to back and paired it follows at once: they are stored plainly
-    // (a rank of eight 0.143 against 0.149 ms).
-    {
-      static const char* forced = std::getenv("AVR_CLASSIFY_STREAM");  // A/B only
-      // (a chunk's bricklets are marched right away, and so are those of a frame that found the
-      // pipeline empty: stored plainly, like back to back)
-      const bool stream = forced != nullptr ? std::atoi(forced) != 0
-                                            : (overlap && !paired && n_chunks == 1 && !was_idle);
-      avr::context_set_classify_stream_stores(classify_ctx, stream);
-    }
-    r->last_overlap = overlap;
-    r->last_paired = paired;
-    r->last_reserve = reserve;
-    r->pipeline_idle = false;
-
-    lap(0);
-    r->stage = "classify";
-    // ---- stream C: classify pass of this frame into classified volume `slot` -------------------
-    wait_for_input(r, input_stream, stream_c);
-    // (With host-side back-pressure the re-use of the frame's classified volume and send buffer
-    // was settled before anything was queued; otherwise the streams wait -- unless the event has
-    // already happened.)
-    auto wait_unless_done = [&](hipStream_t stream, hipEvent_t event) {
-      if (hipEventQuery(event) == hipSuccess) return;
-      (void)hipGetLastError();  // hipErrorNotReady is not an error here
-      hip_ok(hipStreamWaitEvent(stream, event, 0), "hipStreamWaitEvent");
-    };
-    if (!host_side) {
-      if (r->marched_pending[volume]) wait_unless_done(stream_c, r->marched_event[volume]);
-      if (r->composed_pending[slot]) wait_unless_done(stream_m, r->composed_event[slot]);
-    }
-    if (paired && r->paired_previous != nullptr) {  // one classify pass at a time
-      if (hipEventQuery(r->paired_previous) != hipSuccess) {
-        (void)hipGetLastError();
-        hip_ok(hipStreamWaitEvent(stream_c, r->paired_previous, 0), "hipStreamWaitEvent");
-      }
-    }
-    if (r->timing) hip_ok(hipEventRecord(timed.classify_begin, stream_c), "hipEventRecord");
-    if (probe != nullptr) hip_ok(hipEventRecord(probe->events.classify_begin, stream_c), "hipEventRecord");
-    if (cull >= 2) {
-      // (classified chunk by chunk between the march launches, below)
-    } else if (n_chunks > 1) {
-      abi_ok(avr_classify_plan_chunked(classify_ctx, r->scene, plan, volume, n_chunks, chunk_events,
-                                       was_idle ? 1 : 0));
-    } else if (spec_mode == 2) {
-      // only the boxes of the held set: a launch of exactly their tiles
-      abi_ok(avr_classify_plan_positions(classify_ctx, r->scene, plan, volume, sp.positions.data(),
-                                         static_cast<int>(sp.positions.size())));
-    } else {
-      abi_ok(avr_classify_plan(classify_ctx, r->scene, plan, volume));
-    }
-    if (probe != nullptr) hip_ok(hipEventRecord(probe->events.classify_end, stream_c), "hipEventRecord");
-    hipEvent_t classified = r->timing ? timed.classify_end : r->classified_event[volume];
-    if (overlap || r->timing) hip_ok(hipEventRecord(classified, stream_c), "hipEventRecord");
-    // (what the NEXT frame waits on must outlive this frame's timing events, which
-    // avr_renderer_set_timing destroys: always the volume's own ordering event)
-    if (paired && r->timing) {
-      hip_ok(hipEventRecord(r->classified_event[volume], stream_c), "hipEventRecord");
-    }
-    r->paired_previous = paired ? r->classified_event[volume] : nullptr;
-
-    lap(1);
-    r->stage = "march";
-    // ---- stream M: march into send buffer `slot` ------------------------------------------------
-    // (three batches of descriptors per speculating frame on the march's context: the whole ring)
-    avr::context_set_descriptor_lead(march_ctx, spec_mode == 2 ? 9 : 4);
-    // (a speculating frame is observed -- a memset, a copy kernel and an event more on the march's
-    // stream -- every time while the camera moves or a repair was needed lately: what comes into
-    // view is then in the set two or three frames later; every kSpecObserveEvery-th time while the
-    // plan stands.  Sparser for a moving camera was tried: a fly-through gains 7 %, sixteen cameras
-    // in turn lose 4 % -- the ones that fall between the observations are repaired on every visit.)
-    const bool spec_observed =
-        spec_mode != 0 && spec_observation != nullptr &&
-        (spec_mode == 1 || plan != sp.previous_plan || sp.frame % avr_renderer::kSpecObserveEvery == 0 ||
-         sp.frame - sp.last_repair < 2 * avr_renderer::kSpecObserveEvery);
-    if (!mip) sp.previous_plan = plan;
-    if (spec_observed) {  // (cleared while the classify pass still runs)
-      hip_ok(hipMemsetAsync(spec_visited, 0, spec_bytes, stream_m), "hipMemsetAsync(speculation)");
-    }
-    if (spec_mode == 2) {
-      hip_ok(hipMemsetAsync(spec_missed, 0, spec_block, stream_m), "hipMemsetAsync(speculation)");
-    }
-    if (overlap && !paired && n_chunks == 1) {
-      // (paired: the march follows its classify pass on the same stream; chunked: every march
-      // launch waits for its own chunk's event)
-      hip_ok(hipStreamWaitEvent(stream_m, classified, 0), "hipStreamWaitEvent");
-    }
-    if (r->timing) hip_ok(hipEventRecord(timed.march_begin, stream_m), "hipEventRecord");
-    if (probe != nullptr) hip_ok(hipEventRecord(probe->events.march_begin, stream_m), "hipEventRecord");
-    if (mip) {
-      abi_ok(avr_march_plan_max(march_ctx, r->scene, plan, volume, send, samples_out));
-    } else if (cull >= 2) {
-      abi_ok(avr_render_plan_culled(march_ctx, r->scene, plan, volume, send, samples_out, cull, visibility));
-      r->last_chunks = cull;
-    } else if (n_chunks > 1) {
-      abi_ok(avr_march_plan_chunked(march_ctx, r->scene, plan, volume, send, samples_out, n_chunks,
-                                    chunk_events));
-    } else if (spec_mode != 0) {
-      avr_speculation first{};
-      first.visited = spec_observed ? spec_visited : nullptr;
-      if (spec_mode == 2) {
-        first.classified_host = sp.flags.data();
-        first.missed = spec_missed;
-        first.miss_count = spec_count;
-        first.host_miss_flag = sp.host_miss_dev;
-        first.dirty_workgroups = spec_dirty;
-      }
-      abi_ok(avr_march_plan_speculative(march_ctx, r->scene, plan, volume, send, &first));
-      if (spec_mode == 2) {
-        // the repair, queued unconditionally: both launches do nothing unless the march missed
-        abi_ok(avr_classify_plan_flagged(march_ctx, r->scene, plan, volume, spec_missed, spec_count));
-        avr_speculation again{};
-        again.visited = first.visited;
-        again.gate = spec_count;
-        again.dirty_workgroups = spec_dirty;  // (only the workgroups that met an unclassified box)
-        abi_ok(avr_march_plan_speculative(march_ctx, r->scene, plan, volume, send, &again));
-        ++sp.active_frames;
-      }
-      if (spec_observed) {
-        // the boxes this frame's rays sampled go to the host (a copy kernel into pinned memory) and
-        // are read a few frames on, by box
-        abi_ok(avr::launch_upload(spec_visited, spec_observation->host_dev, spec_bytes, stream_m));
-        hip_ok(hipEventRecord(spec_observation->copied, stream_m), "hipEventRecord");
-        spec_observation->order = plan->local_order;
-        spec_observation->frame = sp.frame;
-        spec_observation->pending = true;
-      }
-    } else {
-      abi_ok(avr_march_plan(march_ctx, r->scene, plan, volume, send, samples_out));
-    }
-    if (probe != nullptr) {
-      hip_ok(hipEventRecord(probe->events.march_end, stream_m), "hipEventRecord");
-      ++r->probe_head;
-    }
-    // kBalance: the durations of the frames that are through by now, in frame order
-    while (r->probe_tail != r->probe_head) {
-      avr_renderer::Probe& done = r->probes[r->probe_tail % avr_renderer::kProbes];
-      if (hipEventQuery(done.events.march_end) != hipSuccess ||
-          hipEventQuery(done.events.classify_end) != hipSuccess) {
-        (void)hipGetLastError();  // hipErrorNotReady is not an error here
-        break;
-      }
-      float classify_ms = 0.0f, march_ms = 0.0f;
-      hip_ok(hipEventElapsedTime(&classify_ms, done.events.classify_begin, done.events.classify_end),
-             "hipEventElapsedTime");
-      hip_ok(hipEventElapsedTime(&march_ms, done.events.march_begin, done.events.march_end),
-             "hipEventElapsedTime");
-      ++r->probe_tail;
-      tuner.report_durations(done.candidate, classify_ms, march_ms);
-    }
-    // the tuner's window: the period of a few frames between two events after the march
-    if (tuner.tuning()) {
-      if (tuner.closing) {
-        if (tuner.coordinated) {
-          // (agreed on by all ranks kReportLag frames after the window, above)
-        } else if (hipEventQuery(r->window_end) == hipSuccess) {
-          float elapsed_ms = 0.0f;
-          hip_ok(hipEventElapsedTime(&elapsed_ms, r->window_begin, r->window_end),
-                 "hipEventElapsedTime");
-          tuner.report(elapsed_ms / static_cast<float>(tuner.window_length));
-        } else {
-          (void)hipGetLastError();  // hipErrorNotReady is not an error here
-        }
-      } else {
-        switch (tuner.frame()) {
-          case CoRunTuner::kOpenWindow:
-            if (r->window_begin == nullptr) {
-              r->window_begin = make_event(true);
-              r->window_end = make_event(true);
-            }
-            hip_ok(hipEventRecord(r->window_begin, stream_m), "hipEventRecord");
-            break;
-          case CoRunTuner::kCloseWindow:
-            hip_ok(hipEventRecord(r->window_end, stream_m), "hipEventRecord");
-            break;
-          case CoRunTuner::kNothing:
-            break;
-        }
-      }
-    }
-    if (r->timing) hip_ok(hipEventRecord(timed.march_end, stream_m), "hipEventRecord");
-    hip_ok(hipEventRecord(r->marched_event[volume], stream_m), "hipEventRecord");
-    r->marched_pending[volume] = true;
-    if (r->timing) {
-      r->timed.push_back(timed);
-      timed_guard.kept = true;
-    }
-
-    lap(2);
-    r->stage = "exchange";
-    // ---- stream X: exchange, fold, gather, frame tail ------------------------------------------
-    hip_ok(hipStreamWaitEvent(stream_x, r->marched_event[volume], 0), "hipStreamWaitEvent");
-    // (the rank's block for itself is not copied into the receive buffer: the fold reads it
-    // where the march stored it -- the send buffer lives until composed_event -- which is one
-    // kernel and one gap less on this stream, the busiest of a rank of eight's frame)
-    const float* received = send;
-    const float* own = nullptr;
-    if (many) {
-      exchange_with_pending_gather(r, plan, send, recv, gathered_rgb8, stream_x);
-      received = recv;
-      own = send;
-    }
-    lap(3);
-    r->stage = "fold";
-    // (one rank without antialiasing or wireframe: the fold writes the output file's rows itself)
-    const bool fold_to_image = !many && early_rgb8 && !overlay_piece && is_root;
-    avr::context_set_fold_whole_grid(r->compose, was_idle);
-    if (mip && fold_to_image) {
-      abi_ok(avr_fold_plan_image_max(r->compose, plan, received, index_out, rgb8_out));
-    } else if (mip) {
-      abi_ok(avr_fold_plan_own_max(r->compose, plan, received, own, piece_index, piece_rgb8));
-    } else if (fold_to_image) {
-      abi_ok(avr_fold_plan_image(r->compose, plan, received, piece, rgb8_out));
-    } else {
-      abi_ok(avr_fold_plan_own(r->compose, plan, received, own, piece,
-                               overlay_piece ? nullptr : piece_rgb8));
-    }
-    if (overlay_piece && piece_pixels > 0) {
-      abi_ok(avr_bbox_overlay_piece(r->compose, plan, r->tight_min, r->tight_max, camera, piece,
-                                    piece_rgb8));
-    }
-    hip_ok(hipEventRecord(r->composed_event[slot], stream_x), "hipEventRecord");
-    r->composed_pending[slot] = true;
-
-    lap(4);
-    r->stage = "gather and frame tail";
-    if (defer_gather) {
-      // the bytes travel with the next frame's round (or with avr_renderer_synchronize)
-      avr_renderer::PendingGather& pending = r->pending;
-      pending.valid = true;
-      pending.pieces = plan->pieces;
-      pending.begin.resize(static_cast<size_t>(r->n_ranks));
-      pending.end.resize(static_cast<size_t>(r->n_ranks));
-      abi_ok(avr_frame_plan_piece_ranges(plan, pending.begin.data(), pending.end.data()));
-      pending.own_piece = plan->piece_of_rank[static_cast<size_t>(r->rank)];
-      pending.own_in_place = banded || (plan->pieces.width > 0 &&
-                                        plan->pieces.piece_size % plan->pieces.width == 0);
-      pending.piece = piece_rgb8;
-      pending.out = rgb8_out;
-    } else if (early_rgb8) {
-      uint8_t* full = piece_rgb8;
-      if (many) {
-        full = gathered_rgb8;
-        abi_ok(avr_gather(r->compose, plan, r->comm, piece_rgb8, 3, full, 0));
-      }
-      if (is_root && !fold_to_image) abi_ok(avr_assemble_rows(r->compose, plan, full, 3, 1, rgb8_out));
-      if (mip && many) {
-        abi_ok(avr_gather(r->compose, plan, r->comm, piece_index, 2, gathered_index, 0));
-        if (is_root && banded && index_out != nullptr) {
-          abi_ok(avr_assemble_rows(r->compose, plan, gathered_index, 2, 0, index_out));
-        }
-      }
-      if (gather_image) {
-        if (many) {
-          float* gathered = is_root ? (banded ? gathered_image : image_out) : nullptr;
-          abi_ok(avr_gather(r->compose, plan, r->comm, piece, 20, gathered, 0));
-          if (is_root && banded) abi_ok(avr_assemble_rows(r->compose, plan, gathered, 20, 0, image_out));
-        } else {
-          hip_ok(hipMemcpyAsync(image_out, piece, static_cast<size_t>(n_pixels) * 20,
-                                hipMemcpyDeviceToDevice, stream_x), "hipMemcpyAsync(image)");
-        }
-      }
-    } else {
-      float* full = piece;
-      if (many) {
-        full = gathered_image;
-        abi_ok(avr_gather(r->compose, plan, r->comm, piece, 20, full, 0));
-        if (is_root && banded) {
-          abi_ok(avr_assemble_rows(r->compose, plan, full, 20, 0, assembled));
-          full = assembled;
-        }
-      }
-      if (is_root) {
-        float* target = gather_image ? image_out : small;
-        abi_ok(avr_downsample_depthsort(r->compose, full, width, height, root, target));
-        if (render->draw_bounds) {
-          abi_ok(avr_bbox_overlay(r->compose, r->tight_min, r->tight_max, camera, 1, width, height, 0,
-                                  static_cast<int64_t>(width) * height, target, nullptr));
-        }
-        abi_ok(avr_quantize_rgb8(r->compose, target, width, height, 5, rgb8_out));
-      }
-    }
-    lap(5);
+    Frame f{render, camera, input_stream, samples_out, want_image, rgb8_out, image_out, index_out, kind};
+    check_arguments(r, f);
+    f.mark = std::chrono::steady_clock::now();
+    plan_frame(r, f, group_order);
+    reserve_buffers(r, f);  // (and speculation's; its arrived observations are read)
+    back_pressure(r, f);
+    place_kernels(r, f);  // ++r->frame
+    choose_launch_form(r, f);
+    lap(r, f, 0);
+    queue_classify(r, f);  // stream C
+    lap(r, f, 1);
+    queue_march(r, f);  // stream M
+    service_tuner(r, f);
+    lap(r, f, 2);
+    f.exchanged = exchange_after(r, f.plan, r->marched_event[f.volume], f.send, f.recv, f.gathered_rgb8,
+                                 f.stream_x);  // stream X from here on
+    lap(r, f, 3);
+    queue_fold(r, f);
+    lap(r, f, 4);
+    queue_gather_and_tail(r, f);
+    lap(r, f, 5);
     r->stage = "queued";
     ++r->host_frames;
     r->pipeline_idle = false;  // (a buffer that grew drained the streams in between)
     return AVR_OK;
   });
 }
-
 
 // A column-projection frame (avr_renderer_render_projection): the projection march on stream M,
 // then on stream X the same exchange (carrying a deferred RGB8 gather of the frame before, as a
@@ -1916,42 +1926,33 @@ int render_projection_frame(avr_renderer* r, const avr_render_params* render, co
             "the root rank needs column and length output buffers");
     require(is_root || (column_out == nullptr && length_out == nullptr),
             "column_out and length_out are rank 0's");
-    r->stage = "frame plan";
-    const avr_frame_plan* plan = plan_for(r, *render, *camera, group_order, /*use=*/true);
+    const avr_frame_plan* plan = plan_and_agree(r, *render, *camera, group_order);
     const avr_frame_plan_info& info = plan->info;
     const int64_t piece_pixels = info.piece_end - info.piece_begin;
     const bool many = r->n_ranks > 1;
-    agree_on_plan(r, plan);
     const bool banded = info.piece_layout == AVR_PIECES_ROW_BANDS;
     const int64_t n_pixels = info.n_pixels;
-    auto bytes_of = [](int64_t count, int each) {
-      return static_cast<size_t>(std::max<int64_t>(count, 1)) * static_cast<size_t>(each);
-    };
     hipStream_t stream_m = r->stream_of(r->march);
     hipStream_t stream_x = r->stream_of(r->compose);
-    // (a buffer that grows waits for everything queued; the co-run tuner is not told: nothing of
-    // the pipelined frames' timing is this frame's)
-    auto drain = [&] {
-      for (avr_context* ctx : {r->classify, r->march, r->compose, r->pair_b}) {
-        if (ctx != nullptr) avr::wait_stream_deadline(r->stream_of(ctx), "a stream before a column projection");
-      }
+    // (a buffer that grows waits for everything queued -- quietly: see drain_quietly)
+    auto reserve = [&](avr_renderer::Buffer kind, int64_t count, int each) {
+      return r->buffer(kind).reserve(bytes_of(count, each), [&] { r->drain_quietly(); });
     };
     r->stage = "frame buffers";
-    float* send = static_cast<float*>(r->projection_send.reserve(bytes_of(info.send_floats, 4), drain));
-    float* recv = many ? static_cast<float*>(r->recv.reserve(bytes_of(info.recv_floats, 4), drain))
-                       : nullptr;
+    float* send = static_cast<float*>(reserve(avr_renderer::kProjectionSend, info.send_floats, 4));
+    float* recv = many ? static_cast<float*>(reserve(avr_renderer::kRecv, info.recv_floats, 4)) : nullptr;
     double* piece = nullptr;     // ranks of several: column piece, then length piece
     double* gathered = nullptr;  // root of several: column image, then length image (piece-major)
     if (many) {
-      piece = static_cast<double*>(r->projection_piece.reserve(bytes_of(2 * piece_pixels, 8), drain));
+      piece = static_cast<double*>(reserve(avr_renderer::kProjectionPiece, 2 * piece_pixels, 8));
       if (is_root && banded) {
-        gathered = static_cast<double*>(r->projection_full.reserve(bytes_of(2 * n_pixels, 8), drain));
+        gathered = static_cast<double*>(reserve(avr_renderer::kProjectionFull, 2 * n_pixels, 8));
       }
     }
     uint8_t* gathered_rgb8 = nullptr;  // (the deferred bytes of the frame before, see below)
     if (many && is_root && r->pending.valid) {
-      gathered_rgb8 = static_cast<uint8_t*>(r->full_rgb8.reserve(
-          bytes_of(static_cast<int64_t>(r->pending.pieces.width) * r->pending.pieces.height, 3), drain));
+      gathered_rgb8 = static_cast<uint8_t*>(reserve(
+          avr_renderer::kFullRgb8, static_cast<int64_t>(r->pending.pieces.width) * r->pending.pieces.height, 3));
     }
     if (r->projection_done == nullptr) r->projection_done = make_event(false);
 
@@ -1962,21 +1963,14 @@ int render_projection_frame(avr_renderer* r, const avr_render_params* render, co
     abi_ok(avr_march_plan_projection(r->march, r->scene, plan, 0, send, samples_out));
     hip_ok(hipEventRecord(r->projection_done, stream_m), "hipEventRecord");
 
-    r->stage = "exchange";
-    hip_ok(hipStreamWaitEvent(stream_x, r->projection_done, 0), "hipStreamWaitEvent");
-    const float* received = send;
-    const float* own = nullptr;
-    if (many) {
-      exchange_with_pending_gather(r, plan, send, recv, gathered_rgb8, stream_x);
-      received = recv;
-      own = send;
-    }
+    const Exchanged exchanged = exchange_after(r, plan, r->projection_done, send, recv, gathered_rgb8, stream_x);
     r->stage = "fold";
     if (!many) {
-      abi_ok(avr_fold_plan_projection(r->compose, plan, received, column_out, length_out));
+      abi_ok(avr_fold_plan_projection(r->compose, plan, exchanged.received, column_out, length_out));
     } else {
       double* piece_length = piece + std::max<int64_t>(piece_pixels, 1);
-      abi_ok(avr_fold_plan_own_projection(r->compose, plan, received, own, piece, piece_length));
+      abi_ok(avr_fold_plan_own_projection(r->compose, plan, exchanged.received, exchanged.own, piece,
+                                          piece_length));
       r->stage = "gather";
       double* full_column = is_root ? (banded ? gathered : column_out) : nullptr;
       double* full_length = is_root ? (banded ? gathered + n_pixels : length_out) : nullptr;

@@ -866,7 +866,7 @@ int avr_renderer_last_frame_chunks(const avr_renderer *renderer); /* what the la
  * never change.  The reference's default boxTransparency = 0: config-4's rays sample 58 of 176
  * boxes, the classify pass takes 0.18 instead of 0.55 ms, the frame 0.43 instead of 0.63.  A
  * translucent frame (every box sampled) is observed once and then left alone but for one observing
- * frame in 512; repairs in more than a quarter of the frames suspend it (64 frames, doubling).
+ * frame in 512; repairs in more than half of 32 frames suspend it (64 frames, doubling).
  * 0: never.
  * avr_renderer_speculation_state: state -1 off / 0 observing / 1 waiting for an observation /
  * 2 speculating / 3 not worth it (asleep) / 4 suspended after repairs; frames speculated and
