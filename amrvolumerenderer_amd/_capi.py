@@ -223,6 +223,9 @@ SIGNATURES = {
     "avr_slice_scene": (C.c_int, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.c_int, C.c_int, _ip, _vp, _vp, _vp]),
     "avr_slice_outline": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "avr_scene_axis_projection": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(C.c_double),
+                                            C.c_double, C.c_double, C.c_int, C.c_int,
+                                            C.POINTER(C.c_double), C.c_int, _vp, _vp, _vp]),
     "avr_blend_depthsort_f32x5": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_f32x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_u8x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),

@@ -1365,3 +1365,194 @@ def profile(plotfile: str, x_variable: str, y_variable: str, weight: str = "cell
     return {"x_edges": result["x_edges"], "mean": mean, "weight_sum": weight_sum,
             "cells": result["cells"][0], "outside": result["outside"],
             "nonfinite": result["nonfinite"]}
+
+
+# ---- on-axis projections ("On-axis projection") -------------------------------------
+
+AXIS_PROJECTION_QUANTITIES = ("column", "mean")
+_AXIS_INDEX = {"x": 0, "y": 1, "z": 2}
+
+
+def validate_axis_projection_arguments(width: int, height: int, axis: str = "z",
+                                       quantity: str = "column",
+                                       center: Optional[Sequence[float]] = None,
+                                       plane_width: Optional[Sequence[float]] = None,
+                                       log_scale: bool = False,
+                                       value_range: Optional[Sequence[float]] = None,
+                                       weight: Optional[str] = None):
+    """The argument checks of project_axis(), before any GPU work and before the plotfile is
+    opened.  Returns (center or None, plane_width or None, value_range or None) as floats."""
+    if axis not in _AXIS_INDEX:
+        raise ValueError(f"axis must be one of x, y, z, not {axis!r}")
+    if quantity not in AXIS_PROJECTION_QUANTITIES:
+        raise ValueError(f"quantity must be one of {', '.join(AXIS_PROJECTION_QUANTITIES)}, "
+                         f"not {quantity!r}")
+    rng = validate_projection_arguments(width, height, "column", log_scale, value_range)
+    if center is not None:
+        center = tuple(float(c) for c in center)
+        if len(center) != 3 or not _finite(center):
+            raise ValueError("center must hold three finite values")
+    widths = None
+    if plane_width is not None:
+        widths = tuple(float(v) for v in plane_width)
+        if len(widths) != 2:
+            raise ValueError("plane_width must hold two values (wu, wv)")
+        if not all(math.isfinite(v) and v > 0.0 for v in widths):
+            raise ValueError("plane_width must be finite and positive")
+    if weight is not None:
+        if not isinstance(weight, str) or not weight:
+            raise ValueError(f"weight must be a variable name or None, not {weight!r}")
+        if quantity == "column":
+            raise ValueError('a weighted projection is a mean: quantity="column" takes no weight')
+    return center, widths, rng
+
+
+def combine_axis_projections(parts):
+    """The on-axis projections of several owners -> that of them all: the plain sum, in the order
+    given.  parts: (integral, weight or None, length) triples as Scene.axis_projection returns
+    them (torch tensors or numpy arrays of one shape); weight is None if it is None in every
+    part."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_axis_projections needs at least one part")
+    copy = lambda a: a.copy() if hasattr(a, "copy") else a.clone()
+    integral, weight, length = parts[0]
+    integral, length = copy(integral), copy(length)
+    if weight is not None:
+        weight = copy(weight)
+    for i, w, l in parts[1:]:
+        if tuple(i.shape) != tuple(integral.shape) or tuple(l.shape) != tuple(integral.shape) or \
+                (w is None) != (weight is None):
+            raise ValueError("parts must agree in shape and in having a weight")
+        integral += i
+        length += l
+        if w is not None:
+            weight += w
+    return integral, weight, length
+
+
+def project_axis_scene(ctx, scene_f: SceneGeometry, scene_w: Optional[SceneGeometry], axis: str,
+                       center: Sequence[float], plane_width: Sequence[float], width: int,
+                       height: int, level_dl: Sequence[float], rank: int = 0, n_ranks: int = 1,
+                       process_group=None):
+    """The on-axis projection of loaded scenes ("On-axis projection"): (integral,
+    weight or None without scene_w, length), float64 [height, width] tensors on ctx.device, row 0
+    at the bottom.  scene_f and scene_w are the scenes load_plotfile_geometry returns for two
+    variables of one plotfile with the same levels, rank and world size.  Pixel (x, y) owns the
+    line center + ((x + 0.5) / W - 0.5) wu U + ((y + 0.5) / H - 0.5) wv V along axis "x" | "y" |
+    "z", (U, V) as in SLICE_AXES; center and plane_width = (wu, wv) are in the plotfile's physical
+    units (center's component along the axis is ignored), level_dl[l] = the path length of a cell
+    of level l, one entry per level up to the finest loaded one.  Every rank projects its
+    local_boxes; for n_ranks > 1 the images are SUM-reduced onto rank 0 (other ranks get (None,
+    None, None)), through the host if the group's backend is not NCCL."""
+    if axis not in _AXIS_INDEX:
+        raise ValueError(f"axis must be one of x, y, z, not {axis!r}")
+    a = _AXIS_INDEX[axis]
+    axis_u, axis_v = (a + 1) % 3, (a + 2) % 3
+    wu, wv = (float(w) for w in plane_width)
+    if not (math.isfinite(wu) and wu > 0.0 and math.isfinite(wv) and wv > 0.0):
+        raise ValueError("plane_width must be finite and positive")
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError("image dimensions must be positive")
+    center = tuple(float(c) for c in center)
+    if len(center) != 3 or not _finite((center[axis_u], center[axis_v])):
+        raise ValueError("center must hold three finite values")
+    dl = [float(v) for v in level_dl]
+    finest = max((int(b.level) for b in scene_f.all_boxes), default=0)
+    if not (finest < len(dl) <= 16):
+        raise ValueError("level_dl must hold one entry per level up to the finest loaded one "
+                         "(at most 16)")
+    scale = float(scene_f.world_scale)
+    origin = ((center[axis_u] - 0.5 * wu) * scale, (center[axis_v] - 0.5 * wv) * scale)
+    du = wu * scale / float(width)
+    dv = wv * scale / float(height)
+    fields = [ctx.create_scene(s.local_boxes, s.scalar_transform) if s is not None else None
+              for s in (scene_f, scene_w)]
+    try:
+        images = fields[0].axis_projection(a, origin, du, dv, width, height, dl, fields[1])
+        if n_ranks > 1:
+            import torch.distributed as dist
+            stage = dist.get_backend(process_group) != "nccl"
+            root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+            ctx.synchronize()
+            reduced = []
+            for t in images:
+                if t is None:
+                    reduced.append(None)
+                    continue
+                t = t.cpu() if stage else t
+                dist.reduce(t, root, op=dist.ReduceOp.SUM, group=process_group)
+                reduced.append(t if rank != 0 else t.to(ctx.device))
+            images = (None, None, None) if rank != 0 else tuple(reduced)
+        ctx.synchronize()
+    finally:
+        for field in fields:
+            if field is not None:
+                field.close()
+    return images
+
+
+def project_axis(plotfile: str, axis: str = "z", variable: Optional[str] = None,
+                 weight: Optional[str] = None, width: int = 512, height: int = 512,
+                 min_level: int = 0, max_level: int = -1,
+                 center: Optional[Sequence[float]] = None,
+                 plane_width: Optional[Sequence[float]] = None, quantity: str = "column",
+                 log_scale: bool = False, value_range: Optional[Sequence[float]] = None,
+                 color_map: Optional[Sequence[Sequence[float]]] = None,
+                 output: Optional[str] = None):
+    """On-axis projection of a plotfile's raw field (yt's ProjectionPlot; DESIGN.md 7, "On-axis
+    projection"), on cuda:0: per pixel the line integral along axis "x" | "y" | "z" through every
+    uncovered cell of the loaded levels on the pixel's line, a cell's path length being its level's
+    cell size along the axis in the plotfile's physical units -- exact, with no step and no camera.
+    (right, up) = (y, z), (z, x), (x, y) as in slice(); center defaults to the centre of the data's
+    bounding box and plane_width = (wu, wv) to the data's extent along right and up.  quantity
+    "column": integral = sum dl * f over the finite cells (for a density, the surface density);
+    "mean": integral / length, length = sum dl over those cells.  With weight (a variable's name)
+    the result is the weighted mean sum dl * f * w / sum dl * w over the cells where both are
+    finite; pass quantity="mean" with it, "column" is refused.  Returns the numpy float64 [height, width] image on
+    rank 0, row 0 at the bottom, NaN where the denominator is 0, and None on other ranks.  With
+    output (.png, else PPM) rank 0 also writes the picture, coloured as project() colours a column
+    over value_range (or the min and max shown), log10 with log_scale; pixels whose line meets no
+    counted cell and non-finite values are black."""
+    center, widths, rng = validate_axis_projection_arguments(
+        width, height, axis, quantity, center, plane_width, log_scale, value_range, weight)
+    table = projection_rgb_table(color_map)
+    variables = [variable or ""] + ([weight] if weight is not None else [])
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, variables, min_level, max_level)
+    from . import plotfile as pf
+    import torch
+    a = _AXIS_INDEX[axis]
+    axis_u, axis_v = (a + 1) % 3, (a + 2) % 3
+    scene = scenes[0]
+    finest = max(int(b.level) for b in scene.all_boxes)
+    level_dl = [float(c[a]) for c in pf.PlotFileData(plotfile).cell_size[:finest + 1]]
+    to_physical = 1.0 / float(scene.world_scale)
+    lo = [min(b.min_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    hi = [max(b.max_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    if center is None:
+        center = tuple(0.5 * (lo[i] + hi[i]) for i in range(3))
+    if widths is None:
+        widths = (hi[axis_u] - lo[axis_u], hi[axis_v] - lo[axis_v])
+    integral, weight_image, length = project_axis_scene(
+        ctx, scene, scenes[1] if weight is not None else None, axis, center, widths, width, height,
+        level_dl, rank, world, group)
+    if rank != 0:
+        return None
+    denominator = weight_image if weight is not None else length
+    if weight is None and quantity == "column":
+        shown = integral
+        nan = torch.zeros_like(integral)
+    else:
+        filled = denominator != 0.0
+        nan = torch.full_like(integral, float("nan"))
+        shown = torch.where(filled, integral / torch.where(filled, denominator, 1.0), nan)
+    if output is not None:
+        hit = length > 0.0
+        rgb8, _ = ctx.projection_colorize(
+            torch.where(hit, shown, torch.zeros_like(shown)), hit.to(torch.float64),
+            torch.from_numpy(table).to(integral.device), "column", log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
+        if not writer(rgb8.cpu().numpy(), output):
+            raise RuntimeError(f"could not write '{output}'")
+    return shown.cpu().numpy()

@@ -325,6 +325,8 @@ struct avr_context {
   void* max_layers = nullptr;                  // layer of avr_paint_box_max (grow-only)
   size_t max_layers_capacity = 0;
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
+  void* axis_planes = nullptr;                 // avr_scene_axis_projection's partial planes (grow-only)
+  size_t axis_planes_capacity = 0;
 };
 
 
@@ -855,6 +857,7 @@ void avr_context_destroy(avr_context* ctx) {
   ctx->staging.release();
   if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
   if (ctx->colorize_scratch != nullptr) (void)hipFree(ctx->colorize_scratch);
+  if (ctx->axis_planes != nullptr) (void)hipFree(ctx->axis_planes);
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -1988,6 +1991,145 @@ int avr_slice_outline(avr_context* ctx, const int32_t* box, int width, int heigh
     require(red >= 0 && red <= 255 && green >= 0 && green <= 255 && blue >= 0 && blue <= 255,
             "colour components must lie in [0, 255]");
     return avr::launch_slice_outline(box, width, height, red, green, blue, rgb8, ctx->stream);
+  });
+}
+
+int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const avr_scene* scene_w,
+                              int axis, const double origin_uv[2], double du, double dv, int width,
+                              int height, const double* level_dl, int n_levels,
+                              double* integral_dev, double* weight_dev, double* length_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene_f != nullptr && origin_uv != nullptr && level_dl != nullptr &&
+                integral_dev != nullptr && length_dev != nullptr, "null argument");
+    require((scene_w != nullptr) == (weight_dev != nullptr),
+            "weight_dev is given exactly when scene_w is");
+    require(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
+    require(width > 0 && height > 0, "image width and height must be positive");
+    require(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
+            "image has more than 2^31-1 pixels");
+    require(std::isfinite(origin_uv[0]) && std::isfinite(origin_uv[1]) && std::isfinite(du) &&
+                std::isfinite(dv), "the window must be finite");
+    require(n_levels >= 1 && n_levels <= avr::kAxisMaxLevels, "n_levels must lie in [1, 16]");
+    for (int l = 0; l < n_levels; ++l) require(std::isfinite(level_dl[l]), "level_dl must be finite");
+    const bool weighted = scene_w != nullptr;
+    const avr_scene* fields[2] = {scene_f, weighted ? scene_w : scene_f};
+    const size_t n_boxes = scene_f->boxes.size();
+    for (const avr_scene* field : fields) {
+      require(field->ctx == ctx && field->boxes.size() == n_boxes,
+              "the scenes must belong to the context and hold the same number of boxes");
+    }
+    const int axis_u = (axis + 1) % 3, axis_v = (axis + 2) % 3;
+    std::vector<avr::AxisBoxDev> boxes(n_boxes);
+    std::vector<avr::AxisPlaneDev> planes(n_boxes);
+    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    uint64_t entries = 0;
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& first = scene_f->boxes[b];
+      avr::AxisBoxDev& dev = boxes[b];
+      avr::AxisPlaneDev& plane = planes[b];
+      std::memset(&dev, 0, sizeof(dev));
+      std::memset(&plane, 0, sizeof(plane));
+      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
+      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
+      dev.paired = 1;
+      for (int f = 0; f < 2; ++f) {
+        const avr_box& in = fields[f]->boxes[b];
+        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
+                    in.dims[2] == first.dims[2] && in.level == first.level,
+                "the scenes' boxes differ in dims or level");
+        if (empty) continue;
+        require(in.cells != nullptr, "box has no cell data");
+        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
+                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
+                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
+        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
+                "box spans more than 2^28 cells (or has negative strides)");
+        if (f == 0) {
+          dev.cells_f = in.cells;
+          dev.jstride_f = static_cast<int32_t>(in.jstride);
+          dev.kstride_f = static_cast<int32_t>(in.kstride);
+        } else {
+          dev.cells_w = in.cells;
+          dev.jstride_w = static_cast<int32_t>(in.jstride);
+          dev.kstride_w = static_cast<int32_t>(in.kstride);
+        }
+        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
+            (in.kstride & 1) != 0) {
+          dev.paired = 0;
+        }
+      }
+      uint64_t tiles = 0;
+      dev.plane_begin = plane.plane_begin = static_cast<uint32_t>(entries);
+      if (!empty) {
+        require(std::isfinite(first.min_corner[axis_u]) && std::isfinite(first.max_corner[axis_u]) &&
+                    std::isfinite(first.min_corner[axis_v]) && std::isfinite(first.max_corner[axis_v]),
+                "box corners must be finite");
+        dev.nx = first.dims[0];
+        dev.ny = first.dims[1];
+        dev.nz = first.dims[2];
+        tiles = avr::axis_projection_tiles(axis, dev.nx, dev.ny, dev.nz);
+        plane.min_u = first.min_corner[axis_u];
+        plane.max_u = first.max_corner[axis_u];
+        plane.min_v = first.min_corner[axis_v];
+        plane.max_v = first.max_corner[axis_v];
+        plane.dl = level_dl[first.level];
+        plane.n_u = first.dims[axis_u];
+        plane.n_v = first.dims[axis_v];
+        plane.segments = (first.dims[axis] + avr::kAxisSegment - 1) / avr::kAxisSegment;
+        entries += static_cast<uint64_t>(plane.n_u) * static_cast<uint64_t>(plane.n_v) *
+                   static_cast<uint64_t>(plane.segments);
+      }
+      const uint64_t total = tile_begin[b] + tiles;
+      require(total < (uint64_t{1} << 31) && entries < (uint64_t{1} << 31),
+              "scene has too many cells");
+      tile_begin[b + 1] = static_cast<uint32_t>(total);
+    }
+    // the partial planes: S [entries] f64, Wt [entries] f64 (with a weight), n [entries] u32
+    const size_t n_entries = static_cast<size_t>(entries);
+    const size_t bytes = n_entries * (weighted ? 20 : 12);
+    if (bytes > ctx->axis_planes_capacity) {
+      avr::wait_stream(ctx->stream, "avr_scene_axis_projection");
+      if (ctx->axis_planes != nullptr) (void)hipFree(ctx->axis_planes);
+      ctx->axis_planes = nullptr;
+      ctx->axis_planes_capacity = 0;
+      avr::hip_check(hipMalloc(&ctx->axis_planes, bytes), "hipMalloc(axis planes)");
+      ctx->axis_planes_capacity = bytes;
+    }
+    double* plane_s = static_cast<double*>(ctx->axis_planes);
+    double* plane_w = weighted ? plane_s + n_entries : nullptr;
+    uint32_t* plane_n = reinterpret_cast<uint32_t*>(plane_s + (weighted ? 2 : 1) * n_entries);
+
+    ctx->staging.begin(boxes.size() * sizeof(avr::AxisBoxDev) +
+                           planes.size() * sizeof(avr::AxisPlaneDev) +
+                           tile_begin.size() * sizeof(uint32_t), 3);
+    avr::AxisReduceArgs reduce{};
+    avr::AxisGatherArgs gather{};
+    reduce.boxes = ctx->staging.add(boxes.data(), boxes.size());
+    gather.boxes = ctx->staging.add(planes.data(), planes.size());
+    reduce.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    ctx->staging.commit(ctx->stream);
+    reduce.n_boxes = static_cast<int32_t>(n_boxes);
+    reduce.n_tiles = tile_begin.back();
+    reduce.plane_s = plane_s;
+    reduce.plane_w = plane_w;
+    reduce.plane_n = plane_n;
+    const int status = avr::launch_axis_reduce(reduce, axis, weighted, ctx->stream);
+    if (status != AVR_OK) return status;
+    gather.n_boxes = static_cast<int32_t>(n_boxes);
+    gather.width = width;
+    gather.height = height;
+    gather.origin_u = origin_uv[0];
+    gather.origin_v = origin_uv[1];
+    gather.du = du;
+    gather.dv = dv;
+    gather.plane_s = plane_s;
+    gather.plane_w = plane_w;
+    gather.plane_n = plane_n;
+    gather.integral = integral_dev;
+    gather.weight = weight_dev;
+    gather.length = length_dev;
+    return avr::launch_axis_gather(gather, ctx->stream);
   });
 }
 

@@ -456,6 +456,60 @@ uint32_t joint_histogram_tiles(int nx, int ny, int nz);
 size_t joint_histogram_lds_bytes(int nx, int ny, bool has_y, bool has_s, bool lds);
 int launch_joint_histogram(const JointHistogramArgs& args, bool has_y, bool has_s, void* stream);
 
+// On-axis projection (avr_axis_projection.hip).  Stage 1 reduces every box's columns along the
+// axis into partial planes, one per segment of kAxisSegment cells: S (f64), Wt (f64, with a
+// weight) and n (u32), each [segments][dims_V][dims_U] at `plane_begin`.  Stage 2 gathers them per
+// pixel.  A box as stage 1 reads it:
+constexpr int kAxisSegment = 128;      // cells of a column that one partial sum covers
+constexpr int kAxisMaxLevels = 16;
+struct alignas(16) AxisBoxDev {
+  const double* cells_f;
+  const double* cells_w;  // == cells_f without a weight (not read)
+  int32_t jstride_f, kstride_f;  // element strides (Array4); every field spans < 2^28 elements
+  int32_t jstride_w, kstride_w;
+  int32_t nx, ny, nz;
+  int32_t paired;         // both fields: cells 16-byte aligned, both strides even
+  uint32_t plane_begin;   // first entry of the box's partial planes
+  int32_t pad_[3];
+};
+static_assert(sizeof(AxisBoxDev) == 64, "AxisBoxDev: 16-byte multiple for scalar loads");
+// ... and as stage 2 reads it: the f64 corners of avr_box on the image axes (max = min for a box
+// without cells: it contains no line), the plane's shape and the level's path length.
+struct alignas(16) AxisPlaneDev {
+  double min_u, max_u, min_v, max_v;
+  double dl;
+  int32_t n_u, n_v;
+  int32_t segments;
+  uint32_t plane_begin;
+  int32_t pad_[2];
+};
+static_assert(sizeof(AxisPlaneDev) == 64, "AxisPlaneDev: 16-byte multiple for scalar loads");
+struct AxisReduceArgs {
+  const AxisBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  double* plane_s;
+  double* plane_w;              // null without a weight
+  uint32_t* plane_n;
+};
+struct AxisGatherArgs {
+  const AxisPlaneDev* boxes;
+  int32_t n_boxes;
+  int32_t width, height;
+  double origin_u, origin_v, du, dv;
+  const double* plane_s;
+  const double* plane_w;        // null without a weight
+  const uint32_t* plane_n;
+  double* integral;
+  double* weight;               // null without a weight
+  double* length;
+};
+// tiles of one box in stage 1 for `axis` (0 = x, 1 = y, 2 = z); UINT32_MAX if they do not fit 31 bits
+uint32_t axis_projection_tiles(int axis, int nx, int ny, int nz);
+int launch_axis_reduce(const AxisReduceArgs& args, int axis, bool weighted, void* stream);
+int launch_axis_gather(const AxisGatherArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

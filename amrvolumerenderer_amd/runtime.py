@@ -657,6 +657,58 @@ class Scene:
         ctx.publish()
         return outs[0], outs[1], outs[2]
 
+    def axis_projection(self, axis: int, origin_uv: Sequence[float], du: float, dv: float,
+                        width: int, height: int, level_dl: Sequence[float],
+                        weight_scene: Optional["Scene"] = None,
+                        integral: Optional[torch.Tensor] = None,
+                        weight: Optional[torch.Tensor] = None,
+                        length: Optional[torch.Tensor] = None):
+        """avr_scene_axis_projection with this scene as the field: the line integral along axis
+        (0 = x, 1 = y, 2 = z) through every box that contains the pixel's line u = origin_uv[0] +
+        (x + 0.5) du, v = origin_uv[1] + (y + 0.5) dv (scene coordinates; (U, V) = (y, z), (z, x),
+        (x, y)), a cell's path length being level_dl[its box's level].  weight_scene: a scene of
+        the same context with the same box list, whose cells weight the field's.  Returns
+        (integral, weight or None without weight_scene, length), float64 [height, width] on the
+        device, row 0 at the bottom; all 0 where no box contains the line."""
+        axis, width, height = int(axis), int(width), int(height)
+        if axis not in (0, 1, 2):
+            raise ValueError("axis must be 0 (x), 1 (y) or 2 (z)")
+        if width <= 0 or height <= 0:
+            raise ValueError("image width and height must be positive")
+        origin = tuple(float(c) for c in origin_uv)
+        if len(origin) != 2:
+            raise ValueError("origin_uv must hold two values")
+        dl = np.ascontiguousarray(level_dl, dtype=np.float64)
+        if dl.ndim != 1 or dl.size < 1:
+            raise ValueError("level_dl must hold one value per level")
+        ctx = self.ctx
+        outs = []
+        for name, t, wanted in (("integral", integral, True),
+                                ("weight", weight, weight_scene is not None),
+                                ("length", length, True)):
+            if not wanted:
+                if t is not None:
+                    raise ValueError("weight is given exactly when weight_scene is")
+                outs.append(None)
+                continue
+            if t is None:
+                t = torch.empty((height, width), dtype=torch.float64, device=ctx.device)
+            ctx._check_tensor(t, torch.float64, name)
+            if t.numel() != width * height:
+                raise ValueError(f"{name} has the wrong size")
+            outs.append(t)
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_axis_projection(
+            ctx._handle, self._handle,
+            weight_scene._handle if weight_scene is not None else None, axis,
+            (C.c_double * 2)(*origin), float(du), float(dv), width, height,
+            dl.ctypes.data_as(C.POINTER(C.c_double)), int(dl.size),
+            C.c_void_p(outs[0].data_ptr()),
+            C.c_void_p(outs[1].data_ptr()) if outs[1] is not None else None,
+            C.c_void_p(outs[2].data_ptr())))
+        ctx.publish()
+        return outs[0], outs[1], outs[2]
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

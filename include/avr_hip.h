@@ -1105,6 +1105,31 @@ int avr_slice_scene(avr_context *ctx, const avr_scene *scene, const double origi
 int avr_slice_outline(avr_context *ctx, const int32_t *box, int width, int height, int red,
                       int green, int blue, uint8_t *rgb8);
 
+/* ---- on-axis projections of the raw field ("On-axis projection") ---------------- */
+
+/* The line integral along axis (0 = x, 1 = y, 2 = z) of the raw f64 cells of scene_f, cell by
+ * cell, optionally weighted by the cells of scene_w (NULL: no weight).  The scenes belong to ctx
+ * and hold the same box list as avr_scene_joint_histogram requires; each keeps its own strides.
+ * The image axes (U, V) are (y, z), (z, x), (x, y).  Pixel (x, y), row 0 at the bottom, owns the
+ * line u = origin_uv[0] + (x + 0.5) * du, v = origin_uv[1] + (y + 0.5) * dv (binary64, nothing
+ * fused) in the scene's coordinates.  Box b contains it when min[U] <= u < max[U] and min[V] <=
+ * v < max[V]; EVERY such box contributes the column of its dims[axis] cells at
+ * i_U = min(int(floor((u - min[U]) / (max[U] - min[U]) * dims[U])), dims[U] - 1), i_V likewise:
+ *   without scene_w, per cell with vf finite:         S += vf,      n += 1
+ *   with scene_w, per cell with vf and vw finite:     S += vf * vw, Wt += vw, n += 1
+ * and, with dl = level_dl[the box's level] (host, n_levels <= 16 finite entries),
+ *   integral[p] = sum_b dl * S_b,  weight[p] = sum_b dl * Wt_b,  length[p] = sum_b dl * f64(n_b),
+ * p = y * width + x, f64 on the device, all 0 where no box contains the line; weight_dev is given
+ * exactly when scene_w is.  The outputs are overwritten.  The f64 additions of a column run in an
+ * order fixed by the box's dims and the axis, the boxes are added in ascending index and no
+ * atomic touches an output: equal arguments give equal bits.  Everything is checked on the host
+ * before any device work: AVR_ERR_INVALID_ARGUMENT leaves the outputs untouched.  Asynchronous on
+ * the context's stream; the context keeps the per-box partial planes (grow-only scratch). */
+int avr_scene_axis_projection(avr_context *ctx, const avr_scene *scene_f, const avr_scene *scene_w,
+                              int axis, const double origin_uv[2], double du, double dv, int width,
+                              int height, const double *level_dl, int n_levels,
+                              double *integral_dev, double *weight_dev, double *length_dev);
+
 #ifdef __cplusplus
 }
 #endif
