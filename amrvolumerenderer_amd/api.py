@@ -18,6 +18,8 @@ import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
+from .derive import (DerivedProgram, add_field, compile_expression, derived_fields,
+                     evaluate_program, remove_field)
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
 
@@ -143,6 +145,110 @@ def build_scene_geometry(ctx, all_boxes: Sequence[AmrBox], local_boxes: Sequence
                          processed_range)
 
 
+# ---- derived fields ("Derived fields") ----------------------------------------------
+
+def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"],
+                 geometry: "SceneGeometry", cell_sizes, rank: int = 0, n_ranks: int = 1,
+                 process_group=None, log_scale_input: bool = False,
+                 normalize_to_data_range: bool = True) -> "SceneGeometry":
+    """The derived field of a compiled program as a scene ("Derived fields"): scenes
+    are the loaded scenes of program.fields, in that order, and geometry any loaded scene of the
+    same plotfile, levels, rank and world size (it supplies all_boxes, bounds and world_scale, so
+    that a program without fields still has boxes).  cell_sizes[l] = (dx, dy, dz) of level l in the
+    plotfile's physical units, one entry per level up to the finest loaded one.  One kernel writes
+    program(cell) for every cell of every local box into one new device allocation, every box its
+    own contiguous [nz, ny, nx] block on a 16-byte boundary; statistics, their reduction over ranks
+    and the scalar transform come from build_scene_geometry, to which log_scale_input and
+    normalize_to_data_range go as load_plotfile_geometry's do (the defaults are a loaded scene's).
+    The result is accepted wherever a loaded scene is."""
+    import torch
+    scenes = list(scenes)
+    if len(scenes) != len(program.fields):
+        raise ValueError("scenes must hold one loaded scene per field of the program")
+    local = list(geometry.local_boxes)
+    for scene in scenes:
+        if len(scene.local_boxes) != len(local):
+            raise ValueError("the scenes must hold the same boxes as geometry")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in geometry.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    offsets, total = [], 0
+    for b in local:
+        nx, ny, nz = b.cell_dimensions
+        offsets.append(total)
+        total += (nx * ny * nz + 1) // 2 * 2        # every block starts on a 16-byte boundary
+    cells = torch.empty(total, dtype=torch.float64, device=ctx.device)
+    out_boxes = []
+    for b, begin in zip(local, offsets):
+        nx, ny, nz = b.cell_dimensions
+        out_boxes.append(AmrBox(b.min_corner, b.max_corner,
+                                cells[begin:begin + nx * ny * nz].view(nz, ny, nx), b.level,
+                                owner=rank))
+    to_physical = float(geometry.world_scale)
+    origin = [[float(b.min_corner[a]) / to_physical for a in range(3)] for b in local]
+    inputs = [ctx.create_scene(s.local_boxes, s.scalar_transform) for s in scenes]
+    out = ctx.create_scene(out_boxes, ScalarTransform())
+    try:
+        import numpy as np
+        out.derive(inputs, program.instructions, program.constants,
+                   np.array(origin, dtype=np.float64).reshape(len(local), 3), sizes)
+    finally:
+        out.close()
+        for scene in inputs:
+            scene.close()
+    result = build_scene_geometry(ctx, geometry.all_boxes, out_boxes, geometry.bounds,
+                                  log_scale_input, normalize_to_data_range, process_group, n_ranks)
+    result.world_scale = geometry.world_scale
+    return result
+
+
+def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
+                          log_scale_input: bool, normalize_to_data_range: bool, rank: int,
+                          n_ranks: int, process_group) -> list:
+    """One scene per variable name, for every plotfile-level function.  A name that is not a
+    registered derived field goes to plotfile.load_plotfile_geometry as it always did.  A
+    registered one is compiled, its stored fields are loaded raw (the plotfile's first variable if
+    it reads none) and derive_scene applies the caller's flags.  A stored variable is loaded once
+    per call and pair of flags, however many names need it."""
+    from . import derive
+    from . import plotfile as pf
+    registered = derive.derived_fields()
+    loaded = {}
+
+    def load(name, log, normalize):
+        key = (name, bool(log), bool(normalize))
+        if key not in loaded:
+            loaded[key] = pf.load_plotfile_geometry(ctx, plotfile, name, min_level, max_level, log,
+                                                    normalize, rank, n_ranks, process_group)
+        return loaded[key]
+
+    scenes, header = [], None
+    for name in names:
+        if name not in registered:
+            scenes.append(load(name, log_scale_input, normalize_to_data_range))
+            continue
+        program = derive.compile_field(name)
+        if header is None:
+            header = pf.PlotFileData(plotfile)
+        _check_derived_inputs(plotfile, header, name, program)
+        inputs = [load(field, False, True) for field in program.fields]
+        geometry = inputs[0] if inputs else load("", False, True)
+        finest = max(int(b.level) for b in geometry.all_boxes)
+        scenes.append(derive_scene(ctx, program, inputs, geometry, header.cell_size[:finest + 1],
+                                   rank, n_ranks, process_group, log_scale_input,
+                                   normalize_to_data_range))
+    return scenes
+
+
+def _check_derived_inputs(plotfile: str, header, name: str, program: DerivedProgram) -> None:
+    for field in program.fields:
+        if field not in header.var_names:
+            raise RuntimeError(f"Variable '{field}' (needed by derived field '{name}') not found "
+                               f"in plotfile '{plotfile}'.")
+
+
 def compute_histogram(plotfile: str, variable: Optional[str] = None, min_level: int = 0,
                       max_level: int = -1, log_scale: bool = False, bins: int = 256, ctx=None,
                       rank: int = 0, n_ranks: int = 1, process_group=None) -> dict:
@@ -155,8 +261,8 @@ def compute_histogram(plotfile: str, variable: Optional[str] = None, min_level: 
         raise ValueError("binCount must be positive")
     if ctx is None:
         ctx, rank, n_ranks, process_group = _runtime_scope()
-    scene = pf.load_plotfile_geometry(ctx, plotfile, variable or "", min_level, max_level,
-                                      log_scale, True, rank, n_ranks, process_group)
+    scene = _load_variable_scenes(ctx, plotfile, [variable or ""], min_level, max_level,
+                                  log_scale, True, rank, n_ranks, process_group)[0]
     return compute_scene_histogram(ctx, scene.all_boxes, scene.local_boxes, log_scale, bins,
                                    process_group, n_ranks)
 
@@ -573,9 +679,9 @@ def run(plotfile: str, options: RenderOptions, variable_name: str = "", ctx=None
     if ctx is None:
         ctx = runtime.Context(0)
     has_override = options.scalar_range is not None
-    scene = pf.load_plotfile_geometry(ctx, plotfile, variable_name, options.min_level,
-                                      options.max_level, options.log_scale_input,
-                                      not has_override, rank, n_ranks, process_group)
+    scene = _load_variable_scenes(ctx, plotfile, [variable_name], options.min_level,
+                                  options.max_level, options.log_scale_input,
+                                  not has_override, rank, n_ranks, process_group)[0]
     return _render_loaded_scene(ctx, scene, options, rank, n_ranks, process_group,
                                 stage_through_host)
 
@@ -747,8 +853,8 @@ def project(plotfile: str, width: int = 512, height: int = 512, variable: Option
     from .renderer import FrameRenderer, RenderParameters
     import torch
     ctx, rank, world, group = _runtime_scope()
-    scene = pf.load_plotfile_geometry(ctx, plotfile, variable or "", min_level, max_level, False,
-                                      True, rank, world, group)
+    scene = _load_variable_scenes(ctx, plotfile, [variable or ""], min_level, max_level, False,
+                                  True, rank, world, group)[0]
     if camera is None:
         camera = automatic_camera(scene.bounds,
                                   up_vector=tuple(up_vector) if up_vector is not None else None)
@@ -979,8 +1085,8 @@ def slice(plotfile: str, width: int = 512, height: int = 512, variable: Optional
     from . import plotfile as pf
     import torch
     ctx, rank, world, group = _runtime_scope()
-    scene = pf.load_plotfile_geometry(ctx, plotfile, variable or "", min_level, max_level, False,
-                                      True, rank, world, group)
+    scene = _load_variable_scenes(ctx, plotfile, [variable or ""], min_level, max_level, False,
+                                  True, rank, world, group)[0]
     to_physical = 1.0 / float(scene.world_scale)
     lo = [min(b.min_corner[a] for b in scene.all_boxes) * to_physical for a in range(3)]
     hi = [max(b.max_corner[a] for b in scene.all_boxes) * to_physical for a in range(3)]
@@ -1282,13 +1388,17 @@ def _load_fields(plotfile: str, variables, min_level: int, max_level: int):
     if not os.path.exists(plotfile):
         raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
     from . import plotfile as pf
+    from . import derive
     header = pf.PlotFileData(plotfile)
+    registered = derive.derived_fields()
     for name in variables:
-        if name and name not in header.var_names:
+        if name in registered:
+            _check_derived_inputs(plotfile, header, name, derive.compile_field(name))
+        elif name and name not in header.var_names:
             raise RuntimeError(f"Variable '{name}' not found in plotfile '{plotfile}'.")
     ctx, rank, world, group = _runtime_scope()
-    scenes = [pf.load_plotfile_geometry(ctx, plotfile, name or "", min_level, max_level, False,
-                                        True, rank, world, group) for name in variables]
+    scenes = _load_variable_scenes(ctx, plotfile, [name or "" for name in variables], min_level,
+                                   max_level, False, True, rank, world, group)
     finest = max(int(b.level) for b in scenes[0].all_boxes)
     return ctx, rank, world, group, scenes, level_cell_volumes(header.cell_size[:finest + 1])
 

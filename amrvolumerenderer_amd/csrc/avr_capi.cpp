@@ -2133,6 +2133,154 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
   });
 }
 
+int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inputs, avr_scene* out,
+                     const uint32_t* instructions, int n_instructions, const double* constants,
+                     int n_constants, const double* box_origin, const double* level_cell_size,
+                     int n_levels) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(out != nullptr && instructions != nullptr && level_cell_size != nullptr,
+            "null argument");
+    require(n_inputs >= 0 && n_inputs <= avr::kDeriveMaxFields, "n_inputs must lie in [0, 6]");
+    require(n_inputs == 0 || inputs != nullptr, "null argument");
+    require(n_instructions >= 1 && n_instructions <= avr::kDeriveMaxInstructions,
+            "n_instructions must lie in [1, 64]");
+    require(n_constants >= 0 && n_constants <= avr::kDeriveMaxConstants,
+            "n_constants must lie in [0, 16]");
+    require(n_constants == 0 || constants != nullptr, "null argument");
+    require(n_levels >= 1 && n_levels <= avr::kDeriveMaxLevels, "n_levels must lie in [1, 16]");
+    // the program: known opcodes, operands in range, a stack that neither underflows nor holds more
+    // than 8 values, exactly one value at the end
+    int depth = 0;
+    for (int pc = 0; pc < n_instructions; ++pc) {
+      const uint32_t op = instructions[pc] & 0xffu, operand = instructions[pc] >> 8;
+      require(op < avr::kDeriveOpCount, "unknown opcode");
+      int pops = 2;
+      if (op <= avr::kDeriveBuiltin) {
+        pops = 0;
+        const uint32_t limit = op == avr::kDeriveConst ? static_cast<uint32_t>(n_constants)
+                               : op == avr::kDeriveField ? static_cast<uint32_t>(n_inputs)
+                                                         : avr::kDeriveBuiltinCount;
+        require(operand < limit, "an operand index is out of range");
+      } else {
+        require(operand == 0, "an operator takes no operand");
+        if (op == avr::kDeriveNeg || op == avr::kDeriveSquare || op == avr::kDeriveSqrt ||
+            op == avr::kDeriveAbs) {
+          pops = 1;
+        } else if (op == avr::kDeriveWhere) {
+          pops = 3;
+        }
+      }
+      require(depth >= pops, "the program underflows its stack");
+      depth += 1 - pops;
+      require(depth <= avr::kDeriveMaxDepth, "the program's stack is deeper than 8");
+    }
+    require(depth == 1, "the program must end with exactly one value");
+    for (int l = 0; l < n_levels * 3; ++l) {
+      require(std::isfinite(level_cell_size[l]), "level_cell_size must be finite");
+    }
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    require(n_boxes == 0 || box_origin != nullptr, "null argument");
+    for (int f = 0; f < n_inputs; ++f) {
+      require(inputs[f] != nullptr, "null argument");
+      require(inputs[f]->ctx == ctx && inputs[f]->boxes.size() == n_boxes,
+              "the scenes must belong to the context and hold the same number of boxes");
+    }
+    std::vector<avr::DeriveBoxDev> boxes(n_boxes);
+    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    // the cell ranges [first byte, last byte] of the inputs' boxes and of the output's
+    std::vector<std::pair<uintptr_t, uintptr_t>> read_ranges, write_ranges;
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& first = out->boxes[b];
+      avr::DeriveBoxDev& dev = boxes[b];
+      std::memset(&dev, 0, sizeof(dev));
+      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
+      dev.level = first.level;
+      dev.paired = 1;
+      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
+      for (int f = 0; f <= n_inputs; ++f) {  // the inputs, then the output
+        const bool is_out = f == n_inputs;
+        const avr_box& in = is_out ? first : inputs[f]->boxes[b];
+        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
+                    in.dims[2] == first.dims[2] && in.level == first.level,
+                "the scenes' boxes differ in dims or level");
+        if (empty) continue;
+        require(in.cells != nullptr, "box has no cell data");
+        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
+                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
+                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
+        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
+                "box spans more than 2^28 cells (or has negative strides)");
+        const int slot = is_out ? avr::kDeriveMaxFields : f;
+        if (is_out) {
+          dev.out = const_cast<double*>(in.cells);
+        } else {
+          dev.cells[f] = in.cells;
+        }
+        dev.jstride[slot] = static_cast<int32_t>(in.jstride);
+        dev.kstride[slot] = static_cast<int32_t>(in.kstride);
+        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
+            (in.kstride & 1) != 0) {
+          dev.paired = 0;
+        }
+        const uintptr_t begin = reinterpret_cast<uintptr_t>(in.cells);
+        (is_out ? write_ranges : read_ranges)
+            .emplace_back(begin, begin + static_cast<uintptr_t>(span) * 8 + 7);
+      }
+      for (int a = 0; a < 3; ++a) {
+        require(std::isfinite(box_origin[b * 3 + a]), "box_origin must be finite");
+        dev.origin[a] = box_origin[b * 3 + a];
+      }
+      uint64_t tiles = 0;
+      if (!empty) {
+        dev.nx = first.dims[0];
+        dev.ny = first.dims[1];
+        dev.nz = first.dims[2];
+        tiles = avr::derive_tiles(dev.nx, dev.ny, dev.nz);
+      }
+      const uint64_t total = tile_begin[b] + tiles;
+      require(total < (uint64_t{1} << 31), "scene has too many cells");
+      tile_begin[b + 1] = static_cast<uint32_t>(total);
+    }
+    // no output box may share a byte with an input box: sorted by first byte, the inputs that begin
+    // at or before an output's last byte overlap it iff the largest of their last bytes reaches it
+    std::sort(read_ranges.begin(), read_ranges.end());
+    std::vector<uintptr_t> reach(read_ranges.size());
+    for (size_t r = 0; r < read_ranges.size(); ++r) {
+      reach[r] = r == 0 ? read_ranges[r].second : std::max(reach[r - 1], read_ranges[r].second);
+    }
+    for (const auto& w : write_ranges) {
+      const size_t before =
+          std::upper_bound(read_ranges.begin(), read_ranges.end(),
+                           std::make_pair(w.second, UINTPTR_MAX)) - read_ranges.begin();
+      require(before == 0 || reach[before - 1] < w.first,
+              "an output box's cells overlap an input box's cells");
+    }
+    for (auto& key : out->classified_key) key.clear();
+    if (tile_begin.back() == 0) return AVR_OK;
+    avr::DeriveProgramDev program;
+    std::memset(&program, 0, sizeof(program));
+    std::memcpy(program.code, instructions, static_cast<size_t>(n_instructions) * sizeof(uint32_t));
+    if (n_constants != 0) {
+      std::memcpy(program.constants, constants, static_cast<size_t>(n_constants) * sizeof(double));
+    }
+    std::memcpy(program.cell_size, level_cell_size, static_cast<size_t>(n_levels) * 3 * sizeof(double));
+    avr::DeriveArgs args{};
+    ctx->staging.begin(boxes.size() * sizeof(avr::DeriveBoxDev) +
+                           tile_begin.size() * sizeof(uint32_t) + sizeof(program), 3);
+    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
+    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    args.program = ctx->staging.add(&program, 1);
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_tiles = tile_begin.back();
+    args.n_fields = n_inputs;
+    args.n_instructions = n_instructions;
+    return avr::launch_derive(args, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

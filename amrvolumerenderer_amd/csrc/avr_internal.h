@@ -510,6 +510,62 @@ uint32_t axis_projection_tiles(int axis, int nx, int ny, int nz);
 int launch_axis_reduce(const AxisReduceArgs& args, int axis, bool weighted, void* stream);
 int launch_axis_gather(const AxisGatherArgs& args, void* stream);
 
+// Derived fields (avr_derive.hip).  A program is postfix: one word per instruction, the opcode in
+// the low byte and the operand index (of a constant, a field or a built-in) above it.
+enum DeriveOp : uint32_t {
+  kDeriveConst = 0,   // push constants[operand]
+  kDeriveField = 1,   // push the cell of field `operand`
+  kDeriveBuiltin = 2, // push built-in `operand` (DeriveBuiltin)
+  kDeriveAdd = 3, kDeriveSub = 4, kDeriveMul = 5, kDeriveDiv = 6,
+  kDeriveNeg = 7, kDeriveSquare = 8, kDeriveSqrt = 9, kDeriveAbs = 10,
+  kDeriveMin = 11, kDeriveMax = 12,
+  kDeriveLt = 13, kDeriveLe = 14, kDeriveGt = 15, kDeriveGe = 16, kDeriveEq = 17, kDeriveNe = 18,
+  kDeriveWhere = 19,
+  kDeriveOpCount = 20
+};
+enum DeriveBuiltin : uint32_t {
+  kDeriveX = 0, kDeriveY = 1, kDeriveZ = 2, kDeriveDx = 3, kDeriveDy = 4, kDeriveDz = 5,
+  kDeriveCellVolume = 6, kDeriveLevel = 7, kDeriveBuiltinCount = 8
+};
+constexpr int kDeriveMaxFields = 6;
+constexpr int kDeriveMaxInstructions = 64;
+constexpr int kDeriveMaxConstants = 16;
+constexpr int kDeriveMaxDepth = 8;
+constexpr int kDeriveMaxLevels = 16;
+// A box as the kernel reads it: the cells of the input fields and of the output (entry
+// kDeriveMaxFields of the strides), each with its own strides, the dims and the level they share,
+// and the physical position of the box's low corner.
+struct alignas(16) DeriveBoxDev {
+  const double* cells[kDeriveMaxFields];  // null from n_fields on (not read)
+  double* out;
+  double origin[3];
+  int32_t jstride[kDeriveMaxFields + 1];  // element strides (Array4); every field spans < 2^28
+  int32_t kstride[kDeriveMaxFields + 1];
+  int32_t nx, ny, nz;
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t paired;         // every input and the output: cells 16-byte aligned, both strides even
+  int32_t pad_[1];
+};
+static_assert(sizeof(DeriveBoxDev) == 160, "DeriveBoxDev: 16-byte multiple for scalar loads");
+// The program and the per-level cell sizes, staged in device memory: the kernel indexes them at
+// run time, which a copy in the kernel's arguments does not allow without scratch.
+struct alignas(16) DeriveProgramDev {
+  uint32_t code[kDeriveMaxInstructions];
+  double constants[kDeriveMaxConstants];
+  double cell_size[kDeriveMaxLevels][3];
+};
+struct DeriveArgs {
+  const DeriveBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  const DeriveProgramDev* program;
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  int32_t n_fields, n_instructions;
+};
+// tiles of one box (4 x 4 rows of 128 cells); UINT32_MAX if they do not fit 31 bits
+uint32_t derive_tiles(int nx, int ny, int nz);
+int launch_derive(const DeriveArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

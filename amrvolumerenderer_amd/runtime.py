@@ -709,6 +709,35 @@ class Scene:
         ctx.publish()
         return outs[0], outs[1], outs[2]
 
+    def derive(self, inputs: Sequence["Scene"], instructions, constants, box_origin,
+               level_cell_size) -> None:
+        """avr_scene_derive with this scene as the output: overwrites the cells of this scene's
+        boxes with the program's value per cell.  inputs: up to six scenes of the same context with
+        the same box list (the program's fields, in order); instructions: uint32 words; constants:
+        float64; box_origin: [n_boxes, 3] float64, the physical position of every box's low
+        corner; level_cell_size: [n_levels, 3] float64.  This scene's cells must not overlap any
+        input's.  Asynchronous on the context's stream."""
+        ctx = self.ctx
+        inputs = list(inputs)
+        code = np.ascontiguousarray(instructions, dtype=np.uint32)
+        consts = np.ascontiguousarray(constants, dtype=np.float64)
+        origin = np.ascontiguousarray(box_origin, dtype=np.float64)
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        if code.ndim != 1 or consts.ndim != 1:
+            raise ValueError("instructions and constants must be one-dimensional")
+        if origin.shape != (len(self.boxes), 3):
+            raise ValueError("box_origin must hold three values per box")
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+        handles = (C.c_void_p * max(len(inputs), 1))(*[s._handle.value for s in inputs])
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_derive(
+            ctx._handle, handles, len(inputs), self._handle,
+            code.ctypes.data_as(C.POINTER(C.c_uint32)), int(code.size), as_doubles(consts),
+            int(consts.size), as_doubles(origin), as_doubles(sizes), int(sizes.shape[0])))
+        ctx.publish()
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

@@ -1130,6 +1130,35 @@ int avr_scene_axis_projection(avr_context *ctx, const avr_scene *scene_f, const 
                               int height, const double *level_dl, int n_levels,
                               double *integral_dev, double *weight_dev, double *length_dev);
 
+/* ---- derived fields ("Derived fields") -------------------------------------------- */
+
+/* A new field from a per-cell program over up to six fields of the same cells.  `inputs` are
+ * n_inputs (0..6) scenes of ctx and `out` a scene of ctx over cells the caller allocated, all with
+ * the same box list as avr_scene_joint_histogram requires (equal dims and levels; each keeps its own
+ * strides); the cells of out's boxes are overwritten.  The program is postfix, one word per
+ * instruction (1..64): opcode in the low byte, operand index in the bits above it.
+ *   0 CONST c   push constants[c] (n_constants <= 16)     1 FIELD f   push the cell of inputs[f]
+ *   2 BUILTIN b push 0 x, 1 y, 2 z, 3 dx, 4 dy, 5 dz, 6 cell_volume, 7 level
+ *   3 ADD  4 SUB  5 MUL  6 DIV   a b -> a op b            7 NEG  8 SQUARE (a * a)  9 SQRT  10 ABS
+ *   11 MIN  a b -> (a < b || a != a) ? a : b              12 MAX  a b -> (a > b || a != a) ? a : b
+ *   13 LT  14 LE  15 GT  16 GE  17 EQ  18 NE   a b -> 1.0 or 0.0 (with a NaN: 0.0, NE 1.0)
+ *   19 WHERE  c a b -> (c != 0.0) ? a : b (a NaN c selects a)
+ * Everything is binary64, round to nearest, nothing fused, denormals kept; DIV and SQRT are
+ * correctly rounded.  With (dx, dy, dz) = level_cell_size[3 * level .. ] (host, n_levels <= 16) of
+ * the box's level and origin = box_origin[3 * b ..] (host) of box b, cell (i, j, k) of the box has
+ * x = origin[0] + (f64(i) + 0.5) * dx (a multiply, then an add), y and z likewise, cell_volume =
+ * (dx * dy) * dz and level = f64(the box's level).  The stack holds at most 8 values.
+ * Everything is checked on the host before any device work: AVR_ERR_INVALID_ARGUMENT for counts
+ * over the limits, an unknown opcode, an operand index out of range, a program that underflows
+ * the stack, goes deeper than 8 or does not end with exactly one value, scenes that are not
+ * congruent with `out`, a box level >= n_levels, n_levels > 16, origins or cell sizes that are not
+ * finite, and an output box whose cells overlap an input box's cells -- and `out` is untouched.
+ * Asynchronous on the context's stream; invalidates out's cached classification. */
+int avr_scene_derive(avr_context *ctx, const avr_scene *const *inputs, int n_inputs, avr_scene *out,
+                     const uint32_t *instructions, int n_instructions, const double *constants,
+                     int n_constants, const double *box_origin, const double *level_cell_size,
+                     int n_levels);
+
 #ifdef __cplusplus
 }
 #endif
