@@ -23,6 +23,7 @@
 
 #include <cstdint>
 
+#include "avr_cell_tiles.h"
 #include "avr_internal.h"
 
 namespace avr {
@@ -39,20 +40,6 @@ constexpr int kGatherTile = 8;   // pixels per side of a wave's tile
 typedef const double __attribute__((address_space(1))) const_global_double;
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef const double2_t __attribute__((address_space(1))) const_global_double2;
-
-// Which box does tile number `tile` belong to (binary search over the prefix sums).
-__device__ __forceinline__ int locate_box(const uint32_t* tile_begin, int n_boxes, uint32_t tile) {
-  int lo = 0, hi = n_boxes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_begin[mid] <= tile) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
 
 template <bool W>
 __device__ __forceinline__ void add_cell(double vf, double vw, double& s, double& w, uint32_t& n) {

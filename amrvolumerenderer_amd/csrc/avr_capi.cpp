@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "../../include/avr_hip_debug.h"
+#include "avr_cell_tiles.h"
+#include "avr_field_boxes.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
 
@@ -1823,6 +1825,13 @@ int avr_scene_histogram(avr_context* ctx, const avr_scene* scene,
   });
 }
 
+// A field of a product over several scenes that share a box list (the box rules themselves are
+// avr_field_boxes.h's).
+static void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t n_boxes) {
+  require(field->ctx == ctx && field->boxes.size() == n_boxes,
+          "the scenes must belong to the context and hold the same number of boxes");
+}
+
 // n + 1 finite, strictly increasing edges; returns n / (e[n] - e[0]), or 0 if that is not finite
 static double joint_histogram_axis(const double* edges, int n, const char* axis) {
   const std::string name(axis);
@@ -1859,50 +1868,28 @@ int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const 
     const avr_scene* fields[3] = {scene_x, scene_y != nullptr ? scene_y : scene_x,
                                   scene_s != nullptr ? scene_s : scene_x};
     const size_t n_boxes = scene_x->boxes.size();
-    for (const avr_scene* field : fields) {
-      require(field->ctx == ctx && field->boxes.size() == n_boxes,
-              "the scenes must belong to the context and hold the same number of boxes");
-    }
+    for (const avr_scene* field : fields) require_field_scene(ctx, field, n_boxes);
     std::vector<avr::JointBoxDev> boxes(n_boxes);
-    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    std::vector<uint32_t> tile_begin(1, 0u);
     for (size_t b = 0; b < n_boxes; ++b) {
       const avr_box& first = scene_x->boxes[b];
+      const avr_box* in[3] = {&first, &fields[1]->boxes[b], &fields[2]->boxes[b]};
+      avr::FieldView views[3];
       avr::JointBoxDev& dev = boxes[b];
       std::memset(&dev, 0, sizeof(dev));
-      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
+      const bool cells = avr::field_box_views(first, in, 3, n_levels, views, &dev.paired);
       dev.level = first.level;
-      dev.paired = 1;
-      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
       for (int f = 0; f < 3; ++f) {
-        const avr_box& in = fields[f]->boxes[b];
-        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
-                    in.dims[2] == first.dims[2] && in.level == first.level,
-                "the scenes' boxes differ in dims or level");
-        if (empty) continue;
-        require(in.cells != nullptr, "box has no cell data");
-        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
-                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
-                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
-        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
-                "box spans more than 2^28 cells (or has negative strides)");
-        dev.cells[f] = in.cells;
-        dev.jstride[f] = static_cast<int32_t>(in.jstride);
-        dev.kstride[f] = static_cast<int32_t>(in.kstride);
-        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
-            (in.kstride & 1) != 0) {
-          dev.paired = 0;
-        }
+        dev.cells[f] = views[f].cells;
+        dev.jstride[f] = views[f].jstride;
+        dev.kstride[f] = views[f].kstride;
       }
-      uint64_t tiles = 0;
-      if (!empty) {
+      if (cells) {
         dev.nx = first.dims[0];
         dev.ny = first.dims[1];
         dev.nz = first.dims[2];
-        tiles = avr::joint_histogram_tiles(dev.nx, dev.ny, dev.nz);
       }
-      const uint64_t total = tile_begin[b] + tiles;
-      require(total < (uint64_t{1} << 31), "scene has too many cells");
-      tile_begin[b + 1] = static_cast<uint32_t>(total);
+      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
     }
     if (tile_begin.back() == 0) return AVR_OK;
     const size_t n_x = static_cast<size_t>(nx) + 1;
@@ -1958,21 +1945,16 @@ int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origi
       dev.global_index = global_index != nullptr ? global_index[b] : static_cast<int32_t>(b);
       require(in.level >= 0 && in.level <= 127, "box level must lie in [0, 127]");
       dev.level = in.level;
-      if (in.dims[0] <= 0 || in.dims[1] <= 0 || in.dims[2] <= 0) continue;  // holds no point
-      require(in.cells != nullptr, "box has no cell data");
-      const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
-                           static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
-                           static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
-      require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
-              "box spans more than 2^28 cells (or has negative strides)");
+      if (avr::box_is_empty(in)) continue;  // holds no point
+      const avr::FieldView view = avr::field_view(in);
       for (int a = 0; a < 3; ++a) {
         dev.minc[a] = in.min_corner[a];
         dev.maxc[a] = in.max_corner[a];
         dev.n[a] = in.dims[a];
       }
-      dev.cells = in.cells;
-      dev.jstride = static_cast<int32_t>(in.jstride);
-      dev.kstride = static_cast<int32_t>(in.kstride);
+      dev.cells = view.cells;
+      dev.jstride = view.jstride;
+      dev.kstride = view.kstride;
     }
     ctx->staging.begin(boxes.size() * sizeof(avr::SliceBoxDev), 1);
     const avr::SliceBoxDev* boxes_dev = ctx->staging.add(boxes.data(), boxes.size());
@@ -2015,53 +1997,30 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
     const bool weighted = scene_w != nullptr;
     const avr_scene* fields[2] = {scene_f, weighted ? scene_w : scene_f};
     const size_t n_boxes = scene_f->boxes.size();
-    for (const avr_scene* field : fields) {
-      require(field->ctx == ctx && field->boxes.size() == n_boxes,
-              "the scenes must belong to the context and hold the same number of boxes");
-    }
+    for (const avr_scene* field : fields) require_field_scene(ctx, field, n_boxes);
     const int axis_u = (axis + 1) % 3, axis_v = (axis + 2) % 3;
     std::vector<avr::AxisBoxDev> boxes(n_boxes);
     std::vector<avr::AxisPlaneDev> planes(n_boxes);
-    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    std::vector<uint32_t> tile_begin(1, 0u);
     uint64_t entries = 0;
     for (size_t b = 0; b < n_boxes; ++b) {
       const avr_box& first = scene_f->boxes[b];
+      const avr_box* in[2] = {&first, &fields[1]->boxes[b]};
+      avr::FieldView views[2];
       avr::AxisBoxDev& dev = boxes[b];
       avr::AxisPlaneDev& plane = planes[b];
       std::memset(&dev, 0, sizeof(dev));
       std::memset(&plane, 0, sizeof(plane));
-      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
-      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
-      dev.paired = 1;
-      for (int f = 0; f < 2; ++f) {
-        const avr_box& in = fields[f]->boxes[b];
-        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
-                    in.dims[2] == first.dims[2] && in.level == first.level,
-                "the scenes' boxes differ in dims or level");
-        if (empty) continue;
-        require(in.cells != nullptr, "box has no cell data");
-        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
-                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
-                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
-        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
-                "box spans more than 2^28 cells (or has negative strides)");
-        if (f == 0) {
-          dev.cells_f = in.cells;
-          dev.jstride_f = static_cast<int32_t>(in.jstride);
-          dev.kstride_f = static_cast<int32_t>(in.kstride);
-        } else {
-          dev.cells_w = in.cells;
-          dev.jstride_w = static_cast<int32_t>(in.jstride);
-          dev.kstride_w = static_cast<int32_t>(in.kstride);
-        }
-        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
-            (in.kstride & 1) != 0) {
-          dev.paired = 0;
-        }
-      }
-      uint64_t tiles = 0;
+      const bool cells = avr::field_box_views(first, in, 2, n_levels, views, &dev.paired);
+      dev.cells_f = views[0].cells;
+      dev.jstride_f = views[0].jstride;
+      dev.kstride_f = views[0].kstride;
+      dev.cells_w = views[1].cells;
+      dev.jstride_w = views[1].jstride;
+      dev.kstride_w = views[1].kstride;
+      uint32_t tiles = 0;
       dev.plane_begin = plane.plane_begin = static_cast<uint32_t>(entries);
-      if (!empty) {
+      if (cells) {
         require(std::isfinite(first.min_corner[axis_u]) && std::isfinite(first.max_corner[axis_u]) &&
                     std::isfinite(first.min_corner[axis_v]) && std::isfinite(first.max_corner[axis_v]),
                 "box corners must be finite");
@@ -2080,10 +2039,8 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
         entries += static_cast<uint64_t>(plane.n_u) * static_cast<uint64_t>(plane.n_v) *
                    static_cast<uint64_t>(plane.segments);
       }
-      const uint64_t total = tile_begin[b] + tiles;
-      require(total < (uint64_t{1} << 31) && entries < (uint64_t{1} << 31),
-              "scene has too many cells");
-      tile_begin[b + 1] = static_cast<uint32_t>(total);
+      avr::append_tiles(&tile_begin, tiles);
+      require(entries < (uint64_t{1} << 31), "scene has too many cells");
     }
     // the partial planes: S [entries] f64, Wt [entries] f64 (with a weight), n [entries] u32
     const size_t n_entries = static_cast<size_t>(entries);
@@ -2184,64 +2141,47 @@ int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inp
     require(n_boxes == 0 || box_origin != nullptr, "null argument");
     for (int f = 0; f < n_inputs; ++f) {
       require(inputs[f] != nullptr, "null argument");
-      require(inputs[f]->ctx == ctx && inputs[f]->boxes.size() == n_boxes,
-              "the scenes must belong to the context and hold the same number of boxes");
+      require_field_scene(ctx, inputs[f], n_boxes);
     }
     std::vector<avr::DeriveBoxDev> boxes(n_boxes);
-    std::vector<uint32_t> tile_begin(n_boxes + 1, 0u);
+    std::vector<uint32_t> tile_begin(1, 0u);
     // the cell ranges [first byte, last byte] of the inputs' boxes and of the output's
     std::vector<std::pair<uintptr_t, uintptr_t>> read_ranges, write_ranges;
     for (size_t b = 0; b < n_boxes; ++b) {
       const avr_box& first = out->boxes[b];
+      const avr_box* in[avr::kDeriveMaxFields + 1];  // the inputs, then the output
+      for (int f = 0; f < n_inputs; ++f) in[f] = &inputs[f]->boxes[b];
+      in[n_inputs] = &first;
+      avr::FieldView views[avr::kDeriveMaxFields + 1];
       avr::DeriveBoxDev& dev = boxes[b];
       std::memset(&dev, 0, sizeof(dev));
-      require(first.level >= 0 && first.level < n_levels, "a box's level is not below n_levels");
+      const bool cells = avr::field_box_views(first, in, n_inputs + 1, n_levels, views, &dev.paired);
       dev.level = first.level;
-      dev.paired = 1;
-      const bool empty = first.dims[0] <= 0 || first.dims[1] <= 0 || first.dims[2] <= 0;
-      for (int f = 0; f <= n_inputs; ++f) {  // the inputs, then the output
+      for (int f = 0; f <= n_inputs; ++f) {
         const bool is_out = f == n_inputs;
-        const avr_box& in = is_out ? first : inputs[f]->boxes[b];
-        require(in.dims[0] == first.dims[0] && in.dims[1] == first.dims[1] &&
-                    in.dims[2] == first.dims[2] && in.level == first.level,
-                "the scenes' boxes differ in dims or level");
-        if (empty) continue;
-        require(in.cells != nullptr, "box has no cell data");
-        const int64_t span = static_cast<int64_t>(in.dims[0] - 1) +
-                             static_cast<int64_t>(in.dims[1] - 1) * in.jstride +
-                             static_cast<int64_t>(in.dims[2] - 1) * in.kstride;
-        require(in.jstride >= 0 && in.kstride >= 0 && span < (int64_t{1} << 28),
-                "box spans more than 2^28 cells (or has negative strides)");
         const int slot = is_out ? avr::kDeriveMaxFields : f;
         if (is_out) {
-          dev.out = const_cast<double*>(in.cells);
+          dev.out = const_cast<double*>(views[f].cells);
         } else {
-          dev.cells[f] = in.cells;
+          dev.cells[f] = views[f].cells;
         }
-        dev.jstride[slot] = static_cast<int32_t>(in.jstride);
-        dev.kstride[slot] = static_cast<int32_t>(in.kstride);
-        if ((reinterpret_cast<uintptr_t>(in.cells) & 15u) != 0 || (in.jstride & 1) != 0 ||
-            (in.kstride & 1) != 0) {
-          dev.paired = 0;
-        }
-        const uintptr_t begin = reinterpret_cast<uintptr_t>(in.cells);
+        dev.jstride[slot] = views[f].jstride;
+        dev.kstride[slot] = views[f].kstride;
+        if (!cells) continue;
+        const uintptr_t begin = reinterpret_cast<uintptr_t>(views[f].cells);
         (is_out ? write_ranges : read_ranges)
-            .emplace_back(begin, begin + static_cast<uintptr_t>(span) * 8 + 7);
+            .emplace_back(begin, begin + static_cast<uintptr_t>(views[f].last) * 8 + 7);
       }
       for (int a = 0; a < 3; ++a) {
         require(std::isfinite(box_origin[b * 3 + a]), "box_origin must be finite");
         dev.origin[a] = box_origin[b * 3 + a];
       }
-      uint64_t tiles = 0;
-      if (!empty) {
+      if (cells) {
         dev.nx = first.dims[0];
         dev.ny = first.dims[1];
         dev.nz = first.dims[2];
-        tiles = avr::derive_tiles(dev.nx, dev.ny, dev.nz);
       }
-      const uint64_t total = tile_begin[b] + tiles;
-      require(total < (uint64_t{1} << 31), "scene has too many cells");
-      tile_begin[b + 1] = static_cast<uint32_t>(total);
+      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
     }
     // no output box may share a byte with an input box: sorted by first byte, the inputs that begin
     // at or before an output's last byte overlap it iff the largest of their last bytes reaches it

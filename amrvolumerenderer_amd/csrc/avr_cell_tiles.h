@@ -1,0 +1,75 @@
+// The decomposition of the cell scans (scene statistics, the joint histogram, derived fields): one
+// tile = 4 k-planes x 4 j-rows x 128 cells along x of one box, the tiles of a box numbered chunk
+// fastest, then the brick of rows along y, then along z.  The host's count and the device's decode
+// of a tile number live here together (tests/cxx/field_boxes_test.cpp holds one against the other),
+// with the search that finds a tile's box in the prefix sums of the boxes' tiles.
+#ifndef AVR_CELL_TILES_H
+#define AVR_CELL_TILES_H
+
+#include <cstdint>
+
+#include "avr_internal.h"
+
+namespace avr {
+
+// tiles of one box; UINT32_MAX if they do not fit 31 bits
+inline uint32_t cell_tiles(int nx, int ny, int nz) {
+  const uint64_t bricks_y = static_cast<uint64_t>((ny + kBrickY - 1) / kBrickY);
+  const uint64_t bricks_z = static_cast<uint64_t>((nz + kBrickZ - 1) / kBrickZ);
+  const uint64_t chunks = static_cast<uint64_t>((nx + kClassifyChunk - 1) / kClassifyChunk);
+  const uint64_t tiles = bricks_y * bricks_z * chunks;
+  return tiles < (uint64_t{1} << 31) ? static_cast<uint32_t>(tiles) : UINT32_MAX;
+}
+
+struct CellTile {
+  int chunk, bj, bk;  // the tile's cells: i in [128 chunk, +128), j in [4 bj, +4), k in [4 bk, +4)
+};
+
+// What numbers a box's tiles: its chunks along x and its bricks of rows along y.  Apart from the
+// decode, so that a kernel can work it out before it has loaded the tile's number (the order of
+// its instructions follows the order here).
+struct CellTileShape {
+  int chunks, bricks_y;
+};
+AVR_HD inline __attribute__((always_inline)) CellTileShape cell_tile_shape(int nx, int ny) {
+  CellTileShape s;
+  s.bricks_y = (ny + kBrickY - 1) >> 2;
+  s.chunks = (nx + kClassifyChunk - 1) / kClassifyChunk;
+  return s;
+}
+// Tile number `local` (< cell_tiles) of a box -> its chunk and its brick of rows.
+AVR_HD inline __attribute__((always_inline)) CellTile cell_tile_of(const CellTileShape& s,
+                                                                   uint32_t local) {
+  CellTile t;
+  t.chunk = static_cast<int>(local % static_cast<uint32_t>(s.chunks));
+  local /= static_cast<uint32_t>(s.chunks);
+  t.bj = static_cast<int>(local % static_cast<uint32_t>(s.bricks_y));
+  t.bk = static_cast<int>(local / static_cast<uint32_t>(s.bricks_y));
+  return t;
+}
+AVR_HD inline __attribute__((always_inline)) CellTile cell_tile_of(int nx, int ny, uint32_t local) {
+  return cell_tile_of(cell_tile_shape(nx, ny), local);
+}
+
+#if defined(__HIP__)
+// The box that tile number `tile` belongs to: the largest b with tile_begin[b] <= tile (binary
+// search over the prefix sums).  P: a pointer to uint32_t in whichever address space the kernel
+// reads the prefix sums through.
+template <typename P>
+__device__ __forceinline__ int locate_box(P tile_begin, int n_boxes, uint32_t tile) {
+  int lo = 0, hi = n_boxes;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tile_begin[mid] <= tile) {
+      lo = mid;
+    } else {
+      hi = mid;
+    }
+  }
+  return lo;
+}
+#endif
+
+}  // namespace avr
+
+#endif

@@ -5,10 +5,10 @@
 //
 // The inputs are scenes with the same box list; a cell is read from each at its own strides and the
 // result is written to the output scene at its own.  The decomposition is that of the scan kernels
-// (avr_scene_stats.hip, restated here as avr_joint_histogram.hip restates it, so that their code
-// objects stay as they are): one tile = 4 k-planes x 4 j-rows x 128 cells of one box, rows read
-// coalesced and as f64 pairs where every input and the output allow it, 16 consecutive tiles per
-// workgroup.
+// (avr_cell_tiles.h, shared with avr_scene_stats.hip and avr_joint_histogram.hip; the walk over a
+// tile's rows is this file's own, batched): one tile = 4 k-planes x 4 j-rows x 128 cells of one
+// box, rows read coalesced and as f64 pairs where every input and the output allow it, 16
+// consecutive tiles per workgroup.
 //
 // The program is read through the constant address space, so every wave reads it with scalar loads
 // and branches on scalar values: the interpreter never diverges.  Per tile a lane first issues the
@@ -24,6 +24,7 @@
 
 #include <cstdint>
 
+#include "avr_cell_tiles.h"
 #include "avr_internal.h"
 
 namespace avr {
@@ -95,36 +96,8 @@ __device__ __forceinline__ V field_get(uint32_t field, V f0, V f1, V f2, V f3, V
 
 struct TileCoords {
   constant_box* box;
-  int chunk, bj, bk;
+  CellTile at;
 };
-
-// The box that tile number `tile` belongs to: the largest b with tile_begin[b] <= tile (binary
-// search over the prefix sums; scalar loads).  Done once per workgroup, for its first tile.
-__device__ __forceinline__ int locate_box(constant_u32* tile_begin, int n_boxes, uint32_t tile) {
-  int lo = 0, hi = n_boxes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_begin[mid] <= tile) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
-// Tile number `local` of a box -> its 128-cell chunk and its 4 x 4 brick of rows.
-__device__ __forceinline__ TileCoords tile_of(constant_box* box, uint32_t local) {
-  TileCoords t;
-  t.box = box;
-  const int bricks_y = (box->ny + kBrickY - 1) >> 2;
-  const int chunks = (box->nx + kClassifyChunk - 1) / kClassifyChunk;
-  t.chunk = static_cast<int>(local % static_cast<uint32_t>(chunks));
-  local /= static_cast<uint32_t>(chunks);
-  t.bj = static_cast<int>(local % static_cast<uint32_t>(bricks_y));
-  t.bk = static_cast<int>(local / static_cast<uint32_t>(bricks_y));
-  return t;
-}
 
 // What the built-ins of a pass are made of: the box's values are uniform, (i, j, k) the lane's.
 struct CellFrame {
@@ -310,7 +283,7 @@ __device__ __forceinline__ void derive_tile(const DeriveArgs& a, const TileCoord
   constexpr int kRowsPerPass = kThreads / kLanesPerRow;  // 4 or 2
   constexpr int kPasses = 16 / kRowsPerPass;             // 4 or 8
   const int t = static_cast<int>(threadIdx.x);
-  const int i = tile.chunk * kClassifyChunk + (t % kLanesPerRow) * N;
+  const int i = tile.at.chunk * kClassifyChunk + (t % kLanesPerRow) * N;
   constant_program* program = (constant_program*)a.program;
   CellFrame frame;
   const int level = box->level;
@@ -330,8 +303,8 @@ __device__ __forceinline__ void derive_tile(const DeriveArgs& a, const TileCoord
   const V zero = splat<V>(0.0);
 #define AVR_DERIVE_LOAD(p)                                                                       \
   const int row##p = ((p)*kRowsPerPass) + first_row;                                                \
-  const uint32_t j##p = static_cast<uint32_t>(tile.bj * kBrickY + (row##p & 3));                 \
-  const uint32_t k##p = static_cast<uint32_t>(tile.bk * kBrickZ + (row##p >> 2));                \
+  const uint32_t j##p = static_cast<uint32_t>(tile.at.bj * kBrickY + (row##p & 3));                 \
+  const uint32_t k##p = static_cast<uint32_t>(tile.at.bk * kBrickZ + (row##p >> 2));                \
   const bool valid##p =                                                                          \
       i < nx && static_cast<int>(j##p) < ny && static_cast<int>(k##p) < nz;                      \
   V f0_##p = zero, f1_##p = zero, f2_##p = zero, f3_##p = zero, f4_##p = zero, f5_##p = zero;    \
@@ -375,7 +348,8 @@ __global__ __launch_bounds__(kThreads) void derive_kernel(const DeriveArgs a) {
   constant_u32* tile_begin = (constant_u32*)a.tile_begin;
   const uint32_t first = blockIdx.x * kTilesPerGroup;
   const uint32_t last = (first + kTilesPerGroup < a.n_tiles) ? first + kTilesPerGroup : a.n_tiles;
-  // the workgroup's tiles are consecutive: one search for the first, then a walk along the boxes
+  // the workgroup's tiles are consecutive: one search (scalar loads) for the first, then a walk
+  // along the boxes
   int b = locate_box(tile_begin, a.n_boxes, first);
   uint32_t begin = tile_begin[b], end = tile_begin[b + 1];
   for (uint32_t t = first; t < last; ++t) {
@@ -384,7 +358,7 @@ __global__ __launch_bounds__(kThreads) void derive_kernel(const DeriveArgs a) {
       begin = end;
       end = tile_begin[b + 1];
     }
-    const TileCoords tile = tile_of(boxes + b, t - begin);
+    const TileCoords tile = {boxes + b, cell_tile_of(boxes[b].nx, boxes[b].ny, t - begin)};
     if (tile.box->paired) {
       derive_tile<double2_t, 2, F>(a, tile);
     } else {
@@ -394,14 +368,6 @@ __global__ __launch_bounds__(kThreads) void derive_kernel(const DeriveArgs a) {
 }
 
 }  // namespace
-
-uint32_t derive_tiles(int nx, int ny, int nz) {
-  const uint64_t bricks_y = static_cast<uint64_t>((ny + kBrickY - 1) / kBrickY);
-  const uint64_t bricks_z = static_cast<uint64_t>((nz + kBrickZ - 1) / kBrickZ);
-  const uint64_t chunks = static_cast<uint64_t>((nx + kClassifyChunk - 1) / kClassifyChunk);
-  const uint64_t tiles = bricks_y * bricks_z * chunks;
-  return tiles < (uint64_t{1} << 31) ? static_cast<uint32_t>(tiles) : UINT32_MAX;
-}
 
 int launch_derive(const DeriveArgs& args, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);

@@ -451,8 +451,6 @@ struct JointHistogramArgs {
   double* sums;                 // the same shape (null without s), added to
   unsigned long long* totals;   // [2]: outside, nonfinite, added to
 };
-// tiles of one box (4 x 4 rows of 128 cells); UINT32_MAX if they do not fit 31 bits
-uint32_t joint_histogram_tiles(int nx, int ny, int nz);
 size_t joint_histogram_lds_bytes(int nx, int ny, bool has_y, bool has_s, bool lds);
 int launch_joint_histogram(const JointHistogramArgs& args, bool has_y, bool has_s, void* stream);
 
@@ -562,8 +560,6 @@ struct DeriveArgs {
   uint32_t n_tiles;
   int32_t n_fields, n_instructions;
 };
-// tiles of one box (4 x 4 rows of 128 cells); UINT32_MAX if they do not fit 31 bits
-uint32_t derive_tiles(int nx, int ny, int nz);
 int launch_derive(const DeriveArgs& args, void* stream);
 
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.

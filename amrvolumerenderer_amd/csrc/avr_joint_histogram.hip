@@ -4,8 +4,8 @@
 //   joint_histogram_kernel<HAS_Y, HAS_S, LDS>
 //
 // The fields are scenes with the same box list; a cell is read from each at its own strides.  The
-// decomposition is that of the scan kernels (avr_scene_stats.hip, restated here so that their
-// code objects stay as they are): one tile = 4 k-planes x 4 j-rows x 128 cells of one box, rows
+// decomposition is that of the scan kernels (avr_cell_tiles.h, shared with avr_scene_stats.hip and
+// avr_derive.hip): one tile = 4 k-planes x 4 j-rows x 128 cells of one box, rows
 // read coalesced and as f64 pairs where every field allows it, 16 consecutive tiles per workgroup.
 //
 // Per cell, in this order: a non-finite vx, vy or vs counts as `nonfinite`; a vx or vy outside its
@@ -22,6 +22,7 @@
 
 #include <cstdint>
 
+#include "avr_cell_tiles.h"
 #include "avr_internal.h"
 
 namespace avr {
@@ -37,31 +38,18 @@ typedef const double __attribute__((address_space(1))) const_global_double;
 
 struct TileCoords {
   const JointBoxDev* box;
-  int chunk, bj, bk;
+  CellTile at;
 };
 
-// Which box / tile does tile number `tile` belong to (binary search over the prefix sums).
+// Which box / tile does tile number `tile` belong to.
 __device__ __forceinline__ TileCoords locate_tile(const JointBoxDev* boxes,
                                                   const uint32_t* tile_begin, int n_boxes,
                                                   uint32_t tile) {
-  int lo = 0, hi = n_boxes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_begin[mid] <= tile) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
+  const int b = locate_box(tile_begin, n_boxes, tile);
   TileCoords t;
-  t.box = &boxes[lo];
-  const int bricks_y = (t.box->ny + kBrickY - 1) >> 2;
-  const int chunks = (t.box->nx + kClassifyChunk - 1) / kClassifyChunk;
-  uint32_t local = tile - tile_begin[lo];
-  t.chunk = static_cast<int>(local % static_cast<uint32_t>(chunks));
-  local /= static_cast<uint32_t>(chunks);
-  t.bj = static_cast<int>(local % static_cast<uint32_t>(bricks_y));
-  t.bk = static_cast<int>(local / static_cast<uint32_t>(bricks_y));
+  t.box = &boxes[b];
+  const CellTileShape shape = cell_tile_shape(t.box->nx, t.box->ny);
+  t.at = cell_tile_of(shape, tile - tile_begin[b]);
   return t;
 }
 
@@ -79,12 +67,12 @@ __device__ __forceinline__ void for_each_cell(const TileCoords& tile, F&& visit)
   if (box.paired) {  // every field: 16-byte aligned cells and even strides (set by the host)
     typedef double double2_t __attribute__((ext_vector_type(2)));
     typedef const double2_t __attribute__((address_space(1))) const_global_double2;
-    const int i = tile.chunk * kClassifyChunk + (t & 63) * 2;
+    const int i = tile.at.chunk * kClassifyChunk + (t & 63) * 2;
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
       const int row = pass * 4 + (t >> 6);
-      const uint32_t j = static_cast<uint32_t>(tile.bj * kBrickY + (row & 3));
-      const uint32_t k = static_cast<uint32_t>(tile.bk * kBrickZ + (row >> 2));
+      const uint32_t j = static_cast<uint32_t>(tile.at.bj * kBrickY + (row & 3));
+      const uint32_t k = static_cast<uint32_t>(tile.at.bk * kBrickZ + (row >> 2));
       if (i < box.nx && static_cast<int>(j) < box.ny && static_cast<int>(k) < box.nz) {
         const uint32_t ui = static_cast<uint32_t>(i);
         const uint32_t ax = ui + j * jx + k * kx;
@@ -103,12 +91,12 @@ __device__ __forceinline__ void for_each_cell(const TileCoords& tile, F&& visit)
       }
     }
   } else {
-    const int i = tile.chunk * kClassifyChunk + (t & 127);
+    const int i = tile.at.chunk * kClassifyChunk + (t & 127);
 #pragma unroll
     for (int pass = 0; pass < 8; ++pass) {
       const int row = pass * 2 + (t >> 7);
-      const uint32_t j = static_cast<uint32_t>(tile.bj * kBrickY + (row & 3));
-      const uint32_t k = static_cast<uint32_t>(tile.bk * kBrickZ + (row >> 2));
+      const uint32_t j = static_cast<uint32_t>(tile.at.bj * kBrickY + (row & 3));
+      const uint32_t k = static_cast<uint32_t>(tile.at.bk * kBrickZ + (row >> 2));
       if (i < box.nx && static_cast<int>(j) < box.ny && static_cast<int>(k) < box.nz) {
         const uint32_t ui = static_cast<uint32_t>(i);
         visit(cx[ui + j * jx + k * kx], HAS_Y ? cy[ui + j * jy + k * ky] : 0.0,
@@ -298,14 +286,6 @@ int check(const char* what) {
 }
 
 }  // namespace
-
-uint32_t joint_histogram_tiles(int nx, int ny, int nz) {
-  const uint64_t bricks_y = static_cast<uint64_t>((ny + kBrickY - 1) / kBrickY);
-  const uint64_t bricks_z = static_cast<uint64_t>((nz + kBrickZ - 1) / kBrickZ);
-  const uint64_t chunks = static_cast<uint64_t>((nx + kClassifyChunk - 1) / kClassifyChunk);
-  const uint64_t tiles = bricks_y * bricks_z * chunks;
-  return tiles < (uint64_t{1} << 31) ? static_cast<uint32_t>(tiles) : UINT32_MAX;
-}
 
 size_t joint_histogram_lds_bytes(int nx, int ny, bool has_y, bool has_s, bool lds) {
   const size_t bins = static_cast<size_t>(nx) * static_cast<size_t>(ny);

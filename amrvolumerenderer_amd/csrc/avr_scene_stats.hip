@@ -5,13 +5,15 @@
 //                         (min, max, min positive, finite count over all cells)
 //   histogram_kernel      the binning of ComputeSceneHistogram, SceneBuilder.cpp:495-532
 //
-// Both use the classify pass's decomposition: one workgroup = 4 k-planes x 4 j-rows x 128
-// cells of one box, rows read coalesced (the boxes keep their Array4 strides).  Results are
-// exact and order-independent (min / max / integer counts).
+// Both use the classify pass's decomposition (avr_cell_tiles.h, shared with the joint histogram
+// and the derived fields): one tile = 4 k-planes x 4 j-rows x 128 cells of one box, rows read
+// coalesced (the boxes keep their Array4 strides).  Results are exact and order-independent
+// (min / max / integer counts).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "avr_cell_tiles.h"
 #include "avr_device.h"
 #include "avr_internal.h"
 
@@ -25,30 +27,17 @@ constexpr uint32_t kTilesPerGroup = 16;  // histogram: tiles (2048 cells each) p
 
 struct TileCoords {
   const BoxDev* box;
-  int chunk, bj, bk;
+  CellTile at;
 };
 
-// Which box / tile does workgroup `tile` belong to (binary search over the prefix sums).
+// Which box / tile does workgroup `tile` belong to.
 __device__ __forceinline__ TileCoords locate_tile(const BoxDev* boxes, const uint32_t* tile_begin,
                                                   int n_boxes, uint32_t tile) {
-  int lo = 0, hi = n_boxes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_begin[mid] <= tile) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
+  const int b = locate_box(tile_begin, n_boxes, tile);
   TileCoords t;
-  t.box = &boxes[lo];
-  const int bricks_y = (t.box->ny + kBrickY - 1) >> 2;
-  const int chunks = (t.box->nx + kClassifyChunk - 1) / kClassifyChunk;
-  uint32_t local = tile - tile_begin[lo];
-  t.chunk = static_cast<int>(local % static_cast<uint32_t>(chunks));
-  local /= static_cast<uint32_t>(chunks);
-  t.bj = static_cast<int>(local % static_cast<uint32_t>(bricks_y));
-  t.bk = static_cast<int>(local / static_cast<uint32_t>(bricks_y));
+  t.box = &boxes[b];
+  const CellTileShape shape = cell_tile_shape(t.box->nx, t.box->ny);
+  t.at = cell_tile_of(shape, tile - tile_begin[b]);
   return t;
 }
 
@@ -65,12 +54,12 @@ __device__ __forceinline__ void for_each_cell(const TileCoords& tile, F&& visit)
                       ((jstride & 1u) == 0) && ((kstride & 1u) == 0);
   if (paired) {
     typedef double double2_t __attribute__((ext_vector_type(2)));
-    const int i = tile.chunk * kClassifyChunk + (t & 63) * 2;
+    const int i = tile.at.chunk * kClassifyChunk + (t & 63) * 2;
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
       const int row = pass * 4 + (t >> 6);
-      const int j = tile.bj * kBrickY + (row & 3);
-      const int k = tile.bk * kBrickZ + (row >> 2);
+      const int j = tile.at.bj * kBrickY + (row & 3);
+      const int k = tile.at.bk * kBrickZ + (row >> 2);
       if (i < box.nx && j < box.ny && k < box.nz) {
         const uint32_t at = static_cast<uint32_t>(i) + static_cast<uint32_t>(j) * jstride +
                             static_cast<uint32_t>(k) * kstride;
@@ -84,12 +73,12 @@ __device__ __forceinline__ void for_each_cell(const TileCoords& tile, F&& visit)
       }
     }
   } else {
-    const int i = tile.chunk * kClassifyChunk + (t & 127);
+    const int i = tile.at.chunk * kClassifyChunk + (t & 127);
 #pragma unroll
     for (int pass = 0; pass < 8; ++pass) {
       const int row = pass * 2 + (t >> 7);
-      const int j = tile.bj * kBrickY + (row & 3);
-      const int k = tile.bk * kBrickZ + (row >> 2);
+      const int j = tile.at.bj * kBrickY + (row & 3);
+      const int k = tile.at.bk * kBrickZ + (row >> 2);
       if (i < box.nx && j < box.ny && k < box.nz) {
         visit(cells[static_cast<uint32_t>(i) + static_cast<uint32_t>(j) * jstride +
                     static_cast<uint32_t>(k) * kstride]);

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Compares the device code of two builds of csrc/avr_kernels.hip kernel by kernel (no GPU needed).
+"""Compares the device code of two builds of one csrc/*.hip file kernel by kernel (no GPU needed).
 
-    make -C amrvolumerenderer_amd/csrc asm 2> before.log && cp .../avr_kernels.s before.s   # at the parent
-    make -C amrvolumerenderer_amd/csrc asm 2> after.log  && cp .../avr_kernels.s after.s    # at the head
-    python tools/compare_isa.py before.s after.s before.log after.log
+`make -C amrvolumerenderer_amd/csrc asm` writes, for every .hip source NAME.hip, its gfx950 assembly
+NAME.s and the compiler's resource-usage remarks NAME.asm.log next to it.  Keep the parent's:
+
+    make -C amrvolumerenderer_amd/csrc asm && mkdir before && cp .../csrc/*.s .../csrc/*.asm.log before   # at the parent
+    make -C amrvolumerenderer_amd/csrc asm                                                               # at the head
+    for s in before/*.s; do n=$(basename $s .s); \
+        python tools/compare_isa.py $s .../csrc/$n.s before/$n.asm.log .../csrc/$n.asm.log | tail -1; done
 
 Prints one line per kernel -- `identical` or the first differing instruction -- and exits non-zero
 if any kernel differs, if the number of kernels differs, or if a resource figure differs.
@@ -19,7 +23,7 @@ Kernels are paired by their demangled name without the parameter types; those wh
 arguments were renamed are paired by the function name and, within it, by their order in the file,
 and both names are printed so that the pairing can be read.  Resource figures: SGPRs, VGPRs,
 AGPRs, both spill counts, scratch, LDS and occupancy from the -Rpass-analysis=kernel-resource-usage
-remarks that `make asm` prints (the two logs).
+remarks that `make asm` writes (the two logs).
 """
 from __future__ import annotations
 
@@ -108,7 +112,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("before")
     ap.add_argument("after")
-    ap.add_argument("before_log", help="output of `make asm` (the resource-usage remarks)")
+    ap.add_argument("before_log", help="NAME.asm.log of `make asm` (the resource-usage remarks)")
     ap.add_argument("after_log")
     args = ap.parse_args()
 
