@@ -229,6 +229,8 @@ SIGNATURES = {
     "avr_scene_derive": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, _vp,
                                    C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_double), C.c_int,
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    "avr_scene_gradient": (C.c_int, [_vp, _vp, _vp, C.c_int, _ip, _ip, C.POINTER(C.c_double),
+                                     C.c_int]),
     "avr_blend_depthsort_f32x5": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_f32x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_u8x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),

@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 from .derive import (DerivedProgram, add_field, compile_expression, derived_fields,
                      evaluate_program, remove_field)
+from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
 
@@ -147,6 +148,25 @@ def build_scene_geometry(ctx, all_boxes: Sequence[AmrBox], local_boxes: Sequence
 
 # ---- derived fields ("Derived fields") ----------------------------------------------
 
+def _allocate_like(ctx, local: Sequence[AmrBox], rank: int) -> List[AmrBox]:
+    """New cells for the boxes `local`: one device allocation, every box its own contiguous
+    [nz, ny, nx] block on a 16-byte boundary."""
+    import torch
+    offsets, total = [], 0
+    for b in local:
+        nx, ny, nz = b.cell_dimensions
+        offsets.append(total)
+        total += (nx * ny * nz + 1) // 2 * 2        # every block starts on a 16-byte boundary
+    cells = torch.empty(total, dtype=torch.float64, device=ctx.device)
+    out_boxes = []
+    for b, begin in zip(local, offsets):
+        nx, ny, nz = b.cell_dimensions
+        out_boxes.append(AmrBox(b.min_corner, b.max_corner,
+                                cells[begin:begin + nx * ny * nz].view(nz, ny, nx), b.level,
+                                owner=rank))
+    return out_boxes
+
+
 def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"],
                  geometry: "SceneGeometry", cell_sizes, rank: int = 0, n_ranks: int = 1,
                  process_group=None, log_scale_input: bool = False,
@@ -161,7 +181,6 @@ def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"]
     and the scalar transform come from build_scene_geometry, to which log_scale_input and
     normalize_to_data_range go as load_plotfile_geometry's do (the defaults are a loaded scene's).
     The result is accepted wherever a loaded scene is."""
-    import torch
     scenes = list(scenes)
     if len(scenes) != len(program.fields):
         raise ValueError("scenes must hold one loaded scene per field of the program")
@@ -174,18 +193,7 @@ def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"]
     if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
         raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
                          "(at most 16)")
-    offsets, total = [], 0
-    for b in local:
-        nx, ny, nz = b.cell_dimensions
-        offsets.append(total)
-        total += (nx * ny * nz + 1) // 2 * 2        # every block starts on a 16-byte boundary
-    cells = torch.empty(total, dtype=torch.float64, device=ctx.device)
-    out_boxes = []
-    for b, begin in zip(local, offsets):
-        nx, ny, nz = b.cell_dimensions
-        out_boxes.append(AmrBox(b.min_corner, b.max_corner,
-                                cells[begin:begin + nx * ny * nz].view(nz, ny, nx), b.level,
-                                owner=rank))
+    out_boxes = _allocate_like(ctx, local, rank)
     to_physical = float(geometry.world_scale)
     origin = [[float(b.min_corner[a]) / to_physical for a in range(3)] for b in local]
     inputs = [ctx.create_scene(s.local_boxes, s.scalar_transform) for s in scenes]
@@ -204,49 +212,125 @@ def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"]
     return result
 
 
+# ---- gradient fields ("Gradient fields") --------------------------------------------
+
+def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, ref_ratio,
+                   rank: int = 0, n_ranks: int = 1, process_group=None,
+                   log_scale_input: bool = False,
+                   normalize_to_data_range: bool = True) -> "SceneGeometry":
+    """The difference of a scene's field along axis (0 = x, 1 = y, 2 = z) as a scene (DESIGN.md 7,
+    "Gradient fields"): central where a cell has both neighbours, one-sided where it has one, 0.0
+    where it has none; past a box's face the neighbour is the cell of the same or a coarser level
+    that holds it, or the mean of its children one level finer.  scene is a loaded (or derived)
+    scene of a plotfile whose header gives cell_sizes[l] = (dx, dy, dz) per level up to the finest
+    loaded one, prob_lo and ref_ratio; the boxes' integer indices are recovered from their corners
+    (ValueError if one is not an integer to 1e-6).  The output is allocated as derive_scene's is,
+    and statistics and the scalar transform come from build_scene_geometry with the caller's flags.
+    Every box of the scene must be on this rank: with n_ranks > 1, or fewer local boxes than
+    boxes, NotImplementedError is raised before any device work."""
+    from . import gradient
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError("axis must be 0 (x), 1 (y) or 2 (z)")
+    local = list(scene.local_boxes)
+    if n_ranks > 1 or len(local) != len(scene.all_boxes):
+        raise NotImplementedError("a gradient field needs every box of the scene on one rank: "
+                                  "ghost cells are not exchanged between ranks")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in scene.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
+    if len(ratios) != len(sizes) - 1:
+        raise ValueError("ref_ratio must hold one ratio per level transition")
+    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
+                                  scene.world_scale, prob_lo, sizes)
+    out_boxes = _allocate_like(ctx, local, rank)
+    field = ctx.create_scene(local, scene.scalar_transform)
+    out = ctx.create_scene(out_boxes, ScalarTransform())
+    try:
+        out.gradient(field, axis, index, ratios, [c[axis] for c in sizes])
+    finally:
+        out.close()
+        field.close()
+    result = build_scene_geometry(ctx, scene.all_boxes, out_boxes, scene.bounds, log_scale_input,
+                                  normalize_to_data_range, process_group, n_ranks)
+    result.world_scale = scene.world_scale
+    return result
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:
-    """One scene per variable name, for every plotfile-level function.  A name that is not a
-    registered derived field goes to plotfile.load_plotfile_geometry as it always did.  A
-    registered one is compiled, its stored fields are loaded raw (the plotfile's first variable if
-    it reads none) and derive_scene applies the caller's flags.  A stored variable is loaded once
-    per call and pair of flags, however many names need it."""
-    from . import derive
+    """One scene per variable name, for every plotfile-level function.  A name that is neither a
+    registered derived field nor a registered gradient field goes to
+    plotfile.load_plotfile_geometry as it always did.  A derived field is compiled, its fields are
+    resolved raw (the plotfile's first variable if it reads none) and derive_scene applies the
+    caller's flags.  A gradient field's input is resolved raw and gradient_scene applies the
+    caller's flags.  Resolution is recursive -- a derived field may read gradient fields, a
+    gradient field may take a derived or another gradient field -- and every name is loaded or
+    computed once per call and pair of flags, however many names need it."""
+    from . import derive, gradient
     from . import plotfile as pf
     registered = derive.derived_fields()
-    loaded = {}
+    gradients = gradient.gradient_fields()
+    resolved = {}
+    header = []
 
-    def load(name, log, normalize):
+    def plotfile_header():
+        if not header:
+            header.append(pf.PlotFileData(plotfile))
+        return header[0]
+
+    def resolve(name, log, normalize):
         key = (name, bool(log), bool(normalize))
-        if key not in loaded:
-            loaded[key] = pf.load_plotfile_geometry(ctx, plotfile, name, min_level, max_level, log,
-                                                    normalize, rank, n_ranks, process_group)
-        return loaded[key]
+        if key in resolved:
+            return resolved[key]
+        if name in gradients:
+            of, axis = gradients[name]
+            _check_variable(plotfile, plotfile_header(), of, f"gradient field '{name}'")
+            inner = resolve(of, False, True)
+            finest = max(int(b.level) for b in inner.all_boxes)
+            head = plotfile_header()
+            scene = gradient_scene(ctx, inner, axis, head.cell_size[:finest + 1], head.prob_lo,
+                                   head.ref_ratio[:finest], rank, n_ranks, process_group, log,
+                                   normalize)
+        elif name in registered:
+            program = derive.compile_field(name)
+            _check_derived_inputs(plotfile, plotfile_header(), name, program)
+            inputs = [resolve(field, False, True) for field in program.fields]
+            geometry = inputs[0] if inputs else resolve("", False, True)
+            finest = max(int(b.level) for b in geometry.all_boxes)
+            scene = derive_scene(ctx, program, inputs, geometry,
+                                 plotfile_header().cell_size[:finest + 1], rank, n_ranks,
+                                 process_group, log, normalize)
+        else:
+            scene = pf.load_plotfile_geometry(ctx, plotfile, name, min_level, max_level, log,
+                                              normalize, rank, n_ranks, process_group)
+        resolved[key] = scene
+        return scene
 
-    scenes, header = [], None
-    for name in names:
-        if name not in registered:
-            scenes.append(load(name, log_scale_input, normalize_to_data_range))
-            continue
-        program = derive.compile_field(name)
-        if header is None:
-            header = pf.PlotFileData(plotfile)
-        _check_derived_inputs(plotfile, header, name, program)
-        inputs = [load(field, False, True) for field in program.fields]
-        geometry = inputs[0] if inputs else load("", False, True)
-        finest = max(int(b.level) for b in geometry.all_boxes)
-        scenes.append(derive_scene(ctx, program, inputs, geometry, header.cell_size[:finest + 1],
-                                   rank, n_ranks, process_group, log_scale_input,
-                                   normalize_to_data_range))
-    return scenes
+    return [resolve(name, log_scale_input, normalize_to_data_range) for name in names]
+
+
+def _check_variable(plotfile: str, header, name: str, needed_by: str = "") -> None:
+    """RuntimeError unless `name` is a stored variable of the plotfile or a registered derived or
+    gradient field whose own inputs are."""
+    from . import derive, gradient
+    gradients = gradient.gradient_fields()
+    if name in gradients:
+        _check_variable(plotfile, header, gradients[name][0], f"gradient field '{name}'")
+    elif name in derive.derived_fields():
+        _check_derived_inputs(plotfile, header, name, derive.compile_field(name))
+    elif name not in header.var_names:
+        why = f" (needed by {needed_by})" if needed_by else ""
+        raise RuntimeError(f"Variable '{name}'{why} not found in plotfile '{plotfile}'.")
 
 
 def _check_derived_inputs(plotfile: str, header, name: str, program: DerivedProgram) -> None:
     for field in program.fields:
-        if field not in header.var_names:
-            raise RuntimeError(f"Variable '{field}' (needed by derived field '{name}') not found "
-                               f"in plotfile '{plotfile}'.")
+        _check_variable(plotfile, header, field, f"derived field '{name}'")
 
 
 def compute_histogram(plotfile: str, variable: Optional[str] = None, min_level: int = 0,
@@ -1388,14 +1472,10 @@ def _load_fields(plotfile: str, variables, min_level: int, max_level: int):
     if not os.path.exists(plotfile):
         raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
     from . import plotfile as pf
-    from . import derive
     header = pf.PlotFileData(plotfile)
-    registered = derive.derived_fields()
     for name in variables:
-        if name in registered:
-            _check_derived_inputs(plotfile, header, name, derive.compile_field(name))
-        elif name and name not in header.var_names:
-            raise RuntimeError(f"Variable '{name}' not found in plotfile '{plotfile}'.")
+        if name:
+            _check_variable(plotfile, header, name)
     ctx, rank, world, group = _runtime_scope()
     scenes = _load_variable_scenes(ctx, plotfile, [name or "" for name in variables], min_level,
                                    max_level, False, True, rank, world, group)

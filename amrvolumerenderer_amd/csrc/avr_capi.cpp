@@ -329,6 +329,8 @@ struct avr_context {
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
   void* axis_planes = nullptr;                 // avr_scene_axis_projection's partial planes (grow-only)
   size_t axis_planes_capacity = 0;
+  void* gradient_planes = nullptr;             // avr_scene_gradient's face planes (grow-only)
+  size_t gradient_planes_capacity = 0;
 };
 
 
@@ -860,6 +862,7 @@ void avr_context_destroy(avr_context* ctx) {
   if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
   if (ctx->colorize_scratch != nullptr) (void)hipFree(ctx->colorize_scratch);
   if (ctx->axis_planes != nullptr) (void)hipFree(ctx->axis_planes);
+  if (ctx->gradient_planes != nullptr) (void)hipFree(ctx->gradient_planes);
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -2090,6 +2093,25 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
   });
 }
 
+// The cell ranges [first byte, last byte] of the boxes a product reads and of those it writes: no
+// written box may share a byte with a read one.  Sorted by first byte, the read ranges that begin
+// at or before a written one's last byte overlap it iff the largest of their last bytes reaches it.
+typedef std::vector<std::pair<uintptr_t, uintptr_t>> ByteRanges;
+static void require_no_shared_byte(ByteRanges* read_ranges, const ByteRanges& write_ranges) {
+  std::sort(read_ranges->begin(), read_ranges->end());
+  std::vector<uintptr_t> reach(read_ranges->size());
+  for (size_t r = 0; r < read_ranges->size(); ++r) {
+    reach[r] = r == 0 ? (*read_ranges)[r].second : std::max(reach[r - 1], (*read_ranges)[r].second);
+  }
+  for (const auto& w : write_ranges) {
+    const size_t before =
+        std::upper_bound(read_ranges->begin(), read_ranges->end(),
+                         std::make_pair(w.second, UINTPTR_MAX)) - read_ranges->begin();
+    require(before == 0 || reach[before - 1] < w.first,
+            "an output box's cells overlap an input box's cells");
+  }
+}
+
 int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inputs, avr_scene* out,
                      const uint32_t* instructions, int n_instructions, const double* constants,
                      int n_constants, const double* box_origin, const double* level_cell_size,
@@ -2145,8 +2167,7 @@ int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inp
     }
     std::vector<avr::DeriveBoxDev> boxes(n_boxes);
     std::vector<uint32_t> tile_begin(1, 0u);
-    // the cell ranges [first byte, last byte] of the inputs' boxes and of the output's
-    std::vector<std::pair<uintptr_t, uintptr_t>> read_ranges, write_ranges;
+    ByteRanges read_ranges, write_ranges;  // of the inputs' boxes and of the output's
     for (size_t b = 0; b < n_boxes; ++b) {
       const avr_box& first = out->boxes[b];
       const avr_box* in[avr::kDeriveMaxFields + 1];  // the inputs, then the output
@@ -2183,20 +2204,7 @@ int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inp
       }
       avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
     }
-    // no output box may share a byte with an input box: sorted by first byte, the inputs that begin
-    // at or before an output's last byte overlap it iff the largest of their last bytes reaches it
-    std::sort(read_ranges.begin(), read_ranges.end());
-    std::vector<uintptr_t> reach(read_ranges.size());
-    for (size_t r = 0; r < read_ranges.size(); ++r) {
-      reach[r] = r == 0 ? read_ranges[r].second : std::max(reach[r - 1], read_ranges[r].second);
-    }
-    for (const auto& w : write_ranges) {
-      const size_t before =
-          std::upper_bound(read_ranges.begin(), read_ranges.end(),
-                           std::make_pair(w.second, UINTPTR_MAX)) - read_ranges.begin();
-      require(before == 0 || reach[before - 1] < w.first,
-              "an output box's cells overlap an input box's cells");
-    }
+    require_no_shared_byte(&read_ranges, write_ranges);
     for (auto& key : out->classified_key) key.clear();
     if (tile_begin.back() == 0) return AVR_OK;
     avr::DeriveProgramDev program;
@@ -2218,6 +2226,170 @@ int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inp
     args.n_fields = n_inputs;
     args.n_instructions = n_instructions;
     return avr::launch_derive(args, ctx->stream);
+  });
+}
+
+// The cells [lo, hi] of a box, or of a face's ghost slab, in some level's index space.
+struct IndexRegion {
+  int64_t lo[3], hi[3];
+};
+static bool regions_meet(const IndexRegion& a, const IndexRegion& b) {
+  for (int d = 0; d < 3; ++d) {
+    if (a.lo[d] > b.hi[d] || b.lo[d] > a.hi[d]) return false;
+  }
+  return true;
+}
+static int64_t floor_div(int64_t a, int64_t r) {
+  const int64_t q = a / r;
+  return (a % r != 0 && a < 0) ? q - 1 : q;
+}
+
+int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, int axis,
+                       const int32_t* box_index_lo, const int32_t* level_ratio,
+                       const double* level_cell_size, int n_levels) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(in != nullptr && out != nullptr && level_cell_size != nullptr, "null argument");
+    require(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
+    require(n_levels >= 1 && n_levels <= avr::kGradientMaxLevels, "n_levels must lie in [1, 16]");
+    require(n_levels == 1 || level_ratio != nullptr, "null argument");
+    avr::GradientLevelsDev levels;
+    for (int l = 0; l < avr::kGradientMaxLevels; ++l) levels.ratio[l] = 1;
+    for (int l = 0; l + 1 < n_levels; ++l) {
+      require(level_ratio[l] >= 2, "a level ratio is below 2");
+      levels.ratio[l] = level_ratio[l];
+    }
+    for (int l = 0; l < n_levels; ++l) {
+      require(std::isfinite(level_cell_size[l]) && level_cell_size[l] > 0.0,
+              "level_cell_size must be finite and positive");
+    }
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    require(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+    require_field_scene(ctx, in, n_boxes);
+    std::vector<avr::GradientBoxDev> boxes(n_boxes);
+    std::vector<IndexRegion> regions(n_boxes);
+    std::vector<uint32_t> tile_begin(1, 0u), face_begin(1, 0u);
+    ByteRanges read_ranges, write_ranges;
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& first = in->boxes[b];
+      const avr_box* fields[2] = {&first, &out->boxes[b]};
+      avr::FieldView views[2];
+      avr::GradientBoxDev& dev = boxes[b];
+      std::memset(&dev, 0, sizeof(dev));
+      const bool cells = avr::field_box_views(first, fields, 2, n_levels, views, &dev.paired);
+      dev.in = views[0].cells;
+      dev.out = const_cast<double*>(views[1].cells);
+      dev.jstride_in = views[0].jstride;
+      dev.kstride_in = views[0].kstride;
+      dev.jstride_out = views[1].jstride;
+      dev.kstride_out = views[1].kstride;
+      dev.level = first.level;
+      dev.dx = level_cell_size[first.level];
+      dev.face_begin = face_begin.back();
+      uint64_t faces = 0;
+      if (cells) {
+        dev.nx = first.dims[0];
+        dev.ny = first.dims[1];
+        dev.nz = first.dims[2];
+        for (int f = 0; f < 2; ++f) {
+          const uintptr_t begin = reinterpret_cast<uintptr_t>(views[f].cells);
+          (f == 1 ? write_ranges : read_ranges)
+              .emplace_back(begin, begin + static_cast<uintptr_t>(views[f].last) * 8 + 7);
+        }
+        for (int d = 0; d < 3; ++d) {
+          const int64_t lo = box_index_lo[b * 3 + d];
+          dev.lo[d] = box_index_lo[b * 3 + d];
+          regions[b].lo[d] = lo;
+          regions[b].hi[d] = lo + first.dims[d] - 1;
+          // the ghost indices next to the box, and their children, then stay far inside 64 bits
+          require(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
+                  "a box's index range leaves [-2^30, 2^30)");
+        }
+        faces = static_cast<uint64_t>(first.dims[(axis + 1) % 3]) *
+                static_cast<uint64_t>(first.dims[(axis + 2) % 3]);
+      }
+      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+      const uint64_t total = face_begin.back() + faces;
+      require(total < (uint64_t{1} << 30), "scene has too many cells");
+      face_begin.push_back(static_cast<uint32_t>(total));
+    }
+    require_no_shared_byte(&read_ranges, write_ranges);
+    // Per box and side the ghost slab at the box's own level, at every coarser one and one level
+    // finer; a box of one of those levels whose cells meet the slab there is a candidate.
+    std::vector<uint32_t> candidate_begin(1, 0u);
+    std::vector<int32_t> candidates;
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const int level = boxes[b].level;
+      const bool cells = boxes[b].nx > 0;
+      for (size_t c = b + 1; cells && c < n_boxes; ++c) {
+        require(boxes[c].nx <= 0 || boxes[c].level != level || !regions_meet(regions[b], regions[c]),
+                "two boxes of one level overlap in index space");
+      }
+      for (int side = 0; side < 2; ++side) {
+        if (cells) {
+          IndexRegion slab[avr::kGradientMaxLevels + 1];  // [m] at level m
+          slab[level] = regions[b];
+          slab[level].lo[axis] = slab[level].hi[axis] =
+              side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
+          for (int m = level; m > 0; --m) {
+            for (int d = 0; d < 3; ++d) {
+              slab[m - 1].lo[d] = floor_div(slab[m].lo[d], levels.ratio[m - 1]);
+              slab[m - 1].hi[d] = floor_div(slab[m].hi[d], levels.ratio[m - 1]);
+            }
+          }
+          const int finest = level + 1 < n_levels ? level + 1 : level;
+          if (finest > level) {
+            const int64_t r = levels.ratio[level];
+            for (int d = 0; d < 3; ++d) {
+              slab[finest].lo[d] = slab[level].lo[d] * r;
+              slab[finest].hi[d] = slab[level].hi[d] * r + (r - 1);
+            }
+          }
+          for (size_t c = 0; c < n_boxes; ++c) {
+            if (c == b || boxes[c].nx <= 0 || boxes[c].level > finest) continue;
+            if (regions_meet(slab[boxes[c].level], regions[c])) {
+              candidates.push_back(static_cast<int32_t>(c));
+            }
+          }
+          require(candidates.size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
+        }
+        candidate_begin.push_back(static_cast<uint32_t>(candidates.size()));
+      }
+    }
+    for (auto& key : out->classified_key) key.clear();
+    if (tile_begin.back() == 0) return AVR_OK;
+    // the face planes: [2][faces] f64, then [2][faces] presence bytes
+    const size_t n_faces = face_begin.back();
+    const size_t bytes = n_faces * 2 * (sizeof(double) + 1);
+    if (bytes > ctx->gradient_planes_capacity) {
+      avr::wait_stream(ctx->stream, "avr_scene_gradient");
+      if (ctx->gradient_planes != nullptr) (void)hipFree(ctx->gradient_planes);
+      ctx->gradient_planes = nullptr;
+      ctx->gradient_planes_capacity = 0;
+      avr::hip_check(hipMalloc(&ctx->gradient_planes, bytes), "hipMalloc(gradient planes)");
+      ctx->gradient_planes_capacity = bytes;
+    }
+    if (candidates.empty()) candidates.push_back(0);  // never read: every range is empty
+    avr::GradientArgs args{};
+    ctx->staging.begin(boxes.size() * sizeof(avr::GradientBoxDev) +
+                           (tile_begin.size() + face_begin.size() + candidate_begin.size()) *
+                               sizeof(uint32_t) +
+                           candidates.size() * sizeof(int32_t) + sizeof(levels), 6);
+    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
+    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    args.face_begin = ctx->staging.add(face_begin.data(), face_begin.size());
+    args.candidate_begin = ctx->staging.add(candidate_begin.data(), candidate_begin.size());
+    args.candidates = ctx->staging.add(candidates.data(), candidates.size());
+    args.levels = ctx->staging.add(&levels, 1);
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_levels = n_levels;
+    args.n_tiles = tile_begin.back();
+    args.n_faces = static_cast<uint32_t>(n_faces);
+    args.face_value = static_cast<double*>(ctx->gradient_planes);
+    args.face_present = reinterpret_cast<uint8_t*>(args.face_value + 2 * n_faces);
+    return avr::launch_gradient(args, axis, ctx->stream);
   });
 }
 

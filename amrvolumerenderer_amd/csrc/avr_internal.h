@@ -562,6 +562,44 @@ struct DeriveArgs {
 };
 int launch_derive(const DeriveArgs& args, void* stream);
 
+// Gradient fields (avr_gradient.hip).  Stage 1 (halo) fills, per box, the two face planes of the
+// axis: one f64 and one presence byte per face cell, the face's cells numbered along the lower of
+// the two other axes first.  Stage 2 (difference) streams every cell once and reads the planes at
+// the box's two faces.  A box as both kernels read it:
+constexpr int kGradientMaxLevels = 16;
+struct alignas(16) GradientBoxDev {
+  const double* in;
+  double* out;
+  double dx;              // the cell size of the box's level along the axis
+  int32_t jstride_in, kstride_in;    // element strides (Array4); every field spans < 2^28
+  int32_t jstride_out, kstride_out;
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t paired;         // input and output: cells 16-byte aligned, both strides even
+  uint32_t face_begin;    // first entry of the box's face planes
+  int32_t pad_[1];
+};
+static_assert(sizeof(GradientBoxDev) == 80, "GradientBoxDev: 16-byte multiple for scalar loads");
+struct GradientLevelsDev {
+  int32_t ratio[kGradientMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
+};
+struct GradientArgs {
+  const GradientBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles (difference)
+  const uint32_t* face_begin;   // n_boxes + 1: prefix sum of the boxes' face cells (halo)
+  // CSR over (box, side): the boxes whose cells can hold a ghost of that face, in scene order
+  const uint32_t* candidate_begin;  // 2 n_boxes + 1; entry 2 b + side
+  const int32_t* candidates;
+  const GradientLevelsDev* levels;
+  int32_t n_boxes, n_levels;
+  uint32_t n_tiles;
+  uint32_t n_faces;             // face cells of one side, all boxes
+  double* face_value;           // [2][n_faces]: the low planes, then the high planes
+  uint8_t* face_present;        // the same shape
+};
+int launch_gradient(const GradientArgs& args, int axis, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

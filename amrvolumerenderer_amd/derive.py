@@ -272,6 +272,11 @@ def evaluate_program(program: DerivedProgram, field_arrays: Sequence, builtins: 
 _registry: Dict[str, str] = {}
 
 
+def is_reserved_name(name: str) -> bool:
+    """Whether no registered field may take the name: a built-in, a function or a histogram weight."""
+    return name in BUILTINS or name in FUNCTIONS or name == FIELD_FUNCTION or name in RESERVED_NAMES
+
+
 def add_field(name: str, expression: str) -> DerivedProgram:
     """Registers the derived field `name` = expression for every plotfile-level function of the
     api (render, run, project, project_axis, slice, phase, profile, compute_histogram): wherever
@@ -282,16 +287,24 @@ def add_field(name: str, expression: str) -> DerivedProgram:
     the same name: the stored variable is no longer reachable under it until remove_field, neither
     by the api's functions nor by an expression -- field("density") resolves through the registry
     too, so a field called "density" cannot read the stored density (that is refused as a cycle);
-    give a field that rescales a stored variable a name of its own.
+    give a field that rescales a stored variable a name of its own.  A name that is not registered
+    here stays a field of the program; where it is a registered gradient field (gradient.py) the
+    loader supplies that, and a name registered there is refused here, as is a cycle through both.
     Returns the compiled program."""
     if not isinstance(name, str) or not name:
         raise ValueError("a derived field's name must be a non-empty string")
-    if name in BUILTINS or name in FUNCTIONS or name == FIELD_FUNCTION or name in RESERVED_NAMES:
+    if is_reserved_name(name):
         raise ValueError(f"{name!r} is a built-in, a function or a histogram weight and cannot "
                          "name a derived field")
+    from . import gradient
+    gradients = gradient.gradient_fields()
+    if name in gradients:
+        raise ValueError(f"{name!r} is a registered gradient field")
     trial = dict(_registry)
     trial[name] = expression
     program = compile_expression(name if name.isidentifier() else f"field({name!r})", trial)
+    if gradients:
+        gradient.check_no_cycle(name, trial, gradients)   # a gradient field it reads may read it
     _registry[name] = expression
     return DerivedProgram(program.fields, program.instructions, program.constants, expression)
 

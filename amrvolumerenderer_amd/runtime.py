@@ -738,6 +738,31 @@ class Scene:
             int(consts.size), as_doubles(origin), as_doubles(sizes), int(sizes.shape[0])))
         ctx.publish()
 
+    def gradient(self, field: "Scene", axis: int, box_index_lo, level_ratio,
+                 level_cell_size) -> None:
+        """avr_scene_gradient with this scene as the output: overwrites the cells of this scene's
+        boxes with the difference of `field` (a scene of the same context with the same box list)
+        along axis (0 = x, 1 = y, 2 = z).  box_index_lo: [n_boxes, 3] int32, the index of every
+        box's first cell in its level's index space; level_ratio: n_levels - 1 ints; level_cell_size:
+        n_levels float64, the cell size along the axis.  This scene's cells must not overlap the
+        field's.  Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if sizes.ndim != 1 or sizes.size < 1:
+            raise ValueError("level_cell_size must hold one value per level")
+        if ratios.ndim != 1 or ratios.size != sizes.size - 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_gradient(
+            ctx._handle, field._handle, self._handle, int(axis),
+            index.ctypes.data_as(C.POINTER(C.c_int32)), ratios.ctypes.data_as(C.POINTER(C.c_int32)),
+            sizes.ctypes.data_as(C.POINTER(C.c_double)), int(sizes.size)))
+        ctx.publish()
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

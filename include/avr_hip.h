@@ -1159,6 +1159,33 @@ int avr_scene_derive(avr_context *ctx, const avr_scene *const *inputs, int n_inp
                      int n_constants, const double *box_origin, const double *level_cell_size,
                      int n_levels);
 
+/* ---- gradient fields ("Gradient fields") ------------------------------------------ */
+
+/* The difference of the raw f64 cells of `in` along axis (0 = x, 1 = y, 2 = z), per cell, written
+ * to `out`: scenes of ctx with the same box list as avr_scene_joint_histogram requires (equal dims
+ * and levels; each keeps its own strides), `out` over cells the caller allocated.  The boxes are
+ * the leaves of an AMR hierarchy: box b of level l starts at the integer index box_index_lo[3 * b
+ * ..] (host) of level l's index space, level_ratio[l] >= 2 (host, n_levels - 1 entries) refines
+ * level l to l + 1 (an index maps down by floor division, a cell's children are r * G + (0 .. r -
+ * 1)^3) and level_cell_size[l] (host, n_levels <= 16) is a cell's size along the axis.  A cell's
+ * neighbour on either side is the next cell of its box or, past the box's face, the ghost G (a
+ * level-l index): the cell of the box of the highest level m <= l that contains G mapped to level
+ * m; else (0.0 + the r^3 children of G, added in ascending k, then j, then i) / f64(r^3) if every
+ * child lies in a box of level l + 1; else the neighbour is absent.  With own value f, low
+ * neighbour L and high neighbour H:  both (H - L) / (2.0 * dx); only H (H - f) / dx; only L
+ * (f - L) / dx; neither 0.0 -- binary64, round to nearest, nothing fused, the division correctly
+ * rounded; non-finite values propagate.  Only the cells of the scene's boxes are read, never the
+ * rest of an allocation a box is a view of.  No atomics: equal arguments give equal bits.
+ * Everything is checked on the host before any device work: AVR_ERR_INVALID_ARGUMENT for an axis
+ * outside 0..2, scenes that are not congruent, a box level >= n_levels, n_levels > 16, a ratio
+ * below 2, a cell size that is not finite and positive, a box index range outside [-2^30, 2^30),
+ * an output box whose cells share a byte with an input box's, and two boxes of one level that
+ * overlap in index space -- and `out` is untouched.  Asynchronous on the context's stream; the
+ * context keeps the face planes (grow-only scratch); invalidates out's cached classification. */
+int avr_scene_gradient(avr_context *ctx, const avr_scene *in, avr_scene *out, int axis,
+                       const int32_t *box_index_lo, const int32_t *level_ratio,
+                       const double *level_cell_size, int n_levels);
+
 #ifdef __cplusplus
 }
 #endif
