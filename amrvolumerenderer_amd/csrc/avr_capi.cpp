@@ -16,8 +16,7 @@
 #include <vector>
 
 #include "../../include/avr_hip_debug.h"
-#include "avr_cell_tiles.h"
-#include "avr_field_boxes.h"
+#include "avr_field_plans.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
 
@@ -273,6 +272,33 @@ class StagingRing {
   size_t used_ = 0;
 };
 
+// A device buffer that only grows: a call that fits in it re-uses it.
+struct DeviceBuffer {
+  void* data = nullptr;
+  size_t capacity = 0;
+
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  ~DeviceBuffer() { release(); }
+
+  // Room for `bytes`.  Growing waits for `stream` first (`what` names the wait): work queued there
+  // may still use the old block.  Returns whether it grew -- the old contents are then gone.
+  bool reserve(size_t bytes, hipStream_t stream, const char* what, const char* malloc_label) {
+    if (bytes <= capacity) return false;
+    wait_stream(stream, what);
+    release();
+    hip_check(hipMalloc(&data, bytes), malloc_label);
+    capacity = bytes;
+    return true;
+  }
+  void release() {
+    if (data != nullptr) (void)hipFree(data);
+    data = nullptr;
+    capacity = 0;
+  }
+};
+
 }  // namespace
 }  // namespace avr
 
@@ -283,30 +309,18 @@ struct avr_scene {
   // classified volumes (allocated on first use, grow-only; a frame of the same scene never
   // reallocates): two let the classify pass of frame i+1 overlap the march of frame i, the third
   // lets it run ahead so that neither stream waits for the other's launch (avr_renderer)
-  void* classified[AVR_CLASSIFIED_SLOTS] = {};
-  size_t classified_capacity[AVR_CLASSIFIED_SLOTS] = {};
+  avr::DeviceBuffer classified[AVR_CLASSIFIED_SLOTS];
   int device = 0;
   // optional re-use of a slot's classified volume across frames (avr_scene_set_classification_cache):
   // what the classify pass of the slot's current contents depended on
   bool cache_classification = false;
   std::vector<uint64_t> classified_key[AVR_CLASSIFIED_SLOTS];
 
-  ~avr_scene() {
-    for (void* buffer : classified) {
-      if (buffer != nullptr) (void)hipFree(buffer);
-    }
-  }
   uint8_t* classified_slot(int slot, size_t bytes, hipStream_t stream) {
-    if (bytes > classified_capacity[slot]) {
-      avr::wait_stream(stream, "classified_slot");
-      if (classified[slot] != nullptr) (void)hipFree(classified[slot]);
-      classified[slot] = nullptr;
-      classified_capacity[slot] = 0;
+    if (classified[slot].reserve(bytes, stream, "classified_slot", "hipMalloc(classified)")) {
       classified_key[slot].clear();
-      avr::hip_check(hipMalloc(&classified[slot], bytes), "hipMalloc(classified)");
-      classified_capacity[slot] = bytes;
     }
-    return static_cast<uint8_t*>(classified[slot]);
+    return static_cast<uint8_t*>(classified[slot].data);
   }
 };
 
@@ -324,13 +338,10 @@ struct avr_context {
   bool classify_stream_stores = false;         // context_set_classify_stream_stores
   bool fold_whole_grid = false;                // context_set_fold_whole_grid
   uint64_t* march_counters = nullptr;          // diagnostics (avr_context_set_march_counters)
-  void* max_layers = nullptr;                  // layer of avr_paint_box_max (grow-only)
-  size_t max_layers_capacity = 0;
+  avr::DeviceBuffer max_layers;                // layer of avr_paint_box_max
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
-  void* axis_planes = nullptr;                 // avr_scene_axis_projection's partial planes (grow-only)
-  size_t axis_planes_capacity = 0;
-  void* gradient_planes = nullptr;             // avr_scene_gradient's face planes (grow-only)
-  size_t gradient_planes_capacity = 0;
+  avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
+  avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
 };
 
 
@@ -859,10 +870,10 @@ void avr_context_destroy(avr_context* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->own_stream != nullptr) (void)hipStreamSynchronize(ctx->own_stream);
   ctx->staging.release();
-  if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
+  ctx->max_layers.release();
   if (ctx->colorize_scratch != nullptr) (void)hipFree(ctx->colorize_scratch);
-  if (ctx->axis_planes != nullptr) (void)hipFree(ctx->axis_planes);
-  if (ctx->gradient_planes != nullptr) (void)hipFree(ctx->gradient_planes);
+  ctx->axis_planes.release();
+  ctx->gradient_planes.release();
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -1013,15 +1024,9 @@ int paint_and_fold_one_box(avr_context* ctx, int phases, const avr_box* box,
   require(params.width > 0 && params.height > 0, "image width and height must be positive");
   const int64_t n_pixels = static_cast<int64_t>(params.width) * params.height;
   const size_t bytes = static_cast<size_t>(n_pixels) * 5 * sizeof(float);
-  if (bytes > ctx->max_layers_capacity) {
-    avr::wait_stream(ctx->stream, "avr_paint_box (scratch layer)");
-    if (ctx->max_layers != nullptr) (void)hipFree(ctx->max_layers);
-    ctx->max_layers = nullptr;
-    ctx->max_layers_capacity = 0;
-    avr::hip_check(hipMalloc(&ctx->max_layers, bytes), "hipMalloc(scratch layer)");
-    ctx->max_layers_capacity = bytes;
-  }
-  float* layer = static_cast<float*>(ctx->max_layers);
+  ctx->max_layers.reserve(bytes, ctx->stream, "avr_paint_box (scratch layer)",
+                          "hipMalloc(scratch layer)");
+  float* layer = static_cast<float*>(ctx->max_layers.data);
   OneBoxRun run;
   const int status = paint_one_box(ctx, phases, static_cast<avr::FrameKind>(out.index()), box,
                                    transform, params, camera, layer, samples_out, &run);
@@ -1747,31 +1752,45 @@ int avr_assemble_rows_own(avr_context* ctx, const avr_frame_plan* plan, const vo
   });
 }
 
+namespace {
+// The box records and tile prefix of a scan over every cell of `scene`, staged on the context.
+struct StagedCells {
+  avr::FramePlan plan;
+  const avr::BoxDev* boxes_dev = nullptr;
+  const uint32_t* tiles_dev = nullptr;
+};
+void stage_cells(avr_context* ctx, const avr_scene* scene, const avr_scalar_transform& transform,
+                 StagedCells* cells) {
+  avr::FramePlan& plan = cells->plan;
+  avr::plan_cells(scene->boxes.data(), static_cast<int>(scene->boxes.size()), transform, &plan);
+  ctx->staging.begin(plan.boxes.size() * sizeof(avr::BoxDev) +
+                         plan.classify_tile_begin.size() * sizeof(uint32_t), 2);
+  cells->boxes_dev = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+  cells->tiles_dev =
+      ctx->staging.add(plan.classify_tile_begin.data(), plan.classify_tile_begin.size());
+  ctx->staging.commit(ctx->stream);
+}
+}  // namespace
+
 int avr_scene_scalar_stats(avr_context* ctx, const avr_scene* scene, double stats_host[3],
                            int64_t* finite_count_host) {
   return guarded([&]() -> int {
     bind_device(ctx);
     require(scene != nullptr && stats_host != nullptr && finite_count_host != nullptr,
             "null argument");
-    avr::FramePlan plan;
-    avr::plan_cells(scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
-                    &plan);
-    const uint32_t n_tiles = plan.classify_tile_begin.back();
     void* scratch = nullptr;
     avr::hip_check(hipMalloc(&scratch, (static_cast<size_t>(avr::kScanWorkgroups) + 1) * 32),
                    "hipMalloc");
     struct { double lo, hi, lo_positive; long long finite; } result{};
     int status = AVR_OK;
     try {
-      ctx->staging.begin(plan.boxes.size() * sizeof(avr::BoxDev) +
-                             plan.classify_tile_begin.size() * sizeof(uint32_t), 2);
-      const avr::BoxDev* boxes_dev = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-      const uint32_t* tiles_dev =
-          ctx->staging.add(plan.classify_tile_begin.data(), plan.classify_tile_begin.size());
-      ctx->staging.commit(ctx->stream);
+      StagedCells cells;
+      stage_cells(ctx, scene, scene->transform, &cells);
       char* out_dev = static_cast<char*>(scratch) + static_cast<size_t>(avr::kScanWorkgroups) * 32;
-      status = avr::launch_scalar_stats(boxes_dev, tiles_dev, static_cast<int>(plan.boxes.size()),
-                                        n_tiles, scratch, out_dev, ctx->stream);
+      status = avr::launch_scalar_stats(cells.boxes_dev, cells.tiles_dev,
+                                        static_cast<int>(cells.plan.boxes.size()),
+                                        cells.plan.classify_tile_begin.back(), scratch, out_dev,
+                                        ctx->stream);
       if (status == AVR_OK) {
         avr::hip_check(hipMemcpyAsync(&result, out_dev, sizeof(result), hipMemcpyDeviceToHost,
                                       ctx->stream), "hipMemcpyAsync");
@@ -1813,40 +1832,22 @@ int avr_scene_histogram(avr_context* ctx, const avr_scene* scene,
     require(bin_count > 0, "binCount must be positive");  // SceneBuilder.cpp:448-450
     const float width = range_max - range_min;
     if (!(width > 0.0f) || !std::isfinite(width)) return AVR_OK;  // (:470-472): empty histogram
-    avr::FramePlan plan;
-    avr::plan_cells(scene->boxes.data(), static_cast<int>(scene->boxes.size()), *transform, &plan);
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::BoxDev) +
-                           plan.classify_tile_begin.size() * sizeof(uint32_t), 2);
-    const avr::BoxDev* boxes_dev = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    const uint32_t* tiles_dev =
-        ctx->staging.add(plan.classify_tile_begin.data(), plan.classify_tile_begin.size());
-    ctx->staging.commit(ctx->stream);
-    return avr::launch_histogram(plan.consts, boxes_dev, tiles_dev,
-                                 static_cast<int>(plan.boxes.size()),
-                                 plan.classify_tile_begin.back(), range_min, range_max, bin_count,
-                                 counts_dev, ctx->stream);
+    StagedCells cells;
+    stage_cells(ctx, scene, *transform, &cells);
+    return avr::launch_histogram(cells.plan.consts, cells.boxes_dev, cells.tiles_dev,
+                                 static_cast<int>(cells.plan.boxes.size()),
+                                 cells.plan.classify_tile_begin.back(), range_min, range_max,
+                                 bin_count, counts_dev, ctx->stream);
   });
 }
 
 // A field of a product over several scenes that share a box list (the box rules themselves are
-// avr_field_boxes.h's).
+// avr_field_boxes.h's).  The five entry points below have one shape: bind the device, refuse null
+// handles and device pointers, then scenes of another context or box count, then make the plan
+// (avr_field_plans.h: every rule on the plain arguments and the boxes), then stage and launch.
 static void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t n_boxes) {
   require(field->ctx == ctx && field->boxes.size() == n_boxes,
           "the scenes must belong to the context and hold the same number of boxes");
-}
-
-// n + 1 finite, strictly increasing edges; returns n / (e[n] - e[0]), or 0 if that is not finite
-static double joint_histogram_axis(const double* edges, int n, const char* axis) {
-  const std::string name(axis);
-  require(edges != nullptr, (name + "_edges is null").c_str());
-  require(n >= 1 && n <= avr::kJointHistogramMaxBins,
-          (name + " bin count must lie in [1, 1024]").c_str());
-  for (int i = 0; i <= n; ++i) {
-    require(std::isfinite(edges[i]), (name + "_edges must be finite").c_str());
-    require(i == 0 || edges[i - 1] < edges[i], (name + "_edges must be strictly increasing").c_str());
-  }
-  const double scale = static_cast<double>(n) / (edges[n] - edges[0]);
-  return std::isfinite(scale) ? scale : 0.0;
 }
 
 int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const avr_scene* scene_y,
@@ -1857,63 +1858,25 @@ int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const 
     bind_device(ctx);
     require(scene_x != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
     require(scene_s == nullptr || sums_dev != nullptr, "a summed field needs sums_dev");
-    avr::JointHistogramArgs args{};
-    args.x_scale = joint_histogram_axis(x_edges, nx, "x");
-    if (scene_y != nullptr) {
-      args.y_scale = joint_histogram_axis(y_edges, ny, "y");
-    } else {
-      require(ny == 1, "without scene_y there is one y bin");
-    }
-    require(static_cast<int64_t>(nx) * ny <= avr::kJointHistogramMaxCells,
-            "the histogram has more than 2^20 bins");
-    require(n_levels >= 1 && n_levels <= avr::kJointHistogramMaxLevels,
-            "n_levels must lie in [1, 16]");
-    const avr_scene* fields[3] = {scene_x, scene_y != nullptr ? scene_y : scene_x,
-                                  scene_s != nullptr ? scene_s : scene_x};
     const size_t n_boxes = scene_x->boxes.size();
-    for (const avr_scene* field : fields) require_field_scene(ctx, field, n_boxes);
-    std::vector<avr::JointBoxDev> boxes(n_boxes);
-    std::vector<uint32_t> tile_begin(1, 0u);
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const avr_box& first = scene_x->boxes[b];
-      const avr_box* in[3] = {&first, &fields[1]->boxes[b], &fields[2]->boxes[b]};
-      avr::FieldView views[3];
-      avr::JointBoxDev& dev = boxes[b];
-      std::memset(&dev, 0, sizeof(dev));
-      const bool cells = avr::field_box_views(first, in, 3, n_levels, views, &dev.paired);
-      dev.level = first.level;
-      for (int f = 0; f < 3; ++f) {
-        dev.cells[f] = views[f].cells;
-        dev.jstride[f] = views[f].jstride;
-        dev.kstride[f] = views[f].kstride;
-      }
-      if (cells) {
-        dev.nx = first.dims[0];
-        dev.ny = first.dims[1];
-        dev.nz = first.dims[2];
-      }
-      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+    for (const avr_scene* field : {scene_x, scene_y, scene_s}) {
+      if (field != nullptr) require_field_scene(ctx, field, n_boxes);
     }
-    if (tile_begin.back() == 0) return AVR_OK;
+    const avr::JointHistogramPlan plan = avr::plan_joint_histogram(
+        scene_x->boxes.data(), scene_y != nullptr ? scene_y->boxes.data() : nullptr,
+        scene_s != nullptr ? scene_s->boxes.data() : nullptr, n_boxes, x_edges, nx, y_edges, ny,
+        n_levels);
+    if (plan.tile_begin.back() == 0) return AVR_OK;
     const size_t n_x = static_cast<size_t>(nx) + 1;
     const size_t n_y = scene_y != nullptr ? static_cast<size_t>(ny) + 1 : 0;
-    ctx->staging.begin(boxes.size() * sizeof(avr::JointBoxDev) +
-                           tile_begin.size() * sizeof(uint32_t) + (n_x + n_y) * sizeof(double), 4);
-    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
-    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::JointBoxDev) +
+                           plan.tile_begin.size() * sizeof(uint32_t) + (n_x + n_y) * sizeof(double), 4);
+    avr::JointHistogramArgs args = plan.args;
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
     args.x_edges = ctx->staging.add(x_edges, n_x);
     args.y_edges = n_y != 0 ? ctx->staging.add(y_edges, n_y) : nullptr;
     ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_tiles = tile_begin.back();
-    args.nx = nx;
-    args.ny = ny;
-    args.x_lo = x_edges[0];
-    args.x_hi = x_edges[nx];
-    if (scene_y != nullptr) {
-      args.y_lo = y_edges[0];
-      args.y_hi = y_edges[ny];
-    }
     args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
     args.sums = scene_s != nullptr ? sums_dev : nullptr;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
@@ -1928,42 +1891,13 @@ int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origi
     bind_device(ctx);
     require(scene != nullptr && origin != nullptr && du != nullptr && dv != nullptr &&
                 value != nullptr && level != nullptr && box != nullptr, "null argument");
-    require(width > 0 && height > 0, "image width and height must be positive");
-    require(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
-            "image has more than 2^31-1 pixels");
-    avr::SlicePlaneDev plane;
-    for (int a = 0; a < 3; ++a) {
-      require(std::isfinite(origin[a]) && std::isfinite(du[a]) && std::isfinite(dv[a]),
-              "slice plane must be finite");
-      plane.origin[a] = origin[a];
-      plane.du[a] = du[a];
-      plane.dv[a] = dv[a];
-    }
-    const size_t n_boxes = scene->boxes.size();
-    std::vector<avr::SliceBoxDev> boxes(n_boxes);
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const avr_box& in = scene->boxes[b];
-      avr::SliceBoxDev& dev = boxes[b];
-      std::memset(&dev, 0, sizeof(dev));
-      dev.global_index = global_index != nullptr ? global_index[b] : static_cast<int32_t>(b);
-      require(in.level >= 0 && in.level <= 127, "box level must lie in [0, 127]");
-      dev.level = in.level;
-      if (avr::box_is_empty(in)) continue;  // holds no point
-      const avr::FieldView view = avr::field_view(in);
-      for (int a = 0; a < 3; ++a) {
-        dev.minc[a] = in.min_corner[a];
-        dev.maxc[a] = in.max_corner[a];
-        dev.n[a] = in.dims[a];
-      }
-      dev.cells = view.cells;
-      dev.jstride = view.jstride;
-      dev.kstride = view.kstride;
-    }
-    ctx->staging.begin(boxes.size() * sizeof(avr::SliceBoxDev), 1);
-    const avr::SliceBoxDev* boxes_dev = ctx->staging.add(boxes.data(), boxes.size());
+    const avr::SlicePlan plan = avr::plan_slice(scene->boxes.data(), scene->boxes.size(),
+                                                global_index, origin, du, dv, width, height);
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::SliceBoxDev), 1);
+    const avr::SliceBoxDev* boxes_dev = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
     ctx->staging.commit(ctx->stream);
-    return avr::launch_slice(plane, width, height, boxes_dev, static_cast<int>(n_boxes), value,
-                             level, box, ctx->stream);
+    return avr::launch_slice(plan.plane, width, height, boxes_dev,
+                             static_cast<int>(plan.boxes.size()), value, level, box, ctx->stream);
   });
 }
 
@@ -1989,88 +1923,32 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
                 integral_dev != nullptr && length_dev != nullptr, "null argument");
     require((scene_w != nullptr) == (weight_dev != nullptr),
             "weight_dev is given exactly when scene_w is");
-    require(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
-    require(width > 0 && height > 0, "image width and height must be positive");
-    require(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
-            "image has more than 2^31-1 pixels");
-    require(std::isfinite(origin_uv[0]) && std::isfinite(origin_uv[1]) && std::isfinite(du) &&
-                std::isfinite(dv), "the window must be finite");
-    require(n_levels >= 1 && n_levels <= avr::kAxisMaxLevels, "n_levels must lie in [1, 16]");
-    for (int l = 0; l < n_levels; ++l) require(std::isfinite(level_dl[l]), "level_dl must be finite");
     const bool weighted = scene_w != nullptr;
-    const avr_scene* fields[2] = {scene_f, weighted ? scene_w : scene_f};
     const size_t n_boxes = scene_f->boxes.size();
-    for (const avr_scene* field : fields) require_field_scene(ctx, field, n_boxes);
-    const int axis_u = (axis + 1) % 3, axis_v = (axis + 2) % 3;
-    std::vector<avr::AxisBoxDev> boxes(n_boxes);
-    std::vector<avr::AxisPlaneDev> planes(n_boxes);
-    std::vector<uint32_t> tile_begin(1, 0u);
-    uint64_t entries = 0;
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const avr_box& first = scene_f->boxes[b];
-      const avr_box* in[2] = {&first, &fields[1]->boxes[b]};
-      avr::FieldView views[2];
-      avr::AxisBoxDev& dev = boxes[b];
-      avr::AxisPlaneDev& plane = planes[b];
-      std::memset(&dev, 0, sizeof(dev));
-      std::memset(&plane, 0, sizeof(plane));
-      const bool cells = avr::field_box_views(first, in, 2, n_levels, views, &dev.paired);
-      dev.cells_f = views[0].cells;
-      dev.jstride_f = views[0].jstride;
-      dev.kstride_f = views[0].kstride;
-      dev.cells_w = views[1].cells;
-      dev.jstride_w = views[1].jstride;
-      dev.kstride_w = views[1].kstride;
-      uint32_t tiles = 0;
-      dev.plane_begin = plane.plane_begin = static_cast<uint32_t>(entries);
-      if (cells) {
-        require(std::isfinite(first.min_corner[axis_u]) && std::isfinite(first.max_corner[axis_u]) &&
-                    std::isfinite(first.min_corner[axis_v]) && std::isfinite(first.max_corner[axis_v]),
-                "box corners must be finite");
-        dev.nx = first.dims[0];
-        dev.ny = first.dims[1];
-        dev.nz = first.dims[2];
-        tiles = avr::axis_projection_tiles(axis, dev.nx, dev.ny, dev.nz);
-        plane.min_u = first.min_corner[axis_u];
-        plane.max_u = first.max_corner[axis_u];
-        plane.min_v = first.min_corner[axis_v];
-        plane.max_v = first.max_corner[axis_v];
-        plane.dl = level_dl[first.level];
-        plane.n_u = first.dims[axis_u];
-        plane.n_v = first.dims[axis_v];
-        plane.segments = (first.dims[axis] + avr::kAxisSegment - 1) / avr::kAxisSegment;
-        entries += static_cast<uint64_t>(plane.n_u) * static_cast<uint64_t>(plane.n_v) *
-                   static_cast<uint64_t>(plane.segments);
-      }
-      avr::append_tiles(&tile_begin, tiles);
-      require(entries < (uint64_t{1} << 31), "scene has too many cells");
-    }
+    require_field_scene(ctx, scene_f, n_boxes);
+    if (weighted) require_field_scene(ctx, scene_w, n_boxes);
+    const avr::AxisProjectionPlan plan = avr::plan_axis_projection(
+        scene_f->boxes.data(), weighted ? scene_w->boxes.data() : nullptr, n_boxes, axis, origin_uv,
+        du, dv, width, height, level_dl, n_levels);
     // the partial planes: S [entries] f64, Wt [entries] f64 (with a weight), n [entries] u32
-    const size_t n_entries = static_cast<size_t>(entries);
-    const size_t bytes = n_entries * (weighted ? 20 : 12);
-    if (bytes > ctx->axis_planes_capacity) {
-      avr::wait_stream(ctx->stream, "avr_scene_axis_projection");
-      if (ctx->axis_planes != nullptr) (void)hipFree(ctx->axis_planes);
-      ctx->axis_planes = nullptr;
-      ctx->axis_planes_capacity = 0;
-      avr::hip_check(hipMalloc(&ctx->axis_planes, bytes), "hipMalloc(axis planes)");
-      ctx->axis_planes_capacity = bytes;
-    }
-    double* plane_s = static_cast<double*>(ctx->axis_planes);
+    const size_t n_entries = plan.entries;
+    ctx->axis_planes.reserve(n_entries * (weighted ? 20 : 12), ctx->stream,
+                             "avr_scene_axis_projection", "hipMalloc(axis planes)");
+    double* plane_s = static_cast<double*>(ctx->axis_planes.data);
     double* plane_w = weighted ? plane_s + n_entries : nullptr;
     uint32_t* plane_n = reinterpret_cast<uint32_t*>(plane_s + (weighted ? 2 : 1) * n_entries);
 
-    ctx->staging.begin(boxes.size() * sizeof(avr::AxisBoxDev) +
-                           planes.size() * sizeof(avr::AxisPlaneDev) +
-                           tile_begin.size() * sizeof(uint32_t), 3);
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::AxisBoxDev) +
+                           plan.planes.size() * sizeof(avr::AxisPlaneDev) +
+                           plan.tile_begin.size() * sizeof(uint32_t), 3);
     avr::AxisReduceArgs reduce{};
     avr::AxisGatherArgs gather{};
-    reduce.boxes = ctx->staging.add(boxes.data(), boxes.size());
-    gather.boxes = ctx->staging.add(planes.data(), planes.size());
-    reduce.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
+    reduce.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    gather.boxes = ctx->staging.add(plan.planes.data(), plan.planes.size());
+    reduce.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
     ctx->staging.commit(ctx->stream);
     reduce.n_boxes = static_cast<int32_t>(n_boxes);
-    reduce.n_tiles = tile_begin.back();
+    reduce.n_tiles = plan.tile_begin.back();
     reduce.plane_s = plane_s;
     reduce.plane_w = plane_w;
     reduce.plane_n = plane_n;
@@ -2093,25 +1971,6 @@ int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const 
   });
 }
 
-// The cell ranges [first byte, last byte] of the boxes a product reads and of those it writes: no
-// written box may share a byte with a read one.  Sorted by first byte, the read ranges that begin
-// at or before a written one's last byte overlap it iff the largest of their last bytes reaches it.
-typedef std::vector<std::pair<uintptr_t, uintptr_t>> ByteRanges;
-static void require_no_shared_byte(ByteRanges* read_ranges, const ByteRanges& write_ranges) {
-  std::sort(read_ranges->begin(), read_ranges->end());
-  std::vector<uintptr_t> reach(read_ranges->size());
-  for (size_t r = 0; r < read_ranges->size(); ++r) {
-    reach[r] = r == 0 ? (*read_ranges)[r].second : std::max(reach[r - 1], (*read_ranges)[r].second);
-  }
-  for (const auto& w : write_ranges) {
-    const size_t before =
-        std::upper_bound(read_ranges->begin(), read_ranges->end(),
-                         std::make_pair(w.second, UINTPTR_MAX)) - read_ranges->begin();
-    require(before == 0 || reach[before - 1] < w.first,
-            "an output box's cells overlap an input box's cells");
-  }
-}
-
 int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inputs, avr_scene* out,
                      const uint32_t* instructions, int n_instructions, const double* constants,
                      int n_constants, const double* box_origin, const double* level_cell_size,
@@ -2120,128 +1979,34 @@ int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inp
     bind_device(ctx);
     require(out != nullptr && instructions != nullptr && level_cell_size != nullptr,
             "null argument");
-    require(n_inputs >= 0 && n_inputs <= avr::kDeriveMaxFields, "n_inputs must lie in [0, 6]");
+    avr::require_derive_input_count(n_inputs);
     require(n_inputs == 0 || inputs != nullptr, "null argument");
-    require(n_instructions >= 1 && n_instructions <= avr::kDeriveMaxInstructions,
-            "n_instructions must lie in [1, 64]");
-    require(n_constants >= 0 && n_constants <= avr::kDeriveMaxConstants,
-            "n_constants must lie in [0, 16]");
-    require(n_constants == 0 || constants != nullptr, "null argument");
-    require(n_levels >= 1 && n_levels <= avr::kDeriveMaxLevels, "n_levels must lie in [1, 16]");
-    // the program: known opcodes, operands in range, a stack that neither underflows nor holds more
-    // than 8 values, exactly one value at the end
-    int depth = 0;
-    for (int pc = 0; pc < n_instructions; ++pc) {
-      const uint32_t op = instructions[pc] & 0xffu, operand = instructions[pc] >> 8;
-      require(op < avr::kDeriveOpCount, "unknown opcode");
-      int pops = 2;
-      if (op <= avr::kDeriveBuiltin) {
-        pops = 0;
-        const uint32_t limit = op == avr::kDeriveConst ? static_cast<uint32_t>(n_constants)
-                               : op == avr::kDeriveField ? static_cast<uint32_t>(n_inputs)
-                                                         : avr::kDeriveBuiltinCount;
-        require(operand < limit, "an operand index is out of range");
-      } else {
-        require(operand == 0, "an operator takes no operand");
-        if (op == avr::kDeriveNeg || op == avr::kDeriveSquare || op == avr::kDeriveSqrt ||
-            op == avr::kDeriveAbs) {
-          pops = 1;
-        } else if (op == avr::kDeriveWhere) {
-          pops = 3;
-        }
-      }
-      require(depth >= pops, "the program underflows its stack");
-      depth += 1 - pops;
-      require(depth <= avr::kDeriveMaxDepth, "the program's stack is deeper than 8");
-    }
-    require(depth == 1, "the program must end with exactly one value");
-    for (int l = 0; l < n_levels * 3; ++l) {
-      require(std::isfinite(level_cell_size[l]), "level_cell_size must be finite");
-    }
     require(out->ctx == ctx, "the scenes must belong to the context");
     const size_t n_boxes = out->boxes.size();
-    require(n_boxes == 0 || box_origin != nullptr, "null argument");
+    const avr_box* input_boxes[avr::kDeriveMaxFields] = {};
     for (int f = 0; f < n_inputs; ++f) {
       require(inputs[f] != nullptr, "null argument");
       require_field_scene(ctx, inputs[f], n_boxes);
+      input_boxes[f] = inputs[f]->boxes.data();
     }
-    std::vector<avr::DeriveBoxDev> boxes(n_boxes);
-    std::vector<uint32_t> tile_begin(1, 0u);
-    ByteRanges read_ranges, write_ranges;  // of the inputs' boxes and of the output's
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const avr_box& first = out->boxes[b];
-      const avr_box* in[avr::kDeriveMaxFields + 1];  // the inputs, then the output
-      for (int f = 0; f < n_inputs; ++f) in[f] = &inputs[f]->boxes[b];
-      in[n_inputs] = &first;
-      avr::FieldView views[avr::kDeriveMaxFields + 1];
-      avr::DeriveBoxDev& dev = boxes[b];
-      std::memset(&dev, 0, sizeof(dev));
-      const bool cells = avr::field_box_views(first, in, n_inputs + 1, n_levels, views, &dev.paired);
-      dev.level = first.level;
-      for (int f = 0; f <= n_inputs; ++f) {
-        const bool is_out = f == n_inputs;
-        const int slot = is_out ? avr::kDeriveMaxFields : f;
-        if (is_out) {
-          dev.out = const_cast<double*>(views[f].cells);
-        } else {
-          dev.cells[f] = views[f].cells;
-        }
-        dev.jstride[slot] = views[f].jstride;
-        dev.kstride[slot] = views[f].kstride;
-        if (!cells) continue;
-        const uintptr_t begin = reinterpret_cast<uintptr_t>(views[f].cells);
-        (is_out ? write_ranges : read_ranges)
-            .emplace_back(begin, begin + static_cast<uintptr_t>(views[f].last) * 8 + 7);
-      }
-      for (int a = 0; a < 3; ++a) {
-        require(std::isfinite(box_origin[b * 3 + a]), "box_origin must be finite");
-        dev.origin[a] = box_origin[b * 3 + a];
-      }
-      if (cells) {
-        dev.nx = first.dims[0];
-        dev.ny = first.dims[1];
-        dev.nz = first.dims[2];
-      }
-      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
-    }
-    require_no_shared_byte(&read_ranges, write_ranges);
+    const avr::DerivePlan plan = avr::plan_derive(
+        input_boxes, n_inputs, out->boxes.data(), n_boxes, instructions, n_instructions, constants,
+        n_constants, box_origin, level_cell_size, n_levels);
     for (auto& key : out->classified_key) key.clear();
-    if (tile_begin.back() == 0) return AVR_OK;
-    avr::DeriveProgramDev program;
-    std::memset(&program, 0, sizeof(program));
-    std::memcpy(program.code, instructions, static_cast<size_t>(n_instructions) * sizeof(uint32_t));
-    if (n_constants != 0) {
-      std::memcpy(program.constants, constants, static_cast<size_t>(n_constants) * sizeof(double));
-    }
-    std::memcpy(program.cell_size, level_cell_size, static_cast<size_t>(n_levels) * 3 * sizeof(double));
+    if (plan.tile_begin.back() == 0) return AVR_OK;
     avr::DeriveArgs args{};
-    ctx->staging.begin(boxes.size() * sizeof(avr::DeriveBoxDev) +
-                           tile_begin.size() * sizeof(uint32_t) + sizeof(program), 3);
-    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
-    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
-    args.program = ctx->staging.add(&program, 1);
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::DeriveBoxDev) +
+                           plan.tile_begin.size() * sizeof(uint32_t) + sizeof(plan.program), 3);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
+    args.program = ctx->staging.add(&plan.program, 1);
     ctx->staging.commit(ctx->stream);
     args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_tiles = tile_begin.back();
+    args.n_tiles = plan.tile_begin.back();
     args.n_fields = n_inputs;
     args.n_instructions = n_instructions;
     return avr::launch_derive(args, ctx->stream);
   });
-}
-
-// The cells [lo, hi] of a box, or of a face's ghost slab, in some level's index space.
-struct IndexRegion {
-  int64_t lo[3], hi[3];
-};
-static bool regions_meet(const IndexRegion& a, const IndexRegion& b) {
-  for (int d = 0; d < 3; ++d) {
-    if (a.lo[d] > b.hi[d] || b.lo[d] > a.hi[d]) return false;
-  }
-  return true;
-}
-static int64_t floor_div(int64_t a, int64_t r) {
-  const int64_t q = a / r;
-  return (a % r != 0 && a < 0) ? q - 1 : q;
 }
 
 int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, int axis,
@@ -2250,144 +2015,36 @@ int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, in
   return guarded([&]() -> int {
     bind_device(ctx);
     require(in != nullptr && out != nullptr && level_cell_size != nullptr, "null argument");
-    require(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
-    require(n_levels >= 1 && n_levels <= avr::kGradientMaxLevels, "n_levels must lie in [1, 16]");
-    require(n_levels == 1 || level_ratio != nullptr, "null argument");
-    avr::GradientLevelsDev levels;
-    for (int l = 0; l < avr::kGradientMaxLevels; ++l) levels.ratio[l] = 1;
-    for (int l = 0; l + 1 < n_levels; ++l) {
-      require(level_ratio[l] >= 2, "a level ratio is below 2");
-      levels.ratio[l] = level_ratio[l];
-    }
-    for (int l = 0; l < n_levels; ++l) {
-      require(std::isfinite(level_cell_size[l]) && level_cell_size[l] > 0.0,
-              "level_cell_size must be finite and positive");
-    }
     require(out->ctx == ctx, "the scenes must belong to the context");
     const size_t n_boxes = out->boxes.size();
-    require(n_boxes == 0 || box_index_lo != nullptr, "null argument");
     require_field_scene(ctx, in, n_boxes);
-    std::vector<avr::GradientBoxDev> boxes(n_boxes);
-    std::vector<IndexRegion> regions(n_boxes);
-    std::vector<uint32_t> tile_begin(1, 0u), face_begin(1, 0u);
-    ByteRanges read_ranges, write_ranges;
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const avr_box& first = in->boxes[b];
-      const avr_box* fields[2] = {&first, &out->boxes[b]};
-      avr::FieldView views[2];
-      avr::GradientBoxDev& dev = boxes[b];
-      std::memset(&dev, 0, sizeof(dev));
-      const bool cells = avr::field_box_views(first, fields, 2, n_levels, views, &dev.paired);
-      dev.in = views[0].cells;
-      dev.out = const_cast<double*>(views[1].cells);
-      dev.jstride_in = views[0].jstride;
-      dev.kstride_in = views[0].kstride;
-      dev.jstride_out = views[1].jstride;
-      dev.kstride_out = views[1].kstride;
-      dev.level = first.level;
-      dev.dx = level_cell_size[first.level];
-      dev.face_begin = face_begin.back();
-      uint64_t faces = 0;
-      if (cells) {
-        dev.nx = first.dims[0];
-        dev.ny = first.dims[1];
-        dev.nz = first.dims[2];
-        for (int f = 0; f < 2; ++f) {
-          const uintptr_t begin = reinterpret_cast<uintptr_t>(views[f].cells);
-          (f == 1 ? write_ranges : read_ranges)
-              .emplace_back(begin, begin + static_cast<uintptr_t>(views[f].last) * 8 + 7);
-        }
-        for (int d = 0; d < 3; ++d) {
-          const int64_t lo = box_index_lo[b * 3 + d];
-          dev.lo[d] = box_index_lo[b * 3 + d];
-          regions[b].lo[d] = lo;
-          regions[b].hi[d] = lo + first.dims[d] - 1;
-          // the ghost indices next to the box, and their children, then stay far inside 64 bits
-          require(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
-                  "a box's index range leaves [-2^30, 2^30)");
-        }
-        faces = static_cast<uint64_t>(first.dims[(axis + 1) % 3]) *
-                static_cast<uint64_t>(first.dims[(axis + 2) % 3]);
-      }
-      avr::append_tiles(&tile_begin, cells ? avr::cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
-      const uint64_t total = face_begin.back() + faces;
-      require(total < (uint64_t{1} << 30), "scene has too many cells");
-      face_begin.push_back(static_cast<uint32_t>(total));
-    }
-    require_no_shared_byte(&read_ranges, write_ranges);
-    // Per box and side the ghost slab at the box's own level, at every coarser one and one level
-    // finer; a box of one of those levels whose cells meet the slab there is a candidate.
-    std::vector<uint32_t> candidate_begin(1, 0u);
-    std::vector<int32_t> candidates;
-    for (size_t b = 0; b < n_boxes; ++b) {
-      const int level = boxes[b].level;
-      const bool cells = boxes[b].nx > 0;
-      for (size_t c = b + 1; cells && c < n_boxes; ++c) {
-        require(boxes[c].nx <= 0 || boxes[c].level != level || !regions_meet(regions[b], regions[c]),
-                "two boxes of one level overlap in index space");
-      }
-      for (int side = 0; side < 2; ++side) {
-        if (cells) {
-          IndexRegion slab[avr::kGradientMaxLevels + 1];  // [m] at level m
-          slab[level] = regions[b];
-          slab[level].lo[axis] = slab[level].hi[axis] =
-              side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
-          for (int m = level; m > 0; --m) {
-            for (int d = 0; d < 3; ++d) {
-              slab[m - 1].lo[d] = floor_div(slab[m].lo[d], levels.ratio[m - 1]);
-              slab[m - 1].hi[d] = floor_div(slab[m].hi[d], levels.ratio[m - 1]);
-            }
-          }
-          const int finest = level + 1 < n_levels ? level + 1 : level;
-          if (finest > level) {
-            const int64_t r = levels.ratio[level];
-            for (int d = 0; d < 3; ++d) {
-              slab[finest].lo[d] = slab[level].lo[d] * r;
-              slab[finest].hi[d] = slab[level].hi[d] * r + (r - 1);
-            }
-          }
-          for (size_t c = 0; c < n_boxes; ++c) {
-            if (c == b || boxes[c].nx <= 0 || boxes[c].level > finest) continue;
-            if (regions_meet(slab[boxes[c].level], regions[c])) {
-              candidates.push_back(static_cast<int32_t>(c));
-            }
-          }
-          require(candidates.size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
-        }
-        candidate_begin.push_back(static_cast<uint32_t>(candidates.size()));
-      }
-    }
+    avr::GradientPlan plan =
+        avr::plan_gradient(in->boxes.data(), out->boxes.data(), n_boxes, axis, box_index_lo,
+                           level_ratio, level_cell_size, n_levels);
     for (auto& key : out->classified_key) key.clear();
-    if (tile_begin.back() == 0) return AVR_OK;
+    if (plan.tile_begin.back() == 0) return AVR_OK;
     // the face planes: [2][faces] f64, then [2][faces] presence bytes
-    const size_t n_faces = face_begin.back();
-    const size_t bytes = n_faces * 2 * (sizeof(double) + 1);
-    if (bytes > ctx->gradient_planes_capacity) {
-      avr::wait_stream(ctx->stream, "avr_scene_gradient");
-      if (ctx->gradient_planes != nullptr) (void)hipFree(ctx->gradient_planes);
-      ctx->gradient_planes = nullptr;
-      ctx->gradient_planes_capacity = 0;
-      avr::hip_check(hipMalloc(&ctx->gradient_planes, bytes), "hipMalloc(gradient planes)");
-      ctx->gradient_planes_capacity = bytes;
-    }
-    if (candidates.empty()) candidates.push_back(0);  // never read: every range is empty
+    const size_t n_faces = plan.face_begin.back();
+    ctx->gradient_planes.reserve(n_faces * 2 * (sizeof(double) + 1), ctx->stream,
+                                 "avr_scene_gradient", "hipMalloc(gradient planes)");
+    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
     avr::GradientArgs args{};
-    ctx->staging.begin(boxes.size() * sizeof(avr::GradientBoxDev) +
-                           (tile_begin.size() + face_begin.size() + candidate_begin.size()) *
-                               sizeof(uint32_t) +
-                           candidates.size() * sizeof(int32_t) + sizeof(levels), 6);
-    args.boxes = ctx->staging.add(boxes.data(), boxes.size());
-    args.tile_begin = ctx->staging.add(tile_begin.data(), tile_begin.size());
-    args.face_begin = ctx->staging.add(face_begin.data(), face_begin.size());
-    args.candidate_begin = ctx->staging.add(candidate_begin.data(), candidate_begin.size());
-    args.candidates = ctx->staging.add(candidates.data(), candidates.size());
-    args.levels = ctx->staging.add(&levels, 1);
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::GradientBoxDev) +
+                           (plan.tile_begin.size() + plan.face_begin.size() +
+                            plan.candidate_begin.size()) * sizeof(uint32_t) +
+                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 6);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
+    args.face_begin = ctx->staging.add(plan.face_begin.data(), plan.face_begin.size());
+    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
+    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
     ctx->staging.commit(ctx->stream);
     args.n_boxes = static_cast<int32_t>(n_boxes);
     args.n_levels = n_levels;
-    args.n_tiles = tile_begin.back();
+    args.n_tiles = plan.tile_begin.back();
     args.n_faces = static_cast<uint32_t>(n_faces);
-    args.face_value = static_cast<double*>(ctx->gradient_planes);
+    args.face_value = static_cast<double*>(ctx->gradient_planes.data);
     args.face_present = reinterpret_cast<uint8_t*>(args.face_value + 2 * n_faces);
     return avr::launch_gradient(args, axis, ctx->stream);
   });

@@ -1,0 +1,486 @@
+// The host plans of the field products (slice images, the joint histogram, on-axis projections,
+// derived fields, gradient fields): everything a call works out from its arguments before the
+// first HIP call -- the argument rules, the box table, the tile prefix and the product's own
+// tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
+// rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
+// std::invalid_argument with the message the C ABI reports, and fills vectors and PODs that the
+// entry point stages (tests/cxx/field_plans_test.cpp).  Pointers the ABI refuses as "null
+// argument" whatever the other arguments are have been checked by the entry point.
+#ifndef AVR_FIELD_PLANS_H
+#define AVR_FIELD_PLANS_H
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "avr_cell_tiles.h"
+#include "avr_field_boxes.h"
+#include "avr_internal.h"
+
+namespace avr {
+
+inline void require_image_size(int width, int height) {
+  require_box(width > 0 && height > 0, "image width and height must be positive");
+  require_box(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
+              "image has more than 2^31-1 pixels");
+}
+
+// ---- slice images -------------------------------------------------------------------------
+struct SlicePlan {
+  SlicePlaneDev plane;
+  std::vector<SliceBoxDev> boxes;  // a box without cells stays zeroed but for index and level
+};
+// global_index (may be null): what the box image holds for box b; by default b.
+inline SlicePlan plan_slice(const avr_box* boxes, size_t n_boxes, const int32_t* global_index,
+                            const double origin[3], const double du[3], const double dv[3],
+                            int width, int height) {
+  require_image_size(width, height);
+  SlicePlan plan;
+  for (int a = 0; a < 3; ++a) {
+    require_box(std::isfinite(origin[a]) && std::isfinite(du[a]) && std::isfinite(dv[a]),
+                "slice plane must be finite");
+    plan.plane.origin[a] = origin[a];
+    plan.plane.du[a] = du[a];
+    plan.plane.dv[a] = dv[a];
+  }
+  plan.boxes.resize(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& in = boxes[b];
+    SliceBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    dev.global_index = global_index != nullptr ? global_index[b] : static_cast<int32_t>(b);
+    require_box(in.level >= 0 && in.level <= 127, "box level must lie in [0, 127]");
+    dev.level = in.level;
+    if (box_is_empty(in)) continue;  // holds no point
+    const FieldView view = field_view(in);
+    for (int a = 0; a < 3; ++a) {
+      dev.minc[a] = in.min_corner[a];
+      dev.maxc[a] = in.max_corner[a];
+      dev.n[a] = in.dims[a];
+    }
+    dev.cells = view.cells;
+    dev.jstride = view.jstride;
+    dev.kstride = view.kstride;
+  }
+  return plan;
+}
+
+// ---- joint histogram ----------------------------------------------------------------------
+// n + 1 finite, strictly increasing edges; returns n / (e[n] - e[0]), or 0 if that is not finite
+inline double joint_histogram_axis(const double* edges, int n, const char* axis) {
+  const std::string name(axis);
+  require_box(edges != nullptr, (name + "_edges is null").c_str());
+  require_box(n >= 1 && n <= kJointHistogramMaxBins,
+              (name + " bin count must lie in [1, 1024]").c_str());
+  for (int i = 0; i <= n; ++i) {
+    require_box(std::isfinite(edges[i]), (name + "_edges must be finite").c_str());
+    require_box(i == 0 || edges[i - 1] < edges[i],
+                (name + "_edges must be strictly increasing").c_str());
+  }
+  const double scale = static_cast<double>(n) / (edges[n] - edges[0]);
+  return std::isfinite(scale) ? scale : 0.0;
+}
+
+struct JointHistogramPlan {
+  std::vector<JointBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  JointHistogramArgs args;  // the counts, bounds and scales; its device pointers are left null
+};
+// y and s (may be null): the boxes of the second axis' field and of the summed field; an absent
+// field repeats x.
+inline JointHistogramPlan plan_joint_histogram(const avr_box* x, const avr_box* y, const avr_box* s,
+                                               size_t n_boxes, const double* x_edges, int nx,
+                                               const double* y_edges, int ny, int n_levels) {
+  JointHistogramPlan plan;
+  plan.args = JointHistogramArgs{};
+  plan.args.x_scale = joint_histogram_axis(x_edges, nx, "x");
+  if (y != nullptr) {
+    plan.args.y_scale = joint_histogram_axis(y_edges, ny, "y");
+  } else {
+    require_box(ny == 1, "without scene_y there is one y bin");
+  }
+  require_box(static_cast<int64_t>(nx) * ny <= kJointHistogramMaxCells,
+              "the histogram has more than 2^20 bins");
+  require_box(n_levels >= 1 && n_levels <= kJointHistogramMaxLevels,
+              "n_levels must lie in [1, 16]");
+  const avr_box* fields[3] = {x, y != nullptr ? y : x, s != nullptr ? s : x};
+  plan.boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = x[b];
+    const avr_box* in[3] = {&first, &fields[1][b], &fields[2][b]};
+    FieldView views[3];
+    JointBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, in, 3, n_levels, views, &dev.paired);
+    dev.level = first.level;
+    for (int f = 0; f < 3; ++f) {
+      dev.cells[f] = views[f].cells;
+      dev.jstride[f] = views[f].jstride;
+      dev.kstride[f] = views[f].kstride;
+    }
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.nx = nx;
+  plan.args.ny = ny;
+  plan.args.x_lo = x_edges[0];
+  plan.args.x_hi = x_edges[nx];
+  if (y != nullptr) {
+    plan.args.y_lo = y_edges[0];
+    plan.args.y_hi = y_edges[ny];
+  }
+  return plan;
+}
+
+// ---- on-axis projection -------------------------------------------------------------------
+struct AxisProjectionPlan {
+  std::vector<AxisBoxDev> boxes;     // as the reduction reads them
+  std::vector<AxisPlaneDev> planes;  // as the gather reads them
+  std::vector<uint32_t> tile_begin;
+  uint32_t entries = 0;  // of the partial planes, all boxes: columns x segments, below 2^31
+};
+// w (may be null): the boxes of the weight field; without one it repeats f.
+inline AxisProjectionPlan plan_axis_projection(const avr_box* f, const avr_box* w, size_t n_boxes,
+                                               int axis, const double origin_uv[2], double du,
+                                               double dv, int width, int height,
+                                               const double* level_dl, int n_levels) {
+  require_box(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
+  require_image_size(width, height);
+  require_box(std::isfinite(origin_uv[0]) && std::isfinite(origin_uv[1]) && std::isfinite(du) &&
+                  std::isfinite(dv), "the window must be finite");
+  require_box(n_levels >= 1 && n_levels <= kAxisMaxLevels, "n_levels must lie in [1, 16]");
+  for (int l = 0; l < n_levels; ++l) {
+    require_box(std::isfinite(level_dl[l]), "level_dl must be finite");
+  }
+  const int axis_u = (axis + 1) % 3, axis_v = (axis + 2) % 3;
+  AxisProjectionPlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.planes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  uint64_t entries = 0;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = f[b];
+    const avr_box* in[2] = {&first, w != nullptr ? &w[b] : &first};
+    FieldView views[2];
+    AxisBoxDev& dev = plan.boxes[b];
+    AxisPlaneDev& plane = plan.planes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    std::memset(&plane, 0, sizeof(plane));
+    const bool cells = field_box_views(first, in, 2, n_levels, views, &dev.paired);
+    dev.cells_f = views[0].cells;
+    dev.jstride_f = views[0].jstride;
+    dev.kstride_f = views[0].kstride;
+    dev.cells_w = views[1].cells;
+    dev.jstride_w = views[1].jstride;
+    dev.kstride_w = views[1].kstride;
+    uint32_t tiles = 0;
+    dev.plane_begin = plane.plane_begin = static_cast<uint32_t>(entries);
+    if (cells) {
+      require_box(std::isfinite(first.min_corner[axis_u]) && std::isfinite(first.max_corner[axis_u]) &&
+                      std::isfinite(first.min_corner[axis_v]) &&
+                      std::isfinite(first.max_corner[axis_v]),
+                  "box corners must be finite");
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      tiles = axis_projection_tiles(axis, dev.nx, dev.ny, dev.nz);
+      plane.min_u = first.min_corner[axis_u];
+      plane.max_u = first.max_corner[axis_u];
+      plane.min_v = first.min_corner[axis_v];
+      plane.max_v = first.max_corner[axis_v];
+      plane.dl = level_dl[first.level];
+      plane.n_u = first.dims[axis_u];
+      plane.n_v = first.dims[axis_v];
+      plane.segments = (first.dims[axis] + kAxisSegment - 1) / kAxisSegment;
+      entries += static_cast<uint64_t>(plane.n_u) * static_cast<uint64_t>(plane.n_v) *
+                 static_cast<uint64_t>(plane.segments);
+    }
+    append_tiles(&plan.tile_begin, tiles);
+    require_box(entries < (uint64_t{1} << 31), "scene has too many cells");
+  }
+  plan.entries = static_cast<uint32_t>(entries);
+  return plan;
+}
+
+// ---- shared by the products that write a scene: no written cell is also read --------------
+// The cell ranges [first byte, last byte] of the boxes a product reads and of those it writes: no
+// written box may share a byte with a read one.  Sorted by first byte, the read ranges that begin
+// at or before a written one's last byte overlap it iff the largest of their last bytes reaches it.
+typedef std::vector<std::pair<uintptr_t, uintptr_t>> ByteRanges;
+inline void append_byte_range(ByteRanges* ranges, const FieldView& view) {
+  const uintptr_t begin = reinterpret_cast<uintptr_t>(view.cells);
+  ranges->emplace_back(begin, begin + static_cast<uintptr_t>(view.last) * 8 + 7);
+}
+inline void require_no_shared_byte(ByteRanges* read_ranges, const ByteRanges& write_ranges) {
+  std::sort(read_ranges->begin(), read_ranges->end());
+  std::vector<uintptr_t> reach(read_ranges->size());
+  for (size_t r = 0; r < read_ranges->size(); ++r) {
+    reach[r] = r == 0 ? (*read_ranges)[r].second : std::max(reach[r - 1], (*read_ranges)[r].second);
+  }
+  for (const auto& w : write_ranges) {
+    const size_t before =
+        std::upper_bound(read_ranges->begin(), read_ranges->end(),
+                         std::make_pair(w.second, UINTPTR_MAX)) - read_ranges->begin();
+    require_box(before == 0 || reach[before - 1] < w.first,
+                "an output box's cells overlap an input box's cells");
+  }
+}
+
+// ---- derived fields -----------------------------------------------------------------------
+// The entry point applies it before it reads the array of input scenes, the plan first of all.
+inline void require_derive_input_count(int n_inputs) {
+  require_box(n_inputs >= 0 && n_inputs <= kDeriveMaxFields, "n_inputs must lie in [0, 6]");
+}
+
+// The program: known opcodes, operands in range, a stack that neither underflows nor holds more
+// than 8 values, exactly one value at the end.
+inline void verify_derive_program(const uint32_t* instructions, int n_instructions, int n_constants,
+                                  int n_inputs) {
+  int depth = 0;
+  for (int pc = 0; pc < n_instructions; ++pc) {
+    const uint32_t op = instructions[pc] & 0xffu, operand = instructions[pc] >> 8;
+    require_box(op < kDeriveOpCount, "unknown opcode");
+    int pops = 2;
+    if (op <= kDeriveBuiltin) {
+      pops = 0;
+      const uint32_t limit = op == kDeriveConst   ? static_cast<uint32_t>(n_constants)
+                             : op == kDeriveField ? static_cast<uint32_t>(n_inputs)
+                                                  : kDeriveBuiltinCount;
+      require_box(operand < limit, "an operand index is out of range");
+    } else {
+      require_box(operand == 0, "an operator takes no operand");
+      if (op == kDeriveNeg || op == kDeriveSquare || op == kDeriveSqrt || op == kDeriveAbs) {
+        pops = 1;
+      } else if (op == kDeriveWhere) {
+        pops = 3;
+      }
+    }
+    require_box(depth >= pops, "the program underflows its stack");
+    depth += 1 - pops;
+    require_box(depth <= kDeriveMaxDepth, "the program's stack is deeper than 8");
+  }
+  require_box(depth == 1, "the program must end with exactly one value");
+}
+
+struct DerivePlan {
+  std::vector<DeriveBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  DeriveProgramDev program;
+};
+// inputs: n_inputs box lists of n_boxes boxes each; out: the boxes written, the reference of the
+// box rules.
+inline DerivePlan plan_derive(const avr_box* const* inputs, int n_inputs, const avr_box* out,
+                              size_t n_boxes, const uint32_t* instructions, int n_instructions,
+                              const double* constants, int n_constants, const double* box_origin,
+                              const double* level_cell_size, int n_levels) {
+  require_derive_input_count(n_inputs);
+  require_box(n_instructions >= 1 && n_instructions <= kDeriveMaxInstructions,
+              "n_instructions must lie in [1, 64]");
+  require_box(n_constants >= 0 && n_constants <= kDeriveMaxConstants,
+              "n_constants must lie in [0, 16]");
+  require_box(n_constants == 0 || constants != nullptr, "null argument");
+  require_box(n_levels >= 1 && n_levels <= kDeriveMaxLevels, "n_levels must lie in [1, 16]");
+  verify_derive_program(instructions, n_instructions, n_constants, n_inputs);
+  for (int l = 0; l < n_levels * 3; ++l) {
+    require_box(std::isfinite(level_cell_size[l]), "level_cell_size must be finite");
+  }
+  require_box(n_boxes == 0 || box_origin != nullptr, "null argument");
+  DerivePlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;  // of the inputs' boxes and of the output's
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = out[b];
+    const avr_box* in[kDeriveMaxFields + 1];  // the inputs, then the output
+    for (int f = 0; f < n_inputs; ++f) in[f] = &inputs[f][b];
+    in[n_inputs] = &first;
+    FieldView views[kDeriveMaxFields + 1];
+    DeriveBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, in, n_inputs + 1, n_levels, views, &dev.paired);
+    dev.level = first.level;
+    for (int f = 0; f <= n_inputs; ++f) {
+      const bool is_out = f == n_inputs;
+      const int slot = is_out ? kDeriveMaxFields : f;
+      if (is_out) {
+        dev.out = const_cast<double*>(views[f].cells);
+      } else {
+        dev.cells[f] = views[f].cells;
+      }
+      dev.jstride[slot] = views[f].jstride;
+      dev.kstride[slot] = views[f].kstride;
+      if (cells) append_byte_range(is_out ? &write_ranges : &read_ranges, views[f]);
+    }
+    for (int a = 0; a < 3; ++a) {
+      require_box(std::isfinite(box_origin[b * 3 + a]), "box_origin must be finite");
+      dev.origin[a] = box_origin[b * 3 + a];
+    }
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  require_no_shared_byte(&read_ranges, write_ranges);
+  std::memset(&plan.program, 0, sizeof(plan.program));
+  std::memcpy(plan.program.code, instructions, static_cast<size_t>(n_instructions) * sizeof(uint32_t));
+  if (n_constants != 0) {
+    std::memcpy(plan.program.constants, constants, static_cast<size_t>(n_constants) * sizeof(double));
+  }
+  std::memcpy(plan.program.cell_size, level_cell_size,
+              static_cast<size_t>(n_levels) * 3 * sizeof(double));
+  return plan;
+}
+
+// ---- gradient fields ----------------------------------------------------------------------
+// The cells [lo, hi] of a box, or of a face's ghost slab, in some level's index space.
+struct IndexRegion {
+  int64_t lo[3], hi[3];
+};
+inline bool regions_meet(const IndexRegion& a, const IndexRegion& b) {
+  for (int d = 0; d < 3; ++d) {
+    if (a.lo[d] > b.hi[d] || b.lo[d] > a.hi[d]) return false;
+  }
+  return true;
+}
+inline int64_t floor_div(int64_t a, int64_t r) {
+  const int64_t q = a / r;
+  return (a % r != 0 && a < 0) ? q - 1 : q;
+}
+
+struct GradientPlan {
+  std::vector<GradientBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  std::vector<uint32_t> face_begin;  // n_boxes + 1: prefix sum of the boxes' face cells
+  // CSR over (box, side), entry 2 b + side: the boxes that can hold a ghost of that face
+  std::vector<uint32_t> candidate_begin;
+  std::vector<int32_t> candidates;   // empty when no face has a neighbour
+  GradientLevelsDev levels;
+};
+// box_index_lo: per box the index of its first cell in its level's index space (3 per box);
+// level_ratio[l]: level l -> l + 1.
+inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t n_boxes, int axis,
+                                  const int32_t* box_index_lo, const int32_t* level_ratio,
+                                  const double* level_cell_size, int n_levels) {
+  require_box(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
+  require_box(n_levels >= 1 && n_levels <= kGradientMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  GradientPlan plan;
+  GradientLevelsDev& levels = plan.levels;
+  for (int l = 0; l < kGradientMaxLevels; ++l) levels.ratio[l] = 1;
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
+    levels.ratio[l] = level_ratio[l];
+  }
+  for (int l = 0; l < n_levels; ++l) {
+    require_box(std::isfinite(level_cell_size[l]) && level_cell_size[l] > 0.0,
+                "level_cell_size must be finite and positive");
+  }
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  std::vector<GradientBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  std::vector<IndexRegion> regions(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  plan.face_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = in[b];
+    const avr_box* fields[2] = {&first, &out[b]};
+    FieldView views[2];
+    GradientBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, fields, 2, n_levels, views, &dev.paired);
+    dev.in = views[0].cells;
+    dev.out = const_cast<double*>(views[1].cells);
+    dev.jstride_in = views[0].jstride;
+    dev.kstride_in = views[0].kstride;
+    dev.jstride_out = views[1].jstride;
+    dev.kstride_out = views[1].kstride;
+    dev.level = first.level;
+    dev.dx = level_cell_size[first.level];
+    dev.face_begin = plan.face_begin.back();
+    uint64_t faces = 0;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&read_ranges, views[0]);
+      append_byte_range(&write_ranges, views[1]);
+      for (int d = 0; d < 3; ++d) {
+        const int64_t lo = box_index_lo[b * 3 + d];
+        dev.lo[d] = box_index_lo[b * 3 + d];
+        regions[b].lo[d] = lo;
+        regions[b].hi[d] = lo + first.dims[d] - 1;
+        // the ghost indices next to the box, and their children, then stay far inside 64 bits
+        require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
+                    "a box's index range leaves [-2^30, 2^30)");
+      }
+      faces = static_cast<uint64_t>(first.dims[(axis + 1) % 3]) *
+              static_cast<uint64_t>(first.dims[(axis + 2) % 3]);
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+    const uint64_t total = plan.face_begin.back() + faces;
+    require_box(total < (uint64_t{1} << 30), "scene has too many cells");
+    plan.face_begin.push_back(static_cast<uint32_t>(total));
+  }
+  require_no_shared_byte(&read_ranges, write_ranges);
+  // Per box and side the ghost slab at the box's own level, at every coarser one and one level
+  // finer; a box of one of those levels whose cells meet the slab there is a candidate.
+  std::vector<int32_t>& candidates = plan.candidates;
+  plan.candidate_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const int level = boxes[b].level;
+    const bool cells = boxes[b].nx > 0;
+    for (size_t c = b + 1; cells && c < n_boxes; ++c) {
+      require_box(boxes[c].nx <= 0 || boxes[c].level != level || !regions_meet(regions[b], regions[c]),
+                  "two boxes of one level overlap in index space");
+    }
+    for (int side = 0; side < 2; ++side) {
+      if (cells) {
+        IndexRegion slab[kGradientMaxLevels + 1];  // [m] at level m
+        slab[level] = regions[b];
+        slab[level].lo[axis] = slab[level].hi[axis] =
+            side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
+        for (int m = level; m > 0; --m) {
+          for (int d = 0; d < 3; ++d) {
+            slab[m - 1].lo[d] = floor_div(slab[m].lo[d], levels.ratio[m - 1]);
+            slab[m - 1].hi[d] = floor_div(slab[m].hi[d], levels.ratio[m - 1]);
+          }
+        }
+        const int finest = level + 1 < n_levels ? level + 1 : level;
+        if (finest > level) {
+          const int64_t r = levels.ratio[level];
+          for (int d = 0; d < 3; ++d) {
+            slab[finest].lo[d] = slab[level].lo[d] * r;
+            slab[finest].hi[d] = slab[level].hi[d] * r + (r - 1);
+          }
+        }
+        for (size_t c = 0; c < n_boxes; ++c) {
+          if (c == b || boxes[c].nx <= 0 || boxes[c].level > finest) continue;
+          if (regions_meet(slab[boxes[c].level], regions[c])) {
+            candidates.push_back(static_cast<int32_t>(c));
+          }
+        }
+        require_box(candidates.size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
+      }
+      plan.candidate_begin.push_back(static_cast<uint32_t>(candidates.size()));
+    }
+  }
+  return plan;
+}
+
+}  // namespace avr
+
+#endif
