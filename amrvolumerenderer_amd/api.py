@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 from .derive import (DerivedProgram, add_field, compile_expression, derived_fields,
                      evaluate_program, remove_field)
+from .clumps import add_clump_field, clump_fields, remove_clump_field
 from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
@@ -260,21 +261,126 @@ def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, 
     return result
 
 
+# ---- clumps ("Clumps") ---------------------------------------------------------------
+
+def clump_scene(ctx, scene: "SceneGeometry", lower: float, upper: float, cell_sizes, prob_lo,
+                ref_ratio, rank: int = 0, n_ranks: int = 1, process_group=None,
+                log_scale_input: bool = False, normalize_to_data_range: bool = True):
+    """The clumps of a scene's field as a label scene ("Clumps"): the connected
+    components of the cells whose raw value v satisfies lower <= v <= upper (either bound may be
+    infinite; a NaN is never selected), adjacent through the six faces inside a box and, past a
+    box's face, through the cell of the same or a coarser level that holds the ghost.  Returns
+    (SceneGeometry, n_clumps): the scene holds f64(label) in 1..n_clumps for a selected cell,
+    numbered in ascending order of each clump's smallest cell ordinal (scene order of the boxes,
+    then k, j, i), and 0.0 otherwise.  scene, cell_sizes, prob_lo and ref_ratio as gradient_scene
+    takes them; the output is allocated as derive_scene's is, and statistics and the scalar
+    transform come from build_scene_geometry with the caller's flags.  Every box of the scene must
+    be on this rank: with n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is
+    raised before any device work."""
+    from . import clumps as clump_rules
+    from . import gradient
+    lower, upper = clump_rules.check_bounds(lower, upper)
+    local = list(scene.local_boxes)
+    if n_ranks > 1 or len(local) != len(scene.all_boxes):
+        raise NotImplementedError("clumps need every box of the scene on one rank: "
+                                  "labels are not merged between ranks")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in scene.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
+    if len(ratios) != len(sizes) - 1:
+        raise ValueError("ref_ratio must hold one ratio per level transition")
+    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
+                                  scene.world_scale, prob_lo, sizes)
+    out_boxes = _allocate_like(ctx, local, rank)
+    field = ctx.create_scene(local, scene.scalar_transform)
+    out = ctx.create_scene(out_boxes, ScalarTransform())
+    try:
+        count = out.clumps(field, lower, upper, index, ratios)
+        ctx.synchronize()
+        n_clumps = int(count.item())
+    finally:
+        out.close()
+        field.close()
+    result = build_scene_geometry(ctx, scene.all_boxes, out_boxes, scene.bounds, log_scale_input,
+                                  normalize_to_data_range, process_group, n_ranks)
+    result.world_scale = scene.world_scale
+    return result, n_clumps
+
+
+def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float = math.inf,
+           fields: Sequence[str] = (), min_level: int = 0, max_level: int = -1) -> dict:
+    """The clumps of a plotfile's variable ("Clumps"), on cuda:0: the connected
+    components of the uncovered cells of the loaded levels whose raw value lies in [lower, upper],
+    with their sizes.  variable and every name of fields is a stored variable or a registered
+    derived, gradient or clump field.  Returns a dict: n (the number of clumps, numbered 1..n by
+    smallest cell ordinal; entry c - 1 of every array belongs to clump c), cells_by_level int64
+    [L, n], cells int64 [n], volume float64 [n] = sum_l vol[l] * f64(cells[l]) (level ascending
+    from +0.0), integrals {name: float64 [n]} = sum_l vol[l] * sums[l], the volume integral of
+    each requested field over each clump, taken over the cells where that field is finite,
+    outside (labels that are no clump's; 0) and nonfinite (cells of clumps where a requested
+    field is not finite, over all fields).  n == 0 gives empty arrays."""
+    import numpy as np
+    from . import clumps as clump_rules
+    from . import plotfile as pf
+    lower, upper = clump_rules.check_bounds(lower, upper)
+    names = [str(name) for name in fields]
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
+                                                            min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    labels, n = clump_scene(ctx, scenes[0], lower, upper, header.cell_size[:n_levels],
+                            header.prob_lo, header.ref_ratio[:n_levels - 1], rank, world, group)
+    cells_by_level = np.zeros((n_levels, n), dtype=np.int64)
+    sums = {name: np.zeros((n_levels, n), dtype=np.float64) for name in names}
+    outside = nonfinite = 0
+    if n > 0:
+        if n * n_levels >= clump_rules.TABLE_MAX_ENTRIES:
+            raise ValueError("too many clumps for one table: n * levels must stay below 2^28")
+        label_scene = ctx.create_scene(labels.local_boxes, labels.scalar_transform)
+        try:
+            counted, _, totals = label_scene.clump_table(n, n_levels)
+            ctx.synchronize()
+            cells_by_level = counted.cpu().numpy()
+            outside = int(totals[0].item())
+            for name, scene in zip(names, scenes[1:]):
+                field = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
+                try:
+                    _, summed, totals = label_scene.clump_table(n, n_levels, field)
+                    ctx.synchronize()
+                finally:
+                    field.close()
+                sums[name] = summed.cpu().numpy()
+                nonfinite += int(totals[1].item())
+        finally:
+            label_scene.close()
+    return {"n": n, "cells_by_level": cells_by_level, "cells": cells_by_level.sum(axis=0),
+            "volume": clump_rules.clump_volumes(cells_by_level, volumes),
+            "integrals": {name: clump_rules.clump_integrals(sums[name], volumes)
+                          for name in names},
+            "outside": outside, "nonfinite": nonfinite}
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:
-    """One scene per variable name, for every plotfile-level function.  A name that is neither a
-    registered derived field nor a registered gradient field goes to
+    """One scene per variable name, for every plotfile-level function.  A registered clump field
+    is resolved like a gradient field (its input raw, clump_scene applies the caller's flags).  A
+    name that is neither a registered derived field nor a registered gradient field goes to
     plotfile.load_plotfile_geometry as it always did.  A derived field is compiled, its fields are
     resolved raw (the plotfile's first variable if it reads none) and derive_scene applies the
     caller's flags.  A gradient field's input is resolved raw and gradient_scene applies the
     caller's flags.  Resolution is recursive -- a derived field may read gradient fields, a
     gradient field may take a derived or another gradient field -- and every name is loaded or
     computed once per call and pair of flags, however many names need it."""
+    from . import clumps as clump_rules
     from . import derive, gradient
     from . import plotfile as pf
     registered = derive.derived_fields()
     gradients = gradient.gradient_fields()
+    clump_names = clump_rules.clump_fields()
     resolved = {}
     header = []
 
@@ -296,6 +402,15 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
             scene = gradient_scene(ctx, inner, axis, head.cell_size[:finest + 1], head.prob_lo,
                                    head.ref_ratio[:finest], rank, n_ranks, process_group, log,
                                    normalize)
+        elif name in clump_names:
+            of, lower, upper = clump_names[name]
+            _check_variable(plotfile, plotfile_header(), of, f"clump field '{name}'")
+            inner = resolve(of, False, True)
+            finest = max(int(b.level) for b in inner.all_boxes)
+            head = plotfile_header()
+            scene, _ = clump_scene(ctx, inner, lower, upper, head.cell_size[:finest + 1],
+                                   head.prob_lo, head.ref_ratio[:finest], rank, n_ranks,
+                                   process_group, log, normalize)
         elif name in registered:
             program = derive.compile_field(name)
             _check_derived_inputs(plotfile, plotfile_header(), name, program)
@@ -317,10 +432,14 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
 def _check_variable(plotfile: str, header, name: str, needed_by: str = "") -> None:
     """RuntimeError unless `name` is a stored variable of the plotfile or a registered derived or
     gradient field whose own inputs are."""
+    from . import clumps as clump_rules
     from . import derive, gradient
     gradients = gradient.gradient_fields()
+    clump_names = clump_rules.clump_fields()
     if name in gradients:
         _check_variable(plotfile, header, gradients[name][0], f"gradient field '{name}'")
+    elif name in clump_names:
+        _check_variable(plotfile, header, clump_names[name][0], f"clump field '{name}'")
     elif name in derive.derived_fields():
         _check_derived_inputs(plotfile, header, name, derive.compile_field(name))
     elif name not in header.var_names:

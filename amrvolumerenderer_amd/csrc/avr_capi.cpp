@@ -342,6 +342,7 @@ struct avr_context {
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
   avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
+  avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
 };
 
 
@@ -874,6 +875,7 @@ void avr_context_destroy(avr_context* ctx) {
   if (ctx->colorize_scratch != nullptr) (void)hipFree(ctx->colorize_scratch);
   ctx->axis_planes.release();
   ctx->gradient_planes.release();
+  ctx->clump_parents.release();
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -2047,6 +2049,80 @@ int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, in
     args.face_value = static_cast<double*>(ctx->gradient_planes.data);
     args.face_present = reinterpret_cast<uint8_t*>(args.face_value + 2 * n_faces);
     return avr::launch_gradient(args, axis, ctx->stream);
+  });
+}
+
+int avr_scene_clumps(avr_context* ctx, const avr_scene* in, avr_scene* out, double lower,
+                     double upper, const int32_t* box_index_lo, const int32_t* level_ratio,
+                     int n_levels, uint64_t* count_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(in != nullptr && out != nullptr && count_dev != nullptr, "null argument");
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    require_field_scene(ctx, in, n_boxes);
+    avr::ClumpPlan plan = avr::plan_clumps(in->boxes.data(), out->boxes.data(), n_boxes, lower,
+                                           upper, box_index_lo, level_ratio, n_levels);
+    for (auto& key : out->classified_key) key.clear();
+    avr::hip_check(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), ctx->stream), "hipMemsetAsync");
+    if (plan.tile_begin.back() == 0) return AVR_OK;
+    // the parent entries, padded to whole chunks, then one count per chunk
+    const size_t n_cells = plan.cell_begin.back();
+    const size_t n_chunks = (n_cells + avr::kClumpChunk - 1) / avr::kClumpChunk;
+    ctx->clump_parents.reserve((n_chunks * avr::kClumpChunk + n_chunks) * sizeof(uint32_t),
+                               ctx->stream, "avr_scene_clumps", "hipMalloc(clump parents)");
+    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
+    avr::ClumpArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::ClumpBoxDev) +
+                           (plan.tile_begin.size() + plan.candidate_begin.size()) * sizeof(uint32_t) +
+                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 5);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
+    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
+    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_levels = n_levels;
+    args.n_tiles = plan.tile_begin.back();
+    args.n_cells = static_cast<uint32_t>(n_cells);
+    args.n_chunks = static_cast<uint32_t>(n_chunks);
+    args.lower = lower;
+    args.upper = upper;
+    args.parent = static_cast<uint32_t*>(ctx->clump_parents.data);
+    args.chunk_roots = args.parent + n_chunks * avr::kClumpChunk;
+    args.count = reinterpret_cast<unsigned long long*>(count_dev);
+    return avr::launch_clumps(args, ctx->stream);
+  });
+}
+
+int avr_scene_clump_table(avr_context* ctx, const avr_scene* labels, const avr_scene* field,
+                          uint64_t n_clumps, int n_levels, uint64_t* cells_dev, double* sums_dev,
+                          uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(labels != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
+    require((field != nullptr) == (sums_dev != nullptr), "sums_dev is given exactly when field is");
+    const size_t n_boxes = labels->boxes.size();
+    require_field_scene(ctx, labels, n_boxes);
+    if (field != nullptr) require_field_scene(ctx, field, n_boxes);
+    const avr::ClumpTablePlan plan = avr::plan_clump_table(
+        labels->boxes.data(), field != nullptr ? field->boxes.data() : nullptr, n_boxes, n_clumps,
+        n_levels);
+    if (plan.tile_begin.back() == 0) return AVR_OK;
+    avr::ClumpTableArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::JointBoxDev) +
+                           plan.tile_begin.size() * sizeof(uint32_t), 2);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_tiles = plan.tile_begin.back();
+    args.n_clumps = static_cast<uint32_t>(n_clumps);
+    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
+    args.sums = sums_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_clump_table(args, field != nullptr, ctx->stream);
   });
 }
 

@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields): everything a call works out from its arguments before the
-// first HIP call -- the argument rules, the box table, the tile prefix and the product's own
+// derived fields, gradient fields, clumps): everything a call works out from its arguments before
+// the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
 // rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
 // std::invalid_argument with the message the C ABI reports, and fills vectors and PODs that the
@@ -360,6 +360,43 @@ inline int64_t floor_div(int64_t a, int64_t r) {
   return (a % r != 0 && a < 0) ? q - 1 : q;
 }
 
+// The boxes that can hold a ghost of one face of box b: the ghost slab next to the face (axis,
+// side: 0 low, 1 high) at the box's own level, at every coarser one and, where finest is one above
+// the box's level, one level finer; a box other than b of a level up to finest whose cells meet the
+// slab there is appended, in scene order.  Box: a device box with nx (0 without cells) and level;
+// ratio[l]: level l -> l + 1.
+template <class Box>
+inline void append_face_candidates(const std::vector<Box>& boxes,
+                                   const std::vector<IndexRegion>& regions, size_t b, int axis,
+                                   int side, const int32_t* ratio, int finest,
+                                   std::vector<int32_t>* candidates) {
+  const int level = boxes[b].level;
+  IndexRegion slab[kGradientMaxLevels + 1];  // [m] at level m
+  slab[level] = regions[b];
+  slab[level].lo[axis] = slab[level].hi[axis] =
+      side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
+  for (int m = level; m > 0; --m) {
+    for (int d = 0; d < 3; ++d) {
+      slab[m - 1].lo[d] = floor_div(slab[m].lo[d], ratio[m - 1]);
+      slab[m - 1].hi[d] = floor_div(slab[m].hi[d], ratio[m - 1]);
+    }
+  }
+  if (finest > level) {
+    const int64_t r = ratio[level];
+    for (int d = 0; d < 3; ++d) {
+      slab[finest].lo[d] = slab[level].lo[d] * r;
+      slab[finest].hi[d] = slab[level].hi[d] * r + (r - 1);
+    }
+  }
+  for (size_t c = 0; c < boxes.size(); ++c) {
+    if (c == b || boxes[c].nx <= 0 || boxes[c].level > finest) continue;
+    if (regions_meet(slab[boxes[c].level], regions[c])) {
+      candidates->push_back(static_cast<int32_t>(c));
+    }
+  }
+  require_box(candidates->size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
+}
+
 struct GradientPlan {
   std::vector<GradientBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
@@ -449,34 +486,149 @@ inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t 
     }
     for (int side = 0; side < 2; ++side) {
       if (cells) {
-        IndexRegion slab[kGradientMaxLevels + 1];  // [m] at level m
-        slab[level] = regions[b];
-        slab[level].lo[axis] = slab[level].hi[axis] =
-            side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
-        for (int m = level; m > 0; --m) {
-          for (int d = 0; d < 3; ++d) {
-            slab[m - 1].lo[d] = floor_div(slab[m].lo[d], levels.ratio[m - 1]);
-            slab[m - 1].hi[d] = floor_div(slab[m].hi[d], levels.ratio[m - 1]);
-          }
-        }
         const int finest = level + 1 < n_levels ? level + 1 : level;
-        if (finest > level) {
-          const int64_t r = levels.ratio[level];
-          for (int d = 0; d < 3; ++d) {
-            slab[finest].lo[d] = slab[level].lo[d] * r;
-            slab[finest].hi[d] = slab[level].hi[d] * r + (r - 1);
-          }
-        }
-        for (size_t c = 0; c < n_boxes; ++c) {
-          if (c == b || boxes[c].nx <= 0 || boxes[c].level > finest) continue;
-          if (regions_meet(slab[boxes[c].level], regions[c])) {
-            candidates.push_back(static_cast<int32_t>(c));
-          }
-        }
-        require_box(candidates.size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
+        append_face_candidates(boxes, regions, b, axis, side, levels.ratio, finest, &candidates);
       }
       plan.candidate_begin.push_back(static_cast<uint32_t>(candidates.size()));
     }
+  }
+  return plan;
+}
+
+// ---- clumps -------------------------------------------------------------------------------
+struct ClumpPlan {
+  std::vector<ClumpBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  std::vector<uint32_t> cell_begin;  // n_boxes + 1: prefix sum of the boxes' cells, in scene order
+  // CSR over (box, axis, side), entry 6 b + 2 axis + side: the boxes of the same or a coarser
+  // level that can hold a ghost of that face
+  std::vector<uint32_t> candidate_begin;
+  std::vector<int32_t> candidates;   // empty when no face has a neighbour
+  GradientLevelsDev levels;
+};
+// box_index_lo and level_ratio as plan_gradient takes them.  The rules, in this order: the bounds,
+// n_levels, the box rules (the input is the reference), the ratios, the index ranges, boxes of one
+// level apart in index space, no output byte shared with an input, fewer than 2^31 cells.
+inline ClumpPlan plan_clumps(const avr_box* in, const avr_box* out, size_t n_boxes, double lower,
+                             double upper, const int32_t* box_index_lo, const int32_t* level_ratio,
+                             int n_levels) {
+  require_box(!std::isnan(lower) && !std::isnan(upper), "a bound is NaN");
+  require_box(lower <= upper, "lower must not exceed upper");
+  require_box(n_levels >= 1 && n_levels <= kClumpMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  ClumpPlan plan;
+  std::vector<ClumpBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = in[b];
+    const avr_box* fields[2] = {&first, &out[b]};
+    FieldView views[2];
+    ClumpBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, fields, 2, n_levels, views, &dev.paired);
+    dev.in = views[0].cells;
+    dev.out = const_cast<double*>(views[1].cells);
+    dev.jstride_in = views[0].jstride;
+    dev.kstride_in = views[0].kstride;
+    dev.jstride_out = views[1].jstride;
+    dev.kstride_out = views[1].kstride;
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&read_ranges, views[0]);
+      append_byte_range(&write_ranges, views[1]);
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  GradientLevelsDev& levels = plan.levels;
+  for (int l = 0; l < kGradientMaxLevels; ++l) levels.ratio[l] = 1;
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
+    levels.ratio[l] = level_ratio[l];
+  }
+  std::vector<IndexRegion> regions(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx <= 0) continue;
+    for (int d = 0; d < 3; ++d) {
+      const int64_t lo = box_index_lo[b * 3 + d];
+      boxes[b].lo[d] = box_index_lo[b * 3 + d];
+      regions[b].lo[d] = lo;
+      regions[b].hi[d] = lo + in[b].dims[d] - 1;
+      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
+                  "a box's index range leaves [-2^30, 2^30)");
+    }
+  }
+  for (size_t b = 0; b < n_boxes; ++b) {
+    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
+      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
+                      !regions_meet(regions[b], regions[c]),
+                  "two boxes of one level overlap in index space");
+    }
+  }
+  require_no_shared_byte(&read_ranges, write_ranges);
+  plan.cell_begin.assign(1, 0u);
+  uint64_t total = 0;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    // a box's cells are at most 2^28 (its span), so the sum stays far inside 64 bits
+    total += static_cast<uint64_t>(boxes[b].nx) * static_cast<uint64_t>(boxes[b].ny) *
+             static_cast<uint64_t>(boxes[b].nz);
+    require_box(total < (uint64_t{1} << 31), "scene has too many cells for 32-bit labels");
+    boxes[b].cell_begin = plan.cell_begin.back();
+    plan.cell_begin.push_back(static_cast<uint32_t>(total));
+  }
+  plan.candidate_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    for (int face = 0; face < 6; ++face) {
+      if (boxes[b].nx > 0) {
+        append_face_candidates(boxes, regions, b, face >> 1, face & 1, levels.ratio, boxes[b].level,
+                               &plan.candidates);
+      }
+      plan.candidate_begin.push_back(static_cast<uint32_t>(plan.candidates.size()));
+    }
+  }
+  return plan;
+}
+
+struct ClumpTablePlan {
+  std::vector<JointBoxDev> boxes;  // field 0: the labels; field 1: the summed field, or the labels
+  std::vector<uint32_t> tile_begin;
+};
+// field (may be null): the boxes of the summed field.
+inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* field, size_t n_boxes,
+                                       uint64_t n_clumps, int n_levels) {
+  require_box(n_clumps >= 1, "n_clumps must be at least 1");
+  require_box(n_levels >= 1 && n_levels <= kClumpMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_clumps < static_cast<uint64_t>(kClumpTableMaxEntries) &&
+                  n_clumps * static_cast<uint64_t>(n_levels) <
+                      static_cast<uint64_t>(kClumpTableMaxEntries),
+              "n_clumps * n_levels must stay below 2^28");
+  ClumpTablePlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = labels[b];
+    const avr_box* in[2] = {&first, field != nullptr ? &field[b] : &first};
+    FieldView views[2];
+    JointBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, in, 2, n_levels, views, &dev.paired);
+    dev.level = first.level;
+    for (int f = 0; f < 2; ++f) {
+      dev.cells[f] = views[f].cells;
+      dev.jstride[f] = views[f].jstride;
+      dev.kstride[f] = views[f].kstride;
+    }
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
   }
   return plan;
 }

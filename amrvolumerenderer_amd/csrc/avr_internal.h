@@ -600,6 +600,61 @@ struct GradientArgs {
 };
 int launch_gradient(const GradientArgs& args, int axis, void* stream);
 
+// Clumps (avr_clumps.hip): the connected components of the cells whose value lies in [lower,
+// upper].  Every cell has an ordinal, cell_begin of its box + (k ny + j) nx + i, and a 32-bit
+// parent entry at that ordinal: kClumpNone for a cell that is not selected, else the ordinal of a
+// selected cell of the same clump that is not larger (a root holds its own).  A box as the kernels
+// read it:
+constexpr int kClumpMaxLevels = 16;
+constexpr uint32_t kClumpNone = 0xffffffffu;
+constexpr uint32_t kClumpChunk = 1024;   // consecutive ordinals whose roots one workgroup counts
+constexpr uint32_t kClumpRanked = 0x80000000u;  // a root's entry once numbered: this | (label - 1)
+constexpr int64_t kClumpTableMaxEntries = int64_t{1} << 28;  // n_clumps * n_levels stays below it
+struct alignas(16) ClumpBoxDev {
+  const double* in;
+  double* out;
+  int32_t jstride_in, kstride_in;    // element strides (Array4); every field spans < 2^28
+  int32_t jstride_out, kstride_out;
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t paired;         // input and output: cells 16-byte aligned, both strides even
+  uint32_t cell_begin;    // the ordinal of the box's first cell
+  int32_t pad_[3];
+};
+static_assert(sizeof(ClumpBoxDev) == 80, "ClumpBoxDev: 16-byte multiple for scalar loads");
+struct ClumpArgs {
+  const ClumpBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  // CSR over (box, axis, side), entry 6 b + 2 axis + side: the boxes of the same or a coarser
+  // level whose cells can hold a ghost of that face, in scene order
+  const uint32_t* candidate_begin;  // 6 n_boxes + 1
+  const int32_t* candidates;
+  const GradientLevelsDev* levels;
+  int32_t n_boxes, n_levels;
+  uint32_t n_tiles;
+  uint32_t n_cells;             // < 2^31
+  uint32_t n_chunks;            // ceil(n_cells / kClumpChunk)
+  double lower, upper;
+  uint32_t* parent;             // n_chunks * kClumpChunk entries
+  uint32_t* chunk_roots;        // n_chunks: roots per chunk, then their exclusive prefix sum
+  unsigned long long* count;    // the number of clumps
+};
+int launch_clumps(const ClumpArgs& args, void* stream);
+// The table of a label field: a JointBoxDev holds the labels as field 0 and the summed field as
+// field 1 (the labels again without one).
+struct ClumpTableArgs {
+  const JointBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  uint32_t n_clumps;            // 1 .. 2^28 - 1
+  unsigned long long* cells;    // [n_levels][n_clumps], added to
+  double* sums;                 // the same shape (null without a field), added to
+  unsigned long long* totals;   // [2]: outside, nonfinite, added to
+};
+int launch_clump_table(const ClumpTableArgs& args, bool has_field, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

@@ -300,11 +300,16 @@ def add_field(name: str, expression: str) -> DerivedProgram:
     gradients = gradient.gradient_fields()
     if name in gradients:
         raise ValueError(f"{name!r} is a registered gradient field")
+    from . import clumps
+    clump_fields = clumps.clump_fields()
+    if name in clump_fields:
+        raise ValueError(f"{name!r} is a registered clump field")
     trial = dict(_registry)
     trial[name] = expression
     program = compile_expression(name if name.isidentifier() else f"field({name!r})", trial)
-    if gradients:
-        gradient.check_no_cycle(name, trial, gradients)   # a gradient field it reads may read it
+    if gradients or clump_fields:
+        # a gradient or clump field it reads may read it
+        gradient.check_no_cycle(name, trial, gradients, clump_fields)
     _registry[name] = expression
     return DerivedProgram(program.fields, program.instructions, program.constants, expression)
 

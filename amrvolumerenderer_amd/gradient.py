@@ -4,7 +4,7 @@ csrc/avr_gradient.hip run.  numpy only.
 """
 from __future__ import annotations
 
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -15,26 +15,34 @@ INDEX_TOLERANCE = 1e-6
 _registry: Dict[str, Tuple[str, int]] = {}
 
 
-def _dependencies(name: str, derived: Dict[str, str], gradients: Dict[str, Tuple[str, int]]):
-    """The names `name` is made of, one step down: a gradient field's input, or the fields a
-    derived field reads once the derived fields it names are inlined; () for anything else."""
+def _dependencies(name: str, derived: Dict[str, str], gradients: Dict[str, Tuple[str, int]],
+                  clumps: Dict[str, tuple]):
+    """The names `name` is made of, one step down: a gradient or clump field's input, or the fields
+    a derived field reads once the derived fields it names are inlined; () for anything else."""
     from . import derive
     if name in gradients:
         return (gradients[name][0],)
+    if name in clumps:
+        return (clumps[name][0],)
     if name in derived:
         text = name if name.isidentifier() else f"field({name!r})"
         return derive.compile_expression(text, derived).fields
     return ()
 
 
-def check_no_cycle(start: str, derived: Dict[str, str],
-                   gradients: Dict[str, Tuple[str, int]]) -> None:
-    """ValueError if `start` reaches itself through the two registries."""
+def check_no_cycle(start: str, derived: Dict[str, str], gradients: Dict[str, Tuple[str, int]],
+                   clumps: Optional[Dict[str, tuple]] = None) -> None:
+    """ValueError if `start` reaches itself through the registries of derived, gradient and clump
+    fields (clumps.py; the registered clump fields if None)."""
+    if clumps is None:
+        from . import clumps as clump_registry
+        clumps = clump_registry.clump_fields()
+
     def visit(name, path):
         if name in path:
-            raise ValueError("gradient and derived fields refer to each other in a cycle: "
+            raise ValueError("registered fields refer to each other in a cycle: "
                              + " -> ".join(path + [name]))
-        for inner in _dependencies(name, derived, gradients):
+        for inner in _dependencies(name, derived, gradients, clumps):
             visit(inner, path + [name])
     visit(start, [])
 
@@ -57,6 +65,9 @@ def add_gradient_field(name: str, of: str, axis) -> None:
     derived = derive.derived_fields()
     if name in derived:
         raise ValueError(f"{name!r} is a registered derived field")
+    from . import clumps
+    if name in clumps.clump_fields():
+        raise ValueError(f"{name!r} is a registered clump field")
     if isinstance(axis, bool) or axis not in AXES:
         raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z'")
     trial = dict(_registry)

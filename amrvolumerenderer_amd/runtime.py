@@ -763,6 +763,72 @@ class Scene:
             sizes.ctypes.data_as(C.POINTER(C.c_double)), int(sizes.size)))
         ctx.publish()
 
+    def clumps(self, field: "Scene", lower: float, upper: float, box_index_lo, level_ratio,
+               count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """avr_scene_clumps with this scene as the output: overwrites the cells of this scene's
+        boxes with the clump labels of `field` (a scene of the same context with the same box
+        list) over lower <= v <= upper: f64(label) in 1..N for a selected cell, +0.0 otherwise.
+        box_index_lo: [n_boxes, 3] int32; level_ratio: n_levels - 1 ints.  Returns the number of
+        clumps N as a one-element int64 tensor on the device (count, if given).  This scene's
+        cells must not overlap the field's.  Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if ratios.ndim != 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int64, device=ctx.device)
+        ctx._check_tensor(count, torch.int64, "count")
+        if count.numel() != 1:
+            raise ValueError("count must hold one value")
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_clumps(
+            ctx._handle, field._handle, self._handle, float(lower), float(upper),
+            index.ctypes.data_as(C.POINTER(C.c_int32)), ratios.ctypes.data_as(C.POINTER(C.c_int32)),
+            int(ratios.size) + 1, C.c_void_p(count.data_ptr())))
+        ctx.publish()
+        return count
+
+    def clump_table(self, n_clumps: int, n_levels: int, field: Optional["Scene"] = None,
+                    cells: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
+                    totals: Optional[torch.Tensor] = None):
+        """avr_scene_clump_table with this scene as the labels: per level and label the number of
+        cells and, with `field` (a scene of the same context with the same box list), the sum of
+        its values.  Returns (cells int64 [n_levels, n_clumps], sums float64 of the same shape or
+        None without field, totals int64 [2]: labels that are no integer in [1, n_clumps], field
+        values that are not finite) on the device; tensors handed in are added to."""
+        ctx = self.ctx
+        n_clumps, n_levels = int(n_clumps), int(n_levels)
+        if n_clumps < 1 or n_levels < 1:
+            raise ValueError("n_clumps and n_levels must be at least 1")
+        shape = (n_levels, n_clumps)
+        if cells is None:
+            cells = torch.zeros(shape, dtype=torch.int64, device=ctx.device)
+        if totals is None:
+            totals = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+        ctx._check_tensor(cells, torch.int64, "cells")
+        ctx._check_tensor(totals, torch.int64, "totals")
+        if tuple(cells.shape) != shape or totals.numel() != 2:
+            raise ValueError("cells must be [n_levels, n_clumps] and totals hold two values")
+        if field is not None:
+            if sums is None:
+                sums = torch.zeros(shape, dtype=torch.float64, device=ctx.device)
+            ctx._check_tensor(sums, torch.float64, "sums")
+            if tuple(sums.shape) != shape:
+                raise ValueError("sums must be [n_levels, n_clumps]")
+        elif sums is not None:
+            raise ValueError("sums is given exactly when field is")
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_clump_table(
+            ctx._handle, self._handle, field._handle if field is not None else None, n_clumps,
+            n_levels, C.c_void_p(cells.data_ptr()),
+            C.c_void_p(sums.data_ptr()) if sums is not None else None,
+            C.c_void_p(totals.data_ptr())))
+        ctx.publish()
+        return cells, sums, totals
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

@@ -1186,6 +1186,49 @@ int avr_scene_gradient(avr_context *ctx, const avr_scene *in, avr_scene *out, in
                        const int32_t *box_index_lo, const int32_t *level_ratio,
                        const double *level_cell_size, int n_levels);
 
+/* ---- clumps ("Clumps") ------------------------------------------------------------ */
+
+/* The connected components ("clumps") of the cells of `in` whose raw f64 value v satisfies
+ * v >= lower && v <= upper (no transform; a NaN is never selected, +Inf only by upper = +Inf, -Inf
+ * only by lower = -Inf), labelled into `out`: scenes of ctx with the same box list as
+ * avr_scene_gradient requires, `out` over cells the caller allocated, and the same hierarchy
+ * description (box_index_lo, level_ratio, n_levels <= 16; host).  Two selected cells are adjacent
+ * if they are face neighbours inside a box, or if one is the cell found for the other's ghost:
+ * past a box's face the ghost G (a level-l index) is mapped to levels m = l, l - 1, ..., 0 by
+ * floor division and the first level-m box that contains the mapped index gives the neighbour; a
+ * finer neighbour is never searched for (it finds the coarse cell from its own side), and a ghost
+ * no such box contains has no neighbour there.  A cell's ordinal is cell_begin[b] + (k * ny + j) *
+ * nx + i, cell_begin the prefix sum of nx * ny * nz over the scene's boxes in scene order; clumps
+ * are numbered 1..N in ascending order of their smallest ordinal.  `out` gets f64(label) for a
+ * selected cell and +0.0 otherwise, *count_dev (device) gets N.  Only the cells of the scene's
+ * boxes are read, never the rest of an allocation a box is a view of.  The numbering is canonical:
+ * equal arguments give equal bits, whatever order the atomics inside resolve in.
+ * Everything is checked on the host before any device work: AVR_ERR_INVALID_ARGUMENT for a NaN
+ * bound or lower > upper, n_levels outside [1, 16], scenes that are not congruent, a box level >=
+ * n_levels, a ratio below 2, a box index range outside [-2^30, 2^30), two boxes of one level that
+ * overlap in index space, an output box whose cells share a byte with an input box's, and 2^31
+ * cells or more ("scene has too many cells for 32-bit labels") -- and `out` and *count_dev are
+ * untouched.  Asynchronous on the context's stream; the context keeps 4 bytes per cell of
+ * grow-only scratch; invalidates out's cached classification. */
+int avr_scene_clumps(avr_context *ctx, const avr_scene *in, avr_scene *out, double lower,
+                     double upper, const int32_t *box_index_lo, const int32_t *level_ratio,
+                     int n_levels, uint64_t *count_dev);
+
+/* The table of a label field: for every cell of `labels` (a scene of ctx, as avr_scene_clumps
+ * writes one; any f64 cells are taken), in this order: a label whose bits are +0.0 is skipped; a
+ * label that is not an integer in [1, n_clumps] adds 1 to totals_dev[0]; with `field` (a scene of
+ * ctx with the same box list, or NULL) a field value vs that is not finite adds 1 to
+ * totals_dev[1]; otherwise cells_dev[l * n_clumps + label - 1] += 1 (uint64) for the box's level
+ * l and, with a field, sums_dev[the same entry] += vs (f64).  cells_dev and sums_dev (NULL exactly
+ * when field is) are [n_levels][n_clumps] on the device, totals_dev two uint64; all are added to,
+ * as avr_scene_joint_histogram's are.  Counts are exact; a sum is made of f64 additions in no
+ * fixed order.  AVR_ERR_INVALID_ARGUMENT, before any device work and with the outputs untouched:
+ * n_clumps < 1, n_levels outside [1, 16], n_clumps * n_levels >= 2^28, scenes that are not
+ * congruent, a box level >= n_levels.  Asynchronous on the context's stream. */
+int avr_scene_clump_table(avr_context *ctx, const avr_scene *labels, const avr_scene *field,
+                          uint64_t n_clumps, int n_levels, uint64_t *cells_dev, double *sums_dev,
+                          uint64_t *totals_dev);
+
 #ifdef __cplusplus
 }
 #endif
