@@ -363,6 +363,102 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
             "outside": outside, "nonfinite": nonfinite}
 
 
+# ---- isosurfaces ("Isosurface") -----------------------------------------------------
+
+def isosurface_scene(ctx, scene: "SceneGeometry", value: float, cell_sizes, prob_lo, ref_ratio,
+                     sample: Optional["SceneGeometry"] = None, rank: int = 0, n_ranks: int = 1):
+    """The isosurface field == value of a scene's raw field by marching tetrahedra (DESIGN.md 7,
+    "Isosurface"), as a triangle soup in a canonical order.  scene, cell_sizes, prob_lo and
+    ref_ratio as gradient_scene takes them; sample: a scene with the same boxes whose field is
+    interpolated at every vertex.  Returns (vertices float64 [n, 3, 3] in the plotfile's physical
+    units, levels uint8 [n], samples float64 [n, 3] or None, skipped): numpy arrays and the number
+    of surface cubes left out for a corner that is not finite.  One call counts, the arrays are
+    allocated, a second call emits.  Every box of the scene must be on this rank: with n_ranks >
+    1, or fewer local boxes than boxes, NotImplementedError is raised before any device work."""
+    import numpy as np
+    from . import gradient
+    value = float(value)
+    if not math.isfinite(value):
+        raise ValueError("an isosurface's value must be finite")
+    local = list(scene.local_boxes)
+    if n_ranks > 1 or len(local) != len(scene.all_boxes):
+        raise NotImplementedError("an isosurface needs every box of the scene on one rank: "
+                                  "ghost cells are not exchanged between ranks")
+    if sample is not None and len(sample.local_boxes) != len(local):
+        raise ValueError("the sample scene must hold the same boxes as the scene")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in scene.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
+    if len(ratios) != len(sizes) - 1:
+        raise ValueError("ref_ratio must hold one ratio per level transition")
+    origin = [float(v) for v in prob_lo]
+    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
+                                  scene.world_scale, origin, sizes)
+    field = ctx.create_scene(local, scene.scalar_transform)
+    other = ctx.create_scene(sample.local_boxes, sample.scalar_transform) \
+        if sample is not None else None
+    try:
+        counts, _, _, _ = field.isosurface(value, index, ratios, sizes, origin, other)
+        ctx.synchronize()
+        n, skipped = (int(v) for v in counts.cpu().tolist())
+        vertices = np.zeros((0, 3, 3), dtype=np.float64)
+        levels = np.zeros(0, dtype=np.uint8)
+        samples = np.zeros((0, 3), dtype=np.float64) if sample is not None else None
+        if n > 0:
+            _, v, l, s = field.isosurface(value, index, ratios, sizes, origin, other, capacity=n)
+            ctx.synchronize()
+            vertices, levels = v.cpu().numpy(), l.cpu().numpy()
+            if s is not None:
+                samples = s.cpu().numpy()
+    finally:
+        field.close()
+        if other is not None:
+            other.close()
+    return vertices, levels, samples, skipped
+
+
+def isosurface(plotfile: str, variable: str, value: float, fields: Sequence[str] = (),
+               min_level: int = 0, max_level: int = -1, output: Optional[str] = None) -> dict:
+    """The isosurface variable == value of a plotfile ("Isosurface"), on cuda:0, over
+    the uncovered cells of the loaded levels.  variable and every name of fields is a stored
+    variable or a registered derived, gradient or clump field.  Returns a dict: n (triangles),
+    vertices float64 [n, 3, 3] in the plotfile's physical units, the normal (v1 - v0) x (v2 - v0)
+    pointing to the variable < value side, level uint8 [n] (the level of the cube a triangle came
+    from), area float64 [n] = 0.5 |cross|, total_area (math.fsum), samples {name: float64 [n, 3]}
+    (each requested field interpolated at every vertex) and skipped (surface cubes left out for a
+    corner that is not finite).  n == 0 gives empty arrays.  With output the surface is written
+    as a binary PLY file, the samples as vertex properties (surfaces.save_ply).  At a coarse-fine
+    interface the surface has a crack of half the difference of the two cell sizes."""
+    import numpy as np
+    from . import plotfile as pf
+    from . import surfaces
+    names = [str(name) for name in fields]
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
+                                                            min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    arguments = (float(value), header.cell_size[:n_levels], header.prob_lo,
+                 header.ref_ratio[:n_levels - 1])
+    samples = {}
+    if names:
+        for name, scene in zip(names, scenes[1:]):
+            vertices, levels, sampled, skipped = isosurface_scene(ctx, scenes[0], *arguments,
+                                                                  scene, rank, world)
+            samples[name] = sampled
+    else:
+        vertices, levels, _, skipped = isosurface_scene(ctx, scenes[0], *arguments, None, rank,
+                                                        world)
+    area = surfaces.triangle_areas(vertices)
+    result = {"n": int(vertices.shape[0]), "vertices": vertices, "level": levels, "area": area,
+              "total_area": math.fsum(area.tolist()), "samples": samples, "skipped": skipped}
+    if output:
+        surfaces.save_ply(vertices, output, samples)
+    return result
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:

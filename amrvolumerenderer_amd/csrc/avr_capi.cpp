@@ -343,6 +343,7 @@ struct avr_context {
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
   avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
   avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
+  avr::DeviceBuffer iso_scratch;               // avr_scene_isosurface's shells and chunk counts
 };
 
 
@@ -876,6 +877,7 @@ void avr_context_destroy(avr_context* ctx) {
   ctx->axis_planes.release();
   ctx->gradient_planes.release();
   ctx->clump_parents.release();
+  ctx->iso_scratch.release();
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -2123,6 +2125,68 @@ int avr_scene_clump_table(avr_context* ctx, const avr_scene* labels, const avr_s
     args.sums = sums_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_clump_table(args, field != nullptr, ctx->stream);
+  });
+}
+
+int avr_scene_isosurface(avr_context* ctx, const avr_scene* field, const avr_scene* sample,
+                         double value, const int32_t* box_index_lo, const int32_t* level_ratio,
+                         const double* level_cell_size, const double* prob_lo, int n_levels,
+                         uint64_t capacity, double* vertices_dev, uint8_t* levels_dev,
+                         double* samples_dev, uint64_t* counts_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(field != nullptr && level_cell_size != nullptr && prob_lo != nullptr &&
+                counts_dev != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
+    avr::IsoPlan plan = avr::plan_isosurface(
+        field->boxes.data(), sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, value,
+        box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, capacity, vertices_dev,
+        levels_dev, samples_dev, counts_dev);
+    avr::hip_check(hipMemsetAsync(counts_dev, 0, 2 * sizeof(uint64_t), ctx->stream),
+                   "hipMemsetAsync");
+    const size_t n_bases = plan.base_begin.back();
+    if (n_bases == 0) return AVR_OK;
+    const bool has_sample = sample != nullptr, emit = capacity > 0;
+    // the shells' values (and sample values), the chunks' offsets, triangles and skipped cubes,
+    // then the shells' code bytes
+    const size_t n_shell = plan.shell_begin.back();
+    const size_t n_chunks = (n_bases + avr::kIsoChunk - 1) / avr::kIsoChunk;
+    const size_t shell_doubles = n_shell * (has_sample ? 2 : 1);
+    ctx->iso_scratch.reserve(shell_doubles * sizeof(double) + n_chunks * 16 + n_shell, ctx->stream,
+                             "avr_scene_isosurface", "hipMalloc(isosurface scratch)");
+    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
+    avr::IsoArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::IsoBoxDev) +
+                           (plan.base_begin.size() + plan.candidate_begin.size()) * sizeof(uint32_t) +
+                           plan.shell_begin.size() * sizeof(uint64_t) +
+                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 6);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.shell_begin = ctx->staging.add(plan.shell_begin.data(), plan.shell_begin.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
+    args.base_begin = ctx->staging.add(plan.base_begin.data(), plan.base_begin.size());
+    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
+    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
+    ctx->staging.commit(ctx->stream);
+    args.n_boxes = static_cast<int32_t>(n_boxes);
+    args.n_levels = n_levels;
+    args.n_bases = static_cast<uint32_t>(n_bases);
+    args.n_chunks = static_cast<uint32_t>(n_chunks);
+    args.n_shell = n_shell;
+    args.value = value;
+    args.capacity = capacity;
+    args.shell_value = static_cast<double*>(ctx->iso_scratch.data);
+    args.shell_sample = has_sample ? args.shell_value + n_shell : nullptr;
+    args.chunk_offset = reinterpret_cast<unsigned long long*>(args.shell_value + shell_doubles);
+    args.chunk_triangles = reinterpret_cast<uint32_t*>(args.chunk_offset + n_chunks);
+    args.chunk_skipped = args.chunk_triangles + n_chunks;
+    args.shell_code = reinterpret_cast<uint8_t*>(args.chunk_skipped + n_chunks);
+    args.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+    args.vertices = vertices_dev;
+    args.levels_out = levels_dev;
+    args.samples = has_sample ? samples_dev : nullptr;
+    return avr::launch_isosurface(args, has_sample, emit, ctx->stream);
   });
 }
 

@@ -1,5 +1,5 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps): everything a call works out from its arguments before
+// derived fields, gradient fields, clumps, isosurfaces): everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
 // rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
@@ -222,7 +222,9 @@ inline void append_byte_range(ByteRanges* ranges, const FieldView& view) {
   const uintptr_t begin = reinterpret_cast<uintptr_t>(view.cells);
   ranges->emplace_back(begin, begin + static_cast<uintptr_t>(view.last) * 8 + 7);
 }
-inline void require_no_shared_byte(ByteRanges* read_ranges, const ByteRanges& write_ranges) {
+inline void require_no_shared_byte(
+    ByteRanges* read_ranges, const ByteRanges& write_ranges,
+    const char* message = "an output box's cells overlap an input box's cells") {
   std::sort(read_ranges->begin(), read_ranges->end());
   std::vector<uintptr_t> reach(read_ranges->size());
   for (size_t r = 0; r < read_ranges->size(); ++r) {
@@ -232,8 +234,7 @@ inline void require_no_shared_byte(ByteRanges* read_ranges, const ByteRanges& wr
     const size_t before =
         std::upper_bound(read_ranges->begin(), read_ranges->end(),
                          std::make_pair(w.second, UINTPTR_MAX)) - read_ranges->begin();
-    require_box(before == 0 || reach[before - 1] < w.first,
-                "an output box's cells overlap an input box's cells");
+    require_box(before == 0 || reach[before - 1] < w.first, message);
   }
 }
 
@@ -360,21 +361,19 @@ inline int64_t floor_div(int64_t a, int64_t r) {
   return (a % r != 0 && a < 0) ? q - 1 : q;
 }
 
-// The boxes that can hold a ghost of one face of box b: the ghost slab next to the face (axis,
-// side: 0 low, 1 high) at the box's own level, at every coarser one and, where finest is one above
-// the box's level, one level finer; a box other than b of a level up to finest whose cells meet the
-// slab there is appended, in scene order.  Box: a device box with nx (0 without cells) and level;
-// ratio[l]: level l -> l + 1.
+// The boxes that can hold a cell of `region`, a range of indices of box b's level: the region at
+// the box's own level, at every coarser one and, where finest is one above the box's level, one
+// level finer; a box other than b of a level up to finest whose cells meet the region there is
+// appended, in scene order.  Box: a device box with nx (0 without cells) and level; ratio[l]:
+// level l -> l + 1.
 template <class Box>
-inline void append_face_candidates(const std::vector<Box>& boxes,
-                                   const std::vector<IndexRegion>& regions, size_t b, int axis,
-                                   int side, const int32_t* ratio, int finest,
-                                   std::vector<int32_t>* candidates) {
+inline void append_region_candidates(const std::vector<Box>& boxes,
+                                     const std::vector<IndexRegion>& regions, size_t b,
+                                     const IndexRegion& region, const int32_t* ratio, int finest,
+                                     std::vector<int32_t>* candidates) {
   const int level = boxes[b].level;
   IndexRegion slab[kGradientMaxLevels + 1];  // [m] at level m
-  slab[level] = regions[b];
-  slab[level].lo[axis] = slab[level].hi[axis] =
-      side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
+  slab[level] = region;
   for (int m = level; m > 0; --m) {
     for (int d = 0; d < 3; ++d) {
       slab[m - 1].lo[d] = floor_div(slab[m].lo[d], ratio[m - 1]);
@@ -395,6 +394,18 @@ inline void append_face_candidates(const std::vector<Box>& boxes,
     }
   }
   require_box(candidates->size() < (size_t{1} << 31), "scene has too many neighbouring boxes");
+}
+
+// The boxes that can hold a ghost of one face of box b: append_region_candidates for the ghost
+// slab next to the face (axis, side: 0 low, 1 high).
+template <class Box>
+inline void append_face_candidates(const std::vector<Box>& boxes,
+                                   const std::vector<IndexRegion>& regions, size_t b, int axis,
+                                   int side, const int32_t* ratio, int finest,
+                                   std::vector<int32_t>* candidates) {
+  IndexRegion slab = regions[b];
+  slab.lo[axis] = slab.hi[axis] = side == 0 ? regions[b].lo[axis] - 1 : regions[b].hi[axis] + 1;
+  append_region_candidates(boxes, regions, b, slab, ratio, finest, candidates);
 }
 
 struct GradientPlan {
@@ -629,6 +640,151 @@ inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* fie
       dev.nz = first.dims[2];
     }
     append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  return plan;
+}
+
+// ---- isosurfaces --------------------------------------------------------------------------
+struct IsoPlan {
+  std::vector<IsoBoxDev> boxes;
+  std::vector<uint32_t> base_begin;   // n_boxes + 1: prefix sum of the boxes' cube bases
+  std::vector<uint64_t> shell_begin;  // n_boxes + 1: prefix sum of the boxes' shell cells
+  // CSR over boxes: the boxes of the same or a coarser level that can hold a cell of the box's
+  // one-cell ghost shell
+  std::vector<uint32_t> candidate_begin;
+  std::vector<int32_t> candidates;    // empty when no box has a neighbour
+  IsoLevelsDev levels;
+};
+// sample (may be null): the boxes of the sample field.  box_index_lo and level_ratio as
+// plan_gradient takes them; level_cell_size: (dx, dy, dz) per level; prob_lo: three values.  The
+// outputs are device arrays of `capacity` triangles (unused, and free to be null, with capacity
+// 0); counts is never null.  The rules, in this order: the value, n_levels, null arrays, the cell
+// sizes, prob_lo, the capacity and its arrays, the box rules (the field is the reference, so an
+// incongruent sample scene is refused here), the ratios, the index ranges, boxes of one level
+// apart in index space, no output byte shared with an input, fewer than 2^31 cube bases.
+inline IsoPlan plan_isosurface(const avr_box* field, const avr_box* sample, size_t n_boxes,
+                               double value, const int32_t* box_index_lo,
+                               const int32_t* level_ratio, const double* level_cell_size,
+                               const double* prob_lo, int n_levels, uint64_t capacity,
+                               const void* vertices, const void* levels_out, const void* samples,
+                               const void* counts) {
+  require_box(std::isfinite(value), "value must be finite");
+  require_box(n_levels >= 1 && n_levels <= kIsoMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  IsoPlan plan;
+  IsoLevelsDev& levels = plan.levels;
+  std::memset(&levels, 0, sizeof(levels));
+  for (int l = 0; l < n_levels; ++l) {
+    for (int d = 0; d < 3; ++d) {
+      const double size = level_cell_size[l * 3 + d];
+      require_box(std::isfinite(size) && size > 0.0, "level_cell_size must be finite and positive");
+      levels.cell_size[l][d] = size;
+    }
+  }
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(prob_lo[d]), "prob_lo must be finite");
+    levels.prob_lo[d] = prob_lo[d];
+  }
+  require_box(capacity < kIsoMaxCapacity, "capacity must stay below 2^36");
+  if (capacity > 0) {
+    require_box(vertices != nullptr && levels_out != nullptr, "null argument");
+    require_box((samples != nullptr) == (sample != nullptr),
+                "samples_dev is given exactly when sample is");
+  }
+  std::vector<IsoBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = field[b];
+    const avr_box* fields[2] = {&first, sample != nullptr ? &sample[b] : &first};
+    FieldView views[2];
+    IsoBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool cells = field_box_views(first, fields, 2, n_levels, views, &paired);
+    dev.in = views[0].cells;
+    dev.sample = views[1].cells;
+    dev.jstride_in = views[0].jstride;
+    dev.kstride_in = views[0].kstride;
+    dev.jstride_sample = views[1].jstride;
+    dev.kstride_sample = views[1].kstride;
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&read_ranges, views[0]);
+      if (sample != nullptr) append_byte_range(&read_ranges, views[1]);
+    }
+  }
+  for (int l = 0; l < kIsoMaxLevels; ++l) levels.ratio[l] = 1;
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
+    levels.ratio[l] = level_ratio[l];
+  }
+  std::vector<IndexRegion> regions(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx <= 0) continue;
+    for (int d = 0; d < 3; ++d) {
+      const int64_t lo = box_index_lo[b * 3 + d];
+      boxes[b].lo[d] = box_index_lo[b * 3 + d];
+      regions[b].lo[d] = lo;
+      regions[b].hi[d] = lo + field[b].dims[d] - 1;
+      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
+                  "a box's index range leaves [-2^30, 2^30)");
+    }
+  }
+  for (size_t b = 0; b < n_boxes; ++b) {
+    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
+      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
+                      !regions_meet(regions[b], regions[c]),
+                  "two boxes of one level overlap in index space");
+    }
+  }
+  // what the call writes: the two counts always, the triangles' arrays with a capacity
+  auto written = [&](const void* at, uint64_t bytes) {
+    const uintptr_t begin = reinterpret_cast<uintptr_t>(at);
+    write_ranges.emplace_back(begin, begin + static_cast<uintptr_t>(bytes) - 1);
+  };
+  written(counts, 2 * sizeof(uint64_t));
+  if (capacity > 0) {
+    written(vertices, capacity * 9 * sizeof(double));
+    written(levels_out, capacity);
+    if (samples != nullptr) written(samples, capacity * 3 * sizeof(double));
+  }
+  require_no_shared_byte(&read_ranges, write_ranges,
+                         "an output array overlaps an input box's cells");
+  plan.base_begin.assign(1, 0u);
+  plan.shell_begin.assign(1, uint64_t{0});
+  uint64_t bases = 0;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    // a box's cells are at most 2^28 (its span), its bases at most eight times as many
+    if (boxes[b].nx > 0) {
+      bases += (static_cast<uint64_t>(boxes[b].nx) + 1) * (static_cast<uint64_t>(boxes[b].ny) + 1) *
+               (static_cast<uint64_t>(boxes[b].nz) + 1);
+    }
+    require_box(bases < (uint64_t{1} << 31), "scene has too many cube bases");
+    boxes[b].base_begin = plan.base_begin.back();
+    boxes[b].shell_begin = plan.shell_begin.back();
+    plan.base_begin.push_back(static_cast<uint32_t>(bases));
+    plan.shell_begin.push_back(plan.shell_begin.back() +
+                               (boxes[b].nx > 0
+                                    ? iso_shell_cells(boxes[b].nx, boxes[b].ny, boxes[b].nz)
+                                    : uint64_t{0}));
+  }
+  plan.candidate_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx > 0) {
+      IndexRegion grown = regions[b];
+      for (int d = 0; d < 3; ++d) {
+        grown.lo[d] -= 1;
+        grown.hi[d] += 1;
+      }
+      append_region_candidates(boxes, regions, b, grown, levels.ratio, boxes[b].level,
+                               &plan.candidates);
+    }
+    plan.candidate_begin.push_back(static_cast<uint32_t>(plan.candidates.size()));
   }
   return plan;
 }

@@ -655,6 +655,79 @@ struct ClumpTableArgs {
 };
 int launch_clump_table(const ClumpTableArgs& args, bool has_field, void* stream);
 
+// Isosurfaces (avr_isosurface.hip): marching tetrahedra over the cubes of cell centres.  Box b
+// enumerates the cube bases (i, j, k) in [-1, n - 1]^3 of its own index space; a base's ordinal is
+// base_begin of its box + ((k + 1) (ny + 1) + (j + 1)) (nx + 1) + (i + 1), which is the output
+// order.  The cells of the box's one-cell ghost shell are numbered by iso_shell_index, from
+// shell_begin of the box on.  A box as the kernels read it:
+constexpr int kIsoMaxLevels = 16;
+constexpr uint32_t kIsoChunk = 1024;     // consecutive base ordinals one workgroup counts and emits
+constexpr uint64_t kIsoMaxCapacity = uint64_t{1} << 36;  // 12 triangles x 2^31 bases stay below it
+constexpr uint8_t kIsoAbsent = 0, kIsoCoarser = 1, kIsoSameLevel = 2;  // a shell cell's code byte
+struct alignas(16) IsoBoxDev {
+  const double* in;
+  const double* sample;   // the sample field's cells, or `in` again without one
+  uint64_t shell_begin;   // the number of the box's first shell cell
+  int32_t jstride_in, kstride_in;      // element strides (Array4); every field spans < 2^28
+  int32_t jstride_sample, kstride_sample;
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  uint32_t base_begin;    // the ordinal of the box's first cube base
+  int32_t pad_[2];
+};
+static_assert(sizeof(IsoBoxDev) == 80, "IsoBoxDev: 16-byte multiple");
+struct IsoLevelsDev {
+  double cell_size[kIsoMaxLevels][3];
+  double prob_lo[3];
+  int32_t ratio[kIsoMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
+};
+// The number of the shell cell (i, j, k) of a box of n cells, one coordinate at least outside [0,
+// n): the two k-planes of (nx + 2) (ny + 2) cells, then per k the two j-rows of nx + 2, then per
+// (k, j) the two cells at i = -1 and i = nx.
+AVR_HD inline uint64_t iso_shell_index(int nx, int ny, int nz, int i, int j, int k) {
+  const uint64_t ex = static_cast<uint64_t>(nx) + 2, ey = static_cast<uint64_t>(ny) + 2;
+  const uint64_t a = static_cast<uint64_t>(i + 1), b = static_cast<uint64_t>(j + 1);
+  if (k < 0 || k >= nz) return (k < 0 ? 0 : ex * ey) + b * ex + a;
+  const uint64_t rows = 2 * ex * ey;
+  if (j < 0 || j >= ny) return rows + static_cast<uint64_t>(k) * 2 * ex + (j < 0 ? 0 : ex) + a;
+  return rows + static_cast<uint64_t>(nz) * 2 * ex +
+         (static_cast<uint64_t>(k) * static_cast<uint64_t>(ny) + static_cast<uint64_t>(j)) * 2 +
+         (i < 0 ? 0 : 1);
+}
+AVR_HD inline uint64_t iso_shell_cells(int nx, int ny, int nz) {
+  const uint64_t ex = static_cast<uint64_t>(nx) + 2, ey = static_cast<uint64_t>(ny) + 2;
+  return 2 * ex * ey + static_cast<uint64_t>(nz) * 2 * ex +
+         static_cast<uint64_t>(nz) * static_cast<uint64_t>(ny) * 2;
+}
+struct IsoArgs {
+  const IsoBoxDev* boxes;
+  const uint32_t* base_begin;   // n_boxes + 1: prefix sum of the boxes' cube bases
+  const uint64_t* shell_begin;  // n_boxes + 1: prefix sum of the boxes' shell cells
+  const uint32_t* candidate_begin;  // n_boxes + 1: CSR over boxes, the boxes of the same or a
+  const int32_t* candidates;        // coarser level that can hold a cell of the box's shell
+  const IsoLevelsDev* levels;
+  int32_t n_boxes, n_levels;
+  uint32_t n_bases;             // < 2^31
+  uint32_t n_chunks;            // ceil(n_bases / kIsoChunk)
+  uint64_t n_shell;
+  double value;
+  uint64_t capacity;            // triangles the outputs hold
+  double* shell_value;          // [n_shell]
+  double* shell_sample;         // [n_shell], null without a sample scene
+  uint8_t* shell_code;          // [n_shell]
+  uint32_t* chunk_triangles;    // [n_chunks]
+  uint32_t* chunk_skipped;      // [n_chunks]
+  unsigned long long* chunk_offset;  // [n_chunks]: triangles before the chunk
+  unsigned long long* counts;   // [2]: T, skipped
+  double* vertices;             // [capacity][3][3]
+  uint8_t* levels_out;          // [capacity]
+  double* samples;              // [capacity][3], null without a sample scene
+};
+// Counts always; emits when emit is set (the kernel itself leaves the outputs alone if T exceeds
+// the capacity).
+int launch_isosurface(const IsoArgs& args, bool has_sample, bool emit, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

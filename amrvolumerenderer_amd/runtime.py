@@ -829,6 +829,56 @@ class Scene:
         ctx.publish()
         return cells, sums, totals
 
+    def isosurface(self, value: float, box_index_lo, level_ratio, level_cell_size, prob_lo,
+                   sample: Optional["Scene"] = None, capacity: int = 0,
+                   counts: Optional[torch.Tensor] = None):
+        """avr_scene_isosurface with this scene as the field: the isosurface field == value by
+        marching tetrahedra.  box_index_lo: [n_boxes, 3] int32; level_ratio: n_levels - 1 ints;
+        level_cell_size: [n_levels, 3] float64; prob_lo: three values; sample: a scene of the
+        same context with the same box list, interpolated at every vertex.  capacity == 0 only
+        counts.  Returns (counts int64 [2] on the device: triangles T and skipped cubes,
+        vertices float64 [capacity, 3, 3], levels uint8 [capacity], samples float64 [capacity, 3]
+        or None without sample); the three arrays are None with capacity == 0 and written iff
+        T <= capacity.  Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        capacity = int(capacity)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        if origin.shape != (3,):
+            raise ValueError("prob_lo must hold three values")
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        if counts is None:
+            counts = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+        ctx._check_tensor(counts, torch.int64, "counts")
+        if counts.numel() != 2:
+            raise ValueError("counts must hold two values")
+        vertices = levels = samples = None
+        if capacity > 0:
+            vertices = torch.empty((capacity, 3, 3), dtype=torch.float64, device=ctx.device)
+            levels = torch.empty(capacity, dtype=torch.uint8, device=ctx.device)
+            if sample is not None:
+                samples = torch.empty((capacity, 3), dtype=torch.float64, device=ctx.device)
+        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_isosurface(
+            ctx._handle, self._handle, sample._handle if sample is not None else None,
+            float(value), index.ctypes.data_as(C.POINTER(C.c_int32)),
+            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
+            int(sizes.shape[0]), capacity, pointer(vertices), pointer(levels), pointer(samples),
+            pointer(counts)))
+        ctx.publish()
+        return counts, vertices, levels, samples
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

@@ -1229,6 +1229,46 @@ int avr_scene_clump_table(avr_context *ctx, const avr_scene *labels, const avr_s
                           uint64_t n_clumps, int n_levels, uint64_t *cells_dev, double *sums_dev,
                           uint64_t *totals_dev);
 
+/* ---- isosurfaces ("Isosurface") --------------------------------------------------- */
+
+/* The isosurface field == value of `field` (a scene of ctx; raw f64 cells, no transform) by
+ * marching tetrahedra, as a triangle soup in a canonical order.  A cube has the centres of eight
+ * cells of one level l as corners, C + (di, dj, dk) with corner number c = di + 2 dj + 4 dk; the
+ * value at a level-l index G is that of the level-m box, m = l, l - 1, ..., 0, that contains G
+ * mapped to level m by floor division (the first hit wins; finer cells are never searched), and a
+ * G no such box contains is absent.  A corner always sits at prob_lo[d] + (f64(G[d]) + 0.5) *
+ * level_cell_size[l][d].  A cube is a surface cube iff every corner is present and one at least
+ * lies in a level-l box; it belongs to the box that holds its lowest-numbered such corner.  A
+ * surface cube with a non-finite corner emits nothing and counts as skipped.  Each cube is split
+ * into the six tetrahedra (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7) (0,4,5,7) (0,4,6,7); a corner
+ * is inside iff v >= value; a tetrahedron with one or three inside vertices emits one triangle,
+ * with two the quad as two; the normal (v1 - v0) x (v2 - v0) points to the v < value side.  A
+ * vertex on the edge from L (v_L < value) to H is P_L + t (P_H - P_L), t = (value - v_L) / (v_H -
+ * v_L), IEEE binary64 with nothing fused; with `sample` (a scene of ctx with the same box list,
+ * or NULL) its sample value is s_L + t (s_H - s_L).  Triangles are ordered by owner box in scene
+ * order, then by cube base k, j, i ascending over [-1, n - 1], then tetrahedron, then triangle:
+ * equal arguments give equal bits.  The hierarchy description (box_index_lo, level_ratio,
+ * n_levels <= 16; host) is avr_scene_gradient's; level_cell_size holds (dx, dy, dz) per level,
+ * prob_lo three values (host).
+ * counts_dev (device, two uint64) always gets T, the number of triangles, and the number of
+ * skipped cubes.  Iff T <= capacity the triangles are written: vertices_dev f64 [T][3][3],
+ * levels_dev u8 [T] (the owner box's level) and, with sample, samples_dev f64 [T][3]; the arrays
+ * hold `capacity` triangles.  capacity == 0 is the count-only call: the three arrays are not
+ * looked at and may be NULL.
+ * Everything is checked on the host before any device work: AVR_ERR_INVALID_ARGUMENT for a value
+ * that is not finite, n_levels outside [1, 16], a cell size that is not finite and positive, a
+ * prob_lo that is not finite, capacity >= 2^36, samples_dev given without sample or the reverse,
+ * scenes that are not congruent, a box level >= n_levels, a ratio below 2, a box index range
+ * outside [-2^30, 2^30), two boxes of one level that overlap in index space, an output array that
+ * shares a byte with an input box's cells, and 2^31 cube bases or more -- and every output is
+ * untouched.  Asynchronous on the context's stream; the context keeps grow-only scratch (9 or 17
+ * bytes per cell of the boxes' ghost shells, 16 bytes per 1024 cube bases). */
+int avr_scene_isosurface(avr_context *ctx, const avr_scene *field, const avr_scene *sample,
+                         double value, const int32_t *box_index_lo, const int32_t *level_ratio,
+                         const double *level_cell_size, const double *prob_lo, int n_levels,
+                         uint64_t capacity, double *vertices_dev, uint8_t *levels_dev,
+                         double *samples_dev, uint64_t *counts_dev);
+
 #ifdef __cplusplus
 }
 #endif
