@@ -459,6 +459,157 @@ def isosurface(plotfile: str, variable: str, value: float, fields: Sequence[str]
     return result
 
 
+# ---- streamlines ("Streamlines") ------------------------------------------------------
+
+def streamline_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeometry", seeds,
+                     cell_sizes, prob_lo, ref_ratio, step: float = 0.5, max_steps: int = 1000,
+                     direction: int = 1, sample: Optional["SceneGeometry"] = None, rank: int = 0,
+                     n_ranks: int = 1):
+    """RK4 field lines of the vector field (vx, vy, vz) -- three scenes with the same boxes --
+    from seeds [n, 3] in the plotfile's physical units ("Streamlines"): steps of step
+    times the leaf's smallest cell size along the unit vector, direction +1 or -1, at most
+    max_steps steps.  cell_sizes, prob_lo and ref_ratio as gradient_scene takes them; sample: a
+    scene with the same boxes whose field is interpolated at every point.  Returns numpy arrays
+    (points float64 [n, max_steps + 1, 3], NaN past a line's count; counts int64 [n]; status uint8
+    [n]: 0 max_steps reached, 1 outside, 2 stagnant, 3 not finite; samples float64 [n, max_steps +
+    1] or None).  Every box of the scene must be on this rank: with n_ranks > 1, or fewer local
+    boxes than boxes, NotImplementedError is raised before any device work."""
+    import numpy as np
+    from . import gradient
+    step, direction, max_steps = float(step), int(direction), int(max_steps)
+    if not (math.isfinite(step) and 0.0 < step <= 1.0):
+        raise ValueError("step must be finite and lie in (0, 1]")
+    if direction not in (1, -1):
+        raise ValueError("direction must be +1 or -1")
+    if not 0 <= max_steps <= 2 ** 20:
+        raise ValueError("max_steps must lie in [0, 2^20]")
+    local = list(vx.local_boxes)
+    if n_ranks > 1 or len(local) != len(vx.all_boxes):
+        raise NotImplementedError("streamlines need every box of the scene on one rank: "
+                                  "lines are not handed over between ranks")
+    others = [vy, vz] + ([sample] if sample is not None else [])
+    if any(len(scene.local_boxes) != len(local) for scene in others):
+        raise ValueError("the scenes must hold the same boxes")
+    start = np.ascontiguousarray(seeds, dtype=np.float64)
+    if start.ndim != 2 or start.shape[1] != 3:
+        raise ValueError("seeds must be an array [n, 3]")
+    if start.shape[0] * (max_steps + 1) >= 2 ** 32:
+        raise ValueError("n_seeds * (max_steps + 1) must stay below 2^32")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in vx.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
+    if len(ratios) != len(sizes) - 1:
+        raise ValueError("ref_ratio must hold one ratio per level transition")
+    origin = [float(v) for v in prob_lo]
+    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
+                                  vx.world_scale, origin, sizes)
+    fields = [ctx.create_scene(scene.local_boxes, scene.scalar_transform)
+              for scene in [vx] + others]
+    try:
+        points, samples, counts, status = fields[0].streamlines(
+            fields[1], fields[2], start, step, direction, max_steps, index, ratios, sizes, origin,
+            fields[3] if sample is not None else None)
+        ctx.synchronize()
+        points, counts, status = points.cpu().numpy(), counts.cpu().numpy(), status.cpu().numpy()
+        if samples is not None:
+            samples = samples.cpu().numpy()
+    finally:
+        for scene in fields:
+            scene.close()
+    return points, counts.astype(np.int64), status, samples
+
+
+_DIRECTIONS = {"forward": (1,), "backward": (-1,), "both": (-1, 1)}
+
+
+def streamlines(plotfile: str,
+                variables: Sequence[str] = ("x-velocity", "y-velocity", "z-velocity"),
+                seeds=(), step: float = 0.5, max_steps: int = 1000, direction: str = "forward",
+                fields: Sequence[str] = (), min_level: int = 0, max_level: int = -1,
+                output: Optional[str] = None) -> dict:
+    """Field lines of a plotfile's vector field ("Streamlines"), on cuda:0, through
+    the uncovered cells of the loaded levels: classical RK4 along the unit vector of the three
+    variables, trilinear between cell centres and piecewise constant in the one-cell layer next to
+    a domain face, a hole or a finer region.  variables and every name of fields is a stored
+    variable or a registered derived, gradient or clump field; seeds: [n, 3] in the plotfile's
+    physical units; direction "forward", "backward" or "both" (a backward and a forward call,
+    joined as the backward line reversed, then the forward line, the seed kept once).  Returns a
+    dict: n (lines), lines (a list of float64 [count_i, 3]; empty for a seed outside the loaded
+    cells), status uint8 [n] (0 max_steps reached, 1 outside, 2 stagnant, 3 not finite; [n, 2] =
+    (backward, forward) with "both"), length float64 [n] (math.fsum of a line's segment lengths)
+    and samples {name: list of float64 [count_i]} (each requested field at every point, NaN at a
+    final point that is outside).  With output the lines are written as a legacy-VTK ASCII file,
+    the samples as point scalars (lines.save_vtk_lines)."""
+    import numpy as np
+    from . import lines as line_rules
+    from . import plotfile as pf
+    if direction not in _DIRECTIONS:
+        raise ValueError('direction must be "forward", "backward" or "both"')
+    components = [str(name) for name in variables]
+    if len(components) != 3:
+        raise ValueError("variables must name the three components")
+    names = [str(name) for name in fields]
+    start = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3)
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, components + names,
+                                                            min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    arguments = (header.cell_size[:n_levels], header.prob_lo, header.ref_ratio[:n_levels - 1],
+                 float(step), int(max_steps))
+    passes = []        # per direction (lines, status, {name: values per line})
+    for sign in _DIRECTIONS[direction]:
+        sampled = {}
+        for name, scene in zip(names or [None], scenes[3:] or [None]):
+            points, counts, status, values = streamline_scene(ctx, *scenes[:3], start, *arguments,
+                                                              sign, scene, rank, world)
+            if name is not None:
+                sampled[name] = [values[i, :int(c)].copy() for i, c in enumerate(counts.tolist())]
+        passes.append((line_rules.split_lines(points, counts), status, sampled))
+    if len(passes) == 2:
+        (back, back_status, back_values), (ahead, ahead_status, ahead_values) = passes
+        found = line_rules.join_both(back, ahead)
+        status = np.stack([back_status, ahead_status], axis=1)
+        samples = {name: line_rules.join_both(back_values[name], ahead_values[name])
+                   for name in names}
+    else:
+        found, status, samples = passes[0]
+    result = {"n": len(found), "lines": found, "status": status,
+              "length": line_rules.line_lengths(found), "samples": samples}
+    if output:
+        line_rules.save_vtk_lines(found, output, samples)
+    return result
+
+
+def sample_points(plotfile: str, points, fields: Sequence[str], min_level: int = 0,
+                  max_level: int = -1):
+    """The value of every field of fields at every point of points [n, 3] (the plotfile's physical
+    units), on cuda:0, by the streamlines' rule ("Streamlines"): trilinear between the
+    eight cell centres around the point if all are present (the same level as the point's leaf, or
+    coarser) and finite, else the value of the leaf cell itself.  Returns ({name: float64 [n]},
+    inside bool [n]): a point outside the loaded cells has NaN and inside False.  A thin wrapper:
+    lines of no steps, the field itself as the three components and as the sample."""
+    import numpy as np
+    from . import plotfile as pf
+    names = [str(name) for name in fields]
+    if not names:
+        raise ValueError("sample_points needs at least one field")
+    at = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, names, min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    values, inside = {}, np.zeros(at.shape[0], dtype=bool)
+    for name, scene in zip(names, scenes):
+        _, counts, _, sampled = streamline_scene(
+            ctx, scene, scene, scene, at, header.cell_size[:n_levels], header.prob_lo,
+            header.ref_ratio[:n_levels - 1], 1.0, 0, 1, scene, rank, world)
+        values[name] = sampled[:, 0].copy()
+        inside = counts == 1
+    return values, inside
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:

@@ -2190,6 +2190,54 @@ int avr_scene_isosurface(avr_context* ctx, const avr_scene* field, const avr_sce
   });
 }
 
+int avr_scene_streamlines(avr_context* ctx, const avr_scene* vx, const avr_scene* vy,
+                          const avr_scene* vz, const avr_scene* sample, const double* seeds_dev,
+                          uint64_t n_seeds, double step, int direction, uint64_t max_steps,
+                          const int32_t* box_index_lo, const int32_t* level_ratio,
+                          const double* level_cell_size, const double* prob_lo, int n_levels,
+                          double* points_dev, double* samples_dev, uint32_t* counts_dev,
+                          uint8_t* status_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(vx != nullptr && vy != nullptr && vz != nullptr && level_cell_size != nullptr &&
+                prob_lo != nullptr, "null argument");
+    const size_t n_boxes = vx->boxes.size();
+    require_field_scene(ctx, vx, n_boxes);
+    require_field_scene(ctx, vy, n_boxes);
+    require_field_scene(ctx, vz, n_boxes);
+    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
+    avr::StreamPlan plan = avr::plan_streamlines(
+        vx->boxes.data(), vy->boxes.data(), vz->boxes.data(),
+        sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, n_seeds, step, direction,
+        max_steps, box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, seeds_dev,
+        points_dev, samples_dev, counts_dev, status_dev);
+    if (n_seeds == 0) return AVR_OK;
+    if (plan.boxes.empty()) plan.boxes.resize(1);          // never read: no block lists it
+    if (plan.block_boxes.empty()) plan.block_boxes.push_back(0);  // never read: every list is empty
+    avr::StreamArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::StreamBoxDev) +
+                           plan.block_begin.size() * sizeof(uint32_t) +
+                           plan.block_boxes.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
+    args.block_begin = ctx->staging.add(plan.block_begin.data(), plan.block_begin.size());
+    args.block_boxes = ctx->staging.add(plan.block_boxes.data(), plan.block_boxes.size());
+    ctx->staging.commit(ctx->stream);
+    args.locator = plan.locator;
+    args.n_levels = n_levels;
+    args.n_seeds = static_cast<uint32_t>(n_seeds);
+    args.max_steps = static_cast<uint32_t>(max_steps);
+    args.step = step;
+    args.direction = static_cast<double>(direction);
+    args.seeds = seeds_dev;
+    args.points = points_dev;
+    args.samples = sample != nullptr ? samples_dev : nullptr;
+    args.counts = counts_dev;
+    args.status = status_dev;
+    return avr::launch_streamlines(args, sample != nullptr, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

@@ -1,5 +1,5 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps, isosurfaces): everything a call works out from its arguments before
+// derived fields, gradient fields, clumps, isosurfaces, streamlines): everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
 // rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
@@ -785,6 +785,211 @@ inline IsoPlan plan_isosurface(const avr_box* field, const avr_box* sample, size
                                &plan.candidates);
     }
     plan.candidate_begin.push_back(static_cast<uint32_t>(plan.candidates.size()));
+  }
+  return plan;
+}
+
+// ---- streamlines --------------------------------------------------------------------------
+struct StreamPlan {
+  std::vector<StreamBoxDev> boxes;
+  IsoLevelsDev levels;
+  // the locator (StreamLocatorDev): CSR over its blocks, per block the boxes of any level whose
+  // cells, mapped to level 0, meet it, finest level first, then in scene order
+  StreamLocatorDev locator;
+  std::vector<uint32_t> block_begin;  // blocks + 1 ({0} for a scene without cells)
+  std::vector<int32_t> block_boxes;
+};
+// The blocks of the locator: the smallest power-of-two side that leaves at most `limit` blocks over
+// the level-0 index range [lo, hi].
+inline void size_stream_locator(const int64_t lo[3], const int64_t hi[3], int64_t limit,
+                                StreamLocatorDev* locator) {
+  for (int shift = 0; shift <= 31; ++shift) {
+    int64_t n[3], blocks = 1;
+    for (int d = 0; d < 3; ++d) {
+      n[d] = ((hi[d] - lo[d]) >> shift) + 1;
+      blocks *= n[d];  // n[d] <= 2^31 and limit <= 2^24: compared before the next factor
+      if (blocks > limit) break;
+    }
+    if (blocks > limit) continue;
+    for (int d = 0; d < 3; ++d) {
+      locator->origin[d] = static_cast<int32_t>(lo[d]);
+      locator->n[d] = static_cast<int32_t>(n[d]);
+    }
+    locator->shift = shift;
+    return;
+  }
+}
+// vx, vy, vz: the boxes of the three components; sample (may be null): those of the sample field.
+// box_index_lo, level_ratio, level_cell_size and prob_lo as plan_isosurface takes them.  seeds,
+// points, samples, counts and status are device arrays of n_seeds lines of max_steps + 1 points
+// (free to be null with n_seeds == 0, samples null exactly without a sample scene).  The rules, in
+// this order: step, direction, max_steps, the number of points, n_levels, null arrays, the cell
+// sizes, prob_lo, samples_dev, the box rules (vx is the reference, so an incongruent vy, vz or
+// sample scene is refused here), the ratios, the index ranges, boxes of one level apart in index
+// space, no output byte and no seed shared with an input, the locator's size (max_entries: the
+// bound on its lists, lowered by the plan's test only).
+inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const avr_box* vz,
+                                   const avr_box* sample, size_t n_boxes, uint64_t n_seeds,
+                                   double step, int direction, uint64_t max_steps,
+                                   const int32_t* box_index_lo, const int32_t* level_ratio,
+                                   const double* level_cell_size, const double* prob_lo,
+                                   int n_levels, const void* seeds, const void* points,
+                                   const void* samples, const void* counts, const void* status,
+                                   int64_t max_entries = kStreamMaxEntries) {
+  require_box(std::isfinite(step) && step > 0.0 && step <= 1.0,
+              "step must be finite and lie in (0, 1]");
+  require_box(direction == 1 || direction == -1, "direction must be +1 or -1");
+  require_box(max_steps <= kStreamMaxSteps, "max_steps must not exceed 2^20");
+  // n_seeds < 2^32 first: the product then stays inside 64 bits
+  require_box(n_seeds < (uint64_t{1} << 32) && n_seeds * (max_steps + 1) < (uint64_t{1} << 32),
+              "n_seeds * (max_steps + 1) must stay below 2^32");
+  require_box(n_levels >= 1 && n_levels <= kStreamMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  require_box(n_seeds == 0 || (seeds != nullptr && points != nullptr && counts != nullptr &&
+                               status != nullptr), "null argument");
+  StreamPlan plan;
+  IsoLevelsDev& levels = plan.levels;
+  std::memset(&levels, 0, sizeof(levels));
+  for (int l = 0; l < n_levels; ++l) {
+    for (int d = 0; d < 3; ++d) {
+      const double size = level_cell_size[l * 3 + d];
+      require_box(std::isfinite(size) && size > 0.0, "level_cell_size must be finite and positive");
+      levels.cell_size[l][d] = size;
+    }
+  }
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(prob_lo[d]), "prob_lo must be finite");
+    levels.prob_lo[d] = prob_lo[d];
+  }
+  require_box((samples != nullptr) == (sample != nullptr),
+              "samples_dev is given exactly when sample is");
+  std::vector<StreamBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = vx[b];
+    const avr_box* fields[4] = {&first, &vy[b], &vz[b], sample != nullptr ? &sample[b] : &first};
+    FieldView views[4];
+    StreamBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool cells = field_box_views(first, fields, 4, n_levels, views, &paired);
+    for (int f = 0; f < 4; ++f) {
+      dev.cells[f] = views[f].cells;
+      dev.jstride[f] = views[f].jstride;
+      dev.kstride[f] = views[f].kstride;
+      if (cells && (f < 3 || sample != nullptr)) append_byte_range(&read_ranges, views[f]);
+    }
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+  }
+  for (int l = 0; l < kIsoMaxLevels; ++l) levels.ratio[l] = 1;
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
+    levels.ratio[l] = level_ratio[l];
+  }
+  std::vector<IndexRegion> regions(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx <= 0) continue;
+    for (int d = 0; d < 3; ++d) {
+      const int64_t lo = box_index_lo[b * 3 + d];
+      boxes[b].lo[d] = box_index_lo[b * 3 + d];
+      regions[b].lo[d] = lo;
+      regions[b].hi[d] = lo + vx[b].dims[d] - 1;
+      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
+                  "a box's index range leaves [-2^30, 2^30)");
+    }
+  }
+  for (size_t b = 0; b < n_boxes; ++b) {
+    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
+      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
+                      !regions_meet(regions[b], regions[c]),
+                  "two boxes of one level overlap in index space");
+    }
+  }
+  if (n_seeds > 0) {
+    auto touched = [&](const void* at, uint64_t bytes) {
+      const uintptr_t begin = reinterpret_cast<uintptr_t>(at);
+      write_ranges.emplace_back(begin, begin + static_cast<uintptr_t>(bytes) - 1);
+    };
+    const uint64_t slots = n_seeds * (max_steps + 1);
+    touched(seeds, n_seeds * 3 * sizeof(double));
+    touched(points, slots * 3 * sizeof(double));
+    if (samples != nullptr) touched(samples, slots * sizeof(double));
+    touched(counts, n_seeds * sizeof(uint32_t));
+    touched(status, n_seeds);
+    require_no_shared_byte(&read_ranges, write_ranges,
+                           "an output array or the seeds overlap an input box's cells");
+  }
+  // the locator: every box mapped to level 0, the blocks over their bounding box, the lists
+  std::memset(&plan.locator, 0, sizeof(plan.locator));
+  plan.block_begin.assign(1, 0u);
+  std::vector<IndexRegion> coarse(n_boxes);  // [b]: box b at level 0
+  std::vector<size_t> order;                 // the boxes with cells, finest level first
+  int64_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx <= 0) continue;
+    coarse[b] = regions[b];
+    for (int m = boxes[b].level; m > 0; --m) {
+      for (int d = 0; d < 3; ++d) {
+        coarse[b].lo[d] = floor_div(coarse[b].lo[d], levels.ratio[m - 1]);
+        coarse[b].hi[d] = floor_div(coarse[b].hi[d], levels.ratio[m - 1]);
+      }
+    }
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = order.empty() ? coarse[b].lo[d] : std::min(lo[d], coarse[b].lo[d]);
+      hi[d] = order.empty() ? coarse[b].hi[d] : std::max(hi[d], coarse[b].hi[d]);
+    }
+    order.push_back(b);
+  }
+  if (order.empty()) return plan;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](size_t x, size_t y) { return boxes[x].level > boxes[y].level; });
+  // a few blocks per box keep the lists short; 2^24 blocks at the most
+  const int64_t limit = std::min(kStreamMaxBlocks, 64 + 8 * static_cast<int64_t>(order.size()));
+  size_stream_locator(lo, hi, limit, &plan.locator);
+  const StreamLocatorDev& locator = plan.locator;
+  const size_t blocks = static_cast<size_t>(locator.n[0]) * locator.n[1] * locator.n[2];
+  auto block_range = [&](size_t b, int64_t first[3], int64_t last[3]) {
+    for (int d = 0; d < 3; ++d) {
+      first[d] = (coarse[b].lo[d] - lo[d]) >> locator.shift;
+      last[d] = (coarse[b].hi[d] - lo[d]) >> locator.shift;
+    }
+  };
+  // the lists' size from the boxes' extents, before anything of that size is made
+  uint64_t entries = 0;
+  for (size_t b : order) {
+    int64_t first[3], last[3];
+    block_range(b, first, last);
+    entries += static_cast<uint64_t>(last[0] - first[0] + 1) *
+               static_cast<uint64_t>(last[1] - first[1] + 1) *
+               static_cast<uint64_t>(last[2] - first[2] + 1);  // at most 2^24 each
+    require_box(entries < static_cast<uint64_t>(max_entries),
+                "the locator's lists hold 2^28 entries or more");
+  }
+  auto for_blocks = [&](size_t b, auto&& visit) {
+    int64_t first[3], last[3];
+    block_range(b, first, last);
+    for (int64_t z = first[2]; z <= last[2]; ++z) {
+      for (int64_t y = first[1]; y <= last[1]; ++y) {
+        for (int64_t x = first[0]; x <= last[0]; ++x) {
+          visit(static_cast<size_t>((z * locator.n[1] + y) * locator.n[0] + x));
+        }
+      }
+    }
+  };
+  std::vector<uint32_t> fill(blocks + 1, 0u);
+  for (size_t b : order) for_blocks(b, [&](size_t block) { ++fill[block + 1]; });
+  for (size_t block = 0; block < blocks; ++block) fill[block + 1] += fill[block];
+  plan.block_begin.assign(fill.begin(), fill.end());
+  plan.block_boxes.resize(static_cast<size_t>(fill[blocks]));
+  for (size_t b : order) {
+    for_blocks(b, [&](size_t block) { plan.block_boxes[fill[block]++] = static_cast<int32_t>(b); });
   }
   return plan;
 }

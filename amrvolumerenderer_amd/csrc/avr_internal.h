@@ -728,6 +728,54 @@ struct IsoArgs {
 // the capacity).
 int launch_isosurface(const IsoArgs& args, bool has_sample, bool emit, void* stream);
 
+// Streamlines (avr_streamlines.hip): RK4 field lines of three congruent scenes through the leaf
+// cells, one lane per seed.  A box as the kernel reads it: field 0..2 are the velocity components,
+// field 3 the sample field (the first component again without one).
+constexpr int kStreamMaxLevels = 16;
+constexpr uint32_t kStreamMaxSteps = 1u << 20;
+constexpr int64_t kStreamMaxBlocks = int64_t{1} << 24;   // of the locator
+constexpr int64_t kStreamMaxEntries = int64_t{1} << 28;  // of the locator's lists, all blocks
+constexpr uint8_t kStreamMaxStepsReached = 0, kStreamOutside = 1, kStreamStagnant = 2,
+                  kStreamNonFinite = 3;  // a line's status byte
+struct alignas(16) StreamBoxDev {
+  const double* cells[4];
+  int32_t jstride[4];     // element strides (Array4); every field spans < 2^28 elements
+  int32_t kstride[4];
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t pad_[1];
+};
+static_assert(sizeof(StreamBoxDev) == 96, "StreamBoxDev: 16-byte multiple");
+// The locator: a uniform grid of n[0] x n[1] x n[2] blocks of (1 << shift)^3 level-0 cells from
+// the level-0 index `origin` on, which covers every box mapped to level 0 by floor division.  Block
+// (bx, by, bz) has the number (bz n[1] + by) n[0] + bx; its list is entries [begin[number],
+// begin[number + 1]): the boxes of any level whose cells, mapped to level 0, meet the block, finest
+// level first, then in scene order.  n[0] == 0: the scene has no cells.
+struct StreamLocatorDev {
+  int32_t origin[3];
+  int32_t n[3];
+  int32_t shift;
+  int32_t pad_;
+};
+struct StreamArgs {
+  const StreamBoxDev* boxes;
+  const uint32_t* block_begin;  // blocks + 1
+  const int32_t* block_boxes;
+  const IsoLevelsDev* levels;   // cell sizes, prob_lo and ratios as the isosurfaces stage them
+  StreamLocatorDev locator;
+  int32_t n_levels;
+  uint32_t n_seeds;
+  uint32_t max_steps;           // <= kStreamMaxSteps; n_seeds * (max_steps + 1) < 2^32
+  double step, direction;       // direction: +1.0 or -1.0
+  const double* seeds;          // [n_seeds][3]
+  double* points;               // [n_seeds][max_steps + 1][3]
+  double* samples;              // [n_seeds][max_steps + 1], null without a sample scene
+  uint32_t* counts;             // [n_seeds]
+  uint8_t* status;              // [n_seeds]
+};
+int launch_streamlines(const StreamArgs& args, bool has_sample, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

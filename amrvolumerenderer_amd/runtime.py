@@ -7,6 +7,7 @@ depth hints, layer order, piece ranges) work without a GPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -878,6 +879,64 @@ class Scene:
             pointer(counts)))
         ctx.publish()
         return counts, vertices, levels, samples
+
+    def streamlines(self, vy: "Scene", vz: "Scene", seeds, step: float, direction: int,
+                    max_steps: int, box_index_lo, level_ratio, level_cell_size, prob_lo,
+                    sample: Optional["Scene"] = None):
+        """avr_scene_streamlines with this scene as the x component: RK4 field lines of (this
+        scene, vy, vz) -- scenes of the same context with the same box list -- from seeds
+        (float64 [n, 3] in physical units; a tensor on the device, or anything numpy takes).
+        step in (0, 1] cell sizes of the leaf; direction +1 or -1; box_index_lo: [n_boxes, 3]
+        int32; level_ratio: n_levels - 1 ints; level_cell_size: [n_levels, 3] float64; prob_lo:
+        three values; sample: a scene with the same box list, interpolated at every point.
+        Returns (points float64 [n, max_steps + 1, 3], samples float64 [n, max_steps + 1] or None
+        without sample, counts int32 [n], status uint8 [n]: 0 max_steps reached, 1 outside, 2
+        stagnant, 3 not finite) on the device; points and samples past a line's count are NaN.
+        Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        max_steps = int(max_steps)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        if origin.shape != (3,):
+            raise ValueError("prob_lo must hold three values")
+        if max_steps < 0:
+            raise ValueError("max_steps must not be negative")
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3))
+        seeds = seeds.to(device=ctx.device, dtype=torch.float64).contiguous()
+        if seeds.ndim != 2 or seeds.shape[1] != 3:
+            raise ValueError("seeds must hold three values per seed")
+        n = int(seeds.shape[0])
+        points = torch.full((n, max_steps + 1, 3), math.nan, dtype=torch.float64,
+                            device=ctx.device)
+        samples = None
+        if sample is not None:
+            samples = torch.full((n, max_steps + 1), math.nan, dtype=torch.float64,
+                                 device=ctx.device)
+        counts = torch.zeros(n, dtype=torch.int32, device=ctx.device)
+        status = torch.zeros(n, dtype=torch.uint8, device=ctx.device)
+        if n == 0:                     # nothing to launch, and empty tensors have no address
+            return points, samples, counts, status
+        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_streamlines(
+            ctx._handle, self._handle, vy._handle, vz._handle,
+            sample._handle if sample is not None else None, pointer(seeds), n, float(step),
+            int(direction), max_steps, index.ctypes.data_as(C.POINTER(C.c_int32)),
+            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
+            int(sizes.shape[0]), pointer(points), pointer(samples), pointer(counts),
+            pointer(status)))
+        ctx.publish()
+        return points, samples, counts, status
 
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the

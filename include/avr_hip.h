@@ -1269,6 +1269,55 @@ int avr_scene_isosurface(avr_context *ctx, const avr_scene *field, const avr_sce
                          uint64_t capacity, double *vertices_dev, uint8_t *levels_dev,
                          double *samples_dev, uint64_t *counts_dev);
 
+/* ---- streamlines ("Streamlines") ---------------------------------------------------- */
+
+/* Field lines of the vector field (vx, vy, vz) -- three scenes of ctx with the same box list; raw
+ * f64 cells, no transform -- from n_seeds seeds (seeds_dev: device, f64 [n][3], physical units)
+ * by classical RK4 along the unit vector, IEEE binary64 with nothing fused, / and sqrt correctly
+ * rounded.  The hierarchy description (box_index_lo, level_ratio, n_levels <= 16; host) is
+ * avr_scene_gradient's; level_cell_size holds (dx, dy, dz) per level, prob_lo three values (host).
+ * The leaf of a point P: for l = n_levels - 1, ..., 0, q[d] = (P[d] - prob_lo[d]) / dx[l][d]; a q[d]
+ * that is not finite or lies outside [-2^30, 2^30) makes P outside; else the first level whose
+ * boxes contain G = floor(q) gives the leaf (box, G, l); none: outside.  The value at P with leaf
+ * level l: u = q - 0.5, C = floor(u), w = u - f64(C); the corners C + (di, dj, dk) are found as
+ * avr_scene_isosurface finds a cube's (level l, then l - 1, ..., 0 by floor division; the first
+ * hit wins; finer cells are never searched); with all eight present and every value finite the
+ * value is trilinear -- a = v0 + w[0] * (v1 - v0) along x for the four (dj, dk), then the same
+ * form along y, then z -- else it is the leaf cell's own value.  The three components share one
+ * decision: trilinear iff all eight corners are present and all 24 values finite, else all three
+ * from the leaf cell, and a leaf velocity with a component that is not finite ends the line.
+ * D(P) = direction * V / |V|, |V| = sqrt((vx * vx + vy * vy) + vz * vz); |V| == 0 is stagnant.
+ * A step from P with leaf level l: h = step * min_d dx[l][d]; k1 = D(P), k2 = D(P + (0.5 * h) *
+ * k1), k3 = D(P + (0.5 * h) * k2), k4 = D(P + h * k3); P' = P + (h / 6.0) * (((k1 + 2.0 * k2) +
+ * 2.0 * k3) + k4).  If one of the four evaluations is outside, stagnant or not finite (the first
+ * stage that fails decides; within a stage in that order) no step is taken and the line ends at P
+ * with that status; P' is appended even if it is outside itself, and the next step then ends the
+ * line.  Line s: a seed that is outside (a NaN coordinate included) gives counts_dev[s] = 0 and
+ * status 1; else point 0 is the seed and steps follow until one ends the line or max_steps were
+ * taken.  status_dev[s] (device, u8): 0 max_steps reached, 1 outside, 2 stagnant, 3 not finite;
+ * counts_dev[s] (device, u32) in 0 .. max_steps + 1; points_dev (device, f64 [n][max_steps + 1][3])
+ * holds the line's points and, with `sample` (a scene of ctx with the same box list, or NULL),
+ * samples_dev (device, f64 [n][max_steps + 1]) the sample field at every point by the same rule
+ * on its own (trilinear iff its eight corners are present and finite, else the leaf value,
+ * whatever it is), NaN at a final point that is outside.  Slots past a line's count are left
+ * untouched.  Equal arguments give equal bits.  n_seeds == 0 succeeds without a launch.
+ * Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for a step that is not finite or not in (0, 1], a direction other than
+ * +1 and -1, max_steps > 2^20, n_seeds * (max_steps + 1) >= 2^32, n_levels outside [1, 16], a
+ * cell size that is not finite and positive, a prob_lo that is not finite, samples_dev given
+ * without sample or the reverse, scenes that are not congruent, a box level >= n_levels, a ratio
+ * below 2, a box index range outside [-2^30, 2^30), two boxes of one level that overlap in index
+ * space, an output array or the seeds sharing a byte with an input box's cells, and a locator of
+ * 2^28 list entries or more -- and every output is untouched.  Stateless; asynchronous on the
+ * context's stream. */
+int avr_scene_streamlines(avr_context *ctx, const avr_scene *vx, const avr_scene *vy,
+                          const avr_scene *vz, const avr_scene *sample, const double *seeds_dev,
+                          uint64_t n_seeds, double step, int direction, uint64_t max_steps,
+                          const int32_t *box_index_lo, const int32_t *level_ratio,
+                          const double *level_cell_size, const double *prob_lo, int n_levels,
+                          double *points_dev, double *samples_dev, uint32_t *counts_dev,
+                          uint8_t *status_dev);
+
 #ifdef __cplusplus
 }
 #endif
