@@ -213,6 +213,27 @@ def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"]
     return result
 
 
+# ---- the level setup of the products that cross levels -------------------------------------------
+
+def _level_setup(scene: "SceneGeometry", local, cell_sizes, prob_lo, ref_ratio):
+    """(sizes, ratios, box_index_lo) as the native calls of the gradient fields, clumps,
+    isosurfaces and streamlines take them: cell_sizes as float triples per level up to the finest
+    loaded one, one ref_ratio per level transition, and the index of every local box's first cell
+    recovered from its corner (gradient.box_index_lo)."""
+    from . import gradient
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in scene.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
+    if len(ratios) != len(sizes) - 1:
+        raise ValueError("ref_ratio must hold one ratio per level transition")
+    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
+                                  scene.world_scale, prob_lo, sizes)
+    return sizes, ratios, index
+
+
 # ---- gradient fields (DESIGN.md 7, "Gradient fields") --------------------------------------------
 
 def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, ref_ratio,
@@ -229,7 +250,6 @@ def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, 
     and statistics and the scalar transform come from build_scene_geometry with the caller's flags.
     Every box of the scene must be on this rank: with n_ranks > 1, or fewer local boxes than
     boxes, NotImplementedError is raised before any device work."""
-    from . import gradient
     axis = int(axis)
     if axis not in (0, 1, 2):
         raise ValueError("axis must be 0 (x), 1 (y) or 2 (z)")
@@ -237,16 +257,7 @@ def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, 
     if n_ranks > 1 or len(local) != len(scene.all_boxes):
         raise NotImplementedError("a gradient field needs every box of the scene on one rank: "
                                   "ghost cells are not exchanged between ranks")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in scene.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
-    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
-    if len(ratios) != len(sizes) - 1:
-        raise ValueError("ref_ratio must hold one ratio per level transition")
-    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
-                                  scene.world_scale, prob_lo, sizes)
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
     out_boxes = _allocate_like(ctx, local, rank)
     field = ctx.create_scene(local, scene.scalar_transform)
     out = ctx.create_scene(out_boxes, ScalarTransform())
@@ -278,22 +289,12 @@ def clump_scene(ctx, scene: "SceneGeometry", lower: float, upper: float, cell_si
     be on this rank: with n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is
     raised before any device work."""
     from . import clumps as clump_rules
-    from . import gradient
     lower, upper = clump_rules.check_bounds(lower, upper)
     local = list(scene.local_boxes)
     if n_ranks > 1 or len(local) != len(scene.all_boxes):
         raise NotImplementedError("clumps need every box of the scene on one rank: "
                                   "labels are not merged between ranks")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in scene.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
-    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
-    if len(ratios) != len(sizes) - 1:
-        raise ValueError("ref_ratio must hold one ratio per level transition")
-    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
-                                  scene.world_scale, prob_lo, sizes)
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
     out_boxes = _allocate_like(ctx, local, rank)
     field = ctx.create_scene(local, scene.scalar_transform)
     out = ctx.create_scene(out_boxes, ScalarTransform())
@@ -376,7 +377,6 @@ def isosurface_scene(ctx, scene: "SceneGeometry", value: float, cell_sizes, prob
     allocated, a second call emits.  Every box of the scene must be on this rank: with n_ranks >
     1, or fewer local boxes than boxes, NotImplementedError is raised before any device work."""
     import numpy as np
-    from . import gradient
     value = float(value)
     if not math.isfinite(value):
         raise ValueError("an isosurface's value must be finite")
@@ -386,17 +386,8 @@ def isosurface_scene(ctx, scene: "SceneGeometry", value: float, cell_sizes, prob
                                   "ghost cells are not exchanged between ranks")
     if sample is not None and len(sample.local_boxes) != len(local):
         raise ValueError("the sample scene must hold the same boxes as the scene")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in scene.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
-    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
-    if len(ratios) != len(sizes) - 1:
-        raise ValueError("ref_ratio must hold one ratio per level transition")
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
     origin = [float(v) for v in prob_lo]
-    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
-                                  scene.world_scale, origin, sizes)
     field = ctx.create_scene(local, scene.scalar_transform)
     other = ctx.create_scene(sample.local_boxes, sample.scalar_transform) \
         if sample is not None else None
@@ -475,7 +466,6 @@ def streamline_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGe
     1] or None).  Every box of the scene must be on this rank: with n_ranks > 1, or fewer local
     boxes than boxes, NotImplementedError is raised before any device work."""
     import numpy as np
-    from . import gradient
     step, direction, max_steps = float(step), int(direction), int(max_steps)
     if not (math.isfinite(step) and 0.0 < step <= 1.0):
         raise ValueError("step must be finite and lie in (0, 1]")
@@ -495,17 +485,8 @@ def streamline_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGe
         raise ValueError("seeds must be an array [n, 3]")
     if start.shape[0] * (max_steps + 1) >= 2 ** 32:
         raise ValueError("n_seeds * (max_steps + 1) must stay below 2^32")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in vx.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
-    ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
-    if len(ratios) != len(sizes) - 1:
-        raise ValueError("ref_ratio must hold one ratio per level transition")
+    sizes, ratios, index = _level_setup(vx, local, cell_sizes, prob_lo, ref_ratio)
     origin = [float(v) for v in prob_lo]
-    index = gradient.box_index_lo([b.min_corner for b in local], [b.level for b in local],
-                                  vx.world_scale, origin, sizes)
     fields = [ctx.create_scene(scene.local_boxes, scene.scalar_transform)
               for scene in [vx] + others]
     try:

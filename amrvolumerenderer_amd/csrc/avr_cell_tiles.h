@@ -2,7 +2,8 @@
 // tile = 4 k-planes x 4 j-rows x 128 cells along x of one box, the tiles of a box numbered chunk
 // fastest, then the brick of rows along y, then along z.  The host's count and the device's decode
 // of a tile number live here together (tests/cxx/field_boxes_test.cpp holds one against the other),
-// with the search that finds a tile's box in the prefix sums of the boxes' tiles.
+// with the device's shared steps: the search that finds a tile's box in the prefix sums of the
+// boxes' tiles and the workgroup's prefix sum.
 #ifndef AVR_CELL_TILES_H
 #define AVR_CELL_TILES_H
 
@@ -52,21 +53,46 @@ AVR_HD inline __attribute__((always_inline)) CellTile cell_tile_of(int nx, int n
 }
 
 #if defined(__HIP__)
-// The box that tile number `tile` belongs to: the largest b with tile_begin[b] <= tile (binary
-// search over the prefix sums).  P: a pointer to uint32_t in whichever address space the kernel
-// reads the prefix sums through.
-template <typename P>
-__device__ __forceinline__ int locate_box(P tile_begin, int n_boxes, uint32_t tile) {
+// The box that entry number `at` of a prefix sum belongs to: the largest b with begin[b] <= at
+// (binary search).  P: a pointer to T, the sums' type, in whichever address space the kernel reads
+// them through.
+template <typename P, typename T>
+__device__ __forceinline__ int locate_box(P begin, int n_boxes, T at) {
   int lo = 0, hi = n_boxes;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
-    if (tile_begin[mid] <= tile) {
+    if (begin[mid] <= at) {
       lo = mid;
     } else {
       hi = mid;
     }
   }
   return lo;
+}
+
+// The sum of v over the workgroup's THREADS lanes before this one, and over all of them.  `slot` <
+// SLOTS: the caller's call number, each call of a kernel has its own LDS.
+template <int THREADS, int SLOTS>
+__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, int slot, uint32_t* total) {
+  __shared__ uint32_t wave_sums[SLOTS][THREADS / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t inclusive = v;
+#pragma unroll
+  for (int step = 1; step < 64; step <<= 1) {
+    const uint32_t below = __shfl_up(inclusive, step, 64);
+    if (lane >= static_cast<uint32_t>(step)) inclusive += below;
+  }
+  if (lane == 63u) wave_sums[slot][wave] = inclusive;
+  __syncthreads();
+  uint32_t before = inclusive - v, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < THREADS / 64; ++w) {
+    const uint32_t s = wave_sums[slot][w];
+    if (w < wave) before += s;
+    all += s;
+  }
+  *total = all;
+  return before;
 }
 #endif
 

@@ -21,10 +21,10 @@
 // 128 cells of one box, 16 consecutive tiles per workgroup), one cell per lane and pass, so that a
 // wave holds 64 consecutive cells of one row: init links every run of selected cells inside a
 // wave's 64 to the run's first cell by a ballot, before anything goes to memory, and merge then
-// has no union to make along x but at a wave's last cell.  The ghost of a face cell is found as
-// gradient_halo_kernel finds its same-or-coarser hit: only the boxes the host listed for the face
-// are tested, the highest level that holds the mapped index wins.  Only cells of the scene's
-// boxes are ever read.
+// has no union to make along x but at a wave's last cell.  The ghost of a face cell is found by
+// the same-or-coarser rule (avr_level_cells.h states it; unite_ghost writes the loop out, with
+// the use of the hit inside it) among the boxes the host listed for the face.  Only cells of the
+// scene's boxes are ever read.
 //
 // Every loop is bounded by a count known at launch, or is the find or the union below.  No lane
 // waits for a value another workgroup writes.
@@ -170,14 +170,11 @@ __device__ __forceinline__ void unite(uint32_t* parent, uint32_t u, uint32_t v) 
   }
 }
 
-__device__ __forceinline__ long long floor_div(long long a, long long r) {
-  const long long q = a / r;
-  return (a % r != 0 && a < 0) ? q - 1 : q;
-}
-
 // Unites cell x of box b with the cell that holds the ghost index (gx, gy, gz) of the box's level
 // past face `face` (2 axis + side), if a box of the same or a coarser level holds it and that cell
-// is selected.  The loop runs over the face's candidate list, whose length the host fixed.
+// is selected.  The loop runs over the face's candidate list, whose length the host fixed.  It is
+// find_same_or_coarser's loop with the ordinal formed at the hit, while the box record is at hand:
+// this kernel is bound by dependent loads and its device code is kept as it was measured.
 __device__ __forceinline__ void unite_ghost(const ClumpArgs& a, int b, int level, int face,
                                             long long gx, long long gy, long long gz,
                                             uint32_t x) {
@@ -241,30 +238,6 @@ __global__ __launch_bounds__(kThreads) void clump_merge_kernel(const ClumpArgs a
 
 // ---- flatten, scan, rank -------------------------------------------------------------------------
 
-// The sum of v over the workgroup's lanes before this one (`before`) and over all of them.
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_sums[THREADS / 64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inclusive = v;
-#pragma unroll
-  for (int step = 1; step < 64; step <<= 1) {
-    const uint32_t below = __shfl_up(inclusive, step, 64);
-    if (lane >= static_cast<uint32_t>(step)) inclusive += below;
-  }
-  if (lane == 63u) wave_sums[wave] = inclusive;
-  __syncthreads();
-  uint32_t before = inclusive - v, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < THREADS / 64; ++w) {
-    const uint32_t s = wave_sums[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  *total = all;
-  return before;
-}
-
 // One chunk of kClumpChunk consecutive ordinals per workgroup, four per lane (the buffer is padded
 // to whole chunks; entries from n_cells on are read, never used).  Only this lane writes its four.
 __global__ __launch_bounds__(kThreads) void clump_flatten_kernel(const ClumpArgs a) {
@@ -284,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void clump_flatten_kernel(const ClumpArgs
     }
   }
   uint32_t total;
-  block_exclusive_sum<kThreads>(roots, &total);
+  block_exclusive_sum<kThreads, 1>(roots, 0, &total);
   if (threadIdx.x == 0) a.chunk_roots[blockIdx.x] = total;
 }
 
@@ -297,7 +270,7 @@ __global__ __launch_bounds__(kScanThreads) void clump_scan_kernel(const ClumpArg
   uint32_t sum = 0;
   for (uint32_t c = first; c < last; ++c) sum += a.chunk_roots[c];
   uint32_t total;
-  uint32_t running = block_exclusive_sum<kScanThreads>(sum, &total);
+  uint32_t running = block_exclusive_sum<kScanThreads, 1>(sum, 0, &total);
   for (uint32_t c = first; c < last; ++c) {
     const uint32_t count = a.chunk_roots[c];
     a.chunk_roots[c] = running;
@@ -315,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void clump_rank_kernel(const ClumpArgs a)
 #pragma unroll
   for (uint32_t e = 0; e < 4; ++e) roots += (base + e < a.n_cells && p[e] == base + e) ? 1u : 0u;
   uint32_t total;
-  uint32_t rank = a.chunk_roots[blockIdx.x] + block_exclusive_sum<kThreads>(roots, &total);
+  uint32_t rank = a.chunk_roots[blockIdx.x] + block_exclusive_sum<kThreads, 1>(roots, 0, &total);
 #pragma unroll
   for (uint32_t e = 0; e < 4; ++e) {
     if (base + e < a.n_cells && p[e] == base + e) parent[base + e] = kClumpRanked | rank++;

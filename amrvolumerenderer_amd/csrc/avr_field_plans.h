@@ -20,6 +20,7 @@
 #include "avr_cell_tiles.h"
 #include "avr_field_boxes.h"
 #include "avr_internal.h"
+#include "avr_level_cells.h"
 
 namespace avr {
 
@@ -105,8 +106,7 @@ inline JointHistogramPlan plan_joint_histogram(const avr_box* x, const avr_box* 
   }
   require_box(static_cast<int64_t>(nx) * ny <= kJointHistogramMaxCells,
               "the histogram has more than 2^20 bins");
-  require_box(n_levels >= 1 && n_levels <= kJointHistogramMaxLevels,
-              "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   const avr_box* fields[3] = {x, y != nullptr ? y : x, s != nullptr ? s : x};
   plan.boxes.resize(n_boxes);
   plan.tile_begin.assign(1, 0u);
@@ -159,7 +159,7 @@ inline AxisProjectionPlan plan_axis_projection(const avr_box* f, const avr_box* 
   require_image_size(width, height);
   require_box(std::isfinite(origin_uv[0]) && std::isfinite(origin_uv[1]) && std::isfinite(du) &&
                   std::isfinite(dv), "the window must be finite");
-  require_box(n_levels >= 1 && n_levels <= kAxisMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   for (int l = 0; l < n_levels; ++l) {
     require_box(std::isfinite(level_dl[l]), "level_dl must be finite");
   }
@@ -221,6 +221,11 @@ typedef std::vector<std::pair<uintptr_t, uintptr_t>> ByteRanges;
 inline void append_byte_range(ByteRanges* ranges, const FieldView& view) {
   const uintptr_t begin = reinterpret_cast<uintptr_t>(view.cells);
   ranges->emplace_back(begin, begin + static_cast<uintptr_t>(view.last) * 8 + 7);
+}
+// `bytes` > 0 bytes from `at` on: an array a call writes
+inline void append_byte_range(ByteRanges* ranges, const void* at, uint64_t bytes) {
+  const uintptr_t begin = reinterpret_cast<uintptr_t>(at);
+  ranges->emplace_back(begin, begin + static_cast<uintptr_t>(bytes) - 1);
 }
 inline void require_no_shared_byte(
     ByteRanges* read_ranges, const ByteRanges& write_ranges,
@@ -291,7 +296,7 @@ inline DerivePlan plan_derive(const avr_box* const* inputs, int n_inputs, const 
   require_box(n_constants >= 0 && n_constants <= kDeriveMaxConstants,
               "n_constants must lie in [0, 16]");
   require_box(n_constants == 0 || constants != nullptr, "null argument");
-  require_box(n_levels >= 1 && n_levels <= kDeriveMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   verify_derive_program(instructions, n_instructions, n_constants, n_inputs);
   for (int l = 0; l < n_levels * 3; ++l) {
     require_box(std::isfinite(level_cell_size[l]), "level_cell_size must be finite");
@@ -345,7 +350,8 @@ inline DerivePlan plan_derive(const avr_box* const* inputs, int n_inputs, const 
   return plan;
 }
 
-// ---- gradient fields ----------------------------------------------------------------------
+// ---- shared by the products that cross levels (gradient fields, clumps, isosurfaces,
+// ---- streamlines): the level setup, the boxes in index space, the candidate lists ----------
 // The cells [lo, hi] of a box, or of a face's ghost slab, in some level's index space.
 struct IndexRegion {
   int64_t lo[3], hi[3];
@@ -356,9 +362,77 @@ inline bool regions_meet(const IndexRegion& a, const IndexRegion& b) {
   }
   return true;
 }
-inline int64_t floor_div(int64_t a, int64_t r) {
-  const int64_t q = a / r;
-  return (a % r != 0 && a < 0) ? q - 1 : q;
+
+// ratio[l]: level l -> l + 1, at least 2 between two of the call's levels and 1 from n_levels - 1
+// on.
+inline void fill_level_ratios(const int32_t* level_ratio, int n_levels,
+                              int32_t (&ratio)[kFieldMaxLevels]) {
+  for (int l = 0; l < kFieldMaxLevels; ++l) ratio[l] = 1;
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
+    ratio[l] = level_ratio[l];
+  }
+}
+// level_cell_size: (dx, dy, dz) per level; prob_lo: three values.  Everything else of `levels` is
+// left zero.
+inline void fill_level_geometry(const double* level_cell_size, const double* prob_lo, int n_levels,
+                                IsoLevelsDev* levels) {
+  std::memset(levels, 0, sizeof(*levels));
+  for (int l = 0; l < n_levels; ++l) {
+    for (int d = 0; d < 3; ++d) {
+      const double size = level_cell_size[l * 3 + d];
+      require_box(std::isfinite(size) && size > 0.0, "level_cell_size must be finite and positive");
+      levels->cell_size[l][d] = size;
+    }
+  }
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(prob_lo[d]), "prob_lo must be finite");
+    levels->prob_lo[d] = prob_lo[d];
+  }
+}
+// The cells of box b (which has some) in its level's index space, from box_index_lo (per box the
+// index of its first cell, 3 per box), also as the device box's lo.  Inside [-2^30, 2^30) the
+// ghost indices next to a box, and their children, stay far inside 64 bits.
+inline IndexRegion box_index_region(const int32_t* box_index_lo, size_t b, const int32_t dims[3],
+                                    int32_t (&dev_lo)[3]) {
+  IndexRegion region;
+  for (int d = 0; d < 3; ++d) {
+    const int64_t lo = box_index_lo[b * 3 + d];
+    dev_lo[d] = box_index_lo[b * 3 + d];
+    region.lo[d] = lo;
+    region.hi[d] = lo + dims[d] - 1;
+    require_box(lo >= -(int64_t{1} << 30) && region.hi[d] < (int64_t{1} << 30),
+                "a box's index range leaves [-2^30, 2^30)");
+  }
+  return region;
+}
+// ... of every box; a box without cells (nx == 0) keeps a zeroed entry that nothing reads.  Box: a
+// device box with nx and lo; first: the scene whose dims the boxes took.
+template <class Box>
+inline std::vector<IndexRegion> box_index_regions(const int32_t* box_index_lo, const avr_box* first,
+                                                  std::vector<Box>* boxes) {
+  std::vector<IndexRegion> regions(boxes->size());
+  for (size_t b = 0; b < boxes->size(); ++b) {
+    if ((*boxes)[b].nx <= 0) continue;
+    regions[b] = box_index_region(box_index_lo, b, first[b].dims, (*boxes)[b].lo);
+  }
+  return regions;
+}
+// No later box of box b's level shares an index with it ...
+template <class Box>
+inline void require_level_disjoint(const std::vector<Box>& boxes,
+                                   const std::vector<IndexRegion>& regions, size_t b) {
+  for (size_t c = b + 1; boxes[b].nx > 0 && c < boxes.size(); ++c) {
+    require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
+                    !regions_meet(regions[b], regions[c]),
+                "two boxes of one level overlap in index space");
+  }
+}
+// ... and so for every box: the boxes of one level lie apart in index space.
+template <class Box>
+inline void require_levels_disjoint(const std::vector<Box>& boxes,
+                                    const std::vector<IndexRegion>& regions) {
+  for (size_t b = 0; b < boxes.size(); ++b) require_level_disjoint(boxes, regions, b);
 }
 
 // The boxes that can hold a cell of `region`, a range of indices of box b's level: the region at
@@ -372,7 +446,7 @@ inline void append_region_candidates(const std::vector<Box>& boxes,
                                      const IndexRegion& region, const int32_t* ratio, int finest,
                                      std::vector<int32_t>* candidates) {
   const int level = boxes[b].level;
-  IndexRegion slab[kGradientMaxLevels + 1];  // [m] at level m
+  IndexRegion slab[kFieldMaxLevels + 1];  // [m] at level m
   slab[level] = region;
   for (int m = level; m > 0; --m) {
     for (int d = 0; d < 3; ++d) {
@@ -408,6 +482,7 @@ inline void append_face_candidates(const std::vector<Box>& boxes,
   append_region_candidates(boxes, regions, b, slab, ratio, finest, candidates);
 }
 
+// ---- gradient fields ----------------------------------------------------------------------
 struct GradientPlan {
   std::vector<GradientBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
@@ -415,7 +490,7 @@ struct GradientPlan {
   // CSR over (box, side), entry 2 b + side: the boxes that can hold a ghost of that face
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;   // empty when no face has a neighbour
-  GradientLevelsDev levels;
+  LevelRatiosDev levels;
 };
 // box_index_lo: per box the index of its first cell in its level's index space (3 per box);
 // level_ratio[l]: level l -> l + 1.
@@ -423,15 +498,11 @@ inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t 
                                   const int32_t* box_index_lo, const int32_t* level_ratio,
                                   const double* level_cell_size, int n_levels) {
   require_box(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
-  require_box(n_levels >= 1 && n_levels <= kGradientMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
   GradientPlan plan;
-  GradientLevelsDev& levels = plan.levels;
-  for (int l = 0; l < kGradientMaxLevels; ++l) levels.ratio[l] = 1;
-  for (int l = 0; l + 1 < n_levels; ++l) {
-    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
-    levels.ratio[l] = level_ratio[l];
-  }
+  LevelRatiosDev& levels = plan.levels;
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
   for (int l = 0; l < n_levels; ++l) {
     require_box(std::isfinite(level_cell_size[l]) && level_cell_size[l] > 0.0,
                 "level_cell_size must be finite and positive");
@@ -466,15 +537,7 @@ inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t 
       dev.nz = first.dims[2];
       append_byte_range(&read_ranges, views[0]);
       append_byte_range(&write_ranges, views[1]);
-      for (int d = 0; d < 3; ++d) {
-        const int64_t lo = box_index_lo[b * 3 + d];
-        dev.lo[d] = box_index_lo[b * 3 + d];
-        regions[b].lo[d] = lo;
-        regions[b].hi[d] = lo + first.dims[d] - 1;
-        // the ghost indices next to the box, and their children, then stay far inside 64 bits
-        require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
-                    "a box's index range leaves [-2^30, 2^30)");
-      }
+      regions[b] = box_index_region(box_index_lo, b, first.dims, dev.lo);
       faces = static_cast<uint64_t>(first.dims[(axis + 1) % 3]) *
               static_cast<uint64_t>(first.dims[(axis + 2) % 3]);
     }
@@ -491,10 +554,7 @@ inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t 
   for (size_t b = 0; b < n_boxes; ++b) {
     const int level = boxes[b].level;
     const bool cells = boxes[b].nx > 0;
-    for (size_t c = b + 1; cells && c < n_boxes; ++c) {
-      require_box(boxes[c].nx <= 0 || boxes[c].level != level || !regions_meet(regions[b], regions[c]),
-                  "two boxes of one level overlap in index space");
-    }
+    require_level_disjoint(boxes, regions, b);
     for (int side = 0; side < 2; ++side) {
       if (cells) {
         const int finest = level + 1 < n_levels ? level + 1 : level;
@@ -515,7 +575,7 @@ struct ClumpPlan {
   // level that can hold a ghost of that face
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;   // empty when no face has a neighbour
-  GradientLevelsDev levels;
+  LevelRatiosDev levels;
 };
 // box_index_lo and level_ratio as plan_gradient takes them.  The rules, in this order: the bounds,
 // n_levels, the box rules (the input is the reference), the ratios, the index ranges, boxes of one
@@ -525,7 +585,7 @@ inline ClumpPlan plan_clumps(const avr_box* in, const avr_box* out, size_t n_box
                              int n_levels) {
   require_box(!std::isnan(lower) && !std::isnan(upper), "a bound is NaN");
   require_box(lower <= upper, "lower must not exceed upper");
-  require_box(n_levels >= 1 && n_levels <= kClumpMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
   require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
   ClumpPlan plan;
@@ -556,31 +616,10 @@ inline ClumpPlan plan_clumps(const avr_box* in, const avr_box* out, size_t n_box
     }
     append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
   }
-  GradientLevelsDev& levels = plan.levels;
-  for (int l = 0; l < kGradientMaxLevels; ++l) levels.ratio[l] = 1;
-  for (int l = 0; l + 1 < n_levels; ++l) {
-    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
-    levels.ratio[l] = level_ratio[l];
-  }
-  std::vector<IndexRegion> regions(n_boxes);
-  for (size_t b = 0; b < n_boxes; ++b) {
-    if (boxes[b].nx <= 0) continue;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t lo = box_index_lo[b * 3 + d];
-      boxes[b].lo[d] = box_index_lo[b * 3 + d];
-      regions[b].lo[d] = lo;
-      regions[b].hi[d] = lo + in[b].dims[d] - 1;
-      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
-                  "a box's index range leaves [-2^30, 2^30)");
-    }
-  }
-  for (size_t b = 0; b < n_boxes; ++b) {
-    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
-      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
-                      !regions_meet(regions[b], regions[c]),
-                  "two boxes of one level overlap in index space");
-    }
-  }
+  LevelRatiosDev& levels = plan.levels;
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, in, &boxes);
+  require_levels_disjoint(boxes, regions);
   require_no_shared_byte(&read_ranges, write_ranges);
   plan.cell_begin.assign(1, 0u);
   uint64_t total = 0;
@@ -613,7 +652,7 @@ struct ClumpTablePlan {
 inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* field, size_t n_boxes,
                                        uint64_t n_clumps, int n_levels) {
   require_box(n_clumps >= 1, "n_clumps must be at least 1");
-  require_box(n_levels >= 1 && n_levels <= kClumpMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   require_box(n_clumps < static_cast<uint64_t>(kClumpTableMaxEntries) &&
                   n_clumps * static_cast<uint64_t>(n_levels) <
                       static_cast<uint64_t>(kClumpTableMaxEntries),
@@ -669,23 +708,12 @@ inline IsoPlan plan_isosurface(const avr_box* field, const avr_box* sample, size
                                const void* vertices, const void* levels_out, const void* samples,
                                const void* counts) {
   require_box(std::isfinite(value), "value must be finite");
-  require_box(n_levels >= 1 && n_levels <= kIsoMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
   require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
   IsoPlan plan;
   IsoLevelsDev& levels = plan.levels;
-  std::memset(&levels, 0, sizeof(levels));
-  for (int l = 0; l < n_levels; ++l) {
-    for (int d = 0; d < 3; ++d) {
-      const double size = level_cell_size[l * 3 + d];
-      require_box(std::isfinite(size) && size > 0.0, "level_cell_size must be finite and positive");
-      levels.cell_size[l][d] = size;
-    }
-  }
-  for (int d = 0; d < 3; ++d) {
-    require_box(std::isfinite(prob_lo[d]), "prob_lo must be finite");
-    levels.prob_lo[d] = prob_lo[d];
-  }
+  fill_level_geometry(level_cell_size, prob_lo, n_levels, &levels);
   require_box(capacity < kIsoMaxCapacity, "capacity must stay below 2^36");
   if (capacity > 0) {
     require_box(vertices != nullptr && levels_out != nullptr, "null argument");
@@ -718,40 +746,15 @@ inline IsoPlan plan_isosurface(const avr_box* field, const avr_box* sample, size
       if (sample != nullptr) append_byte_range(&read_ranges, views[1]);
     }
   }
-  for (int l = 0; l < kIsoMaxLevels; ++l) levels.ratio[l] = 1;
-  for (int l = 0; l + 1 < n_levels; ++l) {
-    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
-    levels.ratio[l] = level_ratio[l];
-  }
-  std::vector<IndexRegion> regions(n_boxes);
-  for (size_t b = 0; b < n_boxes; ++b) {
-    if (boxes[b].nx <= 0) continue;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t lo = box_index_lo[b * 3 + d];
-      boxes[b].lo[d] = box_index_lo[b * 3 + d];
-      regions[b].lo[d] = lo;
-      regions[b].hi[d] = lo + field[b].dims[d] - 1;
-      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
-                  "a box's index range leaves [-2^30, 2^30)");
-    }
-  }
-  for (size_t b = 0; b < n_boxes; ++b) {
-    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
-      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
-                      !regions_meet(regions[b], regions[c]),
-                  "two boxes of one level overlap in index space");
-    }
-  }
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, field, &boxes);
+  require_levels_disjoint(boxes, regions);
   // what the call writes: the two counts always, the triangles' arrays with a capacity
-  auto written = [&](const void* at, uint64_t bytes) {
-    const uintptr_t begin = reinterpret_cast<uintptr_t>(at);
-    write_ranges.emplace_back(begin, begin + static_cast<uintptr_t>(bytes) - 1);
-  };
-  written(counts, 2 * sizeof(uint64_t));
+  append_byte_range(&write_ranges, counts, 2 * sizeof(uint64_t));
   if (capacity > 0) {
-    written(vertices, capacity * 9 * sizeof(double));
-    written(levels_out, capacity);
-    if (samples != nullptr) written(samples, capacity * 3 * sizeof(double));
+    append_byte_range(&write_ranges, vertices, capacity * 9 * sizeof(double));
+    append_byte_range(&write_ranges, levels_out, capacity);
+    if (samples != nullptr) append_byte_range(&write_ranges, samples, capacity * 3 * sizeof(double));
   }
   require_no_shared_byte(&read_ranges, write_ranges,
                          "an output array overlaps an input box's cells");
@@ -843,25 +846,14 @@ inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const a
   // n_seeds < 2^32 first: the product then stays inside 64 bits
   require_box(n_seeds < (uint64_t{1} << 32) && n_seeds * (max_steps + 1) < (uint64_t{1} << 32),
               "n_seeds * (max_steps + 1) must stay below 2^32");
-  require_box(n_levels >= 1 && n_levels <= kStreamMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
   require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
   require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
   require_box(n_seeds == 0 || (seeds != nullptr && points != nullptr && counts != nullptr &&
                                status != nullptr), "null argument");
   StreamPlan plan;
   IsoLevelsDev& levels = plan.levels;
-  std::memset(&levels, 0, sizeof(levels));
-  for (int l = 0; l < n_levels; ++l) {
-    for (int d = 0; d < 3; ++d) {
-      const double size = level_cell_size[l * 3 + d];
-      require_box(std::isfinite(size) && size > 0.0, "level_cell_size must be finite and positive");
-      levels.cell_size[l][d] = size;
-    }
-  }
-  for (int d = 0; d < 3; ++d) {
-    require_box(std::isfinite(prob_lo[d]), "prob_lo must be finite");
-    levels.prob_lo[d] = prob_lo[d];
-  }
+  fill_level_geometry(level_cell_size, prob_lo, n_levels, &levels);
   require_box((samples != nullptr) == (sample != nullptr),
               "samples_dev is given exactly when sample is");
   std::vector<StreamBoxDev>& boxes = plan.boxes;
@@ -888,41 +880,16 @@ inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const a
       dev.nz = first.dims[2];
     }
   }
-  for (int l = 0; l < kIsoMaxLevels; ++l) levels.ratio[l] = 1;
-  for (int l = 0; l + 1 < n_levels; ++l) {
-    require_box(level_ratio[l] >= 2, "a level ratio is below 2");
-    levels.ratio[l] = level_ratio[l];
-  }
-  std::vector<IndexRegion> regions(n_boxes);
-  for (size_t b = 0; b < n_boxes; ++b) {
-    if (boxes[b].nx <= 0) continue;
-    for (int d = 0; d < 3; ++d) {
-      const int64_t lo = box_index_lo[b * 3 + d];
-      boxes[b].lo[d] = box_index_lo[b * 3 + d];
-      regions[b].lo[d] = lo;
-      regions[b].hi[d] = lo + vx[b].dims[d] - 1;
-      require_box(lo >= -(int64_t{1} << 30) && regions[b].hi[d] < (int64_t{1} << 30),
-                  "a box's index range leaves [-2^30, 2^30)");
-    }
-  }
-  for (size_t b = 0; b < n_boxes; ++b) {
-    for (size_t c = b + 1; boxes[b].nx > 0 && c < n_boxes; ++c) {
-      require_box(boxes[c].nx <= 0 || boxes[c].level != boxes[b].level ||
-                      !regions_meet(regions[b], regions[c]),
-                  "two boxes of one level overlap in index space");
-    }
-  }
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, vx, &boxes);
+  require_levels_disjoint(boxes, regions);
   if (n_seeds > 0) {
-    auto touched = [&](const void* at, uint64_t bytes) {
-      const uintptr_t begin = reinterpret_cast<uintptr_t>(at);
-      write_ranges.emplace_back(begin, begin + static_cast<uintptr_t>(bytes) - 1);
-    };
     const uint64_t slots = n_seeds * (max_steps + 1);
-    touched(seeds, n_seeds * 3 * sizeof(double));
-    touched(points, slots * 3 * sizeof(double));
-    if (samples != nullptr) touched(samples, slots * sizeof(double));
-    touched(counts, n_seeds * sizeof(uint32_t));
-    touched(status, n_seeds);
+    append_byte_range(&write_ranges, seeds, n_seeds * 3 * sizeof(double));
+    append_byte_range(&write_ranges, points, slots * 3 * sizeof(double));
+    if (samples != nullptr) append_byte_range(&write_ranges, samples, slots * sizeof(double));
+    append_byte_range(&write_ranges, counts, n_seeds * sizeof(uint32_t));
+    append_byte_range(&write_ranges, status, n_seeds);
     require_no_shared_byte(&read_ranges, write_ranges,
                            "an output array or the seeds overlap an input box's cells");
   }

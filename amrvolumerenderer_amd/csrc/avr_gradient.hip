@@ -5,11 +5,11 @@
 //   gradient_kernel<AXIS>               stage 2: one difference per cell
 //
 // Stage 1 takes one lane per face cell and side.  The ghost of a level-l box is a level-l index G
-// next to the face; its value is that of the box of the highest level m <= l that contains G mapped
-// to level m (floor division by the ratios), else the mean of its r^3 children if every one of them
-// lies in a box of level l + 1, else it is absent.  Only the boxes the host listed for the face are
-// tested.  Value and presence go to two planes per box, presence as a byte of its own: a NaN is
-// data.  Faces are a surface term: this kernel is kept plain.
+// next to the face; its value is that of the cell find_same_or_coarser (avr_level_cells.h) gives
+// for G, else the mean of its r^3 children if every one of them lies in a box of level l + 1, else
+// it is absent.  Only the boxes the host listed for the face are tested.  Value and presence go to
+// two planes per box, presence as a byte of its own: a NaN is data.  Faces are a surface term:
+// this kernel is kept plain.
 //
 // Stage 2 is the cell scan of avr_derive.hip (avr_cell_tiles.h): one tile = 4 k-planes x 4 j-rows x
 // 128 cells of one box, rows read coalesced and as f64 pairs where input and output allow it, 16
@@ -52,11 +52,6 @@ struct Index3 {
   long long x, y, z;
 };
 
-__device__ __forceinline__ long long floor_div(long long a, long long r) {
-  const long long q = a / r;
-  return (a % r != 0 && a < 0) ? q - 1 : q;
-}
-
 __device__ __forceinline__ bool box_holds(const GradientBoxDev& box, const Index3& g) {
   return g.x >= box.lo[0] && g.x < static_cast<long long>(box.lo[0]) + box.nx &&
          g.y >= box.lo[1] && g.y < static_cast<long long>(box.lo[1]) + box.ny &&
@@ -92,25 +87,16 @@ __global__ __launch_bounds__(kThreads) void gradient_halo_kernel(const GradientA
   const int level = box.level;
   const uint32_t first = a.candidate_begin[2 * b + side], last = a.candidate_begin[2 * b + side + 1];
 
-  // the same level or a coarser one: the highest level that holds the ghost wins
-  int found_level = -1;
+  // the same level or a coarser one
+  const LevelCell found = find_same_or_coarser(a.boxes, a.candidates, first, last, a.levels->ratio,
+                                               level, ghost.x, ghost.y, ghost.z);
   double value = 0.0;
-  for (uint32_t q = first; q < last; ++q) {
-    const GradientBoxDev& other = a.boxes[a.candidates[q]];
-    if (other.level > level || other.level <= found_level) continue;
-    Index3 g = ghost;
-    for (int m = level; m > other.level; --m) {
-      const long long r = a.levels->ratio[m - 1];
-      g.x = floor_div(g.x, r);
-      g.y = floor_div(g.y, r);
-      g.z = floor_div(g.z, r);
-    }
-    if (box_holds(other, g)) {
-      found_level = other.level;
-      value = box_cell(other, g);
-    }
+  if (found.box >= 0) {
+    const GradientBoxDev& other = a.boxes[found.box];
+    value = other.in[found.i + found.j * static_cast<uint32_t>(other.jstride_in) +
+                     found.k * static_cast<uint32_t>(other.kstride_in)];
   }
-  bool present = found_level >= 0;
+  bool present = found.box >= 0;
   // one level finer: every child, added in ascending k, then j, then i
   if (!present && level + 1 < a.n_levels && first < last) {
     const long long r = a.levels->ratio[level];

@@ -12,6 +12,15 @@
 
 #include "../../include/avr_hip.h"
 
+// host and device where the compiler is hipcc
+#if defined(__HIP__)
+#define AVR_HD __host__ __device__
+#else
+#define AVR_HD
+#endif
+
+#include "avr_level_cells.h"  // kFieldMaxLevels; after AVR_HD, which it would otherwise define
+
 namespace avr {
 
 constexpr int kTableSize = 256;  // kColorTableSize, Common/VolumePainter.cpp:35
@@ -82,12 +91,6 @@ struct FrameConsts {
 // box: see bricklet_offset in avr_kernels.hip).
 constexpr int kBrickX = 8, kBrickY = 4, kBrickZ = 4, kBrickBytes = 128;
 constexpr int kClassifyChunk = 128;  // cells of one x-row handled by one classify workgroup
-
-#if defined(__HIP__)
-#define AVR_HD __host__ __device__
-#else
-#define AVR_HD
-#endif
 
 // How the image's pixels are dealt to the N pieces of the direct-send exchange (one piece per
 // rank of the compositing group).
@@ -432,7 +435,6 @@ struct alignas(16) JointBoxDev {
 static_assert(sizeof(JointBoxDev) == 80, "JointBoxDev: 16-byte multiple for scalar loads");
 constexpr int kJointHistogramMaxBins = 1024;          // per axis
 constexpr int kJointHistogramMaxCells = 1 << 20;      // nx * ny
-constexpr int kJointHistogramMaxLevels = 16;
 // Dynamic LDS of one workgroup (edges + counts + sums) up to which the bins are kept in LDS; above
 // it every cell goes to the global arrays.  64 KiB: what a kernel gets without asking for more,
 // and at least two workgroups (8 waves) per CU at the limit.
@@ -459,7 +461,6 @@ int launch_joint_histogram(const JointHistogramArgs& args, bool has_y, bool has_
 // weight) and n (u32), each [segments][dims_V][dims_U] at `plane_begin`.  Stage 2 gathers them per
 // pixel.  A box as stage 1 reads it:
 constexpr int kAxisSegment = 128;      // cells of a column that one partial sum covers
-constexpr int kAxisMaxLevels = 16;
 struct alignas(16) AxisBoxDev {
   const double* cells_f;
   const double* cells_w;  // == cells_f without a weight (not read)
@@ -529,7 +530,6 @@ constexpr int kDeriveMaxFields = 6;
 constexpr int kDeriveMaxInstructions = 64;
 constexpr int kDeriveMaxConstants = 16;
 constexpr int kDeriveMaxDepth = 8;
-constexpr int kDeriveMaxLevels = 16;
 // A box as the kernel reads it: the cells of the input fields and of the output (entry
 // kDeriveMaxFields of the strides), each with its own strides, the dims and the level they share,
 // and the physical position of the box's low corner.
@@ -550,7 +550,7 @@ static_assert(sizeof(DeriveBoxDev) == 160, "DeriveBoxDev: 16-byte multiple for s
 struct alignas(16) DeriveProgramDev {
   uint32_t code[kDeriveMaxInstructions];
   double constants[kDeriveMaxConstants];
-  double cell_size[kDeriveMaxLevels][3];
+  double cell_size[kFieldMaxLevels][3];
 };
 struct DeriveArgs {
   const DeriveBoxDev* boxes;
@@ -566,7 +566,6 @@ int launch_derive(const DeriveArgs& args, void* stream);
 // axis: one f64 and one presence byte per face cell, the face's cells numbered along the lower of
 // the two other axes first.  Stage 2 (difference) streams every cell once and reads the planes at
 // the box's two faces.  A box as both kernels read it:
-constexpr int kGradientMaxLevels = 16;
 struct alignas(16) GradientBoxDev {
   const double* in;
   double* out;
@@ -581,8 +580,8 @@ struct alignas(16) GradientBoxDev {
   int32_t pad_[1];
 };
 static_assert(sizeof(GradientBoxDev) == 80, "GradientBoxDev: 16-byte multiple for scalar loads");
-struct GradientLevelsDev {
-  int32_t ratio[kGradientMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
+struct LevelRatiosDev {
+  int32_t ratio[kFieldMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
 };
 struct GradientArgs {
   const GradientBoxDev* boxes;
@@ -591,7 +590,7 @@ struct GradientArgs {
   // CSR over (box, side): the boxes whose cells can hold a ghost of that face, in scene order
   const uint32_t* candidate_begin;  // 2 n_boxes + 1; entry 2 b + side
   const int32_t* candidates;
-  const GradientLevelsDev* levels;
+  const LevelRatiosDev* levels;
   int32_t n_boxes, n_levels;
   uint32_t n_tiles;
   uint32_t n_faces;             // face cells of one side, all boxes
@@ -605,7 +604,6 @@ int launch_gradient(const GradientArgs& args, int axis, void* stream);
 // parent entry at that ordinal: kClumpNone for a cell that is not selected, else the ordinal of a
 // selected cell of the same clump that is not larger (a root holds its own).  A box as the kernels
 // read it:
-constexpr int kClumpMaxLevels = 16;
 constexpr uint32_t kClumpNone = 0xffffffffu;
 constexpr uint32_t kClumpChunk = 1024;   // consecutive ordinals whose roots one workgroup counts
 constexpr uint32_t kClumpRanked = 0x80000000u;  // a root's entry once numbered: this | (label - 1)
@@ -630,7 +628,7 @@ struct ClumpArgs {
   // level whose cells can hold a ghost of that face, in scene order
   const uint32_t* candidate_begin;  // 6 n_boxes + 1
   const int32_t* candidates;
-  const GradientLevelsDev* levels;
+  const LevelRatiosDev* levels;
   int32_t n_boxes, n_levels;
   uint32_t n_tiles;
   uint32_t n_cells;             // < 2^31
@@ -660,7 +658,6 @@ int launch_clump_table(const ClumpTableArgs& args, bool has_field, void* stream)
 // base_begin of its box + ((k + 1) (ny + 1) + (j + 1)) (nx + 1) + (i + 1), which is the output
 // order.  The cells of the box's one-cell ghost shell are numbered by iso_shell_index, from
 // shell_begin of the box on.  A box as the kernels read it:
-constexpr int kIsoMaxLevels = 16;
 constexpr uint32_t kIsoChunk = 1024;     // consecutive base ordinals one workgroup counts and emits
 constexpr uint64_t kIsoMaxCapacity = uint64_t{1} << 36;  // 12 triangles x 2^31 bases stay below it
 constexpr uint8_t kIsoAbsent = 0, kIsoCoarser = 1, kIsoSameLevel = 2;  // a shell cell's code byte
@@ -678,9 +675,9 @@ struct alignas(16) IsoBoxDev {
 };
 static_assert(sizeof(IsoBoxDev) == 80, "IsoBoxDev: 16-byte multiple");
 struct IsoLevelsDev {
-  double cell_size[kIsoMaxLevels][3];
+  double cell_size[kFieldMaxLevels][3];
   double prob_lo[3];
-  int32_t ratio[kIsoMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
+  int32_t ratio[kFieldMaxLevels];  // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
 };
 // The number of the shell cell (i, j, k) of a box of n cells, one coordinate at least outside [0,
 // n): the two k-planes of (nx + 2) (ny + 2) cells, then per k the two j-rows of nx + 2, then per
@@ -731,7 +728,6 @@ int launch_isosurface(const IsoArgs& args, bool has_sample, bool emit, void* str
 // Streamlines (avr_streamlines.hip): RK4 field lines of three congruent scenes through the leaf
 // cells, one lane per seed.  A box as the kernel reads it: field 0..2 are the velocity components,
 // field 3 the sample field (the first component again without one).
-constexpr int kStreamMaxLevels = 16;
 constexpr uint32_t kStreamMaxSteps = 1u << 20;
 constexpr int64_t kStreamMaxBlocks = int64_t{1} << 24;   // of the locator
 constexpr int64_t kStreamMaxEntries = int64_t{1} << 28;  // of the locator's lists, all blocks

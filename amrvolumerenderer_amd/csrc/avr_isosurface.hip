@@ -15,10 +15,9 @@
 // before its own in the chunk (wave shuffles, LDS across waves) + its number within the cube:
 // no atomics, equal arguments give equal bits.
 //
-// The shell kernel finds a ghost as gradient_halo_kernel finds its same-or-coarser hit: only the
-// boxes the host listed for the box are tested, the highest level that holds the mapped index
-// wins.  Only cells of the scene's boxes are ever read.  The shell is a surface term: that kernel
-// is kept plain.
+// The shell kernel finds a ghost by find_same_or_coarser (avr_level_cells.h) among the boxes the
+// host listed for the box.  Only cells of the scene's boxes are ever read.  The shell is a surface
+// term: that kernel is kept plain.
 //
 // Every loop is bounded by a count known at launch.  Arithmetic is IEEE binary64, round to
 // nearest, nothing fused (-ffp-contract=off); / is the correctly rounded __ddiv_rn.
@@ -26,6 +25,7 @@
 
 #include <cstdint>
 
+#include "avr_cell_tiles.h"
 #include "avr_internal.h"
 
 namespace avr {
@@ -48,33 +48,13 @@ constexpr uint32_t kTetOdd[6] = {0, 1, 1, 0, 0, 1};
 // of odd order the other cases are.  Cases 0 and 15 emit nothing.
 constexpr uint32_t kSwapEven = 0x4d24u;  // cases 2, 5, 8, 10, 11, 14
 
-__device__ __forceinline__ long long floor_div(long long a, long long r) {
-  const long long q = a / r;
-  return (a % r != 0 && a < 0) ? q - 1 : q;
-}
-
-// The largest b with begin[b] <= at.
-template <typename T>
-__device__ __forceinline__ int locate(const T* begin, int n_boxes, T at) {
-  int lo = 0, hi = n_boxes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (begin[mid] <= at) {
-      lo = mid;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
 // ---- the shell -----------------------------------------------------------------------------------
 
 template <bool HAS_S>
 __global__ __launch_bounds__(kThreads) void iso_shell_kernel(const IsoArgs a) {
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (t >= a.n_shell) return;
-  const int b = locate(a.shell_begin, a.n_boxes, t);
+  const int b = locate_box(a.shell_begin, a.n_boxes, t);
   const IsoBoxDev& box = a.boxes[b];
   const int nx = box.nx, ny = box.ny, nz = box.nz;
   // the inverse of iso_shell_index
@@ -108,37 +88,22 @@ __global__ __launch_bounds__(kThreads) void iso_shell_kernel(const IsoArgs a) {
   const long long gz = static_cast<long long>(box.lo[2]) + k;
   const int level = box.level;
   const uint32_t first = a.candidate_begin[b], last = a.candidate_begin[b + 1];
-  // the same level or a coarser one: the highest level that holds the cell wins
-  int found_level = -1;
+  // the same level or a coarser one
+  const LevelCell found = find_same_or_coarser(a.boxes, a.candidates, first, last, a.levels->ratio,
+                                               level, gx, gy, gz);
   double value = 0.0, sample = 0.0;
-  for (uint32_t q = first; q < last; ++q) {
-    const IsoBoxDev& other = a.boxes[a.candidates[q]];
-    if (other.level > level || other.level <= found_level) continue;
-    long long ox = gx, oy = gy, oz = gz;
-    for (int m = level; m > other.level; --m) {
-      const long long r = a.levels->ratio[m - 1];
-      ox = floor_div(ox, r);
-      oy = floor_div(oy, r);
-      oz = floor_div(oz, r);
-    }
-    ox -= other.lo[0];
-    oy -= other.lo[1];
-    oz -= other.lo[2];
-    if (ox >= 0 && ox < other.nx && oy >= 0 && oy < other.ny && oz >= 0 && oz < other.nz) {
-      found_level = other.level;
-      const uint32_t ui = static_cast<uint32_t>(ox), uj = static_cast<uint32_t>(oy);
-      const uint32_t uk = static_cast<uint32_t>(oz);
-      value = other.in[ui + uj * static_cast<uint32_t>(other.jstride_in) +
-                       uk * static_cast<uint32_t>(other.kstride_in)];
-      if (HAS_S) {
-        sample = other.sample[ui + uj * static_cast<uint32_t>(other.jstride_sample) +
-                              uk * static_cast<uint32_t>(other.kstride_sample)];
-      }
+  if (found.box >= 0) {
+    const IsoBoxDev& other = a.boxes[found.box];
+    value = other.in[found.i + found.j * static_cast<uint32_t>(other.jstride_in) +
+                     found.k * static_cast<uint32_t>(other.kstride_in)];
+    if (HAS_S) {
+      sample = other.sample[found.i + found.j * static_cast<uint32_t>(other.jstride_sample) +
+                            found.k * static_cast<uint32_t>(other.kstride_sample)];
     }
   }
   a.shell_value[t] = value;
   if (HAS_S) a.shell_sample[t] = sample;
-  a.shell_code[t] = found_level < 0 ? kIsoAbsent : found_level == level ? kIsoSameLevel : kIsoCoarser;
+  a.shell_code[t] = found.level < 0 ? kIsoAbsent : found.level == level ? kIsoSameLevel : kIsoCoarser;
 }
 
 // ---- the cubes -----------------------------------------------------------------------------------
@@ -156,7 +121,7 @@ struct Cube {
 // The cube of base ordinal x < n_bases.  POSITIONS: also where its corners are.
 template <bool HAS_S, bool POSITIONS>
 __device__ __forceinline__ void load_cube(const IsoArgs& a, uint32_t x, Cube<HAS_S>* cube) {
-  const int b = locate(a.base_begin, a.n_boxes, x);
+  const int b = locate_box(a.base_begin, a.n_boxes, x);
   const IsoBoxDev& box = a.boxes[b];
   const int nx = box.nx, ny = box.ny, nz = box.nz;
   const uint32_t local = x - box.base_begin;
@@ -240,31 +205,6 @@ __device__ __forceinline__ uint32_t cube_triangles(uint32_t corners) {
 template <typename T>
 __device__ __forceinline__ T pick(uint32_t n, T a0, T a1, T a2, T a3) {
   return n == 0u ? a0 : n == 1u ? a1 : n == 2u ? a2 : a3;
-}
-
-// The sum of v over the workgroup's lanes before this one, and over all of them.  `slot`: the
-// caller's call number, each call has its own LDS.
-template <int SLOTS>
-__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, int slot, uint32_t* total) {
-  __shared__ uint32_t wave_sums[SLOTS][kThreads / 64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inclusive = v;
-#pragma unroll
-  for (int step = 1; step < 64; step <<= 1) {
-    const uint32_t below = __shfl_up(inclusive, step, 64);
-    if (lane >= static_cast<uint32_t>(step)) inclusive += below;
-  }
-  if (lane == 63u) wave_sums[slot][wave] = inclusive;
-  __syncthreads();
-  uint32_t before = inclusive - v, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < kThreads / 64; ++w) {
-    const uint32_t s = wave_sums[slot][w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  *total = all;
-  return before;
 }
 
 // Writes the triangles of one cube from `at` on.
@@ -369,14 +309,14 @@ __global__ __launch_bounds__(kThreads) void iso_cubes_kernel(const IsoArgs a) {
     // a wave none of whose cubes straddles the value has nothing to count
     if (__ballot(cut) != 0ull && cut) mine = cube_triangles(corners);
     uint32_t total;
-    const uint32_t before = block_exclusive_sum<kPasses + 1>(mine, pass, &total);
+    const uint32_t before = block_exclusive_sum<kThreads, kPasses + 1>(mine, pass, &total);
     if (EMIT && mine != 0u) emit_cube<HAS_S>(a, cube, corners, offset + before);
     offset += total;
     triangles += total;
   }
   if (!EMIT) {
     uint32_t all_skipped;
-    block_exclusive_sum<kPasses + 1>(skipped, kPasses, &all_skipped);
+    block_exclusive_sum<kThreads, kPasses + 1>(skipped, kPasses, &all_skipped);
     if (threadIdx.x == 0) {
       a.chunk_triangles[blockIdx.x] = triangles;
       a.chunk_skipped[blockIdx.x] = all_skipped;
