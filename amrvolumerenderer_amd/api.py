@@ -591,6 +591,120 @@ def sample_points(plotfile: str, points, fields: Sequence[str], min_level: int =
     return values, inside
 
 
+# ---- covering grids ("Covering grid") ------------------------------------------------
+
+def covering_grid_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes, prob_lo,
+                        ref_ratio, fill: float = math.nan, with_coverage: bool = True,
+                        rank: int = 0, n_ranks: int = 1):
+    """A scene's raw field resampled to the cells [lo, lo + dims) of level `level` (DESIGN.md 7,
+    "Covering grid"): where a leaf of the same or a coarser level holds the cell, that leaf's
+    value with its bits kept; where finer leaves lie in it, their volume-weighted mean; where
+    nothing does, fill.  lo and dims = (nx, ny, nz) are level-`level` indices; the region may
+    leave the domain.  scene, prob_lo as gradient_scene takes them; cell_sizes and ref_ratio run
+    up to the finer of `level` and the finest loaded level at least (every entry of cell_sizes
+    counts as a level, 16 at the most).  Returns numpy arrays (values float64 [nz, ny, nx], coverage float64
+    [nz, ny, nx]: the fraction of the cell's volume that loaded leaves fill, cell level int8
+    [nz, ny, nx]: the level of the finest leaf used, -1 for none); the last two are None without
+    with_coverage -- they depend on the boxes alone.  Every box of the scene must be on this rank:
+    with n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised before any
+    device work."""
+    level = int(level)
+    lo, dims = tuple(int(v) for v in lo), tuple(int(v) for v in dims)
+    if len(lo) != 3 or len(dims) != 3:
+        raise ValueError("lo and dims must hold three values")
+    if min(dims) < 1:
+        raise ValueError("dims must be at least 1")
+    local = list(scene.local_boxes)
+    if n_ranks > 1 or len(local) != len(scene.all_boxes):
+        raise NotImplementedError("a covering grid needs every box of the scene on one rank: "
+                                  "cells are not gathered between ranks")
+    if not 0 <= level < len(list(cell_sizes)):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
+    field = ctx.create_scene(local, scene.scalar_transform)
+    try:
+        values, coverage, cell_level = field.covering_grid(level, lo, dims, index, ratios,
+                                                           float(fill), bool(with_coverage))
+        ctx.synchronize()
+        values = values.cpu().numpy()
+        if coverage is not None:
+            coverage, cell_level = coverage.cpu().numpy(), cell_level.cpu().numpy()
+    finally:
+        field.close()
+    return values, coverage, cell_level
+
+
+def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[str] = (),
+                  region=None, left_edge=None, right_edge=None, min_level: int = 0,
+                  max_level: int = -1, fill: float = math.nan,
+                  output: Optional[str] = None) -> dict:
+    """Fields of a plotfile as plain arrays at one level (yt's covering_grid; DESIGN.md 7, "Covering
+    grid"), on cuda:0: piecewise constant where the loaded data is coarser than `level`, the
+    volume-weighted mean of the leaves where it is finer, fill where no loaded level has a cell.
+    level: 0 .. the plotfile's finest level, by default the finest loaded one.  fields: stored
+    variables or registered derived, gradient or clump fields; by default the plotfile's first
+    variable.  region = ((ilo, jlo, klo), (ihi, jhi, khi)), inclusive level-`level` indices, or
+    left_edge / right_edge in the plotfile's physical units (the cells whose centres lie in
+    [left_edge, right_edge); grids.index_region), not both; by default the whole domain.  Either
+    may leave the domain.  Returns a dict: level, lo (the index of the first cell), dims (nx, ny,
+    nz), left_edge, right_edge and cell_size (physical), fields {name: float64 [nz, ny, nx]},
+    coverage float64 [nz, ny, nx] (the fraction of a cell's volume that loaded leaves fill),
+    cell_level int8 [nz, ny, nx] (the finest level used, -1 for none), absent (cells of coverage
+    0) and partial (cells of a coverage strictly between 0 and 1).  With output the dict is
+    written as one .npz file (grids.save_npz)."""
+    import numpy as np
+    from . import grids
+    from . import plotfile as pf
+    if region is not None and (left_edge is not None or right_edge is not None):
+        raise ValueError("give region or left_edge / right_edge, not both")
+    if (left_edge is None) != (right_edge is None):
+        raise ValueError("left_edge and right_edge go together")
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    header = pf.PlotFileData(plotfile)
+    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
+    level = finest_loaded if level is None else int(level)
+    if not 0 <= level <= header.finest_level:
+        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
+    size = header.cell_size[level]
+    if region is not None:
+        first, last = (tuple(int(v) for v in corner) for corner in region)
+        if len(first) != 3 or len(last) != 3:
+            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
+        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
+        if min(dims) < 1:
+            raise ValueError("region must hold at least one cell along every axis")
+    elif left_edge is not None:
+        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
+    else:
+        refine = math.prod(header.ref_ratio[:level])
+        domain_lo, domain_hi = header.prob_domain[0]
+        lo = tuple(v * refine for v in domain_lo)
+        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
+    names = [str(name) for name in fields] or [header.var_names[0]]
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
+    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
+    arguments = (level, lo, dims, header.cell_size[:n_levels], header.prob_lo,
+                 header.ref_ratio[:n_levels - 1], float(fill))
+    found, coverage, cell_level = {}, None, None
+    for name, scene in zip(names, scenes):
+        # coverage and cell level are the same for every field of one plotfile: once
+        values, c, l = covering_grid_scene(ctx, scene, *arguments, coverage is None, rank, world)
+        found[name] = values
+        if coverage is None:
+            coverage, cell_level = c, l
+    left, right = grids.grid_edges(header.prob_lo, size, lo, dims)
+    result = {"level": level, "lo": lo, "dims": dims, "left_edge": left, "right_edge": right,
+              "cell_size": tuple(float(v) for v in size), "fields": found, "coverage": coverage,
+              "cell_level": cell_level, "absent": int(np.count_nonzero(coverage == 0.0)),
+              "partial": int(np.count_nonzero((coverage > 0.0) & (coverage < 1.0)))}
+    if output:
+        grids.save_npz(result, output)
+    return result
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:

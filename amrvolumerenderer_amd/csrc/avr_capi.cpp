@@ -2238,6 +2238,45 @@ int avr_scene_streamlines(avr_context* ctx, const avr_scene* vx, const avr_scene
   });
 }
 
+int avr_scene_covering_grid(avr_context* ctx, const avr_scene* field, int level, const int32_t* lo,
+                            const int32_t* dims, const int32_t* box_index_lo,
+                            const int32_t* level_ratio, int n_levels, double fill,
+                            double* values_dev, double* coverage_dev, int8_t* level_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(field != nullptr && lo != nullptr && dims != nullptr && values_dev != nullptr,
+            "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    avr::CoveringGridPlan plan = avr::plan_covering_grid(
+        field->boxes.data(), n_boxes, level, lo, dims, box_index_lo, level_ratio, n_levels,
+        values_dev, coverage_dev, level_dev);
+    if (plan.boxes.empty()) plan.boxes.resize(1);                // never read: no tile lists it
+    if (plan.candidates.empty()) plan.candidates.push_back(0);   // never read: every list is empty
+    avr::CoverArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::CoverBoxDev) +
+                           plan.candidate_begin.size() * sizeof(uint32_t) +
+                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
+    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
+    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
+    ctx->staging.commit(ctx->stream);
+    args.level = level;
+    args.finest = plan.finest;
+    for (int d = 0; d < 3; ++d) args.lo[d] = lo[d];
+    args.nx = dims[0];
+    args.ny = dims[1];
+    args.nz = dims[2];
+    args.n_tiles = static_cast<uint32_t>(plan.candidate_begin.size() - 1);
+    args.fill = fill;
+    args.values = values_dev;
+    args.coverage = coverage_dev;
+    args.cell_level = level_dev;
+    return avr::launch_covering_grid(args, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

@@ -1,5 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps, isosurfaces, streamlines): everything a call works out from its arguments before
+// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids): everything a
+// call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
 // rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
@@ -958,6 +959,184 @@ inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const a
   for (size_t b : order) {
     for_blocks(b, [&](size_t block) { plan.block_boxes[fill[block]++] = static_cast<int32_t>(b); });
   }
+  return plan;
+}
+
+// ---- covering grids -----------------------------------------------------------------------
+// ratio[from] * ... * ratio[to - 1] (from <= to), or 2^32 if it is more: from 2^31 on, every index
+// but 0 and -1 times the factor lies outside [-2^30, 2^30) whatever the factor is, and every index
+// of that range divided by it gives 0 or -1.
+inline int64_t level_factor(const int32_t* ratio, int from, int to) {
+  int64_t factor = 1;
+  for (int l = from; l < to; ++l) {
+    factor = std::min(factor * ratio[l], int64_t{1} << 32);  // below 2^63: a ratio is below 2^31
+  }
+  return factor;
+}
+// A region of level `from` (inside [-2^30, 2^30)) at level `to`: its descendants at a finer level,
+// the cells that hold it at a coarser one.  Past a factor of 2^32 the finer region is not exact,
+// but meets [-2^30, 2^30) in the same cells.
+inline IndexRegion region_at_level(const IndexRegion& region, int from, int to,
+                                   const int32_t* ratio) {
+  IndexRegion out;
+  const int64_t r = from <= to ? level_factor(ratio, from, to) : level_factor(ratio, to, from);
+  for (int d = 0; d < 3; ++d) {
+    out.lo[d] = from <= to ? region.lo[d] * r : floor_div(region.lo[d], r);
+    out.hi[d] = from <= to ? region.hi[d] * r + (r - 1) : floor_div(region.hi[d], r);
+  }
+  return out;
+}
+
+// The candidate lists of the tiles of `output`, a region of level `level` cut into the tiles of
+// avr_cell_tiles.h (numbered as cell_tile_of numbers a box's): CSR over the tiles, per tile every
+// box, in scene order, whose cells meet the tile's index slab at the box's own level -- the slab
+// mapped down by floor division for a coarser box and multiplied up for a finer one, which is to
+// say that the box, mapped to `level` the other way, meets the tile.  A sibling of
+// append_region_candidates, which serves "the surroundings of box b" and looks one level finer at
+// the most; this one serves a region that belongs to no box and looks at every level.  Box: a
+// device box with nx (0 without cells) and level; ratio[l]: level l -> l + 1.
+template <class Box>
+inline void tile_candidate_lists(const std::vector<Box>& boxes,
+                                 const std::vector<IndexRegion>& regions, const int32_t* ratio,
+                                 int level, const IndexRegion& output,
+                                 std::vector<uint32_t>* candidate_begin,
+                                 std::vector<int32_t>* candidates) {
+  const int nx = static_cast<int>(output.hi[0] - output.lo[0] + 1);
+  const int ny = static_cast<int>(output.hi[1] - output.lo[1] + 1);
+  const int nz = static_cast<int>(output.hi[2] - output.lo[2] + 1);
+  const size_t tiles = cell_tiles(nx, ny, nz);
+  const CellTileShape shape = cell_tile_shape(nx, ny);
+  const int64_t edge[3] = {kClassifyChunk, kBrickY, kBrickZ};
+  // the tiles box c meets: [first, last] per axis; false if it meets none
+  auto tile_range = [&](size_t c, int64_t first[3], int64_t last[3]) {
+    if (boxes[c].nx <= 0) return false;
+    const IndexRegion at = region_at_level(regions[c], boxes[c].level, level, ratio);
+    if (!regions_meet(at, output)) return false;
+    for (int d = 0; d < 3; ++d) {
+      first[d] = (std::max(at.lo[d], output.lo[d]) - output.lo[d]) / edge[d];
+      last[d] = (std::min(at.hi[d], output.hi[d]) - output.lo[d]) / edge[d];
+    }
+    return true;
+  };
+  // the lists' size from the boxes' extents, before anything of that size is made
+  uint64_t entries = 0;
+  for (size_t c = 0; c < boxes.size(); ++c) {
+    int64_t first[3], last[3];
+    if (!tile_range(c, first, last)) continue;
+    entries += static_cast<uint64_t>(last[0] - first[0] + 1) *
+               static_cast<uint64_t>(last[1] - first[1] + 1) *
+               static_cast<uint64_t>(last[2] - first[2] + 1);  // at most 2^31 tiles each
+    require_box(entries < (uint64_t{1} << 31), "the tiles' candidate lists hold 2^31 entries or more");
+  }
+  auto for_tiles = [&](size_t c, auto&& visit) {
+    int64_t first[3], last[3];
+    if (!tile_range(c, first, last)) return;
+    for (int64_t bk = first[2]; bk <= last[2]; ++bk) {
+      for (int64_t bj = first[1]; bj <= last[1]; ++bj) {
+        for (int64_t chunk = first[0]; chunk <= last[0]; ++chunk) {
+          visit(static_cast<size_t>((bk * shape.bricks_y + bj) * shape.chunks + chunk));
+        }
+      }
+    }
+  };
+  std::vector<uint32_t> fill(tiles + 1, 0u);
+  for (size_t c = 0; c < boxes.size(); ++c) for_tiles(c, [&](size_t tile) { ++fill[tile + 1]; });
+  for (size_t tile = 0; tile < tiles; ++tile) fill[tile + 1] += fill[tile];
+  candidate_begin->assign(fill.begin(), fill.end());
+  candidates->resize(static_cast<size_t>(fill[tiles]));
+  for (size_t c = 0; c < boxes.size(); ++c) {
+    for_tiles(c, [&](size_t tile) { (*candidates)[fill[tile]++] = static_cast<int32_t>(c); });
+  }
+}
+
+struct CoveringGridPlan {
+  std::vector<CoverBoxDev> boxes;
+  CoverLevelsDev levels;   // the ratios, and R_m and w_m of the loaded levels finer than `level`
+  int32_t finest = -1;     // the finest level that has a box with cells (-1: none has)
+  // CSR over the output's tiles (tile_candidate_lists): candidate_begin has tiles + 1 entries
+  std::vector<uint32_t> candidate_begin;
+  std::vector<int32_t> candidates;  // empty when no box meets the region
+};
+// The field resampled to the cells [lo, lo + dims) of level `level` ("Covering
+// grid").  box_index_lo and level_ratio as plan_gradient takes them; n_levels counts the levels up
+// to the finer of `level` and the finest loaded one.  values, coverage and cell_level are device
+// arrays of dims[0] * dims[1] * dims[2] entries (f64, f64, i8); coverage and cell_level may be
+// null, values has been checked by the entry point.  The rules, in this order: n_levels, level,
+// null arrays, the box rules, the ratios, the index ranges, boxes of one level apart in index
+// space, dims, the region inside [-2^30, 2^30) at `level` and at the finest loaded level, fewer
+// than 2^31 cells, no output byte shared with an input, the candidate lists' size.
+inline CoveringGridPlan plan_covering_grid(const avr_box* field, size_t n_boxes, int level,
+                                           const int32_t lo[3], const int32_t dims[3],
+                                           const int32_t* box_index_lo,
+                                           const int32_t* level_ratio, int n_levels,
+                                           const void* values, const void* coverage,
+                                           const void* cell_level) {
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(level >= 0 && level < n_levels, "level must lie in [0, n_levels)");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  CoveringGridPlan plan;
+  std::vector<CoverBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = field[b];
+    const avr_box* fields[1] = {&first};
+    FieldView view;
+    CoverBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool cells = field_box_views(first, fields, 1, n_levels, &view, &paired);
+    dev.cells = view.cells;
+    dev.jstride = view.jstride;
+    dev.kstride = view.kstride;
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&read_ranges, view);
+      plan.finest = std::max(plan.finest, dev.level);
+    }
+  }
+  CoverLevelsDev& levels = plan.levels;
+  std::memset(&levels, 0, sizeof(levels));
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, field, &boxes);
+  require_levels_disjoint(boxes, regions);
+  require_box(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "dims must be at least 1");
+  const int finest = std::max(plan.finest, level);
+  const int64_t limit = int64_t{1} << 30, up = level_factor(levels.ratio, level, finest);
+  IndexRegion output;
+  for (int d = 0; d < 3; ++d) {
+    output.lo[d] = lo[d];
+    output.hi[d] = static_cast<int64_t>(lo[d]) + dims[d] - 1;
+    require_box(output.lo[d] >= -limit && output.hi[d] < limit &&
+                    output.lo[d] * up >= -limit && (output.hi[d] + 1) * up <= limit,
+                "the region leaves [-2^30, 2^30) at its level or at the finest loaded one");
+  }
+  // dims are at most 2^31 each here: two factors first
+  const uint64_t plane = static_cast<uint64_t>(dims[0]) * static_cast<uint64_t>(dims[1]);
+  require_box(plane < (uint64_t{1} << 31) &&
+                  plane * static_cast<uint64_t>(dims[2]) < (uint64_t{1} << 31),
+              "the region has 2^31 cells or more");
+  const uint64_t n_cells = plane * static_cast<uint64_t>(dims[2]);
+  append_byte_range(&write_ranges, values, n_cells * sizeof(double));
+  if (coverage != nullptr) append_byte_range(&write_ranges, coverage, n_cells * sizeof(double));
+  if (cell_level != nullptr) append_byte_range(&write_ranges, cell_level, n_cells);
+  require_no_shared_byte(&read_ranges, write_ranges,
+                         "an output array overlaps an input box's cells");
+  // R_m and w_m: the region rule keeps R_m of a loaded level at 2^30 or less, R_m^3 inside 2^90
+  for (int m = 0; m < kFieldMaxLevels; ++m) levels.refine[m] = 1;
+  for (int m = level + 1; m <= plan.finest; ++m) {
+    const int64_t r = level_factor(levels.ratio, level, m);
+    levels.refine[m] = static_cast<int32_t>(r);
+    const unsigned __int128 cube = static_cast<unsigned __int128>(r) * static_cast<uint64_t>(r) *
+                                   static_cast<uint64_t>(r);
+    levels.weight[m] = 1.0 / static_cast<double>(cube);
+  }
+  tile_candidate_lists(boxes, regions, levels.ratio, level, output, &plan.candidate_begin,
+                       &plan.candidates);
   return plan;
 }
 

@@ -772,6 +772,43 @@ struct StreamArgs {
 };
 int launch_streamlines(const StreamArgs& args, bool has_sample, void* stream);
 
+// Covering grids (avr_covering_grid.hip): a field resampled to the cells of one level L over a
+// region of nx x ny x nz cells from the level-L index `lo` on, one lane per output cell.  The
+// output is cut into the tiles of avr_cell_tiles.h (128 cells along x by 4 rows by 4 planes,
+// numbered as cell_tile_of numbers a box's); tile t has the candidate list [candidate_begin[t],
+// candidate_begin[t + 1]): every box, in scene order, whose cells hold a cell of the tile, an
+// ancestor or a descendant of one.  A box as the kernel reads it:
+struct alignas(16) CoverBoxDev {
+  const double* cells;
+  int32_t jstride, kstride;  // element strides (Array4); the field spans < 2^28 elements
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t pad_[1];
+};
+static_assert(sizeof(CoverBoxDev) == 48, "CoverBoxDev: 16-byte multiple");
+struct CoverLevelsDev {
+  double weight[kFieldMaxLevels];   // [m], L < m <= finest: w_m = 1 / f64(R_m^3); 0.0 elsewhere
+  int32_t refine[kFieldMaxLevels];  // [m], L < m <= finest: R_m = ratio[L] ... ratio[m - 1]; else 1
+  int32_t ratio[kFieldMaxLevels];   // ratio[l]: level l -> l + 1 (1 from n_levels - 1 on)
+};
+struct CoverArgs {
+  const CoverBoxDev* boxes;
+  const uint32_t* candidate_begin;  // n_tiles + 1
+  const int32_t* candidates;
+  const CoverLevelsDev* levels;
+  int32_t level;          // L
+  int32_t finest;         // the finest level that has a box with cells (-1: none has)
+  int32_t lo[3];
+  int32_t nx, ny, nz;     // nx * ny * nz < 2^31
+  uint32_t n_tiles;
+  double fill;
+  double* values;         // [nz][ny][nx]
+  double* coverage;       // the same shape, or null
+  int8_t* cell_level;     // the same shape, or null
+};
+int launch_covering_grid(const CoverArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

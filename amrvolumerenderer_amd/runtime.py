@@ -938,6 +938,48 @@ class Scene:
         ctx.publish()
         return points, samples, counts, status
 
+    def covering_grid(self, level: int, lo, dims, box_index_lo, level_ratio,
+                      fill: float = math.nan, with_coverage: bool = True):
+        """avr_scene_covering_grid with this scene as the field: the field resampled to the cells
+        [lo, lo + dims) of level `level` -- a leaf of the same or a coarser level gives its value,
+        finer leaves their volume-weighted mean, and a cell no leaf touches gives fill.  lo, dims:
+        three ints each, dims as (nx, ny, nz); box_index_lo: [n_boxes, 3] int32; level_ratio:
+        n_levels - 1 ints, n_levels counting the levels up to the finer of `level` and the finest
+        box level.  Returns (values float64 [nz, ny, nx], coverage float64 [nz, ny, nx], cell
+        level int8 [nz, ny, nx]) on the device; the last two are None without with_coverage.
+        Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        first = np.ascontiguousarray(lo, dtype=np.int64)
+        extent = np.ascontiguousarray(dims, dtype=np.int64)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if ratios.ndim != 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        if first.shape != (3,) or extent.shape != (3,):
+            raise ValueError("lo and dims must hold three values")
+        if (extent < 1).any() or (extent > 2 ** 31 - 1).any() or (abs(first) > 2 ** 31 - 1).any():
+            raise ValueError("dims must be at least 1 (and lo and dims fit 32 bits)")
+        nx, ny, nz = (int(v) for v in extent)
+        if nx * ny * nz >= 2 ** 31:
+            raise ValueError("the region has 2^31 cells or more")
+        first, extent = first.astype(np.int32), extent.astype(np.int32)
+        values = torch.empty((nz, ny, nx), dtype=torch.float64, device=ctx.device)
+        coverage = cell_level = None
+        if with_coverage:
+            coverage = torch.empty((nz, ny, nx), dtype=torch.float64, device=ctx.device)
+            cell_level = torch.empty((nz, ny, nx), dtype=torch.int8, device=ctx.device)
+        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        as_ints = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_covering_grid(
+            ctx._handle, self._handle, int(level), as_ints(first), as_ints(extent), as_ints(index),
+            as_ints(ratios), int(ratios.size) + 1, float(fill), pointer(values), pointer(coverage),
+            pointer(cell_level)))
+        ctx.publish()
+        return values, coverage, cell_level
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

@@ -1318,6 +1318,40 @@ int avr_scene_streamlines(avr_context *ctx, const avr_scene *vx, const avr_scene
                           double *points_dev, double *samples_dev, uint32_t *counts_dev,
                           uint8_t *status_dev);
 
+/* ---- covering grids ("Covering grid") ----------------------------------------------- */
+
+/* `field` (a scene of ctx; raw f64 cells, no transform; its boxes are the uncovered cells of the
+ * loaded levels) resampled to the cells of level `level`: output cell (i, j, k) has the level-
+ * `level` index G = lo + (i, j, k), 0 <= (i, j, k) < dims (lo, dims: host, three values each; the
+ * region may reach past the data and lo may be negative).  The hierarchy description
+ * (box_index_lo, level_ratio, n_levels <= 16; host) is avr_scene_gradient's; n_levels counts the
+ * levels up to the finer of `level` and the finest level of a box, so `level` may be finer than
+ * every box.  Three rules, in order:
+ *  1. if a box of a level m <= level contains G mapped to level m by floor division, the box of
+ *     the highest such m gives the cell's stored double with its bits kept (a NaN, an infinity
+ *     and -0.0 are data), coverage 1.0 and cell level m;
+ *  2. else, from num = den = +0.0, for every m = level + 1, ..., finest box level in that order:
+ *     R_m = level_ratio[level] * ... * level_ratio[m - 1], w_m = 1.0 / f64(R_m^3); s = +0.0 and
+ *     n = 0; for kk, then jj, then ii ascending over [G R_m, (G + 1) R_m), a level-m box that
+ *     holds (ii, jj, kk) adds its cell, s = s + v, and one to n; with n > 0, num = num + w_m * s
+ *     (one rounded multiply, one rounded add, nothing fused), den = den + w_m * f64(n) and the
+ *     cell level is m.  With den > 0 the value is num / den and the coverage den;
+ *  3. else the value is `fill` with its bits kept, the coverage 0.0 and the cell level -1.
+ * values_dev (device, f64 [dims[2]][dims[1]][dims[0]]) gets the values; coverage_dev (f64) and
+ * level_dev (i8) of the same shape get the coverage and the cell level, and either may be NULL:
+ * they depend on the boxes alone, not on the field's values.  Equal arguments give equal bits.
+ * Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for n_levels outside [1, 16], level outside [0, n_levels), a box level
+ * >= n_levels (and the other box rules), a ratio below 2, a box index range outside [-2^30,
+ * 2^30), two boxes of one level that overlap in index space, a dims below 1, a region that leaves
+ * [-2^30, 2^30) at `level` or, multiplied up, at the finest box level, 2^31 cells or more, an
+ * output array that shares a byte with a box's cells, and candidate lists of 2^31 entries or more
+ * -- and every output is untouched.  Stateless; asynchronous on the context's stream. */
+int avr_scene_covering_grid(avr_context *ctx, const avr_scene *field, int level, const int32_t *lo,
+                            const int32_t *dims, const int32_t *box_index_lo,
+                            const int32_t *level_ratio, int n_levels, double fill,
+                            double *values_dev, double *coverage_dev, int8_t *level_dev);
+
 #ifdef __cplusplus
 }
 #endif
