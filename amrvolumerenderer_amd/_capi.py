@@ -130,6 +130,7 @@ SIGNATURES = {
     "avr_context_set_march_occupancy": (C.c_int, [_vp, C.c_int]),
     "avr_context_set_classify_lds_reserve": (C.c_int, [_vp, C.c_int]),
     "avr_context_set_march_counters": (C.c_int, [_vp, _vp]),
+    "avr_context_last_march_mode": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "avr_context_synchronize": (C.c_int, [_vp]),
     "avr_build_color_table": (C.c_int, [C.c_float, C.c_float, _fp, C.POINTER(ColormapPoint),
                                          C.c_int, _fp]),
@@ -321,6 +322,7 @@ SIGNATURES = {
     "avr_renderer_corun_history": (C.c_int, [_vp, C.POINTER(C.c_int16), C.c_int,
                                              C.POINTER(C.c_int)]),
     "avr_renderer_failure": (C.c_char_p, [_vp]),
+    "avr_renderer_last_march_mode": (C.c_int, [_vp, C.POINTER(C.c_int)]),
 }
 
 CONTROL_MAX_BYTES = 2048

@@ -338,6 +338,7 @@ struct avr_context {
   bool classify_stream_stores = false;         // context_set_classify_stream_stores
   bool fold_whole_grid = false;                // context_set_fold_whole_grid
   uint64_t* march_counters = nullptr;          // diagnostics (avr_context_set_march_counters)
+  int last_only_mode = -2;                     // ... (avr_context_last_march_mode; -2: no march yet)
   avr::DeviceBuffer max_layers;                // layer of avr_paint_box_max
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
@@ -742,6 +743,7 @@ int render(avr_context* ctx, const RenderRequest& frame, const FrameChunks& chun
     for (const avr::BoxDev& dev : plan.boxes) {
       if (dev.index_mode != launch.only_mode) launch.only_mode = -1;
     }
+    ctx->last_only_mode = launch.only_mode;
   }
   staging.commit(ctx->stream);
   if (chunked) {
@@ -916,6 +918,14 @@ int avr_context_set_march_counters(avr_context* ctx, uint64_t* counters_dev) {
   return guarded([&]() -> int {
     require(ctx != nullptr, "null context");
     ctx->march_counters = counters_dev;
+    return AVR_OK;
+  });
+}
+
+int avr_context_last_march_mode(const avr_context* ctx, int* only_mode_out) {
+  return guarded([&]() -> int {
+    require(ctx != nullptr && only_mode_out != nullptr, "null argument");
+    *only_mode_out = ctx->last_only_mode;
     return AVR_OK;
   });
 }

@@ -314,6 +314,15 @@ bool fold_is_exact(const BoxDev& dev) {
   return bounded(dev.inv_dx) && bounded(dev.inv_dy) && bounded(dev.inv_dz);
 }
 
+// kPow2Bricks marches with 32 * inv_dz and 32 * nmin_inv[2], so that int(32 * qz) is the z index
+// five bits up (avr_brick_address.h).  fma(pos, 32 a, 32 b) = 32 * fma(pos, a, b) by the argument
+// above as long as the two scaled constants are themselves exact: zero, or finite and normal.
+bool scales_by_32(float v) {
+  const float scaled = 32.0f * v;
+  return v == 0.0f || (std::isfinite(scaled) && std::fpclassify(scaled) == FP_NORMAL &&
+                       std::fpclassify(v) == FP_NORMAL);
+}
+
 // Conservative screen rectangle of a box: every pixel whose forward ray can intersect the box
 // lies inside.  Pixels outside produce the empty layer pixel (0,0,0,0,+inf) in the reference
 // (slab miss, or an intersection interval entirely behind the eye: VolumePainter.cpp:802-837),
@@ -1122,6 +1131,13 @@ void plan_frame(const avr_box* boxes, int n_boxes, const avr_scalar_transform& t
       dev.nmin_inv[0] = -(dev.minc[0] * dev.inv_dx);
       dev.nmin_inv[1] = -(dev.minc[1] * dev.inv_dy);
       dev.nmin_inv[2] = -(dev.minc[2] * dev.inv_dz);
+      int sx = 0, sy = 0;
+      if (pow2_brick_shifts(dev.nx, dev.ny, dev.nz, &sx, &sy) && scales_by_32(dev.inv_dz) &&
+          scales_by_32(dev.nmin_inv[2])) {
+        dev.index_mode = kPow2Bricks;
+        dev.brick_sx = sx;
+        dev.brick_sy = sy;
+      }
     } else {
       dev.index_mode = kReciprocal;
     }

@@ -20,6 +20,7 @@
 #endif
 
 #include "avr_level_cells.h"  // kFieldMaxLevels; after AVR_HD, which it would otherwise define
+#include "avr_brick_address.h"  // pow2_brick_shifts, pow2_brick_offset
 
 namespace avr {
 
@@ -36,6 +37,10 @@ enum IndexMode : int32_t {
                       // floor(q) is the reference's index unless q is within near_tol of an
                       // integer; those samples take the exact divide
   kExactDivide = 2,   // degenerate spacing (dx <= 0 or not finite): always the exact divide
+  kPow2Bricks = 3,    // kPow2Multiply, and the box's y and z bricklet counts are powers of two as
+                      // well (pow2_brick_shifts, avr_brick_address.h): in a launch whose boxes all
+                      // have this mode the interior loops of the march build the bricklet offset in
+                      // four instructions; in any other launch the box is marched as kPow2Multiply
 };
 
 // Per-box constants of VolumePainter::paint's host prologue (Common/VolumePainter.cpp:571-692),
@@ -55,10 +60,10 @@ struct alignas(16) BoxDev {
   int32_t kstride;
   float inv_dx, inv_dy, inv_dz;  // RN(1 / dx)
   float near_tol;         // kReciprocal: |q - rint(q)| <= near_tol sends the sample to the exact divide
-  int32_t pad_;
+  int32_t brick_sy;       // kPow2Bricks: bit of the y bricklet pitch (pow2_brick_shifts), else 0
   uint64_t cls_offset;    // byte offset of this box's classified bricklets in the frame's buffer
   float nmin_inv[3];      // kPow2Multiply: -(minc * inv_d), exact (a power-of-two scaling)
-  int32_t pad2_;
+  int32_t brick_sx;       // kPow2Bricks: bit of the x bricklet pitch, else 0
 };
 static_assert(sizeof(BoxDev) == 144, "BoxDev is read with scalar loads: keep it a multiple of 16 bytes");
 

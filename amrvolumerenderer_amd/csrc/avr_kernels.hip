@@ -144,6 +144,10 @@ __device__ __forceinline__ void slab_axis(float origin, float direction, float i
 // with y_pitch = 128*bz - 32 and x_pitch = 128*bz*by - 8, both < 2^24 (host check), i.e. two
 // shifts, two shift-adds and two 24-bit multiply-adds (the march is bound by the number of
 // vector instructions; an x-fastest brick order needs two more).
+// This is the general form: by and bz may be any number.  Where both are powers of two the pitches
+// are single bits and the same offset is four instructions (pow2_brick_offset, avr_brick_address.h):
+// the interior loops of a launch whose boxes all qualify (kPow2Bricks) use that; the general loop,
+// the other modes and a launch of mixed boxes use this one.
 __device__ __forceinline__ uint32_t bricklet_offset(int i, int j, int k, uint32_t y_pitch,
                                                     uint32_t x_pitch) {
   const uint32_t ui = static_cast<uint32_t>(i), uj = static_cast<uint32_t>(j),
@@ -258,6 +262,10 @@ march_box(const BoxDev& box, const FrameConsts& fc,
                                             float tmin, float tmax, unsigned& fetches,
                                             unsigned& near_hits) {
   constexpr bool is_max = KIND == FrameKind::kMaxIntensity, is_sum = KIND == FrameKind::kProjection;
+  // the fused power-of-two quotient, and with it the four-instruction bricklet offset (a
+  // projection addresses the raw cells and marches a kPow2Bricks box as kPow2Multiply)
+  constexpr bool pow2 = MODE == kPow2Multiply || MODE == kPow2Bricks;
+  constexpr bool brick4 = MODE == kPow2Bricks && !is_sum;
   const float min_x = box.minc[0], min_y = box.minc[1], min_z = box.minc[2];
   const float max_x = box.maxc[0], max_y = box.maxc[1], max_z = box.maxc[2];
   const float step = box.sample_dist;
@@ -339,10 +347,31 @@ march_box(const BoxDev& box, const FrameConsts& fc,
     const float inv_x = box.inv_dx, inv_y = box.inv_dy, inv_z = box.inv_dz;
     // loop-invariant operand pairs of the packed fused quotient (kept in registers: a packed
     // instruction reads at most one scalar-register operand)
-    const float_pair ix2 = {inv_x, inv_x}, iy2 = {inv_y, inv_y}, iz2 = {inv_z, inv_z};
+    // kPow2Bricks: the z quotient of the two loops below is 32 * qz -- its integer part is the z
+    // term of the offset, 32 * k, over five bits of fraction that pow2_brick_offset overwrites --
+    // by scaling both constants of the fused quotient (exact, and commutes with the rounding: the
+    // host checked the magnitudes).  Everything else in this function, the end-point test above
+    // and the general loop included, reads the unscaled box.inv_dz.
+    constexpr float z_scale = brick4 ? 32.0f : 1.0f;
+    const float inv_zs = inv_z * z_scale, nmin_zs = box.nmin_inv[2] * z_scale;
+    const float_pair ix2 = {inv_x, inv_x}, iy2 = {inv_y, inv_y}, iz2 = {inv_zs, inv_zs};
     float_pair nx2 = {box.nmin_inv[0], box.nmin_inv[0]}, ny2 = {box.nmin_inv[1], box.nmin_inv[1]},
-               nz2 = {box.nmin_inv[2], box.nmin_inv[2]};
-    if (MODE == kPow2Multiply) asm volatile("" : "+v"(nx2), "+v"(ny2), "+v"(nz2));
+               nz2 = {nmin_zs, nmin_zs};
+    if (pow2) asm volatile("" : "+v"(nx2), "+v"(ny2), "+v"(nz2));
+    // the two multipliers and two masks of the four-instruction offset, wave-uniform
+    [[maybe_unused]] const Pow2BrickKeys keys =
+        brick4 ? pow2_brick_keys(box.brick_sx, box.brick_sy) : Pow2BrickKeys{};
+    // truncated quotients -> byte offset: the z argument is int(qz), or int(32 * qz) for brick4
+    auto offset_of = [&](float qx, float qy, float qz) -> uint32_t {
+      if constexpr (brick4) {
+        return pow2_brick_offset(static_cast<uint32_t>(static_cast<int>(qx)),
+                                 static_cast<uint32_t>(static_cast<int>(qy)),
+                                 static_cast<uint32_t>(static_cast<int>(qz)), keys);
+      } else {
+        return cell_address<is_sum>(static_cast<int>(qx), static_cast<int>(qy),
+                                    static_cast<int>(qz), row_pitch, plane_pitch);
+      }
+    };
 #if AVR_MARCH_GROUP > 4
     // kDeep (8, 12 ...) steps per trip while all of them lie below safe_end: several groups' worth
     // of cell bytes and table entries in flight per wave.  Side by side with the classify pass a
@@ -350,7 +379,7 @@ march_box(const BoxDev& box, const FrameConsts& fc,
     // trip per trip of this loop (profiles/r5_corun_counters/): more loads per trip is what a wave
     // can still give.  Every sample is accumulated by the same operations in the same order as
     // below; what is left takes the loop of four, then the general loop.
-    if (MODE == kPow2Multiply || MODE == kReciprocal) {
+    if (pow2 || MODE == kReciprocal) {
       constexpr int kDeep = AVR_MARCH_GROUP;
       static_assert(kDeep % 2 == 0, "the positions are computed two at a time");
       for (;;) {
@@ -363,14 +392,12 @@ march_box(const BoxDev& box, const FrameConsts& fc,
 #pragma unroll
         for (int pair = 0; pair < kDeep / 2; ++pair) {
           const float_pair dd = {d[2 * pair], d[2 * pair + 1]};
-          if (MODE == kPow2Multiply) {
+          if (pow2) {
             const float_pair qx = __builtin_elementwise_fma(ray.ox + ray.dx * dd, ix2, nx2);
             const float_pair qy = __builtin_elementwise_fma(ray.oy + ray.dy * dd, iy2, ny2);
             const float_pair qz = __builtin_elementwise_fma(ray.oz + ray.dz * dd, iz2, nz2);
-            off[2 * pair] = cell_address<is_sum>(static_cast<int>(qx.x), static_cast<int>(qy.x),
-                                            static_cast<int>(qz.x), row_pitch, plane_pitch);
-            off[2 * pair + 1] = cell_address<is_sum>(static_cast<int>(qx.y), static_cast<int>(qy.y),
-                                                static_cast<int>(qz.y), row_pitch, plane_pitch);
+            off[2 * pair] = offset_of(qx.x, qy.x, qz.x);
+            off[2 * pair + 1] = offset_of(qx.y, qy.y, qz.y);
           } else {
             // the reference's two roundings, (pos - min) then * RN(1/d), as in the loop of four
             const float_pair fx = (ray.ox + ray.dx * dd) - min_x;
@@ -479,7 +506,7 @@ march_box(const BoxDev& box, const FrameConsts& fc,
                                         (ray.ox + ray.dx * d4) - min_x,
                                         (ray.oy + ray.dy * d4) - min_y,
                                         (ray.oz + ray.dz * d4) - min_z, near_hits);
-      } else if (MODE == kPow2Multiply) {
+      } else if (pow2) {
         // q = (pos - min) * 2^k as ONE fused operation: the exact value pos * 2^k - min * 2^k is
         // rounded once, which is RN(pos - min) * 2^k (see fold_is_exact in avr_host.cpp).  Two
         // samples per packed instruction (v_pk_mul / v_pk_add / v_pk_fma_f32: each half is an
@@ -491,14 +518,10 @@ march_box(const BoxDev& box, const FrameConsts& fc,
         const float_pair qx34 = __builtin_elementwise_fma(ray.ox + ray.dx * d34, ix2, nx2);
         const float_pair qy34 = __builtin_elementwise_fma(ray.oy + ray.dy * d34, iy2, ny2);
         const float_pair qz34 = __builtin_elementwise_fma(ray.oz + ray.dz * d34, iz2, nz2);
-        off1 = cell_address<is_sum>(static_cast<int>(qx12.x), static_cast<int>(qy12.x),
-                               static_cast<int>(qz12.x), row_pitch, plane_pitch);
-        off2 = cell_address<is_sum>(static_cast<int>(qx12.y), static_cast<int>(qy12.y),
-                               static_cast<int>(qz12.y), row_pitch, plane_pitch);
-        off3 = cell_address<is_sum>(static_cast<int>(qx34.x), static_cast<int>(qy34.x),
-                               static_cast<int>(qz34.x), row_pitch, plane_pitch);
-        off4 = cell_address<is_sum>(static_cast<int>(qx34.y), static_cast<int>(qy34.y),
-                               static_cast<int>(qz34.y), row_pitch, plane_pitch);
+        off1 = offset_of(qx12.x, qy12.x, qz12.x);
+        off2 = offset_of(qx12.y, qy12.y, qz12.y);
+        off3 = offset_of(qx34.x, qy34.x, qz34.x);
+        off4 = offset_of(qx34.y, qy34.y, qz34.y);
       } else {
         // the reference's two roundings, (pos - min) then * RN(1/d), two samples per instruction
         const float_pair d12 = {d1, d2}, d34 = {d3, d4};
@@ -594,7 +617,9 @@ march_box(const BoxDev& box, const FrameConsts& fc,
         // some lane's ray terminates inside this group: per-sample selects (sample k + 1 is
         // accumulated only if the reference's loop condition accumA < 1 still holds after
         // sample k; done with selects, not branches, so that the loads above stay unconditional)
-        unsigned taken = 1u;
+        // (a lane that left the loop of kDeep above because its ray terminated there arrives with
+        // accumA == 1: its first sample adds s.w * 0 and is not one the reference takes)
+        unsigned taken = (acc_a < 1.0f) ? 1u : 0u;
         float next = d2;
         AVR_ACCUMULATE(s1);
 #define AVR_ACCUMULATE_IF_RUNNING(sample, following)          \
@@ -694,13 +719,17 @@ march_box(const BoxDev& box, const FrameConsts& fc,
 }
 
 // ONLY_MODE >= 0: every box of the launch uses that IndexMode (the common case: one scene, one
-// kind of spacing), so only that march variant is compiled in; -1 dispatches per box.
+// kind of spacing), so only that march variant is compiled in; -1 dispatches per box, and marches a
+// kPow2Bricks box as kPow2Multiply (no third copy of the loops).
 // Registers, as the compiler reports them (make asm): every march kernel takes 106 SGPRs except
-// the two ONLY_MODE = kPow2Multiply column projections (100), and spills some of them to vector
-// lanes (volume 15-44, maximum intensity 0-6, projection 0-25; no VGPR spills); 16 bytes of scratch
-// per lane in the speculative kernels, 24 in the two ONLY_MODE = -1 volume kernels, none elsewhere;
-// 85-105 VGPRs for a volume frame (5 waves per SIMD, 4 for the two non-speculative ONLY_MODE = -1
-// kernels), 46-56 for maximum intensity (7) and 58-73 for a projection (6-8).
+// the two ONLY_MODE = kPow2Multiply column projections (100) and the two kPow2Bricks maximum-
+// intensity kernels (102), and spills some of them to vector lanes (volume 15-44, maximum
+// intensity 0-6, projection 0-17; no VGPR spills); 16 bytes of scratch per lane in the speculative
+// kernels, 24 in the two ONLY_MODE = -1 volume kernels, none elsewhere; 85-105 VGPRs for a volume
+// frame (5 waves per SIMD; 4 for the two non-speculative ONLY_MODE = -1 kernels and for the
+// kPow2Bricks kernel that counts samples, 98), 46-56 for maximum intensity (7) and 58-73 for a
+// projection (6-8).  The frame's own march, render_runs_kernel<false, kPow2Bricks, false>: 94
+// VGPRs, 25 spilled SGPRs, no scratch, 5 waves (kPow2Multiply: 91, 31).
 // SPEC: the speculative frame's bookkeeping is compiled in (its own instantiation; never together
 // with STATS).
 // KIND, the kind of frame (FrameKind, avr_internal.h; only kVolume goes with SPEC, chunks or
@@ -896,13 +925,16 @@ render_runs_body(
         if (!__builtin_amdgcn_ballot_w64(hit)) continue;
         if (hit) {
           int m;
-          if (ONLY_MODE == kPow2Multiply) {
+          if (ONLY_MODE == kPow2Bricks) {
+            m = march_box<STATS, kPow2Bricks, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
+                                                    fetches, near_hits);
+          } else if (ONLY_MODE == kPow2Multiply) {
             m = march_box<STATS, kPow2Multiply, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                       fetches, near_hits);
           } else if (ONLY_MODE == kReciprocal) {
             m = march_box<STATS, kReciprocal, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                     fetches, near_hits);
-          } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
+          } else if (box.index_mode == kPow2Multiply || box.index_mode == kPow2Bricks) {  // wave-uniform
             m = march_box<STATS, kPow2Multiply, KIND>(box, fc, classified, nullptr, ray, tmin, tmax,
                                                       fetches, near_hits);
           } else if (box.index_mode == kReciprocal) {
@@ -920,13 +952,13 @@ render_runs_body(
         if (!__builtin_amdgcn_ballot_w64(hit)) continue;
         if (hit) {
           ColumnSum c;
-          if (ONLY_MODE == kPow2Multiply) {
+          if (ONLY_MODE == kPow2Multiply || ONLY_MODE == kPow2Bricks) {  // (no bricklets here)
             c = march_box<STATS, kPow2Multiply, KIND>(box, fc, nullptr, nullptr, ray, tmin,
                                                              tmax, fetches, near_hits);
           } else if (ONLY_MODE == kReciprocal) {
             c = march_box<STATS, kReciprocal, KIND>(box, fc, nullptr, nullptr, ray, tmin, tmax,
                                                            fetches, near_hits);
-          } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
+          } else if (box.index_mode == kPow2Multiply || box.index_mode == kPow2Bricks) {  // wave-uniform
             c = march_box<STATS, kPow2Multiply, KIND>(box, fc, nullptr, nullptr, ray, tmin,
                                                              tmax, fetches, near_hits);
           } else if (box.index_mode == kReciprocal) {
@@ -973,14 +1005,18 @@ render_runs_body(
         const float4* table = lds_tables + box.lut * kTableSize;
         Layer5 layer;
         const unsigned before = fetches;
-        int mode = ONLY_MODE;
-        if (ONLY_MODE == kPow2Multiply) {
+        // (kPow2Bricks counts with kPow2Multiply: one entry of the diagnostics for both)
+        int mode = ONLY_MODE == kPow2Bricks ? kPow2Multiply : ONLY_MODE;
+        if (ONLY_MODE == kPow2Bricks) {
+          layer = march_box<STATS, kPow2Bricks>(box, fc, classified, table, ray, tmin, tmax,
+                                                fetches, near_hits);
+        } else if (ONLY_MODE == kPow2Multiply) {
           layer = march_box<STATS, kPow2Multiply>(box, fc, classified, table, ray, tmin, tmax,
                                                   fetches, near_hits);
         } else if (ONLY_MODE == kReciprocal) {
           layer = march_box<STATS, kReciprocal>(box, fc, classified, table, ray, tmin, tmax,
                                                 fetches, near_hits);
-        } else if (box.index_mode == kPow2Multiply) {  // wave-uniform
+        } else if (box.index_mode == kPow2Multiply || box.index_mode == kPow2Bricks) {  // wave-uniform
           mode = kPow2Multiply;
           layer = march_box<STATS, kPow2Multiply>(box, fc, classified, table, ray, tmin, tmax,
                                                   fetches, near_hits);
@@ -2030,7 +2066,9 @@ int launch_classify(const RenderLaunch& L, void* stream_v) {
 template <typename F>
 void with_march_variant(bool stats, int only_mode, F&& f) {
   const auto with_mode = [&](auto stats_c) {
-    if (only_mode == kPow2Multiply) {
+    if (only_mode == kPow2Bricks) {
+      f(stats_c, std::integral_constant<int, kPow2Bricks>{});
+    } else if (only_mode == kPow2Multiply) {
       f(stats_c, std::integral_constant<int, kPow2Multiply>{});
     } else if (only_mode == kReciprocal) {
       f(stats_c, std::integral_constant<int, kReciprocal>{});
@@ -2097,8 +2135,10 @@ int launch_march(const RenderLaunch& L, void* stream_v) {
     return check_launch("render_runs_max_kernel");
   }
   if (L.kind == FrameKind::kProjection) {
+    // (the raw cells are not in bricklets: kPow2Bricks is kPow2Multiply to this march)
     with_march_variant(stats, L.only_mode, [&](auto stats_c, auto only) {
-      launch(render_runs_sum_kernel<stats_c(), only()>);
+      constexpr int mode = only() == kPow2Bricks ? static_cast<int>(kPow2Multiply) : only();
+      launch(render_runs_sum_kernel<stats_c(), mode>);
     });
     return check_launch("render_runs_sum_kernel");
   }

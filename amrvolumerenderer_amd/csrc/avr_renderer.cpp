@@ -128,6 +128,7 @@ struct avr_renderer {
   avr_context* compose = nullptr;   // stream X (high priority)
   avr_context* classify = nullptr;  // stream C (default priority)
   avr_context* pair_b = nullptr;    // stream B of the paired layout (the odd frames'; high priority)
+  avr_context* last_march = nullptr;  // the one the latest frame marched on (avr_renderer_last_march_mode)
   avr_scene* scene = nullptr;
   avr_visibility_graph* visibility = nullptr;
   std::vector<avr_box> all_boxes;
@@ -878,6 +879,15 @@ int avr_renderer_corun_history(const avr_renderer* r, int16_t* candidates_out, i
   });
 }
 
+int avr_renderer_last_march_mode(const avr_renderer* r, int* only_mode_out) {
+  return guarded([&]() -> int {
+    require(r != nullptr && only_mode_out != nullptr, "null argument");
+    *only_mode_out = -2;
+    if (r->last_march == nullptr) return AVR_OK;
+    return avr_context_last_march_mode(r->last_march, only_mode_out);
+  });
+}
+
 const char* avr_renderer_failure(const avr_renderer* r) {
   return (r == nullptr || r->failed.empty()) ? nullptr : r->failed.c_str();
 }
@@ -1516,6 +1526,7 @@ void place_kernels(avr_renderer* r, Frame& f) {
     if (r->pair_b == nullptr) abi_ok(avr_context_create_with_priority(r->device, 1, &r->pair_b));
     f.march_ctx = r->pair_b;
   }
+  r->last_march = f.march_ctx;
   f.classify_ctx = f.paired ? f.march_ctx : f.overlap ? r->classify : r->march;
   // Round 1's march (8 workgroups per CU) gained from being capped at 5 beside the classify
   // pass; the present one is admitted 6 per CU by its register budget and runs best uncapped

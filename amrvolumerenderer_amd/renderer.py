@@ -315,6 +315,13 @@ class FrameRenderer:
         self.march_ctx.synchronize()
         self.comm_ctx.synchronize()
 
+    def last_march_mode(self) -> int:
+        """The index mode the latest frame's march was specialised on (Context.last_march_mode):
+        diagnostics for the parity tests."""
+        if self.native is not None:
+            return self.native.last_march_mode()
+        return self.march_ctx.last_march_mode()
+
     def render(self, p: RenderParameters, camera: CameraParameters,
                samples: Optional[torch.Tensor] = None, want_image: bool = False,
                group_order: Optional[Sequence[int]] = None):

@@ -229,6 +229,14 @@ class Context:
         _capi.check(_capi.lib().avr_context_set_march_counters(
             self._handle, C.c_void_p(counters.data_ptr()) if counters is not None else None))
 
+    def last_march_mode(self) -> int:
+        """avr_context_last_march_mode: the index mode the latest march of this context was
+        specialised on (0 power-of-two product, 1 reciprocal, 2 exact divide, 3 power-of-two product
+        with the four-instruction bricklet offset), -1 if its boxes differed, -2 before any march."""
+        mode = C.c_int(-2)
+        _capi.check(_capi.lib().avr_context_last_march_mode(self._handle, C.byref(mode)))
+        return int(mode.value)
+
     # -- helpers ----------------------------------------------------------------------------
     def _check_tensor(self, t: torch.Tensor, dtype, what: str) -> None:
         if not isinstance(t, torch.Tensor) or t.device != self.device:
@@ -1544,6 +1552,12 @@ class NativeRenderer:
         out = (C.c_int16 * max(n.value, 1))()
         _capi.check(_capi.lib().avr_renderer_corun_history(self._handle, out, n.value, C.byref(n)))
         return list(out[:n.value])
+
+    def last_march_mode(self) -> int:
+        """avr_renderer_last_march_mode: Context.last_march_mode of the latest frame's march."""
+        mode = C.c_int(-2)
+        _capi.check(_capi.lib().avr_renderer_last_march_mode(self._handle, C.byref(mode)))
+        return int(mode.value)
 
     def failure(self) -> Optional[str]:
         """avr_renderer_failure: what did not finish within the deadline, or None."""

@@ -24,11 +24,20 @@ int avr_debug_stall_stream(void *hip_stream, int milliseconds);
  *                Common/VolumePainter.cpp:846-852 because the reciprocal product lay within the
  *                proven error bound of an integer ("Exact index without the divide"),
  *   counters[1..3]  samples of boxes indexed by the exact divide throughout (degenerate spacing) /
- *                by the reciprocal product / by the power-of-two product,
+ *                by the reciprocal product / by the power-of-two product (with either bricklet
+ *                offset: modes 0 and 3 of avr_context_last_march_mode),
  *   counters[4]  non-empty pixels outside the row span of a tightened plan
  *                (avr_frame_plan_tighten): always 0.
  * Never changes results. */
 int avr_context_set_march_counters(avr_context *ctx, uint64_t *counters_dev);
+
+/* The index mode the context's latest march was specialised on: the mode every box of that launch
+ * shared (0 power-of-two product, 1 reciprocal product, 2 exact divide, 3 power-of-two product with
+ * the four-instruction bricklet offset of power-of-two bricklet counts), -1 if the boxes differed
+ * and the kernel chose per box (a box of mode 3 is then marched as mode 0), -2 before any march. */
+int avr_context_last_march_mode(const avr_context *ctx, int *only_mode_out);
+/* ... of the renderer's latest frame. */
+int avr_renderer_last_march_mode(const avr_renderer *renderer, int *only_mode_out);
 
 /* The candidate of each of the next `frames` frames of the renderer's co-run search (-1 back to
  * back, k >= 0 side by side with an LDS reserve of k * 2 KiB, 29 + k paired): the tests of the
