@@ -705,6 +705,128 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     return result
 
 
+# ---- rays ("Rays") ---------------------------------------------------------------------
+
+def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_ratio,
+              max_trips: Optional[int] = None, rank: int = 0, n_ranks: int = 1) -> dict:
+    """The leaf cells of a scene's raw field that the segments start[s] -> end[s] cross, in order
+    (DESIGN.md 7, "Rays"; yt's ds.ray).  start, end: [n, 3] in the plotfile's physical units;
+    scene, cell_sizes, prob_lo and ref_ratio as gradient_scene takes them.  max_trips bounds the
+    cells one ray walks; by default 8 + 2 sum_d (Bhi[d] - Blo[d] + 1) (r_0 ... r_(L - 2)), twice the
+    planes of the finest level across the scene's level-0 bounding box, 2^30 at the most.  Returns
+    a dict of numpy arrays: per ray offsets int64 [n + 1], status uint8 [n] (0 complete, 1 the
+    ray misses, 2 max_trips reached, 3 an end point is not finite or start == end), t_enter and
+    t_leave float64 [n] (NaN for status 1 and 3), integral and covered float64 [n] (sum value ds
+    over the leaf segments with a finite value, sum ds over the leaf segments); per segment,
+    packed by ray at offsets[s], t0, t1 float64, level int8 (-1 where no loaded leaf holds the
+    stretch) and value float64 (the leaf's raw value, NaN at level -1).  One call counts,
+    torch.cumsum gives the offsets, a second call emits.  Every box of the scene must be on this
+    rank: with n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised before
+    any device work."""
+    import numpy as np
+    import torch
+    from . import rays as ray_rules
+    local = list(scene.local_boxes)
+    if n_ranks > 1 or len(local) != len(scene.all_boxes):
+        raise NotImplementedError("rays need every box of the scene on one rank: "
+                                  "rays are not handed over between ranks")
+    first, last = ray_rules.end_points(start, end)
+    if first.shape[0] >= 2 ** 32:
+        raise ValueError("the number of rays must stay below 2^32")
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
+    if max_trips is None:
+        bounds = ray_rules.level0_bounds(index, [b.cell_dimensions for b in local],
+                                         [b.level for b in local], ratios)
+        max_trips = ray_rules.default_max_trips(bounds, ratios, len(sizes))
+    max_trips = int(max_trips)
+    if not 1 <= max_trips <= ray_rules.MAX_TRIPS:
+        raise ValueError("max_trips must lie in [1, 2^30]")
+    origin = [float(v) for v in prob_lo]
+    n = first.shape[0]
+    field = ctx.create_scene(local, scene.scalar_transform)
+    try:
+        a = torch.from_numpy(first).to(ctx.device)
+        b = torch.from_numpy(last).to(ctx.device)
+        arguments = (a, b, max_trips, index, ratios, sizes, origin)
+        counts, status, span = field.rays(*arguments)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=ctx.device)
+        torch.cumsum(counts.to(torch.int64), 0, out=offsets[1:])
+        ctx.synchronize()
+        total = int(offsets[-1].item())
+        segments = [np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.float64),
+                    np.zeros(0, dtype=np.int8), np.zeros(0, dtype=np.float64)]
+        integral, covered = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        if total > 0:
+            emitted = field.rays(*arguments, offsets=offsets, n_segments=total)
+            ctx.synchronize()
+            *segments, integral, covered = (t.cpu().numpy() for t in emitted)
+        status, span = status.cpu().numpy(), span.cpu().numpy()
+        offsets = offsets.cpu().numpy()
+    finally:
+        field.close()
+    t0, t1, level, value = segments
+    return {"offsets": offsets, "status": status, "t_enter": span[:, 0].copy(),
+            "t_leave": span[:, 1].copy(), "integral": integral, "covered": covered,
+            "t0": t0, "t1": t1, "level": level, "value": value}
+
+
+def rays(plotfile: str, start, end, fields: Sequence[str] = (), min_level: int = 0,
+         max_level: int = -1, max_trips: Optional[int] = None,
+         output: Optional[str] = None) -> dict:
+    """Line-outs of a plotfile (yt's ds.ray / LinePlot; DESIGN.md 7, "Rays"), on cuda:0: for every
+    segment start[s] -> end[s] ([n, 3] each, or a single [3] each; the plotfile's physical units)
+    the uncovered cells of the loaded levels that it crosses, in order, and the exact column
+    integral sum value ds of every field along it.  fields: stored variables or registered
+    derived, gradient or clump fields; by default the plotfile's first variable.  Returns a dict:
+    per ray n, start and end float64 [n, 3], offsets int64 [n + 1], status uint8 [n] (0 complete,
+    1 the ray misses the data's bounding box, 2 max_trips reached, 3 an end point is not finite or
+    start == end), t_enter and t_leave float64 [n] (the part of the segment inside the bounding
+    box as parameters in [0, 1]; NaN for status 1 and 3), length float64 [n] (|end - start|) and
+    covered_length float64 [n] (the length inside loaded leaves); per segment, packed by ray at
+    offsets[s], t0, t1 float64 and level int8 (-1 for a stretch no loaded leaf holds, as min_level
+    or a missing grid leaves them); per field fields {name: float64 [total]} (the leaf's raw
+    value, NaN at level -1) and integrals {name: float64 [n]} (over the segments whose value is
+    finite).  max_trips as ray_scene takes it.  With output the dict is written as one .npz file
+    (rays.save_npz)."""
+    import numpy as np
+    from . import plotfile as pf
+    from . import rays as ray_rules
+    first, last = ray_rules.end_points(start, end)
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    header = pf.PlotFileData(plotfile)
+    names = [str(name) for name in fields] or [header.var_names[0]]
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, names, min_level, max_level)
+    n_levels = len(volumes)
+    arguments = (first, last, header.cell_size[:n_levels], header.prob_lo,
+                 header.ref_ratio[:n_levels - 1], max_trips, rank, world)
+    geometry, values, integrals = None, {}, {}
+    for name, scene in zip(names, scenes):
+        found = ray_scene(ctx, scene, *arguments)
+        values[name], integrals[name] = found.pop("value"), found.pop("integral")
+        if geometry is None:
+            geometry = found
+        else:
+            # the cells crossed depend on the boxes alone, not on the field's values
+            for key, array in geometry.items():
+                if array.shape != found[key].shape or array.tobytes() != found[key].tobytes():
+                    raise RuntimeError(f"rays: field '{name}' was walked through other cells "
+                                       f"({key} differs)")
+    with np.errstate(all="ignore"):
+        d = last - first
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    result = {"n": int(first.shape[0]), "start": first, "end": last,
+              "offsets": geometry["offsets"], "status": geometry["status"],
+              "t_enter": geometry["t_enter"], "t_leave": geometry["t_leave"], "length": length,
+              "covered_length": geometry["covered"], "t0": geometry["t0"], "t1": geometry["t1"],
+              "level": geometry["level"], "fields": values, "integrals": integrals}
+    if output:
+        ray_rules.save_npz(result, output)
+    return result
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:

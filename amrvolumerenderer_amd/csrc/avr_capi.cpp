@@ -2287,6 +2287,67 @@ int avr_scene_covering_grid(avr_context* ctx, const avr_scene* field, int level,
   });
 }
 
+int avr_scene_rays(avr_context* ctx, const avr_scene* field, const double* start_dev,
+                   const double* end_dev, uint64_t n_rays, uint64_t max_trips,
+                   const int32_t* box_index_lo, const int32_t* level_ratio,
+                   const double* level_cell_size, const double* prob_lo, int n_levels,
+                   const int64_t* offsets_dev, uint64_t n_segments, uint32_t* counts_dev,
+                   uint8_t* status_dev, double* span_dev, double* t0_dev, double* t1_dev,
+                   int8_t* level_dev, double* value_dev, double* integral_dev,
+                   double* covered_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    // the scene first, without which nothing can be looked at; every other rule, a null
+    // level_cell_size or prob_lo included, is plan_rays' in its documented order
+    require(field != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    const bool emit = offsets_dev != nullptr;
+    avr::RayPlan plan = avr::plan_rays(
+        field->boxes.data(), n_boxes, n_rays, max_trips, box_index_lo, level_ratio,
+        level_cell_size, prob_lo, n_levels, start_dev, end_dev, offsets_dev,
+        emit ? n_segments : 0, counts_dev, status_dev, span_dev, t0_dev, t1_dev, level_dev,
+        value_dev, integral_dev, covered_dev);
+    if (n_rays == 0) return AVR_OK;
+    if (plan.boxes.empty()) plan.boxes.resize(1);          // never read: no block lists it
+    if (plan.block_boxes.empty()) plan.block_boxes.push_back(0);  // never read: every list is empty
+    avr::RayArgs args{};
+    ctx->staging.begin(plan.boxes.size() * sizeof(avr::CoverBoxDev) +
+                           plan.block_begin.size() * sizeof(uint32_t) +
+                           plan.block_boxes.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
+    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
+    args.levels = ctx->staging.add(&plan.levels, 1);
+    args.block_begin = ctx->staging.add(plan.block_begin.data(), plan.block_begin.size());
+    args.block_boxes = ctx->staging.add(plan.block_boxes.data(), plan.block_boxes.size());
+    ctx->staging.commit(ctx->stream);
+    args.locator = plan.locator;
+    for (int d = 0; d < 3; ++d) {
+      args.bound_lo[d] = plan.bound_lo[d];
+      args.bound_hi[d] = plan.bound_hi[d];
+    }
+    args.n_levels = n_levels;
+    args.n_rays = static_cast<uint32_t>(n_rays);
+    args.max_trips = static_cast<uint32_t>(max_trips);
+    args.start = start_dev;
+    args.end = end_dev;
+    if (emit) {
+      args.offsets = reinterpret_cast<const long long*>(offsets_dev);
+      args.n_segments = n_segments;
+      args.t0 = t0_dev;
+      args.t1 = t1_dev;
+      args.level = level_dev;
+      args.value = value_dev;
+      args.integral = integral_dev;
+      args.covered = covered_dev;
+    } else {
+      args.counts = counts_dev;
+      args.status = status_dev;
+      args.span = span_dev;
+    }
+    return avr::launch_rays(args, emit, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

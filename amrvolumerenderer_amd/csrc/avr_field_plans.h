@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids): everything a
-// call works out from its arguments before
+// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids, rays):
+// everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
 // rules it applies: a plan works on arrays of avr_box and the ABI's plain arguments, throws
@@ -823,6 +823,93 @@ inline void size_stream_locator(const int64_t lo[3], const int64_t hi[3], int64_
     return;
   }
 }
+// The locator of the streamlines and the rays (StreamLocatorDev): every box mapped to level 0, the
+// blocks over their bounding box, the lists -- CSR over the blocks ({0} for a scene without cells),
+// per block the boxes of any level whose cells, mapped to level 0, meet it, finest level first,
+// then in scene order.  Returns whether the scene has cells, and with them *bound (may be null),
+// the level-0 index bounding box the blocks cover.  Box: a device box with nx (0 without cells) and
+// level; ratio[l]: level l -> l + 1; max_entries: the bound on the lists.
+template <class Box>
+inline bool build_level_locator(const std::vector<Box>& boxes,
+                                const std::vector<IndexRegion>& regions, const int32_t* ratio,
+                                int64_t max_entries, StreamLocatorDev* locator_out,
+                                std::vector<uint32_t>* block_begin,
+                                std::vector<int32_t>* block_boxes, IndexRegion* bound = nullptr) {
+  std::memset(locator_out, 0, sizeof(*locator_out));
+  block_begin->assign(1, 0u);
+  block_boxes->clear();
+  const size_t n_boxes = boxes.size();
+  std::vector<IndexRegion> coarse(n_boxes);  // [b]: box b at level 0
+  std::vector<size_t> order;                 // the boxes with cells, finest level first
+  int64_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (boxes[b].nx <= 0) continue;
+    coarse[b] = regions[b];
+    for (int m = boxes[b].level; m > 0; --m) {
+      for (int d = 0; d < 3; ++d) {
+        coarse[b].lo[d] = floor_div(coarse[b].lo[d], ratio[m - 1]);
+        coarse[b].hi[d] = floor_div(coarse[b].hi[d], ratio[m - 1]);
+      }
+    }
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = order.empty() ? coarse[b].lo[d] : std::min(lo[d], coarse[b].lo[d]);
+      hi[d] = order.empty() ? coarse[b].hi[d] : std::max(hi[d], coarse[b].hi[d]);
+    }
+    order.push_back(b);
+  }
+  if (order.empty()) return false;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](size_t x, size_t y) { return boxes[x].level > boxes[y].level; });
+  // a few blocks per box keep the lists short; 2^24 blocks at the most
+  const int64_t limit = std::min(kStreamMaxBlocks, 64 + 8 * static_cast<int64_t>(order.size()));
+  size_stream_locator(lo, hi, limit, locator_out);
+  const StreamLocatorDev& locator = *locator_out;
+  const size_t blocks = static_cast<size_t>(locator.n[0]) * locator.n[1] * locator.n[2];
+  auto block_range = [&](size_t b, int64_t first[3], int64_t last[3]) {
+    for (int d = 0; d < 3; ++d) {
+      first[d] = (coarse[b].lo[d] - lo[d]) >> locator.shift;
+      last[d] = (coarse[b].hi[d] - lo[d]) >> locator.shift;
+    }
+  };
+  // the lists' size from the boxes' extents, before anything of that size is made
+  uint64_t entries = 0;
+  for (size_t b : order) {
+    int64_t first[3], last[3];
+    block_range(b, first, last);
+    entries += static_cast<uint64_t>(last[0] - first[0] + 1) *
+               static_cast<uint64_t>(last[1] - first[1] + 1) *
+               static_cast<uint64_t>(last[2] - first[2] + 1);  // at most 2^24 each
+    require_box(entries < static_cast<uint64_t>(max_entries),
+                "the locator's lists hold 2^28 entries or more");
+  }
+  auto for_blocks = [&](size_t b, auto&& visit) {
+    int64_t first[3], last[3];
+    block_range(b, first, last);
+    for (int64_t z = first[2]; z <= last[2]; ++z) {
+      for (int64_t y = first[1]; y <= last[1]; ++y) {
+        for (int64_t x = first[0]; x <= last[0]; ++x) {
+          visit(static_cast<size_t>((z * locator.n[1] + y) * locator.n[0] + x));
+        }
+      }
+    }
+  };
+  std::vector<uint32_t> fill(blocks + 1, 0u);
+  for (size_t b : order) for_blocks(b, [&](size_t block) { ++fill[block + 1]; });
+  for (size_t block = 0; block < blocks; ++block) fill[block + 1] += fill[block];
+  block_begin->assign(fill.begin(), fill.end());
+  block_boxes->resize(static_cast<size_t>(fill[blocks]));
+  for (size_t b : order) {
+    for_blocks(b, [&](size_t block) { (*block_boxes)[fill[block]++] = static_cast<int32_t>(b); });
+  }
+  if (bound != nullptr) {
+    for (int d = 0; d < 3; ++d) {
+      bound->lo[d] = lo[d];
+      bound->hi[d] = hi[d];
+    }
+  }
+  return true;
+}
+
 // vx, vy, vz: the boxes of the three components; sample (may be null): those of the sample field.
 // box_index_lo, level_ratio, level_cell_size and prob_lo as plan_isosurface takes them.  seeds,
 // points, samples, counts and status are device arrays of n_seeds lines of max_steps + 1 points
@@ -894,71 +981,8 @@ inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const a
     require_no_shared_byte(&read_ranges, write_ranges,
                            "an output array or the seeds overlap an input box's cells");
   }
-  // the locator: every box mapped to level 0, the blocks over their bounding box, the lists
-  std::memset(&plan.locator, 0, sizeof(plan.locator));
-  plan.block_begin.assign(1, 0u);
-  std::vector<IndexRegion> coarse(n_boxes);  // [b]: box b at level 0
-  std::vector<size_t> order;                 // the boxes with cells, finest level first
-  int64_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  for (size_t b = 0; b < n_boxes; ++b) {
-    if (boxes[b].nx <= 0) continue;
-    coarse[b] = regions[b];
-    for (int m = boxes[b].level; m > 0; --m) {
-      for (int d = 0; d < 3; ++d) {
-        coarse[b].lo[d] = floor_div(coarse[b].lo[d], levels.ratio[m - 1]);
-        coarse[b].hi[d] = floor_div(coarse[b].hi[d], levels.ratio[m - 1]);
-      }
-    }
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = order.empty() ? coarse[b].lo[d] : std::min(lo[d], coarse[b].lo[d]);
-      hi[d] = order.empty() ? coarse[b].hi[d] : std::max(hi[d], coarse[b].hi[d]);
-    }
-    order.push_back(b);
-  }
-  if (order.empty()) return plan;
-  std::stable_sort(order.begin(), order.end(),
-                   [&](size_t x, size_t y) { return boxes[x].level > boxes[y].level; });
-  // a few blocks per box keep the lists short; 2^24 blocks at the most
-  const int64_t limit = std::min(kStreamMaxBlocks, 64 + 8 * static_cast<int64_t>(order.size()));
-  size_stream_locator(lo, hi, limit, &plan.locator);
-  const StreamLocatorDev& locator = plan.locator;
-  const size_t blocks = static_cast<size_t>(locator.n[0]) * locator.n[1] * locator.n[2];
-  auto block_range = [&](size_t b, int64_t first[3], int64_t last[3]) {
-    for (int d = 0; d < 3; ++d) {
-      first[d] = (coarse[b].lo[d] - lo[d]) >> locator.shift;
-      last[d] = (coarse[b].hi[d] - lo[d]) >> locator.shift;
-    }
-  };
-  // the lists' size from the boxes' extents, before anything of that size is made
-  uint64_t entries = 0;
-  for (size_t b : order) {
-    int64_t first[3], last[3];
-    block_range(b, first, last);
-    entries += static_cast<uint64_t>(last[0] - first[0] + 1) *
-               static_cast<uint64_t>(last[1] - first[1] + 1) *
-               static_cast<uint64_t>(last[2] - first[2] + 1);  // at most 2^24 each
-    require_box(entries < static_cast<uint64_t>(max_entries),
-                "the locator's lists hold 2^28 entries or more");
-  }
-  auto for_blocks = [&](size_t b, auto&& visit) {
-    int64_t first[3], last[3];
-    block_range(b, first, last);
-    for (int64_t z = first[2]; z <= last[2]; ++z) {
-      for (int64_t y = first[1]; y <= last[1]; ++y) {
-        for (int64_t x = first[0]; x <= last[0]; ++x) {
-          visit(static_cast<size_t>((z * locator.n[1] + y) * locator.n[0] + x));
-        }
-      }
-    }
-  };
-  std::vector<uint32_t> fill(blocks + 1, 0u);
-  for (size_t b : order) for_blocks(b, [&](size_t block) { ++fill[block + 1]; });
-  for (size_t block = 0; block < blocks; ++block) fill[block + 1] += fill[block];
-  plan.block_begin.assign(fill.begin(), fill.end());
-  plan.block_boxes.resize(static_cast<size_t>(fill[blocks]));
-  for (size_t b : order) {
-    for_blocks(b, [&](size_t block) { plan.block_boxes[fill[block]++] = static_cast<int32_t>(b); });
-  }
+  build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator, &plan.block_begin,
+                      &plan.block_boxes);
   return plan;
 }
 
@@ -1137,6 +1161,120 @@ inline CoveringGridPlan plan_covering_grid(const avr_box* field, size_t n_boxes,
   }
   tile_candidate_lists(boxes, regions, levels.ratio, level, output, &plan.candidate_begin,
                        &plan.candidates);
+  return plan;
+}
+
+// ---- rays -----------------------------------------------------------------------------------
+struct RayPlan {
+  std::vector<CoverBoxDev> boxes;
+  IsoLevelsDev levels;
+  // the streamlines' locator (build_level_locator) and the level-0 box [Blo, Bhi] it covers
+  StreamLocatorDev locator;
+  std::vector<uint32_t> block_begin;  // blocks + 1 ({0} for a scene without cells)
+  std::vector<int32_t> block_boxes;
+  int32_t bound_lo[3] = {0, 0, 0}, bound_hi[3] = {-1, -1, -1};
+};
+// The leaf cells that n_rays segments start[s] -> end[s] cross ("Rays").  box_index_lo,
+// level_ratio, level_cell_size and prob_lo as plan_isosurface takes them.  start, end: device
+// arrays f64 [n_rays][3].  The count pass (offsets == nullptr) writes counts u32 [n_rays], status
+// u8 [n_rays] and span f64 [n_rays][2]; the emit pass reads offsets i64 [n_rays + 1] and writes
+// t0, t1, value f64 [n_segments], level i8 [n_segments] (free to be null with n_segments == 0),
+// integral and covered f64 [n_rays]; the arrays of the other pass are not looked at.  All of them
+// are free to be null with n_rays == 0.  The rules, in this order: max_trips, n_rays, n_segments,
+// n_levels, null arrays (the hierarchy's, level_cell_size and prob_lo among them, then the rays'
+// and the outputs'), the cell sizes, prob_lo, the box rules, the ratios, the index ranges,
+// boxes of one level apart in index space, no output byte and no byte of start, end or offsets
+// shared with an input, the locator's size (max_entries: the bound on its lists, lowered by the
+// plan's test only), the bounding box refined to the finest level inside [-2^30, 2^30].
+inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, uint64_t max_trips,
+                         const int32_t* box_index_lo, const int32_t* level_ratio,
+                         const double* level_cell_size, const double* prob_lo, int n_levels,
+                         const void* start, const void* end, const void* offsets,
+                         uint64_t n_segments, const void* counts, const void* status,
+                         const void* span, const void* t0, const void* t1, const void* level,
+                         const void* value, const void* integral, const void* covered,
+                         int64_t max_entries = kStreamMaxEntries) {
+  require_box(max_trips >= 1 && max_trips <= kRayMaxTrips, "max_trips must lie in [1, 2^30]");
+  require_box(n_rays < (uint64_t{1} << 32), "n_rays must stay below 2^32");
+  require_box(n_segments <= kRayMaxSegments, "n_segments must not exceed 2^40");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(level_cell_size != nullptr && prob_lo != nullptr, "null argument");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  const bool emit = offsets != nullptr;
+  if (n_rays > 0) {
+    require_box(start != nullptr && end != nullptr, "null argument");
+    if (emit) {
+      require_box(integral != nullptr && covered != nullptr, "null argument");
+      require_box(n_segments == 0 || (t0 != nullptr && t1 != nullptr && level != nullptr &&
+                                      value != nullptr), "null argument");
+    } else {
+      require_box(counts != nullptr && status != nullptr && span != nullptr, "null argument");
+    }
+  }
+  RayPlan plan;
+  IsoLevelsDev& levels = plan.levels;
+  fill_level_geometry(level_cell_size, prob_lo, n_levels, &levels);
+  std::vector<CoverBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = field[b];
+    const avr_box* fields[1] = {&first};
+    FieldView view;
+    CoverBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool cells = field_box_views(first, fields, 1, n_levels, &view, &paired);
+    dev.cells = view.cells;
+    dev.jstride = view.jstride;
+    dev.kstride = view.kstride;
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&read_ranges, view);
+    }
+  }
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, field, &boxes);
+  require_levels_disjoint(boxes, regions);
+  if (n_rays > 0) {
+    append_byte_range(&write_ranges, start, n_rays * 3 * sizeof(double));
+    append_byte_range(&write_ranges, end, n_rays * 3 * sizeof(double));
+    if (emit) {
+      append_byte_range(&write_ranges, offsets, (n_rays + 1) * sizeof(int64_t));
+      if (n_segments > 0) {
+        append_byte_range(&write_ranges, t0, n_segments * sizeof(double));
+        append_byte_range(&write_ranges, t1, n_segments * sizeof(double));
+        append_byte_range(&write_ranges, level, n_segments);
+        append_byte_range(&write_ranges, value, n_segments * sizeof(double));
+      }
+      append_byte_range(&write_ranges, integral, n_rays * sizeof(double));
+      append_byte_range(&write_ranges, covered, n_rays * sizeof(double));
+    } else {
+      append_byte_range(&write_ranges, counts, n_rays * sizeof(uint32_t));
+      append_byte_range(&write_ranges, status, n_rays);
+      append_byte_range(&write_ranges, span, n_rays * 2 * sizeof(double));
+    }
+    require_no_shared_byte(&read_ranges, write_ranges,
+                           "an output array or the rays overlap an input box's cells");
+  }
+  IndexRegion bound;
+  if (!build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator,
+                           &plan.block_begin, &plan.block_boxes, &bound)) {
+    return plan;
+  }
+  // an absent cell has the finest level's geometry wherever it lies in [Blo, Bhi]: the kernel's
+  // 32-bit indices, one step past a cell included, and f64(index) stay exact
+  const int64_t limit = int64_t{1} << 30, up = level_factor(levels.ratio, 0, n_levels - 1);
+  for (int d = 0; d < 3; ++d) {
+    require_box(bound.lo[d] * up >= -limit && (bound.hi[d] + 1) * up <= limit,
+                "the scene's bounding box leaves [-2^30, 2^30] at the finest level");
+    plan.bound_lo[d] = static_cast<int32_t>(bound.lo[d]);
+    plan.bound_hi[d] = static_cast<int32_t>(bound.hi[d]);
+  }
   return plan;
 }
 

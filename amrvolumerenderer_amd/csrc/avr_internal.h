@@ -814,6 +814,40 @@ struct CoverArgs {
 };
 int launch_covering_grid(const CoverArgs& args, void* stream);
 
+// Rays (avr_rays.hip): the leaf cells a segment A -> B crosses, in order, one lane per ray.  A box
+// as the kernel reads it is a CoverBoxDev; the locator is the streamlines'.
+constexpr uint64_t kRayMaxTrips = uint64_t{1} << 30;
+constexpr uint64_t kRayMaxSegments = uint64_t{1} << 40;  // the packed arrays' capacity
+constexpr uint8_t kRayComplete = 0, kRayMiss = 1, kRayTruncated = 2, kRayInvalid = 3;
+struct RayArgs {
+  const CoverBoxDev* boxes;
+  const uint32_t* block_begin;  // blocks + 1
+  const int32_t* block_boxes;
+  const IsoLevelsDev* levels;   // cell sizes, prob_lo and ratios as the isosurfaces stage them
+  StreamLocatorDev locator;
+  int32_t bound_lo[3];          // [Blo, Bhi]: the boxes mapped to level 0 (the locator's box);
+  int32_t bound_hi[3];          // refined to level n_levels - 1 it lies inside [-2^30, 2^30]
+  int32_t n_levels;
+  uint32_t n_rays;
+  uint32_t max_trips;           // 1 .. 2^30
+  const double* start;          // [n_rays][3]
+  const double* end;            // [n_rays][3]
+  // the count pass
+  uint32_t* counts;             // [n_rays]
+  uint8_t* status;              // [n_rays]
+  double* span;                 // [n_rays][2]: t_enter, t_leave
+  // the emit pass: ray s owns the slots [offsets[s], offsets[s + 1]) below n_segments
+  const long long* offsets;     // [n_rays + 1]
+  uint64_t n_segments;
+  double* t0;                   // [n_segments]
+  double* t1;                   // [n_segments]
+  int8_t* level;                // [n_segments]
+  double* value;                // [n_segments]
+  double* integral;             // [n_rays]
+  double* covered;              // [n_rays]
+};
+int launch_rays(const RayArgs& args, bool emit, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

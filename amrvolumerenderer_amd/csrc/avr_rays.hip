@@ -1,0 +1,295 @@
+// Rays ("Rays"): the leaf cells that a segment A -> B crosses, in order, with the
+// entry and exit parameters, the level and the raw value of each, and the exact column integral
+// sum value * ds that comes with them.
+//
+//   rays_kernel<EMIT>    one lane per ray; EMIT: the segments and the sums are written
+//
+// Two passes over the identical walk: the count pass writes every ray's count, status and clipped
+// span, the host takes the exclusive scan, and the emit pass writes ray s's segments into the
+// slots [offsets[s], offsets[s + 1]) that it owns -- never past that range nor past n_segments,
+// whatever the offsets hold -- and the two sums.  A lane keeps its cell (the geometry level l and
+// the index G), steps through the face the ray leaves it by and finds the next cell through the
+// streamlines' locator: the list of the block that holds G mapped to level 0, finest level first,
+// walked once, with the candidate index of a level worked out when the walk reaches a box of it.
+// Only cells of the scene's boxes are ever read.  Workgroups are one wave, so a wave's slot comes
+// back when its own last ray is done; the segment stores are scattered, each lane to its own
+// packed range.
+//
+// Every loop is bounded by a count known at launch: max_trips, the levels, a block's list.  No
+// atomics: equal arguments give equal bits.  Arithmetic is IEEE binary64, round to nearest,
+// nothing fused (-ffp-contract=off); / and sqrt are the correctly rounded __ddiv_rn and
+// __dsqrt_rn.  A maximum or minimum is written as the comparison the definition names.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "avr_internal.h"
+
+namespace avr {
+
+namespace {
+
+constexpr int kThreads = 64;  // one wave: its slot is free again when its own last ray has ended
+
+__device__ __forceinline__ int floor_div(int a, int r) {
+  const int q = a / r;
+  return (a % r != 0 && a < 0) ? q - 1 : q;
+}
+
+// floor(q) within [lo, hi]; lo for a q that is not finite.
+__device__ __forceinline__ int clamped_floor(double q, int lo, int hi) {
+  if (!__builtin_isfinite(q)) return lo;
+  const double f = floor(q);
+  if (f < static_cast<double>(lo)) return lo;
+  if (f > static_cast<double>(hi)) return hi;
+  return static_cast<int>(f);
+}
+
+// T(l, d, g): the parameter at which the ray meets the plane of index g of level l along axis d.
+__device__ __forceinline__ double plane_t(const IsoLevelsDev& levels, int l, int d, int g, double a,
+                                          double dir) {
+  const double x = levels.prob_lo[d] + static_cast<double>(g) * levels.cell_size[l][d];
+  return __ddiv_rn(x - a, dir);
+}
+
+// The cell a trip crosses: its geometry (l, g), the recorded level (-1: absent) and its value's
+// address (null: absent).
+struct RayCell {
+  int l, level;
+  int g[3];
+  const double* at;
+};
+
+// The candidate of level m for the level-c index g taken to hold p: below c the index mapped down,
+// above c the point's index clamped to the children of g.
+__device__ __forceinline__ void candidate(const IsoLevelsDev& levels, int c, const int g[3],
+                                          const double p[3], int m, int out[3]) {
+  if (m <= c) {
+    out[0] = g[0];
+    out[1] = g[1];
+    out[2] = g[2];
+    for (int k = c; k > m; --k) {
+      const int r = levels.ratio[k - 1];
+      out[0] = floor_div(out[0], r);
+      out[1] = floor_div(out[1], r);
+      out[2] = floor_div(out[2], r);
+    }
+    return;
+  }
+  int refine = 1;  // r_c ... r_(m - 1): at most 2^30, and g's children stay inside [-2^30, 2^30)
+  for (int k = c; k < m; ++k) refine *= levels.ratio[k];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const double q = __ddiv_rn(p[d] - levels.prob_lo[d], levels.cell_size[m][d]);
+    const int first = g[d] * refine;
+    out[d] = clamped_floor(q, first, first + (refine - 1));
+  }
+}
+
+// Locate(c, g, p); z: g mapped to level 0, inside [bound_lo, bound_hi].
+__device__ __forceinline__ RayCell locate(const RayArgs& a, const IsoLevelsDev& levels, int c,
+                                          const int g[3], const int z[3], const double p[3]) {
+  RayCell cell;
+  const StreamLocatorDev& locator = a.locator;
+  const uint32_t bx = (static_cast<uint32_t>(z[0]) - static_cast<uint32_t>(locator.origin[0])) >> locator.shift;
+  const uint32_t by = (static_cast<uint32_t>(z[1]) - static_cast<uint32_t>(locator.origin[1])) >> locator.shift;
+  const uint32_t bz = (static_cast<uint32_t>(z[2]) - static_cast<uint32_t>(locator.origin[2])) >> locator.shift;
+  const uint32_t n0 = static_cast<uint32_t>(locator.n[0]), n1 = static_cast<uint32_t>(locator.n[1]);
+  uint32_t first = 0, last = 0;
+  if (bx < n0 && by < n1 && bz < static_cast<uint32_t>(locator.n[2])) {
+    const uint32_t block = (bz * n1 + by) * n0 + bx;
+    first = a.block_begin[block];
+    last = a.block_begin[block + 1];
+  }
+  int at = -1;  // the level cell.g is the candidate of
+  for (uint32_t e = first; e < last; ++e) {
+    const int b = a.block_boxes[e];
+    const CoverBoxDev& box = a.boxes[b];
+    const int m = box.level;
+    if (m != at) {
+      candidate(levels, c, g, p, m, cell.g);
+      at = m;
+    }
+    // the unsigned difference also refuses an index below the box's first
+    const uint32_t i = static_cast<uint32_t>(cell.g[0]) - static_cast<uint32_t>(box.lo[0]);
+    const uint32_t j = static_cast<uint32_t>(cell.g[1]) - static_cast<uint32_t>(box.lo[1]);
+    const uint32_t k = static_cast<uint32_t>(cell.g[2]) - static_cast<uint32_t>(box.lo[2]);
+    if (i < static_cast<uint32_t>(box.nx) && j < static_cast<uint32_t>(box.ny) &&
+        k < static_cast<uint32_t>(box.nz)) {
+      cell.l = cell.level = m;
+      cell.at = box.cells + (i + j * static_cast<uint32_t>(box.jstride) +
+                             k * static_cast<uint32_t>(box.kstride));
+      return cell;
+    }
+  }
+  // absent: the finest level's geometry
+  const int finest = a.n_levels - 1;
+  if (at != finest) candidate(levels, c, g, p, finest, cell.g);
+  cell.l = finest;
+  cell.level = -1;
+  cell.at = nullptr;
+  return cell;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
+  const uint32_t ray = blockIdx.x * kThreads + threadIdx.x;
+  if (ray >= a.n_rays) return;
+  const IsoLevelsDev& levels = *a.levels;
+  double A[3], D[3];
+  bool finite = true, still = true;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    A[d] = a.start[ray * 3ull + d];
+    const double b = a.end[ray * 3ull + d];
+    finite = finite && __builtin_isfinite(A[d]) && __builtin_isfinite(b);
+    D[d] = b - A[d];
+    still = still && D[d] == 0.0;
+  }
+  const double nan = __builtin_nan("");
+  uint32_t count = 0, status = kRayTruncated;
+  double t_enter = 0.0, t_leave = 1.0;
+  // the emit pass: the slots [slot, slot_end) are the ray's own
+  unsigned long long slot = 0, slot_end = 0;
+  double integral = 0.0, covered = 0.0, length = 0.0;
+  if (EMIT) {
+    const long long begin = a.offsets[ray], end = a.offsets[ray + 1ull];
+    if (begin >= 0 && begin <= end && static_cast<unsigned long long>(end) <= a.n_segments) {
+      slot = static_cast<unsigned long long>(begin);
+      slot_end = static_cast<unsigned long long>(end);
+    }
+    length = __dsqrt_rn((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
+  }
+  if (!finite || still) {
+    status = kRayInvalid;
+  } else if (a.locator.n[0] == 0) {
+    status = kRayMiss;  // a scene without cells
+  } else {
+    // the clip against the level-0 box
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int lo = a.bound_lo[d], hi = a.bound_hi[d] + 1;
+      if (D[d] == 0.0) {
+        const double x_lo = levels.prob_lo[d] + static_cast<double>(lo) * levels.cell_size[0][d];
+        const double x_hi = levels.prob_lo[d] + static_cast<double>(hi) * levels.cell_size[0][d];
+        if (!(x_lo <= A[d] && A[d] < x_hi)) status = kRayMiss;
+      } else {
+        const double t_near = plane_t(levels, 0, d, D[d] > 0.0 ? lo : hi, A[d], D[d]);
+        const double t_far = plane_t(levels, 0, d, D[d] > 0.0 ? hi : lo, A[d], D[d]);
+        t_enter = t_near > t_enter ? t_near : t_enter;
+        t_leave = t_far < t_leave ? t_far : t_leave;
+      }
+    }
+    if (!(t_enter < t_leave)) status = kRayMiss;
+  }
+  if (status == kRayTruncated) {
+    // the walk
+    double t_cur = t_enter;
+    double p[3];
+    int c = 0, g[3], z[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      p[d] = A[d] + t_cur * D[d];
+      const double q = __ddiv_rn(p[d] - levels.prob_lo[d], levels.cell_size[0][d]);
+      g[d] = z[d] = clamped_floor(q, a.bound_lo[d], a.bound_hi[d]);
+    }
+    for (uint32_t trip = 0; trip < a.max_trips; ++trip) {
+      const RayCell cell = locate(a, levels, c, g, z, p);
+      double t_out = 0.0;
+      int exit_axis = -1;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        if (D[d] != 0.0) {
+          const double t = plane_t(levels, cell.l, d, D[d] > 0.0 ? cell.g[d] + 1 : cell.g[d], A[d],
+                                   D[d]);
+          if (exit_axis < 0 || t < t_out) {
+            t_out = t;
+            exit_axis = d;
+          }
+        }
+      }
+      const double ahead = t_out > t_cur ? t_out : t_cur;
+      const double t_next = ahead < t_leave ? ahead : t_leave;
+      if (t_next > t_cur) {
+        if (EMIT) {
+          const unsigned long long at = slot + count;
+          if (at < slot_end) {
+            const double v = cell.at != nullptr ? *cell.at : nan;
+            a.t0[at] = t_cur;
+            a.t1[at] = t_next;
+            a.level[at] = static_cast<int8_t>(cell.level);
+            a.value[at] = v;
+            if (cell.at != nullptr) {
+              const double w = (t_next - t_cur) * length;
+              covered = covered + w;
+              if (__builtin_isfinite(v)) integral = integral + v * w;
+            }
+          }
+        }
+        ++count;
+      }
+      if (!(t_out < t_leave)) {
+        status = kRayComplete;
+        break;
+      }
+      // through the exit face; a step out of the level-0 box happens by rounding only
+      c = cell.l;
+      g[0] = cell.g[0];
+      g[1] = cell.g[1];
+      g[2] = cell.g[2];
+      const double along = exit_axis == 0 ? D[0] : (exit_axis == 1 ? D[1] : D[2]);
+      const int step = along > 0.0 ? 1 : -1;
+      if (exit_axis == 0) g[0] += step;
+      if (exit_axis == 1) g[1] += step;
+      if (exit_axis == 2) g[2] += step;
+      z[0] = g[0];
+      z[1] = g[1];
+      z[2] = g[2];
+      for (int m = c; m > 0; --m) {
+        const int r = levels.ratio[m - 1];
+        z[0] = floor_div(z[0], r);
+        z[1] = floor_div(z[1], r);
+        z[2] = floor_div(z[2], r);
+      }
+      if (z[0] < a.bound_lo[0] || z[0] > a.bound_hi[0] || z[1] < a.bound_lo[1] ||
+          z[1] > a.bound_hi[1] || z[2] < a.bound_lo[2] || z[2] > a.bound_hi[2]) {
+        status = kRayComplete;
+        break;
+      }
+#pragma unroll
+      for (int d = 0; d < 3; ++d) p[d] = A[d] + t_next * D[d];
+      t_cur = t_next;
+    }
+  }
+  if (EMIT) {
+    a.integral[ray] = integral;
+    a.covered[ray] = covered;
+  } else {
+    const bool walked = status == kRayComplete || status == kRayTruncated;
+    a.counts[ray] = count;
+    a.status[ray] = static_cast<uint8_t>(status);
+    a.span[ray * 2ull + 0] = walked ? t_enter : nan;
+    a.span[ray * 2ull + 1] = walked ? t_leave : nan;
+  }
+}
+
+}  // namespace
+
+int launch_rays(const RayArgs& args, bool emit, void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (args.n_rays == 0) return AVR_OK;
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(args.n_rays) + kThreads - 1) / kThreads));
+  if (emit) {
+    hipLaunchKernelGGL(rays_kernel<true>, grid, dim3(kThreads), 0, stream, args);
+  } else {
+    hipLaunchKernelGGL(rays_kernel<false>, grid, dim3(kThreads), 0, stream, args);
+  }
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    set_error(std::string("rays kernel: ") + hipGetErrorString(err));
+    return AVR_ERR_RUNTIME;
+  }
+  return AVR_OK;
+}
+
+}  // namespace avr

@@ -946,6 +946,83 @@ class Scene:
         ctx.publish()
         return points, samples, counts, status
 
+    def rays(self, start, end, max_trips: int, box_index_lo, level_ratio, level_cell_size,
+             prob_lo, offsets: Optional[torch.Tensor] = None, n_segments: int = 0):
+        """avr_scene_rays with this scene as the field: the leaf cells that the segments start[s]
+        -> end[s] cross (float64 [n, 3] in physical units; tensors on the device, or anything
+        numpy takes).  max_trips in [1, 2^30]; box_index_lo: [n_boxes, 3] int32; level_ratio:
+        n_levels - 1 ints; level_cell_size: [n_levels, 3] float64; prob_lo: three values.
+        Without offsets it is the count pass and returns (counts int32 [n], status uint8 [n]: 0
+        complete, 1 miss, 2 max_trips reached, 3 invalid, span float64 [n, 2]: t_enter and
+        t_leave, NaN for status 1 and 3).  With offsets (int64 [n + 1] on the device: the
+        exclusive scan of the counts and their total) and n_segments (that total) it is the emit
+        pass and returns (t0, t1 float64 [n_segments], level int8 [n_segments], value float64
+        [n_segments], integral, covered float64 [n]).  Everything is on the device;
+        asynchronous on the context's stream."""
+        ctx = self.ctx
+        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        max_trips, n_segments = int(max_trips), int(n_segments)
+        if index.shape != (len(self.boxes), 3):
+            raise ValueError("box_index_lo must hold three values per box")
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
+            raise ValueError("level_ratio must hold one value per level transition")
+        if origin.shape != (3,):
+            raise ValueError("prob_lo must hold three values")
+        if not 1 <= max_trips <= 2 ** 30:
+            raise ValueError("max_trips must lie in [1, 2^30]")
+        if n_segments < 0:
+            raise ValueError("n_segments must not be negative")
+        ends = []
+        for points in (start, end):
+            if not isinstance(points, torch.Tensor):
+                points = torch.from_numpy(
+                    np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3))
+            points = points.to(device=ctx.device, dtype=torch.float64).contiguous()
+            if points.ndim != 2 or points.shape[1] != 3:
+                raise ValueError("start and end must hold three values per ray")
+            ends.append(points)
+        if ends[0].shape != ends[1].shape:
+            raise ValueError("start and end must hold the same number of rays")
+        n = int(ends[0].shape[0])
+        emit = offsets is not None
+        if emit:
+            ctx._check_tensor(offsets, torch.int64, "offsets")
+            if offsets.numel() != n + 1:
+                raise ValueError("offsets must hold n + 1 values")
+            t0 = torch.empty(n_segments, dtype=torch.float64, device=ctx.device)
+            t1 = torch.empty(n_segments, dtype=torch.float64, device=ctx.device)
+            level = torch.empty(n_segments, dtype=torch.int8, device=ctx.device)
+            value = torch.empty(n_segments, dtype=torch.float64, device=ctx.device)
+            integral = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+            covered = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+            counts = status = span = None
+            result = (t0, t1, level, value, integral, covered)
+        else:
+            counts = torch.zeros(n, dtype=torch.int32, device=ctx.device)
+            status = torch.full((n,), 3, dtype=torch.uint8, device=ctx.device)
+            span = torch.full((n, 2), math.nan, dtype=torch.float64, device=ctx.device)
+            t0 = t1 = level = value = integral = covered = None
+            result = (counts, status, span)
+        if n == 0:                     # nothing to launch, and empty tensors have no address
+            return result
+        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ctx.join()
+        _capi.check(_capi.lib().avr_scene_rays(
+            ctx._handle, self._handle, pointer(ends[0]), pointer(ends[1]), n, max_trips,
+            index.ctypes.data_as(C.POINTER(C.c_int32)),
+            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
+            int(sizes.shape[0]), pointer(offsets), n_segments, pointer(counts), pointer(status),
+            pointer(span), pointer(t0), pointer(t1), pointer(level), pointer(value),
+            pointer(integral), pointer(covered)))
+        ctx.publish()
+        return result
+
     def covering_grid(self, level: int, lo, dims, box_index_lo, level_ratio,
                       fill: float = math.nan, with_coverage: bool = True):
         """avr_scene_covering_grid with this scene as the field: the field resampled to the cells

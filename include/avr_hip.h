@@ -1352,6 +1352,49 @@ int avr_scene_covering_grid(avr_context *ctx, const avr_scene *field, int level,
                             const int32_t *level_ratio, int n_levels, double fill,
                             double *values_dev, double *coverage_dev, int8_t *level_dev);
 
+/* ---- rays ("Rays") -------------------------------------------------------------------- */
+
+/* Line-outs: for each of n_rays segments A -> B (start_dev, end_dev: device, f64 [n][3], physical
+ * units) every leaf cell of `field` (a scene of ctx; raw f64 cells, no transform) that the segment
+ * crosses, in order, as (t0, t1, level, value) with P(t) = A + t (B - A), and the sums
+ * integral = sum value * (t1 - t0) |B - A| over the leaf segments with a finite value and covered =
+ * sum (t1 - t0) |B - A| over the leaf segments.  The definition -- the clip against the scene's
+ * level-0 index bounding box, Locate, the walk from face to face, absent stretches walked at the
+ * finest cell size as level -1 with a NaN value -- is DESIGN.md 7, "Rays"; IEEE binary64 with
+ * nothing fused, / and sqrt correctly rounded.  The hierarchy description (box_index_lo,
+ * level_ratio, n_levels <= 16; host) is avr_scene_gradient's; level_cell_size holds (dx, dy, dz) per
+ * level, prob_lo three values (host).
+ * Two passes.  offsets_dev == NULL is the count pass: counts_dev (device, u32 [n]) gets the number
+ * of segments of every ray, status_dev (u8 [n]) 0 complete, 1 the ray misses the scene's box, 2
+ * max_trips trips were made (the segments found so far are kept), 3 an end point is not finite or
+ * A == B, and span_dev (f64 [n][2]) t_enter and t_leave of the clip, NaN for status 1 and 3; the
+ * other output arrays are not looked at.  With offsets_dev (device, i64 [n + 1], the exclusive
+ * scan of the counts and their total) it is the emit pass: the identical walk writes ray s's
+ * segments to t0_dev, t1_dev, value_dev (f64) and level_dev (i8), arrays of n_segments entries, at
+ * offsets_dev[s] on, and integral_dev and covered_dev (f64 [n]); counts_dev, status_dev and
+ * span_dev are not looked at.  A ray never writes outside [offsets[s], offsets[s + 1]) nor past
+ * n_segments, whatever offsets_dev holds.  Equal arguments give equal bits.  n_rays == 0 succeeds
+ * without a launch.
+ * Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for a NULL field or one that is not a scene of ctx, max_trips outside
+ * [1, 2^30], n_rays >= 2^32, n_segments > 2^40 (emit pass), n_levels outside [1, 16], a required
+ * array that is NULL (level_cell_size, prob_lo, level_ratio with n_levels > 1, box_index_lo with
+ * boxes; with n_rays > 0 the end points and the outputs of the pass that runs), a cell size that is not finite and
+ * positive, a prob_lo that is not finite, a box level >= n_levels (and the other box rules), a
+ * ratio below 2, a box index range outside [-2^30, 2^30), two boxes of one level that overlap in
+ * index space, an output array, start_dev, end_dev or offsets_dev sharing a byte with an input
+ * box's cells, a locator of 2^28 list entries or more, and a level-0 bounding box of the scene
+ * that, refined to level n_levels - 1, leaves [-2^30, 2^30] -- and every output is untouched.
+ * Stateless; asynchronous on the context's stream. */
+int avr_scene_rays(avr_context *ctx, const avr_scene *field, const double *start_dev,
+                   const double *end_dev, uint64_t n_rays, uint64_t max_trips,
+                   const int32_t *box_index_lo, const int32_t *level_ratio,
+                   const double *level_cell_size, const double *prob_lo, int n_levels,
+                   const int64_t *offsets_dev, uint64_t n_segments, uint32_t *counts_dev,
+                   uint8_t *status_dev, double *span_dev, double *t0_dev, double *t1_dev,
+                   int8_t *level_dev, double *value_dev, double *integral_dev,
+                   double *covered_dev);
+
 #ifdef __cplusplus
 }
 #endif
