@@ -1,5 +1,6 @@
 """An exact float64 reference of what the ray march samples: the line integrals of a
-piecewise-constant field along the pinhole camera's rays, and the brackets inside which a march
+piecewise-constant field along the pinhole camera's rays (and, given colour tables, the
+emission-absorption colour and alpha of the same rays), and the brackets inside which a march
 that takes samples every `step` must land.  numpy only, float64 only, no stepping: written from
 the definition of the picture, it shares no code and no float32 path with the oracle or the
 kernels.
@@ -103,6 +104,87 @@ transmittance (1 - a_ref)^(length / reference step) is held against the phase-fr
 [floor(l_b / step_b), ceil(l_b / step_b)] instead: it falls inside exactly when the per-level
 opacities a_b are consistent with a_ref, 1 - a_b = (1 - a_ref)^(step_b / reference step).
 
+Colour: the emission-absorption picture (expected(..., tables=...))
+------------------------------------------------------------------
+Scope: finite cells, no antialiasing, no wireframe, table colours in [0, 1] and per-sample
+opacities a < 1 (asserted; the tests keep a <= 0.6).  Opaque entries (a = 1, kappa infinite) are
+out of scope.  The table P_b [256, 4] = (r, g, b, a) of a box's level is INPUT of the march (built
+by the product's host functions, which tests/test_host_parity.py pins); box.index holds each
+cell's entry.
+
+Along one ray inside box b, with chords()' boundaries t_0 .. t_m and entries k_0 .. k_m-1, write
+(c_j, a_j) = P_b[k_j], kappa_j = -log1p(-a_j) and Y_j = (t_j - t_0) / step_b, the boundaries
+measured in samples.  The layer and the alpha of the box are
+
+    L_b = sum_j T_<j c_j (1 - (1 - a_j)^(Y_j+1 - Y_j)),   A_b = 1 - prod_j (1 - a_j)^(Y_j+1 - Y_j),
+
+T_<j the product over the segments before j, and the pixel is sum_b (prod_b' before b (1 - A_b'))
+L_b, the (disjoint) boxes in the order of their entries along the ray: premultiplied colour, as
+the march stores it.  At integer Y this is exactly the recurrence alpha = a (1 - A); C += c alpha;
+A += alpha.  At the exact real Y it is the reference value `colour`; alpha = 1 - exp(-tau), tau =
+sum kappa_j (Y_j+1 - Y_j) over all boxes.
+
+The march's cumulative sample counts sit at Y'_j = Y_j + E_j / step with E_j in [-below_j,
+above_j], the intervals derived above (entry: [0, step x droppable samples]; and 2 u (t_j - t_0)
+more on either side for the float32 step, which scales every Y_j by 1 + 2 u at most).  Sample
+positions are monotone along the ray on every axis, so the Y'_j are ordered like the Y_j and so is
+every point between the two: no segment has negative length on the way, and C is differentiable
+along it.  For the boundary between segments j-1 and j
+
+    dC/dY_j = T_j [ (kappa_j-1 c_j-1 - kappa_j c_j) + (kappa_j - kappa_j-1) B_j ]
+
+with T_j the transmittance in front of the boundary (earlier boxes included) and B_j the colour
+behind it per unit transmittance, B_j = sum_i>=j (T_i / T_j) c_i (1 - ...) <= 1 - (what is left
+behind) <= 1 and >= 0 because the c are in [0, 1].  The bracket is linear in B: it lies between its
+values D0 at B = 0 and D1 at B = 1.  Entry and exit: the same with kappa = 0 on the empty side.  A
+boundary between cells of the same entry moves nothing (E taken as 0).  By the mean-value theorem
+along the straight path from Y to Y',
+
+    C_march - C_exact = sum_j dC/dY_j(xi) E_j / step,
+
+and each term is at most T_up_j max(max(D0, D1) above_j, -min(D0, D1) below_j, 0) / step above and
+T_up_j max(-min(D0, D1) above_j, max(D0, D1) below_j, 0) / step below: ONE-SIDED per boundary and
+sign, as for the column.
+T_up_j bounds T_j(xi) = exp(-tau'_j).  Summation by parts, with e_i = E_i / step and kappa_-1 = 0:
+
+    tau'_j = sum_i<j kappa_i (Y'_i+1 - Y'_i) = tau_j + kappa_j-1 e_j - sum_i<j (kappa_i - kappa_i-1) e_i
+           >= tau_j - [ kappa_j-1 below_j + sum_i<j ((kappa_i - kappa_i-1)^+ above_i
+                                                     + (kappa_i-1 - kappa_i)^+ below_i) ] / step
+
+the sum running over the entry (jump +kappa_first) and the cell changes before j, of this box and
+of every box in front (each with its exit's term).  T_up_j = exp(-max(that bound, 0)).  This is NOT
+the shorter T_j (1 - a_max)^(-s), s the largest |E| / step so far: with opacity alternating from
+cell to cell and every boundary moved towards the more opaque side, the optical depth in front
+drops by more than kappa_max s, so that form is no bound; the one above is, and where kappa is
+constant it gives the exact kappa (below_j + entry drop) / step.
+Alpha: the same argument with c = 1 needs no linearisation, tau' being monotone in each E_j: the
+march's tau lies in [tau - slack_lo, tau + slack_hi], slack_lo the bracket above at the exit of
+every box, slack_hi its mirror image (above and below exchanged).  For the homogeneous map this
+is NO TIGHTER than alpha_lo / alpha_hi, which also use that a sample count is an integer.
+
+Segments flagged `near` (an end within delta of a cell edge): at most l_c / step + 1 samples, each
+possibly read from one of the 26 neighbours n or dropped as outside.  Replacing (a, c) of one
+sample by (a_n, c_n) changes its own term by T (a c - a_n c_n) and scales all behind it, B T (a_n
+- a) with B in [0, 1]: at most T_up (|a c - a_n c_n| + |a - a_n|); dropped, T_up (a c + a).  Both
+are added (the safe reading), to either side; for alpha T_up (max_n |a - a_n| + a).
+
+float32 rounding, in units of u on values <= 1 (A, C, a, c, 1 - A are all in [0, 1]); a
+perturbation d of A or of a weight changes the final colour by at most d, because everything behind
+is scaled by (1 - d / T) and is at most T.  Per sample and channel (AVR_ACCUMULATE, and its packed
+form AVR_STEP, the same operations): 1 - A, a (1 - A), A + alpha (3, acting through the weight or
+through A), c alpha and C + c alpha (2): k_1 = 5; alpha alone: the product and the sum as
+check_alpha counts them, 2.  Per box crossed (blend_depthsort, once per layer in the run's fold,
+the receiver's fold and the ranks' fold alike): t = 1 - front.a, back.c t, front.c + that (3) and
+the same three on alpha, which act on the colour behind (3): k_2 = 6; alpha alone 3.  Once: the
+clamps to [0, 1] move a value towards the exact one, which lies there, and round nothing; the
+store is of a float32; the exchange and gather copy bits; the picture's byte is int(c * 256), exact
+in float32 and monotone; 1 is kept for the float64 evaluation of the reference itself: k_3 = 1;
+alpha alone 2, as in check_alpha (the tables here are the float32 entries themselves).
+    rounding = (k_1 samples_hi + k_2 boxes_crossed + k_3) u
+The stop at acc_a >= 1: what the march leaves out is at most the transmittance where it stops,
+and float32 alpha can read 1 only when the exact transmittance is within alpha's rounding bound:
+that bound, (2 samples_hi + 3 boxes_crossed + 2) u, is added once more to the colour.
+
 Pixels excluded: those for which some box is hit by the ray when grown by delta but not when
 shrunk by delta (hit or miss is itself uncertain).  Nothing else.
 """
@@ -126,6 +208,18 @@ class Conventions:
     row0_at_bottom: bool = True
     fov_is_full_angle: bool = True
     aspect_on_x: bool = True
+
+
+@dataclass
+class Reading:
+    """The reading of the coloured picture stated in the module docstring (emission-absorption).
+    Other values exist only so that the tests can show the colour brackets tell them apart."""
+    boxes_front_to_back: bool = True
+    segments_front_to_back: bool = True
+    colour_times_opacity: bool = True     # False: the table's colour taken as premultiplied
+    entry_offset: int = 0                 # table[k + entry_offset] for a cell of entry k
+    boxes_shadow: bool = True             # False: layers summed without what is in front
+    swap_red_blue: bool = False
 
 
 @dataclass
@@ -274,6 +368,130 @@ def _dilate(a, reduce):
     return out
 
 
+# float32 roundings, in units of U on values <= 1 (module docstring, "float32 rounding"): per
+# sample, per box crossed, once per pixel; for a colour channel and for alpha
+K_COLOUR = (5, 6, 1)
+K_ALPHA = (2, 3, 2)
+
+
+@dataclass
+class ColourTerms:
+    """Per ray that crosses the box (Chords.rays).  `under`, `over`, `alpha_near` are per unit of
+    the transmittance in front of the box; the tau_* widen the box's optical depth tau."""
+    entry: np.ndarray        # [R] where the ray enters the box (0: the eye is inside)
+    layer: np.ndarray        # [R, 3] L_b
+    under: np.ndarray        # [R, 3]
+    over: np.ndarray         # [R, 3]
+    tau: np.ndarray          # [R] -log(1 - A_b)
+    tau_under: np.ndarray    # [R] the march's optical depth lies in [tau - under, tau + over]
+    tau_over: np.ndarray
+    alpha_near: np.ndarray   # [R] the near-an-edge term of alpha
+    samples_hi: np.ndarray   # [R]
+
+
+def _neighbour_spread(q):
+    """q: [nz, ny, nx, 4], a cell's (r, g, b, a).  What one sample of a cell may be wrong by per
+    unit transmittance when it is read from one of the 26 neighbours (edges clamped) or dropped:
+    max_n (|a c - a_n c_n| + |a - a_n|) + (a c + a)  [nz, ny, nx, 3],  and with c = 1 for alpha
+    max_n |a - a_n| + a  [nz, ny, nx]."""
+    a = q[..., 3]
+    ac = q[..., :3] * a[..., None]
+    worst_c, worst_a = np.zeros(ac.shape), np.zeros(a.shape)
+    at = [np.arange(n) for n in a.shape]
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if not (dz or dy or dx):
+                    continue
+                sel = np.ix_(*[np.clip(at[ax] + s, 0, a.shape[ax] - 1)
+                               for ax, s in enumerate((dz, dy, dx))])
+                da = np.abs(a - a[sel])
+                worst_a = np.maximum(worst_a, da)
+                worst_c = np.maximum(worst_c, np.abs(ac - ac[sel]) + da[..., None])
+    return worst_c + ac + a[..., None], worst_a + a
+
+
+def _colour_terms(box, ch, table, step, reading, real, near, first, last, below, above,
+                  entry_above, samples_hi) -> ColourTerms:
+    """The box's layer and its margins (module docstring, "Colour").  real, near, first, last,
+    below, above, entry_above: box_terms' own."""
+    assert box.index is not None and table.shape == (256, 4)
+    # opaque entries (a = 1, kappa infinite) and colours outside [0, 1] are out of scope
+    assert (table[:, :3] >= 0.0).all() and (table[:, :3] <= 1.0).all()
+    assert (table[:, 3] >= 0.0).all() and (table[:, 3] < 1.0).all()
+    R, S = ch.length.shape
+    rows = np.arange(R)
+    i, j, k = ch.cell[..., 0], ch.cell[..., 1], ch.cell[..., 2]
+    assert np.isfinite(box.cells[k, j, i][real]).all()     # cells are finite here
+    entries = np.clip(box.index.astype(np.int64) + reading.entry_offset, 0, 255)
+    m = entries[k, j, i]
+    a, c = table[m, 3], table[m, :3]                        # [R, S], [R, S, 3]
+    kap = -np.log1p(-a)
+    dY = ch.length / step
+    tau_seg = kap * dY
+    seg_alpha = -np.expm1(-tau_seg)
+
+    # ---- the exact layer
+    if reading.segments_front_to_back:
+        in_front = np.cumsum(tau_seg, axis=1) - tau_seg
+    else:
+        in_front = tau_seg.sum(axis=1, keepdims=True) - np.cumsum(tau_seg, axis=1)
+    if reading.colour_times_opacity:
+        weight = seg_alpha
+    else:       # C += c (1 - A) per sample: the geometric sum over the segment's samples
+        weight = np.where(a > 0.0, seg_alpha / np.where(a > 0.0, a, 1.0), dY)
+    layer = ((np.exp(-in_front) * weight)[..., None] * c).sum(axis=1)
+    if reading.swap_red_blue:
+        layer = layer[:, ::-1]
+    tau = tau_seg.sum(axis=1)
+
+    # ---- boundaries 0 .. S: (kappa, c) in front of (f) and behind (b) each; the last real
+    # segment's values carried over the empty ones, so that jumps are between real cells
+    carry = np.maximum.accumulate(np.where(real, np.arange(S)[None, :], 0), axis=1)
+    kc = np.take_along_axis(kap, carry, axis=1)
+    cc = np.take_along_axis(c, carry[..., None], axis=1)
+    inner = np.arange(1, S)[None, :] > first[:, None]
+    kf, kb = np.zeros((R, S + 1)), np.zeros((R, S + 1))
+    cf, cb = np.zeros((R, S + 1, 3)), np.zeros((R, S + 1, 3))
+    kf[:, 1:S], kb[:, 1:S] = np.where(inner, kc[:, :-1], 0.0), np.where(inner, kc[:, 1:], 0.0)
+    cf[:, 1:S] = np.where(inner[..., None], cc[:, :-1], 0.0)
+    cb[:, 1:S] = np.where(inner[..., None], cc[:, 1:], 0.0)
+    kb[rows, first], cb[rows, first] = kap[rows, first], c[rows, first]          # the entry
+    kf[rows, last + 1], cf[rows, last + 1] = kap[rows, last], c[rows, last]      # the exit
+    kb[rows, last + 1], cb[rows, last + 1] = 0.0, 0.0
+    D0 = kf[..., None] * cf - kb[..., None] * cb            # dC/dY_j / T_j at B = 0 ...
+    D1 = D0 + (kb - kf)[..., None]                          # ... and at B = 1
+    dmax, dmin = np.maximum(D0, D1), np.minimum(D0, D1)
+
+    # ---- E_j in [-e_lo, e_hi] where moving the boundary changes anything; the float32 step
+    # (2 u relative on every Y_j) is a shift of 2 u (t_j - t_0) more
+    moves = (kf != kb) | (D0 != 0.0).any(axis=-1)
+    grow = 2.0 * U * (ch.t - ch.t[:, :1])
+    e_lo = np.where(moves, below + grow, 0.0)
+    e_hi = np.where(moves, above + grow, 0.0)
+    e_lo[rows, first], e_hi[rows, first] = 0.0, entry_above
+    assert np.isfinite(e_lo).all() and np.isfinite(e_hi).all()
+
+    # ---- the optical depth in front of boundary j, from below and from above (summation by parts)
+    tau_front = np.concatenate([np.zeros((R, 1)), np.cumsum(tau_seg, axis=1)], axis=1)
+    up, down = np.maximum(kb - kf, 0.0), np.maximum(kf - kb, 0.0)
+    less, more = up * e_hi + down * e_lo, up * e_lo + down * e_hi
+    slack_lo = (kf * e_lo + np.cumsum(less, axis=1) - less) / step
+    slack_hi = (kf * e_hi + np.cumsum(more, axis=1) - more) / step
+    T_up = np.exp(-np.maximum(tau_front - slack_lo, 0.0))
+
+    over = (T_up[..., None] * np.maximum(np.maximum(dmax * e_hi[..., None], -dmin * e_lo[..., None]),
+                                         0.0)).sum(axis=1) / step
+    under = (T_up[..., None] * np.maximum(np.maximum(-dmin * e_hi[..., None], dmax * e_lo[..., None]),
+                                          0.0)).sum(axis=1) / step
+    spread_c, spread_a = _neighbour_spread(table[entries])
+    wrong = np.where(near, dY + 1.0, 0.0) * T_up[:, :-1]
+    lateral = (wrong[..., None] * spread_c[k, j, i]).sum(axis=1)
+    return ColourTerms(ch.t[:, 0], layer, under + lateral, over + lateral, tau,
+                       slack_lo[rows, last + 1], slack_hi[rows, last + 1],
+                       (wrong * spread_a[k, j, i]).sum(axis=1), samples_hi)
+
+
 @dataclass
 class BoxTerms:
     """Per ray that crosses the box (Chords.rays): exact integrals and derived margins."""
@@ -287,10 +505,14 @@ class BoxTerms:
     depth: np.ndarray
     depth_margin: np.ndarray
     lateral: np.ndarray = None   # [R] bool: some segment carries the near-an-edge term
+    colour: Optional["ColourTerms"] = None   # with a colour table only
 
 
-def box_terms(camera, d, box: Box, step: Optional[float] = None) -> BoxTerms:
-    """d: [P, 3].  `step` overrides the box's own step (tests of the brackets' teeth only)."""
+def box_terms(camera, d, box: Box, step: Optional[float] = None, table=None,
+              reading: Reading = Reading()) -> BoxTerms:
+    """d: [P, 3].  `step` overrides the box's own step (tests of the brackets' teeth only).
+    table: float64 [256, 4] (r, g, b, opacity of one sample) of this box's level; with it and
+    box.index the box's colour layer and its margins are filled in (BoxTerms.colour)."""
     origin, f, _, _ = camera_frame(camera)
     ch = chords(origin, d, box)
     dr = d[ch.rays]
@@ -381,8 +603,13 @@ def box_terms(camera, d, box: Box, step: Optional[float] = None) -> BoxTerms:
     # entry point: 3 components x (position delta + subtract + multiply) + 2 adds of the dot product
     depth_margin = tau_in * np.abs(cos) + 3.0 * ch.delta + \
         8.0 * U * (np.abs(origin).max() + np.abs(ch.t_in))
+    colour = None
+    if table is not None:
+        colour = _colour_terms(box, ch, np.asarray(table, np.float64), step, reading, real, near,
+                               first, last, below, above, entry_above,
+                               np.floor((length + length_margin[1]) / step))
     return BoxTerms(ch, length, length_margin, column, column_margin, mip_lo, mip_hi, depth,
-                    depth_margin, near.any(axis=1))
+                    depth_margin, near.any(axis=1), colour)
 
 
 @dataclass
@@ -407,12 +634,22 @@ class Expected:
     # a medium of the table's opacity per reference step must fall inside whatever the phase
     physical_lo: Optional[np.ndarray] = None
     physical_hi: Optional[np.ndarray] = None
+    # with colour tables: the premultiplied colour [height, width, 3] and the alpha of the
+    # emission-absorption picture, got in [x - x_under, x + x_over] per channel
+    colour: Optional[np.ndarray] = None
+    colour_under: Optional[np.ndarray] = None
+    colour_over: Optional[np.ndarray] = None
+    alpha: Optional[np.ndarray] = None
+    alpha_under: Optional[np.ndarray] = None
+    alpha_over: Optional[np.ndarray] = None
 
     def outside(self, what: str, got) -> np.ndarray:
-        """Where `got` leaves the bracket of "length" or "column"."""
+        """Where `got` leaves the bracket of "length", "column", "alpha" or "colour" (there: in
+        any channel)."""
         exact = getattr(self, what)
-        return (got < exact - getattr(self, what + "_under")) | \
+        bad = (got < exact - getattr(self, what + "_under")) | \
             (got > exact + getattr(self, what + "_over"))
+        return bad.any(axis=-1) if bad.ndim == 3 else bad
 
     def lateral_share(self) -> float:
         """Share of the hitting pixels whose brackets are widened by the near-an-edge term."""
@@ -425,9 +662,14 @@ class Expected:
 def expected(camera, width: int, height: int, boxes: Sequence[Box],
              steps: Optional[Sequence[float]] = None,
              sample_alpha: Optional[Sequence[float]] = None,
-             conventions: Conventions = Conventions()) -> Expected:
+             conventions: Conventions = Conventions(),
+             tables: Optional[Sequence[np.ndarray]] = None,
+             reading: Reading = Reading()) -> Expected:
     """Exact images over disjoint boxes, and the brackets a stepping march must stay inside.
-    sample_alpha[b]: the opacity one sample of box b adds in a homogeneous medium."""
+    sample_alpha[b]: the opacity one sample of box b adds in a homogeneous medium.
+    tables[b]: the colour table [256, 4] of box b's level (boxes then carry .index): fills
+    colour, alpha and their margins.  `reading` other than the default changes the exact colour
+    only (the margins are those of the default reading)."""
     d = rays(camera, width, height, conventions).reshape(-1, 3)
     P = d.shape[0]
     z = lambda: np.zeros(P)  # noqa: E731
@@ -435,9 +677,15 @@ def expected(camera, width: int, height: int, boxes: Sequence[Box],
                    np.full(P, -1, np.int64), np.full(P, -1, np.int64), np.zeros(P, np.int64))
     log_t_lo, log_t_hi, n_hi_total, log_p_lo, log_p_hi = z(), z(), z(), z(), z()
     lateral = np.zeros(P, bool)
+    if tables is not None:
+        # per ray and box, to be put in the order of the entries along the ray
+        col = {name: np.zeros((P, len(boxes)) + tail) for name, tail in (
+            ("layer", (3,)), ("under", (3,)), ("over", (3,)), ("tau", ()), ("tau_under", ()),
+            ("tau_over", ()), ("alpha_near", ()), ("samples_hi", ()))}
+        entry = np.full((P, len(boxes)), np.inf)
     for b, box in enumerate(boxes):
         step = box.step if steps is None else steps[b]
-        bt = box_terms(camera, d, box, step)
+        bt = box_terms(camera, d, box, step, None if tables is None else tables[b], reading)
         r = bt.ch.rays
         out.excluded |= bt.ch.tangential
         out.hit[r] = True
@@ -461,6 +709,10 @@ def expected(camera, width: int, height: int, boxes: Sequence[Box],
             n_hi_total[r] += n_hi
             log_p_hi[r] += np.floor(bt.length / step) * keep
             log_p_lo[r] += np.ceil(bt.length / step) * keep
+        if tables is not None:
+            entry[r, b] = bt.colour.entry
+            for name, values in col.items():
+                values[r, b] = getattr(bt.colour, name)
     shape = (height, width)
     for name in ("hit", "excluded", "length", "length_under", "length_over", "column", "column_under",
                  "column_over", "mip_lo",
@@ -473,7 +725,43 @@ def expected(camera, width: int, height: int, boxes: Sequence[Box],
         out.samples_hi = n_hi_total.reshape(shape)
         out.physical_lo = (-np.expm1(log_p_hi)).reshape(shape)
         out.physical_hi = (-np.expm1(log_p_lo)).reshape(shape)
+    if tables is not None:
+        _compose_colour(out, entry, col, reading, shape)
     return out
+
+
+def _compose_colour(out: Expected, entry, col, reading: Reading, shape) -> None:
+    """The pixel from its boxes' layers in the order of their entries along the ray (missed
+    boxes, entry = inf and nothing in them, come last), and the margins summed with the bound on
+    the transmittance in front of each box (module docstring, "Colour")."""
+    order = np.argsort(entry if reading.boxes_front_to_back else -entry, axis=1, kind="stable")
+    for name, values in col.items():
+        index = order if values.ndim == 2 else order[..., None]
+        col[name] = np.take_along_axis(values, index, axis=1)
+    tau = col["tau"]
+    tau_front = np.cumsum(tau, axis=1) - tau
+    slack_front = np.cumsum(col["tau_under"], axis=1) - col["tau_under"]
+    t_up = np.exp(-np.maximum(tau_front - slack_front, 0.0))
+    t_front = np.exp(-tau_front) if reading.boxes_shadow else np.ones_like(tau_front)
+    samples = col["samples_hi"].sum(axis=1)
+    crossed = out.boxes_crossed.reshape(-1)
+    rounding = {what: (k[0] * samples + k[1] * crossed + k[2]) * U
+                for what, k in (("colour", K_COLOUR), ("alpha", K_ALPHA))}
+    rounding["colour"] = rounding["colour"] + rounding["alpha"]     # the stop at alpha >= 1
+    out.colour = (t_front[..., None] * col["layer"]).sum(axis=1).reshape(shape + (3,))
+    for side in ("under", "over"):
+        margin = (t_up[..., None] * col[side]).sum(axis=1) + rounding["colour"][:, None]
+        setattr(out, "colour_" + side, margin.reshape(shape + (3,)))
+    total = tau.sum(axis=1)
+    alpha = -np.expm1(-total)
+    near = (t_up * col["alpha_near"]).sum(axis=1) + rounding["alpha"]
+    lowest = -np.expm1(-np.maximum(total - col["tau_under"].sum(axis=1), 0.0))
+    highest = -np.expm1(-(total + col["tau_over"].sum(axis=1)))
+    out.alpha = alpha.reshape(shape)
+    out.alpha_under = (alpha - lowest + near).reshape(shape)
+    out.alpha_over = (highest - alpha + near).reshape(shape)
+    if out.samples_hi is None:
+        out.samples_hi = samples.reshape(shape)
 
 
 # ---- AMR hierarchies given as levels with overlap ----------------------------------------------

@@ -1,7 +1,9 @@
 """The oracle's march against exact ray-cell geometry (tests/continuum.py): lengths, columns,
 maximum intensity, homogeneous alpha and depth must lie inside brackets derived from the geometry
 alone -- and the brackets must be tight enough to tell a different reading of the camera, the
-steps, the hierarchy or the axes apart (the mutants at the end).  No GPU.
+steps, the hierarchy or the axes apart (the mutants at the end).  The coloured frame likewise:
+the oracle's RGBA inside the float64 emission-absorption brackets under two colour maps, and seven
+other readings of the coloured picture outside them.  No GPU.
 
 What the oracle computed is read out of its volume march with the indicator and step-map devices
 kept in tests/helpers.py."""
@@ -9,8 +11,8 @@ import numpy as np
 import pytest
 
 import continuum as K
-from amrvolumerenderer_amd import plotfile, scenes
-from amrvolumerenderer_amd.types import AmrBox, CameraParameters, ScalarTransform
+from amrvolumerenderer_amd import plotfile, runtime, scenes
+from amrvolumerenderer_amd.types import AmrBox, CameraParameters, ScalarTransform, make_params
 from helpers import (SAMPLING_BOUNDS, check_step_table, count_samples, oracle_camera,
                      oracle_params, oracle_transform, step_map)
 
@@ -196,6 +198,92 @@ def check_alpha(name, e, alpha, a_ref, ref_step):
            f"{(e.alpha_hi - e.alpha_lo)[e.hit].mean() / e.alpha_hi[e.hit].mean():.3f}")
 
 
+# ---- colour: maps, tables, what the oracle painted -------------------------------------------------
+
+def plateau_map(bands):
+    """Control points of a colour map that is constant (r, g, b, opacity) on each of the entry
+    ranges [0, 20], [21, 80], [81, 140], [141, 200], [201, 255]: the four MIP_LEVELS entries are
+    the last of their plateaus, so entry k + 1 is another colour than entry k.  The values are
+    those at which build_color_table evaluates the entries, float32(i) / float32(255)."""
+    edges = (0, 20, 21, 80, 81, 140, 141, 200, 201, 255)
+    return [(float(np.float32(e) / np.float32(255.0)),) + tuple(bands[n // 2])
+            for n, e in enumerate(edges)]
+
+
+COLOUR_MAPS = {
+    # colours well apart, red against blue too; opacities times (1 - 0.25) in [0.03, 0.3]
+    "contrast": plateau_map([(0.9, 0.1, 0.1, 0.04), (0.1, 0.8, 0.2, 0.12), (0.1, 0.2, 0.9, 0.25),
+                             (0.9, 0.8, 0.1, 0.4), (0.5, 0.5, 0.5, 0.3)]),
+    # the same with a bright band of no opacity: colour without opacity must add nothing
+    "gap": plateau_map([(0.9, 0.1, 0.1, 0.04), (0.1, 0.8, 0.2, 0.12), (1.0, 1.0, 0.95, 0.0),
+                        (0.9, 0.8, 0.1, 0.4), (0.5, 0.5, 0.5, 0.3)]),
+}
+TRANSPARENCIES = (0.25, 0.85)
+
+
+def level_tables(boxes, color_map, transparency, ref_dist, scalar_range=(0.0, 1.0),
+                 bounds=SAMPLING_BOUNDS):
+    """Per box the colour table of its level as float64 [256, 4], from the product's own host
+    functions (pinned by test_host_parity.py): input data of the march, not a result of it.
+    Opaque entries are out of the colour brackets' scope: every opacity <= 0.6 here."""
+    params = make_params(8, 8, scalar_range, transparency, ref_dist, bounds, color_map)
+    tables = []
+    for box in boxes:
+        _, factor, alpha_scale = runtime.box_sampling(meta(box), params)
+        table = runtime.build_color_table(alpha_scale, factor, scalar_range,
+                                          color_map).astype(np.float64)
+        assert table.shape == (256, 4)
+        assert (table[:, :3] >= 0.0).all() and (table[:, :3] <= 1.0).all()
+        assert (table[:, 3] >= 0.0).all() and (table[:, 3] <= 0.6).all()
+        tables.append(table)
+    return tables
+
+
+def index_cells(box):
+    """What is uploaded for a box with .index: the entry is unambiguous under (0, 1) scaling."""
+    return np.ascontiguousarray((box.index + 0.5) / 255.0)
+
+
+def oracle_colour_layers(O, boxes, cam, W, H, color_map, transparency, ref_dist):
+    ocam, otr = oracle_camera(O, cam), oracle_transform(O, NORM)
+    op = oracle_params(O, W, H, (0.0, 1.0), transparency, ref_dist, SAMPLING_BOUNDS, color_map)
+    return [O.paint_box(O.make_box(index_cells(box), box.min_corner, box.max_corner), otr, op, ocam,
+                        threads=16)[0] for box in boxes]
+
+
+def oracle_colour_frame(O, boxes, cam, W, H, color_map, transparency, ref_dist):
+    """[H, W, 5]: the boxes' layers through the oracle's layered compose of one rank, which takes
+    them in the order of their depth hints."""
+    layers = oracle_colour_layers(O, boxes, cam, W, H, color_map, transparency, ref_dist)
+    ocam = oracle_camera(O, cam)
+    hints = [O.box_depth_hint(O.make_box(index_cells(b), b.min_corner, b.max_corner), ocam)
+             for b in boxes]
+    frame, _, _ = O.compose_layered(layers, hints, [0] * len(boxes), list(range(len(boxes))), 1)
+    return frame.reshape(H, W, 5)
+
+
+def check_colour(name, e, rgba):
+    """rgba [H, W, >= 4] (premultiplied colour, alpha) inside the colour and alpha brackets on
+    every pixel not excluded.  Returns the largest error / margin of (colour, alpha)."""
+    ok = ~e.excluded
+    assert e.excluded_share() <= MAX_EXCLUDED
+    assert e.hit.sum() > 200
+    rgba = np.asarray(rgba, np.float64)
+    worst = []
+    for what, got in (("colour", rgba[..., :3]), ("alpha", rgba[..., 3])):
+        exact, under, over = (getattr(e, what + k) for k in ("", "_under", "_over"))
+        err = got - exact
+        used = np.where(err > 0, err / np.maximum(over, 1e-300), -err / np.maximum(under, 1e-300))
+        width = (under + over)[e.hit].mean(axis=0) / exact[e.hit].mean(axis=0)
+        worst.append(float(used[ok].max()))
+        report(name, f"{what}: largest error / margin", f"{worst[-1]:.3f}; mean bracket width / "
+               f"mean value {np.array2string(np.atleast_1d(width), precision=3)}")
+        bad = ok & e.outside(what, got)
+        assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:3])
+    assert not rgba[~e.hit & ok][:, :4].any()
+    return tuple(worst)
+
+
 # ---- single boxes --------------------------------------------------------------------------------
 
 DEFAULT = scenes.default_camera()
@@ -283,6 +371,56 @@ def test_amr_scene(O, avr_lib, name):
     es = K.expected(cam, W, H, smooth_boxes)
     check_length_column(name + "_smooth", es,
                         *oracle_length_column(O, smooth_boxes, cam, W, H, integer=False))
+
+
+# ---- coloured frames ---------------------------------------------------------------------------------
+
+_COLOUR_CASES = {}
+
+
+def colour_case(name, map_name, transparency=0.0):
+    """(boxes, camera, W, H, reference step, tables, expectation) of a SINGLE or AMR case under
+    a colour map: built once per process and shared, read-only, with the GPU tests.  A single
+    box is painted the way test_single_box paints it: no transparency, its own step the
+    reference."""
+    key = (name, map_name, transparency)
+    if key not in _COLOUR_CASES:
+        if name in SINGLE:
+            box, cam, W, H = single_box(name)
+            boxes, bounds, ref_step = [box], SAMPLING_BOUNDS, 0.0
+        else:
+            spec, cam, W, H = AMR[name]
+            boxes, bounds = amr_boxes(spec, ramp), spec.bounds
+            for b in boxes:
+                b.index = mip_index(b.cells)
+            ref_step = runtime.reference_sample_distance([meta(b) for b in boxes],
+                                                         bounds.min_corner, bounds.max_corner)
+        tables = level_tables(boxes, COLOUR_MAPS[map_name], transparency, ref_step, bounds=bounds)
+        _COLOUR_CASES[key] = (boxes, cam, W, H, ref_step, tables,
+                              K.expected(cam, W, H, boxes, tables=tables))
+    return _COLOUR_CASES[key]
+
+
+@pytest.mark.parametrize("map_name", sorted(COLOUR_MAPS))
+@pytest.mark.parametrize("name", sorted(SINGLE))
+def test_single_box_colour(O, avr_lib, name, map_name):
+    boxes, cam, W, H, ref_step, _, e = colour_case(name, map_name)
+    img = oracle_colour_layers(O, boxes, cam, W, H, COLOUR_MAPS[map_name], 0.0, ref_step)[0]
+    check_colour(f"{name}/{map_name}", e, img)
+
+
+@pytest.mark.parametrize("transparency", TRANSPARENCIES)
+@pytest.mark.parametrize("map_name", sorted(COLOUR_MAPS))
+@pytest.mark.parametrize("name", sorted(AMR))
+def test_amr_scene_colour(O, avr_lib, name, map_name, transparency):
+    boxes, cam, W, H, ref_step, tables, e = colour_case(name, map_name, transparency)
+    assert e.boxes_crossed.max() >= 2 * AMR[name][0].levels
+    # the levels' tables differ (the finer, the less opaque per sample), the colours do not
+    coarse, fine = tables[0], tables[-1]
+    assert boxes[0].level == 0 and boxes[-1].level > 0
+    assert (fine[list(MIP_LEVELS), 3] <= 0.75 * coarse[list(MIP_LEVELS), 3]).all()
+    frame = oracle_colour_frame(O, boxes, cam, W, H, COLOUR_MAPS[map_name], transparency, ref_step)
+    check_colour(f"{name}/{map_name}/{transparency}", e, frame)
 
 
 # ---- a written plotfile: levels with overlap, physical extent ------------------------------------
@@ -430,3 +568,49 @@ def test_mutants_of_the_reference_leave_its_brackets(tmp_path):
     assert len(shares) == 8
     for name, share in shares.items():
         assert share > max(excluded, ep.excluded_share()), name
+
+
+def test_mutants_of_the_coloured_reference_leave_its_brackets(avr_lib):
+    """Another reading of the coloured picture (K.Reading, or other tables), evaluated exactly in
+    float64, must leave the colour brackets of the stated one on more pixels than are excluded."""
+    spec, cam, W, H = TEETH
+    boxes = amr_boxes(spec, ramp)
+    for b in boxes:
+        b.index = mip_index(b.cells)
+    ref_step = runtime.reference_sample_distance([meta(b) for b in boxes], spec.bounds.min_corner,
+                                                 spec.bounds.max_corner)
+    # (at transparency 0.25 the coarse boxes in front are all but opaque and the finer levels
+    # behind them hardly show: their tables would not matter)
+    tables = {m: level_tables(boxes, COLOUR_MAPS[m], 0.85, ref_step, bounds=spec.bounds)
+              for m in COLOUR_MAPS}
+    e = {m: K.expected(cam, W, H, boxes, tables=tables[m]) for m in COLOUR_MAPS}
+    excluded = e["contrast"].excluded_share()
+    assert excluded <= MAX_EXCLUDED
+    assert boxes[0].level == 0
+    mutants = {
+        "boxes_back_to_front": ("contrast", {"reading": K.Reading(boxes_front_to_back=False)}),
+        "segments_back_to_front": ("contrast", {"reading": K.Reading(segments_front_to_back=False)}),
+        "colour_taken_as_premultiplied": ("contrast", {"reading": K.Reading(colour_times_opacity=False)}),
+        "coarsest_table_on_every_level": ("contrast", {"tables": [tables["contrast"][0]] * len(boxes)}),
+        "entry_k_plus_1": ("contrast", {"reading": K.Reading(entry_offset=1)}),
+        "red_and_blue_exchanged": ("contrast", {"reading": K.Reading(swap_red_blue=True)}),
+        "layers_summed_without_shadow": ("contrast", {"reading": K.Reading(boxes_shadow=False)}),
+        # colour without opacity must add nothing: the gap map's bright band shows if it does
+        "gap_colour_taken_as_premultiplied": ("gap", {"reading": K.Reading(colour_times_opacity=False)}),
+    }
+    shares = {}
+    for name, (m, change) in mutants.items():
+        mutant = K.expected(cam, W, H, boxes, **{"tables": tables[m], **change})
+        ok = e[m].hit & ~e[m].excluded
+        bad = e[m].outside("colour", mutant.colour) | e[m].outside("alpha", mutant.alpha)
+        shares[name] = float((bad & ok).sum()) / int(ok.sum())
+        report("mutant " + name, "share of pixels outside the colour brackets", f"{shares[name]:.4f}")
+    report("coloured mutants", "excluded share", f"{excluded:.4f}")
+    for m in COLOUR_MAPS:
+        width = (e[m].colour_under + e[m].colour_over)[e[m].hit].mean(axis=0) / \
+            e[m].colour[e[m].hit].mean(axis=0)
+        report("coloured mutants", f"{m}: mean bracket width / mean value per channel",
+               np.array2string(width, precision=3))
+    assert len(shares) == 8
+    for name, share in shares.items():
+        assert share > excluded, name

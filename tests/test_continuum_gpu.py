@@ -1,7 +1,10 @@
 """The HIP march against exact ray-cell geometry (tests/continuum.py), directly: the projection,
 maximum-intensity and volume kernels of one box, the frames of multi-level scenes (one rank, and
-three ranks on one GPU for the projection) and api.project on a written plotfile.  The cases and
-brackets are those of tests/test_continuum.py; nothing here is derived from the oracle's march."""
+three ranks on one GPU for the projection and for the coloured volume frame) and api.project on a
+written plotfile.  The coloured frames -- the march's table lookup and colour recurrence, the fold's
+and the ranks' front-to-back order, the picture's bytes -- are held to the float64
+emission-absorption brackets.  The cases and brackets are those of tests/test_continuum.py; nothing
+here is derived from the oracle's march."""
 import os
 
 import numpy as np
@@ -50,6 +53,20 @@ def test_single_box(ctx, name):
     missed = np.ones(W * H, bool)
     missed[bt.ch.rays] = False
     assert np.isinf(img[missed & keep, 4]).all() and not img[missed & keep, 3].any()
+    # the colour tables: which entry a sample takes, and the colour recurrence
+    for map_name in sorted(T.COLOUR_MAPS):
+        ec = T.colour_case(name, map_name)[-1]
+        cparams = make_params(W, H, (0.0, 1.0), 0.0, 0.0, SAMPLING_BOUNDS, T.COLOUR_MAPS[map_name])
+        if name == "ghost_cells_view":
+            whole = np.full(box.cells.base.shape, 1e30)
+            whole[2:-2, 2:-2, 2:-2] = T.index_cells(box)
+            cbox = AmrBox(tuple(box.min_corner), tuple(box.max_corner),
+                          torch.from_numpy(whole).to(ctx.device)[2:-2, 2:-2, 2:-2])
+        else:
+            cbox = upload(ctx, box, T.index_cells(box))
+        painted = ctx.paint_box(cbox, T.NORM, cparams, cam)
+        ctx.synchronize()
+        T.check_colour(f"{name}/{map_name}", ec, painted.cpu().numpy().reshape(H, W, 5))
 
 
 def frame_renderer(ctx, spec, boxes, cells=None, color_map=None):
@@ -111,7 +128,54 @@ def test_amr_scene_frames(O, ctx, name):
     T.check_alpha(name + "_render_runs", e, fused_alpha, a_ref, ref_step)
 
 
+def check_bytes(e, rgb8):
+    """The picture's bytes [H, W, 3], rows top-down: each between GetComponentAsByte, int(c * 256)
+    clamped to [0, 255] and so monotone in c, of the colour bracket's two ends."""
+    assert rgb8.shape == e.colour.shape and rgb8.dtype == np.uint8
+    as_byte = lambda c: np.clip(np.floor(c * 256.0), 0, 255).astype(np.int64)  # noqa: E731
+    got = rgb8[::-1].astype(np.int64)
+    ok = ~e.excluded
+    assert (got >= as_byte(e.colour - e.colour_under))[ok].all()
+    assert (got <= as_byte(e.colour + e.colour_over))[ok].all()
+    assert not got[~e.hit & ok].any()
+    assert got[e.hit].max() > 64          # a picture, not a black frame
+
+
+@pytest.mark.parametrize("map_name", sorted(T.COLOUR_MAPS))
+@pytest.mark.parametrize("name", sorted(T.AMR))
+def test_amr_scene_frames_colour(ctx, name, map_name):
+    """The coloured volume frame of render() and the fused render_runs, both transparencies."""
+    spec = T.AMR[name][0]
+    color_map = T.COLOUR_MAPS[map_name]
+    cases = {t: T.colour_case(name, map_name, t) for t in T.TRANSPARENCIES}
+    boxes, cam, W, H, ref_step = cases[T.TRANSPARENCIES[0]][:5]
+    renderer, local = frame_renderer(ctx, spec, boxes, T.index_cells, color_map)
+    assert float(renderer.reference_sample_distance) == ref_step
+    frames = {}
+    for transparency in T.TRANSPARENCIES:
+        image, rgb8 = renderer.render(RenderParameters(W, H, transparency, 1, draw_bounds=False), cam,
+                                      want_image=True)
+        renderer.synchronize()
+        frames[transparency] = (image.cpu().numpy().reshape(H, W, 5), rgb8.cpu().numpy())
+    renderer.native.close()
+    # the fused paint + fold of all boxes in one run
+    scene = ctx.create_scene(local, spec.transform)
+    hints = [runtime.box_depth_hint(b, cam) for b in local]
+    order, run_end = runtime.layer_order(hints, [0] * len(local), list(range(len(local))))
+    for transparency in T.TRANSPARENCIES:
+        params = make_params(W, H, spec.scalar_range, transparency, ref_step, spec.bounds, color_map)
+        fused = scene.render_runs(params, cam, order, run_end, 1)
+        ctx.synchronize()
+        e = cases[transparency][-1]
+        case = f"{name}/{map_name}/{transparency}"
+        T.check_colour(case + " render", e, frames[transparency][0])
+        check_bytes(e, frames[transparency][1])
+        T.check_colour(case + " render_runs", e,
+                       fused.cpu().numpy().reshape(-1, 5)[:W * H].reshape(H, W, 5))
+
+
 THREE_RANKS = "two_levels"
+THREE_RANKS_COLOUR = ("contrast", 0.25)
 
 
 def _three_rank_worker(rank, world, port, name, out_path):
@@ -155,6 +219,58 @@ def test_three_ranks_on_one_gpu_projection(tmp_path):
     spec, cam, W, H = T.AMR[THREE_RANKS]
     e = K.expected(cam, W, H, T.amr_boxes(spec, T.ramp))
     T.check_length_column("three_ranks", e, got["length"], got["column"])
+
+
+def _three_rank_colour_worker(rank, world, port, name, out_path):
+    """One of three ranks on the one GPU: its share of the scene, a coloured volume frame."""
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        spec, cam, W, H = T.AMR[THREE_RANKS]
+        map_name, transparency = THREE_RANKS_COLOUR
+        boxes = T.amr_boxes(spec, T.ramp)
+        scenes.assign_owners(spec, world, "morton")
+        ctx = runtime.Context(0)
+        meta = [scenes.metadata_box(spec, i) for i in range(len(boxes))]
+        local = [device_box(ctx, (T.mip_index(boxes[i].cells) + 0.5) / 255.0, spec.boxes[i].min_corner,
+                            spec.boxes[i].max_corner, spec.boxes[i].level, rank)
+                 for i in scenes.local_box_indices(spec, rank)]
+        comm = runtime.Comm.shared(name, rank, world, 64 << 20)
+        cmap = [ColorMapControlPoint(*p) for p in T.COLOUR_MAPS[map_name]]
+        renderer = FrameRenderer(ctx, meta, local, spec.transform, spec.bounds, spec.scalar_range,
+                                 rank, world, dist.group.WORLD, comm=comm, color_map=cmap)
+        assert renderer.native is not None
+        image, rgb8 = renderer.render(RenderParameters(W, H, transparency, 1, draw_bounds=False), cam,
+                                      want_image=True)
+        renderer.synchronize()
+        if rank == 0:
+            np.savez(out_path, image=image.cpu().numpy(), rgb8=rgb8.cpu().numpy(),
+                     ref_step=float(renderer.reference_sample_distance),
+                     owners=np.array([b.owner for b in spec.boxes]))
+        else:
+            assert image is None and rgb8 is None
+        dist.barrier()
+        renderer.native.close()
+        comm.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_three_ranks_on_one_gpu_colour(tmp_path):
+    """The coloured two-level scene, its boxes owned by three ranks: rank 0's frame, composited
+    across the ranks, inside the brackets of the one picture."""
+    out = tmp_path / "colour.npz"
+    name = f"/avr_continuum_colour_{os.getpid()}"
+    spawn_ranks(_three_rank_colour_worker, 3, lambda port: (3, port, name, str(out)))
+    got = np.load(out)
+    assert len(np.unique(got["owners"])) == 3
+    map_name, transparency = THREE_RANKS_COLOUR
+    _, _, W, H, ref_step, _, e = T.colour_case(THREE_RANKS, map_name, transparency)
+    assert float(got["ref_step"]) == ref_step
+    T.check_colour("three_ranks", e, got["image"].reshape(H, W, 5))
+    check_bytes(e, got["rgb8"])
 
 
 def test_config4_shape_reduced(ctx):
