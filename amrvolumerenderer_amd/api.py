@@ -13,6 +13,7 @@ Arguments are validated exactly as the reference does.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from dataclasses import dataclass
@@ -147,6 +148,98 @@ def build_scene_geometry(ctx, all_boxes: Sequence[AmrBox], local_boxes: Sequence
                          processed_range)
 
 
+# ---- what the products below share ---------------------------------------------------------------
+
+def _require_plotfile(plotfile: str) -> None:
+    if not plotfile:
+        raise RuntimeError("plotfile path is required")
+    if not os.path.exists(plotfile):
+        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+
+
+def _header_levels(header, n_levels: int):
+    """(cell_size, prob_lo, ref_ratio) of a plotfile's first n_levels levels, as the *_scene
+    functions take them."""
+    return header.cell_size[:n_levels], header.prob_lo, header.ref_ratio[:n_levels - 1]
+
+
+def _checked_cell_sizes(scene: "SceneGeometry", cell_sizes) -> List[Tuple[float, ...]]:
+    """cell_sizes as float triples: one per level up to the scene's finest at least, 16 at most."""
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    finest = max((int(b.level) for b in scene.all_boxes), default=0)
+    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
+        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
+                         "(at most 16)")
+    return sizes
+
+
+def _require_one_rank(scene: "SceneGeometry", n_ranks: int, message: str) -> None:
+    if n_ranks > 1 or len(scene.local_boxes) != len(scene.all_boxes):
+        raise NotImplementedError(message)
+
+
+@contextlib.contextmanager
+def _native_scenes(ctx, geometries):
+    """The runtime.Scene of every entry's local boxes (None stays None), in order; all of them
+    are closed on the way out, also those made before a later one failed."""
+    made = []
+    try:
+        for geometry in geometries:
+            made.append(None if geometry is None else
+                        ctx.create_scene(geometry.local_boxes, geometry.scalar_transform))
+        yield made
+    finally:
+        for scene in made:
+            if scene is not None:
+                scene.close()
+
+
+def _blank_like(ctx, geometry: "SceneGeometry", rank: int) -> "SceneGeometry":
+    """geometry's boxes with new cells for a kernel to write (_allocate_like), no transform."""
+    return SceneGeometry(geometry.all_boxes, _allocate_like(ctx, geometry.local_boxes, rank),
+                         ScalarTransform(), geometry.bounds, world_scale=geometry.world_scale)
+
+
+def _computed_scene(ctx, written: "SceneGeometry", log_scale_input: bool,
+                    normalize_to_data_range: bool, process_group, n_ranks: int) -> "SceneGeometry":
+    """The scene of cells a kernel has written into _blank_like's boxes: statistics and the
+    scalar transform from build_scene_geometry, the world scale of the scene they came from."""
+    result = build_scene_geometry(ctx, written.all_boxes, written.local_boxes, written.bounds,
+                                  log_scale_input, normalize_to_data_range, process_group, n_ranks)
+    result.world_scale = written.world_scale
+    return result
+
+
+def _sum_over_ranks(ctx, tensors, process_group, root: Optional[int] = None) -> list:
+    """Every tensor (None stays None) summed over the group's ranks, through the host if the
+    group's backend is not NCCL -- the results are then host tensors.  Without root every rank
+    gets the sums (all-reduce); with it only that global rank does (reduce)."""
+    import torch.distributed as dist
+    stage = dist.get_backend(process_group) != "nccl"
+    ctx.synchronize()
+    summed = []
+    for t in tensors:
+        if t is not None:
+            t = t.cpu() if stage else t
+            if root is None:
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+            else:
+                dist.reduce(t, root, op=dist.ReduceOp.SUM, group=process_group)
+        summed.append(t)
+    return summed
+
+
+def _copied(a):
+    return a.copy() if hasattr(a, "copy") else a.clone()
+
+
+def _write_picture(rgb8, output: str) -> None:
+    """rgb8 [height, width, 3] on the device -> `output`: a PNG for .png, else a PPM."""
+    writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
+    if not writer(rgb8.cpu().numpy(), output):
+        raise RuntimeError(f"could not write '{output}'")
+
+
 # ---- derived fields (DESIGN.md 7, "Derived fields") ----------------------------------------------
 
 def _allocate_like(ctx, local: Sequence[AmrBox], rank: int) -> List[AmrBox]:
@@ -189,28 +282,16 @@ def derive_scene(ctx, program: DerivedProgram, scenes: Sequence["SceneGeometry"]
     for scene in scenes:
         if len(scene.local_boxes) != len(local):
             raise ValueError("the scenes must hold the same boxes as geometry")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in geometry.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
-    out_boxes = _allocate_like(ctx, local, rank)
+    sizes = _checked_cell_sizes(geometry, cell_sizes)
+    written = _blank_like(ctx, geometry, rank)
     to_physical = float(geometry.world_scale)
     origin = [[float(b.min_corner[a]) / to_physical for a in range(3)] for b in local]
-    inputs = [ctx.create_scene(s.local_boxes, s.scalar_transform) for s in scenes]
-    out = ctx.create_scene(out_boxes, ScalarTransform())
-    try:
+    with _native_scenes(ctx, scenes + [written]) as (*inputs, out):
         import numpy as np
         out.derive(inputs, program.instructions, program.constants,
                    np.array(origin, dtype=np.float64).reshape(len(local), 3), sizes)
-    finally:
-        out.close()
-        for scene in inputs:
-            scene.close()
-    result = build_scene_geometry(ctx, geometry.all_boxes, out_boxes, geometry.bounds,
-                                  log_scale_input, normalize_to_data_range, process_group, n_ranks)
-    result.world_scale = geometry.world_scale
-    return result
+    return _computed_scene(ctx, written, log_scale_input, normalize_to_data_range, process_group,
+                           n_ranks)
 
 
 # ---- the level setup of the products that cross levels -------------------------------------------
@@ -221,11 +302,7 @@ def _level_setup(scene: "SceneGeometry", local, cell_sizes, prob_lo, ref_ratio):
     loaded one, one ref_ratio per level transition, and the index of every local box's first cell
     recovered from its corner (gradient.box_index_lo)."""
     from . import gradient
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    finest = max((int(b.level) for b in scene.all_boxes), default=0)
-    if not (finest < len(sizes) <= 16) or any(len(c) != 3 for c in sizes):
-        raise ValueError("cell_sizes must hold (dx, dy, dz) per level up to the finest loaded one "
-                         "(at most 16)")
+    sizes = _checked_cell_sizes(scene, cell_sizes)
     ratios = [int(r) for r in ref_ratio][:len(sizes) - 1]
     if len(ratios) != len(sizes) - 1:
         raise ValueError("ref_ratio must hold one ratio per level transition")
@@ -253,23 +330,14 @@ def gradient_scene(ctx, scene: "SceneGeometry", axis: int, cell_sizes, prob_lo, 
     axis = int(axis)
     if axis not in (0, 1, 2):
         raise ValueError("axis must be 0 (x), 1 (y) or 2 (z)")
-    local = list(scene.local_boxes)
-    if n_ranks > 1 or len(local) != len(scene.all_boxes):
-        raise NotImplementedError("a gradient field needs every box of the scene on one rank: "
-                                  "ghost cells are not exchanged between ranks")
-    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
-    out_boxes = _allocate_like(ctx, local, rank)
-    field = ctx.create_scene(local, scene.scalar_transform)
-    out = ctx.create_scene(out_boxes, ScalarTransform())
-    try:
+    _require_one_rank(scene, n_ranks, "a gradient field needs every box of the scene on one rank: "
+                      "ghost cells are not exchanged between ranks")
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    written = _blank_like(ctx, scene, rank)
+    with _native_scenes(ctx, [scene, written]) as (field, out):
         out.gradient(field, axis, index, ratios, [c[axis] for c in sizes])
-    finally:
-        out.close()
-        field.close()
-    result = build_scene_geometry(ctx, scene.all_boxes, out_boxes, scene.bounds, log_scale_input,
-                                  normalize_to_data_range, process_group, n_ranks)
-    result.world_scale = scene.world_scale
-    return result
+    return _computed_scene(ctx, written, log_scale_input, normalize_to_data_range, process_group,
+                           n_ranks)
 
 
 # ---- clumps ("Clumps") ---------------------------------------------------------------
@@ -290,25 +358,16 @@ def clump_scene(ctx, scene: "SceneGeometry", lower: float, upper: float, cell_si
     raised before any device work."""
     from . import clumps as clump_rules
     lower, upper = clump_rules.check_bounds(lower, upper)
-    local = list(scene.local_boxes)
-    if n_ranks > 1 or len(local) != len(scene.all_boxes):
-        raise NotImplementedError("clumps need every box of the scene on one rank: "
-                                  "labels are not merged between ranks")
-    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
-    out_boxes = _allocate_like(ctx, local, rank)
-    field = ctx.create_scene(local, scene.scalar_transform)
-    out = ctx.create_scene(out_boxes, ScalarTransform())
-    try:
+    _require_one_rank(scene, n_ranks, "clumps need every box of the scene on one rank: "
+                      "labels are not merged between ranks")
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    written = _blank_like(ctx, scene, rank)
+    with _native_scenes(ctx, [scene, written]) as (field, out):
         count = out.clumps(field, lower, upper, index, ratios)
         ctx.synchronize()
         n_clumps = int(count.item())
-    finally:
-        out.close()
-        field.close()
-    result = build_scene_geometry(ctx, scene.all_boxes, out_boxes, scene.bounds, log_scale_input,
-                                  normalize_to_data_range, process_group, n_ranks)
-    result.world_scale = scene.world_scale
-    return result, n_clumps
+    return _computed_scene(ctx, written, log_scale_input, normalize_to_data_range, process_group,
+                           n_ranks), n_clumps
 
 
 def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float = math.inf,
@@ -332,31 +391,25 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
                                                             min_level, max_level)
     header = pf.PlotFileData(plotfile)
     n_levels = len(volumes)
-    labels, n = clump_scene(ctx, scenes[0], lower, upper, header.cell_size[:n_levels],
-                            header.prob_lo, header.ref_ratio[:n_levels - 1], rank, world, group)
+    labels, n = clump_scene(ctx, scenes[0], lower, upper, *_header_levels(header, n_levels), rank,
+                            world, group)
     cells_by_level = np.zeros((n_levels, n), dtype=np.int64)
     sums = {name: np.zeros((n_levels, n), dtype=np.float64) for name in names}
     outside = nonfinite = 0
     if n > 0:
         if n * n_levels >= clump_rules.TABLE_MAX_ENTRIES:
             raise ValueError("too many clumps for one table: n * levels must stay below 2^28")
-        label_scene = ctx.create_scene(labels.local_boxes, labels.scalar_transform)
-        try:
+        with _native_scenes(ctx, [labels]) as (label_scene,):
             counted, _, totals = label_scene.clump_table(n, n_levels)
             ctx.synchronize()
             cells_by_level = counted.cpu().numpy()
             outside = int(totals[0].item())
             for name, scene in zip(names, scenes[1:]):
-                field = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
-                try:
+                with _native_scenes(ctx, [scene]) as (field,):
                     _, summed, totals = label_scene.clump_table(n, n_levels, field)
                     ctx.synchronize()
-                finally:
-                    field.close()
                 sums[name] = summed.cpu().numpy()
                 nonfinite += int(totals[1].item())
-        finally:
-            label_scene.close()
     return {"n": n, "cells_by_level": cells_by_level, "cells": cells_by_level.sum(axis=0),
             "volume": clump_rules.clump_volumes(cells_by_level, volumes),
             "integrals": {name: clump_rules.clump_integrals(sums[name], volumes)
@@ -380,18 +433,13 @@ def isosurface_scene(ctx, scene: "SceneGeometry", value: float, cell_sizes, prob
     value = float(value)
     if not math.isfinite(value):
         raise ValueError("an isosurface's value must be finite")
-    local = list(scene.local_boxes)
-    if n_ranks > 1 or len(local) != len(scene.all_boxes):
-        raise NotImplementedError("an isosurface needs every box of the scene on one rank: "
-                                  "ghost cells are not exchanged between ranks")
-    if sample is not None and len(sample.local_boxes) != len(local):
+    _require_one_rank(scene, n_ranks, "an isosurface needs every box of the scene on one rank: "
+                      "ghost cells are not exchanged between ranks")
+    if sample is not None and len(sample.local_boxes) != len(scene.local_boxes):
         raise ValueError("the sample scene must hold the same boxes as the scene")
-    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
     origin = [float(v) for v in prob_lo]
-    field = ctx.create_scene(local, scene.scalar_transform)
-    other = ctx.create_scene(sample.local_boxes, sample.scalar_transform) \
-        if sample is not None else None
-    try:
+    with _native_scenes(ctx, [scene, sample]) as (field, other):
         counts, _, _, _ = field.isosurface(value, index, ratios, sizes, origin, other)
         ctx.synchronize()
         n, skipped = (int(v) for v in counts.cpu().tolist())
@@ -404,10 +452,6 @@ def isosurface_scene(ctx, scene: "SceneGeometry", value: float, cell_sizes, prob
             vertices, levels = v.cpu().numpy(), l.cpu().numpy()
             if s is not None:
                 samples = s.cpu().numpy()
-    finally:
-        field.close()
-        if other is not None:
-            other.close()
     return vertices, levels, samples, skipped
 
 
@@ -431,8 +475,7 @@ def isosurface(plotfile: str, variable: str, value: float, fields: Sequence[str]
                                                             min_level, max_level)
     header = pf.PlotFileData(plotfile)
     n_levels = len(volumes)
-    arguments = (float(value), header.cell_size[:n_levels], header.prob_lo,
-                 header.ref_ratio[:n_levels - 1])
+    arguments = (float(value), *_header_levels(header, n_levels))
     samples = {}
     if names:
         for name, scene in zip(names, scenes[1:]):
@@ -473,33 +516,26 @@ def streamline_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGe
         raise ValueError("direction must be +1 or -1")
     if not 0 <= max_steps <= 2 ** 20:
         raise ValueError("max_steps must lie in [0, 2^20]")
-    local = list(vx.local_boxes)
-    if n_ranks > 1 or len(local) != len(vx.all_boxes):
-        raise NotImplementedError("streamlines need every box of the scene on one rank: "
-                                  "lines are not handed over between ranks")
-    others = [vy, vz] + ([sample] if sample is not None else [])
-    if any(len(scene.local_boxes) != len(local) for scene in others):
+    _require_one_rank(vx, n_ranks, "streamlines need every box of the scene on one rank: "
+                      "lines are not handed over between ranks")
+    if any(scene is not None and len(scene.local_boxes) != len(vx.local_boxes)
+           for scene in (vy, vz, sample)):
         raise ValueError("the scenes must hold the same boxes")
     start = np.ascontiguousarray(seeds, dtype=np.float64)
     if start.ndim != 2 or start.shape[1] != 3:
         raise ValueError("seeds must be an array [n, 3]")
     if start.shape[0] * (max_steps + 1) >= 2 ** 32:
         raise ValueError("n_seeds * (max_steps + 1) must stay below 2^32")
-    sizes, ratios, index = _level_setup(vx, local, cell_sizes, prob_lo, ref_ratio)
+    sizes, ratios, index = _level_setup(vx, vx.local_boxes, cell_sizes, prob_lo, ref_ratio)
     origin = [float(v) for v in prob_lo]
-    fields = [ctx.create_scene(scene.local_boxes, scene.scalar_transform)
-              for scene in [vx] + others]
-    try:
+    with _native_scenes(ctx, [vx, vy, vz, sample]) as fields:
         points, samples, counts, status = fields[0].streamlines(
             fields[1], fields[2], start, step, direction, max_steps, index, ratios, sizes, origin,
-            fields[3] if sample is not None else None)
+            fields[3])
         ctx.synchronize()
         points, counts, status = points.cpu().numpy(), counts.cpu().numpy(), status.cpu().numpy()
         if samples is not None:
             samples = samples.cpu().numpy()
-    finally:
-        for scene in fields:
-            scene.close()
     return points, counts.astype(np.int64), status, samples
 
 
@@ -538,8 +574,7 @@ def streamlines(plotfile: str,
                                                             min_level, max_level)
     header = pf.PlotFileData(plotfile)
     n_levels = len(volumes)
-    arguments = (header.cell_size[:n_levels], header.prob_lo, header.ref_ratio[:n_levels - 1],
-                 float(step), int(max_steps))
+    arguments = (*_header_levels(header, n_levels), float(step), int(max_steps))
     passes = []        # per direction (lines, status, {name: values per line})
     for sign in _DIRECTIONS[direction]:
         sampled = {}
@@ -584,8 +619,8 @@ def sample_points(plotfile: str, points, fields: Sequence[str], min_level: int =
     values, inside = {}, np.zeros(at.shape[0], dtype=bool)
     for name, scene in zip(names, scenes):
         _, counts, _, sampled = streamline_scene(
-            ctx, scene, scene, scene, at, header.cell_size[:n_levels], header.prob_lo,
-            header.ref_ratio[:n_levels - 1], 1.0, 0, 1, scene, rank, world)
+            ctx, scene, scene, scene, at, *_header_levels(header, n_levels), 1.0, 0, 1, scene,
+            rank, world)
         values[name] = sampled[:, 0].copy()
         inside = counts == 1
     return values, inside
@@ -614,23 +649,18 @@ def covering_grid_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_
         raise ValueError("lo and dims must hold three values")
     if min(dims) < 1:
         raise ValueError("dims must be at least 1")
-    local = list(scene.local_boxes)
-    if n_ranks > 1 or len(local) != len(scene.all_boxes):
-        raise NotImplementedError("a covering grid needs every box of the scene on one rank: "
-                                  "cells are not gathered between ranks")
+    _require_one_rank(scene, n_ranks, "a covering grid needs every box of the scene on one rank: "
+                      "cells are not gathered between ranks")
     if not 0 <= level < len(list(cell_sizes)):
         raise ValueError("level must lie in [0, the number of cell_sizes)")
-    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
-    field = ctx.create_scene(local, scene.scalar_transform)
-    try:
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    with _native_scenes(ctx, [scene]) as (field,):
         values, coverage, cell_level = field.covering_grid(level, lo, dims, index, ratios,
                                                            float(fill), bool(with_coverage))
         ctx.synchronize()
         values = values.cpu().numpy()
         if coverage is not None:
             coverage, cell_level = coverage.cpu().numpy(), cell_level.cpu().numpy()
-    finally:
-        field.close()
     return values, coverage, cell_level
 
 
@@ -659,10 +689,7 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
         raise ValueError("give region or left_edge / right_edge, not both")
     if (left_edge is None) != (right_edge is None):
         raise ValueError("left_edge and right_edge go together")
-    if not plotfile:
-        raise RuntimeError("plotfile path is required")
-    if not os.path.exists(plotfile):
-        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    _require_plotfile(plotfile)
     header = pf.PlotFileData(plotfile)
     _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
     level = finest_loaded if level is None else int(level)
@@ -686,8 +713,7 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     names = [str(name) for name in fields] or [header.var_names[0]]
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
     n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    arguments = (level, lo, dims, header.cell_size[:n_levels], header.prob_lo,
-                 header.ref_ratio[:n_levels - 1], float(fill))
+    arguments = (level, lo, dims, *_header_levels(header, n_levels), float(fill))
     found, coverage, cell_level = {}, None, None
     for name, scene in zip(names, scenes):
         # coverage and cell level are the same for every field of one plotfile: once
@@ -727,9 +753,8 @@ def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_
     import torch
     from . import rays as ray_rules
     local = list(scene.local_boxes)
-    if n_ranks > 1 or len(local) != len(scene.all_boxes):
-        raise NotImplementedError("rays need every box of the scene on one rank: "
-                                  "rays are not handed over between ranks")
+    _require_one_rank(scene, n_ranks, "rays need every box of the scene on one rank: "
+                      "rays are not handed over between ranks")
     first, last = ray_rules.end_points(start, end)
     if first.shape[0] >= 2 ** 32:
         raise ValueError("the number of rays must stay below 2^32")
@@ -743,8 +768,7 @@ def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_
         raise ValueError("max_trips must lie in [1, 2^30]")
     origin = [float(v) for v in prob_lo]
     n = first.shape[0]
-    field = ctx.create_scene(local, scene.scalar_transform)
-    try:
+    with _native_scenes(ctx, [scene]) as (field,):
         a = torch.from_numpy(first).to(ctx.device)
         b = torch.from_numpy(last).to(ctx.device)
         arguments = (a, b, max_trips, index, ratios, sizes, origin)
@@ -762,8 +786,6 @@ def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_
             *segments, integral, covered = (t.cpu().numpy() for t in emitted)
         status, span = status.cpu().numpy(), span.cpu().numpy()
         offsets = offsets.cpu().numpy()
-    finally:
-        field.close()
     t0, t1, level, value = segments
     return {"offsets": offsets, "status": status, "t_enter": span[:, 0].copy(),
             "t_leave": span[:, 1].copy(), "integral": integral, "covered": covered,
@@ -792,16 +814,12 @@ def rays(plotfile: str, start, end, fields: Sequence[str] = (), min_level: int =
     from . import plotfile as pf
     from . import rays as ray_rules
     first, last = ray_rules.end_points(start, end)
-    if not plotfile:
-        raise RuntimeError("plotfile path is required")
-    if not os.path.exists(plotfile):
-        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    _require_plotfile(plotfile)
     header = pf.PlotFileData(plotfile)
     names = [str(name) for name in fields] or [header.var_names[0]]
     ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, names, min_level, max_level)
     n_levels = len(volumes)
-    arguments = (first, last, header.cell_size[:n_levels], header.prob_lo,
-                 header.ref_ratio[:n_levels - 1], max_trips, rank, world)
+    arguments = (first, last, *_header_levels(header, n_levels), max_trips, rank, world)
     geometry, values, integrals = None, {}, {}
     for name, scene in zip(names, scenes):
         found = ray_scene(ctx, scene, *arguments)
@@ -862,18 +880,15 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
             _check_variable(plotfile, plotfile_header(), of, f"gradient field '{name}'")
             inner = resolve(of, False, True)
             finest = max(int(b.level) for b in inner.all_boxes)
-            head = plotfile_header()
-            scene = gradient_scene(ctx, inner, axis, head.cell_size[:finest + 1], head.prob_lo,
-                                   head.ref_ratio[:finest], rank, n_ranks, process_group, log,
-                                   normalize)
+            scene = gradient_scene(ctx, inner, axis, *_header_levels(plotfile_header(), finest + 1),
+                                   rank, n_ranks, process_group, log, normalize)
         elif name in clump_names:
             of, lower, upper = clump_names[name]
             _check_variable(plotfile, plotfile_header(), of, f"clump field '{name}'")
             inner = resolve(of, False, True)
             finest = max(int(b.level) for b in inner.all_boxes)
-            head = plotfile_header()
-            scene, _ = clump_scene(ctx, inner, lower, upper, head.cell_size[:finest + 1],
-                                   head.prob_lo, head.ref_ratio[:finest], rank, n_ranks,
+            scene, _ = clump_scene(ctx, inner, lower, upper,
+                                   *_header_levels(plotfile_header(), finest + 1), rank, n_ranks,
                                    process_group, log, normalize)
         elif name in registered:
             program = derive.compile_field(name)
@@ -1512,11 +1527,7 @@ def project(plotfile: str, width: int = 512, height: int = 512, variable: Option
                                   0.1 if camera_near is None else float(camera_near),
                                   1000.0 if camera_far is None else float(camera_far))
     table = projection_rgb_table(color_map)
-    if not plotfile:
-        raise RuntimeError("plotfile path is required")
-    if not os.path.exists(plotfile):
-        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
-    from . import plotfile as pf
+    _require_plotfile(plotfile)
     from .renderer import FrameRenderer, RenderParameters
     import torch
     ctx, rank, world, group = _runtime_scope()
@@ -1545,9 +1556,7 @@ def project(plotfile: str, width: int = 512, height: int = 512, variable: Option
         rgb8, _ = ctx.projection_colorize(
             column, length, torch.from_numpy(table).to(column.device), quantity, log_scale,
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
-        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
-        if not writer(rgb8.cpu().numpy(), output):
-            raise RuntimeError(f"could not write '{output}'")
+        _write_picture(rgb8, output)
     return q.cpu().numpy()
 
 
@@ -1692,27 +1701,25 @@ def slice_scene(ctx, scene: SceneGeometry, plane: SlicePlane, width: int, height
                  for b in scene.local_boxes]
     except KeyError:
         raise ValueError("a local box is not among the scene's all_boxes") from None
-    local = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
-    value, level, box = local.slice(origin, du, dv, width, height, index)
-    if n_ranks > 1:
-        import torch.distributed as dist
-        stage = dist.get_backend(process_group) != "nccl"
-        root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+    with _native_scenes(ctx, [scene]) as (local,):
+        value, level, box = local.slice(origin, du, dv, width, height, index)
+        if n_ranks > 1:
+            import torch.distributed as dist
+            stage = dist.get_backend(process_group) != "nccl"
+            root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+            ctx.synchronize()
+            parts = [value.view(torch.int64), level.to(torch.int32), box]
+            if stage:
+                parts = [t.cpu() for t in parts]
+            dist.reduce(parts[0], root, op=dist.ReduceOp.SUM, group=process_group)
+            dist.reduce(parts[1], root, op=dist.ReduceOp.MAX, group=process_group)
+            dist.reduce(parts[2], root, op=dist.ReduceOp.MAX, group=process_group)
+            if rank != 0:
+                return None, None, None
+            value = parts[0].to(ctx.device).view(torch.float64)
+            level = parts[1].to(ctx.device).to(torch.int8)
+            box = parts[2].to(ctx.device)
         ctx.synchronize()
-        parts = [value.view(torch.int64), level.to(torch.int32), box]
-        if stage:
-            parts = [t.cpu() for t in parts]
-        dist.reduce(parts[0], root, op=dist.ReduceOp.SUM, group=process_group)
-        dist.reduce(parts[1], root, op=dist.ReduceOp.MAX, group=process_group)
-        dist.reduce(parts[2], root, op=dist.ReduceOp.MAX, group=process_group)
-        if rank != 0:
-            local.close()
-            return None, None, None
-        value = parts[0].to(ctx.device).view(torch.float64)
-        level = parts[1].to(ctx.device).to(torch.int8)
-        box = parts[2].to(ctx.device)
-    ctx.synchronize()
-    local.close()
     return value, level, box
 
 
@@ -1745,11 +1752,7 @@ def slice(plotfile: str, width: int = 512, height: int = 512, variable: Optional
         if len(center) != 3 or not _finite(center):
             raise ValueError("center must hold three finite values")
     table = projection_rgb_table(color_map)
-    if not plotfile:
-        raise RuntimeError("plotfile path is required")
-    if not os.path.exists(plotfile):
-        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
-    from . import plotfile as pf
+    _require_plotfile(plotfile)
     import torch
     ctx, rank, world, group = _runtime_scope()
     scene = _load_variable_scenes(ctx, plotfile, [variable or ""], min_level, max_level, False,
@@ -1775,9 +1778,7 @@ def slice(plotfile: str, width: int = 512, height: int = 512, variable: Optional
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
         if annotate_grids:
             ctx.slice_outline(box, rgb8)
-        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
-        if not writer(rgb8.cpu().numpy(), output):
-            raise RuntimeError(f"could not write '{output}'")
+        _write_picture(rgb8, output)
     nan = torch.full_like(shown, float("nan"))
     return torch.where(hit, shown, nan).cpu().numpy()
 
@@ -1935,10 +1936,9 @@ def combine_joint_histograms(parts):
     if not parts:
         raise ValueError("combine_joint_histograms needs at least one part")
     cells, sums, totals = parts[0]
-    cells, totals = cells.copy() if hasattr(cells, "copy") else cells.clone(), \
-        totals.copy() if hasattr(totals, "copy") else totals.clone()
+    cells, totals = _copied(cells), _copied(totals)
     if sums is not None:
-        sums = sums.copy() if hasattr(sums, "copy") else sums.clone()
+        sums = _copied(sums)
     for c, s, t in parts[1:]:
         if tuple(c.shape) != tuple(cells.shape) or (s is None) != (sums is None):
             raise ValueError("parts must agree in shape and in having sums")
@@ -1969,7 +1969,6 @@ def phase_scene(ctx, scene_x: SceneGeometry, scene_y: Optional[SceneGeometry], x
     [ny, nx] and sums float64 [ny, nx] (None without scene_z) summed over levels, cells_by_level
     / sums_by_level [L, ny, nx], outside and nonfinite (int), x_edges, y_edges."""
     import numpy as np
-    import torch
     if (z not in HISTOGRAM_WEIGHTS) != (scene_z is not None):
         raise ValueError("scene_z is given exactly when z names a variable")
     ex = _checked_edges(x_edges, "x_edges")
@@ -1986,31 +1985,14 @@ def phase_scene(ctx, scene_x: SceneGeometry, scene_y: Optional[SceneGeometry], x
     if not (finest < n_levels <= JOINT_HISTOGRAM_MAX_LEVELS):
         raise ValueError("cell_volumes must hold one entry per level up to the finest loaded one "
                          f"(at most {JOINT_HISTOGRAM_MAX_LEVELS})")
-    fields = [ctx.create_scene(s.local_boxes, s.scalar_transform) if s is not None else None
-              for s in (scene_x, scene_y, scene_z)]
-    try:
-        cells, sums, totals = fields[0].joint_histogram(ex, fields[1], ey, fields[2], n_levels)
+    with _native_scenes(ctx, [scene_x, scene_y, scene_z]) as (x, y, s):
+        cells, sums, totals = x.joint_histogram(ex, y, ey, s, n_levels)
         if n_ranks > 1:
-            import torch.distributed as dist
-            stage = dist.get_backend(process_group) != "nccl"
-            ctx.synchronize()
-            reduced = []
-            for t in (cells, sums, totals):
-                if t is None:
-                    reduced.append(None)
-                    continue
-                t = t.cpu() if stage else t
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
-                reduced.append(t)
-            cells, sums, totals = reduced
+            cells, sums, totals = _sum_over_ranks(ctx, (cells, sums, totals), process_group)
         ctx.synchronize()
         cells_by_level = cells.cpu().numpy()
         sums_by_level = None if sums is None else sums.cpu().numpy()
         totals = totals.cpu().numpy()
-    finally:
-        for field in fields:
-            if field is not None:
-                field.close()
     total_sums = None
     if sums_by_level is not None:
         total_sums = np.zeros(sums_by_level.shape[1:], dtype=np.float64)
@@ -2027,9 +2009,8 @@ def _field_range(ctx, scene: SceneGeometry, log: bool, what: str, n_ranks: int, 
     """(lo, hi) of a field's finite cells over all ranks ((min positive, max) with log), hi moved
     off lo if they are equal."""
     import torch
-    local = ctx.create_scene(scene.local_boxes, scene.scalar_transform)
-    lo, hi, lo_pos, finite = local.scalar_stats()
-    local.close()
+    with _native_scenes(ctx, [scene]) as (local,):
+        lo, hi, lo_pos, finite = local.scalar_stats()
     if n_ranks > 1:
         import torch.distributed as dist
         device = ctx.device if dist.get_backend(process_group) == "nccl" else "cpu"
@@ -2050,10 +2031,7 @@ def _field_range(ctx, scene: SceneGeometry, log: bool, what: str, n_ranks: int, 
 
 def _load_fields(plotfile: str, variables, min_level: int, max_level: int):
     """(ctx, rank, world, group, scenes, cell volumes): one scene per variable name."""
-    if not plotfile:
-        raise RuntimeError("plotfile path is required")
-    if not os.path.exists(plotfile):
-        raise RuntimeError(f"plotfile path '{plotfile}' does not exist")
+    _require_plotfile(plotfile)
     from . import plotfile as pf
     header = pf.PlotFileData(plotfile)
     for name in variables:
@@ -2112,9 +2090,7 @@ def phase(plotfile: str, x_variable: str, y_variable: str, z: str = "cell_volume
         rgb8, _ = ctx.projection_colorize(
             column, length, torch.from_numpy(table).to(ctx.device), "column", log_scale,
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
-        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
-        if not writer(rgb8.cpu().numpy(), output):
-            raise RuntimeError(f"could not write '{output}'")
+        _write_picture(rgb8, output)
     return result
 
 
@@ -2188,11 +2164,10 @@ def combine_axis_projections(parts):
     parts = list(parts)
     if not parts:
         raise ValueError("combine_axis_projections needs at least one part")
-    copy = lambda a: a.copy() if hasattr(a, "copy") else a.clone()
     integral, weight, length = parts[0]
-    integral, length = copy(integral), copy(length)
+    integral, length = _copied(integral), _copied(length)
     if weight is not None:
-        weight = copy(weight)
+        weight = _copied(weight)
     for i, w, l in parts[1:]:
         if tuple(i.shape) != tuple(integral.shape) or tuple(l.shape) != tuple(integral.shape) or \
                 (w is None) != (weight is None):
@@ -2239,29 +2214,15 @@ def project_axis_scene(ctx, scene_f: SceneGeometry, scene_w: Optional[SceneGeome
     origin = ((center[axis_u] - 0.5 * wu) * scale, (center[axis_v] - 0.5 * wv) * scale)
     du = wu * scale / float(width)
     dv = wv * scale / float(height)
-    fields = [ctx.create_scene(s.local_boxes, s.scalar_transform) if s is not None else None
-              for s in (scene_f, scene_w)]
-    try:
-        images = fields[0].axis_projection(a, origin, du, dv, width, height, dl, fields[1])
+    with _native_scenes(ctx, [scene_f, scene_w]) as (field, weight):
+        images = field.axis_projection(a, origin, du, dv, width, height, dl, weight)
         if n_ranks > 1:
             import torch.distributed as dist
-            stage = dist.get_backend(process_group) != "nccl"
             root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
-            ctx.synchronize()
-            reduced = []
-            for t in images:
-                if t is None:
-                    reduced.append(None)
-                    continue
-                t = t.cpu() if stage else t
-                dist.reduce(t, root, op=dist.ReduceOp.SUM, group=process_group)
-                reduced.append(t if rank != 0 else t.to(ctx.device))
-            images = (None, None, None) if rank != 0 else tuple(reduced)
+            images = _sum_over_ranks(ctx, images, process_group, root)
+            images = (None, None, None) if rank != 0 else \
+                tuple(t if t is None else t.to(ctx.device) for t in images)
         ctx.synchronize()
-    finally:
-        for field in fields:
-            if field is not None:
-                field.close()
     return images
 
 
@@ -2325,7 +2286,5 @@ def project_axis(plotfile: str, axis: str = "z", variable: Optional[str] = None,
             torch.where(hit, shown, torch.zeros_like(shown)), hit.to(torch.float64),
             torch.from_numpy(table).to(integral.device), "column", log_scale,
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
-        writer = save_png if os.path.splitext(output)[1].lower() == ".png" else save_ppm
-        if not writer(rgb8.cpu().numpy(), output):
-            raise RuntimeError(f"could not write '{output}'")
+        _write_picture(rgb8, output)
     return shown.cpu().numpy()

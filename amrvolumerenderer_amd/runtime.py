@@ -535,6 +535,86 @@ class Context:
         return out
 
 
+# ---------------------------------------------------------------------------------------------
+# what Scene's field products share: pointers, level arguments, outputs, points, the native call
+# ---------------------------------------------------------------------------------------------
+
+_ABSENT = object()
+
+
+def _doubles(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ints(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _pointer(t: Optional[torch.Tensor]):
+    """A tensor's address; null for None and for an empty tensor, which has none."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _level_arguments(n_boxes: int, box_index_lo, level_ratio, level_cell_size=_ABSENT,
+                     prob_lo=_ABSENT, per_axis: bool = True):
+    """(index int32 [n_boxes, 3], ratios int32, sizes float64 or None, origin float64 [3] or
+    None) as the native calls that cross levels take them.  level_cell_size is [n_levels, 3], or
+    [n_levels] (the sizes along one axis) without per_axis; with it there is one ratio per level
+    transition, without it the ratios alone say how many levels there are."""
+    index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
+    ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+    sizes = origin = None
+    if level_cell_size is not _ABSENT:
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+    if prob_lo is not _ABSENT:
+        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+    if index.shape != (n_boxes, 3):
+        raise ValueError("box_index_lo must hold three values per box")
+    if sizes is not None and per_axis:
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+    elif sizes is not None and (sizes.ndim != 1 or sizes.size < 1):
+        raise ValueError("level_cell_size must hold one value per level")
+    if ratios.ndim != 1 or (sizes is not None and ratios.size != sizes.shape[0] - 1):
+        raise ValueError("level_ratio must hold one value per level transition")
+    if origin is not None and origin.shape != (3,):
+        raise ValueError("prob_lo must hold three values")
+    return index, ratios, sizes, origin
+
+
+def _output(ctx: "Context", given: Optional[torch.Tensor], dtype, shape, name: str,
+            fill=torch.empty, wrong_size: Optional[str] = None,
+            exact: bool = False) -> torch.Tensor:
+    """The caller's output tensor, or a new one made by fill (torch.empty or torch.zeros):
+    `dtype` on the context's device, contiguous, with as many elements as `shape` -- of that
+    very shape with exact."""
+    if given is None:
+        given = fill(shape, dtype=dtype, device=ctx.device)
+    ctx._check_tensor(given, dtype, name)
+    fits = tuple(given.shape) == tuple(shape) if exact else given.numel() == math.prod(shape)
+    if not fits:
+        raise ValueError(wrong_size or f"{name} has the wrong size")
+    return given
+
+
+def _device_points(ctx: "Context", points, wrong_shape: str) -> torch.Tensor:
+    """Points [n, 3] (a tensor, or anything numpy takes) as contiguous float64 on the device."""
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3))
+    points = points.to(device=ctx.device, dtype=torch.float64).contiguous()
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(wrong_shape)
+    return points
+
+
+def _native(ctx: "Context", entry: str, *arguments) -> None:
+    """One call of the library on the context's stream, ordered behind torch's current stream
+    and ahead of what torch queues next."""
+    ctx.join()
+    _capi.check(getattr(_capi.lib(), entry)(*arguments))
+    ctx.publish()
+
+
 class Scene:
     """The rank's local boxes + scalar transform (avr_scene).  Keeps the cell tensors alive."""
 
@@ -553,17 +633,10 @@ class Scene:
         """avr_scene_histogram: adds this rank's cells to counts[bin_count] (int64 on device)."""
         if bin_count <= 0:
             raise ValueError("binCount must be positive")
-        if counts is None:
-            counts = torch.zeros(bin_count, dtype=torch.int64, device=self.ctx.device)
-        self.ctx._check_tensor(counts, torch.int64, "counts")
-        if counts.numel() != bin_count:
-            raise ValueError("counts has the wrong size")
+        counts = _output(self.ctx, counts, torch.int64, (bin_count,), "counts", torch.zeros)
         ctr = transform.to_c()
-        self.ctx.join()
-        _capi.check(_capi.lib().avr_scene_histogram(
-            self.ctx._handle, self._handle, C.byref(ctr), float(range_min), float(range_max),
-            int(bin_count), C.c_void_p(counts.data_ptr())))
-        self.ctx.publish()
+        _native(self.ctx, "avr_scene_histogram", self.ctx._handle, self._handle, C.byref(ctr),
+                float(range_min), float(range_max), int(bin_count), _pointer(counts))
         return counts
 
     def joint_histogram(self, x_edges, y: Optional["Scene"] = None, y_edges=None,
@@ -596,32 +669,15 @@ class Scene:
         if n_levels < 1:
             raise ValueError("n_levels must be positive")
         shape = (n_levels, ny, nx)
-        if cells is None:
-            cells = torch.zeros(shape, dtype=torch.int64, device=ctx.device)
-        if totals is None:
-            totals = torch.zeros(2, dtype=torch.int64, device=ctx.device)
-        if s is not None and sums is None:
-            sums = torch.zeros(shape, dtype=torch.float64, device=ctx.device)
-        ctx._check_tensor(cells, torch.int64, "cells")
-        ctx._check_tensor(totals, torch.int64, "totals")
-        if tuple(cells.shape) != shape or totals.numel() != 2:
-            raise ValueError("cells must be [n_levels, ny, nx] and totals [2]")
-        if s is not None:
-            ctx._check_tensor(sums, torch.float64, "sums")
-            if tuple(sums.shape) != shape:
-                raise ValueError("sums must be [n_levels, ny, nx]")
-        else:
-            sums = None
-        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_joint_histogram(
-            ctx._handle, self._handle, y._handle if y is not None else None,
-            s._handle if s is not None else None, as_doubles(ex), int(nx),
-            as_doubles(ey) if ey is not None else None, int(ny), n_levels,
-            C.c_void_p(cells.data_ptr()),
-            C.c_void_p(sums.data_ptr()) if sums is not None else None,
-            C.c_void_p(totals.data_ptr())))
-        ctx.publish()
+        wrong = "cells must be [n_levels, ny, nx] and totals [2]"
+        cells = _output(ctx, cells, torch.int64, shape, "cells", torch.zeros, wrong, exact=True)
+        totals = _output(ctx, totals, torch.int64, (2,), "totals", torch.zeros, wrong)
+        sums = None if s is None else _output(ctx, sums, torch.float64, shape, "sums", torch.zeros,
+                                              "sums must be [n_levels, ny, nx]", exact=True)
+        _native(ctx, "avr_scene_joint_histogram", ctx._handle, self._handle,
+                y._handle if y is not None else None, s._handle if s is not None else None,
+                _doubles(ex), int(nx), _doubles(ey) if ey is not None else None, int(ny), n_levels,
+                _pointer(cells), _pointer(sums), _pointer(totals))
         return cells, sums, totals
 
     def slice(self, origin: Sequence[float], du: Sequence[float], dv: Sequence[float], width: int,
@@ -648,23 +704,13 @@ class Scene:
             if index.shape != (len(self.boxes),):
                 raise ValueError("global_index must hold one entry per box of the scene")
         ctx = self.ctx
-        outs = []
-        for name, t, dtype in (("value", value, torch.float64), ("level", level, torch.int8),
-                               ("box", box, torch.int32)):
-            if t is None:
-                t = torch.empty((height, width), dtype=dtype, device=ctx.device)
-            ctx._check_tensor(t, dtype, name)
-            if t.numel() != width * height:
-                raise ValueError(f"{name} has the wrong size")
-            outs.append(t)
-        ctx.join()
-        _capi.check(_capi.lib().avr_slice_scene(
-            ctx._handle, self._handle, vectors[0], vectors[1], vectors[2], width, height,
-            index.ctypes.data_as(C.POINTER(C.c_int32)) if index is not None else None,
-            C.c_void_p(outs[0].data_ptr()), C.c_void_p(outs[1].data_ptr()),
-            C.c_void_p(outs[2].data_ptr())))
-        ctx.publish()
-        return outs[0], outs[1], outs[2]
+        value = _output(ctx, value, torch.float64, (height, width), "value")
+        level = _output(ctx, level, torch.int8, (height, width), "level")
+        box = _output(ctx, box, torch.int32, (height, width), "box")
+        _native(ctx, "avr_slice_scene", ctx._handle, self._handle, *vectors, width, height,
+                _ints(index) if index is not None else None, _pointer(value), _pointer(level),
+                _pointer(box))
+        return value, level, box
 
     def axis_projection(self, axis: int, origin_uv: Sequence[float], du: float, dv: float,
                         width: int, height: int, level_dl: Sequence[float],
@@ -691,32 +737,17 @@ class Scene:
         if dl.ndim != 1 or dl.size < 1:
             raise ValueError("level_dl must hold one value per level")
         ctx = self.ctx
-        outs = []
-        for name, t, wanted in (("integral", integral, True),
-                                ("weight", weight, weight_scene is not None),
-                                ("length", length, True)):
-            if not wanted:
-                if t is not None:
-                    raise ValueError("weight is given exactly when weight_scene is")
-                outs.append(None)
-                continue
-            if t is None:
-                t = torch.empty((height, width), dtype=torch.float64, device=ctx.device)
-            ctx._check_tensor(t, torch.float64, name)
-            if t.numel() != width * height:
-                raise ValueError(f"{name} has the wrong size")
-            outs.append(t)
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_axis_projection(
-            ctx._handle, self._handle,
-            weight_scene._handle if weight_scene is not None else None, axis,
-            (C.c_double * 2)(*origin), float(du), float(dv), width, height,
-            dl.ctypes.data_as(C.POINTER(C.c_double)), int(dl.size),
-            C.c_void_p(outs[0].data_ptr()),
-            C.c_void_p(outs[1].data_ptr()) if outs[1] is not None else None,
-            C.c_void_p(outs[2].data_ptr())))
-        ctx.publish()
-        return outs[0], outs[1], outs[2]
+        integral = _output(ctx, integral, torch.float64, (height, width), "integral")
+        if weight_scene is not None:
+            weight = _output(ctx, weight, torch.float64, (height, width), "weight")
+        elif weight is not None:
+            raise ValueError("weight is given exactly when weight_scene is")
+        length = _output(ctx, length, torch.float64, (height, width), "length")
+        _native(ctx, "avr_scene_axis_projection", ctx._handle, self._handle,
+                weight_scene._handle if weight_scene is not None else None, axis,
+                (C.c_double * 2)(*origin), float(du), float(dv), width, height, _doubles(dl),
+                int(dl.size), _pointer(integral), _pointer(weight), _pointer(length))
+        return integral, weight, length
 
     def derive(self, inputs: Sequence["Scene"], instructions, constants, box_origin,
                level_cell_size) -> None:
@@ -739,13 +770,9 @@ class Scene:
         if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
             raise ValueError("level_cell_size must hold three values per level")
         handles = (C.c_void_p * max(len(inputs), 1))(*[s._handle.value for s in inputs])
-        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_derive(
-            ctx._handle, handles, len(inputs), self._handle,
-            code.ctypes.data_as(C.POINTER(C.c_uint32)), int(code.size), as_doubles(consts),
-            int(consts.size), as_doubles(origin), as_doubles(sizes), int(sizes.shape[0])))
-        ctx.publish()
+        _native(ctx, "avr_scene_derive", ctx._handle, handles, len(inputs), self._handle,
+                code.ctypes.data_as(C.POINTER(C.c_uint32)), int(code.size), _doubles(consts),
+                int(consts.size), _doubles(origin), _doubles(sizes), int(sizes.shape[0]))
 
     def gradient(self, field: "Scene", axis: int, box_index_lo, level_ratio,
                  level_cell_size) -> None:
@@ -756,21 +783,10 @@ class Scene:
         n_levels float64, the cell size along the axis.  This scene's cells must not overlap the
         field's.  Asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if sizes.ndim != 1 or sizes.size < 1:
-            raise ValueError("level_cell_size must hold one value per level")
-        if ratios.ndim != 1 or ratios.size != sizes.size - 1:
-            raise ValueError("level_ratio must hold one value per level transition")
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_gradient(
-            ctx._handle, field._handle, self._handle, int(axis),
-            index.ctypes.data_as(C.POINTER(C.c_int32)), ratios.ctypes.data_as(C.POINTER(C.c_int32)),
-            sizes.ctypes.data_as(C.POINTER(C.c_double)), int(sizes.size)))
-        ctx.publish()
+        index, ratios, sizes, _ = _level_arguments(len(self.boxes), box_index_lo, level_ratio,
+                                                   level_cell_size, per_axis=False)
+        _native(ctx, "avr_scene_gradient", ctx._handle, field._handle, self._handle, int(axis),
+                _ints(index), _ints(ratios), _doubles(sizes), int(sizes.size))
 
     def clumps(self, field: "Scene", lower: float, upper: float, box_index_lo, level_ratio,
                count: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -781,23 +797,11 @@ class Scene:
         clumps N as a one-element int64 tensor on the device (count, if given).  This scene's
         cells must not overlap the field's.  Asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if ratios.ndim != 1:
-            raise ValueError("level_ratio must hold one value per level transition")
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=ctx.device)
-        ctx._check_tensor(count, torch.int64, "count")
-        if count.numel() != 1:
-            raise ValueError("count must hold one value")
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_clumps(
-            ctx._handle, field._handle, self._handle, float(lower), float(upper),
-            index.ctypes.data_as(C.POINTER(C.c_int32)), ratios.ctypes.data_as(C.POINTER(C.c_int32)),
-            int(ratios.size) + 1, C.c_void_p(count.data_ptr())))
-        ctx.publish()
+        index, ratios, _, _ = _level_arguments(len(self.boxes), box_index_lo, level_ratio)
+        count = _output(ctx, count, torch.int64, (1,), "count", torch.zeros,
+                        "count must hold one value")
+        _native(ctx, "avr_scene_clumps", ctx._handle, field._handle, self._handle, float(lower),
+                float(upper), _ints(index), _ints(ratios), int(ratios.size) + 1, _pointer(count))
         return count
 
     def clump_table(self, n_clumps: int, n_levels: int, field: Optional["Scene"] = None,
@@ -813,29 +817,17 @@ class Scene:
         if n_clumps < 1 or n_levels < 1:
             raise ValueError("n_clumps and n_levels must be at least 1")
         shape = (n_levels, n_clumps)
-        if cells is None:
-            cells = torch.zeros(shape, dtype=torch.int64, device=ctx.device)
-        if totals is None:
-            totals = torch.zeros(2, dtype=torch.int64, device=ctx.device)
-        ctx._check_tensor(cells, torch.int64, "cells")
-        ctx._check_tensor(totals, torch.int64, "totals")
-        if tuple(cells.shape) != shape or totals.numel() != 2:
-            raise ValueError("cells must be [n_levels, n_clumps] and totals hold two values")
+        wrong = "cells must be [n_levels, n_clumps] and totals hold two values"
+        cells = _output(ctx, cells, torch.int64, shape, "cells", torch.zeros, wrong, exact=True)
+        totals = _output(ctx, totals, torch.int64, (2,), "totals", torch.zeros, wrong)
         if field is not None:
-            if sums is None:
-                sums = torch.zeros(shape, dtype=torch.float64, device=ctx.device)
-            ctx._check_tensor(sums, torch.float64, "sums")
-            if tuple(sums.shape) != shape:
-                raise ValueError("sums must be [n_levels, n_clumps]")
+            sums = _output(ctx, sums, torch.float64, shape, "sums", torch.zeros,
+                           "sums must be [n_levels, n_clumps]", exact=True)
         elif sums is not None:
             raise ValueError("sums is given exactly when field is")
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_clump_table(
-            ctx._handle, self._handle, field._handle if field is not None else None, n_clumps,
-            n_levels, C.c_void_p(cells.data_ptr()),
-            C.c_void_p(sums.data_ptr()) if sums is not None else None,
-            C.c_void_p(totals.data_ptr())))
-        ctx.publish()
+        _native(ctx, "avr_scene_clump_table", ctx._handle, self._handle,
+                field._handle if field is not None else None, n_clumps, n_levels, _pointer(cells),
+                _pointer(sums), _pointer(totals))
         return cells, sums, totals
 
     def isosurface(self, value: float, box_index_lo, level_ratio, level_cell_size, prob_lo,
@@ -850,42 +842,23 @@ class Scene:
         or None without sample); the three arrays are None with capacity == 0 and written iff
         T <= capacity.  Asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
-        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
-        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
         capacity = int(capacity)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
-            raise ValueError("level_cell_size must hold three values per level")
-        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
-            raise ValueError("level_ratio must hold one value per level transition")
-        if origin.shape != (3,):
-            raise ValueError("prob_lo must hold three values")
         if capacity < 0:
             raise ValueError("capacity must not be negative")
-        if counts is None:
-            counts = torch.zeros(2, dtype=torch.int64, device=ctx.device)
-        ctx._check_tensor(counts, torch.int64, "counts")
-        if counts.numel() != 2:
-            raise ValueError("counts must hold two values")
+        counts = _output(ctx, counts, torch.int64, (2,), "counts", torch.zeros,
+                         "counts must hold two values")
         vertices = levels = samples = None
         if capacity > 0:
             vertices = torch.empty((capacity, 3, 3), dtype=torch.float64, device=ctx.device)
             levels = torch.empty(capacity, dtype=torch.uint8, device=ctx.device)
             if sample is not None:
                 samples = torch.empty((capacity, 3), dtype=torch.float64, device=ctx.device)
-        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_isosurface(
-            ctx._handle, self._handle, sample._handle if sample is not None else None,
-            float(value), index.ctypes.data_as(C.POINTER(C.c_int32)),
-            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
-            int(sizes.shape[0]), capacity, pointer(vertices), pointer(levels), pointer(samples),
-            pointer(counts)))
-        ctx.publish()
+        _native(ctx, "avr_scene_isosurface", ctx._handle, self._handle,
+                sample._handle if sample is not None else None, float(value), _ints(index),
+                _ints(ratios), _doubles(sizes), _doubles(origin), int(sizes.shape[0]), capacity,
+                _pointer(vertices), _pointer(levels), _pointer(samples), _pointer(counts))
         return counts, vertices, levels, samples
 
     def streamlines(self, vy: "Scene", vz: "Scene", seeds, step: float, direction: int,
@@ -902,26 +875,12 @@ class Scene:
         stagnant, 3 not finite) on the device; points and samples past a line's count are NaN.
         Asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
-        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
-        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
         max_steps = int(max_steps)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
-            raise ValueError("level_cell_size must hold three values per level")
-        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
-            raise ValueError("level_ratio must hold one value per level transition")
-        if origin.shape != (3,):
-            raise ValueError("prob_lo must hold three values")
         if max_steps < 0:
             raise ValueError("max_steps must not be negative")
-        if not isinstance(seeds, torch.Tensor):
-            seeds = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3))
-        seeds = seeds.to(device=ctx.device, dtype=torch.float64).contiguous()
-        if seeds.ndim != 2 or seeds.shape[1] != 3:
-            raise ValueError("seeds must hold three values per seed")
+        seeds = _device_points(ctx, seeds, "seeds must hold three values per seed")
         n = int(seeds.shape[0])
         points = torch.full((n, max_steps + 1, 3), math.nan, dtype=torch.float64,
                             device=ctx.device)
@@ -933,17 +892,11 @@ class Scene:
         status = torch.zeros(n, dtype=torch.uint8, device=ctx.device)
         if n == 0:                     # nothing to launch, and empty tensors have no address
             return points, samples, counts, status
-        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_streamlines(
-            ctx._handle, self._handle, vy._handle, vz._handle,
-            sample._handle if sample is not None else None, pointer(seeds), n, float(step),
-            int(direction), max_steps, index.ctypes.data_as(C.POINTER(C.c_int32)),
-            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
-            int(sizes.shape[0]), pointer(points), pointer(samples), pointer(counts),
-            pointer(status)))
-        ctx.publish()
+        _native(ctx, "avr_scene_streamlines", ctx._handle, self._handle, vy._handle, vz._handle,
+                sample._handle if sample is not None else None, _pointer(seeds), n, float(step),
+                int(direction), max_steps, _ints(index), _ints(ratios), _doubles(sizes),
+                _doubles(origin), int(sizes.shape[0]), _pointer(points), _pointer(samples),
+                _pointer(counts), _pointer(status))
         return points, samples, counts, status
 
     def rays(self, start, end, max_trips: int, box_index_lo, level_ratio, level_cell_size,
@@ -960,35 +913,18 @@ class Scene:
         [n_segments], integral, covered float64 [n]).  Everything is on the device;
         asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
-        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
-        origin = np.ascontiguousarray(prob_lo, dtype=np.float64)
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
         max_trips, n_segments = int(max_trips), int(n_segments)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
-            raise ValueError("level_cell_size must hold three values per level")
-        if ratios.ndim != 1 or ratios.size != sizes.shape[0] - 1:
-            raise ValueError("level_ratio must hold one value per level transition")
-        if origin.shape != (3,):
-            raise ValueError("prob_lo must hold three values")
         if not 1 <= max_trips <= 2 ** 30:
             raise ValueError("max_trips must lie in [1, 2^30]")
         if n_segments < 0:
             raise ValueError("n_segments must not be negative")
-        ends = []
-        for points in (start, end):
-            if not isinstance(points, torch.Tensor):
-                points = torch.from_numpy(
-                    np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3))
-            points = points.to(device=ctx.device, dtype=torch.float64).contiguous()
-            if points.ndim != 2 or points.shape[1] != 3:
-                raise ValueError("start and end must hold three values per ray")
-            ends.append(points)
-        if ends[0].shape != ends[1].shape:
+        start = _device_points(ctx, start, "start and end must hold three values per ray")
+        end = _device_points(ctx, end, "start and end must hold three values per ray")
+        if start.shape != end.shape:
             raise ValueError("start and end must hold the same number of rays")
-        n = int(ends[0].shape[0])
+        n = int(start.shape[0])
         emit = offsets is not None
         if emit:
             ctx._check_tensor(offsets, torch.int64, "offsets")
@@ -1010,17 +946,11 @@ class Scene:
             result = (counts, status, span)
         if n == 0:                     # nothing to launch, and empty tensors have no address
             return result
-        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        as_doubles = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_rays(
-            ctx._handle, self._handle, pointer(ends[0]), pointer(ends[1]), n, max_trips,
-            index.ctypes.data_as(C.POINTER(C.c_int32)),
-            ratios.ctypes.data_as(C.POINTER(C.c_int32)), as_doubles(sizes), as_doubles(origin),
-            int(sizes.shape[0]), pointer(offsets), n_segments, pointer(counts), pointer(status),
-            pointer(span), pointer(t0), pointer(t1), pointer(level), pointer(value),
-            pointer(integral), pointer(covered)))
-        ctx.publish()
+        _native(ctx, "avr_scene_rays", ctx._handle, self._handle, _pointer(start), _pointer(end),
+                n, max_trips, _ints(index), _ints(ratios), _doubles(sizes), _doubles(origin),
+                int(sizes.shape[0]), _pointer(offsets), n_segments, _pointer(counts),
+                _pointer(status), _pointer(span), _pointer(t0), _pointer(t1), _pointer(level),
+                _pointer(value), _pointer(integral), _pointer(covered))
         return result
 
     def covering_grid(self, level: int, lo, dims, box_index_lo, level_ratio,
@@ -1034,14 +964,9 @@ class Scene:
         level int8 [nz, ny, nx]) on the device; the last two are None without with_coverage.
         Asynchronous on the context's stream."""
         ctx = self.ctx
-        index = np.ascontiguousarray(box_index_lo, dtype=np.int32)
-        ratios = np.ascontiguousarray(level_ratio, dtype=np.int32)
+        index, ratios, _, _ = _level_arguments(len(self.boxes), box_index_lo, level_ratio)
         first = np.ascontiguousarray(lo, dtype=np.int64)
         extent = np.ascontiguousarray(dims, dtype=np.int64)
-        if index.shape != (len(self.boxes), 3):
-            raise ValueError("box_index_lo must hold three values per box")
-        if ratios.ndim != 1:
-            raise ValueError("level_ratio must hold one value per level transition")
         if first.shape != (3,) or extent.shape != (3,):
             raise ValueError("lo and dims must hold three values")
         if (extent < 1).any() or (extent > 2 ** 31 - 1).any() or (abs(first) > 2 ** 31 - 1).any():
@@ -1055,14 +980,9 @@ class Scene:
         if with_coverage:
             coverage = torch.empty((nz, ny, nx), dtype=torch.float64, device=ctx.device)
             cell_level = torch.empty((nz, ny, nx), dtype=torch.int8, device=ctx.device)
-        pointer = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        as_ints = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ctx.join()
-        _capi.check(_capi.lib().avr_scene_covering_grid(
-            ctx._handle, self._handle, int(level), as_ints(first), as_ints(extent), as_ints(index),
-            as_ints(ratios), int(ratios.size) + 1, float(fill), pointer(values), pointer(coverage),
-            pointer(cell_level)))
-        ctx.publish()
+        _native(ctx, "avr_scene_covering_grid", ctx._handle, self._handle, int(level),
+                _ints(first), _ints(extent), _ints(index), _ints(ratios), int(ratios.size) + 1,
+                float(fill), _pointer(values), _pointer(coverage), _pointer(cell_level))
         return values, coverage, cell_level
 
     def set_classification_cache(self, enabled: bool) -> None:
