@@ -845,6 +845,49 @@ def rays(plotfile: str, start, end, fields: Sequence[str] = (), min_level: int =
     return result
 
 
+def ray_sums_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_ratio,
+                   weight_scene: Optional["SceneGeometry"] = None,
+                   max_trips: Optional[int] = None, rank: int = 0, n_ranks: int = 1) -> dict:
+    """The exact column of every segment start[s] -> end[s] through a scene's raw field, in one
+    walk and with nothing stored per segment ("Off-axis projection").  The arguments
+    are ray_scene's; weight_scene: a scene with the same boxes (another variable of the plotfile
+    at the same levels, or a computed field of it), or None.  Returns a dict of numpy arrays per
+    ray: count uint32 (the segments ray_scene would list), status uint8, t_enter and t_leave
+    float64 as ray_scene gives them, and float64 sums over the leaf segments in walk order, w
+    being a segment's length: covered = sum w; without weight_scene integral = sum v w and
+    counted = sum w over the finite values v, weight is None; with it integral = sum (v q) w,
+    weight = sum q w and counted = sum w where v and the weight's value q are both finite.  Every
+    box of the scene must be on this rank, as for ray_scene."""
+    import numpy as np
+    import torch
+    from . import rays as ray_rules
+    local = list(scene.local_boxes)
+    _require_one_rank(scene, n_ranks, "rays need every box of the scene on one rank: "
+                      "rays are not handed over between ranks")
+    first, last = ray_rules.end_points(start, end)
+    if first.shape[0] >= 2 ** 32:
+        raise ValueError("the number of rays must stay below 2^32")
+    sizes, ratios, index = _level_setup(scene, local, cell_sizes, prob_lo, ref_ratio)
+    if max_trips is None:
+        bounds = ray_rules.level0_bounds(index, [b.cell_dimensions for b in local],
+                                         [b.level for b in local], ratios)
+        max_trips = ray_rules.default_max_trips(bounds, ratios, len(sizes))
+    max_trips = int(max_trips)
+    if not 1 <= max_trips <= ray_rules.MAX_TRIPS:
+        raise ValueError("max_trips must lie in [1, 2^30]")
+    origin = [float(v) for v in prob_lo]
+    with _native_scenes(ctx, [scene, weight_scene]) as (field, weight):
+        a = torch.from_numpy(first).to(ctx.device)
+        b = torch.from_numpy(last).to(ctx.device)
+        found = field.ray_sums(a, b, max_trips, index, ratios, sizes, origin, weight)
+        ctx.synchronize()
+        counts, status, span, integral, weight_sum, counted, covered = (
+            t if t is None else t.cpu().numpy() for t in found)
+    return {"count": counts.view(np.uint32), "status": status, "t_enter": span[:, 0].copy(),
+            "t_leave": span[:, 1].copy(), "integral": integral, "weight": weight_sum,
+            "counted": counted, "covered": covered}
+
+
 def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: int,
                           log_scale_input: bool, normalize_to_data_range: bool, rank: int,
                           n_ranks: int, process_group) -> list:
@@ -2288,3 +2331,167 @@ def project_axis(plotfile: str, axis: str = "z", variable: Optional[str] = None,
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
         _write_picture(rgb8, output)
     return shown.cpu().numpy()
+
+
+# ---- off-axis projection ("Off-axis projection") --------------------------------------
+
+def validate_off_axis_projection_arguments(width: int, height: int, normal: Sequence[float],
+                                           quantity: str = "column",
+                                           center: Optional[Sequence[float]] = None,
+                                           plane_width: Optional[Sequence[float]] = None,
+                                           depth: Optional[float] = None,
+                                           north: Optional[Sequence[float]] = None,
+                                           log_scale: bool = False,
+                                           value_range: Optional[Sequence[float]] = None,
+                                           weight: Optional[str] = None):
+    """The argument checks of project_off_axis(), before any GPU work and before the plotfile is
+    opened: project_axis' rules for the image, the quantity, the center, plane_width, value_range
+    and the weight, slice_basis' for the directions, and a finite, positive depth.  Returns
+    (normal, north, center or None, plane_width or None, depth or None, value_range or None) as
+    floats; north defaults to z, and to y where the normal is within slice_basis' 1e-6 of +-z."""
+    center, widths, rng = validate_axis_projection_arguments(
+        width, height, "z", quantity, center, plane_width, log_scale, value_range, weight)
+    n = _unit(normal, "normal")
+    if north is None:
+        across = _cross((0.0, 0.0, 1.0), n)
+        along_z = not math.sqrt(across[0] * across[0] + across[1] * across[1] +
+                                across[2] * across[2]) > 1e-6
+        north = (0.0, 1.0, 0.0) if along_z else (0.0, 0.0, 1.0)
+    slice_basis(normal, north)
+    if depth is not None:
+        depth = float(depth)
+        if not (math.isfinite(depth) and depth > 0.0):
+            raise ValueError("depth must be finite and positive")
+    return (tuple(float(c) for c in normal), tuple(float(c) for c in north), center, widths, depth,
+            rng)
+
+
+def project_off_axis_scene(ctx, scene_f: SceneGeometry, scene_w: Optional[SceneGeometry],
+                           center: Sequence[float], normal: Sequence[float],
+                           north: Sequence[float], plane_width: Sequence[float], depth: float,
+                           width: int, height: int, cell_sizes, prob_lo, ref_ratio,
+                           rank: int = 0, n_ranks: int = 1, tile_order: bool = False) -> dict:
+    """The exact off-axis projection of loaded scenes ("Off-axis projection"): one
+    ray per pixel (rays.pixel_rays over (n, U, V) = slice_basis(normal, north); center,
+    plane_width = (wu, wv) and depth in the plotfile's physical units), every ray summed by
+    ray_sums_scene, whose other arguments these are.  The rays go to the device in row-major pixel
+    order; with tile_order tile by tile (rays.pixel_order; measured not to be faster),
+    and either way the images come back in pixel order with the same bits.  Returns a dict of [height, width]
+    images, row 0 at the bottom: integral, weight (None without scene_w), counted and covered
+    float64, status uint8 and count uint32, as ray_sums_scene defines them per ray."""
+    import numpy as np
+    from . import rays as ray_rules
+    _require_one_rank(scene_f, n_ranks, "rays need every box of the scene on one rank: "
+                      "rays are not handed over between ranks")
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("image dimensions must be positive")
+    center = tuple(float(c) for c in center)
+    if len(center) != 3 or not _finite(center):
+        raise ValueError("center must hold three finite values")
+    widths = tuple(float(w) for w in plane_width)
+    if len(widths) != 2 or not all(math.isfinite(w) and w > 0.0 for w in widths):
+        raise ValueError("plane_width must be finite and positive")
+    depth = float(depth)
+    if not (math.isfinite(depth) and depth > 0.0):
+        raise ValueError("depth must be finite and positive")
+    n, u, v = slice_basis(normal, north)
+    start, end = ray_rules.pixel_rays(center, n, u, v, widths, depth, width, height)
+    order = ray_rules.pixel_order(width, height) if tile_order else \
+        np.arange(width * height, dtype=np.int64)
+    found = ray_sums_scene(ctx, scene_f, start[order], end[order], cell_sizes, prob_lo, ref_ratio,
+                           scene_w, None, rank, n_ranks)
+    images = {}
+    for key in ("integral", "weight", "counted", "covered", "status", "count"):
+        values = found[key]
+        if values is not None:
+            image = np.empty(width * height, dtype=values.dtype)
+            image[order] = values
+            values = image.reshape(height, width)
+        images[key] = values
+    return images
+
+
+def project_off_axis(plotfile: str, normal: Sequence[float], variable: Optional[str] = None,
+                     weight: Optional[str] = None, width: int = 512, height: int = 512,
+                     min_level: int = 0, max_level: int = -1,
+                     center: Optional[Sequence[float]] = None,
+                     plane_width: Optional[Sequence[float]] = None,
+                     depth: Optional[float] = None, north: Optional[Sequence[float]] = None,
+                     quantity: str = "column", log_scale: bool = False,
+                     value_range: Optional[Sequence[float]] = None,
+                     color_map: Optional[Sequence[Sequence[float]]] = None,
+                     output: Optional[str] = None):
+    """Exact off-axis projection of a plotfile (yt's OffAxisProjectionPlot; DESIGN.md 7, "Off-axis
+    projection"), on cuda:0: per pixel the line integral sum f ds along the pixel's ray through
+    every uncovered cell of the loaded levels that the ray crosses, ds being the length of the ray
+    inside the cell -- no step and no sampling.  The image plane passes through center with
+    (n, right, up) = slice_basis(normal, north), n pointing at the viewer; the rays are depth long,
+    half of it on either side of the plane.  variable and weight: stored variables or registered
+    derived, gradient or clump fields.  center defaults to the centre of the data's bounding box,
+    plane_width = (wu, wv) and depth to the box's diagonal, so that the whole box is seen from any
+    direction, and north to z (to y for a normal along z).  quantity "column": integral = sum f ds
+    over the finite cells; "mean": integral / counted, counted = sum ds over those cells.  With
+    weight the result is the weighted mean sum f w ds / sum w ds over the cells where both are
+    finite; pass quantity="mean" with it, "column" is refused.  Returns the numpy float64 [height,
+    width] image on rank 0, row 0 at the bottom, NaN where the denominator is 0.  With output
+    (.png, else PPM) the picture is written, coloured as project_axis() colours its own; pixels
+    whose ray meets no counted cell are black.  Several ranks raise NotImplementedError before
+    any device work; a ray that ran out of trips raises RuntimeError."""
+    normal, north, center, widths, depth, rng = validate_off_axis_projection_arguments(
+        width, height, normal, quantity, center, plane_width, depth, north, log_scale, value_range,
+        weight)
+    table = projection_rgb_table(color_map)
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from . import plotfile as pf
+    from . import rays as ray_rules
+    several = "an off-axis projection needs every box of the scene on one rank: rays are not " \
+              "handed over between ranks"
+    # known before the runtime is set up and anything is loaded
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or \
+            (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        raise NotImplementedError(several)
+    variables = [variable or ""] + ([weight] if weight is not None else [])
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, variables, min_level,
+                                                            max_level)
+    scene = scenes[0]
+    _require_one_rank(scene, world, several)
+    to_physical = 1.0 / float(scene.world_scale)
+    lo = [min(b.min_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    hi = [max(b.max_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    extent = [hi[i] - lo[i] for i in range(3)]
+    diagonal = math.sqrt((extent[0] * extent[0] + extent[1] * extent[1]) + extent[2] * extent[2])
+    if center is None:
+        center = tuple(0.5 * (lo[i] + hi[i]) for i in range(3))
+    if widths is None:
+        widths = (diagonal, diagonal)
+    if depth is None:
+        depth = diagonal
+    images = project_off_axis_scene(
+        ctx, scene, scenes[1] if weight is not None else None, center, normal, north, widths,
+        depth, width, height, *_header_levels(pf.PlotFileData(plotfile), len(volumes)), rank,
+        world)
+    cut = np.argwhere(images["status"] == ray_rules.TRUNCATED)
+    if cut.size:
+        y, x = (int(v) for v in cut[0])
+        raise RuntimeError(f"project_off_axis: the ray of pixel (x={x}, y={y}) ran out of trips; "
+                           f"its column would be short")
+    integral, counted = images["integral"], images["counted"]
+    if weight is None and quantity == "column":
+        shown = integral
+    else:
+        denominator = images["weight"] if weight is not None else counted
+        filled = denominator != 0.0
+        shown = np.full_like(integral, math.nan)
+        np.divide(integral, denominator, out=shown, where=filled)
+    if output is not None:
+        hit = torch.from_numpy(counted > 0.0).to(ctx.device)
+        values = torch.from_numpy(shown).to(ctx.device)
+        rgb8, _ = ctx.projection_colorize(
+            torch.where(hit, values, torch.zeros_like(values)), hit.to(torch.float64),
+            torch.from_numpy(table).to(ctx.device), "column", log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        _write_picture(rgb8, output)
+    return shown

@@ -2348,6 +2348,63 @@ int avr_scene_rays(avr_context* ctx, const avr_scene* field, const double* start
   });
 }
 
+int avr_scene_ray_sums(avr_context* ctx, const avr_scene* field, const avr_scene* weight,
+                       const double* start_dev, const double* end_dev, uint64_t n_rays,
+                       uint64_t max_trips, const int32_t* box_index_lo,
+                       const int32_t* level_ratio, const double* level_cell_size,
+                       const double* prob_lo, int n_levels, uint32_t* counts_dev,
+                       uint8_t* status_dev, double* span_dev, double* integral_dev,
+                       double* weight_dev, double* counted_dev, double* covered_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    // as avr_scene_rays: the scenes first, every other rule is plan_ray_sums' in its order
+    require(field != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    if (weight != nullptr) require_field_scene(ctx, weight, weight->boxes.size());
+    avr::RaySumsPlan plan = avr::plan_ray_sums(
+        field->boxes.data(), n_boxes, weight != nullptr ? weight->boxes.data() : nullptr,
+        weight != nullptr ? weight->boxes.size() : 0, n_rays, max_trips, box_index_lo,
+        level_ratio, level_cell_size, prob_lo, n_levels, start_dev, end_dev, counts_dev,
+        status_dev, span_dev, integral_dev, weight_dev, counted_dev, covered_dev);
+    if (n_rays == 0) return AVR_OK;
+    avr::RayPlan& walk = plan.walk;
+    if (walk.boxes.empty()) walk.boxes.resize(1);          // never read: no block lists it
+    if (walk.block_boxes.empty()) walk.block_boxes.push_back(0);  // never read: every list is empty
+    if (weight != nullptr && plan.weight_boxes.empty()) plan.weight_boxes.resize(1);  // never read
+    avr::RayArgs args{};
+    ctx->staging.begin((walk.boxes.size() + plan.weight_boxes.size()) * sizeof(avr::CoverBoxDev) +
+                           walk.block_begin.size() * sizeof(uint32_t) +
+                           walk.block_boxes.size() * sizeof(int32_t) + sizeof(walk.levels), 5);
+    args.boxes = ctx->staging.add(walk.boxes.data(), walk.boxes.size());
+    if (weight != nullptr) {
+      args.weight_boxes = ctx->staging.add(plan.weight_boxes.data(), plan.weight_boxes.size());
+    }
+    args.levels = ctx->staging.add(&walk.levels, 1);
+    args.block_begin = ctx->staging.add(walk.block_begin.data(), walk.block_begin.size());
+    args.block_boxes = ctx->staging.add(walk.block_boxes.data(), walk.block_boxes.size());
+    ctx->staging.commit(ctx->stream);
+    args.locator = walk.locator;
+    for (int d = 0; d < 3; ++d) {
+      args.bound_lo[d] = walk.bound_lo[d];
+      args.bound_hi[d] = walk.bound_hi[d];
+    }
+    args.n_levels = n_levels;
+    args.n_rays = static_cast<uint32_t>(n_rays);
+    args.max_trips = static_cast<uint32_t>(max_trips);
+    args.start = start_dev;
+    args.end = end_dev;
+    args.counts = counts_dev;
+    args.status = status_dev;
+    args.span = span_dev;
+    args.integral = integral_dev;
+    args.weight = weight_dev;
+    args.counted = counted_dev;
+    args.covered = covered_dev;
+    return avr::launch_ray_sums(args, ctx->stream);
+  });
+}
+
 static int blend_common(avr_context* ctx, int kind, const void* top, const void* bottom, void* out,
                         int64_t n_pixels) {
   return guarded([&]() -> int {

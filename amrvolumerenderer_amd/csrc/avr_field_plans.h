@@ -1,5 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids, rays):
+// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids, rays, per-ray
+// sums):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -1186,14 +1187,21 @@ struct RayPlan {
 // boxes of one level apart in index space, no output byte and no byte of start, end or offsets
 // shared with an input, the locator's size (max_entries: the bound on its lists, lowered by the
 // plan's test only), the bounding box refined to the finest level inside [-2^30, 2^30].
-inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, uint64_t max_trips,
-                         const int32_t* box_index_lo, const int32_t* level_ratio,
-                         const double* level_cell_size, const double* prob_lo, int n_levels,
-                         const void* start, const void* end, const void* offsets,
-                         uint64_t n_segments, const void* counts, const void* status,
-                         const void* span, const void* t0, const void* t1, const void* level,
-                         const void* value, const void* integral, const void* covered,
-                         int64_t max_entries = kStreamMaxEntries) {
+// What plan_rays and plan_ray_sums share: the rules above in their order, the tables and the
+// locator.  arrays_present: whether the call's own arrays pass the null rule; arrays: the byte
+// ranges of start, end and what the call writes (looked at only once n_rays > 0 and every size
+// rule has passed).  weight (may be null): the boxes of a second scene read at the same cells,
+// n_weight_boxes of them; its rules come after the field's box rules -- as many boxes as the
+// field has and, box by box, the field's level, dims and corner (from which the caller recovered
+// the one index both share), then the view rule -- and its cells count as inputs in the
+// shared-byte rule.  weight_boxes gets its table.
+inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const avr_box* weight,
+                             size_t n_weight_boxes, uint64_t n_rays, uint64_t max_trips,
+                             uint64_t n_segments, const int32_t* box_index_lo,
+                             const int32_t* level_ratio, const double* level_cell_size,
+                             const double* prob_lo, int n_levels, bool arrays_present,
+                             const ByteRanges& arrays, int64_t max_entries,
+                             std::vector<CoverBoxDev>* weight_boxes) {
   require_box(max_trips >= 1 && max_trips <= kRayMaxTrips, "max_trips must lie in [1, 2^30]");
   require_box(n_rays < (uint64_t{1} << 32), "n_rays must stay below 2^32");
   require_box(n_segments <= kRayMaxSegments, "n_segments must not exceed 2^40");
@@ -1201,23 +1209,13 @@ inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, 
   require_box(level_cell_size != nullptr && prob_lo != nullptr, "null argument");
   require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
   require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
-  const bool emit = offsets != nullptr;
-  if (n_rays > 0) {
-    require_box(start != nullptr && end != nullptr, "null argument");
-    if (emit) {
-      require_box(integral != nullptr && covered != nullptr, "null argument");
-      require_box(n_segments == 0 || (t0 != nullptr && t1 != nullptr && level != nullptr &&
-                                      value != nullptr), "null argument");
-    } else {
-      require_box(counts != nullptr && status != nullptr && span != nullptr, "null argument");
-    }
-  }
+  require_box(n_rays == 0 || arrays_present, "null argument");
   RayPlan plan;
   IsoLevelsDev& levels = plan.levels;
   fill_level_geometry(level_cell_size, prob_lo, n_levels, &levels);
   std::vector<CoverBoxDev>& boxes = plan.boxes;
   boxes.resize(n_boxes);
-  ByteRanges read_ranges, write_ranges;
+  ByteRanges read_ranges;
   for (size_t b = 0; b < n_boxes; ++b) {
     const avr_box& first = field[b];
     const avr_box* fields[1] = {&first};
@@ -1237,28 +1235,42 @@ inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, 
       append_byte_range(&read_ranges, view);
     }
   }
+  if (weight != nullptr) {
+    const char* differ = "the weight scene's boxes differ from the field's";
+    require_box(n_weight_boxes == n_boxes, differ);
+    weight_boxes->resize(n_boxes);
+    for (size_t b = 0; b < n_boxes; ++b) {
+      const avr_box& first = field[b];
+      const avr_box& other = weight[b];
+      CoverBoxDev& dev = (*weight_boxes)[b];
+      std::memset(&dev, 0, sizeof(dev));
+      require_box(other.level == first.level && other.dims[0] == first.dims[0] &&
+                      other.dims[1] == first.dims[1] && other.dims[2] == first.dims[2] &&
+                      other.min_corner[0] == first.min_corner[0] &&
+                      other.min_corner[1] == first.min_corner[1] &&
+                      other.min_corner[2] == first.min_corner[2], differ);
+      dev.level = other.level;
+      if (box_is_empty(other)) continue;
+      const FieldView view = field_view(other);
+      dev.cells = view.cells;
+      dev.jstride = view.jstride;
+      dev.kstride = view.kstride;
+      dev.nx = other.dims[0];
+      dev.ny = other.dims[1];
+      dev.nz = other.dims[2];
+      append_byte_range(&read_ranges, view);
+    }
+  }
   fill_level_ratios(level_ratio, n_levels, levels.ratio);
   const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, field, &boxes);
   require_levels_disjoint(boxes, regions);
-  if (n_rays > 0) {
-    append_byte_range(&write_ranges, start, n_rays * 3 * sizeof(double));
-    append_byte_range(&write_ranges, end, n_rays * 3 * sizeof(double));
-    if (emit) {
-      append_byte_range(&write_ranges, offsets, (n_rays + 1) * sizeof(int64_t));
-      if (n_segments > 0) {
-        append_byte_range(&write_ranges, t0, n_segments * sizeof(double));
-        append_byte_range(&write_ranges, t1, n_segments * sizeof(double));
-        append_byte_range(&write_ranges, level, n_segments);
-        append_byte_range(&write_ranges, value, n_segments * sizeof(double));
-      }
-      append_byte_range(&write_ranges, integral, n_rays * sizeof(double));
-      append_byte_range(&write_ranges, covered, n_rays * sizeof(double));
-    } else {
-      append_byte_range(&write_ranges, counts, n_rays * sizeof(uint32_t));
-      append_byte_range(&write_ranges, status, n_rays);
-      append_byte_range(&write_ranges, span, n_rays * 2 * sizeof(double));
+  if (weight != nullptr) {
+    for (size_t b = 0; b < n_boxes; ++b) {
+      for (int d = 0; d < 3; ++d) (*weight_boxes)[b].lo[d] = boxes[b].lo[d];
     }
-    require_no_shared_byte(&read_ranges, write_ranges,
+  }
+  if (n_rays > 0) {
+    require_no_shared_byte(&read_ranges, arrays,
                            "an output array or the rays overlap an input box's cells");
   }
   IndexRegion bound;
@@ -1275,6 +1287,88 @@ inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, 
     plan.bound_lo[d] = static_cast<int32_t>(bound.lo[d]);
     plan.bound_hi[d] = static_cast<int32_t>(bound.hi[d]);
   }
+  return plan;
+}
+
+inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, uint64_t max_trips,
+                         const int32_t* box_index_lo, const int32_t* level_ratio,
+                         const double* level_cell_size, const double* prob_lo, int n_levels,
+                         const void* start, const void* end, const void* offsets,
+                         uint64_t n_segments, const void* counts, const void* status,
+                         const void* span, const void* t0, const void* t1, const void* level,
+                         const void* value, const void* integral, const void* covered,
+                         int64_t max_entries = kStreamMaxEntries) {
+  const bool emit = offsets != nullptr;
+  bool present = start != nullptr && end != nullptr;
+  ByteRanges arrays;
+  if (n_rays > 0) {
+    append_byte_range(&arrays, start, n_rays * 3 * sizeof(double));
+    append_byte_range(&arrays, end, n_rays * 3 * sizeof(double));
+    if (emit) {
+      present = present && integral != nullptr && covered != nullptr &&
+                (n_segments == 0 ||
+                 (t0 != nullptr && t1 != nullptr && level != nullptr && value != nullptr));
+      append_byte_range(&arrays, offsets, (n_rays + 1) * sizeof(int64_t));
+      if (n_segments > 0) {
+        append_byte_range(&arrays, t0, n_segments * sizeof(double));
+        append_byte_range(&arrays, t1, n_segments * sizeof(double));
+        append_byte_range(&arrays, level, n_segments);
+        append_byte_range(&arrays, value, n_segments * sizeof(double));
+      }
+      append_byte_range(&arrays, integral, n_rays * sizeof(double));
+      append_byte_range(&arrays, covered, n_rays * sizeof(double));
+    } else {
+      present = present && counts != nullptr && status != nullptr && span != nullptr;
+      append_byte_range(&arrays, counts, n_rays * sizeof(uint32_t));
+      append_byte_range(&arrays, status, n_rays);
+      append_byte_range(&arrays, span, n_rays * 2 * sizeof(double));
+    }
+  }
+  return plan_ray_walk(field, n_boxes, nullptr, 0, n_rays, max_trips, n_segments, box_index_lo,
+                       level_ratio, level_cell_size, prob_lo, n_levels, present, arrays,
+                       max_entries, nullptr);
+}
+
+// ---- per-ray sums ("Off-axis projection") --------------------------------------
+struct RaySumsPlan {
+  RayPlan walk;                            // plan_rays' tables, entry for entry
+  std::vector<CoverBoxDev> weight_boxes;   // empty without a weight scene
+};
+// The sums of the one walk, per ray: plan_rays' rules in plan_rays' order with the same messages
+// (there is no n_segments), the same locator, and the weight rules (plan_ray_walk) after the
+// field's box rules.  weight (may be null): the weight scene's n_weight_boxes boxes; weight_out is
+// null exactly without it ("null argument" otherwise).  counts u32 [n_rays], status u8 [n_rays],
+// span f64 [n_rays][2], integral, weight_out, counted and covered f64 [n_rays]: device arrays,
+// free to be null with n_rays == 0; none of them, nor start or end, may share a byte with a cell
+// of either scene.
+inline RaySumsPlan plan_ray_sums(const avr_box* field, size_t n_boxes, const avr_box* weight,
+                                 size_t n_weight_boxes, uint64_t n_rays, uint64_t max_trips,
+                                 const int32_t* box_index_lo, const int32_t* level_ratio,
+                                 const double* level_cell_size, const double* prob_lo, int n_levels,
+                                 const void* start, const void* end, const void* counts,
+                                 const void* status, const void* span, const void* integral,
+                                 const void* weight_out, const void* counted, const void* covered,
+                                 int64_t max_entries = kStreamMaxEntries) {
+  const bool present = start != nullptr && end != nullptr && counts != nullptr &&
+                       status != nullptr && span != nullptr && integral != nullptr &&
+                       counted != nullptr && covered != nullptr &&
+                       (weight != nullptr) == (weight_out != nullptr);
+  ByteRanges arrays;
+  if (n_rays > 0) {
+    append_byte_range(&arrays, start, n_rays * 3 * sizeof(double));
+    append_byte_range(&arrays, end, n_rays * 3 * sizeof(double));
+    append_byte_range(&arrays, counts, n_rays * sizeof(uint32_t));
+    append_byte_range(&arrays, status, n_rays);
+    append_byte_range(&arrays, span, n_rays * 2 * sizeof(double));
+    append_byte_range(&arrays, integral, n_rays * sizeof(double));
+    if (weight_out != nullptr) append_byte_range(&arrays, weight_out, n_rays * sizeof(double));
+    append_byte_range(&arrays, counted, n_rays * sizeof(double));
+    append_byte_range(&arrays, covered, n_rays * sizeof(double));
+  }
+  RaySumsPlan plan;
+  plan.walk = plan_ray_walk(field, n_boxes, weight, n_weight_boxes, n_rays, max_trips, 0,
+                            box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, present,
+                            arrays, max_entries, &plan.weight_boxes);
   return plan;
 }
 

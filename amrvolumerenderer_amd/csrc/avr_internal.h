@@ -845,8 +845,13 @@ struct RayArgs {
   double* value;                // [n_segments]
   double* integral;             // [n_rays]
   double* covered;              // [n_rays]
+  // the sums pass: the count pass's three arrays, integral and covered, and
+  const CoverBoxDev* weight_boxes;  // the weight field's boxes, box by box the field's; or null
+  double* weight;               // [n_rays]; written with weight_boxes only
+  double* counted;              // [n_rays]
 };
 int launch_rays(const RayArgs& args, bool emit, void* stream);
+int launch_ray_sums(const RayArgs& args, void* stream);
 
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {

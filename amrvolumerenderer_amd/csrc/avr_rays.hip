@@ -2,12 +2,16 @@
 // entry and exit parameters, the level and the raw value of each, and the exact column integral
 // sum value * ds that comes with them.
 //
-//   rays_kernel<EMIT>    one lane per ray; EMIT: the segments and the sums are written
+//   rays_kernel<MODE>    one lane per ray; MODE: what the one walk writes
 //
 // Two passes over the identical walk: the count pass writes every ray's count, status and clipped
 // span, the host takes the exclusive scan, and the emit pass writes ray s's segments into the
 // slots [offsets[s], offsets[s + 1]) that it owns -- never past that range nor past n_segments,
-// whatever the offsets hold -- and the two sums.  A lane keeps its cell (the geometry level l and
+// whatever the offsets hold -- and the two sums.  The sums pass ("Off-axis
+// projection") is the same walk once: per ray the count pass's three outputs and, accumulated in
+// walk order over the leaf segments, sum w, sum v w and sum w over the finite values -- with a
+// weight field sum (v q) w, sum q w and sum w where both are finite -- each stored once at the
+// end of the walk and nothing per segment.  A lane keeps its cell (the geometry level l and
 // the index G), steps through the face the ray leaves it by and finds the next cell through the
 // streamlines' locator: the list of the block that holds G mapped to level 0, finest level first,
 // walked once, with the candidate index of a level worked out when the walk reaches a box of it.
@@ -30,6 +34,7 @@ namespace avr {
 namespace {
 
 constexpr int kThreads = 64;  // one wave: its slot is free again when its own last ray has ended
+constexpr int kRayCount = 0, kRayEmit = 1, kRaySums = 2;  // rays_kernel's modes
 
 __device__ __forceinline__ int floor_div(int a, int r) {
   const int q = a / r;
@@ -53,11 +58,12 @@ __device__ __forceinline__ double plane_t(const IsoLevelsDev& levels, int l, int
 }
 
 // The cell a trip crosses: its geometry (l, g), the recorded level (-1: absent) and its value's
-// address (null: absent).
+// address (null: absent); box: the box that holds it, set with the address.
 struct RayCell {
   int l, level;
   int g[3];
   const double* at;
+  int box;
 };
 
 // The candidate of level m for the level-c index g taken to hold p: below c the index mapped down,
@@ -117,6 +123,7 @@ __device__ __forceinline__ RayCell locate(const RayArgs& a, const IsoLevelsDev& 
     if (i < static_cast<uint32_t>(box.nx) && j < static_cast<uint32_t>(box.ny) &&
         k < static_cast<uint32_t>(box.nz)) {
       cell.l = cell.level = m;
+      cell.box = b;
       cell.at = box.cells + (i + j * static_cast<uint32_t>(box.jstride) +
                              k * static_cast<uint32_t>(box.kstride));
       return cell;
@@ -127,11 +134,12 @@ __device__ __forceinline__ RayCell locate(const RayArgs& a, const IsoLevelsDev& 
   if (at != finest) candidate(levels, c, g, p, finest, cell.g);
   cell.l = finest;
   cell.level = -1;
+  cell.box = -1;
   cell.at = nullptr;
   return cell;
 }
 
-template <bool EMIT>
+template <int MODE>
 __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
   const uint32_t ray = blockIdx.x * kThreads + threadIdx.x;
   if (ray >= a.n_rays) return;
@@ -152,14 +160,15 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
   // the emit pass: the slots [slot, slot_end) are the ray's own
   unsigned long long slot = 0, slot_end = 0;
   double integral = 0.0, covered = 0.0, length = 0.0;
-  if (EMIT) {
+  double weight = 0.0, counted = 0.0;  // the sums pass
+  if (MODE == kRayEmit) {
     const long long begin = a.offsets[ray], end = a.offsets[ray + 1ull];
     if (begin >= 0 && begin <= end && static_cast<unsigned long long>(end) <= a.n_segments) {
       slot = static_cast<unsigned long long>(begin);
       slot_end = static_cast<unsigned long long>(end);
     }
-    length = __dsqrt_rn((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
   }
+  if (MODE != kRayCount) length = __dsqrt_rn((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
   if (!finite || still) {
     status = kRayInvalid;
   } else if (a.locator.n[0] == 0) {
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
       const double ahead = t_out > t_cur ? t_out : t_cur;
       const double t_next = ahead < t_leave ? ahead : t_leave;
       if (t_next > t_cur) {
-        if (EMIT) {
+        if (MODE == kRayEmit) {
           const unsigned long long at = slot + count;
           if (at < slot_end) {
             const double v = cell.at != nullptr ? *cell.at : nan;
@@ -223,6 +232,30 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
               const double w = (t_next - t_cur) * length;
               covered = covered + w;
               if (__builtin_isfinite(v)) integral = integral + v * w;
+            }
+          }
+        }
+        if (MODE == kRaySums && cell.at != nullptr) {
+          const double v = *cell.at;
+          const double w = (t_next - t_cur) * length;
+          covered = covered + w;
+          if (a.weight_boxes == nullptr) {
+            if (__builtin_isfinite(v)) {
+              integral = integral + v * w;
+              counted = counted + w;
+            }
+          } else {
+            // the same cell of the weight's box, whose level, dims and index are the field's
+            const CoverBoxDev& other = a.weight_boxes[cell.box];
+            const uint32_t i = static_cast<uint32_t>(cell.g[0]) - static_cast<uint32_t>(other.lo[0]);
+            const uint32_t j = static_cast<uint32_t>(cell.g[1]) - static_cast<uint32_t>(other.lo[1]);
+            const uint32_t k = static_cast<uint32_t>(cell.g[2]) - static_cast<uint32_t>(other.lo[2]);
+            const double q = other.cells[i + j * static_cast<uint32_t>(other.jstride) +
+                                         k * static_cast<uint32_t>(other.kstride)];
+            if (__builtin_isfinite(v) && __builtin_isfinite(q)) {
+              integral = integral + (v * q) * w;
+              weight = weight + q * w;
+              counted = counted + w;
             }
           }
         }
@@ -261,10 +294,15 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
       t_cur = t_next;
     }
   }
-  if (EMIT) {
+  if (MODE != kRayCount) {
     a.integral[ray] = integral;
     a.covered[ray] = covered;
-  } else {
+  }
+  if (MODE == kRaySums) {
+    if (a.weight_boxes != nullptr) a.weight[ray] = weight;
+    a.counted[ray] = counted;
+  }
+  if (MODE != kRayEmit) {
     const bool walked = status == kRayComplete || status == kRayTruncated;
     a.counts[ray] = count;
     a.status[ray] = static_cast<uint8_t>(status);
@@ -273,23 +311,28 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
   }
 }
 
-}  // namespace
-
-int launch_rays(const RayArgs& args, bool emit, void* stream_v) {
+template <int MODE>
+int launch_mode(const RayArgs& args, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (args.n_rays == 0) return AVR_OK;
   const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(args.n_rays) + kThreads - 1) / kThreads));
-  if (emit) {
-    hipLaunchKernelGGL(rays_kernel<true>, grid, dim3(kThreads), 0, stream, args);
-  } else {
-    hipLaunchKernelGGL(rays_kernel<false>, grid, dim3(kThreads), 0, stream, args);
-  }
+  hipLaunchKernelGGL(rays_kernel<MODE>, grid, dim3(kThreads), 0, stream, args);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
     set_error(std::string("rays kernel: ") + hipGetErrorString(err));
     return AVR_ERR_RUNTIME;
   }
   return AVR_OK;
+}
+
+}  // namespace
+
+int launch_rays(const RayArgs& args, bool emit, void* stream) {
+  return emit ? launch_mode<kRayEmit>(args, stream) : launch_mode<kRayCount>(args, stream);
+}
+
+int launch_ray_sums(const RayArgs& args, void* stream) {
+  return launch_mode<kRaySums>(args, stream);
 }
 
 }  // namespace avr

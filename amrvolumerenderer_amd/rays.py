@@ -1,6 +1,8 @@
 """Rays ("Rays"): what api.rays works out on the host around the arrays of
 csrc/avr_rays.hip -- the end points as arrays, the default trip bound, the points in the middle of
-the segments, an .npz file.  numpy only; no device work."""
+the segments, an .npz file -- and around the per-ray sums of an off-axis projection (DESIGN.md 7,
+"Off-axis projection"): the rays of an image's pixels and the order that lists them tile by tile.
+numpy only; no device work."""
 from __future__ import annotations
 
 from typing import Dict, Sequence, Tuple
@@ -56,6 +58,51 @@ def default_max_trips(bounds, ref_ratio: Sequence[int], n_levels: int) -> int:
         refine *= int(r)
     planes = sum(hi - lo + 1 for lo, hi in zip(*bounds)) * refine
     return min(8 + 2 * planes, MAX_TRIPS)
+
+
+PIXEL_TILE = 8          # pixel_order's tiles are 8 x 8: the 64 lanes of a wave
+
+
+def pixel_rays(center, n, U, V, plane_width, depth, width: int,
+               height: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(start, end), float64 [height * width, 3] in row-major pixel order with row 0 at the
+    bottom: the rays of an orthographic image ("Off-axis projection").  Pixel (x, y)
+    owns the point P[d] = (center[d] + su U[d]) + sv V[d] of the image plane, su = ((x + 0.5) /
+    width - 0.5) wu, sv = ((y + 0.5) / height - 0.5) wv, (wu, wv) = plane_width; its ray runs from
+    P + h n to P - h n, h = 0.5 depth -- away from the viewer that n points at.  Plain float64 in
+    the order written here."""
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("image dimensions must be positive")
+    center, n, U, V = (np.asarray(v, dtype=np.float64).reshape(3) for v in (center, n, U, V))
+    wu, wv = (np.float64(w) for w in plane_width)
+    su = ((np.arange(width, dtype=np.float64) + 0.5) / np.float64(width) - 0.5) * wu
+    sv = ((np.arange(height, dtype=np.float64) + 0.5) / np.float64(height) - 0.5) * wv
+    h = 0.5 * np.float64(depth)
+    start = np.empty((height, width, 3), dtype=np.float64)
+    end = np.empty((height, width, 3), dtype=np.float64)
+    for d in range(3):
+        P = (center[d] + su[None, :] * U[d]) + sv[:, None] * V[d]
+        start[:, :, d] = P + h * n[d]
+        end[:, :, d] = P - h * n[d]
+    return start.reshape(-1, 3), end.reshape(-1, 3)
+
+
+def pixel_order(width: int, height: int) -> np.ndarray:
+    """The int64 permutation of the row-major pixel numbers y * width + x that lists the pixels
+    tile by tile: tiles of 8 x 8 pixels taken row-major, the pixels inside a tile row-major, those
+    outside the image dropped.  64 rays in a row are then a compact block of the image where the
+    width is a multiple of 8."""
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("image dimensions must be positive")
+    t = PIXEL_TILE
+    tiles_x, tiles_y = (width + t - 1) // t, (height + t - 1) // t
+    ty, tx, py, px = np.meshgrid(np.arange(tiles_y), np.arange(tiles_x), np.arange(t),
+                                 np.arange(t), indexing="ij")
+    x, y = (tx * t + px).reshape(-1), (ty * t + py).reshape(-1)
+    inside = (x < width) & (y < height)
+    return (y[inside] * width + x[inside]).astype(np.int64)
 
 
 def segment_midpoints(result: Dict) -> np.ndarray:

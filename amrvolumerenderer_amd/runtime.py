@@ -953,6 +953,49 @@ class Scene:
                 _pointer(value), _pointer(integral), _pointer(covered))
         return result
 
+    def ray_sums(self, start, end, max_trips: int, box_index_lo, level_ratio, level_cell_size,
+                 prob_lo, weight: Optional["Scene"] = None):
+        """avr_scene_ray_sums with this scene as the field: Scene.rays' walk once, with nothing
+        stored per segment (DESIGN.md 7, "Off-axis projection").  The arguments are Scene.rays';
+        weight: a scene of the same context with the same boxes, or None.  Returns (counts int32
+        [n], status uint8 [n], span float64 [n, 2]) as Scene.rays' count pass gives them and
+        (integral, weight sum or None without weight, counted, covered), float64 [n]: over the
+        leaf segments in walk order, w being a segment's length, covered = sum w; without weight
+        integral = sum v w and counted = sum w where the value v is finite; with it integral =
+        sum (v q) w, weight sum = sum q w and counted = sum w where v and the weight's value q
+        are both finite.  Everything is on the device; asynchronous on the context's stream."""
+        ctx = self.ctx
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
+        max_trips = int(max_trips)
+        if not 1 <= max_trips <= 2 ** 30:
+            raise ValueError("max_trips must lie in [1, 2^30]")
+        if weight is not None and weight.ctx is not ctx:
+            raise ValueError("the weight scene belongs to another context")
+        start = _device_points(ctx, start, "start and end must hold three values per ray")
+        end = _device_points(ctx, end, "start and end must hold three values per ray")
+        if start.shape != end.shape:
+            raise ValueError("start and end must hold the same number of rays")
+        n = int(start.shape[0])
+        counts = torch.zeros(n, dtype=torch.int32, device=ctx.device)
+        status = torch.full((n,), 3, dtype=torch.uint8, device=ctx.device)
+        span = torch.full((n, 2), math.nan, dtype=torch.float64, device=ctx.device)
+        integral = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        weight_sum = None
+        if weight is not None:
+            weight_sum = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        counted = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        covered = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        result = (counts, status, span, integral, weight_sum, counted, covered)
+        if n == 0:                     # nothing to launch, and empty tensors have no address
+            return result
+        _native(ctx, "avr_scene_ray_sums", ctx._handle, self._handle,
+                weight._handle if weight is not None else None, _pointer(start), _pointer(end), n,
+                max_trips, _ints(index), _ints(ratios), _doubles(sizes), _doubles(origin),
+                int(sizes.shape[0]), _pointer(counts), _pointer(status), _pointer(span),
+                _pointer(integral), _pointer(weight_sum), _pointer(counted), _pointer(covered))
+        return result
+
     def covering_grid(self, level: int, lo, dims, box_index_lo, level_ratio,
                       fill: float = math.nan, with_coverage: bool = True):
         """avr_scene_covering_grid with this scene as the field: the field resampled to the cells

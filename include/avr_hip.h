@@ -1395,6 +1395,35 @@ int avr_scene_rays(avr_context *ctx, const avr_scene *field, const double *start
                    int8_t *level_dev, double *value_dev, double *integral_dev,
                    double *covered_dev);
 
+/* ---- per-ray sums ("Off-axis projection") --------------------------------------------- */
+
+/* The sums of avr_scene_rays' walk in one pass, nothing stored per segment: for each of n_rays
+ * segments A -> B the clip, Locate, the trips and the status rules are those of DESIGN.md 7,
+ * "Rays", and over the emitted segments of leaf cells, in walk order from +0.0, with w = (t1 - t0)
+ * |B - A|: covered = sum w; without `weight` (NULL), where the value v is finite, integral = sum
+ * v w and counted = sum w; with `weight` (a scene of ctx whose boxes are, box by box, the field's
+ * in level, dims and corner) and q the weight's value in the same cell, where v and q are both
+ * finite, integral = sum (v q) w, weight = sum q w and counted = sum w.  counts_dev (device, u32
+ * [n]), status_dev (u8 [n]) and span_dev (f64 [n][2]) get what avr_scene_rays' count pass writes,
+ * integral_dev and covered_dev (f64 [n]) -- without `weight` -- what its emit pass writes, by
+ * bits; weight_dev (f64 [n]) is NULL exactly when `weight` is; counted_dev is f64 [n].  The
+ * hierarchy arguments are avr_scene_rays'.  Equal arguments give equal bits.  n_rays == 0 succeeds
+ * without a launch.
+ * Everything is checked on the host before any device work, in avr_scene_rays' order with its
+ * messages (there is no n_segments; with n_rays > 0 every array named above must be there, and
+ * weight_dev must be there exactly with `weight`: "null argument"); after the field's box rules a
+ * weight scene whose boxes differ from the field's in number, level, dims or corner is refused,
+ * then a weight box that breaks the box rules; and no output, nor start_dev or end_dev, may share a
+ * byte with a cell of either scene -- AVR_ERR_INVALID_ARGUMENT, and every output is untouched.
+ * Stateless; asynchronous on the context's stream. */
+int avr_scene_ray_sums(avr_context *ctx, const avr_scene *field, const avr_scene *weight,
+                       const double *start_dev, const double *end_dev, uint64_t n_rays,
+                       uint64_t max_trips, const int32_t *box_index_lo,
+                       const int32_t *level_ratio, const double *level_cell_size,
+                       const double *prob_lo, int n_levels, uint32_t *counts_dev,
+                       uint8_t *status_dev, double *span_dev, double *integral_dev,
+                       double *weight_dev, double *counted_dev, double *covered_dev);
+
 #ifdef __cplusplus
 }
 #endif
