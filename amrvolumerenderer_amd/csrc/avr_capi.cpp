@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "../../include/avr_hip_debug.h"
-#include "avr_field_plans.h"
+#include "avr_context.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
 
@@ -30,21 +30,7 @@ thread_local std::string g_last_error;
 }
 
 void set_error(const std::string& message) { g_last_error = message; }
-
-namespace {
-
-class HipFailure : public std::runtime_error {
- public:
-  using std::runtime_error::runtime_error;
-};
-
-void hip_check(hipError_t err, const char* what) {
-  if (err != hipSuccess) {
-    throw HipFailure(std::string(what) + ": " + hipGetErrorString(err));
-  }
-}
-
-}  // namespace
+const std::string& last_error() { return g_last_error; }
 
 // Every host wait on device work has a deadline (AVR_FRAME_TIMEOUT_MS, default 30 s; 0 = none): the
 // frame of a rank of several contains collectives, and a peer that died, or whose calls differ from
@@ -126,270 +112,13 @@ void wait_stream_deadline(void* stream_v, const char* what) {
   (void)hipEventDestroy(event);
 }
 
-namespace {
-
-void wait_event(hipEvent_t event, const char* what) { wait_event_deadline(event, what); }
-void wait_stream(hipStream_t stream, const char* what) { wait_stream_deadline(stream, what); }
-
-// Per-call descriptors (box table, transfer-function tables, run tables, ...) travel to the
-// device in ONE asynchronous copy per call: they are packed into a pinned host block and copied
-// to its device twin by a small kernel.  A ring of blocks lets the host run several calls ahead of the GPU
-// without waiting (a block is re-used only after the copy that read it has completed).
-class StagingRing {
- public:
-  // Nine: a speculative frame (avr_renderer.cpp) stages three batches on the march's context -- the
-  // checking march, the gated classify pass, the gated march -- whose flag buffers rotate with the
-  // frame's slot, so the batches repeat with period nine: every slot then always sees the same
-  // batch (not copied again, below), and the host may run three such frames ahead.  (With four the
-  // host waited 0.38 ms per frame here for a block of the frame before.)
-  static constexpr int kSlots = 9;
-  static constexpr size_t kAlign = 256;
-
-  ~StagingRing() { release(); }
-
-  void release() {
-    for (Slot& slot : slots_) {
-      if (slot.dev != nullptr) (void)hipFree(slot.dev);
-      if (slot.host != nullptr) (void)hipHostFree(slot.host);
-      if (slot.done != nullptr) (void)hipEventDestroy(slot.done);
-      slot = Slot{};
-    }
-  }
-
-  // The owner keeps the host from running ahead by other means (the frame driver's host-side
-  // back-pressure): a skipped copy then leaves no packet at all on the consumer stream.
-  void set_lean(bool lean) { lean_ = lean; }
-
-  // Starts a batch with room for `bytes` in `items` arrays.
-  // How many batches the host may run ahead of the consumer (1 .. kSlots; default 4: what the
-  // ring was when it had four blocks -- the frame driver's feedback loops, the co-run search among
-  // them, are timed for that lead; a speculating march context takes all nine).
-  void set_ahead(int batches) { ahead_ = std::min(std::max(batches, 1), kSlots); }
-
-  void begin(size_t bytes, int items) {
-    if (ahead_ < kSlots) {
-      Slot& behind = slots_[(next_ + kSlots - ahead_) % kSlots];
-      if (behind.pending) {
-        wait_event(behind.done, "hipEventQuery(staging)");
-        behind.pending = false;
-      }
-    }
-    current_ = &slots_[next_];
-    next_ = (next_ + 1) % kSlots;
-    if (current_->done == nullptr) {
-      hip_check(hipEventCreateWithFlags(&current_->done, avr::ordering_event_flags()), "hipEventCreate");
-    }
-    if (current_->pending) {
-      wait_event(current_->done, "hipEventQuery(staging)");
-      current_->pending = false;
-    }
-    const size_t need = bytes + static_cast<size_t>(items + 1) * kAlign;
-    if (need > current_->capacity) {
-      if (current_->dev != nullptr) (void)hipFree(current_->dev);
-      if (current_->host != nullptr) (void)hipHostFree(current_->host);
-      current_->dev = current_->host = nullptr;
-      current_->capacity = 0;
-      current_->shadow.clear();
-      size_t cap = 1 << 16;
-      while (cap < need) cap *= 2;
-      hip_check(hipMalloc(&current_->dev, cap), "hipMalloc(staging)");
-      hip_check(hipHostMalloc(&current_->host, cap, hipHostMallocMapped), "hipHostMalloc(staging)");
-      hip_check(hipHostGetDevicePointer(&current_->host_mapped, current_->host, 0),
-                "hipHostGetDevicePointer(staging)");
-      current_->capacity = cap;
-    }
-    used_ = 0;
-  }
-
-  // Adds one array to the batch; returns where it will be on the device.
-  template <typename T>
-  const T* add(const T* src, size_t count) {
-    used_ = (used_ + kAlign - 1) / kAlign * kAlign;
-    const size_t bytes = count * sizeof(T);
-    if (used_ + bytes > current_->capacity) throw std::runtime_error("staging batch overflow");
-    if (bytes != 0) std::memcpy(static_cast<char*>(current_->host) + used_, src, bytes);
-    const T* device = reinterpret_cast<const T*>(static_cast<char*>(current_->dev) + used_);
-    used_ += bytes;
-    return device;
-  }
-
-  // One copy for the whole batch, ordered on `stream` before the kernels that read it.  The
-  // copy is a kernel reading the pinned block through its device mapping: hipMemcpyAsync from
-  // pinned memory was measured to block the host until the stream had drained, every few frames
-  // (5-7 ms with five 1.3 ms frames queued; tools/host_stalls.py), and a launch never does.
-  void commit(hipStream_t stream) {
-    // A batch that equals what this slot's device twin already holds is not copied again: while
-    // camera and parameters repeat, a slot sees the same batch every kSlots calls, and the copy
-    // kernel with its event are two packets less between two kernels of the consumer stream (a
-    // rank of eight: 27 us from one march to the next, of a 0.19 ms frame).  The twin is intact:
-    // begin() has waited for the slot's previous copy, and nothing else writes it.
-    static const bool always_copy = std::getenv("AVR_ALWAYS_UPLOAD") != nullptr;  // A/B only
-    if (!always_copy && used_ != 0 && used_ == current_->shadow.size() &&
-        std::memcmp(current_->host, current_->shadow.data(), used_) == 0) {
-      // The slot's event is what keeps the host at most kSlots batches ahead of the consumer;
-      // unless the owner bounds the frames in flight itself (set_lean), it is still recorded.
-      if (!lean_) {
-        hip_check(hipEventRecord(current_->done, stream), "hipEventRecord(staging)");
-        current_->pending = true;
-      }
-      return;
-    }
-    if (used_ != 0) {
-      const int status = launch_upload(current_->host_mapped, current_->dev, used_, stream);
-      if (status != AVR_OK) throw HipFailure(g_last_error);
-    }
-    hip_check(hipEventRecord(current_->done, stream), "hipEventRecord(staging)");
-    current_->pending = true;
-    current_->shadow.assign(static_cast<const char*>(current_->host),
-                            static_cast<const char*>(current_->host) + used_);
-  }
-
-  // Blocks until every committed batch has been copied (before the context's stream changes).
-  void drain() {
-    for (Slot& slot : slots_) {
-      if (slot.pending) {
-        wait_event(slot.done, "hipEventQuery(staging)");
-        slot.pending = false;
-      }
-    }
-  }
-
- private:
-  struct Slot {
-    void* dev = nullptr;
-    void* host = nullptr;
-    void* host_mapped = nullptr;  // device address of `host`
-    size_t capacity = 0;
-    hipEvent_t done = nullptr;      // the copy has run: the pinned block may be refilled
-    bool pending = false;
-    std::vector<char> shadow;       // what the device twin holds (host copy of the last batch copied)
-  };
-  bool lean_ = false;
-  int ahead_ = 4;
-  Slot slots_[kSlots];
-  Slot* current_ = nullptr;
-  int next_ = 0;
-  size_t used_ = 0;
-};
-
-// A device buffer that only grows: a call that fits in it re-uses it.
-struct DeviceBuffer {
-  void* data = nullptr;
-  size_t capacity = 0;
-
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  ~DeviceBuffer() { release(); }
-
-  // Room for `bytes`.  Growing waits for `stream` first (`what` names the wait): work queued there
-  // may still use the old block.  Returns whether it grew -- the old contents are then gone.
-  bool reserve(size_t bytes, hipStream_t stream, const char* what, const char* malloc_label) {
-    if (bytes <= capacity) return false;
-    wait_stream(stream, what);
-    release();
-    hip_check(hipMalloc(&data, bytes), malloc_label);
-    capacity = bytes;
-    return true;
-  }
-  void release() {
-    if (data != nullptr) (void)hipFree(data);
-    data = nullptr;
-    capacity = 0;
-  }
-};
-
-}  // namespace
 }  // namespace avr
 
-struct avr_scene {
-  avr_context* ctx = nullptr;
-  std::vector<avr_box> boxes;
-  avr_scalar_transform transform{};
-  // classified volumes (allocated on first use, grow-only; a frame of the same scene never
-  // reallocates): two let the classify pass of frame i+1 overlap the march of frame i, the third
-  // lets it run ahead so that neither stream waits for the other's launch (avr_renderer)
-  avr::DeviceBuffer classified[AVR_CLASSIFIED_SLOTS];
-  int device = 0;
-  // optional re-use of a slot's classified volume across frames (avr_scene_set_classification_cache):
-  // what the classify pass of the slot's current contents depended on
-  bool cache_classification = false;
-  std::vector<uint64_t> classified_key[AVR_CLASSIFIED_SLOTS];
-
-  uint8_t* classified_slot(int slot, size_t bytes, hipStream_t stream) {
-    if (classified[slot].reserve(bytes, stream, "classified_slot", "hipMalloc(classified)")) {
-      classified_key[slot].clear();
-    }
-    return static_cast<uint8_t*>(classified[slot].data);
-  }
-};
-
-struct avr_context {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  avr::StagingRing staging;
-  avr_scene scratch_scene;         // classified storage of avr_paint_box
-  std::vector<avr::MarchItemDev> march_items;  // host scratch of render()
-  std::vector<int32_t> order_rects;            // ... (the boxes' screen rectangles in layer order)
-  int priority = 0;                            // 1: own stream in the highest priority class
-  int march_workgroups_per_cu = 0;             // 0 = uncapped
-  uint32_t classify_lds_pad = 0;               // avr_context_set_classify_lds_reserve
-  bool classify_stream_stores = false;         // context_set_classify_stream_stores
-  bool fold_whole_grid = false;                // context_set_fold_whole_grid
-  uint64_t* march_counters = nullptr;          // diagnostics (avr_context_set_march_counters)
-  int last_only_mode = -2;                     // ... (avr_context_last_march_mode; -2: no march yet)
-  avr::DeviceBuffer max_layers;                // layer of avr_paint_box_max
-  double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
-  avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
-  avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
-  avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
-  avr::DeviceBuffer iso_scratch;               // avr_scene_isosurface's shells and chunk counts
-};
-
+using avr::bind_device;
+using avr::guarded;
+using avr::require;
 
 namespace {
-
-// Runs `body`, mapping exceptions to status codes (no exception crosses the ABI).
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::invalid_argument& e) {
-    avr::set_error(e.what());
-    return AVR_ERR_INVALID_ARGUMENT;
-  } catch (const std::bad_alloc&) {
-    avr::set_error("out of host memory");
-    return AVR_ERR_OUT_OF_MEMORY;
-  } catch (const std::exception& e) {
-    avr::set_error(e.what());
-    return AVR_ERR_RUNTIME;
-  } catch (...) {
-    avr::set_error("unknown failure");
-    return AVR_ERR_RUNTIME;
-  }
-}
-
-void require(bool condition, const char* message) {
-  if (!condition) throw std::invalid_argument(message);
-}
-
-void bind_device(avr_context* ctx) {
-  require(ctx != nullptr, "null context");
-  avr::hip_check(hipSetDevice(ctx->device), "hipSetDevice");
-  if (ctx->stream == nullptr) {  // no external stream was supplied: create the context's own
-    if (ctx->priority != 0) {
-      int least = 0, greatest = 0;  // numerically lower = more urgent
-      avr::hip_check(hipDeviceGetStreamPriorityRange(&least, &greatest), "hipDeviceGetStreamPriorityRange");
-      avr::hip_check(hipStreamCreateWithPriority(&ctx->own_stream, hipStreamNonBlocking, greatest),
-                     "hipStreamCreateWithPriority");
-    } else {
-      avr::hip_check(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking),
-                     "hipStreamCreate");
-    }
-    ctx->stream = ctx->own_stream;
-  }
-}
 
 enum Phase { kClassify = 1, kMarch = 2 };
 constexpr avr::FrameKind kVolume = avr::FrameKind::kVolume;
@@ -1855,66 +1584,6 @@ int avr_scene_histogram(avr_context* ctx, const avr_scene* scene,
   });
 }
 
-// A field of a product over several scenes that share a box list (the box rules themselves are
-// avr_field_boxes.h's).  The five entry points below have one shape: bind the device, refuse null
-// handles and device pointers, then scenes of another context or box count, then make the plan
-// (avr_field_plans.h: every rule on the plain arguments and the boxes), then stage and launch.
-static void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t n_boxes) {
-  require(field->ctx == ctx && field->boxes.size() == n_boxes,
-          "the scenes must belong to the context and hold the same number of boxes");
-}
-
-int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const avr_scene* scene_y,
-                              const avr_scene* scene_s, const double* x_edges, int nx,
-                              const double* y_edges, int ny, int n_levels, uint64_t* cells_dev,
-                              double* sums_dev, uint64_t* totals_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(scene_x != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
-    require(scene_s == nullptr || sums_dev != nullptr, "a summed field needs sums_dev");
-    const size_t n_boxes = scene_x->boxes.size();
-    for (const avr_scene* field : {scene_x, scene_y, scene_s}) {
-      if (field != nullptr) require_field_scene(ctx, field, n_boxes);
-    }
-    const avr::JointHistogramPlan plan = avr::plan_joint_histogram(
-        scene_x->boxes.data(), scene_y != nullptr ? scene_y->boxes.data() : nullptr,
-        scene_s != nullptr ? scene_s->boxes.data() : nullptr, n_boxes, x_edges, nx, y_edges, ny,
-        n_levels);
-    if (plan.tile_begin.back() == 0) return AVR_OK;
-    const size_t n_x = static_cast<size_t>(nx) + 1;
-    const size_t n_y = scene_y != nullptr ? static_cast<size_t>(ny) + 1 : 0;
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::JointBoxDev) +
-                           plan.tile_begin.size() * sizeof(uint32_t) + (n_x + n_y) * sizeof(double), 4);
-    avr::JointHistogramArgs args = plan.args;
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    args.x_edges = ctx->staging.add(x_edges, n_x);
-    args.y_edges = n_y != 0 ? ctx->staging.add(y_edges, n_y) : nullptr;
-    ctx->staging.commit(ctx->stream);
-    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
-    args.sums = scene_s != nullptr ? sums_dev : nullptr;
-    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
-    return avr::launch_joint_histogram(args, scene_y != nullptr, scene_s != nullptr, ctx->stream);
-  });
-}
-
-int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origin[3],
-                    const double du[3], const double dv[3], int width, int height,
-                    const int32_t* global_index, double* value, int8_t* level, int32_t* box) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(scene != nullptr && origin != nullptr && du != nullptr && dv != nullptr &&
-                value != nullptr && level != nullptr && box != nullptr, "null argument");
-    const avr::SlicePlan plan = avr::plan_slice(scene->boxes.data(), scene->boxes.size(),
-                                                global_index, origin, du, dv, width, height);
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::SliceBoxDev), 1);
-    const avr::SliceBoxDev* boxes_dev = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    ctx->staging.commit(ctx->stream);
-    return avr::launch_slice(plan.plane, width, height, boxes_dev,
-                             static_cast<int>(plan.boxes.size()), value, level, box, ctx->stream);
-  });
-}
-
 int avr_slice_outline(avr_context* ctx, const int32_t* box, int width, int height, int red,
                       int green, int blue, uint8_t* rgb8) {
   return guarded([&]() -> int {
@@ -1924,484 +1593,6 @@ int avr_slice_outline(avr_context* ctx, const int32_t* box, int width, int heigh
     require(red >= 0 && red <= 255 && green >= 0 && green <= 255 && blue >= 0 && blue <= 255,
             "colour components must lie in [0, 255]");
     return avr::launch_slice_outline(box, width, height, red, green, blue, rgb8, ctx->stream);
-  });
-}
-
-int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const avr_scene* scene_w,
-                              int axis, const double origin_uv[2], double du, double dv, int width,
-                              int height, const double* level_dl, int n_levels,
-                              double* integral_dev, double* weight_dev, double* length_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(scene_f != nullptr && origin_uv != nullptr && level_dl != nullptr &&
-                integral_dev != nullptr && length_dev != nullptr, "null argument");
-    require((scene_w != nullptr) == (weight_dev != nullptr),
-            "weight_dev is given exactly when scene_w is");
-    const bool weighted = scene_w != nullptr;
-    const size_t n_boxes = scene_f->boxes.size();
-    require_field_scene(ctx, scene_f, n_boxes);
-    if (weighted) require_field_scene(ctx, scene_w, n_boxes);
-    const avr::AxisProjectionPlan plan = avr::plan_axis_projection(
-        scene_f->boxes.data(), weighted ? scene_w->boxes.data() : nullptr, n_boxes, axis, origin_uv,
-        du, dv, width, height, level_dl, n_levels);
-    // the partial planes: S [entries] f64, Wt [entries] f64 (with a weight), n [entries] u32
-    const size_t n_entries = plan.entries;
-    ctx->axis_planes.reserve(n_entries * (weighted ? 20 : 12), ctx->stream,
-                             "avr_scene_axis_projection", "hipMalloc(axis planes)");
-    double* plane_s = static_cast<double*>(ctx->axis_planes.data);
-    double* plane_w = weighted ? plane_s + n_entries : nullptr;
-    uint32_t* plane_n = reinterpret_cast<uint32_t*>(plane_s + (weighted ? 2 : 1) * n_entries);
-
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::AxisBoxDev) +
-                           plan.planes.size() * sizeof(avr::AxisPlaneDev) +
-                           plan.tile_begin.size() * sizeof(uint32_t), 3);
-    avr::AxisReduceArgs reduce{};
-    avr::AxisGatherArgs gather{};
-    reduce.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    gather.boxes = ctx->staging.add(plan.planes.data(), plan.planes.size());
-    reduce.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    ctx->staging.commit(ctx->stream);
-    reduce.n_boxes = static_cast<int32_t>(n_boxes);
-    reduce.n_tiles = plan.tile_begin.back();
-    reduce.plane_s = plane_s;
-    reduce.plane_w = plane_w;
-    reduce.plane_n = plane_n;
-    const int status = avr::launch_axis_reduce(reduce, axis, weighted, ctx->stream);
-    if (status != AVR_OK) return status;
-    gather.n_boxes = static_cast<int32_t>(n_boxes);
-    gather.width = width;
-    gather.height = height;
-    gather.origin_u = origin_uv[0];
-    gather.origin_v = origin_uv[1];
-    gather.du = du;
-    gather.dv = dv;
-    gather.plane_s = plane_s;
-    gather.plane_w = plane_w;
-    gather.plane_n = plane_n;
-    gather.integral = integral_dev;
-    gather.weight = weight_dev;
-    gather.length = length_dev;
-    return avr::launch_axis_gather(gather, ctx->stream);
-  });
-}
-
-int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inputs, avr_scene* out,
-                     const uint32_t* instructions, int n_instructions, const double* constants,
-                     int n_constants, const double* box_origin, const double* level_cell_size,
-                     int n_levels) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(out != nullptr && instructions != nullptr && level_cell_size != nullptr,
-            "null argument");
-    avr::require_derive_input_count(n_inputs);
-    require(n_inputs == 0 || inputs != nullptr, "null argument");
-    require(out->ctx == ctx, "the scenes must belong to the context");
-    const size_t n_boxes = out->boxes.size();
-    const avr_box* input_boxes[avr::kDeriveMaxFields] = {};
-    for (int f = 0; f < n_inputs; ++f) {
-      require(inputs[f] != nullptr, "null argument");
-      require_field_scene(ctx, inputs[f], n_boxes);
-      input_boxes[f] = inputs[f]->boxes.data();
-    }
-    const avr::DerivePlan plan = avr::plan_derive(
-        input_boxes, n_inputs, out->boxes.data(), n_boxes, instructions, n_instructions, constants,
-        n_constants, box_origin, level_cell_size, n_levels);
-    for (auto& key : out->classified_key) key.clear();
-    if (plan.tile_begin.back() == 0) return AVR_OK;
-    avr::DeriveArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::DeriveBoxDev) +
-                           plan.tile_begin.size() * sizeof(uint32_t) + sizeof(plan.program), 3);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    args.program = ctx->staging.add(&plan.program, 1);
-    ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_tiles = plan.tile_begin.back();
-    args.n_fields = n_inputs;
-    args.n_instructions = n_instructions;
-    return avr::launch_derive(args, ctx->stream);
-  });
-}
-
-int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, int axis,
-                       const int32_t* box_index_lo, const int32_t* level_ratio,
-                       const double* level_cell_size, int n_levels) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(in != nullptr && out != nullptr && level_cell_size != nullptr, "null argument");
-    require(out->ctx == ctx, "the scenes must belong to the context");
-    const size_t n_boxes = out->boxes.size();
-    require_field_scene(ctx, in, n_boxes);
-    avr::GradientPlan plan =
-        avr::plan_gradient(in->boxes.data(), out->boxes.data(), n_boxes, axis, box_index_lo,
-                           level_ratio, level_cell_size, n_levels);
-    for (auto& key : out->classified_key) key.clear();
-    if (plan.tile_begin.back() == 0) return AVR_OK;
-    // the face planes: [2][faces] f64, then [2][faces] presence bytes
-    const size_t n_faces = plan.face_begin.back();
-    ctx->gradient_planes.reserve(n_faces * 2 * (sizeof(double) + 1), ctx->stream,
-                                 "avr_scene_gradient", "hipMalloc(gradient planes)");
-    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
-    avr::GradientArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::GradientBoxDev) +
-                           (plan.tile_begin.size() + plan.face_begin.size() +
-                            plan.candidate_begin.size()) * sizeof(uint32_t) +
-                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 6);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    args.face_begin = ctx->staging.add(plan.face_begin.data(), plan.face_begin.size());
-    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
-    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_levels = n_levels;
-    args.n_tiles = plan.tile_begin.back();
-    args.n_faces = static_cast<uint32_t>(n_faces);
-    args.face_value = static_cast<double*>(ctx->gradient_planes.data);
-    args.face_present = reinterpret_cast<uint8_t*>(args.face_value + 2 * n_faces);
-    return avr::launch_gradient(args, axis, ctx->stream);
-  });
-}
-
-int avr_scene_clumps(avr_context* ctx, const avr_scene* in, avr_scene* out, double lower,
-                     double upper, const int32_t* box_index_lo, const int32_t* level_ratio,
-                     int n_levels, uint64_t* count_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(in != nullptr && out != nullptr && count_dev != nullptr, "null argument");
-    require(out->ctx == ctx, "the scenes must belong to the context");
-    const size_t n_boxes = out->boxes.size();
-    require_field_scene(ctx, in, n_boxes);
-    avr::ClumpPlan plan = avr::plan_clumps(in->boxes.data(), out->boxes.data(), n_boxes, lower,
-                                           upper, box_index_lo, level_ratio, n_levels);
-    for (auto& key : out->classified_key) key.clear();
-    avr::hip_check(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), ctx->stream), "hipMemsetAsync");
-    if (plan.tile_begin.back() == 0) return AVR_OK;
-    // the parent entries, padded to whole chunks, then one count per chunk
-    const size_t n_cells = plan.cell_begin.back();
-    const size_t n_chunks = (n_cells + avr::kClumpChunk - 1) / avr::kClumpChunk;
-    ctx->clump_parents.reserve((n_chunks * avr::kClumpChunk + n_chunks) * sizeof(uint32_t),
-                               ctx->stream, "avr_scene_clumps", "hipMalloc(clump parents)");
-    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
-    avr::ClumpArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::ClumpBoxDev) +
-                           (plan.tile_begin.size() + plan.candidate_begin.size()) * sizeof(uint32_t) +
-                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 5);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
-    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_levels = n_levels;
-    args.n_tiles = plan.tile_begin.back();
-    args.n_cells = static_cast<uint32_t>(n_cells);
-    args.n_chunks = static_cast<uint32_t>(n_chunks);
-    args.lower = lower;
-    args.upper = upper;
-    args.parent = static_cast<uint32_t*>(ctx->clump_parents.data);
-    args.chunk_roots = args.parent + n_chunks * avr::kClumpChunk;
-    args.count = reinterpret_cast<unsigned long long*>(count_dev);
-    return avr::launch_clumps(args, ctx->stream);
-  });
-}
-
-int avr_scene_clump_table(avr_context* ctx, const avr_scene* labels, const avr_scene* field,
-                          uint64_t n_clumps, int n_levels, uint64_t* cells_dev, double* sums_dev,
-                          uint64_t* totals_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(labels != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
-    require((field != nullptr) == (sums_dev != nullptr), "sums_dev is given exactly when field is");
-    const size_t n_boxes = labels->boxes.size();
-    require_field_scene(ctx, labels, n_boxes);
-    if (field != nullptr) require_field_scene(ctx, field, n_boxes);
-    const avr::ClumpTablePlan plan = avr::plan_clump_table(
-        labels->boxes.data(), field != nullptr ? field->boxes.data() : nullptr, n_boxes, n_clumps,
-        n_levels);
-    if (plan.tile_begin.back() == 0) return AVR_OK;
-    avr::ClumpTableArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::JointBoxDev) +
-                           plan.tile_begin.size() * sizeof(uint32_t), 2);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.tile_begin = ctx->staging.add(plan.tile_begin.data(), plan.tile_begin.size());
-    ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_tiles = plan.tile_begin.back();
-    args.n_clumps = static_cast<uint32_t>(n_clumps);
-    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
-    args.sums = sums_dev;
-    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
-    return avr::launch_clump_table(args, field != nullptr, ctx->stream);
-  });
-}
-
-int avr_scene_isosurface(avr_context* ctx, const avr_scene* field, const avr_scene* sample,
-                         double value, const int32_t* box_index_lo, const int32_t* level_ratio,
-                         const double* level_cell_size, const double* prob_lo, int n_levels,
-                         uint64_t capacity, double* vertices_dev, uint8_t* levels_dev,
-                         double* samples_dev, uint64_t* counts_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(field != nullptr && level_cell_size != nullptr && prob_lo != nullptr &&
-                counts_dev != nullptr, "null argument");
-    const size_t n_boxes = field->boxes.size();
-    require_field_scene(ctx, field, n_boxes);
-    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
-    avr::IsoPlan plan = avr::plan_isosurface(
-        field->boxes.data(), sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, value,
-        box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, capacity, vertices_dev,
-        levels_dev, samples_dev, counts_dev);
-    avr::hip_check(hipMemsetAsync(counts_dev, 0, 2 * sizeof(uint64_t), ctx->stream),
-                   "hipMemsetAsync");
-    const size_t n_bases = plan.base_begin.back();
-    if (n_bases == 0) return AVR_OK;
-    const bool has_sample = sample != nullptr, emit = capacity > 0;
-    // the shells' values (and sample values), the chunks' offsets, triangles and skipped cubes,
-    // then the shells' code bytes
-    const size_t n_shell = plan.shell_begin.back();
-    const size_t n_chunks = (n_bases + avr::kIsoChunk - 1) / avr::kIsoChunk;
-    const size_t shell_doubles = n_shell * (has_sample ? 2 : 1);
-    ctx->iso_scratch.reserve(shell_doubles * sizeof(double) + n_chunks * 16 + n_shell, ctx->stream,
-                             "avr_scene_isosurface", "hipMalloc(isosurface scratch)");
-    if (plan.candidates.empty()) plan.candidates.push_back(0);  // never read: every range is empty
-    avr::IsoArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::IsoBoxDev) +
-                           (plan.base_begin.size() + plan.candidate_begin.size()) * sizeof(uint32_t) +
-                           plan.shell_begin.size() * sizeof(uint64_t) +
-                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 6);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.shell_begin = ctx->staging.add(plan.shell_begin.data(), plan.shell_begin.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    args.base_begin = ctx->staging.add(plan.base_begin.data(), plan.base_begin.size());
-    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
-    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
-    ctx->staging.commit(ctx->stream);
-    args.n_boxes = static_cast<int32_t>(n_boxes);
-    args.n_levels = n_levels;
-    args.n_bases = static_cast<uint32_t>(n_bases);
-    args.n_chunks = static_cast<uint32_t>(n_chunks);
-    args.n_shell = n_shell;
-    args.value = value;
-    args.capacity = capacity;
-    args.shell_value = static_cast<double*>(ctx->iso_scratch.data);
-    args.shell_sample = has_sample ? args.shell_value + n_shell : nullptr;
-    args.chunk_offset = reinterpret_cast<unsigned long long*>(args.shell_value + shell_doubles);
-    args.chunk_triangles = reinterpret_cast<uint32_t*>(args.chunk_offset + n_chunks);
-    args.chunk_skipped = args.chunk_triangles + n_chunks;
-    args.shell_code = reinterpret_cast<uint8_t*>(args.chunk_skipped + n_chunks);
-    args.counts = reinterpret_cast<unsigned long long*>(counts_dev);
-    args.vertices = vertices_dev;
-    args.levels_out = levels_dev;
-    args.samples = has_sample ? samples_dev : nullptr;
-    return avr::launch_isosurface(args, has_sample, emit, ctx->stream);
-  });
-}
-
-int avr_scene_streamlines(avr_context* ctx, const avr_scene* vx, const avr_scene* vy,
-                          const avr_scene* vz, const avr_scene* sample, const double* seeds_dev,
-                          uint64_t n_seeds, double step, int direction, uint64_t max_steps,
-                          const int32_t* box_index_lo, const int32_t* level_ratio,
-                          const double* level_cell_size, const double* prob_lo, int n_levels,
-                          double* points_dev, double* samples_dev, uint32_t* counts_dev,
-                          uint8_t* status_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(vx != nullptr && vy != nullptr && vz != nullptr && level_cell_size != nullptr &&
-                prob_lo != nullptr, "null argument");
-    const size_t n_boxes = vx->boxes.size();
-    require_field_scene(ctx, vx, n_boxes);
-    require_field_scene(ctx, vy, n_boxes);
-    require_field_scene(ctx, vz, n_boxes);
-    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
-    avr::StreamPlan plan = avr::plan_streamlines(
-        vx->boxes.data(), vy->boxes.data(), vz->boxes.data(),
-        sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, n_seeds, step, direction,
-        max_steps, box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, seeds_dev,
-        points_dev, samples_dev, counts_dev, status_dev);
-    if (n_seeds == 0) return AVR_OK;
-    if (plan.boxes.empty()) plan.boxes.resize(1);          // never read: no block lists it
-    if (plan.block_boxes.empty()) plan.block_boxes.push_back(0);  // never read: every list is empty
-    avr::StreamArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::StreamBoxDev) +
-                           plan.block_begin.size() * sizeof(uint32_t) +
-                           plan.block_boxes.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    args.block_begin = ctx->staging.add(plan.block_begin.data(), plan.block_begin.size());
-    args.block_boxes = ctx->staging.add(plan.block_boxes.data(), plan.block_boxes.size());
-    ctx->staging.commit(ctx->stream);
-    args.locator = plan.locator;
-    args.n_levels = n_levels;
-    args.n_seeds = static_cast<uint32_t>(n_seeds);
-    args.max_steps = static_cast<uint32_t>(max_steps);
-    args.step = step;
-    args.direction = static_cast<double>(direction);
-    args.seeds = seeds_dev;
-    args.points = points_dev;
-    args.samples = sample != nullptr ? samples_dev : nullptr;
-    args.counts = counts_dev;
-    args.status = status_dev;
-    return avr::launch_streamlines(args, sample != nullptr, ctx->stream);
-  });
-}
-
-int avr_scene_covering_grid(avr_context* ctx, const avr_scene* field, int level, const int32_t* lo,
-                            const int32_t* dims, const int32_t* box_index_lo,
-                            const int32_t* level_ratio, int n_levels, double fill,
-                            double* values_dev, double* coverage_dev, int8_t* level_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    require(field != nullptr && lo != nullptr && dims != nullptr && values_dev != nullptr,
-            "null argument");
-    const size_t n_boxes = field->boxes.size();
-    require_field_scene(ctx, field, n_boxes);
-    avr::CoveringGridPlan plan = avr::plan_covering_grid(
-        field->boxes.data(), n_boxes, level, lo, dims, box_index_lo, level_ratio, n_levels,
-        values_dev, coverage_dev, level_dev);
-    if (plan.boxes.empty()) plan.boxes.resize(1);                // never read: no tile lists it
-    if (plan.candidates.empty()) plan.candidates.push_back(0);   // never read: every list is empty
-    avr::CoverArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::CoverBoxDev) +
-                           plan.candidate_begin.size() * sizeof(uint32_t) +
-                           plan.candidates.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    args.candidate_begin = ctx->staging.add(plan.candidate_begin.data(), plan.candidate_begin.size());
-    args.candidates = ctx->staging.add(plan.candidates.data(), plan.candidates.size());
-    ctx->staging.commit(ctx->stream);
-    args.level = level;
-    args.finest = plan.finest;
-    for (int d = 0; d < 3; ++d) args.lo[d] = lo[d];
-    args.nx = dims[0];
-    args.ny = dims[1];
-    args.nz = dims[2];
-    args.n_tiles = static_cast<uint32_t>(plan.candidate_begin.size() - 1);
-    args.fill = fill;
-    args.values = values_dev;
-    args.coverage = coverage_dev;
-    args.cell_level = level_dev;
-    return avr::launch_covering_grid(args, ctx->stream);
-  });
-}
-
-int avr_scene_rays(avr_context* ctx, const avr_scene* field, const double* start_dev,
-                   const double* end_dev, uint64_t n_rays, uint64_t max_trips,
-                   const int32_t* box_index_lo, const int32_t* level_ratio,
-                   const double* level_cell_size, const double* prob_lo, int n_levels,
-                   const int64_t* offsets_dev, uint64_t n_segments, uint32_t* counts_dev,
-                   uint8_t* status_dev, double* span_dev, double* t0_dev, double* t1_dev,
-                   int8_t* level_dev, double* value_dev, double* integral_dev,
-                   double* covered_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    // the scene first, without which nothing can be looked at; every other rule, a null
-    // level_cell_size or prob_lo included, is plan_rays' in its documented order
-    require(field != nullptr, "null argument");
-    const size_t n_boxes = field->boxes.size();
-    require_field_scene(ctx, field, n_boxes);
-    const bool emit = offsets_dev != nullptr;
-    avr::RayPlan plan = avr::plan_rays(
-        field->boxes.data(), n_boxes, n_rays, max_trips, box_index_lo, level_ratio,
-        level_cell_size, prob_lo, n_levels, start_dev, end_dev, offsets_dev,
-        emit ? n_segments : 0, counts_dev, status_dev, span_dev, t0_dev, t1_dev, level_dev,
-        value_dev, integral_dev, covered_dev);
-    if (n_rays == 0) return AVR_OK;
-    if (plan.boxes.empty()) plan.boxes.resize(1);          // never read: no block lists it
-    if (plan.block_boxes.empty()) plan.block_boxes.push_back(0);  // never read: every list is empty
-    avr::RayArgs args{};
-    ctx->staging.begin(plan.boxes.size() * sizeof(avr::CoverBoxDev) +
-                           plan.block_begin.size() * sizeof(uint32_t) +
-                           plan.block_boxes.size() * sizeof(int32_t) + sizeof(plan.levels), 4);
-    args.boxes = ctx->staging.add(plan.boxes.data(), plan.boxes.size());
-    args.levels = ctx->staging.add(&plan.levels, 1);
-    args.block_begin = ctx->staging.add(plan.block_begin.data(), plan.block_begin.size());
-    args.block_boxes = ctx->staging.add(plan.block_boxes.data(), plan.block_boxes.size());
-    ctx->staging.commit(ctx->stream);
-    args.locator = plan.locator;
-    for (int d = 0; d < 3; ++d) {
-      args.bound_lo[d] = plan.bound_lo[d];
-      args.bound_hi[d] = plan.bound_hi[d];
-    }
-    args.n_levels = n_levels;
-    args.n_rays = static_cast<uint32_t>(n_rays);
-    args.max_trips = static_cast<uint32_t>(max_trips);
-    args.start = start_dev;
-    args.end = end_dev;
-    if (emit) {
-      args.offsets = reinterpret_cast<const long long*>(offsets_dev);
-      args.n_segments = n_segments;
-      args.t0 = t0_dev;
-      args.t1 = t1_dev;
-      args.level = level_dev;
-      args.value = value_dev;
-      args.integral = integral_dev;
-      args.covered = covered_dev;
-    } else {
-      args.counts = counts_dev;
-      args.status = status_dev;
-      args.span = span_dev;
-    }
-    return avr::launch_rays(args, emit, ctx->stream);
-  });
-}
-
-int avr_scene_ray_sums(avr_context* ctx, const avr_scene* field, const avr_scene* weight,
-                       const double* start_dev, const double* end_dev, uint64_t n_rays,
-                       uint64_t max_trips, const int32_t* box_index_lo,
-                       const int32_t* level_ratio, const double* level_cell_size,
-                       const double* prob_lo, int n_levels, uint32_t* counts_dev,
-                       uint8_t* status_dev, double* span_dev, double* integral_dev,
-                       double* weight_dev, double* counted_dev, double* covered_dev) {
-  return guarded([&]() -> int {
-    bind_device(ctx);
-    // as avr_scene_rays: the scenes first, every other rule is plan_ray_sums' in its order
-    require(field != nullptr, "null argument");
-    const size_t n_boxes = field->boxes.size();
-    require_field_scene(ctx, field, n_boxes);
-    if (weight != nullptr) require_field_scene(ctx, weight, weight->boxes.size());
-    avr::RaySumsPlan plan = avr::plan_ray_sums(
-        field->boxes.data(), n_boxes, weight != nullptr ? weight->boxes.data() : nullptr,
-        weight != nullptr ? weight->boxes.size() : 0, n_rays, max_trips, box_index_lo,
-        level_ratio, level_cell_size, prob_lo, n_levels, start_dev, end_dev, counts_dev,
-        status_dev, span_dev, integral_dev, weight_dev, counted_dev, covered_dev);
-    if (n_rays == 0) return AVR_OK;
-    avr::RayPlan& walk = plan.walk;
-    if (walk.boxes.empty()) walk.boxes.resize(1);          // never read: no block lists it
-    if (walk.block_boxes.empty()) walk.block_boxes.push_back(0);  // never read: every list is empty
-    if (weight != nullptr && plan.weight_boxes.empty()) plan.weight_boxes.resize(1);  // never read
-    avr::RayArgs args{};
-    ctx->staging.begin((walk.boxes.size() + plan.weight_boxes.size()) * sizeof(avr::CoverBoxDev) +
-                           walk.block_begin.size() * sizeof(uint32_t) +
-                           walk.block_boxes.size() * sizeof(int32_t) + sizeof(walk.levels), 5);
-    args.boxes = ctx->staging.add(walk.boxes.data(), walk.boxes.size());
-    if (weight != nullptr) {
-      args.weight_boxes = ctx->staging.add(plan.weight_boxes.data(), plan.weight_boxes.size());
-    }
-    args.levels = ctx->staging.add(&walk.levels, 1);
-    args.block_begin = ctx->staging.add(walk.block_begin.data(), walk.block_begin.size());
-    args.block_boxes = ctx->staging.add(walk.block_boxes.data(), walk.block_boxes.size());
-    ctx->staging.commit(ctx->stream);
-    args.locator = walk.locator;
-    for (int d = 0; d < 3; ++d) {
-      args.bound_lo[d] = walk.bound_lo[d];
-      args.bound_hi[d] = walk.bound_hi[d];
-    }
-    args.n_levels = n_levels;
-    args.n_rays = static_cast<uint32_t>(n_rays);
-    args.max_trips = static_cast<uint32_t>(max_trips);
-    args.start = start_dev;
-    args.end = end_dev;
-    args.counts = counts_dev;
-    args.status = status_dev;
-    args.span = span_dev;
-    args.integral = integral_dev;
-    args.weight = weight_dev;
-    args.counted = counted_dev;
-    args.covered = covered_dev;
-    return avr::launch_ray_sums(args, ctx->stream);
   });
 }
 

@@ -8,6 +8,18 @@
 // std::invalid_argument with the message the C ABI reports, and fills vectors and PODs that the
 // entry point stages (tests/cxx/field_plans_test.cpp).  Pointers the ABI refuses as "null
 // argument" whatever the other arguments are have been checked by the entry point.
+//
+// What a plan hands to its entry point (csrc/avr_field_products.cpp), one rule for every product:
+//  - `args`, the struct the kernel is launched with.  The plan fills every field that is not a
+//    device address -- counts, sizes, bounds, the locator, the image window -- and leaves every
+//    address null; the entry point copies it and fills only addresses: the staged tables, the
+//    context's scratch block and the caller's device arrays.
+//  - visit_tables(args..., visit): the tables the call stages, named once, as visit(where in args
+//    the table's device address goes, the host table, its count) in the order they are staged.  The
+//    stager runs it twice, to size the batch (StagingSize) and to fill it; a table of count 0 is
+//    staged as one value-initialised element that nothing reads, so a plan is never padded.
+//  - `scratch` (where a product has a scratch block): the block's total bytes and each part's
+//    byte offset, in part order.
 #ifndef AVR_FIELD_PLANS_H
 #define AVR_FIELD_PLANS_H
 
@@ -26,6 +38,33 @@
 
 namespace avr {
 
+// The sizing pass of the stager over a plan's visit_tables: what StagingRing::begin is given.
+struct StagingSize {
+  size_t bytes = 0;
+  int items = 0;
+  template <class T>
+  void operator()(const T** /*device*/, const T* /*host*/, size_t count) {
+    bytes += std::max<size_t>(count, 1) * sizeof(T);
+    ++items;
+  }
+};
+
+// One part of a context scratch block: `bytes` from byte `offset` of the block on.  An optional
+// part that the call does without is not present: it has no bytes and its address stays null.
+struct ScratchPart {
+  size_t offset = 0, bytes = 0;
+  bool present = false;
+};
+// The next part of a block of `*total` bytes so far, behind the parts before it.
+inline ScratchPart next_scratch_part(size_t* total, size_t bytes, bool present = true) {
+  ScratchPart part;
+  part.offset = *total;
+  part.bytes = present ? bytes : 0;
+  part.present = present;
+  *total += part.bytes;
+  return part;
+}
+
 inline void require_image_size(int width, int height) {
   require_box(width > 0 && height > 0, "image width and height must be positive");
   require_box(static_cast<int64_t>(width) * height <= (int64_t{1} << 31) - 1,
@@ -33,9 +72,20 @@ inline void require_image_size(int width, int height) {
 }
 
 // ---- slice images -------------------------------------------------------------------------
+// What launch_slice takes besides the plane: the slice kernel has no argument struct of its own.
+struct SliceArgs {
+  const SliceBoxDev* boxes;
+  int32_t n_boxes;
+  int32_t width, height;
+};
 struct SlicePlan {
   SlicePlaneDev plane;
   std::vector<SliceBoxDev> boxes;  // a box without cells stays zeroed but for index and level
+  SliceArgs args{};
+  template <class Visit>
+  void visit_tables(SliceArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+  }
 };
 // global_index (may be null): what the box image holds for box b; by default b.
 inline SlicePlan plan_slice(const avr_box* boxes, size_t n_boxes, const int32_t* global_index,
@@ -69,6 +119,9 @@ inline SlicePlan plan_slice(const avr_box* boxes, size_t n_boxes, const int32_t*
     dev.jstride = view.jstride;
     dev.kstride = view.kstride;
   }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.width = width;
+  plan.args.height = height;
   return plan;
 }
 
@@ -91,7 +144,15 @@ inline double joint_histogram_axis(const double* edges, int n, const char* axis)
 struct JointHistogramPlan {
   std::vector<JointBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
-  JointHistogramArgs args;  // the counts, bounds and scales; its device pointers are left null
+  std::vector<double> x_edges, y_edges;  // nx + 1 and ny + 1 (empty without scene_y)
+  JointHistogramArgs args{};
+  template <class Visit>
+  void visit_tables(JointHistogramArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->x_edges, x_edges.data(), x_edges.size());
+    if (!y_edges.empty()) visit(&to->y_edges, y_edges.data(), y_edges.size());
+  }
 };
 // y and s (may be null): the boxes of the second axis' field and of the summed field; an absent
 // field repeats x.
@@ -99,7 +160,6 @@ inline JointHistogramPlan plan_joint_histogram(const avr_box* x, const avr_box* 
                                                size_t n_boxes, const double* x_edges, int nx,
                                                const double* y_edges, int ny, int n_levels) {
   JointHistogramPlan plan;
-  plan.args = JointHistogramArgs{};
   plan.args.x_scale = joint_histogram_axis(x_edges, nx, "x");
   if (y != nullptr) {
     plan.args.y_scale = joint_histogram_axis(y_edges, ny, "y");
@@ -138,19 +198,42 @@ inline JointHistogramPlan plan_joint_histogram(const avr_box* x, const avr_box* 
   plan.args.ny = ny;
   plan.args.x_lo = x_edges[0];
   plan.args.x_hi = x_edges[nx];
+  plan.x_edges.assign(x_edges, x_edges + nx + 1);
   if (y != nullptr) {
     plan.args.y_lo = y_edges[0];
     plan.args.y_hi = y_edges[ny];
+    plan.y_edges.assign(y_edges, y_edges + ny + 1);
   }
   return plan;
 }
 
 // ---- on-axis projection -------------------------------------------------------------------
+// The partial planes: S [entries] f64, Wt [entries] f64 (with a weight), n [entries] u32.
+struct AxisScratch {
+  ScratchPart s, w, n;
+  size_t total = 0;
+};
+inline AxisScratch axis_scratch(size_t entries, bool weighted) {
+  AxisScratch scratch;
+  scratch.s = next_scratch_part(&scratch.total, entries * sizeof(double));
+  scratch.w = next_scratch_part(&scratch.total, entries * sizeof(double), weighted);
+  scratch.n = next_scratch_part(&scratch.total, entries * sizeof(uint32_t));
+  return scratch;
+}
 struct AxisProjectionPlan {
   std::vector<AxisBoxDev> boxes;     // as the reduction reads them
   std::vector<AxisPlaneDev> planes;  // as the gather reads them
   std::vector<uint32_t> tile_begin;
   uint32_t entries = 0;  // of the partial planes, all boxes: columns x segments, below 2^31
+  AxisReduceArgs reduce{};
+  AxisGatherArgs gather{};
+  AxisScratch scratch;
+  template <class Visit>
+  void visit_tables(AxisReduceArgs* to_reduce, AxisGatherArgs* to_gather, Visit&& visit) const {
+    visit(&to_reduce->boxes, boxes.data(), boxes.size());
+    visit(&to_gather->boxes, planes.data(), planes.size());
+    visit(&to_reduce->tile_begin, tile_begin.data(), tile_begin.size());
+  }
 };
 // w (may be null): the boxes of the weight field; without one it repeats f.
 inline AxisProjectionPlan plan_axis_projection(const avr_box* f, const avr_box* w, size_t n_boxes,
@@ -212,6 +295,15 @@ inline AxisProjectionPlan plan_axis_projection(const avr_box* f, const avr_box* 
     require_box(entries < (uint64_t{1} << 31), "scene has too many cells");
   }
   plan.entries = static_cast<uint32_t>(entries);
+  plan.scratch = axis_scratch(plan.entries, w != nullptr);
+  plan.reduce.n_boxes = plan.gather.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.reduce.n_tiles = plan.tile_begin.back();
+  plan.gather.width = width;
+  plan.gather.height = height;
+  plan.gather.origin_u = origin_uv[0];
+  plan.gather.origin_v = origin_uv[1];
+  plan.gather.du = du;
+  plan.gather.dv = dv;
   return plan;
 }
 
@@ -285,6 +377,13 @@ struct DerivePlan {
   std::vector<DeriveBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
   DeriveProgramDev program;
+  DeriveArgs args{};
+  template <class Visit>
+  void visit_tables(DeriveArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->program, &program, 1);
+  }
 };
 // inputs: n_inputs box lists of n_boxes boxes each; out: the boxes written, the reference of the
 // box rules.
@@ -349,6 +448,10 @@ inline DerivePlan plan_derive(const avr_box* const* inputs, int n_inputs, const 
   }
   std::memcpy(plan.program.cell_size, level_cell_size,
               static_cast<size_t>(n_levels) * 3 * sizeof(double));
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_fields = n_inputs;
+  plan.args.n_instructions = n_instructions;
   return plan;
 }
 
@@ -485,6 +588,17 @@ inline void append_face_candidates(const std::vector<Box>& boxes,
 }
 
 // ---- gradient fields ----------------------------------------------------------------------
+// The face planes: [2][faces] f64, then [2][faces] presence bytes.
+struct GradientScratch {
+  ScratchPart face_value, face_present;
+  size_t total = 0;
+};
+inline GradientScratch gradient_scratch(size_t faces) {
+  GradientScratch scratch;
+  scratch.face_value = next_scratch_part(&scratch.total, faces * 2 * sizeof(double));
+  scratch.face_present = next_scratch_part(&scratch.total, faces * 2);
+  return scratch;
+}
 struct GradientPlan {
   std::vector<GradientBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
@@ -493,6 +607,17 @@ struct GradientPlan {
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;   // empty when no face has a neighbour
   LevelRatiosDev levels;
+  GradientArgs args{};
+  GradientScratch scratch;
+  template <class Visit>
+  void visit_tables(GradientArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->face_begin, face_begin.data(), face_begin.size());
+    visit(&to->candidate_begin, candidate_begin.data(), candidate_begin.size());
+    visit(&to->candidates, candidates.data(), candidates.size());
+    visit(&to->levels, &levels, 1);
+  }
 };
 // box_index_lo: per box the index of its first cell in its level's index space (3 per box);
 // level_ratio[l]: level l -> l + 1.
@@ -565,10 +690,26 @@ inline GradientPlan plan_gradient(const avr_box* in, const avr_box* out, size_t 
       plan.candidate_begin.push_back(static_cast<uint32_t>(candidates.size()));
     }
   }
+  plan.scratch = gradient_scratch(plan.face_begin.back());
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_levels = n_levels;
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_faces = plan.face_begin.back();
   return plan;
 }
 
 // ---- clumps -------------------------------------------------------------------------------
+// The parent entries, padded to whole chunks, then one count per chunk.
+struct ClumpScratch {
+  ScratchPart parent, chunk_roots;
+  size_t total = 0;
+};
+inline ClumpScratch clump_scratch(size_t chunks) {
+  ClumpScratch scratch;
+  scratch.parent = next_scratch_part(&scratch.total, chunks * kClumpChunk * sizeof(uint32_t));
+  scratch.chunk_roots = next_scratch_part(&scratch.total, chunks * sizeof(uint32_t));
+  return scratch;
+}
 struct ClumpPlan {
   std::vector<ClumpBoxDev> boxes;
   std::vector<uint32_t> tile_begin;
@@ -578,6 +719,16 @@ struct ClumpPlan {
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;   // empty when no face has a neighbour
   LevelRatiosDev levels;
+  ClumpArgs args{};
+  ClumpScratch scratch;
+  template <class Visit>
+  void visit_tables(ClumpArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->candidate_begin, candidate_begin.data(), candidate_begin.size());
+    visit(&to->candidates, candidates.data(), candidates.size());
+    visit(&to->levels, &levels, 1);
+  }
 };
 // box_index_lo and level_ratio as plan_gradient takes them.  The rules, in this order: the bounds,
 // n_levels, the box rules (the input is the reference), the ratios, the index ranges, boxes of one
@@ -643,12 +794,26 @@ inline ClumpPlan plan_clumps(const avr_box* in, const avr_box* out, size_t n_box
       plan.candidate_begin.push_back(static_cast<uint32_t>(plan.candidates.size()));
     }
   }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_levels = n_levels;
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_cells = plan.cell_begin.back();
+  plan.args.n_chunks = (plan.args.n_cells + kClumpChunk - 1) / kClumpChunk;
+  plan.args.lower = lower;
+  plan.args.upper = upper;
+  plan.scratch = clump_scratch(plan.args.n_chunks);
   return plan;
 }
 
 struct ClumpTablePlan {
   std::vector<JointBoxDev> boxes;  // field 0: the labels; field 1: the summed field, or the labels
   std::vector<uint32_t> tile_begin;
+  ClumpTableArgs args{};
+  template <class Visit>
+  void visit_tables(ClumpTableArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+  }
 };
 // field (may be null): the boxes of the summed field.
 inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* field, size_t n_boxes,
@@ -682,10 +847,29 @@ inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* fie
     }
     append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
   }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_clumps = static_cast<uint32_t>(n_clumps);
   return plan;
 }
 
 // ---- isosurfaces --------------------------------------------------------------------------
+// The shells' values (and sample values), the chunks' offsets, triangles and skipped cubes, then
+// the shells' code bytes.
+struct IsoScratch {
+  ScratchPart shell_value, shell_sample, chunk_offset, chunk_triangles, chunk_skipped, shell_code;
+  size_t total = 0;
+};
+inline IsoScratch iso_scratch(size_t shell, size_t chunks, bool has_sample) {
+  IsoScratch scratch;
+  scratch.shell_value = next_scratch_part(&scratch.total, shell * sizeof(double));
+  scratch.shell_sample = next_scratch_part(&scratch.total, shell * sizeof(double), has_sample);
+  scratch.chunk_offset = next_scratch_part(&scratch.total, chunks * sizeof(unsigned long long));
+  scratch.chunk_triangles = next_scratch_part(&scratch.total, chunks * sizeof(uint32_t));
+  scratch.chunk_skipped = next_scratch_part(&scratch.total, chunks * sizeof(uint32_t));
+  scratch.shell_code = next_scratch_part(&scratch.total, shell);
+  return scratch;
+}
 struct IsoPlan {
   std::vector<IsoBoxDev> boxes;
   std::vector<uint32_t> base_begin;   // n_boxes + 1: prefix sum of the boxes' cube bases
@@ -695,6 +879,17 @@ struct IsoPlan {
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;    // empty when no box has a neighbour
   IsoLevelsDev levels;
+  IsoArgs args{};
+  IsoScratch scratch;
+  template <class Visit>
+  void visit_tables(IsoArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->shell_begin, shell_begin.data(), shell_begin.size());
+    visit(&to->levels, &levels, 1);
+    visit(&to->base_begin, base_begin.data(), base_begin.size());
+    visit(&to->candidate_begin, candidate_begin.data(), candidate_begin.size());
+    visit(&to->candidates, candidates.data(), candidates.size());
+  }
 };
 // sample (may be null): the boxes of the sample field.  box_index_lo and level_ratio as
 // plan_gradient takes them; level_cell_size: (dx, dy, dz) per level; prob_lo: three values.  The
@@ -791,6 +986,14 @@ inline IsoPlan plan_isosurface(const avr_box* field, const avr_box* sample, size
     }
     plan.candidate_begin.push_back(static_cast<uint32_t>(plan.candidates.size()));
   }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_levels = n_levels;
+  plan.args.n_bases = plan.base_begin.back();
+  plan.args.n_chunks = (plan.args.n_bases + kIsoChunk - 1) / kIsoChunk;
+  plan.args.n_shell = plan.shell_begin.back();
+  plan.args.value = value;
+  plan.args.capacity = capacity;
+  plan.scratch = iso_scratch(plan.args.n_shell, plan.args.n_chunks, sample != nullptr);
   return plan;
 }
 
@@ -803,6 +1006,14 @@ struct StreamPlan {
   StreamLocatorDev locator;
   std::vector<uint32_t> block_begin;  // blocks + 1 ({0} for a scene without cells)
   std::vector<int32_t> block_boxes;
+  StreamArgs args{};
+  template <class Visit>
+  void visit_tables(StreamArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->levels, &levels, 1);
+    visit(&to->block_begin, block_begin.data(), block_begin.size());
+    visit(&to->block_boxes, block_boxes.data(), block_boxes.size());
+  }
 };
 // The blocks of the locator: the smallest power-of-two side that leaves at most `limit` blocks over
 // the level-0 index range [lo, hi].
@@ -984,6 +1195,12 @@ inline StreamPlan plan_streamlines(const avr_box* vx, const avr_box* vy, const a
   }
   build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator, &plan.block_begin,
                       &plan.block_boxes);
+  plan.args.locator = plan.locator;
+  plan.args.n_levels = n_levels;
+  plan.args.n_seeds = static_cast<uint32_t>(n_seeds);
+  plan.args.max_steps = static_cast<uint32_t>(max_steps);
+  plan.args.step = step;
+  plan.args.direction = static_cast<double>(direction);
   return plan;
 }
 
@@ -1081,10 +1298,19 @@ struct CoveringGridPlan {
   // CSR over the output's tiles (tile_candidate_lists): candidate_begin has tiles + 1 entries
   std::vector<uint32_t> candidate_begin;
   std::vector<int32_t> candidates;  // empty when no box meets the region
+  CoverArgs args{};
+  template <class Visit>
+  void visit_tables(CoverArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->levels, &levels, 1);
+    visit(&to->candidate_begin, candidate_begin.data(), candidate_begin.size());
+    visit(&to->candidates, candidates.data(), candidates.size());
+  }
 };
 // The field resampled to the cells [lo, lo + dims) of level `level` ("Covering
 // grid").  box_index_lo and level_ratio as plan_gradient takes them; n_levels counts the levels up
-// to the finer of `level` and the finest loaded one.  values, coverage and cell_level are device
+// to the finer of `level` and the finest loaded one; `fill` is what a cell no box covers gets (any
+// value, NaN included).  values, coverage and cell_level are device
 // arrays of dims[0] * dims[1] * dims[2] entries (f64, f64, i8); coverage and cell_level may be
 // null, values has been checked by the entry point.  The rules, in this order: n_levels, level,
 // null arrays, the box rules, the ratios, the index ranges, boxes of one level apart in index
@@ -1093,7 +1319,7 @@ struct CoveringGridPlan {
 inline CoveringGridPlan plan_covering_grid(const avr_box* field, size_t n_boxes, int level,
                                            const int32_t lo[3], const int32_t dims[3],
                                            const int32_t* box_index_lo,
-                                           const int32_t* level_ratio, int n_levels,
+                                           const int32_t* level_ratio, int n_levels, double fill,
                                            const void* values, const void* coverage,
                                            const void* cell_level) {
   require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
@@ -1162,6 +1388,14 @@ inline CoveringGridPlan plan_covering_grid(const avr_box* field, size_t n_boxes,
   }
   tile_candidate_lists(boxes, regions, levels.ratio, level, output, &plan.candidate_begin,
                        &plan.candidates);
+  plan.args.level = level;
+  plan.args.finest = plan.finest;
+  for (int d = 0; d < 3; ++d) plan.args.lo[d] = lo[d];
+  plan.args.nx = dims[0];
+  plan.args.ny = dims[1];
+  plan.args.nz = dims[2];
+  plan.args.n_tiles = static_cast<uint32_t>(plan.candidate_begin.size() - 1);
+  plan.args.fill = fill;
   return plan;
 }
 
@@ -1174,6 +1408,19 @@ struct RayPlan {
   std::vector<uint32_t> block_begin;  // blocks + 1 ({0} for a scene without cells)
   std::vector<int32_t> block_boxes;
   int32_t bound_lo[3] = {0, 0, 0}, bound_hi[3] = {-1, -1, -1};
+  RayArgs args{};
+  template <class Visit>
+  void visit_tables(RayArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit_walk_tables(to, visit);
+  }
+  // ... but for the boxes: what the per-ray sums stage behind their own
+  template <class Visit>
+  void visit_walk_tables(RayArgs* to, Visit&& visit) const {
+    visit(&to->levels, &levels, 1);
+    visit(&to->block_begin, block_begin.data(), block_begin.size());
+    visit(&to->block_boxes, block_boxes.data(), block_boxes.size());
+  }
 };
 // The leaf cells that n_rays segments start[s] -> end[s] cross ("Rays").  box_index_lo,
 // level_ratio, level_cell_size and prob_lo as plan_isosurface takes them.  start, end: device
@@ -1274,19 +1521,27 @@ inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const avr_box
                            "an output array or the rays overlap an input box's cells");
   }
   IndexRegion bound;
-  if (!build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator,
-                           &plan.block_begin, &plan.block_boxes, &bound)) {
-    return plan;
+  if (build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator,
+                          &plan.block_begin, &plan.block_boxes, &bound)) {
+    // an absent cell has the finest level's geometry wherever it lies in [Blo, Bhi]: the kernel's
+    // 32-bit indices, one step past a cell included, and f64(index) stay exact
+    const int64_t limit = int64_t{1} << 30, up = level_factor(levels.ratio, 0, n_levels - 1);
+    for (int d = 0; d < 3; ++d) {
+      require_box(bound.lo[d] * up >= -limit && (bound.hi[d] + 1) * up <= limit,
+                  "the scene's bounding box leaves [-2^30, 2^30] at the finest level");
+      plan.bound_lo[d] = static_cast<int32_t>(bound.lo[d]);
+      plan.bound_hi[d] = static_cast<int32_t>(bound.hi[d]);
+    }
   }
-  // an absent cell has the finest level's geometry wherever it lies in [Blo, Bhi]: the kernel's
-  // 32-bit indices, one step past a cell included, and f64(index) stay exact
-  const int64_t limit = int64_t{1} << 30, up = level_factor(levels.ratio, 0, n_levels - 1);
+  plan.args.locator = plan.locator;
   for (int d = 0; d < 3; ++d) {
-    require_box(bound.lo[d] * up >= -limit && (bound.hi[d] + 1) * up <= limit,
-                "the scene's bounding box leaves [-2^30, 2^30] at the finest level");
-    plan.bound_lo[d] = static_cast<int32_t>(bound.lo[d]);
-    plan.bound_hi[d] = static_cast<int32_t>(bound.hi[d]);
+    plan.args.bound_lo[d] = plan.bound_lo[d];
+    plan.args.bound_hi[d] = plan.bound_hi[d];
   }
+  plan.args.n_levels = n_levels;
+  plan.args.n_rays = static_cast<uint32_t>(n_rays);
+  plan.args.max_trips = static_cast<uint32_t>(max_trips);
+  plan.args.n_segments = n_segments;
   return plan;
 }
 
@@ -1324,15 +1579,24 @@ inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, 
       append_byte_range(&arrays, span, n_rays * 2 * sizeof(double));
     }
   }
-  return plan_ray_walk(field, n_boxes, nullptr, 0, n_rays, max_trips, n_segments, box_index_lo,
-                       level_ratio, level_cell_size, prob_lo, n_levels, present, arrays,
-                       max_entries, nullptr);
+  RayPlan plan = plan_ray_walk(field, n_boxes, nullptr, 0, n_rays, max_trips, n_segments,
+                               box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels,
+                               present, arrays, max_entries, nullptr);
+  if (!emit) plan.args.n_segments = 0;  // the count pass has no packed arrays
+  return plan;
 }
 
 // ---- per-ray sums ("Off-axis projection") --------------------------------------
 struct RaySumsPlan {
-  RayPlan walk;                            // plan_rays' tables, entry for entry
+  RayPlan walk;                            // plan_rays' tables, entry for entry; its args launch
   std::vector<CoverBoxDev> weight_boxes;   // empty without a weight scene
+  bool weighted = false;
+  template <class Visit>
+  void visit_tables(RayArgs* to, Visit&& visit) const {
+    visit(&to->boxes, walk.boxes.data(), walk.boxes.size());
+    if (weighted) visit(&to->weight_boxes, weight_boxes.data(), weight_boxes.size());
+    walk.visit_walk_tables(to, visit);
+  }
 };
 // The sums of the one walk, per ray: plan_rays' rules in plan_rays' order with the same messages
 // (there is no n_segments), the same locator, and the weight rules (plan_ray_walk) after the
@@ -1366,6 +1630,7 @@ inline RaySumsPlan plan_ray_sums(const avr_box* field, size_t n_boxes, const avr
     append_byte_range(&arrays, covered, n_rays * sizeof(double));
   }
   RaySumsPlan plan;
+  plan.weighted = weight != nullptr;
   plan.walk = plan_ray_walk(field, n_boxes, weight, n_weight_boxes, n_rays, max_trips, 0,
                             box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, present,
                             arrays, max_entries, &plan.weight_boxes);

@@ -1,0 +1,414 @@
+// C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
+// projections, derived fields, gradient fields, clumps and their table, isosurfaces, streamlines,
+// covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
+// stages in which order, the counts it launches with and its scratch layout are its plan's
+// (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.
+#include "avr_context.h"
+#include "avr_field_plans.h"
+
+using avr::bind_device;
+using avr::guarded;
+using avr::require;
+
+namespace {
+
+// The second pass over a plan's visit_tables: adds every table to the batch that StagingSize sized
+// and writes where it will be on the device into the launch arguments.
+struct StagingFill {
+  avr::StagingRing* ring;
+  template <class T>
+  void operator()(const T** device, const T* host, size_t count) const {
+    static const T kUnread{};  // an empty table's one element: no count or range leads to it
+    *device = count != 0 ? ring->add(host, count) : ring->add(&kUnread, 1);
+  }
+};
+
+// Stages the tables of `plan` in one batch on the context's stream and sets their addresses in
+// `args` (the arguments visit_tables takes).
+template <class Plan, class... Args>
+void stage_tables(avr_context* ctx, const Plan& plan, Args*... args) {
+  avr::StagingSize size;
+  plan.visit_tables(args..., size);
+  ctx->staging.begin(size.bytes, size.items);
+  plan.visit_tables(args..., StagingFill{&ctx->staging});
+  ctx->staging.commit(ctx->stream);
+}
+
+// Where a part of a context scratch block lies; null for an optional part the call does without.
+template <class T>
+T* scratch_part(const avr::DeviceBuffer& block, const avr::ScratchPart& part) {
+  if (!part.present) return nullptr;
+  return reinterpret_cast<T*>(static_cast<char*>(block.data) + part.offset);
+}
+
+// A field of a product over several scenes that share a box list (the box rules themselves are
+// avr_field_boxes.h's).
+void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t n_boxes) {
+  require(field->ctx == ctx && field->boxes.size() == n_boxes,
+          "the scenes must belong to the context and hold the same number of boxes");
+}
+
+}  // namespace
+
+// The twelve entry points below read the same way, top to bottom: bind the device; refuse null
+// handles and device pointers; refuse scenes of another context or box count (require_field_scene);
+// make the plan, which holds every rule on the plain arguments and the boxes; the call's side
+// effects on its outputs (a written scene's classification keys, a cleared count); return where
+// there is nothing to launch; copy the plan's launch arguments, stage its tables (stage_tables)
+// and set the remaining addresses -- the scratch block's parts, the caller's arrays; launch.  The
+// plan fills every launch argument that is not a device address, the entry point only addresses.
+extern "C" {
+
+int avr_scene_joint_histogram(avr_context* ctx, const avr_scene* scene_x, const avr_scene* scene_y,
+                              const avr_scene* scene_s, const double* x_edges, int nx,
+                              const double* y_edges, int ny, int n_levels, uint64_t* cells_dev,
+                              double* sums_dev, uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene_x != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
+    require(scene_s == nullptr || sums_dev != nullptr, "a summed field needs sums_dev");
+    const size_t n_boxes = scene_x->boxes.size();
+    for (const avr_scene* field : {scene_x, scene_y, scene_s}) {
+      if (field != nullptr) require_field_scene(ctx, field, n_boxes);
+    }
+    const avr::JointHistogramPlan plan = avr::plan_joint_histogram(
+        scene_x->boxes.data(), scene_y != nullptr ? scene_y->boxes.data() : nullptr,
+        scene_s != nullptr ? scene_s->boxes.data() : nullptr, n_boxes, x_edges, nx, y_edges, ny,
+        n_levels);
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::JointHistogramArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
+    args.sums = scene_s != nullptr ? sums_dev : nullptr;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_joint_histogram(args, scene_y != nullptr, scene_s != nullptr, ctx->stream);
+  });
+}
+
+int avr_slice_scene(avr_context* ctx, const avr_scene* scene, const double origin[3],
+                    const double du[3], const double dv[3], int width, int height,
+                    const int32_t* global_index, double* value, int8_t* level, int32_t* box) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene != nullptr && origin != nullptr && du != nullptr && dv != nullptr &&
+                value != nullptr && level != nullptr && box != nullptr, "null argument");
+    const avr::SlicePlan plan = avr::plan_slice(scene->boxes.data(), scene->boxes.size(),
+                                                global_index, origin, du, dv, width, height);
+    avr::SliceArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    return avr::launch_slice(plan.plane, args.width, args.height, args.boxes, args.n_boxes, value,
+                             level, box, ctx->stream);
+  });
+}
+
+int avr_scene_axis_projection(avr_context* ctx, const avr_scene* scene_f, const avr_scene* scene_w,
+                              int axis, const double origin_uv[2], double du, double dv, int width,
+                              int height, const double* level_dl, int n_levels,
+                              double* integral_dev, double* weight_dev, double* length_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene_f != nullptr && origin_uv != nullptr && level_dl != nullptr &&
+                integral_dev != nullptr && length_dev != nullptr, "null argument");
+    require((scene_w != nullptr) == (weight_dev != nullptr),
+            "weight_dev is given exactly when scene_w is");
+    const bool weighted = scene_w != nullptr;
+    const size_t n_boxes = scene_f->boxes.size();
+    require_field_scene(ctx, scene_f, n_boxes);
+    if (weighted) require_field_scene(ctx, scene_w, n_boxes);
+    const avr::AxisProjectionPlan plan = avr::plan_axis_projection(
+        scene_f->boxes.data(), weighted ? scene_w->boxes.data() : nullptr, n_boxes, axis, origin_uv,
+        du, dv, width, height, level_dl, n_levels);
+    ctx->axis_planes.reserve(plan.scratch.total, ctx->stream, "avr_scene_axis_projection",
+                             "hipMalloc(axis planes)");
+    avr::AxisReduceArgs reduce = plan.reduce;
+    avr::AxisGatherArgs gather = plan.gather;
+    stage_tables(ctx, plan, &reduce, &gather);
+    reduce.plane_s = scratch_part<double>(ctx->axis_planes, plan.scratch.s);
+    reduce.plane_w = scratch_part<double>(ctx->axis_planes, plan.scratch.w);
+    reduce.plane_n = scratch_part<uint32_t>(ctx->axis_planes, plan.scratch.n);
+    const int status = avr::launch_axis_reduce(reduce, axis, weighted, ctx->stream);
+    if (status != AVR_OK) return status;
+    gather.plane_s = reduce.plane_s;
+    gather.plane_w = reduce.plane_w;
+    gather.plane_n = reduce.plane_n;
+    gather.integral = integral_dev;
+    gather.weight = weight_dev;
+    gather.length = length_dev;
+    return avr::launch_axis_gather(gather, ctx->stream);
+  });
+}
+
+int avr_scene_derive(avr_context* ctx, const avr_scene* const* inputs, int n_inputs, avr_scene* out,
+                     const uint32_t* instructions, int n_instructions, const double* constants,
+                     int n_constants, const double* box_origin, const double* level_cell_size,
+                     int n_levels) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(out != nullptr && instructions != nullptr && level_cell_size != nullptr,
+            "null argument");
+    avr::require_derive_input_count(n_inputs);
+    require(n_inputs == 0 || inputs != nullptr, "null argument");
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    const avr_box* input_boxes[avr::kDeriveMaxFields] = {};
+    for (int f = 0; f < n_inputs; ++f) {
+      require(inputs[f] != nullptr, "null argument");
+      require_field_scene(ctx, inputs[f], n_boxes);
+      input_boxes[f] = inputs[f]->boxes.data();
+    }
+    const avr::DerivePlan plan = avr::plan_derive(
+        input_boxes, n_inputs, out->boxes.data(), n_boxes, instructions, n_instructions, constants,
+        n_constants, box_origin, level_cell_size, n_levels);
+    for (auto& key : out->classified_key) key.clear();
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::DeriveArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    return avr::launch_derive(args, ctx->stream);
+  });
+}
+
+int avr_scene_gradient(avr_context* ctx, const avr_scene* in, avr_scene* out, int axis,
+                       const int32_t* box_index_lo, const int32_t* level_ratio,
+                       const double* level_cell_size, int n_levels) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(in != nullptr && out != nullptr && level_cell_size != nullptr, "null argument");
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    require_field_scene(ctx, in, n_boxes);
+    const avr::GradientPlan plan =
+        avr::plan_gradient(in->boxes.data(), out->boxes.data(), n_boxes, axis, box_index_lo,
+                           level_ratio, level_cell_size, n_levels);
+    for (auto& key : out->classified_key) key.clear();
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    ctx->gradient_planes.reserve(plan.scratch.total, ctx->stream, "avr_scene_gradient",
+                                 "hipMalloc(gradient planes)");
+    avr::GradientArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.face_value = scratch_part<double>(ctx->gradient_planes, plan.scratch.face_value);
+    args.face_present = scratch_part<uint8_t>(ctx->gradient_planes, plan.scratch.face_present);
+    return avr::launch_gradient(args, axis, ctx->stream);
+  });
+}
+
+int avr_scene_clumps(avr_context* ctx, const avr_scene* in, avr_scene* out, double lower,
+                     double upper, const int32_t* box_index_lo, const int32_t* level_ratio,
+                     int n_levels, uint64_t* count_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(in != nullptr && out != nullptr && count_dev != nullptr, "null argument");
+    require(out->ctx == ctx, "the scenes must belong to the context");
+    const size_t n_boxes = out->boxes.size();
+    require_field_scene(ctx, in, n_boxes);
+    const avr::ClumpPlan plan = avr::plan_clumps(in->boxes.data(), out->boxes.data(), n_boxes,
+                                                 lower, upper, box_index_lo, level_ratio, n_levels);
+    for (auto& key : out->classified_key) key.clear();
+    avr::hip_check(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), ctx->stream), "hipMemsetAsync");
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    ctx->clump_parents.reserve(plan.scratch.total, ctx->stream, "avr_scene_clumps",
+                               "hipMalloc(clump parents)");
+    avr::ClumpArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.parent = scratch_part<uint32_t>(ctx->clump_parents, plan.scratch.parent);
+    args.chunk_roots = scratch_part<uint32_t>(ctx->clump_parents, plan.scratch.chunk_roots);
+    args.count = reinterpret_cast<unsigned long long*>(count_dev);
+    return avr::launch_clumps(args, ctx->stream);
+  });
+}
+
+int avr_scene_clump_table(avr_context* ctx, const avr_scene* labels, const avr_scene* field,
+                          uint64_t n_clumps, int n_levels, uint64_t* cells_dev, double* sums_dev,
+                          uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(labels != nullptr && cells_dev != nullptr && totals_dev != nullptr, "null argument");
+    require((field != nullptr) == (sums_dev != nullptr), "sums_dev is given exactly when field is");
+    const size_t n_boxes = labels->boxes.size();
+    require_field_scene(ctx, labels, n_boxes);
+    if (field != nullptr) require_field_scene(ctx, field, n_boxes);
+    const avr::ClumpTablePlan plan = avr::plan_clump_table(
+        labels->boxes.data(), field != nullptr ? field->boxes.data() : nullptr, n_boxes, n_clumps,
+        n_levels);
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::ClumpTableArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.cells = reinterpret_cast<unsigned long long*>(cells_dev);
+    args.sums = sums_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_clump_table(args, field != nullptr, ctx->stream);
+  });
+}
+
+int avr_scene_isosurface(avr_context* ctx, const avr_scene* field, const avr_scene* sample,
+                         double value, const int32_t* box_index_lo, const int32_t* level_ratio,
+                         const double* level_cell_size, const double* prob_lo, int n_levels,
+                         uint64_t capacity, double* vertices_dev, uint8_t* levels_dev,
+                         double* samples_dev, uint64_t* counts_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(field != nullptr && level_cell_size != nullptr && prob_lo != nullptr &&
+                counts_dev != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
+    const avr::IsoPlan plan = avr::plan_isosurface(
+        field->boxes.data(), sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, value,
+        box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, capacity, vertices_dev,
+        levels_dev, samples_dev, counts_dev);
+    avr::hip_check(hipMemsetAsync(counts_dev, 0, 2 * sizeof(uint64_t), ctx->stream),
+                   "hipMemsetAsync");
+    if (plan.args.n_bases == 0) return AVR_OK;
+    const bool has_sample = sample != nullptr, emit = capacity > 0;
+    ctx->iso_scratch.reserve(plan.scratch.total, ctx->stream, "avr_scene_isosurface",
+                             "hipMalloc(isosurface scratch)");
+    avr::IsoArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    const avr::IsoScratch& scratch = plan.scratch;
+    args.shell_value = scratch_part<double>(ctx->iso_scratch, scratch.shell_value);
+    args.shell_sample = scratch_part<double>(ctx->iso_scratch, scratch.shell_sample);
+    args.chunk_offset = scratch_part<unsigned long long>(ctx->iso_scratch, scratch.chunk_offset);
+    args.chunk_triangles = scratch_part<uint32_t>(ctx->iso_scratch, scratch.chunk_triangles);
+    args.chunk_skipped = scratch_part<uint32_t>(ctx->iso_scratch, scratch.chunk_skipped);
+    args.shell_code = scratch_part<uint8_t>(ctx->iso_scratch, scratch.shell_code);
+    args.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+    args.vertices = vertices_dev;
+    args.levels_out = levels_dev;
+    args.samples = has_sample ? samples_dev : nullptr;
+    return avr::launch_isosurface(args, has_sample, emit, ctx->stream);
+  });
+}
+
+int avr_scene_streamlines(avr_context* ctx, const avr_scene* vx, const avr_scene* vy,
+                          const avr_scene* vz, const avr_scene* sample, const double* seeds_dev,
+                          uint64_t n_seeds, double step, int direction, uint64_t max_steps,
+                          const int32_t* box_index_lo, const int32_t* level_ratio,
+                          const double* level_cell_size, const double* prob_lo, int n_levels,
+                          double* points_dev, double* samples_dev, uint32_t* counts_dev,
+                          uint8_t* status_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(vx != nullptr && vy != nullptr && vz != nullptr && level_cell_size != nullptr &&
+                prob_lo != nullptr, "null argument");
+    const size_t n_boxes = vx->boxes.size();
+    require_field_scene(ctx, vx, n_boxes);
+    require_field_scene(ctx, vy, n_boxes);
+    require_field_scene(ctx, vz, n_boxes);
+    if (sample != nullptr) require_field_scene(ctx, sample, n_boxes);
+    const avr::StreamPlan plan = avr::plan_streamlines(
+        vx->boxes.data(), vy->boxes.data(), vz->boxes.data(),
+        sample != nullptr ? sample->boxes.data() : nullptr, n_boxes, n_seeds, step, direction,
+        max_steps, box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, seeds_dev,
+        points_dev, samples_dev, counts_dev, status_dev);
+    if (n_seeds == 0) return AVR_OK;
+    avr::StreamArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.seeds = seeds_dev;
+    args.points = points_dev;
+    args.samples = sample != nullptr ? samples_dev : nullptr;
+    args.counts = counts_dev;
+    args.status = status_dev;
+    return avr::launch_streamlines(args, sample != nullptr, ctx->stream);
+  });
+}
+
+int avr_scene_covering_grid(avr_context* ctx, const avr_scene* field, int level, const int32_t* lo,
+                            const int32_t* dims, const int32_t* box_index_lo,
+                            const int32_t* level_ratio, int n_levels, double fill,
+                            double* values_dev, double* coverage_dev, int8_t* level_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(field != nullptr && lo != nullptr && dims != nullptr && values_dev != nullptr,
+            "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    const avr::CoveringGridPlan plan = avr::plan_covering_grid(
+        field->boxes.data(), n_boxes, level, lo, dims, box_index_lo, level_ratio, n_levels, fill,
+        values_dev, coverage_dev, level_dev);
+    avr::CoverArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.values = values_dev;
+    args.coverage = coverage_dev;
+    args.cell_level = level_dev;
+    return avr::launch_covering_grid(args, ctx->stream);
+  });
+}
+
+int avr_scene_rays(avr_context* ctx, const avr_scene* field, const double* start_dev,
+                   const double* end_dev, uint64_t n_rays, uint64_t max_trips,
+                   const int32_t* box_index_lo, const int32_t* level_ratio,
+                   const double* level_cell_size, const double* prob_lo, int n_levels,
+                   const int64_t* offsets_dev, uint64_t n_segments, uint32_t* counts_dev,
+                   uint8_t* status_dev, double* span_dev, double* t0_dev, double* t1_dev,
+                   int8_t* level_dev, double* value_dev, double* integral_dev,
+                   double* covered_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    // the scene first, without which nothing can be looked at; every other rule, a null
+    // level_cell_size or prob_lo included, is plan_rays' in its documented order
+    require(field != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    const bool emit = offsets_dev != nullptr;
+    const avr::RayPlan plan = avr::plan_rays(
+        field->boxes.data(), n_boxes, n_rays, max_trips, box_index_lo, level_ratio,
+        level_cell_size, prob_lo, n_levels, start_dev, end_dev, offsets_dev,
+        emit ? n_segments : 0, counts_dev, status_dev, span_dev, t0_dev, t1_dev, level_dev,
+        value_dev, integral_dev, covered_dev);
+    if (n_rays == 0) return AVR_OK;
+    avr::RayArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.start = start_dev;
+    args.end = end_dev;
+    if (emit) {
+      args.offsets = reinterpret_cast<const long long*>(offsets_dev);
+      args.t0 = t0_dev;
+      args.t1 = t1_dev;
+      args.level = level_dev;
+      args.value = value_dev;
+      args.integral = integral_dev;
+      args.covered = covered_dev;
+    } else {
+      args.counts = counts_dev;
+      args.status = status_dev;
+      args.span = span_dev;
+    }
+    return avr::launch_rays(args, emit, ctx->stream);
+  });
+}
+
+int avr_scene_ray_sums(avr_context* ctx, const avr_scene* field, const avr_scene* weight,
+                       const double* start_dev, const double* end_dev, uint64_t n_rays,
+                       uint64_t max_trips, const int32_t* box_index_lo,
+                       const int32_t* level_ratio, const double* level_cell_size,
+                       const double* prob_lo, int n_levels, uint32_t* counts_dev,
+                       uint8_t* status_dev, double* span_dev, double* integral_dev,
+                       double* weight_dev, double* counted_dev, double* covered_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    // as avr_scene_rays: the scenes first, every other rule is plan_ray_sums' in its order
+    require(field != nullptr, "null argument");
+    const size_t n_boxes = field->boxes.size();
+    require_field_scene(ctx, field, n_boxes);
+    if (weight != nullptr) require_field_scene(ctx, weight, weight->boxes.size());
+    const avr::RaySumsPlan plan = avr::plan_ray_sums(
+        field->boxes.data(), n_boxes, weight != nullptr ? weight->boxes.data() : nullptr,
+        weight != nullptr ? weight->boxes.size() : 0, n_rays, max_trips, box_index_lo,
+        level_ratio, level_cell_size, prob_lo, n_levels, start_dev, end_dev, counts_dev,
+        status_dev, span_dev, integral_dev, weight_dev, counted_dev, covered_dev);
+    if (n_rays == 0) return AVR_OK;
+    avr::RayArgs args = plan.walk.args;
+    stage_tables(ctx, plan, &args);
+    args.start = start_dev;
+    args.end = end_dev;
+    args.counts = counts_dev;
+    args.status = status_dev;
+    args.span = span_dev;
+    args.integral = integral_dev;
+    args.weight = weight_dev;
+    args.counted = counted_dev;
+    args.covered = covered_dev;
+    return avr::launch_ray_sums(args, ctx->stream);
+  });
+}
+
+}  // extern "C"

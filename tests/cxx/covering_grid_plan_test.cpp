@@ -64,8 +64,8 @@ struct Scene {
   avr::CoveringGridPlan plan() const {
     return avr::plan_covering_grid(in.data(), in.size(), level, lo, dims,
                                    index.empty() ? nullptr : index.data(),
-                                   ratio.empty() ? nullptr : ratio.data(), n_levels, values,
-                                   coverage, cell_level);
+                                   ratio.empty() ? nullptr : ratio.data(), n_levels, /*fill=*/0.0,
+                                   values, coverage, cell_level);
   }
 };
 
