@@ -234,6 +234,8 @@ SIGNATURES = {
                                      C.c_int]),
     "avr_scene_clumps": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, _ip, _ip, C.c_int, _vp]),
     "avr_scene_clump_table": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp, _vp, _vp]),
+    "avr_scene_clump_links": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip, C.c_int,
+                                        _vp, _vp, _vp, _vp]),
     "avr_scene_isosurface": (C.c_int, [_vp, _vp, _vp, C.c_double, _ip, _ip, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.c_int,
                                        C.c_uint64, _vp, _vp, _vp, _vp]),

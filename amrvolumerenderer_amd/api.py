@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 
 from .derive import (DerivedProgram, add_field, compile_expression, derived_fields,
                      evaluate_program, remove_field)
-from .clumps import add_clump_field, clump_fields, remove_clump_field
+from .clumps import add_clump_field, clump_fields, remove_clump_field, threshold_ladder
 from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
@@ -415,6 +415,151 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
             "integrals": {name: clump_rules.clump_integrals(sums[name], volumes)
                           for name in names},
             "outside": outside, "nonfinite": nonfinite}
+
+
+# ---- clump trees ("Clump tree") ------------------------------------------------------
+
+def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes, prob_lo,
+                     ref_ratio, tables: Sequence["SceneGeometry"] = (), rank: int = 0,
+                     n_ranks: int = 1) -> dict:
+    """The clumps of a scene's field over a ladder of thresholds, linked into a tree (DESIGN.md 7,
+    "Clump tree").  thresholds: 1 to 64 finite values, strictly ascending; upper: one closed upper
+    bound for all of them (clumps.check_thresholds).  The clumps of thresholds[i] are clump_scene's
+    over [thresholds[i], upper]; every one of them lies inside exactly one clump of thresholds[i -
+    1], its parent.  One clump_scene call per threshold up to the first without a clump (no later
+    one has any, and none is asked for), with at most two label scenes alive; per threshold one
+    Scene.clump_links call against the labels of the threshold below, one Scene.clump_table call,
+    and one more per scene of `tables` (scenes of the same boxes, summed per clump).  scene,
+    cell_sizes, prob_lo and ref_ratio as clump_scene takes them; L = len(cell_sizes).  Returns a
+    dict over the nodes -- ascending threshold, then label: counts (clumps per threshold, one per
+    threshold), parent_labels (per threshold an int64 array, the parent's label per clump; empty
+    for threshold 0), index_lo, index_hi int64 [n, 3] (the inclusive bounding box in level L - 1's
+    index space), left_edge = prob_lo + f64(index_lo) * dx[L - 1], right_edge = prob_lo +
+    f64(index_hi + 1) * dx[L - 1] float64 [n, 3], cells_by_level int64 [L, n], sums (per scene of
+    tables float64 [L, n]) and nonfinite (cells of clumps where a summed field is not finite).
+    RuntimeError, naming the threshold and the label, if a clump's cells carry two parent labels,
+    if a label or parent label is none, or if a clump has no cell.  Every box of the scene must be
+    on this rank, as for clump_scene."""
+    import numpy as np
+    from . import clumps as clump_rules
+    thresholds, upper = clump_rules.check_thresholds(thresholds, upper)
+    _require_one_rank(scene, n_ranks, "clumps need every box of the scene on one rank: "
+                      "labels are not merged between ranks")
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    n_levels = len(sizes)
+    tables = list(tables)
+    counts = [0] * len(thresholds)
+    parent_labels = [np.zeros(0, dtype=np.int64) for _ in thresholds]
+    extents, cells, nonfinite = [], [], 0
+    sums = [[] for _ in tables]
+    below, n_below = None, 0
+    with _native_scenes(ctx, tables) as fields:
+        for step, threshold in enumerate(thresholds):
+            labels, n = clump_scene(ctx, scene, threshold, upper, cell_sizes, prob_lo, ref_ratio,
+                                    rank, n_ranks)
+            if n == 0:
+                break
+            if n * n_levels >= clump_rules.TABLE_MAX_ENTRIES:
+                raise ValueError("too many clumps for one table: n * levels must stay below 2^28")
+            with _native_scenes(ctx, [labels, below]) as (label_scene, parent_scene):
+                extent, parent_lo, parent_hi, link_totals = label_scene.clump_links(
+                    n, index, ratios, parent_scene, n_below)
+                counted, _, totals = label_scene.clump_table(n, n_levels)
+                summed = []
+                for field in fields:
+                    _, field_sums, field_totals = label_scene.clump_table(n, n_levels, field)
+                    summed.append((field_sums, field_totals))
+                ctx.synchronize()
+            where = f"threshold {threshold!r}"
+            if int(totals[0].item()) != 0 or int(link_totals[0].item()) != 0:
+                raise RuntimeError(f"{where}: {max(int(totals[0].item()), int(link_totals[0].item()))} "
+                                   f"cells carry a label that is no clump in 1..{n}")
+            if int(link_totals[1].item()) != 0:
+                raise RuntimeError(f"{where}: {int(link_totals[1].item())} cells of clumps in "
+                                   f"1..{n} lie in no clump of the threshold below")
+            extent = extent.cpu().numpy().astype(np.int64)
+            untouched = np.nonzero((extent[:3] == 2 ** 31 - 1).any(axis=0) |
+                                   (extent[3:] == -2 ** 31).any(axis=0))[0]
+            if untouched.size:
+                raise RuntimeError(f"{where}: clump {int(untouched[0]) + 1} has no cell")
+            if parent_scene is not None:
+                held_lo = parent_lo.cpu().numpy().astype(np.int64)
+                held_hi = parent_hi.cpu().numpy().astype(np.int64)
+                split = np.nonzero(held_lo != held_hi)[0]
+                if split.size:
+                    c = int(split[0])
+                    raise RuntimeError(f"{where}: clump {c + 1} lies in clumps {int(held_lo[c])} "
+                                       f"to {int(held_hi[c])} of the threshold below")
+                parent_labels[step] = held_lo
+            counts[step] = n
+            extents.append(extent)
+            cells.append(counted.cpu().numpy())
+            for held, (field_sums, field_totals) in zip(sums, summed):
+                held.append(field_sums.cpu().numpy())
+                nonfinite += int(field_totals[1].item())
+            below, n_below = labels, n
+    total = sum(counts)
+    extent = np.concatenate(extents + [np.zeros((6, 0), dtype=np.int64)], axis=1)
+    index_lo = np.ascontiguousarray(extent[:3].T)
+    index_hi = np.ascontiguousarray(extent[3:].T)
+    origin = np.array([float(v) for v in prob_lo], dtype=np.float64)
+    finest = np.array(sizes[n_levels - 1], dtype=np.float64)
+    empty_cells = np.zeros((n_levels, 0), dtype=np.int64)
+    empty_sums = np.zeros((n_levels, 0), dtype=np.float64)
+    return {"n": total, "counts": counts, "parent_labels": parent_labels,
+            "index_lo": index_lo, "index_hi": index_hi,
+            "left_edge": origin + index_lo.astype(np.float64) * finest,
+            "right_edge": origin + (index_hi + 1).astype(np.float64) * finest,
+            "cells_by_level": np.concatenate(cells + [empty_cells], axis=1),
+            "sums": [np.concatenate(held + [empty_sums], axis=1) for held in sums],
+            "nonfinite": nonfinite}
+
+
+def clump_tree(plotfile: str, variable: str, thresholds, upper: float = math.inf,
+               fields: Sequence[str] = (), min_cells: int = 1, min_level: int = 0,
+               max_level: int = -1, output: Optional[str] = None) -> dict:
+    """The clump tree of a plotfile's variable over a ladder of thresholds ("Clump
+    tree"; yt's find_clumps), on cuda:0.  thresholds and upper as clump_tree_scene takes them
+    (clumps.threshold_ladder gives yt's ladder); variable and every name of fields as api.clumps
+    takes them.  Returns a dict: thresholds, upper, n (nodes; node v is clump label[v] of threshold
+    threshold_index[v], numbered by ascending threshold, then label), node_begin int64 [k + 1],
+    threshold_index, label, parent (-1 at the first threshold) int64 [n], child_offsets int64 [n +
+    1] and children (CSR, ascending), cells_by_level int64 [L, n], cells, volume and integrals
+    {name: float64 [n]} as api.clumps makes them, index_lo, index_hi int64 [n, 3] (the inclusive
+    bounding box in the finest loaded level's index space), left_edge, right_edge float64 [n, 3],
+    kept, kept_parent and leaves (clumps.collapse_tree with min_cells: a clump that does not split
+    is the same clump), and nonfinite.  n == 0 gives empty arrays.  With output, the dict is also
+    written as one .npz (clumps.save_tree_npz)."""
+    import numpy as np
+    from . import clumps as clump_rules
+    from . import plotfile as pf
+    thresholds, upper = clump_rules.check_thresholds(thresholds, upper)
+    min_cells = int(min_cells)
+    if min_cells < 1:
+        raise ValueError("min_cells must be at least 1")
+    names = [str(name) for name in fields]
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
+                                                            min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    found = clump_tree_scene(ctx, scenes[0], thresholds, upper, *_header_levels(header, n_levels),
+                             tables=scenes[1:], rank=rank, n_ranks=world)
+    nodes = clump_rules.tree_nodes(found["counts"], found["parent_labels"])
+    cells_by_level = found["cells_by_level"]
+    cells = cells_by_level.sum(axis=0)
+    tree = {"thresholds": np.array(thresholds, dtype=np.float64), "upper": upper, "n": found["n"]}
+    tree.update(nodes)
+    tree.update({"cells_by_level": cells_by_level, "cells": cells,
+                 "volume": clump_rules.clump_volumes(cells_by_level, volumes),
+                 "integrals": {name: clump_rules.clump_integrals(summed, volumes)
+                               for name, summed in zip(names, found["sums"])},
+                 "index_lo": found["index_lo"], "index_hi": found["index_hi"],
+                 "left_edge": found["left_edge"], "right_edge": found["right_edge"]})
+    tree.update(clump_rules.collapse_tree(nodes["parent"], cells, min_cells))
+    tree["nonfinite"] = found["nonfinite"]
+    if output:
+        clump_rules.save_tree_npz(output, tree)
+    return tree
 
 
 # ---- isosurfaces (DESIGN.md 7, "Isosurface") -----------------------------------------------------

@@ -1,6 +1,8 @@
 """Clumps ("Clumps"): the registry of named clump label fields -- the connected
 components of the cells of a field whose value lies in [lower, upper] -- and what api.clumps works
-out on the host after the kernels of csrc/avr_clumps.hip ran.  numpy only.
+out on the host after the kernels of csrc/avr_clumps.hip ran; and the host side of the clump tree
+("Clump tree"): the ladder's rules, the node numbering, yt's collapse and the .npz
+writer.  numpy only.
 """
 from __future__ import annotations
 
@@ -83,3 +85,126 @@ def clump_integrals(sums_by_level, cell_volumes: Sequence[float]) -> np.ndarray:
     for level in range(sums.shape[0]):
         values = values + np.float64(cell_volumes[level]) * sums[level]
     return values
+
+
+# ---- clump trees ("Clump tree") -----------------------------------------------------
+
+LADDER_MAX_THRESHOLDS = 64
+
+
+def check_thresholds(thresholds, upper=math.inf) -> Tuple[Tuple[float, ...], float]:
+    """(thresholds, upper) as floats: 1 to 64 finite values, strictly ascending, under one closed
+    upper bound that may be +inf, is no NaN and is not below the last threshold; ValueError
+    otherwise."""
+    values = tuple(float(t) for t in thresholds)
+    upper = float(upper)
+    if not 1 <= len(values) <= LADDER_MAX_THRESHOLDS:
+        raise ValueError("a ladder holds 1 to 64 thresholds")
+    if not all(math.isfinite(t) for t in values):
+        raise ValueError("thresholds must be finite")
+    if any(b <= a for a, b in zip(values, values[1:])):
+        raise ValueError("thresholds must be strictly ascending")
+    if math.isnan(upper):
+        raise ValueError("a clump bound must not be NaN")
+    if values[-1] > upper:
+        raise ValueError("the last threshold must not exceed upper")
+    return values, upper
+
+
+def threshold_ladder(c_min: float, c_max: float, step: float) -> np.ndarray:
+    """yt's ladder: t[0] = c_min, t[i + 1] = t[i] * step (one f64 multiply), every value <= c_max
+    kept.  Needs step > 1, 0 < c_min <= c_max, all finite, and at most 64 values: anything else is
+    a ValueError."""
+    c_min, c_max, step = float(c_min), float(c_max), float(step)
+    if not (math.isfinite(c_min) and math.isfinite(c_max) and math.isfinite(step)):
+        raise ValueError("c_min, c_max and step must be finite")
+    if not step > 1.0:
+        raise ValueError("step must exceed 1")
+    if not 0.0 < c_min <= c_max:
+        raise ValueError("0 < c_min <= c_max is required")
+    values = [c_min]
+    while True:
+        following = float(np.float64(values[-1]) * np.float64(step))
+        if not following <= c_max:
+            break
+        if len(values) == LADDER_MAX_THRESHOLDS:
+            raise ValueError("the ladder holds more than 64 thresholds")
+        values.append(following)
+    return np.array(values, dtype=np.float64)
+
+
+def tree_nodes(counts: Sequence[int], parents_per_threshold) -> Dict[str, np.ndarray]:
+    """The nodes of a clump tree.  counts[i]: the number of clumps of threshold i;
+    parents_per_threshold[i] (i >= 1): per clump of threshold i, ascending label, the label
+    (1-based) of the clump of threshold i - 1 that holds it; entry 0 is not read.  Nodes are
+    numbered by ascending threshold, then label.  Returns node_begin int64 [k + 1],
+    threshold_index, label, parent (node id, -1 at threshold 0) int64 [n], and the children as
+    CSR: child_offsets int64 [n + 1], children int64 (ascending per node)."""
+    counts = [int(c) for c in counts]
+    if any(c < 0 for c in counts):
+        raise ValueError("a count is negative")
+    node_begin = np.zeros(len(counts) + 1, dtype=np.int64)
+    node_begin[1:] = np.cumsum(np.array(counts, dtype=np.int64))
+    n = int(node_begin[-1])
+    threshold_index = np.repeat(np.arange(len(counts), dtype=np.int64),
+                                np.array(counts, dtype=np.int64))
+    label = np.concatenate([np.arange(1, c + 1, dtype=np.int64) for c in counts] +
+                           [np.zeros(0, dtype=np.int64)])
+    parent = np.full(n, -1, dtype=np.int64)
+    for i in range(1, len(counts)):
+        held_by = np.asarray(parents_per_threshold[i], dtype=np.int64).reshape(-1)
+        if held_by.size != counts[i]:
+            raise ValueError("parents_per_threshold must hold one label per clump")
+        if counts[i] and (held_by.min() < 1 or held_by.max() > counts[i - 1]):
+            raise ValueError("a parent label is no clump of the threshold below")
+        parent[node_begin[i]:node_begin[i + 1]] = node_begin[i - 1] + held_by - 1
+    has_parent = parent >= 0
+    child_offsets = np.zeros(n + 1, dtype=np.int64)
+    child_offsets[1:] = np.cumsum(np.bincount(parent[has_parent], minlength=n))
+    nodes = np.nonzero(has_parent)[0].astype(np.int64)
+    children = nodes[np.argsort(parent[has_parent], kind="stable")]
+    return {"node_begin": node_begin, "threshold_index": threshold_index, "label": label,
+            "parent": parent, "child_offsets": child_offsets, "children": children}
+
+
+def collapse_tree(parent, cells, min_cells: int = 1) -> Dict[str, np.ndarray]:
+    """yt's rule that a clump which does not split is the same clump, on a finished tree (parent:
+    node ids, -1 for a root, every parent before its children; cells per node).  valid[v] =
+    cells[v] >= min_cells; kept[v] = valid[v] and (v is a root or its parent has at least two
+    valid children); kept_parent[v] = for a kept v the first kept node met walking up from
+    parent[v] (-1 for a root), for any other node -1; leaves = the kept nodes that are no kept
+    node's kept_parent, ascending.  Returns kept bool [n], kept_parent int64 [n], leaves int64."""
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+    if parent.shape != cells.shape:
+        raise ValueError("parent and cells must hold one entry per node")
+    n = parent.size
+    valid = cells >= int(min_cells)
+    below = valid & (parent >= 0)
+    valid_children = np.bincount(parent[below], minlength=n) if n else np.zeros(0, dtype=np.int64)
+    kept = valid & ((parent < 0) | (valid_children[np.maximum(parent, 0)] >= 2))
+    kept_parent = np.full(n, -1, dtype=np.int64)
+    for v in range(n):
+        if not kept[v]:
+            continue
+        up = int(parent[v])
+        while up >= 0 and not kept[up]:
+            up = int(parent[up])
+        kept_parent[v] = up
+    is_parent = np.zeros(n, dtype=bool)
+    is_parent[kept_parent[kept_parent >= 0]] = True
+    leaves = np.nonzero(kept & ~is_parent)[0].astype(np.int64)
+    return {"kept": kept, "kept_parent": kept_parent, "leaves": leaves}
+
+
+def save_tree_npz(path: str, tree: dict) -> None:
+    """Writes the dict api.clump_tree returns as one .npz: every array under its key, the
+    integrals as integral_<name>, the scalars as zero-dimensional arrays."""
+    arrays = {}
+    for key, value in tree.items():
+        if key == "integrals":
+            for name, values in value.items():
+                arrays[f"integral_{name}"] = np.asarray(values)
+        else:
+            arrays[key] = np.asarray(value)
+    np.savez(path, **arrays)

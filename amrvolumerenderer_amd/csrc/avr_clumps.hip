@@ -9,6 +9,7 @@
 //   clump_rank_kernel      a root's entry becomes kClumpRanked | (label - 1)
 //   clump_label_kernel     f64 labels into the output boxes at their own strides
 //   clump_table_kernel<S>  cells (and sums of a field) per level and label
+//   clump_link_kernel<P>   index extents (and the parent labels in a coarser ladder step) per label
 //
 // A cell's ordinal is cell_begin of its box + (k ny + j) nx + i; parent holds one uint32 per
 // ordinal.  The union-find is lock-free and waits for nothing: a non-root's entry is always a
@@ -50,6 +51,7 @@ typedef double __attribute__((address_space(1))) global_double;
 typedef const double __attribute__((address_space(1))) const_global_double;
 typedef const ClumpBoxDev __attribute__((address_space(4))) constant_box;
 typedef const JointBoxDev __attribute__((address_space(4))) constant_table_box;
+typedef const ClumpLinkBoxDev __attribute__((address_space(4))) constant_link_box;
 typedef const uint32_t __attribute__((address_space(4))) constant_u32;
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef const double2_t __attribute__((address_space(1))) const_global_double2;
@@ -425,6 +427,223 @@ __global__ __launch_bounds__(kThreads) void clump_table_kernel(const ClumpTableA
   }
 }
 
+// ---- links and extents ---------------------------------------------------------------------------
+
+// What a wave has gathered for one label and not yet written ("Clump tree"): the
+// ends are indices of the finest level, so the record outlives a change of box and of level.
+// label 0: nothing is held.  Every member is the same in all lanes of the wave.
+struct LinkRecord {
+  uint32_t label;
+  int32_t lo[3], hi[3];
+  uint32_t parent_lo, parent_hi;
+};
+
+__device__ __forceinline__ void clear(LinkRecord& r, uint32_t label) {
+  r.label = label;
+  for (int a = 0; a < 3; ++a) {
+    r.lo[a] = INT32_MAX;
+    r.hi[a] = INT32_MIN;
+  }
+  r.parent_lo = UINT32_MAX;
+  r.parent_hi = 0u;
+}
+
+__device__ __forceinline__ int32_t load_entry(const int32_t* at) {
+  return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t load_entry(const uint32_t* at) {
+  return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Combines record r into the outputs, reading before it writes: an entry is loaded, and the atomic
+// is issued only if r's value would change what was loaded.  The load may be stale -- other waves
+// combine into the same entry meanwhile -- and nothing is lost by that.  An entry of a minimum only
+// ever falls: whatever it holds now is at most what was loaded.  So if v >= loaded, then v >=
+// loaded >= current and atomicMin(entry, v) would have left the entry as it is: the skipped atomic
+// was a no-op.  If v < loaded the atomic is issued and resolves against the current value, as it
+// would have without the load.  A stale load can therefore only cost an atomic that turns out to
+// be unneeded, never lose one; the same holds for a maximum with the order reversed.  The result
+// is the minimum / maximum of integers over all cells, exact in whatever order the atomics
+// resolve.  The eight loads are issued together, ahead of the atomics; no atomic returns a value.
+template <bool HAS_PARENT>
+__device__ __forceinline__ void combine_into(const ClumpLinkArgs& a, const LinkRecord& r) {
+  const uint32_t n = a.n_clumps, e = r.label - 1u;  // 6 n < 2^31
+  int32_t held_lo[3], held_hi[3];
+  uint32_t held_parent_lo = 0u, held_parent_hi = 0u;
+#pragma unroll
+  for (uint32_t axis = 0; axis < 3; ++axis) {
+    held_lo[axis] = load_entry(a.extent + (axis * n + e));
+    held_hi[axis] = load_entry(a.extent + ((3u + axis) * n + e));
+  }
+  if (HAS_PARENT) {
+    held_parent_lo = load_entry(a.parent_lo + e);
+    held_parent_hi = load_entry(a.parent_hi + e);
+  }
+#pragma unroll
+  for (uint32_t axis = 0; axis < 3; ++axis) {
+    if (r.lo[axis] < held_lo[axis]) atomicMin(a.extent + (axis * n + e), r.lo[axis]);
+    if (r.hi[axis] > held_hi[axis]) atomicMax(a.extent + ((3u + axis) * n + e), r.hi[axis]);
+  }
+  if (HAS_PARENT) {
+    if (r.parent_lo < held_parent_lo) atomicMin(a.parent_lo + e, r.parent_lo);
+    if (r.parent_hi > held_parent_hi) atomicMax(a.parent_hi + e, r.parent_hi);
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+  for (int mask = 32; mask > 0; mask >>= 1) {
+    const uint32_t other = __shfl_xor(v, mask, 64);
+    v = other < v ? other : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+  for (int mask = 32; mask > 0; mask >>= 1) {
+    const uint32_t other = __shfl_xor(v, mask, 64);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// The table kernel's scan with a record carried by each wave instead of atomics per visit.  In a
+// visit a wave's lanes hold cells of one row, `step` apart in i from lane 0's on, so j and k are
+// the wave's, and among the counted lanes the first has the lowest i and the last the highest:
+// while the counted lanes share a label, the visit's six ends follow from the ballot alone, and
+// the parent label from one lane unless the lanes disagree (then two shuffle reductions).  The
+// record goes to memory, through lane 0, when the shared label changes, when a visit is mixed and
+// after the workgroup's last tile; in a mixed visit every counted lane combines its own cell.
+template <bool HAS_PARENT>
+__global__ __launch_bounds__(kThreads) void clump_link_kernel(const ClumpLinkArgs a) {
+  __shared__ uint32_t wave_totals[kThreads / 64][2];
+  const int tid = static_cast<int>(threadIdx.x);
+  const uint32_t lane = threadIdx.x & 63u;
+  const double top = static_cast<double>(a.n_clumps);
+  const double parent_top = static_cast<double>(a.n_parents);
+  uint32_t outside = 0, orphans = 0;
+  LinkRecord held;
+  clear(held, 0u);
+  for_each_tile((constant_table_box*)a.boxes, (constant_u32*)a.tile_begin, a.n_boxes, a.n_tiles,
+                [&](int b, constant_table_box* box, const CellTile& at) {
+    const int nx = box->nx, ny = box->ny, nz = box->nz;
+    constant_link_box* fine = (constant_link_box*)a.refined + b;
+    const int32_t scale = fine->scale;
+    const int32_t lo_x = fine->lo[0], lo_y = fine->lo[1], lo_z = fine->lo[2];
+    const_global_double* cl = (const_global_double*)box->cells[0];
+    const_global_double* cp = (const_global_double*)box->cells[HAS_PARENT ? 1 : 0];
+    const uint32_t jl = static_cast<uint32_t>(box->jstride[0]), kl = static_cast<uint32_t>(box->kstride[0]);
+    const uint32_t jp = static_cast<uint32_t>(box->jstride[1]), kp = static_cast<uint32_t>(box->kstride[1]);
+    // One cell of every lane, in converged control flow: cell (i, j, k) of the box, lane 0 holding
+    // the lowest i and lane m that + m step.
+    auto visit = [&](bool valid, double label, double parent, int i, int j, int k, int step) {
+      const bool active = valid && __double_as_longlong(label) != 0ll;
+      const bool integer = label >= 1.0 && label <= top && label == __builtin_floor(label);
+      const bool linked = !HAS_PARENT || (parent >= 1.0 && parent <= parent_top &&
+                                          parent == __builtin_floor(parent));  // false for a NaN
+      outside += (active && !integer) ? 1u : 0u;
+      orphans += (active && integer && !linked) ? 1u : 0u;
+      const bool counted = active && integer && linked;
+      const unsigned long long mask = __ballot(counted);
+      if (mask == 0ull) return;
+      const uint32_t c = counted ? static_cast<uint32_t>(label) : 0u;
+      const uint32_t p = (HAS_PARENT && counted) ? static_cast<uint32_t>(parent) : 0u;
+      const int first = __ffsll(mask) - 1, last = 63 - __clzll(mask);
+      const uint32_t shared = static_cast<uint32_t>(
+          __builtin_amdgcn_readlane(static_cast<int>(c), first));
+      const bool mixed = __ballot(counted && c != shared) != 0ull;
+      if (held.label != 0u && (mixed || shared != held.label)) {
+        if (lane == 0u) combine_into<HAS_PARENT>(a, held);
+        clear(held, 0u);
+      }
+      if (mixed) {  // every counted lane for itself
+        if (counted) {
+          LinkRecord own;
+          own.label = c;
+          own.lo[0] = lo_x + i * scale;
+          own.lo[1] = lo_y + j * scale;
+          own.lo[2] = lo_z + k * scale;
+          for (int axis = 0; axis < 3; ++axis) own.hi[axis] = own.lo[axis] + (scale - 1);
+          own.parent_lo = own.parent_hi = p;
+          combine_into<HAS_PARENT>(a, own);
+        }
+        return;
+      }
+      if (held.label == 0u) clear(held, shared);
+      // lane 0 may hold no cell of the box: unsigned, so that only the counted ends must fit
+      const uint32_t i0 = static_cast<uint32_t>(uniform(i)), us = static_cast<uint32_t>(scale);
+      const uint32_t ux = static_cast<uint32_t>(lo_x);
+      const int32_t x = static_cast<int32_t>(ux + (i0 + static_cast<uint32_t>(first * step)) * us);
+      const int32_t x_end = static_cast<int32_t>(
+          ux + (i0 + static_cast<uint32_t>(last * step)) * us + (us - 1u));
+      const int32_t y = lo_y + uniform(j) * scale, z = lo_z + uniform(k) * scale;
+      held.lo[0] = x < held.lo[0] ? x : held.lo[0];
+      held.lo[1] = y < held.lo[1] ? y : held.lo[1];
+      held.lo[2] = z < held.lo[2] ? z : held.lo[2];
+      held.hi[0] = x_end > held.hi[0] ? x_end : held.hi[0];
+      held.hi[1] = y + (scale - 1) > held.hi[1] ? y + (scale - 1) : held.hi[1];
+      held.hi[2] = z + (scale - 1) > held.hi[2] ? z + (scale - 1) : held.hi[2];
+      if (HAS_PARENT) {
+        uint32_t least = static_cast<uint32_t>(
+            __builtin_amdgcn_readlane(static_cast<int>(p), first));
+        uint32_t most = least;
+        if (__ballot(counted && p != least) != 0ull) {
+          least = wave_min(counted ? p : UINT32_MAX);
+          most = wave_max(p);
+        }
+        held.parent_lo = least < held.parent_lo ? least : held.parent_lo;
+        held.parent_hi = most > held.parent_hi ? most : held.parent_hi;
+      }
+    };
+    if (box->paired) {  // both fields: 16-byte aligned cells and even strides (set by the host)
+      const int i = at.chunk * kClassifyChunk + (tid & 63) * 2;
+      const uint32_t ui = static_cast<uint32_t>(i);
+#pragma unroll
+      for (int pass = 0; pass < 4; ++pass) {
+        const int row = pass * 4 + (tid >> 6);
+        const int j = at.bj * kBrickY + (row & 3), k = at.bk * kBrickZ + (row >> 2);
+        const uint32_t uj = static_cast<uint32_t>(j), uk = static_cast<uint32_t>(k);
+        const bool valid = i < nx && j < ny && k < nz;
+        const bool whole = valid && i + 1 < nx;
+        double2_t vl = {0.0, 0.0}, vp = {0.0, 0.0};
+        if (whole) {
+          vl = *(const_global_double2*)(cl + (ui + uj * jl + uk * kl));
+          if (HAS_PARENT) vp = *(const_global_double2*)(cp + (ui + uj * jp + uk * kp));
+        } else if (valid) {
+          vl.x = cl[ui + uj * jl + uk * kl];
+          if (HAS_PARENT) vp.x = cp[ui + uj * jp + uk * kp];
+        }
+        visit(valid, vl.x, vp.x, i, j, k, 2);
+        visit(whole, vl.y, vp.y, i + 1, j, k, 2);
+      }
+    } else {
+      for_each_cell(at, nx, ny, nz, [&](int i, int j, int k, bool valid) {
+        double vl = 0.0, vp = 0.0;
+        if (valid) {
+          const uint32_t ui = static_cast<uint32_t>(i), uj = static_cast<uint32_t>(j);
+          const uint32_t uk = static_cast<uint32_t>(k);
+          vl = cl[ui + uj * jl + uk * kl];
+          if (HAS_PARENT) vp = cp[ui + uj * jp + uk * kp];
+        }
+        visit(valid, vl, vp, i, j, k, 1);
+      });
+    }
+  });
+  if (held.label != 0u && lane == 0u) combine_into<HAS_PARENT>(a, held);
+
+  outside = wave_sum(outside);
+  orphans = wave_sum(orphans);
+  if (lane == 0u) {
+    wave_totals[tid >> 6][0] = outside;
+    wave_totals[tid >> 6][1] = orphans;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    uint32_t total = 0;
+    for (int w = 0; w < kThreads / 64; ++w) total += wave_totals[w][tid];
+    if (total != 0u) atomicAdd(&a.totals[tid], static_cast<unsigned long long>(total));
+  }
+}
+
 int check(const char* what) {
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
@@ -459,6 +678,18 @@ int launch_clump_table(const ClumpTableArgs& args, bool has_field, void* stream_
     hipLaunchKernelGGL(clump_table_kernel<false>, groups, dim3(kThreads), 0, stream, args);
   }
   return check("clump_table_kernel");
+}
+
+int launch_clump_links(const ClumpLinkArgs& args, bool has_parent, void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (args.n_tiles == 0) return AVR_OK;
+  const dim3 groups((args.n_tiles + kTilesPerGroup - 1) / kTilesPerGroup);
+  if (has_parent) {
+    hipLaunchKernelGGL(clump_link_kernel<true>, groups, dim3(kThreads), 0, stream, args);
+  } else {
+    hipLaunchKernelGGL(clump_link_kernel<false>, groups, dim3(kThreads), 0, stream, args);
+  }
+  return check("clump_link_kernel");
 }
 
 }  // namespace avr

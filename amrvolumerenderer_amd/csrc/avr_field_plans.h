@@ -853,6 +853,103 @@ inline ClumpTablePlan plan_clump_table(const avr_box* labels, const avr_box* fie
   return plan;
 }
 
+// The links and extents of a label field ("Clump tree").  refined[b]: box b in the
+// index space of level n_levels - 1, a cell of level l covering R_l = ratio[l] * ... *
+// ratio[n_levels - 2] cells of it per axis.
+struct ClumpLinksPlan {
+  std::vector<JointBoxDev> boxes;  // field 0: the labels; field 1: the parent labels, or the labels
+  std::vector<ClumpLinkBoxDev> refined;  // a box without cells keeps a zeroed entry
+  std::vector<uint32_t> tile_begin;
+  ClumpLinkArgs args{};
+  template <class Visit>
+  void visit_tables(ClumpLinkArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->refined, refined.data(), refined.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+  }
+};
+// parents (may be null): the boxes of the label scene of the ladder's step below.  box_index_lo
+// and level_ratio as plan_gradient takes them.  The rules, in this order: n_clumps, n_parents,
+// n_levels, null arrays, the box rules on the labels, the ratios, the index ranges, the refined
+// index ranges, the parents' boxes against the labels'.
+inline ClumpLinksPlan plan_clump_links(const avr_box* labels, const avr_box* parents,
+                                       size_t n_boxes, uint64_t n_clumps, uint64_t n_parents,
+                                       const int32_t* box_index_lo, const int32_t* level_ratio,
+                                       int n_levels) {
+  const uint64_t limit = static_cast<uint64_t>(kClumpTableMaxEntries);
+  require_box(n_clumps >= 1 && n_clumps < limit, "n_clumps must lie in [1, 2^28)");
+  if (parents != nullptr) {
+    require_box(n_parents >= 1 && n_parents < limit, "n_parents must lie in [1, 2^28)");
+  } else {
+    require_box(n_parents == 0, "without a parent scene n_parents must be 0");
+  }
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  ClumpLinksPlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.refined.resize(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = labels[b];
+    const avr_box* in[1] = {&first};
+    FieldView view;
+    JointBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    std::memset(&plan.refined[b], 0, sizeof(plan.refined[b]));
+    const bool cells = field_box_views(first, in, 1, n_levels, &view, &dev.paired);
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+  }
+  LevelRatiosDev levels;
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  // R_l, held at 2^32 from there on: a cell that wide cannot lie inside [-2^30, 2^30)
+  int64_t scale[kFieldMaxLevels];
+  scale[n_levels - 1] = 1;
+  for (int l = n_levels - 2; l >= 0; --l) {
+    scale[l] = std::min(scale[l + 1] * levels.ratio[l], int64_t{1} << 32);
+  }
+  std::vector<IndexRegion> regions(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (plan.boxes[b].nx <= 0) continue;
+    int32_t lo[3];
+    regions[b] = box_index_region(box_index_lo, b, labels[b].dims, lo);
+  }
+  for (size_t b = 0; b < n_boxes; ++b) {
+    if (plan.boxes[b].nx <= 0) continue;
+    const int64_t r = scale[plan.boxes[b].level];
+    for (int d = 0; d < 3; ++d) {
+      const int64_t lo = regions[b].lo[d] * r, hi = (regions[b].hi[d] + 1) * r - 1;
+      require_box(lo >= -(int64_t{1} << 30) && hi < (int64_t{1} << 30),
+                  "a box's refined index range leaves [-2^30, 2^30)");
+      plan.refined[b].lo[d] = static_cast<int32_t>(lo);
+    }
+    plan.refined[b].scale = static_cast<int32_t>(r);
+  }
+  plan.tile_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = labels[b];
+    const avr_box* in[2] = {&first, parents != nullptr ? &parents[b] : &first};
+    FieldView views[2];
+    JointBoxDev& dev = plan.boxes[b];
+    const bool cells = field_box_views(first, in, 2, n_levels, views, &dev.paired);
+    for (int f = 0; f < 2; ++f) {
+      dev.cells[f] = views[f].cells;
+      dev.jstride[f] = views[f].jstride;
+      dev.kstride[f] = views[f].kstride;
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_clumps = static_cast<uint32_t>(n_clumps);
+  plan.args.n_parents = static_cast<uint32_t>(n_parents);
+  return plan;
+}
+
 // ---- isosurfaces --------------------------------------------------------------------------
 // The shells' values (and sample values), the chunks' offsets, triangles and skipped cubes, then
 // the shells' code bytes.

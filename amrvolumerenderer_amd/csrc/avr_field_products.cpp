@@ -1,5 +1,5 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
-// projections, derived fields, gradient fields, clumps and their table, isosurfaces, streamlines,
+// projections, derived fields, gradient fields, clumps, their table and links, isosurfaces, streamlines,
 // covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.
@@ -50,7 +50,7 @@ void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t 
 
 }  // namespace
 
-// The twelve entry points below read the same way, top to bottom: bind the device; refuse null
+// The thirteen entry points below read the same way, top to bottom: bind the device; refuse null
 // handles and device pointers; refuse scenes of another context or box count (require_field_scene);
 // make the plan, which holds every rule on the plain arguments and the boxes; the call's side
 // effects on its outputs (a written scene's classification keys, a cleared count); return where
@@ -236,6 +236,33 @@ int avr_scene_clump_table(avr_context* ctx, const avr_scene* labels, const avr_s
     args.sums = sums_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_clump_table(args, field != nullptr, ctx->stream);
+  });
+}
+
+int avr_scene_clump_links(avr_context* ctx, const avr_scene* labels, const avr_scene* parents,
+                          uint64_t n_clumps, uint64_t n_parents, const int32_t* box_index_lo,
+                          const int32_t* level_ratio, int n_levels, int32_t* extent_dev,
+                          uint32_t* parent_lo_dev, uint32_t* parent_hi_dev, uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(labels != nullptr && extent_dev != nullptr && totals_dev != nullptr, "null argument");
+    require((parents != nullptr) == (parent_lo_dev != nullptr) &&
+                (parents != nullptr) == (parent_hi_dev != nullptr),
+            "parent_lo_dev and parent_hi_dev are given exactly when parents is");
+    const size_t n_boxes = labels->boxes.size();
+    require_field_scene(ctx, labels, n_boxes);
+    if (parents != nullptr) require_field_scene(ctx, parents, n_boxes);
+    const avr::ClumpLinksPlan plan = avr::plan_clump_links(
+        labels->boxes.data(), parents != nullptr ? parents->boxes.data() : nullptr, n_boxes,
+        n_clumps, n_parents, box_index_lo, level_ratio, n_levels);
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::ClumpLinkArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.extent = extent_dev;
+    args.parent_lo = parent_lo_dev;
+    args.parent_hi = parent_hi_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_clump_links(args, parents != nullptr, ctx->stream);
   });
 }
 

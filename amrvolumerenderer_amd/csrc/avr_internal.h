@@ -657,6 +657,28 @@ struct ClumpTableArgs {
   unsigned long long* totals;   // [2]: outside, nonfinite, added to
 };
 int launch_clump_table(const ClumpTableArgs& args, bool has_field, void* stream);
+// The links and extents of a label field ("Clump tree"): a JointBoxDev holds the
+// labels as field 0 and the parent labels as field 1 (the labels again without a parent scene);
+// beside it, per box, where the box lies in the index space of the finest level, n_levels - 1.
+struct alignas(16) ClumpLinkBoxDev {
+  int32_t lo[3];          // box_index_lo * scale: the finest-level index of the box's first cell
+  int32_t scale;          // R_l: finest-level cells per cell of the box's level, per axis
+};
+static_assert(sizeof(ClumpLinkBoxDev) == 16, "ClumpLinkBoxDev: one 16-byte scalar load");
+struct ClumpLinkArgs {
+  const JointBoxDev* boxes;
+  const ClumpLinkBoxDev* refined;  // n_boxes, beside boxes
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  uint32_t n_clumps;            // 1 .. 2^28 - 1
+  uint32_t n_parents;           // 1 .. 2^28 - 1 with a parent scene, else 0
+  int32_t* extent;              // [6][n_clumps]: lows of x, y, z (min), then highs (max)
+  uint32_t* parent_lo;          // [n_clumps] (null without a parent scene), min
+  uint32_t* parent_hi;          // the same, max
+  unsigned long long* totals;   // [2]: labels outside, parent labels outside; added to
+};
+int launch_clump_links(const ClumpLinkArgs& args, bool has_parent, void* stream);
 
 // Isosurfaces (avr_isosurface.hip): marching tetrahedra over the cubes of cell centres.  Box b
 // enumerates the cube bases (i, j, k) in [-1, n - 1]^3 of its own index space; a base's ordinal is

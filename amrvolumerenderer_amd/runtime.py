@@ -830,6 +830,62 @@ class Scene:
                 _pointer(sums), _pointer(totals))
         return cells, sums, totals
 
+    def clump_links(self, n_clumps: int, box_index_lo, level_ratio,
+                    parents: Optional["Scene"] = None, n_parents: int = 0,
+                    extent: Optional[torch.Tensor] = None,
+                    parent_lo: Optional[torch.Tensor] = None,
+                    parent_hi: Optional[torch.Tensor] = None,
+                    totals: Optional[torch.Tensor] = None):
+        """avr_scene_clump_links with this scene as the labels: per label the index bounding box
+        in the finest level's index space and, with `parents` (the label scene of a selection that
+        contains this one, same context and box list, labels 1..n_parents), the smallest and the
+        largest parent label its cells carry.  box_index_lo: [n_boxes, 3] int32; level_ratio:
+        n_levels - 1 ints.  Returns (extent int32 [6, n_clumps]: lows of x, y, z, then highs,
+        inclusive; parent_lo, parent_hi uint32 [n_clumps] or None without parents; totals int64
+        [2]: labels that are no integer in [1, n_clumps], parent labels that are none in [1,
+        n_parents]) on the device.  Tensors handed in are combined into (min / max, totals added
+        to); new ones start at INT32_MAX / INT32_MIN, UINT32_MAX / 0 and 0.  Asynchronous on the
+        context's stream."""
+        ctx = self.ctx
+        n_clumps, n_parents = int(n_clumps), int(n_parents)
+        if n_clumps < 1:
+            raise ValueError("n_clumps must be at least 1")
+        if (parents is None) != (n_parents == 0) or n_parents < 0:
+            raise ValueError("n_parents is at least 1 with parents and 0 without")
+        index, ratios, _, _ = _level_arguments(len(self.boxes), box_index_lo, level_ratio)
+
+        def ends(shape, dtype, low, high):
+            made = torch.empty(shape, dtype=dtype, device=ctx.device)
+            made[:shape[0] // 2] = low
+            made[shape[0] // 2:] = high
+            return made
+
+        wrong = "extent must be [6, n_clumps] and totals hold two values"
+        if extent is None:
+            extent = ends((6, n_clumps), torch.int32, 2 ** 31 - 1, -2 ** 31)
+        extent = _output(ctx, extent, torch.int32, (6, n_clumps), "extent", wrong_size=wrong,
+                         exact=True)
+        totals = _output(ctx, totals, torch.int64, (2,), "totals", torch.zeros, wrong)
+        if parents is not None:
+            wrong = "parent_lo and parent_hi must hold n_clumps values"
+            if parent_lo is None:       # all bits set: UINT32_MAX
+                parent_lo = torch.full((n_clumps,), -1, dtype=torch.int32,
+                                       device=ctx.device).view(torch.uint32)
+            if parent_hi is None:
+                parent_hi = torch.zeros((n_clumps,), dtype=torch.int32,
+                                        device=ctx.device).view(torch.uint32)
+            parent_lo = _output(ctx, parent_lo, torch.uint32, (n_clumps,), "parent_lo",
+                                wrong_size=wrong)
+            parent_hi = _output(ctx, parent_hi, torch.uint32, (n_clumps,), "parent_hi",
+                                wrong_size=wrong)
+        elif parent_lo is not None or parent_hi is not None:
+            raise ValueError("parent_lo and parent_hi are given exactly when parents is")
+        _native(ctx, "avr_scene_clump_links", ctx._handle, self._handle,
+                parents._handle if parents is not None else None, n_clumps, n_parents,
+                _ints(index), _ints(ratios), int(ratios.size) + 1, _pointer(extent),
+                _pointer(parent_lo), _pointer(parent_hi), _pointer(totals))
+        return extent, parent_lo, parent_hi, totals
+
     def isosurface(self, value: float, box_index_lo, level_ratio, level_cell_size, prob_lo,
                    sample: Optional["Scene"] = None, capacity: int = 0,
                    counts: Optional[torch.Tensor] = None):

@@ -1229,6 +1229,33 @@ int avr_scene_clump_table(avr_context *ctx, const avr_scene *labels, const avr_s
                           uint64_t n_clumps, int n_levels, uint64_t *cells_dev, double *sums_dev,
                           uint64_t *totals_dev);
 
+/* The links and extents of a label field ("Clump tree").  `labels` is a label scene
+ * of ctx as avr_scene_clumps writes one, `parents` (or NULL) the label scene of a selection that
+ * contains it -- the same field over a lower threshold -- with the same box list; box_index_lo,
+ * level_ratio and n_levels as avr_scene_clumps takes them.  With R_l = ratio[l] * ... *
+ * ratio[n_levels - 2] (R of the last level is 1), a cell of level l whose index in its level is
+ * (I, J, K) covers [I R_l, (I + 1) R_l - 1] per axis in the index space of level n_levels - 1.
+ * For every cell, in this order: a label whose bits are +0.0 is skipped; a label that is not an
+ * integer in [1, n_clumps] adds 1 to totals_dev[0] and the cell is done; with `parents`, a parent
+ * label that is not an integer in [1, n_parents] (+0.0 and NaN included) adds 1 to totals_dev[1]
+ * and the cell contributes nothing; otherwise, with c the label and p the parent label,
+ * extent_dev[a * n_clumps + c - 1] = min(., low end along axis a), extent_dev[(3 + a) * n_clumps +
+ * c - 1] = max(., high end) (int32 [6][n_clumps]) and, with `parents`, parent_lo_dev[c - 1] =
+ * min(., p), parent_hi_dev[c - 1] = max(., p) (uint32 [n_clumps], NULL exactly when parents is).
+ * Every output is combined into, never initialised: start lows and parent_lo at the type's
+ * maximum, highs at INT32_MIN, parent_hi and totals_dev (two uint64, added to) at 0.  All results
+ * are minima and maxima of integers: exact, equal bits for equal arguments.
+ * AVR_ERR_INVALID_ARGUMENT, before any device work and with the outputs untouched, in this
+ * order: n_clumps outside [1, 2^28); n_parents outside [1, 2^28) with parents, not 0 without;
+ * n_levels outside [1, 16]; the box rules on the labels; a ratio below 2; an index range that
+ * leaves [-2^30, 2^30); a refined index range, I R_l .. (I + n) R_l - 1, that leaves it; scenes
+ * that are not congruent.  Nothing is launched for a scene without cells.  Asynchronous on the
+ * context's stream. */
+int avr_scene_clump_links(avr_context *ctx, const avr_scene *labels, const avr_scene *parents,
+                          uint64_t n_clumps, uint64_t n_parents, const int32_t *box_index_lo,
+                          const int32_t *level_ratio, int n_levels, int32_t *extent_dev,
+                          uint32_t *parent_lo_dev, uint32_t *parent_hi_dev, uint64_t *totals_dev);
+
 /* ---- isosurfaces ("Isosurface") --------------------------------------------------- */
 
 /* The isosurface field == value of `field` (a scene of ctx; raw f64 cells, no transform) by
