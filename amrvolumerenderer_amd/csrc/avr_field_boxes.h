@@ -19,7 +19,10 @@ struct FieldView {
   const double* cells = nullptr;
   int32_t jstride = 0, kstride = 0;  // element strides (Array4)
   int32_t last = 0;                  // element offset of the box's last cell, < 2^28
-  bool paired = false;               // cells 16-byte aligned and both strides even: f64 pairs load
+  // cells 16-byte aligned and both strides even: f64 pairs load.  The rule of every kernel that
+  // forms element offsets; classify_tile (avr_kernels.hip), which forms byte offsets, also caps
+  // jstride below 2^27 and says why.
+  bool paired = false;
 };
 
 inline void require_box(bool condition, const char* message) {

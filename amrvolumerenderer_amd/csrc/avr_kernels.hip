@@ -1203,6 +1203,12 @@ constexpr int kRawBufferFlags = 0x00020000;  // word 3 of a raw (untyped) gfx9 b
 // read once per frame, so non-temporal.  Measured beside the march, the policy does not matter
 // (0, nt, sc1, nt|sc1, sc0|sc1|nt: 1.049-1.063 ms per frame, profiles/experiments_rounds_1_to_3.md section 3).
 constexpr int kStreamingLoad = 2;
+// num_records of the cell loads' buffer resource: all of them, 0xffffffff.  What bounds the loads is
+// the host's span rule (field_view, plan_frame): every cell's byte offset is at most 2^31 - 8.  A
+// paired box at that limit loads its last two cells as 16 bytes at offset 2^31 - 16, ending at byte
+// 2^31; with 2^31 - 1 records the range check of gfx950 gave zeros for that load and the two cells
+// classified as 0.0 (tests/test_wide_views_gpu.py, the cases at the span limit).
+constexpr int kAllRecords = -1;
 
 // One tile (4 planes x 4 rows x 128 cells) of the classify pass; `staged`: 16 bricklets of LDS.
 template <bool SIMPLE>
@@ -1243,7 +1249,14 @@ __device__ __forceinline__ void classify_tile(
   const uint32_t jstride = static_cast<uint32_t>(box.jstride);
   const uint32_t kstride = static_cast<uint32_t>(box.kstride);
   const int t = static_cast<int>(threadIdx.x);
-  // 16-byte loads (two cells per lane) need every row to start 16-byte aligned
+  // 16-byte loads (two cells per lane) need every row to start 16-byte aligned.  The cap on the
+  // row stride is this kernel's alone: its pair paths address by 32-bit BYTE offsets (the buffer
+  // loads below), and below 2^27 the row term jj * jstride * 8 of every brick row jj <= 3 fits them,
+  // also for the rows past ny that `valid` masks, whether or not the product is formed ahead of the
+  // select.  The pair tests of the statistics scans (avr_scene_stats.hip) and FieldView::paired
+  // (avr_field_boxes.h) have no cap because those kernels form 32-bit ELEMENT offsets of valid
+  // cells only, which the pointer arithmetic widens to 64 bits.  A box at or past the cap has at
+  // most two rows per plane (the span rule), so the single-cell path costs it nothing.
   const bool paired = ((reinterpret_cast<uintptr_t>(box.cells) & 15u) == 0) &&
                       ((jstride & 1u) == 0) && ((kstride & 1u) == 0) && jstride < (1u << 27);
   typedef double double2_t __attribute__((ext_vector_type(2)));
@@ -1261,7 +1274,7 @@ __device__ __forceinline__ void classify_tile(
     const uint32_t lane_bytes = (static_cast<uint32_t>(chunk * kClassifyChunk + xi) +
                                  static_cast<uint32_t>(bj * kBrickY + jj) * jstride) * 8u;
     const __amdgpu_buffer_rsrc_t resource = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<double*>(box.cells), 0, 0x7fffffff, kRawBufferFlags);
+        const_cast<double*>(box.cells), 0, kAllRecords, kRawBufferFlags);
     double2_t raw[4];
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
@@ -1308,12 +1321,13 @@ __device__ __forceinline__ void classify_tile(
               : 0u;
     // buffer addressing: the box's cells as the resource, the tile's first pair + the lane's
     // offset in the vector offset, the plane in the scalar offset (host: spans stay below 2^28
-    // cells, so every byte offset fits 31 bits) -- no vector address arithmetic per pass
+    // cells, so every byte offset fits 31 bits and a 16-byte load ends at byte 2^31 at the most)
+    // -- no vector address arithmetic per pass
     const uint32_t row0 = (static_cast<uint32_t>(i0) - lead) +
                           static_cast<uint32_t>(bj * kBrickY) * jstride;
     const uint32_t lane_bytes = (row0 + lane_cell) * 8u;
     const __amdgpu_buffer_rsrc_t resource = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<double*>(box.cells), 0, 0x7fffffff, kRawBufferFlags);
+        const_cast<double*>(box.cells), 0, kAllRecords, kRawBufferFlags);
     // All four planes' loads are issued before the first is used: four round trips in flight per
     // lane, so that a few resident workgroups already keep HBM busy -- what the classify pass
     // gets when it shares the CUs with the march of the previous frame.

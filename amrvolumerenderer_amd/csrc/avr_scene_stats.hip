@@ -50,6 +50,8 @@ __device__ __forceinline__ void for_each_cell(const TileCoords& tile, F&& visit)
   const uint32_t jstride = static_cast<uint32_t>(box.jstride);
   const uint32_t kstride = static_cast<uint32_t>(box.kstride);
   const int t = static_cast<int>(threadIdx.x);
+  // (no cap on jstride as in classify_tile, avr_kernels.hip: `at` below is an element offset of a
+  // valid cell, below 2^28 by the span rule, and the pointer arithmetic is 64 bits wide)
   const bool paired = ((reinterpret_cast<uintptr_t>(box.cells) & 15u) == 0) &&
                       ((jstride & 1u) == 0) && ((kstride & 1u) == 0);
   if (paired) {
