@@ -1,6 +1,7 @@
 // C ABI of the MI355X volume-rendering path (include/avr_hip.h).  Thin: validates, runs the
 // host prologue (avr_host.cpp), stages the per-frame descriptors and launches the kernels
-// (avr_kernels.hip) on the context's stream.  No CPU compute fallback exists behind it.
+// (avr_kernels.hip) on the context's stream; what a frame stages and launches is planned on the
+// host (avr_frame_launch.h).  No CPU compute fallback exists behind it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -118,417 +119,128 @@ using avr::bind_device;
 using avr::guarded;
 using avr::require;
 
+using avr::kClassify;
+using avr::kMarch;
+
 namespace {
 
-enum Phase { kClassify = 1, kMarch = 2 };
 constexpr avr::FrameKind kVolume = avr::FrameKind::kVolume;
 
-// A frame cut into depth-ordered chunks of its global layer order (avr_classify_plan_chunked /
-// avr_march_plan_chunked): chunk k is classified by launch k of the classify call, which records
-// events[k] behind it, and marched by launch k of the march call, which waits for events[k] first.
-struct FrameChunks {
+// The shape of a frame call (avr::FrameChunks, avr_frame_launch.h, which says what the shapes are)
+// with what only the device and the runtime can use: the caller's events and device arrays.
+struct ChunkCall {
   int count = 1;
   hipEvent_t const* events = nullptr;  // count events, or null (both calls on one stream)
-  bool first_alone = false;            // classify: chunk 0 has the GPU to itself (no LDS reserve)
-  // avr_render_plan_culled: ONE call queues classify 0, march 0, classify 1, march 1 ... on the
-  // context's stream; march k flags the boxes behind chunk k that a ray may still sample in
-  // visibility[k * n_order + position] (count * n_order bytes, cleared by the call), classify
-  // k + 1 leaves out the boxes of its chunk whose flag is 0.
-  uint8_t* visibility = nullptr;
-  // A speculative frame (avr_classify_plan_flagged / avr_march_plan_speculative; count == 1):
-  // the classify pass takes only the positions of the layer order whose flag is set (and, with a
-  // gate, does nothing at all unless *gate != 0: the repair pass), the march checks and records.
+  bool first_alone = false;
+  uint8_t* visibility = nullptr;       // avr_render_plan_culled: count * n_order bytes
   const uint8_t* classify_flags = nullptr;
   const uint32_t* classify_gate = nullptr;
-  // ... or the positions themselves, known on the host (avr_classify_plan_positions): a launch of
-  // exactly their tiles
   const int32_t* classify_positions = nullptr;
   int n_classify_positions = 0;
   const avr_speculation* speculation = nullptr;
+
+  avr::FrameChunks shape() const {
+    avr::FrameChunks host;
+    host.count = count;
+    host.first_alone = first_alone;
+    host.events = events != nullptr;
+    host.culled = visibility != nullptr;
+    host.flags = classify_flags != nullptr;
+    host.classify_positions = classify_positions;
+    host.n_classify_positions = n_classify_positions;
+    host.speculation = speculation;
+    return host;
+  }
 };
 
 using VolumeOut = avr::FoldOutputs<avr::FrameKind::kVolume>;
 using MaxOut = avr::FoldOutputs<avr::FrameKind::kMaxIntensity>;
 using SumOut = avr::FoldOutputs<avr::FrameKind::kProjection>;
 
-// What render() is asked for -- the classify pass and/or the march of one frame -- in parts that a
-// caller fills in one expression each.
-struct FrameBoxes {  // the boxes and how they are seen
-  const avr_box* boxes;
-  int n_boxes;
-  const avr_scalar_transform& transform;
-  const avr_paint_params& params;
-  const avr_camera& camera;
-};
-struct FrameRuns {  // their global layer order cut into runs, the runs' tables, the exchange's pieces
-  const int32_t* box_order;
-  int n_order;
-  const int32_t* run_end;
-  int n_runs, n_pieces;
-  const std::vector<avr::RunRectDev>& rects;
-  const std::vector<avr::RunBlockDev>& blocks;  // n_runs x n_pieces
-  const std::vector<avr::RunSpanDev>* spans;    // a tightened plan's, or null
-  const avr::PieceMapDev& pieces;
-};
-struct FrameTarget {  // the scene whose classified slot the frame uses, and where the results go
-  avr_scene* scene;
-  int slot;
-  float* out_layers;
-  uint64_t* samples_out;  // may be null
-  avr::FramePlan* cached;  // null, or the host prologue kept from a frame's classify call to its march
-};
-struct RenderRequest {
-  int phases;  // Phase bits
-  // kMaxIntensity: one march launch, never chunked, culled or speculative.  kProjection: the same,
-  // over the raw cells: march only, the classified volume is neither read nor made.
-  avr::FrameKind kind;
-  FrameBoxes in;
-  FrameRuns runs;
-  FrameTarget to;
-};
-
-// Positions [bounds[k], bounds[k + 1]) of the global layer order for chunk k: equal shares of the
-// classify pass's work (tiles = cells), so that classifying chunk k + 1 takes about as long as
-// any other; a function of the plan alone -- the classify and the march call cut alike.
-std::vector<int> chunk_bounds(const avr::FramePlan& plan, const int32_t* box_order, int n_order,
-                              int n_chunks) {
-  std::vector<int> bounds(static_cast<size_t>(n_chunks) + 1, n_order);
-  bounds[0] = 0;
-  auto tiles_of = [&](int position) -> uint64_t {
-    const size_t b = static_cast<size_t>(box_order[position]);
-    return plan.classify_tile_begin[b + 1] - plan.classify_tile_begin[b];
-  };
-  uint64_t total = 0;
-  for (int i = 0; i < n_order; ++i) total += tiles_of(i);
-  uint64_t seen = 0;
-  int k = 1;
-  for (int i = 0; i < n_order && k < n_chunks; ++i) {
-    seen += tiles_of(i);
-    while (k < n_chunks && seen * static_cast<uint64_t>(n_chunks) >= total * static_cast<uint64_t>(k)) {
-      bounds[static_cast<size_t>(k++)] = i + 1;
-    }
-  }
-  return bounds;
-}
-
-// Upper bound of the march's workgroups: a work item per super-tile of the screen and run, padded
-// to whole rounds of the XCDs, four workgroups each (build_march_items, avr_host.cpp).
-int64_t march_workgroups_bound(int width, int height, int n_runs) {
-  const int64_t span = avr::kTile * avr::kSuperTileSide;
-  const int64_t super_tiles = ((width + span - 1) / span) * ((height + span - 1) / span);
-  const int64_t items = (super_tiles * std::max(n_runs, 0) + avr::kXcds - 1) / avr::kXcds * avr::kXcds;
-  return items * avr::kSuperTileTiles;
-}
-
 // One frame's device work for a list of boxes: the classify pass and/or the march, queued on the
-// context's stream.  This is where a frame's kind enters the native layer, so what the kinds other
-// than kVolume exclude is checked here and nowhere below.
-int render(avr_context* ctx, const RenderRequest& frame, const FrameChunks& chunks = FrameChunks{}) {
-  const FrameBoxes& in = frame.in;
-  const FrameRuns& runs = frame.runs;
-  const FrameTarget& to = frame.to;
-  int phases = frame.phases;
-  require(runs.n_runs >= 0 && runs.n_order >= 0 && runs.n_pieces >= 1, "invalid run description");
-  require(chunks.count >= 1 && chunks.count <= AVR_MAX_FRAME_CHUNKS, "invalid chunk count");
-  require(chunks.count == 1 || phases == kClassify || phases == kMarch || chunks.visibility != nullptr,
-          "a chunked frame is classified and marched by separate calls (or by avr_render_plan_culled)");
-  require(to.slot >= 0 && to.slot < AVR_CLASSIFIED_SLOTS, "classified slot out of range");
-  require(frame.kind == avr::FrameKind::kVolume ||
-              (chunks.count == 1 && chunks.speculation == nullptr),
-          "a maximum-intensity or column-projection march is one launch: no chunks, no speculation");
-  require(frame.kind != avr::FrameKind::kProjection || phases == kMarch,
-          "a column-projection march has no classify pass");
-  avr::FramePlan local;
-  avr::FramePlan& plan = to.cached ? *to.cached : local;
-  if (plan.boxes.size() != static_cast<size_t>(in.n_boxes) || !plan.ready) {
-    avr::plan_frame(in.boxes, in.n_boxes, in.transform, in.params, in.camera, &plan);
-    plan.march_items_ready = false;
-  }
-  if (runs.n_runs == 0) return AVR_OK;
-  require(plan.n_tables <= avr::kMaxLdsTables,
-          "too many distinct sampling levels for the LDS transfer-function cache");
-
-  avr::RenderLaunch launch;
-  launch.consts = plan.consts;
-  launch.n_boxes = in.n_boxes;
-  launch.n_classify_tiles = plan.classify_tile_begin.back();
-  launch.classify_lds_pad = ctx->classify_lds_pad;
-  // (streamed only when the classified volume is more than the 256 MB memory-side cache holds:
-  // config-2's 134 MB, stored plainly, are still there when its march comes a frame later --
-  // 0.378 ms per frame against 0.465 streamed; config-4's 370 MB are not, 0.967 -> 0.958)
-  launch.classify_stream_stores =
-      (ctx->classify_stream_stores && plan.classified_bytes > (256ull << 20)) ? 1 : 0;
-  launch.classified =
-      frame.kind == avr::FrameKind::kProjection
-          ? nullptr
-          : to.scene->classified_slot(to.slot, plan.classified_bytes, ctx->stream);
-
-  if ((phases & kClassify) && to.scene->cache_classification) {
-    // everything classify_kernel reads besides the cells themselves
-    std::vector<uint64_t> key;
-    auto bits = [](double v) {
-      uint64_t u;
-      std::memcpy(&u, &v, sizeof(u));
-      return u;
-    };
-    const avr::FrameConsts& fc = plan.consts;
-    key.reserve(12 + plan.boxes.size() * 4);
-    for (double v : {static_cast<double>(fc.range_min), static_cast<double>(fc.inverse_range),
-                     static_cast<double>(fc.clip_start), fc.positive_floor, fc.norm_min,
-                     fc.inv_norm_span}) {
-      key.push_back(bits(v));
-    }
-    key.push_back(static_cast<uint64_t>(fc.apply_clip) | (static_cast<uint64_t>(fc.log_scale) << 8) |
-                  (static_cast<uint64_t>(fc.normalize) << 16));
-    for (const avr::BoxDev& dev : plan.boxes) {
-      key.push_back(reinterpret_cast<uint64_t>(dev.cells));
-      key.push_back((static_cast<uint64_t>(static_cast<uint32_t>(dev.jstride)) << 32) |
-                    static_cast<uint32_t>(dev.kstride));
-      key.push_back((static_cast<uint64_t>(dev.nx) << 42) | (static_cast<uint64_t>(dev.ny) << 21) |
-                    static_cast<uint64_t>(dev.nz));
-      key.push_back(dev.cls_offset);
-    }
-    if (key == to.scene->classified_key[to.slot]) {
-      phases &= ~kClassify;  // the slot already holds exactly this classification
-      if (phases == 0) return AVR_OK;
-    } else {
-      to.scene->classified_key[to.slot] = std::move(key);
-    }
-  }
-
-  // scratch, reused across frames; a frame plan's prologue keeps its own (they depend on the
-  // plan alone)
-  const bool keep_items = to.cached != nullptr;
-  std::vector<avr::MarchItemDev>& items = keep_items ? plan.march_items : ctx->march_items;
-  size_t bytes = plan.boxes.size() * sizeof(avr::BoxDev);
-  if (phases & kClassify) bytes += plan.classify_tile_begin.size() * sizeof(uint32_t);
-  if (phases & kMarch) {
-    require(to.out_layers != nullptr, "null output image");
-    require(runs.n_runs == 0 || (runs.run_end != nullptr), "null run_end");
-    require(runs.n_order == 0 || (runs.box_order != nullptr), "null box_order");
-    require(runs.rects.size() == static_cast<size_t>(runs.n_runs) &&
-                runs.blocks.size() == static_cast<size_t>(runs.n_runs) * runs.n_pieces,
-            "run tables do not match the runs");
-    if (!(keep_items && plan.march_items_ready)) {
-      int previous = 0;
-      for (int r = 0; r < runs.n_runs; ++r) {
-        require(runs.run_end[r] >= previous && runs.run_end[r] <= runs.n_order,
-                "run_end must be non-decreasing");
-        previous = runs.run_end[r];
-      }
-      require(runs.run_end[runs.n_runs - 1] == runs.n_order, "runs must cover box_order");
-      for (int i = 0; i < runs.n_order; ++i) {
-        require(runs.box_order[i] >= 0 && runs.box_order[i] < in.n_boxes, "box_order entry out of range");
-      }
-      avr::build_march_items(plan, runs.box_order, runs.run_end, runs.n_runs, runs.rects, &items);
-      plan.march_items_ready = keep_items;
-    }
-    bytes += plan.tables.size() * sizeof(float) + static_cast<size_t>(runs.n_order + runs.n_runs) * 4 +
-             static_cast<size_t>(runs.n_order) * 16 +
-             items.size() * sizeof(avr::MarchItemDev) +
-             runs.rects.size() * sizeof(avr::RunRectDev) + runs.blocks.size() * sizeof(avr::RunBlockDev) +
-             (runs.spans != nullptr ? runs.spans->size() * sizeof(avr::RunSpanDev) : 0);
-  }
-  // chunked: the positions of every chunk, and for the classify call the chunks' box lists (the
-  // local boxes in global layer order ARE the lists: chunk k is box_order[bounds[k] .. bounds[k+1]))
-  // with one prefix sum of classify workgroups per chunk
-  const bool chunked = chunks.count > 1;
-  std::vector<int> bounds;
-  std::vector<uint32_t> chunk_tile_begin;  // chunk k: entries bounds[k] + k .. bounds[k + 1] + k
-  if (chunked) {
-    require(runs.n_order == 0 || runs.box_order != nullptr, "null box_order");
-    for (int i = 0; i < runs.n_order; ++i) {
-      require(runs.box_order[i] >= 0 && runs.box_order[i] < in.n_boxes, "box_order entry out of range");
-    }
-    bounds = chunk_bounds(plan, runs.box_order, runs.n_order, chunks.count);
-    if (phases & kClassify) {
-      chunk_tile_begin.reserve(static_cast<size_t>(runs.n_order + chunks.count));
-      for (int k = 0; k < chunks.count; ++k) {
-        uint32_t sum = 0;
-        chunk_tile_begin.push_back(0u);
-        for (int i = bounds[static_cast<size_t>(k)]; i < bounds[static_cast<size_t>(k) + 1]; ++i) {
-          const size_t b = static_cast<size_t>(runs.box_order[i]);
-          sum += plan.classify_tile_begin[b + 1] - plan.classify_tile_begin[b];
-          chunk_tile_begin.push_back(sum);
-        }
-      }
-      bytes += chunk_tile_begin.size() * sizeof(uint32_t) + static_cast<size_t>(runs.n_order) * 4;
-    }
-  }
-  // a flagged classify pass: the local boxes in layer order as ONE list under its own prefix sum
-  std::vector<uint32_t> listed_tile_begin;
-  std::vector<int32_t> listed_boxes;
-  const bool positioned = (phases & kClassify) && chunks.classify_positions != nullptr;
-  const bool flagged = (phases & kClassify) && (chunks.classify_flags != nullptr || positioned);
-  if (flagged) {
-    require(chunks.count == 1, "a flagged classify pass is not cut into chunks");
-    require(runs.n_order == 0 || runs.box_order != nullptr, "null box_order");
-    require(!(positioned && chunks.classify_flags != nullptr), "flags or positions, not both");
-    const int n_listed = positioned ? chunks.n_classify_positions : runs.n_order;
-    require(n_listed >= 0 && n_listed <= runs.n_order, "too many positions");
-    listed_tile_begin.reserve(static_cast<size_t>(n_listed) + 1);
-    listed_boxes.reserve(static_cast<size_t>(n_listed));
-    uint32_t sum = 0;
-    listed_tile_begin.push_back(0u);
-    int previous = -1;
-    for (int i = 0; i < n_listed; ++i) {
-      const int position = positioned ? chunks.classify_positions[i] : i;
-      require(position > previous && position < runs.n_order, "positions must ascend within the layer order");
-      previous = position;
-      require(runs.box_order[position] >= 0 && runs.box_order[position] < in.n_boxes,
-              "box_order entry out of range");
-      const size_t b = static_cast<size_t>(runs.box_order[position]);
-      sum += plan.classify_tile_begin[b + 1] - plan.classify_tile_begin[b];
-      listed_tile_begin.push_back(sum);
-      listed_boxes.push_back(runs.box_order[position]);
-    }
-    bytes += listed_tile_begin.size() * sizeof(uint32_t) + listed_boxes.size() * 4;
-  }
-  if ((phases & kMarch) && chunks.speculation != nullptr) {
-    bytes += sizeof(avr::MarchSpecDev) + static_cast<size_t>(runs.n_order);
-  }
-  avr::StagingRing& staging = ctx->staging;
-  staging.begin(bytes, 16);
-  launch.boxes_dev = staging.add(plan.boxes.data(), plan.boxes.size());
-  const uint32_t* chunk_tile_begin_dev = nullptr;
-  const int32_t* chunk_box_list_dev = nullptr;
-  if (phases & kClassify) {
-    launch.tile_begin_dev =
-        staging.add(plan.classify_tile_begin.data(), plan.classify_tile_begin.size());
-    if (chunked) {
-      chunk_tile_begin_dev = staging.add(chunk_tile_begin.data(), chunk_tile_begin.size());
-      chunk_box_list_dev = staging.add(runs.box_order, static_cast<size_t>(runs.n_order));
-    }
-    if (flagged) {
-      launch.tile_begin_dev = staging.add(listed_tile_begin.data(), listed_tile_begin.size());
-      launch.box_list_dev = staging.add(listed_boxes.data(), listed_boxes.size());
-      launch.n_classify_boxes = static_cast<int>(listed_boxes.size());
-      launch.n_classify_tiles = listed_tile_begin.back();
-      launch.visible_in = chunks.classify_flags;  // (null with positions: all of them)
-      launch.classify_gate = chunks.classify_gate;
-    }
-  }
-  if (phases & kMarch) {
-    launch.tables_dev = staging.add(plan.tables.data(), plan.tables.size());
-    launch.n_tables = plan.n_tables;
-    launch.order_dev = staging.add(runs.box_order, static_cast<size_t>(runs.n_order));
-    {
-      // the boxes' screen rectangles in that order: what the march's cull reads 64 at a time
-      std::vector<int32_t>& rects = ctx->order_rects;
-      rects.resize(static_cast<size_t>(runs.n_order) * 4);
-      for (int i = 0; i < runs.n_order; ++i) {
-        const avr::BoxDev& dev = plan.boxes[static_cast<size_t>(runs.box_order[i])];
-        std::copy(dev.rect, dev.rect + 4, rects.begin() + static_cast<std::ptrdiff_t>(i) * 4);
-      }
-      launch.order_rects_dev = staging.add(rects.data(), rects.size());
-    }
-    launch.run_end_dev = staging.add(runs.run_end, static_cast<size_t>(runs.n_runs));
-    launch.n_order = runs.n_order;
-    launch.n_runs = runs.n_runs;
-    launch.n_pieces = runs.n_pieces;
-    launch.run_rects_dev = staging.add(runs.rects.data(), runs.rects.size());
-    launch.run_blocks_dev = staging.add(runs.blocks.data(), runs.blocks.size());
-    launch.run_spans_dev = (runs.spans != nullptr && !runs.spans->empty())
-                               ? staging.add(runs.spans->data(), runs.spans->size())
-                               : nullptr;
-    launch.pieces = runs.pieces;
-    launch.out_layers = to.out_layers;
-    launch.samples_out = reinterpret_cast<unsigned long long*>(to.samples_out);
-    launch.counters = reinterpret_cast<unsigned long long*>(ctx->march_counters);
-    if (chunks.speculation != nullptr) {
-      require(chunks.count == 1 && to.samples_out == nullptr,
-              "a speculative march is one launch and counts no samples");
-      const avr_speculation& given = *chunks.speculation;
-      require(given.classified == nullptr || given.classified_host == nullptr,
-              "the flags are on the device or on the host, not both");
-      const bool checks = given.classified != nullptr || given.classified_host != nullptr;
-      require(!checks || (given.missed != nullptr && given.miss_count != nullptr),
-              "a speculative march that checks flags needs somewhere to report misses");
-      avr::MarchSpecDev spec{};
-      spec.classified = given.classified_host != nullptr
-                            ? staging.add(given.classified_host, static_cast<size_t>(runs.n_order))
-                            : given.classified;
-      spec.visited = given.visited;
-      spec.missed = given.missed;
-      spec.miss_count = given.miss_count;
-      spec.host_miss_flag = given.host_miss_flag;
-      spec.gate = given.gate;
-      // (the first pass marks, the gated pass reads: one array, a byte per workgroup of the grid)
-      spec.dirty_blocks_out = given.gate == nullptr ? given.dirty_workgroups : nullptr;
-      spec.dirty_blocks = given.gate != nullptr ? given.dirty_workgroups : nullptr;
-      if (given.dirty_workgroups != nullptr) {
-        require(static_cast<int64_t>(items.size()) * avr::kSuperTileTiles <=
-                    march_workgroups_bound(in.params.width, in.params.height, runs.n_runs),
-                "more march workgroups than avr_march_plan_workgroups promised");
-      }
-      launch.spec_dev = staging.add(&spec, 1);
-      launch.spec_is_repair = given.gate != nullptr;
-    }
-    launch.items_dev = staging.add(items.data(), items.size());
-    launch.n_items = static_cast<uint32_t>(items.size());
-    launch.workgroups_per_cu = ctx->march_workgroups_per_cu;
-    launch.kind = frame.kind;
-    launch.only_mode = plan.boxes.empty() ? -1 : plan.boxes[0].index_mode;
-    for (const avr::BoxDev& dev : plan.boxes) {
-      if (dev.index_mode != launch.only_mode) launch.only_mode = -1;
-    }
-    ctx->last_only_mode = launch.only_mode;
-  }
-  staging.commit(ctx->stream);
-  if (chunked) {
-    const uint32_t reserve = launch.classify_lds_pad;
-    if (chunks.visibility != nullptr) {
-      avr::hip_check(hipMemsetAsync(chunks.visibility, 0,
-                                    static_cast<size_t>(chunks.count) * static_cast<size_t>(runs.n_order),
-                                    ctx->stream), "hipMemsetAsync(visibility)");
-    }
-    for (int k = 0; k < chunks.count; ++k) {
-      const int first = bounds[static_cast<size_t>(k)], last = bounds[static_cast<size_t>(k) + 1];
-      if (phases & kClassify) {
-        // (what the march launch of the chunk before found still visible of this chunk's boxes)
-        launch.visible_in = (chunks.visibility != nullptr && k > 0)
-                                ? chunks.visibility + static_cast<size_t>(k - 1) * runs.n_order + first
-                                : nullptr;
-        if (last > first) {
-          launch.box_list_dev = chunk_box_list_dev + first;
-          launch.n_classify_boxes = last - first;
-          launch.tile_begin_dev = chunk_tile_begin_dev + first + k;
-          launch.n_classify_tiles = chunk_tile_begin[static_cast<size_t>(last + k)];
-          launch.classify_lds_pad = (k == 0 && chunks.first_alone) ? 0u : reserve;
-          const int status = avr::launch_classify(launch, ctx->stream);
-          if (status != AVR_OK) return status;
-        }
-        if (chunks.events != nullptr) {
-          avr::hip_check(hipEventRecord(chunks.events[k], ctx->stream), "hipEventRecord(chunk)");
-        }
-      }
-      if (phases & kMarch) {
-        launch.visible_out = (chunks.visibility != nullptr && k + 1 < chunks.count)
-                                 ? chunks.visibility + static_cast<size_t>(k) * runs.n_order
-                                 : nullptr;
-        if (chunks.events != nullptr && !(phases & kClassify)) {
-          avr::hip_check(hipStreamWaitEvent(ctx->stream, chunks.events[k], 0), "hipStreamWaitEvent(chunk)");
-        }
-        // (the first launch stores every pixel of the runs' layers; the later ones resume them)
-        // (with occlusion culling every chunk's march is launched: it is what flags the boxes of
-        // the chunks behind it -- flags left at 0 would mean "nobody samples them")
-        if (last > first || k == 0 || chunks.visibility != nullptr) {
-          launch.pos_begin = first;
-          launch.pos_end = last;
-          launch.resume = k > 0 ? 1 : 0;
-          const int status = avr::launch_march(launch, ctx->stream);
-          if (status != AVR_OK) return status;
-        }
-      }
-    }
+// context's stream.  Every rule, count, table and the list of launches is the frame's launch plan
+// (avr_frame_launch.h, host only, tested without a GPU) -- it is also where a frame's kind enters
+// the native layer, so what the kinds other than kVolume exclude is checked there and nowhere
+// below.  What is left here needs the device: the scene's classified slot and its key, the staging
+// of the plan's tables, the caller's addresses, and the launches and events in the plan's order.
+int render(avr_context* ctx, avr_scene* scene, const avr::RenderRequest& frame,
+           const ChunkCall& chunks = ChunkCall{}) {
+  avr::FrameLaunchPlan& plan = ctx->frame_launch;
+  if (!plan.open(frame, chunks.shape(), ctx->classify_lds_pad, ctx->classify_stream_stores,
+                 ctx->march_workgroups_per_cu)) {
     return AVR_OK;
   }
-  if (phases & kClassify) {
-    const int status = avr::launch_classify(launch, ctx->stream);
-    if (status != AVR_OK) return status;
+  const int slot = frame.to.slot;
+  uint8_t* classified =
+      plan.needs_classified
+          ? scene->classified_slot(slot, plan.prologue->classified_bytes, ctx->stream)
+          : nullptr;
+  if ((plan.phases & kClassify) && scene->cache_classification) {
+    std::vector<uint64_t> key = avr::classification_key(*plan.prologue);
+    if (key == scene->classified_key[slot]) {
+      plan.phases &= ~kClassify;  // the slot already holds exactly this classification
+      if (plan.phases == 0) return AVR_OK;
+    } else {
+      scene->classified_key[slot] = std::move(key);
+    }
   }
-  if (phases & kMarch) return avr::launch_march(launch, ctx->stream);
+  plan.finish();
+
+  avr::RenderLaunch launch = plan.launch;
+  avr::MarchSpecDev spec{};
+  if (chunks.speculation != nullptr) spec = avr::speculation_record(*chunks.speculation);
+  avr::stage_tables(ctx, plan, &launch, &spec);
+  launch.classified = classified;
+  launch.out_layers = frame.to.out_layers;
+  launch.samples_out = reinterpret_cast<unsigned long long*>(frame.to.samples_out);
+  launch.counters = reinterpret_cast<unsigned long long*>(ctx->march_counters);
+  if (plan.flagged) {
+    launch.visible_in = chunks.classify_flags;  // (null with positions: all of them)
+    launch.classify_gate = chunks.classify_gate;
+  }
+  if (plan.phases & kMarch) ctx->last_only_mode = launch.only_mode;
+  if (plan.visibility_bytes != 0) {
+    avr::hip_check(hipMemsetAsync(chunks.visibility, 0, plan.visibility_bytes, ctx->stream),
+                   "hipMemsetAsync(visibility)");
+  }
+  for (const avr::FrameStep& step : plan.steps) {
+    if (step.wait_event >= 0) {
+      avr::hip_check(hipStreamWaitEvent(ctx->stream, chunks.events[step.wait_event], 0),
+                     "hipStreamWaitEvent(chunk)");
+    }
+    if (step.launches) {
+      avr::RenderLaunch one = launch;
+      step.apply(chunks.visibility, &one);
+      const int status = step.march ? avr::launch_march(one, ctx->stream)
+                                    : avr::launch_classify(one, ctx->stream);
+      if (status != AVR_OK) return status;
+    }
+    if (step.record_event >= 0) {
+      avr::hip_check(hipEventRecord(chunks.events[step.record_event], ctx->stream),
+                     "hipEventRecord(chunk)");
+    }
+  }
   return AVR_OK;
+}
+
+// The run tables of a fold, staged in one batch: rectangles, blocks and, for a tightened plan, the
+// blocks' rows (`spans` null or empty: none, and the launch's address stays null).
+struct FoldTables {
+  const std::vector<avr::RunRectDev>& rects;
+  const std::vector<avr::RunBlockDev>& blocks;
+  const std::vector<avr::RunSpanDev>* spans;
+  template <class Visit>
+  void visit_tables(avr::FoldLaunch* to, Visit&& visit) const {
+    visit(&to->run_rects_dev, rects.data(), rects.size());
+    visit(&to->run_blocks_dev, blocks.data(), blocks.size());
+    if (spans != nullptr && !spans->empty()) visit(&to->run_spans_dev, spans->data(), spans->size());
+  }
+};
+void stage_fold_tables(avr_context* ctx, const std::vector<avr::RunRectDev>& rects,
+                       const std::vector<avr::RunBlockDev>& blocks,
+                       const std::vector<avr::RunSpanDev>* spans, avr::FoldLaunch* launch) {
+  launch->run_spans_dev = nullptr;
+  avr::stage_tables(ctx, FoldTables{rects, blocks, spans}, launch);
 }
 
 }  // namespace
@@ -754,9 +466,10 @@ int paint_one_box(avr_context* ctx, int phases, avr::FrameKind kind, const avr_b
                   OneBoxRun* run) {
   avr::dense_run_tables(params.width, params.height, 1, 1, &run->rects, &run->blocks);
   run->pieces = avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, 1, params.width, params.height);
-  return render(ctx, {phases, kind, {box, 1, transform, params, camera},
-                      {run->order, 1, run->run_end, 1, 1, run->rects, run->blocks, nullptr, run->pieces},
-                      {&ctx->scratch_scene, 0, out_layers, samples_out, nullptr}});
+  return render(ctx, &ctx->scratch_scene,
+                {phases, kind, {box, 1, transform, params, camera},
+                 {run->order, 1, run->run_end, 1, 1, run->rects, run->blocks, nullptr, run->pieces},
+                 {0, out_layers, samples_out, nullptr}});
 }
 
 // The same into the context's scratch layer (grown as needed), then the fold of that one run into
@@ -775,12 +488,7 @@ int paint_and_fold_one_box(avr_context* ctx, int phases, const avr_box* box,
                                    transform, params, camera, layer, samples_out, &run);
   if (status != AVR_OK) return status;
   avr::FoldLaunch launch;
-  ctx->staging.begin(run.rects.size() * sizeof(avr::RunRectDev) +
-                         run.blocks.size() * sizeof(avr::RunBlockDev), 2);
-  launch.run_rects_dev = ctx->staging.add(run.rects.data(), run.rects.size());
-  launch.run_blocks_dev = ctx->staging.add(run.blocks.data(), run.blocks.size());
-  launch.run_spans_dev = nullptr;
-  ctx->staging.commit(ctx->stream);
+  stage_fold_tables(ctx, run.rects, run.blocks, nullptr, &launch);
   launch.pieces = run.pieces;
   launch.piece = 0;
   launch.width = params.width;
@@ -889,11 +597,12 @@ int avr_render_runs(avr_context* ctx, const avr_scene* scene, const avr_paint_pa
     avr::dense_run_tables(params->width, params->height, n_runs, n_pieces, &rects, &blocks);
     const avr::PieceMapDev pieces =
         avr::make_piece_map(AVR_PIECES_CONTIGUOUS, 1, n_pieces, params->width, params->height);
-    return render(ctx, {kClassify | kMarch, kVolume,
-                        {scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
-                         *params, *camera},
-                        {box_order, n_order, run_end, n_runs, n_pieces, rects, blocks, nullptr, pieces},
-                        {const_cast<avr_scene*>(scene), 0, out_layers, samples_out, nullptr}});
+    return render(ctx, const_cast<avr_scene*>(scene),
+                  {kClassify | kMarch, kVolume,
+                   {scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
+                    *params, *camera},
+                   {box_order, n_order, run_end, n_runs, n_pieces, rects, blocks, nullptr, pieces},
+                   {0, out_layers, samples_out, nullptr}});
   });
 }
 
@@ -1094,7 +803,7 @@ int avr_frame_plan_recv_block(const avr_frame_plan* plan, int global_run, int64_
 
 static int plan_phase(avr_context* ctx, int phases, avr::FrameKind kind, const avr_scene* scene,
                       const avr_frame_plan* plan, int slot, float* send_buffer,
-                      uint64_t* samples_out, const FrameChunks& chunks = FrameChunks{}) {
+                      uint64_t* samples_out, const ChunkCall& chunks = ChunkCall{}) {
   return guarded([&]() -> int {
     bind_device(ctx);
     require(scene != nullptr && plan != nullptr, "null argument");
@@ -1106,7 +815,7 @@ static int plan_phase(avr_context* ctx, int phases, avr::FrameKind kind, const a
     require(static_cast<int>(scene->boxes.size()) == plan->info.n_local_boxes,
             "the scene does not hold this rank's boxes of the plan");
     if (plan->info.n_local_runs == 0) return AVR_OK;
-    return render(ctx,
+    return render(ctx, const_cast<avr_scene*>(scene),
                   {phases, kind,
                    {scene->boxes.data(), static_cast<int>(scene->boxes.size()), scene->transform,
                     plan->params, plan->camera},
@@ -1114,8 +823,7 @@ static int plan_phase(avr_context* ctx, int phases, avr::FrameKind kind, const a
                     plan->local_run_end.data(), plan->info.n_local_runs, plan->info.n_ranks,
                     plan->local_rects, plan->send_blocks,
                     ((phases & kMarch) && plan->tightened) ? &plan->send_spans : nullptr, plan->pieces},
-                   {const_cast<avr_scene*>(scene), slot, send_buffer, samples_out,
-                    &const_cast<avr_frame_plan*>(plan)->prologue}},
+                   {slot, send_buffer, samples_out, &const_cast<avr_frame_plan*>(plan)->prologue}},
                   chunks);
   });
 }
@@ -1178,7 +886,7 @@ int avr_march_plan(avr_context* ctx, const avr_scene* scene, const avr_frame_pla
 
 int avr_classify_plan_chunked(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                               int slot, int n_chunks, void* const* chunk_events, int first_alone) {
-  FrameChunks chunks;
+  ChunkCall chunks;
   chunks.count = n_chunks;
   chunks.events = reinterpret_cast<hipEvent_t const*>(chunk_events);
   chunks.first_alone = first_alone != 0;
@@ -1188,7 +896,7 @@ int avr_classify_plan_chunked(avr_context* ctx, const avr_scene* scene, const av
 int avr_march_plan_chunked(avr_context* ctx, const avr_scene* scene, const avr_frame_plan* plan,
                            int slot, float* send_buffer, uint64_t* samples_out, int n_chunks,
                            void* const* chunk_events) {
-  FrameChunks chunks;
+  ChunkCall chunks;
   chunks.count = n_chunks;
   chunks.events = reinterpret_cast<hipEvent_t const*>(chunk_events);
   return plan_phase(ctx, kMarch, kVolume, scene, plan, slot, send_buffer, samples_out, chunks);
@@ -1198,7 +906,7 @@ int avr_classify_plan_flagged(avr_context* ctx, const avr_scene* scene, const av
                               int slot, const uint8_t* flags, const uint32_t* gate) {
   return guarded([&]() -> int {
     require(flags != nullptr, "null flags");
-    FrameChunks chunks;
+    ChunkCall chunks;
     chunks.classify_flags = flags;
     chunks.classify_gate = gate;
     return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr, chunks);
@@ -1208,7 +916,7 @@ int avr_classify_plan_flagged(avr_context* ctx, const avr_scene* scene, const av
 int avr_march_plan_workgroups(const avr_frame_plan* plan, int64_t* workgroups) {
   return guarded([&]() -> int {
     require(plan != nullptr && workgroups != nullptr, "null argument");
-    *workgroups = march_workgroups_bound(plan->params.width, plan->params.height, plan->info.n_local_runs);
+    *workgroups = avr::march_workgroups_bound(plan->params.width, plan->params.height, plan->info.n_local_runs);
     return AVR_OK;
   });
 }
@@ -1218,7 +926,7 @@ int avr_classify_plan_positions(avr_context* ctx, const avr_scene* scene, const 
   return guarded([&]() -> int {
     require(positions != nullptr && n_positions >= 0, "null positions");
     if (n_positions == 0) return AVR_OK;
-    FrameChunks chunks;
+    ChunkCall chunks;
     chunks.classify_positions = positions;
     chunks.n_classify_positions = n_positions;
     return plan_phase(ctx, kClassify, kVolume, scene, plan, slot, nullptr, nullptr, chunks);
@@ -1229,7 +937,7 @@ int avr_march_plan_speculative(avr_context* ctx, const avr_scene* scene, const a
                                int slot, float* send_buffer, const avr_speculation* speculation) {
   return guarded([&]() -> int {
     require(speculation != nullptr, "null speculation");
-    FrameChunks chunks;
+    ChunkCall chunks;
     chunks.speculation = speculation;
     return plan_phase(ctx, kMarch, kVolume, scene, plan, slot, send_buffer, nullptr, chunks);
   });
@@ -1240,7 +948,7 @@ int avr_render_plan_culled(avr_context* ctx, const avr_scene* scene, const avr_f
                            uint8_t* visibility) {
   return guarded([&]() -> int {
     require(visibility != nullptr && n_chunks >= 2, "a culled frame needs chunks and a visibility buffer");
-    FrameChunks chunks;
+    ChunkCall chunks;
     chunks.count = n_chunks;
     chunks.visibility = visibility;
     chunks.first_alone = true;
@@ -1322,16 +1030,8 @@ int fold_plan(avr_context* ctx, const avr_frame_plan* plan, const float* recv_bu
             "null argument");
     require(plan->info.recv_floats == 0 || recv_buffer != nullptr, "null receive buffer");
     avr::FoldLaunch launch;
-    const bool spans = plan->tightened && !plan->recv_spans.empty();
-    ctx->staging.begin(plan->global_rects.size() * sizeof(avr::RunRectDev) +
-                           plan->recv_blocks.size() * sizeof(avr::RunBlockDev) +
-                           (spans ? plan->recv_spans.size() * sizeof(avr::RunSpanDev) : 0),
-                       3);
-    launch.run_rects_dev = ctx->staging.add(plan->global_rects.data(), plan->global_rects.size());
-    launch.run_blocks_dev = ctx->staging.add(plan->recv_blocks.data(), plan->recv_blocks.size());
-    launch.run_spans_dev =
-        spans ? ctx->staging.add(plan->recv_spans.data(), plan->recv_spans.size()) : nullptr;
-    ctx->staging.commit(ctx->stream);
+    stage_fold_tables(ctx, plan->global_rects, plan->recv_blocks,
+                      plan->tightened ? &plan->recv_spans : nullptr, &launch);
     launch.pieces = plan->pieces;
     launch.piece = plan->piece_of_rank[static_cast<size_t>(plan->info.rank)];
     launch.width = plan->params.width;

@@ -1,6 +1,6 @@
 // What the C ABI's source files share (avr_capi.cpp, avr_field_products.cpp): the context and the
-// scene behind the ABI's handles, the staging ring and the grow-only device buffer they hold, and
-// the helpers every entry point begins with.  Internal to those files: it includes the HIP runtime.
+// scene behind the ABI's handles, the staging ring with the stager of a plan's tables
+// (stage_tables), the grow-only device buffer, and the helpers every entry point begins with.  Internal to those files: it includes the HIP runtime.
 #ifndef AVR_CONTEXT_H
 #define AVR_CONTEXT_H
 
@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "avr_frame_launch.h"
 #include "avr_internal.h"
 
 namespace avr {
@@ -233,8 +234,7 @@ struct avr_context {
   hipStream_t stream = nullptr;
   avr::StagingRing staging;
   avr_scene scratch_scene;         // classified storage of avr_paint_box
-  std::vector<avr::MarchItemDev> march_items;  // host scratch of render()
-  std::vector<int32_t> order_rects;            // ... (the boxes' screen rectangles in layer order)
+  avr::FrameLaunchPlan frame_launch;           // host scratch of render(): its vectors keep their capacity
   int priority = 0;                            // 1: own stream in the highest priority class
   int march_workgroups_per_cu = 0;             // 0 = uncapped
   uint32_t classify_lds_pad = 0;               // avr_context_set_classify_lds_reserve
@@ -274,6 +274,31 @@ int guarded(F&& body) {
 
 inline void require(bool condition, const char* message) {
   if (!condition) throw std::invalid_argument(message);
+}
+
+// The second pass over a plan's visit_tables: adds every table to the batch that StagingSize sized
+// and writes where it will be on the device into the launch arguments.
+struct StagingFill {
+  StagingRing* ring;
+  template <class T>
+  void operator()(const T** device, const T* host, size_t count) const {
+    static const T kUnread{};  // an empty table's one element: no count or range leads to it
+    *device = count != 0 ? ring->add(host, count) : ring->add(&kUnread, 1);
+  }
+};
+
+// Stages the tables of `plan` in one batch on the context's stream and sets their addresses in
+// `args` (the arguments visit_tables takes).  Two rules meet here.  A table the plan names is
+// never null on the device: an empty one is one unread element (the field products' rule).  A
+// table the plan does NOT name keeps the null its argument had: a frame's launchers branch on that
+// (avr_frame_launch.h, "absent is null"), so a plan must not name a table its call does without.
+template <class Plan, class... Args>
+void stage_tables(avr_context* ctx, const Plan& plan, Args*... args) {
+  StagingSize size;
+  plan.visit_tables(args..., size);
+  ctx->staging.begin(size.bytes, size.items);
+  plan.visit_tables(args..., StagingFill{&ctx->staging});
+  ctx->staging.commit(ctx->stream);
 }
 
 inline void bind_device(avr_context* ctx) {

@@ -16,7 +16,7 @@
 //    context's scratch block and the caller's device arrays.
 //  - visit_tables(args..., visit): the tables the call stages, named once, as visit(where in args
 //    the table's device address goes, the host table, its count) in the order they are staged.  The
-//    stager runs it twice, to size the batch (StagingSize) and to fill it; a table of count 0 is
+//    stager runs it twice, to size the batch (StagingSize, avr_internal.h) and to fill it; a table of count 0 is
 //    staged as one value-initialised element that nothing reads, so a plan is never padded.
 //  - `scratch` (where a product has a scratch block): the block's total bytes and each part's
 //    byte offset, in part order.
@@ -37,17 +37,6 @@
 #include "avr_level_cells.h"
 
 namespace avr {
-
-// The sizing pass of the stager over a plan's visit_tables: what StagingRing::begin is given.
-struct StagingSize {
-  size_t bytes = 0;
-  int items = 0;
-  template <class T>
-  void operator()(const T** /*device*/, const T* /*host*/, size_t count) {
-    bytes += std::max<size_t>(count, 1) * sizeof(T);
-    ++items;
-  }
-};
 
 // One part of a context scratch block: `bytes` from byte `offset` of the block on.  An optional
 // part that the call does without is not present: it has no bytes and its address stays null.

@@ -2,37 +2,17 @@
 // projections, derived fields, gradient fields, clumps, their table and links, isosurfaces, streamlines,
 // covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
-// (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.
+// (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
+// stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
 #include "avr_context.h"
 #include "avr_field_plans.h"
 
 using avr::bind_device;
 using avr::guarded;
 using avr::require;
+using avr::stage_tables;
 
 namespace {
-
-// The second pass over a plan's visit_tables: adds every table to the batch that StagingSize sized
-// and writes where it will be on the device into the launch arguments.
-struct StagingFill {
-  avr::StagingRing* ring;
-  template <class T>
-  void operator()(const T** device, const T* host, size_t count) const {
-    static const T kUnread{};  // an empty table's one element: no count or range leads to it
-    *device = count != 0 ? ring->add(host, count) : ring->add(&kUnread, 1);
-  }
-};
-
-// Stages the tables of `plan` in one batch on the context's stream and sets their addresses in
-// `args` (the arguments visit_tables takes).
-template <class Plan, class... Args>
-void stage_tables(avr_context* ctx, const Plan& plan, Args*... args) {
-  avr::StagingSize size;
-  plan.visit_tables(args..., size);
-  ctx->staging.begin(size.bytes, size.items);
-  plan.visit_tables(args..., StagingFill{&ctx->staging});
-  ctx->staging.commit(ctx->stream);
-}
 
 // Where a part of a context scratch block lies; null for an optional part the call does without.
 template <class T>

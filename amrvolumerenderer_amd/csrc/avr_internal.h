@@ -960,6 +960,18 @@ void context_set_descriptor_lead(avr_context* ctx, int batches);
 // Whether the context's classify passes stream their bricklets to memory (RenderLaunch).
 void context_set_classify_stream_stores(avr_context* ctx, bool stream);
 
+// The sizing pass of the stager (stage_tables, avr_context.h) over a plan's visit_tables: what
+// StagingRing::begin is given.  An empty table counts as the one element it is staged as.
+struct StagingSize {
+  size_t bytes = 0;
+  int items = 0;
+  template <class T>
+  void operator()(const T** /*device*/, const T* /*host*/, size_t count) {
+    bytes += (count != 0 ? count : 1) * sizeof(T);
+    ++items;
+  }
+};
+
 // Flags of the events that only ORDER work between this library's streams on ONE device (a
 // frame's classified volume -> its march -> its fold; the descriptor ring's slots): recorded
 // without the system-scope fence.  Whoever waits on them is another queue of the same GPU (the
