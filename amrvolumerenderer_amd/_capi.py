@@ -236,6 +236,12 @@ SIGNATURES = {
     "avr_scene_clump_table": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp, _vp, _vp]),
     "avr_scene_clump_links": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip, C.c_int,
                                         _vp, _vp, _vp, _vp]),
+    "avr_scene_clump_members": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "avr_scene_clump_member_data": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _ip, _ip,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.c_int, _vp, _vp]),
+    "avr_clump_pair_energy": (C.c_int, [_vp, C.POINTER(_i64), C.c_uint64, _vp, _vp, _vp, _vp, _vp,
+                                        C.POINTER(_i64)]),
     "avr_scene_isosurface": (C.c_int, [_vp, _vp, _vp, C.c_double, _ip, _ip, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.c_int,
                                        C.c_uint64, _vp, _vp, _vp, _vp]),

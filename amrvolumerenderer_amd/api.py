@@ -371,7 +371,9 @@ def clump_scene(ctx, scene: "SceneGeometry", lower: float, upper: float, cell_si
 
 
 def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float = math.inf,
-           fields: Sequence[str] = (), min_level: int = 0, max_level: int = -1) -> dict:
+           fields: Sequence[str] = (), min_level: int = 0, max_level: int = -1,
+           mass: Optional[str] = None, velocity: Optional[Sequence[str]] = None,
+           thermal: Optional[str] = None, G: float = 6.6743e-8, max_cells: int = 2 ** 18) -> dict:
     """The clumps of a plotfile's variable ("Clumps"), on cuda:0: the connected
     components of the uncovered cells of the loaded levels whose raw value lies in [lower, upper],
     with their sizes.  variable and every name of fields is a stored variable or a registered
@@ -381,14 +383,22 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
     from +0.0), integrals {name: float64 [n]} = sum_l vol[l] * sums[l], the volume integral of
     each requested field over each clump, taken over the cells where that field is finite,
     outside (labels that are no clump's; 0) and nonfinite (cells of clumps where a requested
-    field is not finite, over all fields).  n == 0 gives empty arrays."""
+    field is not finite, over all fields).  n == 0 gives empty arrays.  With mass (the name of a
+    mass density; velocity: three names, thermal: a thermal energy density, both optional) every
+    clump of 2 to max_cells cells is also tested for gravitational binding with the constant G
+    (cgs by default), and the dict gains mass, self_energy, kinetic, thermal, bound, evaluated
+    and excluded as clump_binding_scene makes them; the members whose thermal energy is not
+    finite are added to nonfinite.  Without mass nothing of that is loaded or run."""
     import numpy as np
     from . import clumps as clump_rules
     from . import plotfile as pf
     lower, upper = clump_rules.check_bounds(lower, upper)
     names = [str(name) for name in fields]
-    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
-                                                            min_level, max_level)
+    binding_names = _binding_names(mass, velocity, thermal)
+    if mass is not None:
+        clump_rules.check_max_cells(max_cells)
+    ctx, rank, world, group, scenes, volumes = _load_fields(
+        plotfile, [variable] + names + binding_names, min_level, max_level)
     header = pf.PlotFileData(plotfile)
     n_levels = len(volumes)
     labels, n = clump_scene(ctx, scenes[0], lower, upper, *_header_levels(header, n_levels), rank,
@@ -410,18 +420,241 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
                     ctx.synchronize()
                 sums[name] = summed.cpu().numpy()
                 nonfinite += int(totals[1].item())
-    return {"n": n, "cells_by_level": cells_by_level, "cells": cells_by_level.sum(axis=0),
-            "volume": clump_rules.clump_volumes(cells_by_level, volumes),
-            "integrals": {name: clump_rules.clump_integrals(sums[name], volumes)
-                          for name in names},
-            "outside": outside, "nonfinite": nonfinite}
+    found = {"n": n, "cells_by_level": cells_by_level, "cells": cells_by_level.sum(axis=0),
+             "volume": clump_rules.clump_volumes(cells_by_level, volumes),
+             "integrals": {name: clump_rules.clump_integrals(sums[name], volumes)
+                           for name in names},
+             "outside": outside, "nonfinite": nonfinite}
+    if mass is not None:
+        binding = clump_binding_scene(
+            ctx, labels, n, found["cells"],
+            *_binding_scenes(scenes, 1 + len(names), mass, velocity, thermal),
+            *_header_levels(header, n_levels), G=G, max_cells=max_cells, n_ranks=world)
+        found["nonfinite"] += binding.pop("nonfinite")
+        found.update(binding)
+    return found
+
+
+# ---- clump binding ("Clump binding") --------------------------------------------------
+
+def _clump_member_lists(ctx, label_scene, n: int, wanted, offsets, index, ratios, sizes, prob_lo,
+                        fields):
+    """The sorted member keys of the wanted clumps of a native label scene, with the members'
+    levels, centres [3, m] and the raw value of every native scene of `fields`, all on the
+    device.  RuntimeError if a cell carries a label that is no clump in 1..n."""
+    keys, totals = label_scene.clump_members(n, wanted, int(offsets[-1]))
+    if int(totals[0].item()) != 0:
+        raise RuntimeError(f"{int(totals[0].item())} cells carry a label that is no clump in "
+                           f"1..{n}")
+    levels, centres, _ = label_scene.clump_member_data(keys, index, ratios, sizes, prob_lo)
+    values = [label_scene.clump_member_data(keys, index, ratios, sizes, prob_lo, field=field,
+                                            centres=False)[2] for field in fields]
+    return keys, levels, centres, values
+
+
+def clump_members_scene(ctx, labels: "SceneGeometry", n: int, cells, cell_sizes, prob_lo,
+                        ref_ratio, fields: Sequence["SceneGeometry"] = (), min_cells: int = 1,
+                        max_cells: int = 2 ** 18, n_ranks: int = 1) -> dict:
+    """The cells of the clumps of a label scene, clump by clump ("Clump binding").
+    labels and n: what clump_scene returned; cells: the cell count per clump (the clump table's,
+    summed over levels); fields: scenes of the same boxes whose value is read at every member.  A
+    clump is listed if min_cells <= cells <= max_cells (clumps.member_segments).  Returns a dict
+    of numpy arrays: labels int64 (the listed clumps, ascending), offsets int64 (members of
+    labels[s]: offsets[s] .. offsets[s + 1] - 1), ordinal int64 [m] (the cell ordinals of
+    "Clumps", ascending per clump), level uint8 [m], centres float64 [m, 3] = prob_lo + (f64(I) +
+    0.5) * dx_l, values: one float64 [m] per scene of fields.  Every box of the scene must be on
+    this rank, as for clump_scene."""
+    import numpy as np
+    from . import clumps as clump_rules
+    _require_one_rank(labels, n_ranks, "clumps need every box of the scene on one rank: "
+                      "labels are not merged between ranks")
+    sizes, ratios, index = _level_setup(labels, labels.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    wanted, offsets = clump_rules.member_segments(cells, min_cells, max_cells)
+    if len(wanted) != int(n):
+        raise ValueError("cells must hold one count per clump")
+    fields = list(fields)
+    found = {"labels": np.nonzero(wanted)[0].astype(np.int64) + 1, "offsets": offsets,
+             "ordinal": np.zeros(0, dtype=np.int64), "level": np.zeros(0, dtype=np.uint8),
+             "centres": np.zeros((0, 3), dtype=np.float64),
+             "values": [np.zeros(0, dtype=np.float64) for _ in fields]}
+    if int(offsets[-1]) == 0:
+        return found
+    with _native_scenes(ctx, [labels] + fields) as (label_scene, *native_fields):
+        keys, levels, centres, values = _clump_member_lists(
+            ctx, label_scene, int(n), wanted, offsets, index, ratios, sizes, prob_lo, native_fields)
+        ctx.synchronize()
+        found["ordinal"] = (keys & 0xffffffff).cpu().numpy()
+        found["level"] = levels.cpu().numpy()
+        found["centres"] = np.ascontiguousarray(centres.cpu().numpy().T)
+        found["values"] = [v.cpu().numpy() for v in values]
+    return found
+
+
+def clump_members(plotfile: str, variable: str, lower: float = -math.inf, upper: float = math.inf,
+                  fields: Sequence[str] = (), min_cells: int = 1, max_cells: int = 2 ** 18,
+                  min_level: int = 0, max_level: int = -1, output: Optional[str] = None) -> dict:
+    """The cells of the clumps of a plotfile's variable over [lower, upper] (yt's clump[field]),
+    on cuda:0.  variable and every name of fields as api.clumps takes them.  Returns a dict: n
+    (the number of clumps), and labels, offsets, ordinal, level, centres and values {name: float64
+    [m]} as clump_members_scene makes them, for the clumps of min_cells to max_cells cells.  With
+    output, the arrays are also written as one .npz (the values as value_<name>)."""
+    import numpy as np
+    from . import clumps as clump_rules
+    from . import plotfile as pf
+    lower, upper = clump_rules.check_bounds(lower, upper)
+    names = [str(name) for name in fields]
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
+                                                            min_level, max_level)
+    header = pf.PlotFileData(plotfile)
+    n_levels = len(volumes)
+    levels = _header_levels(header, n_levels)
+    labels, n = clump_scene(ctx, scenes[0], lower, upper, *levels, rank, world, group)
+    cells = np.zeros(0, dtype=np.int64)
+    if n > 0:
+        if n * n_levels >= clump_rules.TABLE_MAX_ENTRIES:
+            raise ValueError("too many clumps for one table: n * levels must stay below 2^28")
+        with _native_scenes(ctx, [labels]) as (label_scene,):
+            counted, _, _ = label_scene.clump_table(n, n_levels)
+            ctx.synchronize()
+            cells = counted.cpu().numpy().sum(axis=0)
+    found = clump_members_scene(ctx, labels, n, cells, *levels, fields=scenes[1:],
+                                min_cells=min_cells, max_cells=max_cells, n_ranks=world)
+    found["values"] = dict(zip(names, found["values"]))
+    found["n"] = n
+    if output:
+        arrays = {key: np.asarray(value) for key, value in found.items() if key != "values"}
+        arrays.update({f"value_{name}": values for name, values in found["values"].items()})
+        np.savez(output, **arrays)
+    return found
+
+
+def clump_binding_scene(ctx, labels: "SceneGeometry", n: int, cells, mass: "SceneGeometry",
+                        velocity: Optional[Sequence["SceneGeometry"]],
+                        thermal: Optional["SceneGeometry"], cell_sizes, prob_lo, ref_ratio,
+                        G: float = 6.6743e-8, min_cells: int = 1, max_cells: int = 2 ** 18,
+                        n_ranks: int = 1) -> dict:
+    """yt's gravitationally_bound for the clumps of a label scene ("Clump binding").
+    labels, n and cells as clump_members_scene takes them; mass: the scene of a mass density rho;
+    velocity: None or three scenes; thermal: None or the scene of a thermal energy density e.  A
+    clump of max(min_cells, 2) to max_cells cells (at most 2^22) is evaluated: m = rho * vol_l per
+    member (0, and counted in excluded, where rho is negative or not finite), M = sum m, W =
+    sum_{i<j} m_i m_j / r_ij between the cell centres (Context.clump_pair_energy), vbar = sum m v
+    / M, K = 0.5 sum m |v - vbar|^2 (0 without velocities or with M == 0; the velocity of a member
+    with m == 0 is not looked at: it may be a NaN), T = sum e * vol_l over
+    the members whose e is finite (the others counted in nonfinite); bound = G * W > K + T.  Any
+    other clump has evaluated False, NaNs and bound True.  Returns a dict of numpy arrays per
+    clump: mass, self_energy (= G * W), kinetic, thermal float64 [n], bound, evaluated bool [n],
+    excluded int64 [n], and nonfinite (int)."""
+    import numpy as np
+    import torch
+    from . import clumps as clump_rules
+    _require_one_rank(labels, n_ranks, "clumps need every box of the scene on one rank: "
+                      "labels are not merged between ranks")
+    n = int(n)
+    if velocity is not None and len(velocity) != 3:
+        raise ValueError("velocity holds three scenes or is None")
+    G = float(G)
+    if not (math.isfinite(G) and G > 0.0):
+        raise ValueError("G must be finite and positive")
+    sizes, ratios, index = _level_setup(labels, labels.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    wanted, offsets = clump_rules.binding_segments(cells, min_cells, max_cells)
+    if len(wanted) != n:
+        raise ValueError("cells must hold one count per clump")
+    nan = np.full(n, np.nan, dtype=np.float64)
+    found = {"mass": nan.copy(), "self_energy": nan.copy(), "kinetic": nan.copy(),
+             "thermal": nan.copy(), "bound": np.ones(n, dtype=bool), "evaluated": wanted.copy(),
+             "excluded": np.zeros(n, dtype=np.int64), "nonfinite": 0}
+    n_segments = int(wanted.sum())
+    if n_segments == 0:
+        return found
+    fields = [mass] + (list(velocity) if velocity is not None else []) + \
+        ([thermal] if thermal is not None else [])
+    with _native_scenes(ctx, [labels] + fields) as (label_scene, *native_fields):
+        _, levels, centres, values = _clump_member_lists(
+            ctx, label_scene, n, wanted, offsets, index, ratios, sizes, prob_lo, native_fields)
+        device = ctx.device
+        volume = torch.tensor(level_cell_volumes(sizes), dtype=torch.float64,
+                              device=device)[levels.long()]
+        counts = torch.from_numpy(np.diff(offsets)).to(device)
+        segment = torch.repeat_interleave(torch.arange(n_segments, device=device), counts)
+
+        def per_segment(terms):
+            return torch.zeros(n_segments, dtype=torch.float64,
+                               device=device).index_add_(0, segment, terms)
+
+        rho = values[0]
+        usable = torch.isfinite(rho) & (rho >= 0.0)
+        m = torch.where(usable, rho * volume, torch.zeros_like(rho))
+        excluded = torch.zeros(n_segments, dtype=torch.int64,
+                               device=device).index_add_(0, segment, (~usable).to(torch.int64))
+        W, _ = ctx.clump_pair_energy(offsets, centres[0].contiguous(), centres[1].contiguous(),
+                                     centres[2].contiguous(), m)
+        M = per_segment(m)
+        K = torch.zeros_like(M)
+        if velocity is not None:
+            heavy = M > 0.0
+            safe = torch.where(heavy, M, torch.ones_like(M))
+            for v in values[1:4]:
+                # a member without mass has no velocity: whatever its cell holds, a NaN included
+                v = torch.where(m > 0.0, v, torch.zeros_like(v))
+                vbar = per_segment(m * v) / safe
+                away = v - vbar[segment]
+                K = K + per_segment(m * (away * away))
+            K = torch.where(heavy, 0.5 * K, torch.zeros_like(K))
+        T = torch.zeros_like(M)
+        if thermal is not None:
+            e = values[-1]
+            known = torch.isfinite(e)
+            T = per_segment(torch.where(known, e * volume, torch.zeros_like(e)))
+            found["nonfinite"] = int((~known).sum().item())
+        ctx.synchronize()
+        W, M, K, T = (t.cpu().numpy() for t in (W, M, K, T))
+        found["excluded"][wanted] = excluded.cpu().numpy()
+    found["mass"][wanted] = M
+    found["self_energy"][wanted] = np.float64(G) * W
+    found["kinetic"][wanted] = K
+    found["thermal"][wanted] = T
+    found["bound"] = clump_rules.bound_mask(1.0, found["self_energy"], found["kinetic"],
+                                            found["thermal"], found["evaluated"])
+    return found
+
+
+def _binding_scenes(scenes, n_plain: int, mass, velocity, thermal):
+    """(mass scene, velocity scenes or None, thermal scene or None) from the scenes loaded behind
+    the first n_plain."""
+    at = n_plain
+    mass_scene = scenes[at]
+    at += 1
+    velocity_scenes = None
+    if velocity is not None:
+        velocity_scenes = scenes[at:at + 3]
+        at += 3
+    return mass_scene, velocity_scenes, scenes[at] if thermal is not None else None
+
+
+def _binding_names(mass, velocity, thermal) -> List[str]:
+    """The field names a binding evaluation loads, in _binding_scenes' order; ValueError for
+    velocity or thermal without mass and for a velocity that is not three names."""
+    if mass is None:
+        if velocity is not None or thermal is not None:
+            raise ValueError("velocity and thermal need mass")
+        return []
+    names = [str(mass)]
+    if velocity is not None:
+        velocity = [str(v) for v in velocity]
+        if len(velocity) != 3:
+            raise ValueError("velocity holds three field names")
+        names += velocity
+    if thermal is not None:
+        names.append(str(thermal))
+    return names
 
 
 # ---- clump trees (DESIGN.md 7, "Clump tree") ------------------------------------------------------
 
 def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes, prob_lo,
                      ref_ratio, tables: Sequence["SceneGeometry"] = (), rank: int = 0,
-                     n_ranks: int = 1) -> dict:
+                     n_ranks: int = 1, binding: Optional[dict] = None) -> dict:
     """The clumps of a scene's field over a ladder of thresholds, linked into a tree (DESIGN.md 7,
     "Clump tree").  thresholds: 1 to 64 finite values, strictly ascending; upper: one closed upper
     bound for all of them (clumps.check_thresholds).  The clumps of thresholds[i] are clump_scene's
@@ -438,8 +671,11 @@ def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes,
     f64(index_hi + 1) * dx[L - 1] float64 [n, 3], cells_by_level int64 [L, n], sums (per scene of
     tables float64 [L, n]) and nonfinite (cells of clumps where a summed field is not finite).
     RuntimeError, naming the threshold and the label, if a clump's cells carry two parent labels,
-    if a label or parent label is none, or if a clump has no cell.  Every box of the scene must be
-    on this rank, as for clump_scene."""
+    if a label or parent label is none, or if a clump has no cell.  binding (None, or a dict of
+    clump_binding_scene's arguments mass, velocity, thermal, G, min_cells and max_cells): every
+    threshold's clumps are tested for binding while that threshold's label scene is alive, and
+    the result gains binding, clump_binding_scene's arrays over the nodes, with nonfinite added
+    up.  Every box of the scene must be on this rank, as for clump_scene."""
     import numpy as np
     from . import clumps as clump_rules
     thresholds, upper = clump_rules.check_thresholds(thresholds, upper)
@@ -451,6 +687,7 @@ def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes,
     counts = [0] * len(thresholds)
     parent_labels = [np.zeros(0, dtype=np.int64) for _ in thresholds]
     extents, cells, nonfinite = [], [], 0
+    bindings = []
     sums = [[] for _ in tables]
     below, n_below = None, 0
     with _native_scenes(ctx, tables) as fields:
@@ -497,6 +734,12 @@ def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes,
             for held, (field_sums, field_totals) in zip(sums, summed):
                 held.append(field_sums.cpu().numpy())
                 nonfinite += int(field_totals[1].item())
+            if binding is not None:
+                bindings.append(clump_binding_scene(
+                    ctx, labels, n, cells[-1].sum(axis=0), binding["mass"], binding["velocity"],
+                    binding["thermal"], cell_sizes, prob_lo, ref_ratio, G=binding["G"],
+                    min_cells=binding["min_cells"], max_cells=binding["max_cells"],
+                    n_ranks=n_ranks))
             below, n_below = labels, n
     total = sum(counts)
     extent = np.concatenate(extents + [np.zeros((6, 0), dtype=np.int64)], axis=1)
@@ -506,18 +749,28 @@ def clump_tree_scene(ctx, scene: "SceneGeometry", thresholds, upper, cell_sizes,
     finest = np.array(sizes[n_levels - 1], dtype=np.float64)
     empty_cells = np.zeros((n_levels, 0), dtype=np.int64)
     empty_sums = np.zeros((n_levels, 0), dtype=np.float64)
-    return {"n": total, "counts": counts, "parent_labels": parent_labels,
-            "index_lo": index_lo, "index_hi": index_hi,
-            "left_edge": origin + index_lo.astype(np.float64) * finest,
-            "right_edge": origin + (index_hi + 1).astype(np.float64) * finest,
-            "cells_by_level": np.concatenate(cells + [empty_cells], axis=1),
-            "sums": [np.concatenate(held + [empty_sums], axis=1) for held in sums],
-            "nonfinite": nonfinite}
+    found = {"n": total, "counts": counts, "parent_labels": parent_labels,
+             "index_lo": index_lo, "index_hi": index_hi,
+             "left_edge": origin + index_lo.astype(np.float64) * finest,
+             "right_edge": origin + (index_hi + 1).astype(np.float64) * finest,
+             "cells_by_level": np.concatenate(cells + [empty_cells], axis=1),
+             "sums": [np.concatenate(held + [empty_sums], axis=1) for held in sums],
+             "nonfinite": nonfinite}
+    if binding is not None:
+        kinds = {"mass": np.float64, "self_energy": np.float64, "kinetic": np.float64,
+                 "thermal": np.float64, "bound": bool, "evaluated": bool, "excluded": np.int64}
+        found["binding"] = {key: np.concatenate([b[key] for b in bindings] +
+                                                [np.zeros(0, dtype=kind)])
+                            for key, kind in kinds.items()}
+        found["binding"]["nonfinite"] = sum(b["nonfinite"] for b in bindings)
+    return found
 
 
 def clump_tree(plotfile: str, variable: str, thresholds, upper: float = math.inf,
                fields: Sequence[str] = (), min_cells: int = 1, min_level: int = 0,
-               max_level: int = -1, output: Optional[str] = None) -> dict:
+               max_level: int = -1, output: Optional[str] = None, mass: Optional[str] = None,
+               velocity: Optional[Sequence[str]] = None, thermal: Optional[str] = None,
+               G: float = 6.6743e-8, max_cells: int = 2 ** 18) -> dict:
     """The clump tree of a plotfile's variable over a ladder of thresholds ("Clump
     tree"; yt's find_clumps), on cuda:0.  thresholds and upper as clump_tree_scene takes them
     (clumps.threshold_ladder gives yt's ladder); variable and every name of fields as api.clumps
@@ -528,8 +781,12 @@ def clump_tree(plotfile: str, variable: str, thresholds, upper: float = math.inf
     {name: float64 [n]} as api.clumps makes them, index_lo, index_hi int64 [n, 3] (the inclusive
     bounding box in the finest loaded level's index space), left_edge, right_edge float64 [n, 3],
     kept, kept_parent and leaves (clumps.collapse_tree with min_cells: a clump that does not split
-    is the same clump), and nonfinite.  n == 0 gives empty arrays.  With output, the dict is also
-    written as one .npz (clumps.save_tree_npz)."""
+    is the same clump), and nonfinite.  n == 0 gives empty arrays.  With mass (velocity, thermal,
+    G and max_cells as api.clumps takes them) every node of max(min_cells, 2) to max_cells cells
+    is tested for gravitational binding, the dict gains mass, self_energy, kinetic, thermal,
+    bound, evaluated and excluded per node, and collapse_tree takes bound as its passes: an
+    unbound clump and everything below it are dropped, as yt's gravitationally_bound validator
+    drops them.  With output, the dict is also written as one .npz (clumps.save_tree_npz)."""
     import numpy as np
     from . import clumps as clump_rules
     from . import plotfile as pf
@@ -538,12 +795,22 @@ def clump_tree(plotfile: str, variable: str, thresholds, upper: float = math.inf
     if min_cells < 1:
         raise ValueError("min_cells must be at least 1")
     names = [str(name) for name in fields]
-    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [variable] + names,
-                                                            min_level, max_level)
+    binding_names = _binding_names(mass, velocity, thermal)
+    if mass is not None:
+        clump_rules.check_max_cells(max_cells)
+    ctx, rank, world, group, scenes, volumes = _load_fields(
+        plotfile, [variable] + names + binding_names, min_level, max_level)
     header = pf.PlotFileData(plotfile)
     n_levels = len(volumes)
+    binding = None
+    if mass is not None:
+        mass_scene, velocity_scenes, thermal_scene = _binding_scenes(scenes, 1 + len(names), mass,
+                                                                     velocity, thermal)
+        binding = {"mass": mass_scene, "velocity": velocity_scenes, "thermal": thermal_scene,
+                   "G": G, "min_cells": min_cells, "max_cells": max_cells}
     found = clump_tree_scene(ctx, scenes[0], thresholds, upper, *_header_levels(header, n_levels),
-                             tables=scenes[1:], rank=rank, n_ranks=world)
+                             tables=scenes[1:1 + len(names)], rank=rank, n_ranks=world,
+                             binding=binding)
     nodes = clump_rules.tree_nodes(found["counts"], found["parent_labels"])
     cells_by_level = found["cells_by_level"]
     cells = cells_by_level.sum(axis=0)
@@ -555,8 +822,15 @@ def clump_tree(plotfile: str, variable: str, thresholds, upper: float = math.inf
                                for name, summed in zip(names, found["sums"])},
                  "index_lo": found["index_lo"], "index_hi": found["index_hi"],
                  "left_edge": found["left_edge"], "right_edge": found["right_edge"]})
-    tree.update(clump_rules.collapse_tree(nodes["parent"], cells, min_cells))
-    tree["nonfinite"] = found["nonfinite"]
+    if binding is None:
+        tree.update(clump_rules.collapse_tree(nodes["parent"], cells, min_cells))
+        tree["nonfinite"] = found["nonfinite"]
+    else:
+        tested = found["binding"]
+        tree.update({key: tested[key] for key in ("mass", "self_energy", "kinetic", "thermal",
+                                                  "bound", "evaluated", "excluded")})
+        tree.update(clump_rules.collapse_tree(nodes["parent"], cells, min_cells, tested["bound"]))
+        tree["nonfinite"] = found["nonfinite"] + tested["nonfinite"]
     if output:
         clump_rules.save_tree_npz(output, tree)
     return tree

@@ -167,10 +167,14 @@ def tree_nodes(counts: Sequence[int], parents_per_threshold) -> Dict[str, np.nda
             "parent": parent, "child_offsets": child_offsets, "children": children}
 
 
-def collapse_tree(parent, cells, min_cells: int = 1) -> Dict[str, np.ndarray]:
+def collapse_tree(parent, cells, min_cells: int = 1, passes=None) -> Dict[str, np.ndarray]:
     """yt's rule that a clump which does not split is the same clump, on a finished tree (parent:
     node ids, -1 for a root, every parent before its children; cells per node).  valid[v] =
-    cells[v] >= min_cells; kept[v] = valid[v] and (v is a root or its parent has at least two
+    cells[v] >= min_cells and passes[v] and (v is a root or valid[parent[v]]) -- passes: one
+    bool per node, a further validator's verdict such as bound_mask's, all true by default;
+    validity is inherited from the top down, as yt never looks below a child it rejected.  Without
+    passes this is cells[v] >= min_cells alone, a child holding no more cells than its parent.
+    kept[v] = valid[v] and (v is a root or its parent has at least two
     valid children); kept_parent[v] = for a kept v the first kept node met walking up from
     parent[v] (-1 for a root), for any other node -1; leaves = the kept nodes that are no kept
     node's kept_parent, ascending.  Returns kept bool [n], kept_parent int64 [n], leaves int64."""
@@ -180,6 +184,14 @@ def collapse_tree(parent, cells, min_cells: int = 1) -> Dict[str, np.ndarray]:
         raise ValueError("parent and cells must hold one entry per node")
     n = parent.size
     valid = cells >= int(min_cells)
+    if passes is not None:
+        passes = np.asarray(passes, dtype=bool).reshape(-1)
+        if passes.shape != parent.shape:
+            raise ValueError("passes must hold one entry per node")
+        valid = valid & passes
+        for v in range(n):      # every parent before its children
+            if parent[v] >= 0 and not valid[parent[v]]:
+                valid[v] = False
     below = valid & (parent >= 0)
     valid_children = np.bincount(parent[below], minlength=n) if n else np.zeros(0, dtype=np.int64)
     kept = valid & ((parent < 0) | (valid_children[np.maximum(parent, 0)] >= 2))
@@ -195,6 +207,73 @@ def collapse_tree(parent, cells, min_cells: int = 1) -> Dict[str, np.ndarray]:
     is_parent[kept_parent[kept_parent >= 0]] = True
     leaves = np.nonzero(kept & ~is_parent)[0].astype(np.int64)
     return {"kept": kept, "kept_parent": kept_parent, "leaves": leaves}
+
+
+# ---- clump binding ("Clump binding") ------------------------------------------------
+
+BINDING_MAX_CELLS = 1 << 22        # members of one evaluated clump (avr_clump_pair_energy)
+BINDING_MAX_MEMBERS = 1 << 31      # members of one call stay below this
+BINDING_DEFAULT_MAX_CELLS = 1 << 18     # a guess: tools/clump_binding_timing.py measures it
+
+
+def member_segments(cells, min_cells: int = 1, max_cells: int = BINDING_DEFAULT_MAX_CELLS):
+    """Which clumps' cells are listed and where they lie in the member list.  cells: the cell
+    count per clump, label ascending.  wanted[c] = min_cells <= cells[c] <= max_cells; offsets:
+    the prefix sum of the wanted clumps' counts in label order, from 0.  ValueError for 2^31
+    members or more.  Returns (wanted bool [n], offsets int64 [wanted.sum() + 1])."""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+    wanted = (cells >= int(min_cells)) & (cells <= int(max_cells))
+    offsets = np.zeros(int(wanted.sum()) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(cells[wanted])
+    if int(offsets[-1]) >= BINDING_MAX_MEMBERS:
+        raise ValueError("the wanted clumps hold 2^31 cells or more")
+    return wanted, offsets
+
+
+def check_max_cells(max_cells) -> int:
+    """max_cells as an int; ValueError above 2^22, the most one segment of avr_clump_pair_energy
+    holds."""
+    if int(max_cells) > BINDING_MAX_CELLS:
+        raise ValueError("max_cells must not exceed 2^22")
+    return int(max_cells)
+
+
+def binding_segments(cells, min_cells: int = 1, max_cells: int = BINDING_DEFAULT_MAX_CELLS):
+    """Which clumps are evaluated for binding: member_segments over max(min_cells, 2) <= cells[c]
+    <= max_cells -- a clump of one cell has no pair.  ValueError for max_cells above 2^22
+    (check_max_cells)."""
+    return member_segments(cells, max(int(min_cells), 2), check_max_cells(max_cells))
+
+
+def pair_energy(x, y, z, m, offsets) -> np.ndarray:
+    """The numpy twin of avr_clump_pair_energy: per segment sum_{i<j} m_i m_j / r_ij with r_ij =
+    sqrt((dx dx + dy dy) + dz dz) in float64, the terms of member i against every j > i made
+    row-wise by numpy -- the same correctly rounded operations as the kernel's.  math.fsum adds a
+    row's terms exactly and rounds once, and then the rows' sums in the same way: two roundings,
+    so within 2 * 2^-53 of the exact sum of the terms, which are not negative.  +0.0 for fewer
+    than two members."""
+    x, y, z, m = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y, z, m))
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    energy = np.zeros(max(offsets.size - 1, 0), dtype=np.float64)
+    for s in range(energy.size):
+        lo, hi = int(offsets[s]), int(offsets[s + 1])
+        rows = []
+        for i in range(lo, hi - 1):
+            dx, dy, dz = x[i] - x[i + 1:hi], y[i] - y[i + 1:hi], z[i] - z[i + 1:hi]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                terms = m[i] * m[i + 1:hi] / np.sqrt((dx * dx + dy * dy) + dz * dz)
+            rows.append(math.fsum(terms.tolist()))
+        energy[s] = math.fsum(rows)
+    return energy
+
+
+def bound_mask(G: float, W, K, T, evaluated) -> np.ndarray:
+    """yt's gravitationally_bound per clump: G * W > K + T where the clump was evaluated, True
+    where it was not -- an envelope too large to sum is kept."""
+    W, K, T = (np.asarray(a, dtype=np.float64) for a in (W, K, T))
+    evaluated = np.asarray(evaluated, dtype=bool)
+    with np.errstate(invalid="ignore"):
+        return np.where(evaluated, np.float64(G) * W > K + T, True)
 
 
 def save_tree_npz(path: str, tree: dict) -> None:

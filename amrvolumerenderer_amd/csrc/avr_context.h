@@ -247,6 +247,7 @@ struct avr_context {
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
   avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
   avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
+  avr::DeviceBuffer clump_pair_partials;       // avr_clump_pair_energy's partial sums, one per item
   avr::DeviceBuffer iso_scratch;               // avr_scene_isosurface's shells and chunk counts
 };
 

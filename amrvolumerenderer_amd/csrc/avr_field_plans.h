@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
-// derived fields, gradient fields, clumps, isosurfaces, streamlines, covering grids, rays, per-ray
-// sums):
+// derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
+// streamlines, covering grids, rays, per-ray sums):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -936,6 +936,218 @@ inline ClumpLinksPlan plan_clump_links(const avr_box* labels, const avr_box* par
   plan.args.n_tiles = plan.tile_begin.back();
   plan.args.n_clumps = static_cast<uint32_t>(n_clumps);
   plan.args.n_parents = static_cast<uint32_t>(n_parents);
+  return plan;
+}
+
+// The member cells of a label field's wanted clumps ("Clump binding").  The cell
+// ordinals are those of "Clumps": cell_begin[b] + (k ny + j) nx + i.
+struct ClumpMembersPlan {
+  std::vector<JointBoxDev> boxes;    // every field: the labels
+  std::vector<uint32_t> tile_begin;
+  std::vector<uint32_t> cell_begin;  // n_boxes + 1: prefix sum of the boxes' cells, in scene order
+  ClumpMembersArgs args{};
+  template <class Visit>
+  void visit_tables(ClumpMembersArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->cell_begin, cell_begin.data(), cell_begin.size());
+  }
+};
+// The prefix sum of the boxes' cells: fewer than 2^31 in all.  Box: a device box with nx, ny, nz.
+template <class Box>
+inline std::vector<uint32_t> cell_ordinals(const std::vector<Box>& boxes) {
+  std::vector<uint32_t> cell_begin(1, 0u);
+  uint64_t total = 0;
+  for (const Box& box : boxes) {
+    // a box's cells are at most 2^28 (its span), so the sum stays far inside 64 bits
+    total += static_cast<uint64_t>(box.nx) * static_cast<uint64_t>(box.ny) *
+             static_cast<uint64_t>(box.nz);
+    require_box(total < (uint64_t{1} << 31), "scene has too many cells for 32-bit labels");
+    cell_begin.push_back(static_cast<uint32_t>(total));
+  }
+  return cell_begin;
+}
+// The rules, in this order: n_clumps, capacity, the box rules (a level below 16), fewer than 2^31
+// cells.
+inline ClumpMembersPlan plan_clump_members(const avr_box* labels, size_t n_boxes, uint64_t n_clumps,
+                                           uint64_t capacity) {
+  require_box(n_clumps >= 1 && n_clumps < static_cast<uint64_t>(kClumpTableMaxEntries),
+              "n_clumps must lie in [1, 2^28)");
+  require_box(capacity >= 1 && capacity < (uint64_t{1} << 31), "capacity must lie in [1, 2^31)");
+  ClumpMembersPlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = labels[b];
+    const avr_box* in[1] = {&first};
+    FieldView view;
+    JointBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, in, 1, kFieldMaxLevels, &view, &dev.paired);
+    dev.level = first.level;
+    for (int f = 0; f < 3; ++f) {
+      dev.cells[f] = view.cells;
+      dev.jstride[f] = view.jstride;
+      dev.kstride[f] = view.kstride;
+    }
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  plan.cell_begin = cell_ordinals(plan.boxes);
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_clumps = static_cast<uint32_t>(n_clumps);
+  plan.args.capacity = capacity;
+  return plan;
+}
+
+// What is looked up per member key: the level and centre of the key's cell, and a field's value.
+struct ClumpMemberDataPlan {
+  std::vector<ClumpMemberBoxDev> boxes;
+  std::vector<uint32_t> cell_begin;
+  IsoLevelsDev levels;
+  ClumpMemberDataArgs args{};
+  template <class Visit>
+  void visit_tables(ClumpMemberDataArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->cell_begin, cell_begin.data(), cell_begin.size());
+    visit(&to->levels, &levels, 1);
+  }
+};
+// scene: the boxes the keys' ordinals count; field (may be null): a field's boxes, congruent to
+// them.  The rules, in this order: n_members, n_levels, null arrays, the box rules, fewer than 2^31
+// cells, the ratios, the index ranges, finite sizes and origin.
+inline ClumpMemberDataPlan plan_clump_member_data(const avr_box* scene, const avr_box* field,
+                                                  size_t n_boxes, uint64_t n_members,
+                                                  const int32_t* box_index_lo,
+                                                  const int32_t* level_ratio,
+                                                  const double* level_cell_size,
+                                                  const double* prob_lo, int n_levels) {
+  require_box(n_members < (uint64_t{1} << 31), "n_members must stay below 2^31");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  require_box(level_cell_size != nullptr && prob_lo != nullptr, "null argument");
+  ClumpMemberDataPlan plan;
+  plan.boxes.resize(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = scene[b];
+    const avr_box* in[2] = {&first, field != nullptr ? &field[b] : &first};
+    FieldView views[2];
+    ClumpMemberBoxDev& dev = plan.boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool cells = field_box_views(first, in, 2, n_levels, views, &paired);
+    dev.level = first.level;
+    if (field != nullptr) {
+      dev.field = views[1].cells;
+      dev.jstride = views[1].jstride;
+      dev.kstride = views[1].kstride;
+    }
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+  }
+  plan.cell_begin = cell_ordinals(plan.boxes);
+  int32_t ratio[kFieldMaxLevels];
+  fill_level_ratios(level_ratio, n_levels, ratio);
+  box_index_regions(box_index_lo, scene, &plan.boxes);
+  fill_level_geometry(level_cell_size, prob_lo, n_levels, &plan.levels);
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_cells = plan.cell_begin.back();
+  plan.args.n_members = static_cast<uint32_t>(n_members);
+  return plan;
+}
+
+// The pairwise self-energy of member segments ("Clump binding").  Segment s holds the
+// members offsets[s] .. offsets[s + 1] - 1, cut into tiles of kClumpPairTile; every tile pair
+// (i_tile, j_tile) with j_tile >= i_tile belongs to exactly one item.  A row of T tiles is cut
+// into j chunks of clump_pair_chunk(T) tiles, so that a segment of a few tiles still fills more
+// than a few workgroups, and no lane ever adds more than 64 * 256 terms in a row.
+inline uint32_t clump_pair_chunk(uint32_t tiles) {
+  return std::min(kClumpPairMaxChunk, std::max(1u, (tiles + 7u) / 8u));
+}
+struct ClumpPairsPlan {
+  std::vector<ClumpPairItem> items;     // segment by segment, row by row, chunk by chunk
+  std::vector<uint32_t> partial_begin;  // n_segments + 1: a segment's items and partials
+  // depth[s]: the longest chain of rounded additions a term of segment s passes through -- the
+  // terms one lane adds in a row (at most the segment's members, and the chunk's), 8 for the
+  // workgroup's shuffle steps (6 are taken), the 3 additions of its four waves' sums through LDS,
+  // the partials one lane of the reduction adds, and that wave's 6 shuffle steps.  0 for a
+  // segment of fewer than two members, which has no term.
+  std::vector<int64_t> depth;
+  ClumpPairArgs args{};
+  size_t scratch_bytes = 0;             // the partials
+  template <class Visit>
+  void visit_tables(ClumpPairArgs* to, Visit&& visit) const {
+    visit(&to->items, items.data(), items.size());
+    visit(&to->partial_begin, partial_begin.data(), partial_begin.size());
+  }
+};
+// The items of a segment of `count` members: one per row and j chunk.
+inline uint64_t clump_pair_items(uint32_t count) {
+  if (count < 2) return 0;
+  const uint32_t tiles = (count + kClumpPairTile - 1) / kClumpPairTile;
+  const uint32_t chunk = clump_pair_chunk(tiles);
+  uint64_t items = 0;
+  for (uint32_t i = 0; i < tiles; ++i) items += (tiles - i + chunk - 1) / chunk;
+  return items;
+}
+// The rules, in this order: the offsets ascend from 0; no segment holds more than 2^22 members;
+// fewer than 2^31 members in all; fewer than 2^28 segments; fewer than 2^26 items, counted before
+// any table is made.
+inline ClumpPairsPlan plan_clump_pairs(const int64_t* offsets, uint64_t n_segments) {
+  require_box(offsets != nullptr, "null argument");
+  require_box(offsets[0] == 0, "offsets must ascend from 0");
+  for (uint64_t s = 0; s < n_segments; ++s) {
+    require_box(offsets[s] <= offsets[s + 1], "offsets must ascend from 0");
+  }
+  for (uint64_t s = 0; s < n_segments; ++s) {
+    require_box(static_cast<uint64_t>(offsets[s + 1] - offsets[s]) <= kClumpPairMaxSegment,
+                "a segment holds more than 2^22 members");
+  }
+  require_box(offsets[n_segments] < (int64_t{1} << 31), "the segments hold 2^31 or more members");
+  require_box(n_segments < static_cast<uint64_t>(kClumpTableMaxEntries),
+              "n_segments must stay below 2^28");
+  uint64_t n_items = 0;
+  for (uint64_t s = 0; s < n_segments; ++s) {
+    n_items += clump_pair_items(static_cast<uint32_t>(offsets[s + 1] - offsets[s]));
+    require_box(n_items < kClumpPairMaxItems, "the segments make 2^26 or more work items");
+  }
+  ClumpPairsPlan plan;
+  plan.items.reserve(n_items);
+  plan.partial_begin.assign(1, 0u);
+  plan.partial_begin.reserve(n_segments + 1);
+  plan.depth.assign(n_segments, 0);
+  n_items = 0;
+  for (uint64_t s = 0; s < n_segments; ++s) {
+    const uint32_t begin = static_cast<uint32_t>(offsets[s]);
+    const uint32_t count = static_cast<uint32_t>(offsets[s + 1] - offsets[s]);
+    if (count >= 2) {
+      const uint32_t tiles = (count + kClumpPairTile - 1) / kClumpPairTile;
+      const uint32_t chunk = clump_pair_chunk(tiles);
+      const uint64_t segment_items = clump_pair_items(count);
+      n_items += segment_items;
+      for (uint32_t i = 0; i < tiles; ++i) {
+        for (uint32_t j = i; j < tiles; j += chunk) {
+          plan.items.push_back({begin, count, i, j | (std::min(chunk, tiles - j) << 16)});
+        }
+      }
+      const int64_t lane_terms = std::min<int64_t>(count, int64_t{chunk} * kClumpPairTile);
+      const int64_t strided = static_cast<int64_t>((segment_items + 63) / 64);
+      plan.depth[s] = lane_terms + 8 + 3 + strided + 6;
+    }
+    plan.partial_begin.push_back(static_cast<uint32_t>(n_items));
+  }
+  plan.args.n_items = static_cast<uint32_t>(n_items);
+  plan.args.n_segments = static_cast<uint32_t>(n_segments);
+  plan.scratch_bytes = static_cast<size_t>(n_items) * sizeof(double);
   return plan;
 }
 

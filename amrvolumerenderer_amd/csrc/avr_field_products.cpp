@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
-// projections, derived fields, gradient fields, clumps, their table and links, isosurfaces, streamlines,
-// covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
+// projections, derived fields, gradient fields, clumps, their table, links, members and pair
+// energies, isosurfaces, streamlines, covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -30,7 +30,7 @@ void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t 
 
 }  // namespace
 
-// The thirteen entry points below read the same way, top to bottom: bind the device; refuse null
+// The sixteen entry points below read the same way, top to bottom: bind the device; refuse null
 // handles and device pointers; refuse scenes of another context or box count (require_field_scene);
 // make the plan, which holds every rule on the plain arguments and the boxes; the call's side
 // effects on its outputs (a written scene's classification keys, a cleared count); return where
@@ -243,6 +243,87 @@ int avr_scene_clump_links(avr_context* ctx, const avr_scene* labels, const avr_s
     args.parent_hi = parent_hi_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_clump_links(args, parents != nullptr, ctx->stream);
+  });
+}
+
+int avr_scene_clump_members(avr_context* ctx, const avr_scene* labels, uint64_t n_clumps,
+                            const uint8_t* wanted_dev, uint64_t capacity, uint64_t* keys_dev,
+                            uint64_t* count_dev, uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(labels != nullptr && wanted_dev != nullptr && keys_dev != nullptr &&
+                count_dev != nullptr && totals_dev != nullptr, "null argument");
+    const size_t n_boxes = labels->boxes.size();
+    require_field_scene(ctx, labels, n_boxes);
+    const avr::ClumpMembersPlan plan =
+        avr::plan_clump_members(labels->boxes.data(), n_boxes, n_clumps, capacity);
+    avr::hip_check(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), ctx->stream), "hipMemsetAsync");
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::ClumpMembersArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.wanted = wanted_dev;
+    args.keys = reinterpret_cast<unsigned long long*>(keys_dev);
+    args.cursor = reinterpret_cast<unsigned long long*>(count_dev);
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_clump_members(args, ctx->stream);
+  });
+}
+
+int avr_scene_clump_member_data(avr_context* ctx, const avr_scene* scene, const uint64_t* keys_dev,
+                                uint64_t n_members, const avr_scene* field, double* values_dev,
+                                const int32_t* box_index_lo, const int32_t* level_ratio,
+                                const double* level_cell_size, const double* prob_lo, int n_levels,
+                                double* centres_dev, uint8_t* levels_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene != nullptr, "null argument");
+    require((field != nullptr) == (values_dev != nullptr),
+            "values_dev is given exactly when field is");
+    require((centres_dev != nullptr) == (levels_dev != nullptr),
+            "centres_dev and levels_dev are given together");
+    require(values_dev != nullptr || centres_dev != nullptr, "no output is asked for");
+    require(n_members == 0 || keys_dev != nullptr, "null argument");
+    const size_t n_boxes = scene->boxes.size();
+    require_field_scene(ctx, scene, n_boxes);
+    if (field != nullptr) require_field_scene(ctx, field, n_boxes);
+    const avr::ClumpMemberDataPlan plan = avr::plan_clump_member_data(
+        scene->boxes.data(), field != nullptr ? field->boxes.data() : nullptr, n_boxes, n_members,
+        box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels);
+    if (n_members == 0) return AVR_OK;
+    avr::ClumpMemberDataArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.keys = reinterpret_cast<const unsigned long long*>(keys_dev);
+    args.values = values_dev;
+    args.centres = centres_dev;
+    args.levels_out = levels_dev;
+    return avr::launch_clump_member_data(args, ctx->stream);
+  });
+}
+
+int avr_clump_pair_energy(avr_context* ctx, const int64_t* offsets_host, uint64_t n_segments,
+                          const double* x_dev, const double* y_dev, const double* z_dev,
+                          const double* m_dev, double* w_dev, int64_t* depth_host) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(offsets_host != nullptr, "null argument");
+    require(n_segments == 0 || w_dev != nullptr, "null argument");
+    const avr::ClumpPairsPlan plan = avr::plan_clump_pairs(offsets_host, n_segments);
+    require(offsets_host[n_segments] == 0 || (x_dev != nullptr && y_dev != nullptr &&
+                                              z_dev != nullptr && m_dev != nullptr),
+            "null argument");
+    if (depth_host != nullptr) std::copy(plan.depth.begin(), plan.depth.end(), depth_host);
+    if (n_segments == 0) return AVR_OK;
+    ctx->clump_pair_partials.reserve(plan.scratch_bytes, ctx->stream, "avr_clump_pair_energy",
+                                     "hipMalloc(clump pair partials)");
+    avr::ClumpPairArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.x = x_dev;
+    args.y = y_dev;
+    args.z = z_dev;
+    args.m = m_dev;
+    args.partial = static_cast<double*>(ctx->clump_pair_partials.data);
+    args.w = w_dev;
+    return avr::launch_clump_pairs(args, ctx->stream);
   });
 }
 

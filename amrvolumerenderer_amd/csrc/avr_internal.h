@@ -679,6 +679,78 @@ struct ClumpLinkArgs {
   unsigned long long* totals;   // [2]: labels outside, parent labels outside; added to
 };
 int launch_clump_links(const ClumpLinkArgs& args, bool has_parent, void* stream);
+// The member cells of the wanted clumps of a label field (avr_clump_binding.hip; DESIGN.md 7,
+// "Clump binding"): a JointBoxDev holds the labels as every field.  A member's key is
+// (label - 1) << 32 | cell ordinal.
+struct ClumpMembersArgs {
+  const JointBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  const uint32_t* cell_begin;   // n_boxes + 1: prefix sum of the boxes' cells
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  uint32_t n_clumps;            // 1 .. 2^28 - 1
+  const uint8_t* wanted;        // [n_clumps]
+  unsigned long long capacity;  // of keys, 1 .. 2^31 - 1
+  unsigned long long* keys;     // written at slots below capacity, in no fixed order
+  unsigned long long* cursor;   // the next free slot: added to; in the end the number of members
+  unsigned long long* totals;   // [1]: labels outside, added to
+};
+int launch_clump_members(const ClumpMembersArgs& args, void* stream);
+// What is looked up per member key: the level, the centre and a field's value of the key's cell.
+struct alignas(16) ClumpMemberBoxDev {
+  const double* field;    // the field's cells (null without a field)
+  int32_t jstride, kstride;
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t pad_;
+};
+static_assert(sizeof(ClumpMemberBoxDev) == 48, "ClumpMemberBoxDev: 16-byte multiple");
+struct IsoLevelsDev;
+struct ClumpMemberDataArgs {
+  const ClumpMemberBoxDev* boxes;
+  const uint32_t* cell_begin;   // n_boxes + 1: prefix sum of the boxes' cells
+  const IsoLevelsDev* levels;   // cell_size and prob_lo
+  int32_t n_boxes;
+  uint32_t n_cells;             // < 2^31; a key whose ordinal is not below it names no cell
+  uint32_t n_members;           // < 2^31
+  const unsigned long long* keys;
+  double* values;               // [n_members] (null without a field)
+  double* centres;              // [3][n_members] (null: neither centres nor levels are written)
+  uint8_t* levels_out;          // [n_members] (null exactly when centres is)
+};
+int launch_clump_member_data(const ClumpMemberDataArgs& args, void* stream);
+// The self-energy of member segments by direct summation (avr_clump_binding.hip; DESIGN.md 7,
+// "Clump binding"): a segment's members are cut into tiles of kClumpPairTile, and an item is one
+// workgroup's share of the tile pairs (i_tile, j_tile), j_tile >= i_tile: one i tile against
+// at most kClumpPairMaxChunk consecutive j tiles.  One segment's items, and so its partials, are
+// contiguous.
+constexpr uint32_t kClumpPairTile = 256;
+constexpr uint32_t kClumpPairMaxChunk = 64;                   // j tiles of one item
+constexpr uint64_t kClumpPairMaxSegment = uint64_t{1} << 22;  // members of one segment
+// Items of one call: 1 GiB of item table and 0.5 GiB of partials at the limit.  One segment of
+// 2^22 members makes 2.1 M items, so a call takes 31 of them.
+constexpr uint64_t kClumpPairMaxItems = uint64_t{1} << 26;
+struct alignas(16) ClumpPairItem {
+  uint32_t begin;     // the segment's first member
+  uint32_t count;     // the segment's members, 2 .. 2^22
+  uint32_t i_tile;
+  uint32_t j_tiles;   // the first j tile | the number of j tiles (1 .. 64) << 16
+};
+static_assert(sizeof(ClumpPairItem) == 16, "ClumpPairItem: one 16-byte scalar load");
+struct ClumpPairArgs {
+  const ClumpPairItem* items;       // n_items
+  const uint32_t* partial_begin;    // n_segments + 1: prefix sum of the segments' items
+  uint32_t n_items;                 // < 2^26
+  uint32_t n_segments;              // 1 .. 2^28 - 1
+  const double* x;                  // the members' centres and masses, all segments
+  const double* y;
+  const double* z;
+  const double* m;
+  double* partial;                  // n_items: written by the pair kernel, read by the reduction
+  double* w;                        // n_segments: written
+};
+int launch_clump_pairs(const ClumpPairArgs& args, void* stream);
 
 // Isosurfaces (avr_isosurface.hip): marching tetrahedra over the cubes of cell centres.  Box b
 // enumerates the cube bases (i, j, k) in [-1, n - 1]^3 of its own index space; a base's ordinal is

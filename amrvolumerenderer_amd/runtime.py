@@ -247,6 +247,32 @@ class Context:
     def empty(self, *shape, dtype=torch.float32) -> torch.Tensor:
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
+    # -- clump binding ------------------------------------------------------------------------
+    def clump_pair_energy(self, offsets, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
+                          m: torch.Tensor, w: Optional[torch.Tensor] = None):
+        """avr_clump_pair_energy: per segment s of the members offsets[s] .. offsets[s + 1] - 1
+        (offsets: n_segments + 1 ascending int64 on the host, from 0) the self-energy
+        sum_{i<j} m_i m_j / |x_i - x_j| by direct summation in float64 ("Clump
+        binding").  x, y, z, m: float64 [offsets[-1]] on the device.  Returns (W float64
+        [n_segments] on the device, depth int64 [n_segments] numpy: the longest chain of rounded
+        additions a term of the segment passes through).  Asynchronous on the context's stream."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1:
+            raise ValueError("offsets must hold n_segments + 1 values")
+        n_segments = int(offsets.size) - 1
+        for name, t in (("x", x), ("y", y), ("z", z), ("m", m)):
+            self._check_tensor(t, torch.float64, name)
+            if t.numel() != int(offsets[-1]):
+                raise ValueError("x, y, z and m must hold offsets[-1] values")
+        w = _output(self, w, torch.float64, (n_segments,), "w", wrong_size="w must hold one value "
+                    "per segment")
+        depth = np.zeros(n_segments, dtype=np.int64)
+        _native(self, "avr_clump_pair_energy", self._handle,
+                offsets.ctypes.data_as(C.POINTER(C.c_int64)), n_segments, _pointer(x), _pointer(y),
+                _pointer(z), _pointer(m), _pointer(w),
+                depth.ctypes.data_as(C.POINTER(C.c_int64)))
+        return w, depth
+
     # -- painter ----------------------------------------------------------------------------
     def paint_box(self, box: AmrBox, transform: ScalarTransform, params: _capi.PaintParams,
                   camera: CameraParameters, out: Optional[torch.Tensor] = None,
@@ -885,6 +911,70 @@ class Scene:
                 _ints(index), _ints(ratios), int(ratios.size) + 1, _pointer(extent),
                 _pointer(parent_lo), _pointer(parent_hi), _pointer(totals))
         return extent, parent_lo, parent_hi, totals
+
+    def clump_members(self, n_clumps: int, wanted, capacity: int,
+                      totals: Optional[torch.Tensor] = None):
+        """avr_scene_clump_members with this scene as the labels: the keys (label - 1) << 32 |
+        cell ordinal of the cells whose label c has wanted[c - 1] != 0 (wanted: n_clumps bytes, a
+        tensor on the device or anything numpy takes), sorted ascending -- by label, then by
+        ordinal: the canonical member list ("Clump binding").  capacity: the number
+        of members, which the caller knows from the clump table; ValueError if the kernel counts
+        another number.  Returns (keys int64 [capacity], totals int64 [1]: labels that are no
+        integer in [1, n_clumps], added to a tensor handed in) on the device.  Synchronises, to
+        read the count."""
+        ctx = self.ctx
+        n_clumps, capacity = int(n_clumps), int(capacity)
+        if n_clumps < 1:
+            raise ValueError("n_clumps must be at least 1")
+        if not isinstance(wanted, torch.Tensor):
+            wanted = torch.from_numpy(np.ascontiguousarray(wanted).astype(np.uint8).reshape(-1))
+        wanted = wanted.to(device=ctx.device, dtype=torch.uint8).contiguous()
+        if wanted.numel() != n_clumps:
+            raise ValueError("wanted must hold one byte per label")
+        totals = _output(ctx, totals, torch.int64, (1,), "totals", torch.zeros,
+                         "totals must hold one value")
+        if capacity == 0 and not bool(wanted.any().item()):
+            return torch.zeros(0, dtype=torch.int64, device=ctx.device), totals
+        keys = torch.empty(max(capacity, 1), dtype=torch.int64, device=ctx.device)
+        count = torch.zeros(1, dtype=torch.int64, device=ctx.device)
+        _native(ctx, "avr_scene_clump_members", ctx._handle, self._handle, n_clumps,
+                _pointer(wanted), max(capacity, 1), _pointer(keys), _pointer(count),
+                _pointer(totals))
+        found = int(count.item())
+        if found != capacity:
+            raise ValueError(f"the label scene holds {found} member cells, not the {capacity} "
+                             "its table counted")
+        # keys are below 2^60: the signed order is the unsigned one
+        return torch.sort(keys[:capacity]).values, totals
+
+    def clump_member_data(self, keys: torch.Tensor, box_index_lo, level_ratio, level_cell_size,
+                          prob_lo, field: Optional["Scene"] = None, centres: bool = True):
+        """avr_scene_clump_member_data with this scene's boxes: per key of clump_members (int64
+        [n] on the device) the level and centre of its cell (centres=True) and/or the raw value
+        of `field` (a scene of the same context with the same box list) there.  box_index_lo,
+        level_ratio, level_cell_size and prob_lo as isosurface takes them.  Returns (levels uint8
+        [n] or None, centres float64 [3, n] or None, values float64 [n] or None) on the device.
+        Asynchronous on the context's stream."""
+        ctx = self.ctx
+        ctx._check_tensor(keys, torch.int64, "keys")
+        if keys.ndim != 1:
+            raise ValueError("keys must be one-dimensional")
+        if field is None and not centres:
+            raise ValueError("no output is asked for")
+        n = int(keys.numel())
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo, level_ratio,
+                                                        level_cell_size, prob_lo)
+        levels = torch.empty(n, dtype=torch.uint8, device=ctx.device) if centres else None
+        where = torch.empty((3, n), dtype=torch.float64, device=ctx.device) if centres else None
+        values = torch.empty(n, dtype=torch.float64, device=ctx.device) \
+            if field is not None else None
+        if n == 0:      # nothing to look up, and a tensor without elements has no address
+            return levels, where, values
+        _native(ctx, "avr_scene_clump_member_data", ctx._handle, self._handle, _pointer(keys), n,
+                field._handle if field is not None else None, _pointer(values), _ints(index),
+                _ints(ratios), _doubles(sizes), _doubles(origin), int(sizes.shape[0]),
+                _pointer(where), _pointer(levels))
+        return levels, where, values
 
     def isosurface(self, value: float, box_index_lo, level_ratio, level_cell_size, prob_lo,
                    sample: Optional["Scene"] = None, capacity: int = 0,

@@ -1256,6 +1256,64 @@ int avr_scene_clump_links(avr_context *ctx, const avr_scene *labels, const avr_s
                           const int32_t *level_ratio, int n_levels, int32_t *extent_dev,
                           uint32_t *parent_lo_dev, uint32_t *parent_hi_dev, uint64_t *totals_dev);
 
+/* The member cells of the wanted clumps of a label field ("Clump binding").
+ * `labels` is a label scene of ctx as avr_scene_clumps writes one; wanted_dev holds one byte per
+ * label, wanted_dev[c - 1].  For every cell, in this order: a label whose bits are +0.0 is
+ * skipped; a label that is not an integer in [1, n_clumps] adds 1 to totals_dev[0] (one uint64,
+ * added to); a cell whose label c has wanted_dev[c - 1] != 0 is a member, and its key is
+ * (c - 1) << 32 | ordinal with the cell ordinals of avr_scene_clumps: the cells of the boxes in
+ * scene order, (k ny + j) nx + i inside a box.  A member takes the next free slot s of
+ * count_dev[0] (one uint64, cleared by the call) and writes keys_dev[s] if s < capacity: the keys
+ * arrive in no fixed order -- sorted ascending they are the canonical list, by label and then by
+ * ordinal -- and nothing is written at or past keys_dev[capacity].  count_dev[0] ends as the
+ * number of members, whatever the capacity.  AVR_ERR_INVALID_ARGUMENT, before any device work and
+ * with the outputs untouched, in this order: n_clumps outside [1, 2^28); capacity outside
+ * [1, 2^31); the box rules (a level in [0, 16)); 2^31 cells or more.  Nothing is launched for a
+ * scene without cells.  Asynchronous on the context's stream. */
+int avr_scene_clump_members(avr_context *ctx, const avr_scene *labels, uint64_t n_clumps,
+                            const uint8_t *wanted_dev, uint64_t capacity, uint64_t *keys_dev,
+                            uint64_t *count_dev, uint64_t *totals_dev);
+
+/* What is looked up per member key.  The low 32 bits of keys_dev[n] (n < n_members) are a cell
+ * ordinal of `scene` (a scene of ctx; only its boxes' dims and levels are used).  With
+ * centres_dev and levels_dev (given together or both NULL): levels_dev[n] = the level of the
+ * cell's box and centres_dev[a * n_members + n] = prob_lo[a] + (f64(I_a) + 0.5) * dx_l[a] -- one
+ * addition, one multiplication, one addition, unfused -- where I_a = box_index_lo[b][a] + the
+ * cell's index along axis a in its box.  With `field` (a scene of ctx with the same box list) and
+ * values_dev (given together or both NULL): values_dev[n] = the raw f64 value of that cell of the
+ * field.  An ordinal that names no cell of the scene reads nothing and gives level 255 and NaNs.
+ * box_index_lo, level_ratio, level_cell_size, prob_lo and n_levels as avr_scene_isosurface takes
+ * them.  AVR_ERR_INVALID_ARGUMENT, before any device work and with the outputs untouched: no
+ * output group asked for, or half of one; then in this order: n_members >= 2^31; n_levels outside
+ * [1, 16]; a NULL array; the box rules and scenes that are not congruent; 2^31 cells or more; a
+ * ratio below 2; an index range that leaves [-2^30, 2^30); a cell size that is not finite and
+ * positive, an origin that is not finite.  Nothing is launched for n_members == 0.  Asynchronous
+ * on the context's stream. */
+int avr_scene_clump_member_data(avr_context *ctx, const avr_scene *scene, const uint64_t *keys_dev,
+                                uint64_t n_members, const avr_scene *field, double *values_dev,
+                                const int32_t *box_index_lo, const int32_t *level_ratio,
+                                const double *level_cell_size, const double *prob_lo,
+                                int n_levels, double *centres_dev, uint8_t *levels_dev);
+
+/* The self-energy of member segments by direct summation ("Clump binding").  Segment
+ * s holds the members offsets_host[s] .. offsets_host[s + 1] - 1 of the device arrays x_dev,
+ * y_dev, z_dev (centres) and m_dev (masses, >= 0); w_dev[s] = sum over its pairs i < j of
+ * m_i m_j / r_ij, r_ij = sqrt((dx dx + dy dy) + dz dz), every operation IEEE binary64, correctly
+ * rounded and unfused; +0.0 for a segment of fewer than two members.  Two members at one point
+ * divide by zero as IEEE does.  The sum is taken in an order that the offsets alone fix: equal
+ * arguments give equal bits, and no term passes through more than depth_host[s] rounded additions
+ * (int64 [n_segments] on the host, or NULL; 0 for a segment without pairs; never more than the
+ * segment's members + 64).  The partial sums live in a grow-only scratch block of the context.
+ * AVR_ERR_INVALID_ARGUMENT, before any device work and with the outputs untouched, in this order:
+ * offsets that do not ascend from 0; a segment of more than 2^22 members; 2^31 members or more;
+ * n_segments >= 2^28; 2^26 work items or more (an item is one row of 256 members against at most
+ * 64 * 256 others: a segment of N members makes about N^2 / 2^23 + N / 2^9 of them, 2.1 M at
+ * N = 2^22, so a call takes 31 such segments).  Nothing is launched for n_segments == 0.  Asynchronous on the context's
+ * stream. */
+int avr_clump_pair_energy(avr_context *ctx, const int64_t *offsets_host, uint64_t n_segments,
+                          const double *x_dev, const double *y_dev, const double *z_dev,
+                          const double *m_dev, double *w_dev, int64_t *depth_host);
+
 /* ---- isosurfaces ("Isosurface") --------------------------------------------------- */
 
 /* The isosurface field == value of `field` (a scene of ctx; raw f64 cells, no transform) by
