@@ -278,6 +278,11 @@ struct FrameLaunchPlan {
     // 0.378 ms per frame against 0.465 streamed; config-4's 370 MB are not, 0.967 -> 0.958)
     launch.classify_stream_stores =
         (classify_stream_stores && plan.classified_bytes > (256ull << 20)) ? 1 : 0;
+    // (decided for the frame's boxes, so for every chunk and every list of them)
+    launch.classify_by_wave = true;
+    for (const BoxDev& dev : plan.boxes) {
+      if (!classify_wave_box(dev, plan.consts)) launch.classify_by_wave = false;
+    }
     needs_classified = frame.kind != FrameKind::kProjection;
     return true;
   }

@@ -96,6 +96,21 @@ struct FrameConsts {
 // box: see bricklet_offset in avr_kernels.hip).
 constexpr int kBrickX = 8, kBrickY = 4, kBrickZ = 4, kBrickBytes = 128;
 constexpr int kClassifyChunk = 128;  // cells of one x-row handled by one classify workgroup
+// the standard API path of the scalar mapping (normalise on, scalarRange {0,1}, no log, no soft clip)
+inline bool standard_transform(const FrameConsts& fc) {
+  return !fc.log_scale && fc.normalize && !fc.apply_clip && fc.range_min == 0.0f &&
+         fc.inverse_range == 1.0f;
+}
+// Whether classify_wave_kernel (a wave per quarter tile, avr_kernels.hip) can classify the box:
+// every quarter tile of it lies wholly inside and is read by 16-byte loads at 32-bit byte
+// offsets, which is what classify_kernel asks of a tile before it takes its straight-line path.
+// A box without cells has no tiles and fits any launch.
+inline bool classify_wave_box(const BoxDev& box, const FrameConsts& fc) {
+  if (box.nx <= 0 || box.ny <= 0 || box.nz <= 0) return true;
+  return standard_transform(fc) && (reinterpret_cast<uintptr_t>(box.cells) & 15u) == 0 &&
+         (box.jstride & 1) == 0 && (box.kstride & 1) == 0 && box.jstride < (1 << 27) &&
+         box.nx % (kClassifyChunk / 4) == 0 && box.ny % kBrickY == 0 && box.nz % kBrickZ == 0;
+}
 
 // How the image's pixels are dealt to the N pieces of the direct-send exchange (one piece per
 // rank of the compositing group).
@@ -290,6 +305,7 @@ struct RenderLaunch {
                               // (0 = none): caps its occupancy beside the march
   int classify_stream_stores;  // the classified bricklets are written through to memory as a
                                // stream (their reader is a frame away) instead of stored plainly
+  bool classify_by_wave = false;  // every box takes classify_wave_kernel (classify_wave_box)
   const MarchItemDev* items_dev;  // n_items entries (multiple of kXcds)
   uint32_t n_items;
   int only_mode;                        // the IndexMode shared by every box, or -1

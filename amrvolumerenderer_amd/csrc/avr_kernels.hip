@@ -9,6 +9,8 @@
 //   classify_kernel     streams every f64 cell of the frame's boxes once and stores its
 //                       transfer-function table index as a byte in 8x4x4 bricklets
 //                       (the per-cell part of VolumePainter.cpp:870-883)
+//   classify_wave_kernel  the same pass for frames whose boxes are whole quarter tiles read by
+//                       16-byte loads: a wave per 32 x 4 x 4 cells, bricklets built in registers
 //   render_runs_kernel  one workgroup per (16x16-pixel tile, run), one thread per pixel: marches
 //                       the run's boxes in global layer order, folds them with the depth-sort
 //                       blend in registers and stores the run's layer in DirectSend "send layout"
@@ -1445,6 +1447,137 @@ __global__ __launch_bounds__(kBlockThreads) void classify_gated_kernel(
   }
 }
 
+// One WAVE per quarter tile (32 x-cells x 4 j-rows x 4 k-planes: 4 KiB in, four whole bricklets
+// out), for launches whose boxes all take the whole-tile path of classify_tile in every tile
+// (launch_classify: the standard transform, 16-byte aligned cells, even strides below 2^27, sides
+// that are multiples of 32 x 4 x 4).  The bricklet rows are put together in registers: no LDS
+// array, no barrier, 26 VGPRs, and a wave's slot is free again when its own store has issued,
+// not when the slowest wave of its workgroup has passed a barrier and stored.  The workgroup is
+// still a tile of classify_kernel under the same prefix sums -- four waves that share nothing,
+// quarter = wave -- because workgroups of one wave (four times the dispatches, the reserve
+// divided by four) were slower beside the march than classify_kernel: config-4, 200 frames,
+// 0.880 ms against 0.8675, these 0.857 (profiles/r6_classify_wave/).
+// Lane = (row r = lane >> 4, pair p = lane & 15): cells 2p, 2p + 1 of row r in each of the four
+// planes, so one load instruction covers four 256-byte row segments.
+constexpr int kQuarterCells = kClassifyChunk / 4;
+
+__global__ __launch_bounds__(kBlockThreads) void classify_wave_kernel(
+    const FrameConsts fc, const BoxDev* __restrict__ boxes,
+    const uint32_t* __restrict__ tile_begin, const int n_boxes, uint8_t* __restrict__ classified,
+    const int stream_stores, const int32_t* __restrict__ box_list,
+    const uint8_t* __restrict__ visible) {
+  const uint32_t tile = blockIdx.x;
+  const int quarter = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int lane = static_cast<int>(threadIdx.x & 63u);
+  // the prologue of classify_tile: which box (wave-uniform binary search over the prefix sums)
+  int lo = 0, hi = n_boxes;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tile_begin[mid] <= tile) {
+      lo = mid;
+    } else {
+      hi = mid;
+    }
+  }
+  if (visible != nullptr && visible[lo] == 0) return;
+  const BoxDev& box = boxes[box_list != nullptr ? box_list[lo] : lo];
+  const int nx = box.nx;
+  const int bricks_y = box.ny >> 2;
+  const int bricks_z = box.nz >> 2;
+  const int chunks = (nx + kClassifyChunk - 1) / kClassifyChunk;
+  // (a 32-bit division is ten vector instructions even of wave-uniform values, and beside the
+  // march the frame is bound by the issue of those: boxes of up to 128 cells of x and of a power
+  // of two of bricklets of y, every BASELINE box among them, get by without one)
+  uint32_t local = tile - tile_begin[lo];
+  int chunk = 0;
+  if (chunks > 1) {  // (wave-uniform, as is the next)
+    chunk = static_cast<int>(local % static_cast<uint32_t>(chunks));
+    local /= static_cast<uint32_t>(chunks);
+  }
+  int bj, bk;
+  if ((bricks_y & (bricks_y - 1)) == 0) {
+    bj = static_cast<int>(local & static_cast<uint32_t>(bricks_y - 1));
+    bk = static_cast<int>(local >> __builtin_ctz(static_cast<unsigned>(bricks_y)));
+  } else {
+    bj = static_cast<int>(local % static_cast<uint32_t>(bricks_y));
+    bk = static_cast<int>(local / static_cast<uint32_t>(bricks_y));
+  }
+  const int i0 = chunk * kClassifyChunk + quarter * kQuarterCells;
+  if (i0 >= nx) return;  // (the row's last tile has fewer quarters where nx is no multiple of 128)
+
+  const uint32_t jstride = static_cast<uint32_t>(box.jstride);
+  const uint32_t kstride = static_cast<uint32_t>(box.kstride);
+  const int r = lane >> 4;
+  const int p = lane & 15;
+  const uint32_t lane_bytes = (static_cast<uint32_t>(i0 + p * 2) +
+                               static_cast<uint32_t>(bj * kBrickY + r) * jstride) * 8u;
+  const __amdgpu_buffer_rsrc_t resource = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<double*>(box.cells), 0, kAllRecords, kRawBufferFlags);
+  typedef double double2_t __attribute__((ext_vector_type(2)));
+  double2_t raw[4];
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const uint32_t plane_bytes = static_cast<uint32_t>(bk * kBrickZ + pass) * kstride * 8u;
+    raw[pass] = __builtin_bit_cast(
+        double2_t, __builtin_amdgcn_raw_buffer_load_b128(resource, lane_bytes, plane_bytes, kStreamingLoad));
+  }
+  // All four loads are in flight before the first is used: with no store between them and their
+  // uses the compiler otherwise sinks each load to the block of its conversion, two in flight.
+  asm volatile("" ::: "memory");
+  // (the whole-tile conversion of classify_tile, expression for expression)
+  uint32_t two[4];
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const double a = raw[pass].x, b = raw[pass].y;
+    float sa = __builtin_amdgcn_fmed3f(static_cast<float>((a - fc.norm_min) * fc.inv_norm_span), 0.0f, 1.0f) * 255.0f;
+    float sb = __builtin_amdgcn_fmed3f(static_cast<float>((b - fc.norm_min) * fc.inv_norm_span), 0.0f, 1.0f) * 255.0f;
+    const bool odd = !__builtin_isfinite(a) || !__builtin_isfinite(b);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(odd) != 0, 0)) {
+      const float at_zero =
+          __builtin_amdgcn_fmed3f(static_cast<float>((0.0 - fc.norm_min) * fc.inv_norm_span), 0.0f, 1.0f) * 255.0f;
+      sa = __builtin_isfinite(a) ? sa : at_zero;
+      sb = __builtin_isfinite(b) ? sb : at_zero;
+    }
+    two[pass] = static_cast<uint32_t>(static_cast<int>(sa)) | (static_cast<uint32_t>(static_cast<int>(sb)) << 8);
+  }
+  // A quad of lanes (q = p & 3) holds the 8 x-cells of one bricklet row in each of the four planes:
+  // 4 x 4 byte pairs (lane x plane), transposed here so that lane q ends up with the row of plane q
+  // -- 8 bytes that lie together in the bricklet.  First the 2 x 2 blocks of dwords across lanes
+  // q and q ^ 2, then the 16-bit halves across lanes q and q ^ 1.
+  const uint32_t planes01 = two[0] | (two[1] << 16);
+  const uint32_t planes23 = two[2] | (two[3] << 16);
+  const bool upper = (lane & 2) != 0;  // this lane ends with a plane of 2, 3
+  const uint32_t passed = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(
+      0, static_cast<int>(upper ? planes01 : planes23), 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+  // its plane pair of quad lane (q & 1) and of quad lane (q & 1) + 2
+  const uint32_t near = upper ? passed : planes01;
+  const uint32_t far = upper ? planes23 : passed;
+  const bool second = (lane & 1) != 0;  // ... with the second plane of the pair: the high halves
+  // the halves the neighbour wants: (near's, far's) high ones from an even lane, low ones from an odd
+  const uint32_t give = __builtin_amdgcn_perm(far, near, second ? 0x05040100u : 0x07060302u);
+  const uint32_t got = static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(give), 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+  uint2 v;
+  // cells 0-3 of the row: quad lanes 0 and 1; cells 4-7: quad lanes 2 and 3
+  v.x = second ? __builtin_amdgcn_perm(near, got, 0x07060100u) : __builtin_amdgcn_perm(got, near, 0x05040100u);
+  v.y = second ? __builtin_amdgcn_perm(far, got, 0x07060302u) : __builtin_amdgcn_perm(got, far, 0x07060100u);
+
+  // bricklet (i0 / 8 + p / 4, bj, bk) of the z-fastest brick order, plane p & 3, row r
+  const uint64_t brick0 = (static_cast<uint64_t>(i0 >> 3) * static_cast<uint64_t>(bricks_y) +
+                           static_cast<uint64_t>(bj)) * static_cast<uint64_t>(bricks_z) +
+                          static_cast<uint64_t>(bk);
+  const uint32_t x_pitch = static_cast<uint32_t>(bricks_y * bricks_z) * kBrickBytes;
+  const uint32_t lane_off = static_cast<uint32_t>(__umul24(static_cast<unsigned>(p >> 2), x_pitch)) +
+                            static_cast<uint32_t>(p & 3) * 32u + static_cast<uint32_t>(r) * 8u;
+  uint2* const target =
+      reinterpret_cast<uint2*>(classified + box.cls_offset + brick0 * kBrickBytes + lane_off);
+  if (stream_stores != 0) {  // (wave-uniform; see classify_tile)
+    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1 nt" : : "v"(target), "v"(v) : "memory");
+  } else {
+    *target = v;
+  }
+}
+
 // ---- element-wise image algebra ------------------------------------------------------------
 
 __global__ void blend_depthsort_kernel(const float* __restrict__ top,
@@ -2043,9 +2176,7 @@ int launch_classify(const RenderLaunch& L, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (L.n_classify_tiles == 0) return AVR_OK;
   const FrameConsts& fc = L.consts;
-  // the standard API path (normalise on, scalarRange {0,1}, no log, no soft clip)
-  const bool simple = !fc.log_scale && fc.normalize && !fc.apply_clip && fc.range_min == 0.0f &&
-                      fc.inverse_range == 1.0f;
+  const bool simple = standard_transform(fc);
   const size_t pad = L.classify_lds_pad;  // occupancy cap beside the march (avr_renderer)
   // (a chunk of the frame: n_classify_boxes entries of box_list_dev under the chunk's own prefix)
   const int n_listed = L.box_list_dev != nullptr ? L.n_classify_boxes : L.n_boxes;
@@ -2062,6 +2193,13 @@ int launch_classify(const RenderLaunch& L, void* stream_v) {
                          L.box_list_dev, L.visible_in, L.classify_gate, L.n_classify_tiles);
     }
     return check_launch("classify_gated_kernel");
+  }
+  if (L.classify_by_wave) {
+    // (the same grid and the same reserve per four waves as classify_kernel)
+    hipLaunchKernelGGL(classify_wave_kernel, dim3(L.n_classify_tiles), dim3(kBlockThreads), pad,
+                       stream, L.consts, L.boxes_dev, L.tile_begin_dev, n_listed, L.classified,
+                       L.classify_stream_stores, L.box_list_dev, L.visible_in);
+    return check_launch("classify_wave_kernel");
   }
   if (simple) {
     hipLaunchKernelGGL(classify_kernel<true>, dim3(L.n_classify_tiles), dim3(kBlockThreads), pad,

@@ -31,7 +31,8 @@ for f in glob.glob(out + "/pass*/**/*counter_collection.csv", recursive=True):
         if "render_runs_kernel" in k:
             if "<true" in k: continue
             name = "render_runs_kernel"
-        elif "classify_kernel" in k:
+        elif "classify_kernel" in k or "classify_wave_kernel" in k:
+            # (the classify pass, whichever kernel the launch took: bench.py reads it under this name)
             name = "classify_kernel"
         elif "render_runs_repair_kernel" in k or "classify_gated_kernel" in k:
             # (a speculative frame's two repair launches: idle unless its march missed a box)
