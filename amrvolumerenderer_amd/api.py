@@ -1150,6 +1150,132 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     return result
 
 
+# ---- power spectra ("Power spectrum") ------------------------------------------------
+
+def power_spectrum_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes, prob_lo,
+                         ref_ratio, edges=None, fill: Optional[float] = None, rank: int = 0,
+                         n_ranks: int = 1) -> dict:
+    """The power spectrum of a scene's raw field over the cells [lo, lo + dims) of level `level`
+    ("Power spectrum"): the covering grid of covering_grid_scene, its 3-D transform
+    and the shell sums of |F|^2, all on the device; only the bins come back.  dims = (nx, ny, nz),
+    every one a power of two in [1, 1024]; edges: n + 1 wave numbers (2 pi over a length), by
+    default spectra.default_edges; fill: what a cell without data counts as -- with None such a
+    cell (absent > 0) raises ValueError.  The other arguments are covering_grid_scene's.  Returns
+    a dict: k_edges and k float64, power and spectrum float64 [n] (spectra.normalise), modes int64
+    [n], outside and nonfinite (modes beyond the edges; modes whose |F|^2 is not finite) and
+    absent.  With n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised
+    before any device work."""
+    import numpy as np
+    import torch
+    from . import spectra
+    level = int(level)
+    lo = tuple(int(v) for v in lo)
+    if len(lo) != 3:
+        raise ValueError("lo and dims must hold three values")
+    dims = spectra.check_dims(dims)
+    _require_one_rank(scene, n_ranks, "a power spectrum needs every box of the scene on one rank: "
+                      "cells are not gathered between ranks")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    if not 0 <= level < len(sizes):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    k_edges = (spectra.default_edges(dims, sizes[level]) if edges is None
+               else spectra.check_edges(edges))
+    edges_sq = spectra.squared_edges(k_edges)
+    g = spectra.inverse_length_sq(dims, sizes[level])
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    with _native_scenes(ctx, [scene]) as (field,):
+        values, coverage, _ = field.covering_grid(level, lo, dims, index, ratios,
+                                                  math.nan if fill is None else float(fill), True)
+        absent = int(torch.count_nonzero(coverage == 0.0).item())
+        if absent and fill is None:
+            raise ValueError(f"{absent} cells of the region hold no data: pass a fill value, or a "
+                             "region the loaded levels cover")
+        modes, sums, totals = ctx.spectrum_bins(ctx.fft3d(values), g, edges_sq)
+        ctx.synchronize()
+        modes, sums, totals = modes.cpu().numpy(), sums.cpu().numpy(), totals.cpu().numpy()
+    power, spectrum, k = spectra.normalise(sums, dims[0] * dims[1] * dims[2], k_edges)
+    return {"k_edges": np.array(k_edges), "k": k, "power": power, "spectrum": spectrum,
+            "modes": modes, "outside": int(totals[0]), "nonfinite": int(totals[1]),
+            "absent": absent}
+
+
+def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[int] = None,
+                   region=None, left_edge=None, right_edge=None, bins: Optional[int] = None,
+                   k_range=None, k_log: bool = False, edges=None, min_level: int = 0,
+                   max_level: int = -1, fill: Optional[float] = None,
+                   output: Optional[str] = None) -> dict:
+    """Power spectra of fields of a plotfile ("Power spectrum"), on cuda:0: each
+    field's covering grid at `level` over a region, its forward 3-D transform and |F|^2 summed
+    over shells of the wave number k = 2 pi |m / L|.  fields, level, region, left_edge /
+    right_edge, min_level and max_level as api.covering_grid takes them; the region must hold a
+    power of two of cells, 1024 at most, along every axis.  edges: n + 1 wave numbers, or bins
+    and / or k_range = (k_min, k_max) with k_log for equal ratios (spectra.make_edges); by
+    default spectra.default_edges, one bin per fundamental up to the smallest Nyquist wave
+    number.  fill: what a cell without data counts as; with None such cells raise ValueError.
+    Returns a dict: level, lo, dims (nx, ny, nz), cell_size, k_edges [n + 1], k [n] (the bins'
+    centres), fields {name: {"power", "spectrum", "modes"}} -- power [n]: sum |F|^2 / N^2 per bin,
+    which over all modes adds up to the field's mean square; spectrum [n]: power per unit k;
+    modes int64 [n] -- total [n] (the fields' power added in the order given: three velocity
+    components give a kinetic-energy spectrum), outside and nonfinite (modes beyond the edges and
+    modes whose |F|^2 is not finite, summed over the fields) and absent (cells without data).
+    With output the dict is written as one .npz file (spectra.save_npz)."""
+    import numpy as np
+    from . import grids, spectra
+    from . import plotfile as pf
+    if region is not None and (left_edge is not None or right_edge is not None):
+        raise ValueError("give region or left_edge / right_edge, not both")
+    if (left_edge is None) != (right_edge is None):
+        raise ValueError("left_edge and right_edge go together")
+    if edges is not None and (bins is not None or k_range is not None or k_log):
+        raise ValueError("give edges or bins / k_range / k_log, not both")
+    if edges is not None:
+        edges = spectra.check_edges(edges)
+        spectra.squared_edges(edges)
+    _require_plotfile(plotfile)
+    header = pf.PlotFileData(plotfile)
+    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
+    level = finest_loaded if level is None else int(level)
+    if not 0 <= level <= header.finest_level:
+        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
+    size = header.cell_size[level]
+    if region is not None:
+        first, last = (tuple(int(v) for v in corner) for corner in region)
+        if len(first) != 3 or len(last) != 3:
+            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
+        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
+        if min(dims) < 1:
+            raise ValueError("region must hold at least one cell along every axis")
+    elif left_edge is not None:
+        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
+    else:
+        refine = math.prod(header.ref_ratio[:level])
+        domain_lo, domain_hi = header.prob_domain[0]
+        lo = tuple(v * refine for v in domain_lo)
+        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
+    dims = spectra.check_dims(dims)
+    if edges is None:
+        edges = spectra.make_edges(dims, size, bins, k_range, bool(k_log))
+    spectra.squared_edges(edges)
+    names = [str(name) for name in fields] or [header.var_names[0]]
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
+    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
+    arguments = (level, lo, dims, *_header_levels(header, n_levels), edges, fill)
+    found, total, outside, nonfinite, absent, k = {}, None, 0, 0, 0, None
+    for name, scene in zip(names, scenes):
+        one = power_spectrum_scene(ctx, scene, *arguments, rank, world)
+        found[name] = {key: one[key] for key in ("power", "spectrum", "modes")}
+        total = one["power"].copy() if total is None else total + one["power"]
+        outside += one["outside"]
+        nonfinite += one["nonfinite"]
+        absent, k = one["absent"], one["k"]
+    result = {"level": level, "lo": lo, "dims": dims, "cell_size": tuple(float(v) for v in size),
+              "k_edges": np.array(edges, dtype=np.float64), "k": k, "fields": found,
+              "total": total, "outside": outside, "nonfinite": nonfinite, "absent": absent}
+    if output:
+        spectra.save_npz(result, output)
+    return result
+
+
 # ---- rays (DESIGN.md 7, "Rays") ---------------------------------------------------------------------
 
 def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_ratio,

@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
-// streamlines, covering grids, rays, per-ray sums):
+// streamlines, covering grids, rays, per-ray sums, power spectra):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -1932,6 +1932,143 @@ inline RaySumsPlan plan_ray_sums(const avr_box* field, size_t n_boxes, const avr
   plan.walk = plan_ray_walk(field, n_boxes, weight, n_weight_boxes, n_rays, max_trips, 0,
                             box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, present,
                             arrays, max_entries, &plan.weight_boxes);
+  return plan;
+}
+
+// ---- power spectra ------------------------------------------------------------------------
+// The twiddle table of a length-n transform ("Power spectrum"): n / 2 pairs W[m] =
+// (cos t, sin t) with t = -(2.0 pi m) / n evaluated in that order in f64, by the C library's cos
+// and sin.  n: a power of two in [1, 1024]; n == 1 has no entry.
+inline std::vector<double> fft_twiddles(int n) {
+  const double pi = 3.14159265358979323846;
+  std::vector<double> table(static_cast<size_t>(n / 2) * 2);
+  for (int m = 0; m < n / 2; ++m) {
+    const double theta = -(2.0 * pi * static_cast<double>(m)) / static_cast<double>(n);
+    table[2 * m] = std::cos(theta);
+    table[2 * m + 1] = std::sin(theta);
+  }
+  return table;
+}
+inline bool fft_length_ok(int64_t n) { return n >= 1 && n <= kFftMaxLength && (n & (n - 1)) == 0; }
+inline int fft_log2(int n) {
+  int p = 0;
+  while ((1 << p) < n) ++p;
+  return p;
+}
+// dims = (nx, ny, nz): every one a power of two in [1, 1024], fewer than 2^31 cells in all.
+// Returns the cells.
+inline uint64_t require_fft_dims(const int32_t dims[3]) {
+  for (int d = 0; d < 3; ++d) {
+    require_box(fft_length_ok(dims[d]), "dims must be powers of two in [1, 1024]");
+  }
+  const uint64_t cells = static_cast<uint64_t>(dims[0]) * static_cast<uint64_t>(dims[1]) *
+                         static_cast<uint64_t>(dims[2]);  // at most 2^30
+  require_box(cells < (uint64_t{1} << 31), "the grid has 2^31 cells or more");
+  return cells;
+}
+// How a strided pass over lines of length n cuts a plane of `columns` adjacent lines into
+// workgroups: `group` adjacent columns each -- kFftGroupElements / n, at least kFftMinColumns, at
+// most the plane's -- so that a workgroup's global accesses are runs of `group` 16-byte elements;
+// the last of the `groups` holds `last` columns, fewer when group does not divide columns.
+struct FftColumnGroups {
+  uint32_t group, groups, last;
+};
+inline FftColumnGroups fft_column_groups(uint64_t columns, int n) {
+  const uint64_t wanted = std::max<uint64_t>(kFftGroupElements / n, kFftMinColumns);
+  FftColumnGroups cut;
+  cut.group = static_cast<uint32_t>(std::min(columns, wanted));
+  cut.groups = static_cast<uint32_t>((columns + cut.group - 1) / cut.group);
+  cut.last = static_cast<uint32_t>(columns - static_cast<uint64_t>(cut.groups - 1) * cut.group);
+  return cut;
+}
+struct Fft3dPlan {
+  std::vector<double> twiddle[3];  // x, y, z; empty for an axis of length 1
+  FftArgs args{};
+  template <class Visit>
+  void visit_tables(FftArgs* to, Visit&& visit) const {
+    for (int d = 0; d < 3; ++d) visit(&to->twiddle[d], twiddle[d].data(), twiddle[d].size());
+  }
+};
+// The transform of the real grid `values` [nz][ny][nx] into `spectrum` [nz][ny][nx][2], both device
+// arrays the entry point has checked for null.  The rules, in this order: the dims, fewer than 2^31
+// cells, no byte shared between the input and the spectrum.
+inline Fft3dPlan plan_fft3d(const int32_t dims[3], const void* values, const void* spectrum) {
+  const uint64_t cells = require_fft_dims(dims);
+  ByteRanges read_ranges, write_ranges;
+  append_byte_range(&read_ranges, values, cells * sizeof(double));
+  append_byte_range(&write_ranges, spectrum, cells * 2 * sizeof(double));
+  require_no_shared_byte(&read_ranges, write_ranges, "the spectrum overlaps the input");
+  Fft3dPlan plan;
+  for (int d = 0; d < 3; ++d) plan.twiddle[d] = fft_twiddles(dims[d]);
+  FftArgs& args = plan.args;
+  args.nx = dims[0];
+  args.log2nx = fft_log2(dims[0]);
+  args.x_lines = static_cast<uint32_t>(cells / static_cast<uint64_t>(dims[0]));
+  args.x_group = static_cast<uint32_t>(
+      std::min<uint64_t>(args.x_lines, std::max(kFftGroupElements / dims[0], 1)));
+  const uint64_t row = static_cast<uint64_t>(dims[0]);
+  const uint64_t plane = row * static_cast<uint64_t>(dims[1]);
+  for (int axis = 1; axis <= 2; ++axis) {
+    FftPassDev& pass = args.pass[axis - 1];
+    pass.n = dims[axis];
+    pass.log2n = fft_log2(dims[axis]);
+    pass.planes = axis == 1 ? static_cast<uint32_t>(dims[2]) : 1u;
+    pass.columns = static_cast<uint32_t>(axis == 1 ? row : plane);
+    pass.plane_stride = plane;
+    pass.line_stride = axis == 1 ? row : plane;
+    const FftColumnGroups cut = fft_column_groups(pass.columns, pass.n);
+    pass.group = cut.group;
+    pass.groups = cut.groups;
+    pass.last = cut.last;
+  }
+  return plan;
+}
+
+struct SpectrumBinsPlan {
+  std::vector<double> edges_sq;  // n_bins + 1
+  SpectrumBinsArgs args{};
+  template <class Visit>
+  void visit_tables(SpectrumBinsArgs* to, Visit&& visit) const {
+    visit(&to->edges_sq, edges_sq.data(), edges_sq.size());
+  }
+};
+// The shell sums of `spectrum` [nz][ny][nx][2] ("Power spectrum"): a mode's q =
+// sum_d m_d^2 g[d] against the n_bins + 1 squared edges.  modes (u64 [n_bins]), power (f64
+// [n_bins]) and totals (u64 [2]) are device arrays the entry point has checked for null, as it has
+// inverse_length_sq and edges_sq.  The rules, in this order: the dims, fewer than 2^31 cells, n_bins, the
+// edges finite, E[0] >= 0, strictly increasing, g finite and positive, no output byte shared with
+// the spectrum.
+inline SpectrumBinsPlan plan_spectrum_bins(const int32_t dims[3], const double g[3],
+                                           const double* edges_sq, int n_bins,
+                                           const void* spectrum, const void* modes,
+                                           const void* power, const void* totals) {
+  const uint64_t cells = require_fft_dims(dims);
+  require_box(n_bins >= 1 && n_bins <= kSpectrumMaxBins, "n_bins must lie in [1, 2048]");
+  for (int i = 0; i <= n_bins; ++i) {
+    require_box(std::isfinite(edges_sq[i]), "edges_sq must be finite");
+  }
+  require_box(edges_sq[0] >= 0.0, "edges_sq must not be negative");
+  for (int i = 1; i <= n_bins; ++i) {
+    require_box(edges_sq[i - 1] < edges_sq[i], "edges_sq must be strictly increasing");
+  }
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(g[d]) && g[d] > 0.0,
+                "inverse_length_sq must be finite and positive");
+  }
+  ByteRanges read_ranges, write_ranges;
+  append_byte_range(&read_ranges, spectrum, cells * 2 * sizeof(double));
+  append_byte_range(&write_ranges, modes, static_cast<uint64_t>(n_bins) * sizeof(uint64_t));
+  append_byte_range(&write_ranges, power, static_cast<uint64_t>(n_bins) * sizeof(double));
+  append_byte_range(&write_ranges, totals, 2 * sizeof(uint64_t));
+  require_no_shared_byte(&read_ranges, write_ranges, "an output array overlaps the spectrum");
+  SpectrumBinsPlan plan;
+  plan.edges_sq.assign(edges_sq, edges_sq + n_bins + 1);
+  for (int d = 0; d < 3; ++d) {
+    plan.args.log2n[d] = fft_log2(dims[d]);
+    plan.args.g[d] = g[d];
+  }
+  plan.args.n_bins = n_bins;
+  plan.args.n_modes = static_cast<uint32_t>(cells);
   return plan;
 }
 

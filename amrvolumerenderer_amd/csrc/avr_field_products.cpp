@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, rays and per-ray sums.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, rays, per-ray sums and power spectra.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -30,7 +30,7 @@ void require_field_scene(const avr_context* ctx, const avr_scene* field, size_t 
 
 }  // namespace
 
-// The sixteen entry points below read the same way, top to bottom: bind the device; refuse null
+// The entry points below read the same way, top to bottom: bind the device; refuse null
 // handles and device pointers; refuse scenes of another context or box count (require_field_scene);
 // make the plan, which holds every rule on the plain arguments and the boxes; the call's side
 // effects on its outputs (a written scene's classification keys, a cleared count); return where
@@ -496,6 +496,50 @@ int avr_scene_ray_sums(avr_context* ctx, const avr_scene* field, const avr_scene
     args.counted = counted_dev;
     args.covered = covered_dev;
     return avr::launch_ray_sums(args, ctx->stream);
+  });
+}
+
+int avr_fft_twiddles(int n, double* table) {
+  return guarded([&]() -> int {
+    require(table != nullptr, "null argument");
+    require(n >= 2 && avr::fft_length_ok(n), "n must be a power of two in [2, 1024]");
+    const std::vector<double> made = avr::fft_twiddles(n);
+    std::copy(made.begin(), made.end(), table);
+    return AVR_OK;
+  });
+}
+
+int avr_field_fft(avr_context* ctx, const double* values_dev, const int32_t* dims,
+                  double* spectrum_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(values_dev != nullptr && dims != nullptr && spectrum_dev != nullptr, "null argument");
+    const avr::Fft3dPlan plan = avr::plan_fft3d(dims, values_dev, spectrum_dev);
+    avr::FftArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.values = values_dev;
+    args.spectrum = spectrum_dev;
+    return avr::launch_fft3d(args, ctx->stream);
+  });
+}
+
+int avr_spectrum_bins(avr_context* ctx, const double* spectrum_dev, const int32_t* dims,
+                      const double* inverse_length_sq, const double* edges_sq, int n_bins,
+                      uint64_t* modes_dev, double* power_dev, uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(spectrum_dev != nullptr && dims != nullptr && inverse_length_sq != nullptr &&
+                edges_sq != nullptr && modes_dev != nullptr && power_dev != nullptr &&
+                totals_dev != nullptr, "null argument");
+    const avr::SpectrumBinsPlan plan = avr::plan_spectrum_bins(
+        dims, inverse_length_sq, edges_sq, n_bins, spectrum_dev, modes_dev, power_dev, totals_dev);
+    avr::SpectrumBinsArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.spectrum = spectrum_dev;
+    args.modes = reinterpret_cast<unsigned long long*>(modes_dev);
+    args.power = power_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_spectrum_bins(args, ctx->stream);
   });
 }
 

@@ -963,6 +963,48 @@ struct RayArgs {
 int launch_rays(const RayArgs& args, bool emit, void* stream);
 int launch_ray_sums(const RayArgs& args, void* stream);
 
+// Power spectra (avr_fft.hip; DESIGN.md 7, "Power spectrum"): the forward, unnormalised 3-D
+// transform of a real f64 grid [nz][ny][nx] into an interleaved complex spectrum [nz][ny][nx][2],
+// one radix-2 pass per axis with whole lines in LDS, and the shell sums of a spectrum.
+constexpr int kFftMaxLength = 1024;       // per axis; a power of two
+constexpr int kFftGroupElements = 2048;   // complex elements a workgroup stages (32 KiB) ...
+constexpr int kFftMinColumns = 4;         // ... but never fewer adjacent columns than this (64-byte
+                                          // runs): 4 lines of 1024 are 64 KiB, the most ever staged
+constexpr int kSpectrumMaxBins = 2048;    // 20 bytes of LDS per bin
+// One strided pass (y or z): `planes` planes of `columns` adjacent lines each; element e of the
+// line in column c of plane q is the complex at q * plane_stride + e * line_stride + c.  A
+// workgroup stages `group` adjacent columns, the last of a plane's `groups` only `last`.
+struct FftPassDev {
+  int32_t n, log2n;          // the line's length 2^log2n; n == 1: the pass is not launched
+  uint32_t planes, columns;
+  uint32_t group, groups, last;
+  uint32_t pad_;
+  uint64_t plane_stride, line_stride;  // in complex elements
+};
+struct FftArgs {
+  const double* values;      // [nz][ny][nx]
+  double* spectrum;          // [nz][ny][nx][2]
+  const double* twiddle[3];  // per axis (x, y, z): W[m] = (cos, sin)(-(2 pi m) / n), n / 2 pairs
+  int32_t nx, log2nx;
+  uint32_t x_lines;          // ny * nz
+  uint32_t x_group;          // lines a workgroup of the x pass stages
+  FftPassDev pass[2];        // y, z
+};
+int launch_fft3d(const FftArgs& args, void* stream);
+struct SpectrumBinsArgs {
+  const double* spectrum;    // [nz][ny][nx][2]
+  const double* edges_sq;    // n_bins + 1
+  int32_t log2n[3];          // x, y, z
+  int32_t n_bins;
+  uint32_t n_modes;          // nx * ny * nz < 2^31
+  uint32_t pad_;
+  double g[3];               // 1 / L_d^2
+  unsigned long long* modes; // [n_bins], added to
+  double* power;             // [n_bins], added to
+  unsigned long long* totals;  // (outside, nonfinite), added to
+};
+int launch_spectrum_bins(const SpectrumBinsArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

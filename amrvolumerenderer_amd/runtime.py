@@ -247,6 +247,51 @@ class Context:
     def empty(self, *shape, dtype=torch.float32) -> torch.Tensor:
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
+    # -- power spectra ------------------------------------------------------------------------
+    def fft3d(self, values: torch.Tensor) -> torch.Tensor:
+        """avr_field_fft: the forward, unnormalised 3-D transform of a real grid (DESIGN.md 7,
+        "Power spectrum").  values: contiguous float64 [nz, ny, nx] on the device, every
+        dimension a power of two in [1, 1024].  Returns the spectrum, float64 [nz, ny, nx, 2]
+        with (re, im) interleaved, on the device.  Asynchronous on the context's stream."""
+        self._check_tensor(values, torch.float64, "values")
+        if values.ndim != 3 or values.numel() == 0:
+            raise ValueError("values must be [nz, ny, nx] with at least one cell")
+        nz, ny, nx = (int(v) for v in values.shape)
+        dims = np.array([nx, ny, nz], dtype=np.int32)
+        spectrum = torch.empty((nz, ny, nx, 2), dtype=torch.float64, device=self.device)
+        _native(self, "avr_field_fft", self._handle, _pointer(values), _ints(dims),
+                _pointer(spectrum))
+        return spectrum
+
+    def spectrum_bins(self, spectrum: torch.Tensor, inverse_length_sq, edges_sq, out=None):
+        """avr_spectrum_bins: ADDS the shell sums of a spectrum (float64 [nz, ny, nx, 2] on the
+        device, as fft3d returns it) to (modes int64 [n], power float64 [n], totals int64 [2] =
+        (outside, nonfinite)) on the device: `out`, or new zeroed tensors.  inverse_length_sq:
+        1 / L_d^2 for d = x, y, z; edges_sq: the n + 1 squared edges (e / (2 pi))^2, strictly
+        increasing from a value >= 0 ("Power spectrum").  Returns (modes, power,
+        totals).  Asynchronous on the context's stream."""
+        self._check_tensor(spectrum, torch.float64, "spectrum")
+        if spectrum.ndim != 4 or spectrum.shape[3] != 2 or spectrum.numel() == 0:
+            raise ValueError("spectrum must be [nz, ny, nx, 2] with at least one mode")
+        nz, ny, nx = (int(v) for v in spectrum.shape[:3])
+        dims = np.array([nx, ny, nz], dtype=np.int32)
+        g = np.ascontiguousarray(inverse_length_sq, dtype=np.float64)
+        edges = np.ascontiguousarray(edges_sq, dtype=np.float64)
+        if g.shape != (3,):
+            raise ValueError("inverse_length_sq must hold three values")
+        if edges.ndim != 1 or edges.size < 2:
+            raise ValueError("edges_sq must hold at least two values")
+        n = int(edges.size) - 1
+        modes, power, totals = out if out is not None else (None, None, None)
+        wrong = "out must be (modes int64 [n], power float64 [n], totals int64 [2])"
+        modes = _output(self, modes, torch.int64, (n,), "modes", torch.zeros, wrong)
+        power = _output(self, power, torch.float64, (n,), "power", torch.zeros, wrong)
+        totals = _output(self, totals, torch.int64, (2,), "totals", torch.zeros, wrong)
+        _native(self, "avr_spectrum_bins", self._handle, _pointer(spectrum), _ints(dims),
+                _doubles(g), _doubles(edges), n, _pointer(modes), _pointer(power),
+                _pointer(totals))
+        return modes, power, totals
+
     # -- clump binding ------------------------------------------------------------------------
     def clump_pair_energy(self, offsets, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
                           m: torch.Tensor, w: Optional[torch.Tensor] = None):

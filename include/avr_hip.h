@@ -1509,6 +1509,51 @@ int avr_scene_ray_sums(avr_context *ctx, const avr_scene *field, const avr_scene
                        uint8_t *status_dev, double *span_dev, double *integral_dev,
                        double *weight_dev, double *counted_dev, double *covered_dev);
 
+/* ---- power spectra ("Power spectrum") ------------------------------------------------ */
+
+/* The twiddle table the transform's kernels use for a line of n values, as n / 2 pairs: table[2 m]
+ * = cos t and table[2 m + 1] = sin t with t = -(2.0 pi m) / n evaluated in that order in double,
+ * by the C library's cos and sin.  Host only: no context, no device work.
+ * AVR_ERR_INVALID_ARGUMENT for a NULL table and for an n that is not a power of two in [2, 1024]. */
+int avr_fft_twiddles(int n, double *table);
+
+/* The forward, unnormalised 3-D discrete Fourier transform F[k] = sum_n x[n] exp(-2 pi i k n / N)
+ * of the real grid values_dev (device, f64 [dims[2]][dims[1]][dims[0]], dims = (nx, ny, nz)) into
+ * spectrum_dev (device, f64 [dims[2]][dims[1]][dims[0]][2], (re, im) interleaved).  The imaginary
+ * part starts at +0.0; every line is transformed along x, then along y, then along z.  One line of
+ * N = 2^p values: the input permuted by bit reversal of the p-bit index, then stages s = 1 .. p of
+ * radix-2 decimation in time -- with half = 2^(s - 1) and step = N / 2^s, for every block of
+ * 2 half elements and every j in [0, half): a = v[block + j], b = v[block + j + half], w =
+ * W[j step] (avr_fft_twiddles), t = (w.re b.re - w.im b.im, w.re b.im + w.im b.re), each component
+ * two rounded multiplies and one rounded add or subtract with nothing fused, v[block + j] = a + t
+ * and v[block + j + half] = a - t.  N = 1 is the identity.  Equal arguments give equal bits.
+ * Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for a NULL argument, a dims that is not a power of two in [1, 1024],
+ * 2^31 cells or more, and a spectrum that shares a byte with the input -- and the spectrum is
+ * untouched.  Stateless; asynchronous on the context's stream. */
+int avr_field_fft(avr_context *ctx, const double *values_dev, const int32_t *dims,
+                  double *spectrum_dev);
+
+/* Shell sums of a spectrum (spectrum_dev as avr_field_fft writes it, dims = (nx, ny, nz)).  The
+ * mode at (kz, ky, kx) has per axis the signed wave number m_d = k_d if k_d < N_d / 2 or N_d == 1,
+ * else k_d - N_d; q = f64(mx)^2 g[0] + f64(my)^2 g[1], then + f64(mz)^2 g[2], with g =
+ * inverse_length_sq (host, 3 doubles: 1 / L_d^2), each term one multiply of the exact integer
+ * square; p = re re + im im.  edges_sq (host, n_bins + 1 doubles) are the squared edges E[i] =
+ * (e[i] / (2 pi))^2: E[i] <= q < E[i + 1] puts the mode in bin i, q == E[n_bins] in the last bin,
+ * decided by f64 comparisons alone.  Per mode, in this order: p not finite adds one to
+ * totals_dev[1] (nonfinite); else q outside the edges adds one to totals_dev[0] (outside); else
+ * modes_dev[bin] += 1 and power_dev[bin] += p (f64 additions in no fixed order).  modes_dev (u64
+ * [n_bins]), power_dev (f64 [n_bins]) and totals_dev (u64 [2]) are device arrays that are ADDED
+ * to, as avr_scene_joint_histogram's are.  Everything is checked on the host before any device
+ * work, in this order: AVR_ERR_INVALID_ARGUMENT for a NULL argument, a dims that is not a power of
+ * two in [1, 1024], 2^31 cells or more, n_bins outside [1, 2048], an edge that is not finite, a
+ * negative E[0], edges that do not strictly increase, a g that is not finite and positive, and an
+ * output that shares a byte with the spectrum -- and every output is untouched.  Stateless;
+ * asynchronous on the context's stream. */
+int avr_spectrum_bins(avr_context *ctx, const double *spectrum_dev, const int32_t *dims,
+                      const double *inverse_length_sq, const double *edges_sq, int n_bins,
+                      uint64_t *modes_dev, double *power_dev, uint64_t *totals_dev);
+
 #ifdef __cplusplus
 }
 #endif
