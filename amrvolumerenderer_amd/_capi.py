@@ -254,6 +254,11 @@ SIGNATURES = {
     "avr_field_fft": (C.c_int, [_vp, _vp, _ip, _vp]),
     "avr_spectrum_bins": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.c_int, _vp, _vp, _vp]),
+    "avr_field_ifft": (C.c_int, [_vp, _vp, _ip, _vp, _vp]),
+    "avr_spectrum_helmholtz": (C.c_int, [_vp, C.POINTER(C.c_void_p), _ip, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_void_p)]),
+    "avr_spectrum_inverse_laplacian": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double),
+                                                 C.c_double]),
     "avr_scene_rays": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip,
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _vp,
                                  C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

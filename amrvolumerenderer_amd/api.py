@@ -1276,6 +1276,259 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
     return result
 
 
+# ---- inverse transform, Helmholtz split, potential -----------------------------------
+
+def _periodic_grid_arguments(scene: "SceneGeometry", level, lo, dims, cell_sizes, n_ranks: int,
+                             what: str):
+    """(level, lo, dims, the level's cell size) of a *_scene function over a periodic power-of-two
+    grid, checked as power_spectrum_scene checks them, before any device work."""
+    from . import spectra
+    level = int(level)
+    lo = tuple(int(v) for v in lo)
+    if len(lo) != 3:
+        raise ValueError("lo and dims must hold three values")
+    dims = spectra.check_dims(dims)
+    _require_one_rank(scene, n_ranks, f"{what} needs every box of the scene on one rank: cells "
+                      "are not gathered between ranks")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    if not 0 <= level < len(sizes):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    return level, lo, dims, sizes[level]
+
+
+def _covered_grid(field, level, lo, dims, index, ratios, fill):
+    """(values, absent) of one native scene's covering grid; absent cells without a fill value
+    raise ValueError."""
+    import torch
+    values, coverage, _ = field.covering_grid(level, lo, dims, index, ratios,
+                                              math.nan if fill is None else float(fill), True)
+    absent = int(torch.count_nonzero(coverage == 0.0).item())
+    if absent and fill is None:
+        raise ValueError(f"{absent} cells of the region hold no data: pass a fill value, or a "
+                         "region the loaded levels cover")
+    return values, absent
+
+
+def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeometry",
+                    level: int, lo, dims, cell_sizes, prob_lo, ref_ratio, edges=None,
+                    fill: Optional[float] = None, grids: bool = True, rank: int = 0,
+                    n_ranks: int = 1) -> dict:
+    """The Helmholtz split of the velocity field (vx, vy, vz) -- three scenes over the same boxes
+    -- on the periodic grid of the cells [lo, lo + dims) of level `level` ("Inverse
+    transform, Helmholtz split, potential"): three covering grids, their transforms, the split
+    into a solenoidal (divergence-free) and a compressive (curl-free) part per mode, the shell
+    sums of the three solenoidal and of the three compressive spectra into two sets of bins and,
+    with grids, the six inverse transforms, all on the device.  dims, edges and fill as
+    power_spectrum_scene takes them, the other arguments as covering_grid_scene does.  Returns a
+    dict: k_edges and k float64; power, spectrum and modes, dicts with "solenoidal" and
+    "compressive" (spectra.normalise of the sums over the three components; modes int64 [n] counts
+    a mode once per component) and, power and spectrum, "total", their sum; outside and nonfinite
+    (summed over the six spectra); absent; with grids also solenoidal and compressive (three
+    float64 [nz, ny, nx] numpy arrays each) and imag_max, the largest |imaginary part| the six
+    inverses left.  With n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is
+    raised before any device work."""
+    import numpy as np
+    import torch
+    from . import spectra
+    level, lo, dims, size = _periodic_grid_arguments(vx, level, lo, dims, cell_sizes, n_ranks,
+                                                     "a Helmholtz split")
+    for other in (vy, vz):
+        _require_one_rank(other, n_ranks, "a Helmholtz split needs every box of the scene on one "
+                          "rank: cells are not gathered between ranks")
+        if len(other.local_boxes) != len(vx.local_boxes):
+            raise ValueError("vx, vy and vz must be scenes over the same boxes")
+    k_edges = spectra.default_edges(dims, size) if edges is None else spectra.check_edges(edges)
+    edges_sq = spectra.squared_edges(k_edges)
+    g = spectra.inverse_length_sq(dims, size)
+    h = spectra.inverse_length(dims, size)
+    sizes, ratios, index = _level_setup(vx, vx.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    found = {}
+    with _native_scenes(ctx, [vx, vy, vz]) as fields:
+        transformed, absent = [], 0
+        for field in fields:
+            values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+            transformed.append(ctx.fft3d(values))
+        parts = dict(zip(spectra.PARTS, ctx.helmholtz_split(*transformed, h)))
+        binned = {}
+        for part, three in parts.items():
+            out = None
+            for spectrum in three:
+                out = ctx.spectrum_bins(spectrum, g, edges_sq, out)
+            binned[part] = out
+        if grids:
+            worst = torch.zeros((), dtype=torch.float64, device=ctx.device)
+            for part, three in parts.items():
+                found[part] = []
+                for spectrum in three:
+                    real, imag = ctx.ifft3d(spectrum, with_imag=True)
+                    # torch.maximum lets a NaN through, as the largest |imag| of such a grid is
+                    worst = torch.maximum(worst, imag.abs().max())
+                    found[part].append(real)
+        ctx.synchronize()
+        binned = {part: tuple(t.cpu().numpy() for t in out) for part, out in binned.items()}
+        if grids:
+            found = {part: tuple(t.cpu().numpy() for t in three) for part, three in found.items()}
+            found["imag_max"] = float(worst.item())
+    cells = dims[0] * dims[1] * dims[2]
+    result = {"k_edges": np.array(k_edges), "power": {}, "spectrum": {}, "modes": {}}
+    for part, (modes, sums, totals) in binned.items():
+        power, spectrum, result["k"] = spectra.normalise(sums, cells, k_edges)
+        result["power"][part], result["spectrum"][part], result["modes"][part] = \
+            power, spectrum, modes
+    for key in ("power", "spectrum"):
+        result[key]["total"] = result[key]["solenoidal"] + result[key]["compressive"]
+    result["compressive_fraction"] = spectra.compressive_fraction(
+        result["power"]["solenoidal"], result["power"]["compressive"], k_edges)
+    result["outside"] = sum(int(binned[part][2][0]) for part in binned)
+    result["nonfinite"] = sum(int(binned[part][2][1]) for part in binned)
+    result["absent"] = absent
+    result.update(found)
+    return result
+
+
+def _plotfile_grid(plotfile: str, level, region, left_edge, right_edge, min_level: int,
+                   max_level: int):
+    """(header, level, lo, dims) of a plotfile-level function over a periodic power-of-two grid:
+    region, level and the power-of-two rule as api.power_spectrum has them, before anything is
+    loaded."""
+    from . import grids, spectra
+    from . import plotfile as pf
+    if region is not None and (left_edge is not None or right_edge is not None):
+        raise ValueError("give region or left_edge / right_edge, not both")
+    if (left_edge is None) != (right_edge is None):
+        raise ValueError("left_edge and right_edge go together")
+    _require_plotfile(plotfile)
+    header = pf.PlotFileData(plotfile)
+    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
+    level = finest_loaded if level is None else int(level)
+    if not 0 <= level <= header.finest_level:
+        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
+    size = header.cell_size[level]
+    if region is not None:
+        first, last = (tuple(int(v) for v in corner) for corner in region)
+        if len(first) != 3 or len(last) != 3:
+            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
+        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
+        if min(dims) < 1:
+            raise ValueError("region must hold at least one cell along every axis")
+    elif left_edge is not None:
+        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
+    else:
+        refine = math.prod(header.ref_ratio[:level])
+        domain_lo, domain_hi = header.prob_domain[0]
+        lo = tuple(v * refine for v in domain_lo)
+        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
+    return header, level, lo, spectra.check_dims(dims)
+
+
+def helmholtz(plotfile: str, velocity: Sequence[str], level: Optional[int] = None, region=None,
+              left_edge=None, right_edge=None, bins: Optional[int] = None, k_range=None,
+              k_log: bool = False, edges=None, grids: bool = True, min_level: int = 0,
+              max_level: int = -1, fill: Optional[float] = None,
+              output: Optional[str] = None) -> dict:
+    """The Helmholtz split of a plotfile's velocity field into its solenoidal and compressive
+    parts ("Inverse transform, Helmholtz split, potential"), on cuda:0, over a
+    periodic grid.  velocity: the names of the three components (x, y, z), stored, derived or
+    gradient fields; every other argument as api.power_spectrum takes it.  Returns a dict: level,
+    lo, dims (nx, ny, nz), cell_size, k_edges [n + 1], k [n]; power, spectrum and modes, dicts
+    with "solenoidal" and "compressive" -- the kinetic-energy spectra of the two parts, the three
+    components added, normalised as api.power_spectrum's -- and "total" (power and spectrum);
+    compressive_fraction, sum(P_c) / (sum(P_c) + sum(P_s)) over the bins with a lower edge above
+    0 (spectra.compressive_fraction); outside, nonfinite and absent; and with grids solenoidal
+    and compressive, {name: float64 [nz, ny, nx]} with the components' names, and imag_max, the
+    largest |imaginary part| the six inverse transforms left (rounding alone, unless cells are not
+    finite).  With output the dict is written as one .npz file (spectra.save_helmholtz_npz)."""
+    from . import spectra
+    names = [velocity] if isinstance(velocity, str) else [str(name) for name in velocity]
+    if len(names) != 3:
+        raise ValueError("velocity must name three components")
+    if edges is not None and (bins is not None or k_range is not None or k_log):
+        raise ValueError("give edges or bins / k_range / k_log, not both")
+    if edges is not None:
+        edges = spectra.check_edges(edges)
+        spectra.squared_edges(edges)
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level)
+    size = header.cell_size[level]
+    if edges is None:
+        edges = spectra.make_edges(dims, size, bins, k_range, bool(k_log))
+    spectra.squared_edges(edges)
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
+    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
+    found = helmholtz_scene(ctx, *scenes, level, lo, dims, *_header_levels(header, n_levels),
+                            edges, fill, bool(grids), rank, world)
+    result = {"level": level, "lo": lo, "dims": dims, "cell_size": tuple(float(v) for v in size)}
+    result.update(found)
+    for part in ("solenoidal", "compressive"):
+        if part in found:
+            result[part] = dict(zip(names, found[part]))
+    if output:
+        spectra.save_helmholtz_npz(result, output)
+    return result
+
+
+def potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes, prob_lo,
+                    ref_ratio, constant: float = 1.0, fill: Optional[float] = None,
+                    rank: int = 0, n_ranks: int = 1) -> dict:
+    """The periodic solution of laplace(phi) = constant (rho - mean rho) for a scene's raw field
+    rho over the cells [lo, lo + dims) of level `level` ("Inverse transform,
+    Helmholtz split, potential"): the covering grid, its transform, every mode times scale / q
+    with scale = -(constant / (4 pi^2)) and q = sum_d m_d^2 / L_d^2 (the mean mode becomes 0) and
+    the inverse transform, all on the device.  dims and fill as power_spectrum_scene takes them,
+    the other arguments as covering_grid_scene does.  Returns a dict: potential float64
+    [nz, ny, nx] (numpy), imag_max (the largest |imaginary part| the inverse left) and absent.
+    With n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised before any
+    device work."""
+    from . import spectra
+    constant = float(constant)
+    if not math.isfinite(constant):
+        raise ValueError("constant must be finite")
+    level, lo, dims, size = _periodic_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
+                                                     "a potential")
+    g = spectra.inverse_length_sq(dims, size)
+    scale = -(constant / (4.0 * math.pi * math.pi))
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    with _native_scenes(ctx, [scene]) as (field,):
+        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+        spectrum = ctx.inverse_laplacian(ctx.fft3d(values), g, scale)
+        real, imag = ctx.ifft3d(spectrum, with_imag=True)
+        worst = imag.abs().max()
+        ctx.synchronize()
+        return {"potential": real.cpu().numpy(), "imag_max": float(worst.item()),
+                "absent": absent}
+
+
+def potential(plotfile: str, variable: str = "", constant: float = 1.0,
+              level: Optional[int] = None, region=None, left_edge=None, right_edge=None,
+              min_level: int = 0, max_level: int = -1, fill: Optional[float] = None,
+              output: Optional[str] = None) -> dict:
+    """The periodic potential of a field of a plotfile ("Inverse transform,
+    Helmholtz split, potential"), on cuda:0: phi with laplace(phi) = constant (rho - mean rho) on
+    the covering grid of `variable` (by default the first variable) at `level` over a region with
+    periodic boundaries -- constant = 4 pi G gives the gravitational potential of a density.
+    level, region, left_edge / right_edge, min_level, max_level and fill as api.power_spectrum
+    takes them.  Returns a dict: level, lo, dims (nx, ny, nz), cell_size, constant, potential
+    float64 [nz, ny, nx], imag_max and absent.  With output the dict is written as one .npz file
+    (spectra.save_potential_npz)."""
+    from . import spectra
+    constant = float(constant)
+    if not math.isfinite(constant):
+        raise ValueError("constant must be finite")
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level)
+    name = str(variable) or header.var_names[0]
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, [name], min_level, max_level)
+    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
+    found = potential_scene(ctx, scenes[0], level, lo, dims, *_header_levels(header, n_levels),
+                            constant, fill, rank, world)
+    result = {"level": level, "lo": lo, "dims": dims,
+              "cell_size": tuple(float(v) for v in header.cell_size[level]), "constant": constant}
+    result.update(found)
+    if output:
+        spectra.save_potential_npz(result, output)
+    return result
+
+
 # ---- rays (DESIGN.md 7, "Rays") ---------------------------------------------------------------------
 
 def ray_scene(ctx, scene: "SceneGeometry", start, end, cell_sizes, prob_lo, ref_ratio,

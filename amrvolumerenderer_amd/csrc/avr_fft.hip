@@ -4,6 +4,8 @@
 //   fft_x_kernel          real [nz][ny][nx] -> complex [nz][ny][nx][2], transformed along x
 //   fft_column_kernel     one strided pass (y, then z) in place on the spectrum
 //   spectrum_bins_kernel  |F|^2 of every mode added to the bin of its wave number
+//   ifft_x_kernel         the inverse's last pass: complex lines along x -> real grids, scaled
+//                         (the inverse's z and y passes are fft_column_kernel with conjugate tables)
 //
 // A line is transformed as the definition states it: the input permuted by bit reversal of the
 // log2(n)-bit index, then stages s = 1 .. log2(n) of radix-2 decimation in time, in stage s for
@@ -128,6 +130,34 @@ __global__ __launch_bounds__(kThreads) void fft_column_kernel(double2_t* spectru
   }
 }
 
+// The inverse's x pass ("Inverse transform, Helmholtz split, potential"): x_group
+// whole lines of complex input, the stages with the conjugate table V, then re * scale to `values`
+// and, where asked for, im * scale to `imag`.  Launched for nx == 1 as well: the scale and split.
+__global__ __launch_bounds__(kThreads) void ifft_x_kernel(const IfftArgs a) {
+  extern __shared__ double2_t fft_lds[];
+  const int p = a.log2nx;
+  const uint32_t first = blockIdx.x * a.x_group;
+  const uint32_t left = a.x_lines - first;
+  const uint32_t lines = left < a.x_group ? left : a.x_group;
+  const uint32_t elements = lines << p;
+  const size_t base = static_cast<size_t>(first) << p;
+  const double2_t* __restrict__ in = reinterpret_cast<const double2_t*>(a.spectrum) + base;
+  for (uint32_t e = threadIdx.x; e < elements; e += kThreads) {
+    const uint32_t line = e >> p, index = e & ((1u << p) - 1u);
+    fft_lds[(line << p) + swizzle(reverse_bits(index, p), line, p)] = in[e];
+  }
+  line_stages(fft_lds, lines, p, reinterpret_cast<const double2_t*>(a.twiddle[0]));
+  double* __restrict__ values = a.values + base;
+  double* __restrict__ imag = a.imag != nullptr ? a.imag + base : nullptr;
+  const double scale = a.scale;
+  for (uint32_t e = threadIdx.x; e < elements; e += kThreads) {
+    const uint32_t line = e >> p, k = e & ((1u << p) - 1u);
+    const double2_t value = fft_lds[(line << p) + swizzle(k, line, p)];
+    values[e] = value.x * scale;
+    if (imag != nullptr) imag[e] = value.y * scale;
+  }
+}
+
 // The signed wave number of index k along an axis of 2^p modes (numpy.fft.fftfreq's convention).
 __device__ __forceinline__ double signed_mode(uint32_t k, int p) {
   const int n = 1 << p;
@@ -245,6 +275,25 @@ int launch_fft3d(const FftArgs& args, void* stream_v) {
     status = check("fft_column_kernel");
   }
   return status;
+}
+
+int launch_ifft3d(const IfftArgs& args, void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  int status = AVR_OK;
+  for (int which = 1; which >= 0 && status == AVR_OK; --which) {  // z, then y
+    const FftPassDev& pass = args.pass[which];
+    if (pass.n == 1) continue;  // the identity
+    const size_t bytes = (static_cast<size_t>(pass.group) << pass.log2n) * sizeof(double2_t);
+    hipLaunchKernelGGL(fft_column_kernel, dim3(pass.planes * pass.groups), dim3(kThreads), bytes,
+                       stream, reinterpret_cast<double2_t*>(args.spectrum),
+                       reinterpret_cast<const double2_t*>(args.twiddle[which + 1]), pass);
+    status = check("fft_column_kernel");
+  }
+  if (status != AVR_OK) return status;
+  const uint32_t x_groups = (args.x_lines + args.x_group - 1) / args.x_group;
+  const size_t x_bytes = (static_cast<size_t>(args.x_group) << args.log2nx) * sizeof(double2_t);
+  hipLaunchKernelGGL(ifft_x_kernel, dim3(x_groups), dim3(kThreads), x_bytes, stream, args);
+  return check("ifft_x_kernel");
 }
 
 int launch_spectrum_bins(const SpectrumBinsArgs& args, void* stream_v) {

@@ -24,6 +24,7 @@
 #define AVR_FIELD_PLANS_H
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -1981,6 +1982,30 @@ inline FftColumnGroups fft_column_groups(uint64_t columns, int n) {
   cut.last = static_cast<uint32_t>(columns - static_cast<uint64_t>(cut.groups - 1) * cut.group);
   return cut;
 }
+// The lines a workgroup of an x pass (forward or inverse) stages: kFftGroupElements / nx, at least
+// one, at most all x_lines of them.
+inline uint32_t fft_x_group(uint32_t x_lines, int nx) {
+  return static_cast<uint32_t>(
+      std::min<uint64_t>(x_lines, std::max(kFftGroupElements / nx, 1)));
+}
+// The strided passes along y (pass[0]) and z (pass[1]) of a grid of dims = (nx, ny, nz).
+inline void fft_column_passes(const int32_t dims[3], FftPassDev pass_out[2]) {
+  const uint64_t row = static_cast<uint64_t>(dims[0]);
+  const uint64_t plane = row * static_cast<uint64_t>(dims[1]);
+  for (int axis = 1; axis <= 2; ++axis) {
+    FftPassDev& pass = pass_out[axis - 1];
+    pass.n = dims[axis];
+    pass.log2n = fft_log2(dims[axis]);
+    pass.planes = axis == 1 ? static_cast<uint32_t>(dims[2]) : 1u;
+    pass.columns = static_cast<uint32_t>(axis == 1 ? row : plane);
+    pass.plane_stride = plane;
+    pass.line_stride = axis == 1 ? row : plane;
+    const FftColumnGroups cut = fft_column_groups(pass.columns, pass.n);
+    pass.group = cut.group;
+    pass.groups = cut.groups;
+    pass.last = cut.last;
+  }
+}
 struct Fft3dPlan {
   std::vector<double> twiddle[3];  // x, y, z; empty for an axis of length 1
   FftArgs args{};
@@ -2004,23 +2029,119 @@ inline Fft3dPlan plan_fft3d(const int32_t dims[3], const void* values, const voi
   args.nx = dims[0];
   args.log2nx = fft_log2(dims[0]);
   args.x_lines = static_cast<uint32_t>(cells / static_cast<uint64_t>(dims[0]));
-  args.x_group = static_cast<uint32_t>(
-      std::min<uint64_t>(args.x_lines, std::max(kFftGroupElements / dims[0], 1)));
-  const uint64_t row = static_cast<uint64_t>(dims[0]);
-  const uint64_t plane = row * static_cast<uint64_t>(dims[1]);
-  for (int axis = 1; axis <= 2; ++axis) {
-    FftPassDev& pass = args.pass[axis - 1];
-    pass.n = dims[axis];
-    pass.log2n = fft_log2(dims[axis]);
-    pass.planes = axis == 1 ? static_cast<uint32_t>(dims[2]) : 1u;
-    pass.columns = static_cast<uint32_t>(axis == 1 ? row : plane);
-    pass.plane_stride = plane;
-    pass.line_stride = axis == 1 ? row : plane;
-    const FftColumnGroups cut = fft_column_groups(pass.columns, pass.n);
-    pass.group = cut.group;
-    pass.groups = cut.groups;
-    pass.last = cut.last;
+  args.x_group = fft_x_group(args.x_lines, dims[0]);
+  fft_column_passes(dims, args.pass);
+  return plan;
+}
+
+// ---- inverse transform, Helmholtz split, potential ----------------------------------------
+// ("Inverse transform, Helmholtz split, potential")
+// The inverse table of a line of n values: V[m] = (W[m].re, -W[m].im) of the forward table, the
+// negation exact.
+inline std::vector<double> fft_inverse_twiddles(int n) {
+  std::vector<double> table = fft_twiddles(n);
+  for (size_t m = 0; m < table.size() / 2; ++m) table[2 * m + 1] = -table[2 * m + 1];
+  return table;
+}
+// No byte shared between any two of the arrays: sorted by first byte, a range overlaps an earlier
+// one iff it begins at or before the largest last byte so far.
+inline void require_disjoint(ByteRanges* ranges, const char* message) {
+  std::sort(ranges->begin(), ranges->end());
+  uintptr_t reach = 0;
+  for (size_t r = 1; r < ranges->size(); ++r) {
+    reach = std::max(reach, (*ranges)[r - 1].second);
+    require_box(reach < (*ranges)[r].first, message);
   }
+}
+struct Ifft3dPlan {
+  std::vector<double> twiddle[3];  // V for x, y, z; empty for an axis of length 1
+  IfftArgs args{};
+  template <class Visit>
+  void visit_tables(IfftArgs* to, Visit&& visit) const {
+    for (int d = 0; d < 3; ++d) visit(&to->twiddle[d], twiddle[d].data(), twiddle[d].size());
+  }
+};
+// The inverse of `spectrum` [nz][ny][nx][2] into the real grids `values` and, unless null, `imag`
+// [nz][ny][nx], device arrays of which the entry point has checked the first two for null.  The
+// rules, in this order: the dims, fewer than 2^31 cells, no byte shared among the arrays.
+inline Ifft3dPlan plan_ifft3d(const int32_t dims[3], const void* spectrum, const void* values,
+                              const void* imag) {
+  const uint64_t cells = require_fft_dims(dims);
+  ByteRanges arrays;
+  append_byte_range(&arrays, spectrum, cells * 2 * sizeof(double));
+  append_byte_range(&arrays, values, cells * sizeof(double));
+  if (imag != nullptr) append_byte_range(&arrays, imag, cells * sizeof(double));
+  require_disjoint(&arrays, "the spectrum, values and imag overlap");
+  Ifft3dPlan plan;
+  for (int d = 0; d < 3; ++d) plan.twiddle[d] = fft_inverse_twiddles(dims[d]);
+  IfftArgs& args = plan.args;
+  args.nx = dims[0];
+  args.log2nx = fft_log2(dims[0]);
+  args.x_lines = static_cast<uint32_t>(cells / static_cast<uint64_t>(dims[0]));
+  args.x_group = fft_x_group(args.x_lines, dims[0]);
+  args.scale = 1.0 / static_cast<double>(cells);  // cells is a power of two: exact
+  fft_column_passes(dims, args.pass);
+  return plan;
+}
+
+struct SpectrumHelmholtzPlan {
+  HelmholtzArgs args{};  // no table: nothing is staged
+};
+// The Helmholtz split of the spectra of (vx, vy, vz), each [nz][ny][nx][2]: `spectra` are read and
+// overwritten with the solenoidal part, `compressive` written.  h[d] = 1 / L_d.  The rules, in
+// this order: no null array, the dims, fewer than 2^31 cells, per axis h finite and positive, h^2
+// not below DBL_MIN (kappa^2 of every mode but 0 is a normal number) and (512 h)^2 finite (the
+// largest |m| is 511: q cannot overflow), no byte shared between any two of the six arrays.
+inline SpectrumHelmholtzPlan plan_spectrum_helmholtz(const int32_t dims[3], const double h[3],
+                                                     const double* const spectra[3],
+                                                     const double* const compressive[3]) {
+  for (int d = 0; d < 3; ++d) {
+    require_box(spectra[d] != nullptr && compressive[d] != nullptr, "null argument");
+  }
+  const uint64_t cells = require_fft_dims(dims);
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(h[d]) && h[d] > 0.0, "inverse_length must be finite and positive");
+    require_box(h[d] * h[d] >= DBL_MIN, "inverse_length is too small: its square underflows");
+    const double widest = 512.0 * h[d];
+    require_box(std::isfinite(widest * widest),
+                "inverse_length is too large: a squared wave number overflows");
+  }
+  ByteRanges arrays;
+  for (int d = 0; d < 3; ++d) {
+    append_byte_range(&arrays, spectra[d], cells * 2 * sizeof(double));
+    append_byte_range(&arrays, compressive[d], cells * 2 * sizeof(double));
+  }
+  require_disjoint(&arrays, "two of the six spectra overlap");
+  SpectrumHelmholtzPlan plan;
+  for (int d = 0; d < 3; ++d) {
+    plan.args.log2n[d] = fft_log2(dims[d]);
+    plan.args.h[d] = h[d];
+  }
+  plan.args.n_modes = static_cast<uint32_t>(cells);
+  return plan;
+}
+
+struct InverseLaplacianPlan {
+  InverseLaplacianArgs args{};  // no table: nothing is staged
+};
+// `spectrum` [nz][ny][nx][2] times scale / q in place, q the shell sums' (g[d] = 1 / L_d^2), 0 at
+// q == 0.  The rules, in this order: the dims, fewer than 2^31 cells, g finite and positive, scale
+// finite.
+inline InverseLaplacianPlan plan_spectrum_inverse_laplacian(const int32_t dims[3],
+                                                            const double g[3], double scale) {
+  const uint64_t cells = require_fft_dims(dims);
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(g[d]) && g[d] > 0.0,
+                "inverse_length_sq must be finite and positive");
+  }
+  require_box(std::isfinite(scale), "scale must be finite");
+  InverseLaplacianPlan plan;
+  for (int d = 0; d < 3; ++d) {
+    plan.args.log2n[d] = fft_log2(dims[d]);
+    plan.args.g[d] = g[d];
+  }
+  plan.args.n_modes = static_cast<uint32_t>(cells);
+  plan.args.scale = scale;
   return plan;
 }
 

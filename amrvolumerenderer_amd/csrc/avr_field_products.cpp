@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, rays, per-ray sums and power spectra.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, rays, per-ray sums, power spectra, inverse transforms and the per-mode operators.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -540,6 +540,52 @@ int avr_spectrum_bins(avr_context* ctx, const double* spectrum_dev, const int32_
     args.power = power_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_spectrum_bins(args, ctx->stream);
+  });
+}
+
+int avr_field_ifft(avr_context* ctx, double* spectrum_dev, const int32_t* dims, double* values_dev,
+                   double* imag_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(spectrum_dev != nullptr && dims != nullptr && values_dev != nullptr, "null argument");
+    const avr::Ifft3dPlan plan = avr::plan_ifft3d(dims, spectrum_dev, values_dev, imag_dev);
+    avr::IfftArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.spectrum = spectrum_dev;
+    args.values = values_dev;
+    args.imag = imag_dev;
+    return avr::launch_ifft3d(args, ctx->stream);
+  });
+}
+
+int avr_spectrum_helmholtz(avr_context* ctx, double* const spectra_dev[3], const int32_t* dims,
+                           const double inverse_length[3], double* const compressive_dev[3]) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(spectra_dev != nullptr && dims != nullptr && inverse_length != nullptr &&
+                compressive_dev != nullptr, "null argument");
+    const avr::SpectrumHelmholtzPlan plan =
+        avr::plan_spectrum_helmholtz(dims, inverse_length, spectra_dev, compressive_dev);
+    avr::HelmholtzArgs args = plan.args;
+    for (int d = 0; d < 3; ++d) {
+      args.spectra[d] = spectra_dev[d];
+      args.compressive[d] = compressive_dev[d];
+    }
+    return avr::launch_spectrum_helmholtz(args, ctx->stream);
+  });
+}
+
+int avr_spectrum_inverse_laplacian(avr_context* ctx, double* spectrum_dev, const int32_t* dims,
+                                   const double* inverse_length_sq, double scale) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(spectrum_dev != nullptr && dims != nullptr && inverse_length_sq != nullptr,
+            "null argument");
+    const avr::InverseLaplacianPlan plan =
+        avr::plan_spectrum_inverse_laplacian(dims, inverse_length_sq, scale);
+    avr::InverseLaplacianArgs args = plan.args;
+    args.spectrum = spectrum_dev;
+    return avr::launch_spectrum_inverse_laplacian(args, ctx->stream);
   });
 }
 

@@ -1005,6 +1005,39 @@ struct SpectrumBinsArgs {
 };
 int launch_spectrum_bins(const SpectrumBinsArgs& args, void* stream);
 
+// Inverse transform, Helmholtz split, potential (avr_fft.hip, avr_spectral.hip; DESIGN.md 7,
+// "Inverse transform, Helmholtz split, potential"): the normalised inverse of a complex spectrum
+// into real grids -- the strided passes along z, then y, in place (fft_column_kernel with the
+// conjugate tables), then the x pass, which scales and splits -- and two per-mode operators.
+struct IfftArgs {
+  double* spectrum;          // [nz][ny][nx][2]; the strided passes overwrite it
+  double* values;            // [nz][ny][nx]: re / (nx ny nz)
+  double* imag;              // [nz][ny][nx]: im / (nx ny nz); or null
+  const double* twiddle[3];  // per axis (x, y, z): V[m] = (W[m].re, -W[m].im), n / 2 pairs
+  int32_t nx, log2nx;
+  uint32_t x_lines;          // ny * nz
+  uint32_t x_group;          // lines a workgroup of the x pass stages, as the forward x pass
+  double scale;              // 1.0 / f64(nx ny nz), a power of two
+  FftPassDev pass[2];        // y, z; launched z first
+};
+int launch_ifft3d(const IfftArgs& args, void* stream);
+struct HelmholtzArgs {
+  double* spectra[3];        // (vx, vy, vz) [nz][ny][nx][2]: read, then the solenoidal part
+  double* compressive[3];    // written
+  int32_t log2n[3];          // x, y, z
+  uint32_t n_modes;          // nx * ny * nz < 2^31
+  double h[3];               // 1 / L_d
+};
+int launch_spectrum_helmholtz(const HelmholtzArgs& args, void* stream);
+struct InverseLaplacianArgs {
+  double* spectrum;          // [nz][ny][nx][2], in place
+  int32_t log2n[3];
+  uint32_t n_modes;
+  double g[3];               // 1 / L_d^2
+  double scale;
+};
+int launch_spectrum_inverse_laplacian(const InverseLaplacianArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

@@ -292,6 +292,66 @@ class Context:
                 _pointer(totals))
         return modes, power, totals
 
+    # -- inverse transform, Helmholtz split, potential -----------------------------------------
+    def _spectrum_dims(self, spectrum: torch.Tensor, what: str = "spectrum") -> np.ndarray:
+        self._check_tensor(spectrum, torch.float64, what)
+        if spectrum.ndim != 4 or spectrum.shape[3] != 2 or spectrum.numel() == 0:
+            raise ValueError(f"{what} must be [nz, ny, nx, 2] with at least one mode")
+        nz, ny, nx = (int(v) for v in spectrum.shape[:3])
+        return np.array([nx, ny, nz], dtype=np.int32)
+
+    def ifft3d(self, spectrum: torch.Tensor, with_imag: bool = False):
+        """avr_field_ifft: the normalised inverse 3-D transform of a spectrum (float64
+        [nz, ny, nx, 2] on the device, as fft3d returns it; DESIGN.md 7, "Inverse transform,
+        Helmholtz split, potential").  The strided passes run in place: what `spectrum` holds
+        afterwards is unspecified.  Returns the real part, float64 [nz, ny, nx] on the device --
+        with with_imag (real, imag), the imaginary part a grid of the same shape.  Asynchronous on
+        the context's stream."""
+        dims = self._spectrum_dims(spectrum)
+        shape = tuple(int(v) for v in spectrum.shape[:3])
+        values = torch.empty(shape, dtype=torch.float64, device=self.device)
+        imag = torch.empty(shape, dtype=torch.float64, device=self.device) if with_imag else None
+        _native(self, "avr_field_ifft", self._handle, _pointer(spectrum), _ints(dims),
+                _pointer(values), _pointer(imag))
+        return (values, imag) if with_imag else values
+
+    def helmholtz_split(self, fx: torch.Tensor, fy: torch.Tensor, fz: torch.Tensor,
+                        inverse_length):
+        """avr_spectrum_helmholtz: splits the spectra of (vx, vy, vz) (float64 [nz, ny, nx, 2] on
+        the device, of one shape) into their solenoidal and compressive parts (DESIGN.md 7,
+        "Inverse transform, Helmholtz split, potential").  inverse_length: 1 / L_d for d = x, y,
+        z.  Returns (solenoidal, compressive), three spectra each: the solenoidal ones are fx, fy
+        and fz themselves, overwritten; the compressive ones are new.  Asynchronous on the
+        context's stream."""
+        dims = self._spectrum_dims(fx, "fx")
+        for other, what in ((fy, "fy"), (fz, "fz")):
+            if not np.array_equal(self._spectrum_dims(other, what), dims):
+                raise ValueError("fx, fy and fz must have one shape")
+        h = np.ascontiguousarray(inverse_length, dtype=np.float64)
+        if h.shape != (3,):
+            raise ValueError("inverse_length must hold three values")
+        compressive = tuple(torch.empty_like(fx) for _ in range(3))
+        inputs = (C.c_void_p * 3)(*(f.data_ptr() for f in (fx, fy, fz)))
+        outputs = (C.c_void_p * 3)(*(c.data_ptr() for c in compressive))
+        _native(self, "avr_spectrum_helmholtz", self._handle, inputs, _ints(dims), _doubles(h),
+                outputs)
+        return (fx, fy, fz), compressive
+
+    def inverse_laplacian(self, spectrum: torch.Tensor, inverse_length_sq,
+                          scale: float) -> torch.Tensor:
+        """avr_spectrum_inverse_laplacian: every mode of a spectrum (float64 [nz, ny, nx, 2] on the
+        device) times scale / q in place, q = sum_d m_d^2 / L_d^2 as the shell sums have it, and
+        (0, 0) where q == 0 ("Inverse transform, Helmholtz split, potential").
+        inverse_length_sq: 1 / L_d^2 for d = x, y, z.  Returns `spectrum`.  Asynchronous on the
+        context's stream."""
+        dims = self._spectrum_dims(spectrum)
+        g = np.ascontiguousarray(inverse_length_sq, dtype=np.float64)
+        if g.shape != (3,):
+            raise ValueError("inverse_length_sq must hold three values")
+        _native(self, "avr_spectrum_inverse_laplacian", self._handle, _pointer(spectrum),
+                _ints(dims), _doubles(g), float(scale))
+        return spectrum
+
     # -- clump binding ------------------------------------------------------------------------
     def clump_pair_energy(self, offsets, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
                           m: torch.Tensor, w: Optional[torch.Tensor] = None):

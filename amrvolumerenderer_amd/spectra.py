@@ -1,7 +1,9 @@
 """Power spectra ("Power spectrum"): what api.power_spectrum works out on the host
 around the kernels of csrc/avr_fft.hip -- the wave numbers of a grid, the default, linear and
 logarithmic edges, their squares as the bin kernel compares them, the normalisation of the shell
-sums, an .npz file.  numpy only; no device work."""
+sums, an .npz file -- and, for api.helmholtz and api.potential ("Inverse transform,
+Helmholtz split, potential"), the inverse lengths, the compressive fraction and their .npz files.
+numpy only; no device work."""
 from __future__ import annotations
 
 import math
@@ -50,6 +52,11 @@ def inverse_length_sq(dims, cell_size) -> np.ndarray:
     """g[d] = 1.0 / (L_d * L_d), float64 [3]: what the bin kernel multiplies m_d^2 by."""
     return np.array([1.0 / (length * length) for length in lengths(dims, cell_size)],
                     dtype=np.float64)
+
+
+def inverse_length(dims, cell_size) -> np.ndarray:
+    """h[d] = 1.0 / L_d, float64 [3]: what the Helmholtz kernel multiplies m_d by."""
+    return np.array([1.0 / length for length in lengths(dims, cell_size)], dtype=np.float64)
 
 
 def wave_numbers(dims, cell_size):
@@ -163,3 +170,79 @@ def load_npz(filename: str) -> Dict:
         if key in result:
             result[key] = tuple(result[key].tolist())
     return result
+
+
+# ---- Helmholtz split and potential ("Inverse transform, Helmholtz split, potential") --
+
+PARTS = ("solenoidal", "compressive", "total")
+_NESTED = ("power", "spectrum", "modes", "solenoidal", "compressive")   # dicts of arrays
+_INTS = ("level", "outside", "nonfinite", "absent")
+_FLOATS = ("compressive_fraction", "imag_max", "constant")
+_TUPLES = ("lo", "dims", "cell_size")
+
+
+def compressive_fraction(power_solenoidal, power_compressive, edges) -> float:
+    """sum(P_c) / (sum(P_c) + sum(P_s)) over the bins above k = 0, those with a lower edge > 0:
+    the mean flow, which counts as solenoidal, stays out of the ratio.  NaN without power there."""
+    e = check_edges(edges)
+    above = e[:-1] > 0.0
+    c = float(np.sum(np.asarray(power_compressive, dtype=np.float64)[above]))
+    s = float(np.sum(np.asarray(power_solenoidal, dtype=np.float64)[above]))
+    return c / (c + s) if c + s != 0.0 else math.nan
+
+
+def _save_nested(result: Dict, filename: str) -> None:
+    entries = {}
+    for key, value in result.items():
+        if key in _NESTED:
+            for name, array in value.items():
+                entries[f"{key}/{name}"] = np.asarray(array)
+        else:
+            entries[key] = np.asarray(value)
+    with open(filename, "wb") as out:      # a file object: savez adds no ".npz" of its own
+        np.savez(out, **entries)
+
+
+def _load_nested(filename: str) -> Dict:
+    result: Dict = {}
+    with np.load(filename) as data:
+        for key in data.files:
+            head, _, name = key.partition("/")
+            if head in _NESTED and name:
+                result.setdefault(head, {})[name] = data[key]
+            else:
+                result[key] = data[key]
+    for key in _INTS:
+        if key in result:
+            result[key] = int(result[key])
+    for key in _FLOATS:
+        if key in result:
+            result[key] = float(result[key])
+    for key in _TUPLES:
+        if key in result:
+            result[key] = tuple(result[key].tolist())
+    return result
+
+
+def save_helmholtz_npz(result: Dict, filename: str) -> None:
+    """Writes api.helmholtz's dict as one .npz: every entry under its key, the entries of power,
+    spectrum and modes under key + "/" + the part, the grids under "solenoidal/" and
+    "compressive/" + the field's name."""
+    _save_nested(result, filename)
+
+
+def load_helmholtz_npz(filename: str) -> Dict:
+    """Reads a file save_helmholtz_npz wrote back into a dict of the same shape: arrays stay
+    arrays, level and the counts become ints, compressive_fraction and imag_max floats, lo, dims
+    and cell_size tuples."""
+    return _load_nested(filename)
+
+
+def save_potential_npz(result: Dict, filename: str) -> None:
+    """Writes api.potential's dict as one .npz, every entry under its key."""
+    _save_nested(result, filename)
+
+
+def load_potential_npz(filename: str) -> Dict:
+    """Reads a file save_potential_npz wrote back into a dict of the same shape."""
+    return _load_nested(filename)

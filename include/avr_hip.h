@@ -1554,6 +1554,51 @@ int avr_spectrum_bins(avr_context *ctx, const double *spectrum_dev, const int32_
                       const double *inverse_length_sq, const double *edges_sq, int n_bins,
                       uint64_t *modes_dev, double *power_dev, uint64_t *totals_dev);
 
+/* ---- inverse transform, Helmholtz split, potential --------------------------------- */
+
+/* The normalised inverse 3-D transform x[n] = (1 / N) sum_k F[k] exp(+2 pi i k n / N) of
+ * spectrum_dev (device, f64 [dims[2]][dims[1]][dims[0]][2], as avr_field_fft writes it) into the
+ * real grids values_dev (the real part) and, unless NULL, imag_dev (the imaginary part), both
+ * device f64 [dims[2]][dims[1]][dims[0]].  One line is transformed as avr_field_fft states it --
+ * bit reversal, the stages, the same butterfly, nothing fused -- with the table V[m] = (W[m].re,
+ * -W[m].im) in place of W; every line is transformed along z, then y, then x, and after the x pass
+ * both components are multiplied by s = 1.0 / f64(nx ny nz), an exact power of two.  The strided
+ * passes run in place: what spectrum_dev holds after the call is unspecified.  Equal arguments give
+ * equal bits.  Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for a NULL argument other than imag_dev, a dims that is not a power of
+ * two in [1, 1024], 2^31 cells or more, and any byte shared among the three arrays -- and every
+ * array is untouched.  Stateless; asynchronous on the context's stream. */
+int avr_field_ifft(avr_context *ctx, double *spectrum_dev, const int32_t *dims, double *values_dev,
+                   double *imag_dev);
+
+/* The Helmholtz split of the spectra of (vx, vy, vz) -- spectra_dev (host array of three device
+ * spectra as avr_field_fft writes them), read and then overwritten with the solenoidal part S --
+ * and its compressive part C into compressive_dev (three more device spectra).  Per mode, m_d is
+ * avr_spectrum_bins' signed wave number with the Nyquist rule added (N_d >= 2 and k_d == N_d / 2:
+ * m_d = 0, which keeps the projector Hermitian), kappa_d = f64(m_d) h[d] with h = inverse_length
+ * (host, 3 doubles: 1 / L_d), q = kx kx + ky ky, then + kz kz.  q == 0: every C_d = (+0.0, +0.0)
+ * and S_d = F_d with its bits kept.  Else, for the real and the imaginary component separately:
+ * d = kx Fx + ky Fy, then + kz Fz; s = d / q (one correctly rounded division); C_d = kappa_d s;
+ * S_d = F_d - C_d; nothing fused.  Values that are not finite propagate by IEEE rules.  Equal
+ * arguments give equal bits.  Everything is checked on the host before any device work, in this
+ * order: AVR_ERR_INVALID_ARGUMENT for a NULL argument or array, a dims that is not a power of two
+ * in [1, 1024], 2^31 cells or more, per axis an h that is not finite and positive, an h whose
+ * square is below DBL_MIN, an h with (512 h)^2 not finite, and a byte shared between any two of
+ * the six arrays -- and every array is untouched.  Stateless; asynchronous on the context's
+ * stream. */
+int avr_spectrum_helmholtz(avr_context *ctx, double *const spectra_dev[3], const int32_t *dims,
+                           const double inverse_length[3], double *const compressive_dev[3]);
+
+/* The inverse Laplacian of a spectrum in place: with avr_spectrum_bins' q (no Nyquist rule; g =
+ * inverse_length_sq, host, 3 doubles), a mode with q == 0 becomes (+0.0, +0.0), every other one
+ * (re r, im r) with r = scale / q.  Equal arguments give equal bits.  Everything is checked on the
+ * host before any device work, in this order: AVR_ERR_INVALID_ARGUMENT for a NULL argument, a dims
+ * that is not a power of two in [1, 1024], 2^31 cells or more, a g that is not finite and
+ * positive, and a scale that is not finite -- and the spectrum is untouched.  Stateless;
+ * asynchronous on the context's stream. */
+int avr_spectrum_inverse_laplacian(avr_context *ctx, double *spectrum_dev, const int32_t *dims,
+                                   const double *inverse_length_sq, double scale);
+
 #ifdef __cplusplus
 }
 #endif
