@@ -1387,10 +1387,10 @@ def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeo
 
 
 def _plotfile_grid(plotfile: str, level, region, left_edge, right_edge, min_level: int,
-                   max_level: int):
-    """(header, level, lo, dims) of a plotfile-level function over a periodic power-of-two grid:
-    region, level and the power-of-two rule as api.power_spectrum has them, before anything is
-    loaded."""
+                   max_level: int, check_dims=None):
+    """(header, level, lo, dims) of a plotfile-level function over a grid of one level: region
+    and level as api.power_spectrum has them and the rule on dims -- check_dims, by default the
+    power-of-two rule of a periodic grid (spectra.check_dims) -- before anything is loaded."""
     from . import grids, spectra
     from . import plotfile as pf
     if region is not None and (left_edge is not None or right_edge is not None):
@@ -1418,7 +1418,7 @@ def _plotfile_grid(plotfile: str, level, region, left_edge, right_edge, min_leve
         domain_lo, domain_hi = header.prob_domain[0]
         lo = tuple(v * refine for v in domain_lo)
         dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
-    return header, level, lo, spectra.check_dims(dims)
+    return header, level, lo, (check_dims or spectra.check_dims)(dims)
 
 
 def helmholtz(plotfile: str, velocity: Sequence[str], level: Optional[int] = None, region=None,
@@ -1526,6 +1526,112 @@ def potential(plotfile: str, variable: str = "", constant: float = 1.0,
     result.update(found)
     if output:
         spectra.save_potential_npz(result, output)
+    return result
+
+
+# ---- isolated potential ("Isolated potential") ---------------------------------------
+
+def _isolated_constants(constant, self_term) -> Tuple[float, float]:
+    constant, self_term = float(constant), float(self_term)
+    if not math.isfinite(constant):
+        raise ValueError("constant must be finite")
+    if not (math.isfinite(self_term) and self_term >= 0.0):
+        raise ValueError("self_term must be finite and not negative")
+    return constant, self_term
+
+
+def isolated_potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes,
+                             prob_lo, ref_ratio, constant: float = 1.0, self_term: float = 0.0,
+                             fill: Optional[float] = None, rank: int = 0,
+                             n_ranks: int = 1) -> dict:
+    """The free-space solution of laplace(phi) = constant rho for a scene's raw field rho over the
+    cells [lo, lo + dims) of level `level`, nothing outside them ("Isolated
+    potential"): phi_i = sum_j G(x_i - x_j) rho_j with G = scale / r, scale = -(constant dx dy dz
+    / (4 pi)), and G(0) = scale * self_term, by Hockney and Eastwood's zero-padded convolution --
+    the covering grid, padded with zeros to spectra.padded_dims(dims), its transform, the
+    transform of the Green's grid, their product, the inverse transform and the region's corner
+    of it, all on the device.  dims: between 1 and 512 cells per axis, powers of two or not; fill
+    as power_spectrum_scene takes it, the other arguments as covering_grid_scene does.  Returns a
+    dict: potential float64 [nz, ny, nx] (numpy), imag_max (the largest |imaginary part| the
+    inverse left in the region), absent and padded_dims.  With n_ranks > 1, or fewer local boxes
+    than boxes, NotImplementedError is raised before any device work."""
+    import torch
+    from . import spectra
+    constant, self_term = _isolated_constants(constant, self_term)
+    level = int(level)
+    lo = tuple(int(v) for v in lo)
+    if len(lo) != 3:
+        raise ValueError("lo and dims must hold three values")
+    padded = spectra.padded_dims(dims)
+    nx, ny, nz = dims = tuple(int(v) for v in dims)
+    _require_one_rank(scene, n_ranks, "an isolated potential needs every box of the scene on one "
+                      "rank: cells are not gathered between ranks")
+    all_sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    if not 0 <= level < len(all_sizes):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    size = all_sizes[level]
+    volume = (size[0] * size[1]) * size[2]
+    scale = -((constant * volume) / (4.0 * math.pi))
+    self_value = scale * self_term
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    with _native_scenes(ctx, [scene]) as (field,):
+        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+        # every tensor is dropped as soon as the next step has read it: at 512^3 the padded grids
+        # would otherwise add up to some 70 GB
+        grid = torch.zeros(padded[::-1], dtype=torch.float64, device=ctx.device)
+        grid[:nz, :ny, :nx] = values
+        del values
+        spectrum = ctx.fft3d(grid)
+        del grid
+        green = ctx.isolated_green(padded, size, scale, self_value)
+        kernel = ctx.fft3d(green)
+        del green
+        ctx.spectrum_multiply(spectrum, kernel)
+        del kernel
+        real, imag = ctx.ifft3d(spectrum, with_imag=True)
+        del spectrum
+        worst = imag[:nz, :ny, :nx].abs().max()
+        del imag
+        potential = real[:nz, :ny, :nx].contiguous()
+        del real
+        ctx.synchronize()
+        return {"potential": potential.cpu().numpy(), "imag_max": float(worst.item()),
+                "absent": absent, "padded_dims": padded}
+
+
+def isolated_potential(plotfile: str, variable: str = "", constant: float = 1.0,
+                       level: Optional[int] = None, region=None, left_edge=None, right_edge=None,
+                       self_term: float = 0.0, min_level: int = 0, max_level: int = -1,
+                       fill: Optional[float] = None, output: Optional[str] = None) -> dict:
+    """The potential of a field of a plotfile with isolated (open) boundaries (DESIGN.md 7,
+    "Isolated potential"), on cuda:0: phi with laplace(phi) = constant rho for the covering grid
+    rho of `variable` (by default the first variable) at `level` over a region, with nothing
+    outside the region and phi -> 0 far from it -- constant = 4 pi G gives the gravitational
+    potential of a density.  phi_i = sum_j G_ij rho_j with G_ij = -(constant dx dy dz / (4 pi)) /
+    |x_i - x_j| between cell centres; self_term (1 / length, >= 0, by default 0) stands for
+    1 / |x_i - x_i|, a cell's share in its own potential: with 0 every cell is a point mass that
+    does not act on itself, and 0.5 sum_i m_i phi_i is clump binding's pairwise sum.  The region
+    holds between 1 and 512 cells along every axis, powers of two or not; level, region,
+    left_edge / right_edge, min_level, max_level and fill as api.potential takes them.  Returns a
+    dict: level, lo, dims (nx, ny, nz), padded_dims, cell_size, constant, self_term, potential
+    float64 [nz, ny, nx], imag_max and absent.  With output the dict is written as one .npz file
+    (spectra.save_isolated_potential_npz)."""
+    from . import spectra
+    constant, self_term = _isolated_constants(constant, self_term)
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level, spectra.check_isolated_dims)
+    name = str(variable) or header.var_names[0]
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, [name], min_level, max_level)
+    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
+    found = isolated_potential_scene(ctx, scenes[0], level, lo, dims,
+                                     *_header_levels(header, n_levels), constant, self_term,
+                                     fill, rank, world)
+    result = {"level": level, "lo": lo, "dims": dims, "padded_dims": found["padded_dims"],
+              "cell_size": tuple(float(v) for v in header.cell_size[level]),
+              "constant": constant, "self_term": self_term}
+    result.update(found)
+    if output:
+        spectra.save_isolated_potential_npz(result, output)
     return result
 
 

@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
-// streamlines, covering grids, rays, per-ray sums, power spectra):
+// streamlines, covering grids, rays, per-ray sums, power spectra, isolated potentials):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -1956,6 +1956,11 @@ inline int fft_log2(int n) {
   while ((1 << p) < n) ++p;
   return p;
 }
+// Fewer than 2^31 cells: dims that are in order hold at most 2^30, so the rule guards the kernels'
+// 32-bit cell index against a change of kFftMaxLength.
+inline void require_cell_count(uint64_t cells) {
+  require_box(cells < (uint64_t{1} << 31), "the grid has 2^31 cells or more");
+}
 // dims = (nx, ny, nz): every one a power of two in [1, 1024], fewer than 2^31 cells in all.
 // Returns the cells.
 inline uint64_t require_fft_dims(const int32_t dims[3]) {
@@ -1964,7 +1969,7 @@ inline uint64_t require_fft_dims(const int32_t dims[3]) {
   }
   const uint64_t cells = static_cast<uint64_t>(dims[0]) * static_cast<uint64_t>(dims[1]) *
                          static_cast<uint64_t>(dims[2]);  // at most 2^30
-  require_box(cells < (uint64_t{1} << 31), "the grid has 2^31 cells or more");
+  require_cell_count(cells);
   return cells;
 }
 // How a strided pass over lines of length n cuts a plane of `columns` adjacent lines into
@@ -2142,6 +2147,68 @@ inline InverseLaplacianPlan plan_spectrum_inverse_laplacian(const int32_t dims[3
   }
   plan.args.n_modes = static_cast<uint32_t>(cells);
   plan.args.scale = scale;
+  return plan;
+}
+
+// ---- isolated potential ("Isolated potential") -------------------------------
+// The workgroups of a streaming kernel that takes kSpectralGroupElements elements each.
+inline uint32_t spectral_groups(uint64_t elements) {
+  return static_cast<uint32_t>((elements + kSpectralGroupElements - 1) / kSpectralGroupElements);
+}
+struct IsolatedGreenPlan {
+  IsolatedGreenArgs args{};  // no table: nothing is staged
+  uint32_t groups = 0;       // workgroups of 256 lanes, kSpectralGroupElements cells each
+};
+// The Green's grid G = scale / r of the padded grid padded_dims = (Px, Py, Pz) with cells of
+// cell_size = (dx, dy, dz), r measured to the nearer image of the origin, and self_value at r == 0.
+// The rules, in this order: no null array, the dims powers of two in [1, 1024], fewer than 2^31
+// cells, per axis a size finite and positive, size^2 not below DBL_MIN (r2 of every cell but the
+// origin is a normal number) and (512 size)^2 finite (the largest offset is 512 cells: r2 cannot
+// overflow), scale and self_value finite.
+inline IsolatedGreenPlan plan_isolated_green(const int32_t* padded_dims, const double* cell_size,
+                                             double scale, double self_value, const void* green) {
+  require_box(padded_dims != nullptr && cell_size != nullptr && green != nullptr, "null argument");
+  const uint64_t cells = require_fft_dims(padded_dims);
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(cell_size[d]) && cell_size[d] > 0.0,
+                "cell_size must be finite and positive");
+    require_box(cell_size[d] * cell_size[d] >= DBL_MIN,
+                "cell_size is too small: its square underflows");
+    const double widest = 512.0 * cell_size[d];
+    require_box(std::isfinite(widest * widest),
+                "cell_size is too large: a squared distance overflows");
+  }
+  require_box(std::isfinite(scale) && std::isfinite(self_value),
+              "scale and self_value must be finite");
+  IsolatedGreenPlan plan;
+  for (int d = 0; d < 3; ++d) {
+    plan.args.log2n[d] = fft_log2(padded_dims[d]);
+    plan.args.size[d] = cell_size[d];
+  }
+  plan.args.n_cells = static_cast<uint32_t>(cells);
+  plan.args.scale = scale;
+  plan.args.self_value = self_value;
+  plan.groups = spectral_groups(cells);
+  return plan;
+}
+
+struct SpectrumMultiplyPlan {
+  SpectrumMultiplyArgs args{};  // no table: nothing is staged
+  uint32_t groups = 0;          // workgroups of 256 lanes, kSpectralGroupElements modes each
+};
+// a <- a b mode by mode, both spectra [nz][ny][nx][2].  The rules, in this order: no null array,
+// the dims powers of two in [1, 1024], fewer than 2^31 cells, no byte shared between a and b.
+inline SpectrumMultiplyPlan plan_spectrum_multiply(const int32_t* dims, const void* a,
+                                                   const void* b) {
+  require_box(dims != nullptr && a != nullptr && b != nullptr, "null argument");
+  const uint64_t cells = require_fft_dims(dims);
+  ByteRanges arrays;
+  append_byte_range(&arrays, a, cells * 2 * sizeof(double));
+  append_byte_range(&arrays, b, cells * 2 * sizeof(double));
+  require_disjoint(&arrays, "the two spectra overlap");
+  SpectrumMultiplyPlan plan;
+  plan.args.n_modes = static_cast<uint32_t>(cells);
+  plan.groups = spectral_groups(cells);
   return plan;
 }
 

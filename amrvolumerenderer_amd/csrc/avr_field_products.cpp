@@ -589,4 +589,31 @@ int avr_spectrum_inverse_laplacian(avr_context* ctx, double* spectrum_dev, const
   });
 }
 
+int avr_isolated_green(avr_context* ctx, const int32_t* padded_dims, const double* cell_size,
+                       double scale, double self_value, double* green_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(padded_dims != nullptr && cell_size != nullptr && green_dev != nullptr,
+            "null argument");
+    const avr::IsolatedGreenPlan plan =
+        avr::plan_isolated_green(padded_dims, cell_size, scale, self_value, green_dev);
+    avr::IsolatedGreenArgs args = plan.args;
+    args.green = green_dev;
+    return avr::launch_isolated_green(args, plan.groups, ctx->stream);
+  });
+}
+
+int avr_spectrum_multiply(avr_context* ctx, double* a_dev, const double* b_dev,
+                          const int32_t* dims) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(a_dev != nullptr && b_dev != nullptr && dims != nullptr, "null argument");
+    const avr::SpectrumMultiplyPlan plan = avr::plan_spectrum_multiply(dims, a_dev, b_dev);
+    avr::SpectrumMultiplyArgs args = plan.args;
+    args.a = a_dev;
+    args.b = b_dev;
+    return avr::launch_spectrum_multiply(args, plan.groups, ctx->stream);
+  });
+}
+
 }  // extern "C"

@@ -1038,6 +1038,26 @@ struct InverseLaplacianArgs {
 };
 int launch_spectrum_inverse_laplacian(const InverseLaplacianArgs& args, void* stream);
 
+// Isolated potential (avr_spectral.hip; DESIGN.md 7, "Isolated potential"): the open-boundary
+// Green's function on a zero-padded grid and the product of two spectra, both streaming.
+constexpr uint32_t kSpectralGroupElements = 16384;  // cells or modes a workgroup of 256 lanes takes
+struct IsolatedGreenArgs {
+  double* green;             // [Pz][Py][Px], written
+  int32_t log2n[3];          // x, y, z of the padded grid
+  uint32_t n_cells;          // Px * Py * Pz < 2^31
+  double size[3];            // the cell's (dx, dy, dz)
+  double scale;              // G = scale / sqrt(r2) ...
+  double self_value;         // ... but this at r2 == 0
+};
+int launch_isolated_green(const IsolatedGreenArgs& args, uint32_t groups, void* stream);
+struct SpectrumMultiplyArgs {
+  double* a;                 // [nz][ny][nx][2]: read, then a b
+  const double* b;           // [nz][ny][nx][2]
+  uint32_t n_modes;          // nx * ny * nz < 2^31
+  uint32_t pad_;
+};
+int launch_spectrum_multiply(const SpectrumMultiplyArgs& args, uint32_t groups, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

@@ -1,10 +1,14 @@
-// Per-mode operators on spectra ("Inverse transform, Helmholtz split, potential"):
+// Per-mode operators on spectra ("Inverse transform, Helmholtz split, potential" and
+// "Isolated potential"):
 //
 //   spectrum_helmholtz_kernel          three spectra -> their solenoidal (in place) and compressive
 //                                      parts
 //   spectrum_inverse_laplacian_kernel  one spectrum scaled by scale / q in place, 0 at q == 0
+//   spectrum_multiply_kernel           a <- a b, the complex product mode by mode
+//   isolated_green_kernel              the open-boundary Green's grid scale / r of a padded grid: the
+//                                      same cut over cells, 8-byte stores, nothing loaded
 //
-// Both stream: a workgroup takes kModesPerGroup consecutive modes, a lane one mode per trip, read
+// All stream: a workgroup takes kModesPerGroup consecutive modes, a lane one mode per trip, read
 // and written as 16-byte (re, im) values by the same lane, so a wave's accesses are contiguous
 // runs of 1 KiB and equal arguments give equal bits.  The mode's index is decoded by shifts (every
 // dimension is a power of two).  Every product, sum and quotient is rounded on its own
@@ -21,6 +25,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr uint32_t kModesPerGroup = 16384;  // 64 per lane
+static_assert(kModesPerGroup == kSpectralGroupElements, "the plans count groups of this size");
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
@@ -105,6 +110,48 @@ __global__ __launch_bounds__(kThreads) void spectrum_inverse_laplacian_kernel(
   }
 }
 
+__global__ __launch_bounds__(kThreads) void spectrum_multiply_kernel(
+    const SpectrumMultiplyArgs a) {
+  double2_t* left = reinterpret_cast<double2_t*>(a.a);
+  const double2_t* right = reinterpret_cast<const double2_t*>(a.b);
+  const uint32_t first = blockIdx.x * kModesPerGroup;
+  const uint32_t rest = a.n_modes - first;
+  const uint32_t count = rest < kModesPerGroup ? rest : kModesPerGroup;
+  for (uint32_t e = threadIdx.x; e < count; e += kThreads) {
+    const uint32_t mode = first + e;
+    const double2_t u = left[mode], v = right[mode];
+    double2_t out;
+    out.x = u.x * v.x - u.y * v.y;
+    out.y = u.x * v.y + u.y * v.x;
+    left[mode] = out;
+  }
+}
+
+// The offset of index i of an axis of 2^p cells from the nearer image of the origin, in cells.
+__device__ __forceinline__ uint32_t image_offset(uint32_t i, int p) {
+  const uint32_t back = (1u << p) - i;
+  return i < back ? i : back;
+}
+
+__global__ __launch_bounds__(kThreads) void isolated_green_kernel(const IsolatedGreenArgs a) {
+  const int px = a.log2n[0], py = a.log2n[1];
+  const uint32_t first = blockIdx.x * kModesPerGroup;
+  const uint32_t rest = a.n_cells - first;
+  const uint32_t count = rest < kModesPerGroup ? rest : kModesPerGroup;
+  for (uint32_t e = threadIdx.x; e < count; e += kThreads) {
+    const uint32_t cell = first + e;
+    const double x = static_cast<double>(image_offset(cell & ((1u << px) - 1u), px)) * a.size[0];
+    const double y =
+        static_cast<double>(image_offset((cell >> px) & ((1u << py) - 1u), py)) * a.size[1];
+    const double z = static_cast<double>(image_offset(cell >> (px + py), a.log2n[2])) * a.size[2];
+    double r2 = x * x + y * y;
+    r2 = r2 + z * z;
+    // the origin divides by zero like every other lane and then takes self_value: no branch
+    const double g = a.scale / __builtin_sqrt(r2);
+    a.green[cell] = r2 == 0.0 ? a.self_value : g;
+  }
+}
+
 int check(const char* what) {
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
@@ -129,6 +176,18 @@ int launch_spectrum_inverse_laplacian(const InverseLaplacianArgs& args, void* st
   hipLaunchKernelGGL(spectrum_inverse_laplacian_kernel, dim3(groups), dim3(kThreads), 0, stream,
                      args);
   return check("spectrum_inverse_laplacian_kernel");
+}
+
+int launch_spectrum_multiply(const SpectrumMultiplyArgs& args, uint32_t groups, void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  hipLaunchKernelGGL(spectrum_multiply_kernel, dim3(groups), dim3(kThreads), 0, stream, args);
+  return check("spectrum_multiply_kernel");
+}
+
+int launch_isolated_green(const IsolatedGreenArgs& args, uint32_t groups, void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  hipLaunchKernelGGL(isolated_green_kernel, dim3(groups), dim3(kThreads), 0, stream, args);
+  return check("isolated_green_kernel");
 }
 
 }  // namespace avr

@@ -352,6 +352,41 @@ class Context:
                 _ints(dims), _doubles(g), float(scale))
         return spectrum
 
+    # -- isolated potential -------------------------------------------------------------------
+    def isolated_green(self, padded_dims, cell_size, scale: float,
+                       self_value: float = 0.0) -> torch.Tensor:
+        """avr_isolated_green: the open-boundary Green's function scale / r on the zero-padded
+        grid of padded_dims = (Px, Py, Pz), powers of two in [1, 1024], with cells of cell_size =
+        (dx, dy, dz); r is measured to the nearer image of the origin along every axis, and the
+        cell (0, 0, 0) holds self_value ("Isolated potential").  Returns float64
+        [Pz, Py, Px] on the device.  Asynchronous on the context's stream."""
+        dims = np.ascontiguousarray(padded_dims, dtype=np.int64)
+        size = np.ascontiguousarray(cell_size, dtype=np.float64)
+        if dims.shape != (3,):
+            raise ValueError("padded_dims must hold three values")
+        if size.shape != (3,):
+            raise ValueError("cell_size must hold three values")
+        if not ((dims >= 1) & (dims <= 1024)).all():
+            raise ValueError("padded_dims must be powers of two in [1, 1024]")
+        px, py, pz = (int(v) for v in dims)
+        dims = dims.astype(np.int32)
+        green = torch.empty((pz, py, px), dtype=torch.float64, device=self.device)
+        _native(self, "avr_isolated_green", self._handle, _ints(dims),
+                _doubles(size), float(scale), float(self_value), _pointer(green))
+        return green
+
+    def spectrum_multiply(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """avr_spectrum_multiply: a <- a b, the complex product mode by mode of two spectra
+        (float64 [nz, ny, nx, 2] on the device, of one shape, sharing no memory; DESIGN.md 7,
+        "Isolated potential").  b is only read.  Returns `a`.  Asynchronous on the context's
+        stream."""
+        dims = self._spectrum_dims(a, "a")
+        if not np.array_equal(self._spectrum_dims(b, "b"), dims):
+            raise ValueError("a and b must have one shape")
+        _native(self, "avr_spectrum_multiply", self._handle, _pointer(a), _pointer(b),
+                _ints(dims))
+        return a
+
     # -- clump binding ------------------------------------------------------------------------
     def clump_pair_energy(self, offsets, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
                           m: torch.Tensor, w: Optional[torch.Tensor] = None):

@@ -2,7 +2,8 @@
 around the kernels of csrc/avr_fft.hip -- the wave numbers of a grid, the default, linear and
 logarithmic edges, their squares as the bin kernel compares them, the normalisation of the shell
 sums, an .npz file -- and, for api.helmholtz and api.potential ("Inverse transform,
-Helmholtz split, potential"), the inverse lengths, the compressive fraction and their .npz files.
+Helmholtz split, potential"), the inverse lengths, the compressive fraction and their .npz files;
+for api.isolated_potential ("Isolated potential") the padding rule and its .npz file.
 numpy only; no device work."""
 from __future__ import annotations
 
@@ -177,8 +178,8 @@ def load_npz(filename: str) -> Dict:
 PARTS = ("solenoidal", "compressive", "total")
 _NESTED = ("power", "spectrum", "modes", "solenoidal", "compressive")   # dicts of arrays
 _INTS = ("level", "outside", "nonfinite", "absent")
-_FLOATS = ("compressive_fraction", "imag_max", "constant")
-_TUPLES = ("lo", "dims", "cell_size")
+_FLOATS = ("compressive_fraction", "imag_max", "constant", "self_term")
+_TUPLES = ("lo", "dims", "cell_size", "padded_dims")
 
 
 def compressive_fraction(power_solenoidal, power_compressive, edges) -> float:
@@ -245,4 +246,43 @@ def save_potential_npz(result: Dict, filename: str) -> None:
 
 def load_potential_npz(filename: str) -> Dict:
     """Reads a file save_potential_npz wrote back into a dict of the same shape."""
+    return _load_nested(filename)
+
+
+# ---- isolated potential (DESIGN.md 7, "Isolated potential") ----------------------------------------
+
+MAX_ISOLATED_LENGTH = 512  # cells per axis of a region: its padded axis is at most MAX_LENGTH
+
+
+def padded_dims(dims) -> Tuple[int, int, int]:
+    """(Px, Py, Pz) of a region of dims = (nx, ny, nz) cells: per axis the smallest power of two
+    P >= 2 N - 1, the least that keeps the wrapped images of a zero-padded convolution out of
+    the region (1 for N = 1, at most 1024).  ValueError unless every N lies in [1, 512]; the
+    message names the axis."""
+    out = tuple(int(v) for v in dims)
+    if len(out) != 3:
+        raise ValueError("dims must hold three values")
+    for axis, n in zip("xyz", out):
+        if not 1 <= n <= MAX_ISOLATED_LENGTH:
+            raise ValueError(f"an isolated potential needs between 1 and {MAX_ISOLATED_LENGTH} "
+                             f"cells along every axis, not {n} along {axis}: pass a smaller "
+                             "region or a coarser level")
+    return tuple(1 << (2 * n - 2).bit_length() for n in out)
+
+
+def check_isolated_dims(dims) -> Tuple[int, int, int]:
+    """dims = (nx, ny, nz) as ints, checked as padded_dims checks them."""
+    padded_dims(dims)
+    return tuple(int(v) for v in dims)
+
+
+def save_isolated_potential_npz(result: Dict, filename: str) -> None:
+    """Writes api.isolated_potential's dict as one .npz, every entry under its key."""
+    _save_nested(result, filename)
+
+
+def load_isolated_potential_npz(filename: str) -> Dict:
+    """Reads a file save_isolated_potential_npz wrote back into a dict of the same shape: level
+    and absent ints, imag_max, constant and self_term floats, lo, dims, padded_dims and cell_size
+    tuples."""
     return _load_nested(filename)

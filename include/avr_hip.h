@@ -1599,6 +1599,33 @@ int avr_spectrum_helmholtz(avr_context *ctx, double *const spectra_dev[3], const
 int avr_spectrum_inverse_laplacian(avr_context *ctx, double *spectrum_dev, const int32_t *dims,
                                    const double *inverse_length_sq, double scale);
 
+/* ---- isolated potential ------------------------------------------------------------ */
+
+/* The open-boundary Green's function of a zero-padded grid: green_dev (device, f64
+ * [padded_dims[2]][padded_dims[1]][padded_dims[0]]) is written, nothing is read.  For the cell
+ * (k, j, i), per axis s_d = min(i_d, P_d - i_d) as an integer and x_d = f64(s_d) * cell_size[d]
+ * (host, 3 doubles: dx, dy, dz); r2 = x x + y y, then + z z; G = scale / sqrt(r2), one correctly
+ * rounded square root and one correctly rounded division, nothing fused; the single cell with
+ * r2 == 0, (0, 0, 0), holds self_value.  Equal arguments give equal bits.  Everything is checked on
+ * the host before any device work, in this order: AVR_ERR_INVALID_ARGUMENT for a NULL argument, a
+ * padded_dims that is not a power of two in [1, 1024], 2^31 cells or more, per axis a cell_size
+ * that is not finite and positive, one whose square is below DBL_MIN, one with (512 cell_size)^2
+ * not finite, and a scale or self_value that is not finite -- and the grid is untouched.
+ * Stateless; asynchronous on the context's stream. */
+int avr_isolated_green(avr_context *ctx, const int32_t *padded_dims, const double *cell_size,
+                       double scale, double self_value, double *green_dev);
+
+/* The product of two spectra in place: a_dev and b_dev (device, f64
+ * [dims[2]][dims[1]][dims[0]][2], as avr_field_fft writes them); every mode of a_dev becomes
+ * (a.re b.re - a.im b.im, a.re b.im + a.im b.re), each from two products and one addition, nothing
+ * fused; b_dev is only read.  Values that are not finite propagate by IEEE rules.  Equal arguments
+ * give equal bits.  Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for a NULL argument, a dims that is not a power of two in [1, 1024],
+ * 2^31 cells or more, and any byte shared between the two spectra -- and both are untouched.
+ * Stateless; asynchronous on the context's stream. */
+int avr_spectrum_multiply(avr_context *ctx, double *a_dev, const double *b_dev,
+                          const int32_t *dims);
+
 #ifdef __cplusplus
 }
 #endif
