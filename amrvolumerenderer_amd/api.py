@@ -1045,6 +1045,115 @@ def sample_points(plotfile: str, points, fields: Sequence[str], min_level: int =
     return values, inside
 
 
+# ---- what the grid products share: covering grids, power spectra, the Helmholtz split, potentials --
+
+def _plotfile_grid(plotfile: str, level, region, left_edge, right_edge, min_level: int,
+                   max_level: int, check_dims):
+    """(header, level, lo, dims) of a plotfile-level function over a grid of one level: region
+    and level as api.covering_grid has them and the product's rule on dims -- check_dims, which
+    returns them or raises -- before anything is loaded."""
+    from . import grids
+    from . import plotfile as pf
+    if region is not None and (left_edge is not None or right_edge is not None):
+        raise ValueError("give region or left_edge / right_edge, not both")
+    if (left_edge is None) != (right_edge is None):
+        raise ValueError("left_edge and right_edge go together")
+    _require_plotfile(plotfile)
+    header = pf.PlotFileData(plotfile)
+    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
+    level = finest_loaded if level is None else int(level)
+    if not 0 <= level <= header.finest_level:
+        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
+    size = header.cell_size[level]
+    if region is not None:
+        first, last = (tuple(int(v) for v in corner) for corner in region)
+        if len(first) != 3 or len(last) != 3:
+            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
+        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
+        if min(dims) < 1:
+            raise ValueError("region must hold at least one cell along every axis")
+    elif left_edge is not None:
+        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
+    else:
+        refine = math.prod(header.ref_ratio[:level])
+        domain_lo, domain_hi = header.prob_domain[0]
+        lo = tuple(v * refine for v in domain_lo)
+        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
+    return header, level, lo, check_dims(dims)
+
+
+def _grid_arguments(header, scene: "SceneGeometry", level: int, lo, dims):
+    """(level, lo, dims, cell_sizes, prob_lo, ref_ratio) as the *_scene functions of the grid
+    products take them: the levels run up to the finer of `level` and the finest loaded one."""
+    n_levels = max(level, max(int(b.level) for b in scene.all_boxes)) + 1
+    return (level, lo, dims, *_header_levels(header, n_levels))
+
+
+def _grid_head(header, level: int, lo, dims, **between) -> dict:
+    """How the result of a plotfile-level grid product begins: level, lo, dims, the entries the
+    product puts there (`between`) and the level's cell size."""
+    return {"level": level, "lo": lo, "dims": dims, **between,
+            "cell_size": tuple(float(v) for v in header.cell_size[level])}
+
+
+def _scene_grid_arguments(scene: "SceneGeometry", level, lo, dims, cell_sizes, n_ranks: int,
+                          what: str, check_dims):
+    """(level, lo, dims, the level's cell size) of a *_scene function over a grid whose dims
+    check_dims admits (spectra.check_dims: a periodic power-of-two grid), checked before any
+    device work."""
+    level = int(level)
+    lo = tuple(int(v) for v in lo)
+    if len(lo) != 3:
+        raise ValueError("lo and dims must hold three values")
+    dims = check_dims(dims)
+    _require_one_rank(scene, n_ranks, f"{what} needs every box of the scene on one rank: cells "
+                      "are not gathered between ranks")
+    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
+    if not 0 <= level < len(sizes):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    return level, lo, dims, sizes[level]
+
+
+def _covered_grid(field, level, lo, dims, index, ratios, fill):
+    """(values, absent) of one native scene's covering grid; absent cells without a fill value
+    raise ValueError."""
+    import torch
+    values, coverage, _ = field.covering_grid(level, lo, dims, index, ratios,
+                                              math.nan if fill is None else float(fill), True)
+    absent = int(torch.count_nonzero(coverage == 0.0).item())
+    if absent and fill is None:
+        raise ValueError(f"{absent} cells of the region hold no data: pass a fill value, or a "
+                         "region the loaded levels cover")
+    return values, absent
+
+
+def _edge_arguments(edges, bins, k_range, k_log, grid=None):
+    """The edges of api.power_spectrum and api.helmholtz, in two calls.  Without grid, on the
+    arguments alone, before anything is loaded: edges exclude bins, k_range and k_log and are
+    checked; returns them, or None.  With grid = (dims, cell size), once these are known: the
+    edges spectra.make_edges makes where none were given, checked for their squares."""
+    from . import spectra
+    if grid is None:        # the first call: what the arguments alone can be refused for
+        if edges is not None and (bins is not None or k_range is not None or k_log):
+            raise ValueError("give edges or bins / k_range / k_log, not both")
+        if edges is not None:
+            edges = spectra.check_edges(edges)
+    elif edges is None:     # the second call without explicit edges: made for this grid
+        edges = spectra.make_edges(*grid, bins, k_range, bool(k_log))
+    if edges is not None:   # either call, whenever there are edges: their squares must differ
+        spectra.squared_edges(edges)
+    return edges
+
+
+def _shell_sums(binned, dims, k_edges):
+    """(power, spectrum, k, outside, nonfinite) of what Context.spectrum_bins returned, binned =
+    (modes, sums, totals) as numpy arrays, over a grid of dims (spectra.normalise)."""
+    from . import spectra
+    _, sums, totals = binned
+    power, spectrum, k = spectra.normalise(sums, dims[0] * dims[1] * dims[2], k_edges)
+    return power, spectrum, k, int(totals[0]), int(totals[1])
+
+
 # ---- covering grids (DESIGN.md 7, "Covering grid") ------------------------------------------------
 
 def covering_grid_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes, prob_lo,
@@ -1103,36 +1212,12 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     written as one .npz file (grids.save_npz)."""
     import numpy as np
     from . import grids
-    from . import plotfile as pf
-    if region is not None and (left_edge is not None or right_edge is not None):
-        raise ValueError("give region or left_edge / right_edge, not both")
-    if (left_edge is None) != (right_edge is None):
-        raise ValueError("left_edge and right_edge go together")
-    _require_plotfile(plotfile)
-    header = pf.PlotFileData(plotfile)
-    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
-    level = finest_loaded if level is None else int(level)
-    if not 0 <= level <= header.finest_level:
-        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
-    size = header.cell_size[level]
-    if region is not None:
-        first, last = (tuple(int(v) for v in corner) for corner in region)
-        if len(first) != 3 or len(last) != 3:
-            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
-        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
-        if min(dims) < 1:
-            raise ValueError("region must hold at least one cell along every axis")
-    elif left_edge is not None:
-        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
-    else:
-        refine = math.prod(header.ref_ratio[:level])
-        domain_lo, domain_hi = header.prob_domain[0]
-        lo = tuple(v * refine for v in domain_lo)
-        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level,
+                                             lambda dims: dims)   # a region of any size
     names = [str(name) for name in fields] or [header.var_names[0]]
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
-    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    arguments = (level, lo, dims, *_header_levels(header, n_levels), float(fill))
+    arguments = (*_grid_arguments(header, scenes[0], level, lo, dims), float(fill))
     found, coverage, cell_level = {}, None, None
     for name, scene in zip(names, scenes):
         # coverage and cell level are the same for every field of one plotfile: once
@@ -1140,10 +1225,10 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
         found[name] = values
         if coverage is None:
             coverage, cell_level = c, l
-    left, right = grids.grid_edges(header.prob_lo, size, lo, dims)
-    result = {"level": level, "lo": lo, "dims": dims, "left_edge": left, "right_edge": right,
-              "cell_size": tuple(float(v) for v in size), "fields": found, "coverage": coverage,
-              "cell_level": cell_level, "absent": int(np.count_nonzero(coverage == 0.0)),
+    left, right = grids.grid_edges(header.prob_lo, header.cell_size[level], lo, dims)
+    result = {**_grid_head(header, level, lo, dims, left_edge=left, right_edge=right),
+              "fields": found, "coverage": coverage, "cell_level": cell_level,
+              "absent": int(np.count_nonzero(coverage == 0.0)),
               "partial": int(np.count_nonzero((coverage > 0.0) & (coverage < 1.0)))}
     if output:
         grids.save_npz(result, output)
@@ -1166,37 +1251,21 @@ def power_spectrum_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell
     absent.  With n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised
     before any device work."""
     import numpy as np
-    import torch
     from . import spectra
-    level = int(level)
-    lo = tuple(int(v) for v in lo)
-    if len(lo) != 3:
-        raise ValueError("lo and dims must hold three values")
-    dims = spectra.check_dims(dims)
-    _require_one_rank(scene, n_ranks, "a power spectrum needs every box of the scene on one rank: "
-                      "cells are not gathered between ranks")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    if not 0 <= level < len(sizes):
-        raise ValueError("level must lie in [0, the number of cell_sizes)")
-    k_edges = (spectra.default_edges(dims, sizes[level]) if edges is None
-               else spectra.check_edges(edges))
+    level, lo, dims, size = _scene_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
+                                                  "a power spectrum", spectra.check_dims)
+    k_edges = spectra.default_edges(dims, size) if edges is None else spectra.check_edges(edges)
     edges_sq = spectra.squared_edges(k_edges)
-    g = spectra.inverse_length_sq(dims, sizes[level])
+    g = spectra.inverse_length_sq(dims, size)
     sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
     with _native_scenes(ctx, [scene]) as (field,):
-        values, coverage, _ = field.covering_grid(level, lo, dims, index, ratios,
-                                                  math.nan if fill is None else float(fill), True)
-        absent = int(torch.count_nonzero(coverage == 0.0).item())
-        if absent and fill is None:
-            raise ValueError(f"{absent} cells of the region hold no data: pass a fill value, or a "
-                             "region the loaded levels cover")
-        modes, sums, totals = ctx.spectrum_bins(ctx.fft3d(values), g, edges_sq)
+        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+        binned = ctx.spectrum_bins(ctx.fft3d(values), g, edges_sq)
         ctx.synchronize()
-        modes, sums, totals = modes.cpu().numpy(), sums.cpu().numpy(), totals.cpu().numpy()
-    power, spectrum, k = spectra.normalise(sums, dims[0] * dims[1] * dims[2], k_edges)
+        binned = tuple(t.cpu().numpy() for t in binned)
+    power, spectrum, k, outside, nonfinite = _shell_sums(binned, dims, k_edges)
     return {"k_edges": np.array(k_edges), "k": k, "power": power, "spectrum": spectrum,
-            "modes": modes, "outside": int(totals[0]), "nonfinite": int(totals[1]),
-            "absent": absent}
+            "modes": binned[0], "outside": outside, "nonfinite": nonfinite, "absent": absent}
 
 
 def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[int] = None,
@@ -1220,46 +1289,14 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
     modes whose |F|^2 is not finite, summed over the fields) and absent (cells without data).
     With output the dict is written as one .npz file (spectra.save_npz)."""
     import numpy as np
-    from . import grids, spectra
-    from . import plotfile as pf
-    if region is not None and (left_edge is not None or right_edge is not None):
-        raise ValueError("give region or left_edge / right_edge, not both")
-    if (left_edge is None) != (right_edge is None):
-        raise ValueError("left_edge and right_edge go together")
-    if edges is not None and (bins is not None or k_range is not None or k_log):
-        raise ValueError("give edges or bins / k_range / k_log, not both")
-    if edges is not None:
-        edges = spectra.check_edges(edges)
-        spectra.squared_edges(edges)
-    _require_plotfile(plotfile)
-    header = pf.PlotFileData(plotfile)
-    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
-    level = finest_loaded if level is None else int(level)
-    if not 0 <= level <= header.finest_level:
-        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
-    size = header.cell_size[level]
-    if region is not None:
-        first, last = (tuple(int(v) for v in corner) for corner in region)
-        if len(first) != 3 or len(last) != 3:
-            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
-        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
-        if min(dims) < 1:
-            raise ValueError("region must hold at least one cell along every axis")
-    elif left_edge is not None:
-        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
-    else:
-        refine = math.prod(header.ref_ratio[:level])
-        domain_lo, domain_hi = header.prob_domain[0]
-        lo = tuple(v * refine for v in domain_lo)
-        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
-    dims = spectra.check_dims(dims)
-    if edges is None:
-        edges = spectra.make_edges(dims, size, bins, k_range, bool(k_log))
-    spectra.squared_edges(edges)
+    from . import spectra
+    edges = _edge_arguments(edges, bins, k_range, k_log)
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level, spectra.check_dims)
+    edges = _edge_arguments(edges, bins, k_range, k_log, (dims, header.cell_size[level]))
     names = [str(name) for name in fields] or [header.var_names[0]]
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
-    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    arguments = (level, lo, dims, *_header_levels(header, n_levels), edges, fill)
+    arguments = (*_grid_arguments(header, scenes[0], level, lo, dims), edges, fill)
     found, total, outside, nonfinite, absent, k = {}, None, 0, 0, 0, None
     for name, scene in zip(names, scenes):
         one = power_spectrum_scene(ctx, scene, *arguments, rank, world)
@@ -1268,7 +1305,7 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
         outside += one["outside"]
         nonfinite += one["nonfinite"]
         absent, k = one["absent"], one["k"]
-    result = {"level": level, "lo": lo, "dims": dims, "cell_size": tuple(float(v) for v in size),
+    result = {**_grid_head(header, level, lo, dims),
               "k_edges": np.array(edges, dtype=np.float64), "k": k, "fields": found,
               "total": total, "outside": outside, "nonfinite": nonfinite, "absent": absent}
     if output:
@@ -1277,37 +1314,6 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
 
 
 # ---- inverse transform, Helmholtz split, potential -----------------------------------
-
-def _periodic_grid_arguments(scene: "SceneGeometry", level, lo, dims, cell_sizes, n_ranks: int,
-                             what: str):
-    """(level, lo, dims, the level's cell size) of a *_scene function over a periodic power-of-two
-    grid, checked as power_spectrum_scene checks them, before any device work."""
-    from . import spectra
-    level = int(level)
-    lo = tuple(int(v) for v in lo)
-    if len(lo) != 3:
-        raise ValueError("lo and dims must hold three values")
-    dims = spectra.check_dims(dims)
-    _require_one_rank(scene, n_ranks, f"{what} needs every box of the scene on one rank: cells "
-                      "are not gathered between ranks")
-    sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    if not 0 <= level < len(sizes):
-        raise ValueError("level must lie in [0, the number of cell_sizes)")
-    return level, lo, dims, sizes[level]
-
-
-def _covered_grid(field, level, lo, dims, index, ratios, fill):
-    """(values, absent) of one native scene's covering grid; absent cells without a fill value
-    raise ValueError."""
-    import torch
-    values, coverage, _ = field.covering_grid(level, lo, dims, index, ratios,
-                                              math.nan if fill is None else float(fill), True)
-    absent = int(torch.count_nonzero(coverage == 0.0).item())
-    if absent and fill is None:
-        raise ValueError(f"{absent} cells of the region hold no data: pass a fill value, or a "
-                         "region the loaded levels cover")
-    return values, absent
-
 
 def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeometry",
                     level: int, lo, dims, cell_sizes, prob_lo, ref_ratio, edges=None,
@@ -1330,8 +1336,8 @@ def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeo
     import numpy as np
     import torch
     from . import spectra
-    level, lo, dims, size = _periodic_grid_arguments(vx, level, lo, dims, cell_sizes, n_ranks,
-                                                     "a Helmholtz split")
+    level, lo, dims, size = _scene_grid_arguments(vx, level, lo, dims, cell_sizes, n_ranks,
+                                                  "a Helmholtz split", spectra.check_dims)
     for other in (vy, vz):
         _require_one_rank(other, n_ranks, "a Helmholtz split needs every box of the scene on one "
                           "rank: cells are not gathered between ranks")
@@ -1369,56 +1375,22 @@ def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeo
         if grids:
             found = {part: tuple(t.cpu().numpy() for t in three) for part, three in found.items()}
             found["imag_max"] = float(worst.item())
-    cells = dims[0] * dims[1] * dims[2]
     result = {"k_edges": np.array(k_edges), "power": {}, "spectrum": {}, "modes": {}}
-    for part, (modes, sums, totals) in binned.items():
-        power, spectrum, result["k"] = spectra.normalise(sums, cells, k_edges)
+    outside = nonfinite = 0
+    for part, out in binned.items():
+        power, spectrum, result["k"], out_outside, out_nonfinite = \
+            _shell_sums(out, dims, k_edges)
         result["power"][part], result["spectrum"][part], result["modes"][part] = \
-            power, spectrum, modes
+            power, spectrum, out[0]
+        outside, nonfinite = outside + out_outside, nonfinite + out_nonfinite
     for key in ("power", "spectrum"):
         result[key]["total"] = result[key]["solenoidal"] + result[key]["compressive"]
     result["compressive_fraction"] = spectra.compressive_fraction(
         result["power"]["solenoidal"], result["power"]["compressive"], k_edges)
-    result["outside"] = sum(int(binned[part][2][0]) for part in binned)
-    result["nonfinite"] = sum(int(binned[part][2][1]) for part in binned)
+    result["outside"], result["nonfinite"] = outside, nonfinite
     result["absent"] = absent
     result.update(found)
     return result
-
-
-def _plotfile_grid(plotfile: str, level, region, left_edge, right_edge, min_level: int,
-                   max_level: int, check_dims=None):
-    """(header, level, lo, dims) of a plotfile-level function over a grid of one level: region
-    and level as api.power_spectrum has them and the rule on dims -- check_dims, by default the
-    power-of-two rule of a periodic grid (spectra.check_dims) -- before anything is loaded."""
-    from . import grids, spectra
-    from . import plotfile as pf
-    if region is not None and (left_edge is not None or right_edge is not None):
-        raise ValueError("give region or left_edge / right_edge, not both")
-    if (left_edge is None) != (right_edge is None):
-        raise ValueError("left_edge and right_edge go together")
-    _require_plotfile(plotfile)
-    header = pf.PlotFileData(plotfile)
-    _, finest_loaded = pf.clamp_levels(int(min_level), int(max_level), header.finest_level)
-    level = finest_loaded if level is None else int(level)
-    if not 0 <= level <= header.finest_level:
-        raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
-    size = header.cell_size[level]
-    if region is not None:
-        first, last = (tuple(int(v) for v in corner) for corner in region)
-        if len(first) != 3 or len(last) != 3:
-            raise ValueError("region must be ((ilo, jlo, klo), (ihi, jhi, khi))")
-        lo, dims = first, tuple(last[a] - first[a] + 1 for a in range(3))
-        if min(dims) < 1:
-            raise ValueError("region must hold at least one cell along every axis")
-    elif left_edge is not None:
-        lo, dims = grids.index_region(header.prob_lo, size, left_edge, right_edge)
-    else:
-        refine = math.prod(header.ref_ratio[:level])
-        domain_lo, domain_hi = header.prob_domain[0]
-        lo = tuple(v * refine for v in domain_lo)
-        dims = tuple((domain_hi[a] + 1) * refine - lo[a] for a in range(3))
-    return header, level, lo, (check_dims or spectra.check_dims)(dims)
 
 
 def helmholtz(plotfile: str, velocity: Sequence[str], level: Optional[int] = None, region=None,
@@ -1442,22 +1414,14 @@ def helmholtz(plotfile: str, velocity: Sequence[str], level: Optional[int] = Non
     names = [velocity] if isinstance(velocity, str) else [str(name) for name in velocity]
     if len(names) != 3:
         raise ValueError("velocity must name three components")
-    if edges is not None and (bins is not None or k_range is not None or k_log):
-        raise ValueError("give edges or bins / k_range / k_log, not both")
-    if edges is not None:
-        edges = spectra.check_edges(edges)
-        spectra.squared_edges(edges)
+    edges = _edge_arguments(edges, bins, k_range, k_log)
     header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
-                                             min_level, max_level)
-    size = header.cell_size[level]
-    if edges is None:
-        edges = spectra.make_edges(dims, size, bins, k_range, bool(k_log))
-    spectra.squared_edges(edges)
+                                             min_level, max_level, spectra.check_dims)
+    edges = _edge_arguments(edges, bins, k_range, k_log, (dims, header.cell_size[level]))
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
-    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    found = helmholtz_scene(ctx, *scenes, level, lo, dims, *_header_levels(header, n_levels),
+    found = helmholtz_scene(ctx, *scenes, *_grid_arguments(header, scenes[0], level, lo, dims),
                             edges, fill, bool(grids), rank, world)
-    result = {"level": level, "lo": lo, "dims": dims, "cell_size": tuple(float(v) for v in size)}
+    result = _grid_head(header, level, lo, dims)
     result.update(found)
     for part in ("solenoidal", "compressive"):
         if part in found:
@@ -1483,8 +1447,8 @@ def potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_size
     constant = float(constant)
     if not math.isfinite(constant):
         raise ValueError("constant must be finite")
-    level, lo, dims, size = _periodic_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
-                                                     "a potential")
+    level, lo, dims, size = _scene_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
+                                                  "a potential", spectra.check_dims)
     g = spectra.inverse_length_sq(dims, size)
     scale = -(constant / (4.0 * math.pi * math.pi))
     sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
@@ -1515,14 +1479,12 @@ def potential(plotfile: str, variable: str = "", constant: float = 1.0,
     if not math.isfinite(constant):
         raise ValueError("constant must be finite")
     header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
-                                             min_level, max_level)
+                                             min_level, max_level, spectra.check_dims)
     name = str(variable) or header.var_names[0]
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, [name], min_level, max_level)
-    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    found = potential_scene(ctx, scenes[0], level, lo, dims, *_header_levels(header, n_levels),
+    found = potential_scene(ctx, scenes[0], *_grid_arguments(header, scenes[0], level, lo, dims),
                             constant, fill, rank, world)
-    result = {"level": level, "lo": lo, "dims": dims,
-              "cell_size": tuple(float(v) for v in header.cell_size[level]), "constant": constant}
+    result = {**_grid_head(header, level, lo, dims), "constant": constant}
     result.update(found)
     if output:
         spectra.save_potential_npz(result, output)
@@ -1558,18 +1520,10 @@ def isolated_potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, 
     import torch
     from . import spectra
     constant, self_term = _isolated_constants(constant, self_term)
-    level = int(level)
-    lo = tuple(int(v) for v in lo)
-    if len(lo) != 3:
-        raise ValueError("lo and dims must hold three values")
-    padded = spectra.padded_dims(dims)
-    nx, ny, nz = dims = tuple(int(v) for v in dims)
-    _require_one_rank(scene, n_ranks, "an isolated potential needs every box of the scene on one "
-                      "rank: cells are not gathered between ranks")
-    all_sizes = [tuple(float(v) for v in c) for c in cell_sizes]
-    if not 0 <= level < len(all_sizes):
-        raise ValueError("level must lie in [0, the number of cell_sizes)")
-    size = all_sizes[level]
+    level, lo, dims, size = _scene_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
+                                                  "an isolated potential",
+                                                  spectra.check_isolated_dims)
+    padded, (nx, ny, nz) = spectra.padded_dims(dims), dims
     volume = (size[0] * size[1]) * size[2]
     scale = -((constant * volume) / (4.0 * math.pi))
     self_value = scale * self_term
@@ -1622,12 +1576,10 @@ def isolated_potential(plotfile: str, variable: str = "", constant: float = 1.0,
                                              min_level, max_level, spectra.check_isolated_dims)
     name = str(variable) or header.var_names[0]
     ctx, rank, world, group, scenes, _ = _load_fields(plotfile, [name], min_level, max_level)
-    n_levels = max(level, max(int(b.level) for b in scenes[0].all_boxes)) + 1
-    found = isolated_potential_scene(ctx, scenes[0], level, lo, dims,
-                                     *_header_levels(header, n_levels), constant, self_term,
-                                     fill, rank, world)
-    result = {"level": level, "lo": lo, "dims": dims, "padded_dims": found["padded_dims"],
-              "cell_size": tuple(float(v) for v in header.cell_size[level]),
+    found = isolated_potential_scene(ctx, scenes[0],
+                                     *_grid_arguments(header, scenes[0], level, lo, dims),
+                                     constant, self_term, fill, rank, world)
+    result = {**_grid_head(header, level, lo, dims, padded_dims=found["padded_dims"]),
               "constant": constant, "self_term": self_term}
     result.update(found)
     if output:

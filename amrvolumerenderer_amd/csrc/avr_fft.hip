@@ -1,9 +1,9 @@
-// Power spectra ("Power spectrum"): the forward, unnormalised 3-D transform of a real
-// f64 grid and the shell sums of its spectrum.
+// The transforms ("Power spectrum" and "Inverse transform, Helmholtz split,
+// potential"): the forward, unnormalised 3-D transform of a real f64 grid and the normalised
+// inverse of a spectrum.  The per-mode kernels on a spectrum are avr_spectral.hip's.
 //
 //   fft_x_kernel          real [nz][ny][nx] -> complex [nz][ny][nx][2], transformed along x
 //   fft_column_kernel     one strided pass (y, then z) in place on the spectrum
-//   spectrum_bins_kernel  |F|^2 of every mode added to the bin of its wave number
 //   ifft_x_kernel         the inverse's last pass: complex lines along x -> real grids, scaled
 //                         (the inverse's z and y passes are fft_column_kernel with conjugate tables)
 //
@@ -41,10 +41,8 @@ namespace avr {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr uint32_t kModesPerGroup = 16384;  // of the bin kernel: 64 per lane, a 32-bit count each
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
-typedef double __attribute__((address_space(3))) lds_double;
 
 __device__ __forceinline__ uint32_t reverse_bits(uint32_t index, int p) {
   return p == 0 ? 0u : __brev(index) >> (32 - p);
@@ -86,10 +84,10 @@ __device__ __forceinline__ void line_stages(double2_t* v, uint32_t lines, int p,
 
 __global__ __launch_bounds__(kThreads) void fft_x_kernel(const FftArgs a) {
   extern __shared__ double2_t fft_lds[];
-  const int p = a.log2nx;
-  const uint32_t first = blockIdx.x * a.x_group;
-  const uint32_t left = a.x_lines - first;
-  const uint32_t lines = left < a.x_group ? left : a.x_group;
+  const int p = a.lines.log2nx;
+  const uint32_t first = blockIdx.x * a.lines.x_group;
+  const uint32_t left = a.lines.x_lines - first;
+  const uint32_t lines = left < a.lines.x_group ? left : a.lines.x_group;
   const uint32_t elements = lines << p;
   const size_t base = static_cast<size_t>(first) << p;
   const double* __restrict__ in = a.values + base;
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void fft_x_kernel(const FftArgs a) {
     value.y = 0.0;
     fft_lds[(line << p) + swizzle(reverse_bits(index, p), line, p)] = value;
   }
-  line_stages(fft_lds, lines, p, reinterpret_cast<const double2_t*>(a.twiddle[0]));
+  line_stages(fft_lds, lines, p, reinterpret_cast<const double2_t*>(a.lines.twiddle[0]));
   double2_t* out = reinterpret_cast<double2_t*>(a.spectrum) + base;
   for (uint32_t e = threadIdx.x; e < elements; e += kThreads) {
     const uint32_t line = e >> p, k = e & ((1u << p) - 1u);
@@ -135,10 +133,10 @@ __global__ __launch_bounds__(kThreads) void fft_column_kernel(double2_t* spectru
 // and, where asked for, im * scale to `imag`.  Launched for nx == 1 as well: the scale and split.
 __global__ __launch_bounds__(kThreads) void ifft_x_kernel(const IfftArgs a) {
   extern __shared__ double2_t fft_lds[];
-  const int p = a.log2nx;
-  const uint32_t first = blockIdx.x * a.x_group;
-  const uint32_t left = a.x_lines - first;
-  const uint32_t lines = left < a.x_group ? left : a.x_group;
+  const int p = a.lines.log2nx;
+  const uint32_t first = blockIdx.x * a.lines.x_group;
+  const uint32_t left = a.lines.x_lines - first;
+  const uint32_t lines = left < a.lines.x_group ? left : a.lines.x_group;
   const uint32_t elements = lines << p;
   const size_t base = static_cast<size_t>(first) << p;
   const double2_t* __restrict__ in = reinterpret_cast<const double2_t*>(a.spectrum) + base;
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void ifft_x_kernel(const IfftArgs a) {
     const uint32_t line = e >> p, index = e & ((1u << p) - 1u);
     fft_lds[(line << p) + swizzle(reverse_bits(index, p), line, p)] = in[e];
   }
-  line_stages(fft_lds, lines, p, reinterpret_cast<const double2_t*>(a.twiddle[0]));
+  line_stages(fft_lds, lines, p, reinterpret_cast<const double2_t*>(a.lines.twiddle[0]));
   double* __restrict__ values = a.values + base;
   double* __restrict__ imag = a.imag != nullptr ? a.imag + base : nullptr;
   const double scale = a.scale;
@@ -155,96 +153,6 @@ __global__ __launch_bounds__(kThreads) void ifft_x_kernel(const IfftArgs a) {
     const double2_t value = fft_lds[(line << p) + swizzle(k, line, p)];
     values[e] = value.x * scale;
     if (imag != nullptr) imag[e] = value.y * scale;
-  }
-}
-
-// The signed wave number of index k along an axis of 2^p modes (numpy.fft.fftfreq's convention).
-__device__ __forceinline__ double signed_mode(uint32_t k, int p) {
-  const int n = 1 << p;
-  const int m = (static_cast<int>(k) < (n >> 1) || n == 1) ? static_cast<int>(k)
-                                                            : static_cast<int>(k) - n;
-  return static_cast<double>(m);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int mask = 32; mask > 0; mask >>= 1) v += __shfl_xor(v, mask, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(kThreads) void spectrum_bins_kernel(const SpectrumBinsArgs a) {
-  // [edges: n + 1][sums: n][counts: n x u32]
-  extern __shared__ double bins_lds[];
-  __shared__ uint32_t wave_totals[kThreads / 64][2];
-  const int n = a.n_bins;
-  lds_double* edges = (lds_double*)bins_lds;
-  lds_double* local_sums = edges + (n + 1);
-  unsigned int* local_counts = reinterpret_cast<unsigned int*>(bins_lds + (2 * n + 1));
-  const int tid = static_cast<int>(threadIdx.x);
-  for (int i = tid; i <= n; i += kThreads) edges[i] = a.edges_sq[i];
-  for (int b = tid; b < n; b += kThreads) {
-    local_sums[b] = 0.0;
-    local_counts[b] = 0u;
-  }
-  __syncthreads();
-
-  const double lowest = edges[0], highest = edges[n];
-  const int px = a.log2n[0], py = a.log2n[1];
-  const double2_t* __restrict__ spectrum = reinterpret_cast<const double2_t*>(a.spectrum);
-  uint32_t outside = 0, nonfinite = 0;
-  const uint32_t first = blockIdx.x * kModesPerGroup;
-  const uint32_t left = a.n_modes - first;
-  const uint32_t count = left < kModesPerGroup ? left : kModesPerGroup;
-  for (uint32_t e = threadIdx.x; e < count; e += kThreads) {
-    const uint32_t mode = first + e;
-    const double2_t f = spectrum[mode];
-    const double power = f.x * f.x + f.y * f.y;
-    if (!__builtin_isfinite(power)) {
-      nonfinite += 1;
-      continue;
-    }
-    const double mx = signed_mode(mode & ((1u << px) - 1u), px);
-    const double my = signed_mode((mode >> px) & ((1u << py) - 1u), py);
-    const double mz = signed_mode(mode >> (px + py), a.log2n[2]);
-    double q = (mx * mx) * a.g[0] + (my * my) * a.g[1];
-    q = q + (mz * mz) * a.g[2];
-    if (!((lowest <= q) & (q <= highest))) {
-      outside += 1;
-      continue;
-    }
-    // the largest i in [0, n - 1] with E[i] <= q: E[lo] <= q and (hi == n or q < E[hi])
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (edges[mid] <= q) {
-        lo = mid;
-      } else {
-        hi = mid;
-      }
-    }
-    atomicAdd(&local_counts[lo], 1u);
-    __hip_atomic_fetch_add(local_sums + lo, power, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  __syncthreads();
-  for (int b = tid; b < n; b += kThreads) {
-    const unsigned int c = local_counts[b];
-    if (c != 0u) {
-      atomicAdd(&a.modes[b], static_cast<unsigned long long>(c));
-      // an ordinary (coarse-grained) device allocation: the hardware's f64 add
-      unsafeAtomicAdd(&a.power[b], static_cast<double>(local_sums[b]));
-    }
-  }
-
-  outside = wave_sum(outside);
-  nonfinite = wave_sum(nonfinite);
-  if ((tid & 63) == 0) {
-    wave_totals[tid >> 6][0] = outside;
-    wave_totals[tid >> 6][1] = nonfinite;
-  }
-  __syncthreads();
-  if (tid < 2) {
-    uint32_t total = 0;
-    for (int w = 0; w < kThreads / 64; ++w) total += wave_totals[w][tid];
-    if (total != 0u) atomicAdd(&a.totals[tid], static_cast<unsigned long long>(total));
   }
 }
 
@@ -257,22 +165,34 @@ int check(const char* what) {
   return AVR_OK;
 }
 
+// One strided pass, pass[which] (y or z), in place on `spectrum`; a line of one value is skipped.
+int launch_column_pass(const FftLinesDev& lines, int which, double* spectrum, hipStream_t stream) {
+  const FftPassDev& pass = lines.pass[which];
+  if (pass.n == 1) return AVR_OK;
+  const size_t bytes = (static_cast<size_t>(pass.group) << pass.log2n) * sizeof(double2_t);
+  hipLaunchKernelGGL(fft_column_kernel, dim3(pass.planes * pass.groups), dim3(kThreads), bytes,
+                     stream, reinterpret_cast<double2_t*>(spectrum),
+                     reinterpret_cast<const double2_t*>(lines.twiddle[which + 1]), pass);
+  return check("fft_column_kernel");
+}
+
+// The x pass of either direction: `kernel` over groups of x_group whole lines.
+template <class Args>
+int launch_x_pass(void (*kernel)(Args), const Args& args, const char* name, hipStream_t stream) {
+  const FftLinesDev& lines = args.lines;
+  const uint32_t groups = (lines.x_lines + lines.x_group - 1) / lines.x_group;
+  const size_t bytes = (static_cast<size_t>(lines.x_group) << lines.log2nx) * sizeof(double2_t);
+  hipLaunchKernelGGL(kernel, dim3(groups), dim3(kThreads), bytes, stream, args);
+  return check(name);
+}
+
 }  // namespace
 
 int launch_fft3d(const FftArgs& args, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const uint32_t x_groups = (args.x_lines + args.x_group - 1) / args.x_group;
-  const size_t x_bytes = (static_cast<size_t>(args.x_group) << args.log2nx) * sizeof(double2_t);
-  hipLaunchKernelGGL(fft_x_kernel, dim3(x_groups), dim3(kThreads), x_bytes, stream, args);
-  int status = check("fft_x_kernel");
-  for (int which = 0; which < 2 && status == AVR_OK; ++which) {
-    const FftPassDev& pass = args.pass[which];
-    if (pass.n == 1) continue;  // the identity
-    const size_t bytes = (static_cast<size_t>(pass.group) << pass.log2n) * sizeof(double2_t);
-    hipLaunchKernelGGL(fft_column_kernel, dim3(pass.planes * pass.groups), dim3(kThreads), bytes,
-                       stream, reinterpret_cast<double2_t*>(args.spectrum),
-                       reinterpret_cast<const double2_t*>(args.twiddle[which + 1]), pass);
-    status = check("fft_column_kernel");
+  int status = launch_x_pass(fft_x_kernel, args, "fft_x_kernel", stream);
+  for (int which = 0; which < 2 && status == AVR_OK; ++which) {  // y, then z
+    status = launch_column_pass(args.lines, which, args.spectrum, stream);
   }
   return status;
 }
@@ -281,28 +201,10 @@ int launch_ifft3d(const IfftArgs& args, void* stream_v) {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   int status = AVR_OK;
   for (int which = 1; which >= 0 && status == AVR_OK; --which) {  // z, then y
-    const FftPassDev& pass = args.pass[which];
-    if (pass.n == 1) continue;  // the identity
-    const size_t bytes = (static_cast<size_t>(pass.group) << pass.log2n) * sizeof(double2_t);
-    hipLaunchKernelGGL(fft_column_kernel, dim3(pass.planes * pass.groups), dim3(kThreads), bytes,
-                       stream, reinterpret_cast<double2_t*>(args.spectrum),
-                       reinterpret_cast<const double2_t*>(args.twiddle[which + 1]), pass);
-    status = check("fft_column_kernel");
+    status = launch_column_pass(args.lines, which, args.spectrum, stream);
   }
   if (status != AVR_OK) return status;
-  const uint32_t x_groups = (args.x_lines + args.x_group - 1) / args.x_group;
-  const size_t x_bytes = (static_cast<size_t>(args.x_group) << args.log2nx) * sizeof(double2_t);
-  hipLaunchKernelGGL(ifft_x_kernel, dim3(x_groups), dim3(kThreads), x_bytes, stream, args);
-  return check("ifft_x_kernel");
-}
-
-int launch_spectrum_bins(const SpectrumBinsArgs& args, void* stream_v) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const uint32_t groups = (args.n_modes + kModesPerGroup - 1) / kModesPerGroup;
-  const size_t n = static_cast<size_t>(args.n_bins);
-  const size_t bytes = (n + 1) * 8 + n * 8 + n * 4;
-  hipLaunchKernelGGL(spectrum_bins_kernel, dim3(groups), dim3(kThreads), bytes, stream, args);
-  return check("spectrum_bins_kernel");
+  return launch_x_pass(ifft_x_kernel, args, "ifft_x_kernel", stream);
 }
 
 }  // namespace avr

@@ -1972,6 +1972,10 @@ inline uint64_t require_fft_dims(const int32_t dims[3]) {
   require_cell_count(cells);
   return cells;
 }
+// The workgroups of a streaming kernel that takes kSpectralGroupElements elements each.
+inline uint32_t spectral_groups(uint64_t elements) {
+  return static_cast<uint32_t>((elements + kSpectralGroupElements - 1) / kSpectralGroupElements);
+}
 // How a strided pass over lines of length n cuts a plane of `columns` adjacent lines into
 // workgroups: `group` adjacent columns each -- kFftGroupElements / n, at least kFftMinColumns, at
 // most the plane's -- so that a workgroup's global accesses are runs of `group` 16-byte elements;
@@ -2011,13 +2015,26 @@ inline void fft_column_passes(const int32_t dims[3], FftPassDev pass_out[2]) {
     pass.last = cut.last;
   }
 }
-struct Fft3dPlan {
+// The lines and passes of the transform of a grid of dims = (nx, ny, nz), forward or inverse.
+inline FftLinesDev fft_lines(const int32_t dims[3]) {
+  FftLinesDev lines{};
+  lines.nx = dims[0];
+  lines.log2nx = fft_log2(dims[0]);
+  lines.x_lines = static_cast<uint32_t>(dims[1]) * static_cast<uint32_t>(dims[2]);
+  lines.x_group = fft_x_group(lines.x_lines, dims[0]);
+  fft_column_passes(dims, lines.pass);
+  return lines;
+}
+// A transform's three tables: fft_twiddles for the forward one, fft_inverse_twiddles for the inverse.
+struct FftTables {
   std::vector<double> twiddle[3];  // x, y, z; empty for an axis of length 1
-  FftArgs args{};
   template <class Visit>
-  void visit_tables(FftArgs* to, Visit&& visit) const {
+  void visit_tables(FftLinesDev* to, Visit&& visit) const {
     for (int d = 0; d < 3; ++d) visit(&to->twiddle[d], twiddle[d].data(), twiddle[d].size());
   }
+};
+struct Fft3dPlan : FftTables {
+  FftArgs args{};
 };
 // The transform of the real grid `values` [nz][ny][nx] into `spectrum` [nz][ny][nx][2], both device
 // arrays the entry point has checked for null.  The rules, in this order: the dims, fewer than 2^31
@@ -2030,12 +2047,7 @@ inline Fft3dPlan plan_fft3d(const int32_t dims[3], const void* values, const voi
   require_no_shared_byte(&read_ranges, write_ranges, "the spectrum overlaps the input");
   Fft3dPlan plan;
   for (int d = 0; d < 3; ++d) plan.twiddle[d] = fft_twiddles(dims[d]);
-  FftArgs& args = plan.args;
-  args.nx = dims[0];
-  args.log2nx = fft_log2(dims[0]);
-  args.x_lines = static_cast<uint32_t>(cells / static_cast<uint64_t>(dims[0]));
-  args.x_group = fft_x_group(args.x_lines, dims[0]);
-  fft_column_passes(dims, args.pass);
+  plan.args.lines = fft_lines(dims);
   return plan;
 }
 
@@ -2058,13 +2070,8 @@ inline void require_disjoint(ByteRanges* ranges, const char* message) {
     require_box(reach < (*ranges)[r].first, message);
   }
 }
-struct Ifft3dPlan {
-  std::vector<double> twiddle[3];  // V for x, y, z; empty for an axis of length 1
+struct Ifft3dPlan : FftTables {  // the tables V
   IfftArgs args{};
-  template <class Visit>
-  void visit_tables(IfftArgs* to, Visit&& visit) const {
-    for (int d = 0; d < 3; ++d) visit(&to->twiddle[d], twiddle[d].data(), twiddle[d].size());
-  }
 };
 // The inverse of `spectrum` [nz][ny][nx][2] into the real grids `values` and, unless null, `imag`
 // [nz][ny][nx], device arrays of which the entry point has checked the first two for null.  The
@@ -2079,18 +2086,14 @@ inline Ifft3dPlan plan_ifft3d(const int32_t dims[3], const void* spectrum, const
   require_disjoint(&arrays, "the spectrum, values and imag overlap");
   Ifft3dPlan plan;
   for (int d = 0; d < 3; ++d) plan.twiddle[d] = fft_inverse_twiddles(dims[d]);
-  IfftArgs& args = plan.args;
-  args.nx = dims[0];
-  args.log2nx = fft_log2(dims[0]);
-  args.x_lines = static_cast<uint32_t>(cells / static_cast<uint64_t>(dims[0]));
-  args.x_group = fft_x_group(args.x_lines, dims[0]);
-  args.scale = 1.0 / static_cast<double>(cells);  // cells is a power of two: exact
-  fft_column_passes(dims, args.pass);
+  plan.args.lines = fft_lines(dims);
+  plan.args.scale = 1.0 / static_cast<double>(cells);  // cells is a power of two: exact
   return plan;
 }
 
 struct SpectrumHelmholtzPlan {
   HelmholtzArgs args{};  // no table: nothing is staged
+  uint32_t groups = 0;   // workgroups of 256 lanes, kSpectralGroupElements modes each
 };
 // The Helmholtz split of the spectra of (vx, vy, vz), each [nz][ny][nx][2]: `spectra` are read and
 // overwritten with the solenoidal part, `compressive` written.  h[d] = 1 / L_d.  The rules, in
@@ -2123,11 +2126,13 @@ inline SpectrumHelmholtzPlan plan_spectrum_helmholtz(const int32_t dims[3], cons
     plan.args.h[d] = h[d];
   }
   plan.args.n_modes = static_cast<uint32_t>(cells);
+  plan.groups = spectral_groups(cells);
   return plan;
 }
 
 struct InverseLaplacianPlan {
   InverseLaplacianArgs args{};  // no table: nothing is staged
+  uint32_t groups = 0;          // workgroups of 256 lanes, kSpectralGroupElements modes each
 };
 // `spectrum` [nz][ny][nx][2] times scale / q in place, q the shell sums' (g[d] = 1 / L_d^2), 0 at
 // q == 0.  The rules, in this order: the dims, fewer than 2^31 cells, g finite and positive, scale
@@ -2147,14 +2152,11 @@ inline InverseLaplacianPlan plan_spectrum_inverse_laplacian(const int32_t dims[3
   }
   plan.args.n_modes = static_cast<uint32_t>(cells);
   plan.args.scale = scale;
+  plan.groups = spectral_groups(cells);
   return plan;
 }
 
 // ---- isolated potential ("Isolated potential") -------------------------------
-// The workgroups of a streaming kernel that takes kSpectralGroupElements elements each.
-inline uint32_t spectral_groups(uint64_t elements) {
-  return static_cast<uint32_t>((elements + kSpectralGroupElements - 1) / kSpectralGroupElements);
-}
 struct IsolatedGreenPlan {
   IsolatedGreenArgs args{};  // no table: nothing is staged
   uint32_t groups = 0;       // workgroups of 256 lanes, kSpectralGroupElements cells each
@@ -2215,6 +2217,7 @@ inline SpectrumMultiplyPlan plan_spectrum_multiply(const int32_t* dims, const vo
 struct SpectrumBinsPlan {
   std::vector<double> edges_sq;  // n_bins + 1
   SpectrumBinsArgs args{};
+  uint32_t groups = 0;           // workgroups of 256 lanes, kSpectralGroupElements modes each
   template <class Visit>
   void visit_tables(SpectrumBinsArgs* to, Visit&& visit) const {
     visit(&to->edges_sq, edges_sq.data(), edges_sq.size());
@@ -2257,6 +2260,7 @@ inline SpectrumBinsPlan plan_spectrum_bins(const int32_t dims[3], const double g
   }
   plan.args.n_bins = n_bins;
   plan.args.n_modes = static_cast<uint32_t>(cells);
+  plan.groups = spectral_groups(cells);
   return plan;
 }
 

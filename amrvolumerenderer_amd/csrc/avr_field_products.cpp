@@ -516,7 +516,7 @@ int avr_field_fft(avr_context* ctx, const double* values_dev, const int32_t* dim
     require(values_dev != nullptr && dims != nullptr && spectrum_dev != nullptr, "null argument");
     const avr::Fft3dPlan plan = avr::plan_fft3d(dims, values_dev, spectrum_dev);
     avr::FftArgs args = plan.args;
-    stage_tables(ctx, plan, &args);
+    stage_tables(ctx, plan, &args.lines);
     args.values = values_dev;
     args.spectrum = spectrum_dev;
     return avr::launch_fft3d(args, ctx->stream);
@@ -539,7 +539,7 @@ int avr_spectrum_bins(avr_context* ctx, const double* spectrum_dev, const int32_
     args.modes = reinterpret_cast<unsigned long long*>(modes_dev);
     args.power = power_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
-    return avr::launch_spectrum_bins(args, ctx->stream);
+    return avr::launch_spectrum_bins(args, plan.groups, ctx->stream);
   });
 }
 
@@ -550,7 +550,7 @@ int avr_field_ifft(avr_context* ctx, double* spectrum_dev, const int32_t* dims, 
     require(spectrum_dev != nullptr && dims != nullptr && values_dev != nullptr, "null argument");
     const avr::Ifft3dPlan plan = avr::plan_ifft3d(dims, spectrum_dev, values_dev, imag_dev);
     avr::IfftArgs args = plan.args;
-    stage_tables(ctx, plan, &args);
+    stage_tables(ctx, plan, &args.lines);
     args.spectrum = spectrum_dev;
     args.values = values_dev;
     args.imag = imag_dev;
@@ -571,7 +571,7 @@ int avr_spectrum_helmholtz(avr_context* ctx, double* const spectra_dev[3], const
       args.spectra[d] = spectra_dev[d];
       args.compressive[d] = compressive_dev[d];
     }
-    return avr::launch_spectrum_helmholtz(args, ctx->stream);
+    return avr::launch_spectrum_helmholtz(args, plan.groups, ctx->stream);
   });
 }
 
@@ -585,7 +585,7 @@ int avr_spectrum_inverse_laplacian(avr_context* ctx, double* spectrum_dev, const
         avr::plan_spectrum_inverse_laplacian(dims, inverse_length_sq, scale);
     avr::InverseLaplacianArgs args = plan.args;
     args.spectrum = spectrum_dev;
-    return avr::launch_spectrum_inverse_laplacian(args, ctx->stream);
+    return avr::launch_spectrum_inverse_laplacian(args, plan.groups, ctx->stream);
   });
 }
 

@@ -963,14 +963,16 @@ struct RayArgs {
 int launch_rays(const RayArgs& args, bool emit, void* stream);
 int launch_ray_sums(const RayArgs& args, void* stream);
 
-// Power spectra (avr_fft.hip; DESIGN.md 7, "Power spectrum"): the forward, unnormalised 3-D
-// transform of a real f64 grid [nz][ny][nx] into an interleaved complex spectrum [nz][ny][nx][2],
-// one radix-2 pass per axis with whole lines in LDS, and the shell sums of a spectrum.
+// Power spectra (avr_fft.hip, avr_spectral.hip; DESIGN.md 7, "Power spectrum"): the forward,
+// unnormalised 3-D transform of a real f64 grid [nz][ny][nx] into an interleaved complex spectrum
+// [nz][ny][nx][2], one radix-2 pass per axis with whole lines in LDS, and the shell sums of a
+// spectrum, a streaming kernel (launched with the `groups` of its plan, as every one is).
 constexpr int kFftMaxLength = 1024;       // per axis; a power of two
 constexpr int kFftGroupElements = 2048;   // complex elements a workgroup stages (32 KiB) ...
 constexpr int kFftMinColumns = 4;         // ... but never fewer adjacent columns than this (64-byte
                                           // runs): 4 lines of 1024 are 64 KiB, the most ever staged
 constexpr int kSpectrumMaxBins = 2048;    // 20 bytes of LDS per bin
+constexpr uint32_t kSpectralGroupElements = 16384;  // cells or modes a workgroup of 256 lanes takes
 // One strided pass (y or z): `planes` planes of `columns` adjacent lines each; element e of the
 // line in column c of plane q is the complex at q * plane_stride + e * line_stride + c.  A
 // workgroup stages `group` adjacent columns, the last of a plane's `groups` only `last`.
@@ -981,14 +983,19 @@ struct FftPassDev {
   uint32_t pad_;
   uint64_t plane_stride, line_stride;  // in complex elements
 };
-struct FftArgs {
-  const double* values;      // [nz][ny][nx]
-  double* spectrum;          // [nz][ny][nx][2]
-  const double* twiddle[3];  // per axis (x, y, z): W[m] = (cos, sin)(-(2 pi m) / n), n / 2 pairs
+// The lines and passes of a 3-D transform, forward or inverse: the same cut for both.
+struct FftLinesDev {
+  const double* twiddle[3];  // per axis (x, y, z), n / 2 pairs: forward W[m] = (cos, sin)(-(2 pi m)
+                             // / n), inverse V[m] = (W[m].re, -W[m].im)
   int32_t nx, log2nx;
   uint32_t x_lines;          // ny * nz
   uint32_t x_group;          // lines a workgroup of the x pass stages
-  FftPassDev pass[2];        // y, z
+  FftPassDev pass[2];        // y, z; the inverse launches z first
+};
+struct FftArgs {
+  const double* values;      // [nz][ny][nx]
+  double* spectrum;          // [nz][ny][nx][2]
+  FftLinesDev lines;
 };
 int launch_fft3d(const FftArgs& args, void* stream);
 struct SpectrumBinsArgs {
@@ -1003,7 +1010,7 @@ struct SpectrumBinsArgs {
   double* power;             // [n_bins], added to
   unsigned long long* totals;  // (outside, nonfinite), added to
 };
-int launch_spectrum_bins(const SpectrumBinsArgs& args, void* stream);
+int launch_spectrum_bins(const SpectrumBinsArgs& args, uint32_t groups, void* stream);
 
 // Inverse transform, Helmholtz split, potential (avr_fft.hip, avr_spectral.hip; DESIGN.md 7,
 // "Inverse transform, Helmholtz split, potential"): the normalised inverse of a complex spectrum
@@ -1013,12 +1020,8 @@ struct IfftArgs {
   double* spectrum;          // [nz][ny][nx][2]; the strided passes overwrite it
   double* values;            // [nz][ny][nx]: re / (nx ny nz)
   double* imag;              // [nz][ny][nx]: im / (nx ny nz); or null
-  const double* twiddle[3];  // per axis (x, y, z): V[m] = (W[m].re, -W[m].im), n / 2 pairs
-  int32_t nx, log2nx;
-  uint32_t x_lines;          // ny * nz
-  uint32_t x_group;          // lines a workgroup of the x pass stages, as the forward x pass
   double scale;              // 1.0 / f64(nx ny nz), a power of two
-  FftPassDev pass[2];        // y, z; launched z first
+  FftLinesDev lines;         // with the inverse tables
 };
 int launch_ifft3d(const IfftArgs& args, void* stream);
 struct HelmholtzArgs {
@@ -1028,7 +1031,7 @@ struct HelmholtzArgs {
   uint32_t n_modes;          // nx * ny * nz < 2^31
   double h[3];               // 1 / L_d
 };
-int launch_spectrum_helmholtz(const HelmholtzArgs& args, void* stream);
+int launch_spectrum_helmholtz(const HelmholtzArgs& args, uint32_t groups, void* stream);
 struct InverseLaplacianArgs {
   double* spectrum;          // [nz][ny][nx][2], in place
   int32_t log2n[3];
@@ -1036,11 +1039,11 @@ struct InverseLaplacianArgs {
   double g[3];               // 1 / L_d^2
   double scale;
 };
-int launch_spectrum_inverse_laplacian(const InverseLaplacianArgs& args, void* stream);
+int launch_spectrum_inverse_laplacian(const InverseLaplacianArgs& args, uint32_t groups,
+                                      void* stream);
 
 // Isolated potential (avr_spectral.hip; DESIGN.md 7, "Isolated potential"): the open-boundary
 // Green's function on a zero-padded grid and the product of two spectra, both streaming.
-constexpr uint32_t kSpectralGroupElements = 16384;  // cells or modes a workgroup of 256 lanes takes
 struct IsolatedGreenArgs {
   double* green;             // [Pz][Py][Px], written
   int32_t log2n[3];          // x, y, z of the padded grid

@@ -270,15 +270,10 @@ class Context:
         1 / L_d^2 for d = x, y, z; edges_sq: the n + 1 squared edges (e / (2 pi))^2, strictly
         increasing from a value >= 0 ("Power spectrum").  Returns (modes, power,
         totals).  Asynchronous on the context's stream."""
-        self._check_tensor(spectrum, torch.float64, "spectrum")
-        if spectrum.ndim != 4 or spectrum.shape[3] != 2 or spectrum.numel() == 0:
-            raise ValueError("spectrum must be [nz, ny, nx, 2] with at least one mode")
-        nz, ny, nx = (int(v) for v in spectrum.shape[:3])
-        dims = np.array([nx, ny, nz], dtype=np.int32)
+        dims = self._spectrum_dims(spectrum)
         g = np.ascontiguousarray(inverse_length_sq, dtype=np.float64)
         edges = np.ascontiguousarray(edges_sq, dtype=np.float64)
-        if g.shape != (3,):
-            raise ValueError("inverse_length_sq must hold three values")
+        _require_triple(g, "inverse_length_sq")
         if edges.ndim != 1 or edges.size < 2:
             raise ValueError("edges_sq must hold at least two values")
         n = int(edges.size) - 1
@@ -328,8 +323,7 @@ class Context:
             if not np.array_equal(self._spectrum_dims(other, what), dims):
                 raise ValueError("fx, fy and fz must have one shape")
         h = np.ascontiguousarray(inverse_length, dtype=np.float64)
-        if h.shape != (3,):
-            raise ValueError("inverse_length must hold three values")
+        _require_triple(h, "inverse_length")
         compressive = tuple(torch.empty_like(fx) for _ in range(3))
         inputs = (C.c_void_p * 3)(*(f.data_ptr() for f in (fx, fy, fz)))
         outputs = (C.c_void_p * 3)(*(c.data_ptr() for c in compressive))
@@ -346,8 +340,7 @@ class Context:
         context's stream."""
         dims = self._spectrum_dims(spectrum)
         g = np.ascontiguousarray(inverse_length_sq, dtype=np.float64)
-        if g.shape != (3,):
-            raise ValueError("inverse_length_sq must hold three values")
+        _require_triple(g, "inverse_length_sq")
         _native(self, "avr_spectrum_inverse_laplacian", self._handle, _pointer(spectrum),
                 _ints(dims), _doubles(g), float(scale))
         return spectrum
@@ -364,8 +357,7 @@ class Context:
         size = np.ascontiguousarray(cell_size, dtype=np.float64)
         if dims.shape != (3,):
             raise ValueError("padded_dims must hold three values")
-        if size.shape != (3,):
-            raise ValueError("cell_size must hold three values")
+        _require_triple(size, "cell_size")
         if not ((dims >= 1) & (dims <= 1024)).all():
             raise ValueError("padded_dims must be powers of two in [1, 1024]")
         px, py, pz = (int(v) for v in dims)
@@ -714,6 +706,12 @@ def _doubles(a: np.ndarray):
 
 def _ints(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _require_triple(a: np.ndarray, name: str) -> None:
+    """ValueError, naming the argument, unless the float64 array holds (x, y, z)."""
+    if a.shape != (3,):
+        raise ValueError(f"{name} must hold three values")
 
 
 def _pointer(t: Optional[torch.Tensor]):

@@ -1,10 +1,10 @@
 """Power spectra ("Power spectrum"): what api.power_spectrum works out on the host
-around the kernels of csrc/avr_fft.hip -- the wave numbers of a grid, the default, linear and
-logarithmic edges, their squares as the bin kernel compares them, the normalisation of the shell
-sums, an .npz file -- and, for api.helmholtz and api.potential ("Inverse transform,
-Helmholtz split, potential"), the inverse lengths, the compressive fraction and their .npz files;
-for api.isolated_potential ("Isolated potential") the padding rule and its .npz file.
-numpy only; no device work."""
+around the kernels of csrc/avr_fft.hip and csrc/avr_spectral.hip -- the wave numbers of a grid,
+the default, linear and logarithmic edges, their squares as the bin kernel compares them, the
+normalisation of the shell sums, an .npz file -- and, for api.helmholtz and api.potential
+("Inverse transform, Helmholtz split, potential"), the inverse lengths, the
+compressive fraction and their .npz files; for api.isolated_potential ("Isolated
+potential") the padding rule and its .npz file.  numpy only; no device work."""
 from __future__ import annotations
 
 import math

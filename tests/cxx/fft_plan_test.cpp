@@ -107,9 +107,9 @@ void test_fft_plan() {
   {
     const int32_t dims[3] = {16, 8, 4};
     const avr::Fft3dPlan plan = avr::plan_fft3d(dims, address(kValues), address(kSpectrum));
-    const avr::FftArgs& a = plan.args;
-    expect(a.values == nullptr && a.spectrum == nullptr && a.twiddle[0] == nullptr,
-           "the plan leaves every address null");
+    const avr::FftLinesDev& a = plan.args.lines;
+    expect(plan.args.values == nullptr && plan.args.spectrum == nullptr &&
+               a.twiddle[0] == nullptr, "the plan leaves every address null");
     expect(plan.twiddle[0].size() == 16 && plan.twiddle[1].size() == 8 &&
                plan.twiddle[2].size() == 4, "one table per axis");
     expect(a.nx == 16 && a.log2nx == 4 && a.x_lines == 32 && a.x_group == 32, "the x pass");
@@ -121,7 +121,7 @@ void test_fft_plan() {
     expect(z.n == 4 && z.log2n == 2 && z.planes == 1 && z.columns == 128 && z.group == 128 &&
                z.groups == 1 && z.last == 128 && z.line_stride == 128, "the z pass");
     int visited = 0;
-    avr::FftArgs to{};
+    avr::FftLinesDev to{};
     plan.visit_tables(&to, [&](const double** where, const double* table, size_t count) {
       expect(where == &to.twiddle[visited] && table == plan.twiddle[visited].data() &&
                  count == plan.twiddle[visited].size(), "the tables are staged in axis order");
@@ -132,22 +132,25 @@ void test_fft_plan() {
   {  // the longest lines: 2 lines of 1024 along x, 4 columns of 1024 along y and z
     const int32_t dims[3] = {1024, 1024, 1024};  // 2^30 cells, the most the dims rule admits
     const avr::Fft3dPlan plan = avr::plan_fft3d(dims, address(kValues), address(kSpectrum));
-    expect(plan.args.x_lines == (1u << 20) && plan.args.x_group == 2, "x: 2 lines of 1024");
-    expect(plan.args.pass[0].planes == 1024 && plan.args.pass[0].group == 4 &&
-               plan.args.pass[0].groups == 256 && plan.args.pass[0].last == 4, "y: 4 columns");
-    expect(plan.args.pass[1].columns == (1u << 20) && plan.args.pass[1].groups == (1u << 18) &&
-               plan.args.pass[1].line_stride == (uint64_t{1} << 20), "z: 2^18 groups");
+    const avr::FftLinesDev& a = plan.args.lines;
+    expect(a.x_lines == (1u << 20) && a.x_group == 2, "x: 2 lines of 1024");
+    expect(a.pass[0].planes == 1024 && a.pass[0].group == 4 && a.pass[0].groups == 256 &&
+               a.pass[0].last == 4, "y: 4 columns");
+    expect(a.pass[1].columns == (1u << 20) && a.pass[1].groups == (1u << 18) &&
+               a.pass[1].line_stride == (uint64_t{1} << 20), "z: 2^18 groups");
   }
   {  // axes of one value, and nx below the column group
     const int32_t dims[3] = {2, 1024, 1};
     const avr::Fft3dPlan plan = avr::plan_fft3d(dims, address(kValues), address(kSpectrum));
-    expect(plan.twiddle[2].empty() && plan.args.pass[1].n == 1 && plan.args.pass[1].log2n == 0,
+    const avr::FftLinesDev& a = plan.args.lines;
+    expect(plan.twiddle[2].empty() && a.pass[1].n == 1 && a.pass[1].log2n == 0,
            "an axis of one value has no table");
-    expect(plan.args.x_group == 1024 && plan.args.pass[0].group == 2 &&
-               plan.args.pass[0].groups == 1 && plan.args.pass[0].last == 2, "two columns");
+    expect(a.x_group == 1024 && a.pass[0].group == 2 && a.pass[0].groups == 1 &&
+               a.pass[0].last == 2, "two columns");
     const int32_t one[3] = {1, 1, 1};
     const avr::Fft3dPlan least = avr::plan_fft3d(one, address(kValues), address(kSpectrum));
-    expect(least.args.x_lines == 1 && least.args.x_group == 1 && least.args.log2nx == 0, "1 cell");
+    const avr::FftLinesDev& b = least.args.lines;
+    expect(b.x_lines == 1 && b.x_group == 1 && b.log2nx == 0, "1 cell");
   }
   // the messages, and which one wins
   const int32_t wrong[][3] = {{0, 4, 4}, {4, -8, 4}, {4, 4, 3}, {2048, 4, 4}, {4, 4, 1 << 30},
@@ -185,6 +188,20 @@ void test_bins_plan() {
     expect(a.g[0] == 1.0 && a.g[1] == 0.25 && a.g[2] == 4.0, "g");
     expect(a.spectrum == nullptr && a.edges_sq == nullptr && a.modes == nullptr &&
                a.power == nullptr && a.totals == nullptr, "the plan leaves every address null");
+    expect(plan.groups == 1, "one workgroup");
+  }
+  {  // the workgroups at the group boundary: 16384 modes are one group, 32768 two
+    struct Shape {
+      int32_t dims[3];
+      uint32_t modes, groups;
+    };
+    const Shape shapes[] = {{{1, 1, 1}, 1, 1}, {{64, 16, 16}, 16384, 1}, {{64, 32, 16}, 32768, 2}};
+    for (const Shape& s : shapes) {
+      Bins bins;
+      std::memcpy(bins.dims, s.dims, sizeof(bins.dims));
+      const avr::SpectrumBinsPlan plan = bins.plan();
+      expect(plan.args.n_modes == s.modes && plan.groups == s.groups, "the launch shape");
+    }
   }
   const double inf = INFINITY, nan = NAN;
   auto spoilt = [](auto&& change) {

@@ -71,6 +71,14 @@ Split spoilt(Change&& change) {
   return split;
 }
 
+// The workgroups of a streaming kernel at the group boundary: 16384 modes are one group, 32768 two.
+struct GroupShape {
+  int32_t dims[3];
+  uint32_t modes, groups;
+};
+const GroupShape kGroupShapes[] = {{{1, 1, 1}, 1, 1}, {{64, 16, 16}, 16384, 1},
+                                   {{64, 32, 16}, 32768, 2}};
+
 void test_inverse_twiddles() {
   for (int n : {2, 8, 1024}) {
     const std::vector<double> w = avr::fft_twiddles(n), v = avr::fft_inverse_twiddles(n);
@@ -89,18 +97,34 @@ void test_x_cut() {
   expect(avr::fft_x_group(1, 1) == 1 && avr::fft_x_group(4096, 1) == 2048, "nx = 1");
   expect(avr::fft_x_group(3, 2) == 3 && avr::fft_x_group(1u << 20, 2) == 1024, "nx = 2");
   expect(avr::fft_x_group(1, 1024) == 1 && avr::fft_x_group(1u << 20, 1024) == 2, "nx = 1024");
-  const int32_t shapes[][3] = {{1, 1024, 2},       {2, 1024, 2}, {1024, 2, 1},
-                               {1024, 1024, 1024}, {16, 8, 4},   {1, 1, 1}};
+  // ... and the shared description of the lines and passes, member by member
+  const int32_t shapes[][3] = {{1, 1024, 2}, {2, 1024, 2}, {1024, 2, 1}, {1024, 1024, 1024},
+                               {16, 8, 4},   {1, 1, 1},    {8, 8, 8},    {1024, 4, 2}};
   for (const auto& dims : shapes) {
     const avr::Fft3dPlan forward = avr::plan_fft3d(dims, address(kBase), address(kBase << 1));
     const avr::Ifft3dPlan inverse =
         avr::plan_ifft3d(dims, address(kBase << 1), address(kBase), nullptr);
-    const avr::FftArgs& f = forward.args;
-    const avr::IfftArgs& i = inverse.args;
+    const avr::FftLinesDev& f = forward.args.lines;
+    const avr::FftLinesDev& i = inverse.args.lines;
     expect(i.nx == f.nx && i.log2nx == f.log2nx && i.x_lines == f.x_lines &&
                i.x_group == f.x_group, "the inverse x pass is cut as the forward one");
     expect((static_cast<uint64_t>(i.x_group) << i.log2nx) * 16 <= 64 * 1024, "a group fits 64 KiB");
     expect(std::memcmp(i.pass, f.pass, sizeof(f.pass)) == 0, "the strided passes are the same");
+    for (int which = 0; which < 2; ++which) {
+      const avr::FftPassDev &p = i.pass[which], &q = f.pass[which];
+      expect(p.n == q.n && p.log2n == q.log2n && p.planes == q.planes &&
+                 p.columns == q.columns && p.group == q.group && p.groups == q.groups &&
+                 p.last == q.last && p.plane_stride == q.plane_stride &&
+                 p.line_stride == q.line_stride, "... member by member");
+    }
+    expect(f.nx == dims[0] && f.x_lines == static_cast<uint32_t>(dims[1] * dims[2]) &&
+               f.pass[0].n == dims[1] && f.pass[1].n == dims[2], "the description is the grid's");
+    for (int d = 0; d < 3; ++d) {
+      expect(f.twiddle[d] == nullptr && i.twiddle[d] == nullptr, "no address is set");
+      expect(forward.twiddle[d] == avr::fft_twiddles(dims[d]) &&
+                 inverse.twiddle[d] == avr::fft_inverse_twiddles(dims[d]),
+             "the forward tables W, the inverse tables V");
+    }
   }
 }
 
@@ -109,17 +133,19 @@ void test_ifft_plan() {
     const int32_t dims[3] = {16, 8, 4};
     const avr::Ifft3dPlan plan =
         avr::plan_ifft3d(dims, address(kBase), address(kBase + 8192), address(kBase + 12288));
-    const avr::IfftArgs& a = plan.args;
-    expect(a.spectrum == nullptr && a.values == nullptr && a.imag == nullptr &&
-               a.twiddle[0] == nullptr, "the plan leaves every address null");
+    const avr::FftLinesDev& a = plan.args.lines;
+    expect(plan.args.spectrum == nullptr && plan.args.values == nullptr &&
+               plan.args.imag == nullptr && a.twiddle[0] == nullptr,
+           "the plan leaves every address null");
     expect(plan.twiddle[0] == avr::fft_inverse_twiddles(16) &&
                plan.twiddle[1] == avr::fft_inverse_twiddles(8) &&
                plan.twiddle[2] == avr::fft_inverse_twiddles(4), "one inverse table per axis");
-    expect(a.scale == 1.0 / 512.0 && a.x_lines == 32 && a.x_group == 32, "the scale and x pass");
+    expect(plan.args.scale == 1.0 / 512.0 && a.x_lines == 32 && a.x_group == 32,
+           "the scale and x pass");
     expect(a.pass[0].n == 8 && a.pass[0].line_stride == 16 && a.pass[1].n == 4 &&
                a.pass[1].line_stride == 128, "the y and z passes");
     int visited = 0;
-    avr::IfftArgs to{};
+    avr::FftLinesDev to{};
     plan.visit_tables(&to, [&](const double** where, const double* table, size_t count) {
       expect(where == &to.twiddle[visited] && table == plan.twiddle[visited].data() &&
                  count == plan.twiddle[visited].size(), "the tables are staged in axis order");
@@ -131,8 +157,9 @@ void test_ifft_plan() {
                std::ldexp(1.0, -30), "1 / 2^30");
     const int32_t one[3] = {1, 1, 1};
     const avr::Ifft3dPlan least = avr::plan_ifft3d(one, address(kBase), address(kBase + 16), nullptr);
-    expect(least.args.scale == 1.0 && least.args.x_group == 1 && least.twiddle[0].empty() &&
-               least.args.pass[0].n == 1 && least.args.pass[1].n == 1, "one cell");
+    expect(least.args.scale == 1.0 && least.args.lines.x_group == 1 &&
+               least.twiddle[0].empty() && least.args.lines.pass[0].n == 1 &&
+               least.args.lines.pass[1].n == 1, "one cell");
   }
   // the dims before the overlap
   const int32_t wrong[][3] = {{0, 4, 4}, {4, -8, 4}, {4, 4, 3}, {2048, 4, 4}, {4, 4, 1 << 30}};
@@ -172,11 +199,22 @@ void test_helmholtz_plan() {
     const Split split;
     const avr::HelmholtzArgs a = split.plan().args;
     expect(a.log2n[0] == 3 && a.log2n[1] == 2 && a.log2n[2] == 1 && a.n_modes == 64, "the dims");
+    expect(split.plan().groups == 1, "one workgroup");
     expect(a.h[0] == 1.0 && a.h[1] == 0.5 && a.h[2] == 2.0, "h");
     for (int d = 0; d < 3; ++d) {
       expect(a.spectra[d] == nullptr && a.compressive[d] == nullptr,
              "the plan leaves every address null");
     }
+  }
+  for (const GroupShape& s : kGroupShapes) {
+    const avr::SpectrumHelmholtzPlan plan = spoilt([&](Split& split) {
+      std::memcpy(split.dims, s.dims, sizeof(split.dims));
+      for (uint64_t d = 0; d < 3; ++d) {  // 32768 modes are 512 KiB a spectrum
+        split.spectra[d] = address(kBase + (d << 20));
+        split.compressive[d] = address(kBase + ((d + 3) << 20));
+      }
+    }).plan();
+    expect(plan.args.n_modes == s.modes && plan.groups == s.groups, "the launch shape");
   }
   const double inf = INFINITY, nan = NAN;
   for (int d = 0; d < 3; ++d) {
@@ -273,6 +311,10 @@ void test_inverse_laplacian_plan() {
     expect(std::memcmp(&a.scale, &scale, sizeof(scale)) == 0 && a.n_modes == 64 &&
                a.log2n[0] == 3 && a.log2n[1] == 2 && a.log2n[2] == 1 && a.g[0] == 1.0 &&
                a.g[1] == 0.25 && a.g[2] == 4.0 && a.spectrum == nullptr, "the arguments");
+  }
+  for (const GroupShape& s : kGroupShapes) {
+    const avr::InverseLaplacianPlan plan = avr::plan_spectrum_inverse_laplacian(s.dims, g, 1.0);
+    expect(plan.args.n_modes == s.modes && plan.groups == s.groups, "the launch shape");
   }
   for (double bad : {0.0, -1.0, inf, nan}) {
     for (int d = 0; d < 3; ++d) {
