@@ -2,8 +2,9 @@
 // a plain C++ program, built with AddressSanitizer and UBSan and without HIP: every refusal
 // message and which one wins when several rules are broken, the 1024, 2^31 and 2048 limits
 // (reached with made-up addresses: nothing is allocated or read), the overlap rules to the byte,
-// the passes' strides and column groups with their last, partial group, and the twiddle table
-// against cos and sin.  Prints "ok".
+// the passes' strides and column groups with their last, partial group, the launch shapes of the
+// grids that tests/test_fft_lengths*.py transform (lines of 64 to 1024 in every pass, the two
+// that stage 64 KiB among them), and the twiddle table against cos and sin.  Prints "ok".
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -178,6 +179,74 @@ void test_fft_plan() {
   avr::plan_fft3d(dims, address(kValues), address(kValues - 1024));
 }
 
+// The shapes of tests/test_fft_lengths.py and tests/test_fft_lengths_gpu.py, written out by hand
+// from kFftGroupElements = 2048 and kFftMinColumns = 4: per length N one grid whose x pass, one
+// whose y pass and one whose z pass takes lines of N in two full groups (the y ones in two planes),
+// and a cube.  If this fails because the group constants changed, choose those tests' shapes again
+// (ROLES in test_fft_lengths.py) so that they keep what their comments say, then these values.
+void test_length_shapes() {
+  struct Pass {
+    uint32_t group, groups, last, planes;
+  };
+  struct Want {
+    int32_t dims[3];  // (nx, ny, nz)
+    uint32_t x_lines, x_group;
+    Pass y, z;
+  };
+  const Want cases[] = {
+      // N = 64
+      {{64, 64, 1}, 64, 32, {32, 2, 32, 1}, {2048, 2, 2048, 1}},
+      {{64, 64, 2}, 128, 32, {32, 2, 32, 2}, {1024, 4, 1024, 1}},
+      {{32, 2, 64}, 128, 64, {32, 1, 32, 64}, {32, 2, 32, 1}},
+      // N = 128
+      {{128, 32, 1}, 32, 16, {64, 2, 64, 1}, {2048, 2, 2048, 1}},
+      {{32, 128, 2}, 256, 64, {16, 2, 16, 2}, {1024, 4, 1024, 1}},
+      {{16, 2, 128}, 256, 128, {16, 1, 16, 128}, {16, 2, 16, 1}},
+      // N = 256
+      {{256, 16, 1}, 16, 8, {128, 2, 128, 1}, {2048, 2, 2048, 1}},
+      {{16, 256, 2}, 512, 128, {8, 2, 8, 2}, {1024, 4, 1024, 1}},
+      {{8, 2, 256}, 512, 256, {8, 1, 8, 256}, {8, 2, 8, 1}},
+      // N = 512
+      {{512, 8, 1}, 8, 4, {256, 2, 256, 1}, {2048, 2, 2048, 1}},
+      {{8, 512, 2}, 1024, 256, {4, 2, 4, 2}, {1024, 4, 1024, 1}},
+      {{4, 2, 512}, 1024, 512, {4, 1, 4, 512}, {4, 2, 4, 1}},
+      // N = 1024
+      {{1024, 4, 1}, 4, 2, {512, 2, 512, 1}, {2048, 2, 2048, 1}},
+      {{8, 1024, 2}, 2048, 256, {4, 2, 4, 2}, {1024, 8, 1024, 1}},
+      {{4, 2, 1024}, 2048, 512, {4, 1, 4, 1024}, {4, 2, 4, 1}},
+      // the cube
+      {{64, 64, 64}, 4096, 32, {32, 2, 32, 64}, {32, 128, 32, 1}},
+  };
+  const std::string again = "; the group constants changed: choose the shapes of "
+                            "tests/test_fft_lengths.py again";
+  for (const Want& want : cases) {
+    const std::string name = std::to_string(want.dims[0]) + " x " + std::to_string(want.dims[1]) +
+                             " x " + std::to_string(want.dims[2]);
+    const avr::FftLinesDev a = avr::fft_lines(want.dims);
+    expect(a.x_lines == want.x_lines && a.x_group == want.x_group,
+           "the x pass of " + name + again);
+    expect((static_cast<uint64_t>(a.x_group) << a.log2nx) * 16 <= 32 * 1024,
+           "the x pass of " + name + " stages at most 32 KiB");
+    const Pass* passes[2] = {&want.y, &want.z};
+    for (int which = 0; which < 2; ++which) {
+      const avr::FftPassDev& got = a.pass[which];
+      const Pass& p = *passes[which];
+      expect(got.group == p.group && got.groups == p.groups && got.last == p.last &&
+                 got.planes == p.planes,
+             std::string(which == 0 ? "the y pass of " : "the z pass of ") + name + again);
+      expect(got.n == 1 || (static_cast<uint64_t>(got.group) << got.log2n) * 16 <= 64 * 1024,
+             "a group of " + name + " fits 64 KiB");
+    }
+  }
+  // the two launches that ask for all of the 64 KiB: 4 columns of 1024
+  const int32_t along_y[3] = {8, 1024, 2}, along_z[3] = {4, 2, 1024};
+  const avr::FftPassDev y = avr::fft_lines(along_y).pass[0], z = avr::fft_lines(along_z).pass[1];
+  expect((static_cast<uint64_t>(y.group) << y.log2n) * 16 == 65536,
+         "the y pass of 8 x 1024 x 2 stages exactly 65536 bytes" + again);
+  expect((static_cast<uint64_t>(z.group) << z.log2n) * 16 == 65536,
+         "the z pass of 4 x 2 x 1024 stages exactly 65536 bytes" + again);
+}
+
 void test_bins_plan() {
   {
     const Bins bins;
@@ -276,6 +345,7 @@ int main() {
   test_twiddles();
   test_column_groups();
   test_fft_plan();
+  test_length_shapes();
   test_bins_plan();
   std::printf("ok\n");
   return 0;

@@ -1,7 +1,10 @@
 """The definitions of DESIGN.md 7, "Power spectrum", in numpy: the twiddle table, the radix-2
 transform of one line with its loops in the stated order, the same butterflies on many lines at
 once, the 3-D transform (x, then y, then z) and the shell sums.  numpy's elementwise float64
-arithmetic rounds every product and sum on its own, which is what the kernels do."""
+arithmetic rounds every product and sum on its own, which is what the kernels do.  Apart from that
+restatement, and sharing nothing with it: the transform and its inverse by their definition in
+long double (exact_fft3d, exact_ifft3d) and the closed forms of one cell and of one mode
+(delta_spectrum, plane_wave), what the restatement and the kernels are held to."""
 import math
 
 import numpy as np
@@ -78,6 +81,116 @@ def fft3d(values):
         re, im = fft_lines(re, im)
         re, im = np.moveaxis(re, -1, axis), np.moveaxis(im, -1, axis)
     return np.ascontiguousarray(np.stack([re, im], axis=-1))
+
+
+# ---- the transform by its definition, in long double -------------------------------------------
+# None of what follows shares code or algorithm with the radix-2 restatement above: a dense matrix
+# per axis, its phases from exact integer indices, everything in numpy.longdouble.
+
+def require_long_double():
+    """The long-double helpers are a reference only where long double is wider than float64."""
+    eps = float(np.finfo(np.longdouble).eps)
+    assert eps <= 2.0 ** -63, (
+        f"numpy.longdouble has eps = {eps:g} here, not the 2^-63 or less of an extended format: "
+        "the long-double reference would be no more precise than what it checks")
+
+
+def long_pi():
+    return np.longdouble(4) * np.arctan(np.longdouble(1))
+
+
+def unit_roots(n):
+    """(cos t, sin t) of t = -(2 pi m) / n for m in [0, n), long double [n] each."""
+    require_long_double()
+    m = np.arange(n, dtype=np.int64).astype(np.longdouble)
+    theta = -(2 * long_pi() * m) / np.longdouble(n)
+    return np.cos(theta), np.sin(theta)
+
+
+_DFT = {}
+
+
+def dft_matrix(n):
+    """(C, S) long double [n, n]: exp(-2 pi i k j / n) = C[k, j] + i S[k, j], the phase index
+    (k j) mod n as an exact integer.  Made once per n; read-only."""
+    if n not in _DFT:
+        c, s = unit_roots(n)
+        k = np.arange(n, dtype=np.int64)
+        index = (k[:, None] * k[None, :]) % n
+        big_c, big_s = c[index], s[index]
+        big_c.setflags(write=False)
+        big_s.setflags(write=False)
+        _DFT[n] = (big_c, big_s)
+    return _DFT[n]
+
+
+def _dft_axes(re, im, sign):
+    """The separable DFT of (re, im) long double [nz, ny, nx] over its three axes by matrix
+    products; sign = 1: exp(-i ...), sign = -1: exp(+i ...).  Unnormalised."""
+    for axis in range(3):
+        n = re.shape[axis]
+        if n == 1:
+            continue
+        c, s = dft_matrix(n)                            # symmetric
+        re, im = np.moveaxis(re, axis, -1), np.moveaxis(im, axis, -1)
+        a, b = re @ c, sign * (re @ s)
+        if im.any():                                    # not on a real grid's first axis
+            a, b = a - sign * (im @ s), b + im @ c
+        re, im = np.moveaxis(a, -1, axis), np.moveaxis(b, -1, axis)
+    return np.ascontiguousarray(re), np.ascontiguousarray(im)
+
+
+def exact_fft3d(values):
+    """Real [nz, ny, nx] -> (re, im) long double [nz, ny, nx]: F[kz, ky, kx] = sum over (z, y, x)
+    of v[z, y, x] exp(-2 pi i (kx x / nx + ky y / ny + kz z / nz)), the forward, unnormalised
+    transform by its definition."""
+    require_long_double()
+    re = np.asarray(values, dtype=np.float64).astype(np.longdouble)
+    return _dft_axes(re, np.zeros_like(re), 1)
+
+
+def exact_ifft3d(re, im):
+    """(re, im) [nz, ny, nx] -> (re, im) long double: the inverse with exp(+...) and 1 / Ntot."""
+    require_long_double()
+    re = np.asarray(re, dtype=np.float64).astype(np.longdouble)
+    im = np.asarray(im, dtype=np.float64).astype(np.longdouble)
+    re, im = _dft_axes(re, im, -1)
+    cells = np.longdouble(re.size)
+    return re / cells, im / cells
+
+
+def _phase_product(shape, at, sign):
+    """prod_d exp(-sign 2 pi i k_d at_d / n_d) over the grid, (re, im) long double [nz, ny, nx]:
+    one vector of n_d phases per axis, multiplied out."""
+    re = np.ones((1, 1, 1), dtype=np.longdouble)
+    im = np.zeros((1, 1, 1), dtype=np.longdouble)
+    for axis, (n, x0) in enumerate(zip(shape, at)):
+        assert 0 <= int(x0) < n
+        c, s = unit_roots(n)
+        index = (np.arange(n, dtype=np.int64) * int(x0)) % n
+        where = [1, 1, 1]
+        where[axis] = n
+        pr, pi = c[index].reshape(where), (sign * s[index]).reshape(where)
+        re, im = re * pr - im * pi, re * pi + im * pr
+    return re, im
+
+
+def delta_spectrum(shape, at, amplitude):
+    """The transform of `amplitude` in the cell at = (z0, y0, x0) of a grid of zeros, in closed
+    form: A exp(-2 pi i (kx x0 / nx + ky y0 / ny + kz z0 / nz)), (re, im) long double."""
+    require_long_double()
+    re, im = _phase_product(shape, at, 1)
+    return np.longdouble(amplitude) * re, np.longdouble(amplitude) * im
+
+
+def plane_wave(shape, mode, amplitude):
+    """The mirror: the inverse transform of a spectrum that holds (amplitude, 0) in the mode
+    (kz0, ky0, kx0) and zeros elsewhere, (A / Ntot) exp(+2 pi i (kx0 x / nx + ...)), (re, im)
+    long double."""
+    require_long_double()
+    re, im = _phase_product(shape, mode, -1)
+    scale = np.longdouble(amplitude) / np.longdouble(int(np.prod(shape)))
+    return scale * re, scale * im
 
 
 def signed_modes(n):

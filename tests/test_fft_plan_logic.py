@@ -1,8 +1,9 @@
 """CPU test of the host plans of the power spectra (csrc/avr_field_plans.h: plan_fft3d,
 plan_spectrum_bins); no GPU call.  tests/cxx/fft_plan_test.cpp, built here with AddressSanitizer
 and UBSan, checks every refusal message and which one wins, the 1024, 2^31 and 2048 limits, the
-overlap rules to the byte, the passes' strides and column groups with a last, partial group, and
-the twiddle table for n = 2, 8 and 1024 against cos and sin."""
+overlap rules to the byte, the passes' strides and column groups with a last, partial group, the
+launch shapes of the sixteen grids of test_fft_lengths.py written out by hand (with the two that
+stage exactly 64 KiB), and the twiddle table for n = 2, 8 and 1024 against cos and sin."""
 import os
 import subprocess
 
