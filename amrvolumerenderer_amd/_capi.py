@@ -250,6 +250,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_double), C.c_int, _vp, _vp, _vp, _vp]),
     "avr_scene_covering_grid": (C.c_int, [_vp, _vp, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                           C.c_double, _vp, _vp, _vp]),
+    "avr_scene_grid_field": (C.c_int, [_vp, _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
+                                       C.c_int, C.c_int, C.c_double, _vp]),
     "avr_fft_twiddles": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "avr_field_fft": (C.c_int, [_vp, _vp, _ip, _vp]),
     "avr_spectrum_bins": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -23,6 +23,8 @@ from .derive import (DerivedProgram, add_field, compile_expression, derived_fiel
                      evaluate_program, remove_field)
 from .clumps import add_clump_field, clump_fields, remove_clump_field, threshold_ladder
 from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
+from .gridfields import (add_array_field, add_helmholtz_field, add_potential_field, grid_fields,
+                         remove_grid_field)
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
 
@@ -377,7 +379,7 @@ def clumps(plotfile: str, variable: str, lower: float = -math.inf, upper: float 
     """The clumps of a plotfile's variable ("Clumps"), on cuda:0: the connected
     components of the uncovered cells of the loaded levels whose raw value lies in [lower, upper],
     with their sizes.  variable and every name of fields is a stored variable or a registered
-    derived, gradient or clump field.  Returns a dict: n (the number of clumps, numbered 1..n by
+    derived, gradient, clump or grid field.  Returns a dict: n (the number of clumps, numbered 1..n by
     smallest cell ordinal; entry c - 1 of every array belongs to clump c), cells_by_level int64
     [L, n], cells int64 [n], volume float64 [n] = sum_l vol[l] * f64(cells[l]) (level ascending
     from +0.0), integrals {name: float64 [n]} = sum_l vol[l] * sums[l], the volume integral of
@@ -878,7 +880,7 @@ def isosurface(plotfile: str, variable: str, value: float, fields: Sequence[str]
                min_level: int = 0, max_level: int = -1, output: Optional[str] = None) -> dict:
     """The isosurface variable == value of a plotfile ("Isosurface"), on cuda:0, over
     the uncovered cells of the loaded levels.  variable and every name of fields is a stored
-    variable or a registered derived, gradient or clump field.  Returns a dict: n (triangles),
+    variable or a registered derived, gradient, clump or grid field.  Returns a dict: n (triangles),
     vertices float64 [n, 3, 3] in the plotfile's physical units, the normal (v1 - v0) x (v2 - v0)
     pointing to the variable < value side, level uint8 [n] (the level of the cube a triangle came
     from), area float64 [n] = 0.5 |cross|, total_area (math.fsum), samples {name: float64 [n, 3]}
@@ -970,7 +972,7 @@ def streamlines(plotfile: str,
     the uncovered cells of the loaded levels: classical RK4 along the unit vector of the three
     variables, trilinear between cell centres and piecewise constant in the one-cell layer next to
     a domain face, a hole or a finer region.  variables and every name of fields is a stored
-    variable or a registered derived, gradient or clump field; seeds: [n, 3] in the plotfile's
+    variable or a registered derived, gradient, clump or grid field; seeds: [n, 3] in the plotfile's
     physical units; direction "forward", "backward" or "both" (a backward and a forward call,
     joined as the backward line reversed, then the forward line, the seed kept once).  Returns a
     dict: n (lines), lines (a list of float64 [count_i, 3]; empty for a seed outside the loaded
@@ -1200,7 +1202,7 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     grid"), on cuda:0: piecewise constant where the loaded data is coarser than `level`, the
     volume-weighted mean of the leaves where it is finer, fill where no loaded level has a cell.
     level: 0 .. the plotfile's finest level, by default the finest loaded one.  fields: stored
-    variables or registered derived, gradient or clump fields; by default the plotfile's first
+    variables or registered derived, gradient, clump or grid fields; by default the plotfile's first
     variable.  region = ((ilo, jlo, klo), (ihi, jhi, khi)), inclusive level-`level` indices, or
     left_edge / right_edge in the plotfile's physical units (the cells whose centres lie in
     [left_edge, right_edge); grids.index_region), not both; by default the whole domain.  Either
@@ -1233,6 +1235,132 @@ def covering_grid(plotfile: str, level: Optional[int] = None, fields: Sequence[s
     if output:
         grids.save_npz(result, output)
     return result
+
+
+# ---- grid fields ("Grid fields") -----------------------------------------------------
+
+def grid_scene(ctx, geometry: "SceneGeometry", grid, level: int, lo, cell_sizes, prob_lo,
+               ref_ratio, interpolation: str = "constant", periodic: bool = False,
+               fill: float = math.nan, rank: int = 0, n_ranks: int = 1, process_group=None,
+               log_scale_input: bool = False, normalize_to_data_range: bool = True):
+    """A uniform grid written back onto the cells of a scene ("Grid fields"), the
+    inverse of covering_grid_scene: grid is a numpy or torch float64 [nz, ny, nx] array of the
+    level-`level` cells from the index lo on (what covering_grid_scene, a potential or a Helmholtz
+    component is); geometry is any loaded scene, whose boxes the result has.  A cell of `level`
+    gets the grid's value with its bits kept; a finer cell the value of the grid cell that holds
+    it ("constant") or the trilinear interpolation between the grid's cell centres ("linear";
+    past the region's faces the grid is wrapped with periodic and clamped without); a coarser
+    cell the mean of the grid cells inside it; a cell the grid does not reach gets fill.
+    cell_sizes, prob_lo and ref_ratio as covering_grid_scene takes them.  Returns (SceneGeometry,
+    outside, partial): the cells that got fill, and the coarser cells only part of which the grid
+    covers.  The output is allocated as derive_scene's is, and statistics and the scalar transform
+    come from build_scene_geometry with the caller's flags.  Every box of the scene must be on
+    this rank: with n_ranks > 1, or fewer local boxes than boxes, NotImplementedError is raised
+    before any device work."""
+    import numpy as np
+    import torch
+    from . import gridfields
+    if interpolation not in gridfields.INTERPOLATIONS:
+        raise ValueError('interpolation must be "constant" or "linear"')
+    level = int(level)
+    lo = tuple(int(v) for v in lo)
+    if len(lo) != 3:
+        raise ValueError("lo must hold three values")
+    if not isinstance(grid, torch.Tensor):
+        grid = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float64))
+    if grid.ndim != 3 or grid.numel() == 0 or grid.dtype != torch.float64:
+        raise ValueError("grid must be a float64 [nz, ny, nx] array with at least one cell")
+    _require_one_rank(geometry, n_ranks, "a grid field needs every box of the scene on one rank: "
+                      "the grid is not shared between ranks")
+    if not 0 <= level < len(list(cell_sizes)):
+        raise ValueError("level must lie in [0, the number of cell_sizes)")
+    sizes, ratios, index = _level_setup(geometry, geometry.local_boxes, cell_sizes, prob_lo,
+                                        ref_ratio)
+    grid = grid.to(ctx.device).contiguous()
+    written = _blank_like(ctx, geometry, rank)
+    with _native_scenes(ctx, [written]) as (out,):
+        totals = out.grid_field(grid, level, lo, index, ratios,
+                                gridfields.INTERPOLATIONS.index(interpolation), bool(periodic),
+                                float(fill))
+        ctx.synchronize()
+        outside, partial = (int(v) for v in totals.cpu().tolist())
+    return _computed_scene(ctx, written, log_scale_input, normalize_to_data_range, process_group,
+                           n_ranks), outside, partial
+
+
+def _grid_product_device(ctx, entry: dict, inputs, level: int, lo, dims, cell_sizes, prob_lo,
+                         ref_ratio, shared: dict, n_ranks: int):
+    """The grid of a registered potential or Helmholtz field (gridfields.py) on the device, from
+    the loaded scenes of its inputs.  shared: what the grid fields of one call have computed so
+    far, by product -- a potential; the projected spectra of a velocity field, and every component
+    transformed back from them (a transformed spectrum is used up, so each is transformed once)."""
+    from . import spectra
+    isolated = entry["kind"] == "potential" and entry["boundary"] == "isolated"
+    first = inputs[0]
+    level, lo, dims, size = _scene_grid_arguments(
+        first, level, lo, dims, cell_sizes, n_ranks, "a grid field",
+        spectra.check_isolated_dims if isolated else spectra.check_dims)
+    for other in inputs[1:]:
+        if len(other.local_boxes) != len(first.local_boxes):
+            raise ValueError("the velocity components must be scenes over the same boxes")
+    sizes, ratios, index = _level_setup(first, first.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    where, fill = (level, lo, dims), entry["fill"]
+    if entry["kind"] == "potential":
+        key = ("potential", entry["of"], entry["boundary"], entry["constant"],
+               entry["self_term"], where, repr(fill))       # repr: a NaN equals itself
+        if key not in shared:
+            with _native_scenes(ctx, [first]) as (field,):
+                if isolated:
+                    scale, self_value = _isolated_scale(entry["constant"], entry["self_term"], size)
+                    shared[key], _, _ = _isolated_potential_device(
+                        ctx, field, level, lo, dims, index, ratios, size, scale, self_value, fill)
+                else:
+                    scale = -(entry["constant"] / (4.0 * math.pi * math.pi))
+                    shared[key], _, _ = _potential_device(
+                        ctx, field, level, lo, dims, index, ratios,
+                        spectra.inverse_length_sq(dims, size), scale, fill)
+                ctx.synchronize()
+        return shared[key]
+    split = ("helmholtz", entry["velocity"], where, repr(fill))
+    if split not in shared:
+        with _native_scenes(ctx, inputs) as fields:
+            shared[split], _ = _helmholtz_spectra_device(
+                ctx, fields, level, lo, dims, index, ratios, spectra.inverse_length(dims, size),
+                fill)
+            ctx.synchronize()
+    wanted = (entry["part"], entry["component"])
+    if split + wanted not in shared:
+        shared[split + wanted] = _helmholtz_grids_device(ctx, shared[split], [wanted])[0][wanted]
+    return shared[split + wanted]
+
+
+def _grid_field_scene(ctx, plotfile: str, entry: dict, inputs, geometry: "SceneGeometry",
+                      shared: dict, min_level: int, max_level: int, rank: int, n_ranks: int,
+                      process_group, log_scale_input: bool, normalize_to_data_range: bool):
+    """The scene of a registered grid field (gridfields.py): its grid -- the caller's array, or
+    the product computed from the loaded scenes `inputs`, which stays on the device -- written
+    onto the boxes of `geometry` by grid_scene.  The region and the level follow _plotfile_grid's
+    rules (level None: the call's finest loaded level) with the product's own rule on dims."""
+    from . import plotfile as pf
+    from . import spectra
+    if entry["kind"] == "array":
+        header = pf.PlotFileData(plotfile)
+        level, lo, grid = entry["level"], entry["lo"], entry["array"]
+        if level > header.finest_level:
+            raise ValueError(f"level must lie in [0, {header.finest_level}], the plotfile's levels")
+        arguments = _grid_arguments(header, geometry, level, lo, None)
+    else:
+        isolated = entry["kind"] == "potential" and entry["boundary"] == "isolated"
+        header, level, lo, dims = _plotfile_grid(
+            plotfile, entry["level"], entry["region"], entry["left_edge"], entry["right_edge"],
+            min_level, max_level, spectra.check_isolated_dims if isolated else spectra.check_dims)
+        arguments = _grid_arguments(header, geometry, level, lo, dims)
+        grid = _grid_product_device(ctx, entry, inputs, *arguments, shared, n_ranks)
+    _, _, _, cell_sizes, prob_lo, ref_ratio = arguments
+    scene, _, _ = grid_scene(ctx, geometry, grid, level, lo, cell_sizes, prob_lo, ref_ratio,
+                             entry["interpolation"], entry["periodic"], entry["outside"], rank,
+                             n_ranks, process_group, log_scale_input, normalize_to_data_range)
+    return scene
 
 
 # ---- power spectra (DESIGN.md 7, "Power spectrum") ------------------------------------------------
@@ -1315,6 +1443,73 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
 
 # ---- inverse transform, Helmholtz split, potential -----------------------------------
 
+# The device parts of the grid products whose results are grids: they return device tensors, so
+# that helmholtz_scene, potential_scene and isolated_potential_scene (which copy them to the host)
+# and the grid fields (which hand them to grid_scene) run the same steps.
+
+def _helmholtz_spectra_device(ctx, fields, level, lo, dims, index, ratios, inverse_length, fill):
+    """({part: three spectra}, absent): the covering grids of three native scenes, their
+    transforms and the split into the solenoidal and the compressive part."""
+    from . import spectra
+    transformed, absent = [], 0
+    for field in fields:
+        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+        transformed.append(ctx.fft3d(values))
+    return dict(zip(spectra.PARTS, ctx.helmholtz_split(*transformed, inverse_length))), absent
+
+
+def _helmholtz_grids_device(ctx, parts, wanted):
+    """({(part, component): grid}, the largest |imaginary part| as a 0-d tensor): the inverse
+    transforms of the spectra `wanted` names, in that order, and of no other; a transformed
+    spectrum is used up."""
+    import torch
+    worst = torch.zeros((), dtype=torch.float64, device=ctx.device)
+    found = {}
+    for part, component in wanted:
+        real, imag = ctx.ifft3d(parts[part][component], with_imag=True)
+        # torch.maximum lets a NaN through, as the largest |imag| of such a grid is
+        worst = torch.maximum(worst, imag.abs().max())
+        found[(part, component)] = real
+    return found, worst
+
+
+def _potential_device(ctx, field, level, lo, dims, index, ratios, inverse_length_sq, scale, fill):
+    """(potential, the largest |imaginary part| as a 0-d tensor, absent) of a native scene."""
+    values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+    spectrum = ctx.inverse_laplacian(ctx.fft3d(values), inverse_length_sq, scale)
+    real, imag = ctx.ifft3d(spectrum, with_imag=True)
+    return real, imag.abs().max(), absent
+
+
+def _isolated_potential_device(ctx, field, level, lo, dims, index, ratios, size, scale,
+                               self_value, fill):
+    """(potential, the largest |imaginary part| in the region as a 0-d tensor, absent) of a
+    native scene, by the zero-padded convolution."""
+    import torch
+    from . import spectra
+    padded, (nx, ny, nz) = spectra.padded_dims(dims), dims
+    values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+    # every tensor is dropped as soon as the next step has read it: at 512^3 the padded grids
+    # would otherwise add up to some 70 GB
+    grid = torch.zeros(padded[::-1], dtype=torch.float64, device=ctx.device)
+    grid[:nz, :ny, :nx] = values
+    del values
+    spectrum = ctx.fft3d(grid)
+    del grid
+    green = ctx.isolated_green(padded, size, scale, self_value)
+    kernel = ctx.fft3d(green)
+    del green
+    ctx.spectrum_multiply(spectrum, kernel)
+    del kernel
+    real, imag = ctx.ifft3d(spectrum, with_imag=True)
+    del spectrum
+    worst = imag[:nz, :ny, :nx].abs().max()
+    del imag
+    potential = real[:nz, :ny, :nx].contiguous()
+    del real
+    return potential, worst, absent
+
+
 def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeometry",
                     level: int, lo, dims, cell_sizes, prob_lo, ref_ratio, edges=None,
                     fill: Optional[float] = None, grids: bool = True, rank: int = 0,
@@ -1350,11 +1545,8 @@ def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeo
     sizes, ratios, index = _level_setup(vx, vx.local_boxes, cell_sizes, prob_lo, ref_ratio)
     found = {}
     with _native_scenes(ctx, [vx, vy, vz]) as fields:
-        transformed, absent = [], 0
-        for field in fields:
-            values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
-            transformed.append(ctx.fft3d(values))
-        parts = dict(zip(spectra.PARTS, ctx.helmholtz_split(*transformed, h)))
+        parts, absent = _helmholtz_spectra_device(ctx, fields, level, lo, dims, index, ratios, h,
+                                                  fill)
         binned = {}
         for part, three in parts.items():
             out = None
@@ -1362,14 +1554,9 @@ def helmholtz_scene(ctx, vx: "SceneGeometry", vy: "SceneGeometry", vz: "SceneGeo
                 out = ctx.spectrum_bins(spectrum, g, edges_sq, out)
             binned[part] = out
         if grids:
-            worst = torch.zeros((), dtype=torch.float64, device=ctx.device)
-            for part, three in parts.items():
-                found[part] = []
-                for spectrum in three:
-                    real, imag = ctx.ifft3d(spectrum, with_imag=True)
-                    # torch.maximum lets a NaN through, as the largest |imag| of such a grid is
-                    worst = torch.maximum(worst, imag.abs().max())
-                    found[part].append(real)
+            wanted = [(part, c) for part in parts for c in range(3)]
+            real, worst = _helmholtz_grids_device(ctx, parts, wanted)
+            found = {part: [real[(part, c)] for c in range(3)] for part in parts}
         ctx.synchronize()
         binned = {part: tuple(t.cpu().numpy() for t in out) for part, out in binned.items()}
         if grids:
@@ -1453,10 +1640,8 @@ def potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_size
     scale = -(constant / (4.0 * math.pi * math.pi))
     sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
     with _native_scenes(ctx, [scene]) as (field,):
-        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
-        spectrum = ctx.inverse_laplacian(ctx.fft3d(values), g, scale)
-        real, imag = ctx.ifft3d(spectrum, with_imag=True)
-        worst = imag.abs().max()
+        real, worst, absent = _potential_device(ctx, field, level, lo, dims, index, ratios, g,
+                                                scale, fill)
         ctx.synchronize()
         return {"potential": real.cpu().numpy(), "imag_max": float(worst.item()),
                 "absent": absent}
@@ -1502,6 +1687,13 @@ def _isolated_constants(constant, self_term) -> Tuple[float, float]:
     return constant, self_term
 
 
+def _isolated_scale(constant: float, self_term: float, size) -> Tuple[float, float]:
+    """(scale, G(0)) of the isolated Green's function on cells of `size`."""
+    volume = (size[0] * size[1]) * size[2]
+    scale = -((constant * volume) / (4.0 * math.pi))
+    return scale, scale * self_term
+
+
 def isolated_potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes,
                              prob_lo, ref_ratio, constant: float = 1.0, self_term: float = 0.0,
                              fill: Optional[float] = None, rank: int = 0,
@@ -1523,31 +1715,12 @@ def isolated_potential_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, 
     level, lo, dims, size = _scene_grid_arguments(scene, level, lo, dims, cell_sizes, n_ranks,
                                                   "an isolated potential",
                                                   spectra.check_isolated_dims)
-    padded, (nx, ny, nz) = spectra.padded_dims(dims), dims
-    volume = (size[0] * size[1]) * size[2]
-    scale = -((constant * volume) / (4.0 * math.pi))
-    self_value = scale * self_term
+    padded = spectra.padded_dims(dims)
+    scale, self_value = _isolated_scale(constant, self_term, size)
     sizes, ratios, index = _level_setup(scene, scene.local_boxes, cell_sizes, prob_lo, ref_ratio)
     with _native_scenes(ctx, [scene]) as (field,):
-        values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
-        # every tensor is dropped as soon as the next step has read it: at 512^3 the padded grids
-        # would otherwise add up to some 70 GB
-        grid = torch.zeros(padded[::-1], dtype=torch.float64, device=ctx.device)
-        grid[:nz, :ny, :nx] = values
-        del values
-        spectrum = ctx.fft3d(grid)
-        del grid
-        green = ctx.isolated_green(padded, size, scale, self_value)
-        kernel = ctx.fft3d(green)
-        del green
-        ctx.spectrum_multiply(spectrum, kernel)
-        del kernel
-        real, imag = ctx.ifft3d(spectrum, with_imag=True)
-        del spectrum
-        worst = imag[:nz, :ny, :nx].abs().max()
-        del imag
-        potential = real[:nz, :ny, :nx].contiguous()
-        del real
+        potential, worst, absent = _isolated_potential_device(
+            ctx, field, level, lo, dims, index, ratios, size, scale, self_value, fill)
         ctx.synchronize()
         return {"potential": potential.cpu().numpy(), "imag_max": float(worst.item()),
                 "absent": absent, "padded_dims": padded}
@@ -1655,7 +1828,7 @@ def rays(plotfile: str, start, end, fields: Sequence[str] = (), min_level: int =
     segment start[s] -> end[s] ([n, 3] each, or a single [3] each; the plotfile's physical units)
     the uncovered cells of the loaded levels that it crosses, in order, and the exact column
     integral sum value ds of every field along it.  fields: stored variables or registered
-    derived, gradient or clump fields; by default the plotfile's first variable.  Returns a dict:
+    derived, gradient, clump or grid fields; by default the plotfile's first variable.  Returns a dict:
     per ray n, start and end float64 [n, 3], offsets int64 [n + 1], status uint8 [n] (0 complete,
     1 the ray misses the data's bounding box, 2 max_trips reached, 3 an end point is not finite or
     start == end), t_enter and t_leave float64 [n] (the part of the segment inside the bounding
@@ -1753,16 +1926,22 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
     plotfile.load_plotfile_geometry as it always did.  A derived field is compiled, its fields are
     resolved raw (the plotfile's first variable if it reads none) and derive_scene applies the
     caller's flags.  A gradient field's input is resolved raw and gradient_scene applies the
-    caller's flags.  Resolution is recursive -- a derived field may read gradient fields, a
-    gradient field may take a derived or another gradient field -- and every name is loaded or
-    computed once per call and pair of flags, however many names need it."""
+    caller's flags.  A registered grid field's inputs (gridfields.py: a potential's source, a
+    Helmholtz field's three components, nothing for an array) are resolved raw, its grid is
+    computed on the device and grid_scene writes it onto their boxes with the caller's flags; the
+    grid fields of one call share what they have in common (_grid_product_device).  Resolution is
+    recursive -- a derived field may read gradient or grid fields, a gradient field may take a
+    derived or another gradient field, a potential a derived density -- and every name is loaded
+    or computed once per call and pair of flags, however many names need it."""
     from . import clumps as clump_rules
-    from . import derive, gradient
+    from . import derive, gradient, gridfields
     from . import plotfile as pf
     registered = derive.derived_fields()
     gradients = gradient.gradient_fields()
     clump_names = clump_rules.clump_fields()
+    grid_names = gridfields.grid_fields()
     resolved = {}
+    shared_grids = {}      # what the grid fields of this call share: spectra and grids by product
     header = []
 
     def plotfile_header():
@@ -1789,6 +1968,16 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
             scene, _ = clump_scene(ctx, inner, lower, upper,
                                    *_header_levels(plotfile_header(), finest + 1), rank, n_ranks,
                                    process_group, log, normalize)
+        elif name in grid_names:
+            entry = grid_names[name]
+            for of in gridfields.inputs_of(name):
+                _check_variable(plotfile, plotfile_header(), of, f"grid field '{name}'")
+            # the first input, or the plotfile's first variable, gives the boxes
+            inputs = [resolve(of, False, True) for of in gridfields.inputs_of(name)]
+            geometry = inputs[0] if inputs else resolve("", False, True)
+            scene = _grid_field_scene(ctx, plotfile, entry, inputs, geometry, shared_grids,
+                                      min_level, max_level, rank, n_ranks, process_group, log,
+                                      normalize)
         elif name in registered:
             program = derive.compile_field(name)
             _check_derived_inputs(plotfile, plotfile_header(), name, program)
@@ -1808,13 +1997,16 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
 
 
 def _check_variable(plotfile: str, header, name: str, needed_by: str = "") -> None:
-    """RuntimeError unless `name` is a stored variable of the plotfile or a registered derived or
-    gradient field whose own inputs are."""
+    """RuntimeError unless `name` is a stored variable of the plotfile or a registered derived,
+    gradient, clump or grid field whose own inputs are."""
     from . import clumps as clump_rules
-    from . import derive, gradient
+    from . import derive, gradient, gridfields
     gradients = gradient.gradient_fields()
     clump_names = clump_rules.clump_fields()
-    if name in gradients:
+    if name in gridfields.grid_fields():
+        for of in gridfields.inputs_of(name):
+            _check_variable(plotfile, header, of, f"grid field '{name}'")
+    elif name in gradients:
         _check_variable(plotfile, header, gradients[name][0], f"gradient field '{name}'")
     elif name in clump_names:
         _check_variable(plotfile, header, clump_names[name][0], f"clump field '{name}'")
@@ -3284,7 +3476,7 @@ def project_off_axis(plotfile: str, normal: Sequence[float], variable: Optional[
     inside the cell -- no step and no sampling.  The image plane passes through center with
     (n, right, up) = slice_basis(normal, north), n pointing at the viewer; the rays are depth long,
     half of it on either side of the plane.  variable and weight: stored variables or registered
-    derived, gradient or clump fields.  center defaults to the centre of the data's bounding box,
+    derived, gradient, clump or grid fields.  center defaults to the centre of the data's bounding box,
     plane_width = (wu, wv) and depth to the box's diagonal, so that the whole box is seen from any
     direction, and north to z (to y for a normal along z).  quantity "column": integral = sum f ds
     over the finite cells; "mean": integral / counted, counted = sum ds over those cells.  With

@@ -51,6 +51,9 @@ def add_clump_field(name: str, of: str, lower: float = -math.inf, upper: float =
     gradients = gradient.gradient_fields()
     if name in gradients:
         raise ValueError(f"{name!r} is a registered gradient field")
+    from . import gridfields
+    if name in gridfields.grid_fields():
+        raise ValueError(f"{name!r} is a registered grid field")
     lower, upper = check_bounds(lower, upper)
     trial = dict(_registry)
     trial[name] = (of, lower, upper)

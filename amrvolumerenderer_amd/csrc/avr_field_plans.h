@@ -1,6 +1,6 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
-// streamlines, covering grids, rays, per-ray sums, power spectra, isolated potentials):
+// streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -1694,6 +1694,112 @@ inline CoveringGridPlan plan_covering_grid(const avr_box* field, size_t n_boxes,
   plan.args.ny = dims[1];
   plan.args.nz = dims[2];
   plan.args.n_tiles = static_cast<uint32_t>(plan.candidate_begin.size() - 1);
+  plan.args.fill = fill;
+  return plan;
+}
+
+// ---- grid fields --------------------------------------------------------------------------
+struct GridFieldPlan {
+  std::vector<GridBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  GridLevelsDev levels;    // per level R, f64(2 R) and whether it is finer or coarser than `level`
+  int32_t finest = -1;     // the finest level that has a box with cells (-1: none has)
+  GridFieldArgs args{};
+  template <class Visit>
+  void visit_tables(GridFieldArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->levels, &levels, 1);
+  }
+};
+// The grid of the cells [lo, lo + dims) of level `level` written onto the cells of the boxes `out`
+// ("Grid fields").  box_index_lo, level_ratio and n_levels as plan_covering_grid takes
+// them; `fill` is what a cell outside the region gets (any bits).  grid: a device array of dims[0]
+// * dims[1] * dims[2] f64; totals: a device array of two 64-bit counts; both have been checked by
+// the entry point.  The rules, in this order: n_levels, level, null arrays, the box rules (the
+// output is the reference), the ratios, the index ranges, dims, the region inside [-2^30, 2^30) at
+// `level` and at the finest box level, fewer than 2^31 cells, interpolation and periodic, no byte
+// of the grid or the totals shared with an output box's cells.
+inline GridFieldPlan plan_grid_field(const avr_box* out, size_t n_boxes, int level,
+                                     const int32_t lo[3], const int32_t dims[3],
+                                     const int32_t* box_index_lo, const int32_t* level_ratio,
+                                     int n_levels, int interpolation, int periodic, double fill,
+                                     const void* grid, const void* totals) {
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(level >= 0 && level < n_levels, "level must lie in [0, n_levels)");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  GridFieldPlan plan;
+  std::vector<GridBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;  // of the grid and the totals, and of the output's boxes
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = out[b];
+    const avr_box* fields[1] = {&first};
+    FieldView view;
+    GridBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool cells = field_box_views(first, fields, 1, n_levels, &view, &dev.paired);
+    dev.out = const_cast<double*>(view.cells);
+    dev.jstride = view.jstride;
+    dev.kstride = view.kstride;
+    dev.level = first.level;
+    if (cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&write_ranges, view);
+      plan.finest = std::max(plan.finest, dev.level);
+    }
+    append_tiles(&plan.tile_begin, cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  int32_t ratio[kFieldMaxLevels];
+  fill_level_ratios(level_ratio, n_levels, ratio);
+  box_index_regions(box_index_lo, out, &boxes);
+  require_box(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, "dims must be at least 1");
+  const int finest = std::max(plan.finest, level);
+  const int64_t limit = int64_t{1} << 30, up = level_factor(ratio, level, finest);
+  for (int d = 0; d < 3; ++d) {
+    const int64_t first = lo[d], last = first + dims[d] - 1;
+    require_box(first >= -limit && last < limit && first * up >= -limit && (last + 1) * up <= limit,
+                "the region leaves [-2^30, 2^30) at its level or at the finest box level");
+  }
+  // dims are at most 2^31 each here: two factors first
+  const uint64_t plane = static_cast<uint64_t>(dims[0]) * static_cast<uint64_t>(dims[1]);
+  require_box(plane < (uint64_t{1} << 31) &&
+                  plane * static_cast<uint64_t>(dims[2]) < (uint64_t{1} << 31),
+              "the region has 2^31 cells or more");
+  require_box(interpolation == 0 || interpolation == 1,
+              "interpolation must be 0 (constant) or 1 (linear)");
+  require_box(periodic == 0 || periodic == 1, "periodic must be 0 or 1");
+  const uint64_t n_cells = plane * static_cast<uint64_t>(dims[2]);
+  append_byte_range(&read_ranges, grid, n_cells * sizeof(double));
+  append_byte_range(&read_ranges, totals, 2 * sizeof(uint64_t));
+  require_no_shared_byte(&read_ranges, write_ranges,
+                         "the grid or the totals overlap an output box's cells");
+  // R of a finer level with cells is at most 2^30 by the region rule; of a coarser one it is held
+  // at 2^32, where a cell's footprint meets [-2^30, 2^30) as it does at the true factor
+  GridLevelsDev& levels = plan.levels;
+  std::memset(&levels, 0, sizeof(levels));
+  for (int l = 0; l < kFieldMaxLevels; ++l) {
+    const int64_t r = l < n_levels ? (l < level ? level_factor(ratio, l, level)
+                                                : level_factor(ratio, level, l))
+                                   : 1;
+    levels.refine[l] = r;
+    levels.two_r[l] = 2.0 * static_cast<double>(r);
+    levels.direction[l] = l >= n_levels || l == level ? kGridSame
+                                                      : (l > level ? kGridFiner : kGridCoarser);
+  }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.level = level;
+  for (int d = 0; d < 3; ++d) plan.args.lo[d] = lo[d];
+  plan.args.nx = dims[0];
+  plan.args.ny = dims[1];
+  plan.args.nz = dims[2];
+  plan.args.interpolation = interpolation;
+  plan.args.periodic = periodic;
   plan.args.fill = fill;
   return plan;
 }

@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, rays, per-ray sums, power spectra, inverse transforms and the per-mode operators.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms and the per-mode operators.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -418,6 +418,29 @@ int avr_scene_covering_grid(avr_context* ctx, const avr_scene* field, int level,
     args.coverage = coverage_dev;
     args.cell_level = level_dev;
     return avr::launch_covering_grid(args, ctx->stream);
+  });
+}
+
+int avr_scene_grid_field(avr_context* ctx, avr_scene* out, const double* grid_dev, int level,
+                         const int32_t* lo, const int32_t* dims, const int32_t* box_index_lo,
+                         const int32_t* level_ratio, int n_levels, int interpolation, int periodic,
+                         double fill, int64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(out != nullptr && grid_dev != nullptr && lo != nullptr && dims != nullptr &&
+                totals_dev != nullptr, "null argument");
+    const size_t n_boxes = out->boxes.size();
+    require_field_scene(ctx, out, n_boxes);
+    const avr::GridFieldPlan plan = avr::plan_grid_field(
+        out->boxes.data(), n_boxes, level, lo, dims, box_index_lo, level_ratio, n_levels,
+        interpolation, periodic, fill, grid_dev, totals_dev);
+    for (auto& key : out->classified_key) key.clear();
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::GridFieldArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.grid = grid_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_grid_field(args, ctx->stream);
   });
 }
 

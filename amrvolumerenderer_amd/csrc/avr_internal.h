@@ -924,6 +924,43 @@ struct CoverArgs {
 };
 int launch_covering_grid(const CoverArgs& args, void* stream);
 
+// Grid fields (avr_grid_field.hip): a uniform grid of level L over the region of nx x ny x nz
+// cells from the level-L index `lo` on, written onto every cell of a scene's boxes -- the inverse
+// of the covering grid.  The output is streamed in the tiles of avr_cell_tiles.h, as derive_kernel
+// streams it.  A box as the kernel reads it:
+struct alignas(16) GridBoxDev {
+  double* out;
+  int32_t jstride, kstride;  // element strides (Array4); the box spans < 2^28 elements
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t paired;         // cells 16-byte aligned, both strides even: f64 pairs store
+};
+static_assert(sizeof(GridBoxDev) == 48, "GridBoxDev: 16-byte multiple for scalar loads");
+constexpr int32_t kGridSame = 0, kGridFiner = 1, kGridCoarser = -1;
+struct GridLevelsDev {
+  // [l]: R = the product of the ratios between level l and L (1 for l == L), held at 2^32
+  int64_t refine[kFieldMaxLevels];
+  double two_r[kFieldMaxLevels];      // [l]: f64(2 R)
+  int32_t direction[kFieldMaxLevels];  // [l]: kGridSame, kGridFiner (l > L) or kGridCoarser (l < L)
+};
+struct GridFieldArgs {
+  const GridBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  const GridLevelsDev* levels;
+  const double* grid;           // [nz][ny][nx]
+  unsigned long long* totals;   // [2]: outside, partial; added into
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  int32_t level;                // L
+  int32_t lo[3];
+  int32_t nx, ny, nz;           // nx * ny * nz < 2^31
+  int32_t interpolation;        // 0 constant, 1 linear
+  int32_t periodic;             // 0 clamped, 1 wrapped
+  double fill;
+};
+int launch_grid_field(const GridFieldArgs& args, void* stream);
+
 // Rays (avr_rays.hip): the leaf cells a segment A -> B crosses, in order, one lane per ray.  A box
 // as the kernel reads it is a CoverBoxDev; the locator is the streamlines'.
 constexpr uint64_t kRayMaxTrips = uint64_t{1} << 30;

@@ -304,11 +304,15 @@ def add_field(name: str, expression: str) -> DerivedProgram:
     clump_fields = clumps.clump_fields()
     if name in clump_fields:
         raise ValueError(f"{name!r} is a registered clump field")
+    from . import gridfields
+    grid_fields = gridfields.grid_fields()
+    if name in grid_fields:
+        raise ValueError(f"{name!r} is a registered grid field")
     trial = dict(_registry)
     trial[name] = expression
     program = compile_expression(name if name.isidentifier() else f"field({name!r})", trial)
-    if gradients or clump_fields:
-        # a gradient or clump field it reads may read it
+    if gradients or clump_fields or grid_fields:
+        # a gradient, clump or grid field it reads may read it
         gradient.check_no_cycle(name, trial, gradients, clump_fields)
     _registry[name] = expression
     return DerivedProgram(program.fields, program.instructions, program.constants, expression)

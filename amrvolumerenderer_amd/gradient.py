@@ -17,9 +17,12 @@ _registry: Dict[str, Tuple[str, int]] = {}
 
 def _dependencies(name: str, derived: Dict[str, str], gradients: Dict[str, Tuple[str, int]],
                   clumps: Dict[str, tuple]):
-    """The names `name` is made of, one step down: a gradient or clump field's input, or the fields
-    a derived field reads once the derived fields it names are inlined; () for anything else."""
-    from . import derive
+    """The names `name` is made of, one step down: a gradient or clump field's input, a registered
+    grid field's inputs (gridfields.py), or the fields a derived field reads once the derived
+    fields it names are inlined; () for anything else."""
+    from . import derive, gridfields
+    if name in gridfields.grid_fields():
+        return gridfields.inputs_of(name)
     if name in gradients:
         return (gradients[name][0],)
     if name in clumps:
@@ -68,6 +71,9 @@ def add_gradient_field(name: str, of: str, axis) -> None:
     from . import clumps
     if name in clumps.clump_fields():
         raise ValueError(f"{name!r} is a registered clump field")
+    from . import gridfields
+    if name in gridfields.grid_fields():
+        raise ValueError(f"{name!r} is a registered grid field")
     if isinstance(axis, bool) or axis not in AXES:
         raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z'")
     trial = dict(_registry)

@@ -1312,6 +1312,44 @@ class Scene:
                 float(fill), _pointer(values), _pointer(coverage), _pointer(cell_level))
         return values, coverage, cell_level
 
+    def grid_field(self, grid: torch.Tensor, level: int, lo, box_index_lo, level_ratio,
+                   interpolation: int = 0, periodic: bool = False, fill: float = math.nan,
+                   totals: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """avr_scene_grid_field with this scene as the output: overwrites the cells of this scene's
+        boxes with the uniform grid `grid` (float64 [nz, ny, nx], contiguous, on the device) of the
+        level-`level` cells from the index lo on -- the grid's own value where a box is of that
+        level, the value of the grid cell that holds it (interpolation 0) or the trilinear
+        interpolation between the grid's cell centres (1; past the region's faces wrapped with
+        periodic, clamped without) where it is finer, the mean of the grid cells inside it where it
+        is coarser, and fill where the grid does not reach.  box_index_lo: [n_boxes, 3] int32;
+        level_ratio: n_levels - 1 ints, n_levels counting the levels up to the finer of `level`
+        and the finest box level.  Returns totals, int64 [2] on the device (a tensor handed in is
+        added to): the cells that got fill, and the coarser cells only part of which the grid
+        covers.  The grid must not overlap this scene's cells.  Asynchronous on the context's
+        stream."""
+        ctx = self.ctx
+        index, ratios, _, _ = _level_arguments(len(self.boxes), box_index_lo, level_ratio)
+        first = np.ascontiguousarray(lo, dtype=np.int64)
+        if first.shape != (3,) or (abs(first) > 2 ** 31 - 1).any():
+            raise ValueError("lo must hold three values that fit 32 bits")
+        ctx._check_tensor(grid, torch.float64, "grid")
+        if grid.ndim != 3 or grid.numel() == 0:
+            raise ValueError("grid must be [nz, ny, nx] with at least one cell")
+        if grid.numel() >= 2 ** 31:
+            raise ValueError("the region has 2^31 cells or more")
+        interpolation = int(interpolation)
+        if interpolation not in (0, 1):
+            raise ValueError("interpolation must be 0 (constant) or 1 (linear)")
+        nz, ny, nx = (int(v) for v in grid.shape)
+        extent = np.array([nx, ny, nz], dtype=np.int32)
+        totals = _output(ctx, totals, torch.int64, (2,), "totals", torch.zeros,
+                         "totals must hold two values")
+        _native(ctx, "avr_scene_grid_field", ctx._handle, self._handle, _pointer(grid), int(level),
+                _ints(first.astype(np.int32)), _ints(extent), _ints(index), _ints(ratios),
+                int(ratios.size) + 1, interpolation, int(bool(periodic)), float(fill),
+                _pointer(totals))
+        return totals
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

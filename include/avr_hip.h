@@ -1437,6 +1437,37 @@ int avr_scene_covering_grid(avr_context *ctx, const avr_scene *field, int level,
                             const int32_t *level_ratio, int n_levels, double fill,
                             double *values_dev, double *coverage_dev, int8_t *level_dev);
 
+/* ---- grid fields ("Grid fields") ------------------------------------------------------ */
+
+/* The inverse of avr_scene_covering_grid: the uniform grid grid_dev (device, f64
+ * [dims[2]][dims[1]][dims[0]], fewer than 2^31 cells) of the level-`level` cells G = lo + (i, j, k)
+ * written onto every cell of the boxes of `out` (a scene of ctx, whose cells are overwritten).  The
+ * hierarchy description (box_index_lo, level_ratio, n_levels <= 16; host) is
+ * avr_scene_covering_grid's.  For the cell with index I of a box of level l, per axis, with R the
+ * product of the ratios between l and `level`:
+ *  l == level: G = I; grid[G - lo] with its bits kept if G lies in the region, else `fill`;
+ *  l > level, interpolation 0 (constant): G = floor_div(I, R), then as above;
+ *  l > level, interpolation 1 (linear): p = I - G R, c = 2 p + 1 - R, t = f64(|c|) / f64(2 R), the
+ *    neighbour N = G - 1 for c < 0 and G + 1 otherwise; an N that leaves the region wraps into it
+ *    (periodic 1) or becomes G (periodic 0); `fill` if G is outside the region on any axis, else
+ *    the eight values combined along x, then y, then z, each step a + t * (b - a) (one subtract,
+ *    one multiply, one add, nothing fused, also for t == 0);
+ *  l < level: s = +0.0, n = 0 and, for kk, then jj, then ii ascending over the part of [I R,
+ *    (I + 1) R) inside the region, s = s + grid[...], n += 1; s / f64(n) with n > 0, else `fill`.
+ * `fill` keeps its bits.  totals_dev (device, i64 [2]) is added into: the cells that got `fill`,
+ * and the cells with l < level and 0 < n < R^3.  Equal arguments give equal bits.
+ * Everything is checked on the host before any device work, in this order:
+ * AVR_ERR_INVALID_ARGUMENT for n_levels outside [1, 16], level outside [0, n_levels), a box level
+ * >= n_levels (and the other box rules), a ratio below 2, a box index range outside [-2^30,
+ * 2^30), a dims below 1, a region that leaves [-2^30, 2^30) at `level` or, multiplied up, at the
+ * finest box level, 2^31 cells or more, an interpolation or periodic outside {0, 1}, and a grid or
+ * totals that share a byte with a box's cells -- and `out` and the totals are untouched.
+ * Asynchronous on the context's stream. */
+int avr_scene_grid_field(avr_context *ctx, avr_scene *out, const double *grid_dev, int level,
+                         const int32_t *lo, const int32_t *dims, const int32_t *box_index_lo,
+                         const int32_t *level_ratio, int n_levels, int interpolation, int periodic,
+                         double fill, int64_t *totals_dev);
+
 /* ---- rays ("Rays") -------------------------------------------------------------------- */
 
 /* Line-outs: for each of n_rays segments A -> B (start_dev, end_dev: device, f64 [n][3], physical
