@@ -264,6 +264,9 @@ SIGNATURES = {
     "avr_isolated_green": (C.c_int, [_vp, _ip, C.POINTER(C.c_double), C.c_double, C.c_double,
                                      _vp]),
     "avr_spectrum_multiply": (C.c_int, [_vp, _vp, _vp, _ip]),
+    "avr_grid_structure_functions": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, _ip, _ip,
+                                               C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
+                                               _vp, _vp, _vp]),
     "avr_scene_rays": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip,
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _vp,
                                  C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

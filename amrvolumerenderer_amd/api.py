@@ -1441,6 +1441,121 @@ def power_spectrum(plotfile: str, fields: Sequence[str] = (), level: Optional[in
     return result
 
 
+# ---- structure functions ("Structure functions") -------------------------------------
+
+def _structure_arguments(n_fields: int, max_order, edges, bins, r_range, r_log):
+    """What api.structure_functions and structure_function_scene can be refused for on the
+    arguments alone: one field or three, the order, edges that exclude bins, r_range and r_log.
+    Returns (max_order, the checked edges or None)."""
+    from . import structure
+    structure.kinds(n_fields)
+    order = structure.check_order(max_order)
+    if edges is not None and (bins is not None or r_range is not None or r_log):
+        raise ValueError("give edges or bins / r_range / r_log, not both")
+    return order, None if edges is None else structure.check_edges(edges)
+
+
+def structure_function_scene(ctx, scenes, level: int, lo, dims, cell_sizes, prob_lo, ref_ratio,
+                             lags=None, max_order: int = 6, periodic: bool = False, edges=None,
+                             fill: Optional[float] = None, rank: int = 0,
+                             n_ranks: int = 1) -> dict:
+    """The structure functions S_p(r) = <|v(x + r) - v(x)|^p>, p = 1 .. max_order, of one scene's
+    raw field or of the vector field of three scenes over the same boxes, over the cells [lo, lo +
+    dims) of level `level` ("Structure functions"): the covering grids of
+    covering_grid_scene and every pair of cells a lag apart, all on the device; only the per-lag
+    sums come back.  dims = (nx, ny, nz), any values >= 1.  lags: integers [M, 3], rows (lx, ly,
+    lz), M <= 4096, every |l_d| < N_d, one of each +/- pair; by default structure.default_lags.
+    periodic: the region wraps; without it pairs that leave it count as outside.  edges: n + 1
+    lengths to bin the lags by; by default one bin per distinct lag length.  fill: what a cell
+    without data counts as -- with None such a cell (absent > 0) raises ValueError; with nan its
+    pairs are left out and counted as nonfinite.  The other arguments are covering_grid_scene's.
+    Returns a dict: lags int32 [M, 3], r_lag float64 [M], pairs_lag int64 [M], sums_lag float64
+    [M, K, max_order]; r [n], r_edges (with edges), pairs int64 [n] and S {kind: float64
+    [max_order, n]} with the kinds "scalar", or "longitudinal", "transverse" and "magnitude"
+    (structure.bin_lags); outside, nonfinite and absent.  With n_ranks > 1, or fewer local boxes
+    than boxes, NotImplementedError is raised before any device work."""
+    import numpy as np
+    from . import structure
+    scenes = [scenes] if isinstance(scenes, SceneGeometry) else list(scenes)
+    max_order, edges = _structure_arguments(len(scenes), max_order, edges, None, None, False)
+    first = scenes[0]
+    level, lo, dims, size = _scene_grid_arguments(first, level, lo, dims, cell_sizes, n_ranks,
+                                                  "a structure function", structure.check_dims)
+    for other in scenes[1:]:
+        _require_one_rank(other, n_ranks, "a structure function needs every box of the scene on "
+                          "one rank: cells are not gathered between ranks")
+        if len(other.local_boxes) != len(first.local_boxes):
+            raise ValueError("the three components must be scenes over the same boxes")
+    lags = structure.check_lags(structure.default_lags(dims) if lags is None else lags, dims)
+    r_lag = structure.lag_lengths(lags, size)
+    directions = structure.unit_directions(lags, size) if len(scenes) == 3 else None
+    sizes, ratios, index = _level_setup(first, first.local_boxes, cell_sizes, prob_lo, ref_ratio)
+    with _native_scenes(ctx, scenes) as fields:
+        grids, absent = [], 0
+        for field in fields:
+            values, absent = _covered_grid(field, level, lo, dims, index, ratios, fill)
+            grids.append(values)
+        found = ctx.structure_functions(grids, lags, directions, max_order, bool(periodic))
+        ctx.synchronize()
+        pairs_lag, sums_lag, totals = (t.cpu().numpy() for t in found)
+    binned = structure.bin_lags(r_lag, pairs_lag, sums_lag, edges)
+    result = {"lags": lags, "r_lag": r_lag, "pairs_lag": pairs_lag, "sums_lag": sums_lag,
+              "r": binned["r"]}
+    if edges is not None:
+        result["r_edges"] = np.array(edges)
+    result.update({"pairs": binned["pairs"],
+                   "S": dict(zip(structure.kinds(len(scenes)), binned["S"])),
+                   "outside": int(totals[0]), "nonfinite": int(totals[1]), "absent": absent})
+    return result
+
+
+def structure_functions(plotfile: str, fields, level: Optional[int] = None, region=None,
+                        left_edge=None, right_edge=None, lags=None, max_order: int = 6,
+                        periodic: bool = False, bins: Optional[int] = None, r_range=None,
+                        r_log: bool = False, edges=None, min_level: int = 0, max_level: int = -1,
+                        fill: Optional[float] = None, output: Optional[str] = None) -> dict:
+    """Structure functions of a plotfile ("Structure functions"), on cuda:0: S_p(r) =
+    <|v(x + r) - v(x)|^p> for p = 1 .. max_order (8 at the most) over every pair of cells of a
+    region's covering grid that lies one of the lags apart.  fields: one name -- the moments of
+    |dv| of that field, "scalar" -- or the three components (x, y, z) of a vector field -- the
+    moments of the longitudinal increment |dv . r / r|, of the transverse one |dv - (dv . r) r /
+    r^2| and of the magnitude |dv|; stored, derived, gradient, clump or grid fields.  level,
+    region, left_edge / right_edge, min_level and max_level as api.covering_grid takes them; the
+    region may have any size -- no power of two -- below 2^31 cells.  lags: integers [M, 3] in
+    cells of `level`, by default structure.default_lags (13 directions times 1, 2, 3, 4, 6, 8,
+    12, ... cells).  periodic: the region wraps around.  edges: n + 1 lengths, or bins and / or
+    r_range = (r_min, r_max) with r_log for equal ratios (structure.make_edges); by default one
+    bin per distinct lag length.  fill: what a cell without data counts as; with None such cells
+    raise ValueError, with nan their pairs are left out and counted as nonfinite.  Returns a dict:
+    level, lo, dims (nx, ny, nz), cell_size, fields, max_order, periodic; per lag lags int32 [M,
+    3], r_lag [M] (physical length), pairs_lag int64 [M] and sums_lag float64 [M, K, max_order];
+    per bin r [n], r_edges [n + 1] (with edges), pairs int64 [n] and S {kind: float64 [max_order,
+    n]}, row p - 1 the moment of order p; outside and nonfinite (pairs that leave the region;
+    pairs with a difference that is not finite) and absent (cells without data).  With output the
+    dict is written as one .npz file (structure.save_npz)."""
+    from . import structure
+    names = [fields] if isinstance(fields, str) else [str(name) for name in fields]
+    max_order, edges = _structure_arguments(len(names), max_order, edges, bins, r_range, r_log)
+    if bins is None and r_range is None and r_log:
+        raise ValueError("r_log needs bins or r_range")
+    header, level, lo, dims = _plotfile_grid(plotfile, level, region, left_edge, right_edge,
+                                             min_level, max_level, structure.check_dims)
+    size = header.cell_size[level]
+    lags = structure.check_lags(structure.default_lags(dims) if lags is None else lags, dims)
+    if edges is None:
+        edges = structure.make_edges(structure.lag_lengths(lags, size), bins, r_range,
+                                     bool(r_log))
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, names, min_level, max_level)
+    found = structure_function_scene(ctx, scenes,
+                                     *_grid_arguments(header, scenes[0], level, lo, dims), lags,
+                                     max_order, periodic, edges, fill, rank, world)
+    result = {**_grid_head(header, level, lo, dims), "fields": tuple(names),
+              "max_order": max_order, "periodic": bool(periodic), **found}
+    if output:
+        structure.save_npz(result, output)
+    return result
+
+
 # ---- inverse transform, Helmholtz split, potential (DESIGN.md 7) -----------------------------------
 
 # The device parts of the grid products whose results are grids: they return device tensors, so

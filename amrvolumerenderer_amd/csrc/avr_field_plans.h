@@ -1,6 +1,7 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
-// streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials):
+// streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials,
+// structure functions):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -27,6 +28,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -2367,6 +2369,101 @@ inline SpectrumBinsPlan plan_spectrum_bins(const int32_t dims[3], const double g
   plan.args.n_bins = n_bins;
   plan.args.n_modes = static_cast<uint32_t>(cells);
   plan.groups = spectral_groups(cells);
+  return plan;
+}
+
+// ---- structure functions ("Structure functions") ------------------------------
+struct StructureFunctionsPlan {
+  std::vector<StructureLagDev> lags;  // n_lags: the lag and its direction (zeros with one component)
+  StructureArgs args{};
+  uint32_t groups[3] = {0, 0, 0};     // the grid of workgroups of 256 lanes, the lag running
+                                      // fastest: (n_lags, shares of kStructureGroupCells cells up
+                                      // to kStructureShareRows, rows of that many shares)
+  template <class Visit>
+  void visit_tables(StructureArgs* to, Visit&& visit) const {
+    visit(&to->lags, lags.data(), lags.size());
+  }
+};
+// The moments of orders 1 .. max_order of the increments of n_components grids [nz][ny][nx] of
+// dims = (nx, ny, nz) over n_lags lags (lx, ly, lz), three int32 each, with three f64 of
+// directions per lag when there are three components.  pairs (u64 [n_lags]), sums (f64 [n_lags][K]
+// [max_order], K = n_components) and totals (u64 [2]) are device arrays.  The rules, in this
+// order: no null argument; n_components 1 or 3 (and then every component grid non-null), with
+// directions given exactly when it is 3; every dim at least 1, fewer than 2^31 cells; n_lags in
+// [1, 4096]; max_order in [1, 8]; periodic 0 or 1; no lag zero; every |l_d| < N_d; the directions
+// finite; no byte shared between an output and a component grid, none among the outputs.  The
+// component grids may alias each other: they are only read.
+inline StructureFunctionsPlan plan_structure_functions(
+    const double* const* components, int n_components, const int32_t* dims, const int32_t* lags,
+    const double* directions, int n_lags, int max_order, int periodic, const void* pairs,
+    const void* sums, const void* totals) {
+  require_box(components != nullptr && components[0] != nullptr && dims != nullptr &&
+                  lags != nullptr && pairs != nullptr && sums != nullptr && totals != nullptr,
+              "null argument");
+  require_box(n_components == 1 || n_components == 3, "n_components must be 1 or 3");
+  require_box((directions != nullptr) == (n_components == 3),
+              "directions are given exactly when there are three components");
+  for (int c = 1; c < n_components; ++c) require_box(components[c] != nullptr, "null argument");
+  uint64_t cells = 1;  // at most 2^31 - 1 before every product: no 64-bit overflow
+  for (int d = 0; d < 3; ++d) {
+    require_box(dims[d] >= 1, "dims must be at least 1");
+    cells *= static_cast<uint64_t>(dims[d]);
+    require_cell_count(cells);
+  }
+  require_box(n_lags >= 1 && n_lags <= kStructureMaxLags, "n_lags must lie in [1, 4096]");
+  require_box(max_order >= 1 && max_order <= kStructureMaxOrder, "max_order must lie in [1, 8]");
+  require_box(periodic == 0 || periodic == 1, "periodic must be 0 or 1");
+  for (int m = 0; m < n_lags; ++m) {
+    require_box(lags[3 * m] != 0 || lags[3 * m + 1] != 0 || lags[3 * m + 2] != 0,
+                "a lag is zero");
+  }
+  for (int m = 0; m < n_lags; ++m) {
+    for (int d = 0; d < 3; ++d) {
+      require_box(std::llabs(static_cast<long long>(lags[3 * m + d])) < dims[d],
+                  "a lag spans a grid length or more along an axis");
+    }
+  }
+  if (directions != nullptr) {
+    for (int e = 0; e < 3 * n_lags; ++e) {
+      require_box(std::isfinite(directions[e]), "directions must be finite");
+    }
+  }
+  const uint64_t kinds = static_cast<uint64_t>(n_components);
+  ByteRanges read_ranges, write_ranges;
+  for (int c = 0; c < n_components; ++c) {
+    append_byte_range(&read_ranges, components[c], cells * sizeof(double));
+  }
+  append_byte_range(&write_ranges, pairs, static_cast<uint64_t>(n_lags) * sizeof(uint64_t));
+  append_byte_range(&write_ranges, sums,
+                    static_cast<uint64_t>(n_lags) * kinds * static_cast<uint64_t>(max_order) *
+                        sizeof(double));
+  append_byte_range(&write_ranges, totals, 2 * sizeof(uint64_t));
+  require_no_shared_byte(&read_ranges, write_ranges, "an output array overlaps a component grid");
+  require_disjoint(&write_ranges, "two output arrays overlap");
+  StructureFunctionsPlan plan;
+  plan.lags.resize(static_cast<size_t>(n_lags));
+  for (int m = 0; m < n_lags; ++m) {
+    StructureLagDev& lag = plan.lags[static_cast<size_t>(m)];
+    lag = StructureLagDev{};
+    for (int d = 0; d < 3; ++d) {
+      lag.l[d] = lags[3 * m + d];
+      if (directions != nullptr) lag.u[d] = directions[3 * m + d];
+    }
+  }
+  StructureArgs& a = plan.args;
+  for (int d = 0; d < 3; ++d) a.dims[d] = dims[d];
+  a.n_lags = n_lags;
+  a.max_order = max_order;
+  a.periodic = periodic;
+  a.n_cells = static_cast<uint32_t>(cells);
+  a.shares = static_cast<uint32_t>((cells + kStructureGroupCells - 1) / kStructureGroupCells);
+  const uint32_t rows = kStructureLaneStride / static_cast<uint32_t>(dims[0]);
+  a.stride[0] = kStructureLaneStride % static_cast<uint32_t>(dims[0]);
+  a.stride[1] = rows % static_cast<uint32_t>(dims[1]);
+  a.stride[2] = rows / static_cast<uint32_t>(dims[1]);
+  plan.groups[0] = static_cast<uint32_t>(n_lags);
+  plan.groups[1] = std::min(a.shares, kStructureShareRows);
+  plan.groups[2] = (a.shares + kStructureShareRows - 1) / kStructureShareRows;
   return plan;
 }
 

@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms and the per-mode operators.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms, the per-mode operators and structure functions.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -636,6 +636,29 @@ int avr_spectrum_multiply(avr_context* ctx, double* a_dev, const double* b_dev,
     args.a = a_dev;
     args.b = b_dev;
     return avr::launch_spectrum_multiply(args, plan.groups, ctx->stream);
+  });
+}
+
+int avr_grid_structure_functions(avr_context* ctx, const double* const* components_dev,
+                                 int n_components, const int32_t* dims, const int32_t* lags,
+                                 const double* directions, int n_lags, int max_order,
+                                 int periodic, uint64_t* pairs_dev, double* sums_dev,
+                                 uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(components_dev != nullptr && dims != nullptr && lags != nullptr &&
+                pairs_dev != nullptr && sums_dev != nullptr && totals_dev != nullptr,
+            "null argument");
+    const avr::StructureFunctionsPlan plan = avr::plan_structure_functions(
+        components_dev, n_components, dims, lags, directions, n_lags, max_order, periodic,
+        pairs_dev, sums_dev, totals_dev);
+    avr::StructureArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    for (int c = 0; c < n_components; ++c) args.components[c] = components_dev[c];
+    args.pairs = reinterpret_cast<unsigned long long*>(pairs_dev);
+    args.sums = sums_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_structure_functions(args, n_components, plan.groups, ctx->stream);
   });
 }
 

@@ -1098,6 +1098,41 @@ struct SpectrumMultiplyArgs {
 };
 int launch_spectrum_multiply(const SpectrumMultiplyArgs& args, uint32_t groups, void* stream);
 
+// Structure functions (avr_structure.hip; DESIGN.md 7, "Structure functions"): the moments of the
+// increments of one or three real f64 grids [nz][ny][nx] over a table of integer lag vectors, one
+// workgroup per (lag, share of cells), the lag the fast-running block index.
+constexpr int kStructureMaxLags = 4096;
+constexpr int kStructureMaxOrder = 8;
+constexpr uint32_t kStructureGroupCells = 16384;  // the cells a workgroup of 256 lanes takes for one lag
+constexpr uint32_t kStructureLaneStride = 256;    // the distance between a lane's consecutive cells
+constexpr uint32_t kStructureShareRows = 32768;   // shares per grid row: share = y + this * z, so that
+                                                  // no grid dimension passes 65535 below 2^31 cells
+// One lag: the partner of the cell (i, j, k) is (i + l[0], j + l[1], k + l[2]); u is the direction
+// the longitudinal increment is taken along (three components; zeros with one).
+struct StructureLagDev {
+  int32_t l[3];
+  int32_t pad_;
+  double u[3];
+};
+struct StructureArgs {
+  const double* components[3];  // [nz][ny][nx] each; [1] and [2] null with one component
+  const StructureLagDev* lags;  // [n_lags]
+  int32_t dims[3];              // nx, ny, nz
+  int32_t n_lags;
+  int32_t max_order;            // P
+  int32_t periodic;
+  uint32_t n_cells;             // nx * ny * nz < 2^31
+  uint32_t shares;              // ceil(n_cells / kStructureGroupCells)
+  uint32_t stride[3];           // kStructureLaneStride = stride[0] + nx (stride[1] + ny stride[2]),
+                                // stride[0] < nx, stride[1] < ny: how a lane's (i, j, k) advance
+  uint32_t pad_;
+  unsigned long long* pairs;    // [n_lags], added to
+  double* sums;                 // [n_lags][K][P], K = 1 or 3, added to
+  unsigned long long* totals;   // (outside, nonfinite), added to
+};
+int launch_structure_functions(const StructureArgs& args, int n_components,
+                               const uint32_t groups[3], void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

@@ -379,6 +379,60 @@ class Context:
                 _ints(dims))
         return a
 
+    # -- structure functions ------------------------------------------------------------------
+    def structure_functions(self, components, lags, directions=None, max_order: int = 6,
+                            periodic: bool = False, out=None):
+        """avr_grid_structure_functions: ADDS the moments of the increments of one grid or of
+        three (contiguous float64 [nz, ny, nx] on the device, of one shape, any dims >= 1) over the
+        lags (integers [M, 3], rows (lx, ly, lz), M in [1, 4096], every |l_d| < N_d) to (pairs
+        int64 [M], sums float64 [M, K, max_order], totals int64 [2] = (outside, nonfinite)) on the
+        device: `out`, or new zeroed tensors.  K = 1 for one grid (|dv|), 3 for three
+        (longitudinal, transverse, magnitude), which need directions float64 [M, 3], the unit
+        vector of every lag (structure.unit_directions).  periodic wraps the partner once along
+        every axis; without it a pair that leaves the grid counts as outside (DESIGN.md 7,
+        "Structure functions").  Returns (pairs, sums, totals).  Asynchronous on the context's
+        stream."""
+        if isinstance(components, torch.Tensor):
+            components = (components,)
+        components = tuple(components)
+        if len(components) not in (1, 3):
+            raise ValueError("components must be one grid or three")
+        for c, grid in enumerate(components):
+            self._check_tensor(grid, torch.float64, f"components[{c}]")
+            if grid.ndim != 3 or grid.numel() == 0:
+                raise ValueError("a component must be [nz, ny, nx] with at least one cell")
+            if grid.shape != components[0].shape:
+                raise ValueError("the components must have one shape")
+        nz, ny, nx = (int(v) for v in components[0].shape)
+        dims = np.array([nx, ny, nz], dtype=np.int32)
+        table = np.asarray(lags)
+        if table.ndim != 2 or table.shape[1] != 3 or table.shape[0] < 1:
+            raise ValueError("lags must be [M, 3] with at least one lag")
+        if not np.array_equal(table, table.astype(np.int32)):
+            raise ValueError("lags must be 32-bit integers")
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        n_lags, kinds = int(table.shape[0]), len(components)
+        if (directions is not None) != (kinds == 3):
+            raise ValueError("directions are given exactly with three components")
+        if directions is not None:
+            directions = np.ascontiguousarray(directions, dtype=np.float64)
+            if directions.shape != (n_lags, 3):
+                raise ValueError("directions must hold three values per lag")
+        order = int(max_order)
+        if order < 1:
+            raise ValueError("max_order must lie in [1, 8]")
+        pairs, sums, totals = out if out is not None else (None, None, None)
+        wrong = "out must be (pairs int64 [M], sums float64 [M, K, max_order], totals int64 [2])"
+        pairs = _output(self, pairs, torch.int64, (n_lags,), "pairs", torch.zeros, wrong)
+        sums = _output(self, sums, torch.float64, (n_lags, kinds, order), "sums", torch.zeros,
+                       wrong)
+        totals = _output(self, totals, torch.int64, (2,), "totals", torch.zeros, wrong)
+        grids = (C.c_void_p * 3)(*(grid.data_ptr() for grid in components))
+        _native(self, "avr_grid_structure_functions", self._handle, grids, kinds, _ints(dims),
+                _ints(table), _doubles(directions) if directions is not None else None, n_lags,
+                order, int(bool(periodic)), _pointer(pairs), _pointer(sums), _pointer(totals))
+        return pairs, sums, totals
+
     # -- clump binding ------------------------------------------------------------------------
     def clump_pair_energy(self, offsets, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
                           m: torch.Tensor, w: Optional[torch.Tensor] = None):

@@ -1657,6 +1657,38 @@ int avr_isolated_green(avr_context *ctx, const int32_t *padded_dims, const doubl
 int avr_spectrum_multiply(avr_context *ctx, double *a_dev, const double *b_dev,
                           const int32_t *dims);
 
+/* ---- structure functions ----------------------------------------------------------- */
+
+/* The moments of the increments of n_components (1 or 3) real grids over n_lags integer lag
+ * vectors.  components_dev: host array of n_components device grids, f64
+ * [dims[2]][dims[1]][dims[0]] with dims = (nx, ny, nz), every one at least 1; the grids may alias
+ * each other.  lags (host, 3 n_lags int32: lx, ly, lz per lag); directions (host, 3 n_lags
+ * doubles: ux, uy, uz per lag) with three components, NULL with one.  The partner of the centre
+ * cell c = (i, j, k) under lag m is q = c + l_m: with periodic every axis wraps once, without it a
+ * pair whose partner leaves the grid on any axis adds one to totals_dev[0] (outside) and nothing
+ * else.  Per component delta_d = v_d[q] - v_d[c].  One component: a = |delta|, K = 1 kind.  Three:
+ * m2 = dx dx + dy dy, then + dz dz; L = dx ux + dy uy, then + dz uz; t_d = delta_d - L u_d; T2 =
+ * tx tx + ty ty, then + tz tz; K = 3 kinds a_0 = |L| (longitudinal), a_1 = sqrt(T2) (transverse),
+ * a_2 = sqrt(m2) (magnitude).  Every operation is one rounded f64 operation, nothing fused, the
+ * square roots correctly rounded.  A pair whose a (one component) or m2 (three; an overflowing
+ * square included) is not finite adds one to totals_dev[1] (nonfinite) and nothing else.  Every
+ * other pair adds one to pairs_dev[m] and, with w_1 = a and w_p = w_(p-1) a, w_p to sums_dev[(m K
+ * + kind) max_order + p - 1] for p = 1 .. max_order (f64 additions in no fixed order).  pairs_dev
+ * (u64 [n_lags]), sums_dev (f64 [n_lags][K][max_order]) and totals_dev (u64 [2]) are device
+ * arrays that are ADDED to, as avr_spectrum_bins' are.  Every ordered lag visits every centre
+ * once: l and -l give the same pairs.  Everything is checked on the host before any device work,
+ * in this order: AVR_ERR_INVALID_ARGUMENT for a NULL argument, n_components other than 1 or 3,
+ * directions not given exactly with three components, a NULL grid, a dims below 1, 2^31 cells or
+ * more, n_lags outside [1, 4096], max_order outside [1, 8], periodic other than 0 or 1, a lag
+ * that is zero, a lag with |l_d| >= N_d on an axis (in both boundary modes), a direction that is
+ * not finite, an output that shares a byte with a grid, and two outputs that share a byte -- and
+ * every output is untouched.  Stateless; asynchronous on the context's stream. */
+int avr_grid_structure_functions(avr_context *ctx, const double *const *components_dev,
+                                 int n_components, const int32_t *dims, const int32_t *lags,
+                                 const double *directions, int n_lags, int max_order,
+                                 int periodic, uint64_t *pairs_dev, double *sums_dev,
+                                 uint64_t *totals_dev);
+
 #ifdef __cplusplus
 }
 #endif
