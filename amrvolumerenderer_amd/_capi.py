@@ -267,6 +267,11 @@ SIGNATURES = {
     "avr_grid_structure_functions": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, _ip, _ip,
                                                C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
                                                _vp, _vp, _vp]),
+    "avr_scene_velocity_cube": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_double),
+                                          C.c_double, C.c_double, C.c_int, C.c_int,
+                                          C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                          C.c_int, _vp, _vp, _vp, _vp]),
+    "avr_context_set_velocity_cube_scratch_entries": (C.c_int, [_vp, C.c_uint64]),
     "avr_scene_rays": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip,
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _vp,
                                  C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -3496,6 +3496,117 @@ def project_axis(plotfile: str, axis: str = "z", variable: Optional[str] = None,
     return shown.cpu().numpy()
 
 
+# ---- velocity cubes ("Velocity cubes") ------------------------------------------------
+
+def velocity_cube_scene(ctx, scene_e: SceneGeometry, scene_g: SceneGeometry,
+                        scene_s: Optional[SceneGeometry], axis: str, center: Sequence[float],
+                        plane_width: Sequence[float], width: int, height: int,
+                        level_dl: Sequence[float], edges, rank: int = 0, n_ranks: int = 1,
+                        process_group=None):
+    """The velocity cube of loaded scenes ("Velocity cubes"): (cube [nc, height,
+    width], under, over, length [height, width]), float64 tensors on ctx.device, row 0 at the
+    bottom.  scene_e (emission), scene_g (the field the channels bin: a line-of-sight velocity, or
+    any other) and scene_s (a 1-sigma width in the units of scene_g, or None) are scenes
+    load_plotfile_geometry returns for variables of one plotfile with the same levels, rank and
+    world size.  Axis, center, plane_width, level_dl, the pixel lines and the reduction over ranks
+    are project_axis_scene's; edges are the nc + 1 channel edges (bin_edges, or any finite,
+    strictly increasing array, nc <= 1024)."""
+    if axis not in _AXIS_INDEX:
+        raise ValueError(f"axis must be one of x, y, z, not {axis!r}")
+    a = _AXIS_INDEX[axis]
+    axis_u, axis_v = (a + 1) % 3, (a + 2) % 3
+    wu, wv = (float(w) for w in plane_width)
+    if not (math.isfinite(wu) and wu > 0.0 and math.isfinite(wv) and wv > 0.0):
+        raise ValueError("plane_width must be finite and positive")
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError("image dimensions must be positive")
+    center = tuple(float(c) for c in center)
+    if len(center) != 3 or not _finite((center[axis_u], center[axis_v])):
+        raise ValueError("center must hold three finite values")
+    dl = [float(v) for v in level_dl]
+    finest = max((int(b.level) for b in scene_e.all_boxes), default=0)
+    if not (finest < len(dl) <= 16):
+        raise ValueError("level_dl must hold one entry per level up to the finest loaded one "
+                         "(at most 16)")
+    from . import cubes
+    edges = cubes.checked_edges(edges)
+    scale = float(scene_e.world_scale)
+    origin = ((center[axis_u] - 0.5 * wu) * scale, (center[axis_v] - 0.5 * wv) * scale)
+    du = wu * scale / float(width)
+    dv = wv * scale / float(height)
+    with _native_scenes(ctx, [scene_e, scene_g, scene_s]) as (emission, velocity, sigma):
+        images = emission.velocity_cube(velocity, edges, a, origin, du, dv, width, height, dl,
+                                        sigma)
+        if n_ranks > 1:
+            import torch.distributed as dist
+            root = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+            images = _sum_over_ranks(ctx, images, process_group, root)
+            images = (None, None, None, None) if rank != 0 else \
+                tuple(t.to(ctx.device) for t in images)
+        ctx.synchronize()
+    return tuple(images)
+
+
+def velocity_cube(plotfile: str, axis: str = "z", emission: Optional[str] = None,
+                  velocity: Optional[str] = None, width_field: Optional[str] = None,
+                  channels: int = 64, v_range: Optional[Sequence[float]] = None, edges=None,
+                  width: int = 256, height: int = 256, min_level: int = 0, max_level: int = -1,
+                  center: Optional[Sequence[float]] = None,
+                  plane_width: Optional[Sequence[float]] = None, output: Optional[str] = None):
+    """Position-position-velocity cube of a plotfile ("Velocity cubes"), on cuda:0:
+    per pixel the on-axis column of `emission` along axis "x" | "y" | "z" (project_axis's lines,
+    window and path lengths) split into `channels` channels of `velocity` over v_range -- by
+    default the velocity field's finite (min, max) -- or into the channels of explicit `edges`.
+    emission, velocity and width_field are variable names: stored, derived (add_field), gradient or
+    grid fields.  Without width_field a cell's whole emission goes to the channel that holds its
+    velocity; with it the cell's share is spread as a Gaussian of that 1-sigma width (in the units
+    of velocity; 0 is sharp, cells with a negative or non-finite width are dropped).  Binning by
+    the derived field "z" gives depth-limited slabs, by a temperature an emission-measure
+    distribution.  Returns, on rank 0 (None on other ranks), a dict of numpy float64 arrays: cube
+    [nc, height, width], under, over (what fell below edges[0] / above edges[nc]), length
+    [height, width], edges [nc + 1], centers [nc], moments (moment 0, 1, 2 as cubes.moments
+    defines them).  With output ending in .npz or .fits rank 0 also writes the file."""
+    from . import cubes
+    center, widths, rng, edges = cubes.validate_cube_arguments(
+        axis, emission, velocity, width_field, channels, v_range, edges, width, height, center,
+        plane_width, output)
+    variables = [emission, velocity] + ([width_field] if width_field is not None else [])
+    ctx, rank, world, group, scenes, _ = _load_fields(plotfile, variables, min_level, max_level)
+    from . import plotfile as pf
+    a = _AXIS_INDEX[axis]
+    axis_u, axis_v = (a + 1) % 3, (a + 2) % 3
+    scene = scenes[0]
+    finest = max(int(b.level) for b in scene.all_boxes)
+    level_dl = [float(c[a]) for c in pf.PlotFileData(plotfile).cell_size[:finest + 1]]
+    to_physical = 1.0 / float(scene.world_scale)
+    lo = [min(b.min_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    hi = [max(b.max_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    if center is None:
+        center = tuple(0.5 * (lo[i] + hi[i]) for i in range(3))
+    if widths is None:
+        widths = (hi[axis_u] - lo[axis_u], hi[axis_v] - lo[axis_v])
+    if edges is None:
+        if rng is None:
+            rng = _field_range(ctx, scenes[1], False, "velocity", world, group)
+        edges = cubes.channel_edges(rng, channels)
+    images = velocity_cube_scene(ctx, scene, scenes[1],
+                                 scenes[2] if width_field is not None else None, axis, center,
+                                 widths, width, height, level_dl, edges, rank, world, group)
+    if rank != 0:
+        return None
+    cube, under, over, length = (t.cpu().numpy() for t in images)
+    result = {"cube": cube, "under": under, "over": over, "length": length, "edges": edges,
+              "centers": cubes.channel_centers(edges), "moments": cubes.moments(cube, edges)}
+    if output is not None:
+        if output.lower().endswith(".npz"):
+            cubes.write_npz(output, result)
+        else:
+            origin = (center[axis_u] - 0.5 * widths[0], center[axis_v] - 0.5 * widths[1])
+            cubes.write_fits(output, cube, edges, origin,
+                             (widths[0] / float(width), widths[1] / float(height)), axis)
+    return result
+
+
 # ---- off-axis projection (DESIGN.md 7, "Off-axis projection") --------------------------------------
 
 def validate_off_axis_projection_arguments(width: int, height: int, normal: Sequence[float],

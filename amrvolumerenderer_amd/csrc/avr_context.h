@@ -245,6 +245,8 @@ struct avr_context {
   avr::DeviceBuffer max_layers;                // layer of avr_paint_box_max
   double* colorize_scratch = nullptr;           // avr_projection_colorize's range reduction
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
+  avr::DeviceBuffer cube_planes;               // avr_scene_velocity_cube's partial planes
+  uint64_t cube_scratch_entries = avr::kCubeScratchEntries;  // avr_context_set_velocity_cube_scratch_entries
   avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
   avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
   avr::DeviceBuffer clump_pair_partials;       // avr_clump_pair_energy's partial sums, one per item

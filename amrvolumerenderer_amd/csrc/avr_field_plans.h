@@ -1,7 +1,7 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
 // streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials,
-// structure functions):
+// structure functions, velocity cubes):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -2464,6 +2464,168 @@ inline StructureFunctionsPlan plan_structure_functions(
   plan.groups[0] = static_cast<uint32_t>(n_lags);
   plan.groups[1] = std::min(a.shares, kStructureShareRows);
   plan.groups[2] = (a.shares + kStructureShareRows - 1) / kStructureShareRows;
+  return plan;
+}
+
+// ---- velocity cubes ("Velocity cubes") ----------------------------------------
+// The partial planes of one batch of channels [batch][entries] f64, then under [entries] and over
+// [entries] f64 and n [entries] u32, which the first batch writes and gathers.
+struct CubeScratch {
+  ScratchPart planes, under, over, n;
+  size_t total = 0;
+};
+inline CubeScratch cube_scratch(size_t entries, size_t batch) {
+  CubeScratch scratch;
+  scratch.planes = next_scratch_part(&scratch.total, batch * entries * sizeof(double));
+  scratch.under = next_scratch_part(&scratch.total, entries * sizeof(double));
+  scratch.over = next_scratch_part(&scratch.total, entries * sizeof(double));
+  scratch.n = next_scratch_part(&scratch.total, entries * sizeof(uint32_t));
+  return scratch;
+}
+struct VelocityCubePlan {
+  std::vector<CubeBoxDev> boxes;     // as the reduction reads them
+  std::vector<AxisPlaneDev> planes;  // as the gather reads them
+  std::vector<uint32_t> tile_begin;
+  std::vector<double> edges;         // n_channels + 1, as given
+  uint32_t entries = 0;  // of one partial plane, all boxes: columns x segments, below 2^31
+  int32_t batch = 0;     // channels per host batch: min(n_channels, floor(bound / entries))
+  int32_t n_batches = 0; // the host loops reduce, gather over them; the last may be partial
+  CubeReduceArgs reduce{};  // of batch 0; set_batch() makes those of the others
+  CubeGatherArgs gather{};
+  CubeScratch scratch;
+  template <class Visit>
+  void visit_tables(CubeReduceArgs* to_reduce, CubeGatherArgs* to_gather, Visit&& visit) const {
+    visit(&to_reduce->boxes, boxes.data(), boxes.size());
+    visit(&to_gather->boxes, planes.data(), planes.size());
+    visit(&to_reduce->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to_reduce->edges, edges.data(), edges.size());
+  }
+  // The launch arguments of batch i: its channels, and under, over and n with the first batch.
+  void set_batch(int32_t i, CubeReduceArgs* to_reduce, CubeGatherArgs* to_gather) const {
+    const int32_t first = i * batch;
+    const int32_t count = std::min(batch, reduce.n_channels - first);
+    to_reduce->channel_first = to_gather->channel_first = first;
+    to_reduce->channel_count = to_gather->channel_count = count;
+    to_reduce->totals = to_gather->totals = i == 0 ? 1 : 0;
+  }
+};
+// e, g and s (s may be null: no width field): the boxes of the emission, the bin and the width
+// field.  cube (f64 [n_channels][height][width]), under, over and length (f64 [height][width]) are
+// the device arrays written.  scratch_entries: the bound on batch x entries (kCubeScratchEntries;
+// a parameter so that a test forces several batches on a small scene).  The rules, in this order:
+// the axis; the image size; a finite window; n_levels and a finite level_dl; n_channels in [1,
+// 1024]; finite, strictly increasing edges; n_channels x width x height below 2^31; per box the
+// box rules of field_box_views, finite corners on the image axes and fewer than 2^31 entries and
+// tiles; entries within the scratch bound; no byte shared between an output and an input box's
+// cells, none among the outputs.
+inline VelocityCubePlan plan_velocity_cube(const avr_box* e, const avr_box* g, const avr_box* s,
+                                           size_t n_boxes, int axis, const double origin_uv[2],
+                                           double du, double dv, int width, int height,
+                                           const double* level_dl, int n_levels,
+                                           const double* edges, int n_channels, const void* cube,
+                                           const void* under, const void* over, const void* length,
+                                           uint64_t scratch_entries = kCubeScratchEntries) {
+  require_box(axis >= 0 && axis <= 2, "axis must be 0 (x), 1 (y) or 2 (z)");
+  require_image_size(width, height);
+  require_box(std::isfinite(origin_uv[0]) && std::isfinite(origin_uv[1]) && std::isfinite(du) &&
+                  std::isfinite(dv), "the window must be finite");
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  for (int l = 0; l < n_levels; ++l) {
+    require_box(std::isfinite(level_dl[l]), "level_dl must be finite");
+  }
+  require_box(n_channels >= 1 && n_channels <= kCubeMaxChannels,
+              "n_channels must lie in [1, 1024]");
+  for (int i = 0; i <= n_channels; ++i) {
+    require_box(std::isfinite(edges[i]), "edges must be finite");
+    require_box(i == 0 || edges[i - 1] < edges[i], "edges must be strictly increasing");
+  }
+  const uint64_t pixels = static_cast<uint64_t>(width) * static_cast<uint64_t>(height);
+  require_box(static_cast<uint64_t>(n_channels) * pixels < (uint64_t{1} << 31),
+              "the cube has 2^31 entries or more");
+  const int axis_u = (axis + 1) % 3, axis_v = (axis + 2) % 3;
+  VelocityCubePlan plan;
+  plan.boxes.resize(n_boxes);
+  plan.planes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;
+  uint64_t entries = 0;
+  const int n_fields = s != nullptr ? 3 : 2;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = e[b];
+    const avr_box* in[3] = {&first, &g[b], s != nullptr ? &s[b] : &g[b]};
+    FieldView views[3];
+    CubeBoxDev& dev = plan.boxes[b];
+    AxisPlaneDev& plane = plan.planes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    std::memset(&plane, 0, sizeof(plane));
+    const bool cells = field_box_views(first, in, n_fields, n_levels, views, &dev.paired);
+    if (n_fields == 2) views[2] = views[1];
+    for (int f = 0; f < 3; ++f) {
+      dev.cells[f] = views[f].cells;
+      dev.jstride[f] = views[f].jstride;
+      dev.kstride[f] = views[f].kstride;
+    }
+    uint32_t tiles = 0;
+    dev.plane_begin = plane.plane_begin = static_cast<uint32_t>(entries);
+    if (cells) {
+      require_box(std::isfinite(first.min_corner[axis_u]) && std::isfinite(first.max_corner[axis_u]) &&
+                      std::isfinite(first.min_corner[axis_v]) &&
+                      std::isfinite(first.max_corner[axis_v]),
+                  "box corners must be finite");
+      for (int f = 0; f < n_fields; ++f) append_byte_range(&read_ranges, views[f]);
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      tiles = axis_projection_tiles(axis, dev.nx, dev.ny, dev.nz);
+      plane.min_u = first.min_corner[axis_u];
+      plane.max_u = first.max_corner[axis_u];
+      plane.min_v = first.min_corner[axis_v];
+      plane.max_v = first.max_corner[axis_v];
+      plane.dl = level_dl[first.level];
+      plane.n_u = first.dims[axis_u];
+      plane.n_v = first.dims[axis_v];
+      plane.segments = (first.dims[axis] + kAxisSegment - 1) / kAxisSegment;
+      entries += static_cast<uint64_t>(plane.n_u) * static_cast<uint64_t>(plane.n_v) *
+                 static_cast<uint64_t>(plane.segments);
+    }
+    append_tiles(&plan.tile_begin, tiles);
+    require_box(entries < (uint64_t{1} << 31), "scene has too many cells");
+  }
+  require_box(entries <= scratch_entries,
+              "the partial planes of one channel exceed the scratch bound");
+  append_byte_range(&write_ranges, cube, static_cast<uint64_t>(n_channels) * pixels * sizeof(double));
+  append_byte_range(&write_ranges, under, pixels * sizeof(double));
+  append_byte_range(&write_ranges, over, pixels * sizeof(double));
+  append_byte_range(&write_ranges, length, pixels * sizeof(double));
+  require_no_shared_byte(&read_ranges, write_ranges, "an output array overlaps an input box's cells");
+  require_disjoint(&write_ranges, "two output arrays overlap");
+
+  plan.entries = static_cast<uint32_t>(entries);
+  const uint64_t fit = entries == 0 ? static_cast<uint64_t>(n_channels) : scratch_entries / entries;
+  plan.batch = static_cast<int32_t>(std::min<uint64_t>(static_cast<uint64_t>(n_channels), fit));
+  plan.n_batches = (n_channels + plan.batch - 1) / plan.batch;
+  plan.scratch = cube_scratch(plan.entries, static_cast<size_t>(plan.batch));
+  plan.edges.assign(edges, edges + n_channels + 1);
+  CubeReduceArgs& r = plan.reduce;
+  r.n_boxes = static_cast<int32_t>(n_boxes);
+  r.n_tiles = plan.tile_begin.back();
+  r.n_channels = n_channels;
+  r.chunk = std::min(kCubeChunk[axis], plan.batch);
+  r.entries = plan.entries;
+  r.lo = edges[0];
+  r.hi = edges[n_channels];
+  const double scale = static_cast<double>(n_channels) / (edges[n_channels] - edges[0]);
+  r.scale = std::isfinite(scale) ? scale : 0.0;
+  CubeGatherArgs& t = plan.gather;
+  t.n_boxes = static_cast<int32_t>(n_boxes);
+  t.width = width;
+  t.height = height;
+  t.entries = plan.entries;
+  t.origin_u = origin_uv[0];
+  t.origin_v = origin_uv[1];
+  t.du = du;
+  t.dv = dv;
+  plan.set_batch(0, &r, &t);
   return plan;
 }
 

@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms, the per-mode operators and structure functions.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -659,6 +659,66 @@ int avr_grid_structure_functions(avr_context* ctx, const double* const* componen
     args.sums = sums_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_structure_functions(args, n_components, plan.groups, ctx->stream);
+  });
+}
+
+int avr_context_set_velocity_cube_scratch_entries(avr_context* ctx, uint64_t entries) {
+  return guarded([&]() -> int {
+    require(ctx != nullptr, "null argument");
+    require(entries <= avr::kCubeScratchEntries, "the scratch bound is at most 2^27 entries");
+    ctx->cube_scratch_entries = entries == 0 ? avr::kCubeScratchEntries : entries;
+    return AVR_OK;
+  });
+}
+
+int avr_scene_velocity_cube(avr_context* ctx, const avr_scene* scene_e, const avr_scene* scene_g,
+                            const avr_scene* scene_s, int axis, const double origin_uv[2],
+                            double du, double dv, int width, int height, const double* level_dl,
+                            int n_levels, const double* edges, int n_channels, double* cube_dev,
+                            double* under_dev, double* over_dev, double* length_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene_e != nullptr && scene_g != nullptr && origin_uv != nullptr &&
+                level_dl != nullptr && edges != nullptr && cube_dev != nullptr &&
+                under_dev != nullptr && over_dev != nullptr && length_dev != nullptr,
+            "null argument");
+    const bool broadened = scene_s != nullptr;
+    const size_t n_boxes = scene_e->boxes.size();
+    require_field_scene(ctx, scene_e, n_boxes);
+    require_field_scene(ctx, scene_g, n_boxes);
+    if (broadened) require_field_scene(ctx, scene_s, n_boxes);
+    const avr::VelocityCubePlan plan = avr::plan_velocity_cube(
+        scene_e->boxes.data(), scene_g->boxes.data(),
+        broadened ? scene_s->boxes.data() : nullptr, n_boxes, axis, origin_uv, du, dv, width,
+        height, level_dl, n_levels, edges, n_channels, cube_dev, under_dev, over_dev, length_dev,
+        ctx->cube_scratch_entries);
+    ctx->cube_planes.reserve(plan.scratch.total, ctx->stream, "avr_scene_velocity_cube",
+                             "hipMalloc(cube planes)");
+    avr::CubeReduceArgs reduce = plan.reduce;
+    avr::CubeGatherArgs gather = plan.gather;
+    stage_tables(ctx, plan, &reduce, &gather);
+    reduce.planes = scratch_part<double>(ctx->cube_planes, plan.scratch.planes);
+    reduce.under = scratch_part<double>(ctx->cube_planes, plan.scratch.under);
+    reduce.over = scratch_part<double>(ctx->cube_planes, plan.scratch.over);
+    reduce.plane_n = scratch_part<uint32_t>(ctx->cube_planes, plan.scratch.n);
+    gather.planes = reduce.planes;
+    gather.plane_under = reduce.under;
+    gather.plane_over = reduce.over;
+    gather.plane_n = reduce.plane_n;
+    gather.cube = cube_dev;
+    gather.under = under_dev;
+    gather.over = over_dev;
+    gather.length = length_dev;
+    // one batch's gather has read the planes before the next batch's reduce overwrites them: both
+    // run on the context's stream
+    for (int32_t batch = 0; batch < plan.n_batches; ++batch) {
+      plan.set_batch(batch, &reduce, &gather);
+      int status = avr::launch_cube_reduce(reduce, axis, broadened, ctx->stream);
+      if (status != AVR_OK) return status;
+      status = avr::launch_cube_gather(gather, ctx->stream);
+      if (status != AVR_OK) return status;
+    }
+    return AVR_OK;
   });
 }
 

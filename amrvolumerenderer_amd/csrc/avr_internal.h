@@ -1133,6 +1133,69 @@ struct StructureArgs {
 int launch_structure_functions(const StructureArgs& args, int n_components,
                                const uint32_t groups[3], void* stream);
 
+// Velocity cubes (avr_velocity_cube.hip; DESIGN.md 7, "Velocity cubes"): the on-axis projection of
+// an emission field e split into channels of a bin field g, optionally broadened by a width field
+// s.  The tiles, the segments of kAxisSegment cells, the entries of a partial plane and the gather's
+// box records (AxisPlaneDev) are the on-axis projection's.  Stage 1 writes, per batch of channels,
+// the partial planes [channel in batch][entries] and, with `totals`, under [entries], over
+// [entries] (f64) and n [entries] (u32); a workgroup keeps its columns' accumulators of one chunk
+// of channels in LDS, laid out [channel][column], and the grid's y index numbers the chunks of
+// the batch.  Stage 2 gathers them per pixel.
+constexpr int kCubeMaxChannels = 1024;
+constexpr uint64_t kCubeScratchEntries = uint64_t{1} << 27;  // f64 entries of the channel planes
+constexpr int kCubeColumns[3] = {64, 512, 512};   // columns of one tile, per axis
+constexpr int kCubeChunk[3] = {32, 8, 8};         // channels a workgroup keeps in LDS, per axis
+struct alignas(16) CubeBoxDev {
+  const double* cells[3];   // e, g, s (s == g without a width field: not read)
+  int32_t jstride[3];       // element strides (Array4); every field spans < 2^28 elements
+  int32_t kstride[3];
+  int32_t nx, ny, nz;
+  int32_t paired;           // every field: cells 16-byte aligned, both strides even
+  uint32_t plane_begin;     // first entry of the box's partial planes
+  int32_t pad_[3];
+};
+static_assert(sizeof(CubeBoxDev) == 80, "CubeBoxDev: 16-byte multiple for scalar loads");
+struct CubeReduceArgs {
+  const CubeBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  const double* edges;          // n_channels + 1, device
+  int32_t n_channels;
+  int32_t channel_first;        // the batch: channels [channel_first, channel_first + channel_count)
+  int32_t channel_count;
+  int32_t chunk;                // channels per workgroup: min(kCubeChunk[axis], the largest batch)
+  int32_t totals;               // != 0: the workgroups of the batch's first chunk write under, over, n
+  uint32_t entries;             // of one partial plane, all boxes
+  double lo, hi, scale;         // e[0], e[n] and n / (e[n] - e[0]) (0 if that is not finite)
+  double* planes;               // [channel_count][entries]
+  double* under;                // [entries]
+  double* over;                 // [entries]
+  uint32_t* plane_n;            // [entries]
+};
+struct CubeGatherArgs {
+  const AxisPlaneDev* boxes;
+  int32_t n_boxes;
+  int32_t width, height;
+  int32_t channel_first, channel_count;
+  int32_t totals;               // != 0: under, over and length are written too
+  uint32_t entries;
+  double origin_u, origin_v, du, dv;
+  const double* planes;
+  const double* plane_under;
+  const double* plane_over;
+  const uint32_t* plane_n;
+  double* cube;                 // [n_channels][height][width]
+  double* under;                // [height][width]
+  double* over;
+  double* length;
+};
+// dynamic LDS of a stage 1 workgroup: the edges, chunk + 2 accumulators per column and, for axis x,
+// the staged slab of the three fields
+size_t velocity_cube_lds_bytes(int axis, int n_channels, int chunk);
+int launch_cube_reduce(const CubeReduceArgs& args, int axis, bool broadened, void* stream);
+int launch_cube_gather(const CubeGatherArgs& args, void* stream);
+
 // Wireframe overlay (avr_overlay.hip): the 12 edges of the bounds box projected by the host.
 struct OverlayEdge {
   float sx, sy, ex, ey;   // projected end points (pixels)

@@ -213,6 +213,12 @@ class Context:
     def synchronize(self) -> None:
         _capi.check(_capi.lib().avr_context_synchronize(self._handle))
 
+    def set_velocity_cube_scratch_entries(self, entries: int = 0) -> None:
+        """avr_context_set_velocity_cube_scratch_entries: the bound on channels of a batch x
+        entries of a partial plane of Scene.velocity_cube (0: the default of 2^27)."""
+        _capi.check(_capi.lib().avr_context_set_velocity_cube_scratch_entries(self._handle,
+                                                                              int(entries)))
+
     def set_march_occupancy(self, workgroups_per_cu: int) -> None:
         """avr_context_set_march_occupancy: resident march workgroups per CU (0 = uncapped)."""
         _capi.check(_capi.lib().avr_context_set_march_occupancy(self._handle,
@@ -966,6 +972,46 @@ class Scene:
                 (C.c_double * 2)(*origin), float(du), float(dv), width, height, _doubles(dl),
                 int(dl.size), _pointer(integral), _pointer(weight), _pointer(length))
         return integral, weight, length
+
+    def velocity_cube(self, velocity: "Scene", edges, axis: int, origin_uv: Sequence[float],
+                      du: float, dv: float, width: int, height: int, level_dl: Sequence[float],
+                      width_scene: Optional["Scene"] = None,
+                      cube: Optional[torch.Tensor] = None, under: Optional[torch.Tensor] = None,
+                      over: Optional[torch.Tensor] = None, length: Optional[torch.Tensor] = None):
+        """avr_scene_velocity_cube with this scene as the emission: the on-axis projection of
+        Scene.axis_projection (same axis, window, level_dl and row order) split into the channels
+        edges[c] <= g < edges[c + 1] (the last closed at the top) of the cells g of `velocity`, a
+        scene of the same context with the same box list; width_scene, another such scene, gives a
+        cell's 1-sigma width in the units of g, which spreads its share over the channels as a
+        Gaussian.  edges: float64, finite, strictly increasing, n + 1 <= 1025 values.  Returns
+        (cube [n, height, width], under, over, length [height, width]), float64 on the device;
+        all 0 where no box contains the line."""
+        axis, width, height = int(axis), int(width), int(height)
+        if axis not in (0, 1, 2):
+            raise ValueError("axis must be 0 (x), 1 (y) or 2 (z)")
+        if width <= 0 or height <= 0:
+            raise ValueError("image width and height must be positive")
+        origin = tuple(float(c) for c in origin_uv)
+        if len(origin) != 2:
+            raise ValueError("origin_uv must hold two values")
+        dl = np.ascontiguousarray(level_dl, dtype=np.float64)
+        if dl.ndim != 1 or dl.size < 1:
+            raise ValueError("level_dl must hold one value per level")
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError("edges must hold at least two values")
+        n = int(e.size) - 1
+        ctx = self.ctx
+        cube = _output(ctx, cube, torch.float64, (n, height, width), "cube")
+        under = _output(ctx, under, torch.float64, (height, width), "under")
+        over = _output(ctx, over, torch.float64, (height, width), "over")
+        length = _output(ctx, length, torch.float64, (height, width), "length")
+        _native(ctx, "avr_scene_velocity_cube", ctx._handle, self._handle, velocity._handle,
+                width_scene._handle if width_scene is not None else None, axis,
+                (C.c_double * 2)(*origin), float(du), float(dv), width, height, _doubles(dl),
+                int(dl.size), _doubles(e), n, _pointer(cube), _pointer(under), _pointer(over),
+                _pointer(length))
+        return cube, under, over, length
 
     def derive(self, inputs: Sequence["Scene"], instructions, constants, box_origin,
                level_cell_size) -> None:

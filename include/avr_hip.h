@@ -1689,6 +1689,47 @@ int avr_grid_structure_functions(avr_context *ctx, const double *const *componen
                                  int periodic, uint64_t *pairs_dev, double *sums_dev,
                                  uint64_t *totals_dev);
 
+/* ---- velocity cubes ("Velocity cubes") ---------------------------------------------- */
+
+/* The on-axis projection of the raw f64 cells of scene_e ("emission") split into n_channels
+ * channels of the cells of scene_g ("velocity": any field), a cell's share optionally spread over
+ * the channels by a Gaussian of width scene_s (NULL: none; a 1-sigma width in the units of g).  The
+ * scenes belong to ctx and hold the same box list as avr_scene_joint_histogram requires; each keeps
+ * its own strides.  Axis, window, pixel lines, box containment, cell index, level_dl and row order
+ * are avr_scene_axis_projection's.  edges (host): n_channels + 1 finite, strictly increasing f64, 1
+ * <= n_channels <= 1024.  A cell counts when e and g are finite and, with scene_s, s is finite and
+ * >= 0; other cells add nothing.  Without scene_s, or where s == 0, the cell's e goes to the
+ * channel c with edges[c] <= g < edges[c + 1] (the last channel closed at the top; f64 comparisons
+ * only), to under if g < edges[0], to over if g > edges[n_channels].  Where s > 0, with a_j =
+ * ((edges[j] - g) / s) * 0.70710678118654752440 (three rounded operations) and q_j = -1 if a_j <=
+ * -6, +1 if a_j >= 6, else erf(a_j): channel c gets e * (0.5 * (q_(c+1) - q_c)), under e * (0.5 *
+ * (q_0 + 1)), over e * (0.5 * (1 - q_nc)).  Per pixel p = y * width + x, with dl = level_dl[the
+ * box's level]: cube[c][p], under[p] and over[p] = sum_b dl * (the sum of the box's terms on the
+ * line), length[p] = sum_b dl * f64(the cells that count); f64 on the device, 0 where no box
+ * contains the line, all overwritten.  A column's terms are added in ascending cell order within
+ * segments of 128 cells, the segments and then the boxes in ascending order; no atomic touches an
+ * output or a partial sum: equal arguments give equal bits.  Everything is checked on the host
+ * before any device work, in this order: AVR_ERR_INVALID_ARGUMENT for a NULL argument, scenes of
+ * another context or box count, an axis not in 0..2, a non-positive image size, a non-finite
+ * window, n_levels outside [1, 16], a non-finite level_dl, n_channels outside [1, 1024], edges not
+ * finite or not strictly increasing, n_channels * width * height >= 2^31, boxes that differ in
+ * dims or level or whose level is >= n_levels, partial planes of one channel past the scratch
+ * bound (2^27 entries), an output that shares a byte with an input box's cells or with another
+ * output -- and every output is untouched.  Asynchronous on the context's stream; the context
+ * keeps the partial planes of one batch of channels (grow-only scratch, at most 1 GiB of channel
+ * planes) and loops over the batches. */
+int avr_scene_velocity_cube(avr_context *ctx, const avr_scene *scene_e, const avr_scene *scene_g,
+                            const avr_scene *scene_s, int axis, const double origin_uv[2],
+                            double du, double dv, int width, int height, const double *level_dl,
+                            int n_levels, const double *edges, int n_channels, double *cube_dev,
+                            double *under_dev, double *over_dev, double *length_dev);
+
+/* The bound on (channels of a batch) x (entries of a partial plane) of avr_scene_velocity_cube,
+ * in f64 entries: 1 .. 2^27, 0 restores the default of 2^27.  A smaller bound only cuts the
+ * channels into more batches (the results do not change); it is there for tests and for callers
+ * short of memory. */
+int avr_context_set_velocity_cube_scratch_entries(avr_context *ctx, uint64_t entries);
+
 #ifdef __cplusplus
 }
 #endif
