@@ -278,6 +278,11 @@ SIGNATURES = {
     "avr_scene_ray_sums": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _ip, _ip,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avr_scene_ray_transfer": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64,
+                                         _ip, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.c_int, C.POINTER(C.c_double), C.c_int, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
+    "avr_context_set_ray_transfer_chunk": (C.c_int, [_vp, C.c_int]),
     "avr_blend_depthsort_f32x5": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_f32x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "avr_blend_rgba_u8x4": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),

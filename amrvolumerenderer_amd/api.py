@@ -3769,3 +3769,270 @@ def project_off_axis(plotfile: str, normal: Sequence[float], variable: Optional[
             None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
         _write_picture(rgb8, output)
     return shown
+
+
+# ---- ray transfer ("Ray transfer") ----------------------------------------------------
+
+def ray_transfer_scene(ctx, source: "SceneGeometry", opacity: "SceneGeometry", start, end,
+                       cell_sizes, prob_lo, ref_ratio,
+                       bin_scene: Optional["SceneGeometry"] = None,
+                       width_scene: Optional["SceneGeometry"] = None, edges=None,
+                       max_trips: Optional[int] = None, rank: int = 0, n_ranks: int = 1) -> dict:
+    """Emission and absorption along every segment start[s] -> end[s], the cell nearest the start
+    first ("Ray transfer").  source (the source function S), opacity (the absorption
+    coefficient a per unit length; with channels integrated over the line), bin_scene (the field
+    the channels bin, a line-of-sight velocity; None: grey) and width_scene (a 1-sigma width in the
+    bin field's units, or None): scenes with the same boxes.  edges: the nc + 1 channel edges,
+    given exactly with bin_scene (cubes.checked_edges).  The other arguments are ray_sums_scene's.
+    Returns a dict of numpy arrays: per ray count uint32, status uint8, t_enter, t_leave, counted
+    and covered float64 as ray_sums_scene gives them (a segment counts where S and a are finite
+    and a >= 0, g is finite, s is finite and >= 0); intensity and tau float64 [nc, n] (nc = 1 for
+    grey); outside float64 [2, n], the velocity-integrated optical depth below edges[0] and above
+    edges[nc] (None for grey)."""
+    import numpy as np
+    import torch
+    from . import cubes
+    from . import rays as ray_rules
+    local = list(source.local_boxes)
+    _require_one_rank(source, n_ranks, "rays need every box of the scene on one rank: "
+                      "rays are not handed over between ranks")
+    if opacity is None:
+        raise ValueError("ray transfer needs an opacity scene")
+    if width_scene is not None and bin_scene is None:
+        raise ValueError("a width scene needs a bin scene")
+    if (bin_scene is None) != (edges is None):
+        raise ValueError("edges are given exactly with a bin scene")
+    if edges is not None:
+        edges = cubes.checked_edges(edges)
+    first, last = ray_rules.end_points(start, end)
+    channels = 1 if edges is None else edges.size - 1
+    if channels * first.shape[0] >= 2 ** 31:
+        raise ValueError("the channels of all rays are 2^31 entries or more")
+    sizes, ratios, index = _level_setup(source, local, cell_sizes, prob_lo, ref_ratio)
+    if max_trips is None:
+        bounds = ray_rules.level0_bounds(index, [b.cell_dimensions for b in local],
+                                         [b.level for b in local], ratios)
+        max_trips = ray_rules.default_max_trips(bounds, ratios, len(sizes))
+    max_trips = int(max_trips)
+    if not 1 <= max_trips <= ray_rules.MAX_TRIPS:
+        raise ValueError("max_trips must lie in [1, 2^30]")
+    origin = [float(v) for v in prob_lo]
+    with _native_scenes(ctx, [source, opacity, bin_scene, width_scene]) as (s, a, g, w):
+        found = s.ray_transfer(a, torch.from_numpy(first).to(ctx.device),
+                               torch.from_numpy(last).to(ctx.device), max_trips, index, ratios,
+                               sizes, origin, g, w, edges)
+        ctx.synchronize()
+        counts, status, span, intensity, tau, outside, counted, covered = (
+            t if t is None else t.cpu().numpy() for t in found)
+    return {"count": counts.view(np.uint32), "status": status, "t_enter": span[:, 0].copy(),
+            "t_leave": span[:, 1].copy(), "intensity": intensity, "tau": tau, "outside": outside,
+            "counted": counted, "covered": covered}
+
+
+def transfer_off_axis_scene(ctx, source: SceneGeometry, opacity: SceneGeometry,
+                            center: Sequence[float], normal: Sequence[float],
+                            north: Sequence[float], plane_width: Sequence[float], depth: float,
+                            width: int, height: int, cell_sizes, prob_lo, ref_ratio,
+                            bin_scene: Optional[SceneGeometry] = None,
+                            width_scene: Optional[SceneGeometry] = None, edges=None,
+                            max_trips: Optional[int] = None, rank: int = 0,
+                            n_ranks: int = 1) -> dict:
+    """ray_transfer_scene on the pixel rays of project_off_axis_scene, whose view arguments these
+    are: every ray runs from center + (depth / 2) n to center - (depth / 2) n, so the cell nearest
+    the viewer comes first.  Returns a dict of images, row 0 at the bottom: intensity and tau
+    float64 [nc, height, width], outside float64 [2, height, width] (None for grey), counted and
+    covered float64, status uint8 and count uint32 [height, width]."""
+    from . import rays as ray_rules
+    _require_one_rank(source, n_ranks, "rays need every box of the scene on one rank: "
+                      "rays are not handed over between ranks")
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError("image dimensions must be positive")
+    center = tuple(float(c) for c in center)
+    if len(center) != 3 or not _finite(center):
+        raise ValueError("center must hold three finite values")
+    widths = tuple(float(w) for w in plane_width)
+    if len(widths) != 2 or not all(math.isfinite(w) and w > 0.0 for w in widths):
+        raise ValueError("plane_width must be finite and positive")
+    depth = float(depth)
+    if not (math.isfinite(depth) and depth > 0.0):
+        raise ValueError("depth must be finite and positive")
+    n, u, v = slice_basis(normal, north)
+    start, end = ray_rules.pixel_rays(center, n, u, v, widths, depth, width, height)
+    found = ray_transfer_scene(ctx, source, opacity, start, end, cell_sizes, prob_lo, ref_ratio,
+                               bin_scene, width_scene, edges, max_trips, rank, n_ranks)
+    images = {}
+    for key in ("intensity", "tau", "outside"):
+        values = found[key]
+        images[key] = None if values is None else values.reshape(values.shape[0], height, width)
+    for key in ("counted", "covered", "status", "count"):
+        images[key] = found[key].reshape(height, width)
+    return images
+
+
+_SEVERAL_RANKS = "ray transfer needs every box of the scene on one rank: rays are not handed " \
+                 "over between ranks"
+
+
+def _one_rank_before_loading() -> None:
+    """NotImplementedError for several ranks: known before the runtime is set up."""
+    import torch.distributed as dist
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or \
+            (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        raise NotImplementedError(_SEVERAL_RANKS)
+
+
+def _off_axis_defaults(scene: SceneGeometry, center, widths, depth):
+    """project_off_axis' defaults: the centre of the loaded boxes' bounding box and its diagonal."""
+    to_physical = 1.0 / float(scene.world_scale)
+    lo = [min(b.min_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    hi = [max(b.max_corner[i] for b in scene.all_boxes) * to_physical for i in range(3)]
+    extent = [hi[i] - lo[i] for i in range(3)]
+    diagonal = math.sqrt((extent[0] * extent[0] + extent[1] * extent[1]) + extent[2] * extent[2])
+    if center is None:
+        center = tuple(0.5 * (lo[i] + hi[i]) for i in range(3))
+    return center, widths or (diagonal, diagonal), depth or diagonal
+
+
+def _refuse_truncated(images: dict, what: str) -> None:
+    import numpy as np
+    from . import rays as ray_rules
+    cut = np.argwhere(images["status"] == ray_rules.TRUNCATED)
+    if cut.size:
+        y, x = (int(v) for v in cut[0])
+        raise RuntimeError(f"{what}: the ray of pixel (x={x}, y={y}) ran out of trips; its "
+                           f"optical depth would be short")
+
+
+def emission_absorption(plotfile: str, normal: Sequence[float], source: str, opacity: str,
+                        background: float = 0.0, width: int = 512, height: int = 512,
+                        min_level: int = 0, max_level: int = -1,
+                        center: Optional[Sequence[float]] = None,
+                        plane_width: Optional[Sequence[float]] = None,
+                        depth: Optional[float] = None, north: Optional[Sequence[float]] = None,
+                        log_scale: bool = False, value_range: Optional[Sequence[float]] = None,
+                        color_map: Optional[Sequence[Sequence[float]]] = None,
+                        output: Optional[str] = None) -> dict:
+    """Grey emission and absorption through a plotfile along any line of sight ("Ray
+    transfer"), on cuda:0: per pixel the formal solution I = sum S (1 - exp(-dtau)) exp(-tau in
+    front) over the cells of project_off_axis' ray, nearest the viewer first, dtau = a ds -- dust
+    continuum with a source function, X-ray absorption with a background.  source and opacity:
+    stored variables or registered derived, gradient, clump or grid fields.  The view arguments
+    are project_off_axis'.  background: the intensity behind the far end, added as background *
+    exp(-tau).  Returns a dict of numpy float64 [height, width] images, row 0 at the bottom:
+    intensity, tau, counted and covered (the lengths of the ray inside cells that count -- S and a
+    finite, a >= 0 -- and inside loaded leaves).  With output (.png, else PPM) the intensity is
+    written as a picture, coloured as project_off_axis colours its own; pixels whose ray meets no
+    counted cell are black.  Several ranks raise NotImplementedError before any device work; a ray
+    that ran out of trips raises RuntimeError."""
+    from . import transfer
+    normal, north, center, widths, depth, rng = validate_off_axis_projection_arguments(
+        width, height, normal, "column", center, plane_width, depth, north, log_scale, value_range,
+        None)
+    background = transfer.validate_emission_absorption_arguments(source, opacity, background,
+                                                                 width, height, output)
+    table = projection_rgb_table(color_map)
+    import torch
+    from . import plotfile as pf
+    _one_rank_before_loading()
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [source, opacity], min_level,
+                                                            max_level)
+    _require_one_rank(scenes[0], world, _SEVERAL_RANKS)
+    center, widths, depth = _off_axis_defaults(scenes[0], center, widths, depth)
+    images = transfer_off_axis_scene(
+        ctx, scenes[0], scenes[1], center, normal, north, widths, depth, width, height,
+        *_header_levels(pf.PlotFileData(plotfile), len(volumes)), None, None, None, None, rank,
+        world)
+    _refuse_truncated(images, "emission_absorption")
+    tau = images["tau"][0]
+    intensity = transfer.apply_background(images["intensity"], images["tau"], background)[0]
+    result = {"intensity": intensity, "tau": tau, "counted": images["counted"],
+              "covered": images["covered"]}
+    if output is not None:
+        hit = torch.from_numpy(images["counted"] > 0.0).to(ctx.device)
+        values = torch.from_numpy(intensity).to(ctx.device)
+        rgb8, _ = ctx.projection_colorize(
+            torch.where(hit, values, torch.zeros_like(values)), hit.to(torch.float64),
+            torch.from_numpy(table).to(ctx.device), "column", log_scale,
+            None if rng is None else ((math.log10(rng[0]), math.log10(rng[1])) if log_scale else rng))
+        _write_picture(rgb8, output)
+    return result
+
+
+_LINE_OF_SIGHT_FIELD = "_line_of_sight_velocity"
+
+
+def line_cube(plotfile: str, normal: Sequence[float], source: str, opacity: str, velocity,
+              width_field: Optional[str] = None, channels: int = 64,
+              v_range: Optional[Sequence[float]] = None, edges=None, background=0.0,
+              width: int = 256, height: int = 256, min_level: int = 0, max_level: int = -1,
+              center: Optional[Sequence[float]] = None,
+              plane_width: Optional[Sequence[float]] = None, depth: Optional[float] = None,
+              north: Optional[Sequence[float]] = None, output: Optional[str] = None) -> dict:
+    """Optically thick position-position-velocity cube of a plotfile along any line of sight
+    ("Ray transfer"), on cuda:0: per pixel and channel the formal solution of emission
+    and absorption along project_off_axis' ray, nearest the viewer first.  source: the source
+    function; opacity: the absorption coefficient per unit length integrated over the line (a
+    channel of width dv that holds a whole cell has dtau = a ds / dv).  velocity: one variable
+    name, used as the line-of-sight velocity as it is, or three, the components of a velocity, of
+    which -(n . v) is taken (receding gas is positive; n points at the viewer).  width_field: a
+    1-sigma width in the units of velocity, or None (sharp).  channels, v_range (by default the
+    velocity's finite (min, max)) and edges as api.velocity_cube takes them; the view arguments
+    are project_off_axis'; background: one value or one per channel, added as background[c] *
+    exp(-tau[c]).  Returns a dict of numpy float64 arrays: cube and tau [nc, height, width], outside
+    [2, height, width] (the velocity-integrated optical depth below edges[0] and above edges[nc]),
+    counted and covered [height, width], edges [nc + 1], centers [nc] and moments (cubes.moments of
+    cube * channel width).  With output ending in .npz or .fits the file is written.  Several ranks
+    raise NotImplementedError before any device work; a ray that ran out of trips raises
+    RuntimeError."""
+    from . import cubes
+    from . import transfer
+    normal, north, center, widths, depth, _ = validate_off_axis_projection_arguments(
+        width, height, normal, "column", center, plane_width, depth, north, False, None, None)
+    names, rng, edges, background = transfer.validate_line_cube_arguments(
+        source, opacity, velocity, width_field, channels, v_range, edges, background, width,
+        height, output)
+    import numpy as np
+    from . import plotfile as pf
+    _one_rank_before_loading()
+    temporary = len(names) == 3
+    if temporary:
+        if _LINE_OF_SIGHT_FIELD in derived_fields():
+            raise ValueError(f"{_LINE_OF_SIGHT_FIELD!r} is line_cube's own field name")
+        unit = slice_basis(normal, north)[0]
+        add_field(_LINE_OF_SIGHT_FIELD, transfer.line_of_sight_expression(unit, names))
+    try:
+        variables = [source, opacity, _LINE_OF_SIGHT_FIELD if temporary else names[0]]
+        if width_field is not None:
+            variables.append(width_field)
+        ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, variables, min_level,
+                                                                max_level)
+    finally:
+        if temporary:
+            remove_field(_LINE_OF_SIGHT_FIELD)
+    _require_one_rank(scenes[0], world, _SEVERAL_RANKS)
+    center, widths, depth = _off_axis_defaults(scenes[0], center, widths, depth)
+    if edges is None:
+        if rng is None:
+            rng = _field_range(ctx, scenes[2], False, "velocity", world, group)
+        edges = cubes.channel_edges(rng, channels)
+    images = transfer_off_axis_scene(
+        ctx, scenes[0], scenes[1], center, normal, north, widths, depth, width, height,
+        *_header_levels(pf.PlotFileData(plotfile), len(volumes)), scenes[2],
+        scenes[3] if width_field is not None else None, edges, None, rank, world)
+    _refuse_truncated(images, "line_cube")
+    cube = transfer.apply_background(images["intensity"], images["tau"], background)
+    edges = np.asarray(edges, dtype=np.float64)
+    dv = (edges[1:] - edges[:-1])[:, None, None]
+    result = {"cube": cube, "tau": images["tau"], "outside": images["outside"],
+              "counted": images["counted"], "covered": images["covered"], "edges": edges,
+              "centers": cubes.channel_centers(edges), "moments": cubes.moments(cube * dv, edges)}
+    if output is not None:
+        if output.lower().endswith(".npz"):
+            cubes.write_npz(output, result, ("cube", "tau", "outside", "counted", "covered",
+                                             "edges", "centers"))
+        else:
+            # the image plane's own (right, up) coordinates about the centre
+            cubes.write_fits(output, cube, edges, (-0.5 * widths[0], -0.5 * widths[1]),
+                             (widths[0] / float(width), widths[1] / float(height)), "z")
+    return result

@@ -247,6 +247,7 @@ struct avr_context {
   avr::DeviceBuffer axis_planes;               // avr_scene_axis_projection's partial planes
   avr::DeviceBuffer cube_planes;               // avr_scene_velocity_cube's partial planes
   uint64_t cube_scratch_entries = avr::kCubeScratchEntries;  // avr_context_set_velocity_cube_scratch_entries
+  int ray_transfer_chunk = avr::kTransferChunk;  // avr_context_set_ray_transfer_chunk
   avr::DeviceBuffer gradient_planes;           // avr_scene_gradient's face planes
   avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
   avr::DeviceBuffer clump_pair_partials;       // avr_clump_pair_energy's partial sums, one per item

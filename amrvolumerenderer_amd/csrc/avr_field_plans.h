@@ -1848,14 +1848,20 @@ struct RayPlan {
 // n_weight_boxes of them; its rules come after the field's box rules -- as many boxes as the
 // field has and, box by box, the field's level, dims and corner (from which the caller recovered
 // the one index both share), then the view rule -- and its cells count as inputs in the
-// shared-byte rule.  weight_boxes gets its table.
-inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const avr_box* weight,
-                             size_t n_weight_boxes, uint64_t n_rays, uint64_t max_trips,
+// shared-byte rule.  Such a scene is a companion: its boxes, the message of its congruence rule
+// and where its table goes; several are taken in their order.
+struct RayCompanion {
+  const avr_box* boxes;
+  size_t n_boxes;
+  const char* differ;
+  std::vector<CoverBoxDev>* table;
+};
+inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const RayCompanion* companions,
+                             size_t n_companions, uint64_t n_rays, uint64_t max_trips,
                              uint64_t n_segments, const int32_t* box_index_lo,
                              const int32_t* level_ratio, const double* level_cell_size,
                              const double* prob_lo, int n_levels, bool arrays_present,
-                             const ByteRanges& arrays, int64_t max_entries,
-                             std::vector<CoverBoxDev>* weight_boxes) {
+                             const ByteRanges& arrays, int64_t max_entries) {
   require_box(max_trips >= 1 && max_trips <= kRayMaxTrips, "max_trips must lie in [1, 2^30]");
   require_box(n_rays < (uint64_t{1} << 32), "n_rays must stay below 2^32");
   require_box(n_segments <= kRayMaxSegments, "n_segments must not exceed 2^40");
@@ -1889,14 +1895,15 @@ inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const avr_box
       append_byte_range(&read_ranges, view);
     }
   }
-  if (weight != nullptr) {
-    const char* differ = "the weight scene's boxes differ from the field's";
-    require_box(n_weight_boxes == n_boxes, differ);
-    weight_boxes->resize(n_boxes);
+  for (size_t c = 0; c < n_companions; ++c) {
+    const RayCompanion& companion = companions[c];
+    const char* differ = companion.differ;
+    require_box(companion.n_boxes == n_boxes, differ);
+    companion.table->resize(n_boxes);
     for (size_t b = 0; b < n_boxes; ++b) {
       const avr_box& first = field[b];
-      const avr_box& other = weight[b];
-      CoverBoxDev& dev = (*weight_boxes)[b];
+      const avr_box& other = companion.boxes[b];
+      CoverBoxDev& dev = (*companion.table)[b];
       std::memset(&dev, 0, sizeof(dev));
       require_box(other.level == first.level && other.dims[0] == first.dims[0] &&
                       other.dims[1] == first.dims[1] && other.dims[2] == first.dims[2] &&
@@ -1918,9 +1925,9 @@ inline RayPlan plan_ray_walk(const avr_box* field, size_t n_boxes, const avr_box
   fill_level_ratios(level_ratio, n_levels, levels.ratio);
   const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, field, &boxes);
   require_levels_disjoint(boxes, regions);
-  if (weight != nullptr) {
+  for (size_t c = 0; c < n_companions; ++c) {
     for (size_t b = 0; b < n_boxes; ++b) {
-      for (int d = 0; d < 3; ++d) (*weight_boxes)[b].lo[d] = boxes[b].lo[d];
+      for (int d = 0; d < 3; ++d) (*companions[c].table)[b].lo[d] = boxes[b].lo[d];
     }
   }
   if (n_rays > 0) {
@@ -1988,7 +1995,7 @@ inline RayPlan plan_rays(const avr_box* field, size_t n_boxes, uint64_t n_rays, 
   }
   RayPlan plan = plan_ray_walk(field, n_boxes, nullptr, 0, n_rays, max_trips, n_segments,
                                box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels,
-                               present, arrays, max_entries, nullptr);
+                               present, arrays, max_entries);
   if (!emit) plan.args.n_segments = 0;  // the count pass has no packed arrays
   return plan;
 }
@@ -2038,9 +2045,129 @@ inline RaySumsPlan plan_ray_sums(const avr_box* field, size_t n_boxes, const avr
   }
   RaySumsPlan plan;
   plan.weighted = weight != nullptr;
-  plan.walk = plan_ray_walk(field, n_boxes, weight, n_weight_boxes, n_rays, max_trips, 0,
-                            box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels, present,
-                            arrays, max_entries, &plan.weight_boxes);
+  const RayCompanion companion = {weight, n_weight_boxes,
+                                  "the weight scene's boxes differ from the field's",
+                                  &plan.weight_boxes};
+  plan.walk = plan_ray_walk(field, n_boxes, &companion, plan.weighted ? 1 : 0, n_rays, max_trips,
+                            0, box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels,
+                            present, arrays, max_entries);
+  return plan;
+}
+
+// ---- ray transfer ("Ray transfer") -----------------------------------------------
+struct RayTransferPlan {
+  RayPlan walk;                            // plan_rays' tables, entry for entry; its args launch
+  std::vector<CoverBoxDev> opacity_boxes;
+  std::vector<CoverBoxDev> bin_boxes;      // empty for grey
+  std::vector<CoverBoxDev> width_boxes;    // empty for grey and sharp
+  std::vector<double> edges;               // n_channels + 1 as given; empty for grey
+  std::vector<double> rdv;                 // [c]: 1.0 / (edges[c + 1] - edges[c])
+  int form = kTransferGrey;
+  int32_t n_channels = 1;                  // 1 for grey
+  int32_t chunk = 1;                       // channels of a chunk: min(the size asked for, n_channels)
+  uint32_t n_chunks = 1;                   // the grid's y extent; the last chunk may be partial
+  size_t lds_bytes = 0;                    // of a workgroup: the chunk's tables and accumulators
+  template <class Visit>
+  void visit_tables(RayArgs* to, Visit&& visit) const {
+    visit(&to->boxes, walk.boxes.data(), walk.boxes.size());
+    visit(&to->transfer.opacity_boxes, opacity_boxes.data(), opacity_boxes.size());
+    if (form != kTransferGrey) {
+      visit(&to->transfer.bin_boxes, bin_boxes.data(), bin_boxes.size());
+      visit(&to->transfer.edges, edges.data(), edges.size());
+      visit(&to->transfer.rdv, rdv.data(), rdv.size());
+    }
+    if (form == kTransferBroadened) {
+      visit(&to->transfer.width_boxes, width_boxes.data(), width_boxes.size());
+    }
+    walk.visit_walk_tables(to, visit);
+  }
+};
+// Emission and absorption along the one walk.  source, opacity, bin (may be null: grey) and width
+// (may be null: sharp): the four scenes' boxes; edges: n_channels + 1 of them, given exactly with
+// bin.  chunk: the channels of a chunk as asked for (the context's setting).  counts u32 [n_rays],
+// status u8 [n_rays], span f64 [n_rays][2], intensity and tau f64 [n_channels][n_rays], outside f64
+// [2][n_rays] (exactly with bin), counted and covered f64 [n_rays]: device arrays, free to be null
+// with n_rays == 0.  The rules, in this order.  Its own: no opacity scene, a width without a bin
+// scene, a bin scene without edges or edges without one, and -- while there are rays -- an
+// `outside` without a bin scene or a bin scene without one ("null argument"); with a bin scene
+// n_channels in [1, 1024] and finite, strictly increasing edges, without one n_channels == 1;
+// n_channels x n_rays below 2^31; the chunk in [1, 32].  Then plan_rays' in plan_rays' order with
+// the same messages (there is no n_segments), the three scenes' congruence -- opacity, bin, width:
+// the weight scene's rules of plan_ray_sums, reworded per scene -- after the source's box rules,
+// and no byte of an output, of start or of end shared with a cell of any of the four scenes.
+inline RayTransferPlan plan_ray_transfer(
+    const avr_box* source, size_t n_boxes, const avr_box* opacity, size_t n_opacity_boxes,
+    const avr_box* bin, size_t n_bin_boxes, const avr_box* width, size_t n_width_boxes,
+    uint64_t n_rays, uint64_t max_trips, const int32_t* box_index_lo, const int32_t* level_ratio,
+    const double* level_cell_size, const double* prob_lo, int n_levels, const double* edges,
+    int n_channels, int chunk, const void* start, const void* end, const void* counts,
+    const void* status, const void* span, const void* intensity, const void* tau,
+    const void* outside, const void* counted, const void* covered,
+    int64_t max_entries = kStreamMaxEntries) {
+  require_box(opacity != nullptr, "null argument");
+  require_box(width == nullptr || bin != nullptr, "null argument");
+  require_box((bin != nullptr) == (edges != nullptr), "null argument");
+  require_box(n_rays == 0 || (bin != nullptr) == (outside != nullptr), "null argument");
+  if (bin != nullptr) {
+    require_box(n_channels >= 1 && n_channels <= kTransferMaxChannels,
+                "n_channels must lie in [1, 1024]");
+    for (int i = 0; i <= n_channels; ++i) {
+      require_box(std::isfinite(edges[i]), "edges must be finite");
+      require_box(i == 0 || edges[i - 1] < edges[i], "edges must be strictly increasing");
+    }
+  } else {
+    require_box(n_channels == 1, "n_channels must be 1 without a bin scene");
+  }
+  require_box(n_rays < (uint64_t{1} << 31) &&
+                  static_cast<uint64_t>(n_channels) * n_rays < (uint64_t{1} << 31),
+              "the channels of all rays are 2^31 entries or more");
+  require_box(chunk >= 1 && chunk <= kTransferMaxChunk, "the chunk must lie in [1, 32]");
+  const bool present = start != nullptr && end != nullptr && counts != nullptr &&
+                       status != nullptr && span != nullptr && intensity != nullptr &&
+                       tau != nullptr && counted != nullptr && covered != nullptr;
+  const uint64_t channels = static_cast<uint64_t>(n_channels);
+  ByteRanges arrays;
+  if (n_rays > 0) {
+    append_byte_range(&arrays, start, n_rays * 3 * sizeof(double));
+    append_byte_range(&arrays, end, n_rays * 3 * sizeof(double));
+    append_byte_range(&arrays, counts, n_rays * sizeof(uint32_t));
+    append_byte_range(&arrays, status, n_rays);
+    append_byte_range(&arrays, span, n_rays * 2 * sizeof(double));
+    append_byte_range(&arrays, intensity, channels * n_rays * sizeof(double));
+    append_byte_range(&arrays, tau, channels * n_rays * sizeof(double));
+    if (outside != nullptr) append_byte_range(&arrays, outside, n_rays * 2 * sizeof(double));
+    append_byte_range(&arrays, counted, n_rays * sizeof(double));
+    append_byte_range(&arrays, covered, n_rays * sizeof(double));
+  }
+  RayTransferPlan plan;
+  plan.form = bin == nullptr ? kTransferGrey
+                             : (width == nullptr ? kTransferSharp : kTransferBroadened);
+  const RayCompanion companions[3] = {
+      {opacity, n_opacity_boxes, "the opacity scene's boxes differ from the source's",
+       &plan.opacity_boxes},
+      {bin, n_bin_boxes, "the bin scene's boxes differ from the source's", &plan.bin_boxes},
+      {width, n_width_boxes, "the width scene's boxes differ from the source's",
+       &plan.width_boxes}};
+  plan.walk = plan_ray_walk(source, n_boxes, companions, static_cast<size_t>(1 + plan.form), n_rays,
+                            max_trips, 0, box_index_lo, level_ratio, level_cell_size, prob_lo,
+                            n_levels, present, arrays, max_entries);
+  plan.n_channels = n_channels;
+  plan.chunk = std::min(chunk, n_channels);
+  plan.n_chunks = static_cast<uint32_t>((n_channels + plan.chunk - 1) / plan.chunk);
+  plan.lds_bytes = ray_transfer_lds_bytes(plan.form, plan.chunk);
+  RayTransferPart& t = plan.walk.args.transfer;
+  t.n_channels = n_channels;
+  t.chunk = plan.chunk;
+  if (plan.form != kTransferGrey) {
+    plan.edges.assign(edges, edges + n_channels + 1);
+    plan.rdv.resize(static_cast<size_t>(n_channels));
+    for (int c = 0; c < n_channels; ++c) {
+      const double dv = edges[c + 1] - edges[c];
+      plan.rdv[static_cast<size_t>(c)] = 1.0 / dv;
+    }
+    t.lo = edges[0];
+    t.hi = edges[n_channels];
+  }
   return plan;
 }
 

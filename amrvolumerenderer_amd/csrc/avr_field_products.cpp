@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, ray transfer, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -519,6 +519,59 @@ int avr_scene_ray_sums(avr_context* ctx, const avr_scene* field, const avr_scene
     args.counted = counted_dev;
     args.covered = covered_dev;
     return avr::launch_ray_sums(args, ctx->stream);
+  });
+}
+
+int avr_context_set_ray_transfer_chunk(avr_context* ctx, int channels) {
+  return guarded([&]() -> int {
+    require(ctx != nullptr, "null argument");
+    require(channels >= 0 && channels <= avr::kTransferMaxChunk,
+            "the chunk holds at most 32 channels");
+    ctx->ray_transfer_chunk = channels == 0 ? avr::kTransferChunk : channels;
+    return AVR_OK;
+  });
+}
+
+int avr_scene_ray_transfer(avr_context* ctx, const avr_scene* source, const avr_scene* opacity,
+                           const avr_scene* bin, const avr_scene* width, const double* start_dev,
+                           const double* end_dev, uint64_t n_rays, uint64_t max_trips,
+                           const int32_t* box_index_lo, const int32_t* level_ratio,
+                           const double* level_cell_size, const double* prob_lo, int n_levels,
+                           const double* edges, int n_channels, uint32_t* counts_dev,
+                           uint8_t* status_dev, double* span_dev, double* intensity_dev,
+                           double* tau_dev, double* outside_dev, double* counted_dev,
+                           double* covered_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    // as avr_scene_ray_sums: the scenes first, every other rule is plan_ray_transfer's in its order
+    require(source != nullptr && opacity != nullptr, "null argument");
+    const size_t n_boxes = source->boxes.size();
+    require_field_scene(ctx, source, n_boxes);
+    for (const avr_scene* other : {opacity, bin, width}) {
+      if (other != nullptr) require_field_scene(ctx, other, other->boxes.size());
+    }
+    const avr::RayTransferPlan plan = avr::plan_ray_transfer(
+        source->boxes.data(), n_boxes, opacity->boxes.data(), opacity->boxes.size(),
+        bin != nullptr ? bin->boxes.data() : nullptr, bin != nullptr ? bin->boxes.size() : 0,
+        width != nullptr ? width->boxes.data() : nullptr,
+        width != nullptr ? width->boxes.size() : 0, n_rays, max_trips, box_index_lo, level_ratio,
+        level_cell_size, prob_lo, n_levels, edges, n_channels, ctx->ray_transfer_chunk, start_dev,
+        end_dev, counts_dev, status_dev, span_dev, intensity_dev, tau_dev, outside_dev,
+        counted_dev, covered_dev);
+    if (n_rays == 0) return AVR_OK;
+    avr::RayArgs args = plan.walk.args;
+    stage_tables(ctx, plan, &args);
+    args.start = start_dev;
+    args.end = end_dev;
+    args.counts = counts_dev;
+    args.status = status_dev;
+    args.span = span_dev;
+    args.counted = counted_dev;
+    args.covered = covered_dev;
+    args.transfer.intensity = intensity_dev;
+    args.transfer.tau = tau_dev;
+    args.transfer.outside = outside_dev;
+    return avr::launch_ray_transfer(args, plan.form, plan.n_chunks, plan.lds_bytes, ctx->stream);
   });
 }
 

@@ -961,6 +961,29 @@ struct GridFieldArgs {
 };
 int launch_grid_field(const GridFieldArgs& args, void* stream);
 
+// Ray transfer (avr_rays.hip; DESIGN.md 7, "Ray transfer"): emission and absorption along the same
+// walk, front to back.  The walk's field is the source function S; the opacity a, the bin field g
+// and the width s are read at the same cell through their own box tables.  Grey (no g) keeps its
+// sums in registers; with channels a one-wave workgroup holds the intensity and the optical depth
+// of one chunk of channels in LDS, [channel][2][lane], behind the chunk's edges and reciprocals.
+constexpr int kTransferGrey = 0, kTransferSharp = 1, kTransferBroadened = 2;  // the forms
+constexpr int kTransferMaxChannels = 1024;
+constexpr int kTransferChunk = 16;     // channels of a chunk unless the context was told otherwise
+                                       // (measured: DESIGN.md 7, "Ray transfer")
+constexpr int kTransferMaxChunk = 32;  // 2 x 32 x 64 doubles of LDS, and the tables
+struct RayTransferPart {
+  const CoverBoxDev* opacity_boxes;  // box by box the source's
+  const CoverBoxDev* bin_boxes;      // ... or null (grey)
+  const CoverBoxDev* width_boxes;    // ... or null (grey, sharp)
+  const double* edges;               // [n_channels + 1]; null for grey
+  const double* rdv;                 // [n_channels]: 1 / (edges[c + 1] - edges[c]); null for grey
+  int32_t n_channels;                // 1 for grey
+  int32_t chunk;                     // channels per chunk (the grid's y index numbers the chunks)
+  double lo, hi;                     // edges[0], edges[n_channels]
+  double* intensity;                 // [n_channels][n_rays]
+  double* tau;                       // [n_channels][n_rays]
+  double* outside;                   // [2][n_rays]: under, over; null for grey
+};
 // Rays (avr_rays.hip): the leaf cells a segment A -> B crosses, in order, one lane per ray.  A box
 // as the kernel reads it is a CoverBoxDev; the locator is the streamlines'.
 constexpr uint64_t kRayMaxTrips = uint64_t{1} << 30;
@@ -996,9 +1019,21 @@ struct RayArgs {
   const CoverBoxDev* weight_boxes;  // the weight field's boxes, box by box the field's; or null
   double* weight;               // [n_rays]; written with weight_boxes only
   double* counted;              // [n_rays]
+  // a transfer: the count pass's three arrays, counted and covered, and (behind everything the
+  // other modes read, whose offsets stay)
+  RayTransferPart transfer;
 };
 int launch_rays(const RayArgs& args, bool emit, void* stream);
 int launch_ray_sums(const RayArgs& args, void* stream);
+
+// The dynamic LDS of a one-wave workgroup: the chunk's edges and reciprocals, then the intensity
+// and the optical depth as [channel][2][lane].
+inline size_t ray_transfer_lds_bytes(int form, int chunk) {
+  if (form == kTransferGrey) return 0;
+  return (static_cast<size_t>(2 * chunk + 1) + static_cast<size_t>(chunk) * 2 * 64) * sizeof(double);
+}
+int launch_ray_transfer(const RayArgs& args, int form, uint32_t n_chunks, size_t lds_bytes,
+                        void* stream);
 
 // Power spectra (avr_fft.hip, avr_spectral.hip; DESIGN.md 7, "Power spectrum"): the forward,
 // unnormalised 3-D transform of a real f64 grid [nz][ny][nx] into an interleaved complex spectrum

@@ -19,7 +19,23 @@
 // back when its own last ray is done; the segment stores are scattered, each lane to its own
 // packed range.
 //
-// Every loop is bounded by a count known at launch: max_trips, the levels, a block's list.  No
+// Ray transfer ("Ray transfer") is three further modes of the one walk: the
+// walk's field is the source function S, and per leaf segment the opacity a, the bin field g and the
+// width s are read at the same cell as the sums pass reads its weight.  Per counted segment and
+// channel c, nearest segment first,
+//   dtau = ((a * w) * share) * rdv[c]
+//   I[c] = I[c] + (S * (-expm1(-dtau))) * exp(-tau[c]),  then  tau[c] = tau[c] + dtau
+// with the velocity cube's shares (avr_velocity_cube.hip).  Grey: one channel, share and rdv 1, I
+// and tau in registers, no LDS.  With channels the accumulator a segment adds to is chosen by its
+// g, so a one-wave workgroup keeps I and tau of one chunk of channels (the grid's y index) in
+// dynamic LDS as [channel][2][lane] -- a wave's lanes on consecutive banks, each lane at its own
+// entries only: no barrier but the one after the tables, no atomic -- behind the chunk's edges and
+// reciprocals.  Every chunk repeats the walk for its own channels; a channel's arithmetic does not
+// depend on the chunk that holds it.  Chunk 0 writes the per-ray outputs and under and over; every
+// chunk its channels, one coalesced store per channel and array, [channel][ray].
+//
+// Every loop is bounded by a count known at launch: max_trips, the levels, a block's list, a
+// chunk's channels (the LDS size is the plan's, ray_transfer_lds_bytes, for lanes of 64).  No
 // atomics: equal arguments give equal bits.  Arithmetic is IEEE binary64, round to nearest,
 // nothing fused (-ffp-contract=off); / and sqrt are the correctly rounded __ddiv_rn and
 // __dsqrt_rn.  A maximum or minimum is written as the comparison the definition names.
@@ -35,6 +51,11 @@ namespace {
 
 constexpr int kThreads = 64;  // one wave: its slot is free again when its own last ray has ended
 constexpr int kRayCount = 0, kRayEmit = 1, kRaySums = 2;  // rays_kernel's modes
+constexpr int kRayGrey = 3, kRaySharp = 4, kRayBroadened = 5;  // ... of a transfer
+static_assert(kRayGrey + kTransferSharp == kRaySharp && kRayGrey + kTransferBroadened == kRayBroadened,
+              "a form is a mode");
+
+typedef double __attribute__((address_space(3))) lds_double;
 
 __device__ __forceinline__ int floor_div(int a, int r) {
   const int q = a / r;
@@ -139,8 +160,136 @@ __device__ __forceinline__ RayCell locate(const RayArgs& a, const IsoLevelsDev& 
   return cell;
 }
 
+// A lane's share of a transfer.
+struct TransferLane {
+  const RayTransferPart* args;
+  lds_double* acc;          // the lane's accumulators, [channel][2][lane] from here; grey: unused
+  const lds_double* edges;  // the chunk's count + 1 edges
+  const lds_double* rdv;    // the chunk's count reciprocals
+  int first, count;         // the chunk's channels
+  bool head, tail;          // the chunk holds channel 0 / the last channel
+};
+
+// The value of the cell `cell` in another scene's table: box by box the walk's boxes.
+__device__ __forceinline__ double same_cell(const CoverBoxDev* boxes, const RayCell& cell) {
+  const CoverBoxDev& other = boxes[cell.box];
+  const uint32_t i = static_cast<uint32_t>(cell.g[0]) - static_cast<uint32_t>(other.lo[0]);
+  const uint32_t j = static_cast<uint32_t>(cell.g[1]) - static_cast<uint32_t>(other.lo[1]);
+  const uint32_t k = static_cast<uint32_t>(cell.g[2]) - static_cast<uint32_t>(other.lo[2]);
+  return other.cells[i + j * static_cast<uint32_t>(other.jstride) +
+                     k * static_cast<uint32_t>(other.kstride)];
+}
+
+__device__ __forceinline__ double clamped_erf(double a) {
+  return (a <= -6.0) ? -1.0 : (a >= 6.0) ? 1.0 : erf(a);
+}
+__device__ __forceinline__ double profile_argument(double edge, double g, double s) {
+  return __ddiv_rn(edge - g, s) * 0.70710678118654752440;
+}
+
+// One counted segment's step of one channel: its intensity at p[0], its optical depth at p[kThreads].
+__device__ __forceinline__ void add_channel(lds_double* p, double source, double dtau) {
+  const double tau = p[kThreads];
+  p[0] = p[0] + (source * (-expm1(-dtau))) * exp(-tau);
+  p[kThreads] = tau + dtau;
+}
+
+// One leaf segment of length w whose source function is `source`.  Returns whether it counts.
+template <int MODE>
+__device__ __forceinline__ bool transfer_segment(const TransferLane& x, const RayCell& cell,
+                                                 double source, double w, double* intensity,
+                                                 double* tau, double* under, double* over) {
+  const RayTransferPart& t = *x.args;
+  const double opacity = same_cell(t.opacity_boxes, cell);
+  bool counts = __builtin_isfinite(source) & __builtin_isfinite(opacity) & (opacity >= 0.0);
+  double g = 0.0, s = 0.0;
+  if (MODE != kRayGrey) {
+    g = same_cell(t.bin_boxes, cell);
+    counts = counts & __builtin_isfinite(g);
+  }
+  if (MODE == kRayBroadened) {
+    s = same_cell(t.width_boxes, cell);
+    counts = counts & __builtin_isfinite(s) & (s >= 0.0);
+  }
+  if (!counts) return false;
+  const double aw = opacity * w;
+  if (MODE == kRayGrey) {  // share 1, rdv 1: dtau is a w
+    *intensity = *intensity + (source * (-expm1(-aw))) * exp(-*tau);
+    *tau = *tau + aw;
+    return true;
+  }
+  if (MODE == kRaySharp || s == 0.0) {  // share 1 for one of the channels, under or over
+    if (g < t.lo) {
+      if (x.head) *under = *under + aw;
+    } else if (g > t.hi) {
+      if (x.head) *over = *over + aw;
+    } else if (g >= x.edges[0] && (x.tail || g < x.edges[x.count])) {
+      // the largest channel of the chunk whose lower edge is not above g
+      int first = 0, last = x.count;
+      while (last - first > 1) {
+        const int mid = (first + last) >> 1;
+        if (x.edges[mid] <= g) {
+          first = mid;
+        } else {
+          last = mid;
+        }
+      }
+      add_channel(x.acc + first * (2 * kThreads), source, aw * x.rdv[first]);
+    }
+    return true;
+  }
+  if (x.head) {
+    *under = *under + aw * (0.5 * (clamped_erf(profile_argument(t.lo, g, s)) + 1.0));
+    *over = *over + aw * (0.5 * (1.0 - clamped_erf(profile_argument(t.hi, g, s))));
+  }
+  // the argument does not decrease with the edge: a chunk wholly outside the window has shares of 0
+  const double a_first = profile_argument(x.edges[0], g, s);
+  if (a_first >= 6.0) return true;
+  if (profile_argument(x.edges[x.count], g, s) <= -6.0) return true;
+  double below = clamped_erf(a_first);
+  for (int at = 0; at < x.count; ++at) {
+    const double above = clamped_erf(profile_argument(x.edges[at + 1], g, s));
+    const double share = 0.5 * (above - below);
+    // a share of 0 adds +-0 to sums that are never -0
+    if (share != 0.0) add_channel(x.acc + at * (2 * kThreads), source, (aw * share) * x.rdv[at]);
+    below = above;
+  }
+  return true;
+}
+
+// The grid's y index numbers the chunks of a.transfer.chunk channels; only the sharp and the
+// broadened mode have more than one, and LDS.
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
+  TransferLane x;
+  if constexpr (MODE >= kRayGrey) {
+    extern __shared__ double transfer_lds[];  // [edges: chunk + 1][rdv: chunk][chunk][2][lane]
+    const RayTransferPart& t = a.transfer;
+    x.args = &t;
+    x.acc = nullptr;
+    x.edges = x.rdv = nullptr;
+    x.first = 0;
+    x.count = 1;
+    x.head = x.tail = true;
+    if (MODE != kRayGrey) {
+      lds_double* lds = (lds_double*)transfer_lds;
+      x.first = static_cast<int>(blockIdx.y) * t.chunk;
+      const int left = t.n_channels - x.first;
+      x.count = left < t.chunk ? left : t.chunk;
+      x.head = blockIdx.y == 0;
+      x.tail = x.first + x.count == t.n_channels;
+      for (int i = static_cast<int>(threadIdx.x); i <= x.count; i += kThreads) {
+        lds[i] = t.edges[x.first + i];
+      }
+      for (int i = static_cast<int>(threadIdx.x); i < x.count; i += kThreads) {
+        lds[t.chunk + 1 + i] = t.rdv[x.first + i];
+      }
+      __syncthreads();  // the workgroup's only barrier: before any lane leaves
+      x.edges = lds;
+      x.rdv = lds + (t.chunk + 1);
+      x.acc = lds + (2 * t.chunk + 1) + threadIdx.x;
+    }
+  }
   const uint32_t ray = blockIdx.x * kThreads + threadIdx.x;
   if (ray >= a.n_rays) return;
   const IsoLevelsDev& levels = *a.levels;
@@ -161,6 +310,13 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
   unsigned long long slot = 0, slot_end = 0;
   double integral = 0.0, covered = 0.0, length = 0.0;
   double weight = 0.0, counted = 0.0;  // the sums pass
+  double tau = 0.0, under = 0.0, over = 0.0;  // transfer: with `integral` as the grey intensity
+  if constexpr (MODE >= kRaySharp) {
+    for (int at = 0; at < x.count; ++at) {
+      x.acc[at * (2 * kThreads)] = 0.0;
+      x.acc[at * (2 * kThreads) + kThreads] = 0.0;
+    }
+  }
   if (MODE == kRayEmit) {
     const long long begin = a.offsets[ray], end = a.offsets[ray + 1ull];
     if (begin >= 0 && begin <= end && static_cast<unsigned long long>(end) <= a.n_segments) {
@@ -259,6 +415,15 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
             }
           }
         }
+        if constexpr (MODE >= kRayGrey) {
+          if (cell.at != nullptr) {
+            const double w = (t_next - t_cur) * length;
+            covered = covered + w;
+            if (transfer_segment<MODE>(x, cell, *cell.at, w, &integral, &tau, &under, &over)) {
+              counted = counted + w;
+            }
+          }
+        }
         ++count;
       }
       if (!(t_out < t_leave)) {
@@ -294,7 +459,7 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
       t_cur = t_next;
     }
   }
-  if (MODE != kRayCount) {
+  if (MODE == kRayEmit || MODE == kRaySums) {
     a.integral[ray] = integral;
     a.covered[ray] = covered;
   }
@@ -302,7 +467,31 @@ __global__ __launch_bounds__(kThreads) void rays_kernel(const RayArgs a) {
     if (a.weight_boxes != nullptr) a.weight[ray] = weight;
     a.counted[ray] = counted;
   }
-  if (MODE != kRayEmit) {
+  if constexpr (MODE >= kRayGrey) {
+    const RayTransferPart& t = *x.args;
+    const size_t n = a.n_rays;
+    if (MODE == kRayGrey) {
+      t.intensity[ray] = integral;
+      t.tau[ray] = tau;
+    } else {
+      double* intensity = t.intensity + static_cast<size_t>(x.first) * n + ray;
+      double* depth = t.tau + static_cast<size_t>(x.first) * n + ray;
+      for (int at = 0; at < x.count; ++at) {
+        intensity[static_cast<size_t>(at) * n] = x.acc[at * (2 * kThreads)];
+        depth[static_cast<size_t>(at) * n] = x.acc[at * (2 * kThreads) + kThreads];
+      }
+    }
+    if (x.head) {
+      a.counted[ray] = counted;
+      a.covered[ray] = covered;
+      if (MODE != kRayGrey) {
+        t.outside[ray] = under;
+        t.outside[n + ray] = over;
+      }
+    }
+  }
+  // the count pass's three outputs; of a transfer's chunks the first writes them
+  if (MODE != kRayEmit && (MODE < kRayGrey || x.head)) {
     const bool walked = status == kRayComplete || status == kRayTruncated;
     a.counts[ray] = count;
     a.status[ray] = static_cast<uint8_t>(status);
@@ -333,6 +522,27 @@ int launch_rays(const RayArgs& args, bool emit, void* stream) {
 
 int launch_ray_sums(const RayArgs& args, void* stream) {
   return launch_mode<kRaySums>(args, stream);
+}
+
+int launch_ray_transfer(const RayArgs& args, int form, uint32_t n_chunks, size_t bytes,
+                        void* stream_v) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (args.n_rays == 0) return AVR_OK;
+  const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(args.n_rays) + kThreads - 1) / kThreads),
+                  n_chunks);
+  if (form == kTransferGrey) {
+    hipLaunchKernelGGL(rays_kernel<kRayGrey>, grid, dim3(kThreads), bytes, stream, args);
+  } else if (form == kTransferSharp) {
+    hipLaunchKernelGGL(rays_kernel<kRaySharp>, grid, dim3(kThreads), bytes, stream, args);
+  } else {
+    hipLaunchKernelGGL(rays_kernel<kRayBroadened>, grid, dim3(kThreads), bytes, stream, args);
+  }
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    set_error(std::string("ray transfer kernel: ") + hipGetErrorString(err));
+    return AVR_ERR_RUNTIME;
+  }
+  return AVR_OK;
 }
 
 }  // namespace avr

@@ -145,10 +145,11 @@ def moments(cube, edges):
     return m0, np.where(filled, m1, nan), np.where(filled, m2, nan)
 
 
-def write_npz(path: str, result: dict) -> None:
-    """The arrays of api.velocity_cube's dict -> an .npz (moments as moment0, moment1, moment2)."""
-    arrays = {k: np.asarray(result[k]) for k in ("cube", "under", "over", "length", "edges",
-                                                 "centers")}
+def write_npz(path: str, result: dict,
+              keys: Sequence[str] = ("cube", "under", "over", "length", "edges", "centers")) -> None:
+    """The arrays of api.velocity_cube's dict -> an .npz (moments as moment0, moment1, moment2).
+    keys: the arrays of another cube's dict (api.line_cube)."""
+    arrays = {k: np.asarray(result[k]) for k in keys}
     for i, m in enumerate(result["moments"]):
         arrays[f"moment{i}"] = np.asarray(m)
     with open(path, "wb") as f:

@@ -219,6 +219,11 @@ class Context:
         _capi.check(_capi.lib().avr_context_set_velocity_cube_scratch_entries(self._handle,
                                                                               int(entries)))
 
+    def set_ray_transfer_chunk(self, channels: int = 0) -> None:
+        """avr_context_set_ray_transfer_chunk: the channels a workgroup of Scene.ray_transfer keeps
+        in LDS at a time, 1 .. 32 (0: the default of 16).  The results do not depend on it."""
+        _capi.check(_capi.lib().avr_context_set_ray_transfer_chunk(self._handle, int(channels)))
+
     def set_march_occupancy(self, workgroups_per_cu: int) -> None:
         """avr_context_set_march_occupancy: resident march workgroups per CU (0 = uncapped)."""
         _capi.check(_capi.lib().avr_context_set_march_occupancy(self._handle,
@@ -1378,6 +1383,69 @@ class Scene:
                 max_trips, _ints(index), _ints(ratios), _doubles(sizes), _doubles(origin),
                 int(sizes.shape[0]), _pointer(counts), _pointer(status), _pointer(span),
                 _pointer(integral), _pointer(weight_sum), _pointer(counted), _pointer(covered))
+        return result
+
+    def ray_transfer(self, opacity: "Scene", start, end, max_trips: int, box_index_lo, level_ratio,
+                     level_cell_size, prob_lo, bin_scene: Optional["Scene"] = None,
+                     width_scene: Optional["Scene"] = None, edges=None):
+        """avr_scene_ray_transfer with this scene as the source function: emission and absorption
+        along Scene.ray_sums' walk, nearest cell first ("Ray transfer").  opacity,
+        bin_scene (the field the channels bin, or None: grey) and width_scene (a 1-sigma width in
+        the bin field's units, or None; only with bin_scene): scenes of the same context with the
+        same boxes.  edges: the nc + 1 channel edges, given exactly with bin_scene; grey has one
+        channel.  The other arguments are Scene.rays'.  Returns (counts int32 [n], status uint8
+        [n], span float64 [n, 2]) as Scene.rays' count pass gives them, (intensity, tau) float64
+        [nc, n], outside float64 [2, n] (the optical depth below edges[0] and above edges[nc]; None
+        for grey) and (counted, covered) float64 [n].  Everything is on the device; asynchronous
+        on the context's stream."""
+        ctx = self.ctx
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
+        max_trips = int(max_trips)
+        if not 1 <= max_trips <= 2 ** 30:
+            raise ValueError("max_trips must lie in [1, 2^30]")
+        if opacity is None:
+            raise ValueError("ray_transfer needs an opacity scene")
+        if width_scene is not None and bin_scene is None:
+            raise ValueError("a width scene needs a bin scene")
+        if (bin_scene is None) != (edges is None):
+            raise ValueError("edges are given exactly with a bin scene")
+        for other in (opacity, bin_scene, width_scene):
+            if other is not None and other.ctx is not ctx:
+                raise ValueError("the scenes belong to different contexts")
+        e, nc = None, 1
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2:
+                raise ValueError("edges must hold at least two values")
+            nc = int(e.size) - 1
+        start = _device_points(ctx, start, "start and end must hold three values per ray")
+        end = _device_points(ctx, end, "start and end must hold three values per ray")
+        if start.shape != end.shape:
+            raise ValueError("start and end must hold the same number of rays")
+        n = int(start.shape[0])
+        if nc * n >= 2 ** 31:
+            raise ValueError("the channels of all rays are 2^31 entries or more")
+        counts = torch.zeros(n, dtype=torch.int32, device=ctx.device)
+        status = torch.full((n,), 3, dtype=torch.uint8, device=ctx.device)
+        span = torch.full((n, 2), math.nan, dtype=torch.float64, device=ctx.device)
+        intensity = torch.zeros((nc, n), dtype=torch.float64, device=ctx.device)
+        tau = torch.zeros((nc, n), dtype=torch.float64, device=ctx.device)
+        outside = None
+        if bin_scene is not None:
+            outside = torch.zeros((2, n), dtype=torch.float64, device=ctx.device)
+        counted = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        covered = torch.zeros(n, dtype=torch.float64, device=ctx.device)
+        result = (counts, status, span, intensity, tau, outside, counted, covered)
+        if n == 0:                     # nothing to launch, and empty tensors have no address
+            return result
+        _native(ctx, "avr_scene_ray_transfer", ctx._handle, self._handle, opacity._handle,
+                bin_scene._handle if bin_scene is not None else None,
+                width_scene._handle if width_scene is not None else None, _pointer(start),
+                _pointer(end), n, max_trips, _ints(index), _ints(ratios), _doubles(sizes),
+                _doubles(origin), int(sizes.shape[0]), _doubles(e) if e is not None else None, nc,
+                _pointer(counts), _pointer(status), _pointer(span), _pointer(intensity),
+                _pointer(tau), _pointer(outside), _pointer(counted), _pointer(covered))
         return result
 
     def covering_grid(self, level: int, lo, dims, box_index_lo, level_ratio,

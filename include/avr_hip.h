@@ -1730,6 +1730,45 @@ int avr_scene_velocity_cube(avr_context *ctx, const avr_scene *scene_e, const av
  * short of memory. */
 int avr_context_set_velocity_cube_scratch_entries(avr_context *ctx, uint64_t entries);
 
+/* Ray transfer ("Ray transfer"): emission and absorption along the rays of
+ * avr_scene_ray_sums, front to back.  source (the source function S), opacity (the absorption
+ * coefficient a per unit length; with channels integrated over the line), bin_or_null (the field g
+ * the channels bin: a line-of-sight velocity) and width_or_null (a 1-sigma width s in the units of
+ * g; only with a bin scene) are scenes of this context over the same boxes: box by box the
+ * source's level, dims and corner.  The rays, max_trips, the hierarchy's arguments, counts_dev,
+ * status_dev, span_dev and covered_dev are avr_scene_ray_sums'.  edges_or_null: n_channels + 1
+ * finite, strictly increasing channel edges on the host, 1 <= n_channels <= 1024, given exactly
+ * with a bin scene; without one (grey) n_channels is 1.  A leaf segment of length w counts when S
+ * and a are finite and a >= 0 (and g is finite, and s is finite and >= 0); counted_dev f64
+ * [n_rays] sums w over those.  Per counted segment and channel c, nearest segment first,
+ *   dtau = ((a * w) * share) * rdv[c],   rdv[c] = 1.0 / (edges[c + 1] - edges[c])  (grey: 1)
+ *   I[c] = I[c] + (S * (-expm1(-dtau))) * exp(-tau[c]),   then   tau[c] = tau[c] + dtau
+ * with the shares of avr_scene_velocity_cube: sharp (no width scene, or s == 0) 1 for the channel
+ * with edges[c] <= g < edges[c + 1], the last closed at the top; broadened the Gaussian's part of
+ * the channel; grey 1.  intensity_dev and tau_dev: f64 [n_channels][n_rays].
+ * outside_dev_or_null: f64 [2][n_rays], sum (a * w) * share below edges[0] and above
+ * edges[n_channels], given exactly with a bin scene.  Rays that miss or are invalid get +0.0 in
+ * every channel.  The results do not depend on avr_context_set_ray_transfer_chunk.  n_rays == 0
+ * succeeds without a launch.  Everything is validated before any device work: a null argument, a
+ * scene of another context, a broken rule of avr_scene_ray_sums (the weight scene's read per
+ * scene), a broken channel rule, n_channels x n_rays >= 2^31, or an output, start_dev or end_dev
+ * that shares a byte with a cell of any of the scenes -- AVR_ERR_INVALID_ARGUMENT, and every
+ * output is untouched.  Stateless; asynchronous on the context's stream. */
+int avr_scene_ray_transfer(avr_context *ctx, const avr_scene *source, const avr_scene *opacity,
+                           const avr_scene *bin_or_null, const avr_scene *width_or_null,
+                           const double *start_dev, const double *end_dev, uint64_t n_rays,
+                           uint64_t max_trips, const int32_t *box_index_lo,
+                           const int32_t *level_ratio, const double *level_cell_size,
+                           const double *prob_lo, int n_levels, const double *edges_or_null,
+                           int n_channels, uint32_t *counts_dev, uint8_t *status_dev,
+                           double *span_dev, double *intensity_dev, double *tau_dev,
+                           double *outside_dev_or_null, double *counted_dev, double *covered_dev);
+
+/* The channels a workgroup of avr_scene_ray_transfer keeps in LDS at a time: 1 .. 32, 0 restores
+ * the default of 16.  Every chunk of channels repeats the walk, and fewer workgroups fit a CU with
+ * a larger chunk; the results do not change.  It is there for tests and for timing. */
+int avr_context_set_ray_transfer_chunk(avr_context *ctx, int channels);
+
 #ifdef __cplusplus
 }
 #endif
