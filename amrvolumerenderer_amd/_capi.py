@@ -252,6 +252,11 @@ SIGNATURES = {
                                           C.c_double, _vp, _vp, _vp]),
     "avr_scene_grid_field": (C.c_int, [_vp, _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                        C.c_int, C.c_int, C.c_double, _vp]),
+    "avr_scene_particle_cells": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_int, _ip, _ip,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                           _vp, _vp, _vp, _vp]),
+    "avr_scene_particle_deposit": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_int,
+                                             C.POINTER(C.c_double), C.c_int]),
     "avr_fft_twiddles": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "avr_field_fft": (C.c_int, [_vp, _vp, _ip, _vp]),
     "avr_spectrum_bins": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -25,6 +25,7 @@ from .clumps import add_clump_field, clump_fields, remove_clump_field, threshold
 from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
 from .gridfields import (add_array_field, add_helmholtz_field, add_potential_field, grid_fields,
                          remove_grid_field)
+from .particles import add_particle_field, particle_fields, remove_particle_field
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
 
@@ -1363,6 +1364,78 @@ def _grid_field_scene(ctx, plotfile: str, entry: dict, inputs, geometry: "SceneG
     return scene
 
 
+# ---- particle fields ("Particle fields") ---------------------------------------------
+
+def deposit_scene(ctx, geometry: "SceneGeometry", positions, values, cell_sizes, prob_lo,
+                  ref_ratio, method: str = "cic", quantity: str = "density", rank: int = 0,
+                  n_ranks: int = 1, process_group=None, log_scale_input: bool = False,
+                  normalize_to_data_range: bool = True):
+    """Particles deposited onto the cells of a scene ("Particle fields"): positions
+    is a numpy or torch [n, 3] array in the plotfile's physical units, values an [n] array or None
+    (1.0 each); geometry is any loaded scene, whose boxes the result has.  With method "ngp" a
+    particle's value goes to the leaf cell that holds it; with "cic" it is shared among the eight
+    cell centres around it at the leaf's level, under the same-or-coarser rule of the
+    streamlines' corners, and the share of a corner that rule does not find (a domain face, a
+    hole, a region that finer cells cover) stays with the particle's own cell.  A cell's value is
+    the sum of its shares in particle order (quantity "sum"), or that sum over the cell's volume
+    ("density").  cell_sizes, prob_lo and ref_ratio as streamline_scene takes them.  Returns
+    (SceneGeometry, outside, rerouted): the particles without a leaf, which deposit nothing, and
+    the corner shares that stayed with their own cell.  The output is allocated as derive_scene's
+    is, and statistics and the scalar transform come from build_scene_geometry with the caller's
+    flags.  Every box of the scene must be on this rank: with n_ranks > 1, or fewer local boxes
+    than boxes, NotImplementedError is raised before any device work."""
+    from . import particles
+    particles.check_method(method)
+    particles.check_quantity(quantity)
+    positions, values = particles.check_arrays(positions, values)
+    _require_one_rank(geometry, n_ranks, "a particle field needs every box of the scene on one "
+                      "rank: a particle's cloud is not shared between ranks")
+    sizes, ratios, index = _level_setup(geometry, geometry.local_boxes, cell_sizes, prob_lo,
+                                        ref_ratio)
+    written = _blank_like(ctx, geometry, rank)
+    with _native_scenes(ctx, [written]) as (out,):
+        cells, shares, _, totals = out.particle_cells(
+            positions, values, particles.METHODS.index(method), index, ratios, sizes, prob_lo)
+        out.particle_deposit(cells, shares, particles.QUANTITIES.index(quantity), sizes)
+        ctx.synchronize()
+        outside, rerouted = (int(v) for v in totals.cpu().tolist())
+    return _computed_scene(ctx, written, log_scale_input, normalize_to_data_range, process_group,
+                           n_ranks), outside, rerouted
+
+
+def particle_cells(plotfile: str, positions, min_level: int = 0, max_level: int = -1) -> dict:
+    """The leaf cell of every particle of positions [n, 3] (the plotfile's physical units) among
+    the loaded levels, on cuda:0.  Returns a dict of numpy arrays: level uint8 [n] (255 for a
+    particle outside the loaded cells), ordinal int64 [n] (the cell ordinal of "Clumps", -1
+    outside) and centres float64 [n, 3] = prob_lo + (f64(I) + 0.5) * dx_l (NaN outside)."""
+    import numpy as np
+    import torch
+    from . import particles
+    from . import plotfile as pf
+    positions, _ = particles.check_arrays(positions, None)
+    ctx, rank, world, group, scenes, volumes = _load_fields(plotfile, [""], min_level, max_level)
+    scene = scenes[0]
+    _require_one_rank(scene, world, "a particle field needs every box of the scene on one rank: "
+                      "a particle's cloud is not shared between ranks")
+    header = pf.PlotFileData(plotfile)
+    levels = _header_levels(header, len(volumes))
+    sizes, ratios, index = _level_setup(scene, scene.local_boxes, *levels)
+    with _native_scenes(ctx, [scene]) as (native,):
+        cells, _, level_of, _ = native.particle_cells(positions, None, 0, index, ratios, sizes,
+                                                      levels[1], levels=True)
+        cells = cells.reshape(-1)
+        inside = level_of != 255
+        # the centres of the cells that were found, through the clump members' lookup
+        found = cells[inside].contiguous()
+        _, centres, _ = native.clump_member_data(found, index, ratios, sizes, levels[1])
+        ctx.synchronize()
+        inside = inside.cpu().numpy()
+        where = np.full((inside.size, 3), np.nan)
+        where[inside] = centres.cpu().numpy().T
+        ordinal = torch.where(level_of != 255, cells, torch.full_like(cells, -1)).cpu().numpy()
+    return {"level": level_of.cpu().numpy(), "ordinal": ordinal, "centres": where}
+
+
 # ---- power spectra (DESIGN.md 7, "Power spectrum") ------------------------------------------------
 
 def power_spectrum_scene(ctx, scene: "SceneGeometry", level: int, lo, dims, cell_sizes, prob_lo,
@@ -2044,17 +2117,22 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
     caller's flags.  A registered grid field's inputs (gridfields.py: a potential's source, a
     Helmholtz field's three components, nothing for an array) are resolved raw, its grid is
     computed on the device and grid_scene writes it onto their boxes with the caller's flags; the
-    grid fields of one call share what they have in common (_grid_product_device).  Resolution is
+    grid fields of one call share what they have in common (_grid_product_device).  A registered
+    particle field (particles.py) has no inputs: its positions and values go to the device once
+    per call and deposit_scene puts them onto the boxes of the plotfile's first variable with the
+    caller's flags.  Resolution is
     recursive -- a derived field may read gradient or grid fields, a gradient field may take a
     derived or another gradient field, a potential a derived density -- and every name is loaded
     or computed once per call and pair of flags, however many names need it."""
     from . import clumps as clump_rules
-    from . import derive, gradient, gridfields
+    from . import derive, gradient, gridfields, particles
     from . import plotfile as pf
     registered = derive.derived_fields()
     gradients = gradient.gradient_fields()
     clump_names = clump_rules.clump_fields()
     grid_names = gridfields.grid_fields()
+    particle_names = particles.particle_fields()
+    particle_arrays = {}   # name -> (positions, values) on the device
     resolved = {}
     shared_grids = {}      # what the grid fields of this call share: spectra and grids by product
     header = []
@@ -2093,6 +2171,21 @@ def _load_variable_scenes(ctx, plotfile: str, names, min_level: int, max_level: 
             scene = _grid_field_scene(ctx, plotfile, entry, inputs, geometry, shared_grids,
                                       min_level, max_level, rank, n_ranks, process_group, log,
                                       normalize)
+        elif name in particle_names:
+            # the plotfile's first variable gives the boxes, as for an array grid field; the
+            # positions and values go to the device once per call
+            entry = particle_names[name]
+            geometry = resolve("", False, True)
+            if name not in particle_arrays:
+                import torch
+                particle_arrays[name] = tuple(
+                    None if a is None else torch.from_numpy(a).to(ctx.device)
+                    for a in (entry["positions"], entry["values"]))
+            finest = max(int(b.level) for b in geometry.all_boxes)
+            scene, _, _ = deposit_scene(ctx, geometry, *particle_arrays[name],
+                                        *_header_levels(plotfile_header(), finest + 1),
+                                        entry["method"], entry["quantity"], rank, n_ranks,
+                                        process_group, log, normalize)
         elif name in registered:
             program = derive.compile_field(name)
             _check_derived_inputs(plotfile, plotfile_header(), name, program)
@@ -2115,9 +2208,11 @@ def _check_variable(plotfile: str, header, name: str, needed_by: str = "") -> No
     """RuntimeError unless `name` is a stored variable of the plotfile or a registered derived,
     gradient, clump or grid field whose own inputs are."""
     from . import clumps as clump_rules
-    from . import derive, gradient, gridfields
+    from . import derive, gradient, gridfields, particles
     gradients = gradient.gradient_fields()
     clump_names = clump_rules.clump_fields()
+    if name in particles.particle_fields():
+        return                         # made of the caller's arrays: nothing of the plotfile's
     if name in gridfields.grid_fields():
         for of in gridfields.inputs_of(name):
             _check_variable(plotfile, header, of, f"grid field '{name}'")

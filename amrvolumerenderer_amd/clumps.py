@@ -54,6 +54,9 @@ def add_clump_field(name: str, of: str, lower: float = -math.inf, upper: float =
     from . import gridfields
     if name in gridfields.grid_fields():
         raise ValueError(f"{name!r} is a registered grid field")
+    from . import particles
+    if name in particles.particle_fields():
+        raise ValueError(f"{name!r} is a registered particle field")
     lower, upper = check_bounds(lower, upper)
     trial = dict(_registry)
     trial[name] = (of, lower, upper)

@@ -1,7 +1,7 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
 // streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials,
-// structure functions, velocity cubes):
+// structure functions, velocity cubes, particle fields):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -2753,6 +2753,177 @@ inline VelocityCubePlan plan_velocity_cube(const avr_box* e, const avr_box* g, c
   t.du = du;
   t.dv = dv;
   plan.set_batch(0, &r, &t);
+  return plan;
+}
+
+// ---- particle fields ------------------------------------------------------------------------
+struct ParticleCellsPlan {
+  std::vector<ParticleBoxDev> boxes;
+  std::vector<uint32_t> cell_begin;   // n_boxes + 1: prefix sum of the boxes' cells, in scene order
+  IsoLevelsDev levels;
+  StreamLocatorDev locator;           // build_level_locator's
+  std::vector<uint32_t> block_begin;  // blocks + 1 ({0} for a scene without cells)
+  std::vector<int32_t> block_boxes;
+  ParticleCellsArgs args{};
+  template <class Visit>
+  void visit_tables(ParticleCellsArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->cell_begin, cell_begin.data(), cell_begin.size());
+    visit(&to->levels, &levels, 1);
+    visit(&to->block_begin, block_begin.data(), block_begin.size());
+    visit(&to->block_boxes, block_boxes.data(), block_boxes.size());
+  }
+};
+// The contributions of n particles to the cells of the boxes `scene` ("Particle
+// fields").  box_index_lo, level_ratio, level_cell_size and prob_lo as plan_streamlines takes them.
+// points [n][3], values [n] (may be null), cells and shares [n][C] with C = 1 (method 0, nearest
+// grid point) or 8 (method 1, cloud in cell), levels [n] (may be null) and totals [2] are device
+// arrays; all but totals are free to be null with n == 0.  The rules, in this order: n_levels, null
+// arrays, method, n (below 2^31, with eight entries each below 2^28), the cell sizes, prob_lo, the
+// box rules, the ratios, the index ranges, boxes of one level apart in index space, fewer than 2^31
+// cells, the locator's size (max_entries: the bound on its lists, lowered by the plan's test
+// only), no output byte shared with another output, with the points or with the values.
+inline ParticleCellsPlan plan_particle_cells(const avr_box* scene, size_t n_boxes, uint64_t n,
+                                             int method, const int32_t* box_index_lo,
+                                             const int32_t* level_ratio,
+                                             const double* level_cell_size, const double* prob_lo,
+                                             int n_levels, const void* points, const void* values,
+                                             const void* cells, const void* shares,
+                                             const void* levels_out, const void* totals,
+                                             int64_t max_entries = kStreamMaxEntries) {
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(n_levels == 1 || level_ratio != nullptr, "null argument");
+  require_box(n_boxes == 0 || box_index_lo != nullptr, "null argument");
+  require_box(level_cell_size != nullptr && prob_lo != nullptr && totals != nullptr,
+              "null argument");
+  require_box(n == 0 || (points != nullptr && cells != nullptr && shares != nullptr),
+              "null argument");
+  require_box(method == kParticleNgp || method == kParticleCic,
+              "method must be 0 (nearest grid point) or 1 (cloud in cell)");
+  require_box(n < (uint64_t{1} << (method == kParticleCic ? 28 : 31)),
+              method == kParticleCic ? "n must stay below 2^28 for cloud in cell"
+                                     : "n must stay below 2^31");
+  ParticleCellsPlan plan;
+  IsoLevelsDev& levels = plan.levels;
+  fill_level_geometry(level_cell_size, prob_lo, n_levels, &levels);
+  std::vector<ParticleBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = scene[b];
+    const avr_box* fields[1] = {&first};
+    FieldView view;
+    ParticleBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    int32_t paired;
+    const bool has_cells = field_box_views(first, fields, 1, n_levels, &view, &paired);
+    dev.level = first.level;
+    if (has_cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+    }
+  }
+  fill_level_ratios(level_ratio, n_levels, levels.ratio);
+  const std::vector<IndexRegion> regions = box_index_regions(box_index_lo, scene, &boxes);
+  require_levels_disjoint(boxes, regions);
+  plan.cell_begin = cell_ordinals(boxes);
+  build_level_locator(boxes, regions, levels.ratio, max_entries, &plan.locator, &plan.block_begin,
+                      &plan.block_boxes);
+  const uint64_t entries = n * (method == kParticleCic ? 8u : 1u);
+  if (n > 0) {
+    ByteRanges read_ranges, write_ranges;
+    append_byte_range(&write_ranges, cells, entries * sizeof(int64_t));
+    append_byte_range(&write_ranges, shares, entries * sizeof(double));
+    if (levels_out != nullptr) append_byte_range(&write_ranges, levels_out, n);
+    append_byte_range(&write_ranges, totals, 2 * sizeof(uint64_t));
+    append_byte_range(&read_ranges, points, n * 3 * sizeof(double));
+    if (values != nullptr) append_byte_range(&read_ranges, values, n * sizeof(double));
+    const ByteRanges written = write_ranges;
+    require_disjoint(&write_ranges, "two output arrays overlap");
+    require_no_shared_byte(&read_ranges, written,
+                           "an output array overlaps the points or the values");
+  }
+  plan.args.locator = plan.locator;
+  plan.args.n_levels = n_levels;
+  plan.args.n = static_cast<uint32_t>(n);
+  plan.args.paired = ((reinterpret_cast<uintptr_t>(cells) | reinterpret_cast<uintptr_t>(shares)) &
+                      15u) == 0;
+  return plan;
+}
+
+struct ParticleDepositPlan {
+  std::vector<GridBoxDev> boxes;
+  std::vector<uint32_t> tile_begin;
+  std::vector<uint32_t> cell_begin;
+  ParticleLevelsDev levels;
+  ParticleDepositArgs args{};
+  template <class Visit>
+  void visit_tables(ParticleDepositArgs* to, Visit&& visit) const {
+    visit(&to->boxes, boxes.data(), boxes.size());
+    visit(&to->tile_begin, tile_begin.data(), tile_begin.size());
+    visit(&to->cell_begin, cell_begin.data(), cell_begin.size());
+    visit(&to->levels, &levels, 1);
+  }
+};
+// The contributions cells [n], shares [n] (device arrays, sorted by cell, free to be null with n ==
+// 0) added onto the cells of the boxes `out`: the sum, or with quantity 1 the sum over the volume
+// of a cell of the box's level.  The rules, in this order: n_levels, null arrays, quantity, n, the
+// cell sizes, the box rules, fewer than 2^31 cells, no byte of the cells or the shares shared with
+// an output box's cells.  That the cells ascend is the caller's to see to: they live on the device.
+inline ParticleDepositPlan plan_particle_deposit(const avr_box* out, size_t n_boxes, uint64_t n,
+                                                 int quantity, const double* level_cell_size,
+                                                 int n_levels, const void* cells,
+                                                 const void* shares) {
+  require_box(n_levels >= 1 && n_levels <= kFieldMaxLevels, "n_levels must lie in [1, 16]");
+  require_box(level_cell_size != nullptr, "null argument");
+  require_box(n == 0 || (cells != nullptr && shares != nullptr), "null argument");
+  require_box(quantity == kParticleSum || quantity == kParticleDensity,
+              "quantity must be 0 (sum) or 1 (density)");
+  require_box(n < (uint64_t{1} << 31), "n_contributions must stay below 2^31");
+  ParticleDepositPlan plan;
+  for (int l = 0; l < kFieldMaxLevels; ++l) plan.levels.volume[l] = 1.0;
+  for (int l = 0; l < n_levels; ++l) {
+    const double* size = level_cell_size + l * 3;
+    for (int d = 0; d < 3; ++d) {
+      require_box(std::isfinite(size[d]) && size[d] > 0.0,
+                  "level_cell_size must be finite and positive");
+    }
+    plan.levels.volume[l] = (size[0] * size[1]) * size[2];
+  }
+  std::vector<GridBoxDev>& boxes = plan.boxes;
+  boxes.resize(n_boxes);
+  plan.tile_begin.assign(1, 0u);
+  ByteRanges read_ranges, write_ranges;
+  for (size_t b = 0; b < n_boxes; ++b) {
+    const avr_box& first = out[b];
+    const avr_box* fields[1] = {&first};
+    FieldView view;
+    GridBoxDev& dev = boxes[b];
+    std::memset(&dev, 0, sizeof(dev));
+    const bool has_cells = field_box_views(first, fields, 1, n_levels, &view, &dev.paired);
+    dev.out = const_cast<double*>(view.cells);
+    dev.jstride = view.jstride;
+    dev.kstride = view.kstride;
+    dev.level = first.level;
+    if (has_cells) {
+      dev.nx = first.dims[0];
+      dev.ny = first.dims[1];
+      dev.nz = first.dims[2];
+      append_byte_range(&write_ranges, view);
+    }
+    append_tiles(&plan.tile_begin, has_cells ? cell_tiles(dev.nx, dev.ny, dev.nz) : 0u);
+  }
+  plan.cell_begin = cell_ordinals(boxes);
+  if (n > 0) {
+    append_byte_range(&read_ranges, cells, n * sizeof(int64_t));
+    append_byte_range(&read_ranges, shares, n * sizeof(double));
+    require_no_shared_byte(&read_ranges, write_ranges,
+                           "the cells or the shares overlap an output box's cells");
+  }
+  plan.args.n_boxes = static_cast<int32_t>(n_boxes);
+  plan.args.n_tiles = plan.tile_begin.back();
+  plan.args.n_cells = plan.cell_begin.back();
+  plan.args.n = static_cast<uint32_t>(n);
   return plan;
 }
 

@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, grid fields, rays, per-ray sums, ray transfer, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, particle fields, rays, per-ray sums, ray transfer, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -441,6 +441,54 @@ int avr_scene_grid_field(avr_context* ctx, avr_scene* out, const double* grid_de
     args.grid = grid_dev;
     args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     return avr::launch_grid_field(args, ctx->stream);
+  });
+}
+
+int avr_scene_particle_cells(avr_context* ctx, const avr_scene* scene, const double* points_dev,
+                             uint64_t n, const double* values_dev, int method,
+                             const int32_t* box_index_lo, const int32_t* level_ratio,
+                             const double* level_cell_size, const double* prob_lo, int n_levels,
+                             int64_t* cells_dev, double* shares_dev, uint8_t* levels_dev,
+                             int64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(scene != nullptr, "null argument");
+    const size_t n_boxes = scene->boxes.size();
+    require_field_scene(ctx, scene, n_boxes);
+    const avr::ParticleCellsPlan plan = avr::plan_particle_cells(
+        scene->boxes.data(), n_boxes, n, method, box_index_lo, level_ratio, level_cell_size,
+        prob_lo, n_levels, points_dev, values_dev, cells_dev, shares_dev, levels_dev, totals_dev);
+    if (n == 0) return AVR_OK;
+    avr::ParticleCellsArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.points = points_dev;
+    args.values = values_dev;
+    args.cells = reinterpret_cast<long long*>(cells_dev);
+    args.shares = shares_dev;
+    args.levels_out = levels_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_particle_cells(args, method, ctx->stream);
+  });
+}
+
+int avr_scene_particle_deposit(avr_context* ctx, avr_scene* out, const int64_t* cells_sorted_dev,
+                               const double* shares_sorted_dev, uint64_t n_contributions,
+                               int quantity, const double* level_cell_size, int n_levels) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    require(out != nullptr, "null argument");
+    const size_t n_boxes = out->boxes.size();
+    require_field_scene(ctx, out, n_boxes);
+    const avr::ParticleDepositPlan plan = avr::plan_particle_deposit(
+        out->boxes.data(), n_boxes, n_contributions, quantity, level_cell_size, n_levels,
+        cells_sorted_dev, shares_sorted_dev);
+    for (auto& key : out->classified_key) key.clear();
+    if (plan.args.n_tiles == 0) return AVR_OK;
+    avr::ParticleDepositArgs args = plan.args;
+    stage_tables(ctx, plan, &args);
+    args.cells = reinterpret_cast<const long long*>(cells_sorted_dev);
+    args.shares = shares_sorted_dev;
+    return avr::launch_particle_deposit(args, quantity, ctx->stream);
   });
 }
 

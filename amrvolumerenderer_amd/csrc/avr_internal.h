@@ -961,6 +961,59 @@ struct GridFieldArgs {
 };
 int launch_grid_field(const GridFieldArgs& args, void* stream);
 
+// Particle fields (avr_particles.hip; DESIGN.md 7, "Particle fields"): particles deposited onto the
+// cells of a scene's boxes.  particle_cells_kernel finds every particle's leaf through the
+// streamlines' locator and writes its contributions (cell ordinal, share), one (nearest grid point)
+// or eight (cloud in cell) per particle; the caller sorts them by cell, stably;
+// particle_clear_kernel writes +0.0 to every cell and particle_sum_kernel adds each cell's run of
+// shares in list order.  A box as the first kernel reads it:
+constexpr long long kParticleOutside = 0xFFFFFFFFll;  // the cell of an outside particle's entries
+constexpr int kParticleNgp = 0, kParticleCic = 1;     // the methods
+constexpr int kParticleSum = 0, kParticleDensity = 1;  // the quantities
+struct alignas(16) ParticleBoxDev {
+  int32_t nx, ny, nz;     // 0 for a box without cells
+  int32_t level;          // 0 .. n_levels - 1
+  int32_t lo[3];          // the index of the box's first cell in its level's index space
+  int32_t pad_;
+};
+static_assert(sizeof(ParticleBoxDev) == 32, "ParticleBoxDev: 16-byte multiple");
+struct ParticleCellsArgs {
+  const ParticleBoxDev* boxes;
+  const uint32_t* cell_begin;   // n_boxes + 1: prefix sum of the boxes' cells, in scene order
+  const uint32_t* block_begin;  // blocks + 1
+  const int32_t* block_boxes;
+  const IsoLevelsDev* levels;   // cell sizes, prob_lo and ratios as the isosurfaces stage them
+  StreamLocatorDev locator;
+  int32_t n_levels;
+  uint32_t n;                   // particles: < 2^31 (ngp), < 2^28 (cic)
+  int32_t paired;               // cells and shares 16-byte aligned: a lane's entries store as pairs
+  const double* points;         // [n][3]
+  const double* values;         // [n], or null: every value is 1.0
+  long long* cells;             // [n][C], C = 1 or 8
+  double* shares;               // [n][C]
+  uint8_t* levels_out;          // [n], or null
+  unsigned long long* totals;   // [2]: outside particles, rerouted corner shares; added into
+};
+int launch_particle_cells(const ParticleCellsArgs& args, int method, void* stream);
+struct ParticleLevelsDev {
+  double volume[kFieldMaxLevels];  // [l]: (dx_l * dy_l) * dz_l (1.0 from n_levels on)
+};
+// The output's boxes are GridBoxDev (lo unused).
+struct ParticleDepositArgs {
+  const GridBoxDev* boxes;
+  const uint32_t* tile_begin;   // n_boxes + 1: prefix sum of the boxes' tiles
+  const uint32_t* cell_begin;   // n_boxes + 1: prefix sum of the boxes' cells
+  const ParticleLevelsDev* levels;
+  int32_t n_boxes;
+  uint32_t n_tiles;
+  uint32_t n_cells;             // < 2^31; an ordinal that is not below it names no cell
+  uint32_t n;                   // contributions, < 2^31
+  const long long* cells;       // [n], ascending
+  const double* shares;         // [n]
+};
+// The clear, then (with n > 0) the sum.
+int launch_particle_deposit(const ParticleDepositArgs& args, int quantity, void* stream);
+
 // Ray transfer (avr_rays.hip; DESIGN.md 7, "Ray transfer"): emission and absorption along the same
 // walk, front to back.  The walk's field is the source function S; the opacity a, the bin field g
 // and the width s are read at the same cell through their own box tables.  Grey (no g) keeps its

@@ -308,6 +308,9 @@ def add_field(name: str, expression: str) -> DerivedProgram:
     grid_fields = gridfields.grid_fields()
     if name in grid_fields:
         raise ValueError(f"{name!r} is a registered grid field")
+    from . import particles
+    if name in particles.particle_fields():
+        raise ValueError(f"{name!r} is a registered particle field")
     trial = dict(_registry)
     trial[name] = expression
     program = compile_expression(name if name.isidentifier() else f"field({name!r})", trial)

@@ -20,9 +20,11 @@ def _dependencies(name: str, derived: Dict[str, str], gradients: Dict[str, Tuple
     """The names `name` is made of, one step down: a gradient or clump field's input, a registered
     grid field's inputs (gridfields.py), or the fields a derived field reads once the derived
     fields it names are inlined; () for anything else."""
-    from . import derive, gridfields
+    from . import derive, gridfields, particles
     if name in gridfields.grid_fields():
         return gridfields.inputs_of(name)
+    if name in particles.particle_fields():
+        return ()                      # a particle field reads no field: a leaf of the graph
     if name in gradients:
         return (gradients[name][0],)
     if name in clumps:
@@ -74,6 +76,9 @@ def add_gradient_field(name: str, of: str, axis) -> None:
     from . import gridfields
     if name in gridfields.grid_fields():
         raise ValueError(f"{name!r} is a registered grid field")
+    from . import particles
+    if name in particles.particle_fields():
+        raise ValueError(f"{name!r} is a registered particle field")
     if isinstance(axis, bool) or axis not in AXES:
         raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z'")
     trial = dict(_registry)

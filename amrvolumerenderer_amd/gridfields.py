@@ -21,7 +21,7 @@ _registry: Dict[str, dict] = {}
 
 
 def _check_name(name) -> None:
-    """The names every registry refuses, and a name one of the other three holds."""
+    """The names every registry refuses, and a name one of the other four holds."""
     from . import clumps, derive, gradient
     if not isinstance(name, str) or not name:
         raise ValueError("a grid field's name must be a non-empty string")
@@ -34,6 +34,9 @@ def _check_name(name) -> None:
         raise ValueError(f"{name!r} is a registered gradient field")
     if name in clumps.clump_fields():
         raise ValueError(f"{name!r} is a registered clump field")
+    from . import particles
+    if name in particles.particle_fields():
+        raise ValueError(f"{name!r} is a registered particle field")
 
 
 def _check_input(of, what: str) -> str:

@@ -1518,6 +1518,72 @@ class Scene:
                 _pointer(totals))
         return totals
 
+    def particle_cells(self, points, values, method: int, box_index_lo, level_ratio,
+                       level_cell_size, prob_lo, levels: bool = False,
+                       totals: Optional[torch.Tensor] = None):
+        """avr_scene_particle_cells with this scene's boxes: the contributions of the particles at
+        points (float64 [n, 3] in physical units; a tensor on the device, or anything numpy takes)
+        with values (float64 [n] likewise, or None: 1.0 each) to the cells of this scene's boxes,
+        method 0 (nearest grid point, one entry per particle) or 1 (cloud in cell, eight).
+        box_index_lo, level_ratio, level_cell_size and prob_lo as streamlines takes them.  Returns
+        (cells int64 [n, C] -- cell ordinals, 0xFFFFFFFF for a particle outside --, shares float64
+        [n, C], levels uint8 [n] (255 outside) or None without levels, totals int64 [2]: outside
+        particles and rerouted corner shares; a tensor handed in is added to) on the device.
+        Asynchronous on the context's stream."""
+        ctx = self.ctx
+        index, ratios, sizes, origin = _level_arguments(len(self.boxes), box_index_lo,
+                                                        level_ratio, level_cell_size, prob_lo)
+        method = int(method)
+        if method not in (0, 1):
+            raise ValueError("method must be 0 (nearest grid point) or 1 (cloud in cell)")
+        points = _device_points(ctx, points, "points must hold three values per particle")
+        n = int(points.shape[0])
+        if values is not None:
+            if not isinstance(values, torch.Tensor):
+                values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64))
+            values = values.to(device=ctx.device, dtype=torch.float64).contiguous()
+            if tuple(values.shape) != (n,):
+                raise ValueError("values must hold one value per particle")
+        entries = 8 if method == 1 else 1
+        cells = torch.empty((n, entries), dtype=torch.int64, device=ctx.device)
+        shares = torch.empty((n, entries), dtype=torch.float64, device=ctx.device)
+        level_of = torch.empty(n, dtype=torch.uint8, device=ctx.device) if levels else None
+        totals = _output(ctx, totals, torch.int64, (2,), "totals", torch.zeros,
+                         "totals must hold two values")
+        _native(ctx, "avr_scene_particle_cells", ctx._handle, self._handle, _pointer(points), n,
+                _pointer(values), method, _ints(index), _ints(ratios), _doubles(sizes),
+                _doubles(origin), int(sizes.shape[0]), _pointer(cells), _pointer(shares),
+                _pointer(level_of), _pointer(totals))
+        return cells, shares, level_of, totals
+
+    def particle_deposit(self, cells: torch.Tensor, shares: torch.Tensor, quantity: int,
+                         level_cell_size) -> None:
+        """avr_scene_particle_deposit with this scene as the output: overwrites every cell of
+        this scene's boxes with the sum of the shares that name it -- particle_cells' entries
+        (int64 and float64 tensors of one shape on the device), sorted here by cell with a stable
+        sort, so that a cell's shares are added in list order -- or, with quantity 1, that sum
+        over the volume of a cell of the box's level (level_cell_size: [n_levels, 3] float64).  A
+        cell nothing names gets +0.0.  Asynchronous on the context's stream."""
+        ctx = self.ctx
+        ctx._check_tensor(cells, torch.int64, "cells")
+        ctx._check_tensor(shares, torch.float64, "shares")
+        if tuple(cells.shape) != tuple(shares.shape):
+            raise ValueError("cells and shares must have one shape")
+        quantity = int(quantity)
+        if quantity not in (0, 1):
+            raise ValueError("quantity must be 0 (sum) or 1 (density)")
+        sizes = np.ascontiguousarray(level_cell_size, dtype=np.float64)
+        if sizes.ndim != 2 or sizes.shape[1] != 3 or sizes.shape[0] < 1:
+            raise ValueError("level_cell_size must hold three values per level")
+        n = int(cells.numel())
+        ordered = picked = None
+        if n:
+            # stable: equal cells stay in list order, the order the definition adds them in
+            ordered, order = torch.sort(cells.reshape(-1), stable=True)
+            picked = shares.reshape(-1)[order]
+        _native(ctx, "avr_scene_particle_deposit", ctx._handle, self._handle, _pointer(ordered),
+                _pointer(picked), n, quantity, _doubles(sizes), int(sizes.shape[0]))
+
     def set_classification_cache(self, enabled: bool) -> None:
         """avr_scene_set_classification_cache: keep classified volumes across frames while the
         boxes, the scalar transform and the scalar range are unchanged (off by default)."""

@@ -1468,6 +1468,59 @@ int avr_scene_grid_field(avr_context *ctx, avr_scene *out, const double *grid_de
                          const int32_t *level_ratio, int n_levels, int interpolation, int periodic,
                          double fill, int64_t *totals_dev);
 
+/* ---- particle fields ("Particle fields") ---------------------------------------------- */
+
+/* The contributions of n particles to the cells of the boxes of `scene` (a scene of ctx; only its
+ * boxes' dims and levels are read, never its cells).  points_dev: device, f64 [n][3], physical
+ * units; values_dev: device, f64 [n], or NULL for a value of 1.0 each.  The hierarchy description
+ * (box_index_lo, level_ratio, level_cell_size, prob_lo, n_levels <= 16; host) is
+ * avr_scene_streamlines'.  A particle's leaf is the streamlines' leaf of a point P (levels from the
+ * finest, q = (P - prob_lo) / dx_l, each q finite and inside [-2^30, 2^30)); a particle without one
+ * is outside.  A cell's ordinal is avr_scene_clumps': the cells of the boxes in scene order, (k ny
+ * + j) nx + i inside a box.
+ *  method 0 (nearest grid point), C = 1: (cell, share) = (the leaf's ordinal, v), v's bits kept.
+ *  method 1 (cloud in cell), C = 8: at the leaf's level l, u = q - 0.5, B = floor(u), w = u -
+ *    f64(B); for dk, then dj, then di ascending (entry c = 4 dk + 2 dj + di) the weight along an axis
+ *    is w for a 1 and 1.0 - w for a 0, share = ((wx * wy) * wz) * v (nothing fused, also for a weight
+ *    of 0), and the cell is the ordinal of the level-l index B + (di, dj, dk) under the
+ *    same-or-coarser rule of the streamlines' corners, or, where that rule finds none (a domain
+ *    face, a hole, a region that finer cells cover), the leaf's own: the share is rerouted.
+ * cells_dev (i64 [n][C]) and shares_dev (f64 [n][C]) are written particle-major; an outside
+ * particle's entries are (0xFFFFFFFF, +0.0).  levels_dev (u8 [n], or NULL) gets the leaf's level,
+ * 255 outside.  totals_dev (i64 [2]) is added into: outside particles, rerouted shares.  Equal
+ * arguments give equal bits.  Everything is checked on the host before any device work, in this
+ * order: AVR_ERR_INVALID_ARGUMENT for n_levels outside [1, 16], a null array (all but totals_dev may
+ * be NULL with n == 0), a method outside {0, 1}, n >= 2^31 (2^28 with method 1), a cell size that is
+ * not finite and positive, a prob_lo that is not finite, a box level >= n_levels (and the other box
+ * rules), a ratio below 2, a box index range outside [-2^30, 2^30), two boxes of one level that
+ * overlap in index space, 2^31 cells or more, a locator past its limits, and an output that shares
+ * a byte with another output, the points or the values -- and every output and the totals are
+ * untouched.  n == 0 launches nothing.  Asynchronous on the context's stream. */
+int avr_scene_particle_cells(avr_context *ctx, const avr_scene *scene, const double *points_dev,
+                             uint64_t n, const double *values_dev, int method,
+                             const int32_t *box_index_lo, const int32_t *level_ratio,
+                             const double *level_cell_size, const double *prob_lo, int n_levels,
+                             int64_t *cells_dev, double *shares_dev, uint8_t *levels_dev,
+                             int64_t *totals_dev);
+
+/* Contributions added onto the cells of the boxes of `out` (a scene of ctx, whose cells are
+ * overwritten and whose classification is forgotten).  cells_sorted_dev (device, i64 [n]) and
+ * shares_sorted_dev (device, f64 [n]) are avr_scene_particle_cells' entries sorted by cell, equal
+ * cells in their list order (a stable sort).  Every cell of every box gets s = +0.0, then s = s +
+ * share over the entries that name its ordinal, in ascending position; its value is s (quantity
+ * 0, sum) or s / vol_l (quantity 1, density; one division, vol_l = (dx_l * dy_l) * dz_l of the
+ * box's level, from level_cell_size, f64 [n_levels][3], host).  A cell no entry names holds +0.0.
+ * An entry whose cell names no cell of `out` (0xFFFFFFFF among them) is skipped.  The order is not
+ * checked: each maximal run of equal cells is summed on its own, and a cell named by several runs
+ * keeps one run's sum.  AVR_ERR_INVALID_ARGUMENT, before any device work and in this order, for
+ * n_levels outside [1, 16], a null array (both may be NULL with n_contributions == 0), a quantity
+ * outside {0, 1}, n_contributions >= 2^31, a cell size that is not finite and positive, the box
+ * rules, 2^31 cells or more, and cells or shares that share a byte with a box's cells -- and `out`
+ * is untouched.  n_contributions == 0 still clears.  Asynchronous on the context's stream. */
+int avr_scene_particle_deposit(avr_context *ctx, avr_scene *out, const int64_t *cells_sorted_dev,
+                               const double *shares_sorted_dev, uint64_t n_contributions,
+                               int quantity, const double *level_cell_size, int n_levels);
+
 /* ---- rays ("Rays") -------------------------------------------------------------------- */
 
 /* Line-outs: for each of n_rays segments A -> B (start_dev, end_dev: device, f64 [n][3], physical
