@@ -257,6 +257,11 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp]),
     "avr_scene_particle_deposit": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_int,
                                              C.POINTER(C.c_double), C.c_int]),
+    "avr_particle_group_cells": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), _ip, _ip, _vp, _vp, _vp]),
+    "avr_particle_groups": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_double,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), _ip, _ip,
+                                      C.c_int64, _vp, _vp, _vp, _vp]),
     "avr_fft_twiddles": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "avr_field_fft": (C.c_int, [_vp, _vp, _ip, _vp]),
     "avr_spectrum_bins": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -26,6 +26,7 @@ from .gradient import add_gradient_field, gradient_fields, remove_gradient_field
 from .gridfields import (add_array_field, add_helmholtz_field, add_potential_field, grid_fields,
                          remove_grid_field)
 from .particles import add_particle_field, particle_fields, remove_particle_field
+from .groups import linking_length
 from .types import AmrBox, CameraParameters, ColorMapControlPoint, ScalarTransform, VolumeBounds
 
 
@@ -1434,6 +1435,87 @@ def particle_cells(plotfile: str, positions, min_level: int = 0, max_level: int 
         where[inside] = centres.cpu().numpy().T
         ordinal = torch.where(level_of != 255, cells, torch.full_like(cells, -1)).cpu().numpy()
     return {"level": level_of.cpu().numpy(), "ordinal": ordinal, "centres": where}
+
+
+# ---- particle groups ("Particle groups") ----------------------------------------------
+
+def particle_groups(positions, linking_length, masses=None, velocities=None,
+                    min_members: int = 20, domain=None, periodic=False, max_pair_tests=None,
+                    output: Optional[str] = None, ctx=None) -> dict:
+    """Friends-of-friends groups of particles ("Particle groups"): positions is a
+    numpy or torch [n, 3] array; two particles are linked iff they are at most linking_length
+    apart (api.linking_length gives the conventional 0.2 mean separations), a group is a connected
+    set of linked particles, and the groups of at least min_members members are numbered 1..count
+    by their smallest particle index.  domain is (lo, hi) or a plotfile, whose prob_lo and prob_hi
+    are taken; without one the box is the bounding box of the finite positions and periodic must
+    be false.  periodic is a flag or three: on a periodic axis distances are minimum-image ones
+    over the domain's extent, which must be more than three linking lengths, and a particle not in
+    [lo, hi) there is outside.  A particle with a coordinate that is not finite is outside too;
+    outside particles link to nothing and have label 0.
+
+    The grouping runs on the device (ctx, or the runtime's context): the particles are binned into
+    a uniform grid of cells at least a linking length wide and every pair in the same or adjacent
+    cells is tested, so the cost is quadratic in a cell's occupancy.  The number of pair tests is
+    counted exactly beforehand, and above max_pair_tests (None: groups.DEFAULT_MAX_PAIR_TESTS)
+    ValueError names it before the link kernel is launched.  The result does not depend on the grid.
+
+    Returns a dict: n; labels int32 [n] (0: none); count; first int64 [count] (each group's
+    smallest member); offsets int64 [count + 1] and members int64 (particle indices by label, then
+    ascending: group g + 1 has members[offsets[g]:offsets[g + 1]]); mass [count] (masses, or 1.0
+    each) and centre [count, 3] (mass-weighted; on a periodic axis the first member's coordinate
+    plus the mean minimum-image offset from it, wrapped into the domain -- meaningless for a group
+    wider than half the period); with velocities also velocity [count, 3] (mass-weighted mean) and
+    dispersion [count] (1-D rms about it); outside; pair_tests; dims (the grid that was used).
+    The float sums are numpy's on the host.  output: an .npz file that gets the dict.
+    ValueError, before any device work, for wrong shapes, dtypes that are not real, a
+    linking_length that is not finite and positive, min_members below 1, and periodic without a
+    domain."""
+    import numpy as np
+    import torch
+    from . import groups
+    positions, masses, velocities, b, min_members, box, flags, cap = groups.check_arguments(
+        positions, linking_length, masses, velocities, min_members, domain, periodic,
+        max_pair_tests)
+    if cap is None:
+        cap = groups.DEFAULT_MAX_PAIR_TESTS
+    if ctx is None:
+        ctx = _runtime_scope()[0]
+    n = int(positions.shape[0])
+    if isinstance(positions, torch.Tensor):
+        points = positions.to(device=ctx.device, dtype=torch.float64).contiguous()
+    else:
+        points = torch.from_numpy(np.array(positions, dtype=np.float64, order="C")).to(ctx.device)
+    if box is None:
+        finite = torch.isfinite(points)
+        finite_lo, finite_hi = [None] * 3, [None] * 3
+        if n:
+            low = torch.where(finite, points, torch.full_like(points, math.inf)).amin(0).tolist()
+            high = torch.where(finite, points, torch.full_like(points, -math.inf)).amax(0).tolist()
+            for d in range(3):
+                if low[d] <= high[d]:
+                    finite_lo[d], finite_hi[d] = low[d], high[d]
+        box = groups.bounding_box(finite_lo, finite_hi, b)
+    lo, hi = box
+    dims = groups.choose_dims(n, b, lo, hi, flags)
+    points, cells, parent, totals = ctx.particle_group_cells(points, lo, hi, dims, flags)
+    labels, _, _, n_groups, pair_tests = ctx.particle_groups(
+        points, cells, parent, b, lo, hi, dims, flags, min_members, max_pair_tests=cap)
+    ctx.synchronize()
+    labels = labels.cpu().numpy()
+    count = int(n_groups.item())
+    offsets, members, first = groups.member_lists(labels, count)
+    host = points.cpu().numpy()
+    result = {"n": n, "labels": labels, "count": count, "first": first, "offsets": offsets,
+              "members": members}
+    result.update(groups.catalogue(
+        host, None if masses is None else groups._as_numpy(masses),
+        None if velocities is None else groups._as_numpy(velocities), offsets, members, lo, hi,
+        flags))
+    result.update({"outside": int(totals.item()), "pair_tests": int(pair_tests),
+                   "dims": tuple(int(v) for v in dims)})
+    if output:
+        np.savez(output, **{key: np.asarray(value) for key, value in result.items()})
+    return result
 
 
 # ---- power spectra (DESIGN.md 7, "Power spectrum") ------------------------------------------------

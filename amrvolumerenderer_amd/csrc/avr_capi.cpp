@@ -321,6 +321,7 @@ void avr_context_destroy(avr_context* ctx) {
   ctx->gradient_planes.release();
   ctx->clump_parents.release();
   ctx->iso_scratch.release();
+  ctx->group_counts.release();
   if (ctx->own_stream != nullptr) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }

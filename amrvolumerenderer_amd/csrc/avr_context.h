@@ -252,6 +252,7 @@ struct avr_context {
   avr::DeviceBuffer clump_parents;             // avr_scene_clumps' parent entries and chunk counts
   avr::DeviceBuffer clump_pair_partials;       // avr_clump_pair_energy's partial sums, one per item
   avr::DeviceBuffer iso_scratch;               // avr_scene_isosurface's shells and chunk counts
+  avr::DeviceBuffer group_counts;              // avr_particle_groups' counts per chunk
 };
 
 namespace avr {

@@ -1,7 +1,7 @@
 // The host plans of the field products (slice images, the joint histogram, on-axis projections,
 // derived fields, gradient fields, clumps with their members and pair energies, isosurfaces,
 // streamlines, covering grids, grid fields, rays, per-ray sums, power spectra, isolated potentials,
-// structure functions, velocity cubes, particle fields):
+// structure functions, velocity cubes, particle fields, particle groups):
 // everything a call works out from its arguments before
 // the first HIP call -- the argument rules, the box table, the tile prefix and the product's own
 // tables.  Host only and free of HIP and of the C ABI's handles, like avr_field_boxes.h whose box
@@ -2924,6 +2924,138 @@ inline ParticleDepositPlan plan_particle_deposit(const avr_box* out, size_t n_bo
   plan.args.n_tiles = plan.tile_begin.back();
   plan.args.n_cells = plan.cell_begin.back();
   plan.args.n = static_cast<uint32_t>(n);
+  return plan;
+}
+
+// ---- particle groups ------------------------------------------------------------------------
+// The grid of both calls: lo, hi finite with lo < hi; dims each in [1, 1024], their product below
+// 2^27, at least 3 on a periodic axis.  Fills *grid; the caller has checked the four for null.
+inline void fill_group_grid(const double* lo, const double* hi, const int32_t* dims,
+                            const int32_t* periodic, GroupGridDev* grid) {
+  for (int d = 0; d < 3; ++d) {
+    require_box(std::isfinite(lo[d]) && std::isfinite(hi[d]) && lo[d] < hi[d] &&
+                    std::isfinite(hi[d] - lo[d]),
+                "lo and hi must be finite with lo < hi");
+  }
+  uint64_t cells = 1;
+  for (int d = 0; d < 3; ++d) {
+    require_box(dims[d] >= 1 && dims[d] <= kGroupMaxDim, "dims must lie in [1, 1024]");
+    cells *= static_cast<uint64_t>(dims[d]);
+  }
+  require_box(cells < (uint64_t{1} << 27), "the grid must hold fewer than 2^27 cells");
+  for (int d = 0; d < 3; ++d) {
+    require_box(periodic[d] == 0 || dims[d] >= 3, "a periodic axis needs at least 3 cells");
+  }
+  for (int d = 0; d < 3; ++d) {
+    grid->lo[d] = lo[d];
+    grid->hi[d] = hi[d];
+    grid->length[d] = hi[d] - lo[d];
+    grid->h[d] = grid->length[d] / static_cast<double>(dims[d]);
+    grid->top[d] = static_cast<double>(dims[d] - 1);
+    grid->dims[d] = dims[d];
+    grid->periodic[d] = periodic[d] != 0 ? 1 : 0;
+  }
+}
+
+struct ParticleGroupCellsPlan {
+  ParticleGroupCellsArgs args{};
+};
+// The cells and parent entries of n particles ("Particle groups").  points [n][3],
+// cells [n], parent [n] and totals [1] are device arrays, all free to be null with n == 0; lo, hi,
+// dims and periodic are host arrays of three.  The rules, in this order: null arrays, n below 2^31,
+// lo and hi, the dims, no output byte shared with another output or with the points.
+inline ParticleGroupCellsPlan plan_particle_group_cells(uint64_t n, const double* lo,
+                                                        const double* hi, const int32_t* dims,
+                                                        const int32_t* periodic,
+                                                        const void* points, const void* cells,
+                                                        const void* parent, const void* totals) {
+  require_box(lo != nullptr && hi != nullptr && dims != nullptr && periodic != nullptr,
+              "null argument");
+  require_box(n == 0 || (points != nullptr && cells != nullptr && parent != nullptr &&
+                         totals != nullptr),
+              "null argument");
+  require_box(n < (uint64_t{1} << 31), "n must stay below 2^31");
+  ParticleGroupCellsPlan plan;
+  fill_group_grid(lo, hi, dims, periodic, &plan.args.grid);
+  if (n > 0) {
+    ByteRanges read_ranges, write_ranges;
+    append_byte_range(&write_ranges, cells, n * sizeof(uint32_t));
+    append_byte_range(&write_ranges, parent, n * sizeof(uint32_t));
+    append_byte_range(&write_ranges, totals, sizeof(uint64_t));
+    append_byte_range(&read_ranges, points, n * 3 * sizeof(double));
+    const ByteRanges written = write_ranges;
+    require_disjoint(&write_ranges, "two output arrays overlap");
+    require_no_shared_byte(&read_ranges, written, "an output array overlaps the points");
+  }
+  plan.args.n = static_cast<uint32_t>(n);
+  return plan;
+}
+
+// One count per chunk of kGroupChunk particles.
+struct GroupScratch {
+  ScratchPart chunk_counts;
+  size_t total = 0;
+};
+struct ParticleGroupsPlan {
+  ParticleGroupsArgs args{};
+  GroupScratch scratch;
+};
+// The groups of n particles of which the first n_inside sorted slots are inside.  points_sorted
+// [n][3], order [n] (i64), cell_begin [cells + 1] (i64), parent [n] (u32, read and written), labels
+// [n] (i32), sizes [n] (u32) and n_groups [1] (u64) are device arrays; all but n_groups are free to
+// be null with n == 0.  The rules, in this order: null arrays, n below 2^31, n_inside at most n, b
+// finite and positive, lo and hi, the dims, h >= b (1 + 2^-10) wherever dims > 1, min_members in
+// [1, 2^31), no output byte shared with another output or with an input.
+inline ParticleGroupsPlan plan_particle_groups(uint64_t n, uint64_t n_inside, double b,
+                                               const double* lo, const double* hi,
+                                               const int32_t* dims, const int32_t* periodic,
+                                               int64_t min_members, const void* points_sorted,
+                                               const void* order, const void* cell_begin,
+                                               const void* parent, const void* labels,
+                                               const void* sizes, const void* n_groups) {
+  require_box(lo != nullptr && hi != nullptr && dims != nullptr && periodic != nullptr &&
+                  n_groups != nullptr,
+              "null argument");
+  require_box(n == 0 || (points_sorted != nullptr && order != nullptr && cell_begin != nullptr &&
+                         parent != nullptr && labels != nullptr && sizes != nullptr),
+              "null argument");
+  require_box(n < (uint64_t{1} << 31), "n must stay below 2^31");
+  require_box(n_inside <= n, "n_inside must not exceed n");
+  require_box(std::isfinite(b) && b > 0.0, "the linking length must be finite and positive");
+  ParticleGroupsPlan plan;
+  GroupGridDev& grid = plan.args.grid;
+  fill_group_grid(lo, hi, dims, periodic, &grid);
+  const double least = b * 1.0009765625;  // b (1 + 2^-10), one rounding
+  for (int d = 0; d < 3; ++d) {
+    require_box(dims[d] == 1 || grid.h[d] >= least,
+                "a cell must be at least (1 + 2^-10) linking lengths wide");
+  }
+  require_box(min_members >= 1 && min_members < (int64_t{1} << 31),
+              "min_members must lie in [1, 2^31)");
+  const uint64_t cells = static_cast<uint64_t>(dims[0]) * static_cast<uint64_t>(dims[1]) *
+                         static_cast<uint64_t>(dims[2]);
+  if (n > 0) {
+    ByteRanges read_ranges, write_ranges;
+    append_byte_range(&write_ranges, parent, n * sizeof(uint32_t));
+    append_byte_range(&write_ranges, labels, n * sizeof(int32_t));
+    append_byte_range(&write_ranges, sizes, n * sizeof(uint32_t));
+    append_byte_range(&write_ranges, n_groups, sizeof(uint64_t));
+    append_byte_range(&read_ranges, points_sorted, n * 3 * sizeof(double));
+    append_byte_range(&read_ranges, order, n * sizeof(int64_t));
+    append_byte_range(&read_ranges, cell_begin, (cells + 1) * sizeof(int64_t));
+    const ByteRanges written = write_ranges;
+    require_disjoint(&write_ranges, "two output arrays overlap");
+    require_no_shared_byte(&read_ranges, written,
+                           "an output array overlaps the points, the order or the cell ranges");
+  }
+  plan.args.b2 = b * b;
+  plan.args.n = static_cast<uint32_t>(n);
+  plan.args.n_inside = static_cast<uint32_t>(n_inside);
+  plan.args.n_chunks = static_cast<uint32_t>((n + kGroupChunk - 1) / kGroupChunk);
+  plan.args.n_cells = static_cast<uint32_t>(cells);
+  plan.args.min_members = static_cast<uint32_t>(min_members);
+  plan.scratch.chunk_counts =
+      next_scratch_part(&plan.scratch.total, (plan.args.n_chunks + 1) * sizeof(uint32_t));
   return plan;
 }
 

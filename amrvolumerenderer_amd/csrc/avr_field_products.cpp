@@ -1,6 +1,6 @@
 // C ABI of the field products (include/avr_hip.h): the joint histogram, slice images, on-axis
 // projections, derived fields, gradient fields, clumps, their table, links, members and pair
-// energies, isosurfaces, streamlines, covering grids, grid fields, particle fields, rays, per-ray sums, ray transfer, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
+// energies, isosurfaces, streamlines, covering grids, grid fields, particle fields, particle groups, rays, per-ray sums, ray transfer, power spectra, inverse transforms, the per-mode operators, structure functions and velocity cubes.  Every rule on a call's plain arguments and boxes, what it
 // stages in which order, the counts it launches with and its scratch layout are its plan's
 // (avr_field_plans.h, host only, tested without a GPU); what is left here needs the device.  The
 // stager of a plan's tables (stage_tables) is avr_context.h's, shared with the frame path.
@@ -489,6 +489,55 @@ int avr_scene_particle_deposit(avr_context* ctx, avr_scene* out, const int64_t* 
     args.cells = reinterpret_cast<const long long*>(cells_sorted_dev);
     args.shares = shares_sorted_dev;
     return avr::launch_particle_deposit(args, quantity, ctx->stream);
+  });
+}
+
+int avr_particle_group_cells(avr_context* ctx, const double* points_dev, uint64_t n,
+                             const double* lo, const double* hi, const int32_t* dims,
+                             const int32_t* periodic, uint32_t* cells_dev, uint32_t* parent_dev,
+                             uint64_t* totals_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    const avr::ParticleGroupCellsPlan plan = avr::plan_particle_group_cells(
+        n, lo, hi, dims, periodic, points_dev, cells_dev, parent_dev, totals_dev);
+    if (n == 0) return AVR_OK;
+    avr::ParticleGroupCellsArgs args = plan.args;
+    args.points = points_dev;
+    args.cells = cells_dev;
+    args.parent = parent_dev;
+    args.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    return avr::launch_particle_group_cells(args, ctx->stream);
+  });
+}
+
+int avr_particle_groups(avr_context* ctx, const double* points_sorted_dev,
+                        const int64_t* order_dev, const int64_t* cell_begin_dev, uint64_t n,
+                        uint64_t n_inside, double b, const double* lo, const double* hi,
+                        const int32_t* dims, const int32_t* periodic, int64_t min_members,
+                        uint32_t* parent_dev, int32_t* labels_dev, uint32_t* sizes_dev,
+                        uint64_t* n_groups_dev) {
+  return guarded([&]() -> int {
+    bind_device(ctx);
+    const avr::ParticleGroupsPlan plan = avr::plan_particle_groups(
+        n, n_inside, b, lo, hi, dims, periodic, min_members, points_sorted_dev, order_dev,
+        cell_begin_dev, parent_dev, labels_dev, sizes_dev, n_groups_dev);
+    if (n == 0) {
+      avr::hip_check(hipMemsetAsync(n_groups_dev, 0, sizeof(uint64_t), ctx->stream),
+                     "hipMemsetAsync");
+      return AVR_OK;
+    }
+    ctx->group_counts.reserve(plan.scratch.total, ctx->stream, "avr_particle_groups",
+                              "hipMalloc(particle group counts)");
+    avr::ParticleGroupsArgs args = plan.args;
+    args.points = points_sorted_dev;
+    args.order = reinterpret_cast<const long long*>(order_dev);
+    args.cell_begin = reinterpret_cast<const long long*>(cell_begin_dev);
+    args.parent = parent_dev;
+    args.labels = labels_dev;
+    args.sizes = sizes_dev;
+    args.chunk_counts = scratch_part<uint32_t>(ctx->group_counts, plan.scratch.chunk_counts);
+    args.n_groups = reinterpret_cast<unsigned long long*>(n_groups_dev);
+    return avr::launch_particle_groups(args, ctx->stream);
   });
 }
 

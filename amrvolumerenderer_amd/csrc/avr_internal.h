@@ -1014,6 +1014,51 @@ struct ParticleDepositArgs {
 // The clear, then (with n > 0) the sum.
 int launch_particle_deposit(const ParticleDepositArgs& args, int quantity, void* stream);
 
+// Particle groups (avr_particle_groups.hip; DESIGN.md 7, "Particle groups"): friends-of-friends
+// groups of particles.  group_cells_kernel gives every particle a cell of a uniform grid over the
+// box and a parent entry; the caller sorts the particles by cell, stably; group_link_kernel tests
+// every pair of particles in the same or adjacent cells and unites the linked ones in the clumps'
+// lock-free union-find; flatten, count, scan, rank and label turn the roots into labels 1..N.  The
+// grid as both kernels read it (the plan fills it):
+constexpr uint32_t kGroupOutside = 0xffffffffu;  // the cell and the parent entry of an outside particle
+constexpr uint32_t kGroupChunk = 256;            // particles whose qualifying roots one workgroup counts
+constexpr int kGroupMaxDim = 1024;               // cells along an axis, at most
+struct GroupGridDev {
+  double lo[3], hi[3];
+  double h[3];        // (hi - lo) / dims
+  double length[3];   // hi - lo
+  double top[3];      // f64(dims - 1): the clamp of a cell index
+  int32_t dims[3];    // 1 .. 1024, product < 2^27
+  int32_t periodic[3];
+};
+struct ParticleGroupCellsArgs {
+  GroupGridDev grid;
+  uint32_t n;                  // particles, < 2^31
+  const double* points;        // [n][3]
+  uint32_t* cells;             // [n]
+  uint32_t* parent;            // [n]
+  unsigned long long* totals;  // [1]: outside particles; added into
+};
+int launch_particle_group_cells(const ParticleGroupCellsArgs& args, void* stream);
+struct ParticleGroupsArgs {
+  GroupGridDev grid;
+  double b2;                     // b * b
+  uint32_t n, n_inside;          // n_inside <= n < 2^31
+  uint32_t n_chunks;             // ceil(n / kGroupChunk)
+  uint32_t n_cells;              // the product of dims
+  uint32_t min_members;          // 1 .. 2^31 - 1
+  const double* points;          // [n][3], in sorted order
+  const long long* order;        // [n]: the particle in sorted slot i
+  const long long* cell_begin;   // [n_cells + 1]: the first sorted slot of each cell
+  uint32_t* parent;              // [n]: group_cells_kernel's on entry, roots on return
+  int32_t* labels;               // [n]
+  uint32_t* sizes;               // [n]: the members at a root's entry, 0 elsewhere
+  uint32_t* chunk_counts;        // [n_chunks]: scratch
+  unsigned long long* n_groups;  // [1]
+};
+// The sizes' clear, the link (with n_inside > 0), then flatten, count, scan, rank, label.
+int launch_particle_groups(const ParticleGroupsArgs& args, void* stream);
+
 // Ray transfer (avr_rays.hip; DESIGN.md 7, "Ray transfer"): emission and absorption along the same
 // walk, front to back.  The walk's field is the source function S; the opacity a, the bin field g
 // and the width s are read at the same cell through their own box tables.  Grey (no g) keeps its

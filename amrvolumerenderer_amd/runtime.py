@@ -470,6 +470,75 @@ class Context:
                 depth.ctypes.data_as(C.POINTER(C.c_int64)))
         return w, depth
 
+    # -- particle groups ----------------------------------------------------------------------
+    def particle_group_cells(self, points, lo, hi, dims, periodic,
+                             totals: Optional[torch.Tensor] = None):
+        """avr_particle_group_cells: the cell of every particle of points (float64 [n, 3]; a tensor
+        on the device, or anything numpy takes) in the uniform grid of dims cells over the box lo,
+        hi with the flags periodic ("Particle groups").  Returns (points as they lie
+        on the device, cells int32 [n] -- the cell's bits as uint32, all ones for a particle
+        outside --, parent int32 [n] likewise, totals int64 [1]: the outside particles; a tensor
+        handed in is added to).  Asynchronous on the context's stream."""
+        lo, hi, dims, periodic = _group_box(lo, hi, dims, periodic)
+        points = _device_points(self, points, "points must hold three values per particle")
+        n = int(points.shape[0])
+        cells = torch.empty(n, dtype=torch.int32, device=self.device)
+        parent = torch.empty(n, dtype=torch.int32, device=self.device)
+        totals = _output(self, totals, torch.int64, (1,), "totals", torch.zeros,
+                         "totals must hold one value")
+        _native(self, "avr_particle_group_cells", self._handle, _pointer(points), n, _doubles(lo),
+                _doubles(hi), _ints(dims), _ints(periodic), _pointer(cells), _pointer(parent),
+                _pointer(totals))
+        return points, cells, parent, totals
+
+    def particle_groups(self, points: torch.Tensor, cells: torch.Tensor, parent: torch.Tensor,
+                        linking_length: float, lo, hi, dims, periodic, min_members: int = 1,
+                        max_pair_tests: Optional[int] = None):
+        """avr_particle_groups behind the sort it needs: points, cells and parent as
+        particle_group_cells returned them, for the same box and dims.  The particles are sorted by
+        cell with a stable torch sort, the first slot of every cell is found with
+        torch.searchsorted and the points are gathered into that order (plumbing).  The number of
+        pair tests the link kernel will make is counted exactly from the cells' occupancies first;
+        above max_pair_tests (None: no cap) ValueError is raised and nothing more is launched.
+        Returns (labels int32 [n], parent int32 [n] -- each inside particle's root, in place --,
+        sizes int32 [n] -- the members at a root's index --, n_groups int64 [1]) on the device
+        and pair_tests, an int.  Synchronises once, for the counts; the native call itself is
+        asynchronous on the context's stream."""
+        lo, hi, dims, periodic = _group_box(lo, hi, dims, periodic)
+        self._check_tensor(points, torch.float64, "points")
+        self._check_tensor(cells, torch.int32, "cells")
+        self._check_tensor(parent, torch.int32, "parent")
+        n = int(cells.numel())
+        if tuple(points.shape) != (n, 3) or int(parent.numel()) != n:
+            raise ValueError("points, cells and parent must describe the same particles")
+        n_cells = int(dims[0]) * int(dims[1]) * int(dims[2])
+        labels = torch.empty(n, dtype=torch.int32, device=self.device)
+        sizes = torch.empty(n, dtype=torch.int32, device=self.device)
+        n_groups = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ordered = order = cell_begin = None
+        n_inside = pair_tests = 0
+        if n:
+            # the cell as an unsigned number: an outside particle's sorts behind every cell;
+            # stable, so that the slots of a cell ascend in particle index
+            keys, order = torch.sort(cells.to(torch.int64) & 0xFFFFFFFF, stable=True)
+            edges = torch.arange(n_cells + 1, dtype=torch.int64, device=self.device)
+            cell_begin = torch.searchsorted(keys, edges).contiguous()
+            ordered = points[order].contiguous()
+            counts = (cell_begin[1:] - cell_begin[:-1]).reshape(int(dims[2]), int(dims[1]),
+                                                                int(dims[0]))
+            pair_tests = group_pair_tests(counts, periodic)
+            n_inside = int(cell_begin[-1].item())
+        if max_pair_tests is not None and pair_tests > int(max_pair_tests):
+            raise ValueError(
+                f"the link kernel would test {pair_tests} pairs of particles, more than "
+                f"max_pair_tests = {int(max_pair_tests)}: the cells around the densest particles "
+                "hold too many; use a smaller linking length, or raise max_pair_tests")
+        _native(self, "avr_particle_groups", self._handle, _pointer(ordered), _pointer(order),
+                _pointer(cell_begin), n, n_inside, float(linking_length), _doubles(lo),
+                _doubles(hi), _ints(dims), _ints(periodic), int(min_members), _pointer(parent),
+                _pointer(labels), _pointer(sizes), _pointer(n_groups))
+        return labels, parent, sizes, n_groups, pair_tests
+
     # -- painter ----------------------------------------------------------------------------
     def paint_box(self, box: AmrBox, transform: ScalarTransform, params: _capi.PaintParams,
                   camera: CameraParameters, out: Optional[torch.Tensor] = None,
@@ -834,6 +903,51 @@ def _device_points(ctx: "Context", points, wrong_shape: str) -> torch.Tensor:
     if points.ndim != 2 or points.shape[1] != 3:
         raise ValueError(wrong_shape)
     return points
+
+
+def _group_box(lo, hi, dims, periodic):
+    """(lo float64 [3], hi float64 [3], dims int32 [3], periodic int32 [3]) of the particle
+    groups' calls; periodic is a flag or three."""
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    _require_triple(lo, "lo")
+    _require_triple(hi, "hi")
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    if dims.shape != (3,):
+        raise ValueError("dims must hold three values")
+    flags = np.ascontiguousarray(np.broadcast_to(np.asarray(periodic, dtype=bool), (3,)),
+                                 dtype=np.int32)
+    return lo, hi, dims, flags
+
+
+def group_pair_tests(counts: torch.Tensor, periodic) -> int:
+    """The pair tests group_link_kernel makes on a grid whose cells hold counts (int64 [nz, ny,
+    nx]) particles: m (m - 1) / 2 inside a cell plus m times the occupancy of each of its 13
+    forward neighbours, wrapped on a periodic axis and absent past another face -- as shifted
+    products of the dense grid.  Exact; ValueError where it would not fit 63 bits."""
+    counts = counts.to(torch.int64)
+    flags = [bool(v) for v in np.broadcast_to(np.asarray(periodic, dtype=bool), (3,))]
+    terms = [(counts, counts - 1, 2)]
+    for e in range(14, 27):
+        offset = (e % 3 - 1, (e // 3) % 3 - 1, e // 9 - 1)   # (dx, dy, dz)
+        a = b = counts
+        for axis, d in zip((2, 1, 0), offset):               # the grid is [nz, ny, nx]
+            if d == 0:
+                continue
+            if flags[2 - axis]:
+                b = torch.roll(b, -d, dims=axis)
+            else:
+                size = a.shape[axis]
+                a = a.narrow(axis, 0 if d > 0 else 1, size - 1)
+                b = b.narrow(axis, 1 if d > 0 else 0, size - 1)
+        terms.append((a, b, 1))
+    total = 0
+    for a, b, divisor in terms:
+        if float((a.double() * b.double()).sum().item()) >= 2.0 ** 62:
+            raise ValueError("the link kernel would test more than 2^62 pairs of particles; use "
+                             "a smaller linking length")
+        total += int((a * b).sum().item()) // divisor
+    return total
 
 
 def _native(ctx: "Context", entry: str, *arguments) -> None:

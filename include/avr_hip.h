@@ -1521,6 +1521,54 @@ int avr_scene_particle_deposit(avr_context *ctx, avr_scene *out, const int64_t *
                                const double *shares_sorted_dev, uint64_t n_contributions,
                                int quantity, const double *level_cell_size, int n_levels);
 
+/* ---- particle groups ("Particle groups") ---------------------------------------------- */
+
+/* Friends-of-friends groups of n particles, in two calls with a sort by the caller between them.
+ * The box lo, hi (host, f64 [3], finite, lo < hi), the flags periodic (host, i32 [3]) and the grid
+ * dims (host, i32 [3]: each in [1, 1024], product below 2^27, at least 3 on a periodic axis) are
+ * the same in both.  A particle is outside if a coordinate is not finite or, on a periodic axis,
+ * not in [lo, hi).  The grid is an accelerator only: h_d = (hi_d - lo_d) / dims_d, a particle's cell
+ * along d is floor((x - lo_d) / h_d) clamped in double to [0, dims_d - 1], and its cell is (cz ny +
+ * cy) nx + cx.
+ *
+ * This call: points_dev (device, f64 [n][3]) -> cells_dev (u32 [n], the cell, 0xFFFFFFFF outside),
+ * parent_dev (u32 [n], the particle's own index, 0xFFFFFFFF outside) and totals_dev (u64 [1]), to
+ * which the number of outside particles is added.  AVR_ERR_INVALID_ARGUMENT, before any device work
+ * and in this order, for a null array (the four device arrays may be NULL with n == 0), n >= 2^31,
+ * lo or hi not finite or lo >= hi, a dim outside [1, 1024], 2^27 cells or more, fewer than 3 cells
+ * on a periodic axis, and an output that shares a byte with another output or the points -- and
+ * every output is untouched.  n == 0 launches nothing.  Asynchronous on the context's stream. */
+int avr_particle_group_cells(avr_context *ctx, const double *points_dev, uint64_t n,
+                             const double *lo, const double *hi, const int32_t *dims,
+                             const int32_t *periodic, uint32_t *cells_dev, uint32_t *parent_dev,
+                             uint64_t *totals_dev);
+
+/* The groups.  The caller has sorted the particles by cells_dev, stably: order_dev (device, i64
+ * [n]) names the particle in each sorted slot, points_sorted_dev (f64 [n][3]) holds the points in
+ * that order, cell_begin_dev (i64 [cells + 1]) the first slot of every cell, and the first n_inside
+ * slots are the inside particles.  parent_dev is avr_particle_group_cells' output for the same
+ * points, box and dims.  Inside particles p, q are linked iff (dx dx + dy dy) + dz dz <= b b, with
+ * per axis a = |x_q - x_p| and, on a periodic axis, a = min(a, (hi - lo) - a); IEEE binary64,
+ * nothing fused.  A group is a connected component of the links and its root its smallest particle
+ * index; the groups of at least min_members members are numbered 1..N by ascending root.
+ * labels_dev (i32 [n]) gets each particle's group, 0 for none; parent_dev each inside particle's
+ * root; sizes_dev (u32 [n]) the member count at every root's index and 0 elsewhere; n_groups_dev
+ * (u64 [1]) N.  Equal arguments give equal bits, and the result does not depend on dims.
+ * COST: every pair of particles in the same or in adjacent cells is tested, which is quadratic in
+ * a cell's occupancy; the caller must bound that number itself (the Python api counts it exactly
+ * from the cell ranges and refuses above max_pair_tests).
+ * AVR_ERR_INVALID_ARGUMENT, before any device work and in this order, for a null array (all device
+ * arrays but n_groups_dev may be NULL with n == 0), n >= 2^31, n_inside > n, b not finite and
+ * positive, the box and dims rules above, h_d < b (1 + 2^-10) on an axis with dims_d > 1,
+ * min_members outside [1, 2^31), and an output that shares a byte with another output or an input
+ * -- and every output is untouched.  n == 0 launches nothing but sets n_groups to 0.  The scan's
+ * scratch is a grow-only block of the context.  Asynchronous on the context's stream. */
+int avr_particle_groups(avr_context *ctx, const double *points_sorted_dev, const int64_t *order_dev,
+                        const int64_t *cell_begin_dev, uint64_t n, uint64_t n_inside, double b,
+                        const double *lo, const double *hi, const int32_t *dims,
+                        const int32_t *periodic, int64_t min_members, uint32_t *parent_dev,
+                        int32_t *labels_dev, uint32_t *sizes_dev, uint64_t *n_groups_dev);
+
 /* ---- rays ("Rays") -------------------------------------------------------------------- */
 
 /* Line-outs: for each of n_rays segments A -> B (start_dev, end_dev: device, f64 [n][3], physical
