@@ -1,10 +1,17 @@
 """Holds tests/wide_view_cases.py to its claims, in plain Python integers and numpy: the spans and
 parities of the wide views, that no two cells share an element, the poison around every view, the
-byte offsets reached, and the ends and nesting of the translated hierarchies."""
+byte offsets reached, and the ends and nesting of the translated hierarchies.  For the inputs of
+the newer products the numpy references say, without a GPU, that they reach what the GPU tests are
+about: the cells the fixed particles land in, the leaf counts per level, the cloud corners on the
+index limits, the fill and partial cells of the partial grid, the clump threshold."""
 import numpy as np
 import pytest
 
+import clump_reference
+import grid_field_reference as gf
+import particle_reference as pr
 import wide_view_cases as cases
+from gradient_reference import same_bits
 
 CASES = cases.wide_cases()
 BY_NAME = {c.name: c for c in CASES}
@@ -154,6 +161,120 @@ def test_the_scene_around_a_wide_box_nests_and_keeps_its_last_cell_a_leaf(case, 
     assert cases.corners(fine)[0][0] == (nx - 1) * cases.CELL
 
 
+# ---- part A: the inputs of the newer products --------------------------------------------------
+
+def wide_hierarchy(case):
+    """particle_reference's hierarchy of a case's scene as the runtime sees it.  The scene is made
+    of boxes, not of a plotfile's leaves: the two level-0 cells under the fine box are cells of
+    their boxes like any other, so a level-0 cloud corner finds them present and a share lands in
+    them, while a point inside the fine box is still located there, finest level first."""
+    h = pr.hierarchy(cases.scene_levels(case), cases.RATIO, cases.level_sizes(), (0.0, 0.0, 0.0))
+    assert (~h.mask[0]).sum() == 2 and h.mask[1].sum() == 16
+    h.mask[0][...] = True
+    return h
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_the_channel_edges_put_wide_cells_under_inside_and_over(case):
+    nx, ny, nz = case.view.dims
+    velocity = cases.field_cells(case, 1)
+    edges = cases.CUBE_EDGES
+    assert edges.size == 6 and (np.diff(edges) > 0.0).all()
+    assert (velocity < edges[0]).any() and (velocity > edges[-1]).sum() == 0
+    assert edges[-2] <= velocity[-1, -1, -1] < edges[-1]            # the last cell: the last channel
+    assert all(cases.small_cells(dims, tag + 1).min() > edges[-1]
+               for dims, tag in (((cases.PLAIN_NX, ny, nz), 0), (cases.FINE_DIMS, 10)))
+    binned = cases.field_cells(case, 3)
+    edges = cases.TRANSFER_EDGES
+    assert edges.size == 4 and (np.diff(edges) > 0.0).all()
+    assert (binned < edges[0]).any() and edges[-2] <= binned[-1, -1, -1] < edges[-1]
+    # the opacity's scale is a power of two, and the longest row has an optical depth of order 1
+    assert np.frexp(cases.OPACITY_SCALE)[0] == 0.5
+    row = cases.field_cells(case, 2)[-1, -1, :] * cases.OPACITY_SCALE * cases.CELL
+    assert 0.04 < row.sum() < 8.0
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_the_fixed_particles_land_in_the_cells_claimed(case):
+    nx, ny, nz = case.view.dims
+    points, values = cases.wide_particles(case)
+    assert 256 < len(points) <= 365 and values.shape == (len(points),)
+    assert np.isfinite(points).all() and np.isfinite(values).all() and (values[:5] != 0.0).all()
+    h = wide_hierarchy(case)
+    level, q, index = h.locate(points)
+    assert level[:5].tolist() == [0, 0, 0, 1, 1]
+    assert index[0].tolist() == [0, 0, 0]
+    assert index[1].tolist() == [nx - 1, ny - 1, nz - 1]            # the wide box's last cell
+    assert (q[1] - index[1]).tolist() == [0.75] * 3
+    assert index[2].tolist() == [nx, ny - 1, nz - 1] and q[2][0] == nx      # on the face: plain
+    fine = cases.hierarchy(case)[2]
+    for row in (3, 4):
+        assert all(fine.index_lo[a] <= index[row][a] < fine.index_lo[a] + fine.dims[a]
+                   for a in range(3))
+    assert (level == -1).sum() > 50 and (level == 0).sum() > 100
+    for method in (0, 1):
+        found = pr.contributions(h, points, values, method)
+        assert found["outside"] == (level == -1).sum()
+        assert (found["rerouted"] > 0) == (method == 1)
+        named = {(int(l), tuple(int(v) for v in i))
+                 for l, i in zip(found["level"].reshape(-1), found["index"].reshape(-1, 3)) if l >= 0}
+        assert (0, cases.empty_cell(case)) not in named             # the clear pass alone writes it
+        assert (0, (nx - 1, ny - 1, nz - 1)) in named
+        dense = pr.deposit(h, found, 0)[0]
+        assert dense[nz - 1, ny - 1, nx - 1] != 0.0
+        e = cases.empty_cell(case)
+        assert dense[e[2], e[1], e[0]] == 0.0 and not np.signbit(dense[e[2], e[1], e[0]])
+    # cloud in cell: the last-cell particle's corners past the domain in y and z come back to it,
+    # the one in +x alone lands in the plain box
+    found = pr.contributions(h, points, values, 1)
+    corners = [(int(l), tuple(int(v) for v in i)) for l, i in zip(found["level"][1], found["index"][1])]
+    assert corners.count((0, (nx - 1, ny - 1, nz - 1))) == 7 and corners[1] == (0, (nx, ny - 1, nz - 1))
+    assert (0, (nx - 1, ny - 1, nz - 1)) in [
+        (int(l), tuple(int(v) for v in i)) for l, i in zip(found["level"][2], found["index"][2])]
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_the_partial_grid_leaves_fill_and_partial_cells_in_the_wide_box(case):
+    nx, ny, nz = case.view.dims
+    grids = {g.name: g for g in cases.wide_grids(case)}
+    assert sorted(grids) == ["margin", "partial", "refined"]
+    for g in grids.values():
+        finite = g.grid[np.isfinite(g.grid)]
+        assert np.isnan(g.grid).sum() == 1 and np.unique(finite).size == finite.size == g.grid.size - 1
+    assert grids["margin"].level == 0 and grids["margin"].lo == (-1, 0, 0)
+    assert grids["margin"].grid.shape == (nz, ny, nx + cases.PLAIN_NX + 1)
+    assert grids["margin"].modes == [(0, False), (1, False), (1, True)]
+    assert grids["refined"].grid.shape == (2 * nz, 2 * ny, 2 * (nx + cases.PLAIN_NX))
+    k, j, i = np.indices((nz, ny, nx))
+    index = np.stack([i.reshape(-1), j.reshape(-1), k.reshape(-1)])
+    g = grids["partial"]
+    values, filled, partial = gf.grid_cells(g.grid, g.level, g.lo, 0, index, cases.RATIO)
+    filled, partial = filled.reshape(nz, ny, nx), partial.reshape(nz, ny, nx)
+    assert filled[:, :, 0].all() and not filled[:, :, 1:].any() and partial[:, :, 1:].all()
+    assert partial[-1, -1, -1] and np.isnan(values.reshape(nz, ny, nx)[filled]).all()
+    # the whole grids leave nothing out, and the fine box is finer than the margin grid
+    for name in ("margin", "refined"):
+        g = grids[name]
+        _, filled, partial = gf.grid_cells(g.grid, g.level, g.lo, 0, index, cases.RATIO)
+        assert not filled.any() and not partial.any()
+    assert cases.hierarchy(case)[2].level > grids["margin"].level
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_the_clump_threshold_makes_the_wide_boxs_last_cell_a_member(case):
+    first = cases.field_cells(case, 0, odd=True)
+    assert cases.CLUMP_LOWER <= first[-1, -1, -1] <= cases.CLUMP_UPPER
+    assert (first < cases.CLUMP_LOWER).any()                        # and not every cell is one
+    levels = cases.scene_levels(case)
+    assert same_bits(levels[0]["data"][0][0], first)
+    boxes = [(b.level, b.index_lo, tuple(lo + n - 1 for lo, n in zip(b.index_lo, b.dims)))
+             for b in cases.hierarchy(case)]
+    labels, n = clump_reference.clump_levels(levels, cases.RATIO, 0, cases.CLUMP_LOWER,
+                                             cases.CLUMP_UPPER, boxes)
+    nx, ny, nz = case.view.dims
+    assert n >= 1 and labels[0][nz - 1, ny - 1, nx - 1] >= 1.0
+
+
 # ---- part B ---------------------------------------------------------------------------------------
 
 HIERARCHIES = cases.far_hierarchies()
@@ -197,3 +318,73 @@ def test_translated_hierarchies_end_on_the_index_limits_and_keep_their_nesting(h
                 before = [p for p, (plo, phi) in enumerate(plain[l - 1]["boxes"])
                           if all(plo[a] <= olo[a] // r and ohi[a] // r <= phi[a] for a in range(3))]
                 assert parents == before and len(parents) == 1
+
+
+PLACES = [(h, where) for h in HIERARCHIES for where in (None, "top", "bottom")]
+
+
+def far_conditions(h, where, hier, found, points):
+    """What the far particles must reach, from the reference's own output: shared with the GPU
+    test, which asserts it again on the run it compares with."""
+    leaves = np.bincount(found["leaf_level"][found["leaf_level"] >= 0], minlength=3)
+    assert (leaves >= 32).all(), leaves
+    assert found["outside"] > 0 and found["rerouted"] > 0
+    corners = cases.rerouted_corners(hier, points)
+    assert len(corners) == found["rerouted"]
+    if where == "top":      # a corner cell whose first finest-level index is 2^30
+        assert any(cases.finest_range(h, level, index[a])[0] == 2 ** 30
+                   for level, index in corners for a in range(3))
+    if where == "bottom":   # a corner cell whose last finest-level index is -2^30 - 1
+        assert any(cases.finest_range(h, level, index[a])[1] == -2 ** 30 - 1
+                   for level, index in corners for a in range(3))
+    return leaves
+
+
+@pytest.mark.parametrize("h,where", PLACES, ids=[f"{h.name}-{w}" for h, w in PLACES])
+def test_the_far_particles_reach_every_level_and_the_corners_on_the_index_limits(h, where):
+    translation = cases.translations(h)[where] if where else None
+    sizes, prob_lo = cases.far_geometry(h, translation)
+    hier = pr.hierarchy(cases.far_levels(h, translation), h.ratio, sizes, prob_lo)
+    p = cases.far_particles(h)
+    assert 256 < len(p.points) < 600 and p.values.shape == (len(p.points),)
+    found = pr.contributions(hier, p.points, p.values, 1)
+    far_conditions(h, where, hier, found, p.points)
+    # the lattice batch: q is exact, so it is the untranslated q moved by the translation
+    at = (p.points[p.lattice] - np.array(prob_lo)) / sizes[2][0]
+    near = (p.points[p.lattice] - np.array(cases.FAR_PROB_LO)) / sizes[2][0]
+    shift = np.array(translation[2] if where else (0, 0, 0), dtype=np.float64)
+    assert np.array_equal(at, near + shift) and np.array_equal(at * 16.0, np.rint(at * 16.0))
+    # the corners themselves: prob_lo is inside (cell 0 of level 0), prob_hi is not
+    corner = len(p.points) - 12
+    assert found["leaf_level"][corner] == 0 and found["leaf_level"][corner + 1] == -1
+    base = pr.contributions(pr.hierarchy(cases.far_levels(h), h.ratio, *cases.far_geometry(h)),
+                            p.points, p.values, 1)
+    assert (found["outside"], found["rerouted"]) == (base["outside"], base["rerouted"])
+    assert same_bits(found["shares"][p.lattice], base["shares"][p.lattice])
+
+
+@pytest.mark.parametrize("h", HIERARCHIES, ids=[h.name for h in HIERARCHIES])
+def test_the_far_transfer_fields_and_edges(h):
+    levels = cases.far_levels(h)
+    assert sorted(cases.FAR_FIELDS) == ["bin", "opacity", "source", "width"]
+    for name in cases.FAR_FIELDS:
+        mapped = cases.far_field_levels(levels, name)
+        for lev, was in zip(mapped, levels):
+            assert lev["boxes"] == was["boxes"] and lev["domain"] == was["domain"]
+            for data, stored in zip(lev["data"], was["data"]):
+                assert data.shape == (1,) + stored.shape[1:] and data.dtype == np.float64
+                if name == "source":
+                    assert same_bits(data[0], stored[0])
+                if name == "opacity":
+                    assert same_bits(data[0], np.abs(stored[2]) / 1024.0) and (data >= 0.0).all()
+                if name == "bin":
+                    assert same_bits(data[0], stored[2] / 2.0)
+                if name == "width":
+                    assert (data > 0.0).all() and (data <= 30.0 * 31.25).all()
+    for edges in (cases.FAR_SHARP_EDGES, cases.FAR_BROAD_EDGES):
+        assert edges.size == 4 and (np.diff(edges) > 0.0).all()
+    binned = np.concatenate([d[0].reshape(-1) for lev in cases.far_field_levels(levels, "bin")
+                             for d in lev["data"]])
+    binned = binned[np.abs(binned) < 1e20]                  # without the cells under a finer grid
+    assert (binned < cases.FAR_SHARP_EDGES[0]).any() and (binned > cases.FAR_SHARP_EDGES[-1]).any()
+    assert np.all(np.diff(cases.FAR_BROAD_EDGES) == 31.25)

@@ -8,7 +8,16 @@ made twice, on the views and on contiguous copies of the same cells with the sam
 and indices, and the results must be equal bit for bit, NaN equal to NaN.  The storage around the
 views holds one poison bit pattern; after a product that writes cells the output view's cells are
 copied out, poison is written back over them, and one device reduction checks that the whole
-output storage is poison again and the input storage unchanged."""
+output storage is poison again and the input storage unchanged.
+
+Covered: the painter and the frames, the statistics and histograms, slices, axis projections,
+derive, gradient, clumps with their table and links, covering grids, isosurfaces, streamlines, rays
+and ray sums; and, of the products merged since, velocity cubes, ray transfer, grid fields,
+particle cells and deposits, and clump members with their data.  For those the numpy references
+also say what the wide box's last cells must hold, mixed runs (some fields views, some copies)
+hold the AND over the fields' pairing flags, and one sensitivity test per product shows that the
+wide box's last cell reaches the result.  Left out: structure functions, the FFT products and
+particle groups take contiguous tensors and no boxes, so the span rule does not apply to them."""
 import numpy as np
 import pytest
 import torch
@@ -18,8 +27,11 @@ from amrvolumerenderer_amd.renderer import FrameRenderer, RenderParameters
 from amrvolumerenderer_amd.types import (AmrBox, CameraParameters, ScalarTransform, VolumeBounds,
                                          make_params)
 
+import grid_field_reference
+import particle_reference
 import wide_view_cases as cases
 from gradient_reference import same_bits
+from test_wide_view_cases import wide_hierarchy
 
 pytestmark = pytest.mark.gpu
 CASES = cases.wide_cases()
@@ -130,6 +142,18 @@ class Installed:
 
     def scene(self, field, wide, wide_first=True):
         return self.ctx.create_scene(self.boxes(field, wide, wide_first), ScalarTransform())
+
+    def changed_scene(self, field, at, value):
+        """The contiguous layout with cell `at` of the wide box replaced by value."""
+        boxes = self.boxes(field, False)
+        cells = boxes[0].values.clone()
+        assert float(cells[at].item()) != value
+        cells[at] = value
+        boxes[0] = AmrBox(boxes[0].min_corner, boxes[0].max_corner, cells, boxes[0].level)
+        return self.ctx.create_scene(boxes, ScalarTransform())
+
+    def scaled(self, field, factor):
+        return _Scaled(self, field, factor)
 
     def index_lo(self, wide_first=True):
         return np.array([b.index_lo for b in cases.hierarchy(self.case, wide_first)], dtype=np.int32)
@@ -482,3 +506,304 @@ def test_ray_sums_with_and_without_a_weight(ctx, wide):
 
     plain, weighted = wide.read(run)
     assert plain[4] is None and float(weighted[4].max().item()) > 0.0
+
+
+# ---- the products merged after this module was written -----------------------------------------
+
+class _Scaled:
+    """While it is open, one field of a case is multiplied by a power of two in every layout -- the
+    view in the input storage, its contiguous copy and the ordinary boxes -- which is exact and
+    exactly undone; afterwards the view holds the bits of the host's cells again."""
+
+    def __init__(self, installed, field, factor):
+        assert np.frexp(factor)[0] == 0.5
+        self.installed, self.field, self.factor = installed, field, factor
+        self.tensors = [installed.views[field], installed.dense[field],
+                        installed.small["plain"][field], installed.small["fine"][field]]
+
+    def __enter__(self):
+        for t in self.tensors:
+            t.mul_(self.factor)
+        return self
+
+    def __exit__(self, *error):
+        for t in self.tensors:
+            t.div_(self.factor)
+        self.installed.ctx.synchronize()
+        self.installed.check_storages()
+        assert same_bits(self.tensors[0].cpu().numpy(), self.installed.host[self.field])
+        return False
+
+
+def _flat(result):
+    """A result as a list of comparable pieces: tensors by their bits, on the host."""
+    if isinstance(result, (tuple, list)):
+        return [piece for member in result for piece in _flat(member)]
+    if isinstance(result, torch.Tensor):
+        t = result.contiguous().cpu()
+        return [(t.view(torch.int64) if t.dtype == torch.float64 else t).numpy().tobytes()]
+    return [result]
+
+
+def _last_cell_pixel(case, axis, width=32, height=16):
+    """(row, column) of the pixel whose line along axis crosses the wide box's last cell."""
+    size = cases.extent(case)
+    centre = [(n - 0.5) * cases.CELL for n in case.view.dims]
+    u, v = (axis + 1) % 3, (axis + 2) % 3
+    return int(centre[v] / size[v] * height), int(centre[u] / size[u] * width)
+
+
+def _cube(wide, axis, emission, velocity, width_scene):
+    """The window and level_dl of test_axis_projection_with_and_without_a_weight."""
+    size = cases.extent(wide.case)
+    eu, ev = size[(axis + 1) % 3], size[(axis + 2) % 3]
+    return emission.velocity_cube(velocity, cases.CUBE_EDGES, axis, (0.0, 0.0), eu / 32, ev / 16,
+                                  32, 16, [cases.CELL, cases.CELL / 2], width_scene)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_velocity_cube_sharp_and_broadened(ctx, wide, axis):
+    """The slab staging and the column reads of avr_velocity_cube.hip through the views: emission
+    field 0 with its NaN and infinities, velocity field 1, width field 2."""
+    def run(layout, wide_first):
+        emission, velocity, width = (wide.scene(f, layout, wide_first) for f in (0, 1, 2))
+        return _cube(wide, axis, emission, velocity, None), _cube(wide, axis, emission, velocity,
+                                                                  width)
+
+    sharp, broadened = wide.read(run)
+    row, column = _last_cell_pixel(wide.case, axis)
+    for cube, under, over, length in (sharp, broadened):
+        assert cube.shape == (5, 16, 32) and float(length[row, column].item()) > 0.0
+    # the last cell's velocity lies in the last channel, the other boxes' above every channel; a
+    # pixel stands for the line through its centre, which in the long boxes may miss the last cell
+    size = cases.extent(wide.case)
+    at = [(column + 0.5) * size[(axis + 1) % 3] / 32, (row + 0.5) * size[(axis + 2) % 3] / 16]
+    last = [wide.case.view.dims[(axis + 1) % 3] - 1, wide.case.view.dims[(axis + 2) % 3] - 1]
+    if [int(at[0] / cases.CELL), int(at[1] / cases.CELL)] == last:
+        assert float(sharp[0][-1, row, column].item()) > 0.0
+    assert axis != 0 or float(sharp[0][-1, row, column].item()) > 0.0     # along the last row
+    assert float(sharp[1].max().item()) > 0.0 and float(sharp[2].max().item()) > 0.0
+
+
+MODES = ("grey", "sharp", "broadened")
+
+
+def _transfer(wide, scenes, wide_first, mode):
+    """scenes: source (field 1), opacity (field 2, scaled), bin (field 3), width (field 4)."""
+    source, opacity, binned, width = scenes
+    start, end = _rays(wide.case)
+    arguments = (start, end, 4096, wide.index_lo(wide_first), cases.RATIO, SIZES, ORIGIN)
+    if mode == "grey":
+        return source.ray_transfer(opacity, *arguments)
+    return source.ray_transfer(opacity, *arguments, binned, width if mode == "broadened" else None,
+                               cases.TRANSFER_EDGES)
+
+
+def test_ray_transfer_grey_sharp_and_broadened(ctx, wide):
+    """The companion-field reads of avr_rays.hip through the views; ray 0 runs along the wide box's
+    last row."""
+    with wide.scaled(2, cases.OPACITY_SCALE):
+        def run(layout, wide_first):
+            scenes = [wide.scene(f, layout, wide_first) for f in (1, 2, 3, 4)]
+            return [_transfer(wide, scenes, wide_first, mode) for mode in MODES]
+
+        results = wide.read(run)
+    for mode, (counts, status, span, intensity, tau, outside, counted, covered) in zip(MODES, results):
+        assert int(status[0].item()) == 0 and float(counted[0].item()) > 0.0
+        assert (outside is None) == (mode == "grey")
+        assert intensity.shape == ((1 if mode == "grey" else 3), 32)
+        assert float(intensity[:, 0].max().item()) > 0.0
+    assert 0.1 < float(results[0][4][0, 0].item()) < 10.0        # an optical depth of order 1
+
+
+def _last_row(case):
+    """The level-0 indices [3, nx] of the wide box's last row."""
+    nx, ny, nz = case.view.dims
+    return np.stack([np.arange(nx), np.full(nx, ny - 1), np.full(nx, nz - 1)]).astype(np.int64)
+
+
+def _grid_fields(ctx, wide, out, wide_first, grids):
+    """Every grid in every mode onto the output scene: [(the boxes' cells, totals)]."""
+    results = []
+    for g, device_grid in grids:
+        for interpolation, periodic in g.modes:
+            totals = out.grid_field(device_grid, g.level, g.lo, wide.index_lo(wide_first),
+                                    cases.RATIO, interpolation, periodic)
+            ctx.synchronize()
+            results.append(([b.values.clone() for b in out.boxes], totals))
+    return results
+
+
+def test_grid_field(ctx, wide):
+    """grid_tile's stores through the wide output view: a grid of the same level (the finer case for
+    the fine box, constant and linear, clamped and periodic), a finer grid, and a finer grid that
+    leaves fill and partial cells in the wide box."""
+    grids = [(g, torch.from_numpy(g.grid).to(ctx.device)) for g in cases.wide_grids(wide.case)]
+    _, results = wide.written(
+        lambda layout, wide_first, out: _grid_fields(ctx, wide, out, wide_first, grids))
+    # the contiguous run in the order plain, wide, fine: the wide box's last row by the reference
+    nx, ny, nz = wide.case.view.dims
+    runs = [(g, mode) for g, _ in grids for mode in g.modes]
+    assert len(runs) == len(results) == 5
+    for (g, (interpolation, periodic)), (boxes, totals) in zip(runs, results):
+        want, filled, partial = grid_field_reference.grid_cells(
+            g.grid, g.level, g.lo, 0, _last_row(wide.case), cases.RATIO, interpolation, periodic)
+        assert same_bits(boxes[1][-1, -1, :].cpu().numpy(), want), g.name
+        if g.name == "partial":
+            assert filled[0] and partial[1:].all()
+            assert int(totals[0].item()) >= ny * nz and int(totals[1].item()) >= (nx - 1) * ny * nz
+        else:
+            assert totals.tolist() == [0, 0]
+
+
+def _deposit(ctx, wide, out, wide_first, points, values, method):
+    found = out.particle_cells(points, values, method, wide.index_lo(wide_first), cases.RATIO,
+                               SIZES, ORIGIN, levels=True)
+    out.particle_deposit(found[0], found[1], 0, SIZES)
+    ctx.synchronize()
+    sums = [b.values.clone() for b in out.boxes]
+    out.particle_deposit(found[0], found[1], 1, SIZES)
+    return found, sums
+
+
+@pytest.mark.parametrize("method", [0, 1])
+def test_particle_cells_and_particle_deposit(ctx, wide, method):
+    """clear_tile and particle_sum_kernel store through the wide output view; the cells, shares,
+    levels and totals do not depend on the layout either.  The sums are in list order."""
+    points, values = cases.wide_particles(wide.case)
+    densities, (found, sums) = wide.written(
+        lambda layout, wide_first, out: _deposit(ctx, wide, out, wide_first, points, values, method))
+    nx, ny, nz = wide.case.view.dims
+    h = wide_hierarchy(wide.case)       # the scene's boxes: the cells under the fine box too
+    want = particle_reference.contributions(h, points, values, method)
+    cells, shares, levels, totals = found
+    assert totals.tolist() == [want["outside"], want["rerouted"]]
+    assert same_bits(shares.cpu().numpy(), want["shares"])
+    assert np.array_equal(levels.cpu().numpy(), np.where(want["leaf_level"] < 0, 255,
+                                                         want["leaf_level"]))
+    # the contiguous run in the order plain, wide, fine
+    dense = particle_reference.deposit(h, want, 0)[0][:, :, :nx]
+    got = sums[1].cpu().numpy()
+    assert got.shape == dense.shape and got[-1, -1, -1] != 0.0
+    assert np.array_equal(got.view(np.uint64), dense.view(np.uint64))   # +0.0 where nothing lands
+    i, j, k = cases.empty_cell(wide.case)
+    assert got.view(np.uint64)[k, j, i] == 0                            # the clear pass alone
+    volume = (cases.CELL * cases.CELL) * cases.CELL
+    assert same_bits(densities[1].cpu().numpy(), dense / volume)
+
+
+def _members(ctx, wide, out, wide_first, field, sample):
+    """The clumps of `field` into the output scene, their members and the members' data."""
+    index = wide.index_lo(wide_first)
+    count = out.clumps(field, cases.CLUMP_LOWER, cases.CLUMP_UPPER, index, cases.RATIO)
+    ctx.synchronize()
+    n = int(count.item())
+    assert n >= 1
+    cells = out.clump_table(n, 2)[0]
+    ctx.synchronize()
+    keys, totals = out.clump_members(n, np.ones(n, dtype=np.uint8), int(cells.sum().item()))
+    data = out.clump_member_data(keys, index, cases.RATIO, SIZES, ORIGIN, field=sample)
+    ctx.synchronize()
+    return count, keys, totals, data
+
+
+def _last_cell_ordinal(case, wide_first):
+    nx, ny, nz = case.view.dims
+    return (0 if wide_first else cases.PLAIN_NX * ny * nz) + nx * ny * nz - 1
+
+
+def test_clump_members_and_clump_member_data(ctx, wide):
+    """The labels are written through the wide output view; clump_members reads them back through
+    it, and clump_member_data reads field 1 through its view."""
+    def run(layout, wide_first, out):
+        count, keys, totals, data = _members(ctx, wide, out, wide_first,
+                                             wide.scene(0, layout, wide_first),
+                                             wide.scene(1, layout, wide_first))
+        at = torch.nonzero((keys & 0xffffffff) == _last_cell_ordinal(wide.case, wide_first))
+        assert at.numel() == 1                                  # the last cell is a member
+        return count, keys, totals, data, int(at.item())
+
+    labels, (count, keys, totals, (levels, centres, values), at) = wide.written(run)
+    assert totals.tolist() == [0] and keys.numel() > 8
+    assert int(keys[at].item()) >> 32 == int(labels[1][-1, -1, -1].item()) - 1
+    assert int(levels[at].item()) == 0
+    assert float(values[at].item()) == wide.host[1][-1, -1, -1]
+    assert centres[:, at].tolist() == [(n - 0.5) * cases.CELL for n in wide.case.view.dims]
+    assert set(levels.tolist()) == {0, 1}
+
+
+def test_mixed_layouts_equal_the_all_dense_run(ctx, wide):
+    """Some fields are views, the others contiguous and hence paired copies: in the unpaired cases
+    a product may take the pair path only if every field pairs (field_box_views)."""
+    def cubes(layouts):
+        emission, velocity, width = (wide.scene(f, layout) for f, layout in zip((0, 1, 2), layouts))
+        out = [_cube(wide, axis, emission, velocity, width) for axis in (0, 2)]
+        ctx.synchronize()
+        return out
+
+    want = cubes((False, False, False))
+    for layouts in ((True, False, True), (False, True, False)):
+        assert_same(cubes(layouts), want, (wide.case.name, layouts))
+    with wide.scaled(2, cases.OPACITY_SCALE):
+        def transfers(layouts):
+            scenes = [wide.scene(f, layout) for f, layout in zip((1, 2, 3, 4), layouts)]
+            out = [_transfer(wide, scenes, True, mode) for mode in MODES]
+            ctx.synchronize()
+            return out
+
+        want = transfers((False, False, False, False))
+        for layouts in ((True, False, True, False), (False, True, False, True)):
+            assert_same(transfers(layouts), want, (wide.case.name, layouts))
+
+
+def test_the_wide_boxs_last_cells_reach_every_new_product(ctx, wide):
+    """So that no test above passes by never reaching the limit: on the contiguous copies alone, the
+    wide box's last cell (and, where cells are read in pairs, the one before it) is replaced by
+    another finite value, or the input that lands in it is, and the result must differ."""
+    case = wide.case
+    nx, ny, nz = case.view.dims
+    cells = [(-1, -1, -1)] + ([(-1, -1, -2)] if case.others_pair else [])
+    dense = [wide.scene(f, False) for f in range(5)]
+
+    def done(result):
+        ctx.synchronize()
+        return _flat(result)
+
+    # velocity_cube: the emission
+    was = done(_cube(wide, 0, dense[0], dense[1], dense[2]))
+    for at in cells:
+        assert done(_cube(wide, 0, wide.changed_scene(0, at, 1.25), dense[1], dense[2])) != was, at
+    # ray_transfer: the source, and the companion field the channels bin
+    with wide.scaled(2, cases.OPACITY_SCALE):
+        scenes = [wide.scene(f, False) for f in (1, 2, 3, 4)]
+        was = done(_transfer(wide, scenes, True, "sharp"))
+        for at in cells:
+            changed = [wide.changed_scene(1, at, 2.25)] + scenes[1:]
+            assert done(_transfer(wide, changed, True, "sharp")) != was, at
+            changed = scenes[:2] + [wide.changed_scene(3, at, 4.375), scenes[3]]
+            assert done(_transfer(wide, changed, True, "sharp")) != was, at
+    # grid_field: the grid cells that land in the last cells
+    margin = cases.wide_grids(case)[0]
+    out, tensors = wide.output_scene(False)
+    grids = [(margin._replace(modes=[(0, False)]), torch.from_numpy(margin.grid).to(ctx.device))]
+    was = done(_grid_fields(ctx, wide, out, True, grids))
+    for at in cells:
+        grid = margin.grid.copy()
+        grid[nz - 1, ny - 1, nx + 1 + at[2]] = 0.75         # the grid begins one cell below x = 0
+        grids = [(margin._replace(modes=[(0, False)]), torch.from_numpy(grid).to(ctx.device))]
+        now = _grid_fields(ctx, wide, out, True, grids)
+        assert done(now) != was and float(now[0][0][0][at].item()) == 0.75, at
+    # particles: the value of the particle in the last cell
+    points, values = cases.wide_particles(case)
+    was = done(_deposit(ctx, wide, out, True, points, values, 1)[1])
+    values[1] = 7.0
+    now = _deposit(ctx, wide, out, True, points, values, 1)[1]
+    assert done(now) != was and float(now[0][-1, -1, -1].item()) != 0.0
+    # clump members: the field whose value the data carry, and the field that selects the cells
+    was = _members(ctx, wide, out, True, dense[0], dense[1])
+    for at in cells:
+        now = _members(ctx, wide, out, True, dense[0], wide.changed_scene(1, at, 2.25))
+        assert _flat(now[1]) == _flat(was[1]) and _flat(now[3]) != _flat(was[3]), at
+    now = _members(ctx, wide, out, True, wide.changed_scene(0, (-1, -1, -1), 1.125), dense[1])
+    assert now[1].numel() == was[1].numel() - 1
+    assert not bool(((now[1] & 0xffffffff) == _last_cell_ordinal(case, True)).any())
